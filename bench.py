@@ -7,8 +7,18 @@ ParallelTemperingSampler on testsystems.AlanineDipeptideExplicit: 24 replicas pe
 temperatures logspace(300 K, 600 K), g-BAOAB "V R R O R R V", 2 fs, 500 MD steps per iteration,
 velocities reassigned each iteration, Philox seed 0xC0FFEE.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, runs W untimed and K timed iterations and prints the JSON line: metric, value, unit, higher_is_better,
+dtype, ms_per_step (milliseconds per timed iteration), the configuration and the sampler's timing of the last iteration.
+Everything else the benchmark measures runs only under --full: the roofline figures (HIP events around the heaviest kernel
+classes in the timed region, an extra iteration for the integrator chain), the measured roofs of the box, the CPU baseline and
+the extra ensemble shapes.
+
+--dump-outputs DIR: after the timed iterations, what the last one handed to the caller is written as DIR/<name>.npy in float64
+(labels, u_kl, acceptance counts, positions, velocities and boxes of rank 0's replicas); the inputs are seeded, so two builds can
+be compared output for output.
 
 Default (weak scaling): every rank owns 24 replicas of one 24*N-replica ensemble; the only data-path
 collective is the RCCL all-gather of u_kl rows.  `value` counts 24-replica-iteration units:
@@ -19,14 +29,14 @@ collective is the RCCL all-gather of u_kl rows.  `value` counts 24-replica-itera
                            T = 128: the north_star efficiency target, "1->8 GPUs at 128 replicas").
                           `value` keeps the same unit (T / 24 * iterations / s), `scaling` = "strong".
 
-shapes: besides the main line's `value`, the same JSON line carries `"shapes"`: the other ensemble shapes the scaling question is
-asked on, each measured in this very run on the same N ranks (a few iterations each; `--no-shapes` skips them):
+shapes (--full): besides the main line's `value`, the same JSON line carries `"shapes"`: the other ensemble shapes the scaling
+question is asked on, each measured in this very run on the same N ranks (a few iterations each; `--no-shapes` skips them):
     strong24_alanine       one 24-replica ensemble over the N GPUs  (BASELINE.json's metric as written; = the main line at N = 1)
     strong128_alanine      one 128-replica alanine ensemble over the N GPUs (north_star's "1 -> 8 GPUs at 128 replicas")
     config5_dhfr128_sams   DHFR x 128 temperature states, SAMS global jump, over the N GPUs (BASELINE config 5: mixing is R x K)
 each with its own value, ms per iteration, the slowest rank's mix / propagate / u_kl / all-gather ms and the world size it saw.
 
-cpu_baseline: the same iteration through the same C ABI on oracle/_build/libremd_cpu.so (f64, OpenMP over
+cpu_baseline (--full, N = 1): the same iteration through the same C ABI on oracle/_build/libremd_cpu.so (f64, OpenMP over
 replicas, all host cores), timed on a bounded sample (fewer MD steps per iteration, scaled to 500).
 """
 import argparse
@@ -47,6 +57,7 @@ sys.path.insert(0, ROOT)
 REPLICAS_PER_GPU = 24
 MD_STEPS = 500
 SEED = 0xC0FFEE
+DUMP_COORDINATE_BYTES = 32 << 20   # --dump-outputs: positions + velocities; the whole dump stays under 64 MB up to ~1000 replicas
 # algorithmic work of the direct-space nonbonded kernel: ~210 pairs/atom inside the
 # 1 nm cutoff x ~48 flop/pair (LJ + switch + erfc Coulomb)  =>  10 kflop / atom / force evaluation
 FLOP_PER_ATOM_NONBONDED = 1.0e4
@@ -115,6 +126,26 @@ def build_sampler(n_replicas, engine, comm, md_steps):
     sampler.create(thermo, [sstate], storage=None, min_temperature=300.0 * unit.kelvin,
                    max_temperature=600.0 * unit.kelvin, n_temperatures=n_replicas)
     return sampler, ts
+
+
+def dump_outputs(directory, sampler):
+    """--dump-outputs: what the last iteration handed to its caller, as float64 .npy files (2.6 MB at 24 replicas).  Rank 0 writes
+    the replicated arrays and the coordinates of its own replicas; past 32 MB of coordinates, of a fixed seeded sample of them
+    (replica_index: which replicas)."""
+    os.makedirs(directory, exist_ok=True)
+    block = sampler.sampler_states[sampler._r_begin:sampler._r_begin + sampler._r_count]      # (the property copies them off the device)
+    per_replica = 2 * 8 * block[0].positions.size
+    index = np.arange(len(block))
+    if len(block) * per_replica > DUMP_COORDINATE_BYTES:
+        index = np.sort(np.random.default_rng(SEED).choice(len(block), DUMP_COORDINATE_BYTES // per_replica, replace=False))
+    block = [block[i] for i in index]
+    arrays = dict(replica_index=sampler._r_begin + index, replica_thermodynamic_states=sampler.replica_thermodynamic_states,
+                  energy_thermodynamic_states=sampler.energy_thermodynamic_states,
+                  n_accepted_matrix=sampler._n_accepted_matrix, n_proposed_matrix=sampler._n_proposed_matrix,
+                  positions=np.stack([s.positions for s in block]), velocities=np.stack([s.velocities for s in block]),
+                  box_vectors=np.stack([s.box_vectors for s in block]))
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), np.asarray(a, dtype=np.float64))
 
 
 def cpu_baseline(n_replicas=REPLICAS_PER_GPU, budget_s=12.0, all_cores=True):
@@ -312,12 +343,17 @@ def main():
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--md-steps', type=int, default=MD_STEPS, help='MD steps per iteration (500 = BASELINE)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-shapes', action='store_true', help='skip the extra ensemble shapes (strong-24 / strong-128 / config 5)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: rooflines, measured roofs, CPU baseline, extra ensemble shapes')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed iteration computed as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='under --full: skip the CPU baseline')
+    ap.add_argument('--no-shapes', action='store_true', help='under --full: skip the extra ensemble shapes (strong-24 / strong-128 / config 5)')
     ap.add_argument('--replicas-total', type=int, default=0,
                     help='strong scaling: one ensemble of this many replicas sharded over the ranks (24 = the BASELINE '
                          'metric as written, 128 = the north_star efficiency target); 0 = weak scaling, 24 per GPU')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     import torch
     rank = int(os.environ.get('RANK', '0'))
@@ -369,25 +405,59 @@ def main():
             torch.cuda.synchronize()
 
     sampler.run(args.warmup)
-    engine.profile_reset()
-    engine.profile_enable(True, 'nonbonded|pme_xy')   # asynchronous HIP events around the two heaviest kernel classes only
+    if args.full:
+        engine.profile_reset()
+        engine.profile_enable(True, 'nonbonded|pme_xy')   # asynchronous HIP events around the two heaviest kernel classes only
     sync()
     t0 = time.perf_counter()
     sampler.run(args.steps)
     sync()
     elapsed = time.perf_counter() - t0
-    engine.profile_enable(False)
+    if args.full:
+        engine.profile_enable(False)
     timing_of_timed_region = dict(sampler._timing_data)       # (the untimed integrator-profiling iteration below would overwrite it)
     if world > 1:
         import torch.distributed as dist
         t = torch.tensor([elapsed], dtype=torch.float64, device='cuda' if dist.get_backend() == 'nccl' else 'cpu')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sampler)
 
     out = None
     if rank == 0:
         it_per_s = args.steps / elapsed
         value = it_per_s * (n_replicas / REPLICAS_PER_GPU)
+        out = dict(metric='REMD iterations/s (propagate+u_kl+mix), 24-replica AlanineDipeptideExplicit' +
+                          (' per GPU' if not strong else ' units, one %d-replica ensemble over all GPUs' % n_replicas),
+                   value=value, unit='iterations/s', n_gpus=world, steps=args.steps, warmup=args.warmup,
+                   ms_per_step=1e3 * elapsed / args.steps, higher_is_better=True, scaling='strong' if strong else 'weak',
+                   vs_baseline=None,
+                   dtype='f32', data='synthetic',
+                   config=dict(workload='testsystems.AlanineDipeptideExplicit (2269 atoms, PME) parallel tempering, '
+                                        'logspace(300K,600K), g-BAOAB V R R O R R V 2 fs, %d MD steps/iteration, swap-all'
+                                        % args.md_steps,
+                               replicas_per_gpu=(n_replicas / float(world)), replicas_total=n_replicas, md_steps=args.md_steps,
+                               mode=('strong: one %d-replica ensemble' % n_replicas) if strong else 'weak: 24 replicas per GPU',
+                               parallelism='replica-sharded x%d' % world, seed=SEED, ewald=ewald,
+                               phases_per_gpu=(engine.phases_active() if hasattr(engine, 'phases_active') else 1)),
+                   timing=timing_of_timed_region, full=args.full)
+
+    if not args.full:
+        finish_line(out, rank, None, 0.0)
+    else:
+        full_measurements(args, out, engine, sampler, n_replicas, n_local, n_atoms, ewald, world, rank, local_rank, comm, sync, stream)
+    if world > 1:
+        import torch.distributed as dist
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_measurements(args, out, engine, sampler, n_replicas, n_local, n_atoms, ewald, world, rank, local_rank, comm, sync, stream):
+    """--full: the roofline figures of the timed region, the integrator chain's roofline from one more iteration, the measured roofs
+    of the box, the CPU baseline and the extra ensemble shapes; then the line."""
+    import torch
+    if rank == 0:
         # one force evaluation = the Coulomb launch (class 'nonbonded') + the LJ sub-system launch ('nonbonded_lj')
         n_launch, ms = engine.profile_get('nonbonded')
         n_lj, ms_lj = engine.profile_get('nonbonded_lj')
@@ -457,20 +527,7 @@ def main():
         cands.sort(key=lambda r: -r['total_ms'])
         roof = cands[0] if cands else None
         roof2 = cands[1] if len(cands) > 1 else None
-        out = dict(metric='REMD iterations/s (propagate+u_kl+mix), 24-replica AlanineDipeptideExplicit' +
-                          (' per GPU' if not strong else ' units, one %d-replica ensemble over all GPUs' % n_replicas),
-                   value=value, unit='iterations/s', n_gpus=world, steps=args.steps, warmup=args.warmup,
-                   ms_per_step=1e3 * elapsed / args.steps, higher_is_better=True, scaling='strong' if strong else 'weak',
-                   vs_baseline=None,
-                   dtype='f32', data='synthetic',
-                   config=dict(workload='testsystems.AlanineDipeptideExplicit (2269 atoms, PME) parallel tempering, '
-                                        'logspace(300K,600K), g-BAOAB V R R O R R V 2 fs, %d MD steps/iteration, swap-all'
-                                        % args.md_steps,
-                               replicas_per_gpu=(n_replicas / float(world)), replicas_total=n_replicas, md_steps=args.md_steps,
-                               mode=('strong: one %d-replica ensemble' % n_replicas) if strong else 'weak: 24 replicas per GPU',
-                               parallelism='replica-sharded x%d' % world, seed=SEED, ewald=ewald,
-                               phases_per_gpu=(engine.phases_active() if hasattr(engine, 'phases_active') else 1)),
-                   timing=timing_of_timed_region, roofline=roof, roofline_secondary=roof2, roofline_integrator=roof_ch, shapes=None)
+        out.update(roofline=roof, roofline_secondary=roof2, roofline_integrator=roof_ch, shapes=None)
         try:
             # achievable roofs of THIS box (STREAM triad past the Infinity Cache, FMA chains), SURVEY 8(d)
             out['measured_roofs'] = engine.roof_microbench()
@@ -496,10 +553,6 @@ def main():
         def shapes_fn(shapes):
             run_shapes(args, world, rank, local_rank, comm, sync, stream, out=shapes)
     finish_line(out, rank, shapes_fn, float(os.environ.get('REMD_BENCH_SHAPES_LIMIT_S', '420')), align=sync if world > 1 else None)
-    if world > 1:
-        import torch.distributed as dist
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == '__main__':

@@ -1,5 +1,5 @@
 export TMPDIR=/tmp; O=gpurun_out/r06s3_39; mkdir -p $O
-python bench.py --no-cpu-baseline --steps 5 --warmup 1 2>/dev/null | python -c "
+python bench.py --full --no-cpu-baseline --steps 5 --warmup 1 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('headline %.3f it/s' % d['value'], 'traffic_is_this_kernel', d['roofline'].get('traffic_source_is_this_kernel'))
 for k,v in d['shapes'].items(): print(k, v.get('value'), v.get('ms_per_iteration'))" | tee $O/summary.txt
