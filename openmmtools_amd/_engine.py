@@ -61,6 +61,17 @@ class RemdGbsaDesc(C.Structure):
                 ('solute_dielectric', C.c_double), ('solvent_dielectric', C.c_double), ('surface_area', C.c_int32)]
 
 
+class RemdRestraintDesc(C.Structure):
+    """remd_restraint_desc of include/remd_hip_restraints.h (receptor-ligand restraints, forces.py)."""
+    _fields_ = [('kind', C.c_int32), ('K', C.c_double), ('r0', C.c_double),
+                ('n1', C.c_int32), ('atoms1', c_int32_p), ('weights1', c_double_p),
+                ('n2', C.c_int32), ('atoms2', c_int32_p), ('weights2', c_double_p),
+                ('periodic', C.c_int32), ('force_group', C.c_int32)]
+
+
+# the GPU-only extension of include/remd_hip_restraints.h: bound where the loaded library exports it (the CPU port of the ABI does not)
+RESTRAINT_EXPORTS = ['remd_set_restraints', 'remd_set_restraint_lambdas', 'remd_get_restraint_energies']
+
 EXPORTS = [
     'remd_create', 'remd_destroy', 'remd_last_error', 'remd_version', 'remd_set_system', 'remd_set_coulomb_cutoff', 'remd_set_reaction_field', 'remd_set_alchemical_options', 'remd_set_alchemical_regions',
     'remd_set_region_lambdas', 'remd_set_region_bonded_lambdas', 'remd_set_gbsa', 'remd_set_states',
@@ -159,6 +170,12 @@ def load_library(path=None):
     lib.remd_test_coulomb_table.argtypes = [C.c_double, C.c_double, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     for name in EXPORTS:
         if name not in ('remd_last_error',):
+            getattr(lib, name).restype = C.c_int
+    if hasattr(lib, 'remd_set_restraints'):
+        lib.remd_set_restraints.argtypes = [vp, C.POINTER(RemdRestraintDesc), C.c_int]
+        lib.remd_set_restraint_lambdas.argtypes = [vp, c_double_p]
+        lib.remd_get_restraint_energies.argtypes = [vp, c_double_p]
+        for name in RESTRAINT_EXPORTS:
             getattr(lib, name).restype = C.c_int
     if path == LIB_PATH:
         _lib = lib
@@ -310,6 +327,42 @@ class HipEngine:
             self._check(self.lib.remd_set_gbsa(self.h, C.byref(g)), 'remd_set_gbsa')
         if 'force_groups' in desc_dict:                  # Force.getForceGroup() of the force classes (V<g> substeps)
             self.set_force_groups(desc_dict['force_groups'])
+        self.n_restraints = 0
+        restraints = desc_dict.get('restraints')
+        if restraints:                                   # receptor-ligand restraints (forces.py; csrc/restraints.hip)
+            self.set_restraints([restraints[k] for k in sorted(restraints)])
+
+    def _restraint_entry(self, name):
+        if not hasattr(self.lib, name):
+            raise NotImplementedError('%s: this build of the engine library has no restraints (include/remd_hip_restraints.h is GPU-only)' % name)
+        return getattr(self.lib, name)
+
+    def set_restraints(self, restraints):
+        """The restraints of the system (dicts of system.system_to_desc's 'restraints'); after set_system, which forgets them."""
+        fn = self._restraint_entry('remd_set_restraints')
+        arr = (RemdRestraintDesc * max(1, len(restraints)))()
+        keep = []
+        for k, r in enumerate(restraints):
+            a1, a2 = (np.ascontiguousarray(r['atoms%d' % g], dtype=np.int32) for g in (1, 2))
+            w1, w2 = (np.ascontiguousarray(r['weights%d' % g], dtype=np.float64) for g in (1, 2))
+            keep += [a1, a2, w1, w2]
+            arr[k] = RemdRestraintDesc(int(r['kind']), float(r['K']), float(r['r0']), len(a1), _ip(a1), _dp(w1), len(a2), _ip(a2), _dp(w2),
+                                       int(r['periodic']), int(r['force_group']))
+        self._check(fn(self.h, arr, len(restraints)), 'remd_set_restraints')
+        self.n_restraints = len(restraints)
+
+    def set_restraint_lambdas(self, lam):
+        """[K][n_restraints]: every state's value of each restraint's controlling parameter (after set_states)."""
+        fn = self._restraint_entry('remd_set_restraint_lambdas')
+        lam = np.ascontiguousarray(lam, dtype=np.float64).reshape(self.K, self.n_restraints)
+        self._check(fn(self.h, _dp(lam)), 'remd_set_restraint_lambdas')
+
+    def restraint_energies(self):
+        """[R_local][n_restraints] unscaled restraint energies (kJ/mol) at the current positions."""
+        fn = self._restraint_entry('remd_get_restraint_energies')
+        out = np.zeros((self.R, self.n_restraints))
+        self._check(fn(self.h, _dp(out)), 'remd_get_restraint_energies')
+        return out
 
     def set_states(self, beta, lambda_sterics=None, lambda_electrostatics=None, energy_const=None):
         beta = np.ascontiguousarray(beta, dtype=np.float64)

@@ -137,6 +137,7 @@ int remd_destroy(remd_handle h)
     remd_nocutoff_release(h);
     remd_gbsa_release(h);
     remd_regions_release(h);
+    remd_restraints_release(h);
     remd_mix_release(h);
     dfree(h->d_invmass); dfree(h->d_mass); dfree(h->d_ext_atoms);
     dfree(h->d_aterm); h->n_aterm = 0;
@@ -210,6 +211,7 @@ int remd_set_system(remd_handle h, const remd_system_desc* d)
     hipSetDevice(h->device);
     hipStreamSynchronize(h->stream);
     remd_regions_release(h);                    // remd_set_alchemical_regions follows the system it belongs to
+    remd_restraints_release(h);                 // ... and so do remd_set_restraints (restraints.hip)
     h->N = d->n_atoms;
     h->Npad = (d->n_atoms + 63) / 64 * 64;
     std::vector<float> im(h->Npad, 0.f), m(h->Npad, 0.f);
@@ -239,7 +241,7 @@ int remd_set_states(remd_handle h, int K, const double* beta, const double* lam_
 {
     if (!h || K <= 0 || !beta) return remd_fail(h, -1, "remd_set_states: bad arguments");
     hipSetDevice(h->device);
-    h->K = K; h->config_version++;
+    h->K = K; h->config_version++; h->states_version++;
     h->beta.assign(beta, beta + K);
     h->lam_s.assign(K, 1.0); h->lam_e.assign(K, 1.0); h->econst.assign(K, 0.0);
     if (lam_s) h->lam_s.assign(lam_s, lam_s + K);
@@ -689,6 +691,7 @@ static int phase_children(remd_ctx* h, int P)
         c->seed = h->seed; c->n_restart_attempts = h->n_restart_attempts;
         if (h->gbsa && (rc = remd_gbsa_clone(h, c))) return rc;                    // implicit solvent (gbsa.hip)
         if (h->n_regions > 0 && (rc = remd_regions_clone(h, c))) return rc;       // general alchemical regions (alch_regions.hip)
+        if (h->n_restraints > 0 && (rc = remd_restraints_clone(h, c))) return rc;  // receptor-ligand restraints (restraints.hip)
         if (h->baro_frequency > 0) {
             if ((rc = remd_set_barostat(c, h->K, h->pressure_host.data(), h->baro_frequency))) return remd_fail(h, rc, std::string("phases: ") + c->err);
             c->econst_vref = h->econst_vref;
@@ -1275,7 +1278,7 @@ int remd_get_energy_components(remd_handle h, double* out)
     REMD_CHECK(h, hipStreamSynchronize(h->stream));
     for (int r = 0; r < h->R; ++r) {
         for (int k = 0; k < 8; ++k) out[9 * r + k] = ep[(size_t)r * h->n_epart + k];
-        double nb = 0; for (int k = 8; k < h->n_epart; ++k) nb += ep[(size_t)r * h->n_epart + k];
+        double nb = 0; for (int k = 8; k < h->n_epart - 1; ++k) nb += ep[(size_t)r * h->n_epart + k];     // (the last slot: the restraints)
         out[9 * r + 8] = nb;
     }
     return 0;

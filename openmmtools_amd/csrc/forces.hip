@@ -2053,9 +2053,9 @@ const float4* remd_nb_param(remd_ctx* h)
 int remd_nb_required_epart(remd_ctx* h)
 {
     const int ntile = (h->Npad + 63) / 64;
-    // up to 4 slices per main cluster + 4 per LJ-sub-system cluster; the LAST slot belongs to the custom forces of general alchemical
-    // regions (alch_regions.hip)
-    return EP_NB0 + ntile * 8 * 4 + 8 + ntile * 8 * 4 + 1;
+    // up to 4 slices per main cluster + 4 per LJ-sub-system cluster; the slot before the last belongs to the custom forces of general
+    // alchemical regions (alch_regions.hip), the LAST one to the restraints (restraints.hip; zero without them)
+    return EP_NB0 + ntile * 8 * 4 + 8 + ntile * 8 * 4 + 2;
 }
 
 #define TUNE_SEG 40                       // one re-sort of the spatial order per segment (resort_interval)
@@ -2149,6 +2149,7 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask)
     const bool do_ext = (class_mask >> REMD_FG_EXTERNAL) & 1u, do_bond = (class_mask >> REMD_FG_BOND) & 1u;
     const bool do_angle = (class_mask >> REMD_FG_ANGLE) & 1u, do_torsion = (class_mask >> REMD_FG_TORSION) & 1u;
     const bool do_nb = (class_mask >> REMD_FG_NONBONDED) & 1u, do_recip = (class_mask >> REMD_FG_RECIPROCAL) & 1u;
+    const bool do_rst = h->n_restraints > 0 && ((class_mask >> REMD_FG_RESTRAINT) & 1u);
     if (!h->force_zeroed)
         REMD_CHECK(h, hipMemsetAsync(h->d_force, 0, sizeof(long long) * 3 * (size_t)h->Npad * h->R, h->stream));
     h->force_zeroed = false;
@@ -2158,7 +2159,7 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask)
 #define LAUNCH_E(kern, ...) do { if (with_energy) hipLaunchKernelGGL(kern<true>, __VA_ARGS__); else hipLaunchKernelGGL(kern<false>, __VA_ARGS__); } while (0)
     // custom forces of general alchemical regions (alch_regions.hip): part of the direct-space nonbonded class, launched here -- in
     // front of the fork -- so that both branches of the evaluation are ordered behind them
-    if (h->n_regions > 0 && do_nb) { int rcr = remd_regions_forces(h, with_energy, h->n_epart - 1); if (rcr) return rcr; }
+    if (h->n_regions > 0 && do_nb) { int rcr = remd_regions_forces(h, with_energy, h->n_epart - 2); if (rcr) return rcr; }
     if (h->nocutoff && do_nb) { int rcn = remd_nocutoff_forces(h, with_energy, EP_NB0); if (rcn) return rcn; }
     if (h->gbsa && do_nb) { int rcg = remd_gbsa_forces(h, with_energy, EP_NB0 + 1); if (rcg) return rcg; }
     if (h->n_ext > 0 && do_ext) {
@@ -2263,6 +2264,7 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask)
         LAUNCH_E(torsion_kernel, dim3(R), dim3(256), 0, h->stream, h->n_torsions, h->d_torsion_atoms, h->d_torsion_params, h->Npad,
                  h->d_pos, h->d_force, h->d_epart, h->n_epart);
     }
+    if (!merged && do_rst) { int rcr = remd_restraints_forces(h, with_energy, h->n_epart - 1, h->stream); if (rcr) return rcr; }
     // listed terms of a force-only evaluation: ONE launch, behind the pair kernel (it then starts 20 us earlier, next to the
     // spreading pass: 118.9 -> 116.8 ms per 500 steps)
     // forked force-only evaluations: the listed terms go to the MAIN stream behind the mesh launches (they only need the positions
@@ -2273,7 +2275,11 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask)
     // on a system whose mesh chain is the longer branch the extra work on the main stream costs what it saves here)
     const bool pax = forked && h->pair_after_xy;
     const bool listed_main = listed_main_env && forked && !with_energy && !h->sync_events && h->nb_method != REMD_NB_NONE && g_nb[h].p.prio != 0 && !pax;
+    // the restraints (restraints.hip) go with the listed terms: the launch of a force-only evaluation on the stream the listed terms take
+    // (the main stream when those rode in the spreading launch), behind the torsions of an energy evaluation
+    int rc_rst = 0;
     auto launch_listed = [&](hipStream_t lst) {
+        if (do_rst && !rc_rst) rc_rst = remd_restraints_forces(h, with_energy, h->n_epart - 1, lst);
         if (listed_rode) return;                      // they rode in the spreading launch
         int total = 0;
         const listed_tables T = listed_terms(total);
@@ -2358,6 +2364,7 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask)
                                h->d_epart, h->n_epart);
     }
 #undef LAUNCH_E
+    if (rc_rst) return rc_rst;
     if (with_energy)
         hipLaunchKernelGGL(reduce_energy_kernel, dim3(R), dim3(64), 0, h->stream, h->n_epart, h->d_epart, h->d_potential);
     REMD_CHECK(h, hipGetLastError());
@@ -2423,7 +2430,7 @@ __global__ void assemble_ukl_quad_kernel(int R, int K, int n, const double* __re
     ukl_rows[t] = beta[l] * U;
 }
 
-int remd_assemble_ukl(remd_ctx* h, double* d_rows)
+static int assemble_ukl_rows(remd_ctx* h, double* d_rows)
 {
     const int n = h->R * h->K;
     const double* alch = nullptr;
@@ -2519,4 +2526,11 @@ int remd_assemble_ukl(remd_ctx* h, double* d_rows)
                        h->d_potential, h->d_beta, h->d_econst, alch, alch ? d_own_states : (const int*)nullptr, h->baro_frequency > 0 ? h->d_pressure : (const double*)nullptr, h->d_box, h->econst_vref, d_rows);
     REMD_CHECK(h, hipGetLastError());
     return 0;
+}
+
+int remd_assemble_ukl(remd_ctx* h, double* d_rows)
+{
+    int rc = assemble_ukl_rows(h, d_rows);
+    if (rc) return rc;
+    return h->n_restraints > 0 ? remd_restraints_ukl(h, d_rows) : 0;       // + beta_l (lambda_l - lambda_own) E_r of the restraints
 }

@@ -1240,7 +1240,7 @@ static int remd_run_steps_resident(remd_ctx* h, const std::vector<char>& tokens,
 {
     const bool enabled = !(getenv("REMD_RESIDENT") && atoi(getenv("REMD_RESIDENT")) == 0);      // read per call: the parity tests switch it
     if (!enabled || h->no_resident) return 0;
-    if (h->N > 1024 || h->n_settle > 0 || h->n_shake > 0 || h->n_bonds > 0 || h->n_angles > 0 || h->n_torsions > 0) return 0;
+    if (h->N > 1024 || h->n_settle > 0 || h->n_shake > 0 || h->n_bonds > 0 || h->n_angles > 0 || h->n_torsions > 0 || h->n_restraints > 0) return 0;
     if (h->baro_frequency > 0 || h->profiling == 2 || (int)tokens.size() > MAX_TOK || n_steps < 1) return 0;
     if (h->measure_heat || h->measure_shadow) return 0;
     for (char c : tokens) if (c != 'V' && c != 'R' && c != 'O') return 0;
@@ -1525,7 +1525,7 @@ static int remd_run_steps_resident_mol(remd_ctx* h, const std::vector<char>& tok
 {
     const bool enabled = !(getenv("REMD_RESIDENT") && atoi(getenv("REMD_RESIDENT")) == 0);      // read per call: the parity tests switch it
     if (!enabled || h->no_resident) return 0;
-    if (!h->nocutoff || h->gbsa || h->n_regions > 0 || h->nb_method != REMD_NB_NONE || h->n_ext > 0) return 0;
+    if (!h->nocutoff || h->gbsa || h->n_regions > 0 || h->nb_method != REMD_NB_NONE || h->n_ext > 0 || h->n_restraints > 0) return 0;
     const unit_tables& ut = g_units[h];
     if (h->N > RESIDENT_MOL_MAX_ATOMS || ut.n_units > RESIDENT_MOL_T || ut.n_units < 1) return 0;
     if (getenv("REMD_RESIDENT_MOL") && atoi(getenv("REMD_RESIDENT_MOL")) == 0) return 0;
@@ -1616,6 +1616,7 @@ struct step_runner {
             for (int g = 0; g < 4; ++g) {
                 base.hVg[g] = h->nVg[g] > 0 ? (float)(h->dt / h->nVg[g]) : 0.f;
                 for (int c = 0; c < 6; ++c) if (h->fgroup[c] == g) group_mask[g] |= 1u << c;
+                if (h->n_restraints > 0 && h->rst_group == g) group_mask[g] |= 1u << REMD_FG_RESTRAINT;     // (restraints.hip)
                 if (h->nVg[g] > 0 && (!h->d_force_g[g] || h->force_g_n != nf)) {
                     if (h->d_force_g[g]) { REMD_CHECK(h, hipStreamSynchronize(h->stream)); hipFree(h->d_force_g[g]); h->d_force_g[g] = nullptr; }
                     REMD_CHECK(h, hipMalloc(&h->d_force_g[g], sizeof(long long) * nf));
@@ -1629,6 +1630,9 @@ struct step_runner {
                 if (h->fgroup[c] > 3 || !(named & (1u << c)))
                     return remd_fail(h, -3, "multiple-time-step splitting: a force class sits in a force group that no V of the splitting names "
                                             "(its forces would never act); groups 0-3 are supported");
+            if (h->n_restraints > 0 && (h->rst_group > 3 || !(named & (1u << REMD_FG_RESTRAINT))))
+                return remd_fail(h, -3, "multiple-time-step splitting: the restraints sit in a force group that no V of the splitting names "
+                                        "(their forces would never act); groups 0-3 are supported");
         }
         int n_braces = 0;
         for (char c : tokens_) n_braces += (c == '}');

@@ -151,6 +151,8 @@ struct remd_ctx {
     double sc_alpha = 0.5, sc_a = 1, sc_b = 1, sc_c = 6;
     int n_regions = 0;                 // remd_set_alchemical_regions: general regions (alch_regions.hip holds the tables)
     int regions_exact = 0;             // ... under the exact PME treatment (the regions' scaled charges inside the Ewald sum)
+    long long states_version = 0;      // bumped by every remd_set_states (restraints.hip: the restraint lambdas belong to one set of states)
+    int n_restraints = 0, rst_group = 0;   // remd_set_restraints: receptor-ligand restraints and their force group (restraints.hip holds the tables)
 
     // ---- states ---------------------------------------------------------------------
     int K = 0;
@@ -351,6 +353,7 @@ void remd_nb_invalidate_sort(remd_ctx* h);            // the next force evaluati
 #define REMD_FG_TORSION 3
 #define REMD_FG_NONBONDED 4      /* direct space, exceptions, Ewald exclusion correction */
 #define REMD_FG_RECIPROCAL 5
+#define REMD_FG_RESTRAINT 6      /* receptor-ligand restraints (restraints.hip), force group remd_ctx::rst_group */
 // nocutoff.hip: NonbondedForce with NoCutoff (vacuum systems)
 void remd_nocutoff_release(remd_ctx* h);
 int remd_nocutoff_build(remd_ctx* h, const remd_system_desc* d);
@@ -372,6 +375,12 @@ int remd_regions_le_override(remd_ctx* h, const float* le, int* n, const float**
 int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask = ~0u);   // fills d_force (and d_potential when with_energy)
 int remd_build_nonbonded(remd_ctx* h, const remd_system_desc* d);
 int remd_build_constraints(remd_ctx* h, const remd_system_desc* d);
+
+// restraints.hip: receptor-ligand restraints (include/remd_hip_restraints.h); their energy partial is the LAST slot of d_epart
+void remd_restraints_release(remd_ctx* h);
+int remd_restraints_clone(remd_ctx* parent, remd_ctx* child);
+int remd_restraints_forces(remd_ctx* h, bool with_energy, int ep_slot, hipStream_t st);
+int remd_restraints_ukl(remd_ctx* h, double* d_rows /*[R][K], added to*/);
 
 // ---- pme.hip ----------------------------------------------------------------------------
 int remd_pme_setup(remd_ctx* h);

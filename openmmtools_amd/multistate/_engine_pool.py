@@ -60,6 +60,8 @@ class EnginePool:
     def set_system(self, descs):
         if len(descs) != self.G:
             raise ValueError('one system description per compatibility group')
+        if any(d.get('restraints') for d in descs):
+            raise NotImplementedError('restraints (forces.py) in more than one compatibility group')
         n = {int(d['n_atoms']) for d in descs}
         if len(n) != 1:
             raise ValueError('the Systems of all thermodynamic states must hold the same particles (%s)' % sorted(n))

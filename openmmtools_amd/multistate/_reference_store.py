@@ -227,10 +227,20 @@ class ReferenceStoreReader:
                 if outer is not d:
                     composable = outer.get('composable_states', [])
                     names = [str(c.get('_serialized__class_name')) for c in composable]
-                    if not names or any(n != 'AlchemicalState' for n in names):
-                        raise NotImplementedError('compound thermodynamic states (%s) in a reference store' % ', '.join(names))
+                    if not names:
+                        raise NotImplementedError('compound thermodynamic states without composable states in a reference store')
                     alchs = []
                     for c in composable:
+                        if c.get('_serialized__class_name') != 'AlchemicalState':
+                            # any other composable state is a GlobalParameterState (states.py:3100): the parameters it serialised, under
+                            # the class name it had (the class itself is not imported from a store)
+                            spec = {k: 1.0 for k in c['parameters']}
+                            g = states.StoredGlobalParameterState.__new__(states.StoredGlobalParameterState)
+                            g.__setstate__(dict(class_name=str(c['_serialized__class_name']), spec=spec,
+                                                state=dict(parameters=dict(c['parameters']), function_variables=dict(c.get('function_variables') or {}),
+                                                           parameters_name_suffix=c.get('parameters_name_suffix'))))
+                            alchs.append(g)
+                            continue
                         if c.get('function_variables'):
                             raise NotImplementedError('AlchemicalState with alchemical functions')
                         par = {n: v for n, v in c['parameters'].items() if v is not None}     # None: not defined on the System (alchemy.py:94-99)
@@ -526,6 +536,13 @@ class ReferenceStoreWriter:
                              'parameters': {'lambda_sterics': float(c.lambda_sterics), 'lambda_electrostatics': float(c.lambda_electrostatics),
                                             **{k: (float(getattr(c, k)) if k in c._defined else None) for k in ('lambda_bonds', 'lambda_angles', 'lambda_torsions')}},
                              'function_variables': {}, 'parameters_name_suffix': c.parameters_name_suffix} for c in s._alchs]
+                    # GlobalParameterStates (e.g. lambda_restraints of the restraint forces) as their __getstate__ writes them (:3879-3898)
+                    for g in s._globals:
+                        gs = g.__getstate__()
+                        alch.append({'_serialized__class_name': type(g).__name__, '_serialized__module_name': type(g).__module__,
+                                     'parameters': {k: (None if v is None else v if isinstance(v, str) else float(v)) for k, v in gs['parameters'].items()},
+                                     'function_variables': {k: float(v) for k, v in gs['function_variables'].items()},
+                                     'parameters_name_suffix': gs['parameters_name_suffix']})
                     d = {'_serialized__class_name': 'CompoundThermodynamicState', '_serialized__module_name': 'openmmtools.states',
                          'thermodynamic_state': d, 'composable_states': alch}
                 self._write_text(self._a, '/%s/state%d' % (kind, k), _yaml_dump(d), fixed=True)

@@ -24,6 +24,23 @@ from .comm import SingleProcessComm
 logger = logging.getLogger(__name__)
 
 
+def restraint_lambdas(system, parameters, states):
+    """[K][n]: the value of each restraint's controlling global parameter at every state (the state's GlobalParameterState, else the
+    default value the restraint force carries)."""
+    from ..forces import iterate_forces, RadiallySymmetricRestraintForce
+    defaults = {}
+    for f in iterate_forces(system):
+        if isinstance(f, RadiallySymmetricRestraintForce) or hasattr(f, 'getNumGlobalParameters'):
+            for i in range(f.getNumGlobalParameters()):
+                defaults.setdefault(f.getGlobalParameterName(i), f.getGlobalParameterDefaultValue(i))
+    out = np.empty((len(states), len(parameters)))
+    for k, s in enumerate(states):
+        for i, p in enumerate(parameters):
+            v = s.global_parameter(p)
+            out[k, i] = defaults[p] if v is None else float(v)
+    return out
+
+
 class MultiStateSampler:
     def __init__(self, mcmc_moves=None, number_of_iterations=1, locality=None,
                  online_analysis_interval=200, online_analysis_target_error=0.0,
@@ -664,6 +681,11 @@ class MultiStateSampler:
         elif any(getattr(s, k, 1.0) != 1.0 for s in all_states for k in ('lambda_bonds', 'lambda_angles', 'lambda_torsions')):
             raise NotImplementedError('lambda_bonds / lambda_angles / lambda_torsions act on the bonded terms an AlchemicalRegion names '
                                       '(alchemical_bonds=..., alchemical_angles=..., alchemical_torsions=...): this System has none')
+        restraints = desc.get('restraints') if isinstance(desc, dict) else None
+        if restraints:
+            # receptor-ligand restraints (forces.py): every state's value of each restraint's controlling parameter -- the state's
+            # global parameter (a GlobalParameterState, e.g. lambda_restraints), else the default the force itself carries
+            eng.set_restraint_lambdas(restraint_lambdas(ref.system, [restraints[k]['parameter'] for k in sorted(restraints)], all_states))
         self._program_engine_move()
         pressures = [s.pressure for s in all_states]
         if any(p is not None for p in pressures):

@@ -9,6 +9,7 @@ Mirrors the parts of openmmtools/states.py the hot path touches:
 Quantities are md-unit floats / numpy arrays (see unit.py).
 """
 import copy
+import inspect
 import numpy as np
 from . import constants
 from .unit import to_md
@@ -213,6 +214,10 @@ class ThermodynamicState:
     def region_lambdas(self, names):
         return [1.0] * len(names), [1.0] * len(names)
 
+    def global_parameter(self, name):
+        """no composable state controls a global parameter of a plain ThermodynamicState (CompoundThermodynamicState.global_parameter)"""
+        return None
+
     def region_bonded_lambdas(self, names):
         return [1.0] * len(names), [1.0] * len(names), [1.0] * len(names)
 
@@ -363,17 +368,305 @@ class AlchemicalState:
                 raise AlchemicalStateError('system has %s = %r, the state %r' % (k, getattr(other, k), getattr(self, k)))
 
 
+class ComposableStateError(Exception):
+    """states.py:2524-2530: error raised by a composable state."""
+    pass
+
+
+class GlobalParameterError(ComposableStateError):
+    """Exception raised by ``GlobalParameterState``."""
+    pass
+
+
+class GlobalParameterFunction:
+    """states.py:3058-3097: a function of global parameters, evaluated with ``utils.math_eval`` on the state's function variables."""
+
+    def __init__(self, expression):
+        self._expression = expression
+
+    def __call__(self, variables):
+        from .utils import math_eval
+        return math_eval(self._expression, variables)
+
+
+class GlobalParameterState:
+    """states.py:3100-3935: a composable state controlling global parameters of a System's forces (here the controlling parameters
+    of the restraint forces, forces.py).  Subclasses declare their parameters with the ``GlobalParameter`` descriptor; parameters
+    left undefined read as None.  ``apply_to_context`` has no counterpart: the engine handle stands in for a Context, the sampler
+    hands it every state's values."""
+
+    _GLOBAL_PARAMETER_ERROR = GlobalParameterError
+
+    def __init__(self, parameters_name_suffix=None, **kwargs):
+        self._initialize(parameters_name_suffix=parameters_name_suffix, **kwargs)
+
+    @classmethod
+    def from_system(cls, system, parameters_name_suffix=None):
+        """The state whose parameters are the values the System's forces define (their default values)."""
+        state_parameters = {}
+        for force, parameter_name, parameter_id in cls._get_system_controlled_parameters(system, parameters_name_suffix):
+            parameter_value = force.getGlobalParameterDefaultValue(parameter_id)
+            if parameter_name in state_parameters:
+                if state_parameters[parameter_name] != parameter_value:
+                    err_msg = ('Parameter {} has been found twice (Force {}) with two values: '
+                               '{} and {}').format(parameter_name, force.__class__.__name__,
+                                                   parameter_value, state_parameters[parameter_name])
+                    raise cls._GLOBAL_PARAMETER_ERROR(err_msg)
+            else:
+                state_parameters[parameter_name] = parameter_value
+        if len(state_parameters) == 0:
+            err_msg = 'System has no global parameters controlled by this state.'
+            raise cls._GLOBAL_PARAMETER_ERROR(err_msg)
+        state = cls(parameters_name_suffix)
+        for parameter_name, parameter_value in state_parameters.items():
+            setattr(state, parameter_name, parameter_value)
+        return state
+
+    def get_function_variable(self, variable_name):
+        try:
+            variable_value = self._function_variables[variable_name]
+        except KeyError:
+            err_msg = f'Unknown function variable {variable_name}'
+            raise self._GLOBAL_PARAMETER_ERROR(err_msg)
+        return variable_value
+
+    def set_function_variable(self, variable_name, new_value):
+        forbidden_variable_names = set(self._parameters)
+        if variable_name in forbidden_variable_names:
+            err_msg = ('Cannot have an function variable with the same name '
+                       'of the predefined global parameter {}.'.format(variable_name))
+            raise self._GLOBAL_PARAMETER_ERROR(err_msg)
+        if not (np.isreal(new_value) and np.isscalar(new_value)):
+            err_msg = 'Only integers and floats can be assigned to a function variable.'
+            raise self._GLOBAL_PARAMETER_ERROR(err_msg)
+        self._function_variables[variable_name] = new_value
+
+    def __eq__(self, other):
+        if not isinstance(other, GlobalParameterState):
+            return False
+        if not set(self._parameters) == set(other._parameters):
+            return False
+        return all(getattr(self, p) == getattr(other, p) for p in self._parameters)
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __str__(self):
+        return str(self._parameters)
+
+    class GlobalParameter:
+        """Descriptor for a global parameter (states.py:3434-3482): name, value in the standard state, optional validator
+        ``validator(descriptor, instance, new_value) -> validated_value``."""
+
+        def __init__(self, parameter_name, standard_value, validator=None):
+            self.parameter_name = parameter_name
+            self.standard_value = standard_value
+            self.validator_func = validator
+
+        def __get__(self, instance, owner_class=None):
+            if instance is None:
+                return self
+            self._check_controlled(instance)
+            return instance._get_global_parameter_value(self.parameter_name, self)
+
+        def __set__(self, instance, new_value):
+            self._check_controlled(instance)
+            instance._set_global_parameter_value(self.parameter_name, new_value, self)
+
+        def validator(self, validator):
+            return self.__class__(self.parameter_name, self.standard_value, validator)
+
+        def _check_controlled(self, instance):
+            if instance._parameters_name_suffix is not None:
+                suffixed_parameter_name = self.parameter_name + '_' + instance._parameters_name_suffix
+                err_msg = 'This state does not control {} but {}.'.format(self.parameter_name, suffixed_parameter_name)
+                raise AttributeError(err_msg)
+
+    def apply_to_system(self, system):
+        """Set the System's global parameters (the forces' default values) to this state's."""
+        parameters_applied = set()
+        for force, parameter_name, parameter_id in self._get_system_controlled_parameters(system, self._parameters_name_suffix):
+            parameter_value = getattr(self, parameter_name)
+            if parameter_value is None:
+                err_msg = 'The system parameter {} is not defined in this state.'
+                raise self._GLOBAL_PARAMETER_ERROR(err_msg.format(parameter_name))
+            parameters_applied.add(parameter_name)
+            force.setGlobalParameterDefaultValue(parameter_id, parameter_value)
+        for parameter_name in self._get_controlled_parameters(self._parameters_name_suffix):
+            if self._parameters[parameter_name] is not None and parameter_name not in parameters_applied:
+                err_msg = 'Could not find global parameter {} in the system.'
+                raise self._GLOBAL_PARAMETER_ERROR(err_msg.format(parameter_name))
+
+    def check_system_consistency(self, system):
+        system_state = self.__class__.from_system(system, self._parameters_name_suffix)
+        if self != system_state:
+            err_msg = ('Consistency check failed:\n'
+                       '\tSystem parameters {}\n'
+                       '\t{} parameters {}')
+            raise self._GLOBAL_PARAMETER_ERROR(err_msg.format(system_state, self.__class__.__name__, self))
+
+    def apply_to_context(self, context):
+        raise NotImplementedError('GlobalParameterState.apply_to_context: there is no openmm.Context here; the sampler hands every '
+                                  "state's global parameters to the engine handle")
+
+    @classmethod
+    def _get_controlled_parameters(cls, parameters_name_suffix=None):
+        suffix = '' if parameters_name_suffix is None else '_' + parameters_name_suffix
+        return {name + suffix: descriptor for c in inspect.getmro(cls)
+                for name, descriptor in c.__dict__.items() if isinstance(descriptor, cls.GlobalParameter)}
+
+    def _validate_global_parameter(self, parameter_name, parameter_value, descriptor=None):
+        if descriptor is None:
+            descriptor = self._get_controlled_parameters(self._parameters_name_suffix)[parameter_name]
+        if descriptor.validator_func is not None:
+            parameter_value = descriptor.validator_func(descriptor, self, parameter_value)
+        return parameter_value
+
+    def _get_global_parameter_value(self, parameter_name, descriptor=None, resolve_function=True):
+        parameter_value = self._parameters[parameter_name]
+        if resolve_function and isinstance(parameter_value, GlobalParameterFunction):
+            parameter_value = parameter_value(self._function_variables)
+            parameter_value = self._validate_global_parameter(parameter_name, parameter_value, descriptor)
+        return parameter_value
+
+    def _set_global_parameter_value(self, parameter_name, new_value, descriptor=None):
+        if parameter_name not in self._parameters:
+            raise KeyError(parameter_name)
+        if not isinstance(new_value, GlobalParameterFunction):
+            new_value = self._validate_global_parameter(parameter_name, new_value, descriptor)
+        self._parameters[parameter_name] = new_value
+
+    def __getattr__(self, key):
+        if key.startswith('__') or key in ('_parameters', '_function_variables', '_parameters_name_suffix'):
+            raise AttributeError(key)
+        try:
+            return self._get_global_parameter_value(key)
+        except KeyError:
+            raise AttributeError(key)
+
+    def __setattr__(self, key, value):
+        if '_parameters_name_suffix' in self.__dict__ and self._parameters_name_suffix is not None:
+            try:
+                self._set_global_parameter_value(key, value)
+            except KeyError:
+                pass
+            else:
+                return
+        super().__setattr__(key, value)
+
+    @classmethod
+    def _get_system_controlled_parameters(cls, system, parameters_name_suffix):
+        searched_parameters = cls._get_controlled_parameters(parameters_name_suffix)
+        for force in system.getForces():
+            try:
+                n_global_parameters = force.getNumGlobalParameters()
+            except AttributeError:
+                continue
+            for parameter_id in range(n_global_parameters):
+                parameter_name = force.getGlobalParameterName(parameter_id)
+                if parameter_name in searched_parameters:
+                    yield force, parameter_name, parameter_id
+
+    def __getstate__(self):
+        serialization = dict(parameters={}, function_variables=self._function_variables.copy(),
+                             parameters_name_suffix=self._parameters_name_suffix)
+        suffix = '' if self._parameters_name_suffix is None else '_' + self._parameters_name_suffix
+        for parameter_name in self._get_controlled_parameters():
+            parameter_value = self._parameters[parameter_name + suffix]
+            if isinstance(parameter_value, GlobalParameterFunction):
+                parameter_value = parameter_value._expression
+            serialization['parameters'][parameter_name] = parameter_value
+        return serialization
+
+    def __setstate__(self, serialization):
+        parameters = dict(serialization['parameters'])
+        parameters_name_suffix = serialization.get('parameters_name_suffix', None)
+        function_variables = serialization.get('function_variables', {})
+        global_parameter_functions = {}
+        for parameter_name, value in parameters.items():
+            if isinstance(value, str):
+                global_parameter_functions[parameter_name] = value
+                parameters[parameter_name] = None
+        self._initialize(parameters_name_suffix=parameters_name_suffix, **parameters)
+        for variable_name, value in function_variables.items():
+            self.set_function_variable(variable_name, value)
+        suffix = '' if parameters_name_suffix is None else '_' + parameters_name_suffix
+        for parameter_name, expression in global_parameter_functions.items():
+            setattr(self, parameter_name + suffix, GlobalParameterFunction(expression))
+
+    def _initialize(self, parameters_name_suffix=None, **kwargs):
+        self._function_variables = {}
+        controlled_parameters = set(self._get_controlled_parameters())
+        unknown_parameters = set(kwargs) - controlled_parameters
+        if len(unknown_parameters) > 0:
+            err_msg = f"Unknown parameters {unknown_parameters}"
+            raise self._GLOBAL_PARAMETER_ERROR(err_msg)
+        if parameters_name_suffix is not None:
+            kwargs = {key + '_' + parameters_name_suffix: value for key, value in kwargs.items()}
+            controlled_parameters = {key + '_' + parameters_name_suffix for key in controlled_parameters}
+        self._parameters = dict.fromkeys(controlled_parameters, None)
+        self._parameters_name_suffix = parameters_name_suffix
+        for parameter_name, value in kwargs.items():
+            setattr(self, parameter_name, value)
+
+    def __deepcopy__(self, memo):
+        new = object.__new__(type(self))
+        new.__setstate__(self.__getstate__())
+        return new
+
+    def __copy__(self):
+        return self.__deepcopy__({})
+
+    def __reduce__(self):
+        # a pickled state names no class outside this package (a store opens only this package's classes, multistatereporter.py):
+        # it comes back as a StoredGlobalParameterState that controls the same parameters under the same class name
+        spec = {name: d.standard_value for name, d in type(self)._get_controlled_parameters().items()}
+        return (StoredGlobalParameterState, (), dict(class_name=type(self).__name__, spec=spec, state=self.__getstate__()))
+
+
+_STORED_CLASSES = {}
+
+
+def stored_global_parameter_class(class_name, spec):
+    """The GlobalParameterState subclass named ``class_name`` that controls the parameters of ``spec`` ({name: standard value}): what
+    a store gives back for a user's subclass it cannot import (one class per name and parameter set)."""
+    key = (str(class_name), tuple(sorted((str(k), v) for k, v in spec.items())))
+    cls = _STORED_CLASSES.get(key)
+    if cls is None:
+        attrs = {name: GlobalParameterState.GlobalParameter(name, standard_value=v) for name, v in key[1]}
+        attrs['__module__'] = __name__
+        cls = _STORED_CLASSES[key] = type(key[0], (StoredGlobalParameterState,), attrs)
+    return cls
+
+
+class StoredGlobalParameterState(GlobalParameterState):
+    """A GlobalParameterState read back from a store: the class the store recorded (its name and parameters), without validators."""
+
+    def __setstate__(self, serialization):
+        if 'spec' in serialization:
+            object.__setattr__(self, '__class__', stored_global_parameter_class(serialization['class_name'], serialization['spec']))
+            serialization = serialization['state']
+        GlobalParameterState.__setstate__(self, serialization)
+
+
 class CompoundThermodynamicState(ThermodynamicState):
     """states.py:2524-3046 restricted to AlchemicalState composable states: one (any suffix), or one per named alchemical region."""
 
     def __init__(self, thermodynamic_state, composable_states):
         super().__init__(thermodynamic_state.system, thermodynamic_state.temperature, thermodynamic_state.pressure)
-        if len(composable_states) < 1 or not all(isinstance(c, AlchemicalState) for c in composable_states):
-            raise NotImplementedError('only AlchemicalState composable states are supported')
-        suffixes = [c.parameters_name_suffix for c in composable_states]
-        if len(set(suffixes)) != len(suffixes):
+        if len(composable_states) < 1 or not all(isinstance(c, (AlchemicalState, GlobalParameterState)) for c in composable_states):
+            raise NotImplementedError('only AlchemicalState and GlobalParameterState composable states are supported')
+        alchs = [c for c in composable_states if isinstance(c, AlchemicalState)]
+        globs = [c for c in composable_states if isinstance(c, GlobalParameterState)]
+        suffixes = [c.parameters_name_suffix for c in alchs]
+        names = [p for g in globs for p in g._parameters]
+        if len(set(suffixes)) != len(suffixes) or len(set(names)) != len(names):
             raise ValueError('composable states control the same parameters')                 # states.py:2574-2590
-        object.__setattr__(self, '_alchs', [copy.copy(c) for c in composable_states])
+        object.__setattr__(self, '_alchs', [copy.copy(c) for c in alchs])
+        # GlobalParameterStates (states.py:3100-3935, e.g. lambda_restraints of the restraint forces): parameters by their (suffixed) names
+        object.__setattr__(self, '_globals', [copy.deepcopy(c) for c in globs])
+
+    _globals = ()
 
     @property
     def _alch(self):
@@ -381,6 +674,9 @@ class CompoundThermodynamicState(ThermodynamicState):
 
     def _owner(self, name):
         """the composable state that answers to the attribute ``name`` (plain or suffixed), or None"""
+        for g in self.__dict__.get('_globals', ()):
+            if name in g._parameters:
+                return g, name
         for c in self.__dict__.get('_alchs', ()):
             sfx = c.parameters_name_suffix
             if name in AlchemicalState._PARAMETERS and (sfx is None or len(self._alchs) == 1):
@@ -410,7 +706,7 @@ class CompoundThermodynamicState(ThermodynamicState):
     def __setattr__(self, name, value):
         hit = None if name.startswith('_') else self._owner(name)
         if hit is not None:
-            setattr(hit[0], hit[1], float(value))
+            setattr(hit[0], hit[1], value if isinstance(hit[0], GlobalParameterState) else float(value))
         else:
             object.__setattr__(self, name, value)
 
@@ -434,7 +730,16 @@ class CompoundThermodynamicState(ThermodynamicState):
     def __deepcopy__(self, memo):
         new = copy.copy(self)
         object.__setattr__(new, '_alchs', [copy.copy(c) for c in self._alchs])
+        object.__setattr__(new, '_globals', [copy.deepcopy(c) for c in self.__dict__.get('_globals', ())])
         return new
+
+    def global_parameter(self, name):
+        """The value of the global parameter ``name`` at this state: the GlobalParameterState that controls it, None if none does
+        (or it leaves the parameter undefined)."""
+        for g in self.__dict__.get('_globals', ()):
+            if name in g._parameters:
+                return g._get_global_parameter_value(name)
+        return None
 
     def __setstate__(self, state):
         state = dict(state)

@@ -409,6 +409,11 @@ def _classify_constraints(system):
     return settle, shake, shake_d
 
 
+def _is_restraint(force):
+    from .forces import is_restraint_force
+    return is_restraint_force(force)
+
+
 def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
     """Flatten a System into the arrays of remd_system_desc (include/remd_hip.h).
 
@@ -425,6 +430,7 @@ def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
     nb = None
     gb = None
     cmm = 0
+    restraints = []                     # receptor-ligand restraints (forces.py): remd_set_restraints, include/remd_hip_restraints.h
     # force groups of (external, bonds, angles, torsions, nonbonded direct, PME reciprocal): remd_set_force_groups
     fg = [0, 0, 0, 0, 0, 0]
     for f in system.forces:
@@ -462,6 +468,9 @@ def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
             cmm = f.frequency
         elif isinstance(f, GBSAOBCForce):
             gb = f
+        elif _is_restraint(f):
+            from .forces import restraint_terms
+            restraints.append(restraint_terms(f, system.masses))
         else:
             raise NotImplementedError('unsupported force %r' % type(f).__name__)
     d['bond_atoms'] = np.array([b[:2] for b in bonds], dtype=np.int32).reshape(-1, 2)
@@ -554,6 +563,9 @@ def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
     if getattr(system, 'rf_unshifted_switch_width', None) is not None and d['nb_method'] == 1:
         # the reaction field as the alchemical factory re-writes it for the WHOLE system (alchemical_rf_treatment='switched'): remd_set_reaction_field
         d['rf_unshifted_switch_width'] = float(system.rf_unshifted_switch_width)
+    if restraints:
+        # keyed by position ('000', '001', ...): the fingerprint hashes every array of a nested dict
+        d['restraints'] = {'%03d' % k: r for k, r in enumerate(restraints)}
     if getattr(system, 'alchemical_regions', None) is not None:
         # general regions: this descriptor is the NonbondedForce the factory leaves behind, the custom forces follow through
         # remd_set_alchemical_regions (alchemy.AbsoluteAlchemicalFactory._region_terms)

@@ -93,8 +93,82 @@ def _emit_force(forces, f, force_group=None, particles=None, exceptions=None, gl
         b = ET.SubElement(e, 'Particles')
         for (q, r, sc) in f.particles:
             ET.SubElement(b, 'Particle', dict(q=_f(q), r=_f(r), scale=_f(sc)))
+    elif _is_restraint(f):
+        _emit_restraint(forces, f)
     else:
         raise NotImplementedError('unsupported force %r' % name)
+
+
+def _is_restraint(f):
+    from .forces import is_restraint_force
+    return is_restraint_force(f)
+
+
+def _emit_restraint(forces, f):
+    """A restraint force (forces.py) in the layout of OpenMM's CustomCentroidBondForceProxy / CustomBondForceProxy: energy, force
+    group, usesPeriodic, the per-bond and global parameters, the groups (with their weights when the force gives any) and the bond.
+    External knowledge, not checked against a document OpenMM wrote: no such document exists to compare with."""
+    from .forces import CustomCentroidBondForce
+    kind = 'CustomCentroidBondForce' if isinstance(f, CustomCentroidBondForce) else 'CustomBondForce'
+    attrs = dict(energy=f.getEnergyFunction(), forceGroup=str(f.getForceGroup()), name=kind, type=kind,
+                 usesPeriodic=str(int(f.usesPeriodicBoundaryConditions())), version='3')
+    if kind == 'CustomCentroidBondForce':
+        attrs['groups'] = str(f.getNumGroupsPerBond())
+    e = ET.SubElement(forces, 'Force', attrs)
+    b = ET.SubElement(e, 'PerBondParameters')
+    for i in range(f.getNumPerBondParameters()):
+        ET.SubElement(b, 'Parameter', dict(name=f.getPerBondParameterName(i)))
+    g = ET.SubElement(e, 'GlobalParameters')
+    for i in range(f.getNumGlobalParameters()):
+        ET.SubElement(g, 'Parameter', dict(default=_f(f.getGlobalParameterDefaultValue(i)), name=f.getGlobalParameterName(i)))
+    ET.SubElement(e, 'EnergyParameterDerivatives')
+    bonds = []
+    if kind == 'CustomCentroidBondForce':
+        ET.SubElement(e, 'Functions')
+        gr = ET.SubElement(e, 'Groups')
+        for k in range(f.getNumGroups()):
+            particles, weights = f.getGroupParameters(k)
+            ge = ET.SubElement(gr, 'Group')
+            for n, p in enumerate(particles):
+                ET.SubElement(ge, 'Particle', dict(p=str(p), **({'weight': _f(weights[n])} if len(weights) else {})))
+        for k in range(f.getNumBonds()):
+            groups, params = f.getBondParameters(k)
+            bonds.append(dict({'g%d' % (n + 1): str(x) for n, x in enumerate(groups)}, **{'param%d' % (n + 1): _f(v) for n, v in enumerate(params)}))
+    else:
+        for k in range(f.getNumBonds()):
+            p1, p2, params = f.getBondParameters(k)
+            bonds.append(dict(p1=str(p1), p2=str(p2), **{'param%d' % (n + 1): _f(v) for n, v in enumerate(params)}))
+    bl = ET.SubElement(e, 'Bonds')
+    for a in bonds:
+        ET.SubElement(bl, 'Bond', a)
+
+
+def _parse_restraint(e):
+    """A CustomCentroidBondForce / CustomBondForce element as the force classes of forces.py; the restraint class comes back from the
+    class hash its first global parameter carries (forces.restore_interface)."""
+    from . import forces
+    kind = e.get('type')
+    f = forces.CustomCentroidBondForce(int(e.get('groups', '2')), e.get('energy')) if kind == 'CustomCentroidBondForce' \
+        else forces.CustomBondForce(e.get('energy'))
+    f.setUsesPeriodicBoundaryConditions(bool(int(e.get('usesPeriodic', '0'))))
+    names = [p.get('name') for p in _children(e, 'PerBondParameters', 'Parameter')]
+    for n in names:
+        f.addPerBondParameter(n)
+    for p in _children(e, 'GlobalParameters', 'Parameter'):
+        f.addGlobalParameter(p.get('name'), float(p.get('default')))
+    params = lambda b: [float(b.get('param%d' % (n + 1))) for n in range(len(names))]
+    if kind == 'CustomCentroidBondForce':
+        for ge in _children(e, 'Groups', 'Group'):
+            ps = ge.findall('Particle')
+            weights = [float(p.get('weight')) for p in ps if p.get('weight') is not None]
+            f.addGroup([int(p.get('p')) for p in ps], weights if len(weights) == len(ps) and weights else None)
+        for b in _children(e, 'Bonds', 'Bond'):
+            f.addBond([int(b.get('g%d' % (n + 1))) for n in range(f.getNumGroupsPerBond())], params(b))
+    else:
+        for b in _children(e, 'Bonds', 'Bond'):
+            f.addBond(int(b.get('p1')), int(b.get('p2')), params(b))
+    forces.restore_interface(f)
+    return f
 
 
 def to_xml(system, pressure=None, temperature=None, barostat_frequency=25):
@@ -140,6 +214,11 @@ def _children(elem, block, item):
 def _nonempty(elem, block):
     b = elem.find(block)
     return b is not None and len(list(b)) > 0
+
+
+def _carries_class_hash(e):
+    g = _children(e, 'GlobalParameters', 'Parameter')
+    return len(g) > 0 and g[0].get('name') == '_restorable_force__class_hash'
 
 
 def from_xml(text_or_path):
@@ -205,6 +284,8 @@ def from_xml(text_or_path):
                 f.addParticle(float(b.get('q')), float(b.get('sig')), float(b.get('eps')))
             for b in _children(e, 'Exceptions', 'Exception'):
                 f.addException(int(b.get('p1')), int(b.get('p2')), float(b.get('q')), float(b.get('sig')), float(b.get('eps')))
+        elif kind == 'CustomCentroidBondForce' or (kind == 'CustomBondForce' and _carries_class_hash(e)):
+            f = _parse_restraint(e)                           # a restraint (forces.py); system_to_desc refuses other expressions
         elif kind in ('CustomNonbondedForce', 'CustomBondForce', 'CustomAngleForce', 'CustomTorsionForce'):
             from . import _alchemical_xml
             customs.append(_alchemical_xml.parse_custom(e))        # only as the pieces of an alchemically modified System

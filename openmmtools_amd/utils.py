@@ -111,3 +111,39 @@ def deserialize(serialization):
     except AttributeError:
         raise ValueError('Cannot deserialize class {} without a __setstate__ method'.format(class_name))
     return instance
+
+
+def math_eval(expression, variables=None, functions=None):
+    """openmmtools/utils/utils.py:238-320: evaluate an arithmetic expression (+ - * / **, unary -, & |, the functions of the math
+    module and step / step_hm / sign) with the given variables."""
+    import ast
+    import math
+    import operator
+    import numpy as np
+    operators = {ast.Add: operator.add, ast.Sub: operator.sub, ast.Mult: operator.mul, ast.Div: operator.truediv,
+                 ast.Pow: operator.pow, ast.USub: operator.neg, ast.BitAnd: operator.and_, ast.And: operator.and_,
+                 ast.BitOr: operator.or_, ast.Or: operator.or_}
+    fns = {'step': lambda x: 1 * (x >= 0), 'step_hm': lambda x: 0.5 * (np.sign(x) + 1), 'sign': lambda x: np.sign(x)}
+    if functions is not None:
+        fns.update(functions)
+    variables = variables or {}
+
+    def ev(node):
+        if isinstance(node, ast.Constant):
+            return node.value
+        if isinstance(node, ast.UnaryOp):
+            return operators[type(node.op)](ev(node.operand))
+        if isinstance(node, ast.BinOp):
+            return operators[type(node.op)](ev(node.left), ev(node.right))
+        if isinstance(node, ast.BoolOp):
+            out = ev(node.values[0])
+            for v in node.values[1:]:
+                out = operators[type(node.op)](out, ev(v))
+            return out
+        if isinstance(node, ast.Name):
+            return variables[node.id]
+        if isinstance(node, ast.Call):
+            f = fns.get(node.func.id) or getattr(math, node.func.id)
+            return f(*[ev(a) for a in node.args])
+        raise TypeError('unsupported expression node %r' % type(node).__name__)
+    return ev(ast.parse(expression, mode='eval').body)

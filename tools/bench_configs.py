@@ -57,6 +57,28 @@ def main():
         ss = states.SamplerState(hg.positions, box_vectors=hg.system.getDefaultPeriodicBoxVectors())
         s.create(ths, [ss] * 8)
         run('4 (1-GPU share): HostGuestExplicit, 8 replicas x 64 alchemical states, g-BAOAB 2 fs x 500', s, 3)
+    if '4rs' in which:
+        # config 4's share with a receptor-ligand restraint (forces.py, csrc/restraints.hip): a HarmonicRestraintForce between the CB7
+        # heavy atoms and the B2 guest, K = 0.2 kcal/mol/A^2, lambda_restraints rising 0 -> 1 along the coupled half and 1 where the
+        # guest is decoupled.  ('4r' is taken: the general-regions variant below.)
+        from openmmtools_amd import forces
+
+        class RestraintState(states.GlobalParameterState):
+            lambda_restraints = states.GlobalParameterState.GlobalParameter('lambda_restraints', standard_value=1.0)
+        hg = testsystems.HostGuestExplicit()
+        lam_e = np.concatenate([np.linspace(1.0, 0.0, 32), np.zeros(32)])
+        lam_s = np.concatenate([np.ones(32), np.linspace(1.0, 0.0, 32)])
+        lam_r = np.concatenate([np.linspace(0.0, 1.0, 32), np.ones(32)])
+        asys = alchemy.AbsoluteAlchemicalFactory().create_alchemical_system(hg.system, alchemy.AlchemicalRegion(alchemical_atoms=range(126, 156)))
+        heavy = [i for i in range(126) if hg.system.getParticleMass(i) > 1.5]
+        asys.addForce(forces.HarmonicRestraintForce(0.2 * 4.184 * 100.0, heavy, list(range(126, 156))))
+        ths = [states.CompoundThermodynamicState(states.ThermodynamicState(asys, 300.0),
+                                                 [states.AlchemicalState(lambda_sterics=ls, lambda_electrostatics=le), RestraintState(lambda_restraints=lr)])
+               for le, ls, lr in zip(lam_e, lam_s, lam_r)]
+        s = SAMSSampler(mcmc_moves=move(2.0, 'V R R O R R V'), number_of_iterations=10 ** 9, engine=HipEngine(), seed=1)
+        ss = states.SamplerState(hg.positions, box_vectors=hg.system.getDefaultPeriodicBoxVectors())
+        s.create(ths, [ss] * 8)
+        run('4rs (1-GPU share, restrained): HostGuestExplicit + CB7/B2 HarmonicRestraintForce, 8 replicas x 64 states, g-BAOAB 2 fs x 500', s, 3)
     for tag, kw in (('4r', dict()), ('4d', dict(alchemical_pme_treatment='direct-space'))):
         if tag not in which:
             continue
