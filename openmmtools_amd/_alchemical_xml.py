@@ -315,6 +315,14 @@ def parse_custom_gb(e):
                 terms=[(t.get('expression'), int(t.get('type'))) for t in _kids(e, 'EnergyTerms')])
 
 
+def is_factory_gbsa(f):
+    """True for a CustomGBForce (system.CustomGBForce) holding the factory's own GBSA strings above"""
+    compact = lambda s: s.replace(' ', '')
+    return f.per_particle == ['charge', 'radius', 'scale', 'alchemical'] and \
+        [compact(v[1]) for v in f.computed] == [compact(_GB_I), compact(_GB_B)] and \
+        [compact(t[0]) for t in f.energy_terms] in ([compact(_GB_SELF), compact(_GB_SURFACE), compact(_GB_PAIR)], [compact(_GB_SELF), compact(_GB_PAIR)])
+
+
 def gbsa_from_custom_gb(c):
     """the GBSAOBCForce a parsed alchemical CustomGBForce came from + its alchemical atoms (only the factory's own expressions are understood)"""
     from .system import GBSAOBCForce
@@ -340,8 +348,9 @@ def emit_region_forces(forces, system, emit_plain):
     """The force set of a System in the general-regions mode (``system.alchemical_regions``): the reference's loop over
     single_regions + pair_regions (alchemy.py:1693-2036) restated on plain tables -- INCLUDING its order of reading and zeroing the
     NonbondedForce's parameters, which decides what the later forces' particle tables hold (:1886-1911, 2001-2006)."""
-    from .system import GBSAOBCForce
+    from .system import GBSAOBCForce, CustomGBForce
     gbs = [f for f in system.getForces() if isinstance(f, GBSAOBCForce)]
+    cgbs = [f for f in system.getForces() if isinstance(f, CustomGBForce)]       # already rewritten by the factory (custom_gb.py)
     regions = system.alchemical_regions
     opts = system.alchemical_factory_options
     terms = system.alchemical_region_terms
@@ -467,7 +476,9 @@ def emit_region_forces(forces, system, emit_plain):
     # ---- order and force groups (:1052-1083) ------------------------------------------------------------------------
     for gb in gbs:                                                           # the factory's CustomGBForce joins the lambda_electrostatics forces (:2225)
         by_lambda.setdefault('lambda_electrostatics' + suffix(regions[0]), []).append(('gb', dict(gb=gb, alchemical_atoms=regions[0].alchemical_atoms)))
-    untouched = [f for f in all_forces if not isinstance(f, _REMODELLED) and not isinstance(f, GBSAOBCForce)]
+    for f in cgbs:                                                           # _alchemically_modify_CustomGBForce's force, same group
+        by_lambda.setdefault('lambda_electrostatics' + suffix(regions[0]), []).append(('cgb', dict(f=f)))
+    untouched = [f for f in all_forces if not isinstance(f, _REMODELLED) and not isinstance(f, (GBSAOBCForce, CustomGBForce))]
     readded = [f for f in all_forces if isinstance(f, _REMODELLED) and (not isinstance(f, NonbondedForce) or not exact)]
     free = sorted(set(range(32)) - {f.getForceGroup() for f in untouched + readded})
     if len(free) < len(by_lambda):
@@ -494,6 +505,9 @@ def emit_region_forces(forces, system, emit_plain):
                 _emit_custom_bonded(forces, group, **kw)
             elif kind == 'gb':
                 _emit_custom_gb(forces, group, **kw)
+            elif kind == 'cgb':
+                from .system_xml import emit_custom_gb_force
+                emit_custom_gb_force(forces, kw['f'], group)
             else:
                 _emit_custom_bond(forces, group, kw['energy'], kw['per_params'], kw['lam_globals'], kw['region'], kw['bonds'])
         if exact and key == last_key:
@@ -674,7 +688,11 @@ def rebuild_general_system(system, nb, global_parameters, particle_offsets, exce
     from .alchemy import AlchemicalRegion, AbsoluteAlchemicalFactory
     compact = lambda s: s.replace(' ', '')
     for c in [c for c in customs if c['type'] == 'CustomGBForce']:            # the alchemical GBSA: back to the GBSAOBCForce it came from
-        gb, gb_atoms = gbsa_from_custom_gb(c)
+        if 'force' in c:                                                      # ... or to the CustomGBForce the factory rewrote
+            from .custom_gb import unmodify_custom_gb
+            gb, gb_atoms = unmodify_custom_gb(c['force'])
+        else:
+            gb, gb_atoms = gbsa_from_custom_gb(c)
         system.addForce(gb)
     customs = [c for c in customs if c['type'] != 'CustomGBForce']
     sterics = [c for c in customs if 'U_sterics' in c['energy']]

@@ -69,6 +69,12 @@ class RemdRestraintDesc(C.Structure):
                 ('periodic', C.c_int32), ('force_group', C.c_int32)]
 
 
+class RemdGbModelDesc(C.Structure):
+    """remd_gb_model_desc of include/remd_hip_gb.h (the constants and the cutoff of an OBC-family implicit-solvent model)."""
+    _fields_ = [('offset', C.c_double), ('alpha', C.c_double), ('beta', C.c_double), ('gamma', C.c_double), ('ke', C.c_double),
+                ('surface', C.c_double), ('probe', C.c_double), ('method', C.c_int32), ('cutoff', C.c_double)]
+
+
 # the GPU-only extension of include/remd_hip_restraints.h: bound where the loaded library exports it (the CPU port of the ABI does not)
 RESTRAINT_EXPORTS = ['remd_set_restraints', 'remd_set_restraint_lambdas', 'remd_get_restraint_energies']
 
@@ -177,6 +183,9 @@ def load_library(path=None):
         lib.remd_get_restraint_energies.argtypes = [vp, c_double_p]
         for name in RESTRAINT_EXPORTS:
             getattr(lib, name).restype = C.c_int
+    if hasattr(lib, 'remd_set_gb_model'):                 # include/remd_hip_gb.h (GPU-only, like the restraints)
+        lib.remd_set_gb_model.argtypes = [vp, C.POINTER(RemdGbModelDesc)]
+        lib.remd_set_gb_model.restype = C.c_int
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -320,11 +329,21 @@ class HipEngine:
             self.n_regions = int(r.n_regions)
         gb = desc_dict.get('gbsa')
         if gb is not None:                               # GBSAOBCForce of an implicit-solvent system (alchemy.py:2144-2225)
+            from .custom_gb import is_default_model
+            model = None
+            if not is_default_model(gb):                 # another OBC-family model or a periodic cutoff (custom_gb.py): remd_set_gb_model
+                if not hasattr(self.lib, 'remd_set_gb_model'):
+                    raise NotImplementedError('remd_set_gb_model: this build of the engine library has no GB models other than OBC2 without a cutoff '
+                                              '(include/remd_hip_gb.h is GPU-only)')
+                model = RemdGbModelDesc(*[float(gb[k]) for k in ('offset', 'alpha', 'beta', 'gamma', 'ke', 'surface', 'probe')],
+                                        int(gb['method']), float(gb['cutoff']))
             arrs = [np.ascontiguousarray(gb[k], dtype=np.float64) for k in ('charge', 'radius', 'scale')]
             alch = np.ascontiguousarray(gb.get('alchemical', np.zeros(self.N)), dtype=np.int32)
             g = RemdGbsaDesc(self.N, _dp(arrs[0]), _dp(arrs[1]), _dp(arrs[2]), _ip(alch), float(gb['solute_dielectric']), float(gb['solvent_dielectric']),
                              int(gb.get('surface_area', 1)))
             self._check(self.lib.remd_set_gbsa(self.h, C.byref(g)), 'remd_set_gbsa')
+            if model is not None:
+                self._check(self.lib.remd_set_gb_model(self.h, C.byref(model)), 'remd_set_gb_model')
         if 'force_groups' in desc_dict:                  # Force.getForceGroup() of the force classes (V<g> substeps)
             self.set_force_groups(desc_dict['force_groups'])
         self.n_restraints = 0

@@ -23,7 +23,8 @@ Two device paths serve it:
 Under the exact PME treatment that path scales every region's charges by its own lambda_electrostatics inside the whole Ewald sum
 (remd_alch_regions_desc.exact_pme).  It also carries the softened bonds / angles / torsions of a region (:1115-1354; lambda_bonds ...),
 the vacuum systems (NonbondedForce.NoCutoff: csrc/nocutoff.hip) and, with a GBSAOBCForce in the System, the alchemical GBSA of
-:2144-2225 (csrc/gbsa.hip; one region, as in the reference).  Not built: AMOEBA, GB models other than OBC2, GBSA with a cutoff.
+:2144-2225 (csrc/gbsa.hip; one region, as in the reference), and a CustomGBForce of the OBC family (:2223-2345, custom_gb.py).  Not built: AMOEBA,
+other GB models, GBSAOBCForce with a cutoff.
 This module also computes the per-state long-range-correction constants that MultiStateSampler hands to remd_set_states(energy_const).
 """
 import copy
@@ -122,13 +123,22 @@ class AbsoluteAlchemicalFactory:
                     raise ValueError('Consistent exceptions are' + err)
                 if (r.softcore_beta, r.softcore_d, r.softcore_e) != (0, 1, 1):
                     raise ValueError('Softcore electrostatics is' + err)
-        from .system import GBSAOBCForce
+        from .system import GBSAOBCForce, CustomGBForce
         has_gb = any(isinstance(f, GBSAOBCForce) for f in system.getForces())
         if has_gb and len(regions) > 1:
             raise NotImplementedError('Multiple regions does not work with GBSAOBCForce')               # alchemy.py:2168-2169
+        custom_gb = [k for k, f in enumerate(system.forces) if isinstance(f, CustomGBForce)]
+        if custom_gb and len(regions) > 1:
+            raise NotImplementedError("Multiple regions does not work with CustomGBForce")              # alchemy.py:2274-2275
+        for k in custom_gb:
+            # _alchemically_modify_CustomGBForce (alchemy.py:2223-2345): the reference's rewritten strings; the force joins the
+            # lambda_electrostatics forces when the System is written (_alchemical_xml.emit_region_forces)
+            from .custom_gb import alchemically_modify_custom_gb
+            system.forces[k] = alchemically_modify_custom_gb(system.forces[k], regions[0].alchemical_atoms)
+        has_gb = has_gb or bool(custom_gb)
         r0 = regions[0]
         bonded = self._softened_bonded_terms(system, regions, interactions)           # takes them out of the System's bonded forces
-        fast = (len(regions) == 1 and r0.softcore_c == 6.0 and (exact or not charged) and bonded is None and
+        fast = (len(regions) == 1 and r0.softcore_c == 6.0 and (exact or not charged) and bonded is None and not has_gb and
                 nb is not None and nb.getNonbondedMethod() != NonbondedForce.NoCutoff)      # (that path lives in the cutoff-based pair kernels)
         if fast:
             # the pair kernels' own path: one region, charges scaled inside the Ewald sum or none to scale

@@ -9,14 +9,25 @@
 //   gb_pair_kernel    self + surface + pair energies, the pair term's direct force on i, dE/dB_i  ->  c_i = dE/dB_i dB_i/dI_i
 //   gb_chain_kernel   the force through the Born radii: sum_j [c_i s_j H'(r; or_i, sr_j) + c_j s_i H'(r; or_j, sr_i)] (x_j - x_i) / r
 // s = lambda_electrostatics of the replica's state on the alchemical particles, 1 elsewhere.
+//
+// The model constants (include/remd_hip_gb.h remd_set_gb_model: offset, the tanh coefficients, k_e, the surface term) are kernel
+// arguments; OBC2 without a cutoff unless a model is set.  The three kernels are templated on the cutoff mode: GB_CUT_NONE (every pair)
+// or GB_CUT_PERIODIC (OpenMM's CustomGBForce CutoffPeriodic: the minimum image under the replica's own box, a pair computed value and
+// a pair energy term see only pairs with r < cutoff, no shift, no switch; the single-particle terms are unchanged).
 #include "remd_internal.h"
+#include "../../include/remd_hip_gb.h"
 #include "listed_terms.h"
 #include <cmath>
 #include <algorithm>
 
-#define GB_KE 138.935485f
-#define GB_OFFSET 0.009f
-#define GB_SA 28.3919551f
+#define GB_CUT_NONE 0
+#define GB_CUT_PERIODIC 2
+
+// the model as the kernels take it; the derivative of the tanh argument alpha psi - beta psi^2 + gamma psi^3 is (d0 - d1 psi + d2 psi^2),
+// (d0, d1, d2) = (alpha, 2 beta, 3 gamma) computed in double and rounded to float once (OBC2: 1, 1.6f, 14.55f)
+struct gb_consts {
+    float offset, alpha, beta, gamma, d0, d1, d2, ke, sa, probe, cut2;
+};
 
 struct gbsa_tables {
     int N = 0, n_tile = 0;
@@ -30,6 +41,7 @@ struct gbsa_tables {
     // a deep copy of the descriptor of remd_set_gbsa: the blocks of a phased propagation (api.hip) are set up from it
     remd_gbsa_desc store{}; std::vector<double> st_charge, st_radius, st_scale; std::vector<int32_t> st_alch;
     double* d_epart = nullptr; double* d_col = nullptr; int buf_R = 0;
+    remd_gb_model_desc model{}; gb_consts k{}; int method = GB_CUT_NONE;     // remd_set_gb_model (OBC2, NoCutoff until then)
 };
 static handle_table<gbsa_tables> g_gb;
 
@@ -52,14 +64,46 @@ __device__ __forceinline__ void gb_H(float r, float or1, float sr2, float& H, fl
                  + 0.5f * ((dL * iL - iU) * ir - lg * ir * ir) + dC);
 }
 
+// the vector from i to j and r^2: as it stands (GB_CUT_NONE) or the minimum image under the box L (GB_CUT_PERIODIC)
+template <int CUT>
+__device__ __forceinline__ void gb_vec(const float4& xi, const float4& xj, const float4& L, float& dx, float& dy, float& dz, float& r2)
+{
+    dx = xj.x - xi.x; dy = xj.y - xi.y; dz = xj.z - xi.z;
+    if (CUT == GB_CUT_PERIODIC) { dx -= L.x * rintf(dx / L.x); dy -= L.y * rintf(dy / L.y); dz -= L.z * rintf(dz / L.z); }
+    r2 = dx * dx + dy * dy + dz * dz;
+}
+
+template <int CUT>
+__device__ __forceinline__ float4 gb_box(const float* __restrict__ box, int r)
+{
+    return CUT == GB_CUT_PERIODIC ? reinterpret_cast<const float4*>(box)[r] : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// tanh(alpha psi - beta psi^2 + gamma psi^3) -> B and dB/dI.  The first term is fma(alpha or_i, I, -beta psi^2): with alpha = 1 that is
+// the contraction the compiler made of OBC2's psi - 0.8f psi^2 + 4.85f psi^3 when the constants were literals (same arithmetic)
+__device__ __forceinline__ float2 gb_born_radius(float I, float or_i, float R, const gb_consts& k)
+{
+    const float psi = I * or_i;
+    float arg;
+    {
+#pragma clang fp contract(off)
+        arg = fmaf(k.alpha * or_i, I, -(k.beta * psi * psi)) + k.gamma * psi * psi * psi;
+    }
+    const float th = tanhf(arg);
+    const float B = 1.f / (1.f / or_i - th / R);
+    return make_float2(B, B * B * (1.f - th * th) * (k.d0 - k.d1 * psi + k.d2 * psi * psi) * or_i / R);
+}
+
 // The three kernels: workgroup = (64 atoms i, replica) of GB_WAVES wavefronts; lane = atom i, wavefront w takes the partners
 // j = w (mod GB_WAVES) of every block of GB_BLOCK atoms staged in LDS, an atom's partial sums are added in wavefront order (fixed order).
 // (One wavefront per tile summing N dependent partner terms -- each with a logarithm and a handful of divisions -- was 10 + 7 + 17 us for
 // 22 atoms: profiles/r06_43.)
 #define GB_WAVES 16
 #define GB_BLOCK (64 * GB_WAVES)
+template <int CUT>
 __global__ __launch_bounds__(GB_BLOCK)
-void gb_born_kernel(int N, int Npad, const float4* __restrict__ par, const float* __restrict__ lam, int lam_stride, const float4* __restrict__ pos, float2* __restrict__ born)
+void gb_born_kernel(int N, int Npad, gb_consts kc, const float4* __restrict__ par, const float* __restrict__ lam, int lam_stride, const float4* __restrict__ pos,
+                    const float* __restrict__ box, float2* __restrict__ born)
 {
     __shared__ float4 s_x[GB_BLOCK];       // x, y, z, sr_j
     __shared__ float s_s[GB_BLOCK];        // s_j
@@ -70,13 +114,14 @@ void gb_born_kernel(int N, int Npad, const float4* __restrict__ par, const float
     const bool live = i < N;
     const float4 xi = live ? P[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     const float4 pi = live ? par[i] : make_float4(0.f, 1.f, 0.f, 0.f);
-    const float or_i = pi.y - GB_OFFSET;
+    const float4 L = gb_box<CUT>(box, r);
+    const float or_i = pi.y - kc.offset;
     float I = 0.f;
     for (int j0 = 0; j0 < N; j0 += GB_BLOCK) {
         __syncthreads();
         if (j0 + (int)threadIdx.x < N) {
             const float4 xj = P[j0 + threadIdx.x], pj = par[j0 + threadIdx.x];
-            s_x[threadIdx.x] = make_float4(xj.x, xj.y, xj.z, pj.z * (pj.y - GB_OFFSET));
+            s_x[threadIdx.x] = make_float4(xj.x, xj.y, xj.z, pj.z * (pj.y - kc.offset));
             s_s[threadIdx.x] = pj.w != 0.f ? l : 1.f;
         }
         __syncthreads();
@@ -85,9 +130,11 @@ void gb_born_kernel(int N, int Npad, const float4* __restrict__ par, const float
         for (int k = w; k < jn; k += GB_WAVES) {
             if (j0 + k == i) continue;
             const float4 xj = s_x[k];
-            const float dx = xj.x - xi.x, dy = xj.y - xi.y, dz = xj.z - xi.z;
+            float dx, dy, dz, r2;
+            gb_vec<CUT>(xi, xj, L, dx, dy, dz, r2);
+            if (CUT == GB_CUT_PERIODIC && !(r2 < kc.cut2)) continue;
             float H, dH;
-            gb_H(sqrtf(dx * dx + dy * dy + dz * dz), or_i, xj.w, H, dH);
+            gb_H(sqrtf(r2), or_i, xj.w, H, dH);
             I += s_s[k] * H;
         }
     }
@@ -96,16 +143,14 @@ void gb_born_kernel(int N, int Npad, const float4* __restrict__ par, const float
     if (w == 0 && live) {
         I = 0.f;
         for (int q = 0; q < GB_WAVES; ++q) I += s_part[q][lane];
-        const float psi = I * or_i, th = tanhf(psi - 0.8f * psi * psi + 4.85f * psi * psi * psi);
-        const float B = 1.f / (1.f / or_i - th / pi.y);
-        born[(size_t)r * Npad + i] = make_float2(B, B * B * (1.f - th * th) * (1.f - 1.6f * psi + 14.55f * psi * psi) * or_i / pi.y);
+        born[(size_t)r * Npad + i] = gb_born_radius(I, or_i, pi.y, kc);
     }
 }
 
-template <bool ENERGY, bool FORCE>
+template <int CUT, bool ENERGY, bool FORCE>
 __global__ __launch_bounds__(GB_BLOCK)
-void gb_pair_kernel(int N, int Npad, float tau, int sasa, const float4* __restrict__ par, const float* __restrict__ lam, int lam_stride, const float4* __restrict__ pos,
-                    const float2* __restrict__ born, float* __restrict__ cfac, long long* __restrict__ force, double* __restrict__ epart, int n_tile)
+void gb_pair_kernel(int N, int Npad, gb_consts kc, float tau, int sasa, const float4* __restrict__ par, const float* __restrict__ lam, int lam_stride, const float4* __restrict__ pos,
+                    const float* __restrict__ box, const float2* __restrict__ born, float* __restrict__ cfac, long long* __restrict__ force, double* __restrict__ epart, int n_tile)
 {
     __shared__ float4 s_x[GB_BLOCK];       // x, y, z, B_j
     __shared__ float s_q[GB_BLOCK];        // s_j q_j
@@ -119,15 +164,16 @@ void gb_pair_kernel(int N, int Npad, float tau, int sasa, const float4* __restri
     const float4 xi = live ? P[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     const float4 pi = live ? par[i] : make_float4(0.f, 1.f, 0.f, 0.f);
     const float2 bi = live ? BR[i] : make_float2(1.f, 0.f);
+    const float4 L = gb_box<CUT>(box, r);
     const float si = pi.w != 0.f ? l : 1.f, Qi = si * pi.x;
     float fx = 0.f, fy = 0.f, fz = 0.f, dEdB = 0.f;
     double e = 0.0;
     if (live && w == 0) {
-        const float self = 0.5f * GB_KE * tau * si * pi.x * pi.x / bi.x;
+        const float self = 0.5f * kc.ke * tau * si * pi.x * pi.x / bi.x;
         dEdB += self / bi.x;
         if (ENERGY) e -= (double)self;
         if (sasa) {
-            const float rb = pi.y / bi.x, rb2 = rb * rb, rb6 = rb2 * rb2 * rb2, pre = si * GB_SA * (pi.y + 0.14f) * (pi.y + 0.14f);
+            const float rb = pi.y / bi.x, rb2 = rb * rb, rb6 = rb2 * rb2 * rb2, pre = si * kc.sa * (pi.y + kc.probe) * (pi.y + kc.probe);
             dEdB -= 6.f * pre * rb6 / bi.x;
             if (ENERGY) e += (double)(pre * rb6);
         }
@@ -145,10 +191,11 @@ void gb_pair_kernel(int N, int Npad, float tau, int sasa, const float4* __restri
         for (int k = w; k < jn; k += GB_WAVES) {
             if (j0 + k == i) continue;
             const float4 xj = s_x[k];
-            const float dx = xj.x - xi.x, dy = xj.y - xi.y, dz = xj.z - xi.z;
-            const float r2 = dx * dx + dy * dy + dz * dz;
+            float dx, dy, dz, r2;
+            gb_vec<CUT>(xi, xj, L, dx, dy, dz, r2);
+            if (CUT == GB_CUT_PERIODIC && !(r2 < kc.cut2)) continue;
             const float D = bi.x * xj.w, ex = __expf(-r2 / (4.f * D)), f2 = r2 + D * ex, inv_f = rsqrtf(f2);
-            const float QQ = GB_KE * tau * Qi * s_q[k];
+            const float QQ = kc.ke * tau * Qi * s_q[k];
             const float dEdf = QQ / f2;
             dEdB += dEdf * ex * (1.f + r2 / (4.f * D)) * 0.5f * inv_f * xj.w;
             if (FORCE) { const float gr = dEdf * (1.f - 0.25f * ex) * inv_f; fx += gr * dx; fy += gr * dy; fz += gr * dz; }
@@ -177,9 +224,10 @@ void gb_pair_kernel(int N, int Npad, float tau, int sasa, const float4* __restri
     }
 }
 
+template <int CUT>
 __global__ __launch_bounds__(GB_BLOCK)
-void gb_chain_kernel(int N, int Npad, const float4* __restrict__ par, const float* __restrict__ lam, int lam_stride, const float4* __restrict__ pos,
-                     const float* __restrict__ cfac, long long* __restrict__ force)
+void gb_chain_kernel(int N, int Npad, gb_consts kc, const float4* __restrict__ par, const float* __restrict__ lam, int lam_stride, const float4* __restrict__ pos,
+                     const float* __restrict__ box, const float* __restrict__ cfac, long long* __restrict__ force)
 {
     __shared__ float4 s_x[GB_BLOCK];       // x, y, z, or_j
     __shared__ float4 s_p[GB_BLOCK];       // sr_j, s_j, c_j, -
@@ -191,13 +239,14 @@ void gb_chain_kernel(int N, int Npad, const float4* __restrict__ par, const floa
     const bool live = i < N;
     const float4 xi = live ? P[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     const float4 pi = live ? par[i] : make_float4(0.f, 1.f, 0.f, 0.f);
-    const float or_i = pi.y - GB_OFFSET, sr_i = pi.z * or_i, si = pi.w != 0.f ? l : 1.f, ci = live ? Cf[i] : 0.f;
+    const float4 L = gb_box<CUT>(box, r);
+    const float or_i = pi.y - kc.offset, sr_i = pi.z * or_i, si = pi.w != 0.f ? l : 1.f, ci = live ? Cf[i] : 0.f;
     float fx = 0.f, fy = 0.f, fz = 0.f;
     for (int j0 = 0; j0 < N; j0 += GB_BLOCK) {
         __syncthreads();
         if (j0 + (int)threadIdx.x < N) {
             const float4 xj = P[j0 + threadIdx.x], pj = par[j0 + threadIdx.x];
-            const float orj = pj.y - GB_OFFSET;
+            const float orj = pj.y - kc.offset;
             s_x[threadIdx.x] = make_float4(xj.x, xj.y, xj.z, orj);
             s_p[threadIdx.x] = make_float4(pj.z * orj, pj.w != 0.f ? l : 1.f, Cf[j0 + threadIdx.x], 0.f);
         }
@@ -207,8 +256,10 @@ void gb_chain_kernel(int N, int Npad, const float4* __restrict__ par, const floa
         for (int k = w; k < jn; k += GB_WAVES) {
             if (j0 + k == i) continue;
             const float4 xj = s_x[k], pj = s_p[k];
-            const float dx = xj.x - xi.x, dy = xj.y - xi.y, dz = xj.z - xi.z;
-            const float rr = sqrtf(dx * dx + dy * dy + dz * dz);
+            float dx, dy, dz, r2;
+            gb_vec<CUT>(xi, xj, L, dx, dy, dz, r2);
+            if (CUT == GB_CUT_PERIODIC && !(r2 < kc.cut2)) continue;     // (out of range: neither I_i nor I_j holds the pair)
+            const float rr = sqrtf(r2);
             float H, dH1, dH2;
             gb_H(rr, or_i, pj.x, H, dH1);              // B_i depends on j
             gb_H(rr, xj.w, sr_i, H, dH2);              // B_j depends on i
@@ -242,7 +293,7 @@ void gb_reduce_kernel(int n, const double* __restrict__ part, double* __restrict
 // result does not depend on scheduling); Born radii, dE/dB and c_i stay in LDS between the three passes.
 template <bool ENERGY, bool FORCE>
 __global__ __launch_bounds__(1024)
-void gb_small_kernel(int N, int Npad, float tau, int sasa, const float4* __restrict__ par, const float* __restrict__ lam, int lam_stride, const float4* __restrict__ pos,
+void gb_small_kernel(int N, int Npad, gb_consts kc, float tau, int sasa, const float4* __restrict__ par, const float* __restrict__ lam, int lam_stride, const float4* __restrict__ pos,
                      long long* __restrict__ force, double* __restrict__ out, int out_stride, int out_offset, int add)
 {
     __shared__ float4 s_x[64];             // x, y, z, or_j
@@ -256,7 +307,7 @@ void gb_small_kernel(int N, int Npad, float tau, int sasa, const float4* __restr
     const float l = lam[(size_t)r * lam_stride];         // (stride 0: every replica at one state's lambda, a u_kl column)
     if (w == 0) {
         const float4 x = i < N ? P[i] : make_float4(0.f, 0.f, 0.f, 0.f), p = i < N ? par[i] : make_float4(0.f, 1.f, 0.f, 0.f);
-        const float orj = p.y - GB_OFFSET;
+        const float orj = p.y - kc.offset;
         s_x[i] = make_float4(x.x, x.y, x.z, orj);
         s_p[i] = make_float4(p.x, p.y, p.z * orj, p.w != 0.f ? l : 1.f);
     }
@@ -282,9 +333,7 @@ void gb_small_kernel(int N, int Npad, float tau, int sasa, const float4* __restr
     if (w == 0 && live) {
         float I = 0.f;
         for (int q = 0; q < 16; ++q) I += s_part[q][i].x;
-        const float psi = I * or_i, th = tanhf(psi - 0.8f * psi * psi + 4.85f * psi * psi * psi);
-        const float B = 1.f / (1.f / or_i - th / pi.y);
-        s_born[i] = make_float2(B, B * B * (1.f - th * th) * (1.f - 1.6f * psi + 14.55f * psi * psi) * or_i / pi.y);
+        s_born[i] = gb_born_radius(I, or_i, pi.y, kc);
     }
     __syncthreads();
     // pass 2: self + surface + pair energies, the pair term's direct force on i, dE/dB_i
@@ -295,11 +344,11 @@ void gb_small_kernel(int N, int Npad, float tau, int sasa, const float4* __restr
         float dEdB = 0.f;
         double e = 0.0;
         if (live && w == 0) {
-            const float self = 0.5f * GB_KE * tau * si * pi.x * pi.x / bi.x;
+            const float self = 0.5f * kc.ke * tau * si * pi.x * pi.x / bi.x;
             dEdB += self / bi.x;
             if (ENERGY) e -= (double)self;
             if (sasa) {
-                const float rb = pi.y / bi.x, rb2 = rb * rb, rb6 = rb2 * rb2 * rb2, pre = si * GB_SA * (pi.y + 0.14f) * (pi.y + 0.14f);
+                const float rb = pi.y / bi.x, rb2 = rb * rb, rb6 = rb2 * rb2 * rb2, pre = si * kc.sa * (pi.y + kc.probe) * (pi.y + kc.probe);
                 dEdB -= 6.f * pre * rb6 / bi.x;
                 if (ENERGY) e += (double)(pre * rb6);
             }
@@ -312,7 +361,7 @@ void gb_small_kernel(int N, int Npad, float tau, int sasa, const float4* __restr
                 const float dx = xj.x - xi.x, dy = xj.y - xi.y, dz = xj.z - xi.z;
                 const float r2 = dx * dx + dy * dy + dz * dz;
                 const float D = bi.x * Bj, ex = __expf(-r2 / (4.f * D)), f2 = r2 + D * ex, inv_f = rsqrtf(f2);
-                const float QQ = GB_KE * tau * Qi * (pj.w * pj.x);
+                const float QQ = kc.ke * tau * Qi * (pj.w * pj.x);
                 const float dEdf = QQ / f2;
                 dEdB += dEdf * ex * (1.f + r2 / (4.f * D)) * 0.5f * inv_f * Bj;
                 if (FORCE) { const float gr = dEdf * (1.f - 0.25f * ex) * inv_f; fx += gr * dx; fy += gr * dy; fz += gr * dz; }
@@ -374,6 +423,25 @@ void remd_gbsa_release(remd_ctx* h)
     h->gbsa = 0;
 }
 
+// OBC2 without a cutoff: the model remd_set_gbsa starts from (the constants of the factory's strings, alchemy.py:2192-2210)
+static remd_gb_model_desc gb_default_model()
+{
+    remd_gb_model_desc m{};
+    m.offset = 0.009; m.alpha = 1.0; m.beta = 0.8; m.gamma = 4.85; m.ke = 138.935485; m.surface = 28.3919551; m.probe = 0.14;
+    m.method = REMD_GB_NO_CUTOFF; m.cutoff = 0.0;
+    return m;
+}
+
+static void gb_take_model(gbsa_tables& t, const remd_gb_model_desc& m)
+{
+    t.model = m;
+    t.method = m.method == REMD_GB_CUTOFF_PERIODIC ? GB_CUT_PERIODIC : GB_CUT_NONE;
+    t.k.offset = (float)m.offset; t.k.alpha = (float)m.alpha; t.k.beta = (float)m.beta; t.k.gamma = (float)m.gamma;
+    t.k.d0 = (float)m.alpha; t.k.d1 = (float)(2.0 * m.beta); t.k.d2 = (float)(3.0 * m.gamma);
+    t.k.ke = (float)m.ke; t.k.sa = (float)m.surface; t.k.probe = (float)m.probe;
+    t.k.cut2 = t.method == GB_CUT_PERIODIC ? (float)(m.cutoff * m.cutoff) : 0.f;
+}
+
 int remd_set_gbsa(remd_handle h, const remd_gbsa_desc* d)
 {
     if (!h) return remd_fail(h, -1, "remd_set_gbsa: NULL handle");
@@ -383,12 +451,15 @@ int remd_set_gbsa(remd_handle h, const remd_gbsa_desc* d)
     h->config_version++;
     h->forces_valid = false;
     if (!d) return 0;
-    if (!h->has_system || !h->nocutoff) return remd_fail(h, -3, "remd_set_gbsa: GBSA needs a system with a NoCutoff NonbondedForce (call remd_set_system first)");
+    // a periodic system takes GB only with a CutoffPeriodic model (remd_set_gb_model, checked at every evaluation)
+    if (!h->has_system || !(h->nocutoff || h->nb_method != REMD_NB_NONE))
+        return remd_fail(h, -3, "remd_set_gbsa: GBSA needs a system with a NoCutoff NonbondedForce (call remd_set_system first)");
     if (d->n_atoms != h->N || !d->charge || !d->radius || !d->scale || !(d->solute_dielectric > 0) || !(d->solvent_dielectric > 0)) return remd_fail(h, -1, "remd_set_gbsa: bad arguments");
     gbsa_tables& t = g_gb[h];
     t.N = h->N; t.n_tile = (h->N + 63) / 64;
     t.tau = (float)(1.0 / d->solute_dielectric - 1.0 / d->solvent_dielectric);
     t.sasa = d->surface_area ? 1 : 0;
+    gb_take_model(t, gb_default_model());
     std::vector<float4> par(h->Npad, make_float4(0.f, 1.f, 0.f, 0.f));
     for (int i = 0; i < h->N; ++i) {
         if (!(d->radius[i] > 0.009)) { remd_gbsa_release(h); return remd_fail(h, -1, "remd_set_gbsa: radii must exceed the offset 0.009 nm"); }
@@ -408,12 +479,38 @@ int remd_set_gbsa(remd_handle h, const remd_gbsa_desc* d)
     return 0;
 }
 
+int remd_set_gb_model(remd_handle h, const remd_gb_model_desc* m)
+{
+    if (!h) return remd_fail(h, -1, "remd_set_gb_model: NULL handle");
+    gbsa_tables* tp = g_gb.find(h);
+    if (!tp || !h->gbsa) return remd_fail(h, -2, "remd_set_gb_model: no GBSA on this handle (call remd_set_gbsa first)");
+    const remd_gb_model_desc mm = m ? *m : gb_default_model();
+    if (!(mm.offset >= 0.0) || !std::isfinite(mm.alpha) || !std::isfinite(mm.beta) || !std::isfinite(mm.gamma) || !(mm.ke > 0.0) ||
+        !std::isfinite(mm.surface) || !std::isfinite(mm.probe))
+        return remd_fail(h, -1, "remd_set_gb_model: bad model constants");
+    if (mm.method != REMD_GB_NO_CUTOFF && mm.method != REMD_GB_CUTOFF_PERIODIC)
+        return remd_fail(h, -1, "remd_set_gb_model: method must be REMD_GB_NO_CUTOFF or REMD_GB_CUTOFF_PERIODIC");
+    if (mm.method == REMD_GB_CUTOFF_PERIODIC && (h->nocutoff || h->nb_method == REMD_NB_NONE || !(mm.cutoff > 0.0)))
+        return remd_fail(h, -1, "remd_set_gb_model: a CutoffPeriodic model needs a periodic system and a cutoff > 0");
+    if (mm.method == REMD_GB_NO_CUTOFF && !h->nocutoff)
+        return remd_fail(h, -1, "remd_set_gb_model: a NoCutoff model needs a NoCutoff system");
+    hipSetDevice(h->device);
+    hipStreamSynchronize(h->stream);
+    for (int i = 0; i < tp->N; ++i)
+        if (!(tp->st_radius.empty() || tp->st_radius[i] > mm.offset)) return remd_fail(h, -1, "remd_set_gb_model: radii must exceed the offset");
+    gb_take_model(*tp, mm);
+    h->config_version++;
+    h->forces_valid = false;
+    return 0;
+}
+
 // the implicit solvent of `parent` on one of its blocks (api.hip phase_children)
 int remd_gbsa_clone(remd_ctx* parent, remd_ctx* child)
 {
     gbsa_tables* t = g_gb.find(parent);
     if (!t || !parent->gbsa) return 0;
-    const int rc = remd_set_gbsa(child, &t->store);
+    int rc = remd_set_gbsa(child, &t->store);
+    if (!rc) rc = remd_set_gb_model(child, &t->model);
     if (rc) return remd_fail(parent, rc, std::string("phases: ") + child->err);
     return 0;
 }
@@ -449,37 +546,65 @@ static float gb_state_lambda(remd_ctx* h, int k)
     return (float)le;
 }
 
-// the one-launch kernel for up to 64 atoms (REMD_GB_SMALL=0: the three launches, for the A/B and the tests of the large path)
+// the one-launch kernel for up to 64 atoms without a cutoff (REMD_GB_SMALL=0: the three launches, for the A/B and the tests of the large path)
 static bool gb_small(const gbsa_tables& t)
 {
-    return t.N <= 64 && !(getenv("REMD_GB_SMALL") && atoi(getenv("REMD_GB_SMALL")) == 0);
+    return t.method == GB_CUT_NONE && t.N <= 64 && !(getenv("REMD_GB_SMALL") && atoi(getenv("REMD_GB_SMALL")) == 0);
 }
 
+// the three launches of one evaluation: I -> B, energies + dE/dB, the chain rule through B (no chain without forces)
+template <int CUT>
+static void gb_launch(remd_ctx* h, const gbsa_tables& t, const float* lam, int lam_stride, bool energy, bool force, long long* d_force)
+{
+    const dim3 grid(t.n_tile, h->R);
+    hipLaunchKernelGGL(gb_born_kernel<CUT>, grid, dim3(GB_BLOCK), 0, h->stream, t.N, h->Npad, t.k, t.d_par, lam, lam_stride, h->d_pos, h->d_box, t.d_born);
+    if (energy && force)
+        hipLaunchKernelGGL((gb_pair_kernel<CUT, true, true>), grid, dim3(GB_BLOCK), 0, h->stream, t.N, h->Npad, t.k, t.tau, t.sasa, t.d_par, lam, lam_stride, h->d_pos, h->d_box,
+                           t.d_born, t.d_c, d_force, t.d_epart, t.n_tile);
+    else if (force)
+        hipLaunchKernelGGL((gb_pair_kernel<CUT, false, true>), grid, dim3(GB_BLOCK), 0, h->stream, t.N, h->Npad, t.k, t.tau, t.sasa, t.d_par, lam, lam_stride, h->d_pos, h->d_box,
+                           t.d_born, t.d_c, d_force, (double*)nullptr, t.n_tile);
+    else
+        hipLaunchKernelGGL((gb_pair_kernel<CUT, true, false>), grid, dim3(GB_BLOCK), 0, h->stream, t.N, h->Npad, t.k, t.tau, t.sasa, t.d_par, lam, lam_stride, h->d_pos, h->d_box,
+                           t.d_born, t.d_c, (long long*)nullptr, t.d_epart, t.n_tile);
+    if (force)
+        hipLaunchKernelGGL(gb_chain_kernel<CUT>, grid, dim3(GB_BLOCK), 0, h->stream, t.N, h->Npad, t.k, t.d_par, lam, lam_stride, h->d_pos, h->d_box, t.d_c, d_force);
+}
+
+static int gb_check_method(remd_ctx* h, const gbsa_tables& t)
+{
+    if (t.method == GB_CUT_NONE && !h->nocutoff)
+        return remd_fail(h, -3, "GBSA on a periodic system needs a CutoffPeriodic model (remd_set_gb_model)");
+    return 0;
+}
+
+// ep_slot: the energy slot of a NoCutoff system (written); a periodic system's GB energy is ADDED to the slot before the last, the one of
+// the custom forces of general alchemical regions -- written earlier on this stream, zero without them -- so that no slot of the
+// cutoff pair kernels is touched
 int remd_gbsa_forces(remd_ctx* h, bool with_energy, int ep_slot)
 {
     gbsa_tables* tp = g_gb.find(h);
     if (!tp) return remd_fail(h, -2, "GBSA: no tables on this handle");
     gbsa_tables& t = *tp;
-    int rc = gb_buffers(h, t);
+    int rc = gb_check_method(h, t);
     if (rc) return rc;
+    if ((rc = gb_buffers(h, t))) return rc;
     std::vector<float> lam(h->R, 1.f);
     if (t.any_alch) for (int r = 0; r < h->R; ++r) lam[r] = gb_state_lambda(h, h->labels.empty() ? 0 : (int)h->labels[h->r_begin + r]);
     if ((rc = gb_set_lambdas(h, t, lam))) return rc;
     remd_prof_scope ps(h, "gbsa");
     if (gb_small(t)) {
-        if (with_energy) hipLaunchKernelGGL((gb_small_kernel<true, true>), dim3(h->R), dim3(1024), 0, h->stream, t.N, h->Npad, t.tau, t.sasa, t.d_par, t.d_lam, 1, h->d_pos, h->d_force, h->d_epart, h->n_epart, ep_slot, 0);
-        else hipLaunchKernelGGL((gb_small_kernel<false, true>), dim3(h->R), dim3(1024), 0, h->stream, t.N, h->Npad, t.tau, t.sasa, t.d_par, t.d_lam, 1, h->d_pos, h->d_force, (double*)nullptr, 0, 0, 0);
+        if (with_energy) hipLaunchKernelGGL((gb_small_kernel<true, true>), dim3(h->R), dim3(1024), 0, h->stream, t.N, h->Npad, t.k, t.tau, t.sasa, t.d_par, t.d_lam, 1, h->d_pos, h->d_force, h->d_epart, h->n_epart, ep_slot, 0);
+        else hipLaunchKernelGGL((gb_small_kernel<false, true>), dim3(h->R), dim3(1024), 0, h->stream, t.N, h->Npad, t.k, t.tau, t.sasa, t.d_par, t.d_lam, 1, h->d_pos, h->d_force, (double*)nullptr, 0, 0, 0);
         REMD_CHECK(h, hipGetLastError());
         return 0;
     }
-    const dim3 grid(t.n_tile, h->R);
-    hipLaunchKernelGGL(gb_born_kernel, grid, dim3(GB_BLOCK), 0, h->stream, t.N, h->Npad, t.d_par, t.d_lam, 1, h->d_pos, t.d_born);
+    if (t.method == GB_CUT_PERIODIC) gb_launch<GB_CUT_PERIODIC>(h, t, t.d_lam, 1, with_energy, true, h->d_force);
+    else gb_launch<GB_CUT_NONE>(h, t, t.d_lam, 1, with_energy, true, h->d_force);
     if (with_energy) {
-        hipLaunchKernelGGL((gb_pair_kernel<true, true>), grid, dim3(GB_BLOCK), 0, h->stream, t.N, h->Npad, t.tau, t.sasa, t.d_par, t.d_lam, 1, h->d_pos, t.d_born, t.d_c, h->d_force, t.d_epart, t.n_tile);
-        hipLaunchKernelGGL(gb_reduce_kernel, dim3(h->R), dim3(64), 0, h->stream, t.n_tile, t.d_epart, h->d_epart, h->n_epart, ep_slot, 0);
-    } else
-        hipLaunchKernelGGL((gb_pair_kernel<false, true>), grid, dim3(GB_BLOCK), 0, h->stream, t.N, h->Npad, t.tau, t.sasa, t.d_par, t.d_lam, 1, h->d_pos, t.d_born, t.d_c, h->d_force, (double*)nullptr, t.n_tile);
-    hipLaunchKernelGGL(gb_chain_kernel, grid, dim3(GB_BLOCK), 0, h->stream, t.N, h->Npad, t.d_par, t.d_lam, 1, h->d_pos, t.d_c, h->d_force);
+        const bool periodic = t.method == GB_CUT_PERIODIC;
+        hipLaunchKernelGGL(gb_reduce_kernel, dim3(h->R), dim3(64), 0, h->stream, t.n_tile, t.d_epart, h->d_epart, h->n_epart, periodic ? h->n_epart - 2 : ep_slot, periodic ? 1 : 0);
+    }
     REMD_CHECK(h, hipGetLastError());
     return 0;
 }
@@ -490,9 +615,9 @@ int remd_gbsa_ukl(remd_ctx* h, double* d_alch)
     gbsa_tables* tp = g_gb.find(h);
     if (!tp || !tp->any_alch) return 0;
     gbsa_tables& t = *tp;
-    int rc = gb_buffers(h, t);
+    int rc = gb_check_method(h, t);
     if (rc) return rc;
-    const dim3 grid(t.n_tile, h->R);
+    if ((rc = gb_buffers(h, t))) return rc;
     // the states' lambdas on the device (uploaded when they change: one synchronisation then, none per column)
     {
         std::vector<float> sl(h->K);
@@ -506,12 +631,11 @@ int remd_gbsa_ukl(remd_ctx* h, double* d_alch)
     }
     for (int k = 0; k < h->K; ++k) {
         if (gb_small(t)) {
-            hipLaunchKernelGGL((gb_small_kernel<true, false>), dim3(h->R), dim3(1024), 0, h->stream, t.N, h->Npad, t.tau, t.sasa, t.d_par, t.d_state_lam + k, 0, h->d_pos, (long long*)nullptr, d_alch, h->K, k, 1);
+            hipLaunchKernelGGL((gb_small_kernel<true, false>), dim3(h->R), dim3(1024), 0, h->stream, t.N, h->Npad, t.k, t.tau, t.sasa, t.d_par, t.d_state_lam + k, 0, h->d_pos, (long long*)nullptr, d_alch, h->K, k, 1);
             continue;
         }
-        hipLaunchKernelGGL(gb_born_kernel, grid, dim3(GB_BLOCK), 0, h->stream, t.N, h->Npad, t.d_par, t.d_state_lam + k, 0, h->d_pos, t.d_born);
-        hipLaunchKernelGGL((gb_pair_kernel<true, false>), grid, dim3(GB_BLOCK), 0, h->stream, t.N, h->Npad, t.tau, t.sasa, t.d_par, t.d_state_lam + k, 0, h->d_pos, t.d_born, t.d_c,
-                           (long long*)nullptr, t.d_epart, t.n_tile);
+        if (t.method == GB_CUT_PERIODIC) gb_launch<GB_CUT_PERIODIC>(h, t, t.d_state_lam + k, 0, true, false, nullptr);
+        else gb_launch<GB_CUT_NONE>(h, t, t.d_state_lam + k, 0, true, false, nullptr);
         hipLaunchKernelGGL(gb_reduce_kernel, dim3(h->R), dim3(64), 0, h->stream, t.n_tile, t.d_epart, d_alch, h->K, k, 1);
     }
     REMD_CHECK(h, hipGetLastError());

@@ -1240,7 +1240,7 @@ static int remd_run_steps_resident(remd_ctx* h, const std::vector<char>& tokens,
 {
     const bool enabled = !(getenv("REMD_RESIDENT") && atoi(getenv("REMD_RESIDENT")) == 0);      // read per call: the parity tests switch it
     if (!enabled || h->no_resident) return 0;
-    if (h->N > 1024 || h->n_settle > 0 || h->n_shake > 0 || h->n_bonds > 0 || h->n_angles > 0 || h->n_torsions > 0 || h->n_restraints > 0) return 0;
+    if (h->N > 1024 || h->n_settle > 0 || h->n_shake > 0 || h->n_bonds > 0 || h->n_angles > 0 || h->n_torsions > 0 || h->n_restraints > 0 || h->gbsa) return 0;
     if (h->baro_frequency > 0 || h->profiling == 2 || (int)tokens.size() > MAX_TOK || n_steps < 1) return 0;
     if (h->measure_heat || h->measure_shadow) return 0;
     for (char c : tokens) if (c != 'V' && c != 'R' && c != 'O') return 0;

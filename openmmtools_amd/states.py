@@ -565,6 +565,9 @@ class GlobalParameterState:
             for parameter_id in range(n_global_parameters):
                 parameter_name = force.getGlobalParameterName(parameter_id)
                 if parameter_name in searched_parameters:
+                    if type(force).__name__ == 'CustomGBForce':      # the engine reads a CustomGBForce's globals at their default values
+                        raise cls._GLOBAL_PARAMETER_ERROR('global parameter {} of a CustomGBForce cannot be controlled by a '
+                                                          'state'.format(parameter_name))
                     yield force, parameter_name, parameter_id
 
     def __getstate__(self):

@@ -233,6 +233,64 @@ class GBSAOBCForce(Force):
     def setNonbondedMethod(self, m): self._method = int(m)
 
 
+class CustomGBForce(Force):
+    """openmm.CustomGBForce: per-particle parameters, global parameters, computed values and energy terms given as expression strings.
+    The engine evaluates only the OBC family (openmmtools_amd/custom_gb.py recognises it: the CustomGBForceSystem strings of
+    testsystems.py:4332-4351, the alchemical factory's GBSA strings, and both after _alchemically_modify_CustomGBForce), with
+    NoCutoff or CutoffPeriodic; system_to_desc refuses everything else with NotImplementedError."""
+    NoCutoff, CutoffNonPeriodic, CutoffPeriodic = 0, 1, 2
+    SingleParticle, ParticlePair, ParticlePairNoExclusions = 0, 1, 2
+
+    def __init__(self):
+        super().__init__()
+        self.per_particle = []              # names
+        self.globals = []                   # [name, default]
+        self.computed = []                  # (name, expression, type)
+        self.energy_terms = []              # (expression, type)
+        self.particles = []                 # tuples of floats
+        self.exclusions = []                # (i, j)
+        self.functions = []                 # (name, function): tabulated functions (refused by the engine)
+        self._method, self._cutoff = 0, 1.0
+
+    def addPerParticleParameter(self, name):
+        self.per_particle.append(str(name)); return len(self.per_particle) - 1
+    def getNumPerParticleParameters(self): return len(self.per_particle)
+    def getPerParticleParameterName(self, idx): return self.per_particle[idx]
+    def addGlobalParameter(self, name, defaultValue):
+        self.globals.append([str(name), float(defaultValue)]); return len(self.globals) - 1
+    def getNumGlobalParameters(self): return len(self.globals)
+    def getGlobalParameterName(self, idx): return self.globals[idx][0]
+    def getGlobalParameterDefaultValue(self, idx): return self.globals[idx][1]
+    def setGlobalParameterDefaultValue(self, idx, defaultValue): self.globals[idx][1] = float(defaultValue)
+    def addComputedValue(self, name, expression, computationType):
+        self.computed.append((str(name), str(expression), int(computationType))); return len(self.computed) - 1
+    def getNumComputedValues(self): return len(self.computed)
+    def getComputedValueParameters(self, idx): return self.computed[idx]
+    def addEnergyTerm(self, expression, computationType):
+        self.energy_terms.append((str(expression), int(computationType))); return len(self.energy_terms) - 1
+    def getNumEnergyTerms(self): return len(self.energy_terms)
+    def getEnergyTermParameters(self, idx): return self.energy_terms[idx]
+    def addParticle(self, parameters=()):
+        self.particles.append(tuple(float(v) for v in parameters)); return len(self.particles) - 1
+    def getNumParticles(self): return len(self.particles)
+    def getParticleParameters(self, idx): return list(self.particles[idx])
+    def setParticleParameters(self, idx, parameters): self.particles[idx] = tuple(float(v) for v in parameters)
+    def addExclusion(self, particle1, particle2):
+        self.exclusions.append((int(particle1), int(particle2))); return len(self.exclusions) - 1
+    def getNumExclusions(self): return len(self.exclusions)
+    def getExclusionParticles(self, idx): return list(self.exclusions[idx])
+    def addTabulatedFunction(self, name, function):
+        self.functions.append((str(name), function)); return len(self.functions) - 1
+    def getNumTabulatedFunctions(self): return len(self.functions)
+    def getTabulatedFunctionName(self, idx): return self.functions[idx][0]
+    def getTabulatedFunction(self, idx): return self.functions[idx][1]
+    def getNonbondedMethod(self): return self._method
+    def setNonbondedMethod(self, m): self._method = int(m)
+    def getCutoffDistance(self): return self._cutoff
+    def setCutoffDistance(self, d): self._cutoff = float(d)
+    def usesPeriodicBoundaryConditions(self): return self._method == CustomGBForce.CutoffPeriodic
+
+
 class CMMotionRemover(Force):
     def __init__(self, frequency=1):
         super().__init__()
@@ -466,7 +524,9 @@ def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
             nb = f
         elif isinstance(f, CMMotionRemover):
             cmm = f.frequency
-        elif isinstance(f, GBSAOBCForce):
+        elif isinstance(f, (GBSAOBCForce, CustomGBForce)):
+            if gb is not None:
+                raise NotImplementedError('more than one implicit-solvent force (%s and %s)' % (type(gb).__name__, type(f).__name__))
             gb = f
         elif _is_restraint(f):
             from .forces import restraint_terms
@@ -543,7 +603,13 @@ def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
         d['alch_atoms'] = np.zeros(0, np.int32)
         d['softcore'] = (0.5, 1.0, 1.0, 6.0)
         d['annihilate_sterics'] = False
-    if gb is not None:
+    if isinstance(gb, CustomGBForce):
+        # a CustomGBForce of the OBC family: remd_set_gbsa + remd_set_gb_model (include/remd_hip_gb.h)
+        from .custom_gb import custom_gb_to_desc
+        if box is None:
+            box = np.diag(system.getDefaultPeriodicBoxVectors())
+        d['gbsa'] = custom_gb_to_desc(gb, n, d['nb_method'], box)
+    elif gb is not None:
         # implicit solvent: remd_set_gbsa (csrc/gbsa.hip).  The surface term is the ACE one with OpenMM's default energy (28.3919551 = 4 pi x
         # 2.25936 kJ/mol/nm^2 in the factory's expression, alchemy.py:2207); 0 switches it off
         if d['nb_method'] != 3 or gb.getNonbondedMethod() != GBSAOBCForce.NoCutoff:
@@ -557,9 +623,10 @@ def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
         regions = getattr(system, 'alchemical_regions', None)
         if regions is not None:                       # the factory's alchemical GBSA: one region (alchemy.py:2168-2171)
             alch[regions[0].alchemical_atoms] = 1
+        from .custom_gb import OBC2_MODEL
         d['gbsa'] = dict(charge=gp[:, 0].copy(), radius=gp[:, 1].copy(), scale=gp[:, 2].copy(), alchemical=alch,
                          solute_dielectric=gb.getSoluteDielectric(), solvent_dielectric=gb.getSolventDielectric(),
-                         surface_area=int(gb.getSurfaceAreaEnergy() != 0.0))
+                         surface_area=int(gb.getSurfaceAreaEnergy() != 0.0), **OBC2_MODEL)
     if getattr(system, 'rf_unshifted_switch_width', None) is not None and d['nb_method'] == 1:
         # the reaction field as the alchemical factory re-writes it for the WHOLE system (alchemical_rf_treatment='switched'): remd_set_reaction_field
         d['rf_unshifted_switch_width'] = float(system.rf_unshifted_switch_width)

@@ -21,7 +21,7 @@ other NonbondedForce parameter offsets) raise ``NotImplementedError`` naming the
 import xml.etree.ElementTree as ET
 
 from .system import (System, HarmonicBondForce, HarmonicAngleForce, PeriodicTorsionForce, NonbondedForce, GBSAOBCForce,
-                     CustomExternalForce, CMMotionRemover)
+                     CustomExternalForce, CMMotionRemover, CustomGBForce)
 
 
 def _f(x):
@@ -93,10 +93,68 @@ def _emit_force(forces, f, force_group=None, particles=None, exceptions=None, gl
         b = ET.SubElement(e, 'Particles')
         for (q, r, sc) in f.particles:
             ET.SubElement(b, 'Particle', dict(q=_f(q), r=_f(r), scale=_f(sc)))
+    elif isinstance(f, CustomGBForce):
+        emit_custom_gb_force(forces, f, int(common['forceGroup']))
     elif _is_restraint(f):
         _emit_restraint(forces, f)
     else:
         raise NotImplementedError('unsupported force %r' % name)
+
+
+def emit_custom_gb_force(forces, f, group):
+    """A CustomGBForce in the layout of OpenMM's CustomGBForceProxy: attributes method, cutoff, forceGroup; sections GlobalParameters,
+    PerParticleParameters, ComputedValues, EnergyTerms, Particles, Exclusions, Functions (external knowledge, like the other proxies)"""
+    if f.getNumTabulatedFunctions():
+        raise NotImplementedError('CustomGBForce with tabulated functions')
+    e = ET.SubElement(forces, 'Force', dict(cutoff=_f(f.getCutoffDistance()), forceGroup=str(group), method=str(f.getNonbondedMethod()),
+                                            name='CustomGBForce', type='CustomGBForce', version='3'))
+    b = ET.SubElement(e, 'PerParticleParameters')
+    for n in f.per_particle:
+        ET.SubElement(b, 'Parameter', dict(name=n))
+    b = ET.SubElement(e, 'GlobalParameters')
+    for n, v in f.globals:
+        ET.SubElement(b, 'Parameter', dict(default=_f(v), name=n))
+    ET.SubElement(e, 'EnergyParameterDerivatives')
+    b = ET.SubElement(e, 'ComputedValues')
+    for n, expr, kind in f.computed:
+        ET.SubElement(b, 'Value', dict(expression=expr, name=n, type=str(kind)))
+    b = ET.SubElement(e, 'EnergyTerms')
+    for expr, kind in f.energy_terms:
+        ET.SubElement(b, 'Term', dict(expression=expr, type=str(kind)))
+    b = ET.SubElement(e, 'Particles')
+    for p in f.particles:
+        ET.SubElement(b, 'Particle', {'param%d' % (k + 1): _f(v) for k, v in enumerate(p)})
+    b = ET.SubElement(e, 'Exclusions')
+    for i, j in f.exclusions:
+        ET.SubElement(b, 'Exclusion', dict(p1=str(i), p2=str(j)))
+    ET.SubElement(e, 'Functions')
+    return e
+
+
+def parse_custom_gb_force(e):
+    """the CustomGBForce of a <Force type="CustomGBForce"> element; NotImplementedError for tabulated functions"""
+    f = CustomGBForce()
+    f.setNonbondedMethod(int(e.get('method', '0')))
+    f.setCutoffDistance(float(e.get('cutoff', '1')))
+    f.setForceGroup(int(e.get('forceGroup', '0')))
+    for p in _children(e, 'PerParticleParameters', 'Parameter'):
+        f.addPerParticleParameter(p.get('name'))
+    for p in _children(e, 'GlobalParameters', 'Parameter'):
+        f.addGlobalParameter(p.get('name'), float(p.get('default')))
+    for v in _children(e, 'ComputedValues', 'Value'):
+        f.addComputedValue(v.get('name'), v.get('expression'), int(v.get('type')))
+    for t in _children(e, 'EnergyTerms', 'Term'):
+        f.addEnergyTerm(t.get('expression'), int(t.get('type')))
+    for p in _children(e, 'Particles', 'Particle'):
+        params, k = [], 1
+        while p.get('param%d' % k) is not None:
+            params.append(float(p.get('param%d' % k))); k += 1
+        f.addParticle(params)
+    for x in _children(e, 'Exclusions', 'Exclusion'):
+        f.addExclusion(int(x.get('p1')), int(x.get('p2')))
+    if _nonempty(e, 'Functions'):
+        raise NotImplementedError('CustomGBForce: tabulated functions')
+    return f
 
 
 def _is_restraint(f):
@@ -290,10 +348,18 @@ def from_xml(text_or_path):
             from . import _alchemical_xml
             customs.append(_alchemical_xml.parse_custom(e))        # only as the pieces of an alchemically modified System
             continue
-        elif kind == 'CustomGBForce' and e.find('ComputedValues') is not None:
+        elif kind == 'CustomGBForce':
             from . import _alchemical_xml
-            customs.append(_alchemical_xml.parse_custom_gb(e))     # the alchemical factory's GBSA (alchemy.py:2172-2225)
-            continue
+            from .custom_gb import is_alchemically_modified, recognize_custom_gb
+            f = parse_custom_gb_force(e)
+            if _alchemical_xml.is_factory_gbsa(f):
+                customs.append(_alchemical_xml.parse_custom_gb(e))     # the alchemical factory's GBSA (alchemy.py:2172-2225)
+                continue
+            if is_alchemically_modified(f):                           # _alchemically_modify_CustomGBForce's rewrite (alchemy.py:2223-2345)
+                recognize_custom_gb(f)
+                customs.append(dict(type='CustomGBForce', energy='', group=f.getForceGroup(), force=f))
+                continue
+            recognize_custom_gb(f)                                    # refuses what the engine cannot evaluate, naming the term
         elif kind == 'CustomExternalForce':
             if _nonempty(e, 'PerParticleParameters'):
                 raise NotImplementedError('CustomExternalForce with per-particle parameters')

@@ -271,3 +271,61 @@ class HostGuestExplicit(_AmberExplicit):
 class DHFRExplicit(_AmberExplicit):
     """testsystems.py:3863-3923: DHFR (JAC benchmark), 23558 atoms, positions and velocities from JAC.inpcrd."""
     _name = 'dhfr-explicit'
+
+
+class CustomGBForceSystem(TestSystem):
+    """A periodic system of ions with a CustomGBForce (testsystems.py:4279-4389, after OpenMM's TestReferenceCustomGBForce.cpp): 70 pairs
+    of +1 / -1 particles of 39.9 amu in a 10 nm box, a CutoffPeriodic NonbondedForce and an OBC2 CustomGBForce, both with a 2 nm cutoff;
+    radius 0.2 / 0.1 nm, scale 0.5 for the first half of the particles and 0.8 for the rest; Sobol' positions."""
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        from .system import CustomGBForce
+        n_molecules = 70
+        n_particles = n_molecules * 2
+        box_size = 10.0 * unit.nanometers
+        mass = 39.9 * unit.amu
+        sigma = 3.350 * unit.angstrom
+        epsilon = 0.001603 * unit.kilojoule_per_mole
+        cutoff = 2.0 * unit.nanometers
+        system = System()
+        for _ in range(n_particles):
+            system.addParticle(mass)
+        system.setDefaultPeriodicBoxVectors([box_size, 0.0, 0.0], [0.0, box_size, 0.0], [0.0, 0.0, box_size])
+        nonbonded = NonbondedForce()
+        nonbonded.setNonbondedMethod(NonbondedForce.CutoffPeriodic)
+        nonbonded.setCutoffDistance(cutoff)
+        custom = CustomGBForce()
+        custom.setNonbondedMethod(CustomGBForce.CutoffPeriodic)
+        custom.setCutoffDistance(cutoff)
+        custom.addPerParticleParameter("charge")
+        custom.addPerParticleParameter("radius")
+        custom.addPerParticleParameter("scale")
+        custom.addGlobalParameter("testsystems_CustomGBForceSystem_solventDielectric", 80.0)
+        custom.addGlobalParameter("testsystems_CustomGBForceSystem_soluteDielectric", 1.0)
+        custom.addComputedValue("I", "step(r+sr2-or1)*0.5*(1/L-1/U+0.25*(1/U^2-1/L^2)*(r-sr2*sr2/r)+0.5*log(L/U)/r+C);"
+                                "U=r+sr2;"
+                                "C=2*(1/or1-1/L)*step(sr2-r-or1);"
+                                "L=max(or1, D);"
+                                "D=abs(r-sr2);"
+                                "sr2 = scale2*or2;"
+                                "or1 = radius1-0.009; or2 = radius2-0.009", CustomGBForce.ParticlePairNoExclusions)
+        custom.addComputedValue("B", "1/(1/or-tanh(1*psi-0.8*psi^2+4.85*psi^3)/radius);"
+                                "psi=I*or; or=radius-0.009", CustomGBForce.SingleParticle)
+        energy_expression = '28.3919551*(radius+0.14)^2*(radius/B)^6-0.5*138.935485*(1/soluteDielectric-1/solventDielectric)*charge^2/B;'
+        energy_expression += 'solventDielectric = testsystems_CustomGBForceSystem_solventDielectric;'
+        energy_expression += 'soluteDielectric = testsystems_CustomGBForceSystem_soluteDielectric;'
+        custom.addEnergyTerm(energy_expression, CustomGBForce.SingleParticle)
+        energy_expression = '-138.935485*(1/soluteDielectric-1/solventDielectric)*charge1*charge2/f;'
+        energy_expression += 'f=sqrt(r^2+B1*B2*exp(-r^2/(4*B1*B2)));'
+        energy_expression += 'solventDielectric = testsystems_CustomGBForceSystem_solventDielectric;'
+        energy_expression += 'soluteDielectric = testsystems_CustomGBForceSystem_soluteDielectric;'
+        custom.addEnergyTerm(energy_expression, CustomGBForce.ParticlePairNoExclusions)
+        for i in range(n_molecules):
+            scale = 0.5 if i < n_molecules / 2 else 0.8
+            for charge, radius in ((1.0 * unit.elementary_charge, 0.2 * unit.nanometers), (-1.0 * unit.elementary_charge, 0.1 * unit.nanometers)):
+                nonbonded.addParticle(charge, sigma, epsilon)
+                custom.addParticle([charge, radius, scale])
+        system.addForce(nonbonded)
+        system.addForce(custom)
+        self.system, self.positions = system, subrandom_particle_positions(n_particles, system.getDefaultPeriodicBoxVectors())
