@@ -51,6 +51,39 @@ const char* remd_last_error(remd_handle h)
     return copy.c_str();
 }
 
+// the environment switches of a new handle (remd_internal.h: remd_switches); the only place in the engine that reads them
+static void read_switches(remd_switches& sw)
+{
+    auto flag = [](const char* name, bool def) { const char* e = getenv(name); return e ? atoi(e) != 0 : def; };
+    auto num = [](const char* name, int def) { const char* e = getenv(name); return e ? atoi(e) : def; };
+    auto at_least_1 = [](const char* name, int def) { const char* e = getenv(name); return e ? std::max(1, atoi(e)) : def; };
+    auto pin = [](const char* name) { const char* e = getenv(name); const int v = e ? atoi(e) : -1; return v < 0 ? -1 : v != 0 ? 1 : 0; };
+    auto set = [](const char* name) { return getenv(name) != nullptr; };
+    sw.overlap = flag("REMD_OVERLAP", true);
+    sw.phases = num("REMD_PHASES", -1);
+    sw.resident = flag("REMD_RESIDENT", true);
+    sw.resident_cap = at_least_1("REMD_RESIDENT_CAP", 0);
+    sw.chain_merge = flag("REMD_CHAIN_MERGE", true);
+    sw.nb_tiles = set("REMD_NB_TILES");
+    sw.nb_persist_grid = num("REMD_NB_PERSIST_GRID", -1);
+    sw.nb_prio = pin("REMD_NB_PRIO");
+    sw.nb_fold = flag("REMD_NB_FOLD", true);
+    sw.listed_atoms = flag("REMD_LISTED_ATOMS", true);
+    sw.listed_main = flag("REMD_LISTED_MAIN", true);
+    sw.listed_ride = flag("REMD_LISTED_RIDE", true);
+    sw.pme_chainbin = pin("REMD_PME_CHAINBIN");
+    sw.pme_cbin_cap = at_least_1("REMD_PME_CBIN_CAP", 0);
+    sw.pme_pow2 = num("REMD_PME_POW2", 3);
+    sw.pme_fbin = flag("REMD_PME_FBIN", true);
+    sw.gb_small = flag("REMD_GB_SMALL", true);
+    sw.mix_flow = pin("REMD_MIX_FLOW");
+    sw.mix_pre = flag("REMD_MIX_PRE", true);
+    sw.debug = set("REMD_DEBUG");
+    sw.nb_tune_verbose = set("REMD_NB_TUNE_VERBOSE");
+    sw.many_verbose = set("REMD_MANY_VERBOSE");
+    sw.prof_every = at_least_1("REMD_PROF_EVERY", 16);
+}
+
 int remd_create(remd_handle* out, int device, void* stream)
 {
     if (!out) return remd_fail(nullptr, -1, "remd_create: out is NULL");
@@ -64,35 +97,13 @@ int remd_create(remd_handle* out, int device, void* stream)
     remd_ctx* h = new remd_ctx();
     h->device = device;
     h->stream = (hipStream_t)stream;
-    // Spatial partition of the chip between the two streams of a force evaluation (experiment, profiles/r04_cumask_sweep.txt):
-    // REMD_CU_PAIR = n restricts the direct-space stream to n of the 256 CUs, REMD_CU_MESH = m the handle's own main stream
-    // (only when the caller passed none) to m CUs taken from the other end.  REMD_CU_LAYOUT: 0 = mask bit b is CU b as the
-    // runtime numbers them (KFD deals consecutive bits round-robin to the 8 XCDs), 1 = bit b is CU (b % 32) of XCD (b / 32).
-    auto cu_mask = [](int n, bool from_top, uint32_t* m) {
-        const int layout = getenv("REMD_CU_LAYOUT") ? atoi(getenv("REMD_CU_LAYOUT")) : 0;
-        for (int w = 0; w < 8; ++w) m[w] = 0u;
-        n = std::max(8, std::min(256, n));
-        for (int k = 0; k < n; ++k) {
-            int b;
-            if (layout == 0) b = from_top ? 255 - k : k;
-            else { const int xcd = k % 8, cu = k / 8; b = xcd * 32 + (from_top ? 31 - cu : cu); }
-            m[b >> 5] |= 1u << (b & 31);
-        }
-    };
-    const int cu_pair = getenv("REMD_CU_PAIR") ? atoi(getenv("REMD_CU_PAIR")) : 0;
-    const int cu_mesh = getenv("REMD_CU_MESH") ? atoi(getenv("REMD_CU_MESH")) : 0;
-    if (!h->stream && cu_mesh > 0) {
-        uint32_t m[8]; cu_mask(cu_mesh, false, m);
-        if (hipExtStreamCreateWithCUMask(&h->stream, 8, m) == hipSuccess) h->owns_stream = true; else { h->stream = nullptr; (void)hipGetLastError(); }
-    }
+    read_switches(h->sw);
+    // (Measured and removed: the two streams restricted to CU masks, profiles/r04_cumask_sweep.txt; the main stream at raised queue
+    // priority and the direct-space stream at normal priority, profiles/r06_13_stream_priorities.txt.)
     if (!h->stream) {
         // NULL: a private non-blocking stream (the legacy default stream cannot be captured into a graph, and every entry point
         // that hands results to the caller synchronises before it returns, so nothing relies on default-stream ordering)
-        // (REMD_MAIN_PRIO=1: the private main stream at raised queue priority -- experiment hook, profiles/r06_13_stream_priorities.txt)
-        int lo0 = 0, hi0 = 0;
-        hipDeviceGetStreamPriorityRange(&lo0, &hi0);
-        const bool main_hi = getenv("REMD_MAIN_PRIO") && atoi(getenv("REMD_MAIN_PRIO")) != 0;
-        if ((main_hi ? hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, hi0) : hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) {
+        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
             delete h; return remd_fail(nullptr, -2, "hipStreamCreate failed");
         }
         h->owns_stream = true;
@@ -102,18 +113,11 @@ int remd_create(remd_handle* out, int device, void* stream)
         // second stream: carries the direct-space kernels while the (longer) reciprocal-space chain stays on the main one
         int lo = 0, hi = 0;
         hipDeviceGetStreamPriorityRange(&lo, &hi);
-        if (cu_pair > 0) {
-            uint32_t m[8]; cu_mask(cu_pair, true, m);
-            if (hipExtStreamCreateWithCUMask(&h->stream2, 8, m) != hipSuccess) { h->stream2 = nullptr; (void)hipGetLastError(); }
-        }
-        const bool direct_lo = getenv("REMD_DIRECT_PRIO") && atoi(getenv("REMD_DIRECT_PRIO")) == 0;      // (experiment hook: normal priority)
-        if (!h->stream2 && (direct_lo || hipStreamCreateWithPriority(&h->stream2, hipStreamNonBlocking, hi) != hipSuccess))
+        if (hipStreamCreateWithPriority(&h->stream2, hipStreamNonBlocking, hi) != hipSuccess)
             hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking);
     }
     { const unsigned evf = hipEventReleaseToDevice | hipEventDisableTiming;   // device-scope release: no system-scope cache write-back per fork / join
       hipEventCreateWithFlags(&h->ev_fork, evf); hipEventCreateWithFlags(&h->ev_join, evf); }
-    { const char* env = getenv("REMD_OVERLAP"); h->overlap = !(env && atoi(env) == 0); }
-    h->sync_events = getenv("REMD_SYNC_EVENTS") && atoi(getenv("REMD_SYNC_EVENTS")) != 0;
     if (hipMalloc(&h->d_chain_own, 40 * sizeof(unsigned long long)) == hipSuccess) hipMemset(h->d_chain_own, 0, 40 * sizeof(unsigned long long));
     if (hipMalloc(&h->d_sync, 4 * sizeof(unsigned int)) != hipSuccess || hipMemset(h->d_sync, 0, 4 * sizeof(unsigned int)) != hipSuccess) {
         delete h; return remd_fail(nullptr, -2, "remd_create: hipMalloc failed");
@@ -157,7 +161,6 @@ int remd_destroy(remd_handle h)
     if (h->stream2 && !h->borrowed_stream2) { hipStreamSynchronize(h->stream2); hipStreamDestroy(h->stream2); }
     if (h->owns_stream && h->stream) hipStreamDestroy(h->stream);
     if (h->d_sync) hipFree(h->d_sync);
-    if (h->ev_xy) hipEventDestroy(h->ev_xy);
     if (h->d_chain_own) hipFree(h->d_chain_own);
     if (h->d_work) { hipFree(h->d_work); hipFree(h->d_pe_prev); hipFree(h->d_xold); hipFree(h->d_vold); hipFree(h->d_accept); }
     if (h->d_chain_sync) hipFree(h->d_chain_sync);
@@ -573,7 +576,7 @@ static int phases_for(remd_ctx* h)
 {
     if (h->parent) return 1;
     int want = h->phases_req;
-    if (const char* e = getenv("REMD_PHASES")) want = atoi(e);
+    if (h->sw.phases >= 0) want = h->sw.phases;
     if (want == 1) return 1;
     // what the blocks' interleaved steps need (everything else takes the one-block path):
     //  * a force evaluation that forks into the mesh and the direct-space stream (PME with overlap), a plain single-group V / R / O program
@@ -585,7 +588,7 @@ static int phases_for(remd_ctx* h)
     // (NoCutoff systems -- a step of three or four dependent small launches on ONE stream -- run as two blocks only when asked to: built and
     // measured at the end of round 6, bit-identical, and no faster (24 x CB7:B2 in vacuum 52.7 / 53.2 it/s, the implicit-solvent dipeptide
     // 45.7 / 45.4): with twice the launches per unit of time the HOST's enqueue rate is the limit, ~4.7 us per launch; profiles/r06_45)
-    const bool pme_fork = h->nb_method == REMD_NB_PME && h->overlap && h->stream2;
+    const bool pme_fork = h->nb_method == REMD_NB_PME && h->sw.overlap && h->stream2;
     const bool small_launches = h->nocutoff && h->nb_method == REMD_NB_NONE && (h->gbsa || h->n_regions > 0 || h->N > 64);
     if (!pme_fork && !(small_launches && want == 2)) return 1;
     if (h->measure_heat || h->measure_shadow || h->profiling == 2 || h->comm) return 1;
@@ -669,20 +672,20 @@ static int phase_children(remd_ctx* h, int P)
         if (p == 0) {            // block 0 launches on this handle's own pair of streams (no hardware queue of its own)
             if (c->stream2) hipStreamDestroy(c->stream2);
             c->stream2 = h->stream2; c->borrowed_stream2 = true;
-        } else if (!getenv("REMD_CU_PAIR") && !getenv("REMD_CU_MESH")) {
+        } else {
             // block B's streams must not sit on the hardware queues block A's are on (asked of the device, see above)
             if (c->stream2 && h->stream2 && streams_share_a_queue(h->stream2, c->stream2)) {
                 hipStream_t s2 = stream_beside(h->stream2, true);
                 if (s2) { hipStreamDestroy(c->stream2); c->stream2 = s2; }
-                if (getenv("REMD_MANY_VERBOSE")) fprintf(stderr, "[remd] phases: block B's direct-space stream shared a hardware queue with block A's; re-made (%s)\n", s2 && !streams_share_a_queue(h->stream2, s2) ? "apart now" : "still shared");
+                if (h->sw.many_verbose) fprintf(stderr, "[remd] phases: block B's direct-space stream shared a hardware queue with block A's; re-made (%s)\n", s2 && !streams_share_a_queue(h->stream2, s2) ? "apart now" : "still shared");
             }
             if (c->owns_stream && streams_share_a_queue(h->stream, c->stream)) {
-                hipStream_t s1 = stream_beside(h->stream, getenv("REMD_MAIN_PRIO") && atoi(getenv("REMD_MAIN_PRIO")) != 0);
+                hipStream_t s1 = stream_beside(h->stream, false);
                 if (s1) { hipStreamDestroy(c->stream); c->stream = s1; }
-                if (getenv("REMD_MANY_VERBOSE")) fprintf(stderr, "[remd] phases: block B's main stream shared a hardware queue with block A's; re-made (%s)\n", s1 && !streams_share_a_queue(h->stream, s1) ? "apart now" : "still shared");
+                if (h->sw.many_verbose) fprintf(stderr, "[remd] phases: block B's main stream shared a hardware queue with block A's; re-made (%s)\n", s1 && !streams_share_a_queue(h->stream, s1) ? "apart now" : "still shared");
             }
         }
-        c->sync_events = h->sync_events; c->overlap = h->overlap;
+        c->sw = h->sw; c->sync_events = h->sync_events;      // (a handle that fell back to events keeps its blocks on them)
         c->annihilate_sterics = h->annihilate_sterics; c->coulomb_cutoff = h->coulomb_cutoff; c->rf_unshifted = h->rf_unshifted; c->rf_switch_width = h->rf_switch_width;
         if ((rc = remd_set_system(c, &h->sysdesc->d))) return remd_fail(h, rc, std::string("phases: ") + c->err);
         if ((rc = remd_set_states(c, h->K, h->beta.data(), h->lam_s.data(), h->lam_e.data(), h->econst.data()))) return remd_fail(h, rc, std::string("phases: ") + c->err);
@@ -751,7 +754,7 @@ static int remd_propagate_phased(remd_ctx* h, int P, int64_t iteration, int32_t*
             c->econst_vref = h->econst_vref;
         }
         c->box_uniform = h->box_uniform;
-        c->profiling = h->profiling; c->prof_filter = h->prof_filter; c->prof_every = h->prof_every;
+        c->profiling = h->profiling; c->prof_filter = h->prof_filter;
         remd_nb_invalidate_sort(c);
     }
     std::vector<int32_t> flags((size_t)h->R, 0);
@@ -921,10 +924,9 @@ int remd_propagate_many(remd_handle* hs, int32_t n, int64_t iteration, int32_t* 
         if (!h->d_snap_work) REMD_CHECK(h, hipMalloc(&h->d_snap_work, 2 * wbytes));
         if (h->d_work != nullptr && h->work_R == h->R) REMD_CHECK(h, hipMemcpyAsync(h->d_snap_work, h->d_work, wbytes, hipMemcpyDeviceToDevice, h->stream));
         else REMD_CHECK(h, hipMemsetAsync(h->d_snap_work, 0, wbytes, h->stream));
-        // (REMD_MANY_LEAN=1: no workgroup waits on a CU for another stream -- join by a one-wavefront launch, momentum sum as two
+        // (without polls_ok no workgroup waits on a CU for another stream -- join by a one-wavefront launch, momentum sum as two
         // launches; measured slower than the polling chain once the handles' streams sit on four hardware queues: 76.1 against 72.9 ms)
-        static const bool lean_env = getenv("REMD_MANY_LEAN") && atoi(getenv("REMD_MANY_LEAN")) != 0;
-        h->lean_waits = lean_env || !polls_ok;
+        h->lean_waits = !polls_ok;
         h->no_chain_barrier = !barrier_ok;
         remd_nb_invalidate_sort(h);          // as remd_propagate: the schedule of spatial re-sorts restarts with every propagation
     }
@@ -950,7 +952,7 @@ int remd_propagate_many(remd_handle* hs, int32_t n, int64_t iteration, int32_t* 
         if (h->stream2) hipStreamSynchronize(h->stream2);
     }
     if (rc) return rc;
-    if (getenv("REMD_MANY_VERBOSE"))
+    if (hs[0]->sw.many_verbose)
         fprintf(stderr, "[remd] remd_propagate_many: %d handles, host enqueue of the steps %.2f ms, until the device was done %.2f ms\n", n,
                 1e3 * std::chrono::duration<double>(t_enq1 - t_enq0).count(),
                 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_enq0).count());

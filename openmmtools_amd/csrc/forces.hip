@@ -101,9 +101,8 @@ struct nb_tables {
     int nb_prio = 0;                      // current choice: 1 = the pair kernel runs at raised wave priority and the mesh kernels do not
     std::vector<tune_seg> tune_segs; int tune_state = 0 /* 0 measuring, 1 awaiting resolve, 2 done */, tune_left = 0, tune_next = 0;
     int nb_grid = 0;                      // current choice (workgroups; 0 = one per item)
-    float sort_cell = 0.45f;              // Morton cell edge (nm) of the molecule sort (sort_hbits = 0)
-    int sort_hbits = 0;                   // > 0: 2^sort_hbits cells per box edge along the Hilbert curve (round 6, the default)
-    // Ewald direct-space force table of the force-only pair kernels (coulomb_table.h); REMD_NB_TABLE=0: Abramowitz & Stegun erfc
+    int sort_hbits = 0;                   // 2^sort_hbits cells per box edge along the Hilbert curve (0: not chosen yet)
+    // Ewald direct-space force table of the force-only pair kernels (coulomb_table.h); energy evaluations: Abramowitz & Stegun erfc
     float4* d_ctab = nullptr; bool use_table = false;
     unsigned int* d_pair_done = nullptr; unsigned int pair_done_target = 0;      // remd_fold_args: the scatter launch's done counter
     int* d_tile_of_rank = nullptr;        // [R][ntile] the main system's tiles by descending list length, refreshed with the molecule order
@@ -285,14 +284,6 @@ void listed_forces_kernel(listed_tables T, int Npad, const float4* __restrict__ 
 
 
 // ---- spatial ordering ------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned morton3(unsigned x, unsigned y, unsigned z)
-{
-    unsigned m = 0;
-#pragma unroll
-    for (int b = 0; b < 6; ++b) m |= ((x >> b) & 1u) << (3 * b) | ((y >> b) & 1u) << (3 * b + 1) | ((z >> b) & 1u) << (3 * b + 2);
-    return m;
-}
-
 // index of cell (x, y, z) of a 2^bits cube along the 3-D Hilbert curve (Skilling's transpose algorithm): consecutive indices are
 // face neighbours, so the molecules of a run of the order -- the 8-atom clusters and 64-atom tiles of the pair kernel -- fill
 // compact blobs.  The Z-order curve used until round 6 jumps at every power-of-two boundary: on the headline system its clusters
@@ -330,21 +321,19 @@ __device__ __forceinline__ unsigned hilbert3(unsigned x, unsigned y, unsigned z,
 template <typename KEY>
 __device__ __forceinline__
 void sort_groups_body(int G, int N, int Npad, const int* __restrict__ grp_first, const int* __restrict__ grp_size,
-                      const float4* __restrict__ pos, const float* __restrict__ box, float cell, int* __restrict__ order,
+                      const float4* __restrict__ pos, const float* __restrict__ box, int* __restrict__ order,
                       KEY* key, int* r_first, int* r_size, int* r_off, int* s_part, int hbits)
 {
     const int r = blockIdx.x, tid = threadIdx.x;
     const float Lx = box[4 * r], Ly = box[4 * r + 1], Lz = box[4 * r + 2];
-    // hbits > 0: 2^hbits cells per edge, ordered along the Hilbert curve; 0: cells of edge `cell` along the Z-order curve (until round 6)
-    const int ncx = hbits > 0 ? (1 << hbits) : max(1, min(63, (int)(Lx / cell))), ncy = hbits > 0 ? (1 << hbits) : max(1, min(63, (int)(Ly / cell))),
-              ncz = hbits > 0 ? (1 << hbits) : max(1, min(63, (int)(Lz / cell)));
+    const int nc = 1 << hbits;            // cells per edge, ordered along the Hilbert curve
     constexpr int GBITS = sizeof(KEY) == 8 ? 32 : 13;
     for (int g = tid; g < G; g += 1024) {
         const float4 x = pos[(size_t)r * Npad + grp_first[g]];
         float fx = x.x / Lx, fy = x.y / Ly, fz = x.z / Lz;
         fx -= floorf(fx); fy -= floorf(fy); fz -= floorf(fz);
-        const unsigned cx = min(ncx - 1, (int)(fx * ncx)), cy = min(ncy - 1, (int)(fy * ncy)), cz = min(ncz - 1, (int)(fz * ncz));
-        key[g] = ((KEY)(hbits > 0 ? hilbert3(cx, cy, cz, hbits) : morton3(cx, cy, cz)) << GBITS) | (KEY)(unsigned)g;
+        const unsigned cx = min(nc - 1, (int)(fx * nc)), cy = min(nc - 1, (int)(fy * nc)), cz = min(nc - 1, (int)(fz * nc));
+        key[g] = ((KEY)hilbert3(cx, cy, cz, hbits) << GBITS) | (KEY)(unsigned)g;
     }
     __syncthreads();
     for (int g = tid; g < G; g += 1024) {
@@ -380,26 +369,26 @@ void sort_groups_body(int G, int N, int Npad, const int* __restrict__ grp_first,
 
 __global__ __launch_bounds__(1024)
 void sort_groups_kernel(int G, int N, int Npad, const int* __restrict__ grp_first, const int* __restrict__ grp_size,
-                        const float4* __restrict__ pos, const float* __restrict__ box, float cell, int* __restrict__ order, int hbits)
+                        const float4* __restrict__ pos, const float* __restrict__ box, int* __restrict__ order, int hbits)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned* key = reinterpret_cast<unsigned*>(smem);       // [G]
     int* r_first = reinterpret_cast<int*>(key + G);          // [G] by rank
     __shared__ int s_part[1024];
-    sort_groups_body<unsigned>(G, N, Npad, grp_first, grp_size, pos, box, cell, order, key, r_first, r_first + G, r_first + 2 * G, s_part, hbits);
+    sort_groups_body<unsigned>(G, N, Npad, grp_first, grp_size, pos, box, order, key, r_first, r_first + G, r_first + 2 * G, s_part, hbits);
 }
 
 // scratch: [R][5 G] ints (the 64-bit keys first)
 __global__ __launch_bounds__(1024)
 void sort_groups_large_kernel(int G, int N, int Npad, const int* __restrict__ grp_first, const int* __restrict__ grp_size,
-                              const float4* __restrict__ pos, const float* __restrict__ box, float cell, int* __restrict__ order,
+                              const float4* __restrict__ pos, const float* __restrict__ box, int* __restrict__ order,
                               int* __restrict__ scratch, int hbits)
 {
     __shared__ int s_part[1024];
     int* base = scratch + (size_t)blockIdx.x * 5 * G;
     unsigned long long* key = reinterpret_cast<unsigned long long*>(base);
     int* r_first = base + 2 * G;
-    sort_groups_body<unsigned long long>(G, N, Npad, grp_first, grp_size, pos, box, cell, order, key, r_first, r_first + G, r_first + 2 * G, s_part, hbits);
+    sort_groups_body<unsigned long long>(G, N, Npad, grp_first, grp_size, pos, box, order, key, r_first, r_first + G, r_first + 2 * G, s_part, hbits);
 }
 
 __global__ __launch_bounds__(256)
@@ -586,22 +575,13 @@ void scatter_sorted_forces_kernel(int Npad_a, const int* __restrict__ order_a, l
     }
 }
 
-// lane <-> (i atom ii, j atom jj) of a cluster pair in the sci kernels.  SCI_LANES_IJ = 1 (round 4): ii in the LOW three lane
-// bits, so the per-entry all-reduce of the reaction forces over the 8 i atoms is three DPP adds inside groups of 8 lanes
-// (quad permutes + half-row mirror) instead of a row rotation and two cross-row swaps per component (27 -> 9 instructions per
-// list entry); the exclusion words are ballots in the same lane order (build_excl_kernel).
-#ifndef SCI_LANES_IJ
-#define SCI_LANES_IJ 1
-#endif
-#if SCI_LANES_IJ
+// lane <-> (i atom ii, j atom jj) of a cluster pair in the sci kernels (round 4): ii in the LOW three lane bits, so the per-entry
+// all-reduce of the reaction forces over the 8 i atoms is three DPP adds inside groups of 8 lanes (quad permutes + half-row mirror)
+// instead of a row rotation and two cross-row swaps per component (27 -> 9 instructions per list entry); the exclusion words are
+// ballots in the same lane order (build_excl_kernel).
 #define SCI_LANE_II(lane) ((lane) & 7)
 #define SCI_LANE_JJ(lane) ((lane) >> 3)
 #define SCI_LANE_OF(ii, jj) ((jj) * 8 + (ii))
-#else
-#define SCI_LANE_II(lane) ((lane) >> 3)
-#define SCI_LANE_JJ(lane) ((lane) & 7)
-#define SCI_LANE_OF(ii, jj) ((ii) * 8 + (jj))
-#endif
 
 __global__ __launch_bounds__(64)
 void build_excl_kernel(int Npad, int ncl, int W, int words, const unsigned long long* __restrict__ smask,
@@ -705,32 +685,6 @@ void build_sci_list2_kernel(int nt_a, sci_list_args a, sci_list_args b, float rc
                         g.tile_c, g.tile_h, box, g.list, g.count);
 }
 
-// all-reduce over the lanes that differ in bit 3 / 4 / 5 of the lane id without the LDS crossbar (ds_bpermute: address
-// arithmetic + a round trip per exchange): a row rotation by 8 (DPP) and the gfx950 row / half swaps
-__device__ __forceinline__ float allsum_x8(float v)
-{
-    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, false));
-}
-// all-reduce inside every group of 8 consecutive lanes: two quad permutes and the half-row mirror (DPP, no cross-row traffic)
-__device__ __forceinline__ float allsum_low8(float v)
-{
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, false));   // quad_perm [1,0,3,2]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, false));   // quad_perm [2,3,0,1]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xf, 0xf, false));  // row_half_mirror
-    return v;
-}
-__device__ __forceinline__ float allsum_x16(float v)
-{
-    float a = v, b = v;        // odd rows of a <-> even rows of b
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    return a + b;
-}
-__device__ __forceinline__ float allsum_x32(float v)
-{
-    float a = v, b = v;        // upper half of a <-> lower half of b
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    return a + b;
-}
 // v where bit `lane` of the wave-uniform mask is set, else 0: one v_cndmask on the scalar mask
 __device__ __forceinline__ float keep_where(unsigned long long m, float v)
 {
@@ -764,30 +718,6 @@ struct sci_args {
     const int* tile_of_rank;    // [R][ntile] tiles of a replica by descending list length (rank_tiles_kernel), or NULL: item order = tile order
 };
 #define SCI_EWALD(M) ((M) == NB_EWALD || (M) == NB_EWALD_NOLJ)
-// A/B switches of the round-4 pair-kernel changes (tools/build_variant.sh -DSCI_...=0)
-#ifndef SCI_EARLY_TABLE
-#define SCI_EARLY_TABLE 1
-#endif
-#ifndef SCI_PREFETCH2
-#define SCI_PREFETCH2 1
-#endif
-#ifndef SCI_PACKQ
-#define SCI_PACKQ 1
-#endif
-#ifndef SCI_INTCOORD
-#define SCI_INTCOORD 1
-#endif
-// x / y components of the separation and of both force accumulators as register pairs: one v_pk_fma_f32 each instead of a packed
-// multiply and two adds
-#ifndef SCI_PKACC
-#define SCI_PKACC 1
-#endif
-#ifndef SCI_TABIDX
-#define SCI_TABIDX 1
-#endif
-#ifndef SCI_DPP_ASM
-#define SCI_DPP_ASM 1
-#endif
 typedef float sci_v2f __attribute__((ext_vector_type(2)));
 template <int METHOD, bool ENERGY, bool ALCH, int NW, bool TABLE = false, bool INTPOS = false>
 __device__ __forceinline__
@@ -818,7 +748,7 @@ void nonbonded_sci_body(const nb_params& p, const sci_args& a, int item, const f
     const int ii = SCI_LANE_II(lane), jj = SCI_LANE_JJ(lane);
     // force-only Coulomb-only kernel: positions as integer box fractions (sci_args::sposi), minimum image by wrap-around
     // (INTPOS: the caller also has integer positions for a system that keeps its parameter loads -- the LJ sub-system of a split launch)
-    constexpr bool INTC = SCI_INTCOORD && !ENERGY && ((SCI_PACKQ && !ALCH && (METHOD == NB_EWALD_NOLJ || METHOD == NB_RF_NOLJ)) || INTPOS);
+    constexpr bool INTC = !ENERGY && ((!ALCH && (METHOD == NB_EWALD_NOLJ || METHOD == NB_RF_NOLJ)) || INTPOS);
     const float4* __restrict__ P = (INTC ? a.sposi : spos) + (size_t)r * Npad;      // (the split launch always passes sposi)
     const float4* __restrict__ prm = sparam + (size_t)r * Npad;
     const float Lx = box[4 * r], Ly = box[4 * r + 1], Lz = box[4 * r + 2];
@@ -837,11 +767,12 @@ void nonbonded_sci_body(const nb_params& p, const sci_args& a, int item, const f
     const unsigned int* L = list + ((size_t)r * ntile + T) * cap + zsl;
 
     // Coulomb-only main kernel of a split system: the charge rides in spos.w (gather_positions_body), no parameter loads
-    constexpr bool PACKQ = SCI_PACKQ && (METHOD == NB_EWALD_NOLJ || METHOD == NB_RF_NOLJ) && !ALCH;
-    constexpr bool PF2 = PACKQ && SCI_PREFETCH2;
+    constexpr bool PACKQ = (METHOD == NB_EWALD_NOLJ || METHOD == NB_RF_NOLJ) && !ALCH;
     float4 xi[8], pi[8];
-    float fix[8], fiy[8], fiz[8];
+    // x / y components of the separation and of both force accumulators as register pairs: one v_pk_fma_f32 each instead of a packed
+    // multiply and two adds
     sci_v2f fixy[8];
+    float fiz[8];
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
         fixy[s] = sci_v2f{ 0.f, 0.f };
@@ -849,7 +780,7 @@ void nonbonded_sci_body(const nb_params& p, const sci_args& a, int item, const f
         xi[s] = P[i];
         if (PACKQ) pi[s] = make_float4(xi[s].w, 0.f, 0.f, 0.f); else pi[s] = prm[i];
         if (ALCH && pi[s].w != 0.f) pi[s].x *= lam_e;
-        fix[s] = fiy[s] = fiz[s] = 0.f;
+        fiz[s] = 0.f;
     }
     // exclusion words of this tile's near-diagonal pairs: lane s*8 + dj holds excl[ic_s][dj] (W <= 8), read back with readlane
     unsigned int ex_lo = 0u, ex_hi = 0u;
@@ -870,7 +801,7 @@ void nonbonded_sci_body(const nb_params& p, const sci_args& a, int item, const f
         int jn = (int)(__builtin_amdgcn_readlane(my_ent, 0) & 0xffffu);
         float4 gx = P[jn * 8 + jj], gp = PACKQ ? gx : prm[jn * 8 + jj];
         float4 gx2 = gx;                                         // PACKQ: the entry after the next one
-        if (PF2) { jn = (int)(__builtin_amdgcn_readlane(my_ent, min(1, cnt - 1)) & 0xffffu); gx2 = P[jn * 8 + jj]; }
+        if (PACKQ) { jn = (int)(__builtin_amdgcn_readlane(my_ent, min(1, cnt - 1)) & 0xffffu); gx2 = P[jn * 8 + jj]; }
         for (int k = 0; k < cnt; ++k) {
             const unsigned int ent = __builtin_amdgcn_readlane(my_ent, k);
             const int jc = (int)(ent & 0xffffu);
@@ -880,7 +811,7 @@ void nonbonded_sci_body(const nb_params& p, const sci_args& a, int item, const f
             // prefetch the next entry's j atoms behind this entry's arithmetic (unconditional: the last entry of a chunk
             // re-reads itself, which keeps the loop free of a branch the register allocator would pin copies to); the packed
             // Coulomb-only kernel keeps two entries in flight
-            if (PF2) {
+            if (PACKQ) {
                 gx = gx2;
                 jn = (int)(__builtin_amdgcn_readlane(my_ent, min(k + 2, cnt - 1)) & 0xffffu);
                 gx2 = P[jn * 8 + jj];
@@ -910,29 +841,24 @@ void nonbonded_sci_body(const nb_params& p, const sci_args& a, int item, const f
                 // which lane pairs count is wave-uniform data (cutoff ballot, exclusion word, padding masks): scalar unit
                 unsigned long long in = __builtin_amdgcn_ballot_w64(r2 < rcut2);
                 // lanes beyond the cutoff evaluate at the cutoff (the table also has a lower end)
-                // (SCI_TABIDX, the early-table kernel: only the lower end is clamped.  Lanes beyond the cutoff are discarded by the
-                // select below whatever they read, and an LDS address past the workgroup's allocation reads as zero)
-                constexpr bool EARLY = SCI_EARLY_TABLE && TAB && METHOD == NB_EWALD_NOLJ && !ALCH;
-                float r2c = (EARLY && SCI_TABIDX) ? r2
-                          : TAB ? __builtin_amdgcn_fmed3f(r2, p.ctab_umin, rcut2) : min_sv(rcut2, r2);
+                // (the early-table kernel: only the lower end is clamped.  Lanes beyond the cutoff are discarded by the select below
+                // whatever they read, and an LDS address past the workgroup's allocation reads as zero)
+                constexpr bool EARLY = TAB && METHOD == NB_EWALD_NOLJ && !ALCH;
+                float r2c = EARLY ? r2 : TAB ? __builtin_amdgcn_fmed3f(r2, p.ctab_umin, rcut2) : min_sv(rcut2, r2);
                 // Coulomb-only kernel from the table: the LDS read is issued here, in front of the scalar mask chain and its
                 // branches, so that its round trip overlaps them instead of stalling the polynomial that consumes it
                 float4 tc = make_float4(0.f, 0.f, 0.f, 0.f); float ttf = 0.f;
                 if (EARLY) {
-                    if (SCI_TABIDX) {
-                        // lower clamp, key = bits [18, 32) as a bit-field extract, LDS address = key * 16 + base as one shift-add:
-                        // three instructions (the plain expression: a register copy of the bound, max, shift, mask, add)
-                        typedef float sci_v4f __attribute__((ext_vector_type(4)));
-                        typedef __attribute__((address_space(3))) const sci_v4f lds_v4f;
-                        const unsigned int lds_base = (unsigned int)(__UINTPTR_TYPE__)(lds_v4f*)ctab;
-                        unsigned int addr;
-                        asm("v_max_f32_e32 %0, %2, %3\n\tv_bfe_u32 %1, %0, %5, %6\n\tv_lshl_add_u32 %1, %1, 4, %4"
-                            : "=&v"(r2c), "=&v"(addr) : "s"(p.ctab_umin), "v"(r2), "s"(lds_base), "n"(CTAB_SHIFT), "n"(32 - CTAB_SHIFT));
-                        const sci_v4f c4 = *(lds_v4f*)(__UINTPTR_TYPE__)addr;
-                        tc = make_float4(c4.x, c4.y, c4.z, c4.w);
-                    } else {
-                        tc = ctab[__float_as_uint(r2c) >> CTAB_SHIFT];
-                    }
+                    // lower clamp, key = bits [18, 32) as a bit-field extract, LDS address = key * 16 + base as one shift-add:
+                    // three instructions (the plain expression: a register copy of the bound, max, shift, mask, add)
+                    typedef float sci_v4f __attribute__((ext_vector_type(4)));
+                    typedef __attribute__((address_space(3))) const sci_v4f lds_v4f;
+                    const unsigned int lds_base = (unsigned int)(__UINTPTR_TYPE__)(lds_v4f*)ctab;
+                    unsigned int addr;
+                    asm("v_max_f32_e32 %0, %2, %3\n\tv_bfe_u32 %1, %0, %5, %6\n\tv_lshl_add_u32 %1, %1, 4, %4"
+                        : "=&v"(r2c), "=&v"(addr) : "s"(p.ctab_umin), "v"(r2), "s"(lds_base), "n"(CTAB_SHIFT), "n"(32 - CTAB_SHIFT));
+                    const sci_v4f c4 = *(lds_v4f*)(__UINTPTR_TYPE__)addr;
+                    tc = make_float4(c4.x, c4.y, c4.z, c4.w);
                     ttf = (float)(__float_as_uint(r2c) & CTAB_MASK);
                 }
                 const int dj = jc - ic;
@@ -957,46 +883,32 @@ void nonbonded_sci_body(const nb_params& p, const sci_args& a, int item, const f
                 if (EARLY) { fr = (pi[s].x * pj.x) * fmaf(ttf, fmaf(ttf, fmaf(ttf, tc.w, tc.z), tc.y), tc.x); ee = 0.f; }
                 else pair_interaction<METHOD, ALCH, !ENERGY, TAB>(p, r2c, pi[s], pj, lam_a, sc, fr, false, ee, ctab);
                 fr = keep_where(in, fr);
-                if (SCI_PKACC) {
-                    const sci_v2f dxy = { dx, dy }, fr2 = { fr, fr };
-                    fixy[s] = __builtin_elementwise_fma(dxy, fr2, fixy[s]);
-                    fjxy = __builtin_elementwise_fma(-dxy, fr2, fjxy);
-                    fiz[s] = fmaf(dz, fr, fiz[s]);
-                    fjz = fmaf(-dz, fr, fjz);
-                } else {
-                    const float tx = fr * dx, ty = fr * dy, tz = fr * dz;
-                    fix[s] += tx; fiy[s] += ty; fiz[s] += tz;
-                    fjx -= tx; fjy -= ty; fjz -= tz;
-                }
+                const sci_v2f dxy = { dx, dy }, fr2 = { fr, fr };
+                fixy[s] = __builtin_elementwise_fma(dxy, fr2, fixy[s]);
+                fjxy = __builtin_elementwise_fma(-dxy, fr2, fjxy);
+                fiz[s] = fmaf(dz, fr, fiz[s]);
+                fjz = fmaf(-dz, fr, fjz);
                 if (ENERGY) e += ((in >> lane) & 1ull) ? (double)ee : 0.0;
             }
-            if (SCI_PKACC) { fjx = fjxy.x; fjy = fjxy.y; }
+            fjx = fjxy.x; fjy = fjxy.y;
             if (touched) {
-                // reaction on the j atoms: all-reduce over the 8 ii lanes (every lane ends up with the total of its jj)
-                if (SCI_LANES_IJ && SCI_DPP_ASM) {
-                    // three DPP adds per component inside groups of 8 lanes, written out: left to the compiler the x / y pair stays a
-                    // packed value (register copies + v_mov_b32_dpp + v_pk_add_f32: ~21 instructions per entry instead of these 9).
-                    // (a DPP operand must not be read within two instructions of the VALU write that produced it: the leading s_nop
-                    // covers the accumulators written just before, and inside the block every value is read two instructions after
-                    // its own update)
-                    asm("s_nop 1\n\t"
-                        "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-                        "v_add_f32_dpp %1, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-                        "v_add_f32_dpp %2, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-                        "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-                        "v_add_f32_dpp %1, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-                        "v_add_f32_dpp %2, %2, %2 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-                        "v_add_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-                        "v_add_f32_dpp %1, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-                        "v_add_f32_dpp %2, %2, %2 row_half_mirror row_mask:0xf bank_mask:0xf"
-                        : "+v"(fjx), "+v"(fjy), "+v"(fjz));
-                } else if (SCI_LANES_IJ) {
-                    fjx = allsum_low8(fjx); fjy = allsum_low8(fjy); fjz = allsum_low8(fjz);
-                } else {
-                    fjx = allsum_x8(fjx); fjy = allsum_x8(fjy); fjz = allsum_x8(fjz);
-                    fjx = allsum_x16(fjx); fjy = allsum_x16(fjy); fjz = allsum_x16(fjz);
-                    fjx = allsum_x32(fjx); fjy = allsum_x32(fjy); fjz = allsum_x32(fjz);
-                }
+                // reaction on the j atoms: all-reduce over the 8 ii lanes (every lane ends up with the total of its jj): three DPP adds
+                // per component inside groups of 8 lanes, written out: left to the compiler the x / y pair stays a packed value
+                // (register copies + v_mov_b32_dpp + v_pk_add_f32: ~21 instructions per entry instead of these 9).
+                // (a DPP operand must not be read within two instructions of the VALU write that produced it: the leading s_nop
+                // covers the accumulators written just before, and inside the block every value is read two instructions after
+                // its own update)
+                asm("s_nop 1\n\t"
+                    "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                    "v_add_f32_dpp %1, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                    "v_add_f32_dpp %2, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                    "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                    "v_add_f32_dpp %1, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                    "v_add_f32_dpp %2, %2, %2 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                    "v_add_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+                    "v_add_f32_dpp %1, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+                    "v_add_f32_dpp %2, %2, %2 row_half_mirror row_mask:0xf bank_mask:0xf"
+                    : "+v"(fjx), "+v"(fjy), "+v"(fjz));
             }
             const int eb = k & 7;
             if (ii == eb) { qfx = fjx; qfy = fjy; qfz = fjz; qj = j; }
@@ -1013,20 +925,19 @@ void nonbonded_sci_body(const nb_params& p, const sci_args& a, int item, const f
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const float send = (jj & 4) ? v[q] : v[q + 4], keep = (jj & 4) ? v[q + 4] : v[q];
-            a[q] = keep + __shfl_xor(send, SCI_LANES_IJ ? 32 : 4);
+            a[q] = keep + __shfl_xor(send, 32);
         }
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const float send = (jj & 2) ? a[q] : a[q + 2], keep = (jj & 2) ? a[q + 2] : a[q];
-            b[q] = keep + __shfl_xor(send, SCI_LANES_IJ ? 16 : 2);
+            b[q] = keep + __shfl_xor(send, 16);
         }
         const float send = (jj & 1) ? b[0] : b[1], keep = (jj & 1) ? b[1] : b[0];
-        return keep + __shfl_xor(send, SCI_LANES_IJ ? 8 : 1);
+        return keep + __shfl_xor(send, 8);
     };
-    if (SCI_PKACC) {
+    float fix[8], fiy[8];
 #pragma unroll
-        for (int s = 0; s < 8; ++s) { fix[s] = fixy[s].x; fiy[s] = fixy[s].y; }
-    }
+    for (int s = 0; s < 8; ++s) { fix[s] = fixy[s].x; fiy[s] = fixy[s].y; }
     float fx = reduce_scatter(fix), fy = reduce_scatter(fiy), fz = reduce_scatter(fiz);
     if (NW > 1) {
         __shared__ float s_f[NW][3][64];
@@ -1636,14 +1547,13 @@ int remd_build_nonbonded(remd_ctx* h, const remd_system_desc* d)
         p.rcc2 = (float)(h->coulomb_cutoff * h->coulomb_cutoff);
     }
     p.ctab_key0 = 0; p.ctab_n = 0; p.ctab_umin = 0.f;
-    t.use_table = false;
-    if (t.method == NB_EWALD && !(getenv("REMD_NB_TABLE") && atoi(getenv("REMD_NB_TABLE")) == 0)) {
+    t.use_table = t.method == NB_EWALD;
+    if (t.use_table) {
         const coulomb_table_host T = ctab_build(d->ewald_alpha, (double)p.rcc2);
         std::vector<float4> tab(T.n);
         for (int k = 0; k < T.n; ++k) tab[k] = make_float4(T.c[4 * k], T.c[4 * k + 1], T.c[4 * k + 2], T.c[4 * k + 3]);
         if ((rc = upload(h, t.d_ctab, tab))) return rc;
         p.ctab_key0 = T.key0; p.ctab_n = T.n; p.ctab_umin = T.umin;
-        t.use_table = true;
     }
     const int ntile = (N + 63) / 64;
     {
@@ -1676,23 +1586,21 @@ int remd_build_nonbonded(remd_ctx* h, const remd_system_desc* d)
         t.n_groups = (int)first.size();
         if ((rc = upload(h, t.d_grp_first, first)) || (rc = upload(h, t.d_grp_size, size))) return rc;
         t.sorting = true;
-        t.clusters = !getenv("REMD_NB_TILES");        // test hook: the 64-atom tile kernel a list overflow falls back to
+        t.clusters = !h->sw.nb_tiles;        // test hook: the 64-atom tile kernel a list overflow falls back to
         // 8 slices where the mesh stream runs beside the pair kernel (its launch may become a resident set pulling items: 105.9 vs
         // 106.55 ms per 500 steps on the headline config), 12 elsewhere (LJ fluid, one workgroup per item: 66.6 vs 63.3 it/s).
         // Fixed per system, never per launch mode: the slices' fp32 partial sums enter the forces bit-wise.
-        t.sci_split = (t.method == NB_EWALD && h->overlap && h->stream2) ? 8 : 12;
+        t.sci_split = (t.method == NB_EWALD && h->sw.overlap && h->stream2) ? 8 : 12;
         // (round 6, last scan: systems of 64 tiles or more have work items enough without the finer slicing -- 4 slices: 8 x CB7:B2 (71 tiles)
         // 13.81 -> 14.65 it/s, 16 x DHFR (369) 2.25 -> 2.31, DHFR on an alchemical ladder 1.92 -> 2.04; the headline system (36 tiles) loses
         // 10 % with 4; profiles/r06_45.  A property of the system, not of the replica count: blocks and one-block runs stay bit-identical.)
         // (the plain kernel on CB7:B2 -- the general alchemical path, whose pair kernels see the environment only -- loses 2 % with 4: 13.3 -> 13.0;
         // so from 64 tiles on for the soft-core variant, from 256 on for the plain one)
-        if (t.method == NB_EWALD && h->overlap && h->stream2 && (h->N + 63) / 64 >= (d->n_alch > 0 ? 64 : 256)) t.sci_split = 4;
-        if (getenv("REMD_NB_SPLIT")) t.sci_split = std::max(4, atoi(getenv("REMD_NB_SPLIT")));      // experiment hook
+        if (t.method == NB_EWALD && h->sw.overlap && h->stream2 && (h->N + 63) / 64 >= (d->n_alch > 0 ? 64 : 256)) t.sci_split = 4;
         // the ranking of the sort is G comparisons per molecule on ONE workgroup per replica (0.9 ms on DHFR's 7 k molecules): from 2048
         // molecules on it runs every 160 evaluations instead of every 40 (the order decays slowly: 0.893 -> 0.868 ms per step on 16 x DHFR,
         // flat between 80 and 320, profiles/r06_36_resort_interval.txt; the headline system does not notice either way)
         if (t.n_groups >= 2048) t.resort_interval = 160;
-        if (getenv("REMD_NB_RESORT")) t.resort_interval = std::max(1, atoi(getenv("REMD_NB_RESORT")));
     }
 
     // LJ-active sub-system: worthwhile when charges exist and most atoms carry no LJ (TIP3P hydrogens)
@@ -1850,18 +1758,18 @@ static int ensure_sorted(remd_ctx* h, nb_tables& t)
     if (t.evals_since_sort >= t.resort_interval) {
         remd_prof_scope ps(h, "nb_sort");
         // cells of the molecule order: 2^b per box edge with an edge of ~0.11 nm (b from the longest edge of the first replica's box, as
-        // the host mirrors it; 32 per edge on the headline system, 64 on DHFR: REMD_NB_HBITS scans, profiles/r06_35_hilbert_cells.txt), along the Hilbert curve.  REMD_NB_CURVE=morton: the
-        // Z-order curve on cells of 0.45 nm, as until round 6.  A property of the handle: fixed at the first sort.
-        if (t.sort_hbits == 0 && !(getenv("REMD_NB_CURVE") && getenv("REMD_NB_CURVE")[0] == 'm')) {
+        // the host mirrors it; 32 per edge on the headline system, 64 on DHFR: profiles/r06_35_hilbert_cells.txt), along the Hilbert curve
+        // (the Z-order curve on cells of 0.45 nm, used until round 6, was removed after that measurement).  A property of the handle:
+        // fixed at the first sort.
+        if (t.sort_hbits == 0) {
             double lmax = 0.0;
             for (int k = 0; k < 3 && (size_t)k < h->box_host.size(); ++k) lmax = std::max(lmax, h->box_host[k]);
             t.sort_hbits = lmax > 0.0 ? std::max(1, std::min(6, (int)lround(log2(lmax / 0.11)))) : 4;
-            if (getenv("REMD_NB_HBITS")) t.sort_hbits = std::max(1, std::min(6, atoi(getenv("REMD_NB_HBITS"))));      // experiment hook
         }
         if (t.n_groups < 8192) {
             const size_t lds = sizeof(int) * 4 * (size_t)t.n_groups;
             hipLaunchKernelGGL(sort_groups_kernel, dim3(h->R), dim3(1024), lds, h->stream, t.n_groups, h->N, h->Npad, t.d_grp_first,
-                               t.d_grp_size, h->d_pos, h->d_box, t.sort_cell, t.d_order, t.sort_hbits);
+                               t.d_grp_size, h->d_pos, h->d_box, t.d_order, t.sort_hbits);
         } else {
             const size_t need = (size_t)h->R * 5 * t.n_groups;
             if (t.sort_scratch_n < need) {
@@ -1870,7 +1778,7 @@ static int ensure_sorted(remd_ctx* h, nb_tables& t)
                 t.sort_scratch_n = need;
             }
             hipLaunchKernelGGL(sort_groups_large_kernel, dim3(h->R), dim3(1024), 0, h->stream, t.n_groups, h->N, h->Npad, t.d_grp_first,
-                               t.d_grp_size, h->d_pos, h->d_box, t.sort_cell, t.d_order, t.d_sort_scratch, t.sort_hbits);
+                               t.d_grp_size, h->d_pos, h->d_box, t.d_order, t.d_sort_scratch, t.sort_hbits);
         }
         hipLaunchKernelGGL(gather_params_kernel, dim3((h->Npad + 255) / 256, h->R), dim3(256), 0, h->stream, h->Npad, t.p.excl_words,
                            t.d_order, t.d_param, t.d_mask, t.d_sparam, t.d_smask);
@@ -1903,7 +1811,7 @@ static int ensure_sorted(remd_ctx* h, nb_tables& t)
         hipLaunchKernelGGL(gather_positions2_kernel, dim3(ntile + ntile_lj, h->R), dim3(64), 0, h->stream, ntile, ga, gb, h->Npad, h->d_pos, h->d_box);
         hipLaunchKernelGGL(build_sci_list2_kernel, dim3(ntile + ntile_lj, h->R), dim3(64), 0, h->stream, ntile, la, lb, rc2_main, t.p.rc2, h->d_box);
         // (the list lengths of the evaluation that re-sorted the molecules order the work items until the next re-sort: the geometry
-        // of a tile changes slowly; REMD_NB_RANK=0: tile order)
+        // of a tile changes slowly)
         if (t.evals_since_sort == 1 && t.d_tile_of_rank && ntile <= 2048)
             hipLaunchKernelGGL(rank_tiles_kernel, dim3((ntile + 255) / 256, h->R), dim3(256), 0, h->stream, ntile, t.d_sci_count, t.d_tile_of_rank);
     } else {
@@ -1911,7 +1819,7 @@ static int ensure_sorted(remd_ctx* h, nb_tables& t)
                            t.d_spos, t.d_tile_c, t.d_tile_h, cl ? t.d_cl_c : (float4*)nullptr, cl ? t.d_cl_h : (float4*)nullptr);
         if (cl) launch_list_build(h, t, false);
     }
-    static const bool debug = getenv("REMD_DEBUG") != nullptr;
+    const bool debug = h->sw.debug;
     if (cl && t.evals_since_sort == 1 && (t.cl_cap < ntile * 8 || debug)) {
         // capacity check once per re-sort (the only host synchronisation of this path)
         std::vector<int> cnt((size_t)h->R * ntile);
@@ -1945,13 +1853,12 @@ static void launch_nb(remd_ctx* h, nb_tables& t)
         constexpr int MAIN = (METHOD == NB_EWALD) ? NB_EWALD_NOLJ : (METHOD == NB_RF) ? NB_RF_NOLJ : METHOD;
         const int ssplit = std::max(SCI_NW, std::min(16, t.sci_split / SCI_NW * SCI_NW));
         // (measured, profiles/r05_7_*: -1.2 % of a step on 8 x host-guest (71 tiles) and 16 x DHFR (369 tiles), +1 % on 24 x alanine dipeptide
-        // (36 tiles: its launch is two rounds of the chip whatever the order) -- so from 64 tiles on; REMD_NB_RANK = 0 / 1 pins it)
-        static const int rank_env = getenv("REMD_NB_RANK") ? atoi(getenv("REMD_NB_RANK")) : -1;
+        // (36 tiles: its launch is two rounds of the chip whatever the order) -- so from 64 tiles on)
         // (rank_tiles_kernel compares every pair of a replica's tiles: measured up to 369 tiles; capped where the ranking would cost
         // more than the tail it removes)
         // (round 6, the blocks of a phased propagation: a block's launch is one round of the chip beside the other block's kernels, and the
         // longest lists first help there at 36 tiles too: 24 x alanine dipeptide +2.5 %, profiles/r06_45)
-        const bool ranked = (rank_env < 0 ? ((ntile >= 64 || h->parent != nullptr) && ntile <= 2048) : rank_env != 0) && t.lj_split && t.d_lj_sci_list && t.d_tile_of_rank && (METHOD == NB_EWALD || METHOD == NB_RF);
+        const bool ranked = (ntile >= 64 || h->parent != nullptr) && ntile <= 2048 && t.lj_split && t.d_lj_sci_list && t.d_tile_of_rank && (METHOD == NB_EWALD || METHOD == NB_RF);
         sci_args sa{h->N, h->Npad, ncl, t.cl_cap, t.excl_W, h->Npad, 0, ssplit, t.d_spos, t.d_sparam, t.d_excl, t.d_sci_list, t.d_sci_count, t.d_sforce,
                     t.d_sposi, ranked ? t.d_tile_of_rank : (const int*)nullptr};
         const int items_a = ntile * h->R * (ssplit / SCI_NW);
@@ -1961,8 +1868,7 @@ static void launch_nb(remd_ctx* h, nb_tables& t)
             sci_args sb{t.NL, t.NLpad, t.NLpad / 8, t.lj_cap, t.lj_excl_W, t.NLpad, ncl * 4, ssplit, t.d_lj_spos, t.d_lj_sparam, t.d_lj_excl,
                         t.d_lj_sci_list, t.d_lj_sci_count, t.d_lj_sforce, t.d_lj_sposi, nullptr};
             const int items = items_a + (t.NLpad / 64) * h->R * (ssplit / SCI_NW);
-            const int env_grid = getenv("REMD_NB_PERSIST_GRID") ? atoi(getenv("REMD_NB_PERSIST_GRID")) : -1;
-            const int persist_grid = env_grid >= 0 ? env_grid : t.nb_grid;
+            const int persist_grid = h->sw.nb_persist_grid >= 0 ? h->sw.nb_persist_grid : t.nb_grid;
             const int grid = (h->pme_concurrent && persist_grid > 0) ? std::min(items, persist_grid) : items;
             // requested by remd_compute_forces (h->fold_pending): the scatter's workgroups count themselves done for the integrator
             // chain to poll (remd_fold_args) -- no signal launch behind it
@@ -2071,8 +1977,7 @@ void remd_nb_tune_step(remd_ctx* h, int steps_left_in_call)
     nb_tables* tp = g_nb.find(h);
     if (!tp || h->nb_method == REMD_NB_NONE) return;
     nb_tables& t = *tp;
-    const bool fixed = getenv("REMD_NB_PERSIST_GRID") != nullptr;
-    if (fixed || t.tune_state != 0 || !h->pme_concurrent || h->profiling == 2) return;
+    if (h->sw.nb_persist_grid >= 0 || t.tune_state != 0 || !h->pme_concurrent || h->profiling == 2) return;
     if (t.tune_left == 0) {
         hipEvent_t boundary = nullptr;
         if (!t.tune_segs.empty() && !t.tune_segs.back().b) {            // close the open segment
@@ -2110,7 +2015,7 @@ void remd_nb_tune_resolve(remd_ctx* h)
     for (int c = 1; c < TUNE_NC; ++c) if (ok && ms[c] < ms[best] * 0.995) best = c;     // ties go to the earlier candidate
     t.nb_grid = ok ? g_tune_cands[best].grid : 0; t.nb_prio = ok ? g_tune_cands[best].prio_pair : 0;
     t.tune_state = 2;
-    if (getenv("REMD_NB_TUNE_VERBOSE"))
+    if (h->sw.nb_tune_verbose)
     {
         fprintf(stderr, "[remd] pair-kernel residency, ms per %d steps:", 2 * TUNE_SEG);
         for (int c = 0; c < TUNE_NC; ++c) fprintf(stderr, " %d%s: %.2f", g_tune_cands[c].grid, g_tune_cands[c].prio_pair ? "p" : "", ms[c]);
@@ -2170,7 +2075,7 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask)
     // Two branches between the integrator chains.  The reciprocal-space pipeline is the longer one, so IT stays on the main
     // stream directly behind the integrator; the direct-space launches go to the second stream (h->stream is swapped until
     // the join).  Fork and join are flags in device memory polled by kernels (remd_ctx::d_sync), or events when a handle has
-    // fallen back to them (REMD_SYNC_EVENTS=1 / api.hip: remd_recover_device_flag).  Measured alternatives that lost their
+    // fallen back to them (api.hip: remd_recover_device_flag).  Measured alternatives that lost their
     // A/B and were removed in round 3 (numbers in DESIGN.md 7b): the mesh branch on the second stream, the pair kernel ahead
     // of the listed terms, the listed terms in front of the pair kernel or on a third stream, scatter + listed terms + join
     // flag in one launch.
@@ -2192,22 +2097,18 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask)
         }
         total = T.n_bonds + T.n_angles + T.n_torsions + T.n_exc + T.n_excl;
         // one (term, slot) entry per thread in atom order (REMD_LISTED_ATOMS=0: one term per thread)
-        const bool atoms_env = !(getenv("REMD_LISTED_ATOMS") && atoi(getenv("REMD_LISTED_ATOMS")) == 0);
         T.n_aterm = 0; T.aterm = nullptr;
-        if (atoms_env && total > 0 && h->d_aterm && h->n_aterm > 0) { T.aterm = h->d_aterm; T.n_aterm = h->n_aterm; total = h->n_aterm; }
+        if (h->sw.listed_atoms && total > 0 && h->d_aterm && h->n_aterm > 0) { T.aterm = h->d_aterm; T.n_aterm = h->n_aterm; total = h->n_aterm; }
         return T;
     };
-    const bool listed_main_env = !(getenv("REMD_LISTED_MAIN") && atoi(getenv("REMD_LISTED_MAIN")) == 0);
-    const bool listed_ride_env = !(getenv("REMD_LISTED_RIDE") && atoi(getenv("REMD_LISTED_RIDE")) == 0);
     bool listed_rode = false;
     if (h->nb_method != REMD_NB_NONE) {      // per-replica lambdas must be current before ANY kernel reads them
         nb_tables& t0 = g_nb[h];
         int rc0 = update_replica_lambdas(h, t0);
         if (rc0) return rc0;
-        if (t0.method == NB_EWALD && h->overlap && h->stream2 && do_nb && do_recip) {
+        if (t0.method == NB_EWALD && h->sw.overlap && h->stream2 && do_nb && do_recip) {
             // which stream's kernels run at raised wave priority: chosen together with the pair kernel's residency (remd_nb_tune_step)
-            const int prio_env = getenv("REMD_NB_PRIO") ? atoi(getenv("REMD_NB_PRIO")) : -1;
-            t0.p.prio = prio_env >= 0 ? (prio_env ? 1 : 0) : t0.nb_prio;
+            t0.p.prio = h->sw.nb_prio >= 0 ? h->sw.nb_prio : t0.nb_prio;
             h->mesh_prio_hi = !t0.p.prio;
             if (!h->sync_events) {
                 // the first mesh launch (binning kernel, or the spreading pass when the chain binned the atoms) stores the
@@ -2220,21 +2121,11 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask)
             }
             // direct-space stream critical (t0.p.prio): the listed terms of a force-only evaluation leave it -- as extra workgroups of
             // the spreading launch (REMD_LISTED_RIDE=0: as a launch of their own behind the mesh launches)
+            // (Round 6, measured and removed: holding the pair kernel back until an LDS-resident plane pass has ended -- the two then
+            // stretch the pair kernel and the inverse-z / gather pass instead, 139.9 against 134.8 ms per 100 steps of 16 DHFR replicas,
+            // +30 % on host-guest and alanine; profiles/r06_12_dhfr_pair_after_plane_pass.txt)
             h->mesh_listed_total = 0;
-            {
-                // Round 6, measured and left OFF (REMD_PAIR_AFTER_XY=1 switches it on): when the plane pass keeps whole planes in LDS with ONE
-                // workgroup per CU (DHFR: 128 x 128 planes, 134 KB) its workgroups cannot be placed beside resident pair workgroups -- the
-                // pass crawls for the pair kernel's 600 us and then runs its 240 us alone (876 us in all).  Holding the pair kernel back
-                // until the plane pass has ENDED (an event), with gather, lists and the listed terms in front of the wait, gives the plane
-                // pass the chip (381 us beside the listed terms) -- and then the pair kernel and the inverse-z / gather pass stretch each
-                // other to 690 us: 139.9 against 134.8 ms per 100 steps of 16 DHFR replicas, +30 % on host-guest and alanine.  At this
-                // size the step is the SUM of its kernels' stand-alone times whatever the order (profiles/r06_12_dhfr_pair_after_plane_pass.txt).
-                static const int env_pax = getenv("REMD_PAIR_AFTER_XY") ? atoi(getenv("REMD_PAIR_AFTER_XY")) : -1;
-                h->pair_after_xy = !with_energy && (class_mask & 63u) == 63u && env_pax > 0;
-                if (h->pair_after_xy && !h->ev_xy) hipEventCreateWithFlags(&h->ev_xy, hipEventDisableTiming);
-                h->xy_recorded = false;
-            }
-            if (listed_main_env && listed_ride_env && !with_energy && !h->sync_events && t0.p.prio != 0 && !h->pair_after_xy) {
+            if (h->sw.listed_main && h->sw.listed_ride && !with_energy && !h->sync_events && t0.p.prio != 0) {
                 int total = 0;
                 h->mesh_listed = listed_terms(total);
                 h->mesh_listed_total = total;
@@ -2273,8 +2164,7 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask)
     // kernel on the direct-space stream, as in round 3.
     // (only in the mode in which the direct-space stream is the critical one, chosen by the tuner together with the wave priority:
     // on a system whose mesh chain is the longer branch the extra work on the main stream costs what it saves here)
-    const bool pax = forked && h->pair_after_xy;
-    const bool listed_main = listed_main_env && forked && !with_energy && !h->sync_events && h->nb_method != REMD_NB_NONE && g_nb[h].p.prio != 0 && !pax;
+    const bool listed_main = h->sw.listed_main && forked && !with_energy && !h->sync_events && h->nb_method != REMD_NB_NONE && g_nb[h].p.prio != 0;
     // the restraints (restraints.hip) go with the listed terms: the launch of a force-only evaluation on the stream the listed terms take
     // (the main stream when those rode in the spreading launch), behind the torsions of an energy evaluation
     int rc_rst = 0;
@@ -2300,15 +2190,9 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask)
         // let the integrator chain that consumes this evaluation poll the scatter's done counter (remd_fold_args) instead of a flag
         // from a signal launch: only where that chain is certain to be the next launch on the main stream (remd_run_steps, plain
         // single-group programs) and in the mode in which the direct-space stream is the critical one; REMD_NB_FOLD=0: signal launch
-        const bool fold_env = !(getenv("REMD_NB_FOLD") && atoi(getenv("REMD_NB_FOLD")) == 0);
-        h->fold_pending = fold_env && listed_main && merged && h->defer_join_ok && do_nb && (class_mask & 63u) == 63u && t.sorting && t.clusters &&
+        h->fold_pending = h->sw.nb_fold && listed_main && merged && h->defer_join_ok && do_nb && (class_mask & 63u) == 63u && t.sorting && t.clusters &&
                           t.lj_split && t.d_lj_sci_list && t.d_sci_list && h->profiling != 2;
         h->fold.done = nullptr;                  // (launch_nb fills remd_fold_args where it takes the request)
-        bool listed_early = false;
-        if (pax && h->xy_recorded) {
-            if (merged) { launch_listed(h->stream); listed_early = true; }      // beside the spreading and the plane pass
-            hipStreamWaitEvent(h->stream, h->ev_xy, 0); h->xy_recorded = false;
-        }
         if (do_nb) {
             remd_prof_scope ps(h, "nonbonded");
             if (with_energy) {
@@ -2322,7 +2206,7 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask)
             }
         }
         h->fold_pending = h->fold_pending && h->fold.done != nullptr;
-        if (merged && !listed_main && !listed_early) launch_listed(h->stream);
+        if (merged && !listed_main) launch_listed(h->stream);
         if (!merged && t.n_exc > 0) {
             remd_prof_scope ps(h, "exceptions");
             LAUNCH_E(exception_kernel, dim3(R), dim3(256), 0, h->stream, t.n_exc, t.d_exc_atoms, t.d_exc_params, t.d_exc_alch,

@@ -547,9 +547,9 @@ static float gb_state_lambda(remd_ctx* h, int k)
 }
 
 // the one-launch kernel for up to 64 atoms without a cutoff (REMD_GB_SMALL=0: the three launches, for the A/B and the tests of the large path)
-static bool gb_small(const gbsa_tables& t)
+static bool gb_small(const remd_ctx* h, const gbsa_tables& t)
 {
-    return t.method == GB_CUT_NONE && t.N <= 64 && !(getenv("REMD_GB_SMALL") && atoi(getenv("REMD_GB_SMALL")) == 0);
+    return t.method == GB_CUT_NONE && t.N <= 64 && h->sw.gb_small;
 }
 
 // the three launches of one evaluation: I -> B, energies + dE/dB, the chain rule through B (no chain without forces)
@@ -593,7 +593,7 @@ int remd_gbsa_forces(remd_ctx* h, bool with_energy, int ep_slot)
     if (t.any_alch) for (int r = 0; r < h->R; ++r) lam[r] = gb_state_lambda(h, h->labels.empty() ? 0 : (int)h->labels[h->r_begin + r]);
     if ((rc = gb_set_lambdas(h, t, lam))) return rc;
     remd_prof_scope ps(h, "gbsa");
-    if (gb_small(t)) {
+    if (gb_small(h, t)) {
         if (with_energy) hipLaunchKernelGGL((gb_small_kernel<true, true>), dim3(h->R), dim3(1024), 0, h->stream, t.N, h->Npad, t.k, t.tau, t.sasa, t.d_par, t.d_lam, 1, h->d_pos, h->d_force, h->d_epart, h->n_epart, ep_slot, 0);
         else hipLaunchKernelGGL((gb_small_kernel<false, true>), dim3(h->R), dim3(1024), 0, h->stream, t.N, h->Npad, t.k, t.tau, t.sasa, t.d_par, t.d_lam, 1, h->d_pos, h->d_force, (double*)nullptr, 0, 0, 0);
         REMD_CHECK(h, hipGetLastError());
@@ -630,7 +630,7 @@ int remd_gbsa_ukl(remd_ctx* h, double* d_alch)
         }
     }
     for (int k = 0; k < h->K; ++k) {
-        if (gb_small(t)) {
+        if (gb_small(h, t)) {
             hipLaunchKernelGGL((gb_small_kernel<true, false>), dim3(h->R), dim3(1024), 0, h->stream, t.N, h->Npad, t.k, t.tau, t.sasa, t.d_par, t.d_state_lam + k, 0, h->d_pos, (long long*)nullptr, d_alch, h->K, k, 1);
             continue;
         }

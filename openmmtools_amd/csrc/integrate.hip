@@ -277,7 +277,7 @@ __device__ __forceinline__ float3 gaussian3(uint64_t seed, uint32_t stream, uint
 }
 
 // the whole chain of substeps for one constraint unit, everything in registers
-template <int TYPE, int NAT, bool LOADS>
+template <int TYPE, int NAT>
 __device__ __forceinline__ float3 run_unit(const chain_prog& prog, const int* idx, const float* dist, const settle_const& sc,
                                           float tol, int Npad, float4* __restrict__ P, float4* __restrict__ V,
                                           const long long* F, long long* Fw, const float* __restrict__ invmass, float kT,
@@ -295,14 +295,6 @@ __device__ __forceinline__ float3 run_unit(const chain_prog& prog, const int* id
         return ke; };
     if (first) {
         S.heat = 0.f; S.shadow = 0.f;
-        if (LOADS) {
-#pragma unroll
-            for (int k = 0; k < NAT; ++k) {
-                const float4 p = P[idx[k]], w = V[idx[k]];
-                x[k] = f3(p.x, p.y, p.z); v[k] = f3(w.x, w.y, w.z);
-                im[k] = invmass[idx[k]];
-            }
-        }
 #ifdef CHAIN_STAMPS
         if (S.stamps) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long now = wall_clock64(); atomicAdd(&S.stamps[1 + 21], now - S.t_last); S.t_last = now; }
 #endif
@@ -419,7 +411,6 @@ __device__ __forceinline__ float3 run_unit(const chain_prog& prog, const int* id
     return mom;
 }
 
-template <bool EARLY>
 __device__ __forceinline__ void integrate_chain_body(chain_prog prog, int n_units, const int4* __restrict__ unit_atoms,
                             const unsigned char* __restrict__ unit_type, const float* __restrict__ shake_dist,
                             settle_const sc, float tol,
@@ -432,10 +423,9 @@ __device__ __forceinline__ void integrate_chain_body(chain_prog prog, int n_unit
                             unsigned long long* own_time, long long* __restrict__ work, float4* __restrict__ xold, float4* __restrict__ vold,
                             remd_fold_args fold, const unsigned int* __restrict__ noise_id)
 {
-    // EARLY: what does not depend on the forces travels while this workgroup waits for them (or, when they are complete already, all
-    // at once instead of table -> type -> distances and label -> beta one round trip after the other): the unit table, positions,
-    // velocities, masses, the state's temperature.  Positions and velocities are written by the previous chain launch of this stream
-    // only.  (Not in the two-per-CU compilation: the longer live ranges are 34 more spilled registers there.)
+    // What does not depend on the forces travels while this workgroup waits for them (or, when they are complete already, all at once
+    // instead of table -> type -> distances and label -> beta one round trip after the other): the unit table, positions, velocities,
+    // masses, the state's temperature.  Positions and velocities are written by the previous chain launch of this stream only.
     const int uidx = blockIdx.x * blockDim.x + threadIdx.x;
     const int r = blockIdx.y;
     int4 a4 = make_int4(-1, -1, -1, -1);
@@ -445,7 +435,7 @@ __device__ __forceinline__ void integrate_chain_body(chain_prog prog, int n_unit
     uint32_t rg = 0u;
     unit_regs S;
     S.have_cm = 0; S.shake_it = 0;
-    if (EARLY) {
+    {
         if (uidx < n_units) {
             a4 = unit_atoms[uidx]; type = (int)unit_type[uidx];
             dist[0] = shake_dist[uidx * 3]; dist[1] = shake_dist[uidx * 3 + 1]; dist[2] = shake_dist[uidx * 3 + 2];
@@ -506,13 +496,6 @@ __device__ __forceinline__ void integrate_chain_body(chain_prog prog, int n_unit
         long long* o = cmm + ((size_t)(1 - cmm_r_eff) * gridDim.y + r) * 4;
         o[0] = 0; o[1] = 0; o[2] = 0;
     }
-    if (!EARLY) {
-        if (uidx < n_units) a4 = unit_atoms[uidx];
-        if (a4.x >= 0) type = (int)unit_type[uidx];
-        if (a4.x >= 0 && type == UNIT_SHAKE) { dist[0] = shake_dist[uidx * 3]; dist[1] = shake_dist[uidx * 3 + 1]; dist[2] = shake_dist[uidx * 3 + 2]; }
-        kT = frcp((float)beta[labels[r_begin + r]]);
-        rg = noise_id ? noise_id[r] : (uint32_t)(r_begin + r);
-    }
     const bool active = a4.x >= 0;                              // padding units do nothing (but take part in the 'M' barrier)
     if (!active) type = UNIT_FREE;
     const int idx[4] = { a4.x, a4.y, a4.z, a4.w };
@@ -527,11 +510,7 @@ __device__ __forceinline__ void integrate_chain_body(chain_prog prog, int n_unit
 #endif
     // mesh-column bins: by the workgroup (below, behind the token program) when the columns fit its LDS counters, else atom by atom
     // at the end of run_unit
-#ifdef CHAIN_UNIT_BINS
-    const bool wg_bins = false;
-#else
     const bool wg_bins = bins.count != nullptr && bins.nx <= CHAIN_BIN_COLS;
-#endif
     remd_chain_bins unit_bins = bins;
     if (wg_bins) unit_bins.count = nullptr;
 #ifdef CHAIN_STAMPS
@@ -543,7 +522,7 @@ __device__ __forceinline__ void integrate_chain_body(chain_prog prog, int n_unit
         while (t1 < prog.n && chain_tok(prog, t1) != 'M') ++t1;
         const bool first = t0 == 0, last = t1 == prog.n;
         if (active) {
-#define RUN(TY, NA) mom = run_unit<TY, NA, !EARLY>(prog, idx, dist, sc, tol, Npad, P, V, F, Fw, invmass, kT, rg, seed, cr, inv_total_mass, unit_bins, r, S, t0, t1, first, last, xold ? xold + (size_t)r * Npad : nullptr, vold ? vold + (size_t)r * Npad : nullptr)
+#define RUN(TY, NA) mom = run_unit<TY, NA>(prog, idx, dist, sc, tol, Npad, P, V, F, Fw, invmass, kT, rg, seed, cr, inv_total_mass, unit_bins, r, S, t0, t1, first, last, xold ? xold + (size_t)r * Npad : nullptr, vold ? vold + (size_t)r * Npad : nullptr)
             if (type == UNIT_SETTLE) RUN(UNIT_SETTLE, 3);
             else if (type == UNIT_FREE) { if (a4.y < 0) RUN(UNIT_FREE, 1); else RUN(UNIT_FREE, 4); }
             else if (a4.z < 0) RUN(UNIT_SHAKE, 2);
@@ -687,16 +666,21 @@ __device__ __forceinline__ void integrate_chain_body(chain_prog prog, int n_unit
     }
 }
 
-// Two compilations of the same body.  The integrator's working set under the widest unit type is 256 VGPRs + AGPRs = one wavefront per
-// SIMD, one workgroup per CU; a grid larger than the chip then runs in rounds (DHFR x 16: 512 workgroups).  The second compilation is held
-// to two wavefronts per SIMD (256 registers in all: the four-atom X-H path spills, the water path -- 238 -- does not) and takes such grids
-// in one round.
-#define CHAIN_PARAMS chain_prog prog, int n_units, const int4* __restrict__ unit_atoms, const unsigned char* __restrict__ unit_type, const float* __restrict__ shake_dist, settle_const sc, float tol, int Npad, float4* __restrict__ pos, float4* __restrict__ vel, long long* force, const float* __restrict__ invmass, const int64_t* __restrict__ labels, const double* __restrict__ beta, int r_begin, uint64_t seed, long long* __restrict__ cmm, float inv_total_mass, unsigned int* join_flag, unsigned int join_seq, remd_chain_bins bins, unsigned long long* chain_slots, unsigned int* chain_sync_err, unsigned long long* own_time, long long* __restrict__ work, float4* __restrict__ xold, float4* __restrict__ vold, remd_fold_args fold, const unsigned int* __restrict__ noise_id
-#define CHAIN_ARGS prog, n_units, unit_atoms, unit_type, shake_dist, sc, tol, Npad, pos, vel, force, invmass, labels, beta, r_begin, seed, cmm, inv_total_mass, join_flag, join_seq, bins, chain_slots, chain_sync_err, own_time, work, xold, vold, fold, noise_id
+// The integrator's working set under the widest unit type is 256 VGPRs + AGPRs = one wavefront per SIMD, one workgroup per CU; a grid
+// larger than the chip then runs in rounds (DHFR x 16: 512 workgroups).  (The body stays a function of its own: it works on copies of
+// the arguments, the kernel's parameters would be read in place -- another instruction stream.)
 __global__ __launch_bounds__(256)
-void integrate_chain_kernel(CHAIN_PARAMS) { integrate_chain_body<true>(CHAIN_ARGS); }
-__global__ __launch_bounds__(256, 2)
-void integrate_chain2_kernel(CHAIN_PARAMS) { integrate_chain_body<false>(CHAIN_ARGS); }
+void integrate_chain_kernel(chain_prog prog, int n_units, const int4* __restrict__ unit_atoms, const unsigned char* __restrict__ unit_type,
+                            const float* __restrict__ shake_dist, settle_const sc, float tol, int Npad, float4* __restrict__ pos,
+                            float4* __restrict__ vel, long long* force, const float* __restrict__ invmass, const int64_t* __restrict__ labels,
+                            const double* __restrict__ beta, int r_begin, uint64_t seed, long long* __restrict__ cmm, float inv_total_mass,
+                            unsigned int* join_flag, unsigned int join_seq, remd_chain_bins bins, unsigned long long* chain_slots,
+                            unsigned int* chain_sync_err, unsigned long long* own_time, long long* __restrict__ work, float4* __restrict__ xold,
+                            float4* __restrict__ vold, remd_fold_args fold, const unsigned int* __restrict__ noise_id)
+{
+    integrate_chain_body(prog, n_units, unit_atoms, unit_type, shake_dist, sc, tol, Npad, pos, vel, force, invmass, labels, beta, r_begin, seed,
+                         cmm, inv_total_mass, join_flag, join_seq, bins, chain_slots, chain_sync_err, own_time, work, xold, vold, fold, noise_id);
+}
 
 // Maxwell-Boltzmann velocities (mcmc.py:710-711): v = sqrt(kT/m) xi, then velocity constraints.
 template <int TYPE, int NAT>
@@ -923,23 +907,18 @@ static void launch_chain(remd_ctx* h, const unit_tables& ut, const chain_prog& p
     // critical path); the blocks of a phased propagation bin with a launch of their own, which runs beside the other block's kernels while
     // the chain is the serial part of both (24 x alanine dipeptide: 17.5 -> 18.2 it/s; one block of 8 x CB7:B2: 13.2 -> 12.2 the other way;
     // profiles/r06_45).  REMD_PME_CHAINBIN=0 / 1 pins it (bit-identical either way: the order inside a bin is irrelevant).
-    static const int chainbin_env = getenv("REMD_PME_CHAINBIN") ? atoi(getenv("REMD_PME_CHAINBIN")) : -1;
     // (a block whose chain grid is several rounds of the chip -- 64 x DHFR: 2 048 workgroups -- keeps them too: there the epilogue is
     // amortised over the rounds and the binning launch is the dearer one, 3.38 -> 3.46 s per iteration of 128 x DHFR without this bound)
-    const bool chain_bins = chainbin_env >= 0 ? chainbin_env != 0
-                                              : (h->parent == nullptr || (long long)((ut.n_units + 255) / 256) * h->R > 1024);
+    const bool chain_bins = h->sw.pme_chainbin >= 0 ? h->sw.pme_chainbin != 0
+                                                    : (h->parent == nullptr || (long long)((ut.n_units + 255) / 256) * h->R > 1024);
     const remd_chain_bins bins = (bin_for_pme && chain_bins) ? remd_pme_chain_bins(h) : remd_chain_bins();
     remd_prof_scope ps(h, "integrate_chain");
     dim3 grid((ut.n_units + 255) / 256, h->R);
-    // The two-per-CU compilation is OPT-IN (REMD_CHAIN_TWO=1).  It takes a grid larger than the chip in one round (DHFR x 16: -1.3 % of the
-    // converged step), but its workgroups hold the WHOLE register file of their CUs while they poll for the forces in the prologue, and a
-    // direct-space stream that still has workgroups to place (one workgroup per work item, the scatter) then never gets a slot: the poll runs
-    // out after seconds (seen at the end of round 5 with 128 alanine replicas = 384 workgroups, and as a 4.8 s stall of the tuner's
-    // one-per-item candidate on DHFR).  One workgroup per CU leaves 160 registers per lane for the kernels the chain waits for.
-    static const char* two_env = getenv("REMD_CHAIN_TWO");
-    const bool two = two_env != nullptr && atoi(two_env) != 0;
-    auto kern = two ? integrate_chain2_kernel : integrate_chain_kernel;
-    hipLaunchKernelGGL(kern, grid, dim3(256), 0, h->stream, prog, ut.n_units, ut.d_atoms, ut.d_type,
+    // (A two-per-CU compilation took a grid larger than the chip in one round (DHFR x 16: -1.3 % of the converged step), but its workgroups
+    // held the WHOLE register file of their CUs while they polled for the forces in the prologue, and a direct-space stream that still had
+    // workgroups to place then never got a slot: the poll ran out after seconds (end of round 5, 128 alanine replicas = 384 workgroups).
+    // Removed; one workgroup per CU leaves 160 registers per lane for the kernels the chain waits for.)
+    hipLaunchKernelGGL(integrate_chain_kernel, grid, dim3(256), 0, h->stream, prog, ut.n_units, ut.d_atoms, ut.d_type,
                        ut.d_dist, ut.sc, (float)fmax(h->constraint_tol, REMD_CONSTRAINT_TOL_FLOOR), h->Npad, h->d_pos, h->d_vel, h->d_force,
                        h->d_invmass, h->d_labels, h->d_beta, h->r_begin, h->seed, h->d_cmm,
                        (float)(h->total_mass > 0 ? 1.0 / h->total_mass : 0.0),
@@ -1238,8 +1217,7 @@ void remd_nb_invalidate_sort(remd_ctx* h);
 static int remd_run_steps_resident(remd_ctx* h, const std::vector<char>& tokens, int nV, int nR, int nO,
                                    int64_t iteration, int64_t first_step, int n_steps)
 {
-    const bool enabled = !(getenv("REMD_RESIDENT") && atoi(getenv("REMD_RESIDENT")) == 0);      // read per call: the parity tests switch it
-    if (!enabled || h->no_resident) return 0;
+    if (!h->sw.resident || h->no_resident) return 0;
     if (h->N > 1024 || h->n_settle > 0 || h->n_shake > 0 || h->n_bonds > 0 || h->n_angles > 0 || h->n_torsions > 0 || h->n_restraints > 0 || h->gbsa) return 0;
     if (h->baro_frequency > 0 || h->profiling == 2 || (int)tokens.size() > MAX_TOK || n_steps < 1) return 0;
     if (h->measure_heat || h->measure_shadow) return 0;
@@ -1263,8 +1241,8 @@ static int remd_run_steps_resident(remd_ctx* h, const std::vector<char>& tokens,
     const size_t fixed = (size_t)T * 32 + 64 * sizeof(float) + (size_t)T * 12 + 8 + (size_t)T * 24;
     const size_t lds_max = 144 * 1024;
     S.list_cap = method >= 0 ? (int)std::min<size_t>(32768, (lds_max - fixed) / 4) : 0;
-    if (getenv("REMD_RESIDENT_CAP")) S.list_cap = std::max(1, std::min(S.list_cap, atoi(getenv("REMD_RESIDENT_CAP"))));      // test hook: provoke the overflow path
-    if (method >= 0 && S.list_cap < 4 * h->N && !getenv("REMD_RESIDENT_CAP")) return 0;
+    if (h->sw.resident_cap) S.list_cap = std::max(1, std::min(S.list_cap, h->sw.resident_cap));      // test hook: provoke the overflow path
+    if (method >= 0 && S.list_cap < 4 * h->N && !h->sw.resident_cap) return 0;
     const size_t lds = fixed + (size_t)S.list_cap * 4;
     resident_prog prog{};
     prog.n = (int)tokens.size();
@@ -1523,12 +1501,10 @@ void resident_mol_kernel(resident_prog prog, resident_mol_sys S, float4* __restr
 static int remd_run_steps_resident_mol(remd_ctx* h, const std::vector<char>& tokens, int nV, int nR, int nO,
                                        int64_t iteration, int64_t first_step, int n_steps)
 {
-    const bool enabled = !(getenv("REMD_RESIDENT") && atoi(getenv("REMD_RESIDENT")) == 0);      // read per call: the parity tests switch it
-    if (!enabled || h->no_resident) return 0;
+    if (!h->sw.resident || h->no_resident) return 0;
     if (!h->nocutoff || h->gbsa || h->n_regions > 0 || h->nb_method != REMD_NB_NONE || h->n_ext > 0 || h->n_restraints > 0) return 0;
     const unit_tables& ut = g_units[h];
     if (h->N > RESIDENT_MOL_MAX_ATOMS || ut.n_units > RESIDENT_MOL_T || ut.n_units < 1) return 0;
-    if (getenv("REMD_RESIDENT_MOL") && atoi(getenv("REMD_RESIDENT_MOL")) == 0) return 0;
     if (h->baro_frequency > 0 || h->profiling == 2 || (int)tokens.size() > MAX_TOK || n_steps < 1) return 0;
     if (h->measure_heat || h->measure_shadow) return 0;
     for (char c : tokens) if (c != 'V' && c != 'R' && c != 'O') return 0;
@@ -1647,12 +1623,11 @@ struct step_runner {
         // the centre-of-mass motion remover needs sum(m v) over the whole replica between two tokens of a step: either two launches
         // (the first ends with the sum) or one launch with a barrier over the replica's workgroups in device memory ('M' token) --
         // every workgroup of the grid must then be resident at once, hence the bound on the grid
-        const bool merge_env = !(getenv("REMD_CHAIN_MERGE") && atoi(getenv("REMD_CHAIN_MERGE")) == 0);
         const long long chain_blocks = (long long)((ut->n_units + 255) / 256) * h->R;
         // (the same bound holds for the join polled in the chain's prologue: spinning workgroups of a grid larger than the chip
         // holds at once could keep the direct-space stream's last launches from ever being dispatched)
         device_waits_ok = chain_blocks <= 1024 && !h->no_device_waits;
-        merge_cmm = merge_env && device_waits_ok && h->profiling != 2 && !h->lean_waits && !h->no_chain_barrier && !h->no_chain_merge;
+        merge_cmm = h->sw.chain_merge && device_waits_ok && h->profiling != 2 && !h->lean_waits && !h->no_chain_barrier && !h->no_chain_merge;
         const long long sync_key = (long long)h->R * 1000003ll + ut->n_units;
         if (merge_cmm && (!h->d_chain_sync || h->chain_sync_key != sync_key)) {      // slots of THIS grid shape
             if (h->d_chain_sync) { REMD_CHECK(h, hipStreamSynchronize(h->stream)); hipFree(h->d_chain_sync); h->d_chain_sync = nullptr; }

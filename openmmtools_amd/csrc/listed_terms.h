@@ -10,9 +10,6 @@
 __device__ __forceinline__ void add_force(long long* __restrict__ F, int Npad, int i, float fx, float fy, float fz)
 {
     unsigned long long* U = reinterpret_cast<unsigned long long*>(F);
-#ifdef EXP_NOATOM          // knock-out probe (tools/build_variant.sh -DEXP_NOATOM): the arithmetic stays, the atomics go (results wrong on purpose)
-    if (fx != 1.2345e33f) return;
-#endif
     atomicAdd(&U[i],            remd_f2fix(fx));
     atomicAdd(&U[Npad + i],     remd_f2fix(fy));
     atomicAdd(&U[2 * Npad + i], remd_f2fix(fz));

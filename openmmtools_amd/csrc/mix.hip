@@ -72,13 +72,10 @@ __global__ __launch_bounds__(1024)
 void mix_swap_all_kernel(uint64_t seed, int64_t iteration, int R, int K, int ld,
                          const double* __restrict__ g_ukl, int64_t* __restrict__ g_labels,
                          unsigned long long* __restrict__ g_nacc, unsigned long long* __restrict__ g_nprop,
-                         int64_t n_attempts, int stats_in_lds, long long* __restrict__ g_dbg, unsigned int* __restrict__ g_log)
+                         int64_t n_attempts, int stats_in_lds, unsigned int* __restrict__ g_log)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, W = blockDim.x, nw = W >> 6;
-    long long dbg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long t0 = clock64(), w0 = wall_clock64();
-#define MIX_TICK(slot) do { if (g_dbg) { long long t1 = clock64(); dbg[slot] += t1 - t0; t0 = t1; } } while (0)
     const int Rpad = (R + 1) & ~1;
     double* s_u = reinterpret_cast<double*>(smem);
     unsigned long long* s_touch = reinterpret_cast<unsigned long long*>(smem + (UKL_LDS ? (size_t)R * K * sizeof(double) : 0));   // [R][nw]
@@ -100,7 +97,6 @@ void mix_swap_all_kernel(uint64_t seed, int64_t iteration, int R, int K, int ld,
     int sweep = 0;      // running sweep counter: selects the rotating flag slot
     int cur_lab = 0;    // which half of s_lab holds the labels at window start
 
-    MIX_TICK(0);
     for (int64_t base = 0; base < n_attempts;) {
         const int64_t k = base + tid;
         const bool active = k < n_attempts;
@@ -136,7 +132,6 @@ void mix_swap_all_kernel(uint64_t seed, int64_t iteration, int R, int K, int ld,
             s_chain[j * MIX_CHAIN + ord_j] = (unsigned)i | ((unsigned)ord_i << 16);
         }
         mix_barrier();
-        MIX_TICK(1);
 
         bool acc = false;
         int a_seen = -1, b_seen = -1, si = 0, sj = 0;
@@ -161,10 +156,8 @@ void mix_swap_all_kernel(uint64_t seed, int64_t iteration, int R, int K, int ld,
             }
             if (tid == 0) s_flag[(sweep + 1) % 3] = 0;
             mix_barrier();
-            dbg[5] += 1;
             if (!s_flag[sweep % 3]) { ++sweep; break; }
         }
-        MIX_TICK(2);
         // decisions are final: counts (:339-340, :348-349) and the labels after the window (:345-346)
         if (live) {
             if (stats_in_lds) {
@@ -187,9 +180,7 @@ void mix_swap_all_kernel(uint64_t seed, int64_t iteration, int R, int K, int ld,
         cur_lab ^= 1;
         base += weff;
         mix_barrier();
-        MIX_TICK(3);
     }
-    if (g_dbg && tid == 0) { for (int q = 0; q < 8; ++q) g_dbg[q] = dbg[q]; g_dbg[6] = wall_clock64() - w0; }
     for (int t = tid; t < R; t += W) g_labels[t] = (int64_t)s_lab[cur_lab * Rpad + t];
     if (stats_in_lds)
         for (int t = tid; t < K * K; t += W) { g_nprop[t] = s_nprop[t]; g_nacc[t] = s_nacc[t]; }
@@ -220,12 +211,10 @@ __global__ __launch_bounds__(1024)
 void mix_swap_all_dataflow_kernel(uint64_t seed, int64_t iteration, int R, int K, int ld,
                                   const double* __restrict__ g_ukl, int64_t* __restrict__ g_labels,
                                   unsigned long long* __restrict__ g_nacc, unsigned long long* __restrict__ g_nprop,
-                                  int64_t n_attempts, int stats_in_lds, long long* __restrict__ g_dbg, unsigned int* __restrict__ g_log)
+                                  int64_t n_attempts, int stats_in_lds, unsigned int* __restrict__ g_log)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, W = blockDim.x, nw = W >> 6;
-    long long dbg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long t0 = clock64(), w0 = wall_clock64();
     double* s_u = reinterpret_cast<double*>(smem);
     unsigned long long* s_touch = reinterpret_cast<unsigned long long*>(smem + (UKL_LDS ? (size_t)R * K * sizeof(double) : 0));   // [R][nw]
     unsigned long long* s_slot = s_touch + (size_t)R * nw;                       // [R] label | executed attempts of the window << 32
@@ -239,7 +228,6 @@ void mix_swap_all_dataflow_kernel(uint64_t seed, int64_t iteration, int R, int K
     if (stats_in_lds) for (int t = tid; t < 2 * K * K; t += W) s_nprop[t] = 0u;
     __syncthreads();
     const int ldu = UKL_LDS ? K : ld;
-    MIX_TICK(0);
     for (int64_t base = 0; base < n_attempts; base += W) {
         const int64_t k = base + tid;
         const bool active = k < n_attempts;
@@ -261,7 +249,6 @@ void mix_swap_all_dataflow_kernel(uint64_t seed, int64_t iteration, int R, int K
             for (int q = 0; q < wi; ++q) { ord_i += __popcll(ti[q]); ord_j += __popcll(tj[q]); }
             ord_i += __popcll(ti[wi] & low); ord_j += __popcll(tj[wi] & low);
         }
-        MIX_TICK(1);
         // u < exp(log_p) is decided by log_p - log(u) wherever that is not a borderline case (|difference| > 1e-9, far above
         // the error of either function); the borderline falls back to the deterministic exp the oracle uses, so the decision
         // is the oracle's bit for bit while the 18 dependent f64 operations of that exp stay off the dependency chain
@@ -291,7 +278,6 @@ void mix_swap_all_dataflow_kernel(uint64_t seed, int64_t iteration, int R, int K
                     pending = false;
                 }
             }
-            dbg[5] += 1;
         }
         if (active) {                                    // counts (:339-340, :348-349), off the dependency chain
             if (stats_in_lds) {
@@ -304,14 +290,11 @@ void mix_swap_all_dataflow_kernel(uint64_t seed, int64_t iteration, int R, int K
                 if (acc) { atomicAdd(&g_nacc[(size_t)si * K + sj], 1ull); atomicAdd(&g_nacc[(size_t)sj * K + si], 1ull); }
             }
         }
-        MIX_TICK(2);
         mix_barrier();                                   // every attempt of the window has run
         for (int t = tid; t < R * nw; t += W) s_touch[t] = 0ull;
         for (int t = tid; t < R; t += W) s_slot[t] &= 0xffffffffull;          // keep the labels, restart the counts
         mix_barrier();
-        MIX_TICK(3);
     }
-    if (g_dbg && tid == 0) { for (int q = 0; q < 8; ++q) g_dbg[q] = dbg[q]; g_dbg[6] = wall_clock64() - w0; }
     for (int t = tid; t < R; t += W) g_labels[t] = (int64_t)(unsigned)s_slot[t];
     if (stats_in_lds)
         for (int t = tid; t < K * K; t += W) { g_nprop[t] = s_nprop[t]; g_nacc[t] = s_nacc[t]; }
@@ -401,15 +384,13 @@ void mix_swap_all_pre_kernel(uint64_t seed, int64_t iteration, int R, int K, int
                              int64_t* __restrict__ g_labels, int64_t n_attempts, const uint4* __restrict__ g_rec,
                              const unsigned* __restrict__ g_piece, const unsigned* __restrict__ g_npiece,
                              const unsigned char* __restrict__ g_cnt, int Rpad_cnt, unsigned int* __restrict__ g_log,
-                             long long* __restrict__ g_dbg, const unsigned* __restrict__ g_err)
+                             const unsigned* __restrict__ g_err)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // (a window of mix_prep_kernel needed more than MIXP pieces: nothing is touched here, the host runs the one-kernel path when it
     // reads the flag at the end of the call -- no host round trip between the two launches)
     if (*g_err) return;
     const int tid = threadIdx.x, W = blockDim.x;
-    long long dbg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long t0 = clock64(), w0 = wall_clock64();
     const int Rpad = (R + 1) & ~1;
     double* s_u = reinterpret_cast<double*>(smem);
     unsigned* s_chain = reinterpret_cast<unsigned*>(smem + (UKL_LDS ? (size_t)R * K * sizeof(double) : 0));   // [R][32]
@@ -425,7 +406,6 @@ void mix_swap_all_pre_kernel(uint64_t seed, int64_t iteration, int R, int K, int
     const double* U = UKL_LDS ? s_u : g_ukl;
     const int64_t n_win = (n_attempts + W - 1) / W;
     int sweep = 0, cur_lab = 0;
-    MIX_TICK(0);
     // records of the next window's first piece travel while this window is decided
     unsigned pc_next = n_win > 0 ? g_piece[0] : 0u, np_next = n_win > 0 ? g_npiece[0] : 0u;
     uint4 rec_next = make_uint4(0u, 0u, 0u, 0u);
@@ -457,7 +437,6 @@ void mix_swap_all_pre_kernel(uint64_t seed, int64_t iteration, int R, int K, int
                 s_chain[j * MIX_CHAIN + ord_j] = (unsigned)i | ((unsigned)ord_i << 16);
             }
             mix_barrier();
-            MIX_TICK(1);
             bool acc = false;
             int a_seen = -1, b_seen = -1, si = 0, sj = 0;
             for (;; ++sweep) {
@@ -490,20 +469,16 @@ void mix_swap_all_pre_kernel(uint64_t seed, int64_t iteration, int R, int K, int
                 }
                 if (tid == 0) s_flag[(sweep + 1) % 3] = 0;
                 mix_barrier();
-                dbg[5] += 1;
                 if (!s_flag[sweep % 3]) { ++sweep; break; }
             }
-            MIX_TICK(2);
             if (live) g_log[k] = (unsigned)si | ((unsigned)sj << 15) | (acc ? (1u << 30) : 0u) | (1u << 31);
             const unsigned char* cnt = g_cnt + ((size_t)win * MIXP + p) * Rpad_cnt;
             for (int r = tid; r < R; r += W)
                 lab1[r] = lab0[mix_origin(s_accb, s_chain, r, s_accb[r] & mix_below((int)cnt[r]))];
             cur_lab ^= 1;
             mix_barrier();
-            MIX_TICK(3);
         }
     }
-    if (g_dbg && tid == 0) { for (int q = 0; q < 8; ++q) g_dbg[q] = dbg[q]; g_dbg[6] = wall_clock64() - w0; }
     for (int t = tid; t < R; t += W) g_labels[t] = (int64_t)s_lab[cur_lab * Rpad + t];
 }
 
@@ -615,8 +590,7 @@ struct mix_pre_buffers {
     unsigned* piece = nullptr; unsigned* npiece = nullptr; size_t win_n = 0;
     unsigned char* cnt = nullptr; size_t cnt_n = 0;
     unsigned* err = nullptr;
-    long long* dbg = nullptr;             // REMD_MIX_DEBUG phase counters (per handle: handles may live on different devices)
-    ~mix_pre_buffers() { hipFree(rec); hipFree(piece); hipFree(npiece); hipFree(cnt); hipFree(err); hipFree(dbg); }
+    ~mix_pre_buffers() { hipFree(rec); hipFree(piece); hipFree(npiece); hipFree(cnt); hipFree(err); }
 };
 static handle_table<mix_pre_buffers> g_mix_pre;
 void remd_mix_release(remd_ctx* h) { g_mix_pre.erase(h); }
@@ -642,20 +616,15 @@ int remd_mix_launch(remd_ctx* h, int scheme, int64_t iteration, int R, int K, in
         if (n_attempts < 0) n_attempts = (int64_t)R * R * R;                                   // :269
         size_t ukl_bytes = (size_t)R * K * sizeof(double);
         if (R > 32767) return remd_fail(h, -3, "swap-all supports at most 32767 replicas");
-        // window = 6R attempts (conflict probability between two attempts ~4/R), whole wavefronts, <= 768 threads (measured optimum)
-        const int force_waves = 0;
-        int waves = force_waves > 0 ? force_waves : (4 * R + 63) / 64;
-        waves = std::max(1, std::min(16, waves));
-        // window of 6 R attempts (21.9 ms at R = 128: DESIGN.md 7b; the dataflow kernel: 43.9 ms, 45.5 at 4 R, 52 at 2 R); REMD_MIX_PERR: experiments
-        const int per_r = getenv("REMD_MIX_PERR") ? std::max(1, atoi(getenv("REMD_MIX_PERR"))) : 6;
-        const int max_waves = 12;
-        if (force_waves <= 0) waves = std::max(1, std::min(max_waves, (per_r * R + 63) / 64));
+        // window of 6 R attempts (conflict probability between two attempts ~4/R; 21.9 ms at R = 128: DESIGN.md 7b; the dataflow kernel:
+        // 43.9 ms, 45.5 at 4 R, 52 at 2 R), whole wavefronts, <= 768 threads (measured optimum)
+        int waves = std::max(1, std::min(12, (6 * R + 63) / 64));
         while (waves > 1 && (size_t)R * waves * 8 > 64 * 1024) --waves;      // occupancy masks [R][waves] u64
         const size_t Rp = (size_t)((R + 1) & ~1);
         auto work_for = [&](int wv) { return 8 * (size_t)R * wv + 4 * (size_t)R * 32 + 4 * Rp + 8 * Rp + 16; };
         // a slightly shorter window (>= 5R attempts) that lets u_kl stay in LDS beats a longer one reading it from L2
         // (R = 128: 10 wavefronts, 21.9 ms instead of 25.0 ms with 12; measured, tools/mix_microbench.py)
-        if (force_waves <= 0 && ukl_bytes + work_for(waves) > 156 * 1024)
+        if (ukl_bytes + work_for(waves) > 156 * 1024)
             for (int wv = waves - 1; wv >= std::max(1, (5 * R + 63) / 64); --wv)
                 if (ukl_bytes + work_for(wv) <= 156 * 1024) { waves = wv; break; }
         const size_t work_bytes = work_for(waves);
@@ -671,20 +640,11 @@ int remd_mix_launch(remd_ctx* h, int scheme, int64_t iteration, int R, int K, in
         // (43 ms) where speculation degrades (45 % on an alchemical ladder -> 116 ms); the acceptance of the handle's previous
         // swap-all call decides, crossover measured at 15-20 % for R = 16 ... 128 (profiles/r03_g_mix_kernels.txt).
         // REMD_MIX_FLOW = 0 / 1 pins the kernel (parity tests).
-        const char* flow_env = getenv("REMD_MIX_FLOW");
-        const int flow = flow_env ? atoi(flow_env) : (h->mix_acc_rate > 0.17 ? 1 : 0);
-        static const bool debug = getenv("REMD_MIX_DEBUG") != nullptr;
-        long long* d_dbg = nullptr;
-        if (debug) {
-            mix_pre_buffers& Bd = g_mix_pre[h];
-            if (!Bd.dbg) REMD_CHECK(h, hipMalloc(&Bd.dbg, 8 * sizeof(long long)));
-            d_dbg = Bd.dbg;
-        }
+        const int flow = h->sw.mix_flow >= 0 ? h->sw.mix_flow : (h->mix_acc_rate > 0.17 ? 1 : 0);
         h->mix_pre_launched = false;
         // speculative windows with the label-independent part hoisted into a whole-chip kernel (mix_prep_kernel); REMD_MIX_PRE=0
         // keeps everything in the one serial workgroup (parity tests run both)
-        const bool pre_off = getenv("REMD_MIX_PRE") && atoi(getenv("REMD_MIX_PRE")) == 0;
-        if (!flow && !pre_off && !h->mix_no_pre && n_attempts > 0 && (size_t)n_attempts * sizeof(unsigned int) <= ((size_t)1 << 30)) {
+        if (!flow && h->sw.mix_pre && !h->mix_no_pre && n_attempts > 0 && (size_t)n_attempts * sizeof(unsigned int) <= ((size_t)1 << 30)) {
             const int W = 64 * waves;
             const int64_t n_win = (n_attempts + W - 1) / W;
             const int Rp4 = (R + 3) & ~3;
@@ -715,17 +675,10 @@ int remd_mix_launch(remd_ctx* h, int scheme, int64_t iteration, int R, int K, in
                 REMD_CHECK(h, hipFuncSetAttribute((const void*)pk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pre_lds));
                 hipLaunchKernelGGL(pk, dim3(1), dim3(W), pre_lds, h->stream, h->seed, iteration, R, K, ld, d_ukl, d_labels, n_attempts,
                                    (const uint4*)B.rec, (const unsigned*)B.piece, (const unsigned*)B.npiece, (const unsigned char*)B.cnt, Rp4,
-                                   h->d_mix_log, d_dbg, (const unsigned*)B.err);
+                                   h->d_mix_log, (const unsigned*)B.err);
                 hipLaunchKernelGGL(mix_stats_from_log_kernel, dim3((unsigned)std::min<int64_t>(4096, (n_attempts + 255) / 256)), dim3(256), 0, h->stream,
                                    n_attempts, h->d_mix_log, K, d_nacc, d_nprop, (const unsigned*)B.err);
                 h->mix_pre_launched = true;
-                if (debug) {
-                    long long hd[8];
-                    REMD_CHECK(h, hipStreamSynchronize(h->stream));
-                    REMD_CHECK(h, hipMemcpy(hd, d_dbg, sizeof(hd), hipMemcpyDeviceToHost));
-                    fprintf(stderr, "[mix-pre] R=%d W=%d lds=%zu ukl_lds=%d cycles: setup %lld chain-build %lld sweeps %lld finalize %lld n_sweeps %lld "
-                            "wall(100MHz ticks) %lld\n", R, W, pre_lds, pre_in_lds, hd[0], hd[1], hd[2], hd[3], hd[5], hd[6]);
-                }
                 REMD_CHECK(h, hipGetLastError());
                 return 0;
             }
@@ -745,17 +698,10 @@ int remd_mix_launch(remd_ctx* h, int scheme, int64_t iteration, int R, int K, in
             d_log = h->d_mix_log;
         }
         hipLaunchKernelGGL(kern, dim3(1), dim3(64 * waves), lds, h->stream,
-                           h->seed, iteration, R, K, ld, d_ukl, d_labels, d_nacc, d_nprop, n_attempts, stats_lds, d_dbg, d_log);
+                           h->seed, iteration, R, K, ld, d_ukl, d_labels, d_nacc, d_nprop, n_attempts, stats_lds, d_log);
         if (d_log)
             hipLaunchKernelGGL(mix_stats_from_log_kernel, dim3((unsigned)std::min<int64_t>(4096, (n_attempts + 255) / 256)), dim3(256), 0, h->stream,
                                n_attempts, d_log, K, d_nacc, d_nprop);
-        if (debug) {
-            long long hd[8];
-            REMD_CHECK(h, hipStreamSynchronize(h->stream));
-            REMD_CHECK(h, hipMemcpy(hd, d_dbg, sizeof(hd), hipMemcpyDeviceToHost));
-            fprintf(stderr, "[mix] R=%d waves=%d lds=%zu ukl_lds=%d stats_lds=%d cycles: setup %lld window-prep %lld sweeps %lld finalize %lld "
-                    "n_sweeps %lld wall(100MHz ticks) %lld\n", R, waves, lds, in_lds, stats_lds, hd[0], hd[1], hd[2], hd[3], hd[5], hd[6]);
-        }
     } else if (scheme == REMD_MIX_SWAP_NEIGHBORS) {
         if (R != K) return remd_fail(h, -3, "swap-neighbors requires n_replicas == n_states");
         size_t lds = sizeof(int) * (size_t)(R + K);

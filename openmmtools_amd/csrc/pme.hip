@@ -788,9 +788,6 @@ void pme_zinv_gather_pow2_kernel(int nx, int ny, const float2* __restrict__ spec
             phi[(2 * n + 1) * NL + l] = w[m * R2 + k2].y;
         }
     __syncthreads();
-#ifdef EXP_ZI_NOGATHER    // knock-out probe: transform only
-    if (phi[tid] != 1.2345e33f) return;
-#endif
     const float Lx = box[4 * r], Ly = box[4 * r + 1], Lz = box[4 * r + 2];
     unsigned long long* F = reinterpret_cast<unsigned long long*>(force + (size_t)r * 3 * Npad);
     unsigned long long* FB = fbin ? fbin + (size_t)r * 3 * fbin_P : (unsigned long long*)nullptr;
@@ -826,9 +823,6 @@ void pme_zinv_gather_pow2_kernel(int nx, int ny, const float2* __restrict__ spec
         }
         if (!any) continue;
         const float Fx = -q * dxa * gx * nx / Lx, Fy = -q * wxa * gy * ny / Ly, Fz = -q * wxa * gz * nz / Lz;
-#ifdef EXP_ZI_NOATOM      // knock-out probe: the gather without its atomics (results wrong on purpose)
-        if (Fx != 1.2345e33f) continue;
-#endif
         if (FB) {
             atomicAdd(&FB[flat], remd_f2fix(Fx));
             atomicAdd(&FB[fbin_P + flat], remd_f2fix(Fy));
@@ -1124,17 +1118,11 @@ static bool factorize(int n, int* radix, int& nrad)
     nrad = 0;
     int m = n;
     // the power of two 2^e in ceil(e / 3) stages of radix 8 / 4 / 2, bits spread evenly (16 = 4 x 4, 32 = 8 x 4, 64 = 8 x 8,
-    // 128 = 8 x 4 x 4): every stage is a pass over the LDS image and two workgroup barriers.  REMD_PME_RADIX8=0: 4s and 2s only.
-    static const bool radix8 = !(getenv("REMD_PME_RADIX8") && atoi(getenv("REMD_PME_RADIX8")) == 0);
+    // 128 = 8 x 4 x 4): every stage is a pass over the LDS image and two workgroup barriers
     int e = 0;
     while (m % 2 == 0) { ++e; m /= 2; }
-    if (radix8) {
-        const int st = (e + 2) / 3;
-        for (int k = 0, left = e; k < st; ++k) { const int b = (left + (st - k) - 1) / (st - k); radix[nrad++] = 1 << b; left -= b; }
-    } else {
-        while (e >= 2) { radix[nrad++] = 4; e -= 2; }
-        if (e) radix[nrad++] = 2;
-    }
+    const int st = (e + 2) / 3;
+    for (int k = 0, left = e; k < st; ++k) { const int b = (left + (st - k) - 1) / (st - k); radix[nrad++] = 1 << b; left -= b; }
     while (m % 3 == 0) { radix[nrad++] = 3; m /= 3; }
     while (m % 5 == 0) { radix[nrad++] = 5; m /= 5; }
     return m == 1 && nrad <= 8;
@@ -1237,10 +1225,10 @@ static int pme_setup_impl(remd_ctx* h, bool full_complex)
         REMD_CHECK(h, hipMalloc(&s->d_grid, sizeof(float2) * s->nspec * s->R));
         REMD_CHECK(h, hipMalloc(&s->d_col_start, sizeof(int) * (size_t)(s->n[0] + 1) * s->R));
         REMD_CHECK(h, hipMalloc(&s->d_col_atoms, sizeof(int) * (size_t)h->Npad * s->R));
-        if (!full_complex && !(getenv("REMD_PME_CHAINBIN") && atoi(getenv("REMD_PME_CHAINBIN")) == 0)) {
+        if (!full_complex && h->sw.pme_chainbin != 0) {
             // four times the mean occupancy of a mesh column (x bins are 1 / nx of a homogeneous box): overflow is detected
             s->cbin_cap = std::min(h->Npad, std::max(64, 4 * ((h->N + s->n[0] - 1) / s->n[0])));
-            if (getenv("REMD_PME_CBIN_CAP")) s->cbin_cap = std::max(1, atoi(getenv("REMD_PME_CBIN_CAP")));      // test hook: provoke the overflow path
+            if (h->sw.pme_cbin_cap) s->cbin_cap = h->sw.pme_cbin_cap;      // test hook: provoke the overflow path
             REMD_CHECK(h, hipMalloc(&s->d_cbin_count, sizeof(int) * 2 * (size_t)s->R * s->n[0]));
             REMD_CHECK(h, hipMemset(s->d_cbin_count, 0, sizeof(int) * 2 * (size_t)s->R * s->n[0]));
             REMD_CHECK(h, hipMalloc(&s->d_cbin_atoms, sizeof(float4) * (size_t)s->R * s->n[0] * s->cbin_cap));
@@ -1304,16 +1292,8 @@ static int pme_setup_impl(remd_ctx* h, bool full_complex)
                 }
             if (ok && (best_cost < 0 || cost < best_cost)) { best_cost = cost; best_t = t; }
         }
-        if (getenv("REMD_PME_XYT")) {            // experiment hook: workgroup size of the plane pass (must leave <= ceil(XY_PPT / radix) slots per thread)
-            const int t = atoi(getenv("REMD_PME_XYT"));
-            bool ok = t >= 64 && t <= 1024 && t % 64 == 0;
-            for (int ax = 0; ax < 2 && ok; ++ax)
-                for (int st = 0; st < s->nrad[ax]; ++st) { const int rx = s->radix[ax][st]; if ((np / rx + t - 1) / t > (XY_PPT + rx - 1) / rx) ok = false; }
-            if (ok) best_t = t;
-        }
         s->xy_threads = best_t > 0 ? best_t : 1024;
         s->xy_fused = best_t > 0 && s->xy_lds <= 160 * 1024;
-        h->xy_lds_bytes = s->xy_fused ? s->xy_lds : 0;
     }
     if (!s->xy_fused && !full_complex) {
         // widest divisor of ny whose slab fits the registers of 256 threads and ~40 KB of LDS
@@ -1339,11 +1319,10 @@ static int pme_setup_impl(remd_ctx* h, bool full_complex)
     }
     // square power-of-two planes: the register-resident pass (REMD_PME_POW2=0: the scheduled mixed-radix passes; 1 / 2: plane pass / z passes only)
     if (s->xy_fused && !full_complex && s->n[0] == s->n[1] && (s->n[0] == 64 || s->n[0] == 128) &&
-        !(getenv("REMD_PME_POW2") && !(atoi(getenv("REMD_PME_POW2")) & 1))) {                 // bit 0: the plane pass
+        (h->sw.pme_pow2 & 1)) {                                                                 // bit 0: the plane pass
         s->xy_pow2 = s->n[0];
         s->xy_threads = s->n[0] == 64 ? 512 : 1024;
         s->xy_lds = sizeof(float2) * ((size_t)s->n[0] * (s->n[0] + 8) + s->n[0]) + sizeof(double) * 16;
-        h->xy_lds_bytes = s->xy_lds;
         REMD_CHECK(h, hipFuncSetAttribute((const void*)pme_xy_pow2_kernel<64, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
         REMD_CHECK(h, hipFuncSetAttribute((const void*)pme_xy_pow2_kernel<64, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
         REMD_CHECK(h, hipFuncSetAttribute((const void*)pme_xy_pow2_kernel<128, 16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -1436,8 +1415,7 @@ int remd_pme_forces(remd_ctx* h, bool with_energy, hipStream_t st, int part)
         const int n_mesh_blocks = (int)zgrid.x;
         const int n_listed_blocks = h->mesh_listed_total > 0 ? (h->mesh_listed_total + ZT - 1) / ZT : 0;
         // power-of-two z: 64 lines per workgroup on the register transforms (REMD_PME_POW2=0: the scheduled passes)
-        const bool pow2_env = !(getenv("REMD_PME_POW2") && !(atoi(getenv("REMD_PME_POW2")) & 2));      // bit 1: the z passes
-        const int zp2 = (pow2_env && half && (nz == 64 || nz == 128) && ny % 64 == 0 && nl == 64 && ZT == 64 * (nz / 16)) ? nz : 0;
+        const int zp2 = ((h->sw.pme_pow2 & 2) && half && (nz == 64 || nz == 128) && ny % 64 == 0 && nl == 64 && ZT == 64 * (nz / 16)) ? nz : 0;
         const size_t zlds2 = sizeof(float2) * (size_t)(nz / 2 + 1) * 64;
         if (zp2) {
             const dim3 zg(zgrid.x + n_listed_blocks, zgrid.y);
@@ -1472,15 +1450,11 @@ int remd_pme_forces(remd_ctx* h, bool with_energy, hipStream_t st, int part)
             if (s->xy_pow2 == 64) { if (with_energy) LAUNCH_XY_P2(64, 8, 512, true); else LAUNCH_XY_P2(64, 8, 512, false); }
             else { if (with_energy) LAUNCH_XY_P2(128, 16, 1024, true); else LAUNCH_XY_P2(128, 16, 1024, false); }
 #undef LAUNCH_XY_P2
-            if (h->pair_after_xy && h->ev_xy) { hipEventRecord(h->ev_xy, st); h->xy_recorded = true; }
         } else if (s->xy_fused) {
             remd_prof_scope pxy(h, "pme_xy", st);
             hipLaunchKernelGGL(pme_xy_fused_kernel, dim3(s->nzc, s->R), dim3(s->xy_threads), s->xy_lds, st, make_plan(s, 0), make_plan(s, 1),
                                s->sch_x, s->sch_y, nz, s->d_grid, s->d_tw[0], s->d_tw[1], s->d_bmod[0], s->d_bmod[1], s->d_bmod[2], h->d_box,
                                (float)h->ewald_alpha, with_energy ? 1 : 0, s->d_energy, s->n_eblk, s->d_infl, s->infl_rep);
-            // the pair kernel of this evaluation is held back until the plane pass has ENDED (remd_compute_forces waits for this event on
-            // the direct-space stream): planes that take a CU's whole LDS cannot be placed beside resident pair workgroups
-            if (h->pair_after_xy && h->ev_xy) { hipEventRecord(h->ev_xy, st); h->xy_recorded = true; }
         } else if (s->xs_sw > 0) {
             // spec layout [kz][x][y]: y passes on contiguous lines, then the fused x pass on LDS-resident y slabs
             const size_t ylds = sizeof(float2) * ((size_t)s->ys_sh * (ny | 1) + ny + 2);
@@ -1508,13 +1482,12 @@ int remd_pme_forces(remd_ctx* h, bool with_energy, hipStream_t st, int part)
             launch_pass<+1>(h, s, s->d_grid, s->nspec, 1, 1, s->nzc * nx, s->nzc * nx, 0, 1);
         }
         // mesh forces by bin position + one hand-over to the atoms (REMD_PME_FBIN=0: five scattered atomic triples per atom)
-        const bool fbin_env = !(getenv("REMD_PME_FBIN") && atoi(getenv("REMD_PME_FBIN")) == 0);
-        if (fbin_env && !s->d_fbin) {
+        if (h->sw.pme_fbin && !s->d_fbin) {
             s->fbin_P = std::max((size_t)nx * (size_t)std::max(s->cbin_cap, 0), (size_t)h->Npad);
             REMD_CHECK(h, hipMalloc(&s->d_fbin, sizeof(unsigned long long) * 3 * s->fbin_P * s->R));
             REMD_CHECK(h, hipMemsetAsync(s->d_fbin, 0, sizeof(unsigned long long) * 3 * s->fbin_P * s->R, st));
         }
-        unsigned long long* fbin = fbin_env ? s->d_fbin : (unsigned long long*)nullptr;
+        unsigned long long* fbin = h->sw.pme_fbin ? s->d_fbin : (unsigned long long*)nullptr;
         {
         remd_prof_scope pzg(h, "pme_zinv_gather", st);
         if (zp2) {

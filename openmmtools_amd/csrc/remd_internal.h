@@ -99,8 +99,40 @@ struct remd_desc_store {
     }
 };
 
+// The environment switches the engine honours, read once per handle by remd_create (api.hip: read_switches) and copied
+// to the blocks of a phased handle.  Test hooks that pin one of two bit-identical (or tolerance-equal) paths, the profiling tools'
+// settings and diagnostic printers; nothing else under csrc/ reads the environment.  "Pinned" switches: n >= 0 pins the path
+// (0 off, anything else on), unset or negative leaves the choice to the engine's rule.
+struct remd_switches {
+    bool overlap = true;          // REMD_OVERLAP=0: one stream, no fork of a PME force evaluation into a mesh and a direct-space stream
+    int phases = -1;              // REMD_PHASES=n: overrides remd_set_phases (1 one block, 2 two, 0 by rule); unset: what remd_set_phases asked
+    bool resident = true;         // REMD_RESIDENT=0: neither resident kernel (small systems, small molecules); the regular launches
+    int resident_cap = 0;         // REMD_RESIDENT_CAP=n: the resident kernel's neighbour list holds at most n pairs (provokes its overflow path)
+    bool chain_merge = true;      // REMD_CHAIN_MERGE=0: the centre-of-mass sum as two chain launches instead of a barrier inside one
+    bool nb_tiles = false;        // REMD_NB_TILES set: the 64-atom tile pair kernel (a cluster-list overflow's fall-back) from the start
+    int nb_persist_grid = -1;     // REMD_NB_PERSIST_GRID=n >= 0: the pair kernel's grid fixed (0: a workgroup per work item, else n resident
+                                  //   workgroups pulling items) and the timing tuner off; unset: chosen by timing
+    int nb_prio = -1;             // REMD_NB_PRIO, pinned: the pair kernel (1) or the mesh kernels (0) at raised wave priority; by default chosen by timing
+    bool nb_fold = true;          // REMD_NB_FOLD=0: the integrator chain waits for a signal launch instead of polling the scatter's done counter
+    bool listed_atoms = true;     // REMD_LISTED_ATOMS=0: listed terms one term per thread instead of (term, slot) entries in atom order
+    bool listed_main = true;      // REMD_LISTED_MAIN=0: listed terms of a forked evaluation behind the pair kernel, not on the main stream
+    bool listed_ride = true;      // REMD_LISTED_RIDE=0: listed terms as a launch of their own, not as workgroups of the spreading launch
+    int pme_chainbin = -1;        // REMD_PME_CHAINBIN, pinned: mesh-column bins from the integrator chain's epilogue (0: the binning launch)
+    int pme_cbin_cap = 0;         // REMD_PME_CBIN_CAP=n: at most n atoms per chain-binned mesh column (provokes the overflow path)
+    int pme_pow2 = 3;             // REMD_PME_POW2 bits: 1 the register-resident plane pass, 2 the register-resident z passes of 64 / 128 meshes
+    bool pme_fbin = true;         // REMD_PME_FBIN=0: mesh forces as scattered atomics per atom instead of by bin position
+    bool gb_small = true;         // REMD_GB_SMALL=0: GBSA systems of up to 64 atoms take the three launches instead of one
+    int mix_flow = -1;            // REMD_MIX_FLOW, pinned: the swap-all dataflow kernel (1) or the speculative windows (0); by default by acceptance
+    bool mix_pre = true;          // REMD_MIX_PRE=0: speculative swap-all windows entirely in the serial workgroup (no hoisted mix_prep_kernel)
+    bool debug = false;           // REMD_DEBUG set: print the cluster-pair list statistics after every re-sort
+    bool nb_tune_verbose = false; // REMD_NB_TUNE_VERBOSE set: print the pair-kernel residency tuner's timings
+    bool many_verbose = false;    // REMD_MANY_VERBOSE set: print host enqueue times of remd_propagate_many and the phases' stream set-up
+    int prof_every = 16;          // REMD_PROF_EVERY=n: profiling level 1 samples every n-th launch of a class
+};
+
 struct remd_ctx {
     int device = 0;
+    remd_switches sw;
     hipStream_t stream = nullptr; bool owns_stream = false;
     std::string err;
     uint64_t seed = 0;
@@ -229,7 +261,7 @@ struct remd_ctx {
     // fork / join of the two streams by flags in device memory ([0] fork, [1] join, [2] a spin ran out): the first mesh kernel
     // publishes the fork, a one-wavefront kernel at the head of the second stream waits for it, and the mirror image at the
     // join -- an event record / wait costs ~6 us of command-processor latency on the critical path, twice per step.
-    // REMD_SYNC_EVENTS=1 keeps the events (also the fall-back of a handle whose polled wait ran out, api.hip).
+    // sync_events: the events instead, the fall-back of a handle whose polled wait ran out (api.hip: remd_recover_device_flag).
     unsigned int* d_sync = nullptr; unsigned int sync_seq = 0; unsigned int fork_seq_pending = 0; bool sync_events = false;
     // remd_run_steps: the launch that follows a force evaluation on the main stream is always an integrator chain, so the
     // join is polled in that kernel's prologue (join_deferred = sequence number to wait for) instead of a kernel of its own
@@ -245,8 +277,6 @@ struct remd_ctx {
     // in front of the chain instead of a poll in the chain's prologue (320 registers per lane on every CU it occupies), the momentum
     // sum two launches instead of a barrier over resident workgroups
     bool lean_waits = false, no_chain_barrier = false;
-    // round 6 (DHFR-size meshes): hold the pair kernel of a forked evaluation until the LDS-resident plane pass has ended
-    bool pair_after_xy = false, xy_recorded = false; hipEvent_t ev_xy = nullptr; size_t xy_lds_bytes = 0;
     // ---- phases (round 6): remd_propagate of ONE handle as two groups of replicas whose MD steps take turns ------------------------
     // The local replicas are split into contiguous blocks, each block propagated by a child context of its own (full tables for its
     // share of the replicas; block 0 launches on THIS handle's two streams, block 1 on one more pair), the blocks' steps enqueued in
@@ -262,7 +292,7 @@ struct remd_ctx {
     unsigned long long* d_chain_own = nullptr;   // [2] profiling: sum of (end - flag seen) wall-clock ticks of workgroup (0, 0), launches
     unsigned long long* d_chain_sync = nullptr; unsigned int chain_sync_epoch = 0; long long chain_sync_key = -1;    // [2][R][workgroups][3] epoch-tagged partial momentum sums of the 'M' token (integrate.hip)
     bool cbins_ready = false;          // the chain launched last binned the atoms for the PME pass of the evaluation that follows
-    hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; bool overlap = true; bool pme_concurrent = false;
+    hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; bool pme_concurrent = false;
     // sharding without a Python host (comm.hip): an RCCL communicator over the ranks of one replica-exchange run
     void* comm = nullptr; int comm_rank = 0, comm_world = 1;
     std::vector<long long> comm_begin, comm_count;   // every rank's block of replicas, exchanged when the local block changes
@@ -270,7 +300,6 @@ struct remd_ctx {
     double t_prop = 0, t_energy = 0, t_mix = 0;
     int profiling = 0;                 // 0 off, 1 filtered class only, 2 all classes
     std::string prof_filter = "nonbonded";
-    int prof_every = getenv("REMD_PROF_EVERY") ? std::max(1, atoi(getenv("REMD_PROF_EVERY"))) : 16;   // level 1: sample every n-th launch of a class
     std::map<const char*, long> prof_seen;
     struct pending_t { std::string name; hipEvent_t a, b; };
     std::vector<pending_t> prof_pending;
@@ -311,9 +340,9 @@ struct remd_prof_scope {
                 on = e > b && nm.compare(0, e - b, f, b, e - b) == 0;
                 b = e + 1;
             }
-            // sampled: every prof_every-th launch of a class (an event pair costs host time and, on the main stream, ~12 us of
+            // sampled: every sw.prof_every-th launch of a class (an event pair costs host time and, on the main stream, ~12 us of
             // command-processor latency on the critical path of a step: timing every launch slows what it measures)
-            if (on) on = (h->prof_seen[n]++ % h->prof_every) == 0;
+            if (on) on = (h->prof_seen[n]++ % h->sw.prof_every) == 0;
         }
         if (on) { hipEventCreate(&a); hipEventRecord(a, st); }
     }

@@ -10,7 +10,7 @@ dbs=""
 i=0
 for set in "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_IFETCH SQ_WAIT_INST_ANY" "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAIT_ANY" "SQ_IFETCH_LEVEL SQ_ACTIVE_INST_ANY"; do
   i=$((i+1))
-  (cd /tmp && rm -rf /tmp/pic_$i && env REMD_TOOLS_EWALD_SPLIT=auto rocprofv3 --pmc $set -d /tmp/pic_$i -o p -- python $ROOT/tools/small_r_profile.py 24 > /tmp/pic_$i.log 2>&1)
+  (cd /tmp && rm -rf /tmp/pic_$i && rocprofv3 --pmc $set -d /tmp/pic_$i -o p -- python $ROOT/tools/small_r_profile.py 24 auto > /tmp/pic_$i.log 2>&1)
   db=$(find /tmp/pic_$i -name '*.db' 2>/dev/null | head -1)
   if [ -n "$db" ]; then dbs="$dbs $db"; else echo "(counter group skipped: $set)"; tail -3 /tmp/pic_$i.log; fi
 done

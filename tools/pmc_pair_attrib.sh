@@ -13,7 +13,7 @@ for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY" "SQ_ACTI
            "SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_MISC" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_IFETCH" \
            "SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_ADD_F32" "SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_CVT SQ_INST_LEVEL_LDS SQ_INST_LEVEL_VMEM"; do
   i=$((i+1))
-  (cd /tmp && rm -rf /tmp/ppa_$i && env REMD_OVERLAP=0 REMD_TOOLS_EWALD_SPLIT=auto rocprofv3 --pmc $set -d /tmp/ppa_$i -o p -- python $ROOT/tools/small_r_profile.py 24 > /tmp/ppa_$i.log 2>&1)
+  (cd /tmp && rm -rf /tmp/ppa_$i && env REMD_OVERLAP=0 rocprofv3 --pmc $set -d /tmp/ppa_$i -o p -- python $ROOT/tools/small_r_profile.py 24 auto > /tmp/ppa_$i.log 2>&1)
   db=$(find /tmp/ppa_$i -name '*.db' 2>/dev/null | head -1)
   if [ -n "$db" ]; then dbs="$dbs $db"; else echo "(counter group skipped: $set)"; fi
 done

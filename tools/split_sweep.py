@@ -1,5 +1,5 @@
-"""ms per 500 MD steps of R alanine-dipeptide replicas for one Ewald split; environment variants
-(REMD_NB_TABLE, REMD_CU_PAIR / REMD_CU_MESH / REMD_CU_LAYOUT, REMD_NB_PERSIST_GRID) are per process.
+"""ms per 500 MD steps of R alanine-dipeptide replicas for one Ewald split; environment switches
+(REMD_NB_PERSIST_GRID, ...: DESIGN.md 7b) are set for the process and read when the engine is created.
 usage: python tools/split_sweep.py <reference|auto|r_coul_nm> [R] [system: alanine|hostguest|dhfr] [standalone]"""
 import os, sys, time
 if len(sys.argv) > 4 and sys.argv[4] == 'standalone':
