@@ -426,6 +426,10 @@ int  remd_mix_host(remd_handle h, int scheme, int64_t iteration, int R, int K,
 int  remd_get_replicas(remd_handle h, double* x, double* v, double* potential, double* kinetic);
 /* forces in kJ/mol/nm, [R_local][N][3] (evaluates them first)                           */
 int  remd_get_forces(remd_handle h, double* f);
+/* forces of the selected force groups only, as OpenMM's getState(getForces=True, groups=mask): force class c
+   (remd_set_force_groups) acts when bit fgroup[c] of groups is set, the restraints when bit rst_group is set.
+   Any of the groups 0 ... 31; a mask that selects nothing gives zeros.  f: [R_local][N][3] */
+int  remd_get_group_forces(remd_handle h, uint32_t groups, double* f);
 /* run a splitting string once per call on all local replicas with explicit step counter
    (test hook: single V / R / O substeps).                                               */
 int  remd_step(remd_handle h, const char* splitting, int64_t iteration, int64_t first_step, int n_steps);

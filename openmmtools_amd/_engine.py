@@ -83,7 +83,7 @@ EXPORTS = [
     'remd_set_region_lambdas', 'remd_set_region_bonded_lambdas', 'remd_set_gbsa', 'remd_set_states',
     'remd_set_integrator', 'remd_set_replicas', 'remd_set_replica_ids', 'remd_copy_replicas', 'remd_set_labels', 'remd_seed', 'remd_propagate',
     'remd_compute_energies', 'remd_ukl_device_ptr', 'remd_mix', 'remd_mix_host', 'remd_get_replicas',
-    'remd_get_forces', 'remd_propagate_many', 'remd_set_phases', 'remd_get_phases', 'remd_get_constraint_stats', 'remd_step', 'remd_sync', 'remd_last_timing', 'remd_profile_enable',
+    'remd_get_forces', 'remd_get_group_forces', 'remd_propagate_many', 'remd_set_phases', 'remd_get_phases', 'remd_get_constraint_stats', 'remd_step', 'remd_sync', 'remd_last_timing', 'remd_profile_enable',
     'remd_profile_get', 'remd_profile_reset', 'remd_test_fft3d', 'remd_get_energy_components', 'remd_profile_filter',
     'remd_set_restart_attempts', 'remd_set_force_groups', 'remd_set_work_measurement', 'remd_get_work', 'remd_reset_work', 'remd_minimize', 'remd_set_barostat', 'remd_get_boxes', 'remd_get_barostat_stats',
     'remd_barostat_attempts',
@@ -157,6 +157,7 @@ def load_library(path=None):
                                   c_int64_p, c_double_p, c_double_p, C.c_int64]
     lib.remd_get_replicas.argtypes = [vp, c_double_p, c_double_p, c_double_p, c_double_p]
     lib.remd_get_forces.argtypes = [vp, c_double_p]
+    lib.remd_get_group_forces.argtypes = [vp, C.c_uint32, c_double_p]
     lib.remd_propagate_many.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.POINTER(C.c_int32)]
     lib.remd_get_constraint_stats.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.remd_set_phases.argtypes = [vp, C.c_int32]
@@ -607,9 +608,14 @@ class HipEngine:
         self._check(self.lib.remd_get_replicas(self.h, _dp(x), _dp(v), _dp(u), _dp(k)), 'remd_get_replicas')
         return x, v, u, k
 
-    def get_forces(self):
+    def get_forces(self, groups=None):
+        """Forces [R, N, 3] in kJ/mol/nm.  groups: None (every force) or a bit mask of force groups 0 ... 31, as OpenMM's
+        getState(getForces=True, groups=mask)."""
         f = np.empty((self.R, self.N, 3))
-        self._check(self.lib.remd_get_forces(self.h, _dp(f)), 'remd_get_forces')
+        if groups is None:
+            self._check(self.lib.remd_get_forces(self.h, _dp(f)), 'remd_get_forces')
+        else:
+            self._check(self.lib.remd_get_group_forces(self.h, int(groups) & 0xffffffff, _dp(f)), 'remd_get_group_forces')
         return f
 
     def step(self, splitting, iteration=0, first_step=0, n_steps=1):

@@ -1231,22 +1231,41 @@ int remd_get_replicas(remd_handle h, double* x, double* v, double* potential, do
     return 0;
 }
 
-int remd_get_forces(remd_handle h, double* f)
+// forces of the classes in class_mask (REMD_FG_* bits) into f
+static int remd_read_forces(remd_ctx* h, unsigned class_mask, const char* where, double* f)
 {
-    if (!h || h->R <= 0 || !f) return remd_fail(h, -1, "remd_get_forces: bad arguments");
-    hipSetDevice(h->device);
     for (int attempt = 0;; ++attempt) {
         h->forces_valid = false;
-        int rc = remd_compute_forces(h, false); if (rc) return rc;
+        int rc = remd_compute_forces(h, false, class_mask); if (rc) return rc;
+        // (a subset of the classes is not the force the integrator kicks with: the next step evaluates them all again)
+        if (class_mask != ~0u) { h->forces_valid = false; h->force_zeroed = false; }
         const size_t n = (size_t)h->R * 3 * h->Npad;
         std::vector<long long> buf(n);
         REMD_CHECK(h, hipMemcpyAsync(buf.data(), h->d_force, sizeof(long long) * n, hipMemcpyDeviceToHost, h->stream));
         REMD_CHECK(h, hipStreamSynchronize(h->stream));
         for (int r = 0; r < h->R; ++r) for (int i = 0; i < h->N; ++i) for (int k = 0; k < 3; ++k)
             f[((size_t)r * h->N + i) * 3 + k] = (double)buf[((size_t)r * 3 + k) * h->Npad + i] / REMD_FORCE_SCALE;
-        rc = remd_check_device_flags(h, "remd_get_forces", attempt == 0);
+        rc = remd_check_device_flags(h, where, attempt == 0);
         if (rc != 1) return rc;
     }
+}
+
+int remd_get_forces(remd_handle h, double* f)
+{
+    if (!h || h->R <= 0 || !f) return remd_fail(h, -1, "remd_get_forces: bad arguments");
+    hipSetDevice(h->device);
+    return remd_read_forces(h, ~0u, "remd_get_forces", f);
+}
+
+int remd_get_group_forces(remd_handle h, uint32_t groups, double* f)
+{
+    if (!h || h->R <= 0 || !f) return remd_fail(h, -1, "remd_get_group_forces: bad arguments");
+    hipSetDevice(h->device);
+    // force class c acts when its group's bit is set (OpenMM getState(groups=...)); the restraints by their own group
+    unsigned class_mask = 0u;
+    for (int c = 0; c < 6; ++c) if ((groups >> h->fgroup[c]) & 1u) class_mask |= 1u << c;
+    if (h->n_restraints > 0 && ((groups >> h->rst_group) & 1u)) class_mask |= 1u << REMD_FG_RESTRAINT;
+    return remd_read_forces(h, class_mask, "remd_get_group_forces", f);
 }
 
 // the device reports what it cannot raise: a cross-stream poll or the chain's barrier that ran out, an overfull PME bin

@@ -200,15 +200,21 @@ void listed_forces_body(const listed_tables& T, int Npad, const float4* __restri
         // run (a segmented scan over the wavefront) and the run's last lane issues the atom's one atomic triple.  Atomics of
         // several lanes on ONE address are serialised at the L2 (measured: the entries with an atomic each are slower than the
         // term-per-thread launch), while the runs' last lanes hit distinct, neighbouring atoms.
+        // A segment is a run of NEIGHBOURING lanes with one atom, bounded by head flags -- not "the lane d back has my atom".
+        // Idle lanes sit inside an atom's run wherever a force-group evaluation switches a class off (an atom's entries are
+        // bond, angle, torsion, exception, exclusion: bonds + torsions leave the angle lanes idle between them).  Such a lane
+        // splits the run into two segments, each with its own atomic; a scan that compared atoms across the gap would add the
+        // first segment's partial sum into the second as well, after the first had already sent it: that atom's force twice.
+        const int ap = __shfl_up(a, 1);
+        const unsigned long long heads = __ballot(lane == 0 || ap != a);
+        const int s0 = 63 - __clzll(heads & (~0ull >> (63 - lane)));      // first lane of this lane's segment
         unsigned long long vx = cls < 0 ? 0ull : remd_f2fix(fx), vy = cls < 0 ? 0ull : remd_f2fix(fy), vz = cls < 0 ? 0ull : remd_f2fix(fz);
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
-            const int au = __shfl_up(a, d);
             const unsigned long long ux = __shfl_up(vx, d), uy = __shfl_up(vy, d), uz = __shfl_up(vz, d);
-            if (lane >= d && au == a) { vx += ux; vy += uy; vz += uz; }
+            if (lane - d >= s0) { vx += ux; vy += uy; vz += uz; }
         }
-        const int an = __shfl_down(a, 1);
-        if (cls >= 0 && (lane == 63 || an != a)) {
+        if (cls >= 0 && (lane == 63 || ((heads >> (lane + 1)) & 1ull))) {
             unsigned long long* U = reinterpret_cast<unsigned long long*>(F);
             atomicAdd(&U[a], vx); atomicAdd(&U[Npad + a], vy); atomicAdd(&U[2 * Npad + a], vz);
         }

@@ -2179,6 +2179,20 @@ int remd_get_forces(remd_handle h, double* f)
     return 0;
 }
 
+int remd_get_group_forces(remd_handle h, uint32_t groups, double* f)
+{
+    if (!h || h->R <= 0 || !f || h->K <= 0) return fail(h, -1, "remd_get_group_forces: bad arguments");
+    const int N = h->sys.N;
+    int classes = 0;                                      // force class c acts when its group's bit is set (OpenMM getState(groups=...))
+    for (int c = 0; c < 6; ++c) if ((groups >> h->force_groups[c]) & 1u) classes |= 1 << c;
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int r = 0; r < h->R; ++r) {
+        const int64_t k = h->labels[h->r_begin + r];
+        evaluate(h->sys, h->reps[r], h->lam_s[k], h->lam_e[k], f + (size_t)r * 3 * N, thread_fft(h), PART_ALL, classes, (int)k);
+    }
+    return 0;
+}
+
 int remd_get_energy_components(remd_handle h, double* out)
 {
     if (!h || !out || h->R <= 0 || h->K <= 0) return fail(h, -1, "remd_get_energy_components: bad arguments");

@@ -230,8 +230,14 @@ class OracleEngine:
         k = np.array([mo.kinetic_energy(self.sys.mass, self.v[r]) for r in range(self.R)]) if kinetic else None
         return self.x.copy(), self.v.copy(), u, k
 
-    def get_forces(self):
-        return np.stack([self.sys.energy_forces(self.x[r], self._box(r))[1] for r in range(self.R)])
+    def get_forces(self, groups=None):
+        """groups: None (every force) or a bit mask of force groups: force class c acts when bit desc['force_groups'][c] is set
+        (remd_get_group_forces)"""
+        if groups is None:
+            return np.stack([self.sys.energy_forces(self.x[r], self._box(r))[1] for r in range(self.R)])
+        fg = self.desc.get('force_groups', [0] * 6)
+        classes = {c for c in range(6) if (int(groups) >> int(fg[c])) & 1}
+        return np.stack([self.sys.energy_forces(self.x[r], self._box(r), classes=classes)[1] for r in range(self.R)])
 
     def sync(self):
         pass

@@ -16,11 +16,13 @@ SEED = 0xC0FFEE
 SOLVENT_SOLUTE = 'V0 V1 R R O R R V1 R R O R R V1 V0'           # integrators.py:1053
 
 
-def _grouped(testsystem, bonded=1, nonbonded=0, reciprocal=None):
+def _grouped(testsystem, bonded=1, nonbonded=0, reciprocal=None, bonds=None, angles=None, torsions=None):
+    """bonds / angles / torsions: the group of that force alone (default: bonded)"""
     system = copy.deepcopy(testsystem.system)
     for f in system.getForces():
         if isinstance(f, (HarmonicBondForce, HarmonicAngleForce, PeriodicTorsionForce)):
-            f.setForceGroup(bonded)
+            own = bonds if isinstance(f, HarmonicBondForce) else angles if isinstance(f, HarmonicAngleForce) else torsions
+            f.setForceGroup(bonded if own is None else own)
         elif isinstance(f, NonbondedForce):
             f.setForceGroup(nonbonded)
             if reciprocal is not None:
@@ -85,6 +87,12 @@ def test_equal_group_counts_reduce_to_the_single_time_step_scheme_on_the_device(
 @pytest.mark.parametrize('groups,splitting', [
     (dict(bonded=1, nonbonded=0), SOLVENT_SOLUTE),                                     # the reference's docstring example
     (dict(bonded=0, nonbonded=1, reciprocal=2), 'V2 V1 V0 R V0 R O R V0 R V0 V1 V2'),   # mesh slowest, bonded fastest
+    # groupings whose classes are not a contiguous range of bonds < angles < torsions < nonbonded (idle lanes inside an atom's
+    # run of listed-term entries, csrc/listed_terms.h)
+    (dict(bonds=1, torsions=1, angles=0, nonbonded=0), SOLVENT_SOLUTE),
+    (dict(bonds=1, torsions=1, angles=0, nonbonded=0, reciprocal=2), 'V2 V0 V1 R V1 R O R V1 R V1 V0 V2'),
+    (dict(bonds=1, nonbonded=1, angles=0, torsions=0), SOLVENT_SOLUTE),
+    (dict(angles=1, bonded=0, nonbonded=0), SOLVENT_SOLUTE),
 ])
 def test_device_follows_the_oracle(hip_engine_factory, groups, splitting):
     """Alanine dipeptide in water, 6 steps at 2 fs: device fp32 vs oracle f64 on the same Philox stream, forces per group from
@@ -116,6 +124,12 @@ def test_a_force_class_in_an_unnamed_group_is_refused(hip_engine_factory):
 @pytest.mark.parametrize('groups,splitting', [
     (dict(bonded=1, nonbonded=0), SOLVENT_SOLUTE),                                     # the reference's docstring example
     (dict(bonded=0, nonbonded=1, reciprocal=2), 'V2 V1 V0 R V0 R O R V0 R V0 V1 V2'),   # mesh slowest, bonded fastest
+    # groupings whose classes are not a contiguous range of bonds < angles < torsions < nonbonded (idle lanes inside an atom's
+    # run of listed-term entries, csrc/listed_terms.h)
+    (dict(bonds=1, torsions=1, angles=0, nonbonded=0), SOLVENT_SOLUTE),
+    (dict(bonds=1, torsions=1, angles=0, nonbonded=0, reciprocal=2), 'V2 V0 V1 R V1 R O R V1 R V1 V0 V2'),
+    (dict(bonds=1, nonbonded=1, angles=0, torsions=0), SOLVENT_SOLUTE),
+    (dict(angles=1, bonded=0, nonbonded=0), SOLVENT_SOLUTE),
 ])
 def test_cpu_library_follows_the_oracle(groups, splitting):
     """The C++ port (libremd_cpu.so through the C ABI) on the same Philox stream as the f64 oracle: alanine dipeptide in water,
