@@ -37,24 +37,24 @@ struct region_tables {
     struct cls { int kind, a, b, P; };     // kind 0: (environment, a); 1: (a, a); 2: (a, b) interacting; P = region whose soft-core constants apply
     std::vector<cls> classes;
     std::vector<double> ls, le;            // [K][n_regions]
-    int* d_alch = nullptr;                 // [n_alch] atom
-    float4* d_atom = nullptr;              // [N] q sqrt(k_e), sigma / 2, 2 sqrt(eps), region (bits)
-    unsigned int* d_skip = nullptr;        // [n_alch][words] candidates that are never evaluated
-    int* d_cls_of = nullptr;               // [(n + 1)^2] class of a pair of regions
-    int* d_exc_atoms = nullptr; float4* d_exc_par = nullptr;      // exceptions: (k_e qq, sigma, 4 eps, class bits)
-    float4* d_state_cls = nullptr;         // [K][n_cls][2]: (l^a, alpha (1 - l)^b, l^d, beta (1 - l)^e), (c, f, 0, 0)
-    int* d_own = nullptr; std::vector<int> own_host;
-    double* d_epart = nullptr; size_t epart_n = 0;          // [R][columns][n_alch] energy partials
+    dev_array<int> d_alch;                 // [n_alch] atom
+    dev_array<float4> d_atom;              // [N] q sqrt(k_e), sigma / 2, 2 sqrt(eps), region (bits)
+    dev_array<unsigned int> d_skip;        // [n_alch][words] candidates that are never evaluated
+    dev_array<int> d_cls_of;               // [(n + 1)^2] class of a pair of regions
+    dev_array<int> d_exc_atoms; dev_array<float4> d_exc_par;      // exceptions: (k_e qq, sigma, 4 eps, class bits)
+    dev_array<float4> d_state_cls;         // [K][n_cls][2]: (l^a, alpha (1 - l)^b, l^d, beta (1 - l)^e), (c, f, 0, 0)
+    dev_array<int> d_own; std::vector<int> own_host;
+    dev_array<double> d_epart;         // [R][columns][n_alch] energy partials (grown on demand)
     // softened bonded terms: atoms, parameters (the last entry of a term = its region as float bits), per state the regions' lambdas
-    int* d_bonded_atoms = nullptr; float* d_bonded_par = nullptr;      // bonds [n][2] + angles [n][3] + torsions [n][4]; [n][3] + [n][3] + [n][4]
-    float* d_state_bl = nullptr;           // [K][3][n_regions]
+    dev_array<int> d_bonded_atoms; dev_array<float> d_bonded_par;      // bonds [n][2] + angles [n][3] + torsions [n][4]; [n][3] + [n][3] + [n][4]
+    dev_array<float> d_state_bl;           // [K][3][n_regions]
     std::vector<double> bl;                // host: [3][K][n_regions]
     // exact PME treatment (<= 4 charged regions: the slots of one float4 per replica, which the mesh kernels index by the atom's code)
-    unsigned int* d_corr = nullptr;        // [n_alch][words] skipped candidates that still get the Ewald correction -qq erf(alpha r) / r
-    float4* d_param_pme = nullptr;         // [Npad] the mesh kernels' charges: reference charges of the alchemical atoms, w = 8 + region slot
-    float* d_rep_le = nullptr;             // [R][4] lambda_electrostatics of the regions at each replica's state (or the probe's)
+    dev_array<unsigned int> d_corr;        // [n_alch][words] skipped candidates that still get the Ewald correction -qq erf(alpha r) / r
+    dev_array<float4> d_param_pme;         // [Npad] the mesh kernels' charges: reference charges of the alchemical atoms, w = 8 + region slot
+    dev_array<float> d_rep_le;             // [R][4] lambda_electrostatics of the regions at each replica's state (or the probe's)
     std::vector<float> rep_le_host;
-    float* d_state_le = nullptr;           // [K][4]
+    dev_array<float> d_state_le;           // [K][4]
     bool have_override = false; float le_override[4] = {1.f, 1.f, 1.f, 1.f};
     // a deep copy of the descriptor of remd_set_alchemical_regions: the blocks of a phased propagation (api.hip) are set up from it
     struct desc_store {
@@ -78,19 +78,9 @@ struct region_tables {
     } store;
     bool have_bonded_lambdas = false;
 };
-static handle_table<region_tables> g_reg;
+void remd_table_deleter::operator()(region_tables* t) const { delete t; }
 
 static inline float host_int_as_float(int v) { float f; memcpy(&f, &v, sizeof f); return f; }
-template <typename T> static void dfree(T*& p) { if (p) { hipFree(p); p = nullptr; } }
-template <typename T>
-static int upload(remd_ctx* h, T*& dptr, const std::vector<T>& host)
-{
-    dfree(dptr);
-    if (host.empty()) return 0;
-    REMD_CHECK(h, hipMalloc(&dptr, sizeof(T) * host.size()));
-    REMD_CHECK(h, hipMemcpy(dptr, host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice));
-    return 0;
-}
 
 __device__ __forceinline__ void region_switch(float rs, float inv_sw, float r, float& U, float& dUdr)
 {
@@ -434,16 +424,10 @@ void region_energy_sum_kernel(region_consts c, int cols, const double* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------
+// no regions (remd_set_system: they belong to the system before)
 void remd_regions_release(remd_ctx* h)
 {
-    region_tables* t = g_reg.find(h);
-    if (t) {
-        dfree(t->d_alch); dfree(t->d_atom); dfree(t->d_skip); dfree(t->d_cls_of); dfree(t->d_exc_atoms); dfree(t->d_exc_par);
-        dfree(t->d_state_cls); dfree(t->d_own); dfree(t->d_epart);
-        dfree(t->d_corr); dfree(t->d_param_pme); dfree(t->d_rep_le); dfree(t->d_state_le);
-        dfree(t->d_bonded_atoms); dfree(t->d_bonded_par); dfree(t->d_state_bl);
-        g_reg.erase(h);
-    }
+    h->reg.reset();
     h->n_regions = 0; h->regions_exact = 0;
 }
 
@@ -457,7 +441,7 @@ int remd_set_alchemical_regions(remd_handle h, const remd_alch_regions_desc* d)
     h->forces_valid = false;
     if (!d || d->n_regions == 0) return 0;
     // (a block of a phased propagation reads the descriptor its parent keeps: api.hip phase_children)
-    const remd_desc_store* store = h->parent ? h->parent->sysdesc : h->sysdesc;
+    const remd_desc_store* store = (h->parent ? h->parent : h)->sysdesc.get();
     if (!h->has_system || !store || !store->valid) return remd_fail(h, -2, "remd_set_alchemical_regions: call remd_set_system first");
     const int N = h->N, n = d->n_regions;
     if (d->n_atoms != N) return remd_fail(h, -1, "remd_set_alchemical_regions: n_atoms differs from the system's");
@@ -466,13 +450,14 @@ int remd_set_alchemical_regions(remd_handle h, const remd_alch_regions_desc* d)
         return remd_fail(h, -1, "remd_set_alchemical_regions: bad arguments");
     if (h->nb_method == REMD_NB_NONE && !h->nocutoff) return remd_fail(h, -3, "alchemical regions need a NonbondedForce");
     if (store->d.n_alch != 0) return remd_fail(h, -3, "alchemical regions: the descriptor of remd_set_system must be the factory's NonbondedForce (n_alch = 0)");
-    region_tables& t = g_reg[h];
+    remd_table<region_tables> tab(new region_tables());
+    region_tables& t = *tab;
     t.n_regions = n;
     t.softcore.assign(d->softcore, d->softcore + 8 * (size_t)n);
     t.annihilate.assign(d->annihilate, d->annihilate + 2 * (size_t)n);
     for (int g = 0; g < n; ++g) {
         const double* s = &t.softcore[8 * (size_t)g];
-        if (!(s[4] > 0) || !(s[7] > 0)) { remd_regions_release(h); return remd_fail(h, -1, "alchemical regions: softcore_c and softcore_f must be positive"); }
+        if (!(s[4] > 0) || !(s[7] > 0)) return remd_fail(h, -1, "alchemical regions: softcore_c and softcore_f must be positive");
     }
     // classes of pairs of regions
     std::vector<int> cls_of((size_t)(n + 1) * (n + 1), -1);
@@ -483,13 +468,12 @@ int remd_set_alchemical_regions(remd_handle h, const remd_alch_regions_desc* d)
     }
     const bool exact = d->exact_pme != 0;
     if (exact && (h->nb_method != REMD_NB_PME || n > 4)) {
-        remd_regions_release(h);
         return remd_fail(h, exact && n > 4 ? -3 : -1, n > 4 ? "alchemical regions: more than four regions under the exact PME treatment are not supported" : "alchemical regions: exact_pme needs a PME system");
     }
     std::vector<char> interacting((size_t)(n + 1) * (n + 1), 0);
     for (int k = 0; k < d->n_interactions; ++k) {
         const int a = d->interactions[2 * k], b = d->interactions[2 * k + 1];
-        if (a < 1 || b < 1 || a > n || b > n || a == b) { remd_regions_release(h); return remd_fail(h, -1, "alchemical regions: bad pair of interacting regions"); }
+        if (a < 1 || b < 1 || a > n || b > n || a == b) return remd_fail(h, -1, "alchemical regions: bad pair of interacting regions");
         interacting[(size_t)a * (n + 1) + b] = interacting[(size_t)b * (n + 1) + a] = 1;
         if (exact) continue;                // exact PME: the pair sees each other's scaled charges; no sterics (tables zeroed, alchemy.py:1886-1911)
         if (cls_of[(size_t)a * (n + 1) + b] >= 0) continue;
@@ -501,12 +485,12 @@ int remd_set_alchemical_regions(remd_handle h, const remd_alch_regions_desc* d)
     const double sqk = sqrt(REMD_ONE_4PI_EPS0);
     for (int i = 0; i < N; ++i) {
         const int g = d->region_of_atom[i];
-        if (g < 0 || g > n) { remd_regions_release(h); return remd_fail(h, -1, "alchemical regions: region index out of range"); }
+        if (g < 0 || g > n) return remd_fail(h, -1, "alchemical regions: region index out of range");
         if (g > 0) alch.push_back(i);
-        if (!(d->sigma[i] > 0) && g > 0) { remd_regions_release(h); return remd_fail(h, -1, "alchemical regions: sigma must be positive (the factory sets 0 to 0.1 nm, alchemy.py:1638-1648)"); }
+        if (!(d->sigma[i] > 0) && g > 0) return remd_fail(h, -1, "alchemical regions: sigma must be positive (the factory sets 0 to 0.1 nm, alchemy.py:1638-1648)");
         atom[i] = make_float4((float)(d->charge[i] * sqk), (float)(0.5 * d->sigma[i]), (float)(2.0 * sqrt(d->epsilon[i])), host_int_as_float(g));
     }
-    if (alch.empty()) { remd_regions_release(h); return remd_fail(h, -1, "alchemical regions: no alchemical atom"); }
+    if (alch.empty()) return remd_fail(h, -1, "alchemical regions: no alchemical atom");
     const int na = (int)alch.size(), words = (N + 31) / 32;
     std::vector<int> ord(N, -1);
     for (int k = 0; k < na; ++k) ord[alch[k]] = k;
@@ -526,7 +510,7 @@ int remd_set_alchemical_regions(remd_handle h, const remd_alch_regions_desc* d)
             }
             // environment atoms without sigma cannot enter the mixing rule: they have neither epsilon nor (in the factory's system) a way to interact
             else if (gj == 0 && !(d->sigma[j] > 0) && (d->epsilon[j] != 0.0 || (d->electrostatics && d->charge[j] != 0.0))) {
-                remd_regions_release(h); return remd_fail(h, -1, "alchemical regions: sigma must be positive (the factory sets 0 to 0.1 nm, alchemy.py:1638-1648)");
+                return remd_fail(h, -1, "alchemical regions: sigma must be positive (the factory sets 0 to 0.1 nm, alchemy.py:1638-1648)");
             }
         }
     }
@@ -541,11 +525,11 @@ int remd_set_alchemical_regions(remd_handle h, const remd_alch_regions_desc* d)
     std::vector<int> ea; std::vector<float4> ep;
     for (int e = 0; e < d->n_exceptions; ++e) {
         const int i = d->exception_atoms[2 * e], j = d->exception_atoms[2 * e + 1];
-        if (i < 0 || j < 0 || i >= N || j >= N || i == j) { remd_regions_release(h); return remd_fail(h, -1, "alchemical regions: bad exception pair"); }
+        if (i < 0 || j < 0 || i >= N || j >= N || i == j) return remd_fail(h, -1, "alchemical regions: bad exception pair");
         const int gi = d->region_of_atom[i], gj = d->region_of_atom[j];
         const double qq = d->exception_params[3 * e], sg = d->exception_params[3 * e + 1], eps = d->exception_params[3 * e + 2];
         if ((gi == 0 && gj == 0) || (eps == 0.0 && (qq == 0.0 || !(d->electrostatics || exact)))) continue;
-        if (!(sg > 0)) { remd_regions_release(h); return remd_fail(h, -1, "alchemical regions: exception sigma must be positive"); }
+        if (!(sg > 0)) return remd_fail(h, -1, "alchemical regions: exception sigma must be positive");
         // an exception between atoms of two regions belongs to the FIRST region's (environment, region) bond force: the factory's loop meets
         // it there as "only one alchemical" and zeroes it before the second region's turn (alchemy.py:1972-1976, 1992-2006)
         const int cl = (gi > 0 && gj > 0 && gi != gj) ? cls_of[std::min(gi, gj)] : cls_of[(size_t)gi * (n + 1) + gj];
@@ -578,11 +562,11 @@ int remd_set_alchemical_regions(remd_handle h, const remd_alch_regions_desc* d)
                 c.q_x[g - 1] += d->charge[i];
                 param_pme[i] = make_float4((float)(d->charge[i] * sqk), 0.f, 0.f, (float)(8 + g - 1));
             } else {
-                if (sd.charge[i] != d->charge[i]) { remd_regions_release(h); return remd_fail(h, -1, "alchemical regions: the charges of the environment differ from the system's"); }
+                if (sd.charge[i] != d->charge[i]) return remd_fail(h, -1, "alchemical regions: the charges of the environment differ from the system's");
                 c.q_env += sd.charge[i];
                 param_pme[i] = make_float4((float)(sd.charge[i] * sqk), 0.f, 0.f, 0.f);
             }
-            if (g > 0 && sd.charge[i] != 0.0) { remd_regions_release(h); return remd_fail(h, -1, "alchemical regions (exact PME): the system's descriptor must carry the alchemical atoms without charge"); }
+            if (g > 0 && sd.charge[i] != 0.0) return remd_fail(h, -1, "alchemical regions (exact PME): the system's descriptor must carry the alchemical atoms without charge");
         }
     }
     c.rs_e = c.elec && d->elec_switch_distance >= 0 && d->elec_switch_distance < rcut ? (float)d->elec_switch_distance : -1.f;
@@ -591,13 +575,13 @@ int remd_set_alchemical_regions(remd_handle h, const remd_alch_regions_desc* d)
     c.krf = (float)d->elec_krf; c.crf = (float)d->elec_crf;
     c.n_cls = (int)t.classes.size(); c.n_reg1 = n + 1; c.words = words; c.N = N; c.Npad = h->Npad; c.n_alch = na; c.n_exc = (int)ea.size() / 2;
     int rc;
-    if ((rc = upload(h, t.d_alch, alch)) || (rc = upload(h, t.d_atom, atom)) || (rc = upload(h, t.d_skip, skip)) || (rc = upload(h, t.d_cls_of, cls_of)) ||
-        (rc = upload(h, t.d_exc_atoms, ea)) || (rc = upload(h, t.d_exc_par, ep)) || (rc = upload(h, t.d_corr, corr)) ||
-        (rc = upload(h, t.d_param_pme, param_pme))) { remd_regions_release(h); return rc; }
+    if ((rc = t.d_alch.upload(h, alch)) || (rc = t.d_atom.upload(h, atom)) || (rc = t.d_skip.upload(h, skip)) || (rc = t.d_cls_of.upload(h, cls_of)) ||
+        (rc = t.d_exc_atoms.upload(h, ea)) || (rc = t.d_exc_par.upload(h, ep)) || (rc = t.d_corr.upload(h, corr)) ||
+        (rc = t.d_param_pme.upload(h, param_pme))) return rc;
     {   // softened bonded terms
         if (d->n_bonds < 0 || d->n_angles < 0 || d->n_torsions < 0 || (d->n_bonds > 0 && (!d->bond_atoms || !d->bond_params || !d->bond_region)) ||
             (d->n_angles > 0 && (!d->angle_atoms || !d->angle_params || !d->angle_region)) || (d->n_torsions > 0 && (!d->torsion_atoms || !d->torsion_params || !d->torsion_region))) {
-            remd_regions_release(h); return remd_fail(h, -1, "alchemical regions: bad softened bonded terms");
+            return remd_fail(h, -1, "alchemical regions: bad softened bonded terms");
         }
         std::vector<int> ba; std::vector<float> bp;
         auto take = [&](int cnt, int width, int npar, const int32_t* atoms, const double* par, const int32_t* reg) -> bool {
@@ -611,20 +595,21 @@ int remd_set_alchemical_regions(remd_handle h, const remd_alch_regions_desc* d)
         };
         if (!take(d->n_bonds, 2, 2, d->bond_atoms, d->bond_params, d->bond_region) || !take(d->n_angles, 3, 2, d->angle_atoms, d->angle_params, d->angle_region) ||
             !take(d->n_torsions, 4, 3, d->torsion_atoms, d->torsion_params, d->torsion_region)) {
-            remd_regions_release(h); return remd_fail(h, -1, "alchemical regions: softened bonded term with a bad atom or region");
+            return remd_fail(h, -1, "alchemical regions: softened bonded term with a bad atom or region");
         }
         c.n_bonds = d->n_bonds; c.n_angles = d->n_angles; c.n_torsions = d->n_torsions;
-        if ((rc = upload(h, t.d_bonded_atoms, ba)) || (rc = upload(h, t.d_bonded_par, bp))) { remd_regions_release(h); return rc; }
+        if ((rc = t.d_bonded_atoms.upload(h, ba)) || (rc = t.d_bonded_par.upload(h, bp))) return rc;
     }
-    h->n_regions = n; h->regions_exact = exact ? 1 : 0;
     if (!h->parent) t.store.assign(d);
+    h->reg = std::move(tab);
+    h->n_regions = n; h->regions_exact = exact ? 1 : 0;
     return 0;
 }
 
 int remd_set_region_lambdas(remd_handle h, int K, int n_regions, const double* ls, const double* le)
 {
     if (!h) return remd_fail(h, -1, "remd_set_region_lambdas: NULL handle");
-    region_tables* tp = g_reg.find(h);
+    region_tables* tp = h->reg.get();
     if (!tp || h->n_regions == 0) return remd_fail(h, -2, "remd_set_region_lambdas: no alchemical regions on this handle");
     region_tables& t = *tp;
     if (K != h->K || n_regions != t.n_regions || !ls || !le) return remd_fail(h, -1, "remd_set_region_lambdas: K / n_regions differ from remd_set_states / remd_set_alchemical_regions");
@@ -649,16 +634,16 @@ int remd_set_region_lambdas(remd_handle h, int K, int n_regions, const double* l
                                                        (float)pow(l_e, s[5]), (float)(s[1] * pow(1.0 - l_e, s[6])));
             tab[((size_t)k * C + q) * 2 + 1] = make_float4((float)s[4], (float)s[7], 0.f, 0.f);
         }
-    int rc = upload(h, t.d_state_cls, tab);
+    int rc = t.d_state_cls.upload(h, tab);
     if (rc) return rc;
     std::vector<float> sle((size_t)K * 4, 1.f);
     for (int k = 0; k < K; ++k) for (int g = 0; g < n && g < 4; ++g) sle[4 * (size_t)k + g] = (float)le[(size_t)k * n + g];
-    if ((rc = upload(h, t.d_state_le, sle))) return rc;
+    if ((rc = t.d_state_le.upload(h, sle))) return rc;
     t.rep_le_host.clear();
     t.bl.assign(3 * (size_t)K * n, 1.0);                      // until remd_set_region_bonded_lambdas says otherwise
     {
         std::vector<float> one(3 * (size_t)K * n, 1.f);
-        if ((rc = upload(h, t.d_state_bl, one))) return rc;
+        if ((rc = t.d_state_bl.upload(h, one))) return rc;
     }
     h->config_version++;
     h->forces_valid = false;
@@ -668,7 +653,7 @@ int remd_set_region_lambdas(remd_handle h, int K, int n_regions, const double* l
 int remd_set_region_bonded_lambdas(remd_handle h, int K, int n_regions, const double* lb, const double* la, const double* lt)
 {
     if (!h) return remd_fail(h, -1, "remd_set_region_bonded_lambdas: NULL handle");
-    region_tables* tp = g_reg.find(h);
+    region_tables* tp = h->reg.get();
     if (!tp || h->n_regions == 0) return remd_fail(h, -2, "remd_set_region_bonded_lambdas: no alchemical regions on this handle");
     region_tables& t = *tp;
     if (K != h->K || K != t.K || n_regions != t.n_regions) return remd_fail(h, -1, "remd_set_region_bonded_lambdas: call remd_set_region_lambdas first (same K, n_regions)");
@@ -682,7 +667,7 @@ int remd_set_region_bonded_lambdas(remd_handle h, int K, int n_regions, const do
         if (!(v >= 0.0 && v <= 1.0)) return remd_fail(h, -1, "remd_set_region_bonded_lambdas: lambdas must be in [0, 1]");
         tab[((size_t)k * 3 + q) * n + g] = (float)v;
     }
-    int rc = upload(h, t.d_state_bl, tab);
+    int rc = t.d_state_bl.upload(h, tab);
     if (rc) return rc;
     for (int q = 0; q < 3; ++q) for (int k = 0; k < K; ++k) for (int g = 0; g < n; ++g) t.bl[((size_t)q * K + k) * n + g] = (double)tab[((size_t)k * 3 + q) * n + g];
     t.have_bonded_lambdas = true;
@@ -694,7 +679,7 @@ int remd_set_region_bonded_lambdas(remd_handle h, int K, int n_regions, const do
 // the regions of `parent` on one of its blocks (api.hip phase_children): descriptor, the states' lambdas, the bonded lambdas
 int remd_regions_clone(remd_ctx* parent, remd_ctx* child)
 {
-    region_tables* tp = g_reg.find(parent);
+    region_tables* tp = parent->reg.get();
     if (!tp || parent->n_regions == 0) return 0;
     region_tables& t = *tp;
     if (t.store.d.n_regions != t.n_regions || t.K != parent->K || t.ls.size() != (size_t)t.K * t.n_regions)
@@ -720,14 +705,14 @@ static int region_own_states(remd_ctx* h, region_tables& t)
         for (int r = 0; r < h->R; ++r) for (int g = 0; g < t.n_regions; ++g)
             rl[4 * (size_t)r + g] = t.have_override ? t.le_override[g] : (float)t.le[(size_t)own[r] * t.n_regions + g];
         if (rl != t.rep_le_host || !t.d_rep_le) {
-            if (t.rep_le_host.size() != rl.size() || !t.d_rep_le) { dfree(t.d_rep_le); REMD_CHECK(h, hipMalloc(&t.d_rep_le, sizeof(float) * rl.size())); }
+            if (t.d_rep_le.size() != rl.size()) REMD_TRY(t.d_rep_le.alloc(h, rl.size()));
             REMD_CHECK(h, hipMemcpyAsync(t.d_rep_le, rl.data(), sizeof(float) * rl.size(), hipMemcpyHostToDevice, h->stream));
             REMD_CHECK(h, hipStreamSynchronize(h->stream));
             t.rep_le_host = rl;
         }
     }
     if (own == t.own_host && t.d_own) return 0;          // uploaded only when the labels changed
-    if (t.own_host.size() != own.size()) { dfree(t.d_own); REMD_CHECK(h, hipMalloc(&t.d_own, sizeof(int) * own.size())); }
+    if (t.d_own.size() != own.size()) REMD_TRY(t.d_own.alloc(h, own.size()));
     REMD_CHECK(h, hipMemcpyAsync(t.d_own, own.data(), sizeof(int) * own.size(), hipMemcpyHostToDevice, h->stream));
     REMD_CHECK(h, hipStreamSynchronize(h->stream));
     t.own_host = own;
@@ -737,7 +722,7 @@ static int region_own_states(remd_ctx* h, region_tables& t)
 static int region_energy_launch(remd_ctx* h, region_tables& t, int cols, const int* d_own, const float* d_rep_le, double* d_out, int out_stride, int out_offset)
 {
     const size_t need = (size_t)h->R * cols * t.c.n_alch;
-    if (need > t.epart_n) { dfree(t.d_epart); REMD_CHECK(h, hipMalloc(&t.d_epart, sizeof(double) * need)); t.epart_n = need; }
+    REMD_TRY(t.d_epart.grow(h, need));
     const region_bonded rb{t.d_bonded_atoms, t.d_bonded_par, t.d_state_bl, t.n_regions};
     hipLaunchKernelGGL(region_energy_kernel, dim3(t.c.n_alch, cols, h->R), dim3(256), 0, h->stream, t.c, t.d_alch, t.d_atom, t.d_skip, t.d_cls_of,
                        t.d_state_cls, d_own, t.d_exc_atoms, t.d_exc_par, h->d_pos, h->d_box, t.d_epart, t.d_corr, d_rep_le, rb);
@@ -748,7 +733,7 @@ static int region_energy_launch(remd_ctx* h, region_tables& t, int cols, const i
 // at the head of a force evaluation, on the stream everything else of the evaluation is ordered behind
 int remd_regions_forces(remd_ctx* h, bool with_energy, int ep_slot)
 {
-    region_tables* tp = g_reg.find(h);
+    region_tables* tp = h->reg.get();
     if (!tp) return 0;
     region_tables& t = *tp;
     if (!t.d_state_cls || t.K != h->K) return remd_fail(h, -2, "alchemical regions: remd_set_region_lambdas has not been called for these states");
@@ -768,7 +753,7 @@ int remd_regions_forces(remd_ctx* h, bool with_energy, int ep_slot)
 // the region terms at every state's lambdas: out[r][k]; *d_own = the replicas' own states on the device
 int remd_regions_ukl(remd_ctx* h, double* d_out, const int** d_own)
 {
-    region_tables* tp = g_reg.find(h);
+    region_tables* tp = h->reg.get();
     if (!tp) return remd_fail(h, -2, "alchemical regions: none on this handle");
     region_tables& t = *tp;
     if (!t.d_state_cls || t.K != h->K) return remd_fail(h, -2, "alchemical regions: remd_set_region_lambdas has not been called for these states");
@@ -788,7 +773,7 @@ int remd_regions_pme_tables(remd_ctx* h, const float4** param, const float** rep
 {
     *param = nullptr; *rep_le = nullptr;
     if (!h->regions_exact) return 0;
-    region_tables* t = g_reg.find(h);
+    region_tables* t = h->reg.get();
     if (!t) return 0;
     *param = t->d_param_pme; *rep_le = t->d_rep_le;
     return 1;
@@ -796,7 +781,7 @@ int remd_regions_pme_tables(remd_ctx* h, const float4** param, const float** rep
 // every replica at these lambda_electrostatics (u_kl probes); NULL: back to the replicas' own states.  n = regions.
 int remd_regions_le_override(remd_ctx* h, const float* le, int* n, const float** d_state_le)
 {
-    region_tables* t = g_reg.find(h);
+    region_tables* t = h->reg.get();
     if (!t || !t->c.exact) return remd_fail(h, -2, "alchemical regions: not under the exact PME treatment");
     t->have_override = le != nullptr;
     for (int g = 0; g < 4; ++g) t->le_override[g] = (le && g < t->n_regions) ? le[g] : 1.f;
@@ -808,7 +793,7 @@ int remd_regions_le_override(remd_ctx* h, const float* le, int* n, const float**
 // lambda_electrostatics of region `g` (0-based) at state k, as remd_set_region_lambdas gave it (gbsa.hip: the alchemical particles' factor)
 int remd_regions_state_le(remd_ctx* h, int k, int g, double* le)
 {
-    region_tables* t = g_reg.find(h);
+    region_tables* t = h->reg.get();
     if (!t || t->K <= 0 || k < 0 || k >= t->K || g < 0 || g >= t->n_regions) return -1;
     *le = t->le[(size_t)k * t->n_regions + g];
     return 0;

@@ -10,32 +10,31 @@
 int remd_check_finite(remd_ctx* h);
 int remd_assemble_ukl(remd_ctx* h, double* d_rows);
 int remd_nb_required_epart(remd_ctx* h);
-void remd_free_nonbonded(remd_ctx* h);
-void remd_mix_release(remd_ctx* h);          // mix.hip
 void remd_nb_reset_accumulators(remd_ctx* h); // forces.hip
 void remd_nb_invalidate_sort(remd_ctx* h);    // forces.hip
 int remd_test_fft3d_impl(remd_ctx* h, int nx, int ny, int nz, float* data, int inverse);
 void remd_nb_tune_resolve(remd_ctx* h);
 static int remd_check_device_flags(remd_ctx* h, const char* where, bool may_retry = false);
 const unsigned* remd_mix_pending_flag(remd_ctx* h);      // mix.hip
-void remd_free_constraints(remd_ctx* h);
 
 static std::mutex g_err_mutex;
 static std::string g_last_error;
 
 void remd_set_global_error(const std::string& s) { std::lock_guard<std::mutex> l(g_err_mutex); g_last_error = s; }
 int remd_fail(remd_ctx* h, int code, const std::string& msg) { if (h) h->err = msg; remd_set_global_error(msg); return code; }
+int remd_hip_fail(remd_ctx* h, const char* what, hipError_t e) { return remd_fail(h, -2, std::string(what) + ": " + hipGetErrorString(e)); }
 
-template <typename T> static void dfree(T*& p) { if (p) { hipFree(p); p = nullptr; } }
-
-template <typename T>
-static int upload(remd_ctx* h, T*& dptr, const std::vector<T>& host)
+// What the members do not free themselves, in this order; the device arrays and the feature tables go with the members.
+remd_ctx::~remd_ctx()
 {
-    dfree(dptr);
-    if (host.empty()) return 0;
-    REMD_CHECK(h, hipMalloc(&dptr, sizeof(T) * host.size()));
-    REMD_CHECK(h, hipMemcpy(dptr, host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice));
-    return 0;
+    hipSetDevice(device);
+    if (stream) hipStreamSynchronize(stream);
+    for (remd_ctx* c : phase) delete c;            // (block 0 borrows this handle's streams: before they go)
+    remd_comm_release(this);
+    for (auto& p : prof_pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
+    if (stream2 && !borrowed_stream2) { hipStreamSynchronize(stream2); hipStreamDestroy(stream2); }
+    if (owns_stream && stream) hipStreamDestroy(stream);
+    for (hipEvent_t e : {ev_fork, ev_join, ev0, ev1}) if (e) hipEventDestroy(e);
 }
 
 extern "C" {
@@ -94,7 +93,7 @@ int remd_create(remd_handle* out, int device, void* stream)
     if (device < 0 || device >= n) return remd_fail(nullptr, -1, "remd_create: bad device index");
     e = hipSetDevice(device);
     if (e != hipSuccess) return remd_fail(nullptr, -2, std::string("hipSetDevice: ") + hipGetErrorString(e));
-    remd_ctx* h = new remd_ctx();
+    std::unique_ptr<remd_ctx> h(new remd_ctx());      // (an early return destroys what has been made so far)
     h->device = device;
     h->stream = (hipStream_t)stream;
     read_switches(h->sw);
@@ -104,7 +103,7 @@ int remd_create(remd_handle* out, int device, void* stream)
         // NULL: a private non-blocking stream (the legacy default stream cannot be captured into a graph, and every entry point
         // that hands results to the caller synchronises before it returns, so nothing relies on default-stream ordering)
         if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-            delete h; return remd_fail(nullptr, -2, "hipStreamCreate failed");
+            h->stream = nullptr; return remd_fail(nullptr, -2, "hipStreamCreate failed");
         }
         h->owns_stream = true;
     }
@@ -118,56 +117,15 @@ int remd_create(remd_handle* out, int device, void* stream)
     }
     { const unsigned evf = hipEventReleaseToDevice | hipEventDisableTiming;   // device-scope release: no system-scope cache write-back per fork / join
       hipEventCreateWithFlags(&h->ev_fork, evf); hipEventCreateWithFlags(&h->ev_join, evf); }
-    if (hipMalloc(&h->d_chain_own, 40 * sizeof(unsigned long long)) == hipSuccess) hipMemset(h->d_chain_own, 0, 40 * sizeof(unsigned long long));
-    if (hipMalloc(&h->d_sync, 4 * sizeof(unsigned int)) != hipSuccess || hipMemset(h->d_sync, 0, 4 * sizeof(unsigned int)) != hipSuccess) {
-        delete h; return remd_fail(nullptr, -2, "remd_create: hipMalloc failed");
-    }
-    *out = h;
+    if (!h->d_chain_own.alloc(h.get(), 40)) hipMemset(h->d_chain_own, 0, 40 * sizeof(unsigned long long));
+    if (h->d_sync.alloc(h.get(), 4) || hipMemset(h->d_sync, 0, 4 * sizeof(unsigned int)) != hipSuccess)
+        return remd_fail(nullptr, -2, "remd_create: hipMalloc failed");
+    *out = h.release();
     return 0;
 }
 
 int remd_destroy(remd_handle h)
 {
-    if (!h) return 0;
-    hipSetDevice(h->device);
-    hipStreamSynchronize(h->stream);
-    for (remd_ctx* c : h->phase) remd_destroy(c);         // (block 0 borrows this handle's streams: before they go)
-    h->phase.clear();
-    delete h->sysdesc; h->sysdesc = nullptr;
-    remd_comm_release(h);
-    remd_pme_destroy(h);
-    remd_free_constraints(h);
-    remd_free_nonbonded(h);
-    remd_nocutoff_release(h);
-    remd_gbsa_release(h);
-    remd_regions_release(h);
-    remd_restraints_release(h);
-    remd_mix_release(h);
-    dfree(h->d_invmass); dfree(h->d_mass); dfree(h->d_ext_atoms);
-    dfree(h->d_aterm); h->n_aterm = 0;
-    dfree(h->d_bond_atoms); dfree(h->d_bond_params); dfree(h->d_angle_atoms); dfree(h->d_angle_params);
-    dfree(h->d_torsion_atoms); dfree(h->d_torsion_params);
-    dfree(h->d_nbparam); dfree(h->d_exclmask); dfree(h->d_exc_atoms); dfree(h->d_exc_params); dfree(h->d_excl_pairs);
-    dfree(h->d_alch_atoms);
-    dfree(h->d_beta); dfree(h->d_lam_s); dfree(h->d_lam_e); dfree(h->d_econst);
-    dfree(h->d_pos); dfree(h->d_vel); dfree(h->d_pos_ref); dfree(h->d_force); dfree(h->d_box); dfree(h->d_labels);
-    for (int g = 0; g < 4; ++g) dfree(h->d_force_g[g]);
-    dfree(h->d_ukl); dfree(h->d_potential); dfree(h->d_epart); dfree(h->d_kinetic); dfree(h->d_nan); dfree(h->d_cmm);
-    dfree(h->d_pressure); dfree(h->d_baro); dfree(h->d_box_old); dfree(h->d_baro_x0); dfree(h->d_baro_f0); dfree(h->d_baro_U0); dfree(h->d_baro_acc);
-    dfree(h->d_mix_log); dfree(h->d_noise_id);
-    dfree(h->d_snap_pos); dfree(h->d_snap_vel); dfree(h->d_fin_pos); dfree(h->d_fin_vel); dfree(h->d_snap_box); dfree(h->d_fin_box);
-    dfree(h->d_snap_work);
-    dfree(h->d_nacc); dfree(h->d_nprop); dfree(h->d_logw); dfree(h->d_logP); dfree(h->d_ukl_tmp);
-    if (h->stream2 && !h->borrowed_stream2) { hipStreamSynchronize(h->stream2); hipStreamDestroy(h->stream2); }
-    if (h->owns_stream && h->stream) hipStreamDestroy(h->stream);
-    if (h->d_sync) hipFree(h->d_sync);
-    if (h->d_chain_own) hipFree(h->d_chain_own);
-    if (h->d_work) { hipFree(h->d_work); hipFree(h->d_pe_prev); hipFree(h->d_xold); hipFree(h->d_vold); hipFree(h->d_accept); }
-    if (h->d_chain_sync) hipFree(h->d_chain_sync);
-    if (h->ev_fork) hipEventDestroy(h->ev_fork);
-    if (h->ev_join) hipEventDestroy(h->ev_join);
-    if (h->ev0) hipEventDestroy(h->ev0);
-    if (h->ev1) hipEventDestroy(h->ev1);
     delete h;
     return 0;
 }
@@ -224,15 +182,15 @@ int remd_set_system(remd_handle h, const remd_system_desc* d)
         m[i] = (float)d->mass[i]; im[i] = (float)(1.0 / d->mass[i]); h->total_mass += d->mass[i];
     }
     int rc;
-    if ((rc = upload(h, h->d_invmass, im))) return rc;
-    if ((rc = upload(h, h->d_mass, m))) return rc;
+    if ((rc = h->d_invmass.upload(h, im))) return rc;
+    if ((rc = h->d_mass.upload(h, m))) return rc;
     h->n_ext = d->n_ext; h->ext_K = d->ext_K; h->ext_x0 = d->ext_x0; h->ext_U0 = d->ext_U0;
     {
         std::vector<int> ea(d->ext_atoms, d->ext_atoms + d->n_ext);
-        if ((rc = upload(h, h->d_ext_atoms, ea))) return rc;
+        if ((rc = h->d_ext_atoms.upload(h, ea))) return rc;
     }
     h->cmm_frequency = d->cmm_frequency;
-    if (!h->parent) { if (!h->sysdesc) h->sysdesc = new remd_desc_store(); h->sysdesc->assign(d); h->config_version++; }
+    if (!h->parent) { if (!h->sysdesc) h->sysdesc.reset(new remd_desc_store()); h->sysdesc->assign(d); h->config_version++; }
     if ((rc = remd_build_constraints(h, d))) return rc;
     if ((rc = remd_build_nonbonded(h, d))) return rc;
     h->has_system = true;
@@ -252,13 +210,13 @@ int remd_set_states(remd_handle h, int K, const double* beta, const double* lam_
     if (econst) h->econst.assign(econst, econst + K);
     for (int k = 0; k < K; ++k) if (!(h->beta[k] > 0)) return remd_fail(h, -1, "remd_set_states: beta must be > 0");
     int rc;
-    if ((rc = upload(h, h->d_beta, h->beta))) return rc;
-    if ((rc = upload(h, h->d_lam_s, h->lam_s))) return rc;
-    if ((rc = upload(h, h->d_lam_e, h->lam_e))) return rc;
-    if ((rc = upload(h, h->d_econst, h->econst))) return rc;
-    dfree(h->d_ukl);
+    if ((rc = h->d_beta.upload(h, h->beta))) return rc;
+    if ((rc = h->d_lam_s.upload(h, h->lam_s))) return rc;
+    if ((rc = h->d_lam_e.upload(h, h->lam_e))) return rc;
+    if ((rc = h->d_econst.upload(h, h->econst))) return rc;
+    h->d_ukl.reset();
     if (h->R_global > 0) {
-        REMD_CHECK(h, hipMalloc(&h->d_ukl, sizeof(double) * (size_t)h->R_global * K));
+        REMD_TRY(h->d_ukl.alloc(h, (size_t)h->R_global * K));
         REMD_CHECK(h, hipMemsetAsync(h->d_ukl, 0, sizeof(double) * (size_t)h->R_global * K, h->stream));
     }
     return 0;
@@ -293,7 +251,7 @@ int remd_set_replica_ids(remd_handle h, const int64_t* ids)
 {
     if (!h || h->R <= 0) return remd_fail(h, -1, "remd_set_replica_ids: call remd_set_replicas first");
     hipSetDevice(h->device);
-    if (h->d_noise_id) { REMD_CHECK(h, hipStreamSynchronize(h->stream)); hipFree(h->d_noise_id); h->d_noise_id = nullptr; }
+    if (h->d_noise_id) { REMD_CHECK(h, hipStreamSynchronize(h->stream)); h->d_noise_id.reset(); }
     h->noise_id_host.clear(); h->ids_version++;
     if (!ids) return 0;                                   // back to the block's own global indices
     h->noise_id_host.assign(ids, ids + h->R);
@@ -302,7 +260,7 @@ int remd_set_replica_ids(remd_handle h, const int64_t* ids)
         if (ids[r] < 0 || ids[r] > 0xffffffffll) return remd_fail(h, -1, "remd_set_replica_ids: ids must fit 32 bits");
         v[r] = (unsigned int)ids[r];
     }
-    REMD_CHECK(h, hipMalloc(&h->d_noise_id, sizeof(unsigned int) * h->R));
+    REMD_TRY(h->d_noise_id.alloc(h, h->R));
     REMD_CHECK(h, hipMemcpy(h->d_noise_id, v.data(), sizeof(unsigned int) * h->R, hipMemcpyHostToDevice));
     return 0;
 }
@@ -330,32 +288,30 @@ int remd_set_replicas(remd_handle h, int R_global, int r_begin, int R_local, con
             if (!(box[3 * r + k] >= 2.0 * h->cutoff)) return remd_fail(h, -1, "remd_set_replicas: box smaller than twice the cutoff");
     hipSetDevice(h->device);
     const bool realloc = (R_local != h->R) || (R_global != h->R_global) || !h->d_pos;
-    if (h->d_noise_id) { hipStreamSynchronize(h->stream); hipFree(h->d_noise_id); h->d_noise_id = nullptr; }     // ids belong to one set of replicas
+    if (h->d_noise_id) { hipStreamSynchronize(h->stream); h->d_noise_id.reset(); }     // ids belong to one set of replicas
     h->noise_id_host.clear(); h->ids_version++;
     h->R_global = R_global; h->r_begin = r_begin; h->R = R_local;
     const size_t n = (size_t)R_local * h->Npad;
     if (realloc) {
-        dfree(h->d_pos); dfree(h->d_vel); dfree(h->d_force); dfree(h->d_box); dfree(h->d_labels); dfree(h->d_ukl);
-        for (int g = 0; g < 4; ++g) dfree(h->d_force_g[g]);
-        h->force_g_n = 0;
+        h->d_ukl.reset();
+        for (int g = 0; g < 4; ++g) h->d_force_g[g].reset();
         // per-replica scratch of the barostat and of the restart attempts is sized by R_local as well
-        dfree(h->d_baro); dfree(h->d_box_old); dfree(h->d_baro_x0); dfree(h->d_baro_f0); dfree(h->d_baro_U0); dfree(h->d_baro_acc);
-        dfree(h->d_snap_pos); dfree(h->d_snap_vel); dfree(h->d_fin_pos); dfree(h->d_fin_vel); dfree(h->d_snap_box); dfree(h->d_fin_box);
-        dfree(h->d_snap_work);
-        dfree(h->d_potential); dfree(h->d_epart); dfree(h->d_kinetic); dfree(h->d_nan); dfree(h->d_cmm);
-        REMD_CHECK(h, hipMalloc(&h->d_pos, sizeof(float4) * n));
-        REMD_CHECK(h, hipMalloc(&h->d_vel, sizeof(float4) * n));
-        REMD_CHECK(h, hipMalloc(&h->d_force, sizeof(long long) * 3 * n));
-        REMD_CHECK(h, hipMalloc(&h->d_box, sizeof(float) * 4 * R_local));
-        REMD_CHECK(h, hipMalloc(&h->d_labels, sizeof(int64_t) * R_global));
-        REMD_CHECK(h, hipMalloc(&h->d_potential, sizeof(double) * R_local));
-        REMD_CHECK(h, hipMalloc(&h->d_kinetic, sizeof(double) * R_local));
-        REMD_CHECK(h, hipMalloc(&h->d_nan, sizeof(int) * R_local));
-        REMD_CHECK(h, hipMalloc(&h->d_cmm, sizeof(long long) * 4 * 2 * R_local));
+        h->d_baro.reset(); h->d_box_old.reset(); h->d_baro_x0.reset(); h->d_baro_f0.reset(); h->d_baro_U0.reset(); h->d_baro_acc.reset();
+        h->d_snap_pos.reset(); h->d_snap_vel.reset(); h->d_fin_pos.reset(); h->d_fin_vel.reset(); h->d_snap_box.reset(); h->d_fin_box.reset();
+        h->d_snap_work.reset();
+        REMD_TRY(h->d_pos.alloc(h, n));
+        REMD_TRY(h->d_vel.alloc(h, n));
+        REMD_TRY(h->d_force.alloc(h, 3 * n));
+        REMD_TRY(h->d_box.alloc(h, 4 * R_local));
+        REMD_TRY(h->d_labels.alloc(h, R_global));
+        REMD_TRY(h->d_potential.alloc(h, R_local));
+        REMD_TRY(h->d_kinetic.alloc(h, R_local));
+        REMD_TRY(h->d_nan.alloc(h, R_local));
+        REMD_TRY(h->d_cmm.alloc(h, 4 * 2 * R_local));
         h->n_epart = remd_nb_required_epart(h);
-        REMD_CHECK(h, hipMalloc(&h->d_epart, sizeof(double) * (size_t)h->n_epart * R_local));
+        REMD_TRY(h->d_epart.alloc(h, (size_t)h->n_epart * R_local));
         if (h->K > 0) {
-            REMD_CHECK(h, hipMalloc(&h->d_ukl, sizeof(double) * (size_t)R_global * h->K));
+            REMD_TRY(h->d_ukl.alloc(h, (size_t)R_global * h->K));
             REMD_CHECK(h, hipMemsetAsync(h->d_ukl, 0, sizeof(double) * (size_t)R_global * h->K, h->stream));
         }
     }
@@ -429,9 +385,8 @@ int remd_copy_replicas(remd_handle dst, const int32_t* dst_slot, remd_handle src
     }
     hipSetDevice(dst->device);
     REMD_CHECK(dst, hipStreamSynchronize(src->stream));              // what the source computed last is complete
-    struct scratch { int* p = nullptr; ~scratch() { if (p) hipFree(p); } } slots_dev;      // (freed on every return path)
-    REMD_CHECK(dst, hipMalloc(&slots_dev.p, sizeof(int) * slots.size()));
-    int* d_slots = slots_dev.p;
+    dev_array<int> d_slots;            // (freed on every return path)
+    REMD_TRY(d_slots.alloc(dst, slots.size()));
     REMD_CHECK(dst, hipMemcpyAsync(d_slots, slots.data(), sizeof(int) * slots.size(), hipMemcpyHostToDevice, dst->stream));
     const bool pos = what & 1, vel = what & 2, box = what & 4;
     hipLaunchKernelGGL(copy_replica_rows_kernel, dim3((dst->Npad + 255) / 256, n), dim3(256), 0, dst->stream, dst->Npad, d_slots, n,
@@ -783,6 +738,39 @@ static int remd_propagate_phased(remd_ctx* h, int P, int64_t iteration, int32_t*
     return 0;
 }
 
+// mcmc.py:700-703: the state a propagation starts from is what a failed attempt is reset to (and what a propagation whose device-side
+// waits failed is run again from).  The heat / shadow work / Metropolis counters (remd_get_work) of an attempt that is thrown away must
+// not stay accumulated: they are snapshotted and restored like the coordinates.  d_snap_work [0 .. 4R): at the start of the
+// call, [4R .. 8R): per replica at its successful attempt (remd_propagate fills that half and d_fin_*)
+static int snapshot_capture(remd_ctx* h)
+{
+    const size_t n = (size_t)h->Npad * h->R, wbytes = sizeof(long long) * 4 * h->R;
+    REMD_TRY(h->d_snap_pos.grow(h, n)); REMD_TRY(h->d_snap_vel.grow(h, n));
+    REMD_TRY(h->d_fin_pos.grow(h, n)); REMD_TRY(h->d_fin_vel.grow(h, n));
+    REMD_TRY(h->d_snap_box.grow(h, 4 * (size_t)h->R)); REMD_TRY(h->d_fin_box.grow(h, 4 * (size_t)h->R));
+    REMD_CHECK(h, hipMemcpyAsync(h->d_snap_box, h->d_box, sizeof(float) * 4 * h->R, hipMemcpyDeviceToDevice, h->stream));
+    REMD_CHECK(h, hipMemcpyAsync(h->d_snap_pos, h->d_pos, sizeof(float4) * n, hipMemcpyDeviceToDevice, h->stream));
+    REMD_CHECK(h, hipMemcpyAsync(h->d_snap_vel, h->d_vel, sizeof(float4) * n, hipMemcpyDeviceToDevice, h->stream));
+    REMD_TRY(h->d_snap_work.grow(h, 8 * (size_t)h->R));
+    if (h->d_work.size() == 4 * (size_t)h->R) REMD_CHECK(h, hipMemcpyAsync(h->d_snap_work, h->d_work, wbytes, hipMemcpyDeviceToDevice, h->stream));
+    else REMD_CHECK(h, hipMemsetAsync(h->d_snap_work, 0, wbytes, h->stream));
+    return 0;
+}
+
+// the replicas back at the start of the call (final = false) or at their successful attempts (final = true)
+static int snapshot_restore(remd_ctx* h, bool final)
+{
+    const size_t bytes = sizeof(float4) * (size_t)h->Npad * h->R;
+    REMD_CHECK(h, hipMemcpyAsync(h->d_pos, final ? h->d_fin_pos : h->d_snap_pos, bytes, hipMemcpyDeviceToDevice, h->stream));
+    REMD_CHECK(h, hipMemcpyAsync(h->d_vel, final ? h->d_fin_vel : h->d_snap_vel, bytes, hipMemcpyDeviceToDevice, h->stream));
+    REMD_CHECK(h, hipMemcpyAsync(h->d_box, final ? h->d_fin_box : h->d_snap_box, sizeof(float) * 4 * h->R, hipMemcpyDeviceToDevice, h->stream));
+    if (h->d_work)
+        REMD_CHECK(h, hipMemcpyAsync(h->d_work, h->d_snap_work + (final ? 4 * h->R : 0), sizeof(long long) * 4 * h->R, hipMemcpyDeviceToDevice, h->stream));
+    h->box_version++;
+    h->forces_valid = false; h->force_zeroed = false;
+    return 0;
+}
+
 int remd_propagate(remd_handle h, int64_t iteration, int32_t* nan_flags)
 {
     if (!h || !h->has_system || !h->has_integrator || h->R <= 0 || h->K <= 0)
@@ -800,27 +788,9 @@ int remd_propagate(remd_handle h, int64_t iteration, int32_t* nan_flags)
     hipEventRecord(h->ev0, h->stream);
     int rc;
     const int attempts = h->n_restart_attempts;
-    const size_t seg = (size_t)h->Npad, bytes = sizeof(float4) * seg * h->R;
+    const size_t seg = (size_t)h->Npad;
     int device_retry = 0;
-    {
-        // mcmc.py:700-703: the state the move starts from is what a failed attempt is reset to (and what a propagation whose
-        // device-side waits failed is run again from)
-        if (!h->d_snap_pos) {
-            REMD_CHECK(h, hipMalloc(&h->d_snap_pos, bytes)); REMD_CHECK(h, hipMalloc(&h->d_snap_vel, bytes));
-            REMD_CHECK(h, hipMalloc(&h->d_fin_pos, bytes)); REMD_CHECK(h, hipMalloc(&h->d_fin_vel, bytes));
-            REMD_CHECK(h, hipMalloc(&h->d_snap_box, sizeof(float) * 4 * h->R)); REMD_CHECK(h, hipMalloc(&h->d_fin_box, sizeof(float) * 4 * h->R));
-        }
-        REMD_CHECK(h, hipMemcpyAsync(h->d_snap_box, h->d_box, sizeof(float) * 4 * h->R, hipMemcpyDeviceToDevice, h->stream));
-        REMD_CHECK(h, hipMemcpyAsync(h->d_snap_pos, h->d_pos, bytes, hipMemcpyDeviceToDevice, h->stream));
-        REMD_CHECK(h, hipMemcpyAsync(h->d_snap_vel, h->d_vel, bytes, hipMemcpyDeviceToDevice, h->stream));
-    }
-    // heat / shadow work / Metropolis counters (remd_get_work) of an attempt that is thrown away must not stay accumulated
-    // (ADVICE r3): they are snapshotted and restored like the coordinates.  [0 .. 4R): at the start, [4R .. 8R): per replica at success
-    const size_t wbytes = sizeof(long long) * 4 * h->R;
-    const bool had_work = h->d_work != nullptr && h->work_R == h->R;
-    if (!h->d_snap_work) REMD_CHECK(h, hipMalloc(&h->d_snap_work, 2 * wbytes));
-    if (had_work) REMD_CHECK(h, hipMemcpyAsync(h->d_snap_work, h->d_work, wbytes, hipMemcpyDeviceToDevice, h->stream));
-    else REMD_CHECK(h, hipMemsetAsync(h->d_snap_work, 0, wbytes, h->stream));
+    REMD_TRY(snapshot_capture(h));
     std::vector<int> flags(h->R, 0);
     std::vector<char> pending(h->R, 1);
     for (int a = 0;; ++a) {
@@ -841,12 +811,7 @@ int remd_propagate(remd_handle h, int64_t iteration, int32_t* nan_flags)
             const int rc2 = remd_recover_device_flag(h, spin_out, "remd_propagate", device_retry == 0);
             if (rc2) return rc2;
             ++device_retry;
-            REMD_CHECK(h, hipMemcpyAsync(h->d_pos, h->d_snap_pos, bytes, hipMemcpyDeviceToDevice, h->stream));
-            REMD_CHECK(h, hipMemcpyAsync(h->d_vel, h->d_snap_vel, bytes, hipMemcpyDeviceToDevice, h->stream));
-            REMD_CHECK(h, hipMemcpyAsync(h->d_box, h->d_snap_box, sizeof(float) * 4 * h->R, hipMemcpyDeviceToDevice, h->stream));
-            if (h->d_work) REMD_CHECK(h, hipMemcpyAsync(h->d_work, h->d_snap_work, wbytes, hipMemcpyDeviceToDevice, h->stream));
-            h->box_version++;
-            h->forces_valid = false; h->force_zeroed = false;
+            REMD_TRY(snapshot_restore(h, false));
             --a;
             continue;
         }
@@ -862,14 +827,7 @@ int remd_propagate(remd_handle h, int64_t iteration, int32_t* nan_flags)
             if (h->d_work) REMD_CHECK(h, hipMemcpyAsync(h->d_snap_work + 4 * (h->R + r), h->d_work + 4 * r, sizeof(long long) * 4, hipMemcpyDeviceToDevice, h->stream));
             if (!flags[r]) pending[r] = 0;
         }
-        const float4* src_p = last ? h->d_fin_pos : h->d_snap_pos;
-        const float4* src_v = last ? h->d_fin_vel : h->d_snap_vel;
-        REMD_CHECK(h, hipMemcpyAsync(h->d_pos, src_p, bytes, hipMemcpyDeviceToDevice, h->stream));
-        REMD_CHECK(h, hipMemcpyAsync(h->d_vel, src_v, bytes, hipMemcpyDeviceToDevice, h->stream));
-        REMD_CHECK(h, hipMemcpyAsync(h->d_box, last ? h->d_fin_box : h->d_snap_box, sizeof(float) * 4 * h->R, hipMemcpyDeviceToDevice, h->stream));
-        if (h->d_work) REMD_CHECK(h, hipMemcpyAsync(h->d_work, h->d_snap_work + (last ? 4 * h->R : 0), wbytes, hipMemcpyDeviceToDevice, h->stream));
-        h->box_version++;
-        h->forces_valid = false; h->force_zeroed = false;
+        REMD_TRY(snapshot_restore(h, last));
         if (last) { for (int r = 0; r < h->R; ++r) flags[r] = pending[r] ? 1 : 0; break; }
     }
     hipEventRecord(h->ev1, h->stream);
@@ -911,19 +869,7 @@ int remd_propagate_many(remd_handle* hs, int32_t n, int64_t iteration, int32_t* 
     for (int i = 0; i < n; ++i) {
         remd_ctx* h = hs[i];
         hipEventRecord(h->ev0, h->stream);
-        const size_t bytes = sizeof(float4) * (size_t)h->Npad * h->R;
-        if (!h->d_snap_pos) {
-            REMD_CHECK(h, hipMalloc(&h->d_snap_pos, bytes)); REMD_CHECK(h, hipMalloc(&h->d_snap_vel, bytes));
-            REMD_CHECK(h, hipMalloc(&h->d_fin_pos, bytes)); REMD_CHECK(h, hipMalloc(&h->d_fin_vel, bytes));
-            REMD_CHECK(h, hipMalloc(&h->d_snap_box, sizeof(float) * 4 * h->R)); REMD_CHECK(h, hipMalloc(&h->d_fin_box, sizeof(float) * 4 * h->R));
-        }
-        REMD_CHECK(h, hipMemcpyAsync(h->d_snap_box, h->d_box, sizeof(float) * 4 * h->R, hipMemcpyDeviceToDevice, h->stream));
-        REMD_CHECK(h, hipMemcpyAsync(h->d_snap_pos, h->d_pos, bytes, hipMemcpyDeviceToDevice, h->stream));
-        REMD_CHECK(h, hipMemcpyAsync(h->d_snap_vel, h->d_vel, bytes, hipMemcpyDeviceToDevice, h->stream));
-        const size_t wbytes = sizeof(long long) * 4 * h->R;
-        if (!h->d_snap_work) REMD_CHECK(h, hipMalloc(&h->d_snap_work, 2 * wbytes));
-        if (h->d_work != nullptr && h->work_R == h->R) REMD_CHECK(h, hipMemcpyAsync(h->d_snap_work, h->d_work, wbytes, hipMemcpyDeviceToDevice, h->stream));
-        else REMD_CHECK(h, hipMemsetAsync(h->d_snap_work, 0, wbytes, h->stream));
+        REMD_TRY(snapshot_capture(h));
         // (without polls_ok no workgroup waits on a CU for another stream -- join by a one-wavefront launch, momentum sum as two
         // launches; measured slower than the polling chain once the handles' streams sit on four hardware queues: 76.1 against 72.9 ms)
         h->lean_waits = !polls_ok;
@@ -964,13 +910,7 @@ int remd_propagate_many(remd_handle* hs, int32_t n, int64_t iteration, int32_t* 
         for (int r = 0; r < h->R; ++r) n_bad += flags[i][r] ? 1 : 0;
         if (spin[i] || (n_bad > 0 && h->n_restart_attempts > 0)) {
             // the rare cases go through the single-handle path from the state this call started from
-            const size_t bytes = sizeof(float4) * (size_t)h->Npad * h->R;
-            REMD_CHECK(h, hipMemcpyAsync(h->d_pos, h->d_snap_pos, bytes, hipMemcpyDeviceToDevice, h->stream));
-            REMD_CHECK(h, hipMemcpyAsync(h->d_vel, h->d_snap_vel, bytes, hipMemcpyDeviceToDevice, h->stream));
-            REMD_CHECK(h, hipMemcpyAsync(h->d_box, h->d_snap_box, sizeof(float) * 4 * h->R, hipMemcpyDeviceToDevice, h->stream));
-            if (h->d_work) REMD_CHECK(h, hipMemcpyAsync(h->d_work, h->d_snap_work, sizeof(long long) * 4 * h->R, hipMemcpyDeviceToDevice, h->stream));
-            h->box_version++;
-            h->forces_valid = false; h->force_zeroed = false;
+            REMD_TRY(snapshot_restore(h, false));
             if (!spin[i]) { remd_nb_invalidate_sort(h); }
             int rc1 = remd_propagate(h, iteration, nan_flags ? nan_flags + off : nullptr);
             if (rc1) return rc1;
@@ -991,7 +931,7 @@ int remd_set_barostat(remd_handle h, int K, const double* pressure, int frequenc
     if (K != h->K) return remd_fail(h, -1, "remd_set_barostat: K differs from remd_set_states");
     std::vector<double> p(pressure, pressure + K);
     for (double v : p) if (!(v == v)) return remd_fail(h, -1, "remd_set_barostat: NaN pressure");
-    int rc = upload(h, h->d_pressure, p);
+    int rc = h->d_pressure.upload(h, p);
     if (rc) return rc;
     if (h->baro_frequency != frequency || h->pressure_host != p) h->config_version++;     // (the blocks of a phased propagation follow)
     h->baro_frequency = frequency;
@@ -1107,18 +1047,13 @@ int remd_compute_energies(remd_handle h, double* d_ukl_rows, double* ukl_host, d
 static int ensure_mix_buffers(remd_ctx* h, int R, int K)
 {
     if (h->stats_K != K || !h->d_nacc) {
-        dfree(h->d_nacc); dfree(h->d_nprop); dfree(h->d_logw);
-        REMD_CHECK(h, hipMalloc(&h->d_nacc, sizeof(unsigned long long) * (size_t)K * K));
-        REMD_CHECK(h, hipMalloc(&h->d_nprop, sizeof(unsigned long long) * (size_t)K * K));
-        REMD_CHECK(h, hipMalloc(&h->d_logw, sizeof(double) * K));
+        REMD_TRY(h->d_nacc.alloc(h, (size_t)K * K));
+        REMD_TRY(h->d_nprop.alloc(h, (size_t)K * K));
+        REMD_TRY(h->d_logw.alloc(h, K));
         h->stats_K = K;
     }
-    if (h->ukl_tmp_n < (size_t)R * K) {
-        dfree(h->d_ukl_tmp); dfree(h->d_logP);
-        REMD_CHECK(h, hipMalloc(&h->d_ukl_tmp, sizeof(double) * (size_t)R * K));
-        REMD_CHECK(h, hipMalloc(&h->d_logP, sizeof(double) * (size_t)R * K));
-        h->ukl_tmp_n = (size_t)R * K;
-    }
+    REMD_TRY(h->d_ukl_tmp.grow(h, (size_t)R * K));
+    REMD_TRY(h->d_logP.grow(h, (size_t)R * K));
     return 0;
 }
 
@@ -1170,12 +1105,10 @@ int remd_mix(remd_handle h, int scheme, int64_t iteration, int R, int K, const d
     }
     int rc = ensure_mix_buffers(h, R, K);
     if (rc) return rc;
-    int64_t* d_labels = nullptr;
-    bool own = false;
-    if (h->d_labels && R == h->R_global) d_labels = h->d_labels;
-    else { REMD_CHECK(h, hipMalloc(&d_labels, sizeof(int64_t) * R)); own = true; }
-    rc = mix_common(h, scheme, iteration, R, K, ld, d_ukl, labels, n_accepted, n_proposed, log_weights, sams_log_P, -1, d_labels);
-    if (own) hipFree(d_labels);
+    dev_array<int64_t> scratch;        // the labels of a matrix that is not this handle's
+    const bool own = !(h->d_labels && R == h->R_global);
+    if (own) REMD_TRY(scratch.alloc(h, R));
+    rc = mix_common(h, scheme, iteration, R, K, ld, d_ukl, labels, n_accepted, n_proposed, log_weights, sams_log_P, -1, own ? scratch : h->d_labels);
     if (!rc && !own) h->labels.assign(labels, labels + R);
     return rc;
 }
@@ -1189,12 +1122,10 @@ int remd_mix_host(remd_handle h, int scheme, int64_t iteration, int R, int K, co
     int rc = ensure_mix_buffers(h, R, K);
     if (rc) return rc;
     REMD_CHECK(h, hipMemcpyAsync(h->d_ukl_tmp, ukl_host, sizeof(double) * (size_t)R * K, hipMemcpyHostToDevice, h->stream));
-    int64_t* d_labels = nullptr;
-    REMD_CHECK(h, hipMalloc(&d_labels, sizeof(int64_t) * R));
-    rc = mix_common(h, scheme, iteration, R, K, K, h->d_ukl_tmp, labels, n_accepted, n_proposed, log_weights, sams_log_P,
-                    n_attempts, d_labels);
-    hipFree(d_labels);
-    return rc;
+    dev_array<int64_t> d_labels;
+    REMD_TRY(d_labels.alloc(h, R));
+    return mix_common(h, scheme, iteration, R, K, K, h->d_ukl_tmp, labels, n_accepted, n_proposed, log_weights, sams_log_P,
+                      n_attempts, d_labels);
 }
 
 int remd_get_replicas(remd_handle h, double* x, double* v, double* potential, double* kinetic)

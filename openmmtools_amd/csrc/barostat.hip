@@ -99,12 +99,12 @@ int remd_barostat_buffers(remd_ctx* h)
 {
     const int R = h->R, Npad = h->Npad;
     if (!h->d_baro) {
-        REMD_CHECK(h, hipMalloc(&h->d_baro, sizeof(double) * 8 * R)); REMD_CHECK(h, hipMemsetAsync(h->d_baro, 0, sizeof(double) * 8 * R, h->stream));
-        REMD_CHECK(h, hipMalloc(&h->d_box_old, sizeof(float) * 4 * R));
-        REMD_CHECK(h, hipMalloc(&h->d_baro_x0, sizeof(float4) * (size_t)R * Npad));
-        REMD_CHECK(h, hipMalloc(&h->d_baro_f0, sizeof(long long) * 3 * (size_t)R * Npad));
-        REMD_CHECK(h, hipMalloc(&h->d_baro_U0, sizeof(double) * R));
-        REMD_CHECK(h, hipMalloc(&h->d_baro_acc, sizeof(int) * R));
+        REMD_TRY(h->d_baro.alloc(h, 8 * (size_t)R)); REMD_CHECK(h, hipMemsetAsync(h->d_baro, 0, sizeof(double) * 8 * R, h->stream));
+        REMD_TRY(h->d_box_old.alloc(h, 4 * R));
+        REMD_TRY(h->d_baro_x0.alloc(h, (size_t)R * Npad));
+        REMD_TRY(h->d_baro_f0.alloc(h, 3 * (size_t)R * Npad));
+        REMD_TRY(h->d_baro_U0.alloc(h, R));
+        REMD_TRY(h->d_baro_acc.alloc(h, R));
     }
     return 0;
 }

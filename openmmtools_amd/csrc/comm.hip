@@ -84,7 +84,7 @@ int remd_comm_init(remd_handle h, int rank, int world, const void* id)
     ncclComm_t c = nullptr;
     RCCL_CHECK(h, api, api->CommInitRank(&c, world, u, rank));
     h->comm = c; h->comm_rank = rank; h->comm_world = world; h->comm_part_current = false;
-    REMD_CHECK(h, hipMalloc(&h->d_comm_part, sizeof(long long) * 2 * (size_t)(world + 1)));
+    REMD_TRY(h->d_comm_part.alloc(h, 2 * (size_t)(world + 1)));
     return 0;
 }
 
@@ -154,6 +154,6 @@ void remd_comm_release(remd_ctx* h)
         if (api->lib) api->CommDestroy((ncclComm_t)h->comm);
         h->comm = nullptr;
     }
-    if (h->d_comm_part) { hipFree(h->d_comm_part); h->d_comm_part = nullptr; }
+    h->d_comm_part.reset();
     h->comm_rank = 0; h->comm_world = 1; h->comm_part_current = false;
 }

@@ -44,20 +44,20 @@ struct nb_tables {
     nb_params p{};
     int method = NB_LJ_ONLY;
     bool has_alch = false;
-    float4* d_param = nullptr;            // [Npad] (q*sqrt(k_e), sigma/2, 2*sqrt(eps), alchemical flag)
-    unsigned long long* d_mask = nullptr; // [Npad][excl_words]
-    int n_exc = 0; int* d_exc_atoms = nullptr; float* d_exc_params = nullptr;     // nonzero exceptions
-    int* d_exc_alch = nullptr; int* d_excl_alch = nullptr;   // number of alchemical atoms in each pair (0, 1, 2)
+    dev_array<float4> d_param;            // [Npad] (q*sqrt(k_e), sigma/2, 2*sqrt(eps), alchemical flag)
+    dev_array<unsigned long long> d_mask; // [Npad][excl_words]
+    int n_exc = 0; dev_array<int> d_exc_atoms; dev_array<float> d_exc_params;     // nonzero exceptions
+    dev_array<int> d_exc_alch; dev_array<int> d_excl_alch;   // number of alchemical atoms in each pair (0, 1, 2)
     double lam_e_override = -1.0;         // >= 0: evaluate every replica at this lambda_electrostatics (u_kl probes)
     double self_nn = 0, self_aa = 0, q_n = 0, q_a = 0;   // Ewald self / net-charge pieces (non-alchemical, alchemical)
-    double* d_probe = nullptr; int probe_R = 0;            // [3][R] potentials at lambda_e = 0, 1/2, 1
-    int n_excl = 0; int* d_excl_atoms = nullptr; float* d_excl_qq = nullptr;      // all excluded pairs (Ewald correction)
-    float* d_rep_lam = nullptr;           // [R][4] per replica: lambda_s^a, alpha (1-lambda_s)^b, lambda_e, pad
+    dev_array<double> d_probe; int probe_R = 0;            // [3][R] potentials at lambda_e = 0, 1/2, 1
+    int n_excl = 0; dev_array<int> d_excl_atoms; dev_array<float> d_excl_qq;      // all excluded pairs (Ewald correction)
+    dev_array<float> d_rep_lam;           // [R][4] per replica: lambda_s^a, alpha (1-lambda_s)^b, lambda_e, pad
     int rep_lam_R = 0;
     std::vector<double> state_lam_a, state_sc;   // per state, for the alchemical u_kl kernel
-    double* d_state_lam = nullptr;        // [K][2]
-    double* d_alch_ukl = nullptr;         // [R][K]
-    int* d_own = nullptr;                 // [R] the replicas' own states (column of d_alch_ukl that d_potential already holds)
+    dev_array<double> d_state_lam;        // [K][2]
+    dev_array<double> d_alch_ukl;         // [R][K]
+    dev_array<int> d_own;                 // [R] the replicas' own states (column of d_alch_ukl that d_potential already holds)
     int alch_R = 0, alch_K = 0;
     double disp_coeff = 0.0;              // E_disp = disp_coeff / V
     double self_energy = 0.0;             // Ewald self term, kJ/mol
@@ -66,33 +66,33 @@ struct nb_tables {
     std::vector<char> is_alch;
     // spatial ordering: exclusion/constraint-connected groups (molecules) stay contiguous, groups are ordered
     // along a Morton curve of their cells every resort_interval force evaluations
-    int n_groups = 0; int* d_grp_first = nullptr; int* d_grp_size = nullptr;
-    int* d_order = nullptr;               // [R][Npad] sorted slot -> atom (-1: padding)
-    float4* d_spos = nullptr;             // [R][Npad] positions in sorted order (refreshed every evaluation)
-    float4* d_sposi = nullptr;            // [R][Npad] the same as 32-bit box fractions (bit patterns in x, y, z) + charge in w
-    float4* d_lj_sposi = nullptr;         // [R][NLpad] the LJ sub-system's
-    float4* d_sparam = nullptr;           // [R][Npad]
-    unsigned long long* d_smask = nullptr;// [R][Npad][excl_words]
-    float4* d_tile_c = nullptr; float4* d_tile_h = nullptr;   // [R][ntile] bounding-box centre / half extent
-    float4* d_partial = nullptr; size_t partial_n = 0;      // [R][n_jsplit][Npad] nonbonded force partials
+    int n_groups = 0; dev_array<int> d_grp_first; dev_array<int> d_grp_size;
+    dev_array<int> d_order;               // [R][Npad] sorted slot -> atom (-1: padding)
+    dev_array<float4> d_spos;             // [R][Npad] positions in sorted order (refreshed every evaluation)
+    dev_array<float4> d_sposi;            // [R][Npad] the same as 32-bit box fractions (bit patterns in x, y, z) + charge in w
+    dev_array<float4> d_lj_sposi;         // [R][NLpad] the LJ sub-system's
+    dev_array<float4> d_sparam;           // [R][Npad]
+    dev_array<unsigned long long> d_smask;// [R][Npad][excl_words]
+    dev_array<float4> d_tile_c; dev_array<float4> d_tile_h;   // [R][ntile] bounding-box centre / half extent
+    dev_array<float4> d_partial;          // [R][n_jsplit][Npad] nonbonded force partials (grown on demand)
     // 8-atom cluster pair lists (sorted slot space): lane = (i atom, j atom) of an 8 x 8 cluster pair
-    float4* d_cl_c = nullptr; float4* d_cl_h = nullptr;     // [R][ncl] cluster bounding boxes
+    dev_array<float4> d_cl_c; dev_array<float4> d_cl_h;     // [R][ncl] cluster bounding boxes
     int cl_cap = 0; bool clusters = true;
     // LJ-active sub-system (atoms with eps != 0; 1/3 of a TIP3P box): own sorted order, clusters and pair list, so
     // that the main cluster kernel is Coulomb-only
     bool lj_split = false; int NL = 0, NLpad = 0, lj_words = 1, lj_cap = 0;
-    int* d_lj_ord = nullptr;              // [Npad] atom -> LJ ordinal (-1: no LJ)
-    unsigned long long* d_lj_mask = nullptr;   // [NLpad][lj_words] exclusion window in LJ-ordinal space
-    int* d_lj_order = nullptr; float4* d_lj_spos = nullptr; float4* d_lj_sparam = nullptr; unsigned long long* d_lj_smask = nullptr;
-    float4* d_lj_tile_c = nullptr; float4* d_lj_tile_h = nullptr; float4* d_lj_cl_c = nullptr; float4* d_lj_cl_h = nullptr;
+    dev_array<int> d_lj_ord;              // [Npad] atom -> LJ ordinal (-1: no LJ)
+    dev_array<unsigned long long> d_lj_mask;   // [NLpad][lj_words] exclusion window in LJ-ordinal space
+    dev_array<int> d_lj_order; dev_array<float4> d_lj_spos; dev_array<float4> d_lj_sparam; dev_array<unsigned long long> d_lj_smask;
+    dev_array<float4> d_lj_tile_c; dev_array<float4> d_lj_tile_h; dev_array<float4> d_lj_cl_c; dev_array<float4> d_lj_cl_h;
     // Newton's-third-law path: per-tile union lists (jc | imask << 16) and near-diagonal exclusion words
     int sci_split = 12;     // list slices per tile (workgroups of 4 wavefronts); set per system in remd_build_nonbonded
-    unsigned int* d_sci_list = nullptr; int* d_sci_count = nullptr; unsigned long long* d_excl = nullptr; int excl_W = 0;
-    long long* d_sforce = nullptr; long long* d_lj_sforce = nullptr;   // [R][3][Npad] / [R][3][NLpad] forces in sorted slot space
-    unsigned int* d_lj_sci_list = nullptr; int* d_lj_sci_count = nullptr; unsigned long long* d_lj_excl = nullptr; int lj_excl_W = 0;
+    dev_array<unsigned int> d_sci_list; dev_array<int> d_sci_count; dev_array<unsigned long long> d_excl; int excl_W = 0;
+    dev_array<long long> d_sforce; dev_array<long long> d_lj_sforce;   // [R][3][Npad] / [R][3][NLpad] forces in sorted slot space
+    dev_array<unsigned int> d_lj_sci_list; dev_array<int> d_lj_sci_count; dev_array<unsigned long long> d_lj_excl; int lj_excl_W = 0;
     int sort_R = 0; int evals_since_sort = 1 << 30; int resort_interval = 40; bool sorting = true;
     std::vector<float> rep_lam_host;      // what d_rep_lam holds
-    unsigned int* d_queue = nullptr;      // item queues of the resident-workgroup pair kernel: [0] Coulomb, [1] LJ, [2] workgroups done
+    dev_array<unsigned int> d_queue;      // item queues of the resident-workgroup pair kernel: [0] Coulomb, [1] LJ, [2] workgroups done
     // How many workgroups of the pair kernel stay resident next to the mesh kernels (0 = one per item) is a balance between
     // the two streams that depends on the system (24 x alanine dipeptide: 2 per CU is 4 % faster than one per item, 8 x
     // host-guest: 7 % slower), so it is measured: during the first long remd_run_steps the candidates take turns over
@@ -103,12 +103,13 @@ struct nb_tables {
     int nb_grid = 0;                      // current choice (workgroups; 0 = one per item)
     int sort_hbits = 0;                   // 2^sort_hbits cells per box edge along the Hilbert curve (0: not chosen yet)
     // Ewald direct-space force table of the force-only pair kernels (coulomb_table.h); energy evaluations: Abramowitz & Stegun erfc
-    float4* d_ctab = nullptr; bool use_table = false;
-    unsigned int* d_pair_done = nullptr; unsigned int pair_done_target = 0;      // remd_fold_args: the scatter launch's done counter
-    int* d_tile_of_rank = nullptr;        // [R][ntile] the main system's tiles by descending list length, refreshed with the molecule order
-    int* d_sort_scratch = nullptr; size_t sort_scratch_n = 0;                    // sort_groups_large_kernel (more than 8191 molecules)
+    dev_array<float4> d_ctab; bool use_table = false;
+    dev_array<unsigned int> d_pair_done; unsigned int pair_done_target = 0;      // remd_fold_args: the scatter launch's done counter
+    dev_array<int> d_tile_of_rank;        // [R][ntile] the main system's tiles by descending list length, refreshed with the molecule order
+    dev_array<int> d_sort_scratch;    // sort_groups_large_kernel (more than 8191 molecules), grown on demand
+    ~nb_tables() { for (auto& sg : tune_segs) { if (sg.a) hipEventDestroy(sg.a); if (sg.b) hipEventDestroy(sg.b); } }
 };
-static handle_table<nb_tables> g_nb;
+void remd_table_deleter::operator()(nb_tables* t) const { delete t; }
 
 // cross-stream dependencies without the command processor (see remd_ctx::d_sync): one lane polls a flag in device memory
 __global__ void remd_spin_wait_kernel(const unsigned int* flag, unsigned int seq, unsigned int* spin_out)
@@ -1318,35 +1319,7 @@ __global__ void assemble_ukl_kernel(int R, int K, const double* __restrict__ pot
 }
 
 // ---------------------------------------------------------------------------------------------------
-template <typename T> static void dfree(T*& p) { if (p) { hipFree(p); p = nullptr; } }
-template <typename T>
-static int upload(remd_ctx* h, T*& dptr, const std::vector<T>& host)
-{
-    dfree(dptr);
-    if (host.empty()) return 0;
-    REMD_CHECK(h, hipMalloc(&dptr, sizeof(T) * host.size()));
-    REMD_CHECK(h, hipMemcpy(dptr, host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice));
-    return 0;
-}
 
-void remd_free_nonbonded(remd_ctx* h)
-{
-    nb_tables* it = g_nb.find(h);
-    if (!it) return;
-    nb_tables& t = *it;
-    dfree(t.d_param); dfree(t.d_mask); dfree(t.d_exc_atoms); dfree(t.d_exc_params); dfree(t.d_excl_atoms); dfree(t.d_excl_qq);
-    dfree(t.d_exc_alch); dfree(t.d_excl_alch); dfree(t.d_probe);
-    dfree(t.d_rep_lam); dfree(t.d_state_lam); dfree(t.d_alch_ukl); dfree(t.d_own);
-    dfree(t.d_grp_first); dfree(t.d_grp_size); dfree(t.d_order); dfree(t.d_spos); dfree(t.d_sposi); dfree(t.d_lj_sposi); dfree(t.d_sparam); dfree(t.d_smask);
-    dfree(t.d_tile_c); dfree(t.d_tile_h); dfree(t.d_partial); dfree(t.d_cl_c); dfree(t.d_cl_h);
-    dfree(t.d_lj_ord); dfree(t.d_lj_mask); dfree(t.d_lj_order); dfree(t.d_lj_spos); dfree(t.d_lj_sparam); dfree(t.d_lj_smask);
-    dfree(t.d_lj_tile_c); dfree(t.d_lj_tile_h); dfree(t.d_lj_cl_c); dfree(t.d_lj_cl_h);
-    dfree(t.d_sci_list); dfree(t.d_sci_count); dfree(t.d_excl); dfree(t.d_lj_sci_list); dfree(t.d_lj_sci_count); dfree(t.d_lj_excl);
-    dfree(t.d_tile_of_rank);
-    dfree(t.d_sforce); dfree(t.d_lj_sforce); dfree(t.d_queue); dfree(t.d_ctab); dfree(t.d_pair_done); dfree(t.d_sort_scratch);
-    for (auto& sg : t.tune_segs) { if (sg.a) hipEventDestroy(sg.a); if (sg.b) hipEventDestroy(sg.b); }
-    g_nb.erase(h);
-}
 
 // long-range dispersion correction coefficient (E = coeff / V), OpenMM NonbondedForce convention:
 // averages over the N(N+1)/2 multiset of particle pairs (self pairs included), switching-region
@@ -1393,7 +1366,7 @@ static double dispersion_coefficient(int N, const std::vector<double>& sigma, co
 static int build_atom_terms(remd_ctx* h, int N, const std::vector<int>& ba, const std::vector<int>& aa, const std::vector<int>& ta,
                             const std::vector<int>& exc, int n_exc, const std::vector<int>& excl, int n_excl)
 {
-    if (h->d_aterm) { hipFree(h->d_aterm); h->d_aterm = nullptr; }
+    h->d_aterm.reset();
     h->n_aterm = 0;
     const size_t nterm[5] = { ba.size() / 2, aa.size() / 3, ta.size() / 4, (size_t)n_exc, (size_t)n_excl };
     const std::vector<int>* arr[5] = { &ba, &aa, &ta, &exc, &excl };
@@ -1412,14 +1385,14 @@ static int build_atom_terms(remd_ctx* h, int N, const std::vector<int>& ba, cons
             for (int s = 0; s < width[c]; ++s)
                 ent[cur[(*arr[c])[t * width[c] + s]]++] = ((unsigned int)c << 29) | ((unsigned int)s << 27) | (unsigned int)t;
     h->n_aterm = (int)ent.size();
-    return upload(h, h->d_aterm, ent);
+    return h->d_aterm.upload(h, ent);
 }
 
 int remd_build_nonbonded(remd_ctx* h, const remd_system_desc* d)
 {
-    remd_free_nonbonded(h);
-    remd_nocutoff_release(h);
-    remd_gbsa_release(h);
+    h->nb.reset();
+    h->nc.reset(); h->nocutoff = 0;
+    h->gb.reset(); h->gbsa = 0;
     // NoCutoff (vacuum systems): the direct sum of nocutoff.hip; everything else treats the handle as one without a cutoff-based nonbonded force
     h->nb_method = d->nb_method == REMD_NB_NOCUTOFF ? REMD_NB_NONE : d->nb_method;
     // bonded tables live in the context
@@ -1434,9 +1407,9 @@ int remd_build_nonbonded(remd_ctx* h, const remd_system_desc* d)
         std::vector<float> tp(3 * (size_t)d->n_torsions);
         for (size_t k = 0; k < tp.size(); ++k) tp[k] = (float)d->torsion_params[k];
         int rc;
-        if ((rc = upload(h, h->d_bond_atoms, ba)) || (rc = upload(h, h->d_bond_params, bp)) ||
-            (rc = upload(h, h->d_angle_atoms, aa)) || (rc = upload(h, h->d_angle_params, ap)) ||
-            (rc = upload(h, h->d_torsion_atoms, ta)) || (rc = upload(h, h->d_torsion_params, tp))) return rc;
+        if ((rc = h->d_bond_atoms.upload(h, ba)) || (rc = h->d_bond_params.upload(h, bp)) ||
+            (rc = h->d_angle_atoms.upload(h, aa)) || (rc = h->d_angle_params.upload(h, ap)) ||
+            (rc = h->d_torsion_atoms.upload(h, ta)) || (rc = h->d_torsion_params.upload(h, tp))) return rc;
         h->n_bonds = d->n_bonds; h->n_angles = d->n_angles; h->n_torsions = d->n_torsions;
         for (int k = 0; k < 2 * d->n_bonds; ++k) if (ba[k] < 0 || ba[k] >= d->n_atoms) return remd_fail(h, -3, "bond atom index out of range");
         for (int k = 0; k < 3 * d->n_angles; ++k) if (aa[k] < 0 || aa[k] >= d->n_atoms) return remd_fail(h, -3, "angle atom index out of range");
@@ -1455,7 +1428,7 @@ int remd_build_nonbonded(remd_ctx* h, const remd_system_desc* d)
     if (!d->charge || !d->sigma || !d->epsilon) return remd_fail(h, -1, "nonbonded parameter arrays missing");
     if (!(d->cutoff > 0)) return remd_fail(h, -1, "cutoff must be positive");
     const int N = d->n_atoms;
-    nb_tables& t = g_nb[h];
+    nb_tables& t = remd_table_of(h->nb);
     t.is_alch.assign(N, 0);
     for (int a = 0; a < d->n_alch; ++a) {
         if (d->alch_atoms[a] < 0 || d->alch_atoms[a] >= N) return remd_fail(h, -3, "alchemical atom index out of range");
@@ -1466,7 +1439,7 @@ int remd_build_nonbonded(remd_ctx* h, const remd_system_desc* d)
     h->sc_alpha = d->softcore_alpha; h->sc_a = d->softcore_a; h->sc_b = d->softcore_b; h->sc_c = d->softcore_c;
     {
         std::vector<int> al(d->alch_atoms, d->alch_atoms + d->n_alch);
-        int rc = upload(h, h->d_alch_atoms, al); if (rc) return rc;
+        int rc = h->d_alch_atoms.upload(h, al); if (rc) return rc;
     }
     bool any_charge = false;
     t.charge.assign(d->charge, d->charge + N);
@@ -1479,7 +1452,7 @@ int remd_build_nonbonded(remd_ctx* h, const remd_system_desc* d)
         prm[i] = make_float4((float)(d->charge[i] * sqk), (float)(0.5 * d->sigma[i]), (float)(2.0 * sqrt(d->epsilon[i])),
                              t.is_alch[i] ? (h->annihilate_sterics ? 2.f : 1.f) : 0.f);
     int rc;
-    if ((rc = upload(h, t.d_param, prm))) return rc;
+    if ((rc = t.d_param.upload(h, prm))) return rc;
     // exclusion window
     int maxd = 0;
     for (int e = 0; e < d->n_exceptions; ++e) {
@@ -1514,11 +1487,11 @@ int remd_build_nonbonded(remd_ctx* h, const remd_system_desc* d)
             excl_qq.push_back((float)(d->charge[i] * d->charge[j] * REMD_ONE_4PI_EPS0));
         }
     }
-    if ((rc = upload(h, t.d_mask, mk))) return rc;
+    if ((rc = t.d_mask.upload(h, mk))) return rc;
     t.n_exc = (int)exc_params.size() / 3;
-    if ((rc = upload(h, t.d_exc_atoms, exc_atoms)) || (rc = upload(h, t.d_exc_params, exc_params)) || (rc = upload(h, t.d_exc_alch, exc_alch))) return rc;
+    if ((rc = t.d_exc_atoms.upload(h, exc_atoms)) || (rc = t.d_exc_params.upload(h, exc_params)) || (rc = t.d_exc_alch.upload(h, exc_alch))) return rc;
     t.n_excl = (t.method == NB_EWALD) ? (int)excl_qq.size() : 0;
-    if ((rc = upload(h, t.d_excl_atoms, excl_atoms)) || (rc = upload(h, t.d_excl_qq, excl_qq)) || (rc = upload(h, t.d_excl_alch, excl_alch))) return rc;
+    if ((rc = t.d_excl_atoms.upload(h, excl_atoms)) || (rc = t.d_excl_qq.upload(h, excl_qq)) || (rc = t.d_excl_alch.upload(h, excl_alch))) return rc;
     {
         const std::vector<int> ba(d->bond_atoms, d->bond_atoms + 2 * (size_t)d->n_bonds), aa(d->angle_atoms, d->angle_atoms + 3 * (size_t)d->n_angles),
                                ta(d->torsion_atoms, d->torsion_atoms + 4 * (size_t)d->n_torsions);
@@ -1552,7 +1525,7 @@ int remd_build_nonbonded(remd_ctx* h, const remd_system_desc* d)
         const coulomb_table_host T = ctab_build(d->ewald_alpha, (double)p.rcc2);
         std::vector<float4> tab(T.n);
         for (int k = 0; k < T.n; ++k) tab[k] = make_float4(T.c[4 * k], T.c[4 * k + 1], T.c[4 * k + 2], T.c[4 * k + 3]);
-        if ((rc = upload(h, t.d_ctab, tab))) return rc;
+        if ((rc = t.d_ctab.upload(h, tab))) return rc;
         p.ctab_key0 = T.key0; p.ctab_n = T.n; p.ctab_umin = T.umin;
     }
     const int ntile = (N + 63) / 64;
@@ -1584,7 +1557,7 @@ int remd_build_nonbonded(remd_ctx* h, const remd_system_desc* d)
             i = end + 1;
         }
         t.n_groups = (int)first.size();
-        if ((rc = upload(h, t.d_grp_first, first)) || (rc = upload(h, t.d_grp_size, size))) return rc;
+        if ((rc = t.d_grp_first.upload(h, first)) || (rc = t.d_grp_size.upload(h, size))) return rc;
         t.sorting = true;
         t.clusters = !h->sw.nb_tiles;        // test hook: the 64-atom tile kernel a list overflow falls back to
         // 8 slices where the mesh stream runs beside the pair kernel (its launch may become a resident set pulling items: 105.9 vs
@@ -1627,7 +1600,7 @@ int remd_build_nonbonded(remd_ctx* h, const remd_system_desc* d)
                 const int a = ord[d->exception_atoms[2 * e]], b2 = ord[d->exception_atoms[2 * e + 1]];
                 if (a >= 0 && b2 >= 0) { setb(a, b2); setb(b2, a); }
             }
-            if ((rc = upload(h, t.d_lj_ord, ord)) || (rc = upload(h, t.d_lj_mask, lm))) return rc;
+            if ((rc = t.d_lj_ord.upload(h, ord)) || (rc = t.d_lj_mask.upload(h, lm))) return rc;
         }
     }
 
@@ -1657,7 +1630,7 @@ int remd_build_nonbonded(remd_ctx* h, const remd_system_desc* d)
 static int update_replica_lambdas(remd_ctx* h, nb_tables& t)
 {
     if (!t.has_alch) return 0;
-    if (t.rep_lam_R != h->R) { dfree(t.d_rep_lam); REMD_CHECK(h, hipMalloc(&t.d_rep_lam, sizeof(float) * 4 * h->R)); t.rep_lam_R = h->R; t.rep_lam_host.clear(); }
+    if (t.rep_lam_R != h->R) { t.d_rep_lam.reset(); REMD_TRY(t.d_rep_lam.alloc(h, 4 * h->R)); t.rep_lam_R = h->R; t.rep_lam_host.clear(); }
     std::vector<float> rl(4 * (size_t)h->R, 0.f);
     for (int r = 0; r < h->R; ++r) {
         const int64_t k = h->labels.empty() ? 0 : h->labels[h->r_begin + r];
@@ -1694,62 +1667,62 @@ static int ensure_sorted(remd_ctx* h, nb_tables& t)
     const int ntile = (h->N + 63) / 64;
     const bool cl = t.clusters && ntile * 8 < 65536;
     if (t.sort_R != h->R) {
-        dfree(t.d_order); dfree(t.d_spos); dfree(t.d_sparam); dfree(t.d_smask); dfree(t.d_tile_c); dfree(t.d_tile_h);
+        t.d_order.reset(); t.d_spos.reset(); t.d_sparam.reset(); t.d_smask.reset(); t.d_tile_c.reset(); t.d_tile_h.reset();
         const size_t n = (size_t)h->R * h->Npad;
-        REMD_CHECK(h, hipMalloc(&t.d_order, sizeof(int) * n));
-        REMD_CHECK(h, hipMalloc(&t.d_spos, sizeof(float4) * n));
-        dfree(t.d_sposi);
-        REMD_CHECK(h, hipMalloc(&t.d_sposi, sizeof(float4) * n));
-        REMD_CHECK(h, hipMalloc(&t.d_sparam, sizeof(float4) * n));
-        REMD_CHECK(h, hipMalloc(&t.d_smask, sizeof(unsigned long long) * n * t.p.excl_words));
-        REMD_CHECK(h, hipMalloc(&t.d_tile_c, sizeof(float4) * (size_t)h->R * ntile));
-        REMD_CHECK(h, hipMalloc(&t.d_tile_h, sizeof(float4) * (size_t)h->R * ntile));
-        dfree(t.d_pair_done);
-        REMD_CHECK(h, hipMalloc(&t.d_pair_done, sizeof(unsigned int) * 16 * h->R));       // one arrival counter per replica, 64 bytes apart
+        REMD_TRY(t.d_order.alloc(h, n));
+        REMD_TRY(t.d_spos.alloc(h, n));
+        t.d_sposi.reset();
+        REMD_TRY(t.d_sposi.alloc(h, n));
+        REMD_TRY(t.d_sparam.alloc(h, n));
+        REMD_TRY(t.d_smask.alloc(h, n * t.p.excl_words));
+        REMD_TRY(t.d_tile_c.alloc(h, (size_t)h->R * ntile));
+        REMD_TRY(t.d_tile_h.alloc(h, (size_t)h->R * ntile));
+        t.d_pair_done.reset();
+        REMD_TRY(t.d_pair_done.alloc(h, 16 * h->R));       // one arrival counter per replica, 64 bytes apart
         REMD_CHECK(h, hipMemsetAsync(t.d_pair_done, 0, sizeof(unsigned int) * 16 * h->R, h->stream));
         t.pair_done_target = 0;
-        dfree(t.d_cl_c); dfree(t.d_cl_h);
-        dfree(t.d_sci_list); dfree(t.d_sci_count); dfree(t.d_excl); dfree(t.d_sforce); dfree(t.d_lj_sforce);
-        dfree(t.d_lj_sci_list); dfree(t.d_lj_sci_count); dfree(t.d_lj_excl);
+        t.d_cl_c.reset(); t.d_cl_h.reset();
+        t.d_sci_list.reset(); t.d_sci_count.reset(); t.d_excl.reset(); t.d_sforce.reset(); t.d_lj_sforce.reset();
+        t.d_lj_sci_list.reset(); t.d_lj_sci_count.reset(); t.d_lj_excl.reset();
         const int ncl = ntile * 8;
         t.cl_cap = std::min(ncl, 4096);     // whole row for systems up to 32k atoms: a cluster that straddles a large molecule can neighbour half the box
         if (cl) {
-            REMD_CHECK(h, hipMalloc(&t.d_cl_c, sizeof(float4) * (size_t)h->R * ncl));
-            REMD_CHECK(h, hipMalloc(&t.d_cl_h, sizeof(float4) * (size_t)h->R * ncl));
+            REMD_TRY(t.d_cl_c.alloc(h, (size_t)h->R * ncl));
+            REMD_TRY(t.d_cl_h.alloc(h, (size_t)h->R * ncl));
             t.excl_W = 4 * t.p.excl_words + 1;
-            REMD_CHECK(h, hipMalloc(&t.d_sci_list, sizeof(unsigned int) * (size_t)h->R * ntile * t.cl_cap));
-            REMD_CHECK(h, hipMalloc(&t.d_sci_count, sizeof(int) * (size_t)h->R * ntile));
-            dfree(t.d_tile_of_rank);
-            REMD_CHECK(h, hipMalloc(&t.d_tile_of_rank, sizeof(int) * (size_t)h->R * ntile));
-            REMD_CHECK(h, hipMalloc(&t.d_excl, sizeof(unsigned long long) * (size_t)h->R * ncl * t.excl_W));
-            REMD_CHECK(h, hipMalloc(&t.d_sforce, sizeof(long long) * n * 3));
+            REMD_TRY(t.d_sci_list.alloc(h, (size_t)h->R * ntile * t.cl_cap));
+            REMD_TRY(t.d_sci_count.alloc(h, (size_t)h->R * ntile));
+            t.d_tile_of_rank.reset();
+            REMD_TRY(t.d_tile_of_rank.alloc(h, (size_t)h->R * ntile));
+            REMD_TRY(t.d_excl.alloc(h, (size_t)h->R * ncl * t.excl_W));
+            REMD_TRY(t.d_sforce.alloc(h, n * 3));
             REMD_CHECK(h, hipMemsetAsync(t.d_sforce, 0, sizeof(long long) * n * 3, h->stream));
             if (!t.d_queue) {
-                REMD_CHECK(h, hipMalloc(&t.d_queue, 4 * sizeof(unsigned int)));
+                REMD_TRY(t.d_queue.alloc(h, 4));
                 REMD_CHECK(h, hipMemsetAsync(t.d_queue, 0, 4 * sizeof(unsigned int), h->stream));
             }
         }
         if (cl && t.lj_split) {
-            dfree(t.d_lj_order); dfree(t.d_lj_spos); dfree(t.d_lj_sparam); dfree(t.d_lj_smask); dfree(t.d_lj_tile_c); dfree(t.d_lj_tile_h);
-            dfree(t.d_lj_cl_c); dfree(t.d_lj_cl_h);
+            t.d_lj_order.reset(); t.d_lj_spos.reset(); t.d_lj_sparam.reset(); t.d_lj_smask.reset(); t.d_lj_tile_c.reset(); t.d_lj_tile_h.reset();
+            t.d_lj_cl_c.reset(); t.d_lj_cl_h.reset();
             const size_t nl = (size_t)h->R * t.NLpad;
             const int ncl_lj = t.NLpad / 8;
             t.lj_cap = std::min(ncl_lj, 4096);
-            REMD_CHECK(h, hipMalloc(&t.d_lj_order, sizeof(int) * nl));
-            REMD_CHECK(h, hipMalloc(&t.d_lj_spos, sizeof(float4) * nl));
-            dfree(t.d_lj_sposi);
-            REMD_CHECK(h, hipMalloc(&t.d_lj_sposi, sizeof(float4) * nl));
-            REMD_CHECK(h, hipMalloc(&t.d_lj_sparam, sizeof(float4) * nl));
-            REMD_CHECK(h, hipMalloc(&t.d_lj_smask, sizeof(unsigned long long) * nl * t.lj_words));
-            REMD_CHECK(h, hipMalloc(&t.d_lj_tile_c, sizeof(float4) * (size_t)h->R * (t.NLpad / 64)));
-            REMD_CHECK(h, hipMalloc(&t.d_lj_tile_h, sizeof(float4) * (size_t)h->R * (t.NLpad / 64)));
-            REMD_CHECK(h, hipMalloc(&t.d_lj_cl_c, sizeof(float4) * (size_t)h->R * ncl_lj));
-            REMD_CHECK(h, hipMalloc(&t.d_lj_cl_h, sizeof(float4) * (size_t)h->R * ncl_lj));
+            REMD_TRY(t.d_lj_order.alloc(h, nl));
+            REMD_TRY(t.d_lj_spos.alloc(h, nl));
+            t.d_lj_sposi.reset();
+            REMD_TRY(t.d_lj_sposi.alloc(h, nl));
+            REMD_TRY(t.d_lj_sparam.alloc(h, nl));
+            REMD_TRY(t.d_lj_smask.alloc(h, nl * t.lj_words));
+            REMD_TRY(t.d_lj_tile_c.alloc(h, (size_t)h->R * (t.NLpad / 64)));
+            REMD_TRY(t.d_lj_tile_h.alloc(h, (size_t)h->R * (t.NLpad / 64)));
+            REMD_TRY(t.d_lj_cl_c.alloc(h, (size_t)h->R * ncl_lj));
+            REMD_TRY(t.d_lj_cl_h.alloc(h, (size_t)h->R * ncl_lj));
             t.lj_excl_W = 4 * t.lj_words + 1;
-            REMD_CHECK(h, hipMalloc(&t.d_lj_sci_list, sizeof(unsigned int) * (size_t)h->R * (ncl_lj / 8) * t.lj_cap));
-            REMD_CHECK(h, hipMalloc(&t.d_lj_sci_count, sizeof(int) * (size_t)h->R * (ncl_lj / 8)));
-            REMD_CHECK(h, hipMalloc(&t.d_lj_excl, sizeof(unsigned long long) * (size_t)h->R * ncl_lj * t.lj_excl_W));
-            REMD_CHECK(h, hipMalloc(&t.d_lj_sforce, sizeof(long long) * nl * 3));
+            REMD_TRY(t.d_lj_sci_list.alloc(h, (size_t)h->R * (ncl_lj / 8) * t.lj_cap));
+            REMD_TRY(t.d_lj_sci_count.alloc(h, (size_t)h->R * (ncl_lj / 8)));
+            REMD_TRY(t.d_lj_excl.alloc(h, (size_t)h->R * ncl_lj * t.lj_excl_W));
+            REMD_TRY(t.d_lj_sforce.alloc(h, nl * 3));
             REMD_CHECK(h, hipMemsetAsync(t.d_lj_sforce, 0, sizeof(long long) * nl * 3, h->stream));
         }
         t.sort_R = h->R; t.evals_since_sort = 1 << 30;
@@ -1772,11 +1745,7 @@ static int ensure_sorted(remd_ctx* h, nb_tables& t)
                                t.d_grp_size, h->d_pos, h->d_box, t.d_order, t.sort_hbits);
         } else {
             const size_t need = (size_t)h->R * 5 * t.n_groups;
-            if (t.sort_scratch_n < need) {
-                dfree(t.d_sort_scratch);
-                REMD_CHECK(h, hipMalloc(&t.d_sort_scratch, sizeof(int) * need));
-                t.sort_scratch_n = need;
-            }
+            REMD_TRY(t.d_sort_scratch.grow(h, need));
             hipLaunchKernelGGL(sort_groups_large_kernel, dim3(h->R), dim3(1024), 0, h->stream, t.n_groups, h->N, h->Npad, t.d_grp_first,
                                t.d_grp_size, h->d_pos, h->d_box, t.d_order, t.d_sort_scratch, t.sort_hbits);
         }
@@ -1843,7 +1812,7 @@ static int ensure_sorted(remd_ctx* h, nb_tables& t)
 // Ewald / reaction-field methods, the LJ-only sub-system in the same launch), or the all-tile kernel when the system has no
 // sortable groups or a list outgrew its capacity
 template <int METHOD, bool ENERGY>
-static void launch_nb(remd_ctx* h, nb_tables& t)
+static int launch_nb(remd_ctx* h, nb_tables& t)
 {
     const int ntile = (h->N + 63) / 64;
     if (t.sorting && t.clusters && t.d_order && t.d_sci_list && t.n_groups > 0 && ntile * 8 < 65536) {
@@ -1889,7 +1858,7 @@ static void launch_nb(remd_ctx* h, nb_tables& t)
             }
             hipLaunchKernelGGL(scatter_sorted_forces_kernel, sgrid, dim3(256), 0, h->stream, h->Npad,
                                t.d_order, t.d_sforce, t.NLpad, t.d_lj_order, t.d_lj_sforce, h->d_force, h->Npad, fold ? t.d_pair_done : (unsigned int*)nullptr);
-            return;
+            return 0;
         }
         const bool tab1 = t.use_table && !ENERGY && SCI_EWALD(METHOD);
         const size_t tab1_lds = tab1 ? sizeof(float4) * (size_t)t.p.ctab_n : 0;
@@ -1900,11 +1869,11 @@ static void launch_nb(remd_ctx* h, nb_tables& t)
 #undef LAUNCH_SCI
         hipLaunchKernelGGL(scatter_sorted_forces_kernel, dim3((h->Npad + 255) / 256, h->R), dim3(256), 0, h->stream, h->Npad, t.d_order,
                            t.d_sforce, 0, (const int*)nullptr, (long long*)nullptr, h->d_force, h->Npad);
-        return;
+        return 0;
     }
     dim3 grid((ntile + NB_WAVES - 1) / NB_WAVES, t.p.n_jsplit, h->R);
     const size_t need = (size_t)h->R * t.p.n_jsplit * h->Npad;
-    if (t.partial_n < need) { dfree(t.d_partial); if (hipMalloc(&t.d_partial, sizeof(float4) * need) != hipSuccess) return; t.partial_n = need; }
+    REMD_TRY(t.d_partial.grow(h, need));
     const bool sorted = t.sorting && t.d_order && t.n_groups > 0;
     const float4* P = sorted ? t.d_spos : h->d_pos;
     const float4* prm = sorted ? t.d_sparam : t.d_param;
@@ -1918,12 +1887,13 @@ static void launch_nb(remd_ctx* h, nb_tables& t)
                            prm, mk, ord, t.d_tile_c, t.d_tile_h, h->d_box, (const float*)nullptr, t.d_partial, h->d_epart, h->n_epart, ntile);
     hipLaunchKernelGGL(nb_reduce_kernel, dim3((h->N + 255) / 256, h->R), dim3(256), 0, h->stream, h->N, h->Npad, t.p.n_jsplit,
                        t.d_partial, h->d_force);
+    return 0;
 }
 
 // after a device-side fault: partial sums a discarded evaluation left in the sorted accumulators must not reach the next one
 void remd_nb_reset_accumulators(remd_ctx* h)
 {
-    nb_tables* t = g_nb.find(h);
+    nb_tables* t = h->nb.get();
     h->fold_pending = false;
     if (!t || h->R <= 0) return;
     if (t->d_sforce) hipMemsetAsync(t->d_sforce, 0, sizeof(long long) * 3 * (size_t)h->R * h->Npad, h->stream);
@@ -1932,7 +1902,7 @@ void remd_nb_reset_accumulators(remd_ctx* h)
 
 int remd_nb_molecules(remd_ctx* h, const int** first, const int** size)
 {
-    nb_tables* it = g_nb.find(h);
+    nb_tables* it = h->nb.get();
     if (!it || it->n_groups <= 0) return 0;
     *first = it->d_grp_first; *size = it->d_grp_size;
     return it->n_groups;
@@ -1944,7 +1914,7 @@ const float* remd_nb_rep_lam(remd_ctx* h)
         const float4* prm; const float* le;
         if (remd_regions_pme_tables(h, &prm, &le)) return le;
     }
-    nb_tables* it = g_nb.find(h);
+    nb_tables* it = h->nb.get();
     return (it && it->has_alch) ? it->d_rep_lam : nullptr;
 }
 const float4* remd_nb_param(remd_ctx* h)
@@ -1953,7 +1923,7 @@ const float4* remd_nb_param(remd_ctx* h)
         const float4* prm; const float* le;
         if (remd_regions_pme_tables(h, &prm, &le)) return prm;
     }
-    return g_nb[h].d_param;
+    return remd_table_of(h->nb).d_param;
 }
 
 int remd_nb_required_epart(remd_ctx* h)
@@ -1974,7 +1944,7 @@ static const tune_cand g_tune_cands[TUNE_NC] = {{0, 1}, {0, 0}, {768, 0}, {640, 
 // called at the top of every eagerly launched MD step of remd_run_steps
 void remd_nb_tune_step(remd_ctx* h, int steps_left_in_call)
 {
-    nb_tables* tp = g_nb.find(h);
+    nb_tables* tp = h->nb.get();
     if (!tp || h->nb_method == REMD_NB_NONE) return;
     nb_tables& t = *tp;
     if (h->sw.nb_persist_grid >= 0 || t.tune_state != 0 || !h->pme_concurrent || h->profiling == 2) return;
@@ -1998,7 +1968,7 @@ void remd_nb_tune_step(remd_ctx* h, int steps_left_in_call)
 // after the stream has been synchronised: pick the fastest candidate
 void remd_nb_tune_resolve(remd_ctx* h)
 {
-    nb_tables* tp = g_nb.find(h);
+    nb_tables* tp = h->nb.get();
     if (!tp || tp->tune_state != 1) return;
     nb_tables& t = *tp;
     double ms[TUNE_NC] = {0};
@@ -2027,7 +1997,7 @@ void remd_nb_tune_resolve(remd_ctx* h)
 // evaluations being counted)
 void remd_nb_invalidate_sort(remd_ctx* h)
 {
-    nb_tables* t = g_nb.find(h);
+    nb_tables* t = h->nb.get();
     if (t) t->evals_since_sort = 1 << 30;
 }
 // what the resident small-system kernel (integrate.hip) needs from the nonbonded tables: pair constants, per-atom parameters in
@@ -2037,7 +2007,7 @@ int remd_nb_resident_info(remd_ctx* h, int* ok, int* method, int* has_alch, nb_p
     *ok = 0; *method = -1; *has_alch = 0; *param = nullptr; *rep_lam = nullptr;
     if (h->nb_method == REMD_NB_NONE) { *ok = h->nocutoff ? 0 : 1; return 0; }      // e.g. the harmonic oscillator: external force only (a NoCutoff system: forces.hip + nocutoff.hip)
     if (h->n_regions > 0) return 0;                                       // general alchemical regions: forces.hip + alch_regions.hip
-    nb_tables* t = g_nb.find(h);
+    nb_tables* t = h->nb.get();
     if (!t || t->method != NB_LJ_ONLY || t->n_exc != 0 || t->n_excl != 0 || h->n_exceptions != 0) return 0;
     int rc = update_replica_lambdas(h, *t);
     if (rc) return rc;
@@ -2087,7 +2057,7 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask)
         T.bond_atoms = h->d_bond_atoms; T.bond_params = h->d_bond_params;
         T.angle_atoms = h->d_angle_atoms; T.angle_params = h->d_angle_params;
         T.torsion_atoms = h->d_torsion_atoms; T.torsion_params = h->d_torsion_params;
-        nb_tables* it = g_nb.find(h);
+        nb_tables* it = h->nb.get();
         if (it && h->nb_method != REMD_NB_NONE && do_nb) {
             nb_tables& t = *it;
             T.n_exc = t.n_exc; T.exc_atoms = t.d_exc_atoms; T.exc_params = t.d_exc_params;
@@ -2103,7 +2073,7 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask)
     };
     bool listed_rode = false;
     if (h->nb_method != REMD_NB_NONE) {      // per-replica lambdas must be current before ANY kernel reads them
-        nb_tables& t0 = g_nb[h];
+        nb_tables& t0 = remd_table_of(h->nb);
         int rc0 = update_replica_lambdas(h, t0);
         if (rc0) return rc0;
         if (t0.method == NB_EWALD && h->sw.overlap && h->stream2 && do_nb && do_recip) {
@@ -2138,7 +2108,7 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask)
         }
     }
     h->pme_concurrent = forked;
-    if (!forked) { h->mesh_prio_hi = true; if (h->nb_method != REMD_NB_NONE) g_nb[h].p.prio = 0; }
+    if (!forked) { h->mesh_prio_hi = true; if (h->nb_method != REMD_NB_NONE) remd_table_of(h->nb).p.prio = 0; }
     const bool merged = !with_energy;      // force-only evaluations: every listed term in one launch
     if (!merged && h->n_bonds > 0) {
         remd_prof_scope ps(h, "bonded");
@@ -2164,7 +2134,7 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask)
     // kernel on the direct-space stream, as in round 3.
     // (only in the mode in which the direct-space stream is the critical one, chosen by the tuner together with the wave priority:
     // on a system whose mesh chain is the longer branch the extra work on the main stream costs what it saves here)
-    const bool listed_main = h->sw.listed_main && forked && !with_energy && !h->sync_events && h->nb_method != REMD_NB_NONE && g_nb[h].p.prio != 0;
+    const bool listed_main = h->sw.listed_main && forked && !with_energy && !h->sync_events && h->nb_method != REMD_NB_NONE && remd_table_of(h->nb).p.prio != 0;
     // the restraints (restraints.hip) go with the listed terms: the launch of a force-only evaluation on the stream the listed terms take
     // (the main stream when those rode in the spreading launch), behind the torsions of an energy evaluation
     int rc_rst = 0;
@@ -2182,7 +2152,7 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask)
     if (h->nb_method == REMD_NB_NONE) {
         if (merged) launch_listed(h->stream);
     } else {
-        nb_tables& t = g_nb[h];
+        nb_tables& t = remd_table_of(h->nb);
         int rc = do_nb ? ensure_sorted(h, t) : 0;
         if (rc) return rc;
         // (after the swap h->stream2 is the main stream: the listed terms queue up behind the mesh launches already enqueued there)
@@ -2196,14 +2166,15 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask)
         if (do_nb) {
             remd_prof_scope ps(h, "nonbonded");
             if (with_energy) {
-                if (t.method == NB_LJ_ONLY) launch_nb<NB_LJ_ONLY, true>(h, t);
-                else if (t.method == NB_RF) launch_nb<NB_RF, true>(h, t);
-                else launch_nb<NB_EWALD, true>(h, t);
+                if (t.method == NB_LJ_ONLY) rc = launch_nb<NB_LJ_ONLY, true>(h, t);
+                else if (t.method == NB_RF) rc = launch_nb<NB_RF, true>(h, t);
+                else rc = launch_nb<NB_EWALD, true>(h, t);
             } else {
-                if (t.method == NB_LJ_ONLY) launch_nb<NB_LJ_ONLY, false>(h, t);
-                else if (t.method == NB_RF) launch_nb<NB_RF, false>(h, t);
-                else launch_nb<NB_EWALD, false>(h, t);
+                if (t.method == NB_LJ_ONLY) rc = launch_nb<NB_LJ_ONLY, false>(h, t);
+                else if (t.method == NB_RF) rc = launch_nb<NB_RF, false>(h, t);
+                else rc = launch_nb<NB_EWALD, false>(h, t);
             }
+            if (rc) return rc;
         }
         h->fold_pending = h->fold_pending && h->fold.done != nullptr;
         if (merged && !listed_main) launch_listed(h->stream);
@@ -2318,16 +2289,16 @@ static int assemble_ukl_rows(remd_ctx* h, double* d_rows)
 {
     const int n = h->R * h->K;
     const double* alch = nullptr;
-    nb_tables* it = g_nb.find(h);
+    nb_tables* it = h->nb.get();
     bool poly = false;
     const int* d_own_states = nullptr;
     if (h->n_regions > 0 && (h->nb_method != REMD_NB_NONE || h->nocutoff)) {
         // general alchemical regions: the custom forces at every state's lambdas (d_potential holds them at the replicas' own)
-        nb_tables& t = g_nb[h];
+        nb_tables& t = remd_table_of(h->nb);
         it = &t;
         if (t.alch_R != h->R || t.alch_K != h->K) {
-            dfree(t.d_alch_ukl); dfree(t.d_state_lam); dfree(t.d_own);
-            REMD_CHECK(h, hipMalloc(&t.d_alch_ukl, sizeof(double) * (size_t)n));
+            t.d_alch_ukl.reset(); t.d_state_lam.reset(); t.d_own.reset();
+            REMD_TRY(t.d_alch_ukl.alloc(h, (size_t)n));
             t.alch_R = h->R; t.alch_K = h->K;
         }
         int rc = remd_regions_ukl(h, t.d_alch_ukl, &d_own_states);
@@ -2338,7 +2309,7 @@ static int assemble_ukl_rows(remd_ctx* h, double* d_rows)
             int nreg = 0; const float* d_state_le = nullptr;
             if ((rc = remd_regions_le_override(h, nullptr, &nreg, &d_state_le))) return rc;
             const int P = (nreg + 1) * (nreg + 2) / 2;
-            if (t.probe_R != h->R * P) { dfree(t.d_probe); REMD_CHECK(h, hipMalloc(&t.d_probe, sizeof(double) * (size_t)P * h->R)); t.probe_R = h->R * P; }
+            if (t.probe_R != h->R * P) { t.d_probe.reset(); REMD_TRY(t.d_probe.alloc(h, (size_t)P * h->R)); t.probe_R = h->R * P; }
             std::vector<std::vector<float>> probes;
             probes.push_back(std::vector<float>(4, 0.f));
             for (int x = 0; x < nreg; ++x) for (float v : {0.5f, 1.f}) { std::vector<float> q(4, 0.f); q[x] = v; probes.push_back(q); }
@@ -2361,10 +2332,10 @@ static int assemble_ukl_rows(remd_ctx* h, double* d_rows)
     if (it && it->has_alch && h->nb_method != REMD_NB_NONE) {
         nb_tables& t = *it;
         if (t.alch_R != h->R || t.alch_K != h->K) {
-            dfree(t.d_alch_ukl); dfree(t.d_state_lam); dfree(t.d_own);
-            REMD_CHECK(h, hipMalloc(&t.d_alch_ukl, sizeof(double) * (size_t)n));
-            REMD_CHECK(h, hipMalloc(&t.d_state_lam, sizeof(double) * 2 * h->K));
-            REMD_CHECK(h, hipMalloc(&t.d_own, sizeof(int) * h->R));
+            t.d_alch_ukl.reset(); t.d_state_lam.reset(); t.d_own.reset();
+            REMD_TRY(t.d_alch_ukl.alloc(h, (size_t)n));
+            REMD_TRY(t.d_state_lam.alloc(h, 2 * h->K));
+            REMD_TRY(t.d_own.alloc(h, h->R));
             t.alch_R = h->R; t.alch_K = h->K;
         }
         std::vector<double> sl(2 * (size_t)h->K);
@@ -2389,7 +2360,7 @@ static int assemble_ukl_rows(remd_ctx* h, double* d_rows)
         for (int k = 0; k < h->K; ++k) lam_e_varies |= (h->lam_e[k] != h->lam_e[0]) || (h->lam_e[k] != 1.0);
         poly = lam_e_varies && (t.self_aa != 0.0);
         if (poly) {
-            if (t.probe_R != h->R) { dfree(t.d_probe); REMD_CHECK(h, hipMalloc(&t.d_probe, sizeof(double) * 3 * h->R)); t.probe_R = h->R; }
+            if (t.probe_R != h->R) { t.d_probe.reset(); REMD_TRY(t.d_probe.alloc(h, 3 * h->R)); t.probe_R = h->R; }
             const double probes[3] = { 0.0, 0.5, 1.0 };
             for (int q = 0; q < 3; ++q) {
                 t.lam_e_override = probes[q];

@@ -33,19 +33,18 @@ struct gbsa_tables {
     int N = 0, n_tile = 0;
     float tau = 0.f; int sasa = 1;
     bool any_alch = false;
-    float4* d_par = nullptr;               // [Npad] q, R, scale, alchemical
-    float2* d_born = nullptr;              // [R][Npad] B, dB/dI
-    float* d_c = nullptr;                  // [R][Npad] dE/dB dB/dI
-    float* d_lam = nullptr; std::vector<float> lam_host;      // [R] lambda_electrostatics of each replica's state
-    float* d_state_lam = nullptr; std::vector<float> state_lam_host;   // [K] of every state (u_kl columns)
+    dev_array<float4> d_par;               // [Npad] q, R, scale, alchemical
+    dev_array<float2> d_born;              // [R][Npad] B, dB/dI
+    dev_array<float> d_c;                  // [R][Npad] dE/dB dB/dI
+    dev_array<float> d_lam; std::vector<float> lam_host;      // [R] lambda_electrostatics of each replica's state
+    dev_array<float> d_state_lam; std::vector<float> state_lam_host;   // [K] of every state (u_kl columns)
     // a deep copy of the descriptor of remd_set_gbsa: the blocks of a phased propagation (api.hip) are set up from it
     remd_gbsa_desc store{}; std::vector<double> st_charge, st_radius, st_scale; std::vector<int32_t> st_alch;
-    double* d_epart = nullptr; double* d_col = nullptr; int buf_R = 0;
+    dev_array<double> d_epart; dev_array<double> d_col;     // [R][n_tile], [R]
     remd_gb_model_desc model{}; gb_consts k{}; int method = GB_CUT_NONE;     // remd_set_gb_model (OBC2, NoCutoff until then)
 };
-static handle_table<gbsa_tables> g_gb;
+void remd_table_deleter::operator()(gbsa_tables* t) const { delete t; }
 
-template <typename T> static void dfree(T*& p) { if (p) { hipFree(p); p = nullptr; } }
 
 // H(r; or1, sr2) of the computed value I and its derivative in r (alchemy.py:2195-2201; the step functions are constants under the derivative)
 __device__ __forceinline__ void gb_H(float r, float or1, float sr2, float& H, float& dH)
@@ -413,16 +412,6 @@ void gb_small_kernel(int N, int Npad, gb_consts kc, float tau, int sasa, const f
     }
 }
 
-void remd_gbsa_release(remd_ctx* h)
-{
-    gbsa_tables* t = g_gb.find(h);
-    if (t) {
-        dfree(t->d_par); dfree(t->d_born); dfree(t->d_c); dfree(t->d_lam); dfree(t->d_state_lam); dfree(t->d_epart); dfree(t->d_col);
-        g_gb.erase(h);
-    }
-    h->gbsa = 0;
-}
-
 // OBC2 without a cutoff: the model remd_set_gbsa starts from (the constants of the factory's strings, alchemy.py:2192-2210)
 static remd_gb_model_desc gb_default_model()
 {
@@ -447,7 +436,7 @@ int remd_set_gbsa(remd_handle h, const remd_gbsa_desc* d)
     if (!h) return remd_fail(h, -1, "remd_set_gbsa: NULL handle");
     hipSetDevice(h->device);
     hipStreamSynchronize(h->stream);
-    remd_gbsa_release(h);
+    h->gb.reset(); h->gbsa = 0;
     h->config_version++;
     h->forces_valid = false;
     if (!d) return 0;
@@ -455,20 +444,21 @@ int remd_set_gbsa(remd_handle h, const remd_gbsa_desc* d)
     if (!h->has_system || !(h->nocutoff || h->nb_method != REMD_NB_NONE))
         return remd_fail(h, -3, "remd_set_gbsa: GBSA needs a system with a NoCutoff NonbondedForce (call remd_set_system first)");
     if (d->n_atoms != h->N || !d->charge || !d->radius || !d->scale || !(d->solute_dielectric > 0) || !(d->solvent_dielectric > 0)) return remd_fail(h, -1, "remd_set_gbsa: bad arguments");
-    gbsa_tables& t = g_gb[h];
+    remd_table<gbsa_tables> tab(new gbsa_tables());
+    gbsa_tables& t = *tab;
     t.N = h->N; t.n_tile = (h->N + 63) / 64;
     t.tau = (float)(1.0 / d->solute_dielectric - 1.0 / d->solvent_dielectric);
     t.sasa = d->surface_area ? 1 : 0;
     gb_take_model(t, gb_default_model());
     std::vector<float4> par(h->Npad, make_float4(0.f, 1.f, 0.f, 0.f));
     for (int i = 0; i < h->N; ++i) {
-        if (!(d->radius[i] > 0.009)) { remd_gbsa_release(h); return remd_fail(h, -1, "remd_set_gbsa: radii must exceed the offset 0.009 nm"); }
+        if (!(d->radius[i] > 0.009)) return remd_fail(h, -1, "remd_set_gbsa: radii must exceed the offset 0.009 nm");
         const bool a = d->alchemical && d->alchemical[i];
         t.any_alch |= a;
         par[i] = make_float4((float)d->charge[i], (float)d->radius[i], (float)d->scale[i], a ? 1.f : 0.f);
     }
-    REMD_CHECK(h, hipMalloc(&t.d_par, sizeof(float4) * par.size()));
-    REMD_CHECK(h, hipMemcpy(t.d_par, par.data(), sizeof(float4) * par.size(), hipMemcpyHostToDevice));
+    REMD_TRY(t.d_par.upload(h, par));
+    h->gb = std::move(tab);
     h->gbsa = 1;
     if (!h->parent) {
         t.store = *d;
@@ -482,7 +472,7 @@ int remd_set_gbsa(remd_handle h, const remd_gbsa_desc* d)
 int remd_set_gb_model(remd_handle h, const remd_gb_model_desc* m)
 {
     if (!h) return remd_fail(h, -1, "remd_set_gb_model: NULL handle");
-    gbsa_tables* tp = g_gb.find(h);
+    gbsa_tables* tp = h->gb.get();
     if (!tp || !h->gbsa) return remd_fail(h, -2, "remd_set_gb_model: no GBSA on this handle (call remd_set_gbsa first)");
     const remd_gb_model_desc mm = m ? *m : gb_default_model();
     if (!(mm.offset >= 0.0) || !std::isfinite(mm.alpha) || !std::isfinite(mm.beta) || !std::isfinite(mm.gamma) || !(mm.ke > 0.0) ||
@@ -507,7 +497,7 @@ int remd_set_gb_model(remd_handle h, const remd_gb_model_desc* m)
 // the implicit solvent of `parent` on one of its blocks (api.hip phase_children)
 int remd_gbsa_clone(remd_ctx* parent, remd_ctx* child)
 {
-    gbsa_tables* t = g_gb.find(parent);
+    const gbsa_tables* t = parent->gb.get();
     if (!t || !parent->gbsa) return 0;
     int rc = remd_set_gbsa(child, &t->store);
     if (!rc) rc = remd_set_gb_model(child, &t->model);
@@ -517,14 +507,13 @@ int remd_gbsa_clone(remd_ctx* parent, remd_ctx* child)
 
 static int gb_buffers(remd_ctx* h, gbsa_tables& t)
 {
-    if (t.buf_R == h->R && t.d_born) return 0;
-    dfree(t.d_born); dfree(t.d_c); dfree(t.d_lam); dfree(t.d_epart); dfree(t.d_col);
-    REMD_CHECK(h, hipMalloc(&t.d_born, sizeof(float2) * (size_t)h->R * h->Npad));
-    REMD_CHECK(h, hipMalloc(&t.d_c, sizeof(float) * (size_t)h->R * h->Npad));
-    REMD_CHECK(h, hipMalloc(&t.d_lam, sizeof(float) * h->R));
-    REMD_CHECK(h, hipMalloc(&t.d_epart, sizeof(double) * (size_t)h->R * t.n_tile));
-    REMD_CHECK(h, hipMalloc(&t.d_col, sizeof(double) * h->R));
-    t.buf_R = h->R; t.lam_host.clear();
+    if (t.d_col.size() == (size_t)h->R) return 0;
+    REMD_TRY(t.d_born.alloc(h, (size_t)h->R * h->Npad));
+    REMD_TRY(t.d_c.alloc(h, (size_t)h->R * h->Npad));
+    REMD_TRY(t.d_lam.alloc(h, h->R));
+    REMD_TRY(t.d_epart.alloc(h, (size_t)h->R * t.n_tile));
+    REMD_TRY(t.d_col.alloc(h, h->R));
+    t.lam_host.clear();
     return 0;
 }
 
@@ -583,7 +572,7 @@ static int gb_check_method(remd_ctx* h, const gbsa_tables& t)
 // cutoff pair kernels is touched
 int remd_gbsa_forces(remd_ctx* h, bool with_energy, int ep_slot)
 {
-    gbsa_tables* tp = g_gb.find(h);
+    gbsa_tables* tp = h->gb.get();
     if (!tp) return remd_fail(h, -2, "GBSA: no tables on this handle");
     gbsa_tables& t = *tp;
     int rc = gb_check_method(h, t);
@@ -612,7 +601,7 @@ int remd_gbsa_forces(remd_ctx* h, bool with_energy, int ep_slot)
 // u_kl: the GB energy of every replica at every state's lambda, ADDED to d_alch[r][k] (alchemical particles only: else it is the same in every column)
 int remd_gbsa_ukl(remd_ctx* h, double* d_alch)
 {
-    gbsa_tables* tp = g_gb.find(h);
+    gbsa_tables* tp = h->gb.get();
     if (!tp || !tp->any_alch) return 0;
     gbsa_tables& t = *tp;
     int rc = gb_check_method(h, t);
@@ -623,7 +612,7 @@ int remd_gbsa_ukl(remd_ctx* h, double* d_alch)
         std::vector<float> sl(h->K);
         for (int k = 0; k < h->K; ++k) sl[k] = gb_state_lambda(h, k);
         if (sl != t.state_lam_host) {
-            if ((int)t.state_lam_host.size() != h->K) { dfree(t.d_state_lam); REMD_CHECK(h, hipMalloc(&t.d_state_lam, sizeof(float) * h->K)); }
+            if ((int)t.state_lam_host.size() != h->K) REMD_TRY(t.d_state_lam.alloc(h, h->K));
             REMD_CHECK(h, hipMemcpyAsync(t.d_state_lam, sl.data(), sizeof(float) * h->K, hipMemcpyHostToDevice, h->stream));
             REMD_CHECK(h, hipStreamSynchronize(h->stream));
             t.state_lam_host = sl;

@@ -764,15 +764,15 @@ __global__ void check_finite_kernel(int N, int Npad, const float4* __restrict__ 
 // ---------------------------------------------------------------------------------------------
 struct unit_tables {
     int n_units = 0;
-    int4* d_atoms = nullptr; unsigned char* d_type = nullptr; float* d_dist = nullptr;
+    dev_array<int4> d_atoms; dev_array<unsigned char> d_type; dev_array<float> d_dist;
     settle_const sc{};
 };
-static handle_table<unit_tables> g_units;
+void remd_table_deleter::operator()(unit_tables* t) const { delete t; }
 
 int remd_build_constraints(remd_ctx* h, const remd_system_desc* d)
 {
-    unit_tables& ut = g_units[h];
-    if (ut.d_atoms) { hipFree(ut.d_atoms); hipFree(ut.d_type); hipFree(ut.d_dist); ut = unit_tables(); }
+    h->units.reset(new unit_tables());
+    unit_tables& ut = *h->units;
     const int N = d->n_atoms;
     std::vector<char> used(N, 0);
     std::vector<int4> atoms; std::vector<unsigned char> type; std::vector<float> dist;
@@ -811,12 +811,9 @@ int remd_build_constraints(remd_ctx* h, const remd_system_desc* d)
         }
     }
     ut.n_units = (int)atoms.size();
-    REMD_CHECK(h, hipMalloc(&ut.d_atoms, sizeof(int4) * ut.n_units));
-    REMD_CHECK(h, hipMalloc(&ut.d_type, ut.n_units));
-    REMD_CHECK(h, hipMalloc(&ut.d_dist, sizeof(float) * 3 * ut.n_units));
-    REMD_CHECK(h, hipMemcpy(ut.d_atoms, atoms.data(), sizeof(int4) * ut.n_units, hipMemcpyHostToDevice));
-    REMD_CHECK(h, hipMemcpy(ut.d_type, type.data(), ut.n_units, hipMemcpyHostToDevice));
-    REMD_CHECK(h, hipMemcpy(ut.d_dist, dist.data(), sizeof(float) * 3 * ut.n_units, hipMemcpyHostToDevice));
+    REMD_TRY(ut.d_atoms.upload(h, atoms));
+    REMD_TRY(ut.d_type.upload(h, type));
+    REMD_TRY(ut.d_dist.upload(h, dist));
     h->n_settle = d->n_settle; h->n_shake = d->n_shake;
     int n_con = 3 * d->n_settle;
     for (int s = 0; s < d->n_shake; ++s) for (int k = 1; k < 4; ++k) if (d->shake_atoms[4 * s + k] >= 0) n_con++;
@@ -831,14 +828,6 @@ int remd_build_constraints(remd_ctx* h, const remd_system_desc* d)
         ut.sc.rc = (float)rc; ut.sc.dOH = (float)d->settle_dOH; ut.sc.dHH = (float)d->settle_dHH;
     }
     return 0;
-}
-
-void remd_free_constraints(remd_ctx* h)
-{
-    unit_tables* it = g_units.find(h);
-    if (!it) return;
-    if (it->d_atoms) { hipFree(it->d_atoms); hipFree(it->d_type); hipFree(it->d_dist); }
-    g_units.erase(h);
 }
 
 int remd_parse_splitting(remd_ctx* h, const char* splitting, std::vector<char>& tokens, int& nV, int& nR, int& nO, int* nVg)
@@ -971,16 +960,13 @@ void metropolis_restore_kernel(int N, int Npad, const int* __restrict__ accept, 
 }
 int remd_work_buffers(remd_ctx* h)
 {
-    if (h->work_R == h->R && h->d_work) return 0;
-    if (h->d_work) { hipFree(h->d_work); hipFree(h->d_pe_prev); hipFree(h->d_xold); hipFree(h->d_vold); hipFree(h->d_accept); }
-    h->d_work = nullptr;
-    REMD_CHECK(h, hipMalloc(&h->d_work, sizeof(long long) * 4 * h->R));
-    REMD_CHECK(h, hipMalloc(&h->d_pe_prev, sizeof(double) * h->R));
-    REMD_CHECK(h, hipMalloc(&h->d_xold, sizeof(float4) * (size_t)h->R * h->Npad));
-    REMD_CHECK(h, hipMalloc(&h->d_vold, sizeof(float4) * (size_t)h->R * h->Npad));
-    REMD_CHECK(h, hipMalloc(&h->d_accept, sizeof(int) * h->R));
+    if (h->d_work.size() == 4 * (size_t)h->R) return 0;
+    REMD_TRY(h->d_work.alloc(h, 4 * (size_t)h->R));
+    REMD_TRY(h->d_pe_prev.alloc(h, h->R));
+    REMD_TRY(h->d_xold.alloc(h, (size_t)h->R * h->Npad));
+    REMD_TRY(h->d_vold.alloc(h, (size_t)h->R * h->Npad));
+    REMD_TRY(h->d_accept.alloc(h, h->R));
     REMD_CHECK(h, hipMemsetAsync(h->d_work, 0, sizeof(long long) * 4 * h->R, h->stream));
-    h->work_R = h->R;
     return 0;
 }
 
@@ -1503,7 +1489,7 @@ static int remd_run_steps_resident_mol(remd_ctx* h, const std::vector<char>& tok
 {
     if (!h->sw.resident || h->no_resident) return 0;
     if (!h->nocutoff || h->gbsa || h->n_regions > 0 || h->nb_method != REMD_NB_NONE || h->n_ext > 0 || h->n_restraints > 0) return 0;
-    const unit_tables& ut = g_units[h];
+    const unit_tables& ut = remd_table_of(h->units);
     if (h->N > RESIDENT_MOL_MAX_ATOMS || ut.n_units > RESIDENT_MOL_T || ut.n_units < 1) return 0;
     if (h->baro_frequency > 0 || h->profiling == 2 || (int)tokens.size() > MAX_TOK || n_steps < 1) return 0;
     if (h->measure_heat || h->measure_shadow) return 0;
@@ -1566,7 +1552,7 @@ struct step_runner {
     int begin(remd_ctx* h_, const std::vector<char>& tokens_, int nV, int nR, int nO, int64_t iteration, int64_t first_step_, int n_steps_)
     {
         h = h_; tokens = &tokens_; first_step = first_step_; n_steps = n_steps_;
-        ut = &g_units[h];
+        ut = &remd_table_of(h->units);
         if (ut->n_units == 0) return remd_fail(h, -3, "no system set");
         {
             const int rr = remd_run_steps_resident(h, tokens_, nV, nR, nO, iteration, first_step, n_steps);
@@ -1593,13 +1579,12 @@ struct step_runner {
                 base.hVg[g] = h->nVg[g] > 0 ? (float)(h->dt / h->nVg[g]) : 0.f;
                 for (int c = 0; c < 6; ++c) if (h->fgroup[c] == g) group_mask[g] |= 1u << c;
                 if (h->n_restraints > 0 && h->rst_group == g) group_mask[g] |= 1u << REMD_FG_RESTRAINT;     // (restraints.hip)
-                if (h->nVg[g] > 0 && (!h->d_force_g[g] || h->force_g_n != nf)) {
-                    if (h->d_force_g[g]) { REMD_CHECK(h, hipStreamSynchronize(h->stream)); hipFree(h->d_force_g[g]); h->d_force_g[g] = nullptr; }
-                    REMD_CHECK(h, hipMalloc(&h->d_force_g[g], sizeof(long long) * nf));
+                if (h->nVg[g] > 0 && h->d_force_g[g].size() != nf) {
+                    if (h->d_force_g[g]) REMD_CHECK(h, hipStreamSynchronize(h->stream));
+                    REMD_TRY(h->d_force_g[g].alloc(h, nf));
                 }
                 base.Fg[g] = h->d_force_g[g];
             }
-            h->force_g_n = nf;
             unsigned named = 0u;
             for (int g = 0; g < 4; ++g) if (h->nVg[g] > 0) named |= group_mask[g];
             for (int c = 0; c < 6; ++c)
@@ -1630,11 +1615,11 @@ struct step_runner {
         merge_cmm = h->sw.chain_merge && device_waits_ok && h->profiling != 2 && !h->lean_waits && !h->no_chain_barrier && !h->no_chain_merge;
         const long long sync_key = (long long)h->R * 1000003ll + ut->n_units;
         if (merge_cmm && (!h->d_chain_sync || h->chain_sync_key != sync_key)) {      // slots of THIS grid shape
-            if (h->d_chain_sync) { REMD_CHECK(h, hipStreamSynchronize(h->stream)); hipFree(h->d_chain_sync); h->d_chain_sync = nullptr; }
+            if (h->d_chain_sync) REMD_CHECK(h, hipStreamSynchronize(h->stream));
             h->chain_sync_key = sync_key;
-            const size_t slot_bytes = sizeof(unsigned long long) * 2 * (size_t)h->R * (size_t)((ut->n_units + 255) / 256) * 3;   // [2][R][workgroups][3]
-            REMD_CHECK(h, hipMalloc((void**)&h->d_chain_sync, slot_bytes));
-            REMD_CHECK(h, hipMemsetAsync(h->d_chain_sync, 0, slot_bytes, h->stream));
+            const size_t slots = 2 * (size_t)h->R * (size_t)((ut->n_units + 255) / 256) * 3;   // [2][R][workgroups][3]
+            REMD_TRY(h->d_chain_sync.alloc(h, slots));
+            REMD_CHECK(h, hipMemsetAsync(h->d_chain_sync, 0, sizeof(unsigned long long) * slots, h->stream));
             h->chain_sync_epoch = 0;
         }
         if (h->cmm_frequency > 0)
@@ -1722,13 +1707,12 @@ struct step_runner {
                 const int g = tok - '0';
                 const bool has_mesh = (group_mask[g] >> REMD_FG_RECIPROCAL) & 1u;
                 flush(false, has_mesh);
-                long long* all_forces = h->d_force;
-                h->d_force = h->d_force_g[g];
+                std::swap(h->d_force, h->d_force_g[g]);      // (the evaluation fills the group's array)
                 h->force_zeroed = false; zeroed_by_chain = false;
                 h->defer_join_ok = device_waits_ok && !h->lean_waits;
                 int rc = remd_compute_forces(h, false, group_mask[g]);
                 h->defer_join_ok = false;
-                h->d_force = all_forces;
+                std::swap(h->d_force, h->d_force_g[g]);
                 h->forces_valid = false; h->force_zeroed = false;      // (the all-forces accumulator was not touched)
                 if (rc) return rc;
                 group_valid[g] = true;
@@ -1767,7 +1751,7 @@ struct step_runner {
 // workgroups of one integrator-chain launch of this handle (one per 256 constraint units per replica)
 long long remd_chain_blocks(remd_ctx* h)
 {
-    const unit_tables* ut = g_units.find(h);
+    const unit_tables* ut = h->units.get();
     return ut ? (long long)((ut->n_units + 255) / 256) * h->R : 0;
 }
 
@@ -1808,7 +1792,7 @@ int remd_run_steps_many(remd_ctx** hs, int n, int64_t iteration, int64_t first_s
 
 int remd_assign_velocities(remd_ctx* h, int64_t iteration)
 {
-    const unit_tables& ut = g_units[h];
+    const unit_tables& ut = remd_table_of(h->units);
     remd_prof_scope ps(h, "assign_velocities");
     dim3 grid((ut.n_units + 255) / 256, h->R);
     hipLaunchKernelGGL(assign_velocities_kernel, grid, dim3(256), 0, h->stream, ut.n_units, ut.d_atoms, ut.d_type, ut.sc,
@@ -2038,18 +2022,17 @@ void fire_update_kernel(int n_units, const int4* __restrict__ unit_atoms, int Np
 
 int remd_minimize_impl(remd_ctx* h, double tolerance, int max_iterations, int32_t* converged_out, int32_t* n_iter_out)
 {
-    const unit_tables& ut = g_units[h];
+    const unit_tables& ut = remd_table_of(h->units);
     if (ut.n_units == 0) return remd_fail(h, -3, "no system set");
     const int R = h->R, Npad = h->Npad;
     const dim3 grid((ut.n_units + 255) / 256, R);
     const int nblk = (int)grid.x;
-    float4 *x0 = nullptr, *v0 = nullptr; long long* f0 = nullptr; double* partial = nullptr; fire_rep* st = nullptr;
-    REMD_CHECK(h, hipMalloc(&x0, sizeof(float4) * (size_t)R * Npad));
-    REMD_CHECK(h, hipMalloc(&v0, sizeof(float4) * (size_t)R * Npad));
-    REMD_CHECK(h, hipMalloc(&f0, sizeof(long long) * 3 * (size_t)R * Npad));
-    REMD_CHECK(h, hipMalloc(&partial, sizeof(double) * 3 * (size_t)R * nblk));
-    REMD_CHECK(h, hipMalloc(&st, sizeof(fire_rep) * 2 * (size_t)R));
-    auto cleanup = [&]() { hipFree(x0); hipFree(v0); hipFree(f0); hipFree(partial); hipFree(st); };
+    dev_array<float4> x0, v0; dev_array<long long> f0; dev_array<double> partial; dev_array<fire_rep> st;
+    REMD_TRY(x0.alloc(h, (size_t)R * Npad));
+    REMD_TRY(v0.alloc(h, (size_t)R * Npad));
+    REMD_TRY(f0.alloc(h, 3 * (size_t)R * Npad));
+    REMD_TRY(partial.alloc(h, 3 * (size_t)R * nblk));
+    REMD_TRY(st.alloc(h, 2 * (size_t)R));
     const float timestep = 0.001f;                               // 1 fs (integrators.py:2318)
     fire_consts c{};
     c.dt_max = 0.010f; c.f_inc = 1.1f; c.f_dec = 0.5f; c.alpha0 = 0.1f; c.f_alpha = 0.99f; c.n_min = 5;
@@ -2062,7 +2045,7 @@ int remd_minimize_impl(remd_ctx* h, double tolerance, int max_iterations, int32_
     const float tol = (float)fmax(h->constraint_tol, REMD_CONSTRAINT_TOL_FLOOR);
     int cur = 0, rc = 0, it = 0;
     h->forces_valid = false; h->force_zeroed = false;
-    if ((rc = remd_compute_forces(h, true))) { cleanup(); return rc; }
+    if ((rc = remd_compute_forces(h, true))) return rc;
     hipLaunchKernelGGL(fire_finish_kernel, grid, dim3(256), 0, h->stream, ut.n_units, ut.d_atoms, ut.d_type, ut.sc, tol, Npad, h->d_pos,
                        h->d_vel, h->d_force, h->d_invmass, st, 0, partial);
     hipLaunchKernelGGL(fire_update_kernel, grid, dim3(256), 0, h->stream, ut.n_units, ut.d_atoms, Npad, h->d_pos, h->d_vel, h->d_force,
@@ -2079,7 +2062,7 @@ int remd_minimize_impl(remd_ctx* h, double tolerance, int max_iterations, int32_
             hipLaunchKernelGGL(fire_move_kernel, grid, dim3(256), 0, h->stream, ut.n_units, ut.d_atoms, ut.d_type, ut.d_dist, ut.sc, tol,
                                Npad, h->d_pos, h->d_vel, h->d_force, x0, v0, f0, h->d_invmass, S);
             h->forces_valid = false; h->force_zeroed = false;
-            if ((rc = remd_compute_forces(h, true))) { cleanup(); return rc; }
+            if ((rc = remd_compute_forces(h, true))) return rc;
             hipLaunchKernelGGL(fire_finish_kernel, grid, dim3(256), 0, h->stream, ut.n_units, ut.d_atoms, ut.d_type, ut.sc, tol, Npad,
                                h->d_pos, h->d_vel, h->d_force, h->d_invmass, S, 1, partial);
             hipLaunchKernelGGL(fire_update_kernel, grid, dim3(256), 0, h->stream, ut.n_units, ut.d_atoms, Npad, h->d_pos, h->d_vel,
@@ -2087,7 +2070,7 @@ int remd_minimize_impl(remd_ctx* h, double tolerance, int max_iterations, int32_
             cur = 1 - cur;
         }
         hipMemcpyAsync(host.data(), st + (size_t)cur * R, sizeof(fire_rep) * R, hipMemcpyDeviceToHost, h->stream);
-        if (hipStreamSynchronize(h->stream) != hipSuccess) { cleanup(); return remd_fail(h, -2, "minimize: device error"); }
+        if (hipStreamSynchronize(h->stream) != hipSuccess) return remd_fail(h, -2, "minimize: device error");
         all_done = true;
         for (int r = 0; r < R; ++r) all_done = all_done && host[r].converged;
         if (max_iterations > 0) all_done = false;               // a fixed number of steps was asked for
@@ -2097,7 +2080,6 @@ int remd_minimize_impl(remd_ctx* h, double tolerance, int max_iterations, int32_
     if (converged_out) for (int r = 0; r < R; ++r) converged_out[r] = host[r].converged;
     if (n_iter_out) *n_iter_out = it;
     h->forces_valid = false; h->force_zeroed = false;
-    cleanup();
     REMD_CHECK(h, hipGetLastError());
     return 0;
 }

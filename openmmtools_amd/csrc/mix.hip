@@ -586,20 +586,15 @@ void mix_stats_from_log_kernel(int64_t n_attempts, const unsigned int* __restric
 
 // buffers of the hoisted swap-all path, per handle (grow-only)
 struct mix_pre_buffers {
-    uint4* rec = nullptr; size_t rec_n = 0;
-    unsigned* piece = nullptr; unsigned* npiece = nullptr; size_t win_n = 0;
-    unsigned char* cnt = nullptr; size_t cnt_n = 0;
-    unsigned* err = nullptr;
-    ~mix_pre_buffers() { hipFree(rec); hipFree(piece); hipFree(npiece); hipFree(cnt); hipFree(err); }
+    dev_array<uint4> rec; dev_array<unsigned> piece, npiece; dev_array<unsigned char> cnt; dev_array<unsigned> err;
 };
-static handle_table<mix_pre_buffers> g_mix_pre;
-void remd_mix_release(remd_ctx* h) { g_mix_pre.erase(h); }
+void remd_table_deleter::operator()(mix_pre_buffers* b) const { delete b; }
 // the overflow flag of the hoisted swap-all path launched last (device pointer; NULL: that path did not run): api.hip reads it with
 // the results, at the call's one synchronisation, and repeats the call on the one-kernel path when it is raised
 const unsigned* remd_mix_pending_flag(remd_ctx* h)
 {
-    mix_pre_buffers* B = g_mix_pre.find(h);
-    return (B && h->mix_pre_launched) ? B->err : nullptr;
+    const mix_pre_buffers* B = h->mix_pre.get();
+    return (B && h->mix_pre_launched) ? B->err.get() : nullptr;
 }
 
 int remd_mix_launch(remd_ctx* h, int scheme, int64_t iteration, int R, int K, int ld, const double* d_ukl,
@@ -648,21 +643,13 @@ int remd_mix_launch(remd_ctx* h, int scheme, int64_t iteration, int R, int K, in
             const int W = 64 * waves;
             const int64_t n_win = (n_attempts + W - 1) / W;
             const int Rp4 = (R + 3) & ~3;
-            mix_pre_buffers& B = g_mix_pre[h];
-            if (B.rec_n < (size_t)n_win * W) { hipFree(B.rec); B.rec = nullptr; REMD_CHECK(h, hipMalloc(&B.rec, sizeof(uint4) * (size_t)n_win * W)); B.rec_n = (size_t)n_win * W; }
-            if (B.win_n < (size_t)n_win) {
-                hipFree(B.piece); hipFree(B.npiece); B.piece = B.npiece = nullptr;
-                REMD_CHECK(h, hipMalloc(&B.piece, sizeof(unsigned) * (size_t)n_win * MIXP));
-                REMD_CHECK(h, hipMalloc(&B.npiece, sizeof(unsigned) * (size_t)n_win));
-                B.win_n = (size_t)n_win;
-            }
-            if (B.cnt_n < (size_t)n_win * MIXP * Rp4) { hipFree(B.cnt); B.cnt = nullptr; REMD_CHECK(h, hipMalloc(&B.cnt, (size_t)n_win * MIXP * Rp4)); B.cnt_n = (size_t)n_win * MIXP * Rp4; }
-            if (!B.err) REMD_CHECK(h, hipMalloc(&B.err, sizeof(unsigned)));
-            if (h->mix_log_n < (size_t)n_attempts) {
-                if (h->d_mix_log) { hipFree(h->d_mix_log); h->d_mix_log = nullptr; h->mix_log_n = 0; }
-                REMD_CHECK(h, hipMalloc(&h->d_mix_log, sizeof(unsigned int) * (size_t)n_attempts));
-                h->mix_log_n = (size_t)n_attempts;
-            }
+            mix_pre_buffers& B = remd_table_of(h->mix_pre);
+            REMD_TRY(B.rec.grow(h, (size_t)n_win * W));
+            REMD_TRY(B.piece.grow(h, (size_t)n_win * MIXP));
+            REMD_TRY(B.npiece.grow(h, (size_t)n_win));
+            REMD_TRY(B.cnt.grow(h, (size_t)n_win * MIXP * Rp4));
+            REMD_TRY(B.err.grow(h, 1));
+            REMD_TRY(h->d_mix_log.grow(h, (size_t)n_attempts));
             remd_prof_scope ps(h, "mix_swap_all");
             REMD_CHECK(h, hipMemsetAsync(B.err, 0, sizeof(unsigned), h->stream));
             hipLaunchKernelGGL(mix_prep_kernel, dim3((unsigned)n_win), dim3(W), sizeof(unsigned long long) * (size_t)R * waves, h->stream,
@@ -690,11 +677,7 @@ int remd_mix_launch(remd_ctx* h, int scheme, int64_t iteration, int R, int K, in
         unsigned int* d_log = nullptr;
         const bool use_log = true;              // counters beyond the LDS: attempt log instead of global atomics
         if (!stats_lds && use_log && (size_t)n_attempts * sizeof(unsigned int) <= ((size_t)1 << 30)) {
-            if (h->mix_log_n < (size_t)n_attempts) {
-                if (h->d_mix_log) { hipFree(h->d_mix_log); h->d_mix_log = nullptr; h->mix_log_n = 0; }
-                REMD_CHECK(h, hipMalloc(&h->d_mix_log, sizeof(unsigned int) * (size_t)n_attempts));
-                h->mix_log_n = (size_t)n_attempts;
-            }
+            REMD_TRY(h->d_mix_log.grow(h, (size_t)n_attempts));
             d_log = h->d_mix_log;
         }
         hipLaunchKernelGGL(kern, dim3(1), dim3(64 * waves), lds, h->stream,

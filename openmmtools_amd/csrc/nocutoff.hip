@@ -17,23 +17,12 @@
 
 struct nocutoff_tables {
     int N = 0, words = 0, n_exc = 0, n_tile = 0;
-    float4* d_param = nullptr;             // [Npad] q sqrt(k_e), sigma / 2, 2 sqrt(eps), 0
-    unsigned int* d_excl = nullptr;        // [N][words] excluded partners (all exceptions)
-    int* d_exc_atoms = nullptr; float4* d_exc_par = nullptr;       // non-zero exceptions: k_e qq, sigma, 4 eps
-    double* d_epart = nullptr; int epart_R = 0;                    // [R][n_tile + 1]
+    dev_array<float4> d_param;             // [Npad] q sqrt(k_e), sigma / 2, 2 sqrt(eps), 0
+    dev_array<unsigned int> d_excl;        // [N][words] excluded partners (all exceptions)
+    dev_array<int> d_exc_atoms; dev_array<float4> d_exc_par;       // non-zero exceptions: k_e qq, sigma, 4 eps
+    dev_array<double> d_epart;         // [R][n_tile + 1]
 };
-static handle_table<nocutoff_tables> g_nc;
-
-template <typename T> static void dfree(T*& p) { if (p) { hipFree(p); p = nullptr; } }
-template <typename T>
-static int upload(remd_ctx* h, T*& dptr, const std::vector<T>& host)
-{
-    dfree(dptr);
-    if (host.empty()) return 0;
-    REMD_CHECK(h, hipMalloc(&dptr, sizeof(T) * host.size()));
-    REMD_CHECK(h, hipMemcpy(dptr, host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice));
-    return 0;
-}
+void remd_table_deleter::operator()(nocutoff_tables* t) const { delete t; }
 
 // workgroup = (tile of 64 atoms i, replica), NC_WAVES wavefronts: lane = atom i, wavefront w takes the partners j = w (mod NC_WAVES) of
 // every block of NC_BLOCK atoms staged in LDS; the partial sums of an atom go through LDS and are added in wavefront order (a fixed order:
@@ -122,23 +111,14 @@ void nocutoff_reduce_kernel(int n, const double* __restrict__ part, double* __re
     if (threadIdx.x == 0) epart[(size_t)r * n_epart + slot] = e;
 }
 
-void remd_nocutoff_release(remd_ctx* h)
-{
-    nocutoff_tables* t = g_nc.find(h);
-    if (t) {
-        dfree(t->d_param); dfree(t->d_excl); dfree(t->d_exc_atoms); dfree(t->d_exc_par); dfree(t->d_epart);
-        g_nc.erase(h);
-    }
-    h->nocutoff = 0;
-}
-
 int remd_nocutoff_build(remd_ctx* h, const remd_system_desc* d)
 {
-    remd_nocutoff_release(h);
+    h->nc.reset(); h->nocutoff = 0;
     const int N = d->n_atoms;
     if (!d->charge || !d->sigma || !d->epsilon) return remd_fail(h, -1, "nonbonded parameter arrays missing");
     if (N > 16384) return remd_fail(h, -3, "NoCutoff: more than 16384 atoms (the direct sum is meant for the vacuum test systems)");
-    nocutoff_tables& t = g_nc[h];
+    remd_table<nocutoff_tables> tab(new nocutoff_tables());
+    nocutoff_tables& t = *tab;
     t.N = N; t.words = (N + 31) / 32 + 1; t.n_tile = (N + 63) / 64;
     const double sqk = sqrt(REMD_ONE_4PI_EPS0);
     std::vector<float4> prm(h->Npad, make_float4(0.f, 0.f, 0.f, 0.f));
@@ -147,7 +127,7 @@ int remd_nocutoff_build(remd_ctx* h, const remd_system_desc* d)
     std::vector<int> ea; std::vector<float4> ep;
     for (int e = 0; e < d->n_exceptions; ++e) {
         const int i = d->exception_atoms[2 * e], j = d->exception_atoms[2 * e + 1];
-        if (i < 0 || j < 0 || i >= N || j >= N || i == j) { remd_nocutoff_release(h); return remd_fail(h, -3, "bad exception pair"); }
+        if (i < 0 || j < 0 || i >= N || j >= N || i == j) return remd_fail(h, -3, "bad exception pair");
         ex[(size_t)i * t.words + (j >> 5)] |= 1u << (j & 31);
         ex[(size_t)j * t.words + (i >> 5)] |= 1u << (i & 31);
         const double qq = d->exception_params[3 * e], sg = d->exception_params[3 * e + 1], eps = d->exception_params[3 * e + 2];
@@ -155,7 +135,8 @@ int remd_nocutoff_build(remd_ctx* h, const remd_system_desc* d)
     }
     t.n_exc = (int)ea.size() / 2;
     int rc;
-    if ((rc = upload(h, t.d_param, prm)) || (rc = upload(h, t.d_excl, ex)) || (rc = upload(h, t.d_exc_atoms, ea)) || (rc = upload(h, t.d_exc_par, ep))) { remd_nocutoff_release(h); return rc; }
+    if ((rc = t.d_param.upload(h, prm)) || (rc = t.d_excl.upload(h, ex)) || (rc = t.d_exc_atoms.upload(h, ea)) || (rc = t.d_exc_par.upload(h, ep))) return rc;
+    h->nc = std::move(tab);
     h->nocutoff = 1;
     h->n_exceptions = t.n_exc;
     return 0;
@@ -164,7 +145,7 @@ int remd_nocutoff_build(remd_ctx* h, const remd_system_desc* d)
 // the tables, for the resident small-molecule kernel (integrate.hip)
 int remd_nocutoff_info(remd_ctx* h, const float4** param, const unsigned int** excl, int* words, int* n_exc, const int** exc_atoms, const float4** exc_par)
 {
-    nocutoff_tables* t = g_nc.find(h);
+    const nocutoff_tables* t = h->nc.get();
     if (!t) return -1;
     *param = t->d_param; *excl = t->d_excl; *words = t->words; *n_exc = t->n_exc; *exc_atoms = t->d_exc_atoms; *exc_par = t->d_exc_par;
     return 0;
@@ -173,13 +154,13 @@ int remd_nocutoff_info(remd_ctx* h, const float4** param, const unsigned int** e
 // at the head of a force evaluation (positions current, accumulators zeroed), like the harmonic external force
 int remd_nocutoff_forces(remd_ctx* h, bool with_energy, int ep_slot)
 {
-    nocutoff_tables* tp = g_nc.find(h);
+    nocutoff_tables* tp = h->nc.get();
     if (!tp) return remd_fail(h, -2, "NoCutoff: no tables on this handle");
     nocutoff_tables& t = *tp;
     remd_prof_scope ps(h, "nonbonded");
     const dim3 grid(t.n_tile + 1, h->R);
     if (with_energy) {
-        if (t.epart_R != h->R) { dfree(t.d_epart); REMD_CHECK(h, hipMalloc(&t.d_epart, sizeof(double) * (size_t)h->R * (t.n_tile + 1))); t.epart_R = h->R; }
+        if (t.d_epart.size() != (size_t)h->R * (t.n_tile + 1)) REMD_TRY(t.d_epart.alloc(h, (size_t)h->R * (t.n_tile + 1)));
         hipLaunchKernelGGL(nocutoff_kernel<true>, grid, dim3(NC_BLOCK), 0, h->stream, t.N, h->Npad, t.words, t.d_param, t.d_excl, t.n_exc, t.d_exc_atoms, t.d_exc_par,
                            h->d_pos, h->d_force, t.d_epart, t.n_tile);
         hipLaunchKernelGGL(nocutoff_reduce_kernel, dim3(h->R), dim3(64), 0, h->stream, t.n_tile + 1, t.d_epart, h->d_epart, h->n_epart, ep_slot);

@@ -35,31 +35,31 @@ struct pme_state {
     int R = 0;
     size_t npts = 0;
     bool ready = false;                // buffers of the force path are allocated (not the FFT test hook's)
-    float2* d_grid = nullptr;          // [R][nz/2+1][nx][ny] half spectrum, kz-major (or the full complex grid of the test hook)
+    dev_array<float2> d_grid;          // [R][nz/2+1][nx][ny] half spectrum, kz-major (or the full complex grid of the test hook)
     hipStream_t stream = nullptr;      // stream of the current remd_pme_forces call
     int nzc = 0; size_t nspec = 0; size_t xy_lds = 0; bool xy_fused = false; int xy_threads = 512;
     int xy_pow2 = 0;                   // 64 / 128: the plane pass runs on the register transforms of pme_pow2.h
-    int* d_col_count = nullptr; int* d_col_start = nullptr; int* d_cursor = nullptr; int* d_atom_col = nullptr; int* d_col_atoms = nullptr;
-    float2* d_tw[4] = {nullptr, nullptr, nullptr, nullptr};   // twiddle tables exp(-2 pi i k / n)
-    float* d_bmod[3] = {nullptr, nullptr, nullptr};  // |b(m)|^-2 ... stored as B-spline moduli squared inverse
+    dev_array<int> d_col_count; dev_array<int> d_col_start; dev_array<int> d_cursor; dev_array<int> d_atom_col; dev_array<int> d_col_atoms;
+    dev_array<float2> d_tw[4];   // twiddle tables exp(-2 pi i k / n)
+    dev_array<float> d_bmod[3];  // |b(m)|^-2 ... stored as B-spline moduli squared inverse
     int nrad[4] = {0, 0, 0, 0}; int radix[4][8];
     int xs_sw = 0;                      // y-slab width of pme_x_fused_kernel (planes that do not fit the LDS)
     int ys_sh = 0;                      // x-slab height of pme_y_slab_kernel (the y passes of those planes)
-    float* d_infl = nullptr; int infl_version = -1;   // influence function [R][nz/2+1][nx][ny], rebuilt when a box changes
+    dev_array<float> d_infl; int infl_version = -1;   // influence function [R][nz/2+1][nx][ny], rebuilt when a box changes
     int infl_rep = 0;                                 // planes between two replicas' tables (0: all boxes equal, one table)
     bool z_half = false;               // nz even: z transforms run as nz/2-point complex FFTs of packed real pairs
-    double* d_energy = nullptr;        // [R][n_eblk]
+    dev_array<double> d_energy;        // [R][n_eblk]
     int n_eblk = 0;
     fft_sched sch_x, sch_y, sch_z;     // butterfly schedules of the in-place passes (xy planes; z lines for (sch_nl, sch_zt))
-    uint2* d_sched[3] = {nullptr, nullptr, nullptr};
+    dev_array<uint2> d_sched[3];
     int sch_nl = 0, sch_zt = 0;
     // bins filled by the integrator chain's epilogue (no binning launch on the critical path): count[2][R][nx] double buffered by
     // evaluation parity (the spreading pass zeroes the other one), atoms[R][nx][cbin_cap]; cbin_use: this evaluation reads them
-    float* d_cbin_q = nullptr;
+    dev_array<float> d_cbin_q;
     // mesh forces by position in the bins (round 6): the gather's atomics of neighbouring lanes fall on neighbouring addresses, and
     // pme_unbin_forces_kernel hands every atom its total with ONE scattered triple (the gather used to issue five per atom)
-    unsigned long long* d_fbin = nullptr; size_t fbin_P = 0;
-    int* d_cbin_count = nullptr; float4* d_cbin_atoms = nullptr; int cbin_cap = 0, cbin_parity = 0; bool cbin_use = false;
+    dev_array<unsigned long long> d_fbin; size_t fbin_P = 0;
+    dev_array<int> d_cbin_count; dev_array<float4> d_cbin_atoms; int cbin_cap = 0, cbin_parity = 0; bool cbin_use = false;
 };
 
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
@@ -1134,24 +1134,7 @@ static double bspline_M(int order, double u)
     return u / (order - 1) * bspline_M(order - 1, u) + (order - u) / (order - 1) * bspline_M(order - 1, u - 1.0);
 }
 
-int remd_pme_destroy(remd_ctx* h)
-{
-    pme_state* s = (pme_state*)h->pme;
-    if (!s) return 0;
-    if (s->d_grid) hipFree(s->d_grid);
-    if (s->d_col_count) hipFree(s->d_col_count); if (s->d_col_start) hipFree(s->d_col_start); if (s->d_cursor) hipFree(s->d_cursor);
-    if (s->d_atom_col) hipFree(s->d_atom_col); if (s->d_col_atoms) hipFree(s->d_col_atoms);
-    for (int k = 0; k < 4; ++k) if (s->d_tw[k]) hipFree(s->d_tw[k]);
-    for (int k = 0; k < 3; ++k) if (s->d_bmod[k]) hipFree(s->d_bmod[k]);
-    if (s->d_energy) hipFree(s->d_energy);
-    if (s->d_infl) hipFree(s->d_infl);
-    if (s->d_fbin) hipFree(s->d_fbin);
-    if (s->d_cbin_count) hipFree(s->d_cbin_count); if (s->d_cbin_atoms) hipFree(s->d_cbin_atoms); if (s->d_cbin_q) hipFree(s->d_cbin_q);
-    for (int k = 0; k < 3; ++k) if (s->d_sched[k]) hipFree(s->d_sched[k]);
-    delete s;
-    h->pme = nullptr;
-    return 0;
-}
+void remd_table_deleter::operator()(pme_state* s) const { delete s; }
 
 static fft_plan make_plan(pme_state* s, int axis)
 {
@@ -1168,7 +1151,7 @@ static fft_plan make_plan(pme_state* s, int axis)
 // host mirror of the index arithmetic of one in-place pass (element e of line l at l*ls + e*es, consecutive threads
 // take consecutive lines): fills the butterfly schedule read by fft_stage_sched
 static int build_sched(remd_ctx* h, pme_state* s, int axis, int nlines, int ls, int es, int nthreads, int ppt,
-                       fft_sched* out, uint2** d_tab)
+                       fft_sched* out, dev_array<uint2>& d_tab)
 {
     const int n = s->n[axis];
     std::vector<uint2> tab;
@@ -1193,19 +1176,16 @@ static int build_sched(remd_ctx* h, pme_state* s, int axis, int nlines, int ls, 
             }
         Ns *= Rx;
     }
-    if (*d_tab) { hipFree(*d_tab); *d_tab = nullptr; }
-    REMD_CHECK(h, hipMalloc(d_tab, sizeof(uint2) * tab.size()));
-    REMD_CHECK(h, hipMemcpy(*d_tab, tab.data(), sizeof(uint2) * tab.size(), hipMemcpyHostToDevice));
-    out->tab = *d_tab;
+    REMD_TRY(d_tab.upload(h, tab));
+    out->tab = d_tab;
     return 0;
 }
 
 // full_complex: allocate the [R][nx][ny][nz] complex grid of the FFT test hook instead of the PME buffers
 static int pme_setup_impl(remd_ctx* h, bool full_complex)
 {
-    remd_pme_destroy(h);
-    pme_state* s = new pme_state();
-    h->pme = s;
+    h->pme.reset(new pme_state());
+    pme_state* s = h->pme.get();
     for (int k = 0; k < 3; ++k) {
         s->n[k] = h->grid[k];
         if (s->n[k] < 6 || s->n[k] > 256 || !factorize(s->n[k], s->radix[k], s->nrad[k]))
@@ -1219,34 +1199,34 @@ static int pme_setup_impl(remd_ctx* h, bool full_complex)
     s->nzc = s->n[2] / 2 + 1;
     s->nspec = (size_t)s->nzc * s->n[0] * s->n[1];
     if (full_complex) {
-        REMD_CHECK(h, hipMalloc(&s->d_grid, sizeof(float2) * s->npts * s->R));
+        REMD_TRY(s->d_grid.alloc(h, s->npts * s->R));
     } else {
         s->ready = true;
-        REMD_CHECK(h, hipMalloc(&s->d_grid, sizeof(float2) * s->nspec * s->R));
-        REMD_CHECK(h, hipMalloc(&s->d_col_start, sizeof(int) * (size_t)(s->n[0] + 1) * s->R));
-        REMD_CHECK(h, hipMalloc(&s->d_col_atoms, sizeof(int) * (size_t)h->Npad * s->R));
+        REMD_TRY(s->d_grid.alloc(h, s->nspec * s->R));
+        REMD_TRY(s->d_col_start.alloc(h, (size_t)(s->n[0] + 1) * s->R));
+        REMD_TRY(s->d_col_atoms.alloc(h, (size_t)h->Npad * s->R));
         if (!full_complex && h->sw.pme_chainbin != 0) {
             // four times the mean occupancy of a mesh column (x bins are 1 / nx of a homogeneous box): overflow is detected
             s->cbin_cap = std::min(h->Npad, std::max(64, 4 * ((h->N + s->n[0] - 1) / s->n[0])));
             if (h->sw.pme_cbin_cap) s->cbin_cap = h->sw.pme_cbin_cap;      // test hook: provoke the overflow path
-            REMD_CHECK(h, hipMalloc(&s->d_cbin_count, sizeof(int) * 2 * (size_t)s->R * s->n[0]));
+            REMD_TRY(s->d_cbin_count.alloc(h, 2 * (size_t)s->R * s->n[0]));
             REMD_CHECK(h, hipMemset(s->d_cbin_count, 0, sizeof(int) * 2 * (size_t)s->R * s->n[0]));
-            REMD_CHECK(h, hipMalloc(&s->d_cbin_atoms, sizeof(float4) * (size_t)s->R * s->n[0] * s->cbin_cap));
-            REMD_CHECK(h, hipMalloc(&s->d_cbin_q, sizeof(float) * (size_t)s->R * s->n[0] * s->cbin_cap));
+            REMD_TRY(s->d_cbin_atoms.alloc(h, (size_t)s->R * s->n[0] * s->cbin_cap));
+            REMD_TRY(s->d_cbin_q.alloc(h, (size_t)s->R * s->n[0] * s->cbin_cap));
         }
     }
     if (s->z_half) {
         const int n = s->n[3];
         std::vector<float2> tw(n);
         for (int j = 0; j < n; ++j) tw[j] = make_float2((float)cos(2.0 * M_PI * j / n), (float)(-sin(2.0 * M_PI * j / n)));
-        REMD_CHECK(h, hipMalloc(&s->d_tw[3], sizeof(float2) * n));
+        REMD_TRY(s->d_tw[3].alloc(h, n));
         REMD_CHECK(h, hipMemcpy(s->d_tw[3], tw.data(), sizeof(float2) * n, hipMemcpyHostToDevice));
     }
     for (int k = 0; k < 3; ++k) {
         const int n = s->n[k];
         std::vector<float2> tw(n);
         for (int j = 0; j < n; ++j) tw[j] = make_float2((float)cos(2.0 * M_PI * j / n), (float)(-sin(2.0 * M_PI * j / n)));
-        REMD_CHECK(h, hipMalloc(&s->d_tw[k], sizeof(float2) * n));
+        REMD_TRY(s->d_tw[k].alloc(h, n));
         REMD_CHECK(h, hipMemcpy(s->d_tw[k], tw.data(), sizeof(float2) * n, hipMemcpyHostToDevice));
         // |sum_{k=0}^{order-2} M_n(k+1) exp(2 pi i m k / K)|^2  (Essmann eq. 4.4 denominator)
         std::vector<float> bm(n);
@@ -1261,11 +1241,11 @@ static int pme_setup_impl(remd_ctx* h, bool full_complex)
         // odd spline orders have a zero of the modulus at m = K/2: replace it by the mean of its neighbours
         for (int m = 0; m < n; ++m)
             if (bm[m] < 1e-7f) bm[m] = 0.5f * (bm[(m + n - 1) % n] + bm[(m + 1) % n]);
-        REMD_CHECK(h, hipMalloc(&s->d_bmod[k], sizeof(float) * n));
+        REMD_TRY(s->d_bmod[k].alloc(h, n));
         REMD_CHECK(h, hipMemcpy(s->d_bmod[k], bm.data(), sizeof(float) * n, hipMemcpyHostToDevice));
     }
     s->n_eblk = s->nzc;
-    REMD_CHECK(h, hipMalloc(&s->d_energy, sizeof(double) * (size_t)s->n_eblk * s->R));
+    REMD_TRY(s->d_energy.alloc(h, (size_t)s->n_eblk * s->R));
     s->xy_lds = sizeof(float2) * ((size_t)s->n[0] * (s->n[1] | 1) + s->n[0] + s->n[1]) + 128;
     // workgroup size of the XY kernel: every stage issues ceil(butterflies / threads) butterfly slots per thread,
     // masked-off slots still cost issue cycles, so pick the wavefront count that wastes the fewest (75 x 75: 384 threads
@@ -1300,17 +1280,16 @@ static int pme_setup_impl(remd_ctx* h, bool full_complex)
         for (int c = 1; c <= s->n[1]; ++c)
             if (s->n[1] % c == 0 && (long long)s->n[0] * c <= (long long)XY_PPT * XS_THREADS && (size_t)s->n[0] * (c | 1) * 8 <= 40 * 1024) s->xs_sw = c;
         if (s->xs_sw > 0) {
-            int rc = build_sched(h, s, 0, s->xs_sw, 1, s->xs_sw | 1, XS_THREADS, XY_PPT, &s->sch_x, &s->d_sched[0]);
+            int rc = build_sched(h, s, 0, s->xs_sw, 1, s->xs_sw | 1, XS_THREADS, XY_PPT, &s->sch_x, s->d_sched[0]);
             if (rc) return rc;
             s->n_eblk = s->nzc * (s->n[1] / s->xs_sw);
-            hipFree(s->d_energy); s->d_energy = nullptr;
-            REMD_CHECK(h, hipMalloc(&s->d_energy, sizeof(double) * (size_t)s->n_eblk * s->R));
+            REMD_TRY(s->d_energy.alloc(h, (size_t)s->n_eblk * s->R));
             REMD_CHECK(h, hipFuncSetAttribute((const void*)pme_x_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
             // the y passes on slabs of x rows: tallest divisor of nx that fits the same registers and ~40 KB of LDS
             for (int c = 1; c <= s->n[0]; ++c)
                 if (s->n[0] % c == 0 && (long long)s->n[1] * c <= (long long)XY_PPT * XS_THREADS && (size_t)c * (s->n[1] | 1) * 8 <= 40 * 1024) s->ys_sh = c;
             if (s->ys_sh > 0) {
-                rc = build_sched(h, s, 1, s->ys_sh, s->n[1] | 1, 1, XS_THREADS, XY_PPT, &s->sch_y, &s->d_sched[1]);
+                rc = build_sched(h, s, 1, s->ys_sh, s->n[1] | 1, 1, XS_THREADS, XY_PPT, &s->sch_y, s->d_sched[1]);
                 if (rc) return rc;
                 REMD_CHECK(h, hipFuncSetAttribute((const void*)pme_y_slab_kernel<-1>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
                 REMD_CHECK(h, hipFuncSetAttribute((const void*)pme_y_slab_kernel<+1>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
@@ -1331,8 +1310,8 @@ static int pme_setup_impl(remd_ctx* h, bool full_complex)
     if (s->xy_fused && !full_complex && !s->xy_pow2) {
         REMD_CHECK(h, hipFuncSetAttribute((const void*)pme_xy_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->xy_lds));
         const int PS = s->n[1] | 1;
-        int rc = build_sched(h, s, 1, s->n[0], PS, 1, s->xy_threads, XY_PPT, &s->sch_y, &s->d_sched[1]);      // along y: lines = x rows
-        if (!rc) rc = build_sched(h, s, 0, s->n[1], 1, PS, s->xy_threads, XY_PPT, &s->sch_x, &s->d_sched[0]);  // along x: lines = y columns
+        int rc = build_sched(h, s, 1, s->n[0], PS, 1, s->xy_threads, XY_PPT, &s->sch_y, s->d_sched[1]);      // along y: lines = x rows
+        if (!rc) rc = build_sched(h, s, 0, s->n[1], 1, PS, s->xy_threads, XY_PPT, &s->sch_x, s->d_sched[0]);  // along x: lines = y columns
         if (rc) return rc;
     }
 #define Z_LDS_ATTR(ZT, HF) \
@@ -1363,8 +1342,8 @@ const float4* remd_nb_param(remd_ctx* h);
 
 int remd_pme_forces(remd_ctx* h, bool with_energy, hipStream_t st, int part)
 {
-    pme_state* s = (pme_state*)h->pme;
-    if (!s || s->R != h->R || !s->ready) { int rc = remd_pme_setup(h); if (rc) return rc; s = (pme_state*)h->pme; }
+    pme_state* s = h->pme.get();
+    if (!s || s->R != h->R || !s->ready) { int rc = remd_pme_setup(h); if (rc) return rc; s = h->pme.get(); }
     s->stream = st;
     s->prio_hi = h->mesh_prio_hi;
     const int nx = s->n[0], ny = s->n[1], nz = s->n[2];
@@ -1395,7 +1374,7 @@ int remd_pme_forces(remd_ctx* h, bool with_energy, hipStream_t st, int part)
         const size_t zlds = sizeof(float2) * ((size_t)nl * PZ + nz + (half ? M : 0));
         const dim3 zgrid(nx * ((ny + nl - 1) / nl), s->R);
         if (s->sch_nl != nl || s->sch_zt != ZT) {
-            int rc = build_sched(h, s, zaxis, nl, PZ, 1, ZT, Z_PPT, &s->sch_z, &s->d_sched[2]);
+            int rc = build_sched(h, s, zaxis, nl, PZ, 1, ZT, Z_PPT, &s->sch_z, s->d_sched[2]);
             if (rc) return rc;
             s->sch_nl = nl; s->sch_zt = ZT;
         }
@@ -1405,7 +1384,7 @@ int remd_pme_forces(remd_ctx* h, bool with_energy, hipStream_t st, int part)
         // bins: compact arrays of the binning launch, or the capped ones the integrator chain filled (buffer cbin_parity; this
         // pass zeroes the other buffer for the next evaluation and, with no binning launch in front, publishes the fork)
         const int* bin_cs = s->cbin_use ? s->d_cbin_count + (size_t)s->cbin_parity * s->R * nx : s->d_col_start;
-        const int* bin_ca = s->cbin_use ? reinterpret_cast<const int*>(s->d_cbin_atoms) : s->d_col_atoms;
+        const int* bin_ca = s->cbin_use ? reinterpret_cast<const int*>(s->d_cbin_atoms.get()) : s->d_col_atoms;
         const int bin_cap = s->cbin_use ? s->cbin_cap : 0;
         int* bin_zero = s->cbin_use ? s->d_cbin_count + (size_t)(1 - s->cbin_parity) * s->R * nx : (int*)nullptr;
         unsigned int* fflag = (s->cbin_use && h->fork_seq_pending) ? h->d_sync : (unsigned int*)nullptr;
@@ -1434,7 +1413,7 @@ int remd_pme_forces(remd_ctx* h, bool with_energy, hipStream_t st, int part)
         }
         h->mesh_listed_total = 0;
         if (s->xy_fused || s->xs_sw > 0) {
-            if (!s->d_infl) REMD_CHECK(h, hipMalloc(&s->d_infl, sizeof(float) * s->nspec * s->R));
+            if (!s->d_infl) REMD_TRY(s->d_infl.alloc(h, s->nspec * s->R));
             if (s->infl_version != h->box_version) {
                 // one table serves every replica while all boxes are the same (constant volume): 1 / R of the table traffic
                 hipLaunchKernelGGL(pme_influence_table_kernel, dim3(s->nzc, h->box_uniform ? 1 : s->R), dim3(256), 0, st, nx, ny, nz, s->d_bmod[0], s->d_bmod[1],
@@ -1484,7 +1463,7 @@ int remd_pme_forces(remd_ctx* h, bool with_energy, hipStream_t st, int part)
         // mesh forces by bin position + one hand-over to the atoms (REMD_PME_FBIN=0: five scattered atomic triples per atom)
         if (h->sw.pme_fbin && !s->d_fbin) {
             s->fbin_P = std::max((size_t)nx * (size_t)std::max(s->cbin_cap, 0), (size_t)h->Npad);
-            REMD_CHECK(h, hipMalloc(&s->d_fbin, sizeof(unsigned long long) * 3 * s->fbin_P * s->R));
+            REMD_TRY(s->d_fbin.alloc(h, 3 * s->fbin_P * s->R));
             REMD_CHECK(h, hipMemsetAsync(s->d_fbin, 0, sizeof(unsigned long long) * 3 * s->fbin_P * s->R, st));
         }
         unsigned long long* fbin = h->sw.pme_fbin ? s->d_fbin : (unsigned long long*)nullptr;
@@ -1523,7 +1502,7 @@ int remd_pme_forces(remd_ctx* h, bool with_energy, hipStream_t st, int part)
 remd_chain_bins remd_pme_chain_bins(remd_ctx* h)
 {
     remd_chain_bins b;
-    pme_state* s = (pme_state*)h->pme;
+    const pme_state* s = h->pme.get();
     if (!s || !s->d_cbin_count || s->R != h->R || !h->pme_concurrent || h->no_chain_bins) return b;
     b.nx = s->n[0]; b.cap = s->cbin_cap; b.count = s->d_cbin_count + (size_t)s->cbin_parity * s->R * s->n[0]; b.atoms = s->d_cbin_atoms;
     b.box = h->d_box; b.err = h->d_sync + 2;
@@ -1536,13 +1515,13 @@ remd_chain_bins remd_pme_chain_bins(remd_ctx* h)
 
 int remd_test_fft3d_impl(remd_ctx* h, int nx, int ny, int nz, float* data, int inverse)
 {
-    pme_state* old = (pme_state*)h->pme;
+    remd_table<pme_state> old = std::move(h->pme);
     const int oldgrid[3] = { h->grid[0], h->grid[1], h->grid[2] };
     const int oldR = h->R;
-    h->pme = nullptr; h->grid[0] = nx; h->grid[1] = ny; h->grid[2] = nz; h->R = 1;
+    h->grid[0] = nx; h->grid[1] = ny; h->grid[2] = nz; h->R = 1;
     int rc = pme_setup_impl(h, true);
     if (!rc) {
-        pme_state* s = (pme_state*)h->pme;
+        pme_state* s = h->pme.get();
         hipMemcpy(s->d_grid, data, sizeof(float2) * s->npts, hipMemcpyHostToDevice);
         auto all = [&](auto tag) {
             constexpr int SG = decltype(tag)::value;
@@ -1555,7 +1534,6 @@ int remd_test_fft3d_impl(remd_ctx* h, int nx, int ny, int nz, float* data, int i
         hipMemcpy(data, s->d_grid, sizeof(float2) * s->npts, hipMemcpyDeviceToHost);
         if (hipGetLastError() != hipSuccess) rc = remd_fail(h, -2, "fft test launch failed");
     }
-    remd_pme_destroy(h);
-    h->pme = old; h->grid[0] = oldgrid[0]; h->grid[1] = oldgrid[1]; h->grid[2] = oldgrid[2]; h->R = oldR;
+    h->pme = std::move(old); h->grid[0] = oldgrid[0]; h->grid[1] = oldgrid[1]; h->grid[2] = oldgrid[2]; h->R = oldR;
     return rc;
 }

@@ -5,16 +5,73 @@
 #include <stdlib.h>
 #include <algorithm>
 #include <string>
-#include <mutex>
 #include <map>
+#include <memory>
 #include <vector>
-#include <map>
 #include "../../include/remd_hip.h"
 
 #define REMD_KB 0.00831446261815324   // kJ/mol/K  (BOLTZMANN_CONSTANT_kB * AVOGADRO_CONSTANT_NA)
 #define REMD_ONE_4PI_EPS0 138.93545764438198
 
 struct remd_error { int code; std::string msg; };
+
+struct remd_ctx;
+void remd_set_global_error(const std::string& s);
+int remd_hip_fail(remd_ctx* h, const char* what, hipError_t e);      // h->err and the global error, -2 (as REMD_CHECK)
+
+// The one owner of a device allocation: move-only, freed by its destructor.  It converts to T* for kernel arguments, hipMemcpy*
+// and pointer arithmetic; kernel argument structs hold the raw pointer, never this type.  alloc / upload / grow report a failed
+// allocation through the handle and return -2.
+template <typename T>
+struct dev_array {
+    dev_array() = default;
+    dev_array(const dev_array&) = delete;
+    dev_array& operator=(const dev_array&) = delete;
+    dev_array(dev_array&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+    dev_array& operator=(dev_array&& o) noexcept { if (this != &o) { reset(); std::swap(p_, o.p_); std::swap(n_, o.n_); } return *this; }
+    ~dev_array() { reset(); }
+    operator T*() const { return p_; }
+    T* get() const { return p_; }
+    size_t size() const { return n_; }
+    void reset() { if (p_) hipFree(p_); p_ = nullptr; n_ = 0; }
+    // exactly n elements, contents undefined (n = 0: none)
+    int alloc(remd_ctx* h, size_t n)
+    {
+        reset();
+        if (!n) return 0;
+        const hipError_t e = hipMalloc(&p_, sizeof(T) * n);
+        if (e != hipSuccess) { p_ = nullptr; return remd_hip_fail(h, "hipMalloc", e); }
+        n_ = n;
+        return 0;
+    }
+    // at least n elements; an array that is large enough is kept as it is
+    int grow(remd_ctx* h, size_t n) { return n_ >= n && p_ ? 0 : alloc(h, n); }
+    // a copy of `host` (empty: no allocation)
+    int upload(remd_ctx* h, const std::vector<T>& host)
+    {
+        if (int rc = alloc(h, host.size())) return rc;
+        if (host.empty()) return 0;
+        const hipError_t e = hipMemcpy(p_, host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice);
+        return e == hipSuccess ? 0 : remd_hip_fail(h, "hipMemcpy", e);
+    }
+private:
+    T* p_ = nullptr; size_t n_ = 0;
+};
+
+// what `expr` (an int status: 0 success) failed with, returned from the calling function
+#define REMD_TRY(expr) do { const int _rc = (expr); if (_rc) return _rc; } while (0)
+
+// The feature tables a handle owns, each defined in the .hip file that builds it; the deleter of each is defined there too.
+struct nb_tables; struct pme_state; struct unit_tables; struct gbsa_tables; struct nocutoff_tables; struct region_tables; struct rst_tables;
+struct mix_pre_buffers;
+struct remd_table_deleter {
+    void operator()(nb_tables*) const; void operator()(pme_state*) const; void operator()(unit_tables*) const;
+    void operator()(gbsa_tables*) const; void operator()(nocutoff_tables*) const; void operator()(region_tables*) const;
+    void operator()(rst_tables*) const; void operator()(mix_pre_buffers*) const;
+};
+template <typename T> using remd_table = std::unique_ptr<T, remd_table_deleter>;
+// a handle's table, made on first use
+template <typename T> T& remd_table_of(remd_table<T>& t) { if (!t) t.reset(new T()); return *t; }
 
 // fixed-point scale of the force accumulators (deterministic integer atomics)
 #define REMD_FORCE_SCALE 4294967296.0   // 2^32
@@ -141,17 +198,17 @@ struct remd_ctx {
     int N = 0;            // atoms
     int Npad = 0;         // atoms padded to a multiple of 64
     bool has_system = false;
-    float* d_invmass = nullptr;        // [Npad]  (0 for padding)
-    float* d_mass = nullptr;           // [Npad]
+    dev_array<float> d_invmass;        // [Npad]  (0 for padding)
+    dev_array<float> d_mass;           // [Npad]
     double total_mass = 0.0;
     // harmonic external force
-    int n_ext = 0; int* d_ext_atoms = nullptr; double ext_K = 0, ext_x0 = 0, ext_U0 = 0;
+    int n_ext = 0; dev_array<int> d_ext_atoms; double ext_K = 0, ext_x0 = 0, ext_U0 = 0;
     // bonded
     int n_bonds = 0, n_angles = 0, n_torsions = 0;
-    int* d_bond_atoms = nullptr; float* d_bond_params = nullptr;
-    unsigned int* d_aterm = nullptr; int n_aterm = 0;      // (term, slot) entries of the listed terms by atom (forces.hip: build_atom_terms)
-    int* d_angle_atoms = nullptr; float* d_angle_params = nullptr;
-    int* d_torsion_atoms = nullptr; float* d_torsion_params = nullptr;
+    dev_array<int> d_bond_atoms; dev_array<float> d_bond_params;
+    dev_array<unsigned int> d_aterm; int n_aterm = 0;      // (term, slot) entries of the listed terms by atom (forces.hip: build_atom_terms)
+    dev_array<int> d_angle_atoms; dev_array<float> d_angle_params;
+    dev_array<int> d_torsion_atoms; dev_array<float> d_torsion_params;
     // nonbonded
     int nb_method = REMD_NB_NONE;
     int gbsa = 0;                      // remd_set_gbsa: GBSA (OBC2 + ACE) of a NoCutoff system (gbsa.hip)
@@ -163,23 +220,23 @@ struct remd_ctx {
     int grid[3] = {0, 0, 0};
     int use_disp = 0;
     double disp_coeff = 0;             // E_lrc = disp_coeff / V for the non-alchemical system
-    float4* d_nbparam = nullptr;       // [Npad] (q, sigma/2, 2*sqrt(eps), alch flag)
-    unsigned long long* d_exclmask = nullptr; // [Npad][EXCL_WORDS] window exclusion bit masks
+    dev_array<float4> d_nbparam;       // [Npad] (q, sigma/2, 2*sqrt(eps), alch flag)
+    dev_array<unsigned long long> d_exclmask; // [Npad][EXCL_WORDS] window exclusion bit masks
     int excl_window = 0;               // atoms j in [i-excl_window, i+excl_window] are mask-addressable
     int n_exceptions = 0;              // 1-4 style exceptions with non-zero params
-    int* d_exc_atoms = nullptr; float* d_exc_params = nullptr;   // [n][2], [n][3]
+    dev_array<int> d_exc_atoms; dev_array<float> d_exc_params;   // [n][2], [n][3]
     int n_excl_pairs = 0;              // all excluded pairs (for the PME exclusion correction)
-    int* d_excl_pairs = nullptr;       // [n][2]
+    dev_array<int> d_excl_pairs;       // [n][2]
     double self_energy = 0;            // PME self term (kJ/mol), lambda_elec = 1
     // constraints
-    int n_settle = 0; int* d_settle_atoms = nullptr; double settle_dOH = 0, settle_dHH = 0;
-    int n_shake = 0;  int* d_shake_atoms = nullptr; float* d_shake_dist = nullptr;
-    int n_groups = 0; int* d_group_first = nullptr;   // constraint groups (molecule-like units)
-    int* d_free_atoms = nullptr; int n_free = 0;      // atoms in no constraint
+    int n_settle = 0; dev_array<int> d_settle_atoms; double settle_dOH = 0, settle_dHH = 0;
+    int n_shake = 0;  dev_array<int> d_shake_atoms; dev_array<float> d_shake_dist;
+    int n_groups = 0; dev_array<int> d_group_first;   // constraint groups (molecule-like units)
+    dev_array<int> d_free_atoms; int n_free = 0;      // atoms in no constraint
     int cmm_frequency = 0;
     int n_dof = 0;
     // alchemy
-    int n_alch = 0; int* d_alch_atoms = nullptr;
+    int n_alch = 0; dev_array<int> d_alch_atoms;
     double sc_alpha = 0.5, sc_a = 1, sc_b = 1, sc_c = 6;
     int n_regions = 0;                 // remd_set_alchemical_regions: general regions (alch_regions.hip holds the tables)
     int regions_exact = 0;             // ... under the exact PME treatment (the regions' scaled charges inside the Ewald sum)
@@ -189,7 +246,7 @@ struct remd_ctx {
     // ---- states ---------------------------------------------------------------------
     int K = 0;
     std::vector<double> beta, lam_s, lam_e, econst;
-    double* d_beta = nullptr; double* d_lam_s = nullptr; double* d_lam_e = nullptr; double* d_econst = nullptr;
+    dev_array<double> d_beta; dev_array<double> d_lam_s; dev_array<double> d_lam_e; dev_array<double> d_econst;
 
     // ---- integrator -----------------------------------------------------------------
     std::string splitting = "V R O R V";
@@ -199,61 +256,67 @@ struct remd_ctx {
     // nVg[g] = occurrences per step, fgroup[c] = force group of class c (REMD_FG_*), d_force_g[g] = that group's forces
     int nVg[4] = {0, 0, 0, 0};
     int fgroup[6] = {0, 0, 0, 0, 0, 0};
-    long long* d_force_g[4] = {nullptr, nullptr, nullptr, nullptr}; size_t force_g_n = 0;
+    dev_array<long long> d_force_g[4];
     double dt = 0.001, gamma = 1.0, constraint_tol = 1e-8;
     int n_steps = 1; int reassign = 1;
     bool has_integrator = false;
     // heat / shadow work / Metropolization (integrators.py:1175-1204, 1404-1460, 1539-1557)
     int measure_heat = 0, measure_shadow = 0;                   // (a splitting with '{' '}' measures shadow work whatever the flag says)
-    long long* d_snap_work = nullptr;  // [2][R][4] remd_propagate: d_work at the start of the call / of each replica's successful attempt
-    long long* d_work = nullptr;       // [R][4] fixed point 2^-24 kJ/mol: heat, shadow work; integers: Metropolis trials, rejections
-    double* d_pe_prev = nullptr;       // [R] potential energy at the positions the last energy evaluation saw
-    float4* d_xold = nullptr; float4* d_vold = nullptr; int* d_accept = nullptr;   // '{' snapshot, per-replica decision of '}'
-    int work_R = 0;
+    dev_array<long long> d_snap_work;  // [2][R][4] remd_propagate: d_work at the start of the call / of each replica's successful attempt
+    dev_array<long long> d_work;       // [R][4] fixed point 2^-24 kJ/mol: heat, shadow work; integers: Metropolis trials, rejections
+    dev_array<double> d_pe_prev;       // [R] potential energy at the positions the last energy evaluation saw
+    dev_array<float4> d_xold; dev_array<float4> d_vold; dev_array<int> d_accept;   // '{' snapshot, per-replica decision of '}'
 
     // ---- replicas -------------------------------------------------------------------
     int R_global = 0, r_begin = 0, R = 0;     // R = local replicas
     // remd_set_replica_ids: what keys the local replicas' random streams instead of r_begin + r (a handle that holds a
     // non-contiguous subset of an ensemble, multistate/_engine_pool.py); NULL: the block's own global indices
-    unsigned int* d_noise_id = nullptr;
-    float4* d_pos = nullptr;           // [R][Npad] xyz + pad
-    float4* d_vel = nullptr;           // [R][Npad] xyz + pad
+    dev_array<unsigned int> d_noise_id;
+    dev_array<float4> d_pos;           // [R][Npad] xyz + pad
+    dev_array<float4> d_vel;           // [R][Npad] xyz + pad
     // Monte Carlo barostat (OpenMM MonteCarloBarostat as the reference's NPT ThermodynamicState adds it, states.py:1177-1181)
     int baro_frequency = 0; long long baro_steps = 0, baro_attempts = 0; std::vector<double> pressure_host;   // (pressure_host: for the blocks of a phased propagation)
     double econst_vref = 0.0;          // volume at which the per-state energy constants were evaluated (they scale as 1/V); 0: constant
-    double* d_pressure = nullptr;      // [K] kJ/mol/nm^3 (bar * N_A * 1e-25)
-    double* d_baro = nullptr;          // [R][8]: volumeScale, attempted, accepted (adaptation window), total attempted, total accepted, dV, newV, oldV
-    float* d_box_old = nullptr; float4* d_baro_x0 = nullptr; long long* d_baro_f0 = nullptr; double* d_baro_U0 = nullptr; int* d_baro_acc = nullptr;
+    dev_array<double> d_pressure;      // [K] kJ/mol/nm^3 (bar * N_A * 1e-25)
+    dev_array<double> d_baro;          // [R][8]: volumeScale, attempted, accepted (adaptation window), total attempted, total accepted, dV, newV, oldV
+    dev_array<float> d_box_old; dev_array<float4> d_baro_x0; dev_array<long long> d_baro_f0; dev_array<double> d_baro_U0; dev_array<int> d_baro_acc;
     bool box_uniform = false;          // every local replica has the same box (set_replicas; a barostat move clears it)
     int box_version = 0;               // bumped whenever the box edges on the device change (PME influence table)
     int n_restart_attempts = 0;        // mcmc.py:706-759
-    unsigned int* d_mix_log = nullptr; size_t mix_log_n = 0;      // swap-all attempt log (si, sj, accepted) when the counters do not fit
+    dev_array<unsigned int> d_mix_log;      // swap-all attempt log (si, sj, accepted) when the counters do not fit
     bool mix_pre_launched = false, mix_no_pre = false;   // swap-all: the hoisted path ran last (its overflow flag is pending) / is off for the repeat
     double mix_acc_rate = -1.0;        // accepted / proposed of the previous swap-all call (picks the kernel of the next: mix.hip) in LDS
-    float4* d_snap_pos = nullptr; float4* d_snap_vel = nullptr;   // pre-propagate state (restart attempts)
-    float4* d_fin_pos = nullptr; float4* d_fin_vel = nullptr;     // first successful result of every replica
-    float* d_snap_box = nullptr; float* d_fin_box = nullptr;      // boxes move under the barostat: same treatment
-    float4* d_pos_ref = nullptr;       // [R][Npad] reference (constrained) positions for SHAKE/SETTLE
-    long long* d_force = nullptr;      // [R][3][Npad] fixed point
-    float* d_box = nullptr;            // [R][4] lx, ly, lz, pad
+    dev_array<float4> d_snap_pos; dev_array<float4> d_snap_vel;   // pre-propagate state (restart attempts)
+    dev_array<float4> d_fin_pos; dev_array<float4> d_fin_vel;     // first successful result of every replica
+    dev_array<float> d_snap_box; dev_array<float> d_fin_box;      // boxes move under the barostat: same treatment
+    dev_array<float4> d_pos_ref;       // [R][Npad] reference (constrained) positions for SHAKE/SETTLE
+    dev_array<long long> d_force;      // [R][3][Npad] fixed point
+    dev_array<float> d_box;            // [R][4] lx, ly, lz, pad
     std::vector<double> box_host;      // [R][3]
-    int64_t* d_labels = nullptr;       // [R_global]
+    dev_array<int64_t> d_labels;       // [R_global]
     std::vector<int64_t> labels;
-    double* d_ukl = nullptr;           // [R_global][K]
-    double* d_potential = nullptr;     // [R]
-    double* d_epart = nullptr; int n_epart = 0;   // per-replica per-block energy partials
-    double* d_kinetic = nullptr;       // [R]
-    int* d_nan = nullptr;              // [R]
-    long long* d_cmm = nullptr;        // [2][R][4] double-buffered fixed-point momentum accumulators
+    dev_array<double> d_ukl;           // [R_global][K]
+    dev_array<double> d_potential;     // [R]
+    dev_array<double> d_epart; int n_epart = 0;   // per-replica per-block energy partials
+    dev_array<double> d_kinetic;       // [R]
+    dev_array<int> d_nan;              // [R]
+    dev_array<long long> d_cmm;        // [2][R][4] double-buffered fixed-point momentum accumulators
     bool forces_valid = false;
     bool force_zeroed = false;         // the last integrator chain already cleared d_force (skip the memset)
 
-    // ---- PME ------------------------------------------------------------------------
-    void* pme = nullptr;               // opaque (pme.hip)
+    // ---- feature tables, each defined in the file that owns it ------------------------------
+    remd_table<pme_state> pme;         // pme.hip
+    remd_table<nb_tables> nb;          // forces.hip: the nonbonded setup
+    remd_table<unit_tables> units;     // integrate.hip: constraint units
+    remd_table<nocutoff_tables> nc;    // nocutoff.hip
+    remd_table<gbsa_tables> gb;        // gbsa.hip
+    remd_table<region_tables> reg;     // alch_regions.hip
+    remd_table<rst_tables> rst;        // restraints.hip
+    remd_table<mix_pre_buffers> mix_pre;   // mix.hip: the hoisted swap-all path
 
     // ---- mixing scratch ----------------------------------------------------------------
-    unsigned long long* d_nacc = nullptr; unsigned long long* d_nprop = nullptr; int stats_K = 0;
-    double* d_logw = nullptr; double* d_logP = nullptr; double* d_ukl_tmp = nullptr; size_t ukl_tmp_n = 0;
+    dev_array<unsigned long long> d_nacc; dev_array<unsigned long long> d_nprop; int stats_K = 0;
+    dev_array<double> d_logw; dev_array<double> d_logP; dev_array<double> d_ukl_tmp;
 
     // ---- timing / profiling -------------------------------------------------------------
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -262,7 +325,7 @@ struct remd_ctx {
     // publishes the fork, a one-wavefront kernel at the head of the second stream waits for it, and the mirror image at the
     // join -- an event record / wait costs ~6 us of command-processor latency on the critical path, twice per step.
     // sync_events: the events instead, the fall-back of a handle whose polled wait ran out (api.hip: remd_recover_device_flag).
-    unsigned int* d_sync = nullptr; unsigned int sync_seq = 0; unsigned int fork_seq_pending = 0; bool sync_events = false;
+    dev_array<unsigned int> d_sync; unsigned int sync_seq = 0; unsigned int fork_seq_pending = 0; bool sync_events = false;
     // remd_run_steps: the launch that follows a force evaluation on the main stream is always an integrator chain, so the
     // join is polled in that kernel's prologue (join_deferred = sequence number to wait for) instead of a kernel of its own
     bool defer_join_ok = false; unsigned int join_deferred = 0;
@@ -286,17 +349,17 @@ struct remd_ctx {
     int phases_req = 0; int phases_last = 1;
     std::vector<remd_ctx*> phase; remd_ctx* parent = nullptr; int seen_parent_box = -1; long long ids_version = 0, seen_parent_ids = -1;     // (child: the parent's box_version its boxes were taken at)
     long long config_version = 0, phase_config = -1;      // children are rebuilt when a setter has run since they were made
-    remd_desc_store* sysdesc = nullptr;
+    std::unique_ptr<remd_desc_store> sysdesc;
     std::vector<int64_t> noise_id_host;                   // remd_set_replica_ids, for the children's slices
     bool borrowed_stream2 = false;     // stream2 belongs to another handle (remd_adopt_streams): not destroyed with this one
-    unsigned long long* d_chain_own = nullptr;   // [2] profiling: sum of (end - flag seen) wall-clock ticks of workgroup (0, 0), launches
-    unsigned long long* d_chain_sync = nullptr; unsigned int chain_sync_epoch = 0; long long chain_sync_key = -1;    // [2][R][workgroups][3] epoch-tagged partial momentum sums of the 'M' token (integrate.hip)
+    dev_array<unsigned long long> d_chain_own;   // [2] profiling: sum of (end - flag seen) wall-clock ticks of workgroup (0, 0), launches
+    dev_array<unsigned long long> d_chain_sync; unsigned int chain_sync_epoch = 0; long long chain_sync_key = -1;    // [2][R][workgroups][3] epoch-tagged partial momentum sums of the 'M' token (integrate.hip)
     bool cbins_ready = false;          // the chain launched last binned the atoms for the PME pass of the evaluation that follows
     hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; bool pme_concurrent = false;
     // sharding without a Python host (comm.hip): an RCCL communicator over the ranks of one replica-exchange run
     void* comm = nullptr; int comm_rank = 0, comm_world = 1;
     std::vector<long long> comm_begin, comm_count;   // every rank's block of replicas, exchanged when the local block changes
-    long long* d_comm_part = nullptr; bool comm_part_current = false;
+    dev_array<long long> d_comm_part; bool comm_part_current = false;
     double t_prop = 0, t_energy = 0, t_mix = 0;
     int profiling = 0;                 // 0 off, 1 filtered class only, 2 all classes
     std::string prof_filter = "nonbonded";
@@ -304,6 +367,11 @@ struct remd_ctx {
     struct pending_t { std::string name; hipEvent_t a, b; };
     std::vector<pending_t> prof_pending;
     std::map<std::string, remd_profile_entry> prof;
+
+    remd_ctx() = default;
+    remd_ctx(const remd_ctx&) = delete;
+    remd_ctx& operator=(const remd_ctx&) = delete;
+    ~remd_ctx();                       // api.hip: the phases, the communicator, pending profiling events, then the streams
 };
 
 #define REMD_CHECK(h, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { \
@@ -316,18 +384,6 @@ void remd_comm_release(remd_ctx* h);      // comm.hip
 // profiling wrapper: brackets a launch with HIP events recorded on the handle's stream.  Nothing is
 // synchronised at launch time; the pairs are resolved in remd_profile_get().  Level 1 records only
 // the class named by prof_filter (bench.py: the dominant kernel), level 2 records every class.
-// Per-handle side tables (defined in the .hip files that own them).  Distinct handles may be used from distinct threads
-// (include/remd_hip.h): look-ups and insertions are serialised, and std::map never moves its elements, so a reference
-// obtained here stays valid until the handle itself is destroyed.
-template <typename T>
-struct handle_table {
-    std::mutex m;
-    std::map<remd_ctx*, T> map;
-    T& operator[](remd_ctx* h) { std::lock_guard<std::mutex> l(m); return map[h]; }
-    T* find(remd_ctx* h) { std::lock_guard<std::mutex> l(m); auto it = map.find(h); return it == map.end() ? nullptr : &it->second; }
-    void erase(remd_ctx* h) { std::lock_guard<std::mutex> l(m); map.erase(h); }
-};
-
 struct remd_prof_scope {
     remd_ctx* h; const char* name; hipEvent_t a = nullptr; bool on = false; hipStream_t st;
     remd_prof_scope(remd_ctx* h_, const char* n, hipStream_t stream = (hipStream_t)-1) : h(h_), name(n) {
@@ -384,17 +440,15 @@ void remd_nb_invalidate_sort(remd_ctx* h);            // the next force evaluati
 #define REMD_FG_RECIPROCAL 5
 #define REMD_FG_RESTRAINT 6      /* receptor-ligand restraints (restraints.hip), force group remd_ctx::rst_group */
 // nocutoff.hip: NonbondedForce with NoCutoff (vacuum systems)
-void remd_nocutoff_release(remd_ctx* h);
 int remd_nocutoff_build(remd_ctx* h, const remd_system_desc* d);
 int remd_nocutoff_forces(remd_ctx* h, bool with_energy, int ep_slot);
 int remd_nocutoff_info(remd_ctx* h, const float4** param, const unsigned int** excl, int* words, int* n_exc, const int** exc_atoms, const float4** exc_par);
 // gbsa.hip: implicit solvent of a NoCutoff system
-void remd_gbsa_release(remd_ctx* h);
 int remd_gbsa_forces(remd_ctx* h, bool with_energy, int ep_slot);
 int remd_gbsa_ukl(remd_ctx* h, double* d_alch /*[R][K], added to*/);
 int remd_regions_state_le(remd_ctx* h, int k, int g, double* le);
 // alch_regions.hip: custom forces of general alchemical regions
-void remd_regions_release(remd_ctx* h);
+void remd_regions_release(remd_ctx* h);                // drops the regions (remd_set_system)
 int remd_regions_clone(remd_ctx* parent, remd_ctx* child);
 int remd_gbsa_clone(remd_ctx* parent, remd_ctx* child);
 int remd_regions_forces(remd_ctx* h, bool with_energy, int ep_slot);
@@ -413,5 +467,4 @@ int remd_restraints_ukl(remd_ctx* h, double* d_rows /*[R][K], added to*/);
 
 // ---- pme.hip ----------------------------------------------------------------------------
 int remd_pme_setup(remd_ctx* h);
-int remd_pme_destroy(remd_ctx* h);
 int remd_pme_forces(remd_ctx* h, bool with_energy, hipStream_t st, int part = 3);   // part 1: bin .. inverse z, part 2: gather (+ energy)

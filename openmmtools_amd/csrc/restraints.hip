@@ -22,32 +22,17 @@ struct rst_param {
     double K, r0;
 };
 
+}  // namespace
+
 struct rst_tables {
     int n = 0, K = 0; long long lam_version = -1;     // (lam belongs to the states of that remd_set_states)
     std::vector<rst_param> par; std::vector<int> atoms; std::vector<double> w; std::vector<double> lam;   // host copies (clones)
-    rst_param* d_par = nullptr; int* d_atoms = nullptr; double* d_w = nullptr; double* d_lam = nullptr;
-    double* d_E = nullptr; int E_R = 0;
+    dev_array<rst_param> d_par; dev_array<int> d_atoms; dev_array<double> d_w; dev_array<double> d_lam;
+    dev_array<double> d_E;             // [R][n]
 };
+void remd_table_deleter::operator()(rst_tables* t) const { delete t; }
 
-handle_table<rst_tables> g_rst;
-
-void dfree_(void* p) { if (p) hipFree(p); }
-
-void release(rst_tables& t)
-{
-    dfree_(t.d_par); dfree_(t.d_atoms); dfree_(t.d_w); dfree_(t.d_lam); dfree_(t.d_E);
-    t = rst_tables{};
-}
-
-template <typename T>
-int upload(remd_ctx* h, T*& d, const std::vector<T>& v)
-{
-    dfree_(d); d = nullptr;
-    if (v.empty()) return 0;
-    REMD_CHECK(h, hipMalloc(&d, sizeof(T) * v.size()));
-    REMD_CHECK(h, hipMemcpy(d, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
-    return 0;
-}
+namespace {
 
 __device__ __forceinline__ double wave_sum_d(double v)
 {
@@ -149,20 +134,18 @@ __global__ void restraint_ukl_kernel(int R, int K, int n, const double* __restri
 
 int ensure_E(remd_ctx* h, rst_tables& t)
 {
-    if (t.E_R == h->R && t.d_E) return 0;
-    dfree_(t.d_E); t.d_E = nullptr; t.E_R = 0;
-    REMD_CHECK(h, hipMalloc(&t.d_E, sizeof(double) * (size_t)h->R * t.n));
+    if (t.d_E.size() == (size_t)h->R * t.n) return 0;
+    REMD_TRY(t.d_E.alloc(h, (size_t)h->R * t.n));
     REMD_CHECK(h, hipMemset(t.d_E, 0, sizeof(double) * (size_t)h->R * t.n));
-    t.E_R = h->R;
     return 0;
 }
 
 int set_tables(remd_ctx* h, rst_tables& t)
 {
     int rc;
-    if ((rc = upload(h, t.d_par, t.par)) || (rc = upload(h, t.d_atoms, t.atoms)) || (rc = upload(h, t.d_w, t.w)) ||
-        (rc = upload(h, t.d_lam, t.lam))) return rc;
-    t.E_R = 0;
+    if ((rc = t.d_par.upload(h, t.par)) || (rc = t.d_atoms.upload(h, t.atoms)) || (rc = t.d_w.upload(h, t.w)) ||
+        (rc = t.d_lam.upload(h, t.lam))) return rc;
+    t.d_E.reset();
     return 0;
 }
 
@@ -170,17 +153,16 @@ int set_tables(remd_ctx* h, rst_tables& t)
 
 void remd_restraints_release(remd_ctx* h)
 {
-    rst_tables* t = g_rst.find(h);
-    if (t) { hipStreamSynchronize(h->stream); release(*t); g_rst.erase(h); }
+    if (h->rst) { hipStreamSynchronize(h->stream); h->rst.reset(); }
     h->n_restraints = 0; h->rst_group = 0;
 }
 
 int remd_restraints_clone(remd_ctx* parent, remd_ctx* child)
 {
-    rst_tables* t = g_rst.find(parent);
+    const rst_tables* t = parent->rst.get();
     if (!t || parent->n_restraints == 0) return 0;
-    rst_tables& c = g_rst[child];
-    release(c);
+    child->rst.reset(new rst_tables());
+    rst_tables& c = *child->rst;
     c.n = t->n; c.K = t->K; c.lam_version = t->lam_version == parent->states_version ? child->states_version : -1; c.par = t->par; c.atoms = t->atoms; c.w = t->w; c.lam = t->lam;
     hipSetDevice(child->device);
     const int rc = set_tables(child, c);
@@ -193,7 +175,7 @@ int remd_restraints_clone(remd_ctx* parent, remd_ctx* child)
 // the restraint launch of a force evaluation (forces.hip: on the stream of the listed terms)
 int remd_restraints_forces(remd_ctx* h, bool with_energy, int ep_slot, hipStream_t st)
 {
-    rst_tables* tp = g_rst.find(h);
+    rst_tables* tp = h->rst.get();
     if (!tp || h->n_restraints == 0) return 0;
     rst_tables& t = *tp;
     if (t.K != h->K || t.lam_version != h->states_version)
@@ -212,10 +194,10 @@ int remd_restraints_forces(remd_ctx* h, bool with_energy, int ep_slot, hipStream
 // the restraints' share of the u_kl rows, added to what the assembly wrote (behind the energy evaluation on the main stream)
 int remd_restraints_ukl(remd_ctx* h, double* d_rows)
 {
-    rst_tables* tp = g_rst.find(h);
+    rst_tables* tp = h->rst.get();
     if (!tp || h->n_restraints == 0) return 0;
     rst_tables& t = *tp;
-    if (t.K != h->K || t.lam_version != h->states_version || !t.d_E || t.E_R != h->R) return remd_fail(h, -1, "restraints: u_kl without a current energy evaluation");
+    if (t.K != h->K || t.lam_version != h->states_version || t.d_E.size() != (size_t)h->R * t.n) return remd_fail(h, -1, "restraints: u_kl without a current energy evaluation");
     const int n = h->R * h->K;
     hipLaunchKernelGGL(restraint_ukl_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->R, h->K, t.n, t.d_lam, t.d_E, h->d_beta,
                        h->d_labels, h->r_begin, d_rows);
@@ -267,10 +249,9 @@ int remd_set_restraints(remd_handle h, const remd_restraint_desc* desc, int n)
     }
     t.K = h->K; t.lam_version = h->states_version;
     t.lam.assign((size_t)std::max(h->K, 0) * n, 1.0);
-    rst_tables& dst = g_rst[h];
-    dst = t;
-    int rc = set_tables(h, dst);
-    if (rc) { release(dst); g_rst.erase(h); return rc; }
+    int rc = set_tables(h, t);
+    if (rc) return rc;
+    h->rst.reset(new rst_tables(std::move(t)));
     h->n_restraints = n; h->rst_group = desc[0].force_group;
     return 0;
 }
@@ -278,14 +259,14 @@ int remd_set_restraints(remd_handle h, const remd_restraint_desc* desc, int n)
 int remd_set_restraint_lambdas(remd_handle h, const double* lambda)
 {
     if (!h || !lambda) return remd_fail(h, -1, "remd_set_restraint_lambdas: bad arguments");
-    rst_tables* t = g_rst.find(h);
+    rst_tables* t = h->rst.get();
     if (!t || h->n_restraints == 0) return remd_fail(h, -1, "remd_set_restraint_lambdas: no restraints (remd_set_restraints)");
     if (h->K <= 0) return remd_fail(h, -1, "remd_set_restraint_lambdas: call remd_set_states first");
     hipSetDevice(h->device);
     hipStreamSynchronize(h->stream);
     t->K = h->K; t->lam_version = h->states_version;
     t->lam.assign(lambda, lambda + (size_t)h->K * t->n);
-    int rc = upload(h, t->d_lam, t->lam);
+    int rc = t->d_lam.upload(h, t->lam);
     if (rc) return rc;
     h->config_version++;
     return 0;
@@ -294,7 +275,7 @@ int remd_set_restraint_lambdas(remd_handle h, const double* lambda)
 int remd_get_restraint_energies(remd_handle h, double* out)
 {
     if (!h || !out || h->R <= 0) return remd_fail(h, -1, "remd_get_restraint_energies: bad arguments");
-    rst_tables* t = g_rst.find(h);
+    rst_tables* t = h->rst.get();
     if (!t || h->n_restraints == 0) return remd_fail(h, -1, "remd_get_restraint_energies: no restraints (remd_set_restraints)");
     hipSetDevice(h->device);
     int rc = remd_compute_forces(h, true); if (rc) return rc;

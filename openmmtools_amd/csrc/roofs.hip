@@ -65,8 +65,8 @@ extern "C" int remd_roof_microbench(remd_handle h, double* stream_gb_per_s, doub
     float ms = 0.f;
     if (stream_gb_per_s) {
         const size_t n4 = (size_t)1 << 25;                          // 3 arrays x 512 MiB: past the 256 MiB Infinity Cache
-        float4 *a = nullptr, *b = nullptr, *c = nullptr;
-        REMD_CHECK(h, hipMalloc(&a, n4 * sizeof(float4))); REMD_CHECK(h, hipMalloc(&b, n4 * sizeof(float4))); REMD_CHECK(h, hipMalloc(&c, n4 * sizeof(float4)));
+        dev_array<float4> a, b, c;
+        REMD_TRY(a.alloc(h, n4)); REMD_TRY(b.alloc(h, n4)); REMD_TRY(c.alloc(h, n4));
         REMD_CHECK(h, hipMemsetAsync(a, 0, n4 * sizeof(float4), h->stream)); REMD_CHECK(h, hipMemsetAsync(b, 0, n4 * sizeof(float4), h->stream));
         const int reps = 10;
         hipLaunchKernelGGL(roof_triad_kernel, dim3(256 * 16), dim3(256), 0, h->stream, a, b, c, 1.5f, n4);     // warm-up
@@ -76,11 +76,10 @@ extern "C" int remd_roof_microbench(remd_handle h, double* stream_gb_per_s, doub
         REMD_CHECK(h, hipEventSynchronize(e1));
         hipEventElapsedTime(&ms, e0, e1);
         *stream_gb_per_s = 3.0 * (double)n4 * sizeof(float4) * reps / (ms * 1e-3) / 1e9;
-        hipFree(a); hipFree(b); hipFree(c);
     }
-    float* out = nullptr;
+    dev_array<float> out;
     const int blocks = 256 * 8, iters = 8192;
-    REMD_CHECK(h, hipMalloc(&out, sizeof(float) * blocks * 256));
+    REMD_TRY(out.alloc(h, blocks * 256));
     if (fma_tflop_per_s) {
         hipLaunchKernelGGL(roof_fma_kernel, dim3(blocks), dim3(256), 0, h->stream, out, 64, 1.0f, (unsigned long long*)nullptr);
         hipEventRecord(e0, h->stream);
@@ -99,7 +98,6 @@ extern "C" int remd_roof_microbench(remd_handle h, double* stream_gb_per_s, doub
         hipEventElapsedTime(&ms, e0, e1);
         *pk_fma_tflop_per_s = 4.0 * 16.0 * (double)iters * blocks * 256 / (ms * 1e-3) / 1e12;
     }
-    hipFree(out);
     hipEventDestroy(e0); hipEventDestroy(e1);
     return 0;
 }
@@ -110,16 +108,15 @@ extern "C" int remd_roof_clock_ghz(remd_handle h, double* ghz_under_fma_load)
 {
     if (!h || !ghz_under_fma_load) return -1;
     hipSetDevice(h->device);
-    float* out = nullptr; unsigned long long* clk = nullptr;
+    dev_array<float> out; dev_array<unsigned long long> clk;
     const int blocks = 256 * 8, iters = 8192;
-    REMD_CHECK(h, hipMalloc(&out, sizeof(float) * blocks * 256));
-    REMD_CHECK(h, hipMalloc(&clk, 2 * sizeof(unsigned long long)));
+    REMD_TRY(out.alloc(h, blocks * 256));
+    REMD_TRY(clk.alloc(h, 2));
     hipLaunchKernelGGL(roof_fma_kernel, dim3(blocks), dim3(256), 0, h->stream, out, 64, 1.0f, (unsigned long long*)nullptr);
     hipLaunchKernelGGL(roof_fma_kernel, dim3(blocks), dim3(256), 0, h->stream, out, iters, 1.0f, clk);
     unsigned long long hc[2] = {0, 0};
     REMD_CHECK(h, hipMemcpyAsync(hc, clk, sizeof(hc), hipMemcpyDeviceToHost, h->stream));
     REMD_CHECK(h, hipStreamSynchronize(h->stream));
-    hipFree(out); hipFree(clk);
     *ghz_under_fma_load = hc[1] > 0 ? (double)hc[0] / ((double)hc[1] * 10.0) : 0.0;     // cycles / (ticks * 10 ns) in GHz
     return 0;
 }
@@ -201,8 +198,8 @@ extern "C" int remd_roof_pair_step(remd_handle h, int waves_per_simd, int chains
     const int wg_per_cu = waves_per_simd;
     const size_t lds = std::max((size_t)4096, (size_t)(160 * 1024 / wg_per_cu - 1024) / 256 * 256);
     const int blocks = n_cu * wg_per_cu, iters = 4096;
-    float* out = nullptr;
-    REMD_CHECK(h, hipMalloc(&out, sizeof(float) * (size_t)blocks * 256));
+    dev_array<float> out;
+    REMD_TRY(out.alloc(h, (size_t)blocks * 256));
     hipEvent_t e0, e1;
     REMD_CHECK(h, hipEventCreate(&e0)); REMD_CHECK(h, hipEventCreate(&e1));
     auto kern = chains == 1 ? roof_pair_step_kernel<1> : roof_pair_step_kernel<2>;
@@ -215,7 +212,7 @@ extern "C" int remd_roof_pair_step(remd_handle h, int waves_per_simd, int chains
     REMD_CHECK(h, hipEventSynchronize(e1));
     float ms = 0.f;
     hipEventElapsedTime(&ms, e0, e1);
-    hipFree(out); hipEventDestroy(e0); hipEventDestroy(e1);
+    hipEventDestroy(e0); hipEventDestroy(e1);
     // every SIMD ran waves_per_simd wavefronts x iters x chains steps
     const double steps_per_simd = (double)waves_per_simd * iters * chains;
     if (us_total) *us_total = 1e3 * ms;
