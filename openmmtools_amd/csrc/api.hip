@@ -7,15 +7,7 @@
 #include <mutex>
 #include <cstdlib>
 
-int remd_check_finite(remd_ctx* h);
-int remd_assemble_ukl(remd_ctx* h, double* d_rows);
-int remd_nb_required_epart(remd_ctx* h);
-void remd_nb_reset_accumulators(remd_ctx* h); // forces.hip
-void remd_nb_invalidate_sort(remd_ctx* h);    // forces.hip
-int remd_test_fft3d_impl(remd_ctx* h, int nx, int ny, int nz, float* data, int inverse);
-void remd_nb_tune_resolve(remd_ctx* h);
 static int remd_check_device_flags(remd_ctx* h, const char* where, bool may_retry = false);
-const unsigned* remd_mix_pending_flag(remd_ctx* h);      // mix.hip
 
 static std::mutex g_err_mutex;
 static std::string g_last_error;
@@ -343,7 +335,7 @@ int remd_set_replicas(remd_handle h, int R_global, int r_begin, int R_local, con
     for (int r = 1; r < R_local; ++r) for (int k = 0; k < 3; ++k) if (hb[4 * r + k] != hb[k]) h->box_uniform = false;
     h->box_version++;
     h->forces_valid = false; h->force_zeroed = false;
-    h->cbins_ready = false;              // (bins a chain filled for positions that are gone)
+    h->next.cbins_ready = false;         // (bins a chain filled for positions that are gone)
     h->comm_part_current = false;       // (the ranks exchange their blocks again at the next all-gather)
     remd_nb_invalidate_sort(h);         // (a molecule order made for other coordinates overflows the cluster lists)
     // (the mesh buffers follow the replica count; a call that only replaces coordinates keeps them -- one handle per compatibility
@@ -415,7 +407,7 @@ int remd_copy_replicas(remd_handle dst, const int32_t* dst_slot, remd_handle src
     REMD_CHECK(dst, hipStreamSynchronize(dst->stream));
     if (pos || box) {
         dst->forces_valid = false; dst->force_zeroed = false;
-        dst->cbins_ready = false;
+        dst->next.cbins_ready = false;
         dst->comm_part_current = false;
         remd_nb_invalidate_sort(dst);
     }
@@ -492,7 +484,7 @@ static int remd_recover_device_flag(remd_ctx* h, unsigned int f, const char* whe
         return remd_fail(h, -2, std::string(where) + ": the Monte Carlo barostat proposed a periodic box smaller than twice the nonbonded cutoff "
                                 "(for a PME System: the Coulomb range of the Ewald split, remd_set_coulomb_cutoff) -- the box has shrunk too far "
                                 "for this cutoff (OpenMM: \"The periodic box size has decreased to less than twice the nonbonded cutoff\")");
-    h->join_deferred = 0; h->cbins_ready = false;
+    h->next.reset();
     remd_nb_invalidate_sort(h);
     remd_nb_reset_accumulators(h);
     std::string what;
@@ -510,8 +502,6 @@ static int remd_recover_device_flag(remd_ctx* h, unsigned int f, const char* whe
 }
 
 // ---- phases: one handle's replicas as blocks whose MD steps take turns (remd_internal.h: remd_ctx::phase) -------------------------------
-int remd_propagate_many(remd_handle* hs, int32_t n, int64_t iteration, int32_t* nan_flags);
-
 int remd_set_phases(remd_handle h, int32_t n)
 {
     if (!h || n < 0 || n > 2) return remd_fail(h, -1, "remd_set_phases: 0 (by rule), 1 (off) or 2");
@@ -699,7 +689,7 @@ static int remd_propagate_phased(remd_ctx* h, int P, int64_t iteration, int32_t*
         // do without phases: the blocks' trajectories are those of the one-block path bit for bit
         REMD_CHECK(h, hipMemcpyAsync(c->d_force, h->d_force + 3 * (size_t)r0[p] * row, sizeof(long long) * 3 * row * cnt, hipMemcpyDeviceToDevice, c->stream));
         c->forces_valid = h->forces_valid; c->force_zeroed = h->force_zeroed;
-        c->cbins_ready = false; c->join_deferred = 0; c->fold_pending = false;
+        c->next.reset();
         if (h->baro_frequency > 0) {
             // the barostat's per-replica state (volume step, adaptation window, totals) and the handle's step / attempt counters travel
             // with the replicas: the blocks draw and decide what the one-block path draws and decides (Philox by global replica and attempt)
@@ -729,7 +719,7 @@ static int remd_propagate_phased(remd_ctx* h, int P, int64_t iteration, int32_t*
         if (h->phase[0]->baro_attempts != h->baro_attempts) { h->box_uniform = false; h->box_version++; }
         h->baro_steps = h->phase[0]->baro_steps; h->baro_attempts = h->phase[0]->baro_attempts;
     }
-    h->forces_valid = false; h->force_zeroed = false; h->cbins_ready = false; h->join_deferred = 0; h->fold_pending = false;
+    h->forces_valid = false; h->force_zeroed = false; h->next.reset();
     remd_nb_invalidate_sort(h);
     hipEventRecord(h->ev1, h->stream);
     REMD_CHECK(h, hipStreamSynchronize(h->stream));

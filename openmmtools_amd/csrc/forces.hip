@@ -128,16 +128,14 @@ __global__ void remd_spin_wait_kernel(const unsigned int* flag, unsigned int seq
 }
 void remd_launch_join_wait(remd_ctx* h)      // a deferred join nobody consumed: wait for it now
 {
-    if (h->fold_pending) {
+    const remd_handover::wait_t w = h->next.take_wait();
+    if (w.fold.done) {
         // no chain took it (remd_fold_args): the scatter is the direct-space stream's last launch -- an event is enough here
         // (end of a propagation, once per call)
         hipEventRecord(h->ev_join, h->stream2);
         hipStreamWaitEvent(h->stream, h->ev_join, 0);
-        h->fold_pending = false;
     }
-    if (!h->join_deferred) return;
-    hipLaunchKernelGGL(remd_spin_wait_kernel, dim3(1), dim3(64), 0, h->stream, h->d_sync + 1, h->join_deferred, h->d_sync + 2);
-    h->join_deferred = 0;
+    if (w.seq) hipLaunchKernelGGL(remd_spin_wait_kernel, dim3(1), dim3(64), 0, h->stream, h->d_sync + 1, w.seq, h->d_sync + 2);
 }
 __global__ void remd_signal_kernel(unsigned int* flag, unsigned int seq)
 {
@@ -1649,19 +1647,9 @@ static int update_replica_lambdas(remd_ctx* h, nb_tables& t)
     return 0;
 }
 
-// per-tile union lists of one (sub-)system
-static void launch_list_build(remd_ctx* h, nb_tables& t, bool lj)
-{
-    const int ncl = lj ? t.NLpad / 8 : ((h->N + 63) / 64) * 8;
-    hipLaunchKernelGGL(build_sci_list_kernel, dim3(ncl / 8, h->R), dim3(64), 0, h->stream, ncl, lj ? t.lj_cap : t.cl_cap,
-                       (!lj && t.method == NB_EWALD) ? t.p.rcc2 : t.p.rc2,
-                       lj ? t.d_lj_cl_c : t.d_cl_c, lj ? t.d_lj_cl_h : t.d_cl_h, lj ? t.d_lj_tile_c : t.d_tile_c, lj ? t.d_lj_tile_h : t.d_tile_h,
-                       h->d_box, lj ? t.d_lj_sci_list : t.d_sci_list, lj ? t.d_lj_sci_count : t.d_sci_count);
-}
-
 // sorted order (refreshed every resort_interval evaluations), sorted positions + bounding boxes and the super-cluster
-// lists (every evaluation) of the cluster-pair path
-static int ensure_sorted(remd_ctx* h, nb_tables& t)
+// lists (every evaluation) of the cluster-pair path, on stream st
+static int ensure_sorted(remd_ctx* h, nb_tables& t, hipStream_t st)
 {
     if (!t.sorting || t.n_groups <= 0) return 0;
     const int ntile = (h->N + 63) / 64;
@@ -1679,7 +1667,7 @@ static int ensure_sorted(remd_ctx* h, nb_tables& t)
         REMD_TRY(t.d_tile_h.alloc(h, (size_t)h->R * ntile));
         t.d_pair_done.reset();
         REMD_TRY(t.d_pair_done.alloc(h, 16 * h->R));       // one arrival counter per replica, 64 bytes apart
-        REMD_CHECK(h, hipMemsetAsync(t.d_pair_done, 0, sizeof(unsigned int) * 16 * h->R, h->stream));
+        REMD_CHECK(h, hipMemsetAsync(t.d_pair_done, 0, sizeof(unsigned int) * 16 * h->R, st));
         t.pair_done_target = 0;
         t.d_cl_c.reset(); t.d_cl_h.reset();
         t.d_sci_list.reset(); t.d_sci_count.reset(); t.d_excl.reset(); t.d_sforce.reset(); t.d_lj_sforce.reset();
@@ -1696,10 +1684,10 @@ static int ensure_sorted(remd_ctx* h, nb_tables& t)
             REMD_TRY(t.d_tile_of_rank.alloc(h, (size_t)h->R * ntile));
             REMD_TRY(t.d_excl.alloc(h, (size_t)h->R * ncl * t.excl_W));
             REMD_TRY(t.d_sforce.alloc(h, n * 3));
-            REMD_CHECK(h, hipMemsetAsync(t.d_sforce, 0, sizeof(long long) * n * 3, h->stream));
+            REMD_CHECK(h, hipMemsetAsync(t.d_sforce, 0, sizeof(long long) * n * 3, st));
             if (!t.d_queue) {
                 REMD_TRY(t.d_queue.alloc(h, 4));
-                REMD_CHECK(h, hipMemsetAsync(t.d_queue, 0, 4 * sizeof(unsigned int), h->stream));
+                REMD_CHECK(h, hipMemsetAsync(t.d_queue, 0, 4 * sizeof(unsigned int), st));
             }
         }
         if (cl && t.lj_split) {
@@ -1723,13 +1711,13 @@ static int ensure_sorted(remd_ctx* h, nb_tables& t)
             REMD_TRY(t.d_lj_sci_count.alloc(h, (size_t)h->R * (ncl_lj / 8)));
             REMD_TRY(t.d_lj_excl.alloc(h, (size_t)h->R * ncl_lj * t.lj_excl_W));
             REMD_TRY(t.d_lj_sforce.alloc(h, nl * 3));
-            REMD_CHECK(h, hipMemsetAsync(t.d_lj_sforce, 0, sizeof(long long) * nl * 3, h->stream));
+            REMD_CHECK(h, hipMemsetAsync(t.d_lj_sforce, 0, sizeof(long long) * nl * 3, st));
         }
         t.sort_R = h->R; t.evals_since_sort = 1 << 30;
     }
     const bool split = cl && t.lj_split;
     if (t.evals_since_sort >= t.resort_interval) {
-        remd_prof_scope ps(h, "nb_sort");
+        remd_prof_scope ps(h, "nb_sort", st);
         // cells of the molecule order: 2^b per box edge with an edge of ~0.11 nm (b from the longest edge of the first replica's box, as
         // the host mirrors it; 32 per edge on the headline system, 64 on DHFR: profiles/r06_35_hilbert_cells.txt), along the Hilbert curve
         // (the Z-order curve on cells of 0.45 nm, used until round 6, was removed after that measurement).  A property of the handle:
@@ -1741,30 +1729,30 @@ static int ensure_sorted(remd_ctx* h, nb_tables& t)
         }
         if (t.n_groups < 8192) {
             const size_t lds = sizeof(int) * 4 * (size_t)t.n_groups;
-            hipLaunchKernelGGL(sort_groups_kernel, dim3(h->R), dim3(1024), lds, h->stream, t.n_groups, h->N, h->Npad, t.d_grp_first,
+            hipLaunchKernelGGL(sort_groups_kernel, dim3(h->R), dim3(1024), lds, st, t.n_groups, h->N, h->Npad, t.d_grp_first,
                                t.d_grp_size, h->d_pos, h->d_box, t.d_order, t.sort_hbits);
         } else {
             const size_t need = (size_t)h->R * 5 * t.n_groups;
             REMD_TRY(t.d_sort_scratch.grow(h, need));
-            hipLaunchKernelGGL(sort_groups_large_kernel, dim3(h->R), dim3(1024), 0, h->stream, t.n_groups, h->N, h->Npad, t.d_grp_first,
+            hipLaunchKernelGGL(sort_groups_large_kernel, dim3(h->R), dim3(1024), 0, st, t.n_groups, h->N, h->Npad, t.d_grp_first,
                                t.d_grp_size, h->d_pos, h->d_box, t.d_order, t.d_sort_scratch, t.sort_hbits);
         }
-        hipLaunchKernelGGL(gather_params_kernel, dim3((h->Npad + 255) / 256, h->R), dim3(256), 0, h->stream, h->Npad, t.p.excl_words,
+        hipLaunchKernelGGL(gather_params_kernel, dim3((h->Npad + 255) / 256, h->R), dim3(256), 0, st, h->Npad, t.p.excl_words,
                            t.d_order, t.d_param, t.d_mask, t.d_sparam, t.d_smask);
         if (split)
-            hipLaunchKernelGGL(compact_lj_kernel, dim3(h->R), dim3(1024), 0, h->stream, h->N, h->Npad, t.NL, t.NLpad, t.lj_words, t.d_order,
+            hipLaunchKernelGGL(compact_lj_kernel, dim3(h->R), dim3(1024), 0, st, h->N, h->Npad, t.NL, t.NLpad, t.lj_words, t.d_order,
                                t.d_lj_ord, t.d_param, t.d_lj_mask, t.d_lj_order, t.d_lj_sparam, t.d_lj_smask);
         if (cl) {
-            hipLaunchKernelGGL(build_excl_kernel, dim3(ntile * 8, h->R), dim3(64), 0, h->stream, h->Npad, ntile * 8, t.excl_W, t.p.excl_words,
+            hipLaunchKernelGGL(build_excl_kernel, dim3(ntile * 8, h->R), dim3(64), 0, st, h->Npad, ntile * 8, t.excl_W, t.p.excl_words,
                                t.d_smask, t.d_excl);
             if (split)
-                hipLaunchKernelGGL(build_excl_kernel, dim3(t.NLpad / 8, h->R), dim3(64), 0, h->stream, t.NLpad, t.NLpad / 8, t.lj_excl_W,
+                hipLaunchKernelGGL(build_excl_kernel, dim3(t.NLpad / 8, h->R), dim3(64), 0, st, t.NLpad, t.NLpad / 8, t.lj_excl_W,
                                    t.lj_words, t.d_lj_smask, t.d_lj_excl);
         }
         t.evals_since_sort = 0;
     }
     t.evals_since_sort++;
-    remd_prof_scope ps(h, "nb_gather");
+    remd_prof_scope ps(h, "nb_gather", st);
     if (split) {
         // main system + LJ sub-system in one gather launch and one list launch
         const int ntile_lj = t.NLpad / 64;
@@ -1777,23 +1765,25 @@ static int ensure_sorted(remd_ctx* h, nb_tables& t)
         // before the arrival -- a device-scope release writes back the XCD's whole L2 -- 90 us instead of 11.6 + 12.7; with the boxes
         // as write-through device-scope stores and no fence 23.3 us, what the two launches take: profiles/r04_h_rejected.txt,
         // profiles/r04_r_fused_list_v2.txt)
-        hipLaunchKernelGGL(gather_positions2_kernel, dim3(ntile + ntile_lj, h->R), dim3(64), 0, h->stream, ntile, ga, gb, h->Npad, h->d_pos, h->d_box);
-        hipLaunchKernelGGL(build_sci_list2_kernel, dim3(ntile + ntile_lj, h->R), dim3(64), 0, h->stream, ntile, la, lb, rc2_main, t.p.rc2, h->d_box);
+        hipLaunchKernelGGL(gather_positions2_kernel, dim3(ntile + ntile_lj, h->R), dim3(64), 0, st, ntile, ga, gb, h->Npad, h->d_pos, h->d_box);
+        hipLaunchKernelGGL(build_sci_list2_kernel, dim3(ntile + ntile_lj, h->R), dim3(64), 0, st, ntile, la, lb, rc2_main, t.p.rc2, h->d_box);
         // (the list lengths of the evaluation that re-sorted the molecules order the work items until the next re-sort: the geometry
         // of a tile changes slowly)
         if (t.evals_since_sort == 1 && t.d_tile_of_rank && ntile <= 2048)
-            hipLaunchKernelGGL(rank_tiles_kernel, dim3((ntile + 255) / 256, h->R), dim3(256), 0, h->stream, ntile, t.d_sci_count, t.d_tile_of_rank);
+            hipLaunchKernelGGL(rank_tiles_kernel, dim3((ntile + 255) / 256, h->R), dim3(256), 0, st, ntile, t.d_sci_count, t.d_tile_of_rank);
     } else {
-        hipLaunchKernelGGL(gather_positions_kernel, dim3(ntile, h->R), dim3(64), 0, h->stream, h->Npad, h->Npad, t.d_order, h->d_pos, h->d_box,
+        hipLaunchKernelGGL(gather_positions_kernel, dim3(ntile, h->R), dim3(64), 0, st, h->Npad, h->Npad, t.d_order, h->d_pos, h->d_box,
                            t.d_spos, t.d_tile_c, t.d_tile_h, cl ? t.d_cl_c : (float4*)nullptr, cl ? t.d_cl_h : (float4*)nullptr);
-        if (cl) launch_list_build(h, t, false);
+        if (cl)         // per-tile union lists
+            hipLaunchKernelGGL(build_sci_list_kernel, dim3(ntile, h->R), dim3(64), 0, st, ntile * 8, t.cl_cap, t.method == NB_EWALD ? t.p.rcc2 : t.p.rc2,
+                               t.d_cl_c, t.d_cl_h, t.d_tile_c, t.d_tile_h, h->d_box, t.d_sci_list, t.d_sci_count);
     }
     const bool debug = h->sw.debug;
     if (cl && t.evals_since_sort == 1 && (t.cl_cap < ntile * 8 || debug)) {
         // capacity check once per re-sort (the only host synchronisation of this path)
         std::vector<int> cnt((size_t)h->R * ntile);
-        REMD_CHECK(h, hipMemcpyAsync(cnt.data(), t.d_sci_count, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost, h->stream));
-        REMD_CHECK(h, hipStreamSynchronize(h->stream));
+        REMD_CHECK(h, hipMemcpyAsync(cnt.data(), t.d_sci_count, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost, st));
+        REMD_CHECK(h, hipStreamSynchronize(st));
         int mx = 0; for (int c : cnt) mx = std::max(mx, c);
         if (debug) {
             std::vector<unsigned int> ll((size_t)ntile * t.cl_cap);
@@ -1810,10 +1800,13 @@ static int ensure_sorted(remd_ctx* h, nb_tables& t)
 
 // direct-space launch: the Newton's-third-law cluster-pair kernel over the super-cluster lists (main system and, for the
 // Ewald / reaction-field methods, the LJ-only sub-system in the same launch), or the all-tile kernel when the system has no
-// sortable groups or a list outgrew its capacity
+// sortable groups or a list outgrew its capacity.  count_done: the caller wants the scatter's workgroups to count themselves done
+// for the integrator chain to poll -- no signal launch behind it; `armed` is what that chain has to poll (done = NULL: this launch
+// does not count, the caller joins another way)
 template <int METHOD, bool ENERGY>
-static int launch_nb(remd_ctx* h, nb_tables& t)
+static int launch_nb(remd_ctx* h, nb_tables& t, hipStream_t st, bool count_done, remd_fold_args& armed)
 {
+    armed = remd_fold_args();
     const int ntile = (h->N + 63) / 64;
     if (t.sorting && t.clusters && t.d_order && t.d_sci_list && t.n_groups > 0 && ntile * 8 < 65536) {
         const int ncl = ntile * 8;
@@ -1838,15 +1831,12 @@ static int launch_nb(remd_ctx* h, nb_tables& t)
                         t.d_lj_sci_list, t.d_lj_sci_count, t.d_lj_sforce, t.d_lj_sposi, nullptr};
             const int items = items_a + (t.NLpad / 64) * h->R * (ssplit / SCI_NW);
             const int persist_grid = h->sw.nb_persist_grid >= 0 ? h->sw.nb_persist_grid : t.nb_grid;
-            const int grid = (h->pme_concurrent && persist_grid > 0) ? std::min(items, persist_grid) : items;
-            // requested by remd_compute_forces (h->fold_pending): the scatter's workgroups count themselves done for the integrator
-            // chain to poll (remd_fold_args) -- no signal launch behind it
-            const bool fold = h->fold_pending && !ENERGY && t.d_pair_done;
-            if (h->fold_pending && !fold) h->fold_pending = false;
+            const int grid = (h->next.forked && persist_grid > 0) ? std::min(items, persist_grid) : items;
+            const bool fold = count_done && !ENERGY && t.d_pair_done;
             const bool tab = t.use_table && !ENERGY && SCI_EWALD(MAIN);
             const size_t tab_lds = tab ? sizeof(float4) * (size_t)t.p.ctab_n : 0;
 #define LAUNCH_SCI2(ALCHF, TABF) hipLaunchKernelGGL((nonbonded_sci2_kernel<MAIN, NB_LJ_ONLY, ENERGY, ALCHF, SCI_NW, TABF>), dim3(grid), dim3(64 * SCI_NW), \
-            tab_lds, h->stream, t.p, sa, sb, items_a, items, grid < items ? t.d_queue : (unsigned int*)nullptr, h->d_box, rl, h->d_epart, h->n_epart, h->R, \
+            tab_lds, st, t.p, sa, sb, items_a, items, grid < items ? t.d_queue : (unsigned int*)nullptr, h->d_box, rl, h->d_epart, h->n_epart, h->R, \
             (const float4*)t.d_ctab)
             if (t.has_alch) { if (tab) LAUNCH_SCI2(true, true); else LAUNCH_SCI2(true, false); }
             else { if (tab) LAUNCH_SCI2(false, true); else LAUNCH_SCI2(false, false); }
@@ -1854,20 +1844,20 @@ static int launch_nb(remd_ctx* h, nb_tables& t)
             const dim3 sgrid((h->Npad + t.NLpad + 255) / 256, h->R);
             if (fold) {
                 t.pair_done_target += sgrid.x;           // per replica
-                h->fold.done = t.d_pair_done; h->fold.target = t.pair_done_target;
+                armed.done = t.d_pair_done; armed.target = t.pair_done_target;
             }
-            hipLaunchKernelGGL(scatter_sorted_forces_kernel, sgrid, dim3(256), 0, h->stream, h->Npad,
+            hipLaunchKernelGGL(scatter_sorted_forces_kernel, sgrid, dim3(256), 0, st, h->Npad,
                                t.d_order, t.d_sforce, t.NLpad, t.d_lj_order, t.d_lj_sforce, h->d_force, h->Npad, fold ? t.d_pair_done : (unsigned int*)nullptr);
             return 0;
         }
         const bool tab1 = t.use_table && !ENERGY && SCI_EWALD(METHOD);
         const size_t tab1_lds = tab1 ? sizeof(float4) * (size_t)t.p.ctab_n : 0;
 #define LAUNCH_SCI(ALCHF, TABF) hipLaunchKernelGGL((nonbonded_sci_kernel<METHOD, ENERGY, ALCHF, SCI_NW, TABF>), dim3(items_a), dim3(64 * SCI_NW), tab1_lds, \
-            h->stream, t.p, sa, h->d_box, rl, h->d_epart, h->n_epart, h->R, (const float4*)t.d_ctab)
+            st, t.p, sa, h->d_box, rl, h->d_epart, h->n_epart, h->R, (const float4*)t.d_ctab)
         if (t.has_alch) { if (tab1) LAUNCH_SCI(true, true); else LAUNCH_SCI(true, false); }
         else { if (tab1) LAUNCH_SCI(false, true); else LAUNCH_SCI(false, false); }
 #undef LAUNCH_SCI
-        hipLaunchKernelGGL(scatter_sorted_forces_kernel, dim3((h->Npad + 255) / 256, h->R), dim3(256), 0, h->stream, h->Npad, t.d_order,
+        hipLaunchKernelGGL(scatter_sorted_forces_kernel, dim3((h->Npad + 255) / 256, h->R), dim3(256), 0, st, h->Npad, t.d_order,
                            t.d_sforce, 0, (const int*)nullptr, (long long*)nullptr, h->d_force, h->Npad);
         return 0;
     }
@@ -1880,21 +1870,28 @@ static int launch_nb(remd_ctx* h, nb_tables& t)
     const unsigned long long* mk = sorted ? t.d_smask : t.d_mask;
     const int* ord = sorted ? t.d_order : nullptr;
     if (t.has_alch)
-        hipLaunchKernelGGL((nonbonded_kernel<METHOD, ENERGY, true>), grid, dim3(64 * NB_WAVES), 0, h->stream, t.p, h->N, h->Npad, P,
+        hipLaunchKernelGGL((nonbonded_kernel<METHOD, ENERGY, true>), grid, dim3(64 * NB_WAVES), 0, st, t.p, h->N, h->Npad, P,
                            prm, mk, ord, t.d_tile_c, t.d_tile_h, h->d_box, t.d_rep_lam, t.d_partial, h->d_epart, h->n_epart, ntile);
     else
-        hipLaunchKernelGGL((nonbonded_kernel<METHOD, ENERGY, false>), grid, dim3(64 * NB_WAVES), 0, h->stream, t.p, h->N, h->Npad, P,
+        hipLaunchKernelGGL((nonbonded_kernel<METHOD, ENERGY, false>), grid, dim3(64 * NB_WAVES), 0, st, t.p, h->N, h->Npad, P,
                            prm, mk, ord, t.d_tile_c, t.d_tile_h, h->d_box, (const float*)nullptr, t.d_partial, h->d_epart, h->n_epart, ntile);
-    hipLaunchKernelGGL(nb_reduce_kernel, dim3((h->N + 255) / 256, h->R), dim3(256), 0, h->stream, h->N, h->Npad, t.p.n_jsplit,
+    hipLaunchKernelGGL(nb_reduce_kernel, dim3((h->N + 255) / 256, h->R), dim3(256), 0, st, h->N, h->Npad, t.p.n_jsplit,
                        t.d_partial, h->d_force);
     return 0;
+}
+
+template <bool ENERGY>
+static int launch_nb_method(remd_ctx* h, nb_tables& t, hipStream_t st, bool count_done, remd_fold_args& armed)
+{
+    if (t.method == NB_LJ_ONLY) return launch_nb<NB_LJ_ONLY, ENERGY>(h, t, st, count_done, armed);
+    if (t.method == NB_RF) return launch_nb<NB_RF, ENERGY>(h, t, st, count_done, armed);
+    return launch_nb<NB_EWALD, ENERGY>(h, t, st, count_done, armed);
 }
 
 // after a device-side fault: partial sums a discarded evaluation left in the sorted accumulators must not reach the next one
 void remd_nb_reset_accumulators(remd_ctx* h)
 {
     nb_tables* t = h->nb.get();
-    h->fold_pending = false;
     if (!t || h->R <= 0) return;
     if (t->d_sforce) hipMemsetAsync(t->d_sforce, 0, sizeof(long long) * 3 * (size_t)h->R * h->Npad, h->stream);
     if (t->d_lj_sforce) hipMemsetAsync(t->d_lj_sforce, 0, sizeof(long long) * 3 * (size_t)h->R * t->NLpad, h->stream);
@@ -1947,7 +1944,7 @@ void remd_nb_tune_step(remd_ctx* h, int steps_left_in_call)
     nb_tables* tp = h->nb.get();
     if (!tp || h->nb_method == REMD_NB_NONE) return;
     nb_tables& t = *tp;
-    if (h->sw.nb_persist_grid >= 0 || t.tune_state != 0 || !h->pme_concurrent || h->profiling == 2) return;
+    if (h->sw.nb_persist_grid >= 0 || t.tune_state != 0 || !h->next.forked || h->profiling == 2) return;
     if (t.tune_left == 0) {
         hipEvent_t boundary = nullptr;
         if (!t.tune_segs.empty() && !t.tune_segs.back().b) {            // close the open segment
@@ -2016,212 +2013,204 @@ int remd_nb_resident_info(remd_ctx* h, int* ok, int* method, int* has_alch, nb_p
     return 0;
 }
 
-int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask)
+// every listed term of the classes in class_mask as one table (a force-only evaluation launches them together); total: its threads
+static listed_tables listed_terms(remd_ctx* h, unsigned class_mask, int& total)
+{
+    const bool do_bond = (class_mask >> REMD_FG_BOND) & 1u, do_angle = (class_mask >> REMD_FG_ANGLE) & 1u;
+    const bool do_torsion = (class_mask >> REMD_FG_TORSION) & 1u, do_nb = (class_mask >> REMD_FG_NONBONDED) & 1u;
+    listed_tables T{};
+    T.n_bonds = do_bond ? h->n_bonds : 0; T.n_angles = do_angle ? h->n_angles : 0; T.n_torsions = do_torsion ? h->n_torsions : 0;
+    T.bond_atoms = h->d_bond_atoms; T.bond_params = h->d_bond_params;
+    T.angle_atoms = h->d_angle_atoms; T.angle_params = h->d_angle_params;
+    T.torsion_atoms = h->d_torsion_atoms; T.torsion_params = h->d_torsion_params;
+    nb_tables* it = h->nb.get();
+    if (it && h->nb_method != REMD_NB_NONE && do_nb) {
+        nb_tables& t = *it;
+        T.n_exc = t.n_exc; T.exc_atoms = t.d_exc_atoms; T.exc_params = t.d_exc_params;
+        T.n_excl = t.n_excl; T.excl_atoms = t.d_excl_atoms; T.excl_qq = t.d_excl_qq;
+        T.alpha = t.p.alpha; T.two_alpha_sqrtpi = t.p.two_alpha_sqrtpi;
+        T.exc_alch = t.d_exc_alch; T.excl_alch = t.d_excl_alch; T.rep_lam = t.has_alch ? t.d_rep_lam : nullptr;
+    }
+    total = T.n_bonds + T.n_angles + T.n_torsions + T.n_exc + T.n_excl;
+    // one (term, slot) entry per thread in atom order (REMD_LISTED_ATOMS=0: one term per thread)
+    T.n_aterm = 0; T.aterm = nullptr;
+    if (h->sw.listed_atoms && total > 0 && h->d_aterm && h->n_aterm > 0) { T.aterm = h->d_aterm; T.n_aterm = h->n_aterm; total = h->n_aterm; }
+    return T;
+}
+
+// the restraints (restraints.hip) go with the listed terms of a force-only evaluation: their launch and the ONE launch of the listed
+// terms on stream st (total = 0: the listed terms rode in the spreading launch, or there are none)
+static int launch_listed(remd_ctx* h, bool do_rst, const listed_tables& T, int total, hipStream_t st)
+{
+    if (do_rst) REMD_TRY(remd_restraints_forces(h, false, h->n_epart - 1, st));
+    if (total > 0) {
+        remd_prof_scope ps(h, "bonded", st);
+        hipLaunchKernelGGL(listed_forces_kernel, dim3((total + 255) / 256, h->R), dim3(256), 0, st, T, h->Npad, h->d_pos,
+                           h->d_box, h->d_force);
+    }
+    return 0;
+}
+
+int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask, bool chain_follows)
 {
     // class_mask: which force classes act (REMD_FG_* bits; everything unless a multiple-time-step splitting asks for the forces
     // of one force group, integrate.hip).  Energies are only defined for the full set.
     if (with_energy && (class_mask & 63u) != 63u) return remd_fail(h, -1, "energies need every force class");
-    const bool do_ext = (class_mask >> REMD_FG_EXTERNAL) & 1u, do_bond = (class_mask >> REMD_FG_BOND) & 1u;
-    const bool do_angle = (class_mask >> REMD_FG_ANGLE) & 1u, do_torsion = (class_mask >> REMD_FG_TORSION) & 1u;
+    const bool do_ext = (class_mask >> REMD_FG_EXTERNAL) & 1u;
     const bool do_nb = (class_mask >> REMD_FG_NONBONDED) & 1u, do_recip = (class_mask >> REMD_FG_RECIPROCAL) & 1u;
     const bool do_rst = h->n_restraints > 0 && ((class_mask >> REMD_FG_RESTRAINT) & 1u);
-    if (!h->force_zeroed)
-        REMD_CHECK(h, hipMemsetAsync(h->d_force, 0, sizeof(long long) * 3 * (size_t)h->Npad * h->R, h->stream));
-    h->force_zeroed = false;
-    if (with_energy)
-        REMD_CHECK(h, hipMemsetAsync(h->d_epart, 0, sizeof(double) * (size_t)h->n_epart * h->R, h->stream));
     const int R = h->R;
-#define LAUNCH_E(kern, ...) do { if (with_energy) hipLaunchKernelGGL(kern<true>, __VA_ARGS__); else hipLaunchKernelGGL(kern<false>, __VA_ARGS__); } while (0)
-    // custom forces of general alchemical regions (alch_regions.hip): part of the direct-space nonbonded class, launched here -- in
-    // front of the fork -- so that both branches of the evaluation are ordered behind them
-    if (h->n_regions > 0 && do_nb) { int rcr = remd_regions_forces(h, with_energy, h->n_epart - 2); if (rcr) return rcr; }
-    if (h->nocutoff && do_nb) { int rcn = remd_nocutoff_forces(h, with_energy, EP_NB0); if (rcn) return rcn; }
-    if (h->gbsa && do_nb) { int rcg = remd_gbsa_forces(h, with_energy, EP_NB0 + 1); if (rcg) return rcg; }
-    if (h->n_ext > 0 && do_ext) {
-        remd_prof_scope ps(h, "ext_force");
-        LAUNCH_E(ext_force_kernel, dim3(R), dim3(64), 0, h->stream, h->n_ext, h->d_ext_atoms, (float)h->ext_K, (float)h->ext_x0,
-                 h->ext_U0, h->Npad, h->d_pos, h->d_force, h->d_epart, h->n_epart);
-    }
+    nb_tables* const nbt = h->nb_method != REMD_NB_NONE ? &remd_table_of(h->nb) : nullptr;
+
+    // ---- plan: what this evaluation decides, once -------------------------------------------------------------------------
     // Two branches between the integrator chains.  The reciprocal-space pipeline is the longer one, so IT stays on the main
-    // stream directly behind the integrator; the direct-space launches go to the second stream (h->stream is swapped until
-    // the join).  Fork and join are flags in device memory polled by kernels (remd_ctx::d_sync), or events when a handle has
-    // fallen back to them (api.hip: remd_recover_device_flag).  Measured alternatives that lost their
-    // A/B and were removed in round 3 (numbers in DESIGN.md 7b): the mesh branch on the second stream, the pair kernel ahead
+    // stream directly behind the integrator; the direct-space launches go to the second stream.  Fork and join are flags in
+    // device memory polled by kernels (remd_ctx::d_sync), or events when a handle has fallen back to them (api.hip:
+    // remd_recover_device_flag).  Measured alternatives that lost their A/B and were removed in round 3 (numbers in DESIGN.md 7b): the mesh branch on the second stream, the pair kernel ahead
     // of the listed terms, the listed terms in front of the pair kernel or on a third stream, scatter + listed terms + join
     // flag in one launch.
-    bool forked = false, swapped = false;
-    struct unswap { remd_ctx* h; bool* on; ~unswap() { if (*on) std::swap(h->stream, h->stream2); } } guard{h, &swapped};
-    auto listed_terms = [&](int& total) {
-        listed_tables T{};
-        T.n_bonds = do_bond ? h->n_bonds : 0; T.n_angles = do_angle ? h->n_angles : 0; T.n_torsions = do_torsion ? h->n_torsions : 0;
-        T.bond_atoms = h->d_bond_atoms; T.bond_params = h->d_bond_params;
-        T.angle_atoms = h->d_angle_atoms; T.angle_params = h->d_angle_params;
-        T.torsion_atoms = h->d_torsion_atoms; T.torsion_params = h->d_torsion_params;
-        nb_tables* it = h->nb.get();
-        if (it && h->nb_method != REMD_NB_NONE && do_nb) {
-            nb_tables& t = *it;
-            T.n_exc = t.n_exc; T.exc_atoms = t.d_exc_atoms; T.exc_params = t.d_exc_params;
-            T.n_excl = t.n_excl; T.excl_atoms = t.d_excl_atoms; T.excl_qq = t.d_excl_qq;
-            T.alpha = t.p.alpha; T.two_alpha_sqrtpi = t.p.two_alpha_sqrtpi;
-            T.exc_alch = t.d_exc_alch; T.excl_alch = t.d_excl_alch; T.rep_lam = t.has_alch ? t.d_rep_lam : nullptr;
-        }
-        total = T.n_bonds + T.n_angles + T.n_torsions + T.n_exc + T.n_excl;
-        // one (term, slot) entry per thread in atom order (REMD_LISTED_ATOMS=0: one term per thread)
-        T.n_aterm = 0; T.aterm = nullptr;
-        if (h->sw.listed_atoms && total > 0 && h->d_aterm && h->n_aterm > 0) { T.aterm = h->d_aterm; T.n_aterm = h->n_aterm; total = h->n_aterm; }
-        return T;
-    };
-    bool listed_rode = false;
-    if (h->nb_method != REMD_NB_NONE) {      // per-replica lambdas must be current before ANY kernel reads them
-        nb_tables& t0 = remd_table_of(h->nb);
-        int rc0 = update_replica_lambdas(h, t0);
-        if (rc0) return rc0;
-        if (t0.method == NB_EWALD && h->sw.overlap && h->stream2 && do_nb && do_recip) {
-            // which stream's kernels run at raised wave priority: chosen together with the pair kernel's residency (remd_nb_tune_step)
-            t0.p.prio = h->sw.nb_prio >= 0 ? h->sw.nb_prio : t0.nb_prio;
-            h->mesh_prio_hi = !t0.p.prio;
-            if (!h->sync_events) {
-                // the first mesh launch (binning kernel, or the spreading pass when the chain binned the atoms) stores the
-                // fork flag; a one-wavefront kernel at the head of the second stream polls it
-                h->fork_seq_pending = ++h->sync_seq;
-                hipLaunchKernelGGL(remd_spin_wait_kernel, dim3(1), dim3(64), 0, h->stream2, h->d_sync, h->sync_seq, h->d_sync + 2);
-            } else {
-                hipEventRecord(h->ev_fork, h->stream);
-                hipStreamWaitEvent(h->stream2, h->ev_fork, 0);
-            }
-            // direct-space stream critical (t0.p.prio): the listed terms of a force-only evaluation leave it -- as extra workgroups of
-            // the spreading launch (REMD_LISTED_RIDE=0: as a launch of their own behind the mesh launches)
-            // (Round 6, measured and removed: holding the pair kernel back until an LDS-resident plane pass has ended -- the two then
-            // stretch the pair kernel and the inverse-z / gather pass instead, 139.9 against 134.8 ms per 100 steps of 16 DHFR replicas,
-            // +30 % on host-guest and alanine; profiles/r06_12_dhfr_pair_after_plane_pass.txt)
-            h->mesh_listed_total = 0;
-            if (h->sw.listed_main && h->sw.listed_ride && !with_energy && !h->sync_events && t0.p.prio != 0) {
-                int total = 0;
-                h->mesh_listed = listed_terms(total);
-                h->mesh_listed_total = total;
-                listed_rode = total > 0;
-            }
-            rc0 = remd_pme_forces(h, with_energy, h->stream, 1);        // everything up to the inverse z transform + gather
-            if (rc0) return rc0;
-            std::swap(h->stream, h->stream2);
-            swapped = true; forked = true;
-        }
-    }
-    h->pme_concurrent = forked;
-    if (!forked) { h->mesh_prio_hi = true; if (h->nb_method != REMD_NB_NONE) remd_table_of(h->nb).p.prio = 0; }
-    const bool merged = !with_energy;      // force-only evaluations: every listed term in one launch
-    if (!merged && h->n_bonds > 0) {
-        remd_prof_scope ps(h, "bonded");
-        LAUNCH_E(bond_kernel, dim3(R), dim3(256), 0, h->stream, h->n_bonds, h->d_bond_atoms, h->d_bond_params, h->Npad,
-                 h->d_pos, h->d_force, h->d_epart, h->n_epart);
-    }
-    if (!merged && h->n_angles > 0) {
-        remd_prof_scope ps(h, "bonded");
-        LAUNCH_E(angle_kernel, dim3(R), dim3(256), 0, h->stream, h->n_angles, h->d_angle_atoms, h->d_angle_params, h->Npad,
-                 h->d_pos, h->d_force, h->d_epart, h->n_epart);
-    }
-    if (!merged && h->n_torsions > 0) {
-        remd_prof_scope ps(h, "bonded");
-        LAUNCH_E(torsion_kernel, dim3(R), dim3(256), 0, h->stream, h->n_torsions, h->d_torsion_atoms, h->d_torsion_params, h->Npad,
-                 h->d_pos, h->d_force, h->d_epart, h->n_epart);
-    }
-    if (!merged && do_rst) { int rcr = remd_restraints_forces(h, with_energy, h->n_epart - 1, h->stream); if (rcr) return rcr; }
-    // listed terms of a force-only evaluation: ONE launch, behind the pair kernel (it then starts 20 us earlier, next to the
-    // spreading pass: 118.9 -> 116.8 ms per 500 steps)
-    // forked force-only evaluations: the listed terms go to the MAIN stream behind the mesh launches (they only need the positions
+    const bool forked = nbt && nbt->method == NB_EWALD && h->sw.overlap && h->stream2 && do_nb && do_recip;
+    const hipStream_t main_st = h->stream, direct_st = forked ? h->stream2 : h->stream;
+    // which stream's kernels run at raised wave priority (the pair kernel's: the direct-space stream is the critical path of a step):
+    // chosen together with the pair kernel's residency (remd_nb_tune_step)
+    const int prio_pair = forked ? (h->sw.nb_prio >= 0 ? h->sw.nb_prio : nbt->nb_prio) : 0;
+    // Where the listed terms, and the restraints with them, go.  Energy evaluation: a kernel per kind on the direct-space stream.
+    // Force-only evaluation: ONE launch, behind the pair kernel (it then starts 20 us earlier, next to the
+    // spreading pass: 118.9 -> 116.8 ms per 500 steps).
+    // Forked force-only evaluations: the listed terms go to the MAIN stream behind the mesh launches (they only need the positions
     // and add with the same integer atomics): since the Ewald split was rebalanced the direct-space stream is the critical path of
     // a step, and this takes a dependent 13 us launch off it (93.3 -> 89.5 ms per 500 steps).  REMD_LISTED_MAIN=0: behind the pair
     // kernel on the direct-space stream, as in round 3.
     // (only in the mode in which the direct-space stream is the critical one, chosen by the tuner together with the wave priority:
     // on a system whose mesh chain is the longer branch the extra work on the main stream costs what it saves here)
-    const bool listed_main = h->sw.listed_main && forked && !with_energy && !h->sync_events && h->nb_method != REMD_NB_NONE && remd_table_of(h->nb).p.prio != 0;
-    // the restraints (restraints.hip) go with the listed terms: the launch of a force-only evaluation on the stream the listed terms take
-    // (the main stream when those rode in the spreading launch), behind the torsions of an energy evaluation
-    int rc_rst = 0;
-    auto launch_listed = [&](hipStream_t lst) {
-        if (do_rst && !rc_rst) rc_rst = remd_restraints_forces(h, with_energy, h->n_epart - 1, lst);
-        if (listed_rode) return;                      // they rode in the spreading launch
-        int total = 0;
-        const listed_tables T = listed_terms(total);
-        if (total > 0) {
-            remd_prof_scope ps(h, "bonded");
-            hipLaunchKernelGGL(listed_forces_kernel, dim3((total + 255) / 256, R), dim3(256), 0, lst, T, h->Npad, h->d_pos,
-                               h->d_box, h->d_force);
+    // There they are extra workgroups of the spreading launch (REMD_LISTED_RIDE=0: a launch of their own behind the mesh launches).
+    // (Round 6, measured and removed: holding the pair kernel back until an LDS-resident plane pass has ended -- the two then
+    // stretch the pair kernel and the inverse-z / gather pass instead, 139.9 against 134.8 ms per 100 steps of 16 DHFR replicas,
+    // +30 % on host-guest and alanine; profiles/r06_12_dhfr_pair_after_plane_pass.txt)
+    enum { LISTED_KERNELS, LISTED_DIRECT, LISTED_MAIN, LISTED_RIDE };
+    const bool listed_off_direct = !with_energy && h->sw.listed_main && prio_pair != 0 && !h->sync_events;
+    const int listed = with_energy ? LISTED_KERNELS : !listed_off_direct ? LISTED_DIRECT : h->sw.listed_ride ? LISTED_RIDE : LISTED_MAIN;
+    // The join: events for a handle that fell back to them; else a signal launch behind the direct-space launches and a wait launch
+    // on the main stream -- or, where the caller's next main-stream launch is an integrator chain, that chain's prologue.  With the
+    // listed terms off the direct-space stream the scatter is its last launch, and the chain can poll the scatter's done counter
+    // (remd_fold_args) with no signal launch either, if launch_nb takes the request (REMD_NB_FOLD=0: signal launch).
+    const bool join_in_chain = forked && !h->sync_events && chain_follows && !with_energy;
+    const bool want_fold = join_in_chain && listed_off_direct && h->sw.nb_fold && (class_mask & 63u) == 63u && h->profiling != 2;
+    h->next.forked = forked;
+    if (nbt) nbt->p.prio = prio_pair;
+
+    // ---- in front of the fork: both branches are ordered behind these --------------------------------------------------------
+    if (!h->force_zeroed)
+        REMD_CHECK(h, hipMemsetAsync(h->d_force, 0, sizeof(long long) * 3 * (size_t)h->Npad * h->R, main_st));
+    h->force_zeroed = false;
+    if (with_energy)
+        REMD_CHECK(h, hipMemsetAsync(h->d_epart, 0, sizeof(double) * (size_t)h->n_epart * h->R, main_st));
+#define LAUNCH_E(kern, ...) do { if (with_energy) hipLaunchKernelGGL(kern<true>, __VA_ARGS__); else hipLaunchKernelGGL(kern<false>, __VA_ARGS__); } while (0)
+    // (custom forces of general alchemical regions, alch_regions.hip: part of the direct-space nonbonded class)
+    if (h->n_regions > 0 && do_nb) REMD_TRY(remd_regions_forces(h, with_energy, h->n_epart - 2));
+    if (h->nocutoff && do_nb) REMD_TRY(remd_nocutoff_forces(h, with_energy, EP_NB0));
+    if (h->gbsa && do_nb) REMD_TRY(remd_gbsa_forces(h, with_energy, EP_NB0 + 1));
+    if (h->n_ext > 0 && do_ext) {
+        remd_prof_scope ps(h, "ext_force");
+        LAUNCH_E(ext_force_kernel, dim3(R), dim3(64), 0, main_st, h->n_ext, h->d_ext_atoms, (float)h->ext_K, (float)h->ext_x0,
+                 h->ext_U0, h->Npad, h->d_pos, h->d_force, h->d_epart, h->n_epart);
+    }
+    if (nbt) REMD_TRY(update_replica_lambdas(h, *nbt));      // per-replica lambdas must be current before ANY kernel reads them
+    int listed_total = 0;
+    const listed_tables listed_tab = with_energy ? listed_tables{} : listed_terms(h, class_mask, listed_total);
+
+    // ---- mesh branch (main stream): everything up to the inverse z transform + gather ------------------------------------------
+    remd_mesh_request mesh;
+    mesh.prio_hi = prio_pair == 0;
+    if (forked) {
+        if (!h->sync_events) {
+            // the first mesh launch (binning kernel, or the spreading pass when the chain binned the atoms) stores the
+            // fork flag; a one-wavefront kernel at the head of the second stream polls it
+            mesh.fork_seq = ++h->sync_seq;
+            hipLaunchKernelGGL(remd_spin_wait_kernel, dim3(1), dim3(64), 0, direct_st, h->d_sync, h->sync_seq, h->d_sync + 2);
+        } else {
+            hipEventRecord(h->ev_fork, main_st);
+            hipStreamWaitEvent(direct_st, h->ev_fork, 0);
         }
-    };
-    if (h->nb_method == REMD_NB_NONE) {
-        if (merged) launch_listed(h->stream);
-    } else {
-        nb_tables& t = remd_table_of(h->nb);
-        int rc = do_nb ? ensure_sorted(h, t) : 0;
-        if (rc) return rc;
-        // (after the swap h->stream2 is the main stream: the listed terms queue up behind the mesh launches already enqueued there)
-        if (merged && listed_main) launch_listed(h->stream2);
-        // let the integrator chain that consumes this evaluation poll the scatter's done counter (remd_fold_args) instead of a flag
-        // from a signal launch: only where that chain is certain to be the next launch on the main stream (remd_run_steps, plain
-        // single-group programs) and in the mode in which the direct-space stream is the critical one; REMD_NB_FOLD=0: signal launch
-        h->fold_pending = h->sw.nb_fold && listed_main && merged && h->defer_join_ok && do_nb && (class_mask & 63u) == 63u && t.sorting && t.clusters &&
-                          t.lj_split && t.d_lj_sci_list && t.d_sci_list && h->profiling != 2;
-        h->fold.done = nullptr;                  // (launch_nb fills remd_fold_args where it takes the request)
-        if (do_nb) {
-            remd_prof_scope ps(h, "nonbonded");
-            if (with_energy) {
-                if (t.method == NB_LJ_ONLY) rc = launch_nb<NB_LJ_ONLY, true>(h, t);
-                else if (t.method == NB_RF) rc = launch_nb<NB_RF, true>(h, t);
-                else rc = launch_nb<NB_EWALD, true>(h, t);
-            } else {
-                if (t.method == NB_LJ_ONLY) rc = launch_nb<NB_LJ_ONLY, false>(h, t);
-                else if (t.method == NB_RF) rc = launch_nb<NB_RF, false>(h, t);
-                else rc = launch_nb<NB_EWALD, false>(h, t);
-            }
-            if (rc) return rc;
+        if (listed == LISTED_RIDE) { mesh.listed = listed_tab; mesh.listed_total = listed_total; }
+        mesh.part = 1;
+        REMD_TRY(remd_pme_forces(h, with_energy, main_st, mesh));
+    }
+
+    // ---- direct-space branch (the second stream of a forked evaluation) ----------------------------------------------------------
+    if (listed == LISTED_KERNELS) {
+        if (h->n_bonds > 0) {
+            remd_prof_scope ps(h, "bonded", direct_st);
+            LAUNCH_E(bond_kernel, dim3(R), dim3(256), 0, direct_st, h->n_bonds, h->d_bond_atoms, h->d_bond_params, h->Npad,
+                     h->d_pos, h->d_force, h->d_epart, h->n_epart);
         }
-        h->fold_pending = h->fold_pending && h->fold.done != nullptr;
-        if (merged && !listed_main) launch_listed(h->stream);
-        if (!merged && t.n_exc > 0) {
-            remd_prof_scope ps(h, "exceptions");
-            LAUNCH_E(exception_kernel, dim3(R), dim3(256), 0, h->stream, t.n_exc, t.d_exc_atoms, t.d_exc_params, t.d_exc_alch,
+        if (h->n_angles > 0) {
+            remd_prof_scope ps(h, "bonded", direct_st);
+            LAUNCH_E(angle_kernel, dim3(R), dim3(256), 0, direct_st, h->n_angles, h->d_angle_atoms, h->d_angle_params, h->Npad,
+                     h->d_pos, h->d_force, h->d_epart, h->n_epart);
+        }
+        if (h->n_torsions > 0) {
+            remd_prof_scope ps(h, "bonded", direct_st);
+            LAUNCH_E(torsion_kernel, dim3(R), dim3(256), 0, direct_st, h->n_torsions, h->d_torsion_atoms, h->d_torsion_params, h->Npad,
+                     h->d_pos, h->d_force, h->d_epart, h->n_epart);
+        }
+        if (do_rst) REMD_TRY(remd_restraints_forces(h, with_energy, h->n_epart - 1, direct_st));
+    }
+    if (nbt && do_nb) REMD_TRY(ensure_sorted(h, *nbt, direct_st));
+    // (on the main stream the listed terms queue up behind the mesh launches already enqueued there)
+    if (listed == LISTED_MAIN || listed == LISTED_RIDE)
+        REMD_TRY(launch_listed(h, do_rst, listed_tab, listed == LISTED_RIDE ? 0 : listed_total, main_st));
+    remd_fold_args fold;               // what the scatter counts for the next integrator chain, where launch_nb took want_fold
+    if (nbt && do_nb) {
+        remd_prof_scope ps(h, "nonbonded", direct_st);
+        REMD_TRY(with_energy ? launch_nb_method<true>(h, *nbt, direct_st, want_fold, fold) : launch_nb_method<false>(h, *nbt, direct_st, want_fold, fold));
+    }
+    if (listed == LISTED_DIRECT) REMD_TRY(launch_listed(h, do_rst, listed_tab, listed_total, direct_st));
+    if (nbt && listed == LISTED_KERNELS) {
+        nb_tables& t = *nbt;
+        if (t.n_exc > 0) {
+            remd_prof_scope ps(h, "exceptions", direct_st);
+            LAUNCH_E(exception_kernel, dim3(R), dim3(256), 0, direct_st, t.n_exc, t.d_exc_atoms, t.d_exc_params, t.d_exc_alch,
                      t.has_alch ? t.d_rep_lam : (const float*)nullptr, h->Npad,
                      h->d_pos, h->d_box, h->d_force, h->d_epart, h->n_epart);
         }
-        if (!merged && t.n_excl > 0) {
-            remd_prof_scope ps(h, "exceptions");
-            LAUNCH_E(ewald_exclusion_kernel, dim3(R), dim3(256), 0, h->stream, t.n_excl, t.d_excl_atoms, t.d_excl_qq, t.d_excl_alch,
+        if (t.n_excl > 0) {
+            remd_prof_scope ps(h, "exceptions", direct_st);
+            LAUNCH_E(ewald_exclusion_kernel, dim3(R), dim3(256), 0, direct_st, t.n_excl, t.d_excl_atoms, t.d_excl_qq, t.d_excl_alch,
                      t.has_alch ? t.d_rep_lam : (const float*)nullptr, t.p.alpha,
                      t.p.two_alpha_sqrtpi, h->Npad, h->d_pos, h->d_box, h->d_force, h->d_epart, h->n_epart);
         }
-        if (t.method == NB_EWALD) {
-            if (forked) {                                                       // join
-                if (h->fold_pending) {
-                    // nothing left to launch on the direct-space stream: the chain polls the scatter's done counter
-                    std::swap(h->stream, h->stream2); swapped = false;
-                } else if (!h->sync_events) {
-                    // (the scatter's last workgroup publishing the join instead of this launch: its arrival counter costs more than the
-                    // launch it saves, 14 us against 5.2 + 5.6 with two-level counters -- profiles/r04_h_rejected.txt)
-                    hipLaunchKernelGGL(remd_signal_kernel, dim3(1), dim3(64), 0, h->stream, h->d_sync + 1, h->sync_seq);
-                    std::swap(h->stream, h->stream2); swapped = false;
-                    // inside remd_run_steps the launch that follows on the main stream is an integrator chain: it polls the
-                    // flag in its prologue (no kernel of its own for the wait)
-                    if (h->defer_join_ok && !with_energy) h->join_deferred = h->sync_seq;
-                    else hipLaunchKernelGGL(remd_spin_wait_kernel, dim3(1), dim3(64), 0, h->stream, h->d_sync + 1, h->sync_seq, h->d_sync + 2);
-                } else {
-                    hipEventRecord(h->ev_join, h->stream);
-                    std::swap(h->stream, h->stream2); swapped = false;
-                    hipStreamWaitEvent(h->stream, h->ev_join, 0);
-                }
-                rc = remd_pme_forces(h, with_energy, h->stream, 2); if (rc) return rc;        // (the energy reduction of the mesh part)
-            }
-            else if (do_recip) { rc = remd_pme_forces(h, with_energy, h->stream); if (rc) return rc; }
-        }
-        if (with_energy)
-            hipLaunchKernelGGL(const_energy_kernel, dim3((R + 63) / 64), dim3(64), 0, h->stream, R, t.disp_coeff, t.self_nn, t.self_aa,
-                               t.q_n, t.q_a, t.net_charge_term, t.has_alch ? t.d_rep_lam : (const float*)nullptr, h->d_box,
-                               h->d_epart, h->n_epart);
     }
 #undef LAUNCH_E
-    if (rc_rst) return rc_rst;
+
+    // ---- join, and what is left of the mesh branch behind it ---------------------------------------------------------------------
+    if (forked) {
+        if (fold.done) {
+            // nothing left to launch on the direct-space stream: the chain polls the scatter's done counter
+            h->next.wait.fold = fold;
+        } else if (!h->sync_events) {
+            // (the scatter's last workgroup publishing the join instead of this launch: its arrival counter costs more than the
+            // launch it saves, 14 us against 5.2 + 5.6 with two-level counters -- profiles/r04_h_rejected.txt)
+            hipLaunchKernelGGL(remd_signal_kernel, dim3(1), dim3(64), 0, direct_st, h->d_sync + 1, h->sync_seq);
+            // inside remd_run_steps the launch that follows on the main stream is an integrator chain: it polls the
+            // flag in its prologue (no kernel of its own for the wait)
+            if (join_in_chain) h->next.wait.seq = h->sync_seq;
+            else hipLaunchKernelGGL(remd_spin_wait_kernel, dim3(1), dim3(64), 0, main_st, h->d_sync + 1, h->sync_seq, h->d_sync + 2);
+        } else {
+            hipEventRecord(h->ev_join, direct_st);
+            hipStreamWaitEvent(main_st, h->ev_join, 0);
+        }
+        mesh.part = 2;                 // (what is left: the energy reduction of the mesh part)
+    }
+    if (forked || (nbt && nbt->method == NB_EWALD && do_recip)) REMD_TRY(remd_pme_forces(h, with_energy, main_st, mesh));
+    if (with_energy && nbt) {
+        const nb_tables& t = *nbt;
+        hipLaunchKernelGGL(const_energy_kernel, dim3((R + 63) / 64), dim3(64), 0, main_st, R, t.disp_coeff, t.self_nn, t.self_aa,
+                           t.q_n, t.q_a, t.net_charge_term, t.has_alch ? t.d_rep_lam : (const float*)nullptr, h->d_box,
+                           h->d_epart, h->n_epart);
+    }
     if (with_energy)
-        hipLaunchKernelGGL(reduce_energy_kernel, dim3(R), dim3(64), 0, h->stream, h->n_epart, h->d_epart, h->d_potential);
+        hipLaunchKernelGGL(reduce_energy_kernel, dim3(R), dim3(64), 0, main_st, h->n_epart, h->d_epart, h->d_potential);
     REMD_CHECK(h, hipGetLastError());
     h->forces_valid = true;
     return 0;

@@ -889,7 +889,6 @@ int remd_parse_splitting(remd_ctx* h, const char* splitting, std::vector<char>& 
     return 0;
 }
 
-remd_chain_bins remd_pme_chain_bins(remd_ctx* h);
 static void launch_chain(remd_ctx* h, const unit_tables& ut, const chain_prog& prog, bool bin_for_pme = false)
 {
     // mesh-column bins from the chain's epilogue: in a handle that runs as ONE block (the binning launch would sit on the step's only
@@ -907,15 +906,15 @@ static void launch_chain(remd_ctx* h, const unit_tables& ut, const chain_prog& p
     // held the WHOLE register file of their CUs while they polled for the forces in the prologue, and a direct-space stream that still had
     // workgroups to place then never got a slot: the poll ran out after seconds (end of round 5, 128 alanine replicas = 384 workgroups).
     // Removed; one workgroup per CU leaves 160 registers per lane for the kernels the chain waits for.)
+    const remd_handover::wait_t join = h->next.take_wait();      // the evaluation in front left it for this launch
     hipLaunchKernelGGL(integrate_chain_kernel, grid, dim3(256), 0, h->stream, prog, ut.n_units, ut.d_atoms, ut.d_type,
                        ut.d_dist, ut.sc, (float)fmax(h->constraint_tol, REMD_CONSTRAINT_TOL_FLOOR), h->Npad, h->d_pos, h->d_vel, h->d_force,
                        h->d_invmass, h->d_labels, h->d_beta, h->r_begin, h->seed, h->d_cmm,
                        (float)(h->total_mass > 0 ? 1.0 / h->total_mass : 0.0),
-                       h->join_deferred ? h->d_sync + 1 : (unsigned int*)nullptr, h->join_deferred, bins, h->d_chain_sync, h->d_sync + 2,
+                       join.seq ? h->d_sync + 1 : (unsigned int*)nullptr, join.seq, bins, h->d_chain_sync, h->d_sync + 2,
                        (h->profiling == 2 || (h->profiling == 1 && h->prof_filter.find("integrate_chain") != std::string::npos)) ? h->d_chain_own : (unsigned long long*)nullptr,
-                       h->d_work, h->d_xold, h->d_vold, h->fold_pending ? h->fold : remd_fold_args(), h->d_noise_id);
-    h->join_deferred = 0; h->fold_pending = false;
-    if (bins.count) h->cbins_ready = true;
+                       h->d_work, h->d_xold, h->d_vold, join.fold, h->d_noise_id);
+    if (bins.count) h->next.cbins_ready = true;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1194,10 +1193,6 @@ void resident_md_kernel(resident_prog prog, resident_sys S, float4* __restrict__
         V[tid] = make_float4(v.x, v.y, v.z, 0.f);
     }
 }
-
-void remd_launch_join_wait(remd_ctx* h);
-int remd_nb_resident_info(remd_ctx* h, int* ok, int* method, int* has_alch, nb_params* p, const float4** param, const float** rep_lam);
-void remd_nb_invalidate_sort(remd_ctx* h);
 
 // returns 1 when the propagation was run by the resident kernel, 0 when the system / request is not one it covers, < 0 on error
 static int remd_run_steps_resident(remd_ctx* h, const std::vector<char>& tokens, int nV, int nR, int nO,
@@ -1533,9 +1528,6 @@ static int remd_run_steps_resident_mol(remd_ctx* h, const std::vector<char>& tok
 // One loop body = one MD step's launches: the chain(s) around the centre-of-mass removal and the force evaluation on two streams.
 // (Round 2 also captured the body into a hipGraph and replayed it: bit-identical and no faster on ROCm 7.2 -- the floor of a step is
 // the dependent chain of kernels, not the host -- so the capture path was removed in round 3; DESIGN.md section 7b has the numbers.)
-void remd_launch_join_wait(remd_ctx* h);
-void remd_nb_tune_step(remd_ctx* h, int steps_left_in_call);
-
 // The state remd_run_steps keeps between the MD steps of one call, as an object: begin() = everything in front of the step loop,
 // step(s) = one MD step's launches, end() = the flush behind the last step.  One handle runs begin / step ... / end by itself
 // (remd_run_steps); round 6: SEVERAL handles of one device take turns step by step from one host thread (remd_run_steps_many: the
@@ -1709,9 +1701,7 @@ struct step_runner {
                 flush(false, has_mesh);
                 std::swap(h->d_force, h->d_force_g[g]);      // (the evaluation fills the group's array)
                 h->force_zeroed = false; zeroed_by_chain = false;
-                h->defer_join_ok = device_waits_ok && !h->lean_waits;
-                int rc = remd_compute_forces(h, false, group_mask[g]);
-                h->defer_join_ok = false;
+                int rc = remd_compute_forces(h, false, group_mask[g], device_waits_ok && !h->lean_waits);
                 std::swap(h->d_force, h->d_force_g[g]);
                 h->forces_valid = false; h->force_zeroed = false;      // (the all-forces accumulator was not touched)
                 if (rc) return rc;
@@ -1721,9 +1711,7 @@ struct step_runner {
                 flush(false, true);
                 h->force_zeroed = zeroed_by_chain;
                 zeroed_by_chain = false;
-                h->defer_join_ok = device_waits_ok && !h->lean_waits;   // the next main-stream launch is the chain holding this V
-                int rc = remd_compute_forces(h, false);
-                h->defer_join_ok = false;
+                int rc = remd_compute_forces(h, false, ~0u, device_waits_ok && !h->lean_waits);   // (next on the main stream: the chain holding this V)
                 if (rc) return rc;
             }
             push(tok, tok == 'O' ? oidx : 0, gstep);

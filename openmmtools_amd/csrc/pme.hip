@@ -30,7 +30,7 @@
 struct fft_sched { const uint2* tab; int off[8]; };   // see fft_stage_sched
 
 struct pme_state {
-    bool prio_hi = true;                  // mesh kernels at raised wave priority (remd_pme_forces copies remd_ctx::mesh_prio_hi)
+    bool prio_hi = true;                  // mesh kernels at raised wave priority (remd_pme_forces: remd_mesh_request::prio_hi)
     int n[4] = {0, 0, 0, 0};           // mesh dimensions; n[3] = nz / 2 (length of the packed real-to-complex z transform)
     int R = 0;
     size_t npts = 0;
@@ -1337,28 +1337,24 @@ static void launch_pass(remd_ctx* h, pme_state* s, float2* data, size_t rep_stri
                        line_div, hi, contiguous, s->d_tw[axis_n_index]);
 }
 
-const float* remd_nb_rep_lam(remd_ctx* h);
-const float4* remd_nb_param(remd_ctx* h);
-
-int remd_pme_forces(remd_ctx* h, bool with_energy, hipStream_t st, int part)
+int remd_pme_forces(remd_ctx* h, bool with_energy, hipStream_t st, const remd_mesh_request& rq)
 {
+    const int part = rq.part;
     pme_state* s = h->pme.get();
     if (!s || s->R != h->R || !s->ready) { int rc = remd_pme_setup(h); if (rc) return rc; s = h->pme.get(); }
     s->stream = st;
-    s->prio_hi = h->mesh_prio_hi;
+    s->prio_hi = rq.prio_hi;
     const int nx = s->n[0], ny = s->n[1], nz = s->n[2];
     const float* rep_lam = remd_nb_rep_lam(h);
     const float4* param = remd_nb_param(h);
     if (part & 1) {
-    // bins from the integrator chain (h->cbins_ready: the chain launched just before this evaluation filled buffer cbin_parity)
-    s->cbin_use = h->cbins_ready && s->d_cbin_count;
-    h->cbins_ready = false;
+    // bins from the integrator chain (the chain launched just before this evaluation filled buffer cbin_parity)
+    s->cbin_use = h->next.take_bins() && s->d_cbin_count;
     if (!s->cbin_use)
     {
         remd_prof_scope ps(h, "pme_bin", st);
         hipLaunchKernelGGL(pme_bin_kernel, dim3(h->R), dim3(1024), 0, st, h->N, h->Npad, nx, ny, nz, h->d_pos, h->d_box,
-                           s->d_col_start, s->d_col_atoms, h->fork_seq_pending ? h->d_sync : (unsigned int*)nullptr, h->fork_seq_pending);
-        h->fork_seq_pending = 0;
+                           s->d_col_start, s->d_col_atoms, rq.fork_seq ? h->d_sync : (unsigned int*)nullptr, rq.fork_seq);
     }
     {
         remd_prof_scope ps(h, "pme_fft", st);
@@ -1387,12 +1383,11 @@ int remd_pme_forces(remd_ctx* h, bool with_energy, hipStream_t st, int part)
         const int* bin_ca = s->cbin_use ? reinterpret_cast<const int*>(s->d_cbin_atoms.get()) : s->d_col_atoms;
         const int bin_cap = s->cbin_use ? s->cbin_cap : 0;
         int* bin_zero = s->cbin_use ? s->d_cbin_count + (size_t)(1 - s->cbin_parity) * s->R * nx : (int*)nullptr;
-        unsigned int* fflag = (s->cbin_use && h->fork_seq_pending) ? h->d_sync : (unsigned int*)nullptr;
-        const unsigned int fseq = h->fork_seq_pending;
-        if (s->cbin_use) { h->fork_seq_pending = 0; }
-        // listed terms riding in this launch (forces.hip decides: remd_ctx::mesh_listed_total)
+        const unsigned int fseq = s->cbin_use ? rq.fork_seq : 0u;        // (else the binning launch published it)
+        unsigned int* fflag = fseq ? h->d_sync : (unsigned int*)nullptr;
+        // listed terms riding in this launch (forces.hip decides)
         const int n_mesh_blocks = (int)zgrid.x;
-        const int n_listed_blocks = h->mesh_listed_total > 0 ? (h->mesh_listed_total + ZT - 1) / ZT : 0;
+        const int n_listed_blocks = rq.listed_total > 0 ? (rq.listed_total + ZT - 1) / ZT : 0;
         // power-of-two z: 64 lines per workgroup on the register transforms (REMD_PME_POW2=0: the scheduled passes)
         const int zp2 = ((h->sw.pme_pow2 & 2) && half && (nz == 64 || nz == 128) && ny % 64 == 0 && nl == 64 && ZT == 64 * (nz / 16)) ? nz : 0;
         const size_t zlds2 = sizeof(float2) * (size_t)(nz / 2 + 1) * 64;
@@ -1400,7 +1395,7 @@ int remd_pme_forces(remd_ctx* h, bool with_energy, hipStream_t st, int part)
             const dim3 zg(zgrid.x + n_listed_blocks, zgrid.y);
 #define LAUNCH_ZF2(MMM, RR) hipLaunchKernelGGL((pme_spread_zfwd_pow2_kernel<MMM, RR>), zg, dim3(64 * RR), zlds2, st, nx, ny, h->Npad, h->d_pos, param, h->d_box, rep_lam, \
                        bin_cs, bin_ca, s->d_grid, s->d_tw[2], s->d_tw[3], bin_cap, bin_zero, fflag, fseq, \
-                       (s->cbin_use && !rep_lam) ? s->d_cbin_q : (const float*)nullptr, h->mesh_listed, n_mesh_blocks, h->d_force, s->prio_hi ? 1 : 0)
+                       (s->cbin_use && !rep_lam) ? s->d_cbin_q : (const float*)nullptr, rq.listed, n_mesh_blocks, h->d_force, s->prio_hi ? 1 : 0)
             if (zp2 == 64) LAUNCH_ZF2(32, 4); else LAUNCH_ZF2(64, 8);
 #undef LAUNCH_ZF2
         } else
@@ -1409,9 +1404,8 @@ int remd_pme_forces(remd_ctx* h, bool with_energy, hipStream_t st, int part)
             const dim3 zgrid(zgrid_keep.x + n_listed_blocks, zgrid_keep.y);
             DISPATCH_Z(pme_spread_zfwd_kernel, h->Npad, h->d_pos, param, h->d_box, rep_lam, bin_cs, bin_ca, s->d_grid,
                        s->d_tw[2], s->d_tw[3], bin_cap, bin_zero, fflag, fseq, (s->cbin_use && !rep_lam) ? s->d_cbin_q : (const float*)nullptr,
-                       h->mesh_listed, n_mesh_blocks, h->d_force);
+                       rq.listed, n_mesh_blocks, h->d_force);
         }
-        h->mesh_listed_total = 0;
         if (s->xy_fused || s->xs_sw > 0) {
             if (!s->d_infl) REMD_TRY(s->d_infl.alloc(h, s->nspec * s->R));
             if (s->infl_version != h->box_version) {
@@ -1503,7 +1497,7 @@ remd_chain_bins remd_pme_chain_bins(remd_ctx* h)
 {
     remd_chain_bins b;
     const pme_state* s = h->pme.get();
-    if (!s || !s->d_cbin_count || s->R != h->R || !h->pme_concurrent || h->no_chain_bins) return b;
+    if (!s || !s->d_cbin_count || s->R != h->R || !h->next.forked || h->no_chain_bins) return b;
     b.nx = s->n[0]; b.cap = s->cbin_cap; b.count = s->d_cbin_count + (size_t)s->cbin_parity * s->R * s->n[0]; b.atoms = s->d_cbin_atoms;
     b.box = h->d_box; b.err = h->d_sync + 2;
     // charges ride in the bins only when they do not depend on the replica's state: the chain runs before the evaluation

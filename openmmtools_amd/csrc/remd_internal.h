@@ -129,6 +129,27 @@ struct listed_tables {
     int n_aterm; const unsigned int* aterm;
 };
 
+// What remd_compute_forces (forces.hip) tells the mesh branch of an evaluation (remd_pme_forces, pme.hip).
+struct remd_mesh_request {
+    int part = 3;                      // 1: bin .. inverse z transform + gather, 2: the energy reduction, 3: both
+    unsigned int fork_seq = 0;         // the fork flag that the first launch of part 1 publishes in d_sync[0] (0: none)
+    listed_tables listed{}; int listed_total = 0;   // listed terms riding in the spreading launch as extra workgroups (0: none)
+    bool prio_hi = true;               // the mesh kernels run at raised wave priority (false: the pair kernel does)
+};
+
+// What crosses from one launch function of an MD step to the next; everything else an evaluation decides is an argument.
+struct remd_handover {
+    // evaluation -> integrator chain: the join of a forked evaluation that the next main-stream launch still has to wait for, as the
+    // join flag's sequence number (d_sync[1]) OR the scatter's done counter, never both.  launch_chain (integrate.hip) takes it as
+    // a kernel argument, remd_launch_join_wait (forces.hip) turns what no chain took into a wait on the stream.
+    struct wait_t { unsigned int seq = 0; remd_fold_args fold; } wait;
+    bool cbins_ready = false;          // chain -> evaluation: the chain launched last binned the atoms for the PME pass that follows
+    bool forked = false;               // the last evaluation ran on two streams (a fact, nothing pending: reset() keeps it)
+    wait_t take_wait() { const wait_t w = wait; wait = wait_t(); return w; }
+    bool take_bins() { const bool b = cbins_ready; cbins_ready = false; return b; }
+    void reset() { wait = wait_t(); cbins_ready = false; }      // nothing is pending: positions or in-flight work were replaced
+};
+
 struct remd_profile_entry { int64_t n = 0; double ms = 0.0; };
 
 // a deep copy of the descriptor of the last remd_set_system: the groups of replicas a handle propagates as phases (api.hip) are set up
@@ -325,13 +346,8 @@ struct remd_ctx {
     // publishes the fork, a one-wavefront kernel at the head of the second stream waits for it, and the mirror image at the
     // join -- an event record / wait costs ~6 us of command-processor latency on the critical path, twice per step.
     // sync_events: the events instead, the fall-back of a handle whose polled wait ran out (api.hip: remd_recover_device_flag).
-    dev_array<unsigned int> d_sync; unsigned int sync_seq = 0; unsigned int fork_seq_pending = 0; bool sync_events = false;
-    // remd_run_steps: the launch that follows a force evaluation on the main stream is always an integrator chain, so the
-    // join is polled in that kernel's prologue (join_deferred = sequence number to wait for) instead of a kernel of its own
-    bool defer_join_ok = false; unsigned int join_deferred = 0;
-    listed_tables mesh_listed{}; int mesh_listed_total = 0;   // listed terms to ride in the next spreading launch (0: none)
-    remd_fold_args fold; bool fold_pending = false;      // the next chain launch polls the scatter's done counter instead of a join flag (forces.hip)
-    bool mesh_prio_hi = true;          // which of the two streams' kernels run at raised wave priority (forces.hip: chosen with the pair-kernel residency)
+    dev_array<unsigned int> d_sync; unsigned int sync_seq = 0; bool sync_events = false;
+    remd_handover next;
     // set when a wait polled on the device ran out / a capped PME bin overflowed: the handle falls back to events, two chain
     // launches and the binning launch (api.hip: remd_recover_device_flag) instead of staying dead behind a sticky flag
     bool no_device_waits = false, no_chain_bins = false, no_resident = false, no_chain_merge = false;
@@ -354,8 +370,7 @@ struct remd_ctx {
     bool borrowed_stream2 = false;     // stream2 belongs to another handle (remd_adopt_streams): not destroyed with this one
     dev_array<unsigned long long> d_chain_own;   // [2] profiling: sum of (end - flag seen) wall-clock ticks of workgroup (0, 0), launches
     dev_array<unsigned long long> d_chain_sync; unsigned int chain_sync_epoch = 0; long long chain_sync_key = -1;    // [2][R][workgroups][3] epoch-tagged partial momentum sums of the 'M' token (integrate.hip)
-    bool cbins_ready = false;          // the chain launched last binned the atoms for the PME pass of the evaluation that follows
-    hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; bool pme_concurrent = false;
+    hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // sharding without a Python host (comm.hip): an RCCL communicator over the ranks of one replica-exchange run
     void* comm = nullptr; int comm_rank = 0, comm_world = 1;
     std::vector<long long> comm_begin, comm_count;   // every rank's block of replicas, exchanged when the local block changes
@@ -414,6 +429,7 @@ struct remd_prof_scope {
 int remd_mix_launch(remd_ctx* h, int scheme, int64_t iteration, int R, int K, int ld, const double* d_ukl,
                     int64_t* d_labels, unsigned long long* d_nacc, unsigned long long* d_nprop,
                     const double* d_logw, double* d_logP, int64_t n_attempts);
+const unsigned* remd_mix_pending_flag(remd_ctx* h);
 
 // ---- integrate.hip ----------------------------------------------------------------------
 int remd_parse_splitting(remd_ctx* h, const char* splitting, std::vector<char>& tokens, int& nV, int& nR, int& nO, int* nVg = nullptr);
@@ -423,6 +439,7 @@ int remd_run_steps_many(remd_ctx** hs, int n, int64_t iteration, int64_t first_s
 long long remd_chain_blocks(remd_ctx* h);            // workgroups of one integrator-chain launch   // the handles' steps taking turns
 int remd_assign_velocities(remd_ctx* h, int64_t iteration);
 int remd_kinetic_energy(remd_ctx* h);
+int remd_check_finite(remd_ctx* h);
 int remd_work_buffers(remd_ctx* h);                    // heat / shadow-work accumulators and the '{' snapshot of the local replicas
 
 // ---- forces.hip -------------------------------------------------------------------------
@@ -431,6 +448,16 @@ int remd_barostat_buffers(remd_ctx* h);                      // (its per-replica
 int remd_nb_molecules(remd_ctx* h, const int** first, const int** size);   // molecule table of the nonbonded setup (device); 0: none
 int remd_minimize_impl(remd_ctx* h, double tolerance, int max_iterations, int32_t* converged, int32_t* n_iterations);
 void remd_nb_invalidate_sort(remd_ctx* h);            // the next force evaluation re-sorts the molecules
+void remd_nb_reset_accumulators(remd_ctx* h);         // after a device-side fault: the sorted accumulators of a discarded evaluation
+void remd_nb_tune_step(remd_ctx* h, int steps_left_in_call);   // the pair kernel's residency, chosen by timing
+void remd_nb_tune_resolve(remd_ctx* h);
+struct nb_params;                                     // pair_math.h
+int remd_nb_resident_info(remd_ctx* h, int* ok, int* method, int* has_alch, nb_params* p, const float4** param, const float** rep_lam);
+const float* remd_nb_rep_lam(remd_ctx* h);            // what the mesh kernels read: per-replica lambdas (NULL: none) ...
+const float4* remd_nb_param(remd_ctx* h);             // ... and per-atom parameters
+int remd_nb_required_epart(remd_ctx* h);
+int remd_assemble_ukl(remd_ctx* h, double* d_rows);
+void remd_launch_join_wait(remd_ctx* h);              // a join left for an integrator chain that no chain took (remd_handover::wait)
 // force classes (bits of the mask of remd_compute_forces, indices of remd_ctx::fgroup)
 #define REMD_FG_EXTERNAL 0
 #define REMD_FG_BOND 1
@@ -455,7 +482,9 @@ int remd_regions_forces(remd_ctx* h, bool with_energy, int ep_slot);
 int remd_regions_ukl(remd_ctx* h, double* d_out /*[R][K]*/, const int** d_own);
 int remd_regions_pme_tables(remd_ctx* h, const float4** param, const float** rep_le);
 int remd_regions_le_override(remd_ctx* h, const float* le, int* n, const float** d_state_le);
-int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask = ~0u);   // fills d_force (and d_potential when with_energy)
+// fills d_force (and d_potential when with_energy).  chain_follows: the caller's next launch on the main stream is an integrator
+// chain of this handle, so the join of a forked evaluation may be left in h->next.wait for that chain to poll
+int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask = ~0u, bool chain_follows = false);
 int remd_build_nonbonded(remd_ctx* h, const remd_system_desc* d);
 int remd_build_constraints(remd_ctx* h, const remd_system_desc* d);
 
@@ -467,4 +496,6 @@ int remd_restraints_ukl(remd_ctx* h, double* d_rows /*[R][K], added to*/);
 
 // ---- pme.hip ----------------------------------------------------------------------------
 int remd_pme_setup(remd_ctx* h);
-int remd_pme_forces(remd_ctx* h, bool with_energy, hipStream_t st, int part = 3);   // part 1: bin .. inverse z, part 2: gather (+ energy)
+int remd_pme_forces(remd_ctx* h, bool with_energy, hipStream_t st, const remd_mesh_request& rq);
+remd_chain_bins remd_pme_chain_bins(remd_ctx* h);     // bins for the next evaluation, to be filled by the integrator chain in front of it
+int remd_test_fft3d_impl(remd_ctx* h, int nx, int ny, int nz, float* data, int inverse);
