@@ -77,6 +77,9 @@ class RemdGbModelDesc(C.Structure):
 
 # the GPU-only extension of include/remd_hip_restraints.h: bound where the loaded library exports it (the CPU port of the ABI does not)
 RESTRAINT_EXPORTS = ['remd_set_restraints', 'remd_set_restraint_lambdas', 'remd_get_restraint_energies']
+# the GPU-only extension of include/remd_hip_barostat.h (per-axis Monte Carlo barostats), bound the same way
+BAROSTAT_AXIS_EXPORTS = ['remd_set_barostat_axes', 'remd_get_barostat_axis_stats']
+BAROSTAT_ANISOTROPIC, BAROSTAT_MEMBRANE = 1, 2
 
 EXPORTS = [
     'remd_create', 'remd_destroy', 'remd_last_error', 'remd_version', 'remd_set_system', 'remd_set_coulomb_cutoff', 'remd_set_reaction_field', 'remd_set_alchemical_options', 'remd_set_alchemical_regions',
@@ -183,6 +186,11 @@ def load_library(path=None):
         lib.remd_set_restraint_lambdas.argtypes = [vp, c_double_p]
         lib.remd_get_restraint_energies.argtypes = [vp, c_double_p]
         for name in RESTRAINT_EXPORTS:
+            getattr(lib, name).restype = C.c_int
+    if hasattr(lib, 'remd_set_barostat_axes'):            # include/remd_hip_barostat.h (GPU-only, like the restraints)
+        lib.remd_set_barostat_axes.argtypes = [vp, C.c_int, c_double_p, c_double_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        lib.remd_get_barostat_axis_stats.argtypes = [vp, c_double_p, c_int64_p, c_int64_p]
+        for name in BAROSTAT_AXIS_EXPORTS:
             getattr(lib, name).restype = C.c_int
     if hasattr(lib, 'remd_set_gb_model'):                 # include/remd_hip_gb.h (GPU-only, like the restraints)
         lib.remd_set_gb_model.argtypes = [vp, C.POINTER(RemdGbModelDesc)]
@@ -459,6 +467,29 @@ class HipEngine:
             return
         p = np.ascontiguousarray(pressure, dtype=np.float64)
         self._check(self.lib.remd_set_barostat(self.h, len(p), _dp(p), int(frequency)), 'remd_set_barostat')
+
+    def _barostat_axis_entry(self, name):
+        if not hasattr(self.lib, name):
+            raise NotImplementedError('%s: this build of the engine library has no per-axis barostats (include/remd_hip_barostat.h is GPU-only)' % name)
+        return getattr(self.lib, name)
+
+    def set_barostat_axes(self, pressure, surface_tension, kind, xy_or_scale_mask, zmode=0, frequency=25):
+        """MonteCarloAnisotropicBarostat (kind BAROSTAT_ANISOTROPIC, xy_or_scale_mask = scaleX | scaleY << 1 | scaleZ << 2) or
+        MonteCarloMembraneBarostat (kind BAROSTAT_MEMBRANE, xy_or_scale_mask = the xy mode, zmode the z mode) of the states: pressure
+        per state in kJ/mol/nm^3, surface tension per state in kJ/mol/nm^2 (None: 0).  set_barostat returns to the isotropic move."""
+        fn = self._barostat_axis_entry('remd_set_barostat_axes')
+        p = np.ascontiguousarray(pressure, dtype=np.float64)
+        g = None if surface_tension is None else np.ascontiguousarray(surface_tension, dtype=np.float64)
+        if g is not None and g.shape != p.shape:
+            raise ValueError('one surface tension per state')
+        self._check(fn(self.h, len(p), _dp(p), _dp(g), int(kind), int(xy_or_scale_mask), int(zmode), int(frequency)), 'remd_set_barostat_axes')
+
+    def barostat_axis_stats(self):
+        """(volume step [R][3], attempted [R][3], accepted [R][3]) of the per-axis barostat, axes x, y, z."""
+        fn = self._barostat_axis_entry('remd_get_barostat_axis_stats')
+        vs = np.zeros((self.R, 3)); na = np.zeros((self.R, 3), np.int64); nc = np.zeros((self.R, 3), np.int64)
+        self._check(fn(self.h, _dp(vs), na.ctypes.data_as(c_int64_p), nc.ctypes.data_as(c_int64_p)), 'remd_get_barostat_axis_stats')
+        return vs, na, nc
 
     def set_energy_const_volume(self, volume):
         """The energy constants of set_states scale as volume / V with the replica's box (NPT + alchemical states)."""

@@ -288,7 +288,7 @@ int remd_set_replicas(remd_handle h, int R_global, int r_begin, int R_local, con
         h->d_ukl.reset();
         for (int g = 0; g < 4; ++g) h->d_force_g[g].reset();
         // per-replica scratch of the barostat and of the restart attempts is sized by R_local as well
-        h->d_baro.reset(); h->d_box_old.reset(); h->d_baro_x0.reset(); h->d_baro_f0.reset(); h->d_baro_U0.reset(); h->d_baro_acc.reset();
+        h->d_baro.reset(); h->d_baro_axis.reset(); h->d_box_old.reset(); h->d_baro_x0.reset(); h->d_baro_f0.reset(); h->d_baro_U0.reset(); h->d_baro_acc.reset();
         h->d_snap_pos.reset(); h->d_snap_vel.reset(); h->d_fin_pos.reset(); h->d_fin_vel.reset(); h->d_snap_box.reset(); h->d_fin_box.reset();
         h->d_snap_work.reset();
         REMD_TRY(h->d_pos.alloc(h, n));
@@ -538,6 +538,7 @@ static int phases_for(remd_ctx* h)
     if (!pme_fork && !(small_launches && want == 2)) return 1;
     if (h->measure_heat || h->measure_shadow || h->profiling == 2 || h->comm) return 1;
     if (h->baro_frequency > 0 && (int)h->pressure_host.size() != h->K) return 1;
+    if (h->baro_frequency > 0 && h->baro_kind != 0) return 1;                 // per-axis barostats run as one block
     for (char c : h->tokens) if (c != 'V' && c != 'R' && c != 'O') return 1;
     if (h->R < 2) return 1;
     if (want == 2) return 2;
@@ -917,6 +918,7 @@ int remd_set_barostat(remd_handle h, int K, const double* pressure, int frequenc
 {
     if (!h) return -1;
     hipSetDevice(h->device);
+    if (h->baro_kind != 0) { h->baro_kind = 0; h->config_version++; }          // the isotropic entry leaves axis mode (include/remd_hip_barostat.h)
     if (!pressure || frequency <= 0) { if (h->baro_frequency != 0) h->config_version++; h->baro_frequency = 0; return 0; }
     if (K != h->K) return remd_fail(h, -1, "remd_set_barostat: K differs from remd_set_states");
     std::vector<double> p(pressure, pressure + K);

@@ -2376,5 +2376,7 @@ int remd_assemble_ukl(remd_ctx* h, double* d_rows)
 {
     int rc = assemble_ukl_rows(h, d_rows);
     if (rc) return rc;
+    // - beta_l gamma_l A_xy(r) of a membrane barostat (barostat.hip), behind whichever of the three assemblies ran
+    if (h->baro_frequency > 0 && h->baro_kind == 2 && (rc = remd_tension_ukl(h, d_rows))) return rc;
     return h->n_restraints > 0 ? remd_restraints_ukl(h, d_rows) : 0;       // + beta_l (lambda_l - lambda_own) E_r of the restraints
 }

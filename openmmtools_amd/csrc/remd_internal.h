@@ -300,6 +300,11 @@ struct remd_ctx {
     double econst_vref = 0.0;          // volume at which the per-state energy constants were evaluated (they scale as 1/V); 0: constant
     dev_array<double> d_pressure;      // [K] kJ/mol/nm^3 (bar * N_A * 1e-25)
     dev_array<double> d_baro;          // [R][8]: volumeScale, attempted, accepted (adaptation window), total attempted, total accepted, dV, newV, oldV
+    // per-axis barostats (include/remd_hip_barostat.h; barostat.hip): baro_kind 0 = the isotropic move above
+    int baro_kind = 0, baro_axes = 0, baro_zmode = 0;     // (baro_axes: the anisotropic kind's scale mask / the membrane kind's xy mode)
+    std::vector<double> tension_host;
+    dev_array<double> d_tension;       // [K] kJ/mol/nm^2 (membrane kind)
+    dev_array<double> d_baro_axis;     // [R][REMD_BARO_AXIS_STRIDE]: see barostat.hip
     dev_array<float> d_box_old; dev_array<float4> d_baro_x0; dev_array<long long> d_baro_f0; dev_array<double> d_baro_U0; dev_array<int> d_baro_acc;
     bool box_uniform = false;          // every local replica has the same box (set_replicas; a barostat move clears it)
     int box_version = 0;               // bumped whenever the box edges on the device change (PME influence table)
@@ -445,6 +450,8 @@ int remd_work_buffers(remd_ctx* h);                    // heat / shadow-work acc
 // ---- forces.hip -------------------------------------------------------------------------
 int remd_barostat_attempt(remd_ctx* h);                      // barostat.hip
 int remd_barostat_buffers(remd_ctx* h);                      // (its per-replica state and scratch, allocated on first use)
+#define REMD_BARO_AXIS_STRIDE 24
+int remd_tension_ukl(remd_ctx* h, double* d_rows);           // membrane barostat: - beta_l gamma_l A_xy(r) into the u_kl rows
 int remd_nb_molecules(remd_ctx* h, const int** first, const int** size);   // molecule table of the nonbonded setup (device); 0: none
 int remd_minimize_impl(remd_ctx* h, double tolerance, int max_iterations, int32_t* converged, int32_t* n_iterations);
 void remd_nb_invalidate_sort(remd_ctx* h);            // the next force evaluation re-sorts the molecules

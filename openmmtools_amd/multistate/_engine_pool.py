@@ -91,6 +91,10 @@ class EnginePool:
         self._each('set_barostat', lambda g: (None if pressure is None else np.asarray(pressure, dtype=np.float64)[self._groups[g]],
                                               frequency))
 
+    def set_barostat_axes(self, *args, **kwargs):
+        raise NotImplementedError('EnginePool.set_barostat_axes: anisotropic and membrane barostats (include/remd_hip_barostat.h) are '
+                                  'not supported across several compatibility groups')
+
     def set_energy_const_volume(self, volume):
         self._each('set_energy_const_volume', lambda g: (volume,))
 

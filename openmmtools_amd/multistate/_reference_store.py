@@ -419,6 +419,9 @@ class ReferenceStoreWriter:
         for s in list(thermodynamic_states) + list(unsampled_states):
             if type(s).__name__ not in ('ThermodynamicState', 'CompoundThermodynamicState'):
                 return type(s).__name__
+            for f in s.system.getForces():                  # (the System XML of the per-axis barostats is not written: system_xml.to_xml)
+                if type(f).__name__ in ('MonteCarloAnisotropicBarostat', 'MonteCarloMembraneBarostat'):
+                    return 'a System with a %s' % type(f).__name__
             if (getattr(s.system, 'alchemical_region', None) is not None or getattr(s.system, 'alchemical_regions', None) is not None) and id(s.system) not in seen:
                 seen.add(id(s.system))
                 try:                                        # the factory's force set for this System (_alchemical_xml.py) or why not

@@ -18,6 +18,7 @@ import numpy as np
 from .. import mcmc, unit
 from ..utils import with_timer
 from ..system import system_to_desc
+from .._engine import BAROSTAT_ANISOTROPIC, BAROSTAT_MEMBRANE
 from .utils import SimulationNaNError
 from .comm import SingleProcessComm
 
@@ -653,6 +654,10 @@ class MultiStateSampler:
         # states.py:186-217: states of one standard System share a handle; several Systems => one handle per group behind the
         # same interface (_engine_pool.py), as the reference keeps one Context per compatible group (multistatesampler.py:1470-1490)
         from ..states import group_by_compatibility
+        # one barostat for the ensemble (kind, modes / scale flags, frequency): states that differ there cannot share the engine's move
+        barostats = {(s._barostat_signature(), s.barostat_frequency) for s in all_states if s.pressure is not None}
+        if len(barostats) > 1:
+            raise ValueError('the thermodynamic states carry different barostats: %s' % sorted(barostats, key=repr))
         groups, group_indices = group_by_compatibility(all_states)
         if len(groups) > 1:
             if any(getattr(g[0].system, 'alchemical_region', None) is not None or getattr(g[0].system, 'alchemical_regions', None) is not None for g in groups):
@@ -691,7 +696,16 @@ class MultiStateSampler:
         if any(p is not None for p in pressures):
             if any(p is None for p in pressures):
                 raise ValueError('NPT and NVT thermodynamic states cannot be mixed')
-            eng.set_barostat(np.array(pressures, dtype=np.float64), all_states[0].barostat_frequency)
+            barostat = all_states[0]._system_barostat()
+            kind = type(barostat).__name__
+            if kind == 'MonteCarloAnisotropicBarostat':          # per-axis moves: include/remd_hip_barostat.h
+                mask = int(barostat.getScaleX()) | int(barostat.getScaleY()) << 1 | int(barostat.getScaleZ()) << 2
+                eng.set_barostat_axes(np.array(pressures, dtype=np.float64), None, BAROSTAT_ANISOTROPIC, mask, 0, all_states[0].barostat_frequency)
+            elif kind == 'MonteCarloMembraneBarostat':
+                eng.set_barostat_axes(np.array(pressures, dtype=np.float64), np.array([s.surface_tension for s in all_states], dtype=np.float64),
+                                      BAROSTAT_MEMBRANE, barostat.getXYMode(), barostat.getZMode(), all_states[0].barostat_frequency)
+            else:
+                eng.set_barostat(np.array(pressures, dtype=np.float64), all_states[0].barostat_frequency)
             # the alchemical long-range constants were evaluated at the first sampler state's volume and scale as 1/V
             eng.set_energy_const_volume(self._sampler_states[0].volume if np.any(self._state_energy_constants(all_states) != 0.0) else 0.0)
             self._npt = True

@@ -113,19 +113,80 @@ class MonteCarloBarostatSettings:
 
 
 class ThermodynamicState:
+    _SUPPORTED_BAROSTATS = {'MonteCarloBarostat', 'MonteCarloAnisotropicBarostat', 'MonteCarloMembraneBarostat'}       # states.py:1656
+    _surface_tension = None                 # (states pickled before the NPgammaT ensemble was carried)
+
     def __init__(self, system, temperature=None, pressure=None, surface_tension=None):
-        """states.py:507-508, 1314-1353.  A System here carries no thermostat force a temperature could be read from and no membrane
-        barostat: no temperature is the reference's NO_THERMOSTAT, a surface tension its INCOMPATIBLE_ENSEMBLE."""
+        """states.py:507-508, 1314-1353.  A System here carries no thermostat force a temperature could be read from: no temperature
+        is the reference's NO_THERMOSTAT.  A MonteCarloAnisotropicBarostat or MonteCarloMembraneBarostat among the System's forces
+        (system.py) makes the state an NPT / NPgammaT one of that kind: pressure and surface tension are inferred from it when not
+        given; a surface tension without a membrane barostat is the reference's INCOMPATIBLE_ENSEMBLE."""
         self._system = system
-        if surface_tension is not None:
+        barostat = self._find_barostat(system)
+        is_membrane = type(barostat).__name__ == 'MonteCarloMembraneBarostat'
+        if surface_tension is not None and not is_membrane:
             raise ThermodynamicsError(ThermodynamicsError.INCOMPATIBLE_ENSEMBLE)          # states.py:1330-1331
         if temperature is None:
             raise ThermodynamicsError(ThermodynamicsError.NO_THERMOSTAT)                  # states.py:1336-1339
         self.temperature = temperature
+        if pressure is None and barostat is not None:
+            pressure = self._get_barostat_pressure(barostat)                              # states.py:1319-1324
         # NPT: the reference adds an openmm.MonteCarloBarostat (frequency 25) to the System (states.py:1177-1181); here the
         # pressure (kJ/mol/nm^3, i.e. `p * unit.bar`) and the frequency are handed to the engine's barostat
         self.pressure = pressure                                                 # Quantity -> kJ/mol/nm^3 (md units)
-        self.barostat_frequency = 25
+        self.barostat_frequency = 25 if barostat is None else int(barostat.getFrequency())
+        if is_membrane:                       # kJ/mol/nm^2, i.e. `g * unit.bar * unit.nanometer` (states.py:1326-1333)
+            self._surface_tension = float(barostat.getDefaultSurfaceTension() if surface_tension is None else to_md(surface_tension))
+
+    @classmethod
+    def _find_barostat(cls, system):
+        """states.py:1658-1696: the System's barostat force or None; more than one, an unknown one, or an anisotropic one the
+        reduced potential cannot describe (no scaled axis, or different pressures along the scaled axes) are errors."""
+        found = [f for f in system.getForces() if 'Barostat' in type(f).__name__]
+        if len(found) > 1:
+            raise ThermodynamicsError(ThermodynamicsError.MULTIPLE_BAROSTATS)
+        if not found:
+            return None
+        barostat = found[0]
+        if type(barostat).__name__ not in cls._SUPPORTED_BAROSTATS:
+            raise ThermodynamicsError(ThermodynamicsError.UNSUPPORTED_BAROSTAT, type(barostat).__name__)
+        if type(barostat).__name__ == 'MonteCarloAnisotropicBarostat':
+            scaled = [barostat.getScaleX(), barostat.getScaleY(), barostat.getScaleZ()]
+            if sum(scaled) == 0:
+                raise ThermodynamicsError(ThermodynamicsError.UNSUPPORTED_ANISOTROPIC_BAROSTAT)
+            active = [p for p, on in zip(barostat.getDefaultPressure(), scaled) if on]
+            if any(abs(p - active[0]) > 0 for p in active):
+                raise ThermodynamicsError(ThermodynamicsError.UNSUPPORTED_ANISOTROPIC_BAROSTAT)
+        return barostat
+
+    @staticmethod
+    def _get_barostat_pressure(barostat):
+        """states.py:1794-1802: an anisotropic barostat's pressure is the one along its first scaled axis."""
+        if type(barostat).__name__ == 'MonteCarloAnisotropicBarostat':
+            scaled = [barostat.getScaleX(), barostat.getScaleY(), barostat.getScaleZ()]
+            return barostat.getDefaultPressure()[scaled.index(True)]
+        return barostat.getDefaultPressure()
+
+    def _system_barostat(self):
+        """the System's barostat force while the state is at constant pressure (None at constant volume)"""
+        return None if self._pressure is None else self._find_barostat(self._system)
+
+    def _barostat_signature(self):
+        """what two states' barostats must share to run in one Context (states.py:1716-1721 compares the types; modes and scale
+        flags are part of the standard System the reference hashes): None at constant volume."""
+        if self._pressure is None:
+            return None
+        b = self._system_barostat()
+        name = type(b).__name__
+        if name == 'MonteCarloAnisotropicBarostat':
+            return (name, bool(b.getScaleX()), bool(b.getScaleY()), bool(b.getScaleZ()))
+        if name == 'MonteCarloMembraneBarostat':
+            return (name, int(b.getXYMode()), int(b.getZMode()))
+        return ('MonteCarloBarostat',)
+
+    def _is_barostat_type_consistent(self, barostat):
+        """states.py:1716-1721."""
+        return type(barostat) is type(self._system_barostat())
 
     @property
     def pressure(self):
@@ -140,16 +201,34 @@ class ThermodynamicState:
 
     @property
     def barostat(self):
-        """states.py:705-727: what the reference returns as a copy of the System's MonteCarloBarostat -- here the three numbers it
-        carries (pressure of this state, its temperature, the attempt frequency); None at constant volume."""
+        """states.py:705-727: a copy of the System's barostat force carrying this state's pressure, surface tension and temperature;
+        for a System without one (plain NPT: the reference adds an openmm.MonteCarloBarostat) the three numbers that barostat would
+        carry (pressure of this state, its temperature, the attempt frequency); None at constant volume."""
         if self._pressure is None:
             return None
-        return MonteCarloBarostatSettings(self._pressure, self._temperature, self.barostat_frequency)
+        force = self._system_barostat()
+        if force is None:
+            return MonteCarloBarostatSettings(self._pressure, self._temperature, self.barostat_frequency)
+        force = copy.deepcopy(force)
+        if type(force).__name__ == 'MonteCarloAnisotropicBarostat':
+            force.setDefaultPressure((self._pressure,) * 3)                                  # states.py:1780-1781
+        else:
+            force.setDefaultPressure(self._pressure)
+        force.setDefaultTemperature(self._temperature)
+        if self._surface_tension is not None:
+            force.setDefaultSurfaceTension(self._surface_tension)
+        return force
 
     @property
     def surface_tension(self):
-        """states.py:729-748: None -- a surface tension needs a System with a membrane barostat, which this package does not build."""
-        return None
+        """states.py:806-816: the surface tension (kJ/mol/nm^2) of a state whose System has a MonteCarloMembraneBarostat, else None."""
+        return self._surface_tension
+
+    @surface_tension.setter
+    def surface_tension(self, gamma):
+        if (self._surface_tension is None) != (gamma is None):                               # states.py:813-814
+            raise ThermodynamicsError(ThermodynamicsError.SURFACE_TENSION_NOT_SUPPORTED)
+        self._surface_tension = None if gamma is None else float(to_md(gamma))
 
     def get_volume(self, ignore_ensemble=False):
         """states.py:773-794: volume of the System's default periodic box (nm^3); None when the volume fluctuates (a pressure is set,
@@ -233,12 +312,14 @@ class ThermodynamicState:
         self.__dict__.update(state)
 
     @staticmethod
-    def _compute_reduced_potential(potential_energy, temperature, volume=None, pressure=None):
-        """states.py:1908-1917: u = beta (U + p V); energies per mole, so N_A is already folded in."""
+    def _compute_reduced_potential(potential_energy, temperature, volume=None, pressure=None, area_xy=None, surface_tension=None):
+        """states.py:1908-1917: u = beta (U + p V - gamma A_xy); energies per mole, so N_A is already folded in."""
         beta = 1.0 / (constants.kB * temperature)
         reduced = potential_energy
         if pressure is not None:
             reduced = reduced + pressure * volume
+        if area_xy is not None and surface_tension is not None:
+            reduced = reduced - surface_tension * area_xy
         return beta * reduced
 
     def reduced_potential(self, context_state):
@@ -248,17 +329,18 @@ class ThermodynamicState:
         if isinstance(sampler_state_or_energy, SamplerState):
             energy = sampler_state_or_energy.potential_energy
             volume = sampler_state_or_energy.volume
+            area_xy = sampler_state_or_energy.area_xy
             if energy is None:
                 raise ValueError('SamplerState has no cached potential energy')
         else:
-            energy, volume = float(sampler_state_or_energy), None
-        return self._compute_reduced_potential(energy, self._temperature, volume, self.pressure)
+            energy, volume, area_xy = float(sampler_state_or_energy), None, None
+        return self._compute_reduced_potential(energy, self._temperature, volume, self.pressure, area_xy, self.surface_tension)
 
     def is_state_compatible(self, thermodynamic_state):
         """states.py:994-1050: same standard system and same ensemble."""
         other = thermodynamic_state
         return (self._system is other._system or self._system.fingerprint() == other._system.fingerprint()) \
-            and (self.pressure is None) == (other.pressure is None)
+            and (self.pressure is None) == (other.pressure is None) and self._barostat_signature() == other._barostat_signature()
 
     def __deepcopy__(self, memo):
         # Systems are treated as immutable once wrapped (the reference deep-copies and re-hashes)
@@ -656,7 +738,8 @@ class CompoundThermodynamicState(ThermodynamicState):
     """states.py:2524-3046 restricted to AlchemicalState composable states: one (any suffix), or one per named alchemical region."""
 
     def __init__(self, thermodynamic_state, composable_states):
-        super().__init__(thermodynamic_state.system, thermodynamic_state.temperature, thermodynamic_state.pressure)
+        super().__init__(thermodynamic_state.system, thermodynamic_state.temperature, thermodynamic_state.pressure,
+                         thermodynamic_state.surface_tension)
         if len(composable_states) < 1 or not all(isinstance(c, (AlchemicalState, GlobalParameterState)) for c in composable_states):
             raise NotImplementedError('only AlchemicalState and GlobalParameterState composable states are supported')
         alchs = [c for c in composable_states if isinstance(c, AlchemicalState)]

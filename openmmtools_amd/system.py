@@ -299,6 +299,80 @@ class CMMotionRemover(Force):
         return self.frequency
 
 
+class MonteCarloAnisotropicBarostat(Force):
+    """openmm.MonteCarloAnisotropicBarostat: a Monte Carlo barostat that changes one box edge per attempt, among the axes whose scale
+    flag is set.  Pressure (three components) in kJ/mol/nm^3 (``p * unit.bar``), temperature in K.  Carries no energy: the engine's
+    per-axis barostat (include/remd_hip_barostat.h) makes the moves, for the states of a ThermodynamicState on this System."""
+
+    def __init__(self, defaultPressure, defaultTemperature, scaleX=True, scaleY=True, scaleZ=True, frequency=25):
+        super().__init__()
+        self.setDefaultPressure(defaultPressure)
+        self.setDefaultTemperature(defaultTemperature)
+        self._scale = (bool(scaleX), bool(scaleY), bool(scaleZ))
+        self.setFrequency(frequency)
+
+    def getDefaultPressure(self): return self._pressure
+    def setDefaultPressure(self, pressure):
+        from .unit import to_md
+        p = tuple(float(v) for v in np.asarray(to_md(pressure), dtype=np.float64).reshape(-1))
+        if len(p) != 3:
+            raise ValueError('MonteCarloAnisotropicBarostat takes the pressure along the three axes')
+        self._pressure = p
+    def getDefaultTemperature(self): return self._temperature
+    def setDefaultTemperature(self, temperature):
+        from .unit import to_md
+        self._temperature = float(to_md(temperature))
+    def getScaleX(self): return self._scale[0]
+    def getScaleY(self): return self._scale[1]
+    def getScaleZ(self): return self._scale[2]
+    def getFrequency(self): return self._frequency
+    def setFrequency(self, frequency): self._frequency = int(frequency)
+    def usesPeriodicBoundaryConditions(self): return False      # (as OpenMM's barostats answer: the other forces decide)
+
+
+class MonteCarloMembraneBarostat(Force):
+    """openmm.MonteCarloMembraneBarostat: pressure (kJ/mol/nm^3, ``p * unit.bar``) and surface tension (kJ/mol/nm^2,
+    ``g * unit.bar * unit.nanometer``) on a box whose xy plane holds a membrane; ``xymode`` couples or frees the two in-plane edges,
+    ``zmode`` frees or fixes z or ties it to the plane at constant volume.  Carries no energy, like the anisotropic barostat."""
+    XYIsotropic, XYAnisotropic = 0, 1
+    ZFree, ZFixed, ConstantVolume = 0, 1, 2
+
+    def __init__(self, defaultPressure, defaultSurfaceTension, defaultTemperature, xymode, zmode, frequency=25):
+        super().__init__()
+        self.setDefaultPressure(defaultPressure)
+        self.setDefaultSurfaceTension(defaultSurfaceTension)
+        self.setDefaultTemperature(defaultTemperature)
+        self.setXYMode(xymode)
+        self.setZMode(zmode)
+        self.setFrequency(frequency)
+
+    def getDefaultPressure(self): return self._pressure
+    def setDefaultPressure(self, pressure):
+        from .unit import to_md
+        self._pressure = float(to_md(pressure))
+    def getDefaultSurfaceTension(self): return self._surface_tension
+    def setDefaultSurfaceTension(self, surfaceTension):
+        from .unit import to_md
+        self._surface_tension = float(to_md(surfaceTension))
+    def getDefaultTemperature(self): return self._temperature
+    def setDefaultTemperature(self, temperature):
+        from .unit import to_md
+        self._temperature = float(to_md(temperature))
+    def getXYMode(self): return self._xymode
+    def setXYMode(self, mode):
+        if int(mode) not in (self.XYIsotropic, self.XYAnisotropic):
+            raise ValueError('unknown xy mode %r' % (mode,))
+        self._xymode = int(mode)
+    def getZMode(self): return self._zmode
+    def setZMode(self, mode):
+        if int(mode) not in (self.ZFree, self.ZFixed, self.ConstantVolume):
+            raise ValueError('unknown z mode %r' % (mode,))
+        self._zmode = int(mode)
+    def getFrequency(self): return self._frequency
+    def setFrequency(self, frequency): self._frequency = int(frequency)
+    def usesPeriodicBoundaryConditions(self): return False      # (as OpenMM's barostats answer: the other forces decide)
+
+
 class System:
     def __init__(self):
         self.masses = []
@@ -525,6 +599,8 @@ def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
             if gb is not None:
                 raise NotImplementedError('more than one implicit-solvent force (%s and %s)' % (type(gb).__name__, type(f).__name__))
             gb = f
+        elif isinstance(f, (MonteCarloAnisotropicBarostat, MonteCarloMembraneBarostat)):
+            pass        # no energy: the ThermodynamicState reads it (states.py) and the sampler hands it to the engine's barostat
         elif _is_restraint(f):
             from .forces import restraint_terms
             restraints.append(restraint_terms(f, system.masses))
