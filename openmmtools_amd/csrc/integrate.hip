@@ -1,31 +1,22 @@
-// Langevin splitting integrator kernels (gfx950): V / R / O substeps, constraints,
-// Maxwell-Boltzmann velocity draw, kinetic-energy reduction, CM-motion removal.
+// Langevin splitting integrator (gfx950): the chain kernel that runs the V / R / O substeps between two force evaluations and its
+// host step loop, the Maxwell-Boltzmann velocity draw, kinetic-energy reduction, CM-motion removal, heat / shadow work and
+// Metropolization.  The arithmetic of one constraint unit is in constraint_units.h (shared with resident.hip and minimize.hip).
 //
-// Reference semantics (restated):
-//   openmmtools/integrators.py:1404-1423  R: x += (dt/n_R) v ; constrain x ; v += (x - x1)/(dt/n_R) ; constrain v
-//   openmmtools/integrators.py:1425-1446  V: v += (dt/n_V) f/m ; constrain v
-//   openmmtools/integrators.py:1448-1460  O: v = a v + b sigma xi ; constrain v,  a = exp(-gamma h), b = sqrt(1-a^2),
-//                                            h = dt/max(1,n_O) (:1142-1146), sigma = sqrt(kT/m) (:1314)
+// Reference semantics (restated; the substeps: constraint_units.h):
 //   openmmtools/mcmc.py:710-711           setVelocitiesToTemperature (+ velocity constraints)
 //   openmmtools/integrators.py:1313       addUpdateContextState (CMMotionRemover acts here, once per step)
 //
-// Design: one thread owns one *constraint unit* (a rigid water, an X-H cluster, or a free
-// atom), keeps its <= 4 atoms' x and v in registers and runs the whole chain of substeps
-// between two force evaluations without touching HBM in between.  All replicas of the
-// rank are covered by one launch (blockIdx.y = replica).
-#include "remd_internal.h"
-#include "rng.h"
+// Design: one thread owns one *constraint unit* (a rigid water, an X-H cluster, or a free atom), keeps its <= 4 atoms' x and v in
+// registers and runs the whole chain of substeps between two force evaluations without touching HBM in between.  All replicas of
+// the rank are covered by one launch (blockIdx.y = replica).
+#include "constraint_units.h"
 #include <set>
-#include "pair_math.h"
-#include "listed_terms.h"
-#include "nocutoff_pair.h"
 
-#define UNIT_FREE   0
-#define UNIT_SETTLE 1
-#define UNIT_SHAKE  2
-#define MAX_TOK 24
 #define CHAIN_BIN_COLS 256       // mesh columns (nx) a chain workgroup can bin in its LDS counters
 
+// One launch of the chain.  It holds the fields of a step_prog (constraint_units.h) -- n, tok, o_index, hV, hR, a, b, nO: what prog_tok
+// and remd_step_prog_fill use -- under the same names but not as a base: the chain kernel's instruction stream depends on where they
+// sit among its arguments.
 struct chain_prog {
     int n;                 // tokens in this chain
     char tok[MAX_TOK];     // 'V','R','O','C' (C = subtract centre-of-mass velocity)
@@ -34,8 +25,7 @@ struct chain_prog {
     float hV, hR;          // dt/n_V, dt/n_R
     float hVg[4];          // multiple-time-step splittings: dt / (V tokens of force group g); tokens '0'..'3'
     const long long* Fg[4]; // forces of force group g ([R][3][Npad] fixed point, like the all-forces accumulator)
-    float a, b;            // OU coefficients
-    int nO;
+    float a, b; int nO;    // OU coefficients, O substeps per step
     int accumulate_momentum;  // after the chain, add sum(m v) into cmm buffer cmm_w
     int cmm_w, cmm_r;         // double-buffered momentum accumulators: 'C' reads cmm_r and clears the other one
     int zero_force;           // the chain ends with stale forces (an R after its last V): clear them for the next evaluation
@@ -44,245 +34,12 @@ struct chain_prog {
     int measure;              // bit 0: heat (kinetic-energy change of the O substeps), bit 1: kinetic part of the shadow work (V, R substeps)
 };
 
-// token t of the program, from registers: a dynamic index into the kernel-argument array is a scalar memory load per token on the
-// chain's critical path (the chain is a handful of wavefronts waiting for one thing after another: profiles/r05_15_chain_segments.txt);
-// the six words are loaded once with the other arguments
-__device__ __forceinline__ char chain_tok(const chain_prog& prog, int t)
-{
-    static_assert(MAX_TOK == 24, "six 32-bit words of tokens");
-    const unsigned int* w = reinterpret_cast<const unsigned int*>(prog.tok);
-    const unsigned int w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4], w5 = w[5];
-    const int q = t >> 2;
-    const unsigned int x = q == 0 ? w0 : q == 1 ? w1 : q == 2 ? w2 : q == 3 ? w3 : q == 4 ? w4 : w5;
-    return (char)((x >> ((t & 3) * 8)) & 0xffu);
-}
-
-// state of one constraint unit between the segments of a chain (registers)
-struct unit_regs { float3 x[4], v[4]; float im[4]; float heat, shadow;
-    int shake_it;                            // most Newton updates a position solve of this unit needed in this launch (X-H clusters)
-    float cmx, cmy, cmz; int have_cm;        // centre-of-mass velocity from an 'M' token of this launch, for the 'C' that follows it
-#ifdef CHAIN_STAMPS
-    unsigned long long* stamps; unsigned long long t_last;     // tools/chain_segments.py: per-token wall-clock of workgroup (0, 0)
-#endif
-};
-
-struct settle_const { float mO, mH, ra, rb, rc, dOH, dHH; };
-
-__device__ __forceinline__ float3 f3(float x, float y, float z) { return make_float3(x, y, z); }
-__device__ __forceinline__ float3 operator+(float3 a, float3 b) { return f3(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ float3 operator-(float3 a, float3 b) { return f3(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ float3 operator*(float3 a, float s) { return f3(a.x * s, a.y * s, a.z * s); }
-__device__ __forceinline__ float dot3(float3 a, float3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ float3 cross3(float3 a, float3 b) {
-    return f3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
-}
-
-// One wavefront per SIMD at best (a few hundred waves per launch): the chain kernel is bound by the LATENCY of its
-// dependent arithmetic, so the 1-ulp hardware reciprocal / square root / reciprocal square root replace the IEEE
-// expansions (~10 dependent instructions each) of '/', sqrtf and rsqrtf; fp32 SETTLE is ~1e-7 relative either way.
-__device__ __forceinline__ float frcp(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ float fsqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
-__device__ __forceinline__ float frsq(float x) { return __builtin_amdgcn_rsqf(x); }
-
-// Analytic SETTLE (Miyamoto & Kollman 1992) in coordinates relative to the old O position:
-// p0[] old (constrained) positions relative to A0 (p0[0] = 0), p1[] unconstrained new
-// positions relative to A0.  Returns constrained new positions (relative to A0) in p1.
-__device__ __forceinline__ void settle_positions(const settle_const& sc, const float3* p0, float3* p1)
-{
-    const float3 b0 = p0[1], c0 = p0[2];
-    const float M = sc.mO + 2.f * sc.mH;
-    const float3 d0 = (p1[0] * sc.mO + p1[1] * sc.mH + p1[2] * sc.mH) * frcp(M);
-    const float3 a1 = p1[0] - d0, b1 = p1[1] - d0, c1 = p1[2] - d0;
-    float3 Z = cross3(b0, c0);
-    float3 X = cross3(a1, Z);
-    float3 Y = cross3(Z, X);
-    X = X * frsq(dot3(X, X)); Y = Y * frsq(dot3(Y, Y)); Z = Z * frsq(dot3(Z, Z));
-    const float xb0 = dot3(X, b0), yb0 = dot3(Y, b0);
-    const float xc0 = dot3(X, c0), yc0 = dot3(Y, c0);
-    const float za1 = dot3(Z, a1);
-    const float xb1 = dot3(X, b1), yb1 = dot3(Y, b1), zb1 = dot3(Z, b1);
-    const float xc1 = dot3(X, c1), yc1 = dot3(Y, c1), zc1 = dot3(Z, c1);
-    const float sinphi = za1 * frcp(sc.ra);
-    const float cosphi = fsqrt(fmaxf(0.f, 1.f - sinphi * sinphi));
-    const float sinpsi = (zb1 - zc1) * frcp(2.f * sc.rc * cosphi);
-    const float cospsi = fsqrt(fmaxf(0.f, 1.f - sinpsi * sinpsi));
-    const float ya2 = sc.ra * cosphi;
-    const float xb2 = -sc.rc * cospsi;
-    const float yb2 = -sc.rb * cosphi - sc.rc * sinpsi * sinphi;
-    const float yc2 = -sc.rb * cosphi + sc.rc * sinpsi * sinphi;
-    const float alpha = xb2 * (xb0 - xc0) + yb0 * yb2 + yc0 * yc2;
-    const float beta  = xb2 * (yc0 - yb0) + xb0 * yb2 + xc0 * yc2;
-    const float gamma = xb0 * yb1 - xb1 * yb0 + xc0 * yc1 - xc1 * yc0;
-    const float al2be2 = alpha * alpha + beta * beta;
-    const float sintheta = (alpha * gamma - beta * fsqrt(fmaxf(0.f, al2be2 - gamma * gamma))) * frcp(al2be2);
-    const float costheta = fsqrt(fmaxf(0.f, 1.f - sintheta * sintheta));
-    const float xa3 = -ya2 * sintheta, ya3 = ya2 * costheta, za3 = za1;
-    const float xb3 = xb2 * costheta - yb2 * sintheta, yb3 = xb2 * sintheta + yb2 * costheta, zb3 = zb1;
-    const float xc3 = -xb2 * costheta - yc2 * sintheta, yc3 = -xb2 * sintheta + yc2 * costheta, zc3 = zc1;
-    p1[0] = X * xa3 + Y * ya3 + Z * za3 + d0;
-    p1[1] = X * xb3 + Y * yb3 + Z * zb3 + d0;
-    p1[2] = X * xc3 + Y * yc3 + Z * zc3 + d0;
-}
-
-// Analytic velocity constraint for a rigid triangle: remove the relative velocity along the
-// three bonds by solving the 3x3 Lagrange-multiplier system (Cramer's rule).
-__device__ __forceinline__ void settle_velocities(float imA, float imB, float imC, const float3* p, float3* v)
-{
-    float3 eAB = p[1] - p[0], eBC = p[2] - p[1], eCA = p[0] - p[2];
-    eAB = eAB * frsq(dot3(eAB, eAB)); eBC = eBC * frsq(dot3(eBC, eBC)); eCA = eCA * frsq(dot3(eCA, eCA));
-    const float dAB = dot3(v[1] - v[0], eAB), dBC = dot3(v[2] - v[1], eBC), dCA = dot3(v[0] - v[2], eCA);
-    const float cAB_BC = dot3(eAB, eBC), cAB_CA = dot3(eAB, eCA), cBC_CA = dot3(eBC, eCA);
-    const float m00 = imA + imB,        m01 = -cAB_BC * imB,  m02 = -cAB_CA * imA;
-    const float m10 = -cAB_BC * imB,    m11 = imB + imC,      m12 = -cBC_CA * imC;
-    const float m20 = -cAB_CA * imA,    m21 = -cBC_CA * imC,  m22 = imC + imA;
-    const float det = m00 * (m11 * m22 - m12 * m21) - m01 * (m10 * m22 - m12 * m20) + m02 * (m10 * m21 - m11 * m20);
-    const float idet = frcp(det);
-    const float tAB = (dAB * (m11 * m22 - m12 * m21) - m01 * (dBC * m22 - m12 * dCA) + m02 * (dBC * m21 - m11 * dCA)) * idet;
-    const float tBC = (m00 * (dBC * m22 - m12 * dCA) - dAB * (m10 * m22 - m12 * m20) + m02 * (m10 * dCA - dBC * m20)) * idet;
-    const float tCA = (m00 * (m11 * dCA - dBC * m21) - m01 * (m10 * dCA - dBC * m20) + dAB * (m10 * m21 - m11 * m20)) * idet;
-    v[0] = v[0] + (eAB * tAB - eCA * tCA) * imA;
-    v[1] = v[1] + (eBC * tBC - eAB * tAB) * imB;
-    v[2] = v[2] + (eCA * tCA - eBC * tBC) * imC;
-}
-
-// K x K linear solve (K <= 3: the constraints of one X-H star cluster), Cramer's rule, everything in registers
-template <int K>
-__device__ __forceinline__ void solve_small(const float (&A)[3][3], const float (&b)[3], float (&x)[3])
-{
-    if (K == 1) {
-        x[0] = b[0] * frcp(A[0][0]); x[1] = 0.f; x[2] = 0.f;
-    } else if (K == 2) {
-        const float idet = frcp(A[0][0] * A[1][1] - A[0][1] * A[1][0]);
-        x[0] = (b[0] * A[1][1] - A[0][1] * b[1]) * idet;
-        x[1] = (A[0][0] * b[1] - b[0] * A[1][0]) * idet;
-        x[2] = 0.f;
-    } else {
-        const float c00 = A[1][1] * A[2][2] - A[1][2] * A[2][1], c01 = A[1][0] * A[2][2] - A[1][2] * A[2][0], c02 = A[1][0] * A[2][1] - A[1][1] * A[2][0];
-        const float idet = frcp(A[0][0] * c00 - A[0][1] * c01 + A[0][2] * c02);
-        x[0] = (b[0] * c00 - A[0][1] * (b[1] * A[2][2] - A[1][2] * b[2]) + A[0][2] * (b[1] * A[2][1] - A[1][1] * b[2])) * idet;
-        x[1] = (A[0][0] * (b[1] * A[2][2] - A[1][2] * b[2]) - b[0] * c01 + A[0][2] * (A[1][0] * b[2] - b[1] * A[2][0])) * idet;
-        x[2] = (A[0][0] * (A[1][1] * b[2] - b[1] * A[2][1]) - A[0][1] * (A[1][0] * b[2] - b[1] * A[2][0]) + b[0] * c02) * idet;
-    }
-}
-
-// Position constraints of a star cluster (central atom 0 bonded to atoms 1..NAT-1): p0 old constrained positions, p1
-// unconstrained new positions (both relative to the old central atom).  The SHAKE displacements act along the OLD bond
-// vectors r0_q with one multiplier per bond; instead of Gauss-Seidel sweeps over the bonds (6-10 sweeps, data dependent,
-// and the one wavefront holding the solute's clusters used to set the duration of the whole integrator launch) the K x K
-// system  |s_q + sum_p B_qp lam_p r0_p|^2 = d_q^2,  B_qp = 1/m_0 + delta_qp / m_q,  is solved by Newton iterations with the
-// exact Jacobian (quadratic convergence: a half step moves bond lengths by < 1 %, so two iterations reach fp32 round-off).
-// Round 6: the iteration runs until every bond of the cluster is within the integrator's constraint tolerance (integrators.py:1416-1418:
-// addConstrainPositions works to getConstraintTolerance(), a RELATIVE distance error) -- | |r|^2 - d^2 | <= 2 tol d^2 -- with tol no
-// smaller than what fp32 lengths can hold (the caller passes max(tol, 2e-7)) and at most SHAKE_MAX_IT updates; before it was a fixed
-// three updates whatever the tolerance.  Returns the number of updates made, SHAKE_MAX_IT + 1 when the bound was reached unconverged.
-// NAT is a compile-time constant so that every array lives in registers (no scratch).
-#define SHAKE_MAX_IT 8
-template <int NAT>
-__device__ __forceinline__ int shake_positions(const float* im, const float* d, float tol, const float3* p0, float3* p1)
-{
-    constexpr int K = NAT - 1;
-    float3 r0[3], sv[3];
-    float lam[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        r0[q] = q < K ? p0[q + 1] - p0[0] : f3(0, 0, 0);
-        sv[q] = q < K ? p1[q + 1] - p1[0] : f3(0, 0, 0);
-    }
-    const float tol2 = 2.f * tol;
-    int it = 0;
-    for (;; ++it) {
-        float3 acc = f3(0, 0, 0);                                   // im0 * sum_p lam_p r0_p (the central atom's share)
-#pragma unroll
-        for (int p = 0; p < K; ++p) acc = acc + r0[p] * (lam[p] * im[0]);
-        float J[3][3], g[3], dl[3];
-        bool converged = true;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            if (q < K) {
-                const float3 cur = sv[q] + acc + r0[q] * (lam[q] * im[q + 1]);
-                const float d2 = d[q] * d[q];
-                g[q] = d2 - dot3(cur, cur);
-                converged = converged && fabsf(g[q]) <= tol2 * d2;
-#pragma unroll
-                for (int p = 0; p < 3; ++p) J[q][p] = p < K ? 2.f * dot3(cur, r0[p]) * (im[0] + (p == q ? im[q + 1] : 0.f)) : 0.f;
-            } else {
-                g[q] = 0.f;
-#pragma unroll
-                for (int p = 0; p < 3; ++p) J[q][p] = p == q ? 1.f : 0.f;
-            }
-        }
-        if (converged) break;
-        if (it == SHAKE_MAX_IT) { it = SHAKE_MAX_IT + 1; break; }
-        solve_small<K>(J, g, dl);
-#pragma unroll
-        for (int q = 0; q < K; ++q) lam[q] += dl[q];
-    }
-#pragma unroll
-    for (int q = 0; q < K; ++q) {
-        p1[0] = p1[0] - r0[q] * (lam[q] * im[0]);
-        p1[q + 1] = p1[q + 1] + r0[q] * (lam[q] * im[q + 1]);
-    }
-    return it;
-}
-
-// Velocity constraints of a star cluster: the multipliers solve a K x K LINEAR system exactly (no iteration):
-//   sum_p (1/m_0 r_q.r_p + delta_qp r_q.r_q / m_q) mu_p = r_q . (v_q - v_0)
-template <int NAT>
-__device__ __forceinline__ void shake_velocities(const float* im, float /*tol*/, const float3* p, float3* v)
-{
-    constexpr int K = NAT - 1;
-    float3 r[3];
-    float A[3][3], b[3], mu[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) r[q] = q < K ? p[q + 1] - p[0] : f3(0, 0, 0);
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        b[q] = q < K ? dot3(r[q], v[q + 1] - v[0]) : 0.f;
-#pragma unroll
-        for (int pp = 0; pp < 3; ++pp)
-            A[q][pp] = (q < K && pp < K) ? dot3(r[q], r[pp]) * (im[0] + (pp == q ? im[q + 1] : 0.f)) : (pp == q ? 1.f : 0.f);
-    }
-    solve_small<K>(A, b, mu);
-#pragma unroll
-    for (int q = 0; q < K; ++q) {
-        v[0] = v[0] + r[q] * (mu[q] * im[0]);
-        v[q + 1] = v[q + 1] - r[q] * (mu[q] * im[q + 1]);
-    }
-}
-
-template <int TYPE, int NAT>
-__device__ __forceinline__ void constrain_v(const settle_const& sc, const float* im, float tol, float3* v, const float3* x)
-{
-    if (TYPE == UNIT_SETTLE) {
-        float3 p[3] = { f3(0, 0, 0), x[1] - x[0], x[2] - x[0] };
-        settle_velocities(im[0], im[1], im[2], p, v);
-    } else if (TYPE == UNIT_SHAKE) {
-        float3 p[NAT];
-#pragma unroll
-        for (int k = 0; k < NAT; ++k) p[k] = x[k] - x[0];
-        shake_velocities<NAT>(im, tol, p, v);
-    }
-}
-
-__device__ __forceinline__ float3 gaussian3(uint64_t seed, uint32_t stream, uint32_t atom, uint32_t replica, uint64_t t)
-{
-    philox4 w = remd_philox(seed, stream, atom, replica, t);
-    const float r1 = fsqrt(-2.f * __logf(remd_u23(w.w[0])));
-    const float r2 = fsqrt(-2.f * __logf(remd_u23(w.w[2])));
-    float s1, c1, s2, c2;
-    __sincosf(6.2831853071795865f * remd_u23(w.w[1]), &s1, &c1);
-    __sincosf(6.2831853071795865f * remd_u23(w.w[3]), &s2, &c2);
-    (void)s2;
-    return f3(r1 * c1, r1 * s1, r2 * c2);
-}
-
 // the whole chain of substeps for one constraint unit, everything in registers
 template <int TYPE, int NAT>
 __device__ __forceinline__ float3 run_unit(const chain_prog& prog, const int* idx, const float* dist, const settle_const& sc,
                                           float tol, int Npad, float4* __restrict__ P, float4* __restrict__ V,
-                                          const long long* F, long long* Fw, const float* __restrict__ invmass, float kT,
-                                          uint32_t rg, uint64_t seed, const long long* __restrict__ cmm_r, float inv_total_mass,
-                                          const remd_chain_bins& bins, int r,
+                                          const long long* F, long long* Fw, float kT, uint32_t rg, uint64_t seed,
+                                          const long long* __restrict__ cmm_r, float inv_total_mass, const remd_chain_bins& bins, int r,
                                           unit_regs& S, int t0, int t1, bool first, bool last,
                                           float4* __restrict__ Xold, float4* __restrict__ Vold)
 {
@@ -300,7 +57,7 @@ __device__ __forceinline__ float3 run_unit(const chain_prog& prog, const int* id
 #endif
     }
     for (int t = t0; t < t1; ++t) {
-        const char tok = chain_tok(prog, t);
+        const char tok = prog_tok(prog, t);
         const bool is_v = tok == 'V' || (tok >= '0' && tok <= '3');
         const float ke0 = ((prog.measure & 1) && tok == 'O') || ((prog.measure & 2) && (is_v || tok == 'R')) ? unit_ke() : 0.f;
         if (tok == '{') {
@@ -314,61 +71,25 @@ __device__ __forceinline__ float3 run_unit(const chain_prog& prog, const int* id
             // all forces, or the forces of one force group with that group's share of the time step (integrators.py:1437-1440)
             const long long* Ft = tok == 'V' ? F : prog.Fg[tok - '0'] + (size_t)r * 3 * Npad;
             const float hv = tok == 'V' ? prog.hV : prog.hVg[tok - '0'];
-#pragma unroll
-            for (int k = 0; k < NAT; ++k) {
-                const float s = hv * im[k] * (1.0f / 4294967296.0f);
-                v[k].x += s * (float)Ft[idx[k]];
-                v[k].y += s * (float)Ft[Npad + idx[k]];
-                v[k].z += s * (float)Ft[2 * Npad + idx[k]];
-            }
+            unit_kick_add<NAT>(hv, idx, Ft, Npad, S);
 #ifdef CHAIN_STAMPS
             if (S.stamps && t == 0) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long now = wall_clock64(); atomicAdd(&S.stamps[1 + 22], now - S.t_last); S.t_last = now; }
 #endif
             constrain_v<TYPE, NAT>(sc, im, tol, v, x);
         } else if (tok == 'R') {
-            if (TYPE == UNIT_FREE) {
-#pragma unroll
-                for (int k = 0; k < NAT; ++k) x[k] = x[k] + v[k] * prog.hR;
-            } else {
-                // relative coordinates (origin = old position of atom 0) keep fp32 precision
-                float3 p0[NAT], p1[NAT], q[NAT];
-#pragma unroll
-                for (int k = 0; k < NAT; ++k) {
-                    p0[k] = x[k] - x[0];
-                    p1[k] = p0[k] + v[k] * prog.hR;
-                    q[k] = p1[k];
-                }
-                if (TYPE == UNIT_SETTLE) settle_positions(sc, p0, p1);
-                else S.shake_it = max(S.shake_it, shake_positions<NAT>(im, dist, tol, p0, p1));
-                const float ih = frcp(prog.hR);
-                const float3 org = x[0];
-#pragma unroll
-                for (int k = 0; k < NAT; ++k) {
-                    v[k] = v[k] + (p1[k] - q[k]) * ih;          // integrators.py:1417
-                    x[k] = org + p1[k];
-                }
-                constrain_v<TYPE, NAT>(sc, im, tol, v, x);
-            }
+            unit_drift<TYPE, NAT>(prog.hR, dist, sc, tol, S);
         } else if (tok == 'O') {
             const uint64_t cnt = (uint64_t)prog.step[t] * (uint64_t)prog.nO + (uint64_t)prog.o_index[t];
-#pragma unroll
-            for (int k = 0; k < NAT; ++k) {
-                const float3 xi = gaussian3(seed, REMD_STREAM_OU, (uint32_t)idx[k], rg, cnt);
-                const float sig = prog.b * fsqrt(kT * im[k]);
-                v[k].x = prog.a * v[k].x + sig * xi.x;
-                v[k].y = prog.a * v[k].y + sig * xi.y;
-                v[k].z = prog.a * v[k].z + sig * xi.z;
-            }
-            constrain_v<TYPE, NAT>(sc, im, tol, v, x);
+            unit_ou<TYPE, NAT>(prog.a, prog.b, kT, cnt, seed, rg, idx, sc, tol, S);
         } else if (tok == 'C') {
             // CMMotionRemover: v -= P/M with P accumulated by the previous chain or by the 'M' token in front (read at the
             // coherence point: other workgroups added to it by atomics during this launch)
             float sx, sy, sz;
             if (S.have_cm) { sx = S.cmx; sy = S.cmy; sz = S.cmz; }
             else {
-                sx = (float)__hip_atomic_load(&cmm_r[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) * (1.0f / 4294967296.0f) * inv_total_mass;
-                sy = (float)__hip_atomic_load(&cmm_r[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) * (1.0f / 4294967296.0f) * inv_total_mass;
-                sz = (float)__hip_atomic_load(&cmm_r[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) * (1.0f / 4294967296.0f) * inv_total_mass;
+                sx = (float)__hip_atomic_load(&cmm_r[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) * FIXED_TO_F32 * inv_total_mass;
+                sy = (float)__hip_atomic_load(&cmm_r[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) * FIXED_TO_F32 * inv_total_mass;
+                sz = (float)__hip_atomic_load(&cmm_r[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) * FIXED_TO_F32 * inv_total_mass;
             }
 #pragma unroll
             for (int k = 0; k < NAT; ++k) { v[k].x -= sx; v[k].y -= sy; v[k].z -= sz; }
@@ -428,6 +149,8 @@ __device__ __forceinline__ void integrate_chain_body(chain_prog prog, int n_unit
     // masses, the state's temperature.  Positions and velocities are written by the previous chain launch of this stream only.
     const int uidx = blockIdx.x * blockDim.x + threadIdx.x;
     const int r = blockIdx.y;
+    // (written out, not load_unit_row / load_unit_atoms: through the shared loaders this kernel, at its register limit, is allocated
+    //  differently -- 110 -> 134 AGPRs)
     int4 a4 = make_int4(-1, -1, -1, -1);
     int type = UNIT_FREE;
     float dist[3] = { 0.f, 0.f, 0.f };
@@ -519,15 +242,11 @@ __device__ __forceinline__ void integrate_chain_body(chain_prog prog, int n_unit
     // segments of the token program, split at 'M' (momentum sum + barrier over the replica's workgroups)
     for (int t0 = 0;;) {
         int t1 = t0;
-        while (t1 < prog.n && chain_tok(prog, t1) != 'M') ++t1;
+        while (t1 < prog.n && prog_tok(prog, t1) != 'M') ++t1;
         const bool first = t0 == 0, last = t1 == prog.n;
         if (active) {
-#define RUN(TY, NA) mom = run_unit<TY, NA>(prog, idx, dist, sc, tol, Npad, P, V, F, Fw, invmass, kT, rg, seed, cr, inv_total_mass, unit_bins, r, S, t0, t1, first, last, xold ? xold + (size_t)r * Npad : nullptr, vold ? vold + (size_t)r * Npad : nullptr)
-            if (type == UNIT_SETTLE) RUN(UNIT_SETTLE, 3);
-            else if (type == UNIT_FREE) { if (a4.y < 0) RUN(UNIT_FREE, 1); else RUN(UNIT_FREE, 4); }
-            else if (a4.z < 0) RUN(UNIT_SHAKE, 2);
-            else if (a4.w < 0) RUN(UNIT_SHAKE, 3);
-            else RUN(UNIT_SHAKE, 4);
+#define RUN(TY, NA) mom = run_unit<TY, NA>(prog, idx, dist, sc, tol, Npad, P, V, F, Fw, kT, rg, seed, cr, inv_total_mass, unit_bins, r, S, t0, t1, first, last, xold ? xold + (size_t)r * Npad : nullptr, vold ? vold + (size_t)r * Npad : nullptr)
+            UNIT_LADDER(type, a4, RUN);
 #undef RUN
         }
         if (last) break;
@@ -578,9 +297,9 @@ __device__ __forceinline__ void integrate_chain_body(chain_prog prog, int n_unit
                 atomicAdd(&s_tot[threadIdx.x % 3], (unsigned long long)part);
             }
             __syncthreads();
-            S.cmx = (float)(long long)s_tot[0] * (1.0f / 4294967296.0f) * inv_total_mass;
-            S.cmy = (float)(long long)s_tot[1] * (1.0f / 4294967296.0f) * inv_total_mass;
-            S.cmz = (float)(long long)s_tot[2] * (1.0f / 4294967296.0f) * inv_total_mass;
+            S.cmx = (float)(long long)s_tot[0] * FIXED_TO_F32 * inv_total_mass;
+            S.cmy = (float)(long long)s_tot[1] * FIXED_TO_F32 * inv_total_mass;
+            S.cmz = (float)(long long)s_tot[2] * FIXED_TO_F32 * inv_total_mass;
             S.have_cm = 1;
             __syncthreads();                                    // (s_pm / s_tot may be written again by a second 'M' of this launch)
 #ifdef CHAIN_STAMPS
@@ -723,12 +442,9 @@ void assign_velocities_kernel(int n_units, const int4* __restrict__ unit_atoms,
     float4* V = vel + (size_t)r * Npad;
     const float kT = frcp((float)beta[labels[r_begin + r]]);       // fp32 state: 1 ulp of kT is below its own rounding
     const uint32_t rg = noise_id ? noise_id[r] : (uint32_t)(r_begin + r);
-    if (type == UNIT_SETTLE) assign_unit<UNIT_SETTLE, 3>(idx, sc, tol, P, V, invmass, kT, rg, seed, iteration);
-    else if (type == UNIT_FREE) { if (a4.y < 0) assign_unit<UNIT_FREE, 1>(idx, sc, tol, P, V, invmass, kT, rg, seed, iteration);
-                                  else assign_unit<UNIT_FREE, 4>(idx, sc, tol, P, V, invmass, kT, rg, seed, iteration); }
-    else if (a4.z < 0) assign_unit<UNIT_SHAKE, 2>(idx, sc, tol, P, V, invmass, kT, rg, seed, iteration);
-    else if (a4.w < 0) assign_unit<UNIT_SHAKE, 3>(idx, sc, tol, P, V, invmass, kT, rg, seed, iteration);
-    else assign_unit<UNIT_SHAKE, 4>(idx, sc, tol, P, V, invmass, kT, rg, seed, iteration);
+#define RUN(TY, NA) assign_unit<TY, NA>(idx, sc, tol, P, V, invmass, kT, rg, seed, iteration)
+    UNIT_LADDER(type, a4, RUN);
+#undef RUN
 }
 
 // KE = sum 1/2 m v^2 per replica: per-lane partial -> wave shuffle -> LDS -> one value per block,
@@ -762,11 +478,6 @@ __global__ void check_finite_kernel(int N, int Npad, const float4* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------
-struct unit_tables {
-    int n_units = 0;
-    dev_array<int4> d_atoms; dev_array<unsigned char> d_type; dev_array<float> d_dist;
-    settle_const sc{};
-};
 void remd_table_deleter::operator()(unit_tables* t) const { delete t; }
 
 int remd_build_constraints(remd_ctx* h, const remd_system_desc* d)
@@ -908,7 +619,7 @@ static void launch_chain(remd_ctx* h, const unit_tables& ut, const chain_prog& p
     // Removed; one workgroup per CU leaves 160 registers per lane for the kernels the chain waits for.)
     const remd_handover::wait_t join = h->next.take_wait();      // the evaluation in front left it for this launch
     hipLaunchKernelGGL(integrate_chain_kernel, grid, dim3(256), 0, h->stream, prog, ut.n_units, ut.d_atoms, ut.d_type,
-                       ut.d_dist, ut.sc, (float)fmax(h->constraint_tol, REMD_CONSTRAINT_TOL_FLOOR), h->Npad, h->d_pos, h->d_vel, h->d_force,
+                       ut.d_dist, ut.sc, remd_constraint_tol(h), h->Npad, h->d_pos, h->d_vel, h->d_force,
                        h->d_invmass, h->d_labels, h->d_beta, h->r_begin, h->seed, h->d_cmm,
                        (float)(h->total_mass > 0 ? 1.0 / h->total_mass : 0.0),
                        join.seq ? h->d_sync + 1 : (unsigned int*)nullptr, join.seq, bins, h->d_chain_sync, h->d_sync + 2,
@@ -969,559 +680,6 @@ int remd_work_buffers(remd_ctx* h)
     return 0;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// Resident small-system path (round 3).  For systems of up to 1024 atoms without constraints, mesh or listed terms (the
-// reference's HarmonicOscillator and LennardJonesFluid test systems: BASELINE configs 1 and 2) an MD step of the regular path
-// is a chain of ~8 dependent launches of a few microseconds each and the GPU idles in between (LJ fluid, 16 replicas: 30 us
-// per step for 8 k atoms).  mcmc.py:700-719 is ONE integrator.step(n_steps) per move, so the MI355X-first shape of that is
-// ONE launch per propagation: a workgroup owns a replica, a thread owns an atom (x, v, f, 1/m and the pair parameters stay in
-// registers for all n_steps), positions and a Verlet list live in LDS:
-//   * neighbour list: all pairs inside r_c + skin, FULL list (every pair from both sides: no atomics, every atom sums its
-//     forces in list order -- deterministic), rebuilt by an all-pairs pass over the LDS positions whenever any atom has moved
-//     more than skin / 2 since the last build (a workgroup vote at every evaluation): the list is a superset of the pairs
-//     inside r_c at all times, the cutoff test in the force loop is exact;
-//   * force evaluation where the splitting string needs one (a V after an R), with the pair arithmetic of the regular
-//     kernels (pair_math.h: LJ + switch, soft-core for alchemical / non-alchemical pairs at the replica's lambda);
-//   * V / R / O / centre-of-mass removal as in the chain kernel, same Philox streams (atom, global replica, global O-substep
-//     counter): the trajectories follow the regular path to fp32 summation order.
-// Two workgroup barriers per force evaluation, nothing else between steps.
-struct resident_prog {
-    int n; char tok[MAX_TOK]; int o_index[MAX_TOK];
-    float hV, hR, a, b; int nO;
-    int n_steps, cmm_frequency; long long gstep0, first_step;
-};
-struct resident_sys {
-    int N, Npad, method, alch, n_ext, list_cap;
-    nb_params p;
-    float skin, ext_K, ext_x0, inv_total_mass;
-    const float4* param; const float* rep_lam; const int* ext_atoms; const float* invmass; const float* box;
-    const int64_t* labels; const double* beta; int r_begin; uint64_t seed; const unsigned int* noise_id;
-    unsigned int* err;
-};
-
-#ifndef RES_UNROLL
-#define RES_UNROLL 2
-#endif
-#define RES_FSCALE 8192.f       // LDS force accumulators: 32-bit fixed point, 2^-13 kJ/mol/nm (|F| < 2.6e5 kJ/mol/nm: r > 0.19 nm for argon)
-
-// LJ + switch of one pair without branches: the soft-core form  x = 1 / (sc + (r / sigma)^6),  U = lam eps4 x (x - 1)  IS
-// Lennard-Jones for sc = 0, lam = 1 (alchemy.py:1383-1388 with softcore_c = 6), so alchemical / non-alchemical pairs differ from
-// the rest only in two selected constants; the switching polynomial is evaluated at x clamped to [0, 1].  Hardware reciprocals
-// (1 ulp).  Returns dU/dr / r, so that F_i = fr * (x_j - x_i).
-template <bool ALCH>
-__device__ __forceinline__ float resident_pair(const nb_params& p, float r2, float4 pi, float4 pj, float lam_a, float sc)
-{
-    const float inv_r = __builtin_amdgcn_rsqf(r2), r = r2 * inv_r;
-    const float sig = pi.y + pj.y, eps4 = pi.z * pj.z;
-    const bool soft = ALCH && ((pi.w != pj.w) || pi.w > 1.5f);      // (w = 2: annihilate_sterics, pair_math.h)
-    const float lam = soft ? lam_a : 1.f, s0 = soft ? sc : 0.f;
-    const float is2 = __builtin_amdgcn_rcpf(sig * sig);
-    const float q2 = r2 * is2, t = q2 * q2 * q2;
-    const float x = __builtin_amdgcn_rcpf(s0 + t);
-    float U = lam * eps4 * x * (x - 1.f);
-    float dUdr = lam * eps4 * (2.f * x - 1.f) * (-x * x * 6.f * t * inv_r);
-    const float xs = fminf(fmaxf((r - p.rs) * p.inv_sw, 0.f), 1.f);          // no switch: inv_sw = 0
-    const float Sw = 1.f + xs * xs * xs * (-10.f + xs * (15.f - 6.f * xs));
-    const float dS = xs * xs * (-30.f + xs * (60.f - 30.f * xs)) * p.inv_sw;
-    dUdr = Sw * dUdr + U * dS;
-    return dUdr * inv_r;
-}
-
-template <bool ALCH>
-__global__ __launch_bounds__(1024)
-void resident_md_kernel(resident_prog prog, resident_sys S, float4* __restrict__ pos, float4* __restrict__ vel)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int N = S.N, T = blockDim.x, tid = threadIdx.x, r = blockIdx.x, nw = T >> 6;
-    float4* s_pos = reinterpret_cast<float4*>(smem);                      // [T] positions (w: unused)
-    float4* s_par = s_pos + T;                                            // [T] pair parameters of every atom
-    float* s_red = reinterpret_cast<float*>(s_par + T);                   // [16][4] wavefront partial sums; the last words:
-    int* s_vote = reinterpret_cast<int*>(s_red + 60);                     // [2] "somebody left its skin / 2 sphere", by evaluation parity
-    int* s_np = reinterpret_cast<int*>(s_red + 62);                       // pairs in the list
-    int* s_f = reinterpret_cast<int*>(s_red + 64);                        // [3][T] fixed-point force accumulators
-    unsigned long long* s_fl = reinterpret_cast<unsigned long long*>(s_f + 3 * T + (T & 1));   // [3][T] the same in 64 bits: contributions too large for the fast path
-    unsigned int* s_pairs = reinterpret_cast<unsigned int*>(s_fl + 3 * T); // [cap] i | j << 16, i < j
-    const bool active = tid < N;
-    float4* P = pos + (size_t)r * S.Npad;
-    float4* V = vel + (size_t)r * S.Npad;
-    float3 x = f3(0, 0, 0), v = f3(0, 0, 0), f = f3(0, 0, 0), xref = f3(0, 0, 0);
-    float im = 0.f;
-    float4 par = make_float4(0, 0, 0, 0);
-    if (active) {
-        const float4 p4 = P[tid], v4 = V[tid];
-        x = f3(p4.x, p4.y, p4.z); v = f3(v4.x, v4.y, v4.z);
-        im = S.invmass[tid];
-        if (S.method >= 0) par = S.param[tid];
-    }
-    s_par[tid] = par;
-    s_f[tid] = 0; s_f[T + tid] = 0; s_f[2 * T + tid] = 0;
-    s_fl[tid] = 0ull; s_fl[T + tid] = 0ull; s_fl[2 * T + tid] = 0ull;
-    bool ext = false;
-    for (int k = 0; k < S.n_ext; ++k) ext |= (S.ext_atoms[k] == tid);
-    const float Lx = S.box[4 * r], Ly = S.box[4 * r + 1], Lz = S.box[4 * r + 2];
-    const float iLx = Lx > 0.f ? 1.f / Lx : 0.f, iLy = Ly > 0.f ? 1.f / Ly : 0.f, iLz = Lz > 0.f ? 1.f / Lz : 0.f;
-    float lam_a = 1.f, sc = 0.f;
-    if (ALCH) { lam_a = S.rep_lam[4 * r]; sc = S.rep_lam[4 * r + 1]; }
-    const float kT = frcp((float)S.beta[S.labels[S.r_begin + r]]);
-    const uint32_t rg = S.noise_id ? S.noise_id[r] : (uint32_t)(S.r_begin + r);
-    const float rl = S.p.rc + S.skin, rl2 = rl * rl, half_skin2 = 0.25f * S.skin * S.skin;
-    bool have_list = false, forces_valid = false;
-    int n_eval = 0;
-    if (tid == 0) { s_vote[0] = 0; s_vote[1] = 0; *s_np = 0; }
-    __syncthreads();
-
-    auto evaluate = [&]() {
-        // publish the positions; rebuild the list if any atom has left its skin / 2 sphere.  The vote rides on the barrier that
-        // publishes the positions (two words used in turn: the one of the next evaluation is cleared behind this barrier)
-        const float3 d = x - xref;
-        const bool moved = !have_list || (active && dot3(d, d) > half_skin2);
-        const int par_e = n_eval & 1;
-        s_pos[tid] = make_float4(x.x, x.y, x.z, 0.f);
-        if (moved) s_vote[par_e] = 1;
-        __syncthreads();
-        const int rebuild = s_vote[par_e];
-        if (tid == 0) s_vote[par_e ^ 1] = 0;
-        ++n_eval;
-        f = f3(0, 0, 0);
-        if (S.method >= 0) {
-            if (rebuild) {
-                if (tid == 0) *s_np = 0;
-                __syncthreads();
-                if (active) {
-                    for (int j = 0; j < N; ++j) {                        // wave-uniform j: LDS broadcast reads
-                        const float4 q = s_pos[j];
-                        float dx = q.x - x.x, dy = q.y - x.y, dz = q.z - x.z;
-                        dx -= Lx * rintf(dx * iLx); dy -= Ly * rintf(dy * iLy); dz -= Lz * rintf(dz * iLz);
-                        const float r2 = dx * dx + dy * dy + dz * dz;
-                        if (r2 < rl2 && j > tid) {                       // every pair once; the order of the list does not matter
-                            const int slot = atomicAdd(s_np, 1);         // (forces are integer sums)
-                            if (slot < S.list_cap) s_pairs[slot] = (unsigned int)tid | ((unsigned int)j << 16);
-                        }
-                    }
-                    xref = x;
-                }
-                have_list = true;
-                __syncthreads();
-                if (tid == 0 && *s_np > S.list_cap) atomicCAS(S.err, 0u, 4u);
-            }
-            {
-                // a thread takes pairs tid, tid + T, ...: the same number for every lane (an atom-per-lane loop runs as long as the
-                // busiest atom of the wavefront: 16 slots for 10 neighbours on average), RES_UNROLL pairs per trip with all their
-                // LDS reads in flight
-                const int np = min(*s_np, S.list_cap);
-                for (int k = tid; k < np; k += RES_UNROLL * T) {
-                    unsigned int w[RES_UNROLL]; float4 qi[RES_UNROLL], qj[RES_UNROLL], pi[RES_UNROLL], pj[RES_UNROLL];
-#pragma unroll
-                    for (int u = 0; u < RES_UNROLL; ++u) w[u] = s_pairs[min(k + u * T, np - 1)];
-#pragma unroll
-                    for (int u = 0; u < RES_UNROLL; ++u) {
-                        const int i = w[u] & 0xffffu, j = w[u] >> 16;
-                        qi[u] = s_pos[i]; qj[u] = s_pos[j]; pi[u] = s_par[i]; pj[u] = s_par[j];
-                    }
-#pragma unroll
-                    for (int u = 0; u < RES_UNROLL; ++u) {
-                        const int i = w[u] & 0xffffu, j = w[u] >> 16;
-                        float dx = qj[u].x - qi[u].x, dy = qj[u].y - qi[u].y, dz = qj[u].z - qi[u].z;
-                        dx -= Lx * rintf(dx * iLx); dy -= Ly * rintf(dy * iLy); dz -= Lz * rintf(dz * iLz);
-                        const float r2 = dx * dx + dy * dy + dz * dz;
-                        if (r2 < S.p.rc2 && k + u * T < np) {
-                            const float fr = resident_pair<ALCH>(S.p, r2, pi[u], pj[u], lam_a, sc) * RES_FSCALE;
-                            const float ax = fr * dx, ay = fr * dy, az = fr * dz;                                    // F_i = fr (x_j - x_i)
-                            if (fmaxf(fmaxf(fabsf(ax), fabsf(ay)), fabsf(az)) < 134217728.f) {                       // 2^27: sixteen of them fit 32 bits
-                                const int fx = __float2int_rn(ax), fy = __float2int_rn(ay), fz = __float2int_rn(az);
-                                atomicAdd(&s_f[i], fx); atomicAdd(&s_f[T + i], fy); atomicAdd(&s_f[2 * T + i], fz);
-                                atomicAdd(&s_f[j], -fx); atomicAdd(&s_f[T + j], -fy); atomicAdd(&s_f[2 * T + j], -fz);
-                            } else {
-                                // a pair deep inside the repulsive core (an unminimised start): 64-bit accumulators, rare and slow
-                                const long long fx = (long long)ax, fy = (long long)ay, fz = (long long)az;
-                                atomicAdd(&s_fl[i], (unsigned long long)fx); atomicAdd(&s_fl[T + i], (unsigned long long)fy); atomicAdd(&s_fl[2 * T + i], (unsigned long long)fz);
-                                atomicAdd(&s_fl[j], (unsigned long long)(-fx)); atomicAdd(&s_fl[T + j], (unsigned long long)(-fy)); atomicAdd(&s_fl[2 * T + j], (unsigned long long)(-fz));
-                            }
-                        }
-                    }
-                }
-            }
-            __syncthreads();                                 // every pair is in; nobody reads s_pos any more
-            {
-                const long long lx = (long long)s_fl[tid], ly = (long long)s_fl[T + tid], lz = (long long)s_fl[2 * T + tid];
-                f = f3((float)s_f[tid], (float)s_f[T + tid], (float)s_f[2 * T + tid]);
-                if (lx | ly | lz) {
-                    f = f + f3((float)lx, (float)ly, (float)lz);
-                    s_fl[tid] = 0ull; s_fl[T + tid] = 0ull; s_fl[2 * T + tid] = 0ull;
-                }
-                f = f * (1.f / RES_FSCALE);
-            }
-            s_f[tid] = 0; s_f[T + tid] = 0; s_f[2 * T + tid] = 0;      // (the next accumulation starts behind the next publication barrier)
-        } else {
-            __syncthreads();
-        }
-        if (ext) { f.x -= S.ext_K * (x.x - S.ext_x0); f.y -= S.ext_K * x.y; f.z -= S.ext_K * x.z; }
-        forces_valid = true;
-    };
-
-    for (int s = 0; s < prog.n_steps; ++s) {
-        const long long gstep = prog.gstep0 + s;
-        if (prog.cmm_frequency > 0 && ((prog.first_step + s) % prog.cmm_frequency) == 0) {
-            // integrators.py:1313: CMMotionRemover at the top of a step: v -= sum(m v) / M; fixed-order sums (deterministic)
-            float3 pm = active ? v * frcp(im) : f3(0, 0, 0);
-            for (int off = 32; off > 0; off >>= 1) { pm.x += __shfl_xor(pm.x, off); pm.y += __shfl_xor(pm.y, off); pm.z += __shfl_xor(pm.z, off); }
-            if ((tid & 63) == 0) { s_red[3 * (tid >> 6)] = pm.x; s_red[3 * (tid >> 6) + 1] = pm.y; s_red[3 * (tid >> 6) + 2] = pm.z; }
-            __syncthreads();
-            float3 tot = f3(0, 0, 0);
-            for (int w = 0; w < nw; ++w) tot = tot + f3(s_red[3 * w], s_red[3 * w + 1], s_red[3 * w + 2]);
-            __syncthreads();
-            if (active) v = v - tot * S.inv_total_mass;
-        }
-        for (int t = 0; t < prog.n; ++t) {
-            const char tok = prog.tok[t];
-            if (tok == 'V') {
-                if (!forces_valid) evaluate();
-                v = v + f * (prog.hV * im);
-            } else if (tok == 'R') {
-                x = x + v * prog.hR;
-                forces_valid = false;
-            } else {
-                const uint64_t cnt = (uint64_t)gstep * (uint64_t)prog.nO + (uint64_t)prog.o_index[t];
-                const float3 xi = gaussian3(S.seed, REMD_STREAM_OU, (uint32_t)tid, rg, cnt);
-                const float sig = prog.b * fsqrt(kT * im);
-                v = f3(prog.a * v.x + sig * xi.x, prog.a * v.y + sig * xi.y, prog.a * v.z + sig * xi.z);
-            }
-        }
-    }
-    if (active) {
-        P[tid] = make_float4(x.x, x.y, x.z, 0.f);
-        V[tid] = make_float4(v.x, v.y, v.z, 0.f);
-    }
-}
-
-// returns 1 when the propagation was run by the resident kernel, 0 when the system / request is not one it covers, < 0 on error
-static int remd_run_steps_resident(remd_ctx* h, const std::vector<char>& tokens, int nV, int nR, int nO,
-                                   int64_t iteration, int64_t first_step, int n_steps)
-{
-    if (!h->sw.resident || h->no_resident) return 0;
-    if (h->N > 1024 || h->n_settle > 0 || h->n_shake > 0 || h->n_bonds > 0 || h->n_angles > 0 || h->n_torsions > 0 || h->n_restraints > 0 || h->gbsa) return 0;
-    if (h->baro_frequency > 0 || h->profiling == 2 || (int)tokens.size() > MAX_TOK || n_steps < 1) return 0;
-    if (h->measure_heat || h->measure_shadow) return 0;
-    for (char c : tokens) if (c != 'V' && c != 'R' && c != 'O') return 0;
-    int ok = 0, method = -1, alch = 0; nb_params p{}; const float4* param = nullptr; const float* rep_lam = nullptr;
-    int rc = remd_nb_resident_info(h, &ok, &method, &alch, &p, &param, &rep_lam);
-    if (rc) return rc;
-    if (!ok) return 0;
-    resident_sys S{};
-    S.N = h->N; S.Npad = h->Npad; S.method = method; S.alch = alch; S.n_ext = h->n_ext; S.p = p;
-    // skin: a fifth of the cutoff, at most what keeps r_c + skin inside half the smallest box edge (minimum image)
-    double lmin = 1e30;
-    for (int r = 0; r < h->R; ++r) for (int k = 0; k < 3; ++k) lmin = std::min(lmin, h->box_host.size() >= (size_t)3 * (r + 1) ? h->box_host[3 * r + k] : 1e30);
-    S.skin = method >= 0 ? (float)std::max(0.0, std::min(0.2 * p.rc, 0.5 * lmin - p.rc - 1e-3)) : 0.f;
-    if (method >= 0 && !(0.5 * lmin > p.rc)) return 0;
-    S.ext_K = (float)h->ext_K; S.ext_x0 = (float)h->ext_x0; S.inv_total_mass = (float)(h->total_mass > 0 ? 1.0 / h->total_mass : 0.0);
-    S.param = param; S.rep_lam = rep_lam; S.ext_atoms = h->d_ext_atoms; S.invmass = h->d_invmass; S.box = h->d_box;
-    S.labels = h->d_labels; S.beta = h->d_beta; S.r_begin = h->r_begin; S.seed = h->seed; S.err = h->d_sync + 2; S.noise_id = h->d_noise_id;
-    const int T = std::max(64, (h->N + 63) / 64 * 64);
-    // pair-list capacity from the LDS that is left: positions + parameters (32 B per thread), partial sums / flags, force accumulators
-    const size_t fixed = (size_t)T * 32 + 64 * sizeof(float) + (size_t)T * 12 + 8 + (size_t)T * 24;
-    const size_t lds_max = 144 * 1024;
-    S.list_cap = method >= 0 ? (int)std::min<size_t>(32768, (lds_max - fixed) / 4) : 0;
-    if (h->sw.resident_cap) S.list_cap = std::max(1, std::min(S.list_cap, h->sw.resident_cap));      // test hook: provoke the overflow path
-    if (method >= 0 && S.list_cap < 4 * h->N && !h->sw.resident_cap) return 0;
-    const size_t lds = fixed + (size_t)S.list_cap * 4;
-    resident_prog prog{};
-    prog.n = (int)tokens.size();
-    int oidx = 0;
-    for (int t = 0; t < prog.n; ++t) { prog.tok[t] = tokens[t]; prog.o_index[t] = tokens[t] == 'O' ? oidx++ : 0; }
-    prog.hV = (float)(h->dt / (nV > 0 ? nV : 1)); prog.hR = (float)(h->dt / (nR > 0 ? nR : 1));
-    const double hO = h->dt / (nO > 0 ? nO : 1);
-    prog.a = (float)exp(-h->gamma * hO); prog.b = (float)sqrt(1.0 - exp(-2.0 * h->gamma * hO)); prog.nO = nO > 0 ? nO : 1;
-    prog.n_steps = n_steps; prog.cmm_frequency = h->cmm_frequency;
-    prog.gstep0 = (long long)iteration * (long long)h->n_steps + first_step; prog.first_step = first_step;
-    remd_launch_join_wait(h);
-    remd_prof_scope ps(h, "resident_md");
-    if (alch) {
-        REMD_CHECK(h, hipFuncSetAttribute((const void*)resident_md_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-        hipLaunchKernelGGL(resident_md_kernel<true>, dim3(h->R), dim3(T), lds, h->stream, prog, S, h->d_pos, h->d_vel);
-    } else {
-        REMD_CHECK(h, hipFuncSetAttribute((const void*)resident_md_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-        hipLaunchKernelGGL(resident_md_kernel<false>, dim3(h->R), dim3(T), lds, h->stream, prog, S, h->d_pos, h->d_vel);
-    }
-    REMD_CHECK(h, hipGetLastError());
-    h->forces_valid = false; h->force_zeroed = false;
-    remd_nb_invalidate_sort(h);            // the atoms moved n_steps without the regular path's evaluation counter seeing it
-    return 1;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Resident small-molecule MD (round 6): the reference's vacuum test systems (AlanineDipeptideVacuum 22 atoms, HostGuestVacuum 156,
-// TolueneVacuum 15; testsystems.py:3352-3388) are three dependent launches per MD step on the regular path -- NoCutoff pair sum, listed
-// terms, integrator chain -- of which the chain alone is 25 us of fixed latency for 22 atoms (rocprofv3, profiles/r06_43): 39 us per step
-// whatever the size.  As for the Lennard-Jones fluids above, ONE launch per propagation: a workgroup owns a replica; a thread owns a
-// constraint unit (x, v, 1/m of its <= 4 atoms in registers for all n_steps, the unit arithmetic of the chain kernel: X-H clusters,
-// rigid waters, free atoms) AND, for the pair sum, an atom; positions, pair parameters and the fixed-point force accumulators live in LDS.
-// A force evaluation is: units publish their positions and clear their atoms' accumulators | barrier | every atom sums its partners in
-// ascending order (nocutoff_pair.h: the arithmetic and the order of nocutoff_kernel), exceptions, listed terms (listed_forces_body, the
-// accumulators being an LDS address) | barrier.  Every contribution is converted to fixed point exactly as on the regular path and integer
-// sums do not depend on their order; with the same Philox streams and the same centre-of-mass sum (per-wavefront fp32 partial sums in
-// unit order, then integers) the trajectory follows the regular path to fp32 rounding (one step: velocities within 1 ulp, positions equal;
-// the compiler contracts the long expressions of the two kernels differently; tools/experiments/resident_mol_diff.py), like the
-// Lennard-Jones kernel above (tests/test_nocutoff.py::test_resident_small_molecule_kernel_follows_the_regular_launches).
-// Measured (profiles/r06_43_small_molecule_systems.txt): 24 x AlanineDipeptideVacuum 39 -> 23 us per MD step; a step is then the latency
-// of its seven tokens at one wavefront per SIMD (~1 us each, X-H Newton iterations) + one evaluation.  From ~100 atoms on one workgroup
-// per replica loses against the regular launches, which spread the listed terms over the chip (CB7:B2 in vacuum, 156 atoms: 72 against
-// 61 us per step) -- the kernel takes systems of up to RESIDENT_MOL_MAX_ATOMS atoms.
-struct resident_mol_sys {
-    int N, Npad, n_units, words, n_exc;
-    const float4* nb_param; const unsigned int* excl; const int* exc_atoms; const float4* exc_par;
-    const int4* unit_atoms; const unsigned char* unit_type; const float* shake_dist; settle_const sc; float tol;
-    const float* invmass; const int64_t* labels; const double* beta; int r_begin; uint64_t seed; const unsigned int* noise_id;
-    float inv_total_mass; unsigned int* shake_stat;
-    listed_tables L; int n_listed;
-};
-
-// one token of the step program on the registers of a unit: the V / R / O branches of run_unit, expression for expression
-__device__ __forceinline__ char resident_tok(const resident_prog& prog, int t)
-{
-    static_assert(MAX_TOK == 24, "six 32-bit words of tokens");
-    const unsigned int* w = reinterpret_cast<const unsigned int*>(prog.tok);
-    const unsigned int w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4], w5 = w[5];
-    const int q = t >> 2;
-    const unsigned int x = q == 0 ? w0 : q == 1 ? w1 : q == 2 ? w2 : q == 3 ? w3 : q == 4 ? w4 : w5;
-    return (char)((x >> ((t & 3) * 8)) & 0xffu);
-}
-
-template <int TYPE, int NAT>
-__device__ __forceinline__ void resident_mol_token(char tok, const resident_prog& prog, int o_index, long long gstep, const int* idx, const float* dist,
-                                                   const settle_const& sc, float tol, const long long* F, int Fs, float kT, uint32_t rg, uint64_t seed,
-                                                   unit_regs& S)
-{
-    float3 (&x)[4] = S.x; float3 (&v)[4] = S.v;
-    float (&im)[4] = S.im;
-    if (tok == 'V') {
-        const float hv = prog.hV;
-#pragma unroll
-        for (int k = 0; k < NAT; ++k) {
-            const float s = hv * im[k] * (1.0f / 4294967296.0f);
-            v[k].x += s * (float)F[idx[k]];
-            v[k].y += s * (float)F[Fs + idx[k]];
-            v[k].z += s * (float)F[2 * Fs + idx[k]];
-        }
-        constrain_v<TYPE, NAT>(sc, im, tol, v, x);
-    } else if (tok == 'R') {
-        if (TYPE == UNIT_FREE) {
-#pragma unroll
-            for (int k = 0; k < NAT; ++k) x[k] = x[k] + v[k] * prog.hR;
-        } else {
-            float3 p0[NAT], p1[NAT], q[NAT];
-#pragma unroll
-            for (int k = 0; k < NAT; ++k) {
-                p0[k] = x[k] - x[0];
-                p1[k] = p0[k] + v[k] * prog.hR;
-                q[k] = p1[k];
-            }
-            if (TYPE == UNIT_SETTLE) settle_positions(sc, p0, p1);
-            else S.shake_it = max(S.shake_it, shake_positions<NAT>(im, dist, tol, p0, p1));
-            const float ih = frcp(prog.hR);
-            const float3 org = x[0];
-#pragma unroll
-            for (int k = 0; k < NAT; ++k) {
-                v[k] = v[k] + (p1[k] - q[k]) * ih;
-                x[k] = org + p1[k];
-            }
-            constrain_v<TYPE, NAT>(sc, im, tol, v, x);
-        }
-    } else if (tok == 'O') {
-        const uint64_t cnt = (uint64_t)gstep * (uint64_t)prog.nO + (uint64_t)o_index;
-#pragma unroll
-        for (int k = 0; k < NAT; ++k) {
-            const float3 xi = gaussian3(seed, REMD_STREAM_OU, (uint32_t)idx[k], rg, cnt);
-            const float sig = prog.b * fsqrt(kT * im[k]);
-            v[k].x = prog.a * v[k].x + sig * xi.x;
-            v[k].y = prog.a * v[k].y + sig * xi.y;
-            v[k].z = prog.a * v[k].z + sig * xi.z;
-        }
-        constrain_v<TYPE, NAT>(sc, im, tol, v, x);
-    }
-}
-
-#define RESIDENT_MOL_T 256
-#define RESIDENT_MOL_MAX_ATOMS 64
-__global__ __launch_bounds__(RESIDENT_MOL_T)
-void resident_mol_kernel(resident_prog prog, resident_mol_sys S, float4* __restrict__ pos, float4* __restrict__ vel)
-{
-    __shared__ float4 s_pos[RESIDENT_MOL_T], s_par[RESIDENT_MOL_T];
-    __shared__ long long s_F[3 * RESIDENT_MOL_T];
-    __shared__ long long s_pm[RESIDENT_MOL_T / 64][3];
-    constexpr int Fs = RESIDENT_MOL_T;
-    const int tid = threadIdx.x, r = blockIdx.x, N = S.N;
-    float4* P = pos + (size_t)r * S.Npad;
-    float4* V = vel + (size_t)r * S.Npad;
-    int4 a4 = make_int4(-1, -1, -1, -1);
-    int type = UNIT_FREE;
-    float dist[3] = { 0.f, 0.f, 0.f };
-    if (tid < S.n_units) {
-        a4 = S.unit_atoms[tid]; type = (int)S.unit_type[tid];
-        dist[0] = S.shake_dist[tid * 3]; dist[1] = S.shake_dist[tid * 3 + 1]; dist[2] = S.shake_dist[tid * 3 + 2];
-    }
-    const bool active = a4.x >= 0;
-    if (!active) type = UNIT_FREE;
-    const int idx[4] = { a4.x, a4.y, a4.z, a4.w };
-    unit_regs U;
-    U.have_cm = 0; U.shake_it = 0; U.heat = 0.f; U.shadow = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        U.x[k] = f3(0, 0, 0); U.v[k] = f3(0, 0, 0); U.im[k] = 0.f;
-        if (idx[k] >= 0) {
-            const float4 p = P[idx[k]], w = V[idx[k]];
-            U.x[k] = f3(p.x, p.y, p.z); U.v[k] = f3(w.x, w.y, w.z); U.im[k] = S.invmass[idx[k]];
-        }
-    }
-    s_par[tid] = tid < N ? S.nb_param[tid] : make_float4(0.f, 0.f, 0.f, 0.f);
-    s_pos[tid] = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float kT = frcp((float)S.beta[S.labels[S.r_begin + r]]);
-    const uint32_t rg = S.noise_id ? S.noise_id[r] : (uint32_t)(S.r_begin + r);
-    bool forces_valid = false;
-    __syncthreads();
-
-    auto evaluate = [&]() {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (idx[k] >= 0) {
-                s_pos[idx[k]] = make_float4(U.x[k].x, U.x[k].y, U.x[k].z, 0.f);
-                s_F[idx[k]] = 0; s_F[Fs + idx[k]] = 0; s_F[2 * Fs + idx[k]] = 0;
-            }
-        }
-        __syncthreads();
-        if (tid < N) {
-            const float4 xi = s_pos[tid], pi = s_par[tid];
-            float fx = 0.f, fy = 0.f, fz = 0.f;
-            double e = 0.0;
-            const unsigned int* mrow = S.excl + (size_t)tid * S.words;
-            for (int j0 = 0; j0 < N; j0 += 32) {
-                const unsigned int m = mrow[j0 >> 5];
-                const int jn = min(32, N - j0);
-                for (int k = 0; k < jn; ++k) {
-                    const int j = j0 + k;
-                    if (j == tid || ((m >> k) & 1u)) continue;
-                    nocutoff_pair<false>(xi, pi, s_pos[j], s_par[j], fx, fy, fz, e);
-                }
-            }
-            add_force(s_F, Fs, tid, fx, fy, fz);
-        }
-        for (int t = tid; t < S.n_exc; t += RESIDENT_MOL_T) {
-            const int i = S.exc_atoms[2 * t], j = S.exc_atoms[2 * t + 1];
-            const float4 par = S.exc_par[t];
-            const float3 d = sub3(ld3(s_pos, j), ld3(s_pos, i));
-            double e = 0.0;
-            const float fr = nocutoff_exception<false>(par, d, e);
-            add_force(s_F, Fs, i, fr * d.x, fr * d.y, fr * d.z);
-            add_force(s_F, Fs, j, -fr * d.x, -fr * d.y, -fr * d.z);
-        }
-        // (every lane of a wavefront takes part in listed_forces_body's reduction over the lanes of one atom)
-        for (int base = 0; base < S.n_listed; base += RESIDENT_MOL_T)
-            listed_forces_body(S.L, Fs, s_pos, (const float*)nullptr, s_F, base + tid, 0);
-        __syncthreads();
-        forces_valid = true;
-    };
-
-    for (int s = 0; s < prog.n_steps; ++s) {
-        const long long gstep = prog.gstep0 + s;
-        if (prog.cmm_frequency > 0 && ((prog.first_step + s) % prog.cmm_frequency) == 0) {
-            // CMMotionRemover at the top of a step (integrators.py:1313): the sum of the chain kernel -- fp32 over a unit's atoms and the
-            // units of a wavefront, then fixed point
-            float3 pm = f3(0, 0, 0);
-            if (active) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) if (idx[k] >= 0) pm = pm + U.v[k] * frcp(U.im[k]);
-            }
-            for (int off = 32; off > 0; off >>= 1) { pm.x += __shfl_xor(pm.x, off); pm.y += __shfl_xor(pm.y, off); pm.z += __shfl_xor(pm.z, off); }
-            if ((tid & 63) == 0) {
-                long long* w = s_pm[tid >> 6];
-                w[0] = (long long)((double)pm.x * 4294967296.0); w[1] = (long long)((double)pm.y * 4294967296.0); w[2] = (long long)((double)pm.z * 4294967296.0);
-            }
-            __syncthreads();
-            long long tot[3] = { 0, 0, 0 };
-            for (int w = 0; w < RESIDENT_MOL_T / 64; ++w) { tot[0] += s_pm[w][0]; tot[1] += s_pm[w][1]; tot[2] += s_pm[w][2]; }
-            __syncthreads();
-            const float sx = (float)tot[0] * (1.0f / 4294967296.0f) * S.inv_total_mass;
-            const float sy = (float)tot[1] * (1.0f / 4294967296.0f) * S.inv_total_mass;
-            const float sz = (float)tot[2] * (1.0f / 4294967296.0f) * S.inv_total_mass;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { U.v[k].x -= sx; U.v[k].y -= sy; U.v[k].z -= sz; }
-        }
-        int o_index = 0;
-        for (int t = 0; t < prog.n; ++t) {
-            // (the token from six registers loaded with the kernel arguments, the O counter kept here: a dynamic index into the argument
-            //  arrays is a scalar memory load per token on a path that is all latency, see chain_tok)
-            const char tok = resident_tok(prog, t);
-            if (tok == 'V' && !forces_valid) evaluate();
-            if (tok == 'R') forces_valid = false;
-            const int o_now = o_index;
-            if (tok == 'O') ++o_index;
-            if (active) {
-#define RUN(TY, NA) resident_mol_token<TY, NA>(tok, prog, o_now, gstep, idx, dist, S.sc, S.tol, s_F, Fs, kT, rg, S.seed, U)
-                if (type == UNIT_SETTLE) RUN(UNIT_SETTLE, 3);
-                else if (type == UNIT_FREE) { if (a4.y < 0) RUN(UNIT_FREE, 1); else RUN(UNIT_FREE, 4); }
-                else if (a4.z < 0) RUN(UNIT_SHAKE, 2);
-                else if (a4.w < 0) RUN(UNIT_SHAKE, 3);
-                else RUN(UNIT_SHAKE, 4);
-#undef RUN
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (idx[k] >= 0) {
-            P[idx[k]] = make_float4(U.x[k].x, U.x[k].y, U.x[k].z, 0.f);
-            V[idx[k]] = make_float4(U.v[k].x, U.v[k].y, U.v[k].z, 0.f);
-        }
-    }
-    if (type == UNIT_SHAKE && U.shake_it > 0 &&
-        (unsigned int)U.shake_it > __hip_atomic_load(S.shake_stat, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-        atomicMax(S.shake_stat, (unsigned int)U.shake_it);
-}
-
-// returns 1 when the propagation was run by the resident small-molecule kernel, 0 when the system / request is not one it covers
-static int remd_run_steps_resident_mol(remd_ctx* h, const std::vector<char>& tokens, int nV, int nR, int nO,
-                                       int64_t iteration, int64_t first_step, int n_steps)
-{
-    if (!h->sw.resident || h->no_resident) return 0;
-    if (!h->nocutoff || h->gbsa || h->n_regions > 0 || h->nb_method != REMD_NB_NONE || h->n_ext > 0 || h->n_restraints > 0) return 0;
-    const unit_tables& ut = remd_table_of(h->units);
-    if (h->N > RESIDENT_MOL_MAX_ATOMS || ut.n_units > RESIDENT_MOL_T || ut.n_units < 1) return 0;
-    if (h->baro_frequency > 0 || h->profiling == 2 || (int)tokens.size() > MAX_TOK || n_steps < 1) return 0;
-    if (h->measure_heat || h->measure_shadow) return 0;
-    for (char c : tokens) if (c != 'V' && c != 'R' && c != 'O') return 0;
-    resident_mol_sys S{};
-    S.N = h->N; S.Npad = h->Npad; S.n_units = ut.n_units;
-    if (remd_nocutoff_info(h, &S.nb_param, &S.excl, &S.words, &S.n_exc, &S.exc_atoms, &S.exc_par)) return 0;
-    S.unit_atoms = ut.d_atoms; S.unit_type = ut.d_type; S.shake_dist = ut.d_dist; S.sc = ut.sc;
-    S.tol = (float)fmax(h->constraint_tol, REMD_CONSTRAINT_TOL_FLOOR);
-    S.invmass = h->d_invmass; S.labels = h->d_labels; S.beta = h->d_beta; S.r_begin = h->r_begin; S.seed = h->seed; S.noise_id = h->d_noise_id;
-    S.inv_total_mass = (float)(h->total_mass > 0 ? 1.0 / h->total_mass : 0.0);
-    S.shake_stat = h->d_sync + 3;
-    listed_tables L{};
-    L.n_bonds = h->n_bonds; L.n_angles = h->n_angles; L.n_torsions = h->n_torsions;
-    L.bond_atoms = h->d_bond_atoms; L.bond_params = h->d_bond_params;
-    L.angle_atoms = h->d_angle_atoms; L.angle_params = h->d_angle_params;
-    L.torsion_atoms = h->d_torsion_atoms; L.torsion_params = h->d_torsion_params;
-    S.n_listed = L.n_bonds + L.n_angles + L.n_torsions;
-    if (S.n_listed > 0 && h->d_aterm && h->n_aterm > 0) { L.aterm = h->d_aterm; L.n_aterm = h->n_aterm; S.n_listed = h->n_aterm; }
-    S.L = L;
-    resident_prog prog{};
-    prog.n = (int)tokens.size();
-    int oidx = 0;
-    for (int t = 0; t < prog.n; ++t) { prog.tok[t] = tokens[t]; prog.o_index[t] = tokens[t] == 'O' ? oidx++ : 0; }
-    prog.hV = (float)(h->dt / (nV > 0 ? nV : 1)); prog.hR = (float)(h->dt / (nR > 0 ? nR : 1));
-    const double hO = h->dt / (nO > 0 ? nO : 1);
-    prog.a = (float)exp(-h->gamma * hO); prog.b = (float)sqrt(1.0 - exp(-2.0 * h->gamma * hO)); prog.nO = nO > 0 ? nO : 1;
-    prog.n_steps = n_steps; prog.cmm_frequency = h->cmm_frequency;
-    prog.gstep0 = (long long)iteration * (long long)h->n_steps + first_step; prog.first_step = first_step;
-    remd_launch_join_wait(h);
-    remd_prof_scope ps(h, "resident_md");
-    hipLaunchKernelGGL(resident_mol_kernel, dim3(h->R), dim3(RESIDENT_MOL_T), 0, h->stream, prog, S, h->d_pos, h->d_vel);
-    REMD_CHECK(h, hipGetLastError());
-    h->forces_valid = false; h->force_zeroed = false;
-    return 1;
-}
-
 // Runs n_steps of the token program.  Tokens are grouped into chains that need no new
 // force evaluation; a 'V' after an 'R' forces a force evaluation first.
 //
@@ -1555,12 +713,7 @@ struct step_runner {
             if (rm != 0) { done_by_resident = true; return 0; }
         }
         base = chain_prog{};
-        base.hV = (float)(h->dt / (nV > 0 ? nV : 1));
-        base.hR = (float)(h->dt / (nR > 0 ? nR : 1));
-        const double hO = h->dt / (nO > 0 ? nO : 1);                 // integrators.py:1142
-        base.a = (float)exp(-h->gamma * hO);                         // :1143
-        base.b = (float)sqrt(1.0 - exp(-2.0 * h->gamma * hO));       // :1146
-        base.nO = nO > 0 ? nO : 1;
+        remd_step_prog_fill(base, {}, h->dt, h->gamma, nV, nR, nO);      // (no tokens: push() adds them chain by chain)
         base.cmm_r = -1; base.cmm_w = 0; base.zero_force = 0;
         // multiple-time-step program: one force array per force group that the splitting names, evaluated when a V of the group
         // comes up and the positions have changed since its last evaluation
@@ -1777,14 +930,13 @@ int remd_run_steps_many(remd_ctx** hs, int n, int64_t iteration, int64_t first_s
     return 0;
 }
 
-
 int remd_assign_velocities(remd_ctx* h, int64_t iteration)
 {
     const unit_tables& ut = remd_table_of(h->units);
     remd_prof_scope ps(h, "assign_velocities");
     dim3 grid((ut.n_units + 255) / 256, h->R);
     hipLaunchKernelGGL(assign_velocities_kernel, grid, dim3(256), 0, h->stream, ut.n_units, ut.d_atoms, ut.d_type, ut.sc,
-                       (float)fmax(h->constraint_tol, REMD_CONSTRAINT_TOL_FLOOR), h->Npad, h->d_pos, h->d_vel, h->d_invmass, h->d_labels,
+                       remd_constraint_tol(h), h->Npad, h->d_pos, h->d_vel, h->d_invmass, h->d_labels,
                        h->d_beta, h->r_begin, h->seed, iteration, h->d_noise_id);
     REMD_CHECK(h, hipGetLastError());
     return 0;
@@ -1803,271 +955,6 @@ int remd_check_finite(remd_ctx* h)
     REMD_CHECK(h, hipMemsetAsync(h->d_nan, 0, sizeof(int) * h->R, h->stream));
     dim3 grid((h->N + 255) / 256, h->R);
     hipLaunchKernelGGL(check_finite_kernel, grid, dim3(256), 0, h->stream, h->N, h->Npad, h->d_pos, h->d_vel, h->d_nan);
-    REMD_CHECK(h, hipGetLastError());
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// FIRE minimisation (MultiStateSampler.minimize, multistatesampler.py:611-647, _minimize_replica :1351-1434, with the
-// reference's FIREMinimizationIntegrator, integrators.py:2290-2469), all local replicas at once.  One reference step:
-//   converged if |f| / ndof <= ftol (:2377-2386);  x0 = x, v0 = v, E0 = U(x) (:2392-2394);
-//   v += dt/2 f/m;  x += dt v;  constrain x;  v += dt/2 f(x_new)/m + (x - x1)/dt;  constrain v (:2397-2402);
-//   dE = U(x_new) - E0;  P = f.v;  v = (1 - alpha) v + alpha f/|f| |v| (:2404-2421);
-//   restart (x = x0, v = v0, P = -1) unless dE < 0 (:2423-2431);  converged if dt <= 1e-5 timestep (:2433-2437);
-//   P > 0: N_neg += 1, beyond N_min: dt = min(dt f_inc, dt_max), alpha *= f_alpha (:2439-2449);
-//   P < 0: N_neg = 0, dt *= f_dec, v = 0, alpha = alpha_start (:2451-2458).
-// Three kernels around one energy + force evaluation per step; the per-replica scalars are double buffered.
-struct fire_rep { float dt, alpha; int n_neg, converged; double E, f2; };     // E, f2 = U and sum f^2 at the current x
-struct fire_consts { float dt_max, f_inc, f_dec, alpha0, f_alpha, dt_min, ftol, ndof; int n_min; };
-
-template <int TYPE, int NAT>
-__device__ __forceinline__ void fire_move_unit(const int* idx, const float* dist, const settle_const& sc, float tol, int Npad,
-                                               float4* __restrict__ P, float4* __restrict__ V, const long long* __restrict__ F,
-                                               float4* __restrict__ X0, float4* __restrict__ V0, long long* __restrict__ F0,
-                                               const float* __restrict__ invmass, float dt)
-{
-    float3 x[NAT], v[NAT];
-    float im[NAT];
-#pragma unroll
-    for (int k = 0; k < NAT; ++k) {
-        const float4 p = P[idx[k]], w = V[idx[k]];
-        X0[idx[k]] = p; V0[idx[k]] = w;
-        const long long fx = F[idx[k]], fy = F[Npad + idx[k]], fz = F[2 * Npad + idx[k]];
-        F0[idx[k]] = fx; F0[Npad + idx[k]] = fy; F0[2 * Npad + idx[k]] = fz;
-        x[k] = f3(p.x, p.y, p.z); v[k] = f3(w.x, w.y, w.z);
-        im[k] = invmass[idx[k]];
-        const float s = 0.5f * dt * im[k] * (1.0f / 4294967296.0f);
-        v[k].x += s * (float)fx; v[k].y += s * (float)fy; v[k].z += s * (float)fz;
-    }
-    if (TYPE == UNIT_FREE) {
-#pragma unroll
-        for (int k = 0; k < NAT; ++k) x[k] = x[k] + v[k] * dt;
-    } else {
-        float3 p0[NAT], p1[NAT], q[NAT];
-#pragma unroll
-        for (int k = 0; k < NAT; ++k) { p0[k] = x[k] - x[0]; p1[k] = p0[k] + v[k] * dt; q[k] = p1[k]; }
-        if (TYPE == UNIT_SETTLE) settle_positions(sc, p0, p1);
-        else (void)shake_positions<NAT>(im, dist, tol, p0, p1);
-        const float ih = frcp(dt);
-        const float3 org = x[0];
-#pragma unroll
-        for (int k = 0; k < NAT; ++k) { v[k] = v[k] + (p1[k] - q[k]) * ih; x[k] = org + p1[k]; }
-    }
-#pragma unroll
-    for (int k = 0; k < NAT; ++k) {
-        P[idx[k]] = make_float4(x[k].x, x[k].y, x[k].z, 0.f);
-        V[idx[k]] = make_float4(v[k].x, v[k].y, v[k].z, 0.f);
-    }
-}
-
-__global__ __launch_bounds__(256)
-void fire_move_kernel(int n_units, const int4* __restrict__ unit_atoms, const unsigned char* __restrict__ unit_type,
-                      const float* __restrict__ shake_dist, settle_const sc, float tol, int Npad, float4* __restrict__ pos,
-                      float4* __restrict__ vel, const long long* __restrict__ force, float4* __restrict__ x0,
-                      float4* __restrict__ v0, long long* __restrict__ f0, const float* __restrict__ invmass,
-                      const fire_rep* __restrict__ state)
-{
-    const int uidx = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
-    const fire_rep s = state[r];
-    if (s.converged || uidx >= n_units) return;
-    const int4 a4 = unit_atoms[uidx];
-    if (a4.x < 0) return;
-    const int idx[4] = { a4.x, a4.y, a4.z, a4.w };
-    const int type = unit_type[uidx];
-    float dist[3] = { 0.f, 0.f, 0.f };
-    if (type == UNIT_SHAKE) { dist[0] = shake_dist[uidx * 3]; dist[1] = shake_dist[uidx * 3 + 1]; dist[2] = shake_dist[uidx * 3 + 2]; }
-    const size_t o = (size_t)r * Npad, of = (size_t)r * 3 * Npad;
-#define RUN(TY, NA) fire_move_unit<TY, NA>(idx, dist, sc, tol, Npad, pos + o, vel + o, force + of, x0 + o, v0 + o, f0 + of, invmass, s.dt)
-    if (type == UNIT_SETTLE) RUN(UNIT_SETTLE, 3);
-    else if (type == UNIT_FREE) { if (a4.y < 0) RUN(UNIT_FREE, 1); else RUN(UNIT_FREE, 4); }
-    else if (a4.z < 0) RUN(UNIT_SHAKE, 2);
-    else if (a4.w < 0) RUN(UNIT_SHAKE, 3);
-    else RUN(UNIT_SHAKE, 4);
-#undef RUN
-}
-
-// second half kick with the new forces, velocity constraints, and the per-workgroup partial sums of f.f, v.v, f.v
-template <int TYPE, int NAT>
-__device__ __forceinline__ void fire_finish_unit(const int* idx, const settle_const& sc, float tol, int Npad,
-                                                 const float4* __restrict__ P, float4* __restrict__ V, const long long* __restrict__ F,
-                                                 const float* __restrict__ invmass, float dt, bool kick, double* sums)
-{
-    float3 x[NAT], v[NAT], f[NAT];
-    float im[NAT];
-#pragma unroll
-    for (int k = 0; k < NAT; ++k) {
-        const float4 p = P[idx[k]], w = V[idx[k]];
-        x[k] = f3(p.x, p.y, p.z); v[k] = f3(w.x, w.y, w.z);
-        im[k] = invmass[idx[k]];
-        f[k] = f3((float)F[idx[k]] * (1.0f / 4294967296.0f), (float)F[Npad + idx[k]] * (1.0f / 4294967296.0f),
-                  (float)F[2 * Npad + idx[k]] * (1.0f / 4294967296.0f));
-        if (kick) v[k] = v[k] + f[k] * (0.5f * dt * im[k]);
-    }
-    if (kick) {
-        constrain_v<TYPE, NAT>(sc, im, tol, v, x);
-#pragma unroll
-        for (int k = 0; k < NAT; ++k) V[idx[k]] = make_float4(v[k].x, v[k].y, v[k].z, 0.f);
-    }
-#pragma unroll
-    for (int k = 0; k < NAT; ++k) { sums[0] += (double)dot3(f[k], f[k]); sums[1] += (double)dot3(v[k], v[k]); sums[2] += (double)dot3(f[k], v[k]); }
-}
-
-__global__ __launch_bounds__(256)
-void fire_finish_kernel(int n_units, const int4* __restrict__ unit_atoms, const unsigned char* __restrict__ unit_type,
-                        settle_const sc, float tol, int Npad, const float4* __restrict__ pos, float4* __restrict__ vel,
-                        const long long* __restrict__ force, const float* __restrict__ invmass,
-                        const fire_rep* __restrict__ state, int kick, double* __restrict__ partial /*[R][gridDim.x][3]*/)
-{
-    const int uidx = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
-    const fire_rep s = state[r];
-    double sums[3] = { 0.0, 0.0, 0.0 };
-    const int4 a4 = (uidx < n_units) ? unit_atoms[uidx] : make_int4(-1, -1, -1, -1);
-    if (a4.x >= 0 && !(s.converged && kick)) {
-        const int idx[4] = { a4.x, a4.y, a4.z, a4.w };
-        const int type = unit_type[uidx];
-        const size_t o = (size_t)r * Npad, of = (size_t)r * 3 * Npad;
-#define RUN(TY, NA) fire_finish_unit<TY, NA>(idx, sc, tol, Npad, pos + o, vel + o, force + of, invmass, s.dt, kick != 0, sums)
-        if (type == UNIT_SETTLE) RUN(UNIT_SETTLE, 3);
-        else if (type == UNIT_FREE) { if (a4.y < 0) RUN(UNIT_FREE, 1); else RUN(UNIT_FREE, 4); }
-        else if (a4.z < 0) RUN(UNIT_SHAKE, 2);
-        else if (a4.w < 0) RUN(UNIT_SHAKE, 3);
-        else RUN(UNIT_SHAKE, 4);
-#undef RUN
-    }
-    __shared__ double s_part[4][3];
-    for (int q = 0; q < 3; ++q) {
-        double v = sums[q];
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-        if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6][q] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        double v = 0.0;
-        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) v += s_part[w][threadIdx.x];         // fixed order => reproducible
-        partial[((size_t)r * gridDim.x + blockIdx.x) * 3 + threadIdx.x] = v;
-    }
-}
-
-// scalar FIRE logic of every replica (computed redundantly by every thread from the partial sums) + the per-atom update
-__global__ __launch_bounds__(256)
-void fire_update_kernel(int n_units, const int4* __restrict__ unit_atoms, int Npad, float4* __restrict__ pos, float4* __restrict__ vel,
-                        long long* __restrict__ force, const float4* __restrict__ x0, const float4* __restrict__ v0,
-                        const long long* __restrict__ f0, const double* __restrict__ potential, const double* __restrict__ partial,
-                        int nblk, fire_consts c, const fire_rep* __restrict__ cur, fire_rep* __restrict__ nxt, int init)
-{
-    const int uidx = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
-    const fire_rep s = cur[r];
-    double f2 = 0.0, v2 = 0.0, fv = 0.0;
-    for (int b = 0; b < nblk; ++b) { f2 += partial[((size_t)r * nblk + b) * 3]; v2 += partial[((size_t)r * nblk + b) * 3 + 1]; fv += partial[((size_t)r * nblk + b) * 3 + 2]; }
-    fire_rep n = s;
-    if (init) {
-        // before the first step: forces and energy at the start positions, convergence test of the first step (:2377-2386)
-        n.E = potential[r]; n.f2 = f2;
-        n.converged = (sqrt(f2) / (double)c.ndof <= (double)c.ftol) ? 1 : 0;
-        if (uidx == 0) nxt[r] = n;
-        return;
-    }
-    if (s.converged) { if (uidx == 0) nxt[r] = s; return; }
-    const double E_new = potential[r];
-    const bool restart = !(E_new - s.E < 0.0);                                   // :2423-2427, NaN-safe
-    const float fmag = (float)sqrt(f2), vmag = (float)sqrt(v2);
-    const float P = restart ? -1.f : (float)fv;
-    const int4 a4 = (uidx < n_units) ? unit_atoms[uidx] : make_int4(-1, -1, -1, -1);
-    if (a4.x >= 0) {
-        const int idx[4] = { a4.x, a4.y, a4.z, a4.w };
-        const size_t o = (size_t)r * Npad, of = (size_t)r * 3 * Npad;
-        for (int k = 0; k < 4; ++k) {
-            const int i = idx[k];
-            if (i < 0) break;
-            if (restart) {
-                pos[o + i] = x0[o + i];
-                force[of + i] = f0[of + i]; force[of + Npad + i] = f0[of + Npad + i]; force[of + 2 * Npad + i] = f0[of + 2 * Npad + i];
-            }
-            float4 w = restart ? v0[o + i] : vel[o + i];
-            if (!restart && fmag > 0.f) {
-                const float sf = s.alpha * vmag / fmag * (1.0f / 4294967296.0f);    // alpha |v| / |f| on the fixed-point force
-                w.x = (1.f - s.alpha) * w.x + sf * (float)force[of + i];
-                w.y = (1.f - s.alpha) * w.y + sf * (float)force[of + Npad + i];
-                w.z = (1.f - s.alpha) * w.z + sf * (float)force[of + 2 * Npad + i];
-            }
-            if (P < 0.f) w = make_float4(0.f, 0.f, 0.f, 0.f);                     // :2455
-            vel[o + i] = w;
-        }
-    }
-    if (uidx == 0) {
-        if (!restart) { n.E = E_new; n.f2 = f2; }
-        if (s.dt <= c.dt_min) n.converged = 1;                                    // :2433-2437
-        if (P > 0.f) {
-            n.n_neg = s.n_neg + 1;
-            if (n.n_neg > c.n_min) { n.dt = fminf(s.dt * c.f_inc, c.dt_max); n.alpha = s.alpha * c.f_alpha; }
-        }
-        if (P < 0.f) { n.n_neg = 0; n.dt = s.dt * c.f_dec; n.alpha = c.alpha0; }
-        // convergence test at the top of the next step (:2377-2386), on the forces the next step starts from
-        if (sqrt(n.f2) / (double)c.ndof <= (double)c.ftol) n.converged = 1;
-        nxt[r] = n;
-    }
-}
-
-int remd_minimize_impl(remd_ctx* h, double tolerance, int max_iterations, int32_t* converged_out, int32_t* n_iter_out)
-{
-    const unit_tables& ut = remd_table_of(h->units);
-    if (ut.n_units == 0) return remd_fail(h, -3, "no system set");
-    const int R = h->R, Npad = h->Npad;
-    const dim3 grid((ut.n_units + 255) / 256, R);
-    const int nblk = (int)grid.x;
-    dev_array<float4> x0, v0; dev_array<long long> f0; dev_array<double> partial; dev_array<fire_rep> st;
-    REMD_TRY(x0.alloc(h, (size_t)R * Npad));
-    REMD_TRY(v0.alloc(h, (size_t)R * Npad));
-    REMD_TRY(f0.alloc(h, 3 * (size_t)R * Npad));
-    REMD_TRY(partial.alloc(h, 3 * (size_t)R * nblk));
-    REMD_TRY(st.alloc(h, 2 * (size_t)R));
-    const float timestep = 0.001f;                               // 1 fs (integrators.py:2318)
-    fire_consts c{};
-    c.dt_max = 0.010f; c.f_inc = 1.1f; c.f_dec = 0.5f; c.alpha0 = 0.1f; c.f_alpha = 0.99f; c.n_min = 5;
-    c.dt_min = 1.0e-5f * timestep; c.ftol = (float)tolerance; c.ndof = 3.0f * (float)h->N;
-    std::vector<fire_rep> init(2 * (size_t)R);
-    for (auto& s : init) { s.dt = timestep; s.alpha = c.alpha0; s.n_neg = 0; s.converged = 0; s.E = 0.0; s.f2 = 0.0; }
-    REMD_CHECK(h, hipMemcpyAsync(st, init.data(), sizeof(fire_rep) * init.size(), hipMemcpyHostToDevice, h->stream));
-    // "velocities should be set to zero before using this integrator" (integrators.py:2341)
-    REMD_CHECK(h, hipMemsetAsync(h->d_vel, 0, sizeof(float4) * (size_t)R * Npad, h->stream));
-    const float tol = (float)fmax(h->constraint_tol, REMD_CONSTRAINT_TOL_FLOOR);
-    int cur = 0, rc = 0, it = 0;
-    h->forces_valid = false; h->force_zeroed = false;
-    if ((rc = remd_compute_forces(h, true))) return rc;
-    hipLaunchKernelGGL(fire_finish_kernel, grid, dim3(256), 0, h->stream, ut.n_units, ut.d_atoms, ut.d_type, ut.sc, tol, Npad, h->d_pos,
-                       h->d_vel, h->d_force, h->d_invmass, st, 0, partial);
-    hipLaunchKernelGGL(fire_update_kernel, grid, dim3(256), 0, h->stream, ut.n_units, ut.d_atoms, Npad, h->d_pos, h->d_vel, h->d_force,
-                       x0, v0, f0, h->d_potential, partial, nblk, c, st, st + R, 1);
-    cur = 1;
-    std::vector<fire_rep> host(R);
-    const int limit = max_iterations > 0 ? max_iterations : 200000;
-    bool all_done = false;
-    while (it < limit && !all_done) {
-        const int chunk = std::min(50, limit - it);              // the reference polls 'converged' every 50 steps (:1407-1409)
-        for (int k = 0; k < chunk; ++k, ++it) {
-            fire_rep* S = st + (size_t)cur * R;
-            fire_rep* Nx = st + (size_t)(1 - cur) * R;
-            hipLaunchKernelGGL(fire_move_kernel, grid, dim3(256), 0, h->stream, ut.n_units, ut.d_atoms, ut.d_type, ut.d_dist, ut.sc, tol,
-                               Npad, h->d_pos, h->d_vel, h->d_force, x0, v0, f0, h->d_invmass, S);
-            h->forces_valid = false; h->force_zeroed = false;
-            if ((rc = remd_compute_forces(h, true))) return rc;
-            hipLaunchKernelGGL(fire_finish_kernel, grid, dim3(256), 0, h->stream, ut.n_units, ut.d_atoms, ut.d_type, ut.sc, tol, Npad,
-                               h->d_pos, h->d_vel, h->d_force, h->d_invmass, S, 1, partial);
-            hipLaunchKernelGGL(fire_update_kernel, grid, dim3(256), 0, h->stream, ut.n_units, ut.d_atoms, Npad, h->d_pos, h->d_vel,
-                               h->d_force, x0, v0, f0, h->d_potential, partial, nblk, c, S, Nx, 0);
-            cur = 1 - cur;
-        }
-        hipMemcpyAsync(host.data(), st + (size_t)cur * R, sizeof(fire_rep) * R, hipMemcpyDeviceToHost, h->stream);
-        if (hipStreamSynchronize(h->stream) != hipSuccess) return remd_fail(h, -2, "minimize: device error");
-        all_done = true;
-        for (int r = 0; r < R; ++r) all_done = all_done && host[r].converged;
-        if (max_iterations > 0) all_done = false;               // a fixed number of steps was asked for
-    }
-    hipMemcpyAsync(host.data(), st + (size_t)cur * R, sizeof(fire_rep) * R, hipMemcpyDeviceToHost, h->stream);
-    hipStreamSynchronize(h->stream);
-    if (converged_out) for (int r = 0; r < R; ++r) converged_out[r] = host[r].converged;
-    if (n_iter_out) *n_iter_out = it;
-    h->forces_valid = false; h->force_zeroed = false;
     REMD_CHECK(h, hipGetLastError());
     return 0;
 }

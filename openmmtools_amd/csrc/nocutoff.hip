@@ -142,7 +142,7 @@ int remd_nocutoff_build(remd_ctx* h, const remd_system_desc* d)
     return 0;
 }
 
-// the tables, for the resident small-molecule kernel (integrate.hip)
+// the tables, for the resident small-molecule kernel (resident.hip)
 int remd_nocutoff_info(remd_ctx* h, const float4** param, const unsigned int** excl, int* words, int* n_exc, const int** exc_atoms, const float4** exc_par)
 {
     const nocutoff_tables* t = h->nc.get();

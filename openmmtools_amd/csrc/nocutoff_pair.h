@@ -1,5 +1,5 @@
 // The pair and exception arithmetic of a NoCutoff NonbondedForce (nocutoff.hip), shared with the resident small-molecule kernel of
-// integrate.hip: both sum an atom's pair forces in ascending partner order in fp32 and convert once to fixed point, so the two paths give
+// resident.hip: both sum an atom's pair forces in ascending partner order in fp32 and convert once to fixed point, so the two paths give
 // the same bits.
 #pragma once
 #include "remd_internal.h"

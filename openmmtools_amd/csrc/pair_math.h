@@ -1,4 +1,4 @@
-// Pair arithmetic of the direct-space nonbonded kernels (forces.hip) and of the resident small-system kernel (integrate.hip):
+// Pair arithmetic of the direct-space nonbonded kernels (forces.hip) and of the resident small-system kernel (resident.hip):
 // one definition, so that both paths evaluate a pair with the same instructions.
 // Reference semantics: OpenMM NonbondedForce as the test systems configure it (testsystems.py:1978-2000, 3504-3517) and the
 // alchemical soft-core of alchemy.py:1383-1388; f64 restatement: oracle/forcefield.py.

@@ -333,7 +333,7 @@ struct remd_ctx {
     // ---- feature tables, each defined in the file that owns it ------------------------------
     remd_table<pme_state> pme;         // pme.hip
     remd_table<nb_tables> nb;          // forces.hip: the nonbonded setup
-    remd_table<unit_tables> units;     // integrate.hip: constraint units
+    remd_table<unit_tables> units;     // constraint_units.h, built by integrate.hip: constraint units
     remd_table<nocutoff_tables> nc;    // nocutoff.hip
     remd_table<gbsa_tables> gb;        // gbsa.hip
     remd_table<region_tables> reg;     // alch_regions.hip
@@ -399,6 +399,8 @@ struct remd_ctx {
 
 void remd_set_global_error(const std::string& s);
 int remd_fail(remd_ctx* h, int code, const std::string& msg);
+// the tolerance every constraint solve of this handle is launched with
+inline float remd_constraint_tol(const remd_ctx* h) { return (float)fmax(h->constraint_tol, REMD_CONSTRAINT_TOL_FLOOR); }
 void remd_comm_release(remd_ctx* h);      // comm.hip
 
 // profiling wrapper: brackets a launch with HIP events recorded on the handle's stream.  Nothing is
@@ -440,12 +442,23 @@ const unsigned* remd_mix_pending_flag(remd_ctx* h);
 int remd_parse_splitting(remd_ctx* h, const char* splitting, std::vector<char>& tokens, int& nV, int& nR, int& nO, int* nVg = nullptr);
 int remd_run_steps(remd_ctx* h, const std::vector<char>& tokens, int nV, int nR, int nO,
                    int64_t iteration, int64_t first_step, int n_steps);
-int remd_run_steps_many(remd_ctx** hs, int n, int64_t iteration, int64_t first_step, int n_steps);
-long long remd_chain_blocks(remd_ctx* h);            // workgroups of one integrator-chain launch   // the handles' steps taking turns
+int remd_run_steps_many(remd_ctx** hs, int n, int64_t iteration, int64_t first_step, int n_steps);   // the handles' steps taking turns
+long long remd_chain_blocks(remd_ctx* h);            // workgroups of one integrator-chain launch
 int remd_assign_velocities(remd_ctx* h, int64_t iteration);
 int remd_kinetic_energy(remd_ctx* h);
 int remd_check_finite(remd_ctx* h);
 int remd_work_buffers(remd_ctx* h);                    // heat / shadow-work accumulators and the '{' snapshot of the local replicas
+int remd_build_constraints(remd_ctx* h, const remd_system_desc* d);
+
+// ---- resident.hip: a whole propagation in one launch ------------------------------------------
+// each returns 1 when it ran the propagation, 0 when the system / request is not one it covers, < 0 on error
+int remd_run_steps_resident(remd_ctx* h, const std::vector<char>& tokens, int nV, int nR, int nO,
+                            int64_t iteration, int64_t first_step, int n_steps);
+int remd_run_steps_resident_mol(remd_ctx* h, const std::vector<char>& tokens, int nV, int nR, int nO,
+                                int64_t iteration, int64_t first_step, int n_steps);
+
+// ---- minimize.hip -----------------------------------------------------------------------
+int remd_minimize_impl(remd_ctx* h, double tolerance, int max_iterations, int32_t* converged, int32_t* n_iterations);
 
 // ---- forces.hip -------------------------------------------------------------------------
 int remd_barostat_attempt(remd_ctx* h);                      // barostat.hip
@@ -453,7 +466,6 @@ int remd_barostat_buffers(remd_ctx* h);                      // (its per-replica
 #define REMD_BARO_AXIS_STRIDE 24
 int remd_tension_ukl(remd_ctx* h, double* d_rows);           // membrane barostat: - beta_l gamma_l A_xy(r) into the u_kl rows
 int remd_nb_molecules(remd_ctx* h, const int** first, const int** size);   // molecule table of the nonbonded setup (device); 0: none
-int remd_minimize_impl(remd_ctx* h, double tolerance, int max_iterations, int32_t* converged, int32_t* n_iterations);
 void remd_nb_invalidate_sort(remd_ctx* h);            // the next force evaluation re-sorts the molecules
 void remd_nb_reset_accumulators(remd_ctx* h);         // after a device-side fault: the sorted accumulators of a discarded evaluation
 void remd_nb_tune_step(remd_ctx* h, int steps_left_in_call);   // the pair kernel's residency, chosen by timing
@@ -493,7 +505,6 @@ int remd_regions_le_override(remd_ctx* h, const float* le, int* n, const float**
 // chain of this handle, so the join of a forked evaluation may be left in h->next.wait for that chain to poll
 int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask = ~0u, bool chain_follows = false);
 int remd_build_nonbonded(remd_ctx* h, const remd_system_desc* d);
-int remd_build_constraints(remd_ctx* h, const remd_system_desc* d);
 
 // restraints.hip: receptor-ligand restraints (include/remd_hip_restraints.h); their energy partial is the LAST slot of d_epart
 void remd_restraints_release(remd_ctx* h);

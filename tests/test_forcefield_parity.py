@@ -1,4 +1,4 @@
-"""GPU parity of the force-field kernels (csrc/forces.hip, pme.hip, SETTLE/SHAKE in integrate.hip) against the
+"""GPU parity of the force-field kernels (csrc/forces.hip, pme.hip, SETTLE/SHAKE in constraint_units.h) against the
 f64 oracle, through the C ABI.  Tolerances: u_kl / potential 1e-5 relative (north_star); forces to the
 reference's own cross-platform bar of 0.06 kcal/mol/A RMSE = 2.5 kJ/mol/nm (scripts/test_openmm_platforms.py:154-155),
 in practice ~1e-4 relative; FFT vs numpy to fp32 round-off."""

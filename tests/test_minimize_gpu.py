@@ -1,4 +1,4 @@
-"""GPU parity of the FIRE minimiser (integrate.hip: fire_move / fire_finish / fire_update kernels behind remd_minimize)
+"""GPU parity of the FIRE minimiser (minimize.hip: fire_move / fire_finish / fire_update kernels behind remd_minimize)
 against the f64 oracle restatement of the reference's FIREMinimizationIntegrator (integrators.py:2290-2469).
 
 FIRE is deterministic: the discrete protocol (accepted / restarted steps, time step, alpha) must follow the oracle step

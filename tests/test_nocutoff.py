@@ -208,7 +208,7 @@ def _water_cluster(n=12):
 @pytest.mark.parametrize('which,splitting,dt,n_steps', [('alanine', 'V R R O R R V', 0.002, 10), ('alanine', 'V R R O R R V', 0.002, 500),
                                                         ('alanine', 'O V R V O', 0.001, 100), ('droplet', 'V R O R V', 0.002, 100), ('water', 'V R O R V', 0.001, 5), ('water', 'V R R O R R V', 0.002, 10)])
 def test_resident_small_molecule_kernel_follows_the_regular_launches(hip_engine_factory, monkeypatch, which, splitting, dt, n_steps):
-    """NoCutoff systems of up to 64 atoms are propagated by ONE launch per move (integrate.hip resident_mol_kernel: a workgroup per
+    """NoCutoff systems of up to 64 atoms are propagated by ONE launch per move (resident.hip resident_mol_kernel: a workgroup per
     replica, a constraint unit per thread, positions and fixed-point force accumulators in LDS) instead of three dependent launches per
     MD step.  Pair sums in the same fp32 order, every contribution converted to fixed point the same way, the same Philox streams and
     the same centre-of-mass sum: the trajectory follows the regular launches (REMD_RESIDENT=0) to fp32 rounding -- one ulp of a velocity
