@@ -1,0 +1,116 @@
+/*
+ * remd_hip_custom.h — GPU-only extension of the C ABI in remd_hip.h: custom bond, angle, torsion and external forces.
+ *
+ * OpenMM's CustomBondForce, CustomAngleForce, CustomTorsionForce and CustomExternalForce: an energy expression of r (bond), theta
+ * (angle, torsion) or x, y, z (external), of per-term parameters and of global parameters, evaluated per term.  The host compiles
+ * the expression (openmmtools_amd/custom_expr.py) into a postfix program; the device runs it on a small stack machine that carries
+ * every value together with its partial derivatives with respect to the force's variables (forward mode), so the forces need no
+ * second program.
+ *
+ * The program: n_program (opcode, operand) pairs of int32.  Operands index the constant table (REMD_CX_CONST), the force's
+ * variables (REMD_CX_VAR: 0 = r / theta / x, 1 = y, 2 = z), the term's parameters (REMD_CX_PARAM), the handle's global-parameter
+ * columns (REMD_CX_GLOBAL) or give the exponent itself (REMD_CX_POWI: a small constant integer power, evaluated with
+ * multiplications).  Every other opcode takes its arguments from the stack, first argument deepest, and pushes one result.
+ * Piecewise functions (abs, min, max, select) differentiate as the branch taken; step, delta, floor and ceil have derivative zero.
+ *
+ * Global parameters belong to the handle: every force's program addresses the same n_globals columns, and every state carries one
+ * value per column (remd_set_custom_globals).  A term acts in every force evaluation (MD steps, energies, the barostat,
+ * minimisation); the u_kl rows get beta_l (E_r(g_l) - E_r(g_own(r))) for every state l, E_r(g) the sum of all custom terms at
+ * replica r's positions under the globals g.
+ *
+ * Limits (a descriptor beyond them is refused): REMD_CUSTOM_MAX_PROGRAM instructions per force, REMD_CUSTOM_MAX_STACK stack slots,
+ * REMD_CUSTOM_MAX_PARAMS parameters per term, REMD_CUSTOM_MAX_GLOBALS global columns per handle, REMD_CUSTOM_MAX_FORCES forces
+ * per handle.
+ *
+ * These entry points are declared here and not in remd_hip.h because the CPU port of the ABI does not provide them: a host binds
+ * them only where the loaded library exports them.  Conventions as in remd_hip.h.
+ */
+#ifndef REMD_HIP_CUSTOM_H
+#define REMD_HIP_CUSTOM_H
+
+#include "remd_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define REMD_CUSTOM_BOND     0     /* atoms [n][2], variable r                                                              */
+#define REMD_CUSTOM_ANGLE    1     /* atoms [n][3], variable theta in [0, pi]                                               */
+#define REMD_CUSTOM_TORSION  2     /* atoms [n][4], variable theta in (-pi, pi], the sign convention of PeriodicTorsionForce */
+#define REMD_CUSTOM_EXTERNAL 3     /* atoms [n][1], variables x, y, z                                                       */
+
+#define REMD_CUSTOM_MAX_PROGRAM 256
+#define REMD_CUSTOM_MAX_STACK   16
+#define REMD_CUSTOM_MAX_PARAMS  16
+#define REMD_CUSTOM_MAX_GLOBALS 16
+#define REMD_CUSTOM_MAX_FORCES  8
+
+/* opcodes */
+#define REMD_CX_CONST   0      /* push consts[operand]                                                                      */
+#define REMD_CX_VAR     1      /* push variable operand                                                                     */
+#define REMD_CX_PARAM   2      /* push the term's parameter operand                                                         */
+#define REMD_CX_GLOBAL  3      /* push global column operand at the state in question                                       */
+#define REMD_CX_ADD     4
+#define REMD_CX_SUB     5
+#define REMD_CX_MUL     6
+#define REMD_CX_DIV     7
+#define REMD_CX_NEG     8
+#define REMD_CX_POWI    9      /* a ^ operand, operand a constant integer with |operand| <= 64: multiplications              */
+#define REMD_CX_POW     10     /* a ^ b, both from the stack                                                                */
+#define REMD_CX_SQRT    11
+#define REMD_CX_EXP     12
+#define REMD_CX_LOG     13
+#define REMD_CX_SIN     14
+#define REMD_CX_COS     15
+#define REMD_CX_TAN     16
+#define REMD_CX_ASIN    17
+#define REMD_CX_ACOS    18
+#define REMD_CX_ATAN    19
+#define REMD_CX_ATAN2   20
+#define REMD_CX_SINH    21
+#define REMD_CX_COSH    22
+#define REMD_CX_TANH    23
+#define REMD_CX_ERF     24
+#define REMD_CX_ERFC    25
+#define REMD_CX_ABS     26
+#define REMD_CX_MIN     27
+#define REMD_CX_MAX     28
+#define REMD_CX_STEP    29     /* 1 for x >= 0, else 0                                                                      */
+#define REMD_CX_DELTA   30     /* 1 for x == 0, else 0                                                                      */
+#define REMD_CX_SELECT  31     /* select(x, y, z): y where x != 0, else z                                                   */
+#define REMD_CX_FLOOR   32
+#define REMD_CX_CEIL    33
+#define REMD_CX_PERIODICDISTANCE 34   /* (x1, y1, z1, x2, y2, z2): minimum-image distance under the replica's own box        */
+#define REMD_CX_N_OPCODES 35
+
+typedef struct remd_custom_force_desc {
+    int32_t kind;                  /* REMD_CUSTOM_*                                                                        */
+    int32_t n_terms;               /* bonds / angles / torsions / particles                                                */
+    const int32_t* atoms;          /* [n_terms][2 | 3 | 4 | 1]                                                             */
+    int32_t n_params;              /* parameters per term                                                                  */
+    const double* params;          /* [n_terms][n_params]                                                                  */
+    int32_t n_program;             /* instructions                                                                         */
+    const int32_t* program;        /* [n_program][2]: opcode, operand                                                      */
+    int32_t n_consts;
+    const double* consts;          /* [n_consts]                                                                           */
+    int32_t stack_depth;           /* the most stack slots the program holds at once                                       */
+    int32_t n_globals;             /* the handle's global-parameter columns: the same in every descriptor of a call        */
+    const double* global_defaults; /* [n_globals]: every state's values until remd_set_custom_globals                      */
+    int32_t periodic;              /* 1: differences between atoms are minimum images under the replica's own box          */
+    int32_t force_group;           /* Force.getForceGroup() (multiple-time-step splittings)                                */
+} remd_custom_force_desc;
+
+/* the custom forces of the system; call after remd_set_system (which forgets them).  n = 0: none.  Every custom force of a handle
+   sits in one force group.                                                                                                       */
+int  remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, int n);
+/* values[K][n_globals]: every state's value of each global column; K as in remd_set_states (call after it: the terms refuse to act
+   on globals that belong to an older set of states)                                                                              */
+int  remd_set_custom_globals(remd_handle h, const double* values);
+/* out[R_local][n]: each custom force's energy (kJ/mol) at the local replicas' current positions and own states                   */
+int  remd_get_custom_energies(remd_handle h, double* out);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif

@@ -69,6 +69,14 @@ class RemdRestraintDesc(C.Structure):
                 ('periodic', C.c_int32), ('force_group', C.c_int32)]
 
 
+class RemdCustomForceDesc(C.Structure):
+    """remd_custom_force_desc of include/remd_hip_custom.h (custom bond / angle / torsion / external forces, custom_expr.py)."""
+    _fields_ = [('kind', C.c_int32), ('n_terms', C.c_int32), ('atoms', c_int32_p), ('n_params', C.c_int32), ('params', c_double_p),
+                ('n_program', C.c_int32), ('program', c_int32_p), ('n_consts', C.c_int32), ('consts', c_double_p),
+                ('stack_depth', C.c_int32), ('n_globals', C.c_int32), ('global_defaults', c_double_p),
+                ('periodic', C.c_int32), ('force_group', C.c_int32)]
+
+
 class RemdGbModelDesc(C.Structure):
     """remd_gb_model_desc of include/remd_hip_gb.h (the constants and the cutoff of an OBC-family implicit-solvent model)."""
     _fields_ = [('offset', C.c_double), ('alpha', C.c_double), ('beta', C.c_double), ('gamma', C.c_double), ('ke', C.c_double),
@@ -77,6 +85,8 @@ class RemdGbModelDesc(C.Structure):
 
 # the GPU-only extension of include/remd_hip_restraints.h: bound where the loaded library exports it (the CPU port of the ABI does not)
 RESTRAINT_EXPORTS = ['remd_set_restraints', 'remd_set_restraint_lambdas', 'remd_get_restraint_energies']
+# the GPU-only extension of include/remd_hip_custom.h (custom bond / angle / torsion / external forces), bound the same way
+CUSTOM_EXPORTS = ['remd_set_custom_terms', 'remd_set_custom_globals', 'remd_get_custom_energies']
 # the GPU-only extension of include/remd_hip_barostat.h (per-axis Monte Carlo barostats), bound the same way
 BAROSTAT_AXIS_EXPORTS = ['remd_set_barostat_axes', 'remd_get_barostat_axis_stats']
 BAROSTAT_ANISOTROPIC, BAROSTAT_MEMBRANE = 1, 2
@@ -186,6 +196,12 @@ def load_library(path=None):
         lib.remd_set_restraint_lambdas.argtypes = [vp, c_double_p]
         lib.remd_get_restraint_energies.argtypes = [vp, c_double_p]
         for name in RESTRAINT_EXPORTS:
+            getattr(lib, name).restype = C.c_int
+    if hasattr(lib, 'remd_set_custom_terms'):             # include/remd_hip_custom.h (GPU-only, like the restraints)
+        lib.remd_set_custom_terms.argtypes = [vp, C.POINTER(RemdCustomForceDesc), C.c_int]
+        lib.remd_set_custom_globals.argtypes = [vp, c_double_p]
+        lib.remd_get_custom_energies.argtypes = [vp, c_double_p]
+        for name in CUSTOM_EXPORTS:
             getattr(lib, name).restype = C.c_int
     if hasattr(lib, 'remd_set_barostat_axes'):            # include/remd_hip_barostat.h (GPU-only, like the restraints)
         lib.remd_set_barostat_axes.argtypes = [vp, C.c_int, c_double_p, c_double_p, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -359,6 +375,10 @@ class HipEngine:
         restraints = desc_dict.get('restraints')
         if restraints:                                   # receptor-ligand restraints (forces.py; csrc/restraints.hip)
             self.set_restraints([restraints[k] for k in sorted(restraints)])
+        self.n_custom = self.n_custom_globals = 0
+        custom = desc_dict.get('custom_terms')
+        if custom:                                       # custom bond / angle / torsion / external forces (custom_expr.py; csrc/custom_terms.hip)
+            self.set_custom_terms([custom[k] for k in sorted(custom)])
 
     def _restraint_entry(self, name):
         if not hasattr(self.lib, name):
@@ -390,6 +410,44 @@ class HipEngine:
         fn = self._restraint_entry('remd_get_restraint_energies')
         out = np.zeros((self.R, self.n_restraints))
         self._check(fn(self.h, _dp(out)), 'remd_get_restraint_energies')
+        return out
+
+    def _custom_entry(self, name):
+        if not hasattr(self.lib, name):
+            raise NotImplementedError('%s: this build of the engine library has no custom bond / angle / torsion / external forces '
+                                      '(include/remd_hip_custom.h is GPU-only)' % name)
+        return getattr(self.lib, name)
+
+    def set_custom_terms(self, terms):
+        """The custom forces of the system (dicts of system.system_to_desc's 'custom_terms'); after set_system, which forgets them."""
+        fn = self._custom_entry('remd_set_custom_terms')
+        arr = (RemdCustomForceDesc * max(1, len(terms)))()
+        keep = []
+        for k, t in enumerate(terms):
+            atoms = np.ascontiguousarray(t['atoms'], dtype=np.int32)
+            params = np.ascontiguousarray(t['params'], dtype=np.float64).reshape(len(atoms), -1)
+            program = np.ascontiguousarray(t['program'], dtype=np.int32).reshape(-1, 2)
+            consts = np.ascontiguousarray(t['consts'], dtype=np.float64)
+            defaults = np.ascontiguousarray(t['global_defaults'], dtype=np.float64)
+            keep += [atoms, params, program, consts, defaults]
+            arr[k] = RemdCustomForceDesc(int(t['kind']), len(atoms), _ip(atoms), params.shape[1], _dp(params), len(program), _ip(program),
+                                         len(consts), _dp(consts), int(t['stack_depth']), len(defaults), _dp(defaults),
+                                         int(t['periodic']), int(t['force_group']))
+        self._check(fn(self.h, arr, len(terms)), 'remd_set_custom_terms')
+        self.n_custom = len(terms)
+        self.n_custom_globals = len(terms[0]['global_defaults']) if terms else 0
+
+    def set_custom_globals(self, values):
+        """[K][n_globals]: every state's value of each global parameter of the custom forces (after set_states)."""
+        fn = self._custom_entry('remd_set_custom_globals')
+        values = np.ascontiguousarray(values, dtype=np.float64).reshape(self.K, self.n_custom_globals)
+        self._check(fn(self.h, _dp(values)), 'remd_set_custom_globals')
+
+    def custom_energies(self):
+        """[R_local][n_custom] energy (kJ/mol) of each custom force at the current positions and the replicas' own states."""
+        fn = self._custom_entry('remd_get_custom_energies')
+        out = np.zeros((self.R, self.n_custom))
+        self._check(fn(self.h, _dp(out)), 'remd_get_custom_energies')
         return out
 
     def set_states(self, beta, lambda_sterics=None, lambda_electrostatics=None, energy_const=None):

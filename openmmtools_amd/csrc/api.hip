@@ -165,6 +165,7 @@ int remd_set_system(remd_handle h, const remd_system_desc* d)
     hipStreamSynchronize(h->stream);
     remd_regions_release(h);                    // remd_set_alchemical_regions follows the system it belongs to
     remd_restraints_release(h);                 // ... and so do remd_set_restraints (restraints.hip)
+    remd_custom_release(h);                     // ... and remd_set_custom_terms (custom_terms.hip)
     h->N = d->n_atoms;
     h->Npad = (d->n_atoms + 63) / 64 * 64;
     std::vector<float> im(h->Npad, 0.f), m(h->Npad, 0.f);
@@ -641,6 +642,7 @@ static int phase_children(remd_ctx* h, int P)
         if (h->gbsa && (rc = remd_gbsa_clone(h, c))) return rc;                    // implicit solvent (gbsa.hip)
         if (h->n_regions > 0 && (rc = remd_regions_clone(h, c))) return rc;       // general alchemical regions (alch_regions.hip)
         if (h->n_restraints > 0 && (rc = remd_restraints_clone(h, c))) return rc;  // receptor-ligand restraints (restraints.hip)
+        if (h->n_custom > 0 && (rc = remd_custom_clone(h, c))) return rc;          // custom bond / angle / torsion / external forces (custom_terms.hip)
         if (h->baro_frequency > 0) {
             if ((rc = remd_set_barostat(c, h->K, h->pressure_host.data(), h->baro_frequency))) return remd_fail(h, rc, std::string("phases: ") + c->err);
             c->econst_vref = h->econst_vref;
@@ -1188,6 +1190,7 @@ int remd_get_group_forces(remd_handle h, uint32_t groups, double* f)
     unsigned class_mask = 0u;
     for (int c = 0; c < 6; ++c) if ((groups >> h->fgroup[c]) & 1u) class_mask |= 1u << c;
     if (h->n_restraints > 0 && ((groups >> h->rst_group) & 1u)) class_mask |= 1u << REMD_FG_RESTRAINT;
+    if (h->n_custom > 0 && ((groups >> h->cst_group) & 1u)) class_mask |= 1u << REMD_FG_CUSTOM;
     return remd_read_forces(h, class_mask, "remd_get_group_forces", f);
 }
 
@@ -1222,7 +1225,7 @@ int remd_get_energy_components(remd_handle h, double* out)
     REMD_CHECK(h, hipStreamSynchronize(h->stream));
     for (int r = 0; r < h->R; ++r) {
         for (int k = 0; k < 8; ++k) out[9 * r + k] = ep[(size_t)r * h->n_epart + k];
-        double nb = 0; for (int k = 8; k < h->n_epart - 1; ++k) nb += ep[(size_t)r * h->n_epart + k];     // (the last slot: the restraints)
+        double nb = 0; for (int k = 8; k < h->n_epart - 1; ++k) nb += ep[(size_t)r * h->n_epart + k];     // (the last slot: the restraints and the custom terms)
         out[9 * r + 8] = nb;
     }
     return 0;

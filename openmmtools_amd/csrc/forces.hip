@@ -2040,9 +2040,10 @@ static listed_tables listed_terms(remd_ctx* h, unsigned class_mask, int& total)
 
 // the restraints (restraints.hip) go with the listed terms of a force-only evaluation: their launch and the ONE launch of the listed
 // terms on stream st (total = 0: the listed terms rode in the spreading launch, or there are none)
-static int launch_listed(remd_ctx* h, bool do_rst, const listed_tables& T, int total, hipStream_t st)
+static int launch_listed(remd_ctx* h, bool do_rst, bool do_cst, const listed_tables& T, int total, hipStream_t st)
 {
     if (do_rst) REMD_TRY(remd_restraints_forces(h, false, h->n_epart - 1, st));
+    if (do_cst) REMD_TRY(remd_custom_forces(h, false, h->n_epart - 1, st));
     if (total > 0) {
         remd_prof_scope ps(h, "bonded", st);
         hipLaunchKernelGGL(listed_forces_kernel, dim3((total + 255) / 256, h->R), dim3(256), 0, st, T, h->Npad, h->d_pos,
@@ -2059,6 +2060,7 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask, bool
     const bool do_ext = (class_mask >> REMD_FG_EXTERNAL) & 1u;
     const bool do_nb = (class_mask >> REMD_FG_NONBONDED) & 1u, do_recip = (class_mask >> REMD_FG_RECIPROCAL) & 1u;
     const bool do_rst = h->n_restraints > 0 && ((class_mask >> REMD_FG_RESTRAINT) & 1u);
+    const bool do_cst = h->n_custom > 0 && ((class_mask >> REMD_FG_CUSTOM) & 1u);      // (custom_terms.hip: beside the restraints)
     const int R = h->R;
     nb_tables* const nbt = h->nb_method != REMD_NB_NONE ? &remd_table_of(h->nb) : nullptr;
 
@@ -2155,17 +2157,18 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask, bool
                      h->d_pos, h->d_force, h->d_epart, h->n_epart);
         }
         if (do_rst) REMD_TRY(remd_restraints_forces(h, with_energy, h->n_epart - 1, direct_st));
+        if (do_cst) REMD_TRY(remd_custom_forces(h, with_energy, h->n_epart - 1, direct_st));
     }
     if (nbt && do_nb) REMD_TRY(ensure_sorted(h, *nbt, direct_st));
     // (on the main stream the listed terms queue up behind the mesh launches already enqueued there)
     if (listed == LISTED_MAIN || listed == LISTED_RIDE)
-        REMD_TRY(launch_listed(h, do_rst, listed_tab, listed == LISTED_RIDE ? 0 : listed_total, main_st));
+        REMD_TRY(launch_listed(h, do_rst, do_cst, listed_tab, listed == LISTED_RIDE ? 0 : listed_total, main_st));
     remd_fold_args fold;               // what the scatter counts for the next integrator chain, where launch_nb took want_fold
     if (nbt && do_nb) {
         remd_prof_scope ps(h, "nonbonded", direct_st);
         REMD_TRY(with_energy ? launch_nb_method<true>(h, *nbt, direct_st, want_fold, fold) : launch_nb_method<false>(h, *nbt, direct_st, want_fold, fold));
     }
-    if (listed == LISTED_DIRECT) REMD_TRY(launch_listed(h, do_rst, listed_tab, listed_total, direct_st));
+    if (listed == LISTED_DIRECT) REMD_TRY(launch_listed(h, do_rst, do_cst, listed_tab, listed_total, direct_st));
     if (nbt && listed == LISTED_KERNELS) {
         nb_tables& t = *nbt;
         if (t.n_exc > 0) {
@@ -2378,5 +2381,6 @@ int remd_assemble_ukl(remd_ctx* h, double* d_rows)
     if (rc) return rc;
     // - beta_l gamma_l A_xy(r) of a membrane barostat (barostat.hip), behind whichever of the three assemblies ran
     if (h->baro_frequency > 0 && h->baro_kind == 2 && (rc = remd_tension_ukl(h, d_rows))) return rc;
-    return h->n_restraints > 0 ? remd_restraints_ukl(h, d_rows) : 0;       // + beta_l (lambda_l - lambda_own) E_r of the restraints
+    if (h->n_restraints > 0 && (rc = remd_restraints_ukl(h, d_rows))) return rc;       // + beta_l (lambda_l - lambda_own) E_r of the restraints
+    return h->n_custom > 0 ? remd_custom_ukl(h, d_rows) : 0;                           // + beta_l (E_r(g_l) - E_r(g_own)) of the custom terms
 }

@@ -724,6 +724,7 @@ struct step_runner {
                 base.hVg[g] = h->nVg[g] > 0 ? (float)(h->dt / h->nVg[g]) : 0.f;
                 for (int c = 0; c < 6; ++c) if (h->fgroup[c] == g) group_mask[g] |= 1u << c;
                 if (h->n_restraints > 0 && h->rst_group == g) group_mask[g] |= 1u << REMD_FG_RESTRAINT;     // (restraints.hip)
+                if (h->n_custom > 0 && h->cst_group == g) group_mask[g] |= 1u << REMD_FG_CUSTOM;            // (custom_terms.hip)
                 if (h->nVg[g] > 0 && h->d_force_g[g].size() != nf) {
                     if (h->d_force_g[g]) REMD_CHECK(h, hipStreamSynchronize(h->stream));
                     REMD_TRY(h->d_force_g[g].alloc(h, nf));
@@ -738,6 +739,9 @@ struct step_runner {
                                             "(its forces would never act); groups 0-3 are supported");
             if (h->n_restraints > 0 && (h->rst_group > 3 || !(named & (1u << REMD_FG_RESTRAINT))))
                 return remd_fail(h, -3, "multiple-time-step splitting: the restraints sit in a force group that no V of the splitting names "
+                                        "(their forces would never act); groups 0-3 are supported");
+            if (h->n_custom > 0 && (h->cst_group > 3 || !(named & (1u << REMD_FG_CUSTOM))))
+                return remd_fail(h, -3, "multiple-time-step splitting: the custom forces sit in a force group that no V of the splitting names "
                                         "(their forces would never act); groups 0-3 are supported");
         }
         int n_braces = 0;

@@ -62,12 +62,12 @@ private:
 #define REMD_TRY(expr) do { const int _rc = (expr); if (_rc) return _rc; } while (0)
 
 // The feature tables a handle owns, each defined in the .hip file that builds it; the deleter of each is defined there too.
-struct nb_tables; struct pme_state; struct unit_tables; struct gbsa_tables; struct nocutoff_tables; struct region_tables; struct rst_tables;
+struct nb_tables; struct pme_state; struct unit_tables; struct gbsa_tables; struct nocutoff_tables; struct region_tables; struct rst_tables; struct cst_tables;
 struct mix_pre_buffers;
 struct remd_table_deleter {
     void operator()(nb_tables*) const; void operator()(pme_state*) const; void operator()(unit_tables*) const;
     void operator()(gbsa_tables*) const; void operator()(nocutoff_tables*) const; void operator()(region_tables*) const;
-    void operator()(rst_tables*) const; void operator()(mix_pre_buffers*) const;
+    void operator()(rst_tables*) const; void operator()(cst_tables*) const; void operator()(mix_pre_buffers*) const;
 };
 template <typename T> using remd_table = std::unique_ptr<T, remd_table_deleter>;
 // a handle's table, made on first use
@@ -263,6 +263,7 @@ struct remd_ctx {
     int regions_exact = 0;             // ... under the exact PME treatment (the regions' scaled charges inside the Ewald sum)
     long long states_version = 0;      // bumped by every remd_set_states (restraints.hip: the restraint lambdas belong to one set of states)
     int n_restraints = 0, rst_group = 0;   // remd_set_restraints: receptor-ligand restraints and their force group (restraints.hip holds the tables)
+    int n_custom = 0, cst_group = 0;       // remd_set_custom_terms: custom bond / angle / torsion / external forces and their force group (custom_terms.hip)
 
     // ---- states ---------------------------------------------------------------------
     int K = 0;
@@ -338,6 +339,7 @@ struct remd_ctx {
     remd_table<gbsa_tables> gb;        // gbsa.hip
     remd_table<region_tables> reg;     // alch_regions.hip
     remd_table<rst_tables> rst;        // restraints.hip
+    remd_table<cst_tables> cst;        // custom_terms.hip
     remd_table<mix_pre_buffers> mix_pre;   // mix.hip: the hoisted swap-all path
 
     // ---- mixing scratch ----------------------------------------------------------------
@@ -485,6 +487,7 @@ void remd_launch_join_wait(remd_ctx* h);              // a join left for an inte
 #define REMD_FG_NONBONDED 4      /* direct space, exceptions, Ewald exclusion correction */
 #define REMD_FG_RECIPROCAL 5
 #define REMD_FG_RESTRAINT 6      /* receptor-ligand restraints (restraints.hip), force group remd_ctx::rst_group */
+#define REMD_FG_CUSTOM 7         /* custom bond / angle / torsion / external forces (custom_terms.hip), force group remd_ctx::cst_group */
 // nocutoff.hip: NonbondedForce with NoCutoff (vacuum systems)
 int remd_nocutoff_build(remd_ctx* h, const remd_system_desc* d);
 int remd_nocutoff_forces(remd_ctx* h, bool with_energy, int ep_slot);
@@ -511,6 +514,13 @@ void remd_restraints_release(remd_ctx* h);
 int remd_restraints_clone(remd_ctx* parent, remd_ctx* child);
 int remd_restraints_forces(remd_ctx* h, bool with_energy, int ep_slot, hipStream_t st);
 int remd_restraints_ukl(remd_ctx* h, double* d_rows /*[R][K], added to*/);
+
+// custom_terms.hip: custom bond / angle / torsion / external forces (include/remd_hip_custom.h); their energy joins the restraints'
+// slot of d_epart, added behind the restraint launch on the same stream
+void remd_custom_release(remd_ctx* h);
+int remd_custom_clone(remd_ctx* parent, remd_ctx* child);
+int remd_custom_forces(remd_ctx* h, bool with_energy, int ep_slot, hipStream_t st);
+int remd_custom_ukl(remd_ctx* h, double* d_rows /*[R][K], added to*/);
 
 // ---- pme.hip ----------------------------------------------------------------------------
 int remd_pme_setup(remd_ctx* h);

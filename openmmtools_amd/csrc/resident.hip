@@ -257,7 +257,7 @@ int remd_run_steps_resident(remd_ctx* h, const std::vector<char>& tokens, int nV
                             int64_t iteration, int64_t first_step, int n_steps)
 {
     if (!resident_takes_request(h, tokens, n_steps)) return 0;
-    if (h->N > 1024 || h->n_settle > 0 || h->n_shake > 0 || h->n_bonds > 0 || h->n_angles > 0 || h->n_torsions > 0 || h->n_restraints > 0 || h->gbsa) return 0;
+    if (h->N > 1024 || h->n_settle > 0 || h->n_shake > 0 || h->n_bonds > 0 || h->n_angles > 0 || h->n_torsions > 0 || h->n_restraints > 0 || h->n_custom > 0 || h->gbsa) return 0;
     int ok = 0, method = -1, alch = 0; nb_params p{}; const float4* param = nullptr; const float* rep_lam = nullptr;
     int rc = remd_nb_resident_info(h, &ok, &method, &alch, &p, &param, &rep_lam);
     if (rc) return rc;
@@ -478,7 +478,7 @@ int remd_run_steps_resident_mol(remd_ctx* h, const std::vector<char>& tokens, in
                                 int64_t iteration, int64_t first_step, int n_steps)
 {
     if (!resident_takes_request(h, tokens, n_steps)) return 0;
-    if (!h->nocutoff || h->gbsa || h->n_regions > 0 || h->nb_method != REMD_NB_NONE || h->n_ext > 0 || h->n_restraints > 0) return 0;
+    if (!h->nocutoff || h->gbsa || h->n_regions > 0 || h->nb_method != REMD_NB_NONE || h->n_ext > 0 || h->n_restraints > 0 || h->n_custom > 0) return 0;
     const unit_tables& ut = remd_table_of(h->units);
     if (h->N > RESIDENT_MOL_MAX_ATOMS || ut.n_units > RESIDENT_MOL_T || ut.n_units < 1) return 0;
     resident_mol_sys S{};

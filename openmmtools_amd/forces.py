@@ -16,7 +16,7 @@ import zlib
 
 import numpy as np
 
-from .system import Force
+from .system import Force, _CustomForce, CustomBondForce
 from .unit import to_md
 
 # 1 L / (N_A mol) in nm^3 (openmmtools/constants.py:18)
@@ -33,54 +33,7 @@ class NoForceFoundError(Exception):
     pass
 
 
-# ---- the two OpenMM custom forces, as far as the restraints use them ------------------------------------------------------------
-class _CustomForce(Force):
-    def __init__(self, energy):
-        super().__init__()
-        self._energy = str(energy)
-        self._globals = []                    # [name, default]
-        self._per_bond = []
-        self._periodic = False
-
-    def getEnergyFunction(self):
-        return self._energy
-
-    def setEnergyFunction(self, energy):
-        self._energy = str(energy)
-
-    def addGlobalParameter(self, name, defaultValue):
-        self._globals.append([str(name), float(defaultValue)])
-        return len(self._globals) - 1
-
-    def getNumGlobalParameters(self):
-        return len(self._globals)
-
-    def getGlobalParameterName(self, index):
-        return self._globals[index][0]
-
-    def getGlobalParameterDefaultValue(self, index):
-        return self._globals[index][1]
-
-    def setGlobalParameterDefaultValue(self, index, defaultValue):
-        self._globals[index][1] = float(defaultValue)
-
-    def addPerBondParameter(self, name):
-        self._per_bond.append(str(name))
-        return len(self._per_bond) - 1
-
-    def getNumPerBondParameters(self):
-        return len(self._per_bond)
-
-    def getPerBondParameterName(self, index):
-        return self._per_bond[index]
-
-    def setUsesPeriodicBoundaryConditions(self, periodic):
-        self._periodic = bool(periodic)
-
-    def usesPeriodicBoundaryConditions(self):
-        return self._periodic
-
-
+# ---- the OpenMM custom forces the restraints build on: CustomBondForce is system.py's, CustomCentroidBondForce as far as they use it ----
 class CustomCentroidBondForce(_CustomForce):
     """openmm.CustomCentroidBondForce: groups of particles (weights None = the particles' masses) and bonds between groups."""
 
@@ -120,28 +73,6 @@ class CustomCentroidBondForce(_CustomForce):
 
     def setBondParameters(self, index, groups, parameters=()):
         self._bonds[index] = (list(int(g) for g in groups), [float(p) for p in parameters])
-
-
-class CustomBondForce(_CustomForce):
-    """openmm.CustomBondForce: bonds between two particles, the energy a function of their distance r."""
-
-    def __init__(self, energy):
-        super().__init__(energy)
-        self._bonds = []                      # (p1, p2, parameters)
-
-    def addBond(self, particle1, particle2, parameters=()):
-        self._bonds.append((int(particle1), int(particle2), [float(p) for p in parameters]))
-        return len(self._bonds) - 1
-
-    def getNumBonds(self):
-        return len(self._bonds)
-
-    def getBondParameters(self, index):
-        p1, p2, parameters = self._bonds[index]
-        return p1, p2, list(parameters)
-
-    def setBondParameters(self, index, particle1, particle2, parameters=()):
-        self._bonds[index] = (int(particle1), int(particle2), [float(p) for p in parameters])
 
 
 # ---- restorable class hash (openmmtools/utils/utils.py:830, 912, 1023-1037) ----------------------------------------------------
@@ -522,10 +453,9 @@ _RESTRAINT_CLASSES = (HarmonicRestraintForce, HarmonicRestraintBondForce, FlatBo
 _BODIES = {HarmonicRestraintForceMixIn.ENERGY_FUNCTION: 0, FlatBottomRestraintForceMixIn.ENERGY_FUNCTION: 1}
 
 
-def restraint_terms(force, masses):
-    """What the engine needs of one restraint force (system.system_to_desc): dict(kind 0 harmonic / 1 flat bottom, K, r0, the two
-    groups with their centroid weights -- masses where the group gives none --, periodic flag, controlling parameter name, force
-    group).  NotImplementedError for a custom force whose energy is not one of the four restraint forms."""
+def _match_restraint_form(force):
+    """(kind 0 harmonic / 1 flat bottom, controlling parameter name) of a custom force whose energy is '<global> * (<restraint body>)',
+    else (None, None).  The one place that decides which kernel a CustomBondForce reaches (restraint_terms, is_restraint_form)."""
     restore_interface(force)
     energy = force.getEnergyFunction().replace(' ', '')
     names = [force.getGlobalParameterName(i) for i in range(force.getNumGlobalParameters())]
@@ -537,6 +467,15 @@ def restraint_terms(force, masses):
         for name in names:
             if energy == (name + '*(' + form + ')').replace(' ', ''):
                 kind, parameter = k, name
+    return kind, parameter
+
+
+def restraint_terms(force, masses):
+    """What the engine needs of one restraint force (system.system_to_desc): dict(kind 0 harmonic / 1 flat bottom, K, r0, the two
+    groups with their centroid weights -- masses where the group gives none --, periodic flag, controlling parameter name, force
+    group).  NotImplementedError for a custom force whose energy is not one of the four restraint forms."""
+    kind, parameter = _match_restraint_form(force)
+    is_centroid = isinstance(force, CustomCentroidBondForce)
     if kind is None or (is_centroid and force.getNumGroupsPerBond() != 2):
         raise NotImplementedError('unsupported custom force %r (energy %r): only the restraint forms of openmmtools.forces are supported'
                                   % (type(force).__name__, force.getEnergyFunction()))
@@ -559,5 +498,14 @@ def restraint_terms(force, masses):
     return out
 
 
+def is_restraint_form(force):
+    """Whether a custom force carries one of the restraint forms (csrc/restraints.hip evaluates it): restraint_terms' own matcher."""
+    return _match_restraint_form(force)[0] is not None
+
+
 def is_restraint_force(force):
-    return isinstance(force, (CustomCentroidBondForce, CustomBondForce))
+    """The forces restraint_terms takes: a CustomCentroidBondForce (refused there unless it is a restraint form) and a CustomBondForce
+    in one of the restraint forms; any other CustomBondForce expression takes the expression path (custom_expr.py)."""
+    if isinstance(force, CustomCentroidBondForce):
+        return True
+    return isinstance(force, CustomBondForce) and is_restraint_form(force)

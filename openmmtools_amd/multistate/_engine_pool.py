@@ -62,6 +62,8 @@ class EnginePool:
             raise ValueError('one system description per compatibility group')
         if any(d.get('restraints') for d in descs):
             raise NotImplementedError('restraints (forces.py) in more than one compatibility group')
+        if any(d.get('custom_terms') for d in descs):
+            raise NotImplementedError('custom bond / angle / torsion / external forces (custom_expr.py) in more than one compatibility group')
         n = {int(d['n_atoms']) for d in descs}
         if len(n) != 1:
             raise ValueError('the Systems of all thermodynamic states must hold the same particles (%s)' % sorted(n))

@@ -675,6 +675,10 @@ class MultiStateSampler:
         lam_e = np.array([s.lambda_electrostatics for s in all_states], dtype=np.float64)
         eng.set_states(beta, lam_s, lam_e, self._state_energy_constants(all_states))
         regions = getattr(ref.system, 'alchemical_regions', None)
+        # (a global parameter of a custom force may carry one of the alchemical names -- the reference's lambda_bonds example: it is that
+        # force's own, handed over with the custom globals below)
+        custom = desc.get('custom_globals') if isinstance(desc, dict) else None
+        custom_global_names = set(custom['names']) if custom else set()
         if regions is not None:
             # general alchemical regions (alchemy.py here; csrc/alch_regions.hip): every region's lambdas at every state
             names = [r.name for r in regions]
@@ -683,7 +687,8 @@ class MultiStateSampler:
             bonded = np.array([s.region_bonded_lambdas(names) for s in all_states], dtype=np.float64)           # [K][3][n]
             if np.any(bonded != 1.0):
                 eng.set_region_bonded_lambdas(bonded[:, 0], bonded[:, 1], bonded[:, 2])
-        elif any(getattr(s, k, 1.0) != 1.0 for s in all_states for k in ('lambda_bonds', 'lambda_angles', 'lambda_torsions')):
+        elif any(getattr(s, k, 1.0) != 1.0 for s in all_states for k in ('lambda_bonds', 'lambda_angles', 'lambda_torsions')
+                 if k not in custom_global_names):
             raise NotImplementedError('lambda_bonds / lambda_angles / lambda_torsions act on the bonded terms an AlchemicalRegion names '
                                       '(alchemical_bonds=..., alchemical_angles=..., alchemical_torsions=...): this System has none')
         restraints = desc.get('restraints') if isinstance(desc, dict) else None
@@ -691,6 +696,11 @@ class MultiStateSampler:
             # receptor-ligand restraints (forces.py): every state's value of each restraint's controlling parameter -- the state's
             # global parameter (a GlobalParameterState, e.g. lambda_restraints), else the default the force itself carries
             eng.set_restraint_lambdas(restraint_lambdas(ref.system, [restraints[k]['parameter'] for k in sorted(restraints)], all_states))
+        if custom:
+            # custom bond / angle / torsion / external forces (custom_expr.py): every state's value of each global parameter -- the
+            # state's GlobalParameterState where it carries the name, else the default the forces carry
+            from ..custom_expr import custom_globals
+            eng.set_custom_globals(custom_globals(ref.system, custom['names'], all_states))
         self._program_engine_move()
         pressures = [s.pressure for s in all_states]
         if any(p is not None for p in pressures):

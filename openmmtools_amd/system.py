@@ -176,8 +176,166 @@ class NonbondedForce(Force):
         return self._method in (NonbondedForce.CutoffPeriodic, NonbondedForce.Ewald, NonbondedForce.PME)
 
 
-class CustomExternalForce(Force):
-    """Only the harmonic-well expression of testsystems.HarmonicOscillator (testsystems.py:779-786)."""
+class _CustomForce(Force):
+    """What OpenMM's custom forces share: the energy string, global parameters with default values, per-term parameter names, the
+    periodic-boundary flag and tabulated functions (which the engine refuses)."""
+
+    def __init__(self, energy):
+        super().__init__()
+        self._energy = str(energy)
+        self._globals = []                    # [name, default]
+        self._per_bond = []                   # per-term parameter names (per bond / angle / torsion / particle)
+        self._periodic = False
+        self._functions = []                  # (name, function)
+
+    def getEnergyFunction(self):
+        return self._energy
+
+    def setEnergyFunction(self, energy):
+        self._energy = str(energy)
+
+    def addGlobalParameter(self, name, defaultValue):
+        self._globals.append([str(name), float(defaultValue)])
+        return len(self._globals) - 1
+
+    def getNumGlobalParameters(self):
+        return len(self._globals)
+
+    def getGlobalParameterName(self, index):
+        return self._globals[index][0]
+
+    def getGlobalParameterDefaultValue(self, index):
+        return self._globals[index][1]
+
+    def setGlobalParameterDefaultValue(self, index, defaultValue):
+        self._globals[index][1] = float(defaultValue)
+
+    def addPerBondParameter(self, name):
+        self._per_bond.append(str(name))
+        return len(self._per_bond) - 1
+
+    def getNumPerBondParameters(self):
+        return len(self._per_bond)
+
+    def getPerBondParameterName(self, index):
+        return self._per_bond[index]
+
+    def setUsesPeriodicBoundaryConditions(self, periodic):
+        self._periodic = bool(periodic)
+
+    def usesPeriodicBoundaryConditions(self):
+        return self._periodic
+
+    def addTabulatedFunction(self, name, function):
+        self._functions.append((str(name), function))
+        return len(self._functions) - 1
+
+    def getNumTabulatedFunctions(self):
+        return len(self._functions)
+
+    def getTabulatedFunctionName(self, index):
+        return self._functions[index][0]
+
+
+def _term_arrays(terms, width, n_params, what):
+    """atoms int32 [n][width] and params float64 [n][n_params] of a custom force's terms ((atoms..., parameters) tuples)."""
+    for t in terms:
+        if len(t[-1]) != n_params:
+            raise ValueError('%s: a term carries %d parameters, the force declares %d' % (what, len(t[-1]), n_params))
+    atoms = np.array([t[:width] for t in terms], dtype=np.int32).reshape(-1, width)
+    params = np.array([t[-1] for t in terms], dtype=np.float64).reshape(len(terms), n_params)
+    return atoms, params
+
+
+class CustomBondForce(_CustomForce):
+    """openmm.CustomBondForce: bonds between two particles, the energy a function of their distance r, of per-bond and of global
+    parameters.  The restraint forms of forces.py go to csrc/restraints.hip, every other expression to csrc/custom_terms.hip."""
+
+    def __init__(self, energy):
+        super().__init__(energy)
+        self._bonds = []                      # (p1, p2, parameters)
+
+    def addBond(self, particle1, particle2, parameters=()):
+        self._bonds.append((int(particle1), int(particle2), [float(p) for p in parameters]))
+        return len(self._bonds) - 1
+
+    def getNumBonds(self):
+        return len(self._bonds)
+
+    def getBondParameters(self, index):
+        p1, p2, parameters = self._bonds[index]
+        return p1, p2, list(parameters)
+
+    def setBondParameters(self, index, particle1, particle2, parameters=()):
+        self._bonds[index] = (int(particle1), int(particle2), [float(p) for p in parameters])
+
+    def _term_arrays(self):
+        return _term_arrays(self._bonds, 2, len(self._per_bond), 'CustomBondForce')
+
+
+class CustomAngleForce(_CustomForce):
+    """openmm.CustomAngleForce: the energy a function of the angle theta (radians, 0 ... pi) at the middle one of three particles."""
+
+    def __init__(self, energy):
+        super().__init__(energy)
+        self._angles = []                     # (p1, p2, p3, parameters)
+
+    addPerAngleParameter = _CustomForce.addPerBondParameter
+    getNumPerAngleParameters = _CustomForce.getNumPerBondParameters
+    getPerAngleParameterName = _CustomForce.getPerBondParameterName
+
+    def addAngle(self, particle1, particle2, particle3, parameters=()):
+        self._angles.append((int(particle1), int(particle2), int(particle3), [float(p) for p in parameters]))
+        return len(self._angles) - 1
+
+    def getNumAngles(self):
+        return len(self._angles)
+
+    def getAngleParameters(self, index):
+        p1, p2, p3, parameters = self._angles[index]
+        return p1, p2, p3, list(parameters)
+
+    def setAngleParameters(self, index, particle1, particle2, particle3, parameters=()):
+        self._angles[index] = (int(particle1), int(particle2), int(particle3), [float(p) for p in parameters])
+
+    def _term_arrays(self):
+        return _term_arrays(self._angles, 3, len(self._per_bond), 'CustomAngleForce')
+
+
+class CustomTorsionForce(_CustomForce):
+    """openmm.CustomTorsionForce: the energy a function of the dihedral theta (radians, -pi ... pi, the sign convention of
+    PeriodicTorsionForce) of four particles."""
+
+    def __init__(self, energy):
+        super().__init__(energy)
+        self._torsions = []                   # (p1, p2, p3, p4, parameters)
+
+    addPerTorsionParameter = _CustomForce.addPerBondParameter
+    getNumPerTorsionParameters = _CustomForce.getNumPerBondParameters
+    getPerTorsionParameterName = _CustomForce.getPerBondParameterName
+
+    def addTorsion(self, particle1, particle2, particle3, particle4, parameters=()):
+        self._torsions.append((int(particle1), int(particle2), int(particle3), int(particle4), [float(p) for p in parameters]))
+        return len(self._torsions) - 1
+
+    def getNumTorsions(self):
+        return len(self._torsions)
+
+    def getTorsionParameters(self, index):
+        p1, p2, p3, p4, parameters = self._torsions[index]
+        return p1, p2, p3, p4, list(parameters)
+
+    def setTorsionParameters(self, index, particle1, particle2, particle3, particle4, parameters=()):
+        self._torsions[index] = (int(particle1), int(particle2), int(particle3), int(particle4), [float(p) for p in parameters])
+
+    def _term_arrays(self):
+        return _term_arrays(self._torsions, 4, len(self._per_bond), 'CustomTorsionForce')
+
+
+class CustomExternalForce(_CustomForce):
+    """openmm.CustomExternalForce: the energy a function of a particle's x, y, z, of per-particle and of global parameters.  The
+    harmonic-well expression of testsystems.HarmonicOscillator (testsystems.py:779-786) keeps the engine's own kernel (ext_K / ext_x0 /
+    ext_U0 of remd_system_desc); every other expression goes to csrc/custom_terms.hip."""
 
     HARMONIC_EXPRESSION = ('(K/2.0) * ((x-x0)^2 + y^2 + z^2) + U0;'
                            'K = testsystems_HarmonicOscillator_K;'
@@ -185,24 +343,39 @@ class CustomExternalForce(Force):
                            'U0 = testsystems_HarmonicOscillator_U0;')
 
     def __init__(self, energy_expression):
-        super().__init__()
-        if energy_expression.replace(' ', '') != self.HARMONIC_EXPRESSION.replace(' ', ''):
-            raise NotImplementedError('only the testsystems.HarmonicOscillator expression is supported')
-        self.energy_expression = energy_expression
-        self.globals = {}
-        self.particles = []
+        super().__init__(energy_expression)
+        self._particles = []                  # (index, parameters)
 
-    def addGlobalParameter(self, name, value):
-        self.globals[name] = float(value)
+    addPerParticleParameter = _CustomForce.addPerBondParameter
+    getNumPerParticleParameters = _CustomForce.getNumPerBondParameters
+    getPerParticleParameterName = _CustomForce.getPerBondParameterName
+
+    energy_expression = property(lambda self: self._energy)
+    globals = property(lambda self: dict((n, v) for n, v in self._globals))       # {name: default value}
+    particles = property(lambda self: [p[0] for p in self._particles])            # particle indices
+
+    def is_harmonic_oscillator(self):
+        return self._energy.replace(' ', '') == self.HARMONIC_EXPRESSION.replace(' ', '') and not self._per_bond
 
     def getGlobalParameter(self, name):
         return self.globals[name]
 
     def addParticle(self, index, params=()):
-        self.particles.append(int(index))
+        self._particles.append((int(index), [float(p) for p in params]))
+        return len(self._particles) - 1
 
     def getNumParticles(self):
-        return len(self.particles)
+        return len(self._particles)
+
+    def getParticleParameters(self, index):
+        p, parameters = self._particles[index]
+        return p, list(parameters)
+
+    def setParticleParameters(self, index, particle, parameters=()):
+        self._particles[index] = (int(particle), [float(p) for p in parameters])
+
+    def _term_arrays(self):
+        return _term_arrays(self._particles, 1, len(self._per_bond), 'CustomExternalForce')
 
 
 class GBSAOBCForce(Force):
@@ -545,6 +718,11 @@ def _is_restraint(force):
     return is_restraint_force(force)
 
 
+def _is_custom_term(force):
+    from .custom_expr import is_custom_term_force
+    return is_custom_term_force(force)
+
+
 def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
     """Flatten a System into the arrays of remd_system_desc (include/remd_hip.h).
 
@@ -560,12 +738,14 @@ def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
     gb = None
     cmm = 0
     restraints = []                     # receptor-ligand restraints (forces.py): remd_set_restraints, include/remd_hip_restraints.h
+    custom = []                         # custom bond / angle / torsion / external expressions: remd_set_custom_terms, include/remd_hip_custom.h
     # force groups of (external, bonds, angles, torsions, nonbonded direct, PME reciprocal): remd_set_force_groups
     fg = [0, 0, 0, 0, 0, 0]
     for f in system.forces:
         g = f.getForceGroup() if hasattr(f, 'getForceGroup') else 0
         if isinstance(f, CustomExternalForce):
-            fg[0] = g
+            if f.is_harmonic_oscillator():
+                fg[0] = g
         elif isinstance(f, HarmonicBondForce):
             fg[1] = g
         elif isinstance(f, HarmonicAngleForce):
@@ -577,7 +757,9 @@ def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
             fg[5] = g if f.getReciprocalSpaceForceGroup() < 0 else f.getReciprocalSpaceForceGroup()
     d['force_groups'] = np.array(fg, dtype=np.int32)
     for f in system.forces:
-        if isinstance(f, CustomExternalForce):
+        if _is_custom_term(f):
+            custom.append(f)
+        elif isinstance(f, CustomExternalForce):
             d['n_ext'] = len(f.particles)
             d['ext_atoms'] = np.array(f.particles, dtype=np.int32)
             d['ext_K'] = f.globals['testsystems_HarmonicOscillator_K']
@@ -706,6 +888,14 @@ def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
     if restraints:
         # keyed by position ('000', '001', ...): the fingerprint hashes every array of a nested dict
         d['restraints'] = {'%03d' % k: r for k, r in enumerate(restraints)}
+    if custom:
+        from .custom_expr import custom_terms_desc
+        terms = custom_terms_desc(custom)
+        if terms:
+            d['custom_terms'] = terms
+            # the handle's global-parameter columns, once (every entry above repeats them for remd_custom_force_desc)
+            first = terms['000']
+            d['custom_globals'] = dict(names=list(first['global_names']), defaults=first['global_defaults'].copy())
     if getattr(system, 'alchemical_regions', None) is not None:
         # general regions: this descriptor is the NonbondedForce the factory leaves behind, the custom forces follow through
         # remd_set_alchemical_regions (alchemy.AbsoluteAlchemicalFactory._region_terms)

@@ -75,6 +75,9 @@ def _emit_force(forces, f, force_group=None, particles=None, exceptions=None, gl
         b = ET.SubElement(e, 'Exceptions')
         for (i, j, qq, sig, eps) in (f.exceptions if exceptions is None else exceptions):
             ET.SubElement(b, 'Exception', dict(eps=_f(eps), p1=str(i), p2=str(j), q=_f(qq), sig=_f(sig)))
+    elif _is_custom_term(f):
+        raise NotImplementedError('%s with the energy %r in a System document (only the HarmonicOscillator string and the restraint forms are written)'
+                                  % (name, f.getEnergyFunction()))
     elif isinstance(f, CustomExternalForce):
         e = ET.SubElement(forces, 'Force', dict(common, energy=f.energy_expression, version='1'))
         ET.SubElement(e, 'PerParticleParameters')
@@ -155,6 +158,11 @@ def parse_custom_gb_force(e):
     if _nonempty(e, 'Functions'):
         raise NotImplementedError('CustomGBForce: tabulated functions')
     return f
+
+
+def _is_custom_term(f):
+    from .custom_expr import is_custom_term_force
+    return is_custom_term_force(f)
 
 
 def _is_restraint(f):
@@ -363,7 +371,9 @@ def from_xml(text_or_path):
         elif kind == 'CustomExternalForce':
             if _nonempty(e, 'PerParticleParameters'):
                 raise NotImplementedError('CustomExternalForce with per-particle parameters')
-            f = CustomExternalForce(e.get('energy'))          # raises for anything but the harmonic-oscillator expression
+            f = CustomExternalForce(e.get('energy'))
+            if not f.is_harmonic_oscillator():                # (other expressions run on the engine but are not read from a document)
+                raise NotImplementedError('only the testsystems.HarmonicOscillator expression is supported')
             for g in _children(e, 'GlobalParameters', 'Parameter'):
                 f.addGlobalParameter(g.get('name'), float(g.get('default')))
             for b in _children(e, 'Particles', 'Particle'):

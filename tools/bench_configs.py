@@ -79,6 +79,61 @@ def main():
         ss = states.SamplerState(hg.positions, box_vectors=hg.system.getDefaultPeriodicBoxVectors())
         s.create(ths, [ss] * 8)
         run('4rs (1-GPU share, restrained): HostGuestExplicit + CB7/B2 HarmonicRestraintForce, 8 replicas x 64 states, g-BAOAB 2 fs x 500', s, 3)
+    if '4cb' in which:
+        # config 4's share with one custom bond force (custom_expr.py, csrc/custom_terms.hip): 30 bonds between the guest's atoms and CB7
+        # heavy atoms, K = 0.2 kcal/mol/A^2, the global lambda_bonds rising 0 -> 1 along the coupled half and 1 where the guest is decoupled
+        from openmmtools_amd.system import CustomBondForce
+
+        class BondState(states.GlobalParameterState):
+            lambda_bonds = states.GlobalParameterState.GlobalParameter('lambda_bonds', standard_value=1.0)
+        hg = testsystems.HostGuestExplicit()
+        lam_e = np.concatenate([np.linspace(1.0, 0.0, 32), np.zeros(32)])
+        lam_s = np.concatenate([np.ones(32), np.linspace(1.0, 0.0, 32)])
+        lam_b = np.concatenate([np.linspace(0.0, 1.0, 32), np.ones(32)])
+        asys = alchemy.AbsoluteAlchemicalFactory().create_alchemical_system(hg.system, alchemy.AlchemicalRegion(alchemical_atoms=range(126, 156)))
+        heavy = [i for i in range(126) if hg.system.getParticleMass(i) > 1.5]
+        f = CustomBondForce('lambda_bonds*0.5*K*r^2')
+        f.addGlobalParameter('lambda_bonds', 1.0)
+        f.addPerBondParameter('K')
+        for k, g in enumerate(range(126, 156)):
+            f.addBond(heavy[(3 * k) % len(heavy)], g, [0.2 * 4.184 * 100.0 / 30.0])
+        asys.addForce(f)
+        ths = [states.CompoundThermodynamicState(states.ThermodynamicState(asys, 300.0),
+                                                 [states.AlchemicalState(lambda_sterics=ls, lambda_electrostatics=le), BondState(lambda_bonds=lb)])
+               for le, ls, lb in zip(lam_e, lam_s, lam_b)]
+        s = SAMSSampler(mcmc_moves=move(2.0, 'V R R O R R V'), number_of_iterations=10 ** 9, engine=HipEngine(), seed=1)
+        ss = states.SamplerState(hg.positions, box_vectors=hg.system.getDefaultPeriodicBoxVectors())
+        s.create(ths, [ss] * 8)
+        run('4cb (1-GPU share, custom bond force): HostGuestExplicit + a 30-bond CustomBondForce, 8 replicas x 64 states, g-BAOAB 2 fs x 500', s, 3)
+    if '4cr' in which:
+        # config 4's share with EVERY harmonic bond, harmonic angle and periodic torsion of the System moved to custom forces with the
+        # same formulas (custom_expr.py): what the expression machine costs at a force field's size, against the built-in listed terms of '4'
+        from openmmtools_amd.system import (CustomBondForce, CustomAngleForce, CustomTorsionForce, HarmonicBondForce, HarmonicAngleForce,
+                                            PeriodicTorsionForce)
+        hg = testsystems.HostGuestExplicit()
+        lam_e = np.concatenate([np.linspace(1.0, 0.0, 32), np.zeros(32)])
+        lam_s = np.concatenate([np.ones(32), np.linspace(1.0, 0.0, 32)])
+        b = CustomBondForce('0.5*k*(r-r0)^2'); b.addPerBondParameter('r0'); b.addPerBondParameter('k')
+        a = CustomAngleForce('0.5*k*(theta-theta0)^2'); a.addPerAngleParameter('theta0'); a.addPerAngleParameter('k')
+        t = CustomTorsionForce('k*(1+cos(n*theta-phase))')
+        for name in ('n', 'phase', 'k'):
+            t.addPerTorsionParameter(name)
+        for f in hg.system.getForces():
+            if isinstance(f, HarmonicBondForce):
+                for q in f.bonds: b.addBond(q[0], q[1], q[2:])
+            elif isinstance(f, HarmonicAngleForce):
+                for q in f.angles: a.addAngle(q[0], q[1], q[2], q[3:])
+            elif isinstance(f, PeriodicTorsionForce):
+                for q in f.torsions: t.addTorsion(q[0], q[1], q[2], q[3], q[4:])
+        hg.system.forces = [f for f in hg.system.forces if not isinstance(f, (HarmonicBondForce, HarmonicAngleForce, PeriodicTorsionForce))]
+        for f in (b, a, t):
+            hg.system.addForce(f)
+        ths = alchemical_states(hg.system, range(126, 156), lam_e, lam_s)
+        s = SAMSSampler(mcmc_moves=move(2.0, 'V R R O R R V'), number_of_iterations=10 ** 9, engine=HipEngine(), seed=1)
+        ss = states.SamplerState(hg.positions, box_vectors=hg.system.getDefaultPeriodicBoxVectors())
+        s.create(ths, [ss] * 8)
+        run('4cr (1-GPU share, %d custom bonds + %d custom angles + %d custom torsions instead of the built-in ones): HostGuestExplicit, '
+            '8 replicas x 64 states, g-BAOAB 2 fs x 500' % (b.getNumBonds(), a.getNumAngles(), t.getNumTorsions()), s, 3)
     for tag, kw in (('4r', dict()), ('4d', dict(alchemical_pme_treatment='direct-space'))):
         if tag not in which:
             continue
