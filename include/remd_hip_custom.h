@@ -1,5 +1,5 @@
 /*
- * remd_hip_custom.h — GPU-only extension of the C ABI in remd_hip.h: custom bond, angle, torsion and external forces.
+ * remd_hip_custom.h — GPU-only extension of the C ABI in remd_hip.h: custom bond, angle, torsion, external and compound-bond forces.
  *
  * OpenMM's CustomBondForce, CustomAngleForce, CustomTorsionForce and CustomExternalForce: an energy expression of r (bond), theta
  * (angle, torsion) or x, y, z (external), of per-term parameters and of global parameters, evaluated per term.  The host compiles
@@ -13,6 +13,15 @@
  * multiplications).  Every other opcode takes its arguments from the stack, first argument deepest, and pushes one result.
  * Piecewise functions (abs, min, max, select) differentiate as the branch taken; step, delta, floor and ceil have derivative zero.
  *
+ * Compound-bond forces (REMD_CUSTOM_COMPOUND, OpenMM's CustomCompoundBondForce): every term joins n_particles particles (1 ...
+ * REMD_CUSTOM_MAX_PARTICLES), the variables are their coordinates x1 y1 z1 ... (REMD_CX_VAR operand 3 * particle + component, particle
+ * zero-based), and REMD_CX_DISTANCE / REMD_CX_ANGLE / REMD_CX_DIHEDRAL push the distance, angle (0 ... pi) or dihedral (-pi ... pi, the
+ * sign convention of PeriodicTorsionForce) of the particle slots packed into the operand, 4 bits each, first argument lowest; they
+ * take nothing from the stack and are legal only in such a program.  pointdistance is REMD_CX_PERIODICDISTANCE; it and the differences
+ * between particles are minimum images only where the force is periodic.  The device runs the program once per particle slot, each
+ * pass carrying the gradient with respect to that particle (csrc/custom_compound.hip).  Not provided: tabulated functions,
+ * pointangle, pointdihedral, CustomCentroidBondForce beyond the restraint forms (remd_hip_restraints.h).
+ *
  * Global parameters belong to the handle: every force's program addresses the same n_globals columns, and every state carries one
  * value per column (remd_set_custom_globals).  A term acts in every force evaluation (MD steps, energies, the barostat,
  * minimisation); the u_kl rows get beta_l (E_r(g_l) - E_r(g_own(r))) for every state l, E_r(g) the sum of all custom terms at
@@ -20,7 +29,7 @@
  *
  * Limits (a descriptor beyond them is refused): REMD_CUSTOM_MAX_PROGRAM instructions per force, REMD_CUSTOM_MAX_STACK stack slots,
  * REMD_CUSTOM_MAX_PARAMS parameters per term, REMD_CUSTOM_MAX_GLOBALS global columns per handle, REMD_CUSTOM_MAX_FORCES forces
- * per handle.
+ * per handle (of all kinds together), REMD_CUSTOM_MAX_PARTICLES particles per compound bond.
  *
  * These entry points are declared here and not in remd_hip.h because the CPU port of the ABI does not provide them: a host binds
  * them only where the loaded library exports them.  Conventions as in remd_hip.h.
@@ -38,12 +47,14 @@ extern "C" {
 #define REMD_CUSTOM_ANGLE    1     /* atoms [n][3], variable theta in [0, pi]                                               */
 #define REMD_CUSTOM_TORSION  2     /* atoms [n][4], variable theta in (-pi, pi], the sign convention of PeriodicTorsionForce */
 #define REMD_CUSTOM_EXTERNAL 3     /* atoms [n][1], variables x, y, z                                                       */
+#define REMD_CUSTOM_COMPOUND 4     /* atoms [n][n_particles], variables x1, y1, z1, ..., and functions of the particles     */
 
 #define REMD_CUSTOM_MAX_PROGRAM 256
 #define REMD_CUSTOM_MAX_STACK   16
 #define REMD_CUSTOM_MAX_PARAMS  16
 #define REMD_CUSTOM_MAX_GLOBALS 16
 #define REMD_CUSTOM_MAX_FORCES  8
+#define REMD_CUSTOM_MAX_PARTICLES 8
 
 /* opcodes */
 #define REMD_CX_CONST   0      /* push consts[operand]                                                                      */
@@ -81,12 +92,15 @@ extern "C" {
 #define REMD_CX_FLOOR   32
 #define REMD_CX_CEIL    33
 #define REMD_CX_PERIODICDISTANCE 34   /* (x1, y1, z1, x2, y2, z2): minimum-image distance under the replica's own box        */
-#define REMD_CX_N_OPCODES 35
+#define REMD_CX_DISTANCE 35     /* distance of the particle slots operand & 15, (operand >> 4) & 15; pushes, pops nothing    */
+#define REMD_CX_ANGLE    36     /* angle at the middle one of three particle slots, 4 bits each                              */
+#define REMD_CX_DIHEDRAL 37     /* dihedral of four particle slots, 4 bits each                                              */
+#define REMD_CX_N_OPCODES 38
 
 typedef struct remd_custom_force_desc {
     int32_t kind;                  /* REMD_CUSTOM_*                                                                        */
     int32_t n_terms;               /* bonds / angles / torsions / particles                                                */
-    const int32_t* atoms;          /* [n_terms][2 | 3 | 4 | 1]                                                             */
+    const int32_t* atoms;          /* [n_terms][2 | 3 | 4 | 1 | n_particles]                                               */
     int32_t n_params;              /* parameters per term                                                                  */
     const double* params;          /* [n_terms][n_params]                                                                  */
     int32_t n_program;             /* instructions                                                                         */
@@ -98,6 +112,7 @@ typedef struct remd_custom_force_desc {
     const double* global_defaults; /* [n_globals]: every state's values until remd_set_custom_globals                      */
     int32_t periodic;              /* 1: differences between atoms are minimum images under the replica's own box          */
     int32_t force_group;           /* Force.getForceGroup() (multiple-time-step splittings)                                */
+    int32_t n_particles;           /* REMD_CUSTOM_COMPOUND: particles per bond, 1 ... REMD_CUSTOM_MAX_PARTICLES; else 0    */
 } remd_custom_force_desc;
 
 /* the custom forces of the system; call after remd_set_system (which forgets them).  n = 0: none.  Every custom force of a handle
@@ -106,7 +121,7 @@ int  remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, in
 /* values[K][n_globals]: every state's value of each global column; K as in remd_set_states (call after it: the terms refuse to act
    on globals that belong to an older set of states)                                                                              */
 int  remd_set_custom_globals(remd_handle h, const double* values);
-/* out[R_local][n]: each custom force's energy (kJ/mol) at the local replicas' current positions and own states                   */
+/* out[R_local][n]: each custom force's energy, in the order of the descriptors whatever their kinds (kJ/mol) at the local replicas' current positions and own states                   */
 int  remd_get_custom_energies(remd_handle h, double* out);
 
 #ifdef __cplusplus

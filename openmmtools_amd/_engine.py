@@ -70,11 +70,12 @@ class RemdRestraintDesc(C.Structure):
 
 
 class RemdCustomForceDesc(C.Structure):
-    """remd_custom_force_desc of include/remd_hip_custom.h (custom bond / angle / torsion / external forces, custom_expr.py)."""
+    """remd_custom_force_desc of include/remd_hip_custom.h (custom bond / angle / torsion / external / compound-bond forces,
+    custom_expr.py)."""
     _fields_ = [('kind', C.c_int32), ('n_terms', C.c_int32), ('atoms', c_int32_p), ('n_params', C.c_int32), ('params', c_double_p),
                 ('n_program', C.c_int32), ('program', c_int32_p), ('n_consts', C.c_int32), ('consts', c_double_p),
                 ('stack_depth', C.c_int32), ('n_globals', C.c_int32), ('global_defaults', c_double_p),
-                ('periodic', C.c_int32), ('force_group', C.c_int32)]
+                ('periodic', C.c_int32), ('force_group', C.c_int32), ('n_particles', C.c_int32)]
 
 
 class RemdGbModelDesc(C.Structure):
@@ -414,7 +415,7 @@ class HipEngine:
 
     def _custom_entry(self, name):
         if not hasattr(self.lib, name):
-            raise NotImplementedError('%s: this build of the engine library has no custom bond / angle / torsion / external forces '
+            raise NotImplementedError('%s: this build of the engine library has no custom bond / angle / torsion / external forces and no compound-bond forces '
                                       '(include/remd_hip_custom.h is GPU-only)' % name)
         return getattr(self.lib, name)
 
@@ -426,13 +427,14 @@ class HipEngine:
         for k, t in enumerate(terms):
             atoms = np.ascontiguousarray(t['atoms'], dtype=np.int32)
             params = np.ascontiguousarray(t['params'], dtype=np.float64).reshape(len(atoms), -1)
+            n_particles = int(t.get('n_particles', 0))               # a compound-bond force: atoms [n][n_particles]
             program = np.ascontiguousarray(t['program'], dtype=np.int32).reshape(-1, 2)
             consts = np.ascontiguousarray(t['consts'], dtype=np.float64)
             defaults = np.ascontiguousarray(t['global_defaults'], dtype=np.float64)
             keep += [atoms, params, program, consts, defaults]
             arr[k] = RemdCustomForceDesc(int(t['kind']), len(atoms), _ip(atoms), params.shape[1], _dp(params), len(program), _ip(program),
                                          len(consts), _dp(consts), int(t['stack_depth']), len(defaults), _dp(defaults),
-                                         int(t['periodic']), int(t['force_group']))
+                                         int(t['periodic']), int(t['force_group']), n_particles)
         self._check(fn(self.h, arr, len(terms)), 'remd_set_custom_terms')
         self.n_custom = len(terms)
         self.n_custom_globals = len(terms[0]['global_defaults']) if terms else 0

@@ -22,161 +22,22 @@
 // Energies: a wavefront sums its terms by a xor-shuffle tree, the partial goes to [R][wavefronts], and a second one-wavefront launch
 // per replica adds each force's partials in a fixed order -> [R][n_forces] and the replica's energy partial (the restraints' slot,
 // the last one: added behind the restraint kernel on the same stream).  No atomics touch an energy.
+//
+// The machine itself (cst_eval) lives in custom_machine.h: custom_compound.hip runs the same one for CustomCompoundBondForce, whose
+// wavefronts follow the ones of this file's four kinds in the padded term space and share the energy and u_kl reductions below.
 #include "remd_internal.h"
 #include "listed_terms.h"
-#include "../../include/remd_hip_custom.h"
+#include "custom_machine.h"
 
-namespace {
-
-struct cst_force {
-    int kind, periodic, n_terms, n_params;
-    int slot0, npad;             // first slot in the padded term space of the launch / slots of this force (a multiple of 64)
-    int par0;                    // offset of its parameters [n_params][npad]
-    int prog0, n_prog, const0;   // its program and constants in the handle's tables
-};
-
-}  // namespace
-
-struct cst_tables {
-    int nf = 0, ng = 0, K = 0, total_pad = 0; long long glob_version = -1;   // (glob belongs to the states of that remd_set_states)
-    bool uniform = true;                                                       // every state carries the same globals: no u_kl share
-    std::vector<cst_force> F; std::vector<int> wave_force, atoms; std::vector<double> par, consts, glob, defaults; std::vector<int2> prog;
-    dev_array<cst_force> d_F; dev_array<int> d_wave_force; dev_array<int> d_atoms;      // atoms [4][total_pad]
-    dev_array<double> d_par; dev_array<double> d_consts; dev_array<double> d_glob; dev_array<int2> d_prog;
-    dev_array<double> d_E;             // [R][nf]
-    dev_array<double> d_Ewave;         // [R][total_pad / 64]
-    dev_array<double> d_D;             // [R][K][total_pad / 64] u_kl partials
-};
 void remd_table_deleter::operator()(cst_tables* t) const { delete t; }
 
 namespace {
-
-struct cx { double v, a, b, c; };       // a value and its partials
-typedef double cst_slot[4][64];
-
-__device__ __forceinline__ cx cx_ld(const cst_slot* S, int sp, int lane) { return cx{S[sp][0][lane], S[sp][1][lane], S[sp][2][lane], S[sp][3][lane]}; }
-__device__ __forceinline__ void cx_st(cst_slot* S, int sp, int lane, const cx& x) { S[sp][0][lane] = x.v; S[sp][1][lane] = x.a; S[sp][2][lane] = x.b; S[sp][3][lane] = x.c; }
-__device__ __forceinline__ cx cx_chain(double v, double k, const cx& x) { return cx{v, k * x.a, k * x.b, k * x.c}; }
-
-__device__ __forceinline__ double cst_image(double d, double L) { return L > 0.0 ? d - L * rint(d / L) : d; }
-
-// a ^ n by multiplications (n >= 0)
-__device__ __forceinline__ double cst_ipow(double a, int n)
-{
-    double r = 1.0;
-    for (; n > 0; n >>= 1) { if (n & 1) r *= a; a *= a; }
-    return r;
-}
-
-// the program of force f at term t (lane's own) under the globals g (wave-uniform); the result's partials are dE/dvariable
-__device__ __forceinline__ cx cst_eval(const cst_force& f, const int2* __restrict__ prog, const double* __restrict__ consts,
-                                       const double* __restrict__ par, int t, const double* __restrict__ g, double x0, double x1,
-                                       double x2, double Lx, double Ly, double Lz, cst_slot* S, int lane)
-{
-    int sp = 0;
-    for (int pc = 0; pc < f.n_prog; ++pc) {
-        const int2 ins = prog[f.prog0 + pc];
-        const int op = ins.x, arg = ins.y;
-        switch (op) {
-        case REMD_CX_CONST:  cx_st(S, sp++, lane, cx{consts[f.const0 + arg], 0.0, 0.0, 0.0}); break;
-        // (variable `arg` has the unit partial `arg`; scalars picked by value: a pick among structs becomes a pick of addresses in scratch)
-        case REMD_CX_VAR:    cx_st(S, sp++, lane, cx{arg == 0 ? x0 : arg == 1 ? x1 : x2, arg == 0 ? 1.0 : 0.0, arg == 1 ? 1.0 : 0.0, arg == 2 ? 1.0 : 0.0}); break;
-        case REMD_CX_PARAM:  cx_st(S, sp++, lane, cx{par[f.par0 + (size_t)arg * f.npad + t], 0.0, 0.0, 0.0}); break;
-        case REMD_CX_GLOBAL: cx_st(S, sp++, lane, cx{g[arg], 0.0, 0.0, 0.0}); break;
-        case REMD_CX_ADD: case REMD_CX_SUB: case REMD_CX_MUL: case REMD_CX_DIV: case REMD_CX_POW: case REMD_CX_ATAN2:
-        case REMD_CX_MIN: case REMD_CX_MAX: {
-            const cx x = cx_ld(S, sp - 2, lane), y = cx_ld(S, sp - 1, lane);
-            cx z;
-            if (op == REMD_CX_ADD) z = cx{x.v + y.v, x.a + y.a, x.b + y.b, x.c + y.c};
-            else if (op == REMD_CX_SUB) z = cx{x.v - y.v, x.a - y.a, x.b - y.b, x.c - y.c};
-            else if (op == REMD_CX_MUL) z = cx{x.v * y.v, x.a * y.v + x.v * y.a, x.b * y.v + x.v * y.b, x.c * y.v + x.v * y.c};
-            else if (op == REMD_CX_DIV) {
-                const double q = x.v / y.v, iy = 1.0 / y.v;
-                z = cx{q, (x.a - q * y.a) * iy, (x.b - q * y.b) * iy, (x.c - q * y.c) * iy};
-            } else if (op == REMD_CX_POW) {
-                // d(x^y) = y x^(y-1) dx + x^y ln x dy; the second term only where the exponent varies (ln of a base <= 0 otherwise
-                // poisons a constant exponent's zero partial)
-                const double p = pow(x.v, y.v), kx = y.v * pow(x.v, y.v - 1.0);
-                const bool yvar = y.a != 0.0 || y.b != 0.0 || y.c != 0.0;
-                const double ky = yvar ? p * log(x.v) : 0.0;
-                z = cx{p, kx * x.a + ky * y.a, kx * x.b + ky * y.b, kx * x.c + ky * y.c};
-            } else if (op == REMD_CX_ATAN2) {
-                const double n2 = 1.0 / (x.v * x.v + y.v * y.v);          // atan2(x, y): x the sine-like argument
-                z = cx{atan2(x.v, y.v), (y.v * x.a - x.v * y.a) * n2, (y.v * x.b - x.v * y.b) * n2, (y.v * x.c - x.v * y.c) * n2};
-            } else if (op == REMD_CX_MIN) z = x.v < y.v ? x : y;
-            else z = x.v > y.v ? x : y;
-            cx_st(S, sp - 2, lane, z); --sp;
-        } break;
-        case REMD_CX_SELECT: {
-            const cx x = cx_ld(S, sp - 3, lane), y = cx_ld(S, sp - 2, lane), z = cx_ld(S, sp - 1, lane);
-            cx_st(S, sp - 3, lane, x.v != 0.0 ? y : z); sp -= 2;
-        } break;
-        case REMD_CX_PERIODICDISTANCE: {
-            const cx x1 = cx_ld(S, sp - 6, lane), y1 = cx_ld(S, sp - 5, lane), z1 = cx_ld(S, sp - 4, lane);
-            const cx x2 = cx_ld(S, sp - 3, lane), y2 = cx_ld(S, sp - 2, lane), z2 = cx_ld(S, sp - 1, lane);
-            const double dx = cst_image(x2.v - x1.v, Lx), dy = cst_image(y2.v - y1.v, Ly), dz = cst_image(z2.v - z1.v, Lz);
-            const double d = sqrt(dx * dx + dy * dy + dz * dz), id = d > 0.0 ? 1.0 / d : 0.0;
-            const double ux = dx * id, uy = dy * id, uz = dz * id;
-            cx_st(S, sp - 6, lane, cx{d, ux * (x2.a - x1.a) + uy * (y2.a - y1.a) + uz * (z2.a - z1.a),
-                                         ux * (x2.b - x1.b) + uy * (y2.b - y1.b) + uz * (z2.b - z1.b),
-                                         ux * (x2.c - x1.c) + uy * (y2.c - y1.c) + uz * (z2.c - z1.c)});
-            sp -= 5;
-        } break;
-        default: {                                        // one argument
-            const cx x = cx_ld(S, sp - 1, lane);
-            double v = 0.0, k = 0.0;
-            switch (op) {
-            case REMD_CX_NEG:  v = -x.v; k = -1.0; break;
-            case REMD_CX_POWI: {
-                const int m = arg < 0 ? -arg : arg;
-                const double pm1 = m > 0 ? cst_ipow(x.v, m - 1) : 0.0, pm = m > 0 ? pm1 * x.v : 1.0;
-                if (arg >= 0) { v = pm; k = (double)m * pm1; }
-                else { v = 1.0 / pm; k = -(double)m * v / x.v; }
-            } break;
-            case REMD_CX_SQRT: v = sqrt(x.v); k = v > 0.0 ? 0.5 / v : 0.0; break;
-            case REMD_CX_EXP:  v = exp(x.v); k = v; break;
-            case REMD_CX_LOG:  v = log(x.v); k = 1.0 / x.v; break;
-            case REMD_CX_SIN:  v = sin(x.v); k = cos(x.v); break;
-            case REMD_CX_COS:  v = cos(x.v); k = -sin(x.v); break;
-            case REMD_CX_TAN:  v = tan(x.v); k = 1.0 + v * v; break;
-            case REMD_CX_ASIN: v = asin(x.v); k = 1.0 / sqrt(1.0 - x.v * x.v); break;
-            case REMD_CX_ACOS: v = acos(x.v); k = -1.0 / sqrt(1.0 - x.v * x.v); break;
-            case REMD_CX_ATAN: v = atan(x.v); k = 1.0 / (1.0 + x.v * x.v); break;
-            case REMD_CX_SINH: v = sinh(x.v); k = cosh(x.v); break;
-            case REMD_CX_COSH: v = cosh(x.v); k = sinh(x.v); break;
-            case REMD_CX_TANH: v = tanh(x.v); k = 1.0 - v * v; break;
-            case REMD_CX_ERF:  v = erf(x.v); k = 1.1283791670955126 * exp(-x.v * x.v); break;
-            case REMD_CX_ERFC: v = erfc(x.v); k = -1.1283791670955126 * exp(-x.v * x.v); break;
-            case REMD_CX_ABS:  v = fabs(x.v); k = x.v < 0.0 ? -1.0 : 1.0; break;
-            case REMD_CX_STEP: v = x.v >= 0.0 ? 1.0 : 0.0; break;
-            case REMD_CX_DELTA: v = x.v == 0.0 ? 1.0 : 0.0; break;
-            case REMD_CX_FLOOR: v = floor(x.v); break;
-            case REMD_CX_CEIL: v = ceil(x.v); break;
-            default: break;
-            }
-            cx_st(S, sp - 1, lane, cx_chain(v, k, x));
-        } break;
-        }
-    }
-    return cx_ld(S, 0, lane);
-}
 
 struct cst_geom {
     int a0, a1, a2, a3;
     double x0, x1, x2;                // the force's variables: r / theta / x, then y, z of an external force
     double3 g0, g1, g2, g3;           // gradient of the ONE variable of a bond / angle / torsion with respect to each atom
 };
-
-__device__ __forceinline__ double3 d3(double x, double y, double z) { return make_double3(x, y, z); }
-__device__ __forceinline__ double3 d3sub(const float4& a, const float4& b) { return d3((double)a.x - (double)b.x, (double)a.y - (double)b.y, (double)a.z - (double)b.z); }
-__device__ __forceinline__ double d3dot(double3 a, double3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ double3 d3crs(double3 a, double3 b) { return d3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-__device__ __forceinline__ double3 d3scl(double3 a, double s) { return d3(a.x * s, a.y * s, a.z * s); }
-__device__ __forceinline__ double3 d3add(double3 a, double3 b) { return d3(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ double3 d3img(double3 d, bool pbc, double Lx, double Ly, double Lz)
-{
-    return pbc ? d3(cst_image(d.x, Lx), cst_image(d.y, Ly), cst_image(d.z, Lz)) : d;
-}
 
 // the variables of slot s of force f: the formulas of listed_terms.h (listed_bond / listed_angle / listed_torsion) in f64
 __device__ __forceinline__ void cst_geometry(const cst_force& f, const int* __restrict__ atoms, int total_pad, int s,
@@ -223,16 +84,10 @@ __device__ __forceinline__ void cst_geometry(const cst_force& f, const int* __re
     }
 }
 
-__device__ __forceinline__ double cst_wave_sum(double v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// grid (wavefronts of the padded term space, R), 64 threads
+// grid (wavefronts of the four kinds' part of the padded term space, R), 64 threads; `waves` counts those of the whole space
 template <bool ENERGY>
 __global__ __launch_bounds__(64)
-void custom_terms_kernel(int total_pad, const cst_force* __restrict__ F, const int* __restrict__ wave_force, const int* __restrict__ atoms,
+void custom_terms_kernel(int total_pad, int waves, const cst_force* __restrict__ F, const int* __restrict__ wave_force, const int* __restrict__ atoms,
                          const double* __restrict__ par, const int2* __restrict__ prog, const double* __restrict__ consts,
                          const double* __restrict__ glob /*[K][ng]*/, int ng, const int64_t* __restrict__ labels, int r_begin, int Npad,
                          const float4* __restrict__ pos, const float* __restrict__ box, long long* __restrict__ force,
@@ -247,7 +102,7 @@ void custom_terms_kernel(int total_pad, const cst_force* __restrict__ F, const i
     const double* g = glob + (size_t)labels[r_begin + r] * ng;
     cst_geom o;
     cst_geometry(f, atoms, total_pad, s, P, Lx, Ly, Lz, o);
-    const cx e = cst_eval(f, prog, consts, par, t, g, o.x0, o.x1, o.x2, Lx, Ly, Lz, S, lane);
+    const cx e = cst_eval<false>(f, prog, consts, par, t, g, o.x0, o.x1, o.x2, Lx, Ly, Lz, S, lane);
     const bool active = t < f.n_terms;
     if (active) {
         long long* Fr = force + (size_t)r * 3 * Npad;
@@ -262,7 +117,7 @@ void custom_terms_kernel(int total_pad, const cst_force* __restrict__ F, const i
     }
     if (ENERGY) {
         const double ew = cst_wave_sum(active ? e.v : 0.0);
-        if (lane == 0) Ewave[(size_t)r * gridDim.x + w] = ew;
+        if (lane == 0) Ewave[(size_t)r * waves + w] = ew;
     }
 }
 
@@ -286,7 +141,7 @@ void custom_reduce_kernel(int nf, const cst_force* __restrict__ F, int waves, co
 
 // u_kl partials, grid (wavefronts, R): D[r][l][w] = sum over the wavefront's terms of e(g_l) - e(g_own), the difference formed per term
 __global__ __launch_bounds__(64)
-void custom_ukl_kernel(int total_pad, const cst_force* __restrict__ F, const int* __restrict__ wave_force, const int* __restrict__ atoms,
+void custom_ukl_kernel(int total_pad, int waves, const cst_force* __restrict__ F, const int* __restrict__ wave_force, const int* __restrict__ atoms,
                        const double* __restrict__ par, const int2* __restrict__ prog, const double* __restrict__ consts,
                        const double* __restrict__ glob, int ng, int K, const int64_t* __restrict__ labels, int r_begin, int Npad,
                        const float4* __restrict__ pos, const float* __restrict__ box, double* __restrict__ D)
@@ -308,12 +163,12 @@ void custom_ukl_kernel(int total_pad, const cst_force* __restrict__ F, const int
         for (int i = 0; i < ng && same; ++i) same = g[i] == g_own[i];
         double d = 0.0;
         if (!same) {
-            const double e = cst_eval(f, prog, consts, par, t, g, o.x0, o.x1, o.x2, Lx, Ly, Lz, S, lane).v;
+            const double e = cst_eval<false>(f, prog, consts, par, t, g, o.x0, o.x1, o.x2, Lx, Ly, Lz, S, lane).v;
             if (l < 0) e_own = e; else d = active ? e - e_own : 0.0;
         }
         if (l >= 0) {
             d = cst_wave_sum(d);
-            if (lane == 0) D[((size_t)r * K + l) * gridDim.x + w] = d;
+            if (lane == 0) D[((size_t)r * K + l) * waves + w] = d;
         }
     }
 }
@@ -359,6 +214,7 @@ bool globals_uniform(const cst_tables& t)
 // what a program may do is settled here, once: the kernels index the stack, the constants, the parameters and the globals unchecked
 const char* check_program(const remd_custom_force_desc& d, int n_vars)
 {
+    const bool compound = d.kind == REMD_CUSTOM_COMPOUND;
     if (d.n_program <= 0 || !d.program) return "an empty program";
     if (d.n_program > REMD_CUSTOM_MAX_PROGRAM) return "a program over REMD_CUSTOM_MAX_PROGRAM instructions";
     int sp = 0, top = 0;
@@ -374,6 +230,14 @@ const char* check_program(const remd_custom_force_desc& d, int n_vars)
         case REMD_CX_MIN: case REMD_CX_MAX: pops = 2; break;
         case REMD_CX_SELECT: pops = 3; break;
         case REMD_CX_PERIODICDISTANCE: pops = 6; break;
+        case REMD_CX_DISTANCE: case REMD_CX_ANGLE: case REMD_CX_DIHEDRAL: {
+            // the zero-based particle slots in 4-bit fields, first argument lowest; nothing above them
+            if (!compound) return "a function of particles outside a compound-bond force";
+            const int n_args = op - REMD_CX_DISTANCE + 2;
+            if (arg < 0 || (arg >> (4 * n_args)) != 0) return "a particle slot out of range";
+            for (int k = 0; k < n_args; ++k) if (((arg >> (4 * k)) & 15) >= d.n_particles) return "a particle slot out of range";
+            pops = 0;
+        } break;
         case REMD_CX_POWI: if (arg < -64 || arg > 64) return "an integer power beyond +-64"; break;
         default: if (op < 0 || op >= REMD_CX_N_OPCODES) return "an unknown opcode"; break;
         }
@@ -401,7 +265,7 @@ int remd_custom_clone(remd_ctx* parent, remd_ctx* child)
     if (!t || parent->n_custom == 0) return 0;
     child->cst.reset(new cst_tables());
     cst_tables& c = *child->cst;
-    c.nf = t->nf; c.ng = t->ng; c.K = t->K; c.total_pad = t->total_pad; c.uniform = t->uniform;
+    c.nf = t->nf; c.ng = t->ng; c.K = t->K; c.total_pad = t->total_pad; c.waves_simple = t->waves_simple; c.uniform = t->uniform;
     c.glob_version = t->glob_version == parent->states_version ? child->states_version : -1;
     c.F = t->F; c.wave_force = t->wave_force; c.atoms = t->atoms; c.par = t->par; c.consts = t->consts; c.glob = t->glob;
     c.defaults = t->defaults; c.prog = t->prog;
@@ -424,13 +288,19 @@ int remd_custom_forces(remd_ctx* h, bool with_energy, int ep_slot, hipStream_t s
     int rc = ensure_buffers(h, t); if (rc) return rc;
     const int waves = t.total_pad / 64;
     remd_prof_scope ps(h, "custom_terms", st);
-    if (with_energy) {
-        hipLaunchKernelGGL(custom_terms_kernel<true>, dim3(waves, h->R), dim3(64), 0, st, t.total_pad, t.d_F, t.d_wave_force, t.d_atoms, t.d_par,
-                           t.d_prog, t.d_consts, t.d_glob, t.ng, h->d_labels, h->r_begin, h->Npad, h->d_pos, h->d_box, h->d_force, t.d_Ewave);
+    if (t.waves_simple > 0) {
+        if (with_energy)
+            hipLaunchKernelGGL(custom_terms_kernel<true>, dim3(t.waves_simple, h->R), dim3(64), 0, st, t.total_pad, waves, t.d_F,
+                               t.d_wave_force, t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, h->d_labels, h->r_begin, h->Npad, h->d_pos,
+                               h->d_box, h->d_force, t.d_Ewave);
+        else
+            hipLaunchKernelGGL(custom_terms_kernel<false>, dim3(t.waves_simple, h->R), dim3(64), 0, st, t.total_pad, waves, t.d_F,
+                               t.d_wave_force, t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, h->d_labels, h->r_begin, h->Npad, h->d_pos,
+                               h->d_box, h->d_force, t.d_Ewave);
+    }
+    if (waves > t.waves_simple) remd_custom_compound_forces(h, t, with_energy, st);       // (custom_compound.hip: the wavefronts behind)
+    if (with_energy)
         hipLaunchKernelGGL(custom_reduce_kernel, dim3(h->R), dim3(64), 0, st, t.nf, t.d_F, waves, t.d_Ewave, t.d_E, h->d_epart, h->n_epart, ep_slot);
-    } else
-        hipLaunchKernelGGL(custom_terms_kernel<false>, dim3(waves, h->R), dim3(64), 0, st, t.total_pad, t.d_F, t.d_wave_force, t.d_atoms, t.d_par,
-                           t.d_prog, t.d_consts, t.d_glob, t.ng, h->d_labels, h->r_begin, h->Npad, h->d_pos, h->d_box, h->d_force, t.d_Ewave);
     REMD_CHECK(h, hipGetLastError());
     return 0;
 }
@@ -448,8 +318,10 @@ int remd_custom_ukl(remd_ctx* h, double* d_rows)
     const size_t nD = (size_t)h->R * h->K * waves;
     if (t.d_D.size() != nD) REMD_TRY(t.d_D.alloc(h, nD));
     remd_prof_scope ps(h, "custom_ukl");
-    hipLaunchKernelGGL(custom_ukl_kernel, dim3(waves, h->R), dim3(64), 0, h->stream, t.total_pad, t.d_F, t.d_wave_force, t.d_atoms, t.d_par,
-                       t.d_prog, t.d_consts, t.d_glob, t.ng, h->K, h->d_labels, h->r_begin, h->Npad, h->d_pos, h->d_box, t.d_D);
+    if (t.waves_simple > 0)
+        hipLaunchKernelGGL(custom_ukl_kernel, dim3(t.waves_simple, h->R), dim3(64), 0, h->stream, t.total_pad, waves, t.d_F, t.d_wave_force,
+                           t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, h->K, h->d_labels, h->r_begin, h->Npad, h->d_pos, h->d_box, t.d_D);
+    if (waves > t.waves_simple) remd_custom_compound_ukl(h, t);
     hipLaunchKernelGGL(custom_ukl_reduce_kernel, dim3(h->K, h->R), dim3(64), 0, h->stream, h->K, waves, t.d_D, h->d_beta, d_rows);
     REMD_CHECK(h, hipGetLastError());
     return 0;
@@ -471,11 +343,15 @@ int remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, int
     if (t.ng < 0 || t.ng > REMD_CUSTOM_MAX_GLOBALS) return remd_fail(h, -1, "remd_set_custom_terms: more than REMD_CUSTOM_MAX_GLOBALS global parameters");
     if (t.ng > 0 && !desc[0].global_defaults) return remd_fail(h, -1, "remd_set_custom_terms: global_defaults missing");
     t.defaults.assign(desc[0].global_defaults, desc[0].global_defaults + t.ng);
-    static const int width[4] = {2, 3, 4, 1}, n_vars[4] = {1, 1, 1, 3};
+    static const int width4[4] = {2, 3, 4, 1}, n_vars4[4] = {1, 1, 1, 3};
     for (int i = 0; i < n; ++i) {
         const remd_custom_force_desc& d = desc[i];
         const std::string who = "remd_set_custom_terms: force " + std::to_string(i) + ": ";
-        if (d.kind < 0 || d.kind > 3) return remd_fail(h, -1, who + "unknown kind");
+        if (d.kind < 0 || d.kind > REMD_CUSTOM_COMPOUND) return remd_fail(h, -1, who + "unknown kind");
+        const bool compound = d.kind == REMD_CUSTOM_COMPOUND;
+        if (compound ? (d.n_particles < 1 || d.n_particles > REMD_CUSTOM_MAX_PARTICLES) : d.n_particles != 0)
+            return remd_fail(h, -1, who + "n_particles is 1 ... REMD_CUSTOM_MAX_PARTICLES for a compound-bond force and 0 for every other kind");
+        const int wd = compound ? d.n_particles : width4[d.kind];
         if (d.n_terms <= 0 || !d.atoms) return remd_fail(h, -1, who + "no terms");
         if (d.n_params < 0 || d.n_params > REMD_CUSTOM_MAX_PARAMS || (d.n_params > 0 && !d.params))
             return remd_fail(h, -1, who + "0 ... REMD_CUSTOM_MAX_PARAMS parameters per term are supported");
@@ -483,24 +359,34 @@ int remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, int
         for (int k = 0; k < t.ng; ++k) if (d.global_defaults && d.global_defaults[k] != t.defaults[k]) return remd_fail(h, -1, who + "global_defaults differ between the descriptors");
         if (d.force_group != desc[0].force_group || d.force_group < 0 || d.force_group > 31)
             return remd_fail(h, -1, who + "every custom force of a handle must sit in one force group (0 ... 31)");
-        if (const char* bad = check_program(d, n_vars[d.kind])) return remd_fail(h, -1, who + bad);
-        const int wd = width[d.kind];
+        if (const char* bad = check_program(d, compound ? 3 * d.n_particles : n_vars4[d.kind])) return remd_fail(h, -1, who + bad);
         for (int k = 0; k < d.n_terms * wd; ++k) if (d.atoms[k] < 0 || d.atoms[k] >= h->N) return remd_fail(h, -1, who + "atom index out of range");
         cst_force f{};
-        f.kind = d.kind; f.periodic = d.periodic ? 1 : 0; f.n_terms = d.n_terms; f.n_params = d.n_params;
-        f.slot0 = t.total_pad; f.npad = (d.n_terms + 63) / 64 * 64;
+        f.kind = d.kind; f.periodic = d.periodic ? 1 : 0; f.n_terms = d.n_terms; f.n_params = d.n_params; f.n_particles = wd;
+        f.npad = (d.n_terms + 63) / 64 * 64;
         f.par0 = (int)t.par.size(); f.prog0 = (int)t.prog.size(); f.n_prog = d.n_program; f.const0 = (int)t.consts.size();
-        t.total_pad += f.npad;
-        for (int w = 0; w < f.npad / 64; ++w) t.wave_force.push_back(i);
         // parameters [n_params][npad]; a padding slot repeats the last term (finite arithmetic in lanes that add nothing)
         for (int p = 0; p < d.n_params; ++p) for (int s = 0; s < f.npad; ++s) t.par.push_back(d.params[(size_t)std::min(s, d.n_terms - 1) * d.n_params + p]);
         for (int pc = 0; pc < d.n_program; ++pc) t.prog.push_back(make_int2(d.program[2 * pc], d.program[2 * pc + 1]));
         if (d.n_consts > 0) t.consts.insert(t.consts.end(), d.consts, d.consts + d.n_consts);
         t.F.push_back(f);
     }
-    t.atoms.assign((size_t)4 * t.total_pad, 0);
+    // the padded term space: the four one-variable kinds first, the compound-bond forces behind them (each part has its own kernel);
+    // the energy columns keep the forces' order whatever their slots
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int i = 0; i < n; ++i) {
+            cst_force& f = t.F[i];
+            if ((f.kind == REMD_CUSTOM_COMPOUND) != (pass == 1)) continue;
+            f.slot0 = t.total_pad; t.total_pad += f.npad;
+            for (int w = 0; w < f.npad / 64; ++w) t.wave_force.push_back(i);
+        }
+        if (pass == 0) t.waves_simple = t.total_pad / 64;
+    }
+    int rows = 4;
+    for (int i = 0; i < n; ++i) rows = std::max(rows, t.F[i].n_particles);
+    t.atoms.assign((size_t)rows * t.total_pad, 0);
     for (int i = 0; i < n; ++i) {
-        const cst_force& f = t.F[i]; const int wd = width[f.kind];
+        const cst_force& f = t.F[i]; const int wd = f.n_particles;
         for (int s = 0; s < f.npad; ++s) for (int a = 0; a < wd; ++a)
             t.atoms[(size_t)a * t.total_pad + f.slot0 + s] = desc[i].atoms[(size_t)std::min(s, f.n_terms - 1) * wd + a];
     }

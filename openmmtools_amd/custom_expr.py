@@ -1,7 +1,12 @@
-"""Compiler of OpenMM energy expressions for the custom bond, angle, torsion and external forces (system.CustomBondForce,
-CustomAngleForce, CustomTorsionForce, CustomExternalForce): an energy string becomes the postfix program of
-include/remd_hip_custom.h, which csrc/custom_terms.hip runs on a forward-mode stack machine (every stack slot a value and its
-partial derivatives with respect to the force's variables).
+"""Compiler of OpenMM energy expressions for the custom bond, angle, torsion, external and compound-bond forces
+(system.CustomBondForce, CustomAngleForce, CustomTorsionForce, CustomExternalForce, CustomCompoundBondForce): an energy string becomes
+the postfix program of include/remd_hip_custom.h, which csrc/custom_terms.hip and csrc/custom_compound.hip run on a forward-mode
+stack machine (every stack slot a value and its partial derivatives with respect to the force's variables).
+
+A compound-bond force of P particles (1 ... MAX_PARTICLES) has the variables x1 y1 z1 ... xP yP zP (operand 3*(i-1)+c) and the
+functions distance(pi,pj), angle(pi,pj,pk) and dihedral(pi,pj,pk,pl), whose operand packs the zero-based particle slots in 4-bit
+fields, first argument lowest; the particle names p1 ... pP are legal only there.  pointdistance(x1,y1,z1,x2,y2,z2) is the
+periodicdistance opcode (the engine images it only where the force is periodic); pointangle and pointdihedral are refused.
 
 Grammar: numbers (exponent notation included), ``+ - * / ^``, unary minus, parentheses, function calls, and ``;``-separated
 definitions ``name = expr`` in any order, substituted where they are used.  ``^`` binds tighter than unary minus and groups to the
@@ -17,15 +22,22 @@ import numpy as np
 
 MAX_PROGRAM, MAX_STACK, MAX_PARAMS, MAX_GLOBALS, MAX_FORCES = 256, 16, 16, 16, 8
 MAX_INTEGER_POWER = 64
+MAX_PARTICLES = 8                               # particles per bond of a compound-bond force
 
-KIND_BOND, KIND_ANGLE, KIND_TORSION, KIND_EXTERNAL = 0, 1, 2, 3
+KIND_BOND, KIND_ANGLE, KIND_TORSION, KIND_EXTERNAL, KIND_COMPOUND = 0, 1, 2, 3, 4
 KIND_OF_CLASS = {'CustomBondForce': KIND_BOND, 'CustomAngleForce': KIND_ANGLE, 'CustomTorsionForce': KIND_TORSION,
-                 'CustomExternalForce': KIND_EXTERNAL}
+                 'CustomExternalForce': KIND_EXTERNAL, 'CustomCompoundBondForce': KIND_COMPOUND}
 VARIABLES = {KIND_BOND: ('r',), KIND_ANGLE: ('theta',), KIND_TORSION: ('theta',), KIND_EXTERNAL: ('x', 'y', 'z')}
+
+
+def compound_variables(n_particles):
+    """x1 y1 z1 ... xP yP zP: the variables of a compound-bond force in operand order"""
+    return tuple('%s%d' % (c, i) for i in range(1, n_particles + 1) for c in 'xyz')
+
 
 # opcodes (include/remd_hip_custom.h)
 (CONST, VAR, PARAM, GLOBAL, ADD, SUB, MUL, DIV, NEG, POWI, POW, SQRT, EXP, LOG, SIN, COS, TAN, ASIN, ACOS, ATAN, ATAN2, SINH, COSH,
- TANH, ERF, ERFC, ABS, MIN, MAX, STEP, DELTA, SELECT, FLOOR, CEIL, PERIODICDISTANCE) = range(35)
+ TANH, ERF, ERFC, ABS, MIN, MAX, STEP, DELTA, SELECT, FLOOR, CEIL, PERIODICDISTANCE, DISTANCE, ANGLE, DIHEDRAL) = range(38)
 
 # name -> (opcode, number of arguments)
 FUNCTIONS = dict(sqrt=(SQRT, 1), exp=(EXP, 1), log=(LOG, 1), sin=(SIN, 1), cos=(COS, 1), tan=(TAN, 1), asin=(ASIN, 1), acos=(ACOS, 1),
@@ -35,7 +47,10 @@ FUNCTIONS = dict(sqrt=(SQRT, 1), exp=(EXP, 1), log=(LOG, 1), sin=(SIN, 1), cos=(
 _BINARY = {'+': ADD, '-': SUB, '*': MUL, '/': DIV}
 # slots an opcode takes from the stack (it pushes one)
 POPS = {CONST: 0, VAR: 0, PARAM: 0, GLOBAL: 0, ADD: 2, SUB: 2, MUL: 2, DIV: 2, POW: 2, ATAN2: 2, MIN: 2, MAX: 2, SELECT: 3,
-        PERIODICDISTANCE: 6}
+        PERIODICDISTANCE: 6, DISTANCE: 0, ANGLE: 0, DIHEDRAL: 0}
+# the functions of particles of a compound-bond force: name -> (opcode, number of particles)
+PARTICLE_FUNCTIONS = dict(distance=(DISTANCE, 2), angle=(ANGLE, 3), dihedral=(DIHEDRAL, 4))
+_PARTICLE_NAME = re.compile(r'p([1-9][0-9]*)')
 
 _TOKEN = re.compile(r'\s*(?:(\d+\.?\d*(?:[eE][+-]?\d+)?|\.\d+(?:[eE][+-]?\d+)?)|([A-Za-z_][A-Za-z_0-9]*)|(.))')
 
@@ -164,12 +179,14 @@ def split_definitions(energy, where='expression'):
     return parts[0], definitions
 
 
-def compile_expression(energy, variables, parameters, global_columns, where='expression', tabulated=(), periodic_distance=False):
+def compile_expression(energy, variables, parameters, global_columns, where='expression', tabulated=(), periodic_distance=False,
+                       n_particles=0):
     """The postfix program of ``energy``.
 
     variables: the force's own variable names in operand order; parameters: the per-term parameter names in order; global_columns:
     {global parameter name: column of the handle's table}; tabulated: names of tabulated functions (refused); periodic_distance:
-    whether periodicdistance(...) is allowed (an external force that uses periodic boundary conditions).
+    whether periodicdistance(...) is allowed (an external force that uses periodic boundary conditions); n_particles: the particles
+    per bond of a compound-bond force (0: another force), which opens distance / angle / dihedral over p1 ... pP and pointdistance.
 
     Returns dict(program int32 [n][2], consts float64 [m], stack_depth).
     """
@@ -213,6 +230,8 @@ def compile_expression(energy, variables, parameters, global_columns, where='exp
                 return emit(PARAM, parameters.index(name))
             if name in global_columns:
                 return emit(GLOBAL, global_columns[name])
+            if n_particles and _PARTICLE_NAME.fullmatch(name):
+                raise NotImplementedError('%s: particle name %r outside distance(), angle() and dihedral()' % (where, name))
             raise NotImplementedError('%s: unknown variable %r' % (where, name))
         if kind == 'neg':
             walk(node[1], active)
@@ -232,6 +251,27 @@ def compile_expression(energy, variables, parameters, global_columns, where='exp
             name, args = node[1], node[2]
             if name in tabulated:
                 raise NotImplementedError('%s: tabulated function %r (tabulated functions are not supported)' % (where, name))
+            if n_particles and name in PARTICLE_FUNCTIONS:
+                op, n_args = PARTICLE_FUNCTIONS[name]
+                if len(args) != n_args:
+                    raise NotImplementedError('%s: function %r takes %d particles, not %d' % (where, name, n_args, len(args)))
+                packed = 0
+                for k, a in enumerate(args):
+                    m = _PARTICLE_NAME.fullmatch(a[1]) if a[0] == 'name' else None
+                    if m is None:
+                        raise NotImplementedError('%s: the arguments of %r are particle names p1 ... p%d' % (where, name, n_particles))
+                    if int(m.group(1)) > n_particles:
+                        raise NotImplementedError('%s: particle %r in a bond of %d particles' % (where, a[1], n_particles))
+                    packed |= (int(m.group(1)) - 1) << (4 * k)
+                return emit(op, packed)
+            if n_particles and name in ('pointangle', 'pointdihedral'):
+                raise NotImplementedError('%s: function %r (pointangle and pointdihedral are not supported)' % (where, name))
+            if n_particles and name == 'pointdistance':
+                if len(args) != 6:
+                    raise NotImplementedError('%s: function %r takes 6 arguments, not %d' % (where, name, len(args)))
+                for a in args:
+                    walk(a, active)
+                return emit(PERIODICDISTANCE)
             if name not in FUNCTIONS or (name == 'periodicdistance' and not periodic_distance):
                 raise NotImplementedError('%s: unknown function %r' % (where, name))
             op, n_args = FUNCTIONS[name]
@@ -258,9 +298,12 @@ def _per_term_names(force):
 
 def is_custom_term_force(force):
     """Whether system_to_desc sends this force down the expression path: one of the four classes whose energy is neither the
-    HarmonicOscillator string (ext_K / ext_x0 / ext_U0) nor one of the restraint forms (csrc/restraints.hip)."""
+    HarmonicOscillator string (ext_K / ext_x0 / ext_U0) nor one of the restraint forms (csrc/restraints.hip), or a
+    CustomCompoundBondForce."""
     from . import system as _system
     from . import forces as _forces
+    if isinstance(force, _system.CustomCompoundBondForce):
+        return True
     if isinstance(force, _system.CustomExternalForce):
         return not force.is_harmonic_oscillator()
     if isinstance(force, (_system.CustomAngleForce, _system.CustomTorsionForce)):
@@ -272,7 +315,7 @@ def is_custom_term_force(force):
 
 def custom_terms_desc(forces):
     """The 'custom_terms' entry of system.system_to_desc for the custom forces ``forces`` (in System order): a dict keyed by position
-    ('000', '001', ...), each value dict(kind, atoms [n][1..4], params [n][p], global_names, global_defaults, program, consts,
+    ('000', '001', ...), each value dict(kind, atoms [n][1..4] ([n][P] and n_particles = P of a compound-bond force), params [n][p], global_names, global_defaults, program, consts,
     stack_depth, periodic, force_group, energy).  The global names and defaults are the handle's columns, the same in every entry: a
     global two forces share is one column."""
     if len(forces) > MAX_FORCES:
@@ -307,8 +350,14 @@ def custom_terms_desc(forces):
         tabulated = [f.getTabulatedFunctionName(i) for i in range(f.getNumTabulatedFunctions())]
         own = {n: columns[n] for n in (f.getGlobalParameterName(i) for i in range(f.getNumGlobalParameters()))}
         periodic = bool(f.usesPeriodicBoundaryConditions())
-        prog = compile_expression(f.getEnergyFunction(), VARIABLES[kind], per_term, own, where=where, tabulated=tabulated,
-                                  periodic_distance=(kind == KIND_EXTERNAL and periodic))
+        n_particles = 0
+        if kind == KIND_COMPOUND:
+            n_particles = int(f.getNumParticlesPerBond())
+            if not 1 <= n_particles <= MAX_PARTICLES:
+                raise NotImplementedError('%s: bonds of %d particles (the engine takes 1 ... %d)' % (cls, n_particles, MAX_PARTICLES))
+        prog = compile_expression(f.getEnergyFunction(), compound_variables(n_particles) if n_particles else VARIABLES[kind], per_term, own,
+                                  where=where, tabulated=tabulated, periodic_distance=(kind == KIND_EXTERNAL and periodic),
+                                  n_particles=n_particles)
         atoms, params = f._term_arrays()
         if len(atoms) == 0:
             continue
@@ -316,6 +365,8 @@ def custom_terms_desc(forces):
                                       global_defaults=np.array(defaults, dtype=np.float64), program=prog['program'], consts=prog['consts'],
                                       stack_depth=prog['stack_depth'], periodic=int(periodic), force_group=int(f.getForceGroup()),
                                       energy=f.getEnergyFunction())
+        if n_particles:
+            out['%03d' % (len(out) - 1)]['n_particles'] = n_particles
     return out
 
 

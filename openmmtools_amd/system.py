@@ -332,6 +332,44 @@ class CustomTorsionForce(_CustomForce):
         return _term_arrays(self._torsions, 4, len(self._per_bond), 'CustomTorsionForce')
 
 
+class CustomCompoundBondForce(_CustomForce):
+    """openmm.CustomCompoundBondForce: bonds between ``numParticles`` particles, the energy a function of their coordinates
+    x1 y1 z1 ... and of distance(p1,p2), angle(p1,p2,p3), dihedral(p1,p2,p3,p4) and pointdistance(x1,y1,z1,x2,y2,z2) between them, of
+    per-bond and of global parameters (Boresch restraints are one six-particle bond).  Every expression goes to
+    csrc/custom_compound.hip."""
+
+    def __init__(self, numParticles, energy):
+        super().__init__(energy)
+        self._n_particles = int(numParticles)
+        self._bonds = []                      # (p1, ..., pP, parameters)
+
+    def getNumParticlesPerBond(self):
+        return self._n_particles
+
+    def _bond(self, particles, parameters):
+        particles = [int(p) for p in particles]
+        if len(particles) != self._n_particles:
+            raise ValueError('CustomCompoundBondForce: a bond of %d particles, the force declares %d' % (len(particles), self._n_particles))
+        return tuple(particles) + ([float(p) for p in parameters],)
+
+    def addBond(self, particles, parameters=()):
+        self._bonds.append(self._bond(particles, parameters))
+        return len(self._bonds) - 1
+
+    def getNumBonds(self):
+        return len(self._bonds)
+
+    def getBondParameters(self, index):
+        bond = self._bonds[index]
+        return list(bond[:-1]), list(bond[-1])
+
+    def setBondParameters(self, index, particles, parameters=()):
+        self._bonds[index] = self._bond(particles, parameters)
+
+    def _term_arrays(self):
+        return _term_arrays(self._bonds, self._n_particles, len(self._per_bond), 'CustomCompoundBondForce')
+
+
 class CustomExternalForce(_CustomForce):
     """openmm.CustomExternalForce: the energy a function of a particle's x, y, z, of per-particle and of global parameters.  The
     harmonic-well expression of testsystems.HarmonicOscillator (testsystems.py:779-786) keeps the engine's own kernel (ext_K / ext_x0 /

@@ -105,6 +105,54 @@ def main():
         ss = states.SamplerState(hg.positions, box_vectors=hg.system.getDefaultPeriodicBoxVectors())
         s.create(ths, [ss] * 8)
         run('4cb (1-GPU share, custom bond force): HostGuestExplicit + a 30-bond CustomBondForce, 8 replicas x 64 states, g-BAOAB 2 fs x 500', s, 3)
+    if '4bo' in which:
+        # config 4's share with one orientational (Boresch) restraint (custom_expr.py, csrc/custom_compound.hip): a six-particle
+        # CustomCompoundBondForce on three CB7 and three guest heavy atoms, the reference values the starting geometry's, the global
+        # lambda_restraints rising 0 -> 1 along the coupled half and 1 where the guest is decoupled
+        from openmmtools_amd.system import CustomCompoundBondForce
+
+        class RestraintState(states.GlobalParameterState):
+            lambda_restraints = states.GlobalParameterState.GlobalParameter('lambda_restraints', standard_value=1.0)
+        hg = testsystems.HostGuestExplicit()
+        lam_e = np.concatenate([np.linspace(1.0, 0.0, 32), np.zeros(32)])
+        lam_s = np.concatenate([np.ones(32), np.linspace(1.0, 0.0, 32)])
+        lam_r = np.concatenate([np.linspace(0.0, 1.0, 32), np.ones(32)])
+        asys = alchemy.AbsoluteAlchemicalFactory().create_alchemical_system(hg.system, alchemy.AlchemicalRegion(alchemical_atoms=range(126, 156)))
+        heavy = [i for i in range(126) if hg.system.getParticleMass(i) > 1.5]
+        guest = [i for i in range(126, 156) if hg.system.getParticleMass(i) > 1.5]
+        atoms = [heavy[2 * len(heavy) // 3], heavy[len(heavy) // 3], heavy[0], guest[0], guest[len(guest) // 2], guest[-1]]
+        f = CustomCompoundBondForce(6, 'lambda_restraints*E; E = (K_r/2)*(distance(p3,p4)-r_aA0)^2 + (K_thetaA/2)*(angle(p2,p3,p4)-theta_A0)^2 '
+                                       '+ (K_thetaB/2)*(angle(p3,p4,p5)-theta_B0)^2 + (K_phiA/2)*dphi_A^2 + (K_phiB/2)*dphi_B^2 + (K_phiC/2)*dphi_C^2; '
+                                       'dphi_A = dA - floor(dA/(2*pi)+0.5)*(2*pi); dA = dihedral(p1,p2,p3,p4)-phi_A0; '
+                                       'dphi_B = dB - floor(dB/(2*pi)+0.5)*(2*pi); dB = dihedral(p2,p3,p4,p5)-phi_B0; '
+                                       'dphi_C = dC - floor(dC/(2*pi)+0.5)*(2*pi); dC = dihedral(p3,p4,p5,p6)-phi_C0; pi = 3.1415926535897932385')
+        f.addGlobalParameter('lambda_restraints', 1.0)
+        x = np.asarray(hg.positions, dtype=np.float64)[atoms]
+
+        def angle(i, j, k):
+            u, v = x[i] - x[j], x[k] - x[j]
+            return float(np.arccos(np.dot(u, v) / np.sqrt(np.dot(u, u) * np.dot(v, v))))
+
+        def dihedral(i, j, k, l):
+            b1, b2, b3 = x[j] - x[i], x[k] - x[j], x[l] - x[k]
+            m, n = np.cross(b1, b2), np.cross(b2, b3)
+            return float(np.arctan2(np.linalg.norm(b2) * np.dot(b1, n), np.dot(m, n)))
+        reference = dict(r_aA0=float(np.linalg.norm(x[3] - x[2])), theta_A0=angle(1, 2, 3), theta_B0=angle(2, 3, 4), phi_A0=dihedral(0, 1, 2, 3),
+                         phi_B0=dihedral(1, 2, 3, 4), phi_C0=dihedral(2, 3, 4, 5))
+        springs = dict(K_r=20.0 * 4.184 * 100.0, K_thetaA=20.0 * 4.184, K_thetaB=20.0 * 4.184, K_phiA=20.0 * 4.184, K_phiB=20.0 * 4.184, K_phiC=20.0 * 4.184)
+        values = dict(reference, **springs)
+        for name in values:
+            f.addPerBondParameter(name)
+        f.addBond(atoms, list(values.values()))
+        asys.addForce(f)
+        ths = [states.CompoundThermodynamicState(states.ThermodynamicState(asys, 300.0),
+                                                 [states.AlchemicalState(lambda_sterics=ls, lambda_electrostatics=le), RestraintState(lambda_restraints=lr)])
+               for le, ls, lr in zip(lam_e, lam_s, lam_r)]
+        s = SAMSSampler(mcmc_moves=move(2.0, 'V R R O R R V'), number_of_iterations=10 ** 9, engine=HipEngine(), seed=1)
+        ss = states.SamplerState(hg.positions, box_vectors=hg.system.getDefaultPeriodicBoxVectors())
+        s.create(ths, [ss] * 8)
+        run('4bo (1-GPU share, Boresch restraint): HostGuestExplicit + one six-particle CustomCompoundBondForce, 8 replicas x 64 states, '
+            'g-BAOAB 2 fs x 500', s, 3)
     if '4cr' in which:
         # config 4's share with EVERY harmonic bond, harmonic angle and periodic torsion of the System moved to custom forces with the
         # same formulas (custom_expr.py): what the expression machine costs at a force field's size, against the built-in listed terms of '4'
