@@ -9,81 +9,12 @@ import pytest
 
 import compound_expr_oracle as oracle
 from custom_expr_oracle import Expression
+from custom_opcode_cases import run_pass
 from openmmtools_amd import alchemy, custom_expr as cx, states, testsystems
 from openmmtools_amd.system import System, system_to_desc, CustomBondForce, CustomCompoundBondForce
 
 
-# ---- a mirror of the machine for a compound program: every slot a value and its gradient with respect to particle `seed` ---------------
-def _particles_op(op, arg, x, seed):
-    """value and gradient with respect to particle `seed` of distance / angle / dihedral over the slots packed in `arg` (the formulas
-    of the bonded kernels: bond, angle, dihedral in the sign convention of PeriodicTorsionForce)"""
-    s = [(arg >> (4 * k)) & 15 for k in range(op - cx.DISTANCE + 2)]
-    g = np.zeros((len(s), 3))
-    if op == cx.DISTANCE:
-        d = x[s[1]] - x[s[0]]
-        v = np.linalg.norm(d)
-        g[1], g[0] = d / v, -d / v
-    elif op == cx.ANGLE:
-        v0, v1 = x[s[0]] - x[s[1]], x[s[2]] - x[s[1]]
-        cp = np.cross(v0, v1)
-        rp = max(np.linalg.norm(cp), 1e-6)
-        v = math.acos(max(-1.0, min(1.0, np.dot(v0, v1) / math.sqrt(np.dot(v0, v0) * np.dot(v1, v1)))))
-        g[0], g[2] = np.cross(v0, cp) / (np.dot(v0, v0) * rp), np.cross(cp, v1) / (np.dot(v1, v1) * rp)
-        g[1] = -(g[0] + g[2])
-    else:
-        b1, b2, b3 = x[s[1]] - x[s[0]], x[s[2]] - x[s[1]], x[s[3]] - x[s[2]]
-        m, n = np.cross(b1, b2), np.cross(b2, b3)
-        lb2 = np.linalg.norm(b2)
-        v = math.atan2(lb2 * np.dot(b1, n), np.dot(m, n))
-        g[0], g[3] = -lb2 / np.dot(m, m) * m, lb2 / np.dot(n, n) * n
-        s12, s32 = np.dot(b1, b2) / lb2 ** 2, np.dot(b3, b2) / lb2 ** 2
-        g[1], g[2] = -(1.0 + s12) * g[0] + s32 * g[3], -(1.0 + s32) * g[3] + s12 * g[0]
-    return np.concatenate([[v], sum((g[k] for k in range(len(s)) if s[k] == seed), np.zeros(3))])
-
-
-def run_pass(prog, x, params, global_values, seed):
-    """one pass of the program over the bond's particles x [P][3] -> (value, dE/d(x, y, z) of particle seed, the deepest stack)"""
-    consts, stack, deepest = prog['consts'], [], 0
-    unary = {cx.NEG: lambda a: (-a, -1.0), cx.SQRT: lambda a: (math.sqrt(a), 0.5 / math.sqrt(a)), cx.EXP: lambda a: (math.exp(a), math.exp(a)),
-             cx.SIN: lambda a: (math.sin(a), math.cos(a)), cx.COS: lambda a: (math.cos(a), -math.sin(a)),
-             cx.FLOOR: lambda a: (float(math.floor(a)), 0.0)}
-    for op, arg in prog['program']:
-        if op == cx.CONST:
-            stack.append(np.array([consts[arg], 0.0, 0.0, 0.0]))
-        elif op == cx.VAR:
-            e = np.zeros(4); e[0] = x[arg // 3][arg % 3]
-            if arg // 3 == seed:
-                e[1 + arg % 3] = 1.0
-            stack.append(e)
-        elif op == cx.PARAM:
-            stack.append(np.array([params[arg], 0.0, 0.0, 0.0]))
-        elif op == cx.GLOBAL:
-            stack.append(np.array([global_values[arg], 0.0, 0.0, 0.0]))
-        elif op in (cx.DISTANCE, cx.ANGLE, cx.DIHEDRAL):
-            stack.append(_particles_op(op, arg, x, seed))
-        elif op in (cx.ADD, cx.SUB, cx.MUL, cx.DIV):
-            b, a = stack.pop(), stack.pop()
-            if op == cx.ADD: z = a + b
-            elif op == cx.SUB: z = a - b
-            elif op == cx.MUL: z = np.concatenate([[a[0] * b[0]], a[1:] * b[0] + a[0] * b[1:]])
-            else: z = np.concatenate([[a[0] / b[0]], (a[1:] - a[0] / b[0] * b[1:]) / b[0]])
-            stack.append(z)
-        elif op == cx.PERIODICDISTANCE:                              # pointdistance of a force that is not periodic: no image
-            a = [stack.pop() for _ in range(6)][::-1]
-            d = np.array([a[3][0] - a[0][0], a[4][0] - a[1][0], a[5][0] - a[2][0]])
-            n = np.linalg.norm(d)
-            stack.append(np.concatenate([[n], sum(d[k] / n * (a[3 + k][1:] - a[k][1:]) for k in range(3))]))
-        elif op == cx.POWI:
-            a = stack.pop()
-            v = a[0] ** abs(arg) if arg >= 0 else 1.0 / a[0] ** abs(arg)
-            stack.append(np.concatenate([[v], arg * v / a[0] * a[1:]]))
-        else:
-            a = stack.pop()
-            v, k = unary[op](a[0])
-            stack.append(np.concatenate([[v], k * a[1:]]))
-        deepest = max(deepest, len(stack))
-    assert len(stack) == 1
-    return stack[0][0], stack[0][1:], deepest
+# (the mirror of the machine for a compound program, run_pass with its seeded passes, lives in tests/custom_opcode_cases.py)
 
 
 # six particles of a bent chain: no three in a line, no four in a plane

@@ -8,75 +8,12 @@ import numpy as np
 import pytest
 
 import custom_expr_oracle as oracle
+from custom_opcode_cases import run_program
 from openmmtools_amd import alchemy, custom_expr as cx, forces, states, testsystems
 from openmmtools_amd.system import (System, system_to_desc, CustomBondForce, CustomAngleForce, CustomTorsionForce, CustomExternalForce)
 
 
-# ---- a small stack machine for the postfix program: every slot a value and its partials with respect to the three variables ----------
-def run_program(prog, variables, params, global_values, box=None):
-    """-> (value, partials [3], the deepest the stack got)"""
-    consts, stack, deepest = prog['consts'], [], 0
-
-    def chain(x, v, k):
-        return np.concatenate([[v], k * x[1:]])
-
-    unary = {cx.NEG: lambda a: (-a, -1.0), cx.SQRT: lambda a: (math.sqrt(a), 0.5 / math.sqrt(a)), cx.EXP: lambda a: (math.exp(a), math.exp(a)),
-             cx.LOG: lambda a: (math.log(a), 1.0 / a), cx.SIN: lambda a: (math.sin(a), math.cos(a)), cx.COS: lambda a: (math.cos(a), -math.sin(a)),
-             cx.TAN: lambda a: (math.tan(a), 1.0 + math.tan(a) ** 2), cx.ASIN: lambda a: (math.asin(a), 1.0 / math.sqrt(1.0 - a * a)),
-             cx.ACOS: lambda a: (math.acos(a), -1.0 / math.sqrt(1.0 - a * a)), cx.ATAN: lambda a: (math.atan(a), 1.0 / (1.0 + a * a)),
-             cx.SINH: lambda a: (math.sinh(a), math.cosh(a)), cx.COSH: lambda a: (math.cosh(a), math.sinh(a)),
-             cx.TANH: lambda a: (math.tanh(a), 1.0 - math.tanh(a) ** 2),
-             cx.ERF: lambda a: (math.erf(a), 2.0 / math.sqrt(math.pi) * math.exp(-a * a)),
-             cx.ERFC: lambda a: (math.erfc(a), -2.0 / math.sqrt(math.pi) * math.exp(-a * a)),
-             cx.ABS: lambda a: (abs(a), -1.0 if a < 0 else 1.0), cx.STEP: lambda a: (1.0 if a >= 0 else 0.0, 0.0),
-             cx.DELTA: lambda a: (1.0 if a == 0 else 0.0, 0.0), cx.FLOOR: lambda a: (float(math.floor(a)), 0.0),
-             cx.CEIL: lambda a: (float(math.ceil(a)), 0.0)}
-    for op, arg in prog['program']:
-        if op == cx.CONST:
-            stack.append(np.array([consts[arg], 0.0, 0.0, 0.0]))
-        elif op == cx.VAR:
-            e = np.zeros(4); e[0] = variables[arg]; e[1 + arg] = 1.0
-            stack.append(e)
-        elif op == cx.PARAM:
-            stack.append(np.array([params[arg], 0.0, 0.0, 0.0]))
-        elif op == cx.GLOBAL:
-            stack.append(np.array([global_values[arg], 0.0, 0.0, 0.0]))
-        elif op in (cx.ADD, cx.SUB, cx.MUL, cx.DIV, cx.POW, cx.ATAN2, cx.MIN, cx.MAX):
-            y, x = stack.pop(), stack.pop()
-            if op == cx.ADD: z = x + y
-            elif op == cx.SUB: z = x - y
-            elif op == cx.MUL: z = np.concatenate([[x[0] * y[0]], x[1:] * y[0] + x[0] * y[1:]])
-            elif op == cx.DIV: z = np.concatenate([[x[0] / y[0]], (x[1:] - x[0] / y[0] * y[1:]) / y[0]])
-            elif op == cx.POW:
-                p = x[0] ** y[0]
-                z = np.concatenate([[p], y[0] * x[0] ** (y[0] - 1.0) * x[1:] + (p * math.log(x[0]) * y[1:] if np.any(y[1:] != 0.0) else 0.0)])
-            elif op == cx.ATAN2: z = np.concatenate([[math.atan2(x[0], y[0])], (y[0] * x[1:] - x[0] * y[1:]) / (x[0] ** 2 + y[0] ** 2)])
-            elif op == cx.MIN: z = x if x[0] < y[0] else y
-            else: z = x if x[0] > y[0] else y
-            stack.append(z)
-        elif op == cx.SELECT:
-            z, y, x = stack.pop(), stack.pop(), stack.pop()
-            stack.append(y if x[0] != 0.0 else z)
-        elif op == cx.PERIODICDISTANCE:
-            a = [stack.pop() for _ in range(6)][::-1]
-            d = oracle.minimum_image(np.array([a[3][0] - a[0][0], a[4][0] - a[1][0], a[5][0] - a[2][0]]), box)
-            n = np.linalg.norm(d)
-            stack.append(np.concatenate([[n], sum(d[k] / n * (a[3 + k][1:] - a[k][1:]) for k in range(3))]))
-        elif op == cx.POWI:
-            x = stack.pop()
-            v = 1.0
-            for _ in range(abs(arg)):
-                v *= x[0]                                    # multiplications only: defined for a negative base
-            if arg < 0:
-                v = 1.0 / v
-            stack.append(chain(x, v, arg * v / x[0] if arg else 0.0))
-        else:
-            x = stack.pop()
-            v, k = unary[op](x[0])
-            stack.append(chain(x, v, k))
-        deepest = max(deepest, len(stack))
-    assert len(stack) == 1
-    return stack[0][0], stack[0][1:], deepest
+# (the small stack machine for the postfix program, run_program, lives in tests/custom_opcode_cases.py)
 
 
 # (energy, variables, parameter names -> values, global names -> values); between them every operator and every function
