@@ -1,0 +1,59 @@
+/*
+ * remd_hip_mbar.h — GPU-only extension of the C ABI in remd_hip.h: the passes of the MBAR estimator on the device.
+ *
+ * The multistate Bennett acceptance ratio estimator (Shirts & Chodera 2008) as multistate/analysis.py::MBAR solves it, with the
+ * passes over the [K][N] matrix of reduced potentials done on the device: the log of the mixture denominator per sample
+ *
+ *   log_den_n = ln sum_k N_k exp(f_k - u_kn)                  (over the sampled states, N_k > 0)
+ *
+ * the self-consistent update  f_i = -ln sum_n exp(-u_in - log_den_n)  (eq. 11), the sums the Newton step needs, the Gram matrix
+ * W^T W of the weights  W_nk = exp(f_k - u_kn - log_den_n)  that the asymptotic covariance (eq. 8) needs, and the weights
+ * themselves.  The K x K linear algebra stays with the host.  Everything is f64.  No pass uses a floating-point atomic: every
+ * sum is taken per chunk of samples and the chunks are merged in chunk order, so a result depends on the input alone.
+ *
+ * An MBAR problem is an object of its own: it needs a device, not a remd_handle.  A failed call returns non-zero and leaves its
+ * message in remd_last_error(NULL).
+ *
+ * These entry points are declared here and not in remd_hip.h because the CPU port of the ABI does not provide them: a host binds
+ * them only where the loaded library exports them.  Conventions as in remd_hip.h.
+ */
+#ifndef REMD_HIP_MBAR_H
+#define REMD_HIP_MBAR_H
+
+#include "remd_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* the most states of one problem: the augmented Gram matrix of remd_mbar_gram then has 2 x 512 = 1024 columns */
+#define REMD_MBAR_MAX_STATES 512
+
+typedef struct remd_mbar_ctx* remd_mbar;
+
+/* Uploads u_kn[K][N] (sample index fastest) and N_k[K] once.  Refused: K < 1 or N < 1, K > REMD_MBAR_MAX_STATES, a negative N_k,
+   sum N_k != N, a non-finite u_kn in a row with N_k > 0.                                                                          */
+int  remd_mbar_create(int device, int K, int64_t N, const double* u_kn, const int64_t* N_k, remd_mbar* out);
+void remd_mbar_destroy(remd_mbar m);
+
+/* log_den[N] (or NULL) at f_k[K], and the objective  phi = sum_n log_den_n - sum_k N_k f_k  (or NULL)                            */
+int  remd_mbar_log_denominator(remd_mbar m, const double* f_k, double* log_den, double* phi);
+/* one application of eq. 11 to every state, sampled or not, with the denominator at f_k:  f_new[K], not shifted                  */
+int  remd_mbar_self_consistent(remd_mbar m, const double* f_k, double* f_new);
+/* W_sum[K] = sum_n W_kn and gram[K][K] = W W^T at f_k; rows and columns of unsampled states are 0.  phi (or NULL) as above.      */
+int  remd_mbar_newton_parts(remd_mbar m, const double* f_k, double* W_sum, double* gram, double* phi);
+/* gram[C][C] = W^T W over all K states (C = K), or with_observable != 0: C = 2K, column K + k = exp(ln W_nk + ln A_kn - log_cA_k)
+   with the observable A = u - (min u - 1) and log_cA_k = ln sum_n W_nk A_kn, returned in log_cA[K] (or NULL).                     */
+int  remd_mbar_gram(remd_mbar m, const double* f_k, int with_observable, double* gram, double* log_cA);
+/* log_W_nk[N][K] = f_k - u_kn - log_den_n, state index fastest                                                                   */
+int  remd_mbar_log_weights(remd_mbar m, const double* f_k, double* log_W_nk);
+/* the samples per workgroup of the column pass, the row pass and the Gram pass (C columns) of this problem, for tests and tools  */
+int  remd_mbar_chunks(remd_mbar m, int C, int64_t* column_chunk, int64_t* row_chunk, int64_t* gram_chunk);
+/* device milliseconds of the kernels of the last call on this object (events around its launches), for tools                     */
+int  remd_mbar_last_ms(remd_mbar m, double* ms);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif

@@ -91,6 +91,10 @@ CUSTOM_EXPORTS = ['remd_set_custom_terms', 'remd_set_custom_globals', 'remd_get_
 # the GPU-only extension of include/remd_hip_barostat.h (per-axis Monte Carlo barostats), bound the same way
 BAROSTAT_AXIS_EXPORTS = ['remd_set_barostat_axes', 'remd_get_barostat_axis_stats']
 BAROSTAT_ANISOTROPIC, BAROSTAT_MEMBRANE = 1, 2
+# the GPU-only extension of include/remd_hip_mbar.h (the passes of the MBAR estimator), bound the same way
+MBAR_EXPORTS = ['remd_mbar_create', 'remd_mbar_destroy', 'remd_mbar_log_denominator', 'remd_mbar_self_consistent', 'remd_mbar_newton_parts',
+                'remd_mbar_gram', 'remd_mbar_log_weights', 'remd_mbar_chunks', 'remd_mbar_last_ms']
+MBAR_MAX_STATES = 512
 
 EXPORTS = [
     'remd_create', 'remd_destroy', 'remd_last_error', 'remd_version', 'remd_set_system', 'remd_set_coulomb_cutoff', 'remd_set_reaction_field', 'remd_set_alchemical_options', 'remd_set_alchemical_regions',
@@ -212,6 +216,18 @@ def load_library(path=None):
     if hasattr(lib, 'remd_set_gb_model'):                 # include/remd_hip_gb.h (GPU-only, like the restraints)
         lib.remd_set_gb_model.argtypes = [vp, C.POINTER(RemdGbModelDesc)]
         lib.remd_set_gb_model.restype = C.c_int
+    if hasattr(lib, 'remd_mbar_create'):                  # include/remd_hip_mbar.h (GPU-only, like the restraints)
+        lib.remd_mbar_create.argtypes = [C.c_int, C.c_int, C.c_int64, c_double_p, c_int64_p, C.POINTER(vp)]
+        lib.remd_mbar_destroy.argtypes = [vp]
+        lib.remd_mbar_log_denominator.argtypes = [vp, c_double_p, c_double_p, c_double_p]
+        lib.remd_mbar_self_consistent.argtypes = [vp, c_double_p, c_double_p]
+        lib.remd_mbar_newton_parts.argtypes = [vp, c_double_p, c_double_p, c_double_p, c_double_p]
+        lib.remd_mbar_gram.argtypes = [vp, c_double_p, C.c_int, c_double_p, c_double_p]
+        lib.remd_mbar_log_weights.argtypes = [vp, c_double_p, c_double_p]
+        lib.remd_mbar_chunks.argtypes = [vp, C.c_int, c_int64_p, c_int64_p, c_int64_p]
+        lib.remd_mbar_last_ms.argtypes = [vp, c_double_p]
+        for name in MBAR_EXPORTS:
+            getattr(lib, name).restype = None if name == 'remd_mbar_destroy' else C.c_int
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -265,6 +281,99 @@ def build_desc(d):
     s.n_alch = len(d['alch_atoms']); s.alch_atoms = i32(d['alch_atoms'])
     s.softcore_alpha, s.softcore_a, s.softcore_b, s.softcore_c = [float(v) for v in d['softcore']]
     return s, keep
+
+
+class DeviceMBAR:
+    """One MBAR problem on the device (include/remd_hip_mbar.h): u_kn [K][N] and N_k are uploaded once; every method is one pass at
+    the f_k it is given.  The K x K algebra of the estimator stays with the caller (multistate/analysis.py::MBAR, solver='device')."""
+
+    def __init__(self, u_kn, N_k, device=0, lib_path=None):
+        self.lib = load_library(lib_path)
+        self.h = None
+        for name in MBAR_EXPORTS:
+            if not hasattr(self.lib, name):
+                raise NotImplementedError('%s: this build of the engine library has no MBAR passes (include/remd_hip_mbar.h is GPU-only)' % name)
+        u = np.ascontiguousarray(u_kn, dtype=np.float64)
+        nk = np.ascontiguousarray(N_k, dtype=np.int64)
+        if u.ndim != 2 or nk.shape != (u.shape[0],):
+            raise ValueError('u_kn must be [K][N] and N_k [K]')
+        self.K, self.N = int(u.shape[0]), int(u.shape[1])
+        h = C.c_void_p()
+        rc = self.lib.remd_mbar_create(int(device), self.K, self.N, _dp(u), _lp(nk), C.byref(h))
+        if rc != 0:
+            raise RuntimeError('remd_mbar_create failed (%d): %s' % (rc, self.lib.remd_last_error(None).decode()))
+        self.h = h
+
+    def close(self):
+        if self.h is not None:
+            self.lib.remd_mbar_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, name):
+        if rc != 0:
+            raise RuntimeError('%s failed (%d): %s' % (name, rc, self.lib.remd_last_error(None).decode()))
+
+    def _f(self, f_k):
+        f = np.ascontiguousarray(f_k, dtype=np.float64)
+        if f.shape != (self.K,):
+            raise ValueError('f_k must have one entry per state')
+        return f
+
+    def log_denominator(self, f_k, want_log_den=True):
+        """(log_den [N] or None, phi): ln sum_k N_k exp(f_k - u_kn) per sample and the objective sum_n log_den - sum_k N_k f_k."""
+        f = self._f(f_k)
+        log_den = np.empty(self.N) if want_log_den else None
+        phi = C.c_double()
+        self._check(self.lib.remd_mbar_log_denominator(self.h, _dp(f), _dp(log_den), C.byref(phi)), 'remd_mbar_log_denominator')
+        return log_den, phi.value
+
+    def self_consistent(self, f_k):
+        """One application of eq. 11 to every state with the denominator at f_k: f_new [K], not shifted."""
+        f = self._f(f_k)
+        out = np.empty(self.K)
+        self._check(self.lib.remd_mbar_self_consistent(self.h, _dp(f), _dp(out)), 'remd_mbar_self_consistent')
+        return out
+
+    def newton_parts(self, f_k):
+        """(W_sum [K], W W^T [K][K], phi) at f_k; rows and columns of unsampled states are 0."""
+        f = self._f(f_k)
+        w, g, phi = np.empty(self.K), np.empty((self.K, self.K)), C.c_double()
+        self._check(self.lib.remd_mbar_newton_parts(self.h, _dp(f), _dp(w), _dp(g), C.byref(phi)), 'remd_mbar_newton_parts')
+        return w, g, phi.value
+
+    def gram(self, f_k, with_observable=False):
+        """W^T W over all K states, [K][K]; with_observable: ([2K][2K] with the u-weighted columns, log_cA [K])."""
+        f = self._f(f_k)
+        c = 2 * self.K if with_observable else self.K
+        g = np.empty((c, c))
+        log_cA = np.empty(self.K) if with_observable else None
+        self._check(self.lib.remd_mbar_gram(self.h, _dp(f), int(bool(with_observable)), _dp(g), _dp(log_cA)), 'remd_mbar_gram')
+        return (g, log_cA) if with_observable else g
+
+    def log_weights(self, f_k):
+        """log_W_nk [N][K] at f_k."""
+        f = self._f(f_k)
+        out = np.empty((self.N, self.K))
+        self._check(self.lib.remd_mbar_log_weights(self.h, _dp(f), _dp(out)), 'remd_mbar_log_weights')
+        return out
+
+    def chunks(self, C_columns):
+        """(column, row, Gram) samples per workgroup; the Gram chunk for a matrix of C_columns columns."""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self.lib.remd_mbar_chunks(self.h, int(C_columns), C.byref(a), C.byref(b), C.byref(c)), 'remd_mbar_chunks')
+        return a.value, b.value, c.value
+
+    def last_ms(self):
+        """Device milliseconds of the kernels of the last pass."""
+        ms = C.c_double()
+        self._check(self.lib.remd_mbar_last_ms(self.h, C.byref(ms)), 'remd_mbar_last_ms')
+        return ms.value
 
 
 class HipEngine:

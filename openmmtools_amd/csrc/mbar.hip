@@ -1,0 +1,508 @@
+// The passes of the MBAR estimator on the device (include/remd_hip_mbar.h).  All f64; u_kn stays [K][N], sample index fastest.
+//
+//   column pass  one thread per sample over the sampled states: log_den_n, and its sum per workgroup -> fixed-order second stage
+//   row pass     workgroups per (state, chunk of samples): a (max, scaled sum) pair each, merged per state in chunk order
+//   Gram pass    workgroups per (64 x 64 tile of the lower triangle, chunk of samples): the weights are recomputed from u, f and
+//                log_den into LDS, 16 samples at a time, and accumulated in a 4 x 4 register tile per thread with plain f64 FMAs;
+//                the per-chunk partials are summed in chunk order by a second stage
+//
+// No floating-point atomics: every sum has one fixed order, set by (K, N) alone.
+#include "remd_internal.h"
+#include "../../include/remd_hip_mbar.h"
+#include <cmath>
+#include <limits>
+
+#define MBAR_BLOCK       256
+#define MBAR_ROW_CHUNK   4096          // samples per workgroup of the row pass: 16 per thread
+#define MBAR_TILE        64            // columns of the Gram matrix per tile edge
+#define MBAR_TSTEP       16            // samples staged in LDS per step of the Gram pass
+#define MBAR_LDS_STRIDE  (MBAR_TILE + 2)
+#define MBAR_GRAM_MIN_CHUNK   256
+#define MBAR_GRAM_MAX_CHUNKS  256
+#define MBAR_GRAM_PARTIAL_CAP (int64_t(1) << 25)   // doubles of per-chunk partials at most (256 MiB)
+
+enum { MBAR_ROW_SC = 0, MBAR_ROW_LOGCA = 1, MBAR_ROW_WSUM = 2 };
+
+// np.max's NaN: it stays
+__device__ __forceinline__ double mbar_nanmax(double m, double a) { return (a > m || a != a) ? a : m; }
+// _logsumexp's guard: a non-finite maximum counts as 0
+__device__ __forceinline__ double mbar_guard(double m) { return isfinite(m) ? m : 0.0; }
+
+// both in one fixed order: lanes by __shfl_down, then the four waves in wave order; every thread gets the result
+__device__ __forceinline__ double mbar_block_sum(double v, double* sh)
+{
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+__device__ __forceinline__ double mbar_block_nanmax(double v, double* sh)
+{
+    for (int o = 32; o > 0; o >>= 1) v = mbar_nanmax(v, __shfl_down(v, o));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return mbar_nanmax(mbar_nanmax(mbar_nanmax(sh[0], sh[1]), sh[2]), sh[3]);
+}
+
+// ---- column pass ----------------------------------------------------------------------------------------------------------------
+// fs[Ks], nk[Ks], srow[Ks]: f_k, N_k and the row of u of the sampled states
+__global__ __launch_bounds__(MBAR_BLOCK) void mbar_logden_kernel(const double* __restrict__ u, const double* __restrict__ fs,
+                                                                 const double* __restrict__ nk, const int* __restrict__ srow, int Ks,
+                                                                 int64_t N, double* __restrict__ log_den, double* __restrict__ partial)
+{
+    __shared__ double sh[4];
+    const int64_t n = (int64_t)blockIdx.x * MBAR_BLOCK + threadIdx.x;
+    double ld = 0.0;
+    if (n < N) {
+        double m = -INFINITY;
+        for (int j = 0; j < Ks; j++) m = mbar_nanmax(m, fs[j] - u[(int64_t)srow[j] * N + n]);
+        m = mbar_guard(m);
+        double s = 0.0;
+        for (int j = 0; j < Ks; j++) s += nk[j] * exp((fs[j] - u[(int64_t)srow[j] * N + n]) - m);
+        ld = log(s) + m;
+        log_den[n] = ld;
+    }
+    const double t = mbar_block_sum(ld, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = t;
+}
+
+// out[0] = the sum of partial[n]: thread t takes t, t + 256, ... in order, then the block sum
+__global__ __launch_bounds__(MBAR_BLOCK) void mbar_sum_kernel(const double* __restrict__ partial, int64_t n, double* __restrict__ out)
+{
+    __shared__ double sh[4];
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += MBAR_BLOCK) s += partial[i];
+    const double t = mbar_block_sum(s, sh);
+    if (threadIdx.x == 0) out[0] = t;
+}
+
+// ---- row pass -------------------------------------------------------------------------------------------------------------------
+template <int MODE>
+__device__ __forceinline__ double mbar_row_term(double uu, double ld, double fk, double shift)
+{
+    if (MODE == MBAR_ROW_SC) return -uu - ld;
+    const double lw = (fk - uu) - ld;
+    if (MODE == MBAR_ROW_LOGCA) return lw + log(uu - shift);
+    return lw;
+}
+
+// grid (chunks, K): pairs[k * chunks + c] = (max of the terms, sum exp(term - guarded max)); MBAR_ROW_WSUM: (0, sum exp(term))
+template <int MODE>
+__global__ __launch_bounds__(MBAR_BLOCK) void mbar_row_kernel(const double* __restrict__ u, const double* __restrict__ log_den,
+                                                              const double* __restrict__ f, int64_t N, double shift,
+                                                              double2* __restrict__ pairs)
+{
+    __shared__ double sh[4];
+    const int k = blockIdx.y;
+    const int64_t n0 = (int64_t)blockIdx.x * MBAR_ROW_CHUNK;
+    const int64_t n1 = n0 + MBAR_ROW_CHUNK < N ? n0 + MBAR_ROW_CHUNK : N;
+    const double* __restrict__ uk = u + (int64_t)k * N;
+    const double fk = f[k];
+    double mraw = 0.0, m = 0.0;
+    if (MODE != MBAR_ROW_WSUM) {
+        double mt = -INFINITY;
+        for (int64_t n = n0 + threadIdx.x; n < n1; n += MBAR_BLOCK) mt = mbar_nanmax(mt, mbar_row_term<MODE>(uk[n], log_den[n], fk, shift));
+        mraw = mbar_block_nanmax(mt, sh);
+        m = mbar_guard(mraw);
+    }
+    double s = 0.0;
+    for (int64_t n = n0 + threadIdx.x; n < n1; n += MBAR_BLOCK) s += exp(mbar_row_term<MODE>(uk[n], log_den[n], fk, shift) - m);
+    const double t = mbar_block_sum(s, sh);
+    if (threadIdx.x == 0) pairs[(int64_t)k * gridDim.x + blockIdx.x] = make_double2(mraw, t);
+}
+
+// one thread per state merges its pairs in chunk order.  as_log: out = sign * (ln S + M), else out = S
+__global__ void mbar_row_merge_kernel(const double2* __restrict__ pairs, int K, int chunks, int as_log, double sign, double* __restrict__ out)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= K) return;
+    const double2* p = pairs + (int64_t)k * chunks;
+    double M = -INFINITY;
+    for (int c = 0; c < chunks; c++) M = mbar_nanmax(M, p[c].x);
+    M = mbar_guard(M);
+    double S = 0.0;
+    for (int c = 0; c < chunks; c++)
+        if (p[c].y != 0.0) S += p[c].y * exp(mbar_guard(p[c].x) - M);      // (an empty chunk's scale may overflow: it adds nothing)
+    out[k] = as_log ? sign * (log(S) + M) : S;
+}
+
+// ---- Gram pass ------------------------------------------------------------------------------------------------------------------
+struct mbar_gram_args {
+    const double* u; const double* log_den; const double* f; const double* log_cA;
+    const int* col_state;        // [C] the state of a column
+    const int2* tiles;           // (ti, tj), ti >= tj
+    int C, n_plain;              // columns >= n_plain carry the observable
+    int64_t N, chunk;
+    double shift;
+    double* partial;             // [chunks][C][C], the lower triangle's tiles
+};
+
+__device__ __forceinline__ double mbar_column_value(const mbar_gram_args& a, int c, int64_t n, int64_t n1, double ld)
+{
+    if (c >= a.C || n >= n1) return 0.0;
+    const int k = a.col_state[c];
+    const double uu = a.u[(int64_t)k * a.N + n];
+    double lw = (a.f[k] - uu) - ld;
+    if (c >= a.n_plain) lw = (lw + log(uu - a.shift)) - a.log_cA[k];
+    return exp(lw);
+}
+
+__global__ __launch_bounds__(MBAR_BLOCK) void mbar_gram_kernel(mbar_gram_args a)
+{
+    __shared__ double As[MBAR_TSTEP][MBAR_LDS_STRIDE];
+    __shared__ double Bs[MBAR_TSTEP][MBAR_LDS_STRIDE];
+    const int2 tile = a.tiles[blockIdx.x];
+    const int i0 = tile.x * MBAR_TILE, j0 = tile.y * MBAR_TILE;
+    const int64_t n0 = (int64_t)blockIdx.y * a.chunk;
+    const int64_t n1 = n0 + a.chunk < a.N ? n0 + a.chunk : a.N;
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const int fs = t & (MBAR_TSTEP - 1), fc = t >> 4;             // the sample and the first column this thread stages
+    const bool diagonal = i0 == j0;                               // both operands are the same columns: staged once
+    const double (*Bp)[MBAR_LDS_STRIDE] = diagonal ? As : Bs;
+    double acc[4][4];
+    for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) acc[i][j] = 0.0;
+    for (int64_t nb = n0; nb < n1; nb += MBAR_TSTEP) {
+        const int64_t n = nb + fs;
+        const double ld = n < n1 ? a.log_den[n] : 0.0;
+        #pragma unroll
+        for (int p = 0; p < 4; p++) {
+            const int cl = fc + 16 * p;
+            As[fs][cl] = mbar_column_value(a, i0 + cl, n, n1, ld);
+            if (!diagonal) Bs[fs][cl] = mbar_column_value(a, j0 + cl, n, n1, ld);
+        }
+        __syncthreads();
+        #pragma unroll
+        for (int s = 0; s < MBAR_TSTEP; s++) {
+            double av[4], bv[4];
+            #pragma unroll
+            for (int i = 0; i < 4; i++) { av[i] = As[s][ty * 4 + i]; bv[i] = Bp[s][tx * 4 + i]; }
+            #pragma unroll
+            for (int i = 0; i < 4; i++)
+                #pragma unroll
+                for (int j = 0; j < 4; j++) acc[i][j] = fma(av[i], bv[j], acc[i][j]);
+        }
+        __syncthreads();
+    }
+    double* out = a.partial + (int64_t)blockIdx.y * a.C * a.C;
+    for (int i = 0; i < 4; i++) {
+        const int gi = i0 + ty * 4 + i;
+        if (gi >= a.C) continue;
+        for (int j = 0; j < 4; j++) {
+            const int gj = j0 + tx * 4 + j;
+            if (gj < a.C) out[(int64_t)gi * a.C + gj] = acc[i][j];
+        }
+    }
+}
+
+// one thread per entry of the lower triangle sums the partials in chunk order and writes both halves
+__global__ __launch_bounds__(MBAR_BLOCK) void mbar_gram_sum_kernel(const double* __restrict__ partial, int C, int chunks, double* __restrict__ gram)
+{
+    const int64_t idx = (int64_t)blockIdx.x * MBAR_BLOCK + threadIdx.x;
+    if (idx >= (int64_t)C * C) return;
+    const int i = (int)(idx / C), j = (int)(idx % C);
+    if (j > i) return;
+    double s = 0.0;
+    for (int c = 0; c < chunks; c++) s += partial[(int64_t)c * C * C + idx];
+    gram[(int64_t)i * C + j] = s;
+    gram[(int64_t)j * C + i] = s;
+}
+
+// ---- weights --------------------------------------------------------------------------------------------------------------------
+// 16 x 16 tiles through LDS: u is read along the samples, log_W_nk[N][K] written along the states
+__global__ __launch_bounds__(MBAR_BLOCK) void mbar_log_weights_kernel(const double* __restrict__ u, const double* __restrict__ log_den,
+                                                                      const double* __restrict__ f, int K, int64_t N, double* __restrict__ out)
+{
+    __shared__ double tile[16][17];
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const int64_t nb = (int64_t)blockIdx.x * 16;
+    const int kb = blockIdx.y * 16;
+    {
+        const int64_t n = nb + tx; const int k = kb + ty;
+        tile[ty][tx] = (n < N && k < K) ? (f[k] - u[(int64_t)k * N + n]) - log_den[n] : 0.0;
+    }
+    __syncthreads();
+    {
+        const int64_t n = nb + ty; const int k = kb + tx;
+        if (n < N && k < K) out[n * K + k] = tile[tx][ty];
+    }
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------------------
+struct remd_mbar_ctx {
+    int device = 0, K = 0, Ks = 0;
+    int64_t N = 0;
+    double shift = 0.0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool timed = false;                     // a pass has run: ev0 and ev1 hold its kernels
+    std::vector<double> nk_all;             // [K]
+    std::vector<int> srow;                  // [Ks]
+    dev_array<double> u, nk, fs, f, log_den, col_partial, scalar, row_out, log_cA, gram, gram_partial, weights;
+    dev_array<int> d_srow, col_state;
+    dev_array<int2> tiles;
+    dev_array<double2> pairs;
+    ~remd_mbar_ctx()
+    {
+        hipSetDevice(device);
+        if (stream) { hipStreamSynchronize(stream); hipStreamDestroy(stream); }
+        if (ev0) hipEventDestroy(ev0);
+        if (ev1) hipEventDestroy(ev1);
+    }
+};
+
+#define MBAR_CHECK(expr) do { const hipError_t _e = (expr); if (_e != hipSuccess) return remd_hip_fail(nullptr, #expr, _e); } while (0)
+
+static int64_t mbar_gram_chunk(int64_t N, int C)
+{
+    int64_t max_chunks = MBAR_GRAM_PARTIAL_CAP / ((int64_t)C * C);
+    max_chunks = std::max<int64_t>(1, std::min<int64_t>(MBAR_GRAM_MAX_CHUNKS, max_chunks));
+    int64_t chunk = (N + max_chunks - 1) / max_chunks;
+    chunk = (chunk + MBAR_TSTEP - 1) / MBAR_TSTEP * MBAR_TSTEP;
+    return std::max<int64_t>(MBAR_GRAM_MIN_CHUNK, chunk);
+}
+
+// every pointer of a call is checked before anything is copied; `out` and `out2` are the outputs that may not be NULL
+static int mbar_begin(remd_mbar m, const char* who, const double* f_k, const void* out = (const void*)1, const void* out2 = (const void*)1)
+{
+    if (!m) return remd_fail(nullptr, -1, std::string(who) + ": the problem is NULL");
+    if (!f_k) return remd_fail(nullptr, -1, std::string(who) + ": f_k is NULL");
+    if (!out || !out2) return remd_fail(nullptr, -1, std::string(who) + ": an output array is NULL");
+    MBAR_CHECK(hipSetDevice(m->device));
+    std::vector<double> fs(m->Ks);
+    for (int j = 0; j < m->Ks; j++) fs[j] = f_k[m->srow[j]];
+    MBAR_CHECK(hipMemcpyAsync(m->f, f_k, sizeof(double) * m->K, hipMemcpyHostToDevice, m->stream));
+    MBAR_CHECK(hipMemcpyAsync(m->fs, fs.data(), sizeof(double) * m->Ks, hipMemcpyHostToDevice, m->stream));
+    MBAR_CHECK(hipStreamSynchronize(m->stream));            // (fs is a local)
+    MBAR_CHECK(hipEventRecord(m->ev0, m->stream));
+    return 0;
+}
+
+static int mbar_end(remd_mbar m)
+{
+    MBAR_CHECK(hipEventRecord(m->ev1, m->stream));
+    MBAR_CHECK(hipStreamSynchronize(m->stream));
+    m->timed = true;
+    return 0;
+}
+
+// log_den on the device, its sum in scalar[0]
+static int mbar_column_pass(remd_mbar m)
+{
+    const int64_t blocks = (m->N + MBAR_BLOCK - 1) / MBAR_BLOCK;
+    hipLaunchKernelGGL(mbar_logden_kernel, dim3((unsigned)blocks), dim3(MBAR_BLOCK), 0, m->stream, m->u.get(), m->fs.get(), m->nk.get(),
+                       m->d_srow.get(), m->Ks, m->N, m->log_den.get(), m->col_partial.get());
+    hipLaunchKernelGGL(mbar_sum_kernel, dim3(1), dim3(MBAR_BLOCK), 0, m->stream, m->col_partial.get(), blocks, m->scalar.get());
+    MBAR_CHECK(hipGetLastError());
+    return 0;
+}
+
+static int mbar_phi(remd_mbar m, const double* f_k, double* phi)
+{
+    double sum = 0.0;
+    MBAR_CHECK(hipMemcpy(&sum, m->scalar, sizeof(double), hipMemcpyDeviceToHost));
+    double dot = 0.0;
+    for (int j = 0; j < m->Ks; j++) dot += m->nk_all[m->srow[j]] * f_k[m->srow[j]];
+    *phi = sum - dot;
+    return 0;
+}
+
+// the row pass over all K states into dst[K] (device)
+static int mbar_row_pass(remd_mbar m, int mode, double* dst)
+{
+    const int chunks = (int)((m->N + MBAR_ROW_CHUNK - 1) / MBAR_ROW_CHUNK);
+    const dim3 grid((unsigned)chunks, (unsigned)m->K);
+    if (mode == MBAR_ROW_SC)
+        hipLaunchKernelGGL(mbar_row_kernel<MBAR_ROW_SC>, grid, dim3(MBAR_BLOCK), 0, m->stream, m->u.get(), m->log_den.get(), m->f.get(), m->N, m->shift, m->pairs.get());
+    else if (mode == MBAR_ROW_LOGCA)
+        hipLaunchKernelGGL(mbar_row_kernel<MBAR_ROW_LOGCA>, grid, dim3(MBAR_BLOCK), 0, m->stream, m->u.get(), m->log_den.get(), m->f.get(), m->N, m->shift, m->pairs.get());
+    else
+        hipLaunchKernelGGL(mbar_row_kernel<MBAR_ROW_WSUM>, grid, dim3(MBAR_BLOCK), 0, m->stream, m->u.get(), m->log_den.get(), m->f.get(), m->N, m->shift, m->pairs.get());
+    hipLaunchKernelGGL(mbar_row_merge_kernel, dim3((unsigned)((m->K + 63) / 64)), dim3(64), 0, m->stream, m->pairs.get(), m->K, chunks,
+                       mode == MBAR_ROW_WSUM ? 0 : 1, mode == MBAR_ROW_SC ? -1.0 : 1.0, dst);
+    MBAR_CHECK(hipGetLastError());
+    return 0;
+}
+
+// the Gram matrix of the columns `states` (the first n_plain plain weights, the rest observable-weighted) into m->gram [C][C]
+static int mbar_gram_pass(remd_mbar m, const std::vector<int>& states, int n_plain)
+{
+    const int C = (int)states.size();
+    const int T = (C + MBAR_TILE - 1) / MBAR_TILE;
+    std::vector<int2> tiles;
+    for (int ti = 0; ti < T; ti++) for (int tj = 0; tj <= ti; tj++) tiles.push_back(make_int2(ti, tj));
+    const int64_t chunk = mbar_gram_chunk(m->N, C);
+    const int chunks = (int)((m->N + chunk - 1) / chunk);
+    REMD_TRY(m->col_state.grow(nullptr, C));
+    REMD_TRY(m->tiles.grow(nullptr, tiles.size()));
+    REMD_TRY(m->gram.grow(nullptr, (size_t)C * C));
+    REMD_TRY(m->gram_partial.grow(nullptr, (size_t)chunks * C * C));
+    MBAR_CHECK(hipMemcpyAsync(m->col_state, states.data(), sizeof(int) * C, hipMemcpyHostToDevice, m->stream));
+    MBAR_CHECK(hipMemcpyAsync(m->tiles, tiles.data(), sizeof(int2) * tiles.size(), hipMemcpyHostToDevice, m->stream));
+    MBAR_CHECK(hipStreamSynchronize(m->stream));            // (both sources are locals)
+    mbar_gram_args a;
+    a.u = m->u; a.log_den = m->log_den; a.f = m->f; a.log_cA = m->log_cA; a.col_state = m->col_state; a.tiles = m->tiles;
+    a.C = C; a.n_plain = n_plain; a.N = m->N; a.chunk = chunk; a.shift = m->shift; a.partial = m->gram_partial;
+    hipLaunchKernelGGL(mbar_gram_kernel, dim3((unsigned)tiles.size(), (unsigned)chunks), dim3(MBAR_BLOCK), 0, m->stream, a);
+    const int64_t entries = (int64_t)C * C;
+    hipLaunchKernelGGL(mbar_gram_sum_kernel, dim3((unsigned)((entries + MBAR_BLOCK - 1) / MBAR_BLOCK)), dim3(MBAR_BLOCK), 0, m->stream,
+                       m->gram_partial.get(), C, chunks, m->gram.get());
+    MBAR_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" {
+
+int remd_mbar_create(int device, int K, int64_t N, const double* u_kn, const int64_t* N_k, remd_mbar* out)
+{
+    if (!out) return remd_fail(nullptr, -1, "remd_mbar_create: out is NULL");
+    *out = nullptr;
+    if (K < 1 || N < 1) return remd_fail(nullptr, -1, "remd_mbar_create: K and N must be at least 1");
+    if (K > REMD_MBAR_MAX_STATES)
+        return remd_fail(nullptr, -1, "remd_mbar_create: K = " + std::to_string(K) + " exceeds REMD_MBAR_MAX_STATES = " + std::to_string(REMD_MBAR_MAX_STATES));
+    if (!u_kn || !N_k) return remd_fail(nullptr, -1, "remd_mbar_create: u_kn or N_k is NULL");
+    int64_t total = 0;
+    for (int k = 0; k < K; k++) {
+        if (N_k[k] < 0 || N_k[k] > N) return remd_fail(nullptr, -1, "remd_mbar_create: N_k[" + std::to_string(k) + "] is negative or above N");
+        total += N_k[k];
+    }
+    if (total != N) return remd_fail(nullptr, -1, "remd_mbar_create: sum N_k = " + std::to_string(total) + " is not N = " + std::to_string(N));
+    double umin = std::numeric_limits<double>::infinity();
+    bool has_nan = false;
+    for (int k = 0; k < K; k++) {
+        const double* row = u_kn + (int64_t)k * N;
+        for (int64_t n = 0; n < N; n++) {
+            if (N_k[k] > 0 && !std::isfinite(row[n]))
+                return remd_fail(nullptr, -1, "remd_mbar_create: non-finite u_kn in sampled state " + std::to_string(k));
+            if (row[n] != row[n]) has_nan = true;
+            if (row[n] < umin) umin = row[n];
+        }
+    }
+    int n = 0;
+    hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess || n == 0)
+        return remd_fail(nullptr, -2, std::string("remd_mbar_create: no HIP device available (") + hipGetErrorString(e) + ")");
+    if (device < 0 || device >= n) return remd_fail(nullptr, -1, "remd_mbar_create: bad device index");
+    MBAR_CHECK(hipSetDevice(device));
+    std::unique_ptr<remd_mbar_ctx> m(new remd_mbar_ctx());
+    m->device = device; m->K = K; m->N = N;
+    m->shift = (has_nan ? std::numeric_limits<double>::quiet_NaN() : umin) - 1.0;      // np.min keeps a NaN
+    std::vector<double> nk;
+    m->nk_all.resize(K);
+    for (int k = 0; k < K; k++) {
+        m->nk_all[k] = (double)N_k[k];
+        if (N_k[k] > 0) { m->srow.push_back(k); nk.push_back((double)N_k[k]); }
+    }
+    m->Ks = (int)m->srow.size();
+    MBAR_CHECK(hipStreamCreate(&m->stream));
+    MBAR_CHECK(hipEventCreate(&m->ev0));
+    MBAR_CHECK(hipEventCreate(&m->ev1));
+    REMD_TRY(m->u.alloc(nullptr, (size_t)K * N));
+    MBAR_CHECK(hipMemcpy(m->u, u_kn, sizeof(double) * (size_t)K * N, hipMemcpyHostToDevice));
+    REMD_TRY(m->nk.upload(nullptr, nk));
+    REMD_TRY(m->d_srow.upload(nullptr, m->srow));
+    REMD_TRY(m->fs.alloc(nullptr, m->Ks));
+    REMD_TRY(m->f.alloc(nullptr, K));
+    REMD_TRY(m->log_den.alloc(nullptr, N));
+    REMD_TRY(m->col_partial.alloc(nullptr, (size_t)((N + MBAR_BLOCK - 1) / MBAR_BLOCK)));
+    REMD_TRY(m->scalar.alloc(nullptr, 1));
+    REMD_TRY(m->row_out.alloc(nullptr, K));
+    REMD_TRY(m->log_cA.alloc(nullptr, K));
+    REMD_TRY(m->pairs.alloc(nullptr, (size_t)K * (size_t)((N + MBAR_ROW_CHUNK - 1) / MBAR_ROW_CHUNK)));
+    *out = m.release();
+    return 0;
+}
+
+void remd_mbar_destroy(remd_mbar m) { delete m; }
+
+int remd_mbar_log_denominator(remd_mbar m, const double* f_k, double* log_den, double* phi)
+{
+    REMD_TRY(mbar_begin(m, "remd_mbar_log_denominator", f_k));
+    REMD_TRY(mbar_column_pass(m));
+    REMD_TRY(mbar_end(m));
+    if (log_den) MBAR_CHECK(hipMemcpy(log_den, m->log_den, sizeof(double) * m->N, hipMemcpyDeviceToHost));
+    if (phi) REMD_TRY(mbar_phi(m, f_k, phi));
+    return 0;
+}
+
+int remd_mbar_self_consistent(remd_mbar m, const double* f_k, double* f_new)
+{
+    REMD_TRY(mbar_begin(m, "remd_mbar_self_consistent", f_k, f_new));
+    REMD_TRY(mbar_column_pass(m));
+    REMD_TRY(mbar_row_pass(m, MBAR_ROW_SC, m->row_out));
+    REMD_TRY(mbar_end(m));
+    MBAR_CHECK(hipMemcpy(f_new, m->row_out, sizeof(double) * m->K, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int remd_mbar_newton_parts(remd_mbar m, const double* f_k, double* W_sum, double* gram, double* phi)
+{
+    REMD_TRY(mbar_begin(m, "remd_mbar_newton_parts", f_k, W_sum, gram));
+    REMD_TRY(mbar_column_pass(m));
+    REMD_TRY(mbar_row_pass(m, MBAR_ROW_WSUM, m->row_out));
+    REMD_TRY(mbar_gram_pass(m, m->srow, m->Ks));
+    REMD_TRY(mbar_end(m));
+    const int K = m->K, Ks = m->Ks;
+    std::vector<double> ws(K), g((size_t)Ks * Ks);
+    MBAR_CHECK(hipMemcpy(ws.data(), m->row_out, sizeof(double) * K, hipMemcpyDeviceToHost));
+    MBAR_CHECK(hipMemcpy(g.data(), m->gram, sizeof(double) * g.size(), hipMemcpyDeviceToHost));
+    for (int k = 0; k < K; k++) W_sum[k] = 0.0;
+    for (int64_t i = 0; i < (int64_t)K * K; i++) gram[i] = 0.0;
+    for (int a = 0; a < Ks; a++) {
+        W_sum[m->srow[a]] = ws[m->srow[a]];
+        for (int b = 0; b < Ks; b++) gram[(int64_t)m->srow[a] * K + m->srow[b]] = g[(size_t)a * Ks + b];
+    }
+    if (phi) REMD_TRY(mbar_phi(m, f_k, phi));
+    return 0;
+}
+
+int remd_mbar_gram(remd_mbar m, const double* f_k, int with_observable, double* gram, double* log_cA)
+{
+    REMD_TRY(mbar_begin(m, "remd_mbar_gram", f_k, gram));
+    const int K = m->K, C = with_observable ? 2 * K : K;
+    std::vector<int> states(C);
+    for (int c = 0; c < C; c++) states[c] = c % K;
+    REMD_TRY(mbar_column_pass(m));
+    if (with_observable) REMD_TRY(mbar_row_pass(m, MBAR_ROW_LOGCA, m->log_cA));
+    REMD_TRY(mbar_gram_pass(m, states, K));
+    REMD_TRY(mbar_end(m));
+    MBAR_CHECK(hipMemcpy(gram, m->gram, sizeof(double) * (size_t)C * C, hipMemcpyDeviceToHost));
+    if (with_observable && log_cA) MBAR_CHECK(hipMemcpy(log_cA, m->log_cA, sizeof(double) * K, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int remd_mbar_log_weights(remd_mbar m, const double* f_k, double* log_W_nk)
+{
+    REMD_TRY(mbar_begin(m, "remd_mbar_log_weights", f_k, log_W_nk));
+    REMD_TRY(m->weights.grow(nullptr, (size_t)m->N * m->K));
+    REMD_TRY(mbar_column_pass(m));
+    hipLaunchKernelGGL(mbar_log_weights_kernel, dim3((unsigned)((m->N + 15) / 16), (unsigned)((m->K + 15) / 16)), dim3(MBAR_BLOCK), 0, m->stream,
+                       m->u.get(), m->log_den.get(), m->f.get(), m->K, m->N, m->weights.get());
+    MBAR_CHECK(hipGetLastError());
+    REMD_TRY(mbar_end(m));
+    MBAR_CHECK(hipMemcpy(log_W_nk, m->weights, sizeof(double) * (size_t)m->N * m->K, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int remd_mbar_chunks(remd_mbar m, int C, int64_t* column_chunk, int64_t* row_chunk, int64_t* gram_chunk)
+{
+    if (!m || C < 1) return remd_fail(nullptr, -1, "remd_mbar_chunks: the problem is NULL or C < 1");
+    if (column_chunk) *column_chunk = MBAR_BLOCK;
+    if (row_chunk) *row_chunk = MBAR_ROW_CHUNK;
+    if (gram_chunk) *gram_chunk = mbar_gram_chunk(m->N, C);
+    return 0;
+}
+
+int remd_mbar_last_ms(remd_mbar m, double* ms)
+{
+    if (!m || !ms) return remd_fail(nullptr, -1, "remd_mbar_last_ms: the problem or ms is NULL");
+    if (!m->timed) return remd_fail(nullptr, -1, "remd_mbar_last_ms: no pass has run on this problem yet");
+    MBAR_CHECK(hipSetDevice(m->device));
+    float t = 0.0f;
+    MBAR_CHECK(hipEventElapsedTime(&t, m->ev0, m->ev1));
+    *ms = t;
+    return 0;
+}
+
+}

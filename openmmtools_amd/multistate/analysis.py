@@ -183,9 +183,18 @@ class MBAR:
     ``u_kn[k, n]`` is the reduced potential of sample ``n`` evaluated in state ``k``; ``N_k[k]`` the number of samples
     drawn from state ``k`` (0 for unsampled states).  Solves  f_i = -ln sum_n exp(-u_in) / sum_k N_k exp(f_k - u_kn)
     (eq. 11) with f_0 = 0.
+
+    ``solver='numpy'`` (the default) does every pass over ``u_kn`` on the host; ``solver='device'`` does them on the GPU
+    (include/remd_hip_mbar.h: the same sweeps, Newton iteration, backtracking rule and convergence test, with the K x K algebra
+    still on the host).  ``device`` and ``lib_path`` choose the GPU and the engine library of the device solver.
     """
 
-    def __init__(self, u_kn, N_k, initial_f_k=None, relative_tolerance=1.0e-12, maximum_iterations=10000):
+    def __init__(self, u_kn, N_k, initial_f_k=None, relative_tolerance=1.0e-12, maximum_iterations=10000, solver='numpy',
+                 device=0, lib_path=None):
+        if solver not in ('numpy', 'device'):
+            raise ValueError("solver must be 'numpy' or 'device', not %r" % (solver,))
+        self.solver = solver
+        self._dev = None
         self.u_kn = np.array(u_kn, dtype=np.float64)
         self.N_k = np.array(N_k, dtype=np.int64)
         K, N = self.u_kn.shape
@@ -195,7 +204,12 @@ class MBAR:
             raise ParameterError('non-finite reduced potentials in a sampled state')
         self.K, self.N = K, N
         f = np.zeros(K) if initial_f_k is None else np.array(initial_f_k, dtype=np.float64) - float(np.asarray(initial_f_k)[0])
-        self.f_k = self._solve(f, relative_tolerance, maximum_iterations)
+        if solver == 'device':
+            from .._engine import DeviceMBAR
+            self._dev = DeviceMBAR(self.u_kn, self.N_k, device=device, lib_path=lib_path)
+            self.f_k = self._solve_device(f, relative_tolerance, maximum_iterations)
+        else:
+            self.f_k = self._solve(f, relative_tolerance, maximum_iterations)
         self._log_W = None
 
     # log of the mixture denominator per sample: ln sum_k N_k exp(f_k - u_kn)
@@ -260,8 +274,62 @@ class MBAR:
             out[uns] = -_logsumexp(-self.u_kn[uns] - log_den[None, :], axis=1)
         return out - out[0]
 
+    def _solve_device(self, f_k, rtol, maxiter):
+        """_solve with the passes over u_kn on the device: the same algorithm, line by line."""
+        dev = self._dev
+        s = np.flatnonzero(self.N_k > 0)
+        if s.size == 0:
+            raise ParameterError('no sampled state')
+        Nk = self.N_k[s].astype(np.float64)
+        f = f_k[s] - f_k[s][0]
+
+        def full(f):                                                      # the device takes one f per state; the unsampled do not enter
+            out = np.zeros(self.K)
+            out[s] = f
+            return out
+
+        for _ in range(5):
+            f_new = dev.self_consistent(full(f))[s]
+            f = f_new - f_new[0]
+        for _ in range(maxiter):
+            W_sum, gram, phi0 = dev.newton_parts(full(f))
+            W_sum, WWt = W_sum[s], gram[np.ix_(s, s)]
+            g = Nk * (W_sum - 1.0)
+            H = np.diag(Nk * W_sum) - (Nk[:, None] * Nk[None, :]) * WWt
+            if s.size > 1:
+                try:
+                    step = np.zeros_like(f)
+                    step[1:] = np.linalg.solve(H[1:, 1:], g[1:])
+                except np.linalg.LinAlgError:
+                    step = np.zeros_like(f)
+                    step[1:] = np.linalg.lstsq(H[1:, 1:], g[1:], rcond=None)[0]
+            else:
+                step = np.zeros_like(f)
+            scale = 1.0
+            while True:                                                   # backtrack: the objective must not increase
+                f_try = f - scale * step
+                phi = dev.log_denominator(full(f_try), want_log_den=False)[1]
+                if phi <= phi0 + 1e-12 * abs(phi0) or scale < 1e-6:
+                    break
+                scale *= 0.5
+            delta = np.max(np.abs(f_try - f))
+            f = f_try
+            if delta <= rtol * max(1.0, np.max(np.abs(f))):
+                break
+        else:
+            raise ParameterError('MBAR did not converge')
+        if not np.all(np.isfinite(f)):
+            raise ParameterError('MBAR produced non-finite free energies')
+        out = full(f)
+        uns = np.flatnonzero(self.N_k == 0)
+        if uns.size:
+            out[uns] = dev.self_consistent(out)[uns]
+        return out - out[0]
+
     @property
     def log_W_nk(self):
+        if self._log_W is None and self._dev is not None:
+            self._log_W = self._dev.log_weights(self.f_k)
         if self._log_W is None:
             log_den = self._log_denominator(self.f_k)
             self._log_W = (self.f_k[:, None] - self.u_kn - log_den[None, :]).T          # [N, K]
@@ -272,14 +340,20 @@ class MBAR:
         """Asymptotic covariance (eq. 8), SVD form:  Theta = V S (I - S V^T N V S)^+ S V^T  with W = U S V^T — only
         the Gram matrix W^T W is needed.  ``W`` may carry extra columns with N_k = 0 (unsampled or observable-weighted
         states)."""
-        G = W.T @ W
+        return MBAR._theta_of_gram(W.T @ W, N_k)
+
+    @staticmethod
+    def _theta_of_gram(G, N_k):
+        """_theta_of from the Gram matrix G = W^T W."""
         evals, V = np.linalg.eigh(G)
         evals = np.clip(evals, 0.0, None)
         S = np.sqrt(evals)
-        M = np.eye(W.shape[1]) - (S[:, None] * (V.T @ (np.asarray(N_k, dtype=np.float64)[:, None] * V))) * S[None, :]
+        M = np.eye(G.shape[0]) - (S[:, None] * (V.T @ (np.asarray(N_k, dtype=np.float64)[:, None] * V))) * S[None, :]
         return (V * S[None, :]) @ np.linalg.pinv(M, rcond=1e-10) @ (V * S[None, :]).T
 
     def _theta(self):
+        if self._dev is not None:
+            return self._theta_of_gram(self._dev.gram(self.f_k), self.N_k)
         return self._theta_of(np.exp(self.log_W_nk), self.N_k)
 
     def compute_entropy_and_enthalpy(self):
@@ -289,14 +363,19 @@ class MBAR:
         of the augmented set of free energies).  Returns a dict with Delta_f, dDelta_f, Delta_u, dDelta_u, Delta_s,
         dDelta_s; Delta_x[i, j] = x_j - x_i."""
         K = self.K
-        log_W = self.log_W_nk                                         # [N, K]
-        u = self.u_kn.T                                               # [N, K]
-        shift = u.min() - 1.0                                         # observable made positive for the logarithm
-        A = u - shift
-        log_WA_raw = log_W + np.log(A)
-        log_cA = _logsumexp(log_WA_raw, axis=0)                       # ln <A>_i (shifted)
-        W_aug = np.concatenate([np.exp(log_W), np.exp(log_WA_raw - log_cA[None, :])], axis=1)
-        Theta = self._theta_of(W_aug, np.concatenate([self.N_k, np.zeros(K, dtype=np.int64)]))
+        if self._dev is not None:
+            shift = self.u_kn.min() - 1.0
+            G, log_cA = self._dev.gram(self.f_k, with_observable=True)
+            Theta = self._theta_of_gram(G, np.concatenate([self.N_k, np.zeros(K, dtype=np.int64)]))
+        else:
+            log_W = self.log_W_nk                                         # [N, K]
+            u = self.u_kn.T                                               # [N, K]
+            shift = u.min() - 1.0                                         # observable made positive for the logarithm
+            A = u - shift
+            log_WA_raw = log_W + np.log(A)
+            log_cA = _logsumexp(log_WA_raw, axis=0)                       # ln <A>_i (shifted)
+            W_aug = np.concatenate([np.exp(log_W), np.exp(log_WA_raw - log_cA[None, :])], axis=1)
+            Theta = self._theta_of(W_aug, np.concatenate([self.N_k, np.zeros(K, dtype=np.int64)]))
         A_i = np.exp(log_cA)
         u_i = A_i + shift
         # x = (f_0..f_{K-1}, u_0..u_{K-1}) is linear in the augmented free energies: du_i = <A>_i (df_i - df_{K+i})
@@ -551,7 +630,8 @@ class MultiStateSamplerAnalyzer:
     def mbar(self):
         if self._mbar is None:
             u_ln, N_l = self._compute_mbar_decorrelated_energies()
-            self._mbar = MBAR(u_ln, N_l, initial_f_k=self._kwargs.get('initial_f_k'))
+            extra = {k: self._kwargs[k] for k in ('solver', 'device', 'lib_path') if k in self._kwargs}
+            self._mbar = MBAR(u_ln, N_l, initial_f_k=self._kwargs.get('initial_f_k'), **extra)
         return self._mbar
 
     MixingStatistics = collections.namedtuple('MixingStatistics', ['transition_matrix', 'eigenvalues', 'statistical_inefficiency'])

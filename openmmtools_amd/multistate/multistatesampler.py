@@ -45,7 +45,7 @@ def restraint_lambdas(system, parameters, states):
 class MultiStateSampler:
     def __init__(self, mcmc_moves=None, number_of_iterations=1, locality=None,
                  online_analysis_interval=200, online_analysis_target_error=0.0,
-                 online_analysis_minimum_iterations=200, engine=None, seed=0xC0FFEE, comm=None):
+                 online_analysis_minimum_iterations=200, engine=None, seed=0xC0FFEE, comm=None, online_analysis_solver='numpy'):
         if locality is not None and ((type(locality) != int) or (locality <= 0)):      # :504-508
             raise ValueError('locality must be an int > 0')
         # multistatesampler.py:478-501
@@ -56,6 +56,8 @@ class MultiStateSampler:
                 raise ValueError('online_analysis_target_error must be a float >= 0')
             if type(online_analysis_minimum_iterations) is not int or online_analysis_minimum_iterations < 0:
                 raise ValueError('online_analysis_minimum_iterations must be an integer >= 0')
+        if online_analysis_solver not in ('numpy', 'device'):
+            raise ValueError("online_analysis_solver must be 'numpy' or 'device'")
         if not (0 <= number_of_iterations <= float('inf')):                              # :469-475 (the text is the reference's, run-on included)
             raise ValueError('Accepted values for number_of_iterations are' 'non-negative integers and infinity.')
         if mcmc_moves is None:
@@ -71,6 +73,7 @@ class MultiStateSampler:
         self.online_analysis_interval = online_analysis_interval
         self.online_analysis_target_error = online_analysis_target_error
         self.online_analysis_minimum_iterations = online_analysis_minimum_iterations
+        self.online_analysis_solver = online_analysis_solver      # analysis.MBAR's solver for the offline estimate inside the run loop
         self._last_mbar_f_k = None                # :246-247
         self._last_err_free_energy = None
         self._engine = engine
@@ -349,6 +352,8 @@ class MultiStateSampler:
         kwargs = dict(locality=self.locality, online_analysis_interval=self.online_analysis_interval,
                       online_analysis_target_error=self.online_analysis_target_error,
                       online_analysis_minimum_iterations=self.online_analysis_minimum_iterations)
+        if self.online_analysis_solver != 'numpy':                # stored only off its default: stores written before the option read and write unchanged
+            kwargs['online_analysis_solver'] = self.online_analysis_solver
         kwargs.update(self._ctor_kwargs())
         return dict(cls=type(self).__name__, module=type(self).__module__, number_of_iterations=self.number_of_iterations,
                     seed=self._seed, kwargs=kwargs)
@@ -932,7 +937,12 @@ class MultiStateSampler:
             self._last_mbar_f_k_offline = np.zeros(self.n_states + len(self._unsampled_states))
         err = None
         if self._comm.rank == 0:
-            analysis = MultiStateSamplerAnalyzer(self._reporter, analysis_kwargs={'initial_f_k': self._last_mbar_f_k_offline})
+            analysis_kwargs = {'initial_f_k': self._last_mbar_f_k_offline}
+            if self.online_analysis_solver != 'numpy':
+                analysis_kwargs['solver'] = self.online_analysis_solver
+                if isinstance(getattr(self._engine, 'device', None), int):
+                    analysis_kwargs['device'] = self._engine.device
+            analysis = MultiStateSamplerAnalyzer(self._reporter, analysis_kwargs=analysis_kwargs)
             try:
                 mbar = analysis.mbar
                 free_energy, err_free_energy = analysis.get_free_energy()
