@@ -1,5 +1,6 @@
 /*
- * remd_hip_custom.h — GPU-only extension of the C ABI in remd_hip.h: custom bond, angle, torsion, external and compound-bond forces.
+ * remd_hip_custom.h — GPU-only extension of the C ABI in remd_hip.h: custom bond, angle, torsion, external, compound-bond and
+ * centroid-bond forces.
  *
  * OpenMM's CustomBondForce, CustomAngleForce, CustomTorsionForce and CustomExternalForce: an energy expression of r (bond), theta
  * (angle, torsion) or x, y, z (external), of per-term parameters and of global parameters, evaluated per term.  The host compiles
@@ -19,8 +20,19 @@
  * sign convention of PeriodicTorsionForce) of the particle slots packed into the operand, 4 bits each, first argument lowest; they
  * take nothing from the stack and are legal only in such a program.  pointdistance is REMD_CX_PERIODICDISTANCE; it and the differences
  * between particles are minimum images only where the force is periodic.  The device runs the program once per particle slot, each
- * pass carrying the gradient with respect to that particle (csrc/custom_compound.hip).  Not provided: tabulated functions,
- * pointangle, pointdihedral, CustomCentroidBondForce beyond the restraint forms (remd_hip_restraints.h).
+ * pass carrying the gradient with respect to that particle (csrc/custom_compound.hip).
+ *
+ * Centroid-bond forces (REMD_CUSTOM_CENTROID, OpenMM's CustomCentroidBondForce): a compound-bond force whose particles are the weighted
+ * centroids of groups of atoms.  The descriptor carries the force's n_groups groups in CSR form (group_offsets, group_atoms) with
+ * weights that sum to 1 in every group (group_weights); `atoms` holds group numbers, n_particles of them per bond, and the program is a
+ * compound-bond program over the centroids x1 y1 z1 ....  A centroid is x_first + sum_i w_i img(x_i - x_first), the differences minimum
+ * images under the replica's own box where the force is periodic (the convention of remd_hip_restraints.h: a group whose molecules were
+ * wrapped one by one keeps its centroid), summed in f64 in a fixed order.  Per force evaluation the device computes every centroid,
+ * runs the bonds over them as it runs compound bonds, and gives atom i of a group -w_i dE/d(centroid) (csrc/custom_centroid.hip).  A
+ * group may be named by any number of bonds, an atom may sit in any number of groups.  The restraint forms of remd_hip_restraints.h keep
+ * their own entry points.
+ *
+ * Not provided: tabulated functions, pointangle, pointdihedral.
  *
  * Global parameters belong to the handle: every force's program addresses the same n_globals columns, and every state carries one
  * value per column (remd_set_custom_globals).  A term acts in every force evaluation (MD steps, energies, the barostat,
@@ -29,7 +41,7 @@
  *
  * Limits (a descriptor beyond them is refused): REMD_CUSTOM_MAX_PROGRAM instructions per force, REMD_CUSTOM_MAX_STACK stack slots,
  * REMD_CUSTOM_MAX_PARAMS parameters per term, REMD_CUSTOM_MAX_GLOBALS global columns per handle, REMD_CUSTOM_MAX_FORCES forces
- * per handle (of all kinds together), REMD_CUSTOM_MAX_PARTICLES particles per compound bond.
+ * per handle (of all kinds together), REMD_CUSTOM_MAX_PARTICLES particles per compound bond or groups per centroid bond.
  *
  * These entry points are declared here and not in remd_hip.h because the CPU port of the ABI does not provide them: a host binds
  * them only where the loaded library exports them.  Conventions as in remd_hip.h.
@@ -48,6 +60,7 @@ extern "C" {
 #define REMD_CUSTOM_TORSION  2     /* atoms [n][4], variable theta in (-pi, pi], the sign convention of PeriodicTorsionForce */
 #define REMD_CUSTOM_EXTERNAL 3     /* atoms [n][1], variables x, y, z                                                       */
 #define REMD_CUSTOM_COMPOUND 4     /* atoms [n][n_particles], variables x1, y1, z1, ..., and functions of the particles     */
+#define REMD_CUSTOM_CENTROID 5     /* atoms [n][n_particles] are GROUP numbers; the particles are the groups' centroids     */
 
 #define REMD_CUSTOM_MAX_PROGRAM 256
 #define REMD_CUSTOM_MAX_STACK   16
@@ -100,7 +113,7 @@ extern "C" {
 typedef struct remd_custom_force_desc {
     int32_t kind;                  /* REMD_CUSTOM_*                                                                        */
     int32_t n_terms;               /* bonds / angles / torsions / particles                                                */
-    const int32_t* atoms;          /* [n_terms][2 | 3 | 4 | 1 | n_particles]                                               */
+    const int32_t* atoms;          /* [n_terms][2 | 3 | 4 | 1 | n_particles]; REMD_CUSTOM_CENTROID: group numbers          */
     int32_t n_params;              /* parameters per term                                                                  */
     const double* params;          /* [n_terms][n_params]                                                                  */
     int32_t n_program;             /* instructions                                                                         */
@@ -112,7 +125,12 @@ typedef struct remd_custom_force_desc {
     const double* global_defaults; /* [n_globals]: every state's values until remd_set_custom_globals                      */
     int32_t periodic;              /* 1: differences between atoms are minimum images under the replica's own box          */
     int32_t force_group;           /* Force.getForceGroup() (multiple-time-step splittings)                                */
-    int32_t n_particles;           /* REMD_CUSTOM_COMPOUND: particles per bond, 1 ... REMD_CUSTOM_MAX_PARTICLES; else 0    */
+    int32_t n_particles;           /* REMD_CUSTOM_COMPOUND / _CENTROID: particles (groups) per bond, 1 ... REMD_CUSTOM_MAX_PARTICLES; else 0 */
+    /* REMD_CUSTOM_CENTROID only (every other kind ignores them)                                                          */
+    int32_t n_groups;              /* the force's groups, > 0                                                              */
+    const int32_t* group_offsets;  /* [n_groups + 1]: group g holds group_atoms[group_offsets[g] ... group_offsets[g + 1]), none empty */
+    const int32_t* group_atoms;    /* atom indices, 0 ... N - 1                                                            */
+    const double* group_weights;   /* beside group_atoms: >= 0, summing to 1 in every group (within 1e-12)                 */
 } remd_custom_force_desc;
 
 /* the custom forces of the system; call after remd_set_system (which forgets them).  n = 0: none.  Every custom force of a handle

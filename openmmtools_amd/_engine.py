@@ -70,12 +70,13 @@ class RemdRestraintDesc(C.Structure):
 
 
 class RemdCustomForceDesc(C.Structure):
-    """remd_custom_force_desc of include/remd_hip_custom.h (custom bond / angle / torsion / external / compound-bond forces,
-    custom_expr.py)."""
+    """remd_custom_force_desc of include/remd_hip_custom.h (custom bond / angle / torsion / external / compound-bond / centroid-bond
+    forces, custom_expr.py)."""
     _fields_ = [('kind', C.c_int32), ('n_terms', C.c_int32), ('atoms', c_int32_p), ('n_params', C.c_int32), ('params', c_double_p),
                 ('n_program', C.c_int32), ('program', c_int32_p), ('n_consts', C.c_int32), ('consts', c_double_p),
                 ('stack_depth', C.c_int32), ('n_globals', C.c_int32), ('global_defaults', c_double_p),
-                ('periodic', C.c_int32), ('force_group', C.c_int32), ('n_particles', C.c_int32)]
+                ('periodic', C.c_int32), ('force_group', C.c_int32), ('n_particles', C.c_int32),
+                ('n_groups', C.c_int32), ('group_offsets', c_int32_p), ('group_atoms', c_int32_p), ('group_weights', c_double_p)]
 
 
 class RemdGbModelDesc(C.Structure):
@@ -525,7 +526,7 @@ class HipEngine:
     def _custom_entry(self, name):
         if not hasattr(self.lib, name):
             raise NotImplementedError('%s: this build of the engine library has no custom bond / angle / torsion / external forces and no compound-bond forces '
-                                      '(include/remd_hip_custom.h is GPU-only)' % name)
+                                      'or centroid-bond forces (include/remd_hip_custom.h is GPU-only)' % name)
         return getattr(self.lib, name)
 
     def set_custom_terms(self, terms):
@@ -541,9 +542,16 @@ class HipEngine:
             consts = np.ascontiguousarray(t['consts'], dtype=np.float64)
             defaults = np.ascontiguousarray(t['global_defaults'], dtype=np.float64)
             keep += [atoms, params, program, consts, defaults]
+            groups = (0, None, None, None)
+            if 'group_offsets' in t:                                 # a centroid-bond force: atoms holds group numbers
+                g_off = np.ascontiguousarray(t['group_offsets'], dtype=np.int32)
+                g_atoms = np.ascontiguousarray(t['group_atoms'], dtype=np.int32)
+                g_w = np.ascontiguousarray(t['group_weights'], dtype=np.float64)
+                keep += [g_off, g_atoms, g_w]
+                groups = (len(g_off) - 1, _ip(g_off), _ip(g_atoms), _dp(g_w))
             arr[k] = RemdCustomForceDesc(int(t['kind']), len(atoms), _ip(atoms), params.shape[1], _dp(params), len(program), _ip(program),
                                          len(consts), _dp(consts), int(t['stack_depth']), len(defaults), _dp(defaults),
-                                         int(t['periodic']), int(t['force_group']), n_particles)
+                                         int(t['periodic']), int(t['force_group']), n_particles, *groups)
         self._check(fn(self.h, arr, len(terms)), 'remd_set_custom_terms')
         self.n_custom = len(terms)
         self.n_custom_globals = len(terms[0]['global_defaults']) if terms else 0

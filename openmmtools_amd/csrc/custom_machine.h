@@ -1,5 +1,5 @@
-// The stack machine of the custom forces (include/remd_hip_custom.h), shared by custom_terms.hip (bond, angle, torsion, external)
-// and custom_compound.hip (compound bonds): the per-force record, the handle's tables, and cst_eval, which runs a postfix program
+// The stack machine of the custom forces (include/remd_hip_custom.h), shared by custom_terms.hip (bond, angle, torsion, external),
+// custom_compound.hip (compound bonds) and custom_centroid.hip (centroid bonds, whose particles are centroids): the per-force record, the handle's tables, and cst_eval, which runs a postfix program
 // one term per lane with every stack slot a value and three partials, the stack in LDS as [slot][component][lane].
 //
 // cst_eval<GEOM>: the instantiation of the four one-variable kinds (GEOM = false) has the variables in three registers and no case
@@ -14,7 +14,7 @@
 
 struct cst_force {
     int kind, periodic, n_terms, n_params;
-    int n_particles;             // atoms per term (the particles per bond of a compound-bond force)
+    int n_particles;             // atoms per term (the particles per bond of a compound-bond force, the groups per bond of a centroid force)
     int slot0, npad;             // first slot in the padded term space of the launch / slots of this force (a multiple of 64)
     int par0;                    // offset of its parameters [n_params][npad]
     int prog0, n_prog, const0;   // its program and constants in the handle's tables
@@ -22,6 +22,8 @@ struct cst_force {
 
 struct cst_tables {
     int nf = 0, ng = 0, K = 0, total_pad = 0, waves_simple = 0; long long glob_version = -1;   // (waves_simple: the wavefronts of the four one-variable kinds, in front; glob belongs to the states of that remd_set_states)
+    int waves_particles = 0;                                                   // where the compound-bond forces' wavefronts end and the centroid forces' begin (the last part)
+    int n_groups = 0;                                                          // the groups of all centroid forces (0: no centroid force, none of the members below holds anything)
     bool uniform = true;                                                       // every state carries the same globals: no u_kl share
     std::vector<cst_force> F; std::vector<int> wave_force, atoms; std::vector<double> par, consts, glob, defaults; std::vector<int2> prog;
     dev_array<cst_force> d_F; dev_array<int> d_wave_force; dev_array<int> d_atoms;      // atoms [max(4, most particles per bond)][total_pad]
@@ -29,6 +31,15 @@ struct cst_tables {
     dev_array<double> d_E;             // [R][nf]
     dev_array<double> d_Ewave;         // [R][total_pad / 64]
     dev_array<double> d_D;             // [R][K][total_pad / 64] u_kl partials
+    // centroid forces (custom_centroid.hip): a centroid force's row of `atoms` holds handle-wide group numbers
+    std::vector<int> grp_off, grp_atoms, grp_periodic, ref_off, refs; std::vector<double> grp_w;
+    dev_array<int> d_grp_off;          // [n_groups + 1] into grp_atoms / grp_w
+    dev_array<int> d_grp_atoms; dev_array<double> d_grp_w;      // the groups' atoms and their weights (sum 1 per group)
+    dev_array<int> d_grp_periodic;     // [n_groups]: the flag of the force the group belongs to
+    dev_array<int> d_ref_off;          // [n_groups + 1] into refs
+    dev_array<int> d_refs;             // (centroid slot * REMD_CUSTOM_MAX_PARTICLES + position in the bond) of every bond that names the group, in table order
+    dev_array<double> d_C;             // [R][n_groups][3] centroids
+    dev_array<double> d_G;             // [R][centroid slots][REMD_CUSTOM_MAX_PARTICLES][3] dE / d centroid
 };
 
 namespace {
@@ -223,3 +234,6 @@ __device__ __forceinline__ double cst_wave_sum(double v)
 // launches of remd_custom_forces / remd_custom_ukl
 void remd_custom_compound_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
 void remd_custom_compound_ukl(remd_ctx* h, cst_tables& t);
+// custom_centroid.hip: the same for the centroid forces' wavefronts (those behind waves_particles): centroids, bonds, spread
+void remd_custom_centroid_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
+void remd_custom_centroid_ukl(remd_ctx* h, cst_tables& t);

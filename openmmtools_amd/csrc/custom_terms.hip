@@ -24,7 +24,8 @@
 // the last one: added behind the restraint kernel on the same stream).  No atomics touch an energy.
 //
 // The machine itself (cst_eval) lives in custom_machine.h: custom_compound.hip runs the same one for CustomCompoundBondForce, whose
-// wavefronts follow the ones of this file's four kinds in the padded term space and share the energy and u_kl reductions below.
+// wavefronts follow the ones of this file's four kinds in the padded term space and share the energy and u_kl reductions below, and
+// custom_centroid.hip runs it for CustomCentroidBondForce, whose wavefronts come last.
 #include "remd_internal.h"
 #include "listed_terms.h"
 #include "custom_machine.h"
@@ -192,6 +193,10 @@ int ensure_buffers(remd_ctx* h, cst_tables& t)
         REMD_CHECK(h, hipMemset(t.d_E, 0, sizeof(double) * (size_t)h->R * t.nf));
     }
     if (t.d_Ewave.size() != (size_t)h->R * waves) REMD_TRY(t.d_Ewave.alloc(h, (size_t)h->R * waves));
+    // centroid forces: the centroids and the gradients on them (a handle without such a force: n_groups = 0, nothing is allocated)
+    const size_t nC = (size_t)h->R * t.n_groups * 3, nG = (size_t)h->R * (waves - t.waves_particles) * 64 * REMD_CUSTOM_MAX_PARTICLES * 3;
+    if (t.d_C.size() != nC) REMD_TRY(t.d_C.alloc(h, nC));
+    if (t.d_G.size() != nG) REMD_TRY(t.d_G.alloc(h, nG));
     return 0;
 }
 
@@ -200,8 +205,10 @@ int set_tables(remd_ctx* h, cst_tables& t)
     int rc;
     if ((rc = t.d_F.upload(h, t.F)) || (rc = t.d_wave_force.upload(h, t.wave_force)) || (rc = t.d_atoms.upload(h, t.atoms)) ||
         (rc = t.d_par.upload(h, t.par)) || (rc = t.d_consts.upload(h, t.consts)) || (rc = t.d_glob.upload(h, t.glob)) ||
-        (rc = t.d_prog.upload(h, t.prog))) return rc;
-    t.d_E.reset(); t.d_Ewave.reset(); t.d_D.reset();
+        (rc = t.d_prog.upload(h, t.prog)) || (rc = t.d_grp_off.upload(h, t.grp_off)) || (rc = t.d_grp_atoms.upload(h, t.grp_atoms)) ||
+        (rc = t.d_grp_w.upload(h, t.grp_w)) || (rc = t.d_grp_periodic.upload(h, t.grp_periodic)) || (rc = t.d_ref_off.upload(h, t.ref_off)) ||
+        (rc = t.d_refs.upload(h, t.refs))) return rc;
+    t.d_E.reset(); t.d_Ewave.reset(); t.d_D.reset(); t.d_C.reset(); t.d_G.reset();
     return 0;
 }
 
@@ -214,7 +221,7 @@ bool globals_uniform(const cst_tables& t)
 // what a program may do is settled here, once: the kernels index the stack, the constants, the parameters and the globals unchecked
 const char* check_program(const remd_custom_force_desc& d, int n_vars)
 {
-    const bool compound = d.kind == REMD_CUSTOM_COMPOUND;
+    const bool compound = d.kind == REMD_CUSTOM_COMPOUND || d.kind == REMD_CUSTOM_CENTROID;
     if (d.n_program <= 0 || !d.program) return "an empty program";
     if (d.n_program > REMD_CUSTOM_MAX_PROGRAM) return "a program over REMD_CUSTOM_MAX_PROGRAM instructions";
     int sp = 0, top = 0;
@@ -232,7 +239,7 @@ const char* check_program(const remd_custom_force_desc& d, int n_vars)
         case REMD_CX_PERIODICDISTANCE: pops = 6; break;
         case REMD_CX_DISTANCE: case REMD_CX_ANGLE: case REMD_CX_DIHEDRAL: {
             // the zero-based particle slots in 4-bit fields, first argument lowest; nothing above them
-            if (!compound) return "a function of particles outside a compound-bond force";
+            if (!compound) return "a function of particles outside a compound-bond or centroid-bond force";
             const int n_args = op - REMD_CX_DISTANCE + 2;
             if (arg < 0 || (arg >> (4 * n_args)) != 0) return "a particle slot out of range";
             for (int k = 0; k < n_args; ++k) if (((arg >> (4 * k)) & 15) >= d.n_particles) return "a particle slot out of range";
@@ -266,6 +273,8 @@ int remd_custom_clone(remd_ctx* parent, remd_ctx* child)
     child->cst.reset(new cst_tables());
     cst_tables& c = *child->cst;
     c.nf = t->nf; c.ng = t->ng; c.K = t->K; c.total_pad = t->total_pad; c.waves_simple = t->waves_simple; c.uniform = t->uniform;
+    c.waves_particles = t->waves_particles; c.n_groups = t->n_groups;
+    c.grp_off = t->grp_off; c.grp_atoms = t->grp_atoms; c.grp_w = t->grp_w; c.grp_periodic = t->grp_periodic; c.ref_off = t->ref_off; c.refs = t->refs;
     c.glob_version = t->glob_version == parent->states_version ? child->states_version : -1;
     c.F = t->F; c.wave_force = t->wave_force; c.atoms = t->atoms; c.par = t->par; c.consts = t->consts; c.glob = t->glob;
     c.defaults = t->defaults; c.prog = t->prog;
@@ -298,7 +307,8 @@ int remd_custom_forces(remd_ctx* h, bool with_energy, int ep_slot, hipStream_t s
                                t.d_wave_force, t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, h->d_labels, h->r_begin, h->Npad, h->d_pos,
                                h->d_box, h->d_force, t.d_Ewave);
     }
-    if (waves > t.waves_simple) remd_custom_compound_forces(h, t, with_energy, st);       // (custom_compound.hip: the wavefronts behind)
+    if (t.waves_particles > t.waves_simple) remd_custom_compound_forces(h, t, with_energy, st);   // (custom_compound.hip: the wavefronts behind)
+    if (waves > t.waves_particles) remd_custom_centroid_forces(h, t, with_energy, st);            // (custom_centroid.hip: the last ones)
     if (with_energy)
         hipLaunchKernelGGL(custom_reduce_kernel, dim3(h->R), dim3(64), 0, st, t.nf, t.d_F, waves, t.d_Ewave, t.d_E, h->d_epart, h->n_epart, ep_slot);
     REMD_CHECK(h, hipGetLastError());
@@ -321,7 +331,8 @@ int remd_custom_ukl(remd_ctx* h, double* d_rows)
     if (t.waves_simple > 0)
         hipLaunchKernelGGL(custom_ukl_kernel, dim3(t.waves_simple, h->R), dim3(64), 0, h->stream, t.total_pad, waves, t.d_F, t.d_wave_force,
                            t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, h->K, h->d_labels, h->r_begin, h->Npad, h->d_pos, h->d_box, t.d_D);
-    if (waves > t.waves_simple) remd_custom_compound_ukl(h, t);
+    if (t.waves_particles > t.waves_simple) remd_custom_compound_ukl(h, t);
+    if (waves > t.waves_particles) remd_custom_centroid_ukl(h, t);
     hipLaunchKernelGGL(custom_ukl_reduce_kernel, dim3(h->K, h->R), dim3(64), 0, h->stream, h->K, waves, t.d_D, h->d_beta, d_rows);
     REMD_CHECK(h, hipGetLastError());
     return 0;
@@ -347,10 +358,10 @@ int remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, int
     for (int i = 0; i < n; ++i) {
         const remd_custom_force_desc& d = desc[i];
         const std::string who = "remd_set_custom_terms: force " + std::to_string(i) + ": ";
-        if (d.kind < 0 || d.kind > REMD_CUSTOM_COMPOUND) return remd_fail(h, -1, who + "unknown kind");
-        const bool compound = d.kind == REMD_CUSTOM_COMPOUND;
+        if (d.kind < 0 || d.kind > REMD_CUSTOM_CENTROID) return remd_fail(h, -1, who + "unknown kind");
+        const bool centroid = d.kind == REMD_CUSTOM_CENTROID, compound = d.kind == REMD_CUSTOM_COMPOUND || centroid;
         if (compound ? (d.n_particles < 1 || d.n_particles > REMD_CUSTOM_MAX_PARTICLES) : d.n_particles != 0)
-            return remd_fail(h, -1, who + "n_particles is 1 ... REMD_CUSTOM_MAX_PARTICLES for a compound-bond force and 0 for every other kind");
+            return remd_fail(h, -1, who + "n_particles is 1 ... REMD_CUSTOM_MAX_PARTICLES for a compound-bond or centroid-bond force and 0 for every other kind");
         const int wd = compound ? d.n_particles : width4[d.kind];
         if (d.n_terms <= 0 || !d.atoms) return remd_fail(h, -1, who + "no terms");
         if (d.n_params < 0 || d.n_params > REMD_CUSTOM_MAX_PARAMS || (d.n_params > 0 && !d.params))
@@ -360,7 +371,24 @@ int remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, int
         if (d.force_group != desc[0].force_group || d.force_group < 0 || d.force_group > 31)
             return remd_fail(h, -1, who + "every custom force of a handle must sit in one force group (0 ... 31)");
         if (const char* bad = check_program(d, compound ? 3 * d.n_particles : n_vars4[d.kind])) return remd_fail(h, -1, who + bad);
-        for (int k = 0; k < d.n_terms * wd; ++k) if (d.atoms[k] < 0 || d.atoms[k] >= h->N) return remd_fail(h, -1, who + "atom index out of range");
+        if (centroid) {
+            // the groups: CSR offsets that start at 0 and increase (no empty group), atoms of the system, weights that sum to 1
+            if (d.n_groups <= 0 || !d.group_offsets || !d.group_atoms || !d.group_weights) return remd_fail(h, -1, who + "a centroid-bond force needs n_groups > 0, group_offsets, group_atoms and group_weights");
+            if (d.group_offsets[0] != 0) return remd_fail(h, -1, who + "group_offsets must start at 0");
+            for (int g = 0; g < d.n_groups; ++g) {
+                const int b = d.group_offsets[g], e = d.group_offsets[g + 1];
+                if (e <= b) return remd_fail(h, -1, who + "group_offsets must increase (an empty group has no centroid)");
+                double W = 0.0;
+                for (int k = b; k < e; ++k) {
+                    if (d.group_atoms[k] < 0 || d.group_atoms[k] >= h->N) return remd_fail(h, -1, who + "group atom index out of range");
+                    if (!(d.group_weights[k] >= 0.0)) return remd_fail(h, -1, who + "negative group weight");
+                    W += d.group_weights[k];
+                }
+                if (!(fabs(W - 1.0) <= 1e-12)) return remd_fail(h, -1, who + "the weights of a group must sum to 1 (within 1e-12)");
+            }
+            for (int k = 0; k < d.n_terms * wd; ++k) if (d.atoms[k] < 0 || d.atoms[k] >= d.n_groups) return remd_fail(h, -1, who + "group index out of range");
+        } else
+            for (int k = 0; k < d.n_terms * wd; ++k) if (d.atoms[k] < 0 || d.atoms[k] >= h->N) return remd_fail(h, -1, who + "atom index out of range");
         cst_force f{};
         f.kind = d.kind; f.periodic = d.periodic ? 1 : 0; f.n_terms = d.n_terms; f.n_params = d.n_params; f.n_particles = wd;
         f.npad = (d.n_terms + 63) / 64 * 64;
@@ -371,24 +399,53 @@ int remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, int
         if (d.n_consts > 0) t.consts.insert(t.consts.end(), d.consts, d.consts + d.n_consts);
         t.F.push_back(f);
     }
-    // the padded term space: the four one-variable kinds first, the compound-bond forces behind them (each part has its own kernel);
-    // the energy columns keep the forces' order whatever their slots
-    for (int pass = 0; pass < 2; ++pass) {
+    // the padded term space: the four one-variable kinds first, the compound-bond forces behind them, the centroid-bond forces last
+    // (each part has its own kernel); the energy columns keep the forces' order whatever their slots
+    for (int pass = 0; pass < 3; ++pass) {
         for (int i = 0; i < n; ++i) {
             cst_force& f = t.F[i];
-            if ((f.kind == REMD_CUSTOM_COMPOUND) != (pass == 1)) continue;
+            if ((f.kind == REMD_CUSTOM_CENTROID ? 2 : f.kind == REMD_CUSTOM_COMPOUND ? 1 : 0) != pass) continue;
             f.slot0 = t.total_pad; t.total_pad += f.npad;
             for (int w = 0; w < f.npad / 64; ++w) t.wave_force.push_back(i);
         }
         if (pass == 0) t.waves_simple = t.total_pad / 64;
+        if (pass == 1) t.waves_particles = t.total_pad / 64;
     }
     int rows = 4;
     for (int i = 0; i < n; ++i) rows = std::max(rows, t.F[i].n_particles);
     t.atoms.assign((size_t)rows * t.total_pad, 0);
+    // a centroid force's groups join the handle's group tables; its row of `atoms` holds the handle-wide group numbers
+    std::vector<int> group0(n, 0);
+    for (int i = 0; i < n; ++i) {
+        if (t.F[i].kind != REMD_CUSTOM_CENTROID) continue;
+        const remd_custom_force_desc& d = desc[i];
+        group0[i] = t.n_groups;
+        if (t.grp_off.empty()) t.grp_off.push_back(0);
+        for (int g = 0; g < d.n_groups; ++g) {
+            t.grp_atoms.insert(t.grp_atoms.end(), d.group_atoms + d.group_offsets[g], d.group_atoms + d.group_offsets[g + 1]);
+            t.grp_w.insert(t.grp_w.end(), d.group_weights + d.group_offsets[g], d.group_weights + d.group_offsets[g + 1]);
+            t.grp_off.push_back((int)t.grp_atoms.size());
+            t.grp_periodic.push_back(t.F[i].periodic);
+        }
+        t.n_groups += d.n_groups;
+    }
     for (int i = 0; i < n; ++i) {
         const cst_force& f = t.F[i]; const int wd = f.n_particles;
         for (int s = 0; s < f.npad; ++s) for (int a = 0; a < wd; ++a)
-            t.atoms[(size_t)a * t.total_pad + f.slot0 + s] = desc[i].atoms[(size_t)std::min(s, f.n_terms - 1) * wd + a];
+            t.atoms[(size_t)a * t.total_pad + f.slot0 + s] = group0[i] + desc[i].atoms[(size_t)std::min(s, f.n_terms - 1) * wd + a];
+    }
+    if (t.n_groups > 0) {
+        // per group, every (bond, position) that names it, in table order: the spread kernel adds their gradients in this order
+        std::vector<std::vector<int>> named(t.n_groups);
+        const int slot_c = t.waves_particles * 64;
+        for (int i = 0; i < n; ++i) {
+            const cst_force& f = t.F[i];
+            if (f.kind != REMD_CUSTOM_CENTROID) continue;
+            for (int b = 0; b < f.n_terms; ++b) for (int a = 0; a < f.n_particles; ++a)
+                named[t.atoms[(size_t)a * t.total_pad + f.slot0 + b]].push_back((f.slot0 + b - slot_c) * REMD_CUSTOM_MAX_PARTICLES + a);
+        }
+        t.ref_off.push_back(0);
+        for (const std::vector<int>& v : named) { t.refs.insert(t.refs.end(), v.begin(), v.end()); t.ref_off.push_back((int)t.refs.size()); }
     }
     t.K = h->K; t.glob_version = h->states_version; t.uniform = true;
     for (int k = 0; k < std::max(h->K, 0); ++k) t.glob.insert(t.glob.end(), t.defaults.begin(), t.defaults.end());

@@ -3,15 +3,16 @@
 // (lambda_restraints) of the replica's state.
 //
 // One workgroup per replica walks the handle's restraints in order (a system carries one or two).  Per restraint: both centroids in
-// f64, each thread summing its strided share of a group's atoms, then a xor-shuffle tree inside each wavefront and the four
-// wavefronts' sums added in a fixed order -- no atomics touch a centroid, the result does not depend on scheduling.  Atom positions
-// enter relative to the group's first atom (minimum image under the replica's own box when the force is periodic): a group
-// whose molecules the barostat wrapped one by one keeps its centroid.  Each atom then gets its share
+// f64 (centroid_sum.h, shared with custom_centroid.hip), each thread summing its strided share of a group's atoms, then a xor-shuffle
+// tree inside each wavefront and the four wavefronts' sums added in a fixed order -- no atomics touch a centroid, the result does not
+// depend on scheduling.  Atom positions enter relative to the group's first atom (minimum image under the replica's own box when the
+// force is periodic): a group whose molecules the barostat wrapped one by one keeps its centroid.  Each atom then gets its share
 //   F_i = -/+ lambda_own dE/dr (w_i) d / r        (d = centroid 2 - centroid 1, w_i = m_i / M_group)
 // through the fixed-point force accumulators; lambda_own E goes to the replica's energy partial (the potential, the barostat and
 // the minimiser see it) and the unscaled E to a [R][n] buffer the u_kl rows read.
 #include "remd_internal.h"
 #include "listed_terms.h"
+#include "centroid_sum.h"
 #include "../../include/remd_hip_restraints.h"
 
 namespace {
@@ -34,43 +35,6 @@ void remd_table_deleter::operator()(rst_tables* t) const { delete t; }
 
 namespace {
 
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// sum over the workgroup (256 threads = 4 wavefronts) in a fixed order; every thread gets the result
-__device__ __forceinline__ double3 block_sum3(double3 v, double (*s)[4])
-{
-    v.x = wave_sum_d(v.x); v.y = wave_sum_d(v.y); v.z = wave_sum_d(v.z);
-    const int wv = threadIdx.x >> 6;
-    __syncthreads();                                  // (the previous call's readers are done with s)
-    if ((threadIdx.x & 63) == 0) { s[0][wv] = v.x; s[1][wv] = v.y; s[2][wv] = v.z; }
-    __syncthreads();
-    return make_double3(((s[0][0] + s[0][1]) + s[0][2]) + s[0][3], ((s[1][0] + s[1][1]) + s[1][2]) + s[1][3],
-                        ((s[2][0] + s[2][1]) + s[2][2]) + s[2][3]);
-}
-
-__device__ __forceinline__ double min_image(double d, double L) { return L > 0.0 ? d - L * rint(d / L) : d; }
-
-// centroid of one group: first atom + sum_i w_i (x_i - x_first), the differences imaged when periodic
-__device__ __forceinline__ double3 centroid(const float4* __restrict__ P, const int* __restrict__ atoms, const double* __restrict__ w,
-                                            int b, int n, bool periodic, double Lx, double Ly, double Lz, double (*s)[4])
-{
-    const float4 a0 = P[atoms[b]];
-    double3 acc = make_double3(0.0, 0.0, 0.0);
-    for (int k = threadIdx.x; k < n; k += 256) {
-        const float4 q = P[atoms[b + k]];
-        double dx = (double)q.x - (double)a0.x, dy = (double)q.y - (double)a0.y, dz = (double)q.z - (double)a0.z;
-        if (periodic) { dx = min_image(dx, Lx); dy = min_image(dy, Ly); dz = min_image(dz, Lz); }
-        const double wk = w[b + k];
-        acc.x += wk * dx; acc.y += wk * dy; acc.z += wk * dz;
-    }
-    acc = block_sum3(acc, s);
-    return make_double3((double)a0.x + acc.x, (double)a0.y + acc.y, (double)a0.z + acc.z);
-}
-
 template <bool ENERGY>
 __global__ __launch_bounds__(256)
 void restraint_kernel(int n, const rst_param* __restrict__ par, const int* __restrict__ atoms, const double* __restrict__ w,
@@ -88,8 +52,8 @@ void restraint_kernel(int n, const rst_param* __restrict__ par, const int* __res
     for (int i = 0; i < n; ++i) {
         const rst_param p = par[i];
         const bool pbc = p.periodic != 0;
-        const double3 c1 = centroid(P, atoms, w, p.b1, p.n1, pbc, Lx, Ly, Lz, s);
-        const double3 c2 = centroid(P, atoms, w, p.b2, p.n2, pbc, Lx, Ly, Lz, s);
+        const double3 c1 = centroid<256>(P, atoms, w, p.b1, p.n1, pbc, Lx, Ly, Lz, s);
+        const double3 c2 = centroid<256>(P, atoms, w, p.b2, p.n2, pbc, Lx, Ly, Lz, s);
         double dx = c2.x - c1.x, dy = c2.y - c1.y, dz = c2.z - c1.z;
         if (pbc) { dx = min_image(dx, Lx); dy = min_image(dy, Ly); dz = min_image(dz, Lz); }
         const double rr = sqrt(dx * dx + dy * dy + dz * dz);

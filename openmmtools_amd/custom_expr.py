@@ -1,12 +1,16 @@
-"""Compiler of OpenMM energy expressions for the custom bond, angle, torsion, external and compound-bond forces
-(system.CustomBondForce, CustomAngleForce, CustomTorsionForce, CustomExternalForce, CustomCompoundBondForce): an energy string becomes
-the postfix program of include/remd_hip_custom.h, which csrc/custom_terms.hip and csrc/custom_compound.hip run on a forward-mode
-stack machine (every stack slot a value and its partial derivatives with respect to the force's variables).
+"""Compiler of OpenMM energy expressions for the custom bond, angle, torsion, external, compound-bond and centroid-bond forces
+(system.CustomBondForce, CustomAngleForce, CustomTorsionForce, CustomExternalForce, CustomCompoundBondForce, CustomCentroidBondForce):
+an energy string becomes the postfix program of include/remd_hip_custom.h, which csrc/custom_terms.hip, csrc/custom_compound.hip and
+csrc/custom_centroid.hip run on a forward-mode stack machine (every stack slot a value and its partial derivatives with respect to
+the force's variables).
 
 A compound-bond force of P particles (1 ... MAX_PARTICLES) has the variables x1 y1 z1 ... xP yP zP (operand 3*(i-1)+c) and the
 functions distance(pi,pj), angle(pi,pj,pk) and dihedral(pi,pj,pk,pl), whose operand packs the zero-based particle slots in 4-bit
 fields, first argument lowest; the particle names p1 ... pP are legal only there.  pointdistance(x1,y1,z1,x2,y2,z2) is the
 periodicdistance opcode (the engine images it only where the force is periodic); pointangle and pointdihedral are refused.
+
+A centroid-bond force of P groups per bond is the same thing over the groups' centroids: the same variables, the same functions with
+the names g1 ... gP in place of p1 ... pP, the same program.  Its descriptor carries the groups beside it (custom_terms_desc).
 
 Grammar: numbers (exponent notation included), ``+ - * / ^``, unary minus, parentheses, function calls, and ``;``-separated
 definitions ``name = expr`` in any order, substituted where they are used.  ``^`` binds tighter than unary minus and groups to the
@@ -24,9 +28,9 @@ MAX_PROGRAM, MAX_STACK, MAX_PARAMS, MAX_GLOBALS, MAX_FORCES = 256, 16, 16, 16, 8
 MAX_INTEGER_POWER = 64
 MAX_PARTICLES = 8                               # particles per bond of a compound-bond force
 
-KIND_BOND, KIND_ANGLE, KIND_TORSION, KIND_EXTERNAL, KIND_COMPOUND = 0, 1, 2, 3, 4
+KIND_BOND, KIND_ANGLE, KIND_TORSION, KIND_EXTERNAL, KIND_COMPOUND, KIND_CENTROID = 0, 1, 2, 3, 4, 5
 KIND_OF_CLASS = {'CustomBondForce': KIND_BOND, 'CustomAngleForce': KIND_ANGLE, 'CustomTorsionForce': KIND_TORSION,
-                 'CustomExternalForce': KIND_EXTERNAL, 'CustomCompoundBondForce': KIND_COMPOUND}
+                 'CustomExternalForce': KIND_EXTERNAL, 'CustomCompoundBondForce': KIND_COMPOUND, 'CustomCentroidBondForce': KIND_CENTROID}
 VARIABLES = {KIND_BOND: ('r',), KIND_ANGLE: ('theta',), KIND_TORSION: ('theta',), KIND_EXTERNAL: ('x', 'y', 'z')}
 
 
@@ -50,7 +54,8 @@ POPS = {CONST: 0, VAR: 0, PARAM: 0, GLOBAL: 0, ADD: 2, SUB: 2, MUL: 2, DIV: 2, P
         PERIODICDISTANCE: 6, DISTANCE: 0, ANGLE: 0, DIHEDRAL: 0}
 # the functions of particles of a compound-bond force: name -> (opcode, number of particles)
 PARTICLE_FUNCTIONS = dict(distance=(DISTANCE, 2), angle=(ANGLE, 3), dihedral=(DIHEDRAL, 4))
-_PARTICLE_NAME = re.compile(r'p([1-9][0-9]*)')
+# the names of a bond's particles: p1 ... of a compound-bond force, g1 ... of a centroid-bond force (prefix -> pattern, noun)
+_PARTICLE_NAMES = {'p': (re.compile(r'p([1-9][0-9]*)'), 'particle'), 'g': (re.compile(r'g([1-9][0-9]*)'), 'group')}
 
 _TOKEN = re.compile(r'\s*(?:(\d+\.?\d*(?:[eE][+-]?\d+)?|\.\d+(?:[eE][+-]?\d+)?)|([A-Za-z_][A-Za-z_0-9]*)|(.))')
 
@@ -180,17 +185,20 @@ def split_definitions(energy, where='expression'):
 
 
 def compile_expression(energy, variables, parameters, global_columns, where='expression', tabulated=(), periodic_distance=False,
-                       n_particles=0):
+                       n_particles=0, particle_prefix='p'):
     """The postfix program of ``energy``.
 
     variables: the force's own variable names in operand order; parameters: the per-term parameter names in order; global_columns:
     {global parameter name: column of the handle's table}; tabulated: names of tabulated functions (refused); periodic_distance:
     whether periodicdistance(...) is allowed (an external force that uses periodic boundary conditions); n_particles: the particles
-    per bond of a compound-bond force (0: another force), which opens distance / angle / dihedral over p1 ... pP and pointdistance.
+    per bond of a compound-bond force (0: another force), which opens distance / angle / dihedral over p1 ... pP and pointdistance;
+    particle_prefix: 'p', or 'g' for the groups g1 ... gP of a centroid-bond force (the messages then speak of groups).
 
     Returns dict(program int32 [n][2], consts float64 [m], stack_depth).
     """
     body, definitions = split_definitions(energy, where)
+    _PARTICLE_NAME, noun = _PARTICLE_NAMES[particle_prefix]
+    other = {'p': 'g', 'g': 'p'}[particle_prefix]
     trees = {}
     program, consts, const_index = [], [], {}
     depth = [0, 0]                              # current, maximum
@@ -231,7 +239,10 @@ def compile_expression(energy, variables, parameters, global_columns, where='exp
             if name in global_columns:
                 return emit(GLOBAL, global_columns[name])
             if n_particles and _PARTICLE_NAME.fullmatch(name):
-                raise NotImplementedError('%s: particle name %r outside distance(), angle() and dihedral()' % (where, name))
+                raise NotImplementedError('%s: %s name %r outside distance(), angle() and dihedral()' % (where, noun, name))
+            if n_particles and _PARTICLE_NAMES[other][0].fullmatch(name):
+                raise NotImplementedError('%s: %s name %r (the %ss of this force are %s1 ... %s%d)'
+                                          % (where, _PARTICLE_NAMES[other][1], name, noun, particle_prefix, particle_prefix, n_particles))
             raise NotImplementedError('%s: unknown variable %r' % (where, name))
         if kind == 'neg':
             walk(node[1], active)
@@ -254,14 +265,18 @@ def compile_expression(energy, variables, parameters, global_columns, where='exp
             if n_particles and name in PARTICLE_FUNCTIONS:
                 op, n_args = PARTICLE_FUNCTIONS[name]
                 if len(args) != n_args:
-                    raise NotImplementedError('%s: function %r takes %d particles, not %d' % (where, name, n_args, len(args)))
+                    raise NotImplementedError('%s: function %r takes %d %ss, not %d' % (where, name, n_args, noun, len(args)))
                 packed = 0
                 for k, a in enumerate(args):
                     m = _PARTICLE_NAME.fullmatch(a[1]) if a[0] == 'name' else None
+                    if m is None and a[0] == 'name' and _PARTICLE_NAMES[other][0].fullmatch(a[1]):
+                        raise NotImplementedError('%s: %s name %r (the %ss of this force are %s1 ... %s%d)'
+                                                  % (where, _PARTICLE_NAMES[other][1], a[1], noun, particle_prefix, particle_prefix, n_particles))
                     if m is None:
-                        raise NotImplementedError('%s: the arguments of %r are particle names p1 ... p%d' % (where, name, n_particles))
+                        raise NotImplementedError('%s: the arguments of %r are %s names %s1 ... %s%d'
+                                                  % (where, name, noun, particle_prefix, particle_prefix, n_particles))
                     if int(m.group(1)) > n_particles:
-                        raise NotImplementedError('%s: particle %r in a bond of %d particles' % (where, a[1], n_particles))
+                        raise NotImplementedError('%s: %s %r in a bond of %d %ss' % (where, noun, a[1], n_particles, noun))
                     packed |= (int(m.group(1)) - 1) << (4 * k)
                 return emit(op, packed)
             if n_particles and name in ('pointangle', 'pointdihedral'):
@@ -299,10 +314,10 @@ def _per_term_names(force):
 def is_custom_term_force(force):
     """Whether system_to_desc sends this force down the expression path: one of the four classes whose energy is neither the
     HarmonicOscillator string (ext_K / ext_x0 / ext_U0) nor one of the restraint forms (csrc/restraints.hip), or a
-    CustomCompoundBondForce."""
+    CustomCompoundBondForce, or a system.CustomCentroidBondForce (forces.CustomCentroidBondForce, the restraints' base, is another class)."""
     from . import system as _system
     from . import forces as _forces
-    if isinstance(force, _system.CustomCompoundBondForce):
+    if isinstance(force, (_system.CustomCompoundBondForce, _system.CustomCentroidBondForce)):
         return True
     if isinstance(force, _system.CustomExternalForce):
         return not force.is_harmonic_oscillator()
@@ -313,9 +328,40 @@ def is_custom_term_force(force):
     return False
 
 
-def custom_terms_desc(forces):
+def centroid_groups(force, masses):
+    """The groups of a centroid-bond force in CSR form: (group_offsets int32 [G+1], group_atoms int32, group_weights float64), the
+    weights normalised to sum 1 per group in f64 -- the group's own where it gives any, else the particles' masses."""
+    n_atoms = None if masses is None else len(masses)
+    offsets, atoms, weights = [0], [], []
+    for g in range(force.getNumGroups()):
+        particles, w = force.getGroupParameters(g)
+        if len(particles) == 0:
+            raise ValueError('CustomCentroidBondForce: group %d is empty' % g)
+        if len(w) not in (0, len(particles)):
+            raise ValueError('CustomCentroidBondForce: group %d has %d particles and %d weights' % (g, len(particles), len(w)))
+        if min(particles) < 0 or (n_atoms is not None and max(particles) >= n_atoms):
+            raise ValueError('CustomCentroidBondForce: group %d names particle %d (the System has %s)'
+                             % (g, min(particles) if min(particles) < 0 else max(particles), n_atoms))
+        if len(w) == 0:
+            if masses is None:
+                raise ValueError('CustomCentroidBondForce: group %d has no weights and no masses were given' % g)
+            w = [float(masses[p]) for p in particles]
+        w = np.array(w, dtype=np.float64)
+        if np.any(w < 0.0):
+            raise ValueError('CustomCentroidBondForce: group %d has a negative weight' % g)
+        if not w.sum() > 0.0:
+            raise ValueError('CustomCentroidBondForce: the weights of group %d sum to zero' % g)
+        atoms += list(particles)
+        weights.append(w / w.sum())
+        offsets.append(len(atoms))
+    return (np.array(offsets, dtype=np.int32), np.array(atoms, dtype=np.int32),
+            np.concatenate(weights) if weights else np.zeros(0, dtype=np.float64))
+
+
+def custom_terms_desc(forces, masses=None):
     """The 'custom_terms' entry of system.system_to_desc for the custom forces ``forces`` (in System order): a dict keyed by position
-    ('000', '001', ...), each value dict(kind, atoms [n][1..4] ([n][P] and n_particles = P of a compound-bond force), params [n][p], global_names, global_defaults, program, consts,
+    ('000', '001', ...), each value dict(kind, atoms [n][1..4] ([n][P] and n_particles = P of a compound-bond force; of a centroid-bond force atoms holds
+    group numbers and group_offsets, group_atoms, group_weights describe the groups, centroid_groups(force, masses)), params [n][p], global_names, global_defaults, program, consts,
     stack_depth, periodic, force_group, energy).  The global names and defaults are the handle's columns, the same in every entry: a
     global two forces share is one column."""
     if len(forces) > MAX_FORCES:
@@ -355,18 +401,29 @@ def custom_terms_desc(forces):
             n_particles = int(f.getNumParticlesPerBond())
             if not 1 <= n_particles <= MAX_PARTICLES:
                 raise NotImplementedError('%s: bonds of %d particles (the engine takes 1 ... %d)' % (cls, n_particles, MAX_PARTICLES))
+        if kind == KIND_CENTROID:
+            n_particles = int(f.getNumGroupsPerBond())
+            if not 1 <= n_particles <= MAX_PARTICLES:
+                raise NotImplementedError('%s: bonds of %d groups (the engine takes 1 ... %d)' % (cls, n_particles, MAX_PARTICLES))
         prog = compile_expression(f.getEnergyFunction(), compound_variables(n_particles) if n_particles else VARIABLES[kind], per_term, own,
                                   where=where, tabulated=tabulated, periodic_distance=(kind == KIND_EXTERNAL and periodic),
-                                  n_particles=n_particles)
+                                  n_particles=n_particles, particle_prefix='g' if kind == KIND_CENTROID else 'p')
         atoms, params = f._term_arrays()
         if len(atoms) == 0:
             continue
+        if kind == KIND_CENTROID:
+            groups = centroid_groups(f, masses)
+            if atoms.min() < 0 or atoms.max() >= f.getNumGroups():
+                raise ValueError('%s: a bond names group %d (the force has %d)'
+                                 % (cls, atoms.min() if atoms.min() < 0 else atoms.max(), f.getNumGroups()))
         out['%03d' % len(out)] = dict(kind=kind, atoms=atoms, params=params, global_names=list(names),
                                       global_defaults=np.array(defaults, dtype=np.float64), program=prog['program'], consts=prog['consts'],
                                       stack_depth=prog['stack_depth'], periodic=int(periodic), force_group=int(f.getForceGroup()),
                                       energy=f.getEnergyFunction())
         if n_particles:
             out['%03d' % (len(out) - 1)]['n_particles'] = n_particles
+        if kind == KIND_CENTROID:
+            out['%03d' % (len(out) - 1)].update(group_offsets=groups[0], group_atoms=groups[1], group_weights=groups[2])
     return out
 
 

@@ -370,6 +370,69 @@ class CustomCompoundBondForce(_CustomForce):
         return _term_arrays(self._bonds, self._n_particles, len(self._per_bond), 'CustomCompoundBondForce')
 
 
+class CustomCentroidBondForce(_CustomForce):
+    """openmm.CustomCentroidBondForce: bonds between ``numGroups`` groups of particles, the energy a compound-bond expression of the
+    groups' weighted centroids: their coordinates x1 y1 z1 ..., distance(g1,g2), angle(g1,g2,g3), dihedral(g1,g2,g3,g4) and
+    pointdistance(x1,y1,z1,x2,y2,z2), per-bond and global parameters.  A group without weights is weighted by its particles' masses.
+    Every expression goes to csrc/custom_centroid.hip; the radially symmetric restraints of forces.py, which build on a class of
+    their own (forces.CustomCentroidBondForce), keep csrc/restraints.hip."""
+
+    def __init__(self, numGroups, energy):
+        super().__init__(energy)
+        self._n_groups_per_bond = int(numGroups)
+        self._groups = []                     # (particles, weights or None)
+        self._bonds = []                      # (g1, ..., gP, parameters)
+
+    def getNumGroupsPerBond(self):
+        return self._n_groups_per_bond
+
+    @staticmethod
+    def _checked_group(particles, weights):
+        particles = [int(p) for p in particles]
+        weights = None if weights is None or len(weights) == 0 else [float(w) for w in weights]
+        if weights is not None and len(weights) != len(particles):
+            raise ValueError('CustomCentroidBondForce: a group of %d particles with %d weights' % (len(particles), len(weights)))
+        return particles, weights
+
+    def addGroup(self, particles, weights=None):
+        self._groups.append(self._checked_group(particles, weights))
+        return len(self._groups) - 1
+
+    def getNumGroups(self):
+        return len(self._groups)
+
+    def getGroupParameters(self, index):
+        particles, weights = self._groups[index]
+        return list(particles), ([] if weights is None else list(weights))
+
+    def setGroupParameters(self, index, particles, weights=None):
+        self._groups[index] = self._checked_group(particles, weights)
+
+    def _bond(self, groups, parameters):
+        groups = [int(g) for g in groups]
+        if len(groups) != self._n_groups_per_bond:
+            raise ValueError('CustomCentroidBondForce: a bond of %d groups, the force declares %d' % (len(groups), self._n_groups_per_bond))
+        return tuple(groups) + ([float(p) for p in parameters],)
+
+    def addBond(self, groups, parameters=()):
+        self._bonds.append(self._bond(groups, parameters))
+        return len(self._bonds) - 1
+
+    def getNumBonds(self):
+        return len(self._bonds)
+
+    def getBondParameters(self, index):
+        bond = self._bonds[index]
+        return list(bond[:-1]), list(bond[-1])
+
+    def setBondParameters(self, index, groups, parameters=()):
+        self._bonds[index] = self._bond(groups, parameters)
+
+    def _term_arrays(self):
+        """the bonds' group numbers int32 [n][groups per bond] and parameters float64 [n][p]"""
+        return _term_arrays(self._bonds, self._n_groups_per_bond, len(self._per_bond), 'CustomCentroidBondForce')
+
+
 class CustomExternalForce(_CustomForce):
     """openmm.CustomExternalForce: the energy a function of a particle's x, y, z, of per-particle and of global parameters.  The
     harmonic-well expression of testsystems.HarmonicOscillator (testsystems.py:779-786) keeps the engine's own kernel (ext_K / ext_x0 /
@@ -928,7 +991,7 @@ def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
         d['restraints'] = {'%03d' % k: r for k, r in enumerate(restraints)}
     if custom:
         from .custom_expr import custom_terms_desc
-        terms = custom_terms_desc(custom)
+        terms = custom_terms_desc(custom, system.masses)
         if terms:
             d['custom_terms'] = terms
             # the handle's global-parameter columns, once (every entry above repeats them for remd_custom_force_desc)

@@ -153,6 +153,53 @@ def main():
         s.create(ths, [ss] * 8)
         run('4bo (1-GPU share, Boresch restraint): HostGuestExplicit + one six-particle CustomCompoundBondForce, 8 replicas x 64 states, '
             'g-BAOAB 2 fs x 500', s, 3)
+    for tag in ('4c1', '4cc'):
+        if tag not in which:
+            continue
+        # config 4's share with one centroid bond (custom_expr.py, csrc/custom_centroid.hip): '4c1' between two single-atom groups (a CB7
+        # and a guest heavy atom), '4cc' between the guest and ALL host atoms (30 and 126 atoms, mass weights); a quartic
+        # wall on the centroid distance, its global lambda_com rising 0 -> 1 along the coupled half and 1 where the guest is decoupled.
+        # After the timed iterations one more runs with the engine's profile on for the three launches of the feature.
+        from openmmtools_amd.system import CustomCentroidBondForce
+
+        class ComState(states.GlobalParameterState):
+            lambda_com = states.GlobalParameterState.GlobalParameter('lambda_com', standard_value=1.0)
+        hg = testsystems.HostGuestExplicit()
+        lam_e = np.concatenate([np.linspace(1.0, 0.0, 32), np.zeros(32)])
+        lam_s = np.concatenate([np.ones(32), np.linspace(1.0, 0.0, 32)])
+        lam_c = np.concatenate([np.linspace(0.0, 1.0, 32), np.ones(32)])
+        asys = alchemy.AbsoluteAlchemicalFactory().create_alchemical_system(hg.system, alchemy.AlchemicalRegion(alchemical_atoms=range(126, 156)))
+        f = CustomCentroidBondForce(2, 'lambda_com*K*max(0, distance(g1,g2)-r0)^4')
+        f.addGlobalParameter('lambda_com', 1.0)
+        f.addPerBondParameter('K'); f.addPerBondParameter('r0')
+        if tag == '4c1':
+            heavy = [i for i in range(126) if hg.system.getParticleMass(i) > 1.5]
+            guest = [i for i in range(126, 156) if hg.system.getParticleMass(i) > 1.5]
+            f.addGroup([heavy[0]]); f.addGroup([guest[0]])
+        else:
+            f.addGroup(list(range(0, 126))); f.addGroup(list(range(126, 156)))
+        f.addBond([0, 1], [500.0, 0.0])
+        f.setUsesPeriodicBoundaryConditions(True)
+        asys.addForce(f)
+        ths = [states.CompoundThermodynamicState(states.ThermodynamicState(asys, 300.0),
+                                                 [states.AlchemicalState(lambda_sterics=ls, lambda_electrostatics=le), ComState(lambda_com=lc)])
+               for le, ls, lc in zip(lam_e, lam_s, lam_c)]
+        engine = HipEngine()
+        s = SAMSSampler(mcmc_moves=move(2.0, 'V R R O R R V'), number_of_iterations=10 ** 9, engine=engine, seed=1)
+        ss = states.SamplerState(hg.positions, box_vectors=hg.system.getDefaultPeriodicBoxVectors())
+        s.create(ths, [ss] * 8)
+        run('%s (1-GPU share, centroid bond of groups of %d and %d atoms): HostGuestExplicit + one CustomCentroidBondForce, 8 replicas x 64 '
+            'states, g-BAOAB 2 fs x 500' % (tag, len(f.getGroupParameters(0)[0]), len(f.getGroupParameters(1)[0])), s, 3)
+        engine.profile_enable(1, 'custom_centroid')
+        engine.profile_reset()
+        s.run(1)
+        torch.cuda.synchronize()
+        out = {}
+        for name in ('custom_centroid_sum', 'custom_centroid_bonds', 'custom_centroid_spread'):
+            n, ms = engine.profile_get(name)
+            out[name] = dict(launches_timed=n, us_per_launch=1e3 * ms / max(n, 1))
+        engine.profile_enable(0)
+        print(json.dumps(dict(config=tag, profile=out)), flush=True)
     if '4cr' in which:
         # config 4's share with EVERY harmonic bond, harmonic angle and periodic torsion of the System moved to custom forces with the
         # same formulas (custom_expr.py): what the expression machine costs at a force field's size, against the built-in listed terms of '4'
