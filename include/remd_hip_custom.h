@@ -1,6 +1,6 @@
 /*
- * remd_hip_custom.h — GPU-only extension of the C ABI in remd_hip.h: custom bond, angle, torsion, external, compound-bond and
- * centroid-bond forces.
+ * remd_hip_custom.h — GPU-only extension of the C ABI in remd_hip.h: custom bond, angle, torsion, external, compound-bond,
+ * centroid-bond and nonbonded forces.
  *
  * OpenMM's CustomBondForce, CustomAngleForce, CustomTorsionForce and CustomExternalForce: an energy expression of r (bond), theta
  * (angle, torsion) or x, y, z (external), of per-term parameters and of global parameters, evaluated per term.  The host compiles
@@ -32,7 +32,20 @@
  * group may be named by any number of bonds, an atom may sit in any number of groups.  The restraint forms of remd_hip_restraints.h keep
  * their own entry points.
  *
- * Not provided: tabulated functions, pointangle, pointdihedral.
+ * Nonbonded forces (REMD_CUSTOM_NONBONDED, OpenMM's CustomNonbondedForce): the energy is an expression of the distance r of two
+ * particles (REMD_CX_VAR 0), summed over every pair i < j that no exclusion names and, with a cutoff, that lies inside it.  n_terms is
+ * the system's particle count N, params is [N][n_params] with n_params <= REMD_CUSTOM_MAX_PARAMS / 2, atoms is NULL, and REMD_CX_PARAM
+ * operand k is parameter k of the pair's first particle, n_params + k of its second.  nb_method: 0 every pair, 1 a cutoff without and 2
+ * with minimum images under the replica's own box (periodic = 1 exactly then; every box edge must stay >= 2 cutoff, also under a
+ * barostat).  switch_distance in (0, cutoff) multiplies the energy by OpenMM's switching function 1 - 10 t^3 + 15 t^4 - 6 t^5,
+ * t = (r - switch_distance) / (cutoff - switch_distance); < 0: none.  Exclusions in CSR form, symmetric (j in i's row and i in j's),
+ * each row sorted.  long_range_correction = 1 (nb_method 2 only): the force's energy gains coeff[state][force] / V, V the replica's own
+ * box volume and coeff the host's integral of the expression beyond the cutoff under the state's globals (remd_set_custom_lrc, to be
+ * called after every remd_set_custom_globals: the forces refuse to act on coefficients older than the globals); the u_kl rows gain
+ * beta_l (coeff_l - coeff_own) / V.  One wavefront per tile of 64 x 64 particles, every tile visited (csrc/custom_nonbonded.hip): the
+ * cost is quadratic in N.
+ *
+ * Not provided: tabulated functions, pointangle, pointdihedral, interaction groups.
  *
  * Global parameters belong to the handle: every force's program addresses the same n_globals columns, and every state carries one
  * value per column (remd_set_custom_globals).  A term acts in every force evaluation (MD steps, energies, the barostat,
@@ -61,6 +74,7 @@ extern "C" {
 #define REMD_CUSTOM_EXTERNAL 3     /* atoms [n][1], variables x, y, z                                                       */
 #define REMD_CUSTOM_COMPOUND 4     /* atoms [n][n_particles], variables x1, y1, z1, ..., and functions of the particles     */
 #define REMD_CUSTOM_CENTROID 5     /* atoms [n][n_particles] are GROUP numbers; the particles are the groups' centroids     */
+#define REMD_CUSTOM_NONBONDED 6    /* atoms NULL, n_terms = N, params [N][n_params]; variable r of every pair inside the cutoff */
 
 #define REMD_CUSTOM_MAX_PROGRAM 256
 #define REMD_CUSTOM_MAX_STACK   16
@@ -131,6 +145,13 @@ typedef struct remd_custom_force_desc {
     const int32_t* group_offsets;  /* [n_groups + 1]: group g holds group_atoms[group_offsets[g] ... group_offsets[g + 1]), none empty */
     const int32_t* group_atoms;    /* atom indices, 0 ... N - 1                                                            */
     const double* group_weights;   /* beside group_atoms: >= 0, summing to 1 in every group (within 1e-12)                 */
+    /* REMD_CUSTOM_NONBONDED only (every other kind ignores them)                                                         */
+    int32_t nb_method;             /* 0 NoCutoff, 1 CutoffNonPeriodic, 2 CutoffPeriodic                                    */
+    double cutoff;                 /* nm (nb_method 1, 2)                                                                  */
+    double switch_distance;        /* nm, in (0, cutoff); < 0: no switching function                                       */
+    const int32_t* excl_offsets;   /* [N + 1]: particle i is excluded from excl_atoms[excl_offsets[i] ... excl_offsets[i + 1]) */
+    const int32_t* excl_atoms;     /* particle indices, symmetric, sorted within a row, never the row's own particle       */
+    int32_t long_range_correction; /* 1: the energy gains coeff / V (remd_set_custom_lrc); nb_method 2 only                */
 } remd_custom_force_desc;
 
 /* the custom forces of the system; call after remd_set_system (which forgets them).  n = 0: none.  Every custom force of a handle
@@ -139,6 +160,9 @@ int  remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, in
 /* values[K][n_globals]: every state's value of each global column; K as in remd_set_states (call after it: the terms refuse to act
    on globals that belong to an older set of states)                                                                              */
 int  remd_set_custom_globals(remd_handle h, const double* values);
+/* coeff[K][n]: the long-range correction of every state and custom force (kJ/mol nm^3; 0 for a force without one), the descriptors'
+   order; call after remd_set_custom_globals (which forgets the coefficients: they are integrals under the globals)               */
+int  remd_set_custom_lrc(remd_handle h, const double* coeff);
 /* out[R_local][n]: each custom force's energy, in the order of the descriptors whatever their kinds (kJ/mol) at the local replicas' current positions and own states                   */
 int  remd_get_custom_energies(remd_handle h, double* out);
 

@@ -76,7 +76,9 @@ class RemdCustomForceDesc(C.Structure):
                 ('n_program', C.c_int32), ('program', c_int32_p), ('n_consts', C.c_int32), ('consts', c_double_p),
                 ('stack_depth', C.c_int32), ('n_globals', C.c_int32), ('global_defaults', c_double_p),
                 ('periodic', C.c_int32), ('force_group', C.c_int32), ('n_particles', C.c_int32),
-                ('n_groups', C.c_int32), ('group_offsets', c_int32_p), ('group_atoms', c_int32_p), ('group_weights', c_double_p)]
+                ('n_groups', C.c_int32), ('group_offsets', c_int32_p), ('group_atoms', c_int32_p), ('group_weights', c_double_p),
+                ('nb_method', C.c_int32), ('cutoff', C.c_double), ('switch_distance', C.c_double), ('excl_offsets', c_int32_p),
+                ('excl_atoms', c_int32_p), ('long_range_correction', C.c_int32)]
 
 
 class RemdGbModelDesc(C.Structure):
@@ -88,7 +90,7 @@ class RemdGbModelDesc(C.Structure):
 # the GPU-only extension of include/remd_hip_restraints.h: bound where the loaded library exports it (the CPU port of the ABI does not)
 RESTRAINT_EXPORTS = ['remd_set_restraints', 'remd_set_restraint_lambdas', 'remd_get_restraint_energies']
 # the GPU-only extension of include/remd_hip_custom.h (custom bond / angle / torsion / external forces), bound the same way
-CUSTOM_EXPORTS = ['remd_set_custom_terms', 'remd_set_custom_globals', 'remd_get_custom_energies']
+CUSTOM_EXPORTS = ['remd_set_custom_terms', 'remd_set_custom_globals', 'remd_set_custom_lrc', 'remd_get_custom_energies']
 # the GPU-only extension of include/remd_hip_barostat.h (per-axis Monte Carlo barostats), bound the same way
 BAROSTAT_AXIS_EXPORTS = ['remd_set_barostat_axes', 'remd_get_barostat_axis_stats']
 BAROSTAT_ANISOTROPIC, BAROSTAT_MEMBRANE = 1, 2
@@ -206,6 +208,7 @@ def load_library(path=None):
     if hasattr(lib, 'remd_set_custom_terms'):             # include/remd_hip_custom.h (GPU-only, like the restraints)
         lib.remd_set_custom_terms.argtypes = [vp, C.POINTER(RemdCustomForceDesc), C.c_int]
         lib.remd_set_custom_globals.argtypes = [vp, c_double_p]
+        lib.remd_set_custom_lrc.argtypes = [vp, c_double_p]
         lib.remd_get_custom_energies.argtypes = [vp, c_double_p]
         for name in CUSTOM_EXPORTS:
             getattr(lib, name).restype = C.c_int
@@ -487,6 +490,7 @@ class HipEngine:
         if restraints:                                   # receptor-ligand restraints (forces.py; csrc/restraints.hip)
             self.set_restraints([restraints[k] for k in sorted(restraints)])
         self.n_custom = self.n_custom_globals = 0
+        self._custom_lrc = None
         custom = desc_dict.get('custom_terms')
         if custom:                                       # custom bond / angle / torsion / external forces (custom_expr.py; csrc/custom_terms.hip)
             self.set_custom_terms([custom[k] for k in sorted(custom)])
@@ -525,8 +529,8 @@ class HipEngine:
 
     def _custom_entry(self, name):
         if not hasattr(self.lib, name):
-            raise NotImplementedError('%s: this build of the engine library has no custom bond / angle / torsion / external forces and no compound-bond forces '
-                                      'or centroid-bond forces (include/remd_hip_custom.h is GPU-only)' % name)
+            raise NotImplementedError('%s: this build of the engine library has no custom bond / angle / torsion / external forces and no compound-bond forces, '
+                                      'centroid-bond forces or nonbonded custom forces (include/remd_hip_custom.h is GPU-only)' % name)
         return getattr(self.lib, name)
 
     def set_custom_terms(self, terms):
@@ -536,7 +540,10 @@ class HipEngine:
         keep = []
         for k, t in enumerate(terms):
             atoms = np.ascontiguousarray(t['atoms'], dtype=np.int32)
-            params = np.ascontiguousarray(t['params'], dtype=np.float64).reshape(len(atoms), -1)
+            nonbonded = 'excl_offsets' in t                          # a nonbonded force: no atoms, one parameter row per particle
+            params = np.ascontiguousarray(t['params'], dtype=np.float64)
+            n_terms = len(params) if nonbonded else len(atoms)
+            params = params.reshape(n_terms, -1)
             n_particles = int(t.get('n_particles', 0))               # a compound-bond force: atoms [n][n_particles]
             program = np.ascontiguousarray(t['program'], dtype=np.int32).reshape(-1, 2)
             consts = np.ascontiguousarray(t['consts'], dtype=np.float64)
@@ -549,18 +556,33 @@ class HipEngine:
                 g_w = np.ascontiguousarray(t['group_weights'], dtype=np.float64)
                 keep += [g_off, g_atoms, g_w]
                 groups = (len(g_off) - 1, _ip(g_off), _ip(g_atoms), _dp(g_w))
-            arr[k] = RemdCustomForceDesc(int(t['kind']), len(atoms), _ip(atoms), params.shape[1], _dp(params), len(program), _ip(program),
+            pairs = (0, 0.0, -1.0, None, None, 0)
+            if nonbonded:
+                e_off = np.ascontiguousarray(t['excl_offsets'], dtype=np.int32)
+                e_atoms = np.ascontiguousarray(t['excl_atoms'], dtype=np.int32)
+                keep += [e_off, e_atoms]
+                pairs = (int(t['nb_method']), float(t['cutoff']), float(t['switch_distance']), _ip(e_off), _ip(e_atoms) if len(e_atoms) else None,
+                         int(t['long_range_correction']))
+            arr[k] = RemdCustomForceDesc(int(t['kind']), n_terms, None if nonbonded else _ip(atoms), params.shape[1], _dp(params), len(program), _ip(program),
                                          len(consts), _dp(consts), int(t['stack_depth']), len(defaults), _dp(defaults),
-                                         int(t['periodic']), int(t['force_group']), n_particles, *groups)
+                                         int(t['periodic']), int(t['force_group']), n_particles, *groups, *pairs)
         self._check(fn(self.h, arr, len(terms)), 'remd_set_custom_terms')
         self.n_custom = len(terms)
         self.n_custom_globals = len(terms[0]['global_defaults']) if terms else 0
+        # the long-range corrections of nonbonded forces: host integrals under every state's globals (custom_expr.LongRangeCorrection),
+        # handed over behind every set_custom_globals
+        self._custom_lrc = (list(terms), {}) if any(t.get('long_range_correction') for t in terms) else None
 
     def set_custom_globals(self, values):
         """[K][n_globals]: every state's value of each global parameter of the custom forces (after set_states)."""
         fn = self._custom_entry('remd_set_custom_globals')
         values = np.ascontiguousarray(values, dtype=np.float64).reshape(self.K, self.n_custom_globals)
         self._check(fn(self.h, _dp(values)), 'remd_set_custom_globals')
+        if getattr(self, '_custom_lrc', None) is not None:
+            from .custom_expr import long_range_coefficients
+            terms, cache = self._custom_lrc
+            coeff = np.ascontiguousarray(long_range_coefficients(terms, values, cache), dtype=np.float64)
+            self._check(self._custom_entry('remd_set_custom_lrc')(self.h, _dp(coeff)), 'remd_set_custom_lrc')
 
     def custom_energies(self):
         """[R_local][n_custom] energy (kJ/mol) of each custom force at the current positions and the replicas' own states."""

@@ -94,6 +94,11 @@ class AbsoluteAlchemicalFactory:
         names = [r.name for r in regions]
         if len(regions) > 1 and (None in names or len(set(names)) != len(names)):
             raise ValueError('several alchemical regions need distinct names')                          # alchemy.py:666-672
+        from .system import CustomNonbondedForce
+        if any(isinstance(f, CustomNonbondedForce) for f in reference_system.getForces()):
+            # _alchemically_modify_CustomNonbondedForce (alchemy.py:2347-2396) is not built
+            raise NotImplementedError('AbsoluteAlchemicalFactory: a System with a CustomNonbondedForce (the alchemical modification of a '
+                                      'CustomNonbondedForce is not supported)')
         system = copy.deepcopy(reference_system)
         n = system.getNumParticles()
         seen = set()

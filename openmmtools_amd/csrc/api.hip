@@ -279,6 +279,9 @@ int remd_set_replicas(remd_handle h, int R_global, int r_begin, int R_local, con
     if (h->nb_method != REMD_NB_NONE && box)
         for (int r = 0; r < R_local; ++r) for (int k = 0; k < 3; ++k)
             if (!(box[3 * r + k] >= 2.0 * h->cutoff)) return remd_fail(h, -1, "remd_set_replicas: box smaller than twice the cutoff");
+    if (h->cst_cutoff > 0.0 && box)                  // (a CutoffPeriodic CustomNonbondedForce: the same minimum-image condition)
+        for (int r = 0; r < R_local; ++r) for (int k = 0; k < 3; ++k)
+            if (!(box[3 * r + k] >= 2.0 * h->cst_cutoff)) return remd_fail(h, -1, "remd_set_replicas: box smaller than twice the cutoff of a custom nonbonded force");
     hipSetDevice(h->device);
     const bool realloc = (R_local != h->R) || (R_global != h->R_global) || !h->d_pos;
     if (h->d_noise_id) { hipStreamSynchronize(h->stream); h->d_noise_id.reset(); }     // ids belong to one set of replicas
@@ -399,6 +402,9 @@ int remd_copy_replicas(remd_handle dst, const int32_t* dst_slot, remd_handle src
         if (dst->nb_method != REMD_NB_NONE)
             for (int r = 0; r < dst->R; ++r) for (int k = 0; k < 3; ++k)
                 if (dst->box_host[3 * r + k] < 2.0 * dst->cutoff) return remd_fail(dst, -1, "remd_copy_replicas: box smaller than twice the cutoff");
+        if (dst->cst_cutoff > 0.0)
+            for (int r = 0; r < dst->R; ++r) for (int k = 0; k < 3; ++k)
+                if (dst->box_host[3 * r + k] < 2.0 * dst->cst_cutoff) return remd_fail(dst, -1, "remd_copy_replicas: box smaller than twice the cutoff of a custom nonbonded force");
         if (changed) {
             dst->box_uniform = true;
             for (int r = 1; r < dst->R; ++r) for (int k = 0; k < 3; ++k) if (hb[4 * r + k] != hb[k]) dst->box_uniform = false;

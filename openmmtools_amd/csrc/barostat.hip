@@ -242,8 +242,9 @@ int remd_barostat_buffers(remd_ctx* h)
 int remd_barostat_attempt(remd_ctx* h)
 {
     const int* grp_first = nullptr; const int* grp_size = nullptr;
-    const int n_groups = remd_nb_molecules(h, &grp_first, &grp_size);
-    if (n_groups <= 0) return remd_fail(h, -3, "barostat: the system has no molecule table (needs a NonbondedForce)");
+    int n_groups = remd_nb_molecules(h, &grp_first, &grp_size);
+    if (n_groups <= 0) n_groups = remd_custom_molecules(h, &grp_first, &grp_size);     // (a System whose only pair force is a CustomNonbondedForce)
+    if (n_groups <= 0) return remd_fail(h, -3, "barostat: the system has no molecule table (needs a NonbondedForce, or a CutoffPeriodic CustomNonbondedForce whose molecules are contiguous and joined by custom forces only)");
     const int R = h->R, Npad = h->Npad;
     int rc;
     if ((rc = remd_barostat_buffers(h))) return rc;
@@ -274,11 +275,11 @@ int remd_barostat_attempt(remd_ctx* h)
                            h->d_baro_U0, h->d_potential, h->d_labels, h->d_beta, h->d_pressure,
                            h->baro_kind == REMD_BAROSTAT_MEMBRANE ? (const double*)h->d_tension : (const double*)nullptr, h->d_econst, h->econst_vref,
                            h->d_box, h->d_box_old, h->d_baro_axis, h->d_baro_acc, h->d_noise_id,
-                           (float)(2.0 * std::max(h->cutoff, h->coulomb_cutoff)), h->d_sync + 2);
+                           (float)(2.0 * std::max(std::max(h->cutoff, h->coulomb_cutoff), h->cst_cutoff)), h->d_sync + 2);
     else
     hipLaunchKernelGGL(baro_decide_kernel, dim3((R + 63) / 64), dim3(64), 0, h->stream, R, h->r_begin, h->seed, attempt, n_groups,
                        h->d_baro_U0, h->d_potential, h->d_labels, h->d_beta, h->d_pressure, h->d_econst, h->econst_vref, h->d_box, h->d_box_old, h->d_baro,
-                       h->d_baro_acc, h->d_noise_id, (float)(2.0 * std::max(h->cutoff, h->coulomb_cutoff)), h->d_sync + 2);
+                       h->d_baro_acc, h->d_noise_id, (float)(2.0 * std::max(std::max(h->cutoff, h->coulomb_cutoff), h->cst_cutoff)), h->d_sync + 2);
     hipLaunchKernelGGL(baro_restore_kernel, dim3((h->N + 255) / 256, R), dim3(256), 0, h->stream, h->N, Npad, h->d_baro_acc, h->d_pos,
                        h->d_baro_x0, h->d_force, h->d_baro_f0, h->d_potential, h->d_baro_U0);
     h->box_version++;

@@ -18,11 +18,17 @@ struct cst_force {
     int slot0, npad;             // first slot in the padded term space of the launch / slots of this force (a multiple of 64)
     int par0;                    // offset of its parameters [n_params][npad]
     int prog0, n_prog, const0;   // its program and constants in the handle's tables
+    // REMD_CUSTOM_NONBONDED only (custom_nonbonded.hip): n_terms = N particles, npad = 64 x its upper-triangular tiles, parameters [n_params][Npad]
+    int nb_method;               // 0 NoCutoff, 1 CutoffNonPeriodic, 2 CutoffPeriodic
+    int excl0;                   // its row offsets [N + 1] in the handle's excl_off (which point into the handle's excl_atoms)
+    int lrc;                     // 1: it has a long-range correction (the handle's lrc table carries its column)
+    double cutoff, switch_dist;  // switch_dist < 0: no switching function
 };
 
 struct cst_tables {
     int nf = 0, ng = 0, K = 0, total_pad = 0, waves_simple = 0; long long glob_version = -1;   // (waves_simple: the wavefronts of the four one-variable kinds, in front; glob belongs to the states of that remd_set_states)
-    int waves_particles = 0;                                                   // where the compound-bond forces' wavefronts end and the centroid forces' begin (the last part)
+    int waves_compound = 0;                                                    // where the compound-bond forces' wavefronts end and the nonbonded forces' tiles begin
+    int waves_particles = 0;                                                   // where the nonbonded forces' tiles end and the centroid forces' wavefronts begin (the last part)
     int n_groups = 0;                                                          // the groups of all centroid forces (0: no centroid force, none of the members below holds anything)
     bool uniform = true;                                                       // every state carries the same globals: no u_kl share
     std::vector<cst_force> F; std::vector<int> wave_force, atoms; std::vector<double> par, consts, glob, defaults; std::vector<int2> prog;
@@ -40,6 +46,16 @@ struct cst_tables {
     dev_array<int> d_refs;             // (centroid slot * REMD_CUSTOM_MAX_PARTICLES + position in the bond) of every bond that names the group, in table order
     dev_array<double> d_C;             // [R][n_groups][3] centroids
     dev_array<double> d_G;             // [R][centroid slots][REMD_CUSTOM_MAX_PARTICLES][3] dE / d centroid
+    // nonbonded forces (custom_nonbonded.hip): the exclusion rows of all of them, and the long-range coefficients of the states
+    std::vector<int> excl_off, excl_atoms; std::vector<double> lrc;
+    dev_array<int> d_excl_off;         // per nonbonded force N + 1 offsets into excl_atoms (cst_force::excl0 names the first)
+    dev_array<int> d_excl_atoms;       // symmetric, sorted within a row
+    dev_array<double> d_lrc;           // [K][nf] kJ/mol nm^3: the energy is lrc[state][force] / V (zero for a force without the correction)
+    bool has_lrc = false, lrc_valid = false;   // (lrc_valid: remd_set_custom_lrc ran since the globals were last set)
+    double periodic_cutoff = 0.0;      // the longest cutoff of a CutoffPeriodic nonbonded force (remd_ctx::cst_cutoff)
+    // the molecules a barostat moves as wholes where the handle has no NonbondedForce to take them from (remd_custom_molecules): atoms
+    // the custom bonds, angles, torsions and compound bonds join, each a contiguous range [first, first + size); empty: no table
+    std::vector<int> mol_first, mol_size; dev_array<int> d_mol_first; dev_array<int> d_mol_size;
 };
 
 namespace {
@@ -237,3 +253,9 @@ void remd_custom_compound_ukl(remd_ctx* h, cst_tables& t);
 // custom_centroid.hip: the same for the centroid forces' wavefronts (those behind waves_particles): centroids, bonds, spread
 void remd_custom_centroid_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
 void remd_custom_centroid_ukl(remd_ctx* h, cst_tables& t);
+// custom_nonbonded.hip: the same for the nonbonded forces' tiles (those between waves_compound and waves_particles), and the long-range
+// correction's share of the energies (behind custom_reduce_kernel) and of the u_kl rows (behind custom_ukl_reduce_kernel)
+void remd_custom_nonbonded_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
+void remd_custom_nonbonded_lrc(remd_ctx* h, cst_tables& t, int ep_slot, hipStream_t st);
+void remd_custom_nonbonded_ukl(remd_ctx* h, cst_tables& t);
+void remd_custom_nonbonded_lrc_ukl(remd_ctx* h, cst_tables& t, double* d_rows);

@@ -25,7 +25,8 @@
 //
 // The machine itself (cst_eval) lives in custom_machine.h: custom_compound.hip runs the same one for CustomCompoundBondForce, whose
 // wavefronts follow the ones of this file's four kinds in the padded term space and share the energy and u_kl reductions below, and
-// custom_centroid.hip runs it for CustomCentroidBondForce, whose wavefronts come last.
+// custom_centroid.hip runs it for CustomCentroidBondForce, whose wavefronts come last; custom_nonbonded.hip runs it for
+// CustomNonbondedForce, one wavefront per tile of 64 x 64 atoms, between those two.
 #include "remd_internal.h"
 #include "listed_terms.h"
 #include "custom_machine.h"
@@ -207,7 +208,8 @@ int set_tables(remd_ctx* h, cst_tables& t)
         (rc = t.d_par.upload(h, t.par)) || (rc = t.d_consts.upload(h, t.consts)) || (rc = t.d_glob.upload(h, t.glob)) ||
         (rc = t.d_prog.upload(h, t.prog)) || (rc = t.d_grp_off.upload(h, t.grp_off)) || (rc = t.d_grp_atoms.upload(h, t.grp_atoms)) ||
         (rc = t.d_grp_w.upload(h, t.grp_w)) || (rc = t.d_grp_periodic.upload(h, t.grp_periodic)) || (rc = t.d_ref_off.upload(h, t.ref_off)) ||
-        (rc = t.d_refs.upload(h, t.refs))) return rc;
+        (rc = t.d_refs.upload(h, t.refs)) || (rc = t.d_excl_off.upload(h, t.excl_off)) || (rc = t.d_excl_atoms.upload(h, t.excl_atoms)) ||
+        (rc = t.d_lrc.upload(h, t.lrc)) || (rc = t.d_mol_first.upload(h, t.mol_first)) || (rc = t.d_mol_size.upload(h, t.mol_size))) return rc;
     t.d_E.reset(); t.d_Ewave.reset(); t.d_D.reset(); t.d_C.reset(); t.d_G.reset();
     return 0;
 }
@@ -222,6 +224,7 @@ bool globals_uniform(const cst_tables& t)
 const char* check_program(const remd_custom_force_desc& d, int n_vars)
 {
     const bool compound = d.kind == REMD_CUSTOM_COMPOUND || d.kind == REMD_CUSTOM_CENTROID;
+    const int n_par = d.kind == REMD_CUSTOM_NONBONDED ? 2 * d.n_params : d.n_params;     // (a pair: particle 1's parameters, then particle 2's)
     if (d.n_program <= 0 || !d.program) return "an empty program";
     if (d.n_program > REMD_CUSTOM_MAX_PROGRAM) return "a program over REMD_CUSTOM_MAX_PROGRAM instructions";
     int sp = 0, top = 0;
@@ -231,7 +234,7 @@ const char* check_program(const remd_custom_force_desc& d, int n_vars)
         switch (op) {
         case REMD_CX_CONST:  if (arg < 0 || arg >= d.n_consts || !d.consts) return "a constant index out of range"; pops = 0; break;
         case REMD_CX_VAR:    if (arg < 0 || arg >= n_vars) return "a variable index out of range"; pops = 0; break;
-        case REMD_CX_PARAM:  if (arg < 0 || arg >= d.n_params) return "a parameter index out of range"; pops = 0; break;
+        case REMD_CX_PARAM:  if (arg < 0 || arg >= n_par) return "a parameter index out of range"; pops = 0; break;
         case REMD_CX_GLOBAL: if (arg < 0 || arg >= d.n_globals) return "a global-parameter index out of range"; pops = 0; break;
         case REMD_CX_ADD: case REMD_CX_SUB: case REMD_CX_MUL: case REMD_CX_DIV: case REMD_CX_POW: case REMD_CX_ATAN2:
         case REMD_CX_MIN: case REMD_CX_MAX: pops = 2; break;
@@ -260,10 +263,18 @@ const char* check_program(const remd_custom_force_desc& d, int n_vars)
 
 }  // namespace
 
+int remd_custom_molecules(remd_ctx* h, const int** first, const int** size)
+{
+    cst_tables* t = h->cst.get();
+    if (!t || h->n_custom == 0 || t->mol_first.empty()) return 0;
+    *first = t->d_mol_first; *size = t->d_mol_size;
+    return (int)t->mol_first.size();
+}
+
 void remd_custom_release(remd_ctx* h)
 {
     if (h->cst) { hipStreamSynchronize(h->stream); if (h->stream2) hipStreamSynchronize(h->stream2); h->cst.reset(); }
-    h->n_custom = 0; h->cst_group = 0;
+    h->n_custom = 0; h->cst_group = 0; h->cst_cutoff = 0.0;
 }
 
 int remd_custom_clone(remd_ctx* parent, remd_ctx* child)
@@ -273,7 +284,9 @@ int remd_custom_clone(remd_ctx* parent, remd_ctx* child)
     child->cst.reset(new cst_tables());
     cst_tables& c = *child->cst;
     c.nf = t->nf; c.ng = t->ng; c.K = t->K; c.total_pad = t->total_pad; c.waves_simple = t->waves_simple; c.uniform = t->uniform;
-    c.waves_particles = t->waves_particles; c.n_groups = t->n_groups;
+    c.waves_particles = t->waves_particles; c.n_groups = t->n_groups; c.waves_compound = t->waves_compound;
+    c.excl_off = t->excl_off; c.excl_atoms = t->excl_atoms; c.lrc = t->lrc; c.has_lrc = t->has_lrc; c.lrc_valid = t->lrc_valid; c.periodic_cutoff = t->periodic_cutoff;
+    c.mol_first = t->mol_first; c.mol_size = t->mol_size;
     c.grp_off = t->grp_off; c.grp_atoms = t->grp_atoms; c.grp_w = t->grp_w; c.grp_periodic = t->grp_periodic; c.ref_off = t->ref_off; c.refs = t->refs;
     c.glob_version = t->glob_version == parent->states_version ? child->states_version : -1;
     c.F = t->F; c.wave_force = t->wave_force; c.atoms = t->atoms; c.par = t->par; c.consts = t->consts; c.glob = t->glob;
@@ -281,7 +294,7 @@ int remd_custom_clone(remd_ctx* parent, remd_ctx* child)
     hipSetDevice(child->device);
     const int rc = set_tables(child, c);
     if (rc) return remd_fail(parent, rc, std::string("phases: ") + child->err);
-    child->n_custom = parent->n_custom; child->cst_group = parent->cst_group;
+    child->n_custom = parent->n_custom; child->cst_group = parent->cst_group; child->cst_cutoff = parent->cst_cutoff;
     child->config_version++;
     return 0;
 }
@@ -294,6 +307,8 @@ int remd_custom_forces(remd_ctx* h, bool with_energy, int ep_slot, hipStream_t s
     cst_tables& t = *tp;
     if (t.K != h->K || t.glob_version != h->states_version)
         return remd_fail(h, -1, "custom terms: the states changed since remd_set_custom_globals (call it after remd_set_states)");
+    if (t.has_lrc && !t.lrc_valid)
+        return remd_fail(h, -1, "custom terms: a nonbonded force has a long-range correction and the globals changed since remd_set_custom_lrc (call it after remd_set_custom_globals)");
     int rc = ensure_buffers(h, t); if (rc) return rc;
     const int waves = t.total_pad / 64;
     remd_prof_scope ps(h, "custom_terms", st);
@@ -307,10 +322,12 @@ int remd_custom_forces(remd_ctx* h, bool with_energy, int ep_slot, hipStream_t s
                                t.d_wave_force, t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, h->d_labels, h->r_begin, h->Npad, h->d_pos,
                                h->d_box, h->d_force, t.d_Ewave);
     }
-    if (t.waves_particles > t.waves_simple) remd_custom_compound_forces(h, t, with_energy, st);   // (custom_compound.hip: the wavefronts behind)
+    if (t.waves_compound > t.waves_simple) remd_custom_compound_forces(h, t, with_energy, st);    // (custom_compound.hip: the wavefronts behind)
+    if (t.waves_particles > t.waves_compound) remd_custom_nonbonded_forces(h, t, with_energy, st); // (custom_nonbonded.hip: the tiles behind those)
     if (waves > t.waves_particles) remd_custom_centroid_forces(h, t, with_energy, st);            // (custom_centroid.hip: the last ones)
     if (with_energy)
         hipLaunchKernelGGL(custom_reduce_kernel, dim3(h->R), dim3(64), 0, st, t.nf, t.d_F, waves, t.d_Ewave, t.d_E, h->d_epart, h->n_epart, ep_slot);
+    if (with_energy && t.has_lrc) remd_custom_nonbonded_lrc(h, t, ep_slot, st);
     REMD_CHECK(h, hipGetLastError());
     return 0;
 }
@@ -323,6 +340,8 @@ int remd_custom_ukl(remd_ctx* h, double* d_rows)
     cst_tables& t = *tp;
     if (t.K != h->K || t.glob_version != h->states_version)
         return remd_fail(h, -1, "custom terms: the states changed since remd_set_custom_globals (call it after remd_set_states)");
+    if (t.has_lrc && !t.lrc_valid)
+        return remd_fail(h, -1, "custom terms: a nonbonded force has a long-range correction and the globals changed since remd_set_custom_lrc (call it after remd_set_custom_globals)");
     if (t.uniform) return 0;                          // every state carries the same globals: the share is exactly zero
     const int waves = t.total_pad / 64;
     const size_t nD = (size_t)h->R * h->K * waves;
@@ -331,9 +350,11 @@ int remd_custom_ukl(remd_ctx* h, double* d_rows)
     if (t.waves_simple > 0)
         hipLaunchKernelGGL(custom_ukl_kernel, dim3(t.waves_simple, h->R), dim3(64), 0, h->stream, t.total_pad, waves, t.d_F, t.d_wave_force,
                            t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, h->K, h->d_labels, h->r_begin, h->Npad, h->d_pos, h->d_box, t.d_D);
-    if (t.waves_particles > t.waves_simple) remd_custom_compound_ukl(h, t);
+    if (t.waves_compound > t.waves_simple) remd_custom_compound_ukl(h, t);
+    if (t.waves_particles > t.waves_compound) remd_custom_nonbonded_ukl(h, t);
     if (waves > t.waves_particles) remd_custom_centroid_ukl(h, t);
     hipLaunchKernelGGL(custom_ukl_reduce_kernel, dim3(h->K, h->R), dim3(64), 0, h->stream, h->K, waves, t.d_D, h->d_beta, d_rows);
+    if (t.has_lrc) remd_custom_nonbonded_lrc_ukl(h, t, d_rows);
     REMD_CHECK(h, hipGetLastError());
     return 0;
 }
@@ -358,19 +379,43 @@ int remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, int
     for (int i = 0; i < n; ++i) {
         const remd_custom_force_desc& d = desc[i];
         const std::string who = "remd_set_custom_terms: force " + std::to_string(i) + ": ";
-        if (d.kind < 0 || d.kind > REMD_CUSTOM_CENTROID) return remd_fail(h, -1, who + "unknown kind");
+        if (d.kind < 0 || d.kind > REMD_CUSTOM_NONBONDED) return remd_fail(h, -1, who + "unknown kind");
+        const bool nonbonded = d.kind == REMD_CUSTOM_NONBONDED;
         const bool centroid = d.kind == REMD_CUSTOM_CENTROID, compound = d.kind == REMD_CUSTOM_COMPOUND || centroid;
         if (compound ? (d.n_particles < 1 || d.n_particles > REMD_CUSTOM_MAX_PARTICLES) : d.n_particles != 0)
             return remd_fail(h, -1, who + "n_particles is 1 ... REMD_CUSTOM_MAX_PARTICLES for a compound-bond or centroid-bond force and 0 for every other kind");
-        const int wd = compound ? d.n_particles : width4[d.kind];
-        if (d.n_terms <= 0 || !d.atoms) return remd_fail(h, -1, who + "no terms");
+        const int wd = compound ? d.n_particles : nonbonded ? 0 : width4[d.kind];
+        if (d.n_terms <= 0 || (!d.atoms && !nonbonded)) return remd_fail(h, -1, who + "no terms");
         if (d.n_params < 0 || d.n_params > REMD_CUSTOM_MAX_PARAMS || (d.n_params > 0 && !d.params))
             return remd_fail(h, -1, who + "0 ... REMD_CUSTOM_MAX_PARAMS parameters per term are supported");
+        if (nonbonded) {
+            // what custom_nonbonded.hip indexes unchecked: one parameter row per atom of the system, 2 n_params operands, the exclusion rows
+            if (d.n_terms != h->N) return remd_fail(h, -1, who + "a nonbonded force has " + std::to_string(d.n_terms) + " particles, the system has " + std::to_string(h->N));
+            if (2 * d.n_params > REMD_CUSTOM_MAX_PARAMS) return remd_fail(h, -1, who + "a nonbonded force takes at most REMD_CUSTOM_MAX_PARAMS / 2 per-particle parameters");
+            if (d.nb_method < 0 || d.nb_method > 2) return remd_fail(h, -1, who + "unknown nonbonded method (0 NoCutoff, 1 CutoffNonPeriodic, 2 CutoffPeriodic)");
+            if ((d.periodic != 0) != (d.nb_method == 2)) return remd_fail(h, -1, who + "a nonbonded force is periodic exactly where its method is CutoffPeriodic");
+            if (d.nb_method != 0 && !(d.cutoff > 0.0)) return remd_fail(h, -1, who + "a cutoff that is not positive");
+            if (d.switch_distance >= 0.0 && (d.nb_method == 0 || !(d.switch_distance > 0.0 && d.switch_distance < d.cutoff)))
+                return remd_fail(h, -1, who + "the switching distance must lie in (0, cutoff) and needs a cutoff");
+            if (d.long_range_correction && d.nb_method != 2) return remd_fail(h, -1, who + "a long-range correction needs CutoffPeriodic");
+            if (!d.excl_offsets || d.excl_offsets[0] != 0) return remd_fail(h, -1, who + "excl_offsets [N + 1] must start at 0");
+            for (int a = 0; a < d.n_terms; ++a) {
+                const int b = d.excl_offsets[a], e = d.excl_offsets[a + 1];
+                if (e < b || (e > b && !d.excl_atoms)) return remd_fail(h, -1, who + "excl_offsets must not decrease");
+                for (int k = b; k < e; ++k) {
+                    if (d.excl_atoms[k] < 0 || d.excl_atoms[k] >= d.n_terms) return remd_fail(h, -1, who + "exclusion index out of range");
+                    if (d.excl_atoms[k] == a) return remd_fail(h, -1, who + "a particle excluded from itself");
+                }
+            }
+            if (d.nb_method == 2 && !h->box_host.empty())
+                for (size_t k = 0; k < h->box_host.size(); ++k)
+                    if (!(h->box_host[k] >= 2.0 * d.cutoff)) return remd_fail(h, -1, who + "box smaller than twice the cutoff");
+        }
         if (d.n_globals != t.ng) return remd_fail(h, -1, who + "every descriptor must carry the handle's n_globals");
         for (int k = 0; k < t.ng; ++k) if (d.global_defaults && d.global_defaults[k] != t.defaults[k]) return remd_fail(h, -1, who + "global_defaults differ between the descriptors");
         if (d.force_group != desc[0].force_group || d.force_group < 0 || d.force_group > 31)
             return remd_fail(h, -1, who + "every custom force of a handle must sit in one force group (0 ... 31)");
-        if (const char* bad = check_program(d, compound ? 3 * d.n_particles : n_vars4[d.kind])) return remd_fail(h, -1, who + bad);
+        if (const char* bad = check_program(d, compound ? 3 * d.n_particles : nonbonded ? 1 : n_vars4[d.kind])) return remd_fail(h, -1, who + bad);
         if (centroid) {
             // the groups: CSR offsets that start at 0 and increase (no empty group), atoms of the system, weights that sum to 1
             if (d.n_groups <= 0 || !d.group_offsets || !d.group_atoms || !d.group_weights) return remd_fail(h, -1, who + "a centroid-bond force needs n_groups > 0, group_offsets, group_atoms and group_weights");
@@ -393,23 +438,40 @@ int remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, int
         f.kind = d.kind; f.periodic = d.periodic ? 1 : 0; f.n_terms = d.n_terms; f.n_params = d.n_params; f.n_particles = wd;
         f.npad = (d.n_terms + 63) / 64 * 64;
         f.par0 = (int)t.par.size(); f.prog0 = (int)t.prog.size(); f.n_prog = d.n_program; f.const0 = (int)t.consts.size();
+        f.switch_dist = -1.0;
+        int par_stride = f.npad;
+        if (nonbonded) {
+            // its wavefronts are the upper-triangular tiles of 64 x 64 atoms; its parameters one row per atom, [n_params][Npad]
+            const int nb = (d.n_terms + 63) / 64;
+            f.npad = 64 * (nb * (nb + 1) / 2);
+            par_stride = h->Npad;
+            f.nb_method = d.nb_method; f.cutoff = d.nb_method ? d.cutoff : 0.0; f.switch_dist = d.switch_distance >= 0.0 ? d.switch_distance : -1.0;
+            f.lrc = d.long_range_correction ? 1 : 0;
+            if (f.lrc) t.has_lrc = true;
+            if (d.nb_method == 2) t.periodic_cutoff = std::max(t.periodic_cutoff, d.cutoff);
+            f.excl0 = (int)t.excl_off.size();
+            const int base = (int)t.excl_atoms.size();
+            for (int a = 0; a <= d.n_terms; ++a) t.excl_off.push_back(base + d.excl_offsets[a]);
+            if (d.excl_offsets[d.n_terms] > 0) t.excl_atoms.insert(t.excl_atoms.end(), d.excl_atoms, d.excl_atoms + d.excl_offsets[d.n_terms]);
+        }
         // parameters [n_params][npad]; a padding slot repeats the last term (finite arithmetic in lanes that add nothing)
-        for (int p = 0; p < d.n_params; ++p) for (int s = 0; s < f.npad; ++s) t.par.push_back(d.params[(size_t)std::min(s, d.n_terms - 1) * d.n_params + p]);
+        for (int p = 0; p < d.n_params; ++p) for (int s = 0; s < par_stride; ++s) t.par.push_back(d.params[(size_t)std::min(s, d.n_terms - 1) * d.n_params + p]);
         for (int pc = 0; pc < d.n_program; ++pc) t.prog.push_back(make_int2(d.program[2 * pc], d.program[2 * pc + 1]));
         if (d.n_consts > 0) t.consts.insert(t.consts.end(), d.consts, d.consts + d.n_consts);
         t.F.push_back(f);
     }
-    // the padded term space: the four one-variable kinds first, the compound-bond forces behind them, the centroid-bond forces last
-    // (each part has its own kernel); the energy columns keep the forces' order whatever their slots
-    for (int pass = 0; pass < 3; ++pass) {
+    // the padded term space: the four one-variable kinds first, the compound-bond forces behind them, then the nonbonded forces' tiles,
+    // the centroid-bond forces last (each part has its own kernel); the energy columns keep the forces' order whatever their slots
+    for (int pass = 0; pass < 4; ++pass) {
         for (int i = 0; i < n; ++i) {
             cst_force& f = t.F[i];
-            if ((f.kind == REMD_CUSTOM_CENTROID ? 2 : f.kind == REMD_CUSTOM_COMPOUND ? 1 : 0) != pass) continue;
+            if ((f.kind == REMD_CUSTOM_CENTROID ? 3 : f.kind == REMD_CUSTOM_NONBONDED ? 2 : f.kind == REMD_CUSTOM_COMPOUND ? 1 : 0) != pass) continue;
             f.slot0 = t.total_pad; t.total_pad += f.npad;
             for (int w = 0; w < f.npad / 64; ++w) t.wave_force.push_back(i);
         }
         if (pass == 0) t.waves_simple = t.total_pad / 64;
-        if (pass == 1) t.waves_particles = t.total_pad / 64;
+        if (pass == 1) t.waves_compound = t.total_pad / 64;
+        if (pass == 2) t.waves_particles = t.total_pad / 64;
     }
     int rows = 4;
     for (int i = 0; i < n; ++i) rows = std::max(rows, t.F[i].n_particles);
@@ -450,10 +512,36 @@ int remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, int
     t.K = h->K; t.glob_version = h->states_version; t.uniform = true;
     for (int k = 0; k < std::max(h->K, 0); ++k) t.glob.insert(t.glob.end(), t.defaults.begin(), t.defaults.end());
     if (t.glob.empty()) t.glob.assign(1, 0.0);          // (a force without globals: the kernels still take a pointer)
+    t.lrc.assign((size_t)std::max(h->K, 1) * n, 0.0);
+    if (t.periodic_cutoff > 0.0 && h->nb_method == REMD_NB_NONE && !h->nocutoff && h->n_bonds + h->n_angles + h->n_torsions + h->n_settle + h->n_shake == 0) {
+        // no NonbondedForce and no built-in bonded term or constraint: the molecules a barostat scales are what the custom bonds,
+        // angles, torsions and compound bonds join (OpenMM takes molecules from the bonds its forces report); the scaling kernels take
+        // contiguous ranges, so a molecule whose atoms are not one gives no table (the barostat then refuses)
+        std::vector<int> root(h->N);
+        for (int a = 0; a < h->N; ++a) root[a] = a;
+        auto find = [&](int a) { while (root[a] != a) a = root[a] = root[root[a]]; return a; };
+        for (int i = 0; i < n; ++i) {
+            const cst_force& f = t.F[i];
+            if (f.kind == REMD_CUSTOM_EXTERNAL || f.kind == REMD_CUSTOM_CENTROID || f.kind == REMD_CUSTOM_NONBONDED) continue;
+            for (int b = 0; b < f.n_terms; ++b) for (int a = 1; a < f.n_particles; ++a) {
+                const int p = find(desc[i].atoms[(size_t)b * f.n_particles]), q = find(desc[i].atoms[(size_t)b * f.n_particles + a]);
+                if (p != q) root[std::max(p, q)] = std::min(p, q);
+            }
+        }
+        bool contiguous = true;                         // (roots are the lowest atom of a molecule: a range starts at its root)
+        for (int a = 0; a < h->N && contiguous; ++a) {
+            const int r = find(a);
+            if (r == a) { t.mol_first.push_back(a); t.mol_size.push_back(1); }
+            else if (r == t.mol_first.back()) t.mol_size.back()++;
+            else contiguous = false;
+        }
+        if (!contiguous) { t.mol_first.clear(); t.mol_size.clear(); }
+    }
     int rc = set_tables(h, t);
     if (rc) return rc;
+    const double periodic_cutoff = t.periodic_cutoff;
     h->cst.reset(new cst_tables(std::move(t)));
-    h->n_custom = n; h->cst_group = desc[0].force_group;
+    h->n_custom = n; h->cst_group = desc[0].force_group; h->cst_cutoff = periodic_cutoff;
     return 0;
 }
 
@@ -470,9 +558,33 @@ int remd_set_custom_globals(remd_handle h, const double* values)
     t->K = h->K; t->glob_version = h->states_version;
     if (t->ng > 0) t->glob.assign(values, values + (size_t)h->K * t->ng); else t->glob.assign(1, 0.0);
     t->uniform = t->ng == 0 || globals_uniform(*t);
+    t->lrc_valid = false;                               // (the coefficients are integrals of the expressions under the globals)
     int rc = t->d_glob.upload(h, t->glob);
     if (rc) return rc;
     h->config_version++;
+    return 0;
+}
+
+int remd_set_custom_lrc(remd_handle h, const double* coeff)
+{
+    if (!h) return remd_fail(h, -1, "remd_set_custom_lrc: bad arguments");
+    cst_tables* t = h->cst.get();
+    if (!t || h->n_custom == 0) return remd_fail(h, -1, "remd_set_custom_lrc: no custom terms (remd_set_custom_terms)");
+    if (h->K <= 0 || t->K != h->K || t->glob_version != h->states_version)
+        return remd_fail(h, -1, "remd_set_custom_lrc: call remd_set_states and remd_set_custom_globals first");
+    if (!coeff) return remd_fail(h, -1, "remd_set_custom_lrc: bad arguments");
+    for (size_t k = 0; k < (size_t)h->K * t->nf; ++k)
+        if (!std::isfinite(coeff[k]) || (coeff[k] != 0.0 && !t->F[k % t->nf].lrc))
+            return remd_fail(h, -1, "remd_set_custom_lrc: a coefficient that is not finite, or not zero for a force without a long-range correction");
+    hipSetDevice(h->device);
+    hipStreamSynchronize(h->stream);
+    if (h->stream2) hipStreamSynchronize(h->stream2);
+    t->lrc.assign(coeff, coeff + (size_t)h->K * t->nf);
+    int rc = t->d_lrc.upload(h, t->lrc);
+    if (rc) return rc;
+    t->lrc_valid = true;
+    h->config_version++;
+    h->forces_valid = false;
     return 0;
 }
 

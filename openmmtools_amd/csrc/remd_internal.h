@@ -263,6 +263,7 @@ struct remd_ctx {
     int regions_exact = 0;             // ... under the exact PME treatment (the regions' scaled charges inside the Ewald sum)
     long long states_version = 0;      // bumped by every remd_set_states (restraints.hip: the restraint lambdas belong to one set of states)
     int n_restraints = 0, rst_group = 0;   // remd_set_restraints: receptor-ligand restraints and their force group (restraints.hip holds the tables)
+    double cst_cutoff = 0;                 // the longest cutoff of a CutoffPeriodic CustomNonbondedForce (custom_nonbonded.hip): the box checks honour it
     int n_custom = 0, cst_group = 0;       // remd_set_custom_terms: custom bond / angle / torsion / external forces and their force group (custom_terms.hip)
 
     // ---- states ---------------------------------------------------------------------
@@ -519,6 +520,7 @@ int remd_restraints_ukl(remd_ctx* h, double* d_rows /*[R][K], added to*/);
 // slot of d_epart, added behind the restraint launch on the same stream
 void remd_custom_release(remd_ctx* h);
 int remd_custom_clone(remd_ctx* parent, remd_ctx* child);
+int remd_custom_molecules(remd_ctx* h, const int** first, const int** size);   // molecule table of a handle whose only pair force is a periodic CustomNonbondedForce (device); 0: none
 int remd_custom_forces(remd_ctx* h, bool with_energy, int ep_slot, hipStream_t st);
 int remd_custom_ukl(remd_ctx* h, double* d_rows /*[R][K], added to*/);
 

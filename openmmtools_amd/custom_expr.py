@@ -1,7 +1,7 @@
-"""Compiler of OpenMM energy expressions for the custom bond, angle, torsion, external, compound-bond and centroid-bond forces
-(system.CustomBondForce, CustomAngleForce, CustomTorsionForce, CustomExternalForce, CustomCompoundBondForce, CustomCentroidBondForce):
-an energy string becomes the postfix program of include/remd_hip_custom.h, which csrc/custom_terms.hip, csrc/custom_compound.hip and
-csrc/custom_centroid.hip run on a forward-mode stack machine (every stack slot a value and its partial derivatives with respect to
+"""Compiler of OpenMM energy expressions for the custom bond, angle, torsion, external, compound-bond, centroid-bond and nonbonded forces
+(system.CustomBondForce, CustomAngleForce, CustomTorsionForce, CustomExternalForce, CustomCompoundBondForce, CustomCentroidBondForce,
+CustomNonbondedForce): an energy string becomes the postfix program of include/remd_hip_custom.h, which csrc/custom_terms.hip,
+csrc/custom_compound.hip, csrc/custom_centroid.hip and csrc/custom_nonbonded.hip run on a forward-mode stack machine (every stack slot a value and its partial derivatives with respect to
 the force's variables).
 
 A compound-bond force of P particles (1 ... MAX_PARTICLES) has the variables x1 y1 z1 ... xP yP zP (operand 3*(i-1)+c) and the
@@ -11,6 +11,11 @@ periodicdistance opcode (the engine images it only where the force is periodic);
 
 A centroid-bond force of P groups per bond is the same thing over the groups' centroids: the same variables, the same functions with
 the names g1 ... gP in place of p1 ... pP, the same program.  Its descriptor carries the groups beside it (custom_terms_desc).
+
+A nonbonded force has the one variable r; a per-particle parameter p appears as p1 and p2 (PARAM operand k for particle 1,
+n_params + k for particle 2; at most MAX_PAIR_PARAMS per-particle parameters, so that MAX_PARAMS bounds the operand).  A bare
+per-particle name, a suffix 3 and x / y / z are refused by name.  Its long-range correction is computed here, on the host in f64
+(long_range_coefficients).
 
 Grammar: numbers (exponent notation included), ``+ - * / ^``, unary minus, parentheses, function calls, and ``;``-separated
 definitions ``name = expr`` in any order, substituted where they are used.  ``^`` binds tighter than unary minus and groups to the
@@ -27,11 +32,12 @@ import numpy as np
 MAX_PROGRAM, MAX_STACK, MAX_PARAMS, MAX_GLOBALS, MAX_FORCES = 256, 16, 16, 16, 8
 MAX_INTEGER_POWER = 64
 MAX_PARTICLES = 8                               # particles per bond of a compound-bond force
+MAX_PAIR_PARAMS = MAX_PARAMS // 2               # per-particle parameters of a nonbonded force (each appears twice in a pair's program)
 
-KIND_BOND, KIND_ANGLE, KIND_TORSION, KIND_EXTERNAL, KIND_COMPOUND, KIND_CENTROID = 0, 1, 2, 3, 4, 5
-KIND_OF_CLASS = {'CustomBondForce': KIND_BOND, 'CustomAngleForce': KIND_ANGLE, 'CustomTorsionForce': KIND_TORSION,
+KIND_BOND, KIND_ANGLE, KIND_TORSION, KIND_EXTERNAL, KIND_COMPOUND, KIND_CENTROID, KIND_NONBONDED = 0, 1, 2, 3, 4, 5, 6
+KIND_OF_CLASS = {'CustomNonbondedForce': KIND_NONBONDED, 'CustomBondForce': KIND_BOND, 'CustomAngleForce': KIND_ANGLE, 'CustomTorsionForce': KIND_TORSION,
                  'CustomExternalForce': KIND_EXTERNAL, 'CustomCompoundBondForce': KIND_COMPOUND, 'CustomCentroidBondForce': KIND_CENTROID}
-VARIABLES = {KIND_BOND: ('r',), KIND_ANGLE: ('theta',), KIND_TORSION: ('theta',), KIND_EXTERNAL: ('x', 'y', 'z')}
+VARIABLES = {KIND_BOND: ('r',), KIND_ANGLE: ('theta',), KIND_TORSION: ('theta',), KIND_EXTERNAL: ('x', 'y', 'z'), KIND_NONBONDED: ('r',)}
 
 
 def compound_variables(n_particles):
@@ -185,14 +191,16 @@ def split_definitions(energy, where='expression'):
 
 
 def compile_expression(energy, variables, parameters, global_columns, where='expression', tabulated=(), periodic_distance=False,
-                       n_particles=0, particle_prefix='p'):
+                       n_particles=0, particle_prefix='p', pair_parameters=()):
     """The postfix program of ``energy``.
 
     variables: the force's own variable names in operand order; parameters: the per-term parameter names in order; global_columns:
     {global parameter name: column of the handle's table}; tabulated: names of tabulated functions (refused); periodic_distance:
     whether periodicdistance(...) is allowed (an external force that uses periodic boundary conditions); n_particles: the particles
     per bond of a compound-bond force (0: another force), which opens distance / angle / dihedral over p1 ... pP and pointdistance;
-    particle_prefix: 'p', or 'g' for the groups g1 ... gP of a centroid-bond force (the messages then speak of groups).
+    particle_prefix: 'p', or 'g' for the groups g1 ... gP of a centroid-bond force (the messages then speak of groups);
+    pair_parameters: the per-particle parameter names of a nonbonded force, in order: name p is legal as p1 (PARAM operand k) and p2
+    (operand len(pair_parameters) + k) only.
 
     Returns dict(program int32 [n][2], consts float64 [m], stack_depth).
     """
@@ -238,6 +246,16 @@ def compile_expression(energy, variables, parameters, global_columns, where='exp
                 return emit(PARAM, parameters.index(name))
             if name in global_columns:
                 return emit(GLOBAL, global_columns[name])
+            if pair_parameters:
+                if name[-1:] in ('1', '2') and name[:-1] in pair_parameters:
+                    return emit(PARAM, pair_parameters.index(name[:-1]) + (len(pair_parameters) if name[-1] == '2' else 0))
+                if name in pair_parameters:
+                    raise NotImplementedError('%s: per-particle parameter %r without a particle suffix (%s1 or %s2)' % (where, name, name, name))
+                if name[-1:].isdigit() and name.rstrip('0123456789') in pair_parameters:
+                    raise NotImplementedError('%s: per-particle parameter %r (a pair has the particles 1 and 2: %s1, %s2)'
+                                              % (where, name, name.rstrip('0123456789'), name.rstrip('0123456789')))
+                if name in ('x', 'y', 'z'):
+                    raise NotImplementedError('%s: variable %r (the only variable of a nonbonded force is r)' % (where, name))
             if n_particles and _PARTICLE_NAME.fullmatch(name):
                 raise NotImplementedError('%s: %s name %r outside distance(), angle() and dihedral()' % (where, noun, name))
             if n_particles and _PARTICLE_NAMES[other][0].fullmatch(name):
@@ -317,7 +335,7 @@ def is_custom_term_force(force):
     CustomCompoundBondForce, or a system.CustomCentroidBondForce (forces.CustomCentroidBondForce, the restraints' base, is another class)."""
     from . import system as _system
     from . import forces as _forces
-    if isinstance(force, (_system.CustomCompoundBondForce, _system.CustomCentroidBondForce)):
+    if isinstance(force, (_system.CustomCompoundBondForce, _system.CustomCentroidBondForce, _system.CustomNonbondedForce)):
         return True
     if isinstance(force, _system.CustomExternalForce):
         return not force.is_harmonic_oscillator()
@@ -358,7 +376,152 @@ def centroid_groups(force, masses):
             np.concatenate(weights) if weights else np.zeros(0, dtype=np.float64))
 
 
-def custom_terms_desc(forces, masses=None):
+def run_values(prog, r, params, global_values):
+    """The value of a compiled one-variable program at every element of the array ``r`` (f64): the Python interpreter of the machine,
+    values only (no partials), numpy-vectorised over r.  params: the PARAM operands' values; global_values: the GLOBAL columns'."""
+    from math import erf, erfc
+    r = np.asarray(r, dtype=np.float64)
+    one = np.ones_like(r)
+    verf, verfc = np.vectorize(erf, otypes=[float]), np.vectorize(erfc, otypes=[float])
+    unary = {NEG: np.negative, SQRT: np.sqrt, EXP: np.exp, LOG: np.log, SIN: np.sin, COS: np.cos, TAN: np.tan, ASIN: np.arcsin,
+             ACOS: np.arccos, ATAN: np.arctan, SINH: np.sinh, COSH: np.cosh, TANH: np.tanh, ERF: verf, ERFC: verfc, ABS: np.abs,
+             STEP: lambda x: (x >= 0.0) * 1.0, DELTA: lambda x: (x == 0.0) * 1.0, FLOOR: np.floor, CEIL: np.ceil}
+    binary = {ADD: np.add, SUB: np.subtract, MUL: np.multiply, DIV: np.divide, POW: np.power, ATAN2: np.arctan2, MIN: np.minimum,
+              MAX: np.maximum}
+    stack = []
+    with np.errstate(all='ignore'):
+        for op, arg in np.asarray(prog['program']).reshape(-1, 2).tolist():
+            if op == CONST:
+                stack.append(prog['consts'][arg] * one)
+            elif op == VAR:
+                if arg != 0:
+                    raise NotImplementedError('run_values: a program of one variable')
+                stack.append(r.copy())
+            elif op == PARAM:
+                stack.append(float(params[arg]) * one)
+            elif op == GLOBAL:
+                stack.append(float(global_values[arg]) * one)
+            elif op in binary:
+                y, x = stack.pop(), stack.pop()
+                stack.append(binary[op](x, y))
+            elif op == SELECT:
+                z, y, x = stack.pop(), stack.pop(), stack.pop()
+                stack.append(np.where(x != 0.0, y, z))
+            elif op == POWI:
+                x = stack.pop()
+                v = one.copy()
+                for _ in range(abs(arg)):
+                    v = v * x
+                stack.append(1.0 / v if arg < 0 else v)
+            elif op in unary:
+                stack.append(unary[op](stack.pop()))
+            else:
+                raise NotImplementedError('run_values: opcode %d' % op)
+    assert len(stack) == 1
+    return stack[0]
+
+
+def _refined_quadrature(f, a, b, what):
+    """Gauss-Legendre of f over (a, b), the order doubled until two successive refinements agree to 1e-12 relative."""
+    previous = None
+    for n in (16, 32, 64, 128, 256, 512, 1024):
+        x, w = np.polynomial.legendre.leggauss(n)
+        value = 0.5 * (b - a) * float(np.dot(w, f(0.5 * (b - a) * x + 0.5 * (b + a))))
+        if not np.isfinite(value):
+            break
+        if previous is not None and abs(value - previous) <= 1e-12 * max(abs(value), abs(previous)):
+            return value
+        previous = value
+    raise ValueError('%s does not converge (the energy must fall off faster than 1 / r^3)' % what)
+
+
+class LongRangeCorrection:
+    """The long-range correction of one nonbonded force (OpenMM's CustomNonbondedForceImpl::calcLongRangeCorrection, the convention
+    alchemy.alchemical_long_range_constants restates): coefficient(g) = 2 pi N^2 sum_pairs-of-classes count I / (N (N + 1) / 2), the
+    energy coefficient / V.  I = int_rc^inf E r^2 dr, plus int_rs^rc (1 - S) E r^2 dr with a switch, E the compiled program under
+    the class pair's parameters and the globals g; count = n_a (n_a + 1) / 2 within a class, n_a n_b across classes.  The outer
+    integral is taken in x = rc / r over (0, 1], where a Lennard-Jones tail is a polynomial and Gauss-Legendre exact.  Integrals are
+    cached by (class pair, globals row)."""
+
+    def __init__(self, term):
+        self.term = term
+        self.n = len(term['params'])
+        n_params = int(np.asarray(term['params']).size // max(self.n, 1))
+        params = np.asarray(term['params'], dtype=np.float64).reshape(self.n, n_params)
+        classes = {}
+        for row in params:
+            classes[tuple(row.tolist())] = classes.get(tuple(row.tolist()), 0) + 1
+        self.classes = sorted(classes.items())
+        self.rc, self.rs = float(term['cutoff']), float(term['switch_distance'])
+        self._cache = {}
+
+    def _integral(self, pa, pb, g):
+        key = (pa, pb, tuple(g))
+        if key in self._cache:
+            return self._cache[key]
+        prog, rc, rs, par = self.term, self.rc, self.rs, list(pa) + list(pb)
+        where = 'CustomNonbondedForce (energy %r): the long-range correction' % (self.term.get('energy'),)
+
+        def tail(x):                            # r = rc / x: E r^2 dr = rc^3 E(rc / x) x^-4 dx
+            return rc ** 3 * run_values(prog, rc / x, par, g) / x ** 4
+        value = _refined_quadrature(tail, 0.0, 1.0, where)
+        if rs >= 0.0:
+            def switched(r):
+                t = (r - rs) / (rc - rs)
+                return (10.0 * t ** 3 - 15.0 * t ** 4 + 6.0 * t ** 5) * run_values(prog, r, par, g) * r * r
+            value += _refined_quadrature(switched, rs, rc, where)
+        self._cache[key] = value
+        return value
+
+    def coefficient(self, g):
+        """kJ/mol nm^3 under the globals row g (the handle's columns)"""
+        g = [float(v) for v in g]
+        total = 0.0
+        for a, (pa, na) in enumerate(self.classes):
+            for pb, nb in self.classes[a:]:
+                total += (na * (na + 1) // 2 if pa == pb else na * nb) * self._integral(pa, pb, g)
+        return 2.0 * np.pi * self.n * self.n * total / (self.n * (self.n + 1) / 2.0)
+
+
+def long_range_coefficients(terms, global_values, cache=None):
+    """[K][n_forces]: the long-range coefficient of every state (row of global_values [K][n_globals]) and custom force of ``terms``
+    (the list of custom_terms_desc's entries); zero for a force without the correction.  cache: a dict that keeps the integrators
+    between calls, keyed by position; an entry made for another term (another dict object) is replaced, not reused."""
+    global_values = np.asarray(global_values, dtype=np.float64)
+    if global_values.ndim != 2:
+        raise ValueError('long_range_coefficients: global_values is [K][n_globals]')
+    out = np.zeros((len(global_values), len(terms)))
+    cache = {} if cache is None else cache
+    for i, t in enumerate(terms):
+        if not t.get('long_range_correction'):
+            continue
+        if i not in cache or cache[i].term is not t:
+            cache[i] = LongRangeCorrection(t)
+        lrc = cache[i]
+        for k, g in enumerate(global_values):
+            out[k, i] = lrc.coefficient(g)
+    return out
+
+
+def nonbonded_exclusions(force, n):
+    """The exclusions of a nonbonded force in CSR form: (excl_offsets int32 [n + 1], excl_atoms int32), symmetric, each row sorted."""
+    rows = [set() for _ in range(n)]
+    for k in range(force.getNumExclusions()):
+        i, j = force.getExclusionParticles(k)
+        if not (0 <= i < n and 0 <= j < n):
+            raise ValueError('CustomNonbondedForce: exclusion %d names particle %d (the force has %d)' % (k, i if not 0 <= i < n else j, n))
+        if i == j:
+            raise ValueError('CustomNonbondedForce: exclusion %d excludes particle %d from itself' % (k, i))
+        if j in rows[i]:
+            raise ValueError('CustomNonbondedForce: particles %d and %d are excluded twice' % (i, j))
+        rows[i].add(j); rows[j].add(i)
+    offsets = np.zeros(n + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum([len(r) for r in rows])
+    atoms = np.array([j for r in rows for j in sorted(r)], dtype=np.int32)
+    return offsets, atoms
+
+
+def custom_terms_desc(forces, masses=None, box_vectors=None):
     """The 'custom_terms' entry of system.system_to_desc for the custom forces ``forces`` (in System order): a dict keyed by position
     ('000', '001', ...), each value dict(kind, atoms [n][1..4] ([n][P] and n_particles = P of a compound-bond force; of a centroid-bond force atoms holds
     group numbers and group_offsets, group_atoms, group_weights describe the groups, centroid_groups(force, masses)), params [n][p], global_names, global_defaults, program, consts,
@@ -391,6 +554,8 @@ def custom_terms_desc(forces, masses=None):
         kind = KIND_OF_CLASS[cls]
         where = '%s (energy %r)' % (cls, f.getEnergyFunction())
         per_term = _per_term_names(f)
+        if kind == KIND_NONBONDED and len(per_term) > MAX_PAIR_PARAMS:
+            raise NotImplementedError('%s: %d per-particle parameters (the engine takes %d): %s' % (cls, len(per_term), MAX_PAIR_PARAMS, ', '.join(per_term)))
         if len(per_term) > MAX_PARAMS:
             raise NotImplementedError('%s: %d per-term parameters (the engine takes %d): %s' % (cls, len(per_term), MAX_PARAMS, ', '.join(per_term)))
         tabulated = [f.getTabulatedFunctionName(i) for i in range(f.getNumTabulatedFunctions())]
@@ -405,9 +570,14 @@ def custom_terms_desc(forces, masses=None):
             n_particles = int(f.getNumGroupsPerBond())
             if not 1 <= n_particles <= MAX_PARTICLES:
                 raise NotImplementedError('%s: bonds of %d groups (the engine takes 1 ... %d)' % (cls, n_particles, MAX_PARTICLES))
-        prog = compile_expression(f.getEnergyFunction(), compound_variables(n_particles) if n_particles else VARIABLES[kind], per_term, own,
+        prog = compile_expression(f.getEnergyFunction(), compound_variables(n_particles) if n_particles else VARIABLES[kind],
+                                  () if kind == KIND_NONBONDED else per_term, own,
                                   where=where, tabulated=tabulated, periodic_distance=(kind == KIND_EXTERNAL and periodic),
-                                  n_particles=n_particles, particle_prefix='g' if kind == KIND_CENTROID else 'p')
+                                  n_particles=n_particles, particle_prefix='g' if kind == KIND_CENTROID else 'p',
+                                  pair_parameters=tuple(per_term) if kind == KIND_NONBONDED else ())
+        if kind == KIND_NONBONDED:
+            out['%03d' % len(out)] = _nonbonded_entry(f, cls, prog, names, defaults, per_term, masses, box_vectors)
+            continue
         atoms, params = f._term_arrays()
         if len(atoms) == 0:
             continue
@@ -425,6 +595,41 @@ def custom_terms_desc(forces, masses=None):
         if kind == KIND_CENTROID:
             out['%03d' % (len(out) - 1)].update(group_offsets=groups[0], group_atoms=groups[1], group_weights=groups[2])
     return out
+
+
+def _nonbonded_entry(f, cls, prog, names, defaults, per_term, masses, box_vectors):
+    """the entry of a nonbonded force: atoms is empty ([0][0]; the terms are the particles, n_terms = N), params [N][n_params],
+    nb_method, cutoff, switch_distance (< 0: none), excl_offsets / excl_atoms and long_range_correction beside the common keys"""
+    n = f.getNumParticles()
+    if masses is not None and n != len(masses):
+        raise ValueError('%s has %d particles, the System has %d' % (cls, n, len(masses)))
+    if n == 0:
+        raise ValueError('%s has no particles' % cls)
+    for k in range(n):
+        if len(f.getParticleParameters(k)) != len(per_term):
+            raise ValueError('%s: particle %d carries %d parameters, the force declares %d' % (cls, k, len(f.getParticleParameters(k)), len(per_term)))
+    method = int(f.getNonbondedMethod())
+    cutoff = float(f.getCutoffDistance()) if method else 0.0
+    switch = float(f.getSwitchingDistance()) if (method and f.getUseSwitchingFunction()) else -1.0
+    if method and not cutoff > 0.0:
+        raise ValueError('%s: cutoff distance %r' % (cls, cutoff))
+    if switch >= 0.0 and not 0.0 < switch < cutoff:
+        raise ValueError('%s: the switching distance %r must lie between 0 and the cutoff %r' % (cls, switch, cutoff))
+    if method == 2:
+        if box_vectors is None:
+            raise ValueError('%s: CutoffPeriodic needs the periodic box vectors of the System' % cls)
+        box = np.asarray(box_vectors, dtype=np.float64).reshape(3, 3)
+        if np.any(box != np.diag(np.diag(box))):
+            raise NotImplementedError('%s: triclinic boxes are not supported (CutoffPeriodic takes a rectangular box)' % cls)
+        if cutoff > 0.5 * np.diag(box).min():
+            raise ValueError('%s: the cutoff %r nm exceeds half the smallest box edge (%r nm)' % (cls, cutoff, np.diag(box).min()))
+    offsets, atoms = nonbonded_exclusions(f, n)
+    params = np.array([f.getParticleParameters(k) for k in range(n)], dtype=np.float64).reshape(n, len(per_term))
+    return dict(kind=KIND_NONBONDED, atoms=np.zeros((0, 0), dtype=np.int32), params=params, global_names=list(names),
+                global_defaults=np.array(defaults, dtype=np.float64), program=prog['program'], consts=prog['consts'],
+                stack_depth=prog['stack_depth'], periodic=int(method == 2), force_group=int(f.getForceGroup()),
+                energy=f.getEnergyFunction(), nb_method=method, cutoff=cutoff, switch_distance=switch, excl_offsets=offsets,
+                excl_atoms=atoms, long_range_correction=int(bool(f.getUseLongRangeCorrection()) and method == 2))
 
 
 def custom_globals(system, names, states):

@@ -479,6 +479,121 @@ class CustomExternalForce(_CustomForce):
         return _term_arrays(self._particles, 1, len(self._per_bond), 'CustomExternalForce')
 
 
+class CustomNonbondedForce(_CustomForce):
+    """openmm.CustomNonbondedForce: the energy a function of the distance r of two particles, of their per-particle parameters (a
+    parameter p appears as p1 and p2) and of global parameters, summed over every pair that no exclusion names and, with a cutoff,
+    that lies inside it.  Every expression goes to csrc/custom_nonbonded.hip (one wavefront per tile of 64 x 64 particles: the cost is
+    quadratic in the particle count).  Interaction groups, tabulated functions and energy parameter derivatives are refused."""
+    NoCutoff, CutoffNonPeriodic, CutoffPeriodic = 0, 1, 2
+
+    def __init__(self, energy):
+        super().__init__(energy)
+        self._particles = []                  # per-particle parameter lists
+        self._exclusions = []                 # (i, j)
+        self._method = CustomNonbondedForce.NoCutoff
+        self._cutoff = 1.0
+        self._use_switch = False
+        self._switch = -1.0
+        self._lrc = False
+
+    addPerParticleParameter = _CustomForce.addPerBondParameter
+    getNumPerParticleParameters = _CustomForce.getNumPerBondParameters
+    getPerParticleParameterName = _CustomForce.getPerBondParameterName
+
+    def addParticle(self, parameters=()):
+        self._particles.append([float(p) for p in parameters])
+        return len(self._particles) - 1
+
+    def getNumParticles(self):
+        return len(self._particles)
+
+    def getParticleParameters(self, index):
+        return list(self._particles[index])
+
+    def setParticleParameters(self, index, parameters=()):
+        self._particles[index] = [float(p) for p in parameters]
+
+    def addExclusion(self, particle1, particle2):
+        self._exclusions.append((int(particle1), int(particle2)))
+        return len(self._exclusions) - 1
+
+    def getNumExclusions(self):
+        return len(self._exclusions)
+
+    def getExclusionParticles(self, index):
+        return self._exclusions[index]
+
+    def createExclusionsFromBonds(self, bonds, bondCutoff):
+        """OpenMM's rule: every pair of particles joined by at most ``bondCutoff`` of the bonds (pairs of particle indices) becomes an
+        exclusion, each pair once, in the order of the lower particle."""
+        if bondCutoff < 1:
+            return
+        n = len(self._particles)
+        for a, b in bonds:
+            if not (0 <= a < n and 0 <= b < n):
+                raise ValueError('CustomNonbondedForce.createExclusionsFromBonds: a bond names particle %d (the force has %d)' % (max(a, b) if min(a, b) >= 0 else min(a, b), n))
+        near = [set() for _ in range(n)]
+        for a, b in bonds:
+            near[a].add(int(b)); near[b].add(int(a))
+        reach = [set(s) for s in near]
+        for _ in range(int(bondCutoff) - 1):
+            reach = [set(r).union(*[near[k] for k in r]) for r in reach]
+        for i in range(n):
+            for j in sorted(reach[i]):
+                if j < i:
+                    self.addExclusion(j, i)
+
+    def setNonbondedMethod(self, method):
+        if int(method) not in (0, 1, 2):
+            raise ValueError('CustomNonbondedForce: nonbonded method %r (NoCutoff, CutoffNonPeriodic or CutoffPeriodic)' % (method,))
+        self._method = int(method)
+
+    def getNonbondedMethod(self):
+        return self._method
+
+    def setCutoffDistance(self, distance):
+        self._cutoff = float(distance)
+
+    def getCutoffDistance(self):
+        return self._cutoff
+
+    def setUseSwitchingFunction(self, use):
+        self._use_switch = bool(use)
+
+    def getUseSwitchingFunction(self):
+        return self._use_switch
+
+    def setSwitchingDistance(self, distance):
+        self._switch = float(distance)
+
+    def getSwitchingDistance(self):
+        return self._switch
+
+    def setUseLongRangeCorrection(self, use):
+        self._lrc = bool(use)
+
+    def getUseLongRangeCorrection(self):
+        return self._lrc
+
+    def usesPeriodicBoundaryConditions(self):
+        return self._method == CustomNonbondedForce.CutoffPeriodic
+
+    def setUsesPeriodicBoundaryConditions(self, periodic):
+        raise ValueError('CustomNonbondedForce: periodic boundary conditions follow the nonbonded method (setNonbondedMethod(CutoffPeriodic))')
+
+    def addInteractionGroup(self, set1, set2):
+        raise NotImplementedError('CustomNonbondedForce: interaction groups (addInteractionGroup) are not supported')
+
+    def getNumInteractionGroups(self):
+        return 0
+
+    def addEnergyParameterDerivative(self, name):
+        raise NotImplementedError('CustomNonbondedForce: energy parameter derivatives (addEnergyParameterDerivative) are not supported')
+
+    def getNumEnergyParameterDerivatives(self):
+        return 0
+
+
 class GBSAOBCForce(Force):
     """openmm.GBSAOBCForce: OBC2 Born radii + ACE surface term (the form the reference's alchemical factory spells out, alchemy.py:2144-2225).
     NoCutoff only."""
@@ -991,7 +1106,7 @@ def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
         d['restraints'] = {'%03d' % k: r for k, r in enumerate(restraints)}
     if custom:
         from .custom_expr import custom_terms_desc
-        terms = custom_terms_desc(custom, system.masses)
+        terms = custom_terms_desc(custom, system.masses, box_vectors=system.getDefaultPeriodicBoxVectors())
         if terms:
             d['custom_terms'] = terms
             # the handle's global-parameter columns, once (every entry above repeats them for remd_custom_force_desc)

@@ -13,7 +13,7 @@ import os
 import numpy as np
 from . import unit
 from .system import (System, NonbondedForce, CustomExternalForce, HarmonicBondForce, HarmonicAngleForce,
-                     PeriodicTorsionForce, CMMotionRemover)
+                     PeriodicTorsionForce, CMMotionRemover, CustomNonbondedForce, CustomBondForce)
 
 DEFAULT_EWALD_ERROR_TOLERANCE = 1.0e-5            # testsystems.py:69
 DEFAULT_CUTOFF_DISTANCE = 10.0 * unit.angstroms   # :70
@@ -130,6 +130,149 @@ class LennardJonesFluid(TestSystem):
         system.addForce(nb)
         self.system, self.positions = system, positions
         self.ndof = 3 * nparticles
+
+
+class CustomLennardJonesFluidMixture(TestSystem):
+    """testsystems.py:2169-2305: the argon fluid of LennardJonesFluid split between a NonbondedForce and a CustomNonbondedForce with the
+    Lennard-Jones string (sigma and epsilon written into it as definitions; the per-particle parameters charge, sigma, epsilon are
+    carried and not read).  The first nparticles // 2 particles have their epsilon in the custom force and zero in the NonbondedForce,
+    the others the reverse.  Both forces share the cutoff, the switch and the long-range correction."""
+
+    def __init__(self, nparticles=1000, reduced_density=0.05, mass=39.9 * unit.amu, sigma=3.4 * unit.angstrom,
+                 epsilon=0.238 * unit.kilocalories_per_mole, cutoff=None, switch_width=None, dispersion_correction=True, **kwargs):
+        super().__init__(**kwargs)
+        charge = 0.0
+        if cutoff is None:
+            cutoff = 3.0 * sigma                                           # :2233-2234
+        ncustom = int(nparticles / 2)                                      # :2237
+        system = System()
+        number_density = reduced_density / sigma ** 3
+        volume = nparticles / number_density
+        box_edge = volume ** (1.0 / 3.0)
+        system.setDefaultPeriodicBoxVectors([box_edge, 0, 0], [0, box_edge, 0], [0, 0, box_edge])
+        nb = NonbondedForce()
+        nb.setNonbondedMethod(NonbondedForce.CutoffPeriodic)
+        nb.setCutoffDistance(cutoff)
+        nb.setUseDispersionCorrection(dispersion_correction)
+        nb.setUseSwitchingFunction(False)
+        if switch_width is not None:
+            nb.setUseSwitchingFunction(True)
+            nb.setSwitchingDistance(cutoff - switch_width)
+        system.addForce(nb)
+        energy_expression = '4*epsilon*((sigma/r)^12 - (sigma/r)^6);'      # :2265-2267 ('%f': six decimals, as the reference writes them)
+        energy_expression += 'sigma = %f;' % sigma
+        energy_expression += 'epsilon = %f;' % epsilon
+        cnb = CustomNonbondedForce(energy_expression)
+        cnb.addPerParticleParameter('charge')
+        cnb.addPerParticleParameter('sigma')
+        cnb.addPerParticleParameter('epsilon')
+        cnb.setNonbondedMethod(CustomNonbondedForce.CutoffPeriodic)
+        cnb.setUseLongRangeCorrection(dispersion_correction)
+        cnb.setCutoffDistance(cutoff)
+        cnb.setUseSwitchingFunction(False)
+        if switch_width is not None:
+            cnb.setUseSwitchingFunction(True)
+            cnb.setSwitchingDistance(cutoff - switch_width)
+        system.addForce(cnb)
+        for atom_index in range(nparticles):
+            system.addParticle(mass)
+            if atom_index < ncustom:
+                cnb.addParticle([charge, sigma, epsilon])
+                nb.addParticle(0.0, sigma, 0.0)
+            else:
+                cnb.addParticle([0.0, sigma, 0.0])
+                nb.addParticle(charge, sigma, epsilon)
+        self.system = system
+        self.positions = subrandom_particle_positions(nparticles, system.getDefaultPeriodicBoxVectors())
+        self.ndof = 3 * nparticles
+
+
+class WCAFluid(TestSystem):
+    """testsystems.py:2312-2386: a Weeks-Chandler-Andersen fluid.  No NonbondedForce: the only pair interaction is a CustomNonbondedForce
+    with the shifted Lennard-Jones string cut at its minimum 2^(1/6) sigma (CutoffPeriodic, no switch, no long-range correction).  As in
+    the reference the box edge is (nparticles / density)^(1/3) nm, rounded to f32 -- the density is not scaled by sigma^3 there."""
+
+    def __init__(self, nparticles=216, density=0.96, mass=39.9 * unit.amu, epsilon=None, sigma=3.4 * unit.angstrom, **kwargs):
+        super().__init__(**kwargs)
+        from .constants import kB
+        if epsilon is None:
+            epsilon = 120.0 * unit.kelvin * kB                             # :2314
+        system = System()
+        volume = nparticles / density
+        length = float(np.float32(1.0) * volume ** (1.0 / 3.0))             # (:2342-2346: the box vectors are f32 arrays)
+        system.setDefaultPeriodicBoxVectors([length, 0, 0], [0, length, 0], [0, 0, length])
+        for _ in range(nparticles):
+            system.addParticle(mass)
+        energy_expression = '4.0*epsilon*((sigma/r)^12 - (sigma/r)^6) + epsilon;'      # :2354-2356
+        energy_expression += 'sigma = %f;' % sigma
+        energy_expression += 'epsilon = %f;' % epsilon
+        force = CustomNonbondedForce(energy_expression)
+        for _ in range(nparticles):
+            force.addParticle([])
+        force.setNonbondedMethod(CustomNonbondedForce.CutoffPeriodic)
+        rmin = 2.0 ** (1.0 / 6.0) * sigma
+        force.setCutoffDistance(rmin)
+        system.addForce(force)
+        self.system = system
+        self.positions = subrandom_particle_positions(nparticles, system.getDefaultPeriodicBoxVectors())
+        self.ndof = 3 * nparticles
+
+
+class DoubleWellDimer_WCAFluid(WCAFluid):
+    """testsystems.py:2393-2533: ``ndimers`` pairs (2k, 2k + 1) of the WCA fluid joined by the double-well CustomBondForce
+    h (1 - ((r - r0 - w) / w)^2)^2.  The reference puts that force in force group 1; here it stays in group 0 beside the WCA force,
+    because the engine keeps every custom force of a System in one force group (custom_expr.custom_terms_desc).  As in the reference the bonded pairs keep their WCA interaction (it adds no
+    exclusions) and the positions stay in the fluid's order (its reordering step returns them unchanged)."""
+
+    def __init__(self, ndimers=1, nparticles=216, density=0.96, mass=39.9 * unit.amu, epsilon=None, sigma=3.4 * unit.angstrom, h=None,
+                 r0=2.0 ** (1.0 / 6.0) * 3.4 * unit.angstrom, w=0.3 * 3.4 * unit.angstrom, **kwargs):
+        from .constants import kB
+        if h is None:
+            h = self._default_h(kB)
+        if not (0 <= ndimers <= self._max_bonds(nparticles)):
+            raise ValueError("Can't create %s bonds with %s particles" % (str(ndimers), str(nparticles)))
+        super().__init__(nparticles, density, mass, epsilon, sigma, **kwargs)
+        self.dw_dimer = CustomBondForce('h*(1 - ((r-r0-w)/w)^2)^2')        # :2477-2483
+        self.dw_dimer.addPerBondParameter('h')
+        self.dw_dimer.addPerBondParameter('r0')
+        self.dw_dimer.addPerBondParameter('w')
+        self.system.addForce(self.dw_dimer)
+        for a, b in self._bond_pairs(ndimers):
+            self.dw_dimer.addBond(a, b, [h, r0, w])
+
+    @staticmethod
+    def _default_h(kB):
+        return 6.0 * 0.824 * 120 * unit.kelvin * kB                        # :2397
+
+    @staticmethod
+    def _max_bonds(nparticles):
+        return nparticles / 2
+
+    def _bond_pairs(self, nbonds):
+        for bond_idx in range(nbonds):
+            yield (2 * bond_idx, 2 * bond_idx + 1)
+
+
+class DoubleWellChain_WCAFluid(DoubleWellDimer_WCAFluid):
+    """testsystems.py:2540-2623: a chain of ``nchained`` particles 0, 1, 2, ... joined by double-well bonds in the WCA fluid (nchained 0
+    or 1: the plain fluid).  The reference's default barrier here is 6 x 0.824 K kB (without the dimer's factor 120)."""
+
+    def __init__(self, nchained=3, nparticles=216, density=0.96, mass=39.9 * unit.amu, epsilon=None, sigma=3.4 * unit.angstrom, h=None,
+                 r0=2.0 ** (1.0 / 6.0) * 3.4 * unit.angstrom, w=0.3 * 3.4 * unit.angstrom, **kwargs):
+        nchained = 1 if nchained == 0 else nchained
+        super().__init__(nchained - 1, nparticles, density, mass, epsilon, sigma, h, r0, w, **kwargs)
+
+    @staticmethod
+    def _default_h(kB):
+        return 6.0 * 0.824 * unit.kelvin * kB                              # :2543
+
+    @staticmethod
+    def _max_bonds(nparticles):
+        return nparticles - 1
+
+    def _bond_pairs(self, nbonds):
+        for bond_idx in range(nbonds):
+            yield (bond_idx, bond_idx + 1)
 
 
 class IdealGas(TestSystem):

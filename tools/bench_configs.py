@@ -57,6 +57,15 @@ def main():
         ss = states.SamplerState(hg.positions, box_vectors=hg.system.getDefaultPeriodicBoxVectors())
         s.create(ths, [ss] * 8)
         run('4 (1-GPU share): HostGuestExplicit, 8 replicas x 64 alchemical states, g-BAOAB 2 fs x 500', s, 3)
+    if 'wca' in which:
+        # a System whose only pair force is a CustomNonbondedForce (custom_expr.py kind 6, csrc/custom_nonbonded.hip): 24-replica parallel
+        # tempering of testsystems.WCAFluid (216 particles, no NonbondedForce)
+        wca = testsystems.WCAFluid()
+        s = ParallelTemperingSampler(mcmc_moves=move(2.0, 'V R O R V'), number_of_iterations=10 ** 9, engine=HipEngine(), seed=1)
+        ss = states.SamplerState(wca.positions, box_vectors=wca.system.getDefaultPeriodicBoxVectors())
+        s.create(states.ThermodynamicState(wca.system, 120.0 * unit.kelvin), [ss], storage=None, min_temperature=120.0 * unit.kelvin,
+                 max_temperature=240.0 * unit.kelvin, n_temperatures=24)
+        run('wca: WCAFluid(216), 24 temperatures 120 - 240 K, BAOAB 2 fs x 500', s, 5)
     if '4rs' in which:
         # config 4's share with a receptor-ligand restraint (forces.py, csrc/restraints.hip): a HarmonicRestraintForce between the CB7
         # heavy atoms and the B2 guest, K = 0.2 kcal/mol/A^2, lambda_restraints rising 0 -> 1 along the coupled half and 1 where the
