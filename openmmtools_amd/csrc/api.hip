@@ -161,6 +161,7 @@ int remd_set_system(remd_handle h, const remd_system_desc* d)
     if (h) for (int c = 0; c < 6; ++c) h->fgroup[c] = 0;           // until remd_set_force_groups says otherwise
     if (!h || !d) return remd_fail(h, -1, "remd_set_system: NULL argument");
     if (d->n_atoms <= 0 || !d->mass) return remd_fail(h, -1, "remd_set_system: n_atoms/mass missing");
+    { const int rcm = remd_check_settle_masses(h, d); if (rcm) return rcm; }      // refused with the handle's system as it was
     hipSetDevice(h->device);
     hipStreamSynchronize(h->stream);
     remd_regions_release(h);                    // remd_set_alchemical_regions follows the system it belongs to

@@ -480,11 +480,26 @@ __global__ void check_finite_kernel(int N, int Npad, const float4* __restrict__ 
 // ---------------------------------------------------------------------------------------------
 void remd_table_deleter::operator()(unit_tables* t) const { delete t; }
 
+// The analytic water solve takes its centre of mass and ra / rb from ONE set of masses, the first water's: a water with others (D2O,
+// 18-O) would get correct bond lengths around the wrong centre of mass.  Refused; remd_set_system asks before it changes the handle.
+int remd_check_settle_masses(remd_ctx* h, const remd_system_desc* d)
+{
+    for (int s = 0; s < d->n_settle; ++s) {
+        const int* a = d->settle_atoms + 3 * s;
+        for (int k = 0; k < 3; ++k) if (a[k] < 0 || a[k] >= d->n_atoms) return remd_fail(h, -3, "bad SETTLE triple");
+        for (int k = 0; k < 3; ++k)
+            if (fabs(d->mass[a[k]] - d->mass[d->settle_atoms[k]]) > 1e-9)
+                return remd_fail(h, -3, "remd_set_system: SETTLE waters must share one set of masses");
+    }
+    return 0;
+}
+
 int remd_build_constraints(remd_ctx* h, const remd_system_desc* d)
 {
+    const int N = d->n_atoms;
+    { const int rc = remd_check_settle_masses(h, d); if (rc) return rc; }      // before the handle's tables are touched
     h->units.reset(new unit_tables());
     unit_tables& ut = *h->units;
-    const int N = d->n_atoms;
     std::vector<char> used(N, 0);
     std::vector<int4> atoms; std::vector<unsigned char> type; std::vector<float> dist;
     for (int s = 0; s < d->n_settle; ++s) {

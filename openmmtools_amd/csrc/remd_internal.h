@@ -452,6 +452,7 @@ int remd_kinetic_energy(remd_ctx* h);
 int remd_check_finite(remd_ctx* h);
 int remd_work_buffers(remd_ctx* h);                    // heat / shadow-work accumulators and the '{' snapshot of the local replicas
 int remd_build_constraints(remd_ctx* h, const remd_system_desc* d);
+int remd_check_settle_masses(remd_ctx* h, const remd_system_desc* d);      // 0, or remd_fail(-3): nothing of the handle changed
 
 // ---- resident.hip: a whole propagation in one launch ------------------------------------------
 // each returns 1 when it ran the propagation, 0 when the system / request is not one it covers, < 0 on error

@@ -926,6 +926,10 @@ def _classify_constraints(system):
             ds = [d for (_, d) in adj[centre]]
             shake.append([centre] + hs + [-1] * (3 - len(hs)))
             shake_d.append(ds + [0.0] * (3 - len(ds)))
+    # the engine's analytic solve takes its centre of mass from ONE set of masses, the first water's (remd_build_constraints)
+    for s in settle:
+        if any(abs(system.masses[s[k]] - system.masses[settle[0][k]]) > 1e-9 for k in range(3)):
+            raise NotImplementedError('all rigid waters must share one set of masses (a D2O or 18-O water among H2O is not supported)')
     return settle, shake, shake_d
 
 

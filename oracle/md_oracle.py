@@ -160,10 +160,13 @@ _colour_cache = {}
 
 
 def _colours(cons):
+    # keyed by the list's identity; the entry holds the list itself, so that the id of a list that is gone cannot come back as the
+    # id of another system's list and hand it that system's colours
     key = id(cons)
-    if key not in _colour_cache:
-        _colour_cache[key] = _color_constraints(cons)
-    return _colour_cache[key]
+    hit = _colour_cache.get(key)
+    if hit is None or hit[0] is not cons:
+        hit = _colour_cache[key] = (cons, _color_constraints(cons))
+    return hit[1]
 
 
 def shake(cons, invm, x_old, x_new, tol=1e-12, max_iter=500):

@@ -158,3 +158,75 @@ def test_harmonic_oscillator_equipartition_oracle():
     U = np.array(U)
     sem = U.std() / np.sqrt(len(U) / 2.0)
     assert abs(U.mean() - 1.5 * kT) < 6 * sem
+
+
+# ---- the reference side of tests/test_constraint_units_gpu.py: SHAKE / RATTLE of the oracle on every constraint-zoo composition ----
+def _zoo_compositions():
+    import constraint_zoo as cz
+    return [(c, False) for c in [cz.MAIN] + cz.PACKING] + [(cz.MAIN, True)]
+
+
+@pytest.mark.parametrize('counts,hmr', _zoo_compositions())
+def test_oracle_shake_and_rattle_on_the_constraint_zoo(counts, hmr):
+    """Every composition the GPU tests hold the device to: the oracle's SHAKE converges to 1e-12 (relative, on d^2) from a thermal
+    half step, its RATTLE leaves no r.dv above 1e-12 d^2, and both conserve every unit's momentum sum(m v) to 1e-12 of sum(|m v|)
+    (the correction of an R substep, (x_c - x_1) / h, included); the builder's own bookkeeping agrees with the descriptor."""
+    import constraint_zoo as cz
+    z = cz.build(*counts, hmr=hmr, periodic=True, charges=False)
+    desc = system_to_desc(z.system)
+    osys = mo.OracleSystem(desc)
+    assert z.system.getNumParticles() == 3 * counts[0] + 2 * counts[1] + 3 * counts[2] + 4 * counts[3] + counts[4]
+    assert len(osys.constraints) == z.n_constraints == 3 * counts[0] + counts[1] + 2 * counts[2] + 3 * counts[3]
+    assert len(desc['settle_atoms']) == counts[0] and len(desc['shake_atoms']) == counts[1] + counts[2] + counts[3]
+    # every atom in exactly one unit, every kind counted, and (unless there is one unit only) no cluster contiguous in index order
+    flat = np.concatenate([idx for _, idx in z.units])
+    assert np.array_equal(np.sort(flat), np.arange(z.system.getNumParticles()))
+    if len(z.units) > 1:
+        assert all(np.ptp(idx) > len(idx) - 1 for _, idx in z.units if len(idx) > 1)
+    i, j, d = z.cons
+    x0 = z.positions
+    assert not len(d) or np.abs(np.linalg.norm(x0[j] - x0[i], axis=1) - d).max() < 1e-12
+    rng = np.random.default_rng(5)
+    invm = 1.0 / z.mass
+    v = np.sqrt(2.49 * invm)[:, None] * rng.normal(size=x0.shape)
+    if not osys.constraints:
+        return
+    for h in (0.0005, 0.004):
+        vr = mo.rattle(osys.constraints, invm, x0, v)
+        assert np.abs(np.einsum('ij,ij->i', x0[j] - x0[i], vr[j] - vr[i]) / d ** 2).max() < 1e-12
+        P0, S0 = cz.unit_momenta(z, v)
+        assert np.abs(cz.unit_momenta(z, vr)[0] - P0).max() < 1e-12 * S0.max()
+        x1 = x0 + h * vr
+        xc = mo.shake(osys.constraints, invm, x0, x1)
+        r = xc[j] - xc[i]
+        assert np.abs(np.einsum('ij,ij->i', r, r) / d ** 2 - 1.0).max() < 1e-12
+        v2 = mo.rattle(osys.constraints, invm, xc, vr + (xc - x1) / h)
+        # (the correction (x_c - x_1) / h carries the f64 roundings of the coordinates themselves, 2^-52 |x| each and a handful per
+        #  sweep, times the unit's mass over h: 2e-10 at h = 0.5 fs, far below anything the fp32 device is compared at)
+        m_unit = max(z.mass[idx].sum() for _, idx in z.units)
+        assert np.abs(cz.unit_momenta(z, v2)[0] - P0).max() < 1e-12 * S0.max() + 8 * 2.0 ** -52 * np.abs(xc).max() * m_unit / h
+        assert np.abs(np.einsum('ij,ij->i', r, v2[j] - v2[i]) / d ** 2).max() < 1e-12
+
+
+@pytest.mark.parametrize('which', ['d2o', 'o18'])
+def test_waters_of_mixed_masses_are_refused(which):
+    """The analytic water solve takes its centre of mass from the first water's masses: a D2O or an 18-O water among H2O is refused by
+    the host classes (system_to_desc) and by the C entry point (remd_set_system of the C++ build of the ABI, which the HIP build
+    mirrors: tests/test_constraint_units_gpu.py) instead of being integrated around the wrong centre of mass."""
+    import os
+    import oracle
+    import constraint_zoo as cz
+    from openmmtools_amd._engine import HipEngine
+    z = cz.build(3, 0, 0, 0, 0, water_masses=cz.MIXED_WATERS[which])
+    with pytest.raises(NotImplementedError, match='one set of masses'):
+        system_to_desc(z.system)
+    same = cz.build(3, 0, 0, 0, 0)
+    desc = system_to_desc(same.system)
+    desc['mass'] = z.mass.copy()                       # past the host classes, as a caller of the C ABI could
+    lib = os.path.join(os.path.dirname(os.path.abspath(oracle.__file__)), '_build', 'libremd_cpu.so')
+    if not os.path.exists(lib):
+        oracle.build()
+    eng = HipEngine(lib_path=lib)
+    with pytest.raises(RuntimeError, match='one set of masses'):
+        eng.set_system(desc)
+    eng.close()
