@@ -44,6 +44,22 @@ int  remd_set_restraint_lambdas(remd_handle h, const double* lambda);
 /* out[R_local][n]: the unscaled restraint energies (kJ/mol) at the local replicas' current positions                            */
 int  remd_get_restraint_energies(remd_handle h, double* out);
 
+/* ---- the analysis pass over stored frames: no handle, a device (like the entry points of remd_hip_mbar.h) ----------------------
+   energy[F] (kJ/mol, unscaled: lambda = 1) and distance[F] (nm; either may be NULL) of one restraint at F stored frames.
+   pos [F][n_atoms][3] f32, box [F][3] f32 (NULL: not periodic; required when desc->periodic).
+   desc's atom indices address 0 ... n_atoms-1; weights NULL -> masses[n_atoms].  desc->force_group is not read.
+   max_frames_per_launch <= 0: the library's choice.  The host uploads at most that many frames at a time; a frame's result does
+   not depend on the chunking.  The centroid is the engine's own, the one the run was sampled with: first atom + sum_i w_i
+   img(x_i - x_first), img the minimum image under the frame's own box when periodic, in f64 in a fixed order.
+   Refused before anything is launched (non-zero, the reason in remd_last_error(NULL)): F < 1, an empty group, an atom index outside
+   0 ... n_atoms-1, a negative weight or weights that sum to zero, periodic without box, a non-finite or non-positive box edge when
+   periodic, an unknown kind, K or r0 < 0, a NULL desc or pos.                                                                       */
+int  remd_restraint_frames(int device, const remd_restraint_desc* desc, int64_t F, int n_atoms,
+                           const float* pos, const float* box, const double* masses,
+                           int64_t max_frames_per_launch, double* energy, double* distance);
+/* device milliseconds (events) of the kernels of the last completed remd_restraint_frames call of this process                   */
+int  remd_restraint_frames_last_ms(double* ms);
+
 #ifdef __cplusplus
 }
 #endif

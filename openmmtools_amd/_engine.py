@@ -89,6 +89,8 @@ class RemdGbModelDesc(C.Structure):
 
 # the GPU-only extension of include/remd_hip_restraints.h: bound where the loaded library exports it (the CPU port of the ABI does not)
 RESTRAINT_EXPORTS = ['remd_set_restraints', 'remd_set_restraint_lambdas', 'remd_get_restraint_energies']
+# the analysis pass over stored frames of the same header (no handle: a device), bound the same way
+RESTRAINT_FRAMES_EXPORTS = ['remd_restraint_frames', 'remd_restraint_frames_last_ms']
 # the GPU-only extension of include/remd_hip_custom.h (custom bond / angle / torsion / external forces), bound the same way
 CUSTOM_EXPORTS = ['remd_set_custom_terms', 'remd_set_custom_globals', 'remd_set_custom_lrc', 'remd_get_custom_energies']
 # the GPU-only extension of include/remd_hip_barostat.h (per-axis Monte Carlo barostats), bound the same way
@@ -205,6 +207,12 @@ def load_library(path=None):
         lib.remd_get_restraint_energies.argtypes = [vp, c_double_p]
         for name in RESTRAINT_EXPORTS:
             getattr(lib, name).restype = C.c_int
+    if hasattr(lib, 'remd_restraint_frames'):
+        lib.remd_restraint_frames.argtypes = [C.c_int, C.POINTER(RemdRestraintDesc), C.c_int64, C.c_int, C.POINTER(C.c_float),
+                                              C.POINTER(C.c_float), c_double_p, C.c_int64, c_double_p, c_double_p]
+        lib.remd_restraint_frames_last_ms.argtypes = [c_double_p]
+        for name in RESTRAINT_FRAMES_EXPORTS:
+            getattr(lib, name).restype = C.c_int
     if hasattr(lib, 'remd_set_custom_terms'):             # include/remd_hip_custom.h (GPU-only, like the restraints)
         lib.remd_set_custom_terms.argtypes = [vp, C.POINTER(RemdCustomForceDesc), C.c_int]
         lib.remd_set_custom_globals.argtypes = [vp, c_double_p]
@@ -285,6 +293,59 @@ def build_desc(d):
     s.n_alch = len(d['alch_atoms']); s.alch_atoms = i32(d['alch_atoms'])
     s.softcore_alpha, s.softcore_a, s.softcore_b, s.softcore_c = [float(v) for v in d['softcore']]
     return s, keep
+
+
+def _fp(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _restraint_frames_entry(name, lib_path=None):
+    lib = load_library(lib_path)
+    if not hasattr(lib, name):
+        raise NotImplementedError('%s: this build of the engine library has no pass over stored frames (include/remd_hip_restraints.h is '
+                                  'GPU-only)' % name)
+    return lib, getattr(lib, name)
+
+
+def restraint_frames(desc, pos, box, masses, device=0, max_frames_per_launch=0, lib_path=None):
+    """(energy [F] kJ/mol at lambda = 1, distance [F] nm) of one restraint at F stored frames (include/remd_hip_restraints.h,
+    csrc/restraint_frames.hip).  ``desc``: a dict of forces.restraint_terms (kind, K, r0, atoms1, weights1, atoms2, weights2, periodic;
+    weights None: ``masses``), its atom indices addressing the atoms of ``pos`` [F][n_atoms][3] f32; ``box`` [F][3] f32 or None."""
+    lib, fn = _restraint_frames_entry('remd_restraint_frames', lib_path)
+    pos = np.ascontiguousarray(pos, dtype=np.float32)
+    if pos.ndim != 3 or pos.shape[2] != 3:
+        raise ValueError('pos must be [F][n_atoms][3]')
+    F, n_atoms = int(pos.shape[0]), int(pos.shape[1])
+    if box is not None:
+        box = np.ascontiguousarray(box, dtype=np.float32)
+        if box.shape != (F, 3):
+            raise ValueError('box must be [F][3] (the edges of a rectangular box; triclinic boxes are not supported)')
+    if masses is not None:
+        masses = np.ascontiguousarray(masses, dtype=np.float64)
+        if masses.shape != (n_atoms,):
+            raise ValueError('masses must have one entry per atom of pos')
+    a1, a2 = (np.ascontiguousarray(desc['atoms%d' % g], dtype=np.int32).reshape(-1) for g in (1, 2))
+    w1, w2 = (None if desc.get('weights%d' % g) is None else np.ascontiguousarray(desc['weights%d' % g], dtype=np.float64).reshape(-1)
+              for g in (1, 2))
+    for a, w in ((a1, w1), (a2, w2)):
+        if w is not None and w.shape != a.shape:
+            raise ValueError('a group needs one weight per atom')
+    d = RemdRestraintDesc(int(desc['kind']), float(desc['K']), float(desc.get('r0', 0.0)), len(a1), _ip(a1), _dp(w1), len(a2), _ip(a2), _dp(w2),
+                          int(desc.get('periodic', 0)), int(desc.get('force_group', 0)))
+    energy, distance = np.empty(max(F, 0)), np.empty(max(F, 0))
+    rc = fn(int(device), C.byref(d), F, n_atoms, _fp(pos), _fp(box), _dp(masses), int(max_frames_per_launch), _dp(energy), _dp(distance))
+    if rc != 0:
+        raise RuntimeError('remd_restraint_frames failed (%d): %s' % (rc, lib.remd_last_error(None).decode()))
+    return energy, distance
+
+
+def restraint_frames_last_ms(lib_path=None):
+    """Device milliseconds of the kernels of the last restraint_frames call."""
+    lib, fn = _restraint_frames_entry('remd_restraint_frames_last_ms', lib_path)
+    ms = C.c_double()
+    if fn(C.byref(ms)) != 0:
+        raise RuntimeError('remd_restraint_frames_last_ms failed: %s' % lib.remd_last_error(None).decode())
+    return ms.value
 
 
 class DeviceMBAR:

@@ -50,4 +50,22 @@ __device__ __forceinline__ double3 centroid(const float4* __restrict__ P, const 
     return make_double3((double)a0.x + acc.x, (double)a0.y + acc.y, (double)a0.z + acc.z);
 }
 
+// the same centroid by ONE wavefront of a workgroup of any size, over packed xyz (restraint_frames.hip: one stored frame per wavefront,
+// P the frame's [n_atoms][3] floats): lanes stride over the group's atoms, the xor-shuffle tree alone adds them -- no LDS, no barrier
+__device__ __forceinline__ double3 centroid_wave_xyz(const float* __restrict__ P, const int* __restrict__ atoms, const double* __restrict__ w,
+                                                     int b, int n, bool periodic, double Lx, double Ly, double Lz)
+{
+    const float* p0 = P + 3 * (size_t)atoms[b];
+    const double x0 = (double)p0[0], y0 = (double)p0[1], z0 = (double)p0[2];
+    double3 acc = make_double3(0.0, 0.0, 0.0);
+    for (int k = threadIdx.x & 63; k < n; k += 64) {
+        const float* q = P + 3 * (size_t)atoms[b + k];
+        double dx = (double)q[0] - x0, dy = (double)q[1] - y0, dz = (double)q[2] - z0;
+        if (periodic) { dx = min_image(dx, Lx); dy = min_image(dy, Ly); dz = min_image(dz, Lz); }
+        const double wk = w[b + k];
+        acc.x += wk * dx; acc.y += wk * dy; acc.z += wk * dz;
+    }
+    return make_double3(x0 + wave_sum_d(acc.x), y0 + wave_sum_d(acc.y), z0 + wave_sum_d(acc.z));
+}
+
 }  // namespace

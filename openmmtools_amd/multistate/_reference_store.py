@@ -316,6 +316,26 @@ class ReferenceStoreReader:
         return out
 
 
+    def read_analysis_positions(self, iterations, missing):
+        """(positions [n_it][R][n_analysis][3] f4, box vectors [n_it][R][3][3] f4 or None) of the analysis file; ``missing(iteration)``
+        makes the error for a frame that was never written (behind the last record, or still at netCDF's fill value)."""
+        if '/positions' not in self._a:
+            raise missing(iterations[0] if len(iterations) else 0)
+
+        def rows(name):
+            data = np.asarray(self._a.read(name))
+            for it in iterations:
+                if it < 0 or it >= data.shape[0]:
+                    raise missing(it)
+            out = np.array(data[list(iterations)], dtype=np.float32) if len(iterations) else np.zeros((0,) + data.shape[1:], np.float32)
+            bad = ~np.isfinite(out) | (np.abs(out) > 1e30)
+            for k in np.flatnonzero(bad.reshape(len(iterations), -1).any(axis=1)):
+                raise missing(iterations[k])
+            return out
+        x = rows('/positions')
+        return x, (rows('/box_vectors') if '/box_vectors' in self._a else None)
+
+
 # =====================================================================================================================
 # Writing the same layout (multistatereporter.py:280-460, 476-690, 865-1115, 1597-1737, 1817-1880)
 # =====================================================================================================================

@@ -14,7 +14,11 @@ published algorithms the analyzer relies on, in plain numpy:
   dimensionless free energies and the asymptotic covariance of eq. 8 / D6 (SVD form) for their uncertainties;
 * ``MultiStateSamplerAnalyzer`` — the analyzer's pipeline for global neighbourhoods: effective-energy timeseries
   (multistateanalyzer.py:1414-1478), equilibration data (:2026-2088), decorrelated u_ln / N_l assembly with the
-  unsampled states at the end points (:1479-1545), free energy differences (:1919-2003).
+  unsampled states at the end points (:1479-1545), free energy differences (:1919-2003); the unbiasing of a radially symmetric
+  receptor-ligand restraint (:1355-1408, :1556-1913): the restraint is re-evaluated at every stored, decorrelated frame, frames
+  outside a cutoff are dropped and two end states without the restraint join the MBAR problem.  The frames are evaluated in one
+  call, by ``restraint_frames_numpy`` or on the device (``analysis_kwargs={'restraint_solver': 'device'}``, csrc/restraint_frames.hip),
+  with the centroid convention the run was sampled with -- not the reference's, see DESIGN.md.
 
 Parity: unpinned against pymbar itself (absent); pinned against the analytical free energies of harmonic oscillators,
 the reference's own acceptance test (tests/test_sampling.py:100-300), in tests/test_analysis_cpu.py.
@@ -158,6 +162,78 @@ def generate_phase_name(current_name, name_list):
             name = current_name + str(counter)
         return name
     return current_name
+
+
+# ---- restraints at stored frames ---------------------------------------------------------------------------------
+class InsufficientData(Exception):
+    """multistateanalyzer.py:62-64: the stored data cannot answer the question (no frame of the bound state for an 'auto' cutoff)."""
+
+
+def compute_centroid_distance(positions_group1, positions_group2, weights_group1, weights_group2):
+    """multistateanalyzer.py:75-99: the distance between the weighted centres of two groups of positions (same units in, same out)."""
+    assert len(positions_group1) == len(weights_group1)
+    assert len(positions_group2) == len(weights_group2)
+    com_group1 = np.average(positions_group1, axis=0, weights=weights_group1)
+    com_group2 = np.average(positions_group2, axis=0, weights=weights_group2)
+    return np.linalg.norm(com_group1 - com_group2)
+
+
+def restraint_frames_numpy(desc, pos, box=None, masses=None, frames_per_pass=4096):
+    """(energy [F] kJ/mol at lambda = 1, distance [F] nm) of one restraint at F stored frames, in f64: the host counterpart of
+    remd_restraint_frames (include/remd_hip_restraints.h) with the engine's centroid convention, c = x_first + sum_i w_i img(x_i -
+    x_first), img the minimum image under the frame's own box when the restraint is periodic; d = c2 - c1 imaged the same way.
+    ``desc``: a dict of forces.restraint_terms whose atom indices address the atoms of ``pos`` [F][n_atoms][3]; weights None:
+    ``masses``.  ``box`` [F][3] or None."""
+    pos = np.asarray(pos)
+    if pos.ndim != 3 or pos.shape[2] != 3 or pos.shape[0] < 1:
+        raise ValueError('pos must be [F][n_atoms][3] with F >= 1')
+    F, n_atoms = pos.shape[0], pos.shape[1]
+    kind, K, r0 = int(desc['kind']), float(desc['K']), float(desc.get('r0', 0.0))
+    if kind not in (0, 1):
+        raise ValueError('unknown restraint kind %r' % (kind,))
+    periodic = bool(desc.get('periodic', 0))
+    if periodic:
+        if box is None:
+            raise ValueError('a periodic restraint needs the box of every frame')
+        box = np.asarray(box, dtype=np.float64)
+        if box.shape != (F, 3):
+            raise ValueError('box must be [F][3] (the edges of a rectangular box; triclinic boxes are not supported)')
+        if not (np.all(np.isfinite(box)) and np.all(box > 0.0)):
+            raise ValueError('a non-finite or non-positive box edge')
+    groups = []
+    for g in (1, 2):
+        atoms = np.asarray(desc['atoms%d' % g], dtype=np.int64).reshape(-1)
+        if atoms.size == 0:
+            raise ValueError('group %d is empty' % g)
+        if atoms.min() < 0 or atoms.max() >= n_atoms:
+            raise ValueError('an atom index of group %d is outside 0 ... %d' % (g, n_atoms - 1))
+        w = desc.get('weights%d' % g)
+        w = np.asarray(masses, dtype=np.float64)[atoms] if w is None else np.asarray(w, dtype=np.float64).reshape(-1)
+        if w.shape != atoms.shape or np.any(w < 0.0) or not w.sum() > 0.0:
+            raise ValueError('the weights of group %d are negative, sum to zero or do not match its atoms' % g)
+        groups.append((atoms, w / w.sum()))
+    energy, distance = np.empty(F), np.empty(F)
+    for f0 in range(0, F, frames_per_pass):                     # (bounds the f64 copies of the positions)
+        sl = slice(f0, min(F, f0 + frames_per_pass))
+        L = box[sl, None, :] if periodic else None
+        c = []
+        for atoms, w in groups:
+            x = pos[sl][:, atoms, :].astype(np.float64)
+            d = x - x[:, :1, :]
+            if periodic:
+                d -= L * np.rint(d / L)
+            c.append(x[:, 0, :] + np.einsum('k,fkc->fc', w, d))
+        d = c[1] - c[0]
+        if periodic:
+            d -= L[:, 0, :] * np.rint(d / L[:, 0, :])
+        r = np.sqrt((d * d).sum(axis=1))
+        distance[sl] = r
+        if kind == 0:
+            energy[sl] = 0.5 * K * r * r
+        else:
+            x = r - r0
+            energy[sl] = np.where(x >= 0.0, 1.0, 0.0) * 0.5 * K * x * x
+    return energy, distance
 
 
 # ---- MBAR --------------------------------------------------------------------------------------------------------
@@ -418,7 +494,8 @@ class MultiStateSamplerAnalyzer:
     """Free energies from a ``MultiStateReporter`` (multistateanalyzer.py:1164; global neighbourhoods only)."""
 
     def __init__(self, reporter, n_equilibration_iterations=None, statistical_inefficiency=None, max_subset=100,
-                 max_n_iterations=None, use_full_trajectory=False, analysis_kwargs=None):
+                 max_n_iterations=None, use_full_trajectory=False, analysis_kwargs=None, unbias_restraint=True,
+                 restraint_energy_cutoff='auto', restraint_distance_cutoff='auto'):
         if statistical_inefficiency is not None and n_equilibration_iterations is None:
             raise Exception('Cannot specify statistical_inefficiency without n_equilibration_iterations, because '
                             'otherwise n_equilibration_iterations cannot be computed for the given '
@@ -430,8 +507,17 @@ class MultiStateSamplerAnalyzer:
         self._max_n_iterations = max_n_iterations
         self.use_full_trajectory = use_full_trajectory
         self._kwargs = dict(analysis_kwargs or {})
+        # who evaluates the restraint at the stored frames: 'numpy' (restraint_frames_numpy, no GPU) or 'device' (csrc/restraint_frames.hip)
+        if self._kwargs.get('restraint_solver', 'numpy') not in ('numpy', 'device'):
+            raise ValueError("analysis_kwargs['restraint_solver'] must be 'numpy' or 'device', not %r" % (self._kwargs['restraint_solver'],))
         self._equilibration_data = None
         self._mbar = None
+        self._unbiased = None                   # (u_ln, N_l, initial_f_k) handed to MBAR
+        self._radially_symmetric_restraint_data = None
+        self._restraint_energies, self._restraint_distances = {}, {}      # {iteration: [replica]} kJ/mol / nm, kept across cutoffs
+        self._unbias_restraint = unbias_restraint
+        self._restraint_energy_cutoff = restraint_energy_cutoff
+        self._restraint_distance_cutoff = restraint_distance_cutoff
         self.name = None                       # :611-617: the phase name used when analyzers are combined
         self.reference_states = (0, -1)         # :633-643: the two states a phase's free energy is reported between
         self._sign = '+'
@@ -442,6 +528,24 @@ class MultiStateSamplerAnalyzer:
     @property
     def reporter(self):
         return self._reporter
+
+    def _restraint_option(name):                 # :1136-1169: a change forgets MBAR and the unbiased matrices, not the frame energies
+        def fget(self):
+            return getattr(self, '_' + name)
+
+        def fset(self, value):
+            old = getattr(self, '_' + name)
+            same = type(old) is type(value) and old == value
+            setattr(self, '_' + name, value)
+            if not same:
+                self._mbar = None
+                self._unbiased = None
+        return property(fget, fset)
+
+    unbias_restraint = _restraint_option('unbias_restraint')
+    restraint_energy_cutoff = _restraint_option('restraint_energy_cutoff')            # kT, 'auto' or None
+    restraint_distance_cutoff = _restraint_option('restraint_distance_cutoff')        # nm, 'auto' or None
+    del _restraint_option
 
     @property
     def n_iterations(self):
@@ -481,6 +585,9 @@ class MultiStateSamplerAnalyzer:
         """:596-608 / :1230-1241: forget everything derived from the storage."""
         self._equilibration_data = None
         self._mbar = None
+        self._unbiased = None
+        self._radially_symmetric_restraint_data = None
+        self._restraint_energies, self._restraint_distances = {}, {}
 
     @property
     def effective_length(self):
@@ -604,14 +711,19 @@ class MultiStateSamplerAnalyzer:
     def statistical_inefficiency(self):
         return (self._equilibration_data or self._get_equilibration_data())[1]
 
-    def _compute_mbar_decorrelated_energies(self):
-        """(u_ln, N_l) with the unsampled states at the two end points (:1479-1545)."""
+    def _decorrelated_selection(self):
+        """(sampled energies, unsampled energies, replica state indices, iterations): the equilibrated, decorrelated iterations."""
         e, eu, nb, states = self._read_energies()
         n_eq, g_t, _ = self._get_equilibration_data(e, states)
+        iterations = np.arange(e.shape[-1])
         if not self.use_full_trajectory:
-            e, eu, states = e[..., n_eq:], eu[..., n_eq:], states[..., n_eq:]
-            idx = subsample_correlated_data(np.zeros(e.shape[-1]), g=g_t)
-            e, eu, states = e[..., idx], eu[..., idx], states[..., idx]
+            iterations = iterations[n_eq:]
+            iterations = iterations[subsample_correlated_data(np.zeros(iterations.size), g=g_t)]
+        return e[..., iterations], eu[..., iterations], states[..., iterations], iterations
+
+    def _compute_mbar_decorrelated_energies(self, selection=None):
+        """(u_ln, N_l) with the unsampled states at the two end points (:1479-1545)."""
+        e, eu, states, _ = selection or self._decorrelated_selection()
         n_replicas, n_sampled, n_it = e.shape
         n_uns = eu.shape[1]
         n_total = n_sampled + n_uns
@@ -626,12 +738,169 @@ class MultiStateSamplerAnalyzer:
             u_ln[[0, -1], :] = np.concatenate([eu[k] for k in range(n_replicas)], axis=1)
         return u_ln, N_l
 
+    # ---- unbiasing a radially symmetric restraint (:1355-1408, :1556-1913) ----------------------------------------
+    def _get_radially_symmetric_restraint_data(self):
+        """(restraint force of the first end state's System, masses of its group 1, masses of its group 2), :1355-1408.
+        forces.NoForceFoundError without such a force (MultipleForcesError with several), TypeError when an end state has it off."""
+        from .. import forces
+        if self._radially_symmetric_restraint_data is not None:
+            return self._radially_symmetric_restraint_data
+        end_states = self._reporter.read_end_thermodynamic_states()
+        system = end_states[0].system
+        _, restraint_force = forces.find_forces(system, forces.RadiallySymmetricRestraintForce, only_one=True, include_subclasses=True)
+        default = restraint_force.getGlobalParameterDefaultValue(1)         # (a state that does not control the parameter leaves it there)
+        if getattr(end_states[0], 'lambda_restraints', default) != 1.0 or getattr(end_states[-1], 'lambda_restraints', default) != 1.0:
+            raise TypeError('Cannot unbias a restraint that is turned off at one of the end states.')
+        masses = np.asarray(system.masses, dtype=np.float64)
+        self._radially_symmetric_restraint_data = (restraint_force, [float(masses[i]) for i in restraint_force.restrained_atom_indices1],
+                                                   [float(masses[i]) for i in restraint_force.restrained_atom_indices2])
+        return self._radially_symmetric_restraint_data
+
+    def _evaluate_restraint_frames(self, desc, pos, box):
+        """(energy [F], distance [F]) by the solver analysis_kwargs['restraint_solver'] names."""
+        if self._kwargs.get('restraint_solver', 'numpy') == 'device':
+            from .._engine import restraint_frames
+            return restraint_frames(desc, pos, box, None, device=self._kwargs.get('device', 0), lib_path=self._kwargs.get('lib_path'))
+        return restraint_frames_numpy(desc, pos, box)
+
+    def _compute_restraint_energies(self, restraint_force, weights_group1, weights_group2, iterations=None):
+        """(energies [n_replicas * n_iterations] kJ/mol, distances [...] nm) of the restraint at the decorrelated iterations, frame =
+        replica * n_iterations + iteration index: the column order of _compute_mbar_decorrelated_energies (:1668-1825).  Iterations
+        evaluated before are served from the cache; the others are read in bulk and evaluated in ONE call."""
+        from .. import forces
+        if iterations is None:
+            iterations = self._decorrelated_selection()[3]
+        iterations = [int(i) for i in iterations]
+        todo = [i for i in iterations if i not in self._restraint_energies or i not in self._restraint_distances]
+        if todo:
+            analysis_indices = [int(i) for i in self._reporter.analysis_particle_indices]
+            where = {a: k for k, a in enumerate(analysis_indices)}
+            groups = (restraint_force.restrained_atom_indices1, restraint_force.restrained_atom_indices2)
+            mass_of = dict(zip(list(groups[0]) + list(groups[1]), list(weights_group1) + list(weights_group2)))
+            desc = forces.restraint_terms(restraint_force, mass_of)         # (a group without weights of its own: the masses)
+            for g in (1, 2):
+                atoms = [int(a) for a in groups[g - 1]]
+                for a in atoms:
+                    if a not in where:
+                        raise ValueError('restrained atom %d is not one of the analysis particles of the store: create the reporter '
+                                         'with analysis_particle_indices that include every restrained atom' % a)
+                desc['atoms%d' % g] = np.array([where[a] for a in atoms], dtype=np.int32)
+            x, box = self._reporter.read_analysis_positions(todo)            # [n_it][R][n_analysis][3], [n_it][R][3]
+            n_it, R = x.shape[0], x.shape[1]
+            pos = np.ascontiguousarray(x.transpose(1, 0, 2, 3)).reshape(R * n_it, x.shape[2], 3)
+            if desc['periodic'] and box is None:
+                raise ValueError('the restraint is periodic but the store holds no box vectors of the analysis particles')
+            box = None if box is None else np.ascontiguousarray(box.transpose(1, 0, 2)).reshape(R * n_it, 3)
+            energy, distance = self._evaluate_restraint_frames(desc, pos, box)
+            energy, distance = np.asarray(energy).reshape(R, n_it), np.asarray(distance).reshape(R, n_it)
+            for k, it in enumerate(todo):
+                self._restraint_energies[it], self._restraint_distances[it] = energy[:, k].copy(), distance[:, k].copy()
+        if not iterations:
+            return np.zeros(0), np.zeros(0)
+        return (np.stack([self._restraint_energies[i] for i in iterations], axis=1).reshape(-1),
+                np.stack([self._restraint_distances[i] for i in iterations], axis=1).reshape(-1))
+
+    def _get_use_restraint_cutoff(self):
+        """(apply an energy cutoff, apply a distance cutoff), :1827-1836: a number applies; both 'auto': the distance cutoff alone."""
+        is_number = lambda v: v is not None and not isinstance(v, str)
+        apply_distance_cutoff = is_number(self.restraint_distance_cutoff)
+        apply_energy_cutoff = is_number(self.restraint_energy_cutoff)
+        if self.restraint_distance_cutoff == 'auto' and not apply_energy_cutoff:
+            apply_distance_cutoff = True
+        elif self.restraint_energy_cutoff == 'auto' and self.restraint_distance_cutoff is None:
+            apply_energy_cutoff = True
+        return apply_energy_cutoff, apply_distance_cutoff
+
+    def _determine_automatic_restraint_cutoff(self, compute_energy_cutoff=True, compute_distance_cutoff=True):
+        """:1838-1892: the 99.9th percentile of the restraint energies (kT) / distances (nm) over the evaluated frames whose replica was
+        in state 0, the bound state."""
+        replica_state_indices = self._reporter.read_replica_thermodynamic_states()
+        out = []
+        for wanted, cached, scale, what in ((compute_energy_cutoff, self._restraint_energies, 1.0 / self.kT, 'energy'),
+                                            (compute_distance_cutoff, self._restraint_distances, 1.0, 'distance')):
+            if not wanted:
+                out.append(None)
+                continue
+            values = [cached[it][r] for it in cached for r in np.flatnonzero(replica_state_indices[it] == 0)]
+            if len(values) == 0:
+                raise InsufficientData('Thermodynamic state 0 has not been sampled enough to determine automatically the restraint '
+                                       '%s cutoff.' % what)
+            out.append(float(np.percentile(np.array(values) * scale, 99.9)))
+        return tuple(out)
+
+    def _get_restraint_cutoffs(self):
+        """(energy cutoff in kT or None, distance cutoff in nm or None), :1894-1913."""
+        from ..unit import to_md
+        apply_energy_cutoff, apply_distance_cutoff = self._get_use_restraint_cutoff()
+        if apply_distance_cutoff and self.restraint_distance_cutoff == 'auto':
+            distance_cutoff = self._determine_automatic_restraint_cutoff(compute_energy_cutoff=False)[1]
+        elif self.restraint_distance_cutoff == 'auto':
+            distance_cutoff = None
+        else:
+            distance_cutoff = None if self.restraint_distance_cutoff is None else float(to_md(self.restraint_distance_cutoff))
+        if apply_energy_cutoff and self.restraint_energy_cutoff == 'auto':
+            energy_cutoff = self._determine_automatic_restraint_cutoff(compute_distance_cutoff=False)[0]
+        elif self.restraint_energy_cutoff == 'auto':
+            energy_cutoff = None
+        else:
+            energy_cutoff = None if self.restraint_energy_cutoff is None else float(self.restraint_energy_cutoff)
+        return energy_cutoff, distance_cutoff
+
+    def _compute_mbar_unbiased_energies(self):
+        """(u_ln, N_l) with the restraint unbiased (:1556-1666): frames outside a cutoff dropped, two end states without the restraint
+        added.  Without a restraint to unbias, exactly what _compute_mbar_decorrelated_energies returns."""
+        from .. import forces
+        self._unbiased = None
+        selection = self._decorrelated_selection()
+        u_ln, N_l = self._compute_mbar_decorrelated_energies(selection)
+        initial_f_k = self._kwargs.get('initial_f_k')
+        restraint_data = None
+        if self.unbias_restraint:
+            try:
+                restraint_data = self._get_radially_symmetric_restraint_data()
+            except (TypeError, forces.NoForceFoundError):
+                restraint_data = None                   # nothing to unbias
+        if restraint_data is None:
+            self._unbiased = (u_ln, N_l, initial_f_k)
+            return u_ln, N_l
+        e, _, states, iterations = selection
+        energies_ln, distances_ln = self._compute_restraint_energies(*restraint_data, iterations=iterations)
+        energies_kJ, energies_ln = energies_ln, energies_ln / self.kT           # (kT of the first state: what the energy cutoff is in)
+        state_indices_ln = states.reshape(-1)                                 # [replica][iteration] -> frame
+        assert len(energies_ln) == u_ln.shape[1] == len(state_indices_ln)
+        energy_cutoff, distance_cutoff = self._get_restraint_cutoffs()
+        n_states = e.shape[1]
+        first_sampled_state_idx = int((len(u_ln) - n_states) / 2)
+        drop = np.zeros(len(energies_ln), dtype=bool)
+        if energy_cutoff is not None:
+            drop |= energies_ln > energy_cutoff
+        if distance_cutoff is not None:
+            drop |= distances_ln > distance_cutoff
+        N_l = N_l.copy()
+        np.subtract.at(N_l, state_indices_ln[drop] + first_sampled_state_idx, 1)
+        keep = np.flatnonzero(~drop)
+        u_ln, energies_kJ = u_ln[:, keep], energies_kJ[keep]
+        u_ln_new = np.zeros((u_ln.shape[0] + 2, u_ln.shape[1]), u_ln.dtype)
+        N_l_new = np.zeros(len(N_l) + 2, N_l.dtype)
+        # each end row loses the restraint in the kT of ITS OWN end state.  The reference divides both by the first state's kT
+        # (:1603, 1647-1648), the same number whenever all states share one temperature -- the only case in which it is right
+        from .. import constants
+        end_states = self._reporter.read_end_thermodynamic_states()
+        u_ln_new[0, :] = u_ln[0] - energies_kJ / (constants.kB * float(end_states[0].temperature))
+        u_ln_new[-1, :] = u_ln[-1] - energies_kJ / (constants.kB * float(end_states[-1].temperature))
+        u_ln_new[1:-1, :] = u_ln
+        N_l_new[1:-1] = N_l
+        if initial_f_k is not None and len(initial_f_k) == len(N_l):
+            initial_f_k = np.concatenate([[0.0], np.asarray(initial_f_k, dtype=np.float64), [0.0]])
+        self._unbiased = (u_ln_new, N_l_new, initial_f_k)
+        return u_ln_new, N_l_new
+
     @property
     def mbar(self):
         if self._mbar is None:
-            u_ln, N_l = self._compute_mbar_decorrelated_energies()
+            u_ln, N_l = self._compute_mbar_unbiased_energies()
             extra = {k: self._kwargs[k] for k in ('solver', 'device', 'lib_path') if k in self._kwargs}
-            self._mbar = MBAR(u_ln, N_l, initial_f_k=self._kwargs.get('initial_f_k'), **extra)
+            self._mbar = MBAR(u_ln, N_l, initial_f_k=self._unbiased[2], **extra)
         return self._mbar
 
     MixingStatistics = collections.namedtuple('MixingStatistics', ['transition_matrix', 'eigenvalues', 'statistical_inefficiency'])

@@ -236,12 +236,15 @@ class MultiStateReporter:
             with open(os.path.join(self._storage_analysis, 'meta.json')) as fh:
                 self._meta = json.load(fh)
             self._checkpoint_interval = int(self._meta.get('checkpoint_interval', self._checkpoint_interval))
+            # what the store holds takes priority over the constructor's argument, as in the netCDF4 layout: a trajectory of other
+            # particles, or one that starts in the middle of the run, could not be told from the one the analysis expects
+            self._analysis_particle_indices = tuple(int(i) for i in self._meta.get('analysis_particle_indices', ()))
             self._declare()
 
     _OWNED_NAMES = re.compile(
         r'^(meta\.json|last_iteration\.json(\.tmp)?|(thermodynamic_states|mcmc_moves|options|metadata)\.pkl|online_\w+_\d{9}\.pkl|'
         r'(energies|unsampled_energies|timestamp|logZ|log_weights|f_k|f_k_offline|free_energy)\.f8|neighborhoods\.i1|'
-        r'(states|accepted|proposed)\.i4|iteration_\d{9}(\.tmp)?\.npz)$')
+        r'(states|accepted|proposed)\.i4|analysis_(positions|box_vectors)\.f4|iteration_\d{9}(\.tmp)?\.npz)$')
 
     @classmethod
     def _owns(cls, filename):
@@ -287,6 +290,12 @@ class MultiStateReporter:
             'f_k_offline': _RecordFile(os.path.join(d, 'f_k_offline.f8'), 'f8', (K + U,)),
             'free_energy': _RecordFile(os.path.join(d, 'free_energy.f8'), 'f8', (2,)),
         }
+        n_analysis = len(m.get('analysis_particle_indices', ()))
+        if n_analysis:
+            # the flagged particles at EVERY iteration, dtype and particle order of the netCDF4 layout (:722-741; indices sorted);
+            # the box file exists only for a periodic store
+            self._files['analysis_positions'] = _RecordFile(os.path.join(d, 'analysis_positions.f4'), 'f4', (R, n_analysis, 3))
+            self._files['analysis_box_vectors'] = _RecordFile(os.path.join(d, 'analysis_box_vectors.f4'), 'f4', (R, 3, 3))
 
     def initialize(self, n_replicas, n_states, n_unsampled, n_atoms):
         """Dimensions of the record variables (the reference creates them lazily on first write)."""
@@ -296,6 +305,9 @@ class MultiStateReporter:
         self._meta = dict(n_replicas=int(n_replicas), n_states=int(n_states), n_unsampled=int(n_unsampled),
                           n_atoms=int(n_atoms), checkpoint_interval=self._checkpoint_interval,
                           format='openmmtools_amd-records-1', created=time.time())
+        if self._analysis_particle_indices:
+            self._analysis_particle_indices = tuple(sorted(self._analysis_particle_indices))
+            self._meta['analysis_particle_indices'] = list(self._analysis_particle_indices)
         with open(os.path.join(self._storage_analysis, 'meta.json'), 'w') as fh:
             json.dump(self._meta, fh)
         self._declare()
@@ -552,6 +564,17 @@ class MultiStateReporter:
             self._require_write()
             return self._ncw.write_sampler_states(sampler_states, iteration)
         self._require_write()
+        if self._analysis_particle_indices and 'analysis_positions' in self._files:
+            # :722-741: the flagged particles go to the ANALYSIS store at every iteration (every position_interval-th; the ones in
+            # between are written as NaN, which read_analysis_positions reports as missing)
+            sel = list(self._analysis_particle_indices)
+            xs = np.stack([np.asarray(s.positions, dtype=np.float64)[sel] for s in sampler_states]).astype('<f4')
+            written = self._position_interval != 0 and int(iteration) % self._position_interval == 0
+            self._files['analysis_positions'].write(iteration, xs if written else np.full_like(xs, np.nan))
+            # (an engine hands a vacuum run zero box vectors: not a box)
+            if written and all(s.box_vectors is not None and np.any(s.box_vectors) for s in sampler_states):
+                self._files['analysis_box_vectors'].write(
+                    iteration, np.stack([np.asarray(s.box_vectors, dtype=np.float64).reshape(3, 3) for s in sampler_states]))
         if iteration % self._checkpoint_interval != 0:
             return False
         x = np.stack([np.asarray(s.positions, dtype=np.float64) for s in sampler_states]).astype('<f4')
@@ -567,21 +590,70 @@ class MultiStateReporter:
 
     @_reference_read
     def read_sampler_states(self, iteration, analysis_particles_only=False):
-        """:1117-1165: None when ``iteration`` is not a checkpoint iteration."""
+        """:1117-1165: None when ``iteration`` is not a checkpoint iteration.  ``analysis_particles_only``: the flagged particles, which
+        the analysis store carries at every iteration (:696-705; zero velocities: the record container keeps none for them)."""
+        from .. import states
+        if analysis_particles_only:
+            if 'analysis_positions' not in self._files:
+                raise ValueError('No particles were flagged for special analysis! No such trajectory would have been written!')
+            x, box = self._read_analysis_records([int(iteration)])
+            return [states.SamplerState(x[0, r].astype(np.float64), velocities=np.zeros(x.shape[2:]),
+                                        box_vectors=None if box is None else box[0, r].astype(np.float64)) for r in range(x.shape[1])]
         path = self._checkpoint_path(iteration)
         if not os.path.exists(path):
             return None
-        from .. import states
         with np.load(path) as d:
             x, v, box, has_box = d['positions'], d['velocities'], d['box_vectors'], bool(d['has_box'])
         return [states.SamplerState(x[r].astype(np.float64), velocities=v[r].astype(np.float64),
                                     box_vectors=box[r].astype(np.float64) if has_box else None) for r in range(len(x))]
 
+    @staticmethod
+    def _missing_positions(iteration):
+        return ValueError('iteration %d has no stored positions of the analysis particles: set analysis_particle_indices (or '
+                          'checkpoint_interval=1) when the simulation is created' % int(iteration))
+
+    def _read_analysis_records(self, iterations):
+        """(positions [n_it][R][n_analysis][3] f4, box vectors [n_it][R][3][3] f4 or None) of the record container."""
+        if 'analysis_positions' not in self._files:
+            raise self._missing_positions(iterations[0] if len(iterations) else 0)
+        last = self.read_last_iteration(last_checkpoint=False)
+
+        def rows(f):
+            n = f.count()
+            for it in iterations:
+                if it < 0 or it >= n or (last is not None and it > last):
+                    raise self._missing_positions(it)
+            if not len(iterations):
+                return np.zeros((0,) + f.shape, f.dtype)
+            return np.array(np.memmap(f.path, dtype=f.dtype, mode='r', shape=(n,) + f.shape)[list(iterations)])
+        x = rows(self._files['analysis_positions'])
+        for k in np.flatnonzero(~np.isfinite(x).all(axis=(1, 2, 3))):
+            raise self._missing_positions(iterations[k])
+        fb = self._files['analysis_box_vectors']
+        return x, (rows(fb) if os.path.exists(fb.path) else None)
+
+    def read_analysis_positions(self, iterations):
+        """The analysis particles at many iterations at once, in both layouts: (positions [n_it][R][n_analysis][3] f4 in the order of
+        ``analysis_particle_indices``, box [n_it][R][3] f4 -- the edges of the rectangular box -- or None for a store that is not
+        periodic).  No SamplerState is built.  ValueError names an iteration that has no stored positions."""
+        iterations = [int(i) for i in iterations]
+        if self._ref is not None:
+            x, box = self._ref.read_analysis_positions(iterations, self._missing_positions)
+        else:
+            x, box = self._read_analysis_records(iterations)
+        if box is None or not np.any(box):
+            return x, None
+        off = box.copy()
+        off[..., [0, 1, 2], [0, 1, 2]] = 0.0
+        if np.any(off != 0.0):
+            raise ValueError('triclinic boxes are not supported: the stored box vectors of the analysis particles are not rectangular')
+        return x, np.ascontiguousarray(box[..., [0, 1, 2], [0, 1, 2]])
+
     # ---- the sampler's hook: what MultiStateSampler._report_iteration does (multistatesampler.py:1189-1222) --
     def write_iteration(self, sampler):
         # positions are needed on checkpoint iterations -- and at every iteration when particles are flagged for the analysis file
-        # (multistatereporter.py:722-741; the netCDF4 layout only)
-        every = bool(self._analysis_particle_indices) and str(self._storage_analysis).endswith('.nc') and self.layout != 'records'
+        # (multistatereporter.py:722-741; both layouts)
+        every = bool(self._analysis_particle_indices)
         if getattr(sampler, '_comm', None) is not None and sampler._comm.rank != 0:
             if every or sampler._iteration % self._checkpoint_interval == 0:
                 sampler._gather_sampler_states()          # collective: every rank takes part

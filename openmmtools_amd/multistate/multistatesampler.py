@@ -942,7 +942,9 @@ class MultiStateSampler:
                 analysis_kwargs['solver'] = self.online_analysis_solver
                 if isinstance(getattr(self._engine, 'device', None), int):
                     analysis_kwargs['device'] = self._engine.device
-            analysis = MultiStateSamplerAnalyzer(self._reporter, analysis_kwargs=analysis_kwargs)
+            # the estimate inside the run loop stays between the states as they were sampled: its stored record (f_k_offline) has one
+            # entry per sampled and unsampled state, and unbiasing a restraint adds two (multistate/analysis.py does it after the run)
+            analysis = MultiStateSamplerAnalyzer(self._reporter, analysis_kwargs=analysis_kwargs, unbias_restraint=False)
             try:
                 mbar = analysis.mbar
                 free_energy, err_free_energy = analysis.get_free_energy()
