@@ -45,7 +45,29 @@
  * beta_l (coeff_l - coeff_own) / V.  One wavefront per tile of 64 x 64 particles, every tile visited (csrc/custom_nonbonded.hip): the
  * cost is quadratic in N.
  *
- * Not provided: tabulated functions, pointangle, pointdihedral, interaction groups.
+ * Tabulated functions (OpenMM's Continuous1DFunction and Discrete1DFunction) of every kind above: REMD_CX_TABLE1D and
+ * REMD_CX_LOOKUP1D take one argument x from the stack and push one result; the operand is the offset of the function's block in the
+ * force's constants.  The blocks follow the scalar constants, one per function:
+ *     REMD_CX_TABLE1D:  [n, min, max, periodic], y[n], y''[n]     (4 + 2 n doubles; n = 2 ... REMD_CUSTOM_MAX_TABLE_POINTS, integral;
+ *                                                                  min < max, both finite; periodic 0 or 1)
+ *     REMD_CX_LOOKUP1D: [n], values[n]                            (1 + n doubles; n = 1 ... REMD_CUSTOM_MAX_TABLE_POINTS)
+ * y are the samples at n uniformly spaced points over [min, max], y'' the second derivatives of the cubic spline through them, solved
+ * by the host in f64 (natural: y'' = 0 at both ends; periodic: y''[n-1] = y''[0]).  With h = (max - min) / (n - 1), on interval i,
+ * a = (x[i+1] - t) / h, b = (t - x[i]) / h:
+ *     y = a y[i] + b y[i+1] + ((a^3 - a) y''[i] + (b^3 - b) y''[i+1]) h^2 / 6,
+ *     dy/dt = (y[i+1] - y[i]) / h + ((1 - 3 a^2) y''[i] + (3 b^2 - 1) y''[i+1]) h / 6.
+ * (b is computed as (t - min) / h - i and a as 1 - b, so that a + b is exactly 1.)  periodic = 1 wraps the argument,
+ * t = x - (max - min) floor((x - min) / (max - min)), clamped into [min, max] (the wrap's rounding may leave it an ulp outside; an
+ * argument too large to have a place in the period lands on an end); else t = x.  Out of range: t outside [min, max] (a function that
+ * is not periodic) pushes 0 with the derivative 0, OpenMM's reference behaviour; exactly min and max belong to the end intervals; a
+ * NaN argument (an infinite one of a periodic function) pushes NaN.  REMD_CX_LOOKUP1D pushes values[round(x)] (halves away from zero, C's round) with the derivative 0, and NaN where the index
+ * falls outside 0 ... n - 1: the device cannot raise, and a NaN energy is what a host's NaN check catches.  No argument makes the
+ * device load outside the block.  n_consts has no cap of its own: scalars and blocks together, at most what REMD_CUSTOM_MAX_PROGRAM
+ * instructions can name (128 one-argument calls of 4 + 2 REMD_CUSTOM_MAX_TABLE_POINTS doubles each, 2 097 664 doubles per force).
+ * The long-range correction of a nonbonded force whose expression calls a table is the host's business (openmmtools_amd refuses it).
+ *
+ * Not provided: Continuous2DFunction, Continuous3DFunction, Discrete2DFunction, Discrete3DFunction, changing a table after
+ * remd_set_custom_terms, pointangle, pointdihedral, interaction groups.
  *
  * Global parameters belong to the handle: every force's program addresses the same n_globals columns, and every state carries one
  * value per column (remd_set_custom_globals).  A term acts in every force evaluation (MD steps, energies, the barostat,
@@ -54,7 +76,8 @@
  *
  * Limits (a descriptor beyond them is refused): REMD_CUSTOM_MAX_PROGRAM instructions per force, REMD_CUSTOM_MAX_STACK stack slots,
  * REMD_CUSTOM_MAX_PARAMS parameters per term, REMD_CUSTOM_MAX_GLOBALS global columns per handle, REMD_CUSTOM_MAX_FORCES forces
- * per handle (of all kinds together), REMD_CUSTOM_MAX_PARTICLES particles per compound bond or groups per centroid bond.
+ * per handle (of all kinds together), REMD_CUSTOM_MAX_PARTICLES particles per compound bond or groups per centroid bond,
+ * REMD_CUSTOM_MAX_TABLE_POINTS points per tabulated function.
  *
  * These entry points are declared here and not in remd_hip.h because the CPU port of the ABI does not provide them: a host binds
  * them only where the loaded library exports them.  Conventions as in remd_hip.h.
@@ -82,6 +105,7 @@ extern "C" {
 #define REMD_CUSTOM_MAX_GLOBALS 16
 #define REMD_CUSTOM_MAX_FORCES  8
 #define REMD_CUSTOM_MAX_PARTICLES 8
+#define REMD_CUSTOM_MAX_TABLE_POINTS 8192   /* points of one tabulated function                                               */
 
 /* opcodes */
 #define REMD_CX_CONST   0      /* push consts[operand]                                                                      */
@@ -122,7 +146,9 @@ extern "C" {
 #define REMD_CX_DISTANCE 35     /* distance of the particle slots operand & 15, (operand >> 4) & 15; pushes, pops nothing    */
 #define REMD_CX_ANGLE    36     /* angle at the middle one of three particle slots, 4 bits each                              */
 #define REMD_CX_DIHEDRAL 37     /* dihedral of four particle slots, 4 bits each                                              */
-#define REMD_CX_N_OPCODES 38
+#define REMD_CX_TABLE1D  38     /* the cubic spline of the block at consts[operand] at the argument on the stack               */
+#define REMD_CX_LOOKUP1D 39     /* values[round(argument)] of the block at consts[operand]; NaN outside 0 ... n - 1           */
+#define REMD_CX_N_OPCODES 40
 
 typedef struct remd_custom_force_desc {
     int32_t kind;                  /* REMD_CUSTOM_*                                                                        */

@@ -8,6 +8,7 @@
 // gradient with respect to ONE particle, `seed`: the coordinates of that particle carry the unit partials, every other coordinate
 // carries zero, and an opcode of particles pushes its value with its gradient with respect to particle `seed` (zero where `seed` is
 // not among its arguments; formulas and guards of cst_geometry in custom_terms.hip).  seed = -1: values only.
+// Both instantiations know the tabulated functions, REMD_CX_TABLE1D / REMD_CX_LOOKUP1D (cst_table1d, cst_lookup1d below).
 #pragma once
 #include "remd_internal.h"
 #include "../../include/remd_hip_custom.h"
@@ -134,6 +135,45 @@ __device__ __forceinline__ cx cst_particles_op(int op, int arg, int seed, const 
     return cx{v, g.x, g.y, g.z};
 }
 
+// Tabulated functions (include/remd_hip_custom.h: REMD_CX_TABLE1D, REMD_CX_LOOKUP1D).  B is the function's block in the force's
+// constants, consts + f.const0 + operand: wave-uniform, so the header loads are; the loads of y and y'' are one gather per lane.
+// remd_set_custom_terms has checked the header and that the block ends inside the constants (check_program), so an index is safe
+// exactly when it lies inside the block.  That must hold for EVERY argument: the padding lanes of a wavefront, and of a nonbonded
+// tile, run the program on whatever their registers hold (a repeated last term, a distance of atoms that are not a pair, possibly
+// huge, infinite or NaN), and a function of a variable is handed whatever the geometry gives.  Hence: the argument is range-tested
+// in f64 first (a NaN fails every comparison), only a value that passed is converted to an integer, the integer is clamped again,
+// and a lane that failed loads nothing.  Such a lane pushes 0 (OpenMM's value outside the range), or NaN for a NaN.
+__device__ __forceinline__ void cst_table1d(const double* __restrict__ B, double x, double& v, double& k)
+{
+    const int n = (int)B[0];                                  // 2 ... REMD_CUSTOM_MAX_TABLE_POINTS
+    const double lo = B[1], hi = B[2], L = hi - lo, h = L / (double)(n - 1);
+    // periodic: into [min, max); the rounding of the wrap may leave it an ulp outside, so it is clamped (an argument too large to
+    // have a place in the period lands on an end; an infinite one gives NaN, which the comparisons keep: fmin / fmax would drop it)
+    const double w = x - L * floor((x - lo) / L);
+    const double t = B[3] != 0.0 ? (w < lo ? lo : w > hi ? hi : w) : x;
+    const bool inside = t >= lo && t <= hi;
+    const double s = inside ? (t - lo) / h : 0.0;                            // in [0, n - 1] (rounding aside) where it is converted
+    const int i = min(max((int)s, 0), n - 2);
+    v = t != t ? t : 0.0; k = 0.0;
+    if (inside) {
+        const double y0 = B[4 + i], y1 = B[5 + i], d0 = B[4 + n + i], d1 = B[5 + n + i];
+        const double b = s - (double)i, a = 1.0 - b;          // (t - x_i) / h; a = (x_{i+1} - t) / h as 1 - b, so that a + b is exactly 1
+        v = a * y0 + b * y1 + ((a * a * a - a) * d0 + (b * b * b - b) * d1) * (h * h / 6.0);
+        k = (y1 - y0) / h + ((1.0 - 3.0 * a * a) * d0 + (3.0 * b * b - 1.0) * d1) * (h / 6.0);
+    }
+}
+
+// values[round(x)], halves away from zero; NaN, and no load, where the index falls outside 0 ... n - 1 (the device cannot raise)
+__device__ __forceinline__ double cst_lookup1d(const double* __restrict__ B, double x)
+{
+    const double r = round(x), last = B[0] - 1.0;            // B[0] = n, 1 ... REMD_CUSTOM_MAX_TABLE_POINTS
+    const bool inside = r >= 0.0 && r <= last;
+    const int i = inside ? (int)r : 0;
+    double v = __builtin_nan("");
+    if (inside) v = B[1 + i];
+    return v;
+}
+
 // the program of force f at term t (lane's own) under the globals g (wave-uniform); the result's partials are dE/dvariable
 // (GEOM: dE/d(x, y, z) of particle `seed`; x0, x1, x2 are not read)
 template <bool GEOM>
@@ -199,7 +239,7 @@ __device__ __forceinline__ cx cst_eval(const cst_force& f, const int2* __restric
             sp -= 5;
         } break;
         default: {                                        // one argument, or (GEOM) a function of particles: no argument
-            if (GEOM && op >= REMD_CX_DISTANCE) { cx_st(S, sp++, lane, cst_particles_op(op, arg, seed, X, lane, Lx, Ly, Lz)); break; }
+            if (GEOM && op >= REMD_CX_DISTANCE && op <= REMD_CX_DIHEDRAL) { cx_st(S, sp++, lane, cst_particles_op(op, arg, seed, X, lane, Lx, Ly, Lz)); break; }
             const cx x = cx_ld(S, sp - 1, lane);
             double v = 0.0, k = 0.0;
             switch (op) {
@@ -229,6 +269,8 @@ __device__ __forceinline__ cx cst_eval(const cst_force& f, const int2* __restric
             case REMD_CX_DELTA: v = x.v == 0.0 ? 1.0 : 0.0; break;
             case REMD_CX_FLOOR: v = floor(x.v); break;
             case REMD_CX_CEIL: v = ceil(x.v); break;
+            case REMD_CX_TABLE1D: cst_table1d(consts + f.const0 + arg, x.v, v, k); break;
+            case REMD_CX_LOOKUP1D: v = cst_lookup1d(consts + f.const0 + arg, x.v); break;
             default: break;
             }
             cx_st(S, sp - 1, lane, cx_chain(v, k, x));

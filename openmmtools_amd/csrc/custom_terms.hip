@@ -249,6 +249,21 @@ const char* check_program(const remd_custom_force_desc& d, int n_vars)
             pops = 0;
         } break;
         case REMD_CX_POWI: if (arg < -64 || arg > 64) return "an integer power beyond +-64"; break;
+        case REMD_CX_TABLE1D: case REMD_CX_LOOKUP1D: {
+            // the block of the function at consts[arg] (include/remd_hip_custom.h): the kernels trust n, min, max and the block's extent
+            const bool spline = op == REMD_CX_TABLE1D;
+            if (arg < 0 || arg >= d.n_consts || !d.consts) return "a table offset out of range";
+            const double n = d.consts[arg];
+            if (!(n >= (spline ? 2.0 : 1.0) && n <= (double)REMD_CUSTOM_MAX_TABLE_POINTS) || n != floor(n))
+                return spline ? "a table whose point count is not an integer 2 ... REMD_CUSTOM_MAX_TABLE_POINTS"
+                              : "a lookup table whose value count is not an integer 1 ... REMD_CUSTOM_MAX_TABLE_POINTS";
+            if ((long long)arg + (spline ? 4 + 2 * (long long)n : 1 + (long long)n) > (long long)d.n_consts) return "a table that runs past n_consts";
+            if (spline) {
+                const double lo = d.consts[arg + 1], hi = d.consts[arg + 2], periodic = d.consts[arg + 3];
+                if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi)) return "a table whose bounds are not finite with min < max";
+                if (periodic != 0.0 && periodic != 1.0) return "a table whose periodic flag is neither 0 nor 1";
+            }
+        } break;
         default: if (op < 0 || op >= REMD_CX_N_OPCODES) return "an unknown opcode"; break;
         }
         if (sp < pops) return "a program that pops an empty stack";

@@ -22,8 +22,13 @@ definitions ``name = expr`` in any order, substituted where they are used.  ``^`
 right, as in OpenMM's Lepton.  A constant integer exponent up to +-64 becomes REMD_CX_POWI (multiplications: defined for a negative
 base); every other power is REMD_CX_POW.
 
-The limits are the engine's (include/remd_hip_custom.h); what is over them, an unknown name, an unknown or tabulated function is
-refused with NotImplementedError naming the force and the item.
+Tabulated functions: a call of a force's system.Continuous1DFunction (natural or periodic cubic spline) compiles to TABLE1D, of a
+system.Discrete1DFunction to LOOKUP1D; the function's samples, and the spline's second derivatives solved here in f64
+(spline_second_derivatives), travel as a block of the force's constants behind the scalars, the operand its offset (layout and
+out-of-range rules: include/remd_hip_custom.h).  At most MAX_TABLE_POINTS points per function.
+
+The limits are the engine's (include/remd_hip_custom.h); what is over them, an unknown name, an unknown function or a tabulated
+function of another kind is refused with NotImplementedError naming the force and the item.
 """
 import re
 
@@ -33,6 +38,7 @@ MAX_PROGRAM, MAX_STACK, MAX_PARAMS, MAX_GLOBALS, MAX_FORCES = 256, 16, 16, 16, 8
 MAX_INTEGER_POWER = 64
 MAX_PARTICLES = 8                               # particles per bond of a compound-bond force
 MAX_PAIR_PARAMS = MAX_PARAMS // 2               # per-particle parameters of a nonbonded force (each appears twice in a pair's program)
+MAX_TABLE_POINTS = 8192                         # points of one tabulated function
 
 KIND_BOND, KIND_ANGLE, KIND_TORSION, KIND_EXTERNAL, KIND_COMPOUND, KIND_CENTROID, KIND_NONBONDED = 0, 1, 2, 3, 4, 5, 6
 KIND_OF_CLASS = {'CustomNonbondedForce': KIND_NONBONDED, 'CustomBondForce': KIND_BOND, 'CustomAngleForce': KIND_ANGLE, 'CustomTorsionForce': KIND_TORSION,
@@ -47,7 +53,8 @@ def compound_variables(n_particles):
 
 # opcodes (include/remd_hip_custom.h)
 (CONST, VAR, PARAM, GLOBAL, ADD, SUB, MUL, DIV, NEG, POWI, POW, SQRT, EXP, LOG, SIN, COS, TAN, ASIN, ACOS, ATAN, ATAN2, SINH, COSH,
- TANH, ERF, ERFC, ABS, MIN, MAX, STEP, DELTA, SELECT, FLOOR, CEIL, PERIODICDISTANCE, DISTANCE, ANGLE, DIHEDRAL) = range(38)
+ TANH, ERF, ERFC, ABS, MIN, MAX, STEP, DELTA, SELECT, FLOOR, CEIL, PERIODICDISTANCE, DISTANCE, ANGLE, DIHEDRAL, TABLE1D,
+ LOOKUP1D) = range(40)
 
 # name -> (opcode, number of arguments)
 FUNCTIONS = dict(sqrt=(SQRT, 1), exp=(EXP, 1), log=(LOG, 1), sin=(SIN, 1), cos=(COS, 1), tan=(TAN, 1), asin=(ASIN, 1), acos=(ACOS, 1),
@@ -190,12 +197,78 @@ def split_definitions(energy, where='expression'):
     return parts[0], definitions
 
 
+def spline_second_derivatives(values, lo, hi, periodic=False):
+    """y'' [n] of the cubic spline through ``values`` at n uniformly spaced points over [lo, hi], in f64: the natural spline (y'' = 0 at
+    both ends; the tridiagonal system y''[i-1] + 4 y''[i] + y''[i+1] = 6 (y[i+1] - 2 y[i] + y[i-1]) / h^2 by the Thomas algorithm) or the
+    periodic one (the same rows cyclically over the n - 1 distinct points, by the Thomas algorithm with the Sherman-Morrison correction;
+    y''[n-1] = y''[0])."""
+    y = np.asarray(values, dtype=np.float64)
+    n = len(y)
+    h = (float(hi) - float(lo)) / (n - 1)
+    out = np.zeros(n)
+
+    def thomas(diag, rhs):                      # off-diagonals 1
+        m = len(rhs)
+        c, d = np.zeros(m), np.zeros(m)
+        c[0], d[0] = 1.0 / diag[0], rhs[0] / diag[0]
+        for i in range(1, m):
+            w = diag[i] - c[i - 1]
+            c[i], d[i] = 1.0 / w, (rhs[i] - d[i - 1]) / w
+        x = np.zeros(m)
+        x[-1] = d[-1]
+        for i in range(m - 2, -1, -1):
+            x[i] = d[i] - c[i] * x[i + 1]
+        return x
+
+    if not periodic:
+        if n > 2:
+            out[1:-1] = thomas(np.full(n - 2, 4.0), 6.0 * (y[2:] - 2.0 * y[1:-1] + y[:-2]) / (h * h))
+        return out
+    m = n - 1                                   # the distinct points; the neighbours of point i are i - 1 and i + 1 modulo m
+    p = y[:m]
+    rhs = 6.0 * (np.roll(p, -1) - 2.0 * p + np.roll(p, 1)) / (h * h)
+    if m == 2:                                  # both neighbours are the other point: 4 a + 2 b = rhs0, 2 a + 4 b = rhs1
+        out[0], out[1] = (4.0 * rhs[0] - 2.0 * rhs[1]) / 12.0, (4.0 * rhs[1] - 2.0 * rhs[0]) / 12.0
+    else:
+        gamma = -4.0
+        diag = np.full(m, 4.0)
+        diag[0] -= gamma
+        diag[-1] -= 1.0 / gamma
+        u = np.zeros(m)
+        u[0], u[-1] = gamma, 1.0
+        x, z = thomas(diag, rhs), thomas(diag, u)
+        out[:m] = x - z * (x[0] + x[-1] / gamma) / (1.0 + z[0] + z[-1] / gamma)
+    out[-1] = out[0]
+    return out
+
+
+def _table_block(name, function, where):
+    """(opcode, the function's block of the constant table): [n, min, max, periodic], y [n], y'' [n] of a Continuous1DFunction,
+    [n], values [n] of a Discrete1DFunction (include/remd_hip_custom.h)"""
+    from . import system as _system
+    if isinstance(function, _system.Continuous1DFunction):
+        values, lo, hi = function.getFunctionParameters()
+        periodic = bool(function.getPeriodic())
+        if len(values) > MAX_TABLE_POINTS:
+            raise NotImplementedError('%s: tabulated function %r has %d points (the engine takes %d)' % (where, name, len(values), MAX_TABLE_POINTS))
+        return TABLE1D, np.concatenate([[len(values), lo, hi, float(periodic)], values, spline_second_derivatives(values, lo, hi, periodic)])
+    if isinstance(function, _system.Discrete1DFunction):
+        values = function.getFunctionParameters()
+        if len(values) > MAX_TABLE_POINTS:
+            raise NotImplementedError('%s: tabulated function %r has %d points (the engine takes %d)' % (where, name, len(values), MAX_TABLE_POINTS))
+        return LOOKUP1D, np.concatenate([[len(values)], values])
+    raise NotImplementedError('%s: tabulated function %r (a %s: only Continuous1DFunction and Discrete1DFunction are supported)'
+                              % (where, name, type(function).__name__))
+
+
 def compile_expression(energy, variables, parameters, global_columns, where='expression', tabulated=(), periodic_distance=False,
                        n_particles=0, particle_prefix='p', pair_parameters=()):
     """The postfix program of ``energy``.
 
     variables: the force's own variable names in operand order; parameters: the per-term parameter names in order; global_columns:
-    {global parameter name: column of the handle's table}; tabulated: names of tabulated functions (refused); periodic_distance:
+    {global parameter name: column of the handle's table}; tabulated: the force's (name, function) pairs: a call of a
+    system.Continuous1DFunction compiles to TABLE1D, of a system.Discrete1DFunction to LOOKUP1D, the operand the offset of the
+    function's block in the constants (behind the scalar constants, one block per function called); periodic_distance:
     whether periodicdistance(...) is allowed (an external force that uses periodic boundary conditions); n_particles: the particles
     per bond of a compound-bond force (0: another force), which opens distance / angle / dihedral over p1 ... pP and pointdistance;
     particle_prefix: 'p', or 'g' for the groups g1 ... gP of a centroid-bond force (the messages then speak of groups);
@@ -209,6 +282,8 @@ def compile_expression(energy, variables, parameters, global_columns, where='exp
     other = {'p': 'g', 'g': 'p'}[particle_prefix]
     trees = {}
     program, consts, const_index = [], [], {}
+    functions = dict(tabulated)                 # name -> function
+    blocks, table_calls = {}, []                # name -> (opcode, block), in the order first called; (instruction, name) of every call
     depth = [0, 0]                              # current, maximum
 
     def tree_of(name):
@@ -278,8 +353,14 @@ def compile_expression(energy, variables, parameters, global_columns, where='exp
             return emit(POW)
         if kind == 'call':
             name, args = node[1], node[2]
-            if name in tabulated:
-                raise NotImplementedError('%s: tabulated function %r (tabulated functions are not supported)' % (where, name))
+            if name in functions:
+                if name not in blocks:
+                    blocks[name] = _table_block(name, functions[name], where)
+                if len(args) != 1:
+                    raise NotImplementedError('%s: tabulated function %r takes 1 argument, not %d' % (where, name, len(args)))
+                walk(args[0], active)
+                table_calls.append((len(program), name))
+                return emit(blocks[name][0])
             if n_particles and name in PARTICLE_FUNCTIONS:
                 op, n_args = PARTICLE_FUNCTIONS[name]
                 if len(args) != n_args:
@@ -316,6 +397,13 @@ def compile_expression(energy, variables, parameters, global_columns, where='exp
         raise NotImplementedError('%s: cannot compile %r' % (where, node))
 
     walk(_Parser(body, where).parse(), frozenset())
+    # the tables' blocks behind the scalar constants (which deduplicate among themselves only); a call's operand is its block's offset
+    offsets = {}
+    for name, (_, block) in blocks.items():
+        offsets[name] = len(consts)
+        consts += block.tolist()
+    for pc, name in table_calls:
+        program[pc] = (program[pc][0], offsets[name])
     if len(program) > MAX_PROGRAM:
         raise NotImplementedError('%s: a program of %d instructions (the engine takes %d)' % (where, len(program), MAX_PROGRAM))
     if depth[1] > MAX_STACK:
@@ -376,6 +464,37 @@ def centroid_groups(force, masses):
             np.concatenate(weights) if weights else np.zeros(0, dtype=np.float64))
 
 
+def table_values(consts, offset, x):
+    """TABLE1D at every element of x: the spline of the block at ``offset`` (the formulas of the device, csrc/custom_machine.h); 0 outside
+    [min, max] of a function that is not periodic, NaN for a NaN argument"""
+    consts, x = np.asarray(consts, dtype=np.float64), np.asarray(x, dtype=np.float64)
+    n, lo, hi, periodic = int(consts[offset]), consts[offset + 1], consts[offset + 2], consts[offset + 3] != 0.0
+    y, y2 = consts[offset + 4:offset + 4 + n], consts[offset + 4 + n:offset + 4 + 2 * n]
+    h = (hi - lo) / (n - 1)
+    with np.errstate(all='ignore'):
+        # (the wrap's rounding may leave t an ulp outside [min, max]: clamped; np.clip keeps a NaN)
+        t = np.clip(x - (hi - lo) * np.floor((x - lo) / (hi - lo)), lo, hi) if periodic else x
+        inside = (t >= lo) & (t <= hi)
+        s = (np.where(inside, t, lo) - lo) / h
+        i = np.clip(s.astype(np.int64), 0, n - 2)
+        b = s - i                               # (t - x_i) / h, and a = (x_{i+1} - t) / h taken as 1 - b: a + b is exactly 1
+        a = 1.0 - b
+        v = a * y[i] + b * y[i + 1] + ((a * a * a - a) * y2[i] + (b * b * b - b) * y2[i + 1]) * (h * h / 6.0)
+    return np.where(inside, v, np.where(np.isnan(t), np.nan, 0.0))
+
+
+def lookup_values(consts, offset, x):
+    """LOOKUP1D at every element of x: values[round(x)], halves away from zero; NaN where the index is outside 0 ... n - 1"""
+    consts, x = np.asarray(consts, dtype=np.float64), np.asarray(x, dtype=np.float64)
+    n = int(consts[offset])
+    with np.errstate(all='ignore'):
+        whole = np.trunc(x)
+        k = whole + np.where(np.abs(x - whole) >= 0.5, np.sign(x), 0.0)
+        inside = (k >= 0.0) & (k <= n - 1.0)
+        v = consts[offset + 1 + np.where(inside, k, 0.0).astype(np.int64)]
+    return np.where(inside, v, np.nan)
+
+
 def run_values(prog, r, params, global_values):
     """The value of a compiled one-variable program at every element of the array ``r`` (f64): the Python interpreter of the machine,
     values only (no partials), numpy-vectorised over r.  params: the PARAM operands' values; global_values: the GLOBAL columns'."""
@@ -415,6 +534,10 @@ def run_values(prog, r, params, global_values):
                 stack.append(1.0 / v if arg < 0 else v)
             elif op in unary:
                 stack.append(unary[op](stack.pop()))
+            elif op == TABLE1D:
+                stack.append(table_values(prog['consts'], arg, stack.pop()))
+            elif op == LOOKUP1D:
+                stack.append(lookup_values(prog['consts'], arg, stack.pop()))
             else:
                 raise NotImplementedError('run_values: opcode %d' % op)
     assert len(stack) == 1
@@ -558,7 +681,7 @@ def custom_terms_desc(forces, masses=None, box_vectors=None):
             raise NotImplementedError('%s: %d per-particle parameters (the engine takes %d): %s' % (cls, len(per_term), MAX_PAIR_PARAMS, ', '.join(per_term)))
         if len(per_term) > MAX_PARAMS:
             raise NotImplementedError('%s: %d per-term parameters (the engine takes %d): %s' % (cls, len(per_term), MAX_PARAMS, ', '.join(per_term)))
-        tabulated = [f.getTabulatedFunctionName(i) for i in range(f.getNumTabulatedFunctions())]
+        tabulated = [(f.getTabulatedFunctionName(i), f.getTabulatedFunction(i)) for i in range(f.getNumTabulatedFunctions())]
         own = {n: columns[n] for n in (f.getGlobalParameterName(i) for i in range(f.getNumGlobalParameters()))}
         periodic = bool(f.usesPeriodicBoundaryConditions())
         n_particles = 0
@@ -575,6 +698,10 @@ def custom_terms_desc(forces, masses=None, box_vectors=None):
                                   where=where, tabulated=tabulated, periodic_distance=(kind == KIND_EXTERNAL and periodic),
                                   n_particles=n_particles, particle_prefix='g' if kind == KIND_CENTROID else 'p',
                                   pair_parameters=tuple(per_term) if kind == KIND_NONBONDED else ())
+        if kind == KIND_NONBONDED and f.getUseLongRangeCorrection() and np.isin(prog['program'][:, 0], (TABLE1D, LOOKUP1D)).any():
+            # (the tail quadrature assumes a smooth integrand; a spline that ends inside the tail is not one)
+            raise NotImplementedError('%s: the long-range correction of an expression that calls a tabulated function (%s)'
+                                      % (where, ', '.join(repr(n) for n, _ in tabulated)))
         if kind == KIND_NONBONDED:
             out['%03d' % len(out)] = _nonbonded_entry(f, cls, prog, names, defaults, per_term, masses, box_vectors)
             continue

@@ -176,9 +176,70 @@ class NonbondedForce(Force):
         return self._method in (NonbondedForce.CutoffPeriodic, NonbondedForce.Ewald, NonbondedForce.PME)
 
 
+class Continuous1DFunction:
+    """openmm.Continuous1DFunction: ``values`` are samples at n uniformly spaced points over [min, max]; the function is the natural
+    cubic spline through them (second derivative zero at both ends) or, with ``periodic``, the periodic cubic spline with the argument
+    wrapped into [min, max).  Outside [min, max] a function that is not periodic has the value 0 and the derivative 0 (OpenMM's
+    reference platform); at exactly min and max the end intervals' own value and one-sided derivative apply.  At least 2 values (3
+    when periodic, the first equal to the last), at most custom_expr.MAX_TABLE_POINTS where a custom force's expression calls it."""
+
+    def __init__(self, values, min, max, periodic=False):
+        self._periodic = bool(periodic)
+        self.setFunctionParameters(values, min, max)
+
+    def setFunctionParameters(self, values, min, max):
+        values = np.array(values, dtype=np.float64).reshape(-1)
+        lo, hi = float(min), float(max)
+        least = 3 if self._periodic else 2
+        if len(values) < least:
+            raise ValueError('Continuous1DFunction: %d values (a %s function needs at least %d)'
+                             % (len(values), 'periodic' if self._periodic else 'continuous', least))
+        if not (np.isfinite(lo) and np.isfinite(hi)):
+            raise ValueError('Continuous1DFunction: the bounds min = %r, max = %r are not finite' % (lo, hi))
+        if lo >= hi:
+            raise ValueError('Continuous1DFunction: min = %r is not below max = %r' % (lo, hi))
+        if not np.isfinite(values).all():
+            raise ValueError('Continuous1DFunction: value %d is not finite' % int(np.flatnonzero(~np.isfinite(values))[0]))
+        if self._periodic and values[0] != values[-1]:
+            raise ValueError('Continuous1DFunction: a periodic function needs values[0] == values[-1] (%r and %r)' % (values[0], values[-1]))
+        self._values, self._min, self._max = values, lo, hi
+
+    def getFunctionParameters(self):
+        return self._values.tolist(), self._min, self._max
+
+    def getPeriodic(self):
+        return self._periodic
+
+    def Copy(self):
+        return Continuous1DFunction(self._values, self._min, self._max, self._periodic)
+
+
+class Discrete1DFunction:
+    """openmm.Discrete1DFunction: the value is values[round(x)], halves rounded away from zero as C's round does; the derivative is 0.
+    An index outside 0 ... n - 1 gives NaN: OpenMM throws there, the device cannot, and a NaN energy is what the sampler's NaN check
+    catches."""
+
+    def __init__(self, values):
+        self.setFunctionParameters(values)
+
+    def setFunctionParameters(self, values):
+        values = np.array(values, dtype=np.float64).reshape(-1)
+        if len(values) < 1:
+            raise ValueError('Discrete1DFunction: no values')
+        if not np.isfinite(values).all():
+            raise ValueError('Discrete1DFunction: value %d is not finite' % int(np.flatnonzero(~np.isfinite(values))[0]))
+        self._values = values
+
+    def getFunctionParameters(self):
+        return self._values.tolist()
+
+    def Copy(self):
+        return Discrete1DFunction(self._values)
+
+
 class _CustomForce(Force):
     """What OpenMM's custom forces share: the energy string, global parameters with default values, per-term parameter names, the
-    periodic-boundary flag and tabulated functions (which the engine refuses)."""
+    periodic-boundary flag and tabulated functions (Continuous1DFunction and Discrete1DFunction; the engine refuses every other kind)."""
 
     def __init__(self, energy):
         super().__init__()
@@ -235,6 +296,9 @@ class _CustomForce(Force):
 
     def getTabulatedFunctionName(self, index):
         return self._functions[index][0]
+
+    def getTabulatedFunction(self, index):
+        return self._functions[index][1]
 
 
 def _term_arrays(terms, width, n_params, what):
@@ -483,7 +547,8 @@ class CustomNonbondedForce(_CustomForce):
     """openmm.CustomNonbondedForce: the energy a function of the distance r of two particles, of their per-particle parameters (a
     parameter p appears as p1 and p2) and of global parameters, summed over every pair that no exclusion names and, with a cutoff,
     that lies inside it.  Every expression goes to csrc/custom_nonbonded.hip (one wavefront per tile of 64 x 64 particles: the cost is
-    quadratic in the particle count).  Interaction groups, tabulated functions and energy parameter derivatives are refused."""
+    quadratic in the particle count).  Interaction groups, energy parameter derivatives and the long-range correction of an expression
+    that calls a tabulated function are refused."""
     NoCutoff, CutoffNonPeriodic, CutoffPeriodic = 0, 1, 2
 
     def __init__(self, energy):
