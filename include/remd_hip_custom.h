@@ -66,8 +66,35 @@
  * instructions can name (128 one-argument calls of 4 + 2 REMD_CUSTOM_MAX_TABLE_POINTS doubles each, 2 097 664 doubles per force).
  * The long-range correction of a nonbonded force whose expression calls a table is the host's business (openmmtools_amd refuses it).
  *
- * Not provided: Continuous2DFunction, Continuous3DFunction, Discrete2DFunction, Discrete3DFunction, changing a table after
- * remd_set_custom_terms, pointangle, pointdihedral, interaction groups.
+ *
+ * Tabulated functions of two and three arguments (OpenMM's Continuous2DFunction, Discrete2DFunction, Discrete3DFunction):
+ * REMD_CX_TABLE2D and REMD_CX_LOOKUP2D take two arguments (x, y) from the stack, first deepest, REMD_CX_LOOKUP3D three (x, y, z); each
+ * pushes one result; the operand is the offset of the function's block, which lies among the blocks above:
+ *     REMD_CX_TABLE2D:  [nx, ny, xmin, xmax, ymin, ymax, periodic, 0], node[ny][nx][4]   (8 + 4 nx ny doubles; nx, ny integral >= 2;
+ *                                                                  min < max, all finite; periodic 0 or 1)
+ *     REMD_CX_LOOKUP2D: [nx, ny], values[ny][nx]                  (2 + nx ny doubles; nx, ny integral >= 1)
+ *     REMD_CX_LOOKUP3D: [nx, ny, nz, 0], values[nz][ny][nx]       (4 + nx ny nz doubles)
+ * with nx ny (nz) <= REMD_CUSTOM_MAX_TABLE_CELLS.  The first index runs fastest: values[i + nx j (+ nx ny k)], OpenMM's order.
+ * Node data of REMD_CX_TABLE2D.  The samples f(x_i, y_j) lie on uniform grids over [xmin, xmax] and [ymin, ymax] with spacings hx, hy.
+ * Let D be the linear map "samples of a row -> first derivatives at the nodes of the 1D cubic spline through them", the spline of
+ * REMD_CX_TABLE1D (natural where periodic = 0, periodic where 1; one flag for both directions): with M its second derivatives,
+ *     s'(x_i) = (y[i+1] - y[i]) / h - h (2 M[i] + M[i+1]) / 6,   at the last node (y[n-1] - y[n-2]) / h + h (M[n-2] + 2 M[n-1]) / 6.
+ * Every node carries node[j][i] = (f, fx, fy, fxy): fx = D_x f (along x for each j), fy = D_y f (along y for each i), fxy = D_y fx
+ * (= D_x fy: the maps act on different indices); the last row and column of a periodic function repeat the first.  A corner is 32
+ * contiguous bytes, the two corners of a patch row 64.  The host fits the node data in f64.
+ * Evaluation.  In patch (i, j), with u = (x - x_i) / hx computed as (x - xmin) / hx - i and w likewise (the patch index is the integer
+ * part, clamped to 0 ... n - 2), the function is the bicubic Hermite interpolant of the four corners (a, b in {0, 1}: corner
+ * (i + a, j + b)), with h00(t) = 2 t^3 - 3 t^2 + 1, h01(t) = -2 t^3 + 3 t^2, h10(t) = t^3 - 2 t^2 + t, h11(t) = t^3 - t^2:
+ *     F = sum_ab [ h0a(u) h0b(w) f_ab + hx h1a(u) h0b(w) fx_ab + hy h0a(u) h1b(w) fy_ab + hx hy h1a(u) h1b(w) fxy_ab ],
+ * dF/dx and dF/dy from the derivatives of the basis divided by hx and hy.  F is C1 across patch edges, interpolates f, reproduces
+ * a + b x + c y + d x y, and equals g(x) h(y) of the two 1D splines where the samples are g(x_i) h(y_j).
+ * Out of range, per argument by the rules of REMD_CX_TABLE1D: a function that is not periodic pushes 0 with both derivatives 0 where
+ * either argument lies outside its range; exactly min and max belong to the end patches; a periodic function wraps each argument,
+ * t = x - L floor((x - min) / L), clamped into [min, max]; a NaN argument (an infinite one of a periodic function) pushes NaN,
+ * whatever the other argument is.  The lookups push values[round(x) + nx round(y) (+ nx ny round(z))] (C's round) with derivatives 0,
+ * and NaN where any index falls outside its range.  No arguments make the device load outside the block.
+ *
+ * Not provided: Continuous3DFunction, changing a table after remd_set_custom_terms, pointangle, pointdihedral, interaction groups.
  *
  * Global parameters belong to the handle: every force's program addresses the same n_globals columns, and every state carries one
  * value per column (remd_set_custom_globals).  A term acts in every force evaluation (MD steps, energies, the barostat,
@@ -77,7 +104,8 @@
  * Limits (a descriptor beyond them is refused): REMD_CUSTOM_MAX_PROGRAM instructions per force, REMD_CUSTOM_MAX_STACK stack slots,
  * REMD_CUSTOM_MAX_PARAMS parameters per term, REMD_CUSTOM_MAX_GLOBALS global columns per handle, REMD_CUSTOM_MAX_FORCES forces
  * per handle (of all kinds together), REMD_CUSTOM_MAX_PARTICLES particles per compound bond or groups per centroid bond,
- * REMD_CUSTOM_MAX_TABLE_POINTS points per tabulated function.
+ * REMD_CUSTOM_MAX_TABLE_POINTS points per tabulated function of one argument, REMD_CUSTOM_MAX_TABLE_CELLS values per tabulated
+ * function of two or three.
  *
  * These entry points are declared here and not in remd_hip.h because the CPU port of the ABI does not provide them: a host binds
  * them only where the loaded library exports them.  Conventions as in remd_hip.h.
@@ -105,7 +133,8 @@ extern "C" {
 #define REMD_CUSTOM_MAX_GLOBALS 16
 #define REMD_CUSTOM_MAX_FORCES  8
 #define REMD_CUSTOM_MAX_PARTICLES 8
-#define REMD_CUSTOM_MAX_TABLE_POINTS 8192   /* points of one tabulated function                                               */
+#define REMD_CUSTOM_MAX_TABLE_POINTS 8192   /* points of one tabulated function of one argument                               */
+#define REMD_CUSTOM_MAX_TABLE_CELLS 65536   /* nx ny (nz) of one tabulated function of two or three arguments                  */
 
 /* opcodes */
 #define REMD_CX_CONST   0      /* push consts[operand]                                                                      */
@@ -148,7 +177,10 @@ extern "C" {
 #define REMD_CX_DIHEDRAL 37     /* dihedral of four particle slots, 4 bits each                                              */
 #define REMD_CX_TABLE1D  38     /* the cubic spline of the block at consts[operand] at the argument on the stack               */
 #define REMD_CX_LOOKUP1D 39     /* values[round(argument)] of the block at consts[operand]; NaN outside 0 ... n - 1           */
-#define REMD_CX_N_OPCODES 40
+#define REMD_CX_TABLE2D  40     /* the bicubic patch of the block at consts[operand] at the two arguments on the stack          */
+#define REMD_CX_LOOKUP2D 41     /* values[round(x) + nx round(y)] of the block at consts[operand]; NaN outside the ranges        */
+#define REMD_CX_LOOKUP3D 42     /* values[round(x) + nx round(y) + nx ny round(z)], three arguments; NaN outside the ranges      */
+#define REMD_CX_N_OPCODES 43
 
 typedef struct remd_custom_force_desc {
     int32_t kind;                  /* REMD_CUSTOM_*                                                                        */

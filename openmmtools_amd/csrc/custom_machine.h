@@ -8,7 +8,8 @@
 // gradient with respect to ONE particle, `seed`: the coordinates of that particle carry the unit partials, every other coordinate
 // carries zero, and an opcode of particles pushes its value with its gradient with respect to particle `seed` (zero where `seed` is
 // not among its arguments; formulas and guards of cst_geometry in custom_terms.hip).  seed = -1: values only.
-// Both instantiations know the tabulated functions, REMD_CX_TABLE1D / REMD_CX_LOOKUP1D (cst_table1d, cst_lookup1d below).
+// Both instantiations know the tabulated functions, REMD_CX_TABLE1D / REMD_CX_LOOKUP1D (cst_table1d, cst_lookup1d below) and
+// REMD_CX_TABLE2D / REMD_CX_LOOKUP2D / REMD_CX_LOOKUP3D (cst_table2d, cst_lookup2d, cst_lookup3d).
 #pragma once
 #include "remd_internal.h"
 #include "../../include/remd_hip_custom.h"
@@ -174,6 +175,84 @@ __device__ __forceinline__ double cst_lookup1d(const double* __restrict__ B, dou
     return v;
 }
 
+// One argument of REMD_CX_TABLE2D on its axis of n nodes over [lo, hi] with spacing h, by the rules of cst_table1d: the wrap of a
+// periodic function, the range test in f64, then the patch index (clamped again) and the offset u = (t - min) / h - i in the patch.
+// Returns whether the argument lies inside; `nan` whether it is a NaN (an infinite argument of a periodic function wraps to one).
+__device__ __forceinline__ bool cst_table_axis(int n, double lo, double hi, double h, bool periodic, double x, int& i, double& u, bool& nan)
+{
+    const double L = hi - lo;
+    const double w = x - L * floor((x - lo) / L);
+    const double t = periodic ? (w < lo ? lo : w > hi ? hi : w) : x;
+    const bool inside = t >= lo && t <= hi;
+    const double s = inside ? (t - lo) / h : 0.0;
+    i = min(max((int)s, 0), n - 2);
+    u = s - (double)i;
+    nan = t != t;
+    return inside;
+}
+
+// REMD_CX_TABLE2D (include/remd_hip_custom.h): the bicubic Hermite patch of the block [nx, ny, xmin, xmax, ymin, ymax, periodic, 0],
+// node[ny][nx][4] = (f, fx, fy, fxy), with its two partials kx = dF/dx, ky = dF/dy.  The sixteen terms are summed row by row: the two
+// corners (j + b, i) and (j + b, i + 1) of a row are 64 contiguous bytes, one access of the memory system's granularity, and only
+// their eight numbers are live beside the row's four sums -- sixteen loads in flight at once would not fit beside the stack machine's
+// state in the nonbonded tile kernel.  Along x a row gives P = sum_a h0a(u) f_a + hx h1a(u) fx_a and Q, the same of (fy, fxy), with
+// their u-derivatives; along y, F = sum_b h0b(w) P_b + hy h1b(w) Q_b.  A lane whose arguments are not both inside loads nothing and
+// pushes 0, or NaN where either argument is a NaN (the discipline of cst_table1d, per argument).
+__device__ __forceinline__ void cst_table2d(const double* __restrict__ B, double x, double y, double& v, double& kx, double& ky)
+{
+    const int nx = (int)B[0], ny = (int)B[1];                 // 2 ..., nx ny <= REMD_CUSTOM_MAX_TABLE_CELLS
+    const double hx = (B[3] - B[2]) / (double)(nx - 1), hy = (B[5] - B[4]) / (double)(ny - 1);
+    const bool periodic = B[6] != 0.0;
+    int i, j; double u, w; bool nanx, nany;
+    const bool inx = cst_table_axis(nx, B[2], B[3], hx, periodic, x, i, u, nanx);
+    const bool iny = cst_table_axis(ny, B[4], B[5], hy, periodic, y, j, w, nany);
+    v = nanx || nany ? __builtin_nan("") : 0.0; kx = 0.0; ky = 0.0;
+    if (inx && iny) {
+        const double u2 = u * u, u3 = u2 * u, w2 = w * w, w3 = w2 * w;
+        // h00, h01, hx h10, hx h11 at u and their u-derivatives (the latter still to be divided by hx)
+        const double a0 = 2.0 * u3 - 3.0 * u2 + 1.0, a1 = 3.0 * u2 - 2.0 * u3, a2 = hx * (u3 - 2.0 * u2 + u), a3 = hx * (u3 - u2);
+        const double d0 = 6.0 * (u2 - u), d2 = hx * (3.0 * u2 - 4.0 * u + 1.0), d3 = hx * (3.0 * u2 - 2.0 * u);      // d1 = -d0
+        double F = 0.0, Fu = 0.0, Fw = 0.0;
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const double* __restrict__ c = B + 8 + 4 * ((j + b) * nx + i);        // (f, fx, fy, fxy) of corner i, then of corner i + 1
+            const double P = a0 * c[0] + a1 * c[4] + a2 * c[1] + a3 * c[5], Q = a0 * c[2] + a1 * c[6] + a2 * c[3] + a3 * c[7];
+            const double dP = d0 * (c[0] - c[4]) + d2 * c[1] + d3 * c[5], dQ = d0 * (c[2] - c[6]) + d2 * c[3] + d3 * c[7];
+            const double e0 = b ? 3.0 * w2 - 2.0 * w3 : 2.0 * w3 - 3.0 * w2 + 1.0, e1 = hy * (b ? w3 - w2 : w3 - 2.0 * w2 + w);
+            const double g0 = b ? -6.0 * (w2 - w) : 6.0 * (w2 - w), g1 = hy * (b ? 3.0 * w2 - 2.0 * w : 3.0 * w2 - 4.0 * w + 1.0);
+            F += e0 * P + e1 * Q;
+            Fu += e0 * dP + e1 * dQ;
+            Fw += g0 * P + g1 * Q;
+        }
+        v = F; kx = Fu / hx; ky = Fw / hy;
+    }
+}
+
+// values[round(x) + nx round(y)] of the block [nx, ny], values[ny][nx]; NaN, and no load, where an index falls outside its range
+__device__ __forceinline__ double cst_lookup2d(const double* __restrict__ B, double x, double y)
+{
+    const double rx = round(x), ry = round(y);
+    const int nx = (int)B[0], ny = (int)B[1];                // >= 1, nx ny <= REMD_CUSTOM_MAX_TABLE_CELLS
+    const bool inside = rx >= 0.0 && rx <= (double)(nx - 1) && ry >= 0.0 && ry <= (double)(ny - 1);
+    const int i = inside ? min(max((int)rx, 0), nx - 1) : 0, j = inside ? min(max((int)ry, 0), ny - 1) : 0;
+    double v = __builtin_nan("");
+    if (inside) v = B[2 + j * nx + i];
+    return v;
+}
+
+// values[round(x) + nx round(y) + nx ny round(z)] of the block [nx, ny, nz, 0], values[nz][ny][nx]
+__device__ __forceinline__ double cst_lookup3d(const double* __restrict__ B, double x, double y, double z)
+{
+    const double rx = round(x), ry = round(y), rz = round(z);
+    const int nx = (int)B[0], ny = (int)B[1], nz = (int)B[2];
+    const bool inside = rx >= 0.0 && rx <= (double)(nx - 1) && ry >= 0.0 && ry <= (double)(ny - 1) && rz >= 0.0 && rz <= (double)(nz - 1);
+    const int i = inside ? min(max((int)rx, 0), nx - 1) : 0, j = inside ? min(max((int)ry, 0), ny - 1) : 0;
+    const int k = inside ? min(max((int)rz, 0), nz - 1) : 0;
+    double v = __builtin_nan("");
+    if (inside) v = B[4 + (k * ny + j) * nx + i];
+    return v;
+}
+
 // the program of force f at term t (lane's own) under the globals g (wave-uniform); the result's partials are dE/dvariable
 // (GEOM: dE/d(x, y, z) of particle `seed`; x0, x1, x2 are not read)
 template <bool GEOM>
@@ -200,7 +279,7 @@ __device__ __forceinline__ cx cst_eval(const cst_force& f, const int2* __restric
         case REMD_CX_PARAM:  cx_st(S, sp++, lane, cx{par[f.par0 + (size_t)arg * f.npad + t], 0.0, 0.0, 0.0}); break;
         case REMD_CX_GLOBAL: cx_st(S, sp++, lane, cx{g[arg], 0.0, 0.0, 0.0}); break;
         case REMD_CX_ADD: case REMD_CX_SUB: case REMD_CX_MUL: case REMD_CX_DIV: case REMD_CX_POW: case REMD_CX_ATAN2:
-        case REMD_CX_MIN: case REMD_CX_MAX: {
+        case REMD_CX_MIN: case REMD_CX_MAX: case REMD_CX_TABLE2D: case REMD_CX_LOOKUP2D: {
             const cx x = cx_ld(S, sp - 2, lane), y = cx_ld(S, sp - 1, lane);
             cx z;
             if (op == REMD_CX_ADD) z = cx{x.v + y.v, x.a + y.a, x.b + y.b, x.c + y.c};
@@ -219,7 +298,12 @@ __device__ __forceinline__ cx cst_eval(const cst_force& f, const int2* __restric
             } else if (op == REMD_CX_ATAN2) {
                 const double n2 = 1.0 / (x.v * x.v + y.v * y.v);          // atan2(x, y): x the sine-like argument
                 z = cx{atan2(x.v, y.v), (y.v * x.a - x.v * y.a) * n2, (y.v * x.b - x.v * y.b) * n2, (y.v * x.c - x.v * y.c) * n2};
-            } else if (op == REMD_CX_MIN) z = x.v < y.v ? x : y;
+            } else if (op == REMD_CX_TABLE2D) {
+                double v, kx, ky;
+                cst_table2d(consts + f.const0 + arg, x.v, y.v, v, kx, ky);
+                z = cx{v, kx * x.a + ky * y.a, kx * x.b + ky * y.b, kx * x.c + ky * y.c};
+            } else if (op == REMD_CX_LOOKUP2D) z = cx{cst_lookup2d(consts + f.const0 + arg, x.v, y.v), 0.0, 0.0, 0.0};
+            else if (op == REMD_CX_MIN) z = x.v < y.v ? x : y;
             else z = x.v > y.v ? x : y;
             cx_st(S, sp - 2, lane, z); --sp;
         } break;
@@ -227,6 +311,10 @@ __device__ __forceinline__ cx cst_eval(const cst_force& f, const int2* __restric
             const cx x = cx_ld(S, sp - 3, lane), y = cx_ld(S, sp - 2, lane), z = cx_ld(S, sp - 1, lane);
             cx_st(S, sp - 3, lane, x.v != 0.0 ? y : z); sp -= 2;
         } break;
+        case REMD_CX_LOOKUP3D:                            // the arguments' values only: the result's partials are zero
+            cx_st(S, sp - 3, lane, cx{cst_lookup3d(consts + f.const0 + arg, S[sp - 3][0][lane], S[sp - 2][0][lane], S[sp - 1][0][lane]), 0.0, 0.0, 0.0});
+            sp -= 2;
+            break;
         case REMD_CX_PERIODICDISTANCE: {
             const cx x1 = cx_ld(S, sp - 6, lane), y1 = cx_ld(S, sp - 5, lane), z1 = cx_ld(S, sp - 4, lane);
             const cx x2 = cx_ld(S, sp - 3, lane), y2 = cx_ld(S, sp - 2, lane), z2 = cx_ld(S, sp - 1, lane);

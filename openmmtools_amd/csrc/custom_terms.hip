@@ -264,6 +264,31 @@ const char* check_program(const remd_custom_force_desc& d, int n_vars)
                 if (periodic != 0.0 && periodic != 1.0) return "a table whose periodic flag is neither 0 nor 1";
             }
         } break;
+        case REMD_CX_TABLE2D: case REMD_CX_LOOKUP2D: case REMD_CX_LOOKUP3D: {
+            // the same for the blocks of two and three arguments: the sizes, their product, the bounds and the extent
+            const bool patch = op == REMD_CX_TABLE2D;
+            const int dims = op == REMD_CX_LOOKUP3D ? 3 : 2, header = patch ? 8 : dims == 3 ? 4 : 2;
+            if (arg < 0 || arg >= d.n_consts || !d.consts) return "a table offset out of range";
+            if ((long long)arg + header > (long long)d.n_consts) return "a table that runs past n_consts";
+            double cells = 1.0;
+            for (int k = 0; k < dims; ++k) {
+                const double n = d.consts[arg + k];
+                if (!(n >= (patch ? 2.0 : 1.0) && n <= (double)REMD_CUSTOM_MAX_TABLE_CELLS) || n != floor(n))
+                    return patch ? "a 2D table whose size is not an integer 2 ... REMD_CUSTOM_MAX_TABLE_CELLS"
+                                 : "a lookup table whose size is not an integer 1 ... REMD_CUSTOM_MAX_TABLE_CELLS";
+                cells *= n;
+            }
+            if (cells > (double)REMD_CUSTOM_MAX_TABLE_CELLS) return "a table of more than REMD_CUSTOM_MAX_TABLE_CELLS cells";
+            if ((long long)arg + header + (patch ? 4 : 1) * (long long)cells > (long long)d.n_consts) return "a table that runs past n_consts";
+            if (patch) {
+                for (int k = 0; k < 2; ++k) {
+                    const double lo = d.consts[arg + 2 + 2 * k], hi = d.consts[arg + 3 + 2 * k];
+                    if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi)) return "a table whose bounds are not finite with min < max";
+                }
+                if (d.consts[arg + 6] != 0.0 && d.consts[arg + 6] != 1.0) return "a table whose periodic flag is neither 0 nor 1";
+            }
+            pops = dims;
+        } break;
         default: if (op < 0 || op >= REMD_CX_N_OPCODES) return "an unknown opcode"; break;
         }
         if (sp < pops) return "a program that pops an empty stack";

@@ -25,7 +25,9 @@ base); every other power is REMD_CX_POW.
 Tabulated functions: a call of a force's system.Continuous1DFunction (natural or periodic cubic spline) compiles to TABLE1D, of a
 system.Discrete1DFunction to LOOKUP1D; the function's samples, and the spline's second derivatives solved here in f64
 (spline_second_derivatives), travel as a block of the force's constants behind the scalars, the operand its offset (layout and
-out-of-range rules: include/remd_hip_custom.h).  At most MAX_TABLE_POINTS points per function.
+out-of-range rules: include/remd_hip_custom.h).  At most MAX_TABLE_POINTS points per function.  A system.Continuous2DFunction
+compiles to TABLE2D (two arguments; the block carries f, fx, fy, fxy at every node, fitted here in f64: table2d_nodes), a
+system.Discrete2DFunction to LOOKUP2D and a system.Discrete3DFunction to LOOKUP3D (three arguments); at most MAX_TABLE_CELLS values.
 
 The limits are the engine's (include/remd_hip_custom.h); what is over them, an unknown name, an unknown function or a tabulated
 function of another kind is refused with NotImplementedError naming the force and the item.
@@ -38,7 +40,8 @@ MAX_PROGRAM, MAX_STACK, MAX_PARAMS, MAX_GLOBALS, MAX_FORCES = 256, 16, 16, 16, 8
 MAX_INTEGER_POWER = 64
 MAX_PARTICLES = 8                               # particles per bond of a compound-bond force
 MAX_PAIR_PARAMS = MAX_PARAMS // 2               # per-particle parameters of a nonbonded force (each appears twice in a pair's program)
-MAX_TABLE_POINTS = 8192                         # points of one tabulated function
+MAX_TABLE_POINTS = 8192                         # points of one tabulated function of one argument
+MAX_TABLE_CELLS = 65536                         # values (the product of the sizes) of one tabulated function of two or three arguments
 
 KIND_BOND, KIND_ANGLE, KIND_TORSION, KIND_EXTERNAL, KIND_COMPOUND, KIND_CENTROID, KIND_NONBONDED = 0, 1, 2, 3, 4, 5, 6
 KIND_OF_CLASS = {'CustomNonbondedForce': KIND_NONBONDED, 'CustomBondForce': KIND_BOND, 'CustomAngleForce': KIND_ANGLE, 'CustomTorsionForce': KIND_TORSION,
@@ -54,7 +57,7 @@ def compound_variables(n_particles):
 # opcodes (include/remd_hip_custom.h)
 (CONST, VAR, PARAM, GLOBAL, ADD, SUB, MUL, DIV, NEG, POWI, POW, SQRT, EXP, LOG, SIN, COS, TAN, ASIN, ACOS, ATAN, ATAN2, SINH, COSH,
  TANH, ERF, ERFC, ABS, MIN, MAX, STEP, DELTA, SELECT, FLOOR, CEIL, PERIODICDISTANCE, DISTANCE, ANGLE, DIHEDRAL, TABLE1D,
- LOOKUP1D) = range(40)
+ LOOKUP1D, TABLE2D, LOOKUP2D, LOOKUP3D) = range(43)
 
 # name -> (opcode, number of arguments)
 FUNCTIONS = dict(sqrt=(SQRT, 1), exp=(EXP, 1), log=(LOG, 1), sin=(SIN, 1), cos=(COS, 1), tan=(TAN, 1), asin=(ASIN, 1), acos=(ACOS, 1),
@@ -64,7 +67,7 @@ FUNCTIONS = dict(sqrt=(SQRT, 1), exp=(EXP, 1), log=(LOG, 1), sin=(SIN, 1), cos=(
 _BINARY = {'+': ADD, '-': SUB, '*': MUL, '/': DIV}
 # slots an opcode takes from the stack (it pushes one)
 POPS = {CONST: 0, VAR: 0, PARAM: 0, GLOBAL: 0, ADD: 2, SUB: 2, MUL: 2, DIV: 2, POW: 2, ATAN2: 2, MIN: 2, MAX: 2, SELECT: 3,
-        PERIODICDISTANCE: 6, DISTANCE: 0, ANGLE: 0, DIHEDRAL: 0}
+        PERIODICDISTANCE: 6, DISTANCE: 0, ANGLE: 0, DIHEDRAL: 0, TABLE2D: 2, LOOKUP2D: 2, LOOKUP3D: 3}
 # the functions of particles of a compound-bond force: name -> (opcode, number of particles)
 PARTICLE_FUNCTIONS = dict(distance=(DISTANCE, 2), angle=(ANGLE, 3), dihedral=(DIHEDRAL, 4))
 # the names of a bond's particles: p1 ... of a compound-bond force, g1 ... of a centroid-bond force (prefix -> pattern, noun)
@@ -242,10 +245,49 @@ def spline_second_derivatives(values, lo, hi, periodic=False):
     return out
 
 
+def spline_node_derivatives(values, lo, hi, periodic=False):
+    """s'(x_i) [..., n] of the cubic splines (natural or periodic) through the rows ``values[..., :]`` at n uniformly spaced points over
+    [lo, hi]: (y[i+1] - y[i]) / h - h (2 M[i] + M[i+1]) / 6, at the last node (y[n-1] - y[n-2]) / h + h (M[n-2] + 2 M[n-1]) / 6, M the
+    second derivatives of spline_second_derivatives; the last node of a periodic spline repeats the first"""
+    y = np.asarray(values, dtype=np.float64)
+    n = y.shape[-1]
+    h = (float(hi) - float(lo)) / (n - 1)
+    flat = y.reshape(-1, n)
+    M = np.array([spline_second_derivatives(row, lo, hi, periodic) for row in flat])
+    d = np.empty_like(flat)
+    d[:, :-1] = (flat[:, 1:] - flat[:, :-1]) / h - h * (2.0 * M[:, :-1] + M[:, 1:]) / 6.0
+    d[:, -1] = d[:, 0] if periodic else (flat[:, -1] - flat[:, -2]) / h + h * (M[:, -2] + 2.0 * M[:, -1]) / 6.0
+    return d.reshape(y.shape)
+
+
+def table2d_nodes(nx, ny, values, xmin, xmax, ymin, ymax, periodic=False):
+    """node [ny][nx][4] = (f, fx, fy, fxy) of a Continuous2DFunction (include/remd_hip_custom.h): fx the node derivatives of the 1D
+    splines along x for every j, fy those along y for every i, fxy those of fx along y"""
+    f = np.asarray(values, dtype=np.float64).reshape(ny, nx)
+    fx = spline_node_derivatives(f, xmin, xmax, periodic)
+    fy = spline_node_derivatives(f.T, ymin, ymax, periodic).T
+    fxy = spline_node_derivatives(fx.T, ymin, ymax, periodic).T
+    return np.stack([f, fx, fy, fxy], axis=-1)
+
+
 def _table_block(name, function, where):
     """(opcode, the function's block of the constant table): [n, min, max, periodic], y [n], y'' [n] of a Continuous1DFunction,
-    [n], values [n] of a Discrete1DFunction (include/remd_hip_custom.h)"""
+    [n], values [n] of a Discrete1DFunction, [nx, ny, xmin, xmax, ymin, ymax, periodic, 0], node [ny][nx][4] of a Continuous2DFunction,
+    [nx, ny], values [ny][nx] of a Discrete2DFunction, [nx, ny, nz, 0], values [nz][ny][nx] of a Discrete3DFunction
+    (include/remd_hip_custom.h)"""
     from . import system as _system
+    if isinstance(function, (_system.Continuous2DFunction, _system.Discrete2DFunction, _system.Discrete3DFunction)):
+        parameters = function.getFunctionParameters()
+        dims = 3 if isinstance(function, _system.Discrete3DFunction) else 2
+        sizes = parameters[:dims]
+        if int(np.prod(sizes)) > MAX_TABLE_CELLS:
+            raise NotImplementedError('%s: tabulated function %r has %d values (%s; the engine takes %d)'
+                                      % (where, name, int(np.prod(sizes)), ' x '.join(str(n) for n in sizes), MAX_TABLE_CELLS))
+        if isinstance(function, _system.Continuous2DFunction):
+            periodic = bool(function.getPeriodic())
+            nodes = table2d_nodes(*parameters, periodic=periodic)
+            return TABLE2D, np.concatenate([[sizes[0], sizes[1]], parameters[3:], [float(periodic), 0.0], nodes.reshape(-1)])
+        return (LOOKUP3D if dims == 3 else LOOKUP2D), np.concatenate([list(sizes) + [0.0] * (dims == 3), parameters[dims]])
     if isinstance(function, _system.Continuous1DFunction):
         values, lo, hi = function.getFunctionParameters()
         periodic = bool(function.getPeriodic())
@@ -257,7 +299,8 @@ def _table_block(name, function, where):
         if len(values) > MAX_TABLE_POINTS:
             raise NotImplementedError('%s: tabulated function %r has %d points (the engine takes %d)' % (where, name, len(values), MAX_TABLE_POINTS))
         return LOOKUP1D, np.concatenate([[len(values)], values])
-    raise NotImplementedError('%s: tabulated function %r (a %s: only Continuous1DFunction and Discrete1DFunction are supported)'
+    raise NotImplementedError('%s: tabulated function %r (a %s: only Continuous1DFunction, Discrete1DFunction, Continuous2DFunction, '
+                              'Discrete2DFunction and Discrete3DFunction are supported)'
                               % (where, name, type(function).__name__))
 
 
@@ -267,7 +310,8 @@ def compile_expression(energy, variables, parameters, global_columns, where='exp
 
     variables: the force's own variable names in operand order; parameters: the per-term parameter names in order; global_columns:
     {global parameter name: column of the handle's table}; tabulated: the force's (name, function) pairs: a call of a
-    system.Continuous1DFunction compiles to TABLE1D, of a system.Discrete1DFunction to LOOKUP1D, the operand the offset of the
+    system.Continuous1DFunction compiles to TABLE1D, of a system.Discrete1DFunction to LOOKUP1D (of the 2D and 3D classes to TABLE2D,
+    LOOKUP2D, LOOKUP3D, with two and three arguments), the operand the offset of the
     function's block in the constants (behind the scalar constants, one block per function called); periodic_distance:
     whether periodicdistance(...) is allowed (an external force that uses periodic boundary conditions); n_particles: the particles
     per bond of a compound-bond force (0: another force), which opens distance / angle / dihedral over p1 ... pP and pointdistance;
@@ -356,9 +400,12 @@ def compile_expression(energy, variables, parameters, global_columns, where='exp
             if name in functions:
                 if name not in blocks:
                     blocks[name] = _table_block(name, functions[name], where)
-                if len(args) != 1:
-                    raise NotImplementedError('%s: tabulated function %r takes 1 argument, not %d' % (where, name, len(args)))
-                walk(args[0], active)
+                n_args = POPS.get(blocks[name][0], 1)
+                if len(args) != n_args:
+                    raise NotImplementedError('%s: tabulated function %r takes %d argument%s, not %d'
+                                              % (where, name, n_args, 's' if n_args > 1 else '', len(args)))
+                for a in args:
+                    walk(a, active)
                 table_calls.append((len(program), name))
                 return emit(blocks[name][0])
             if n_particles and name in PARTICLE_FUNCTIONS:
@@ -495,6 +542,66 @@ def lookup_values(consts, offset, x):
     return np.where(inside, v, np.nan)
 
 
+def _round_half_away(x):
+    whole = np.trunc(x)
+    return whole + np.where(np.abs(x - whole) >= 0.5, np.sign(x), 0.0)
+
+
+def _axis(n, lo, hi, periodic, x):
+    """(inside, patch index, offset in the patch, is NaN) of one argument of TABLE2D, the device's cst_table_axis"""
+    h = (hi - lo) / (n - 1)
+    t = np.clip(x - (hi - lo) * np.floor((x - lo) / (hi - lo)), lo, hi) if periodic else x
+    inside = (t >= lo) & (t <= hi)
+    s = (np.where(inside, t, lo) - lo) / h
+    i = np.clip(s.astype(np.int64), 0, n - 2)
+    return inside, i, s - i, np.isnan(t)
+
+
+def table2d_values(consts, offset, x, y):
+    """TABLE2D at every element of x, y: the sixteen-term bicubic Hermite sum over the patch's corners (include/remd_hip_custom.h); 0
+    where either argument of a function that is not periodic lies outside its range, NaN for a NaN argument"""
+    consts = np.asarray(consts, dtype=np.float64)
+    x, y = np.broadcast_arrays(np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64))
+    nx, ny = int(consts[offset]), int(consts[offset + 1])
+    xmin, xmax, ymin, ymax = consts[offset + 2:offset + 6]
+    periodic = consts[offset + 6] != 0.0
+    node = consts[offset + 8:offset + 8 + 4 * nx * ny].reshape(ny, nx, 4)
+    hx, hy = (xmax - xmin) / (nx - 1), (ymax - ymin) / (ny - 1)
+    with np.errstate(all='ignore'):
+        inx, i, u, nanx = _axis(nx, xmin, xmax, periodic, x)
+        iny, j, w, nany = _axis(ny, ymin, ymax, periodic, y)
+
+        def basis(t):                           # [h0a][a], [h1a][a]
+            return ((2.0 * t ** 3 - 3.0 * t ** 2 + 1.0, 3.0 * t ** 2 - 2.0 * t ** 3), (t ** 3 - 2.0 * t ** 2 + t, t ** 3 - t ** 2))
+        bu, bw = basis(u), basis(w)
+        v = np.zeros(x.shape)
+        for a in (0, 1):
+            for b in (0, 1):
+                c = node[j + b, i + a]
+                v = v + (bu[0][a] * bw[0][b] * c[..., 0] + hx * bu[1][a] * bw[0][b] * c[..., 1] + hy * bu[0][a] * bw[1][b] * c[..., 2]
+                         + hx * hy * bu[1][a] * bw[1][b] * c[..., 3])
+    return np.where(nanx | nany, np.nan, np.where(inx & iny, v, 0.0))
+
+
+def lookup_grid_values(consts, offset, *args):
+    """LOOKUP2D (two arguments) / LOOKUP3D (three) at every element: values[round(x) + nx round(y) (+ nx ny round(z))], halves away
+    from zero; NaN where an index is outside its range"""
+    consts = np.asarray(consts, dtype=np.float64)
+    dims = len(args)
+    args = np.broadcast_arrays(*[np.asarray(a, dtype=np.float64) for a in args])
+    sizes = [int(consts[offset + k]) for k in range(dims)]
+    with np.errstate(all='ignore'):
+        inside, flat, stride = np.ones(args[0].shape, dtype=bool), np.zeros(args[0].shape, dtype=np.int64), 1
+        for n, a in zip(sizes, args):
+            k = _round_half_away(a)
+            ok = (k >= 0.0) & (k <= n - 1.0)
+            inside &= ok
+            flat = flat + stride * np.where(ok, k, 0.0).astype(np.int64)
+            stride *= n
+        v = consts[offset + (4 if dims == 3 else 2) + flat]
+    return np.where(inside, v, np.nan)
+
+
 def run_values(prog, r, params, global_values):
     """The value of a compiled one-variable program at every element of the array ``r`` (f64): the Python interpreter of the machine,
     values only (no partials), numpy-vectorised over r.  params: the PARAM operands' values; global_values: the GLOBAL columns'."""
@@ -538,6 +645,15 @@ def run_values(prog, r, params, global_values):
                 stack.append(table_values(prog['consts'], arg, stack.pop()))
             elif op == LOOKUP1D:
                 stack.append(lookup_values(prog['consts'], arg, stack.pop()))
+            elif op == TABLE2D:
+                y, x = stack.pop(), stack.pop()
+                stack.append(table2d_values(prog['consts'], arg, x, y))
+            elif op == LOOKUP2D:
+                y, x = stack.pop(), stack.pop()
+                stack.append(lookup_grid_values(prog['consts'], arg, x, y))
+            elif op == LOOKUP3D:
+                z, y, x = stack.pop(), stack.pop(), stack.pop()
+                stack.append(lookup_grid_values(prog['consts'], arg, x, y, z))
             else:
                 raise NotImplementedError('run_values: opcode %d' % op)
     assert len(stack) == 1
@@ -698,7 +814,7 @@ def custom_terms_desc(forces, masses=None, box_vectors=None):
                                   where=where, tabulated=tabulated, periodic_distance=(kind == KIND_EXTERNAL and periodic),
                                   n_particles=n_particles, particle_prefix='g' if kind == KIND_CENTROID else 'p',
                                   pair_parameters=tuple(per_term) if kind == KIND_NONBONDED else ())
-        if kind == KIND_NONBONDED and f.getUseLongRangeCorrection() and np.isin(prog['program'][:, 0], (TABLE1D, LOOKUP1D)).any():
+        if kind == KIND_NONBONDED and f.getUseLongRangeCorrection() and np.isin(prog['program'][:, 0], (TABLE1D, LOOKUP1D, TABLE2D, LOOKUP2D, LOOKUP3D)).any():
             # (the tail quadrature assumes a smooth integrand; a spline that ends inside the tail is not one)
             raise NotImplementedError('%s: the long-range correction of an expression that calls a tabulated function (%s)'
                                       % (where, ', '.join(repr(n) for n, _ in tabulated)))

@@ -237,9 +237,93 @@ class Discrete1DFunction:
         return Discrete1DFunction(self._values)
 
 
+def _grid_values(cls, sizes, values, least):
+    """the flat values of a function on a grid of ``sizes`` (first index fastest), checked as the 1D classes check theirs"""
+    sizes = tuple(int(n) for n in sizes)
+    values = np.array(values, dtype=np.float64).reshape(-1)
+    for axis, n in zip('xyz', sizes):
+        if n < least:
+            raise ValueError('%s: %ssize = %d (at least %d)' % (cls, axis, n, least))
+    if len(values) != int(np.prod(sizes)):
+        raise ValueError('%s: %d values for a grid of %s (%d)' % (cls, len(values), ' x '.join(str(n) for n in sizes), int(np.prod(sizes))))
+    if not np.isfinite(values).all():
+        raise ValueError('%s: value %d is not finite' % (cls, int(np.flatnonzero(~np.isfinite(values))[0])))
+    return sizes, values
+
+
+class Continuous2DFunction:
+    """openmm.Continuous2DFunction: ``values[i + xsize*j]`` are samples f(x_i, y_j) on uniform grids of xsize points over [xmin, xmax]
+    and ysize points over [ymin, ymax]; the function is the bicubic Hermite interpolant whose node derivatives are those of the 1D
+    cubic splines through the rows and columns (natural, or with ``periodic`` periodic in both directions with both arguments
+    wrapped; definition: include/remd_hip_custom.h).  Outside either range a function that is not periodic has the value 0 and both
+    derivatives 0.  Both sizes at least 2; a periodic function needs its last row and column equal to the first; at most
+    custom_expr.MAX_TABLE_CELLS values where a custom force's expression calls it.  (Continuous3DFunction does not exist here: the
+    custom forces refuse it by name, like any foreign object.)"""
+
+    def __init__(self, xsize, ysize, values, xmin, xmax, ymin, ymax, periodic=False):
+        self._periodic = bool(periodic)
+        self.setFunctionParameters(xsize, ysize, values, xmin, xmax, ymin, ymax)
+
+    def setFunctionParameters(self, xsize, ysize, values, xmin, xmax, ymin, ymax):
+        (nx, ny), values = _grid_values('Continuous2DFunction', (xsize, ysize), values, 2)
+        bounds = tuple(float(v) for v in (xmin, xmax, ymin, ymax))
+        for axis, lo, hi in (('x', bounds[0], bounds[1]), ('y', bounds[2], bounds[3])):
+            if not (np.isfinite(lo) and np.isfinite(hi)):
+                raise ValueError('Continuous2DFunction: the bounds %smin = %r, %smax = %r are not finite' % (axis, lo, axis, hi))
+            if lo >= hi:
+                raise ValueError('Continuous2DFunction: %smin = %r is not below %smax = %r' % (axis, lo, axis, hi))
+        grid = values.reshape(ny, nx)
+        if self._periodic and not (np.array_equal(grid[0], grid[-1]) and np.array_equal(grid[:, 0], grid[:, -1])):
+            raise ValueError('Continuous2DFunction: a periodic function needs its last row and column equal to the first')
+        self._nx, self._ny, self._values, self._bounds = nx, ny, values, bounds
+
+    def getFunctionParameters(self):
+        return (self._nx, self._ny, self._values.tolist()) + self._bounds
+
+    def getPeriodic(self):
+        return self._periodic
+
+    def Copy(self):
+        return Continuous2DFunction(self._nx, self._ny, self._values, *self._bounds, periodic=self._periodic)
+
+
+class Discrete2DFunction:
+    """openmm.Discrete2DFunction: the value is values[round(x) + xsize*round(y)], halves rounded away from zero; the derivatives are
+    0.  An index outside its range gives NaN (see Discrete1DFunction)."""
+
+    def __init__(self, xsize, ysize, values):
+        self.setFunctionParameters(xsize, ysize, values)
+
+    def setFunctionParameters(self, xsize, ysize, values):
+        (self._nx, self._ny), self._values = _grid_values('Discrete2DFunction', (xsize, ysize), values, 1)
+
+    def getFunctionParameters(self):
+        return self._nx, self._ny, self._values.tolist()
+
+    def Copy(self):
+        return Discrete2DFunction(self._nx, self._ny, self._values)
+
+
+class Discrete3DFunction:
+    """openmm.Discrete3DFunction: values[round(x) + xsize*round(y) + xsize*ysize*round(z)]; otherwise as Discrete2DFunction."""
+
+    def __init__(self, xsize, ysize, zsize, values):
+        self.setFunctionParameters(xsize, ysize, zsize, values)
+
+    def setFunctionParameters(self, xsize, ysize, zsize, values):
+        (self._nx, self._ny, self._nz), self._values = _grid_values('Discrete3DFunction', (xsize, ysize, zsize), values, 1)
+
+    def getFunctionParameters(self):
+        return self._nx, self._ny, self._nz, self._values.tolist()
+
+    def Copy(self):
+        return Discrete3DFunction(self._nx, self._ny, self._nz, self._values)
+
+
 class _CustomForce(Force):
     """What OpenMM's custom forces share: the energy string, global parameters with default values, per-term parameter names, the
-    periodic-boundary flag and tabulated functions (Continuous1DFunction and Discrete1DFunction; the engine refuses every other kind)."""
+    periodic-boundary flag and tabulated functions (Continuous1DFunction, Discrete1DFunction, Continuous2DFunction, Discrete2DFunction
+    and Discrete3DFunction; the engine refuses every other kind, Continuous3DFunction among them)."""
 
     def __init__(self, energy):
         super().__init__()
