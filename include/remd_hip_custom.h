@@ -1,6 +1,6 @@
 /*
  * remd_hip_custom.h — GPU-only extension of the C ABI in remd_hip.h: custom bond, angle, torsion, external, compound-bond,
- * centroid-bond and nonbonded forces.
+ * centroid-bond, nonbonded and collective-variable forces.
  *
  * OpenMM's CustomBondForce, CustomAngleForce, CustomTorsionForce and CustomExternalForce: an energy expression of r (bond), theta
  * (angle, torsion) or x, y, z (external), of per-term parameters and of global parameters, evaluated per term.  The host compiles
@@ -44,6 +44,18 @@
  * called after every remd_set_custom_globals: the forces refuse to act on coefficients older than the globals); the u_kl rows gain
  * beta_l (coeff_l - coeff_own) / V.  One wavefront per tile of 64 x 64 particles, every tile visited (csrc/custom_nonbonded.hip): the
  * cost is quadratic in N.
+ *
+ * Collective-variable forces (REMD_CUSTOM_CV, OpenMM's CustomCVForce over RMSDForce variables): the energy is an expression of n_cvs (1 ...
+ * REMD_CUSTOM_MAX_CVS) collective variables (REMD_CX_VAR operand 0, 1, 2), each the RMSD in nm of a set of particles from reference
+ * coordinates after the optimal superposition: V = sqrt(min over proper rotations U of sum_i |x_i - c - U ref_i|^2 / n), c the centroid of
+ * the n particles.  The variables come in CSR form (cv_offsets, cv_atoms) with cv_reference [.][3] beside cv_atoms, the reference of
+ * every variable centred on the centroid of its own rows (within 1e-9 nm); a variable has at least 3 particles, none twice; a particle
+ * may sit in several variables.  n_terms = 1, atoms NULL, n_params = 0, periodic = 0: no difference is a minimum image (OpenMM's rule),
+ * so the particles of a variable must be ones that no barostat moves apart (the host's business: openmmtools_amd refuses a variable
+ * that spans molecules of a periodic System).  Per force evaluation the device superposes every variable (f64 sums in a fixed order,
+ * the rotation from Horn's quaternion matrix by Jacobi rotations, the deviation summed directly), runs the expression on the RMSDs and
+ * gives particle i of variable k -(dE/dV_k) (x_i - c - U ref_i) / (n V_k); a mean square deviation below 1e-20 nm^2 gives V = 0 and no
+ * force from that variable (csrc/custom_cv.hip).  remd_get_custom_cv_values reads the RMSDs back.
  *
  * Tabulated functions (OpenMM's Continuous1DFunction and Discrete1DFunction) of every kind above: REMD_CX_TABLE1D and
  * REMD_CX_LOOKUP1D take one argument x from the stack and push one result; the operand is the offset of the function's block in the
@@ -94,7 +106,8 @@
  * whatever the other argument is.  The lookups push values[round(x) + nx round(y) (+ nx ny round(z))] (C's round) with derivatives 0,
  * and NaN where any index falls outside its range.  No arguments make the device load outside the block.
  *
- * Not provided: Continuous3DFunction, changing a table after remd_set_custom_terms, pointangle, pointdihedral, interaction groups.
+ * Not provided: Continuous3DFunction, changing a table or a reference after remd_set_custom_terms, pointangle, pointdihedral, interaction
+ * groups, collective variables other than the RMSD, a weighted RMSD, energy parameter derivatives.
  *
  * Global parameters belong to the handle: every force's program addresses the same n_globals columns, and every state carries one
  * value per column (remd_set_custom_globals).  A term acts in every force evaluation (MD steps, energies, the barostat,
@@ -105,7 +118,7 @@
  * REMD_CUSTOM_MAX_PARAMS parameters per term, REMD_CUSTOM_MAX_GLOBALS global columns per handle, REMD_CUSTOM_MAX_FORCES forces
  * per handle (of all kinds together), REMD_CUSTOM_MAX_PARTICLES particles per compound bond or groups per centroid bond,
  * REMD_CUSTOM_MAX_TABLE_POINTS points per tabulated function of one argument, REMD_CUSTOM_MAX_TABLE_CELLS values per tabulated
- * function of two or three.
+ * function of two or three, REMD_CUSTOM_MAX_CVS collective variables per collective-variable force.
  *
  * These entry points are declared here and not in remd_hip.h because the CPU port of the ABI does not provide them: a host binds
  * them only where the loaded library exports them.  Conventions as in remd_hip.h.
@@ -127,12 +140,15 @@ extern "C" {
 #define REMD_CUSTOM_CENTROID 5     /* atoms [n][n_particles] are GROUP numbers; the particles are the groups' centroids     */
 #define REMD_CUSTOM_NONBONDED 6    /* atoms NULL, n_terms = N, params [N][n_params]; variable r of every pair inside the cutoff */
 
+#define REMD_CUSTOM_CV       7     /* atoms NULL, n_terms = 1; variables the RMSDs of the force's collective variables            */
+
 #define REMD_CUSTOM_MAX_PROGRAM 256
 #define REMD_CUSTOM_MAX_STACK   16
 #define REMD_CUSTOM_MAX_PARAMS  16
 #define REMD_CUSTOM_MAX_GLOBALS 16
 #define REMD_CUSTOM_MAX_FORCES  8
 #define REMD_CUSTOM_MAX_PARTICLES 8
+#define REMD_CUSTOM_MAX_CVS   3
 #define REMD_CUSTOM_MAX_TABLE_POINTS 8192   /* points of one tabulated function of one argument                               */
 #define REMD_CUSTOM_MAX_TABLE_CELLS 65536   /* nx ny (nz) of one tabulated function of two or three arguments                  */
 
@@ -210,6 +226,11 @@ typedef struct remd_custom_force_desc {
     const int32_t* excl_offsets;   /* [N + 1]: particle i is excluded from excl_atoms[excl_offsets[i] ... excl_offsets[i + 1]) */
     const int32_t* excl_atoms;     /* particle indices, symmetric, sorted within a row, never the row's own particle       */
     int32_t long_range_correction; /* 1: the energy gains coeff / V (remd_set_custom_lrc); nb_method 2 only                */
+    /* REMD_CUSTOM_CV only (every other kind ignores them)                                                                */
+    int32_t n_cvs;                 /* the force's collective variables, 1 ... REMD_CUSTOM_MAX_CVS                          */
+    const int32_t* cv_offsets;     /* [n_cvs + 1]: variable k holds cv_atoms[cv_offsets[k] ... cv_offsets[k + 1]), at least 3 */
+    const int32_t* cv_atoms;       /* particle indices, 0 ... N - 1, none twice within a variable                          */
+    const double* cv_reference;    /* beside cv_atoms, [.][3] nm: each variable's rows centred on their own centroid       */
 } remd_custom_force_desc;
 
 /* the custom forces of the system; call after remd_set_system (which forgets them).  n = 0: none.  Every custom force of a handle
@@ -223,6 +244,9 @@ int  remd_set_custom_globals(remd_handle h, const double* values);
 int  remd_set_custom_lrc(remd_handle h, const double* coeff);
 /* out[R_local][n]: each custom force's energy, in the order of the descriptors whatever their kinds (kJ/mol) at the local replicas' current positions and own states                   */
 int  remd_get_custom_energies(remd_handle h, double* out);
+/* out[R_local][total]: the RMSD (nm) of every collective variable of the REMD_CUSTOM_CV forces at the local replicas' current
+   positions, in the order of the descriptors and of the variables within one (OpenMM's getCollectiveVariableValues)              */
+int  remd_get_custom_cv_values(remd_handle h, double* out);
 
 #ifdef __cplusplus
 }

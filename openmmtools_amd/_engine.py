@@ -78,7 +78,8 @@ class RemdCustomForceDesc(C.Structure):
                 ('periodic', C.c_int32), ('force_group', C.c_int32), ('n_particles', C.c_int32),
                 ('n_groups', C.c_int32), ('group_offsets', c_int32_p), ('group_atoms', c_int32_p), ('group_weights', c_double_p),
                 ('nb_method', C.c_int32), ('cutoff', C.c_double), ('switch_distance', C.c_double), ('excl_offsets', c_int32_p),
-                ('excl_atoms', c_int32_p), ('long_range_correction', C.c_int32)]
+                ('excl_atoms', c_int32_p), ('long_range_correction', C.c_int32),
+                ('n_cvs', C.c_int32), ('cv_offsets', c_int32_p), ('cv_atoms', c_int32_p), ('cv_reference', c_double_p)]
 
 
 class RemdGbModelDesc(C.Structure):
@@ -93,6 +94,8 @@ RESTRAINT_EXPORTS = ['remd_set_restraints', 'remd_set_restraint_lambdas', 'remd_
 RESTRAINT_FRAMES_EXPORTS = ['remd_restraint_frames', 'remd_restraint_frames_last_ms']
 # the GPU-only extension of include/remd_hip_custom.h (custom bond / angle / torsion / external forces), bound the same way
 CUSTOM_EXPORTS = ['remd_set_custom_terms', 'remd_set_custom_globals', 'remd_set_custom_lrc', 'remd_get_custom_energies']
+# the collective-variable forces of the same header (REMD_CUSTOM_CV): a library built before them lacks the entry point
+CUSTOM_CV_EXPORTS = ['remd_get_custom_cv_values']
 # the GPU-only extension of include/remd_hip_barostat.h (per-axis Monte Carlo barostats), bound the same way
 BAROSTAT_AXIS_EXPORTS = ['remd_set_barostat_axes', 'remd_get_barostat_axis_stats']
 BAROSTAT_ANISOTROPIC, BAROSTAT_MEMBRANE = 1, 2
@@ -219,6 +222,10 @@ def load_library(path=None):
         lib.remd_set_custom_lrc.argtypes = [vp, c_double_p]
         lib.remd_get_custom_energies.argtypes = [vp, c_double_p]
         for name in CUSTOM_EXPORTS:
+            getattr(lib, name).restype = C.c_int
+    if hasattr(lib, 'remd_get_custom_cv_values'):
+        lib.remd_get_custom_cv_values.argtypes = [vp, c_double_p]
+        for name in CUSTOM_CV_EXPORTS:
             getattr(lib, name).restype = C.c_int
     if hasattr(lib, 'remd_set_barostat_axes'):            # include/remd_hip_barostat.h (GPU-only, like the restraints)
         lib.remd_set_barostat_axes.argtypes = [vp, C.c_int, c_double_p, c_double_p, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -550,7 +557,7 @@ class HipEngine:
         restraints = desc_dict.get('restraints')
         if restraints:                                   # receptor-ligand restraints (forces.py; csrc/restraints.hip)
             self.set_restraints([restraints[k] for k in sorted(restraints)])
-        self.n_custom = self.n_custom_globals = 0
+        self.n_custom = self.n_custom_globals = self.n_custom_cvs = 0
         self._custom_lrc = None
         custom = desc_dict.get('custom_terms')
         if custom:                                       # custom bond / angle / torsion / external forces (custom_expr.py; csrc/custom_terms.hip)
@@ -597,6 +604,9 @@ class HipEngine:
     def set_custom_terms(self, terms):
         """The custom forces of the system (dicts of system.system_to_desc's 'custom_terms'); after set_system, which forgets them."""
         fn = self._custom_entry('remd_set_custom_terms')
+        n_cv = sum(len(t['cv_offsets']) - 1 for t in terms if 'cv_offsets' in t)
+        if n_cv:
+            self._custom_cv_entry('remd_get_custom_cv_values')
         arr = (RemdCustomForceDesc * max(1, len(terms)))()
         keep = []
         for k, t in enumerate(terms):
@@ -624,11 +634,23 @@ class HipEngine:
                 keep += [e_off, e_atoms]
                 pairs = (int(t['nb_method']), float(t['cutoff']), float(t['switch_distance']), _ip(e_off), _ip(e_atoms) if len(e_atoms) else None,
                          int(t['long_range_correction']))
-            arr[k] = RemdCustomForceDesc(int(t['kind']), n_terms, None if nonbonded else _ip(atoms), params.shape[1], _dp(params), len(program), _ip(program),
+            cvs = (0, None, None, None)
+            if 'cv_offsets' in t:                                    # a collective-variable force: one term, no atoms of its own
+                c_off = np.ascontiguousarray(t['cv_offsets'], dtype=np.int32)
+                c_atoms = np.ascontiguousarray(t['cv_atoms'], dtype=np.int32)
+                c_ref = np.ascontiguousarray(t['cv_reference'], dtype=np.float64).reshape(-1, 3)
+                if len(c_atoms) != c_off[-1] or len(c_ref) != len(c_atoms):
+                    raise ValueError('set_custom_terms: cv_atoms and cv_reference must hold cv_offsets[-1] = %d rows' % c_off[-1])
+                keep += [c_off, c_atoms, c_ref]
+                cvs = (len(c_off) - 1, _ip(c_off), _ip(c_atoms), _dp(c_ref))
+                n_terms = 1
+            no_atoms = nonbonded or 'cv_offsets' in t
+            arr[k] = RemdCustomForceDesc(int(t['kind']), n_terms, None if no_atoms else _ip(atoms), params.shape[1], _dp(params), len(program), _ip(program),
                                          len(consts), _dp(consts), int(t['stack_depth']), len(defaults), _dp(defaults),
-                                         int(t['periodic']), int(t['force_group']), n_particles, *groups, *pairs)
+                                         int(t['periodic']), int(t['force_group']), n_particles, *groups, *pairs, *cvs)
         self._check(fn(self.h, arr, len(terms)), 'remd_set_custom_terms')
         self.n_custom = len(terms)
+        self.n_custom_cvs = n_cv
         self.n_custom_globals = len(terms[0]['global_defaults']) if terms else 0
         # the long-range corrections of nonbonded forces: host integrals under every state's globals (custom_expr.LongRangeCorrection),
         # handed over behind every set_custom_globals
@@ -650,6 +672,22 @@ class HipEngine:
         fn = self._custom_entry('remd_get_custom_energies')
         out = np.zeros((self.R, self.n_custom))
         self._check(fn(self.h, _dp(out)), 'remd_get_custom_energies')
+        return out
+
+    def _custom_cv_entry(self, name):
+        if not hasattr(self.lib, name):
+            raise NotImplementedError('%s: this build of the engine library has no collective-variable forces (CustomCVForce / RMSDForce: '
+                                      'REMD_CUSTOM_CV of include/remd_hip_custom.h is GPU-only)' % name)
+        return getattr(self.lib, name)
+
+    def custom_cv_values(self):
+        """[R_local][total collective variables]: the current RMSDs (nm) of the CustomCVForce / RMSDForce forces, in the order of
+        the forces and of the variables within one (OpenMM's getCollectiveVariableValues)."""
+        fn = self._custom_cv_entry('remd_get_custom_cv_values')
+        if not getattr(self, 'n_custom_cvs', 0):
+            raise ValueError('custom_cv_values: the system has no CustomCVForce or RMSDForce')
+        out = np.zeros((self.R, self.n_custom_cvs))
+        self._check(fn(self.h, _dp(out)), 'remd_get_custom_cv_values')
         return out
 
     def set_states(self, beta, lambda_sterics=None, lambda_electrostatics=None, energy_const=None):

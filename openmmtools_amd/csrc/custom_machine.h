@@ -1,5 +1,5 @@
 // The stack machine of the custom forces (include/remd_hip_custom.h), shared by custom_terms.hip (bond, angle, torsion, external),
-// custom_compound.hip (compound bonds) and custom_centroid.hip (centroid bonds, whose particles are centroids): the per-force record, the handle's tables, and cst_eval, which runs a postfix program
+// custom_compound.hip (compound bonds) and custom_centroid.hip (centroid bonds, whose particles are centroids) and custom_cv.hip (collective variables, whose variables are RMSDs): the per-force record, the handle's tables, and cst_eval, which runs a postfix program
 // one term per lane with every stack slot a value and three partials, the stack in LDS as [slot][component][lane].
 //
 // cst_eval<GEOM>: the instantiation of the four one-variable kinds (GEOM = false) has the variables in three registers and no case
@@ -25,12 +25,16 @@ struct cst_force {
     int excl0;                   // its row offsets [N + 1] in the handle's excl_off (which point into the handle's excl_atoms)
     int lrc;                     // 1: it has a long-range correction (the handle's lrc table carries its column)
     double cutoff, switch_dist;  // switch_dist < 0: no switching function
+    // REMD_CUSTOM_CV only (custom_cv.hip): n_terms = 1, npad = 64, no atoms of its own
+    int cv0, n_cvs;              // its first collective variable among the handle's, and how many it has (1 ... 3)
 };
 
 struct cst_tables {
     int nf = 0, ng = 0, K = 0, total_pad = 0, waves_simple = 0; long long glob_version = -1;   // (waves_simple: the wavefronts of the four one-variable kinds, in front; glob belongs to the states of that remd_set_states)
     int waves_compound = 0;                                                    // where the compound-bond forces' wavefronts end and the nonbonded forces' tiles begin
-    int waves_particles = 0;                                                   // where the nonbonded forces' tiles end and the centroid forces' wavefronts begin (the last part)
+    int waves_particles = 0;                                                   // where the nonbonded forces' tiles end and the centroid forces' wavefronts begin
+    int waves_centroid = 0;                                                    // where the centroid forces' wavefronts end and the collective-variable forces' begin (the last part)
+    int n_cv = 0;                                                              // the collective variables of all such forces (0: no such force, none of the cv members below holds anything)
     int n_groups = 0;                                                          // the groups of all centroid forces (0: no centroid force, none of the members below holds anything)
     bool uniform = true;                                                       // every state carries the same globals: no u_kl share
     std::vector<cst_force> F; std::vector<int> wave_force, atoms; std::vector<double> par, consts, glob, defaults; std::vector<int2> prog;
@@ -48,6 +52,12 @@ struct cst_tables {
     dev_array<int> d_refs;             // (centroid slot * REMD_CUSTOM_MAX_PARTICLES + position in the bond) of every bond that names the group, in table order
     dev_array<double> d_C;             // [R][n_groups][3] centroids
     dev_array<double> d_G;             // [R][centroid slots][REMD_CUSTOM_MAX_PARTICLES][3] dE / d centroid
+    // collective-variable forces (custom_cv.hip): the RMSD variables of all of them in CSR form (cst_force::cv0 names a force's first)
+    std::vector<int> cv_off, cv_atoms; std::vector<double> cv_ref;
+    dev_array<int> d_cv_off;           // [n_cv + 1] into cv_atoms / cv_ref
+    dev_array<int> d_cv_atoms;         // the variables' particles
+    dev_array<double> d_cv_ref;        // beside cv_atoms, [.][3]: the reference, centred on each variable's own centroid
+    dev_array<double> d_W;             // [R][n_cv][16]: RMSD, "no force" flag, centroid, rotation, dE/dRMSD (custom_cv.hip)
     // nonbonded forces (custom_nonbonded.hip): the exclusion rows of all of them, and the long-range coefficients of the states
     std::vector<int> excl_off, excl_atoms; std::vector<double> lrc;
     dev_array<int> d_excl_off;         // per nonbonded force N + 1 offsets into excl_atoms (cst_force::excl0 names the first)
@@ -383,6 +393,10 @@ void remd_custom_compound_ukl(remd_ctx* h, cst_tables& t);
 // custom_centroid.hip: the same for the centroid forces' wavefronts (those behind waves_particles): centroids, bonds, spread
 void remd_custom_centroid_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
 void remd_custom_centroid_ukl(remd_ctx* h, cst_tables& t);
+// custom_cv.hip: the same for the collective-variable forces' wavefronts (those behind waves_centroid): superposition, expression, spread
+void remd_custom_cv_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
+void remd_custom_cv_ukl(remd_ctx* h, cst_tables& t);
+size_t remd_custom_cv_w();             // doubles per (replica, variable) of cst_tables::d_W; the RMSD is the first
 // custom_nonbonded.hip: the same for the nonbonded forces' tiles (those between waves_compound and waves_particles), and the long-range
 // correction's share of the energies (behind custom_reduce_kernel) and of the u_kl rows (behind custom_ukl_reduce_kernel)
 void remd_custom_nonbonded_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);

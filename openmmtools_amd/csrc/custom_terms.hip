@@ -26,7 +26,8 @@
 // The machine itself (cst_eval) lives in custom_machine.h: custom_compound.hip runs the same one for CustomCompoundBondForce, whose
 // wavefronts follow the ones of this file's four kinds in the padded term space and share the energy and u_kl reductions below, and
 // custom_centroid.hip runs it for CustomCentroidBondForce, whose wavefronts come last; custom_nonbonded.hip runs it for
-// CustomNonbondedForce, one wavefront per tile of 64 x 64 atoms, between those two.
+// CustomNonbondedForce, one wavefront per tile of 64 x 64 atoms, between those two; custom_cv.hip runs it for CustomCVForce, one
+// wavefront per force behind the centroid forces', its variables the RMSDs a launch of its own computed.
 #include "remd_internal.h"
 #include "listed_terms.h"
 #include "custom_machine.h"
@@ -198,6 +199,9 @@ int ensure_buffers(remd_ctx* h, cst_tables& t)
     const size_t nC = (size_t)h->R * t.n_groups * 3, nG = (size_t)h->R * (waves - t.waves_particles) * 64 * REMD_CUSTOM_MAX_PARTICLES * 3;
     if (t.d_C.size() != nC) REMD_TRY(t.d_C.alloc(h, nC));
     if (t.d_G.size() != nG) REMD_TRY(t.d_G.alloc(h, nG));
+    // collective-variable forces: what the superposition hands on (n_cv = 0: nothing is allocated)
+    const size_t nW = (size_t)h->R * t.n_cv * remd_custom_cv_w();
+    if (t.d_W.size() != nW) REMD_TRY(t.d_W.alloc(h, nW));
     return 0;
 }
 
@@ -209,8 +213,9 @@ int set_tables(remd_ctx* h, cst_tables& t)
         (rc = t.d_prog.upload(h, t.prog)) || (rc = t.d_grp_off.upload(h, t.grp_off)) || (rc = t.d_grp_atoms.upload(h, t.grp_atoms)) ||
         (rc = t.d_grp_w.upload(h, t.grp_w)) || (rc = t.d_grp_periodic.upload(h, t.grp_periodic)) || (rc = t.d_ref_off.upload(h, t.ref_off)) ||
         (rc = t.d_refs.upload(h, t.refs)) || (rc = t.d_excl_off.upload(h, t.excl_off)) || (rc = t.d_excl_atoms.upload(h, t.excl_atoms)) ||
-        (rc = t.d_lrc.upload(h, t.lrc)) || (rc = t.d_mol_first.upload(h, t.mol_first)) || (rc = t.d_mol_size.upload(h, t.mol_size))) return rc;
-    t.d_E.reset(); t.d_Ewave.reset(); t.d_D.reset(); t.d_C.reset(); t.d_G.reset();
+        (rc = t.d_lrc.upload(h, t.lrc)) || (rc = t.d_mol_first.upload(h, t.mol_first)) || (rc = t.d_mol_size.upload(h, t.mol_size)) ||
+        (rc = t.d_cv_off.upload(h, t.cv_off)) || (rc = t.d_cv_atoms.upload(h, t.cv_atoms)) || (rc = t.d_cv_ref.upload(h, t.cv_ref))) return rc;
+    t.d_E.reset(); t.d_Ewave.reset(); t.d_D.reset(); t.d_C.reset(); t.d_G.reset(); t.d_W.reset();
     return 0;
 }
 
@@ -327,6 +332,7 @@ int remd_custom_clone(remd_ctx* parent, remd_ctx* child)
     c.waves_particles = t->waves_particles; c.n_groups = t->n_groups; c.waves_compound = t->waves_compound;
     c.excl_off = t->excl_off; c.excl_atoms = t->excl_atoms; c.lrc = t->lrc; c.has_lrc = t->has_lrc; c.lrc_valid = t->lrc_valid; c.periodic_cutoff = t->periodic_cutoff;
     c.mol_first = t->mol_first; c.mol_size = t->mol_size;
+    c.waves_centroid = t->waves_centroid; c.n_cv = t->n_cv; c.cv_off = t->cv_off; c.cv_atoms = t->cv_atoms; c.cv_ref = t->cv_ref;
     c.grp_off = t->grp_off; c.grp_atoms = t->grp_atoms; c.grp_w = t->grp_w; c.grp_periodic = t->grp_periodic; c.ref_off = t->ref_off; c.refs = t->refs;
     c.glob_version = t->glob_version == parent->states_version ? child->states_version : -1;
     c.F = t->F; c.wave_force = t->wave_force; c.atoms = t->atoms; c.par = t->par; c.consts = t->consts; c.glob = t->glob;
@@ -364,7 +370,8 @@ int remd_custom_forces(remd_ctx* h, bool with_energy, int ep_slot, hipStream_t s
     }
     if (t.waves_compound > t.waves_simple) remd_custom_compound_forces(h, t, with_energy, st);    // (custom_compound.hip: the wavefronts behind)
     if (t.waves_particles > t.waves_compound) remd_custom_nonbonded_forces(h, t, with_energy, st); // (custom_nonbonded.hip: the tiles behind those)
-    if (waves > t.waves_particles) remd_custom_centroid_forces(h, t, with_energy, st);            // (custom_centroid.hip: the last ones)
+    if (t.waves_centroid > t.waves_particles) remd_custom_centroid_forces(h, t, with_energy, st);  // (custom_centroid.hip: behind those)
+    if (waves > t.waves_centroid) remd_custom_cv_forces(h, t, with_energy, st);                    // (custom_cv.hip: the last ones)
     if (with_energy)
         hipLaunchKernelGGL(custom_reduce_kernel, dim3(h->R), dim3(64), 0, st, t.nf, t.d_F, waves, t.d_Ewave, t.d_E, h->d_epart, h->n_epart, ep_slot);
     if (with_energy && t.has_lrc) remd_custom_nonbonded_lrc(h, t, ep_slot, st);
@@ -392,7 +399,8 @@ int remd_custom_ukl(remd_ctx* h, double* d_rows)
                            t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, h->K, h->d_labels, h->r_begin, h->Npad, h->d_pos, h->d_box, t.d_D);
     if (t.waves_compound > t.waves_simple) remd_custom_compound_ukl(h, t);
     if (t.waves_particles > t.waves_compound) remd_custom_nonbonded_ukl(h, t);
-    if (waves > t.waves_particles) remd_custom_centroid_ukl(h, t);
+    if (t.waves_centroid > t.waves_particles) remd_custom_centroid_ukl(h, t);
+    if (waves > t.waves_centroid) remd_custom_cv_ukl(h, t);
     hipLaunchKernelGGL(custom_ukl_reduce_kernel, dim3(h->K, h->R), dim3(64), 0, h->stream, h->K, waves, t.d_D, h->d_beta, d_rows);
     if (t.has_lrc) remd_custom_nonbonded_lrc_ukl(h, t, d_rows);
     REMD_CHECK(h, hipGetLastError());
@@ -406,9 +414,8 @@ int remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, int
     if (!h || n < 0 || (n > 0 && !desc)) return remd_fail(h, -1, "remd_set_custom_terms: bad arguments");
     if (!h->has_system) return remd_fail(h, -1, "remd_set_custom_terms: call remd_set_system first");
     hipSetDevice(h->device);
-    remd_custom_release(h);
-    h->config_version++;
-    if (n == 0) return 0;
+    if (n == 0) { remd_custom_release(h); h->config_version++; return 0; }
+    // (everything below up to set_tables only fills `t`: a refused call leaves the handle as it was)
     if (n > REMD_CUSTOM_MAX_FORCES) return remd_fail(h, -1, "remd_set_custom_terms: more than REMD_CUSTOM_MAX_FORCES custom forces");
     cst_tables t;
     t.nf = n; t.ng = desc[0].n_globals;
@@ -419,13 +426,13 @@ int remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, int
     for (int i = 0; i < n; ++i) {
         const remd_custom_force_desc& d = desc[i];
         const std::string who = "remd_set_custom_terms: force " + std::to_string(i) + ": ";
-        if (d.kind < 0 || d.kind > REMD_CUSTOM_NONBONDED) return remd_fail(h, -1, who + "unknown kind");
-        const bool nonbonded = d.kind == REMD_CUSTOM_NONBONDED;
+        if (d.kind < 0 || d.kind > REMD_CUSTOM_CV) return remd_fail(h, -1, who + "unknown kind");
+        const bool nonbonded = d.kind == REMD_CUSTOM_NONBONDED, cv = d.kind == REMD_CUSTOM_CV;
         const bool centroid = d.kind == REMD_CUSTOM_CENTROID, compound = d.kind == REMD_CUSTOM_COMPOUND || centroid;
         if (compound ? (d.n_particles < 1 || d.n_particles > REMD_CUSTOM_MAX_PARTICLES) : d.n_particles != 0)
             return remd_fail(h, -1, who + "n_particles is 1 ... REMD_CUSTOM_MAX_PARTICLES for a compound-bond or centroid-bond force and 0 for every other kind");
-        const int wd = compound ? d.n_particles : nonbonded ? 0 : width4[d.kind];
-        if (d.n_terms <= 0 || (!d.atoms && !nonbonded)) return remd_fail(h, -1, who + "no terms");
+        const int wd = compound ? d.n_particles : (nonbonded || cv) ? 0 : width4[d.kind];
+        if (d.n_terms <= 0 || (!d.atoms && !nonbonded && !cv)) return remd_fail(h, -1, who + "no terms");
         if (d.n_params < 0 || d.n_params > REMD_CUSTOM_MAX_PARAMS || (d.n_params > 0 && !d.params))
             return remd_fail(h, -1, who + "0 ... REMD_CUSTOM_MAX_PARAMS parameters per term are supported");
         if (nonbonded) {
@@ -451,11 +458,37 @@ int remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, int
                 for (size_t k = 0; k < h->box_host.size(); ++k)
                     if (!(h->box_host[k] >= 2.0 * d.cutoff)) return remd_fail(h, -1, who + "box smaller than twice the cutoff");
         }
+        if (cv) {
+            // what custom_cv.hip indexes unchecked: the variables in CSR form, their particles, the reference beside them
+            if (d.n_terms != 1 || d.n_params != 0 || d.periodic != 0) return remd_fail(h, -1, who + "a collective-variable force has n_terms = 1, no per-term parameters and is not periodic");
+            if (d.n_cvs < 1 || d.n_cvs > REMD_CUSTOM_MAX_CVS) return remd_fail(h, -1, who + "a collective-variable force has 1 ... REMD_CUSTOM_MAX_CVS collective variables");
+            if (!d.cv_offsets || !d.cv_atoms || !d.cv_reference) return remd_fail(h, -1, who + "a collective-variable force needs cv_offsets, cv_atoms and cv_reference");
+            if (d.cv_offsets[0] != 0) return remd_fail(h, -1, who + "cv_offsets must start at 0");
+            std::vector<char> seen(h->N);
+            for (int c = 0; c < d.n_cvs; ++c) {
+                const int b = d.cv_offsets[c], e = d.cv_offsets[c + 1];
+                if (e < b || e - b < 3) return remd_fail(h, -1, who + "collective variable " + std::to_string(c) + ": an RMSD needs at least 3 particles");
+                std::fill(seen.begin(), seen.end(), 0);
+                double m[3] = {0.0, 0.0, 0.0};
+                for (int k = b; k < e; ++k) {
+                    const int a = d.cv_atoms[k];
+                    if (a < 0 || a >= h->N) return remd_fail(h, -1, who + "collective variable " + std::to_string(c) + ": particle index out of range");
+                    if (seen[a]) return remd_fail(h, -1, who + "collective variable " + std::to_string(c) + ": particle " + std::to_string(a) + " named twice");
+                    seen[a] = 1;
+                    for (int x = 0; x < 3; ++x) {
+                        if (!std::isfinite(d.cv_reference[3 * (size_t)k + x])) return remd_fail(h, -1, who + "collective variable " + std::to_string(c) + ": a reference position that is not finite");
+                        m[x] += d.cv_reference[3 * (size_t)k + x];
+                    }
+                }
+                for (int x = 0; x < 3; ++x)
+                    if (!(fabs(m[x]) <= 1e-9 * (e - b))) return remd_fail(h, -1, who + "collective variable " + std::to_string(c) + ": the reference must be centred on its own centroid (within 1e-9 nm)");
+            }
+        }
         if (d.n_globals != t.ng) return remd_fail(h, -1, who + "every descriptor must carry the handle's n_globals");
         for (int k = 0; k < t.ng; ++k) if (d.global_defaults && d.global_defaults[k] != t.defaults[k]) return remd_fail(h, -1, who + "global_defaults differ between the descriptors");
         if (d.force_group != desc[0].force_group || d.force_group < 0 || d.force_group > 31)
             return remd_fail(h, -1, who + "every custom force of a handle must sit in one force group (0 ... 31)");
-        if (const char* bad = check_program(d, compound ? 3 * d.n_particles : nonbonded ? 1 : n_vars4[d.kind])) return remd_fail(h, -1, who + bad);
+        if (const char* bad = check_program(d, compound ? 3 * d.n_particles : nonbonded ? 1 : cv ? d.n_cvs : n_vars4[d.kind])) return remd_fail(h, -1, who + bad);
         if (centroid) {
             // the groups: CSR offsets that start at 0 and increase (no empty group), atoms of the system, weights that sum to 1
             if (d.n_groups <= 0 || !d.group_offsets || !d.group_atoms || !d.group_weights) return remd_fail(h, -1, who + "a centroid-bond force needs n_groups > 0, group_offsets, group_atoms and group_weights");
@@ -498,20 +531,32 @@ int remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, int
         for (int p = 0; p < d.n_params; ++p) for (int s = 0; s < par_stride; ++s) t.par.push_back(d.params[(size_t)std::min(s, d.n_terms - 1) * d.n_params + p]);
         for (int pc = 0; pc < d.n_program; ++pc) t.prog.push_back(make_int2(d.program[2 * pc], d.program[2 * pc + 1]));
         if (d.n_consts > 0) t.consts.insert(t.consts.end(), d.consts, d.consts + d.n_consts);
+        if (cv) {
+            // its variables join the handle's tables
+            f.cv0 = t.n_cv; f.n_cvs = d.n_cvs;
+            if (t.cv_off.empty()) t.cv_off.push_back(0);
+            const int base = (int)t.cv_atoms.size(), total = d.cv_offsets[d.n_cvs];
+            for (int c = 1; c <= d.n_cvs; ++c) t.cv_off.push_back(base + d.cv_offsets[c]);
+            t.cv_atoms.insert(t.cv_atoms.end(), d.cv_atoms, d.cv_atoms + total);
+            t.cv_ref.insert(t.cv_ref.end(), d.cv_reference, d.cv_reference + 3 * (size_t)total);
+            t.n_cv += d.n_cvs;
+        }
         t.F.push_back(f);
     }
     // the padded term space: the four one-variable kinds first, the compound-bond forces behind them, then the nonbonded forces' tiles,
-    // the centroid-bond forces last (each part has its own kernel); the energy columns keep the forces' order whatever their slots
-    for (int pass = 0; pass < 4; ++pass) {
+    // the centroid-bond forces, the collective-variable forces last (each part has its own kernel); the energy columns keep the forces'
+    // order whatever their slots
+    for (int pass = 0; pass < 5; ++pass) {
         for (int i = 0; i < n; ++i) {
             cst_force& f = t.F[i];
-            if ((f.kind == REMD_CUSTOM_CENTROID ? 3 : f.kind == REMD_CUSTOM_NONBONDED ? 2 : f.kind == REMD_CUSTOM_COMPOUND ? 1 : 0) != pass) continue;
+            if ((f.kind == REMD_CUSTOM_CV ? 4 : f.kind == REMD_CUSTOM_CENTROID ? 3 : f.kind == REMD_CUSTOM_NONBONDED ? 2 : f.kind == REMD_CUSTOM_COMPOUND ? 1 : 0) != pass) continue;
             f.slot0 = t.total_pad; t.total_pad += f.npad;
             for (int w = 0; w < f.npad / 64; ++w) t.wave_force.push_back(i);
         }
         if (pass == 0) t.waves_simple = t.total_pad / 64;
         if (pass == 1) t.waves_compound = t.total_pad / 64;
         if (pass == 2) t.waves_particles = t.total_pad / 64;
+        if (pass == 3) t.waves_centroid = t.total_pad / 64;
     }
     int rows = 4;
     for (int i = 0; i < n; ++i) rows = std::max(rows, t.F[i].n_particles);
@@ -562,7 +607,7 @@ int remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, int
         auto find = [&](int a) { while (root[a] != a) a = root[a] = root[root[a]]; return a; };
         for (int i = 0; i < n; ++i) {
             const cst_force& f = t.F[i];
-            if (f.kind == REMD_CUSTOM_EXTERNAL || f.kind == REMD_CUSTOM_CENTROID || f.kind == REMD_CUSTOM_NONBONDED) continue;
+            if (f.kind == REMD_CUSTOM_EXTERNAL || f.kind == REMD_CUSTOM_CENTROID || f.kind == REMD_CUSTOM_NONBONDED || f.kind == REMD_CUSTOM_CV) continue;
             for (int b = 0; b < f.n_terms; ++b) for (int a = 1; a < f.n_particles; ++a) {
                 const int p = find(desc[i].atoms[(size_t)b * f.n_particles]), q = find(desc[i].atoms[(size_t)b * f.n_particles + a]);
                 if (p != q) root[std::max(p, q)] = std::min(p, q);
@@ -577,6 +622,8 @@ int remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, int
         }
         if (!contiguous) { t.mol_first.clear(); t.mol_size.clear(); }
     }
+    remd_custom_release(h);
+    h->config_version++;
     int rc = set_tables(h, t);
     if (rc) return rc;
     const double periodic_cutoff = t.periodic_cutoff;
@@ -637,6 +684,21 @@ int remd_get_custom_energies(remd_handle h, double* out)
     int rc = remd_compute_forces(h, true); if (rc) return rc;
     REMD_CHECK(h, hipMemcpyAsync(out, t->d_E, sizeof(double) * (size_t)h->R * t->nf, hipMemcpyDeviceToHost, h->stream));
     REMD_CHECK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int remd_get_custom_cv_values(remd_handle h, double* out)
+{
+    if (!h || !out || h->R <= 0) return remd_fail(h, -1, "remd_get_custom_cv_values: bad arguments");
+    cst_tables* t = h->cst.get();
+    if (!t || h->n_custom == 0 || t->n_cv == 0) return remd_fail(h, -1, "remd_get_custom_cv_values: no collective-variable force (remd_set_custom_terms)");
+    hipSetDevice(h->device);
+    int rc = remd_compute_forces(h, true); if (rc) return rc;
+    const size_t w = remd_custom_cv_w(), n = (size_t)h->R * t->n_cv;
+    std::vector<double> W(n * w);
+    REMD_CHECK(h, hipMemcpyAsync(W.data(), t->d_W, sizeof(double) * n * w, hipMemcpyDeviceToHost, h->stream));
+    REMD_CHECK(h, hipStreamSynchronize(h->stream));
+    for (size_t k = 0; k < n; ++k) out[k] = W[k * w];
     return 0;
 }
 

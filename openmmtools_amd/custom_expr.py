@@ -1,7 +1,7 @@
 """Compiler of OpenMM energy expressions for the custom bond, angle, torsion, external, compound-bond, centroid-bond and nonbonded forces
 (system.CustomBondForce, CustomAngleForce, CustomTorsionForce, CustomExternalForce, CustomCompoundBondForce, CustomCentroidBondForce,
 CustomNonbondedForce): an energy string becomes the postfix program of include/remd_hip_custom.h, which csrc/custom_terms.hip,
-csrc/custom_compound.hip, csrc/custom_centroid.hip and csrc/custom_nonbonded.hip run on a forward-mode stack machine (every stack slot a value and its partial derivatives with respect to
+csrc/custom_compound.hip, csrc/custom_centroid.hip, csrc/custom_cv.hip and csrc/custom_nonbonded.hip run on a forward-mode stack machine (every stack slot a value and its partial derivatives with respect to
 the force's variables).
 
 A compound-bond force of P particles (1 ... MAX_PARTICLES) has the variables x1 y1 z1 ... xP yP zP (operand 3*(i-1)+c) and the
@@ -44,8 +44,11 @@ MAX_TABLE_POINTS = 8192                         # points of one tabulated functi
 MAX_TABLE_CELLS = 65536                         # values (the product of the sizes) of one tabulated function of two or three arguments
 
 KIND_BOND, KIND_ANGLE, KIND_TORSION, KIND_EXTERNAL, KIND_COMPOUND, KIND_CENTROID, KIND_NONBONDED = 0, 1, 2, 3, 4, 5, 6
+KIND_CV = 7                                     # system.CustomCVForce over RMSDForce variables (csrc/custom_cv.hip)
+MAX_CVS = 3                                     # collective variables per CustomCVForce: the machine carries three partials
 KIND_OF_CLASS = {'CustomNonbondedForce': KIND_NONBONDED, 'CustomBondForce': KIND_BOND, 'CustomAngleForce': KIND_ANGLE, 'CustomTorsionForce': KIND_TORSION,
-                 'CustomExternalForce': KIND_EXTERNAL, 'CustomCompoundBondForce': KIND_COMPOUND, 'CustomCentroidBondForce': KIND_CENTROID}
+                 'CustomExternalForce': KIND_EXTERNAL, 'CustomCompoundBondForce': KIND_COMPOUND, 'CustomCentroidBondForce': KIND_CENTROID,
+                 'CustomCVForce': KIND_CV}
 VARIABLES = {KIND_BOND: ('r',), KIND_ANGLE: ('theta',), KIND_TORSION: ('theta',), KIND_EXTERNAL: ('x', 'y', 'z'), KIND_NONBONDED: ('r',)}
 
 
@@ -470,7 +473,8 @@ def is_custom_term_force(force):
     CustomCompoundBondForce, or a system.CustomCentroidBondForce (forces.CustomCentroidBondForce, the restraints' base, is another class)."""
     from . import system as _system
     from . import forces as _forces
-    if isinstance(force, (_system.CustomCompoundBondForce, _system.CustomCentroidBondForce, _system.CustomNonbondedForce)):
+    if isinstance(force, (_system.CustomCompoundBondForce, _system.CustomCentroidBondForce, _system.CustomNonbondedForce,
+                          _system.CustomCVForce, _system.RMSDForce)):
         return True
     if isinstance(force, _system.CustomExternalForce):
         return not force.is_harmonic_oscillator()
@@ -479,6 +483,133 @@ def is_custom_term_force(force):
     if isinstance(force, _system.CustomBondForce):
         return not _forces.is_restraint_form(force)
     return False
+
+
+def energy_text(force):
+    """The energy string by which a message names a custom force; a bare RMSDForce has none of its own (OpenMM gives it no
+    getEnergyFunction): it is named by the expression it acts as, 'v'."""
+    return as_cv_force(force).getEnergyFunction()
+
+
+def as_cv_force(force):
+    """A bare system.RMSDForce as what it acts as in a System, CustomCVForce('v') with itself as v; every other force as it is."""
+    from . import system as _system
+    if not isinstance(force, _system.RMSDForce):
+        return force
+    cv = _system.CustomCVForce('v')
+    cv.addCollectiveVariable('v', force)
+    cv.setForceGroup(force.getForceGroup())
+    return cv
+
+
+def cv_variables(force, n_atoms):
+    """The collective variables of a CustomCVForce in CSR form: (names, cv_offsets int32 [n + 1], cv_atoms int32, cv_reference float64
+    [sum n][3]), each variable's reference rows centred on the centroid of its own particles in f64."""
+    from . import system as _system
+    n_cvs = force.getNumCollectiveVariables()
+    if n_cvs == 0:
+        raise ValueError('CustomCVForce (energy %r) has no collective variable' % (force.getEnergyFunction(),))
+    if n_cvs > MAX_CVS:
+        raise NotImplementedError('CustomCVForce (energy %r): %d collective variables (the engine takes 1 ... %d): %s'
+                                  % (force.getEnergyFunction(), n_cvs, MAX_CVS, ', '.join(force.getCollectiveVariableName(i) for i in range(n_cvs))))
+    global_names = [force.getGlobalParameterName(i) for i in range(force.getNumGlobalParameters())]
+    names, offsets, atoms, reference = [], [0], [], []
+    for i in range(n_cvs):
+        name, v = force.getCollectiveVariableName(i), force.getCollectiveVariable(i)
+        where = 'CustomCVForce: collective variable %r' % name
+        if name in names:
+            raise ValueError('%s is named twice' % where)
+        if name in global_names:
+            raise ValueError('%s is also a global parameter of the force' % where)
+        if not isinstance(v, _system.RMSDForce):
+            raise NotImplementedError('%s is a %s (only RMSDForce collective variables are supported)' % (where, type(v).__name__))
+        ref = v.getReferencePositions()
+        if n_atoms is not None and len(ref) != n_atoms:
+            raise ValueError('%s: RMSDForce has %d reference positions, the System has %d particles' % (where, len(ref), n_atoms))
+        particles = v.getParticles() or list(range(len(ref)))
+        if len(particles) < 3:
+            raise ValueError('%s: RMSDForce over %d particles (an RMSD after superposition needs at least 3)' % (where, len(particles)))
+        if min(particles) < 0 or max(particles) >= len(ref):
+            raise ValueError('%s: RMSDForce names particle %d (the System has %d)'
+                             % (where, min(particles) if min(particles) < 0 else max(particles), len(ref)))
+        if len(set(particles)) != len(particles):
+            raise ValueError('%s: RMSDForce names particle %d twice' % (where, [p for p in particles if particles.count(p) > 1][0]))
+        rows = ref[particles]
+        if not np.all(np.isfinite(rows)):
+            raise ValueError('%s: RMSDForce has a reference position that is not finite' % where)
+        names.append(name)
+        atoms += particles
+        reference.append(rows - rows.mean(axis=0))
+        offsets.append(len(atoms))
+    return names, np.array(offsets, dtype=np.int32), np.array(atoms, dtype=np.int32), np.concatenate(reference).astype(np.float64)
+
+
+def barostat_molecules(desc):
+    """molecule number of every particle, as the engine's barostats move them (csrc/forces.hip: the components of the NonbondedForce's
+    exceptions and of the constraints, each stretched to a contiguous range of indices, interleaved ones merged).  None where the
+    System has no NonbondedForce (no table from it)."""
+    n = int(desc['n_atoms'])
+    if int(desc.get('nb_method', 0)) == 0:
+        return None
+    parent = list(range(n))
+
+    def find(a):
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        return a
+
+    def unite(a, b):
+        a, b = find(int(a)), find(int(b))
+        if a != b:
+            parent[max(a, b)] = min(a, b)
+    for i, j in np.asarray(desc['exception_atoms']).reshape(-1, 2):
+        unite(i, j)
+    for w in np.asarray(desc['settle_atoms']).reshape(-1, 3):
+        unite(w[0], w[1]); unite(w[0], w[2])
+    for c in np.asarray(desc['shake_atoms']).reshape(-1, 4):
+        for k in range(1, 4):
+            if c[k] >= 0:
+                unite(c[0], c[k])
+    hi = list(range(n))
+    for i in range(n):
+        r = find(i)
+        hi[r] = max(hi[r], i)
+    molecule = np.zeros(n, dtype=np.int64)
+    i = m = 0
+    while i < n:
+        end, k = hi[find(i)], i
+        while k <= end:
+            end = max(end, hi[find(k)])
+            k += 1
+        molecule[i:end + 1] = m
+        i, m = end + 1, m + 1
+    return molecule
+
+
+def check_cv_molecules(desc, terms):
+    """RMSDForce takes no minimum images (OpenMM's rule) while the engine's barostats wrap molecule by molecule: on a periodic System a
+    collective variable whose particles span more than one molecule is refused."""
+    periodic = int(desc.get('nb_method', 0)) in (1, 2) or any(int(t.get('nb_method', 0)) == 2 for t in terms.values())
+    if not periodic:
+        return
+    molecule = barostat_molecules(desc)
+    for t in terms.values():
+        if t['kind'] != KIND_CV:
+            continue
+        for k, name in enumerate(t['cv_names']):
+            atoms = t['cv_atoms'][t['cv_offsets'][k]:t['cv_offsets'][k + 1]]
+            if molecule is None:
+                # (periodic through a CutoffPeriodic CustomNonbondedForce alone: the barostat's molecules then come from the table the
+                # library builds from the custom bonds, csrc/custom_terms.hip, which the host does not rebuild)
+                raise NotImplementedError('CustomCVForce (energy %r): collective variable %r in a periodic System without a NonbondedForce: the '
+                                          'molecules a barostat wraps are then known to the library only, and RMSDForce takes no minimum images '
+                                          '(imaging across molecules is not supported)' % (t['energy'], name))
+            spans = len(set(molecule[atoms].tolist()))
+            if spans > 1:
+                raise NotImplementedError('CustomCVForce (energy %r): collective variable %r spans %d molecules of a periodic System: RMSDForce '
+                                          'takes no minimum images and the barostat wraps molecule by molecule (imaging across molecules is not supported)'
+                                          % (t['energy'], name, spans))
 
 
 def centroid_groups(force, masses):
@@ -766,6 +897,7 @@ def custom_terms_desc(forces, masses=None, box_vectors=None):
     group numbers and group_offsets, group_atoms, group_weights describe the groups, centroid_groups(force, masses)), params [n][p], global_names, global_defaults, program, consts,
     stack_depth, periodic, force_group, energy).  The global names and defaults are the handle's columns, the same in every entry: a
     global two forces share is one column."""
+    forces = [as_cv_force(f) for f in forces]
     if len(forces) > MAX_FORCES:
         raise NotImplementedError('%d custom forces in one System (the engine takes %d)' % (len(forces), MAX_FORCES))
     names, defaults = [], []
@@ -801,6 +933,10 @@ def custom_terms_desc(forces, masses=None, box_vectors=None):
         own = {n: columns[n] for n in (f.getGlobalParameterName(i) for i in range(f.getNumGlobalParameters()))}
         periodic = bool(f.usesPeriodicBoundaryConditions())
         n_particles = 0
+        if kind == KIND_CV:
+            cv = cv_variables(f, None if masses is None else len(masses))
+            if per_term:
+                raise ValueError('%s: a CustomCVForce has no per-term parameters (%s)' % (cls, ', '.join(per_term)))
         if kind == KIND_COMPOUND:
             n_particles = int(f.getNumParticlesPerBond())
             if not 1 <= n_particles <= MAX_PARTICLES:
@@ -809,7 +945,7 @@ def custom_terms_desc(forces, masses=None, box_vectors=None):
             n_particles = int(f.getNumGroupsPerBond())
             if not 1 <= n_particles <= MAX_PARTICLES:
                 raise NotImplementedError('%s: bonds of %d groups (the engine takes 1 ... %d)' % (cls, n_particles, MAX_PARTICLES))
-        prog = compile_expression(f.getEnergyFunction(), compound_variables(n_particles) if n_particles else VARIABLES[kind],
+        prog = compile_expression(f.getEnergyFunction(), compound_variables(n_particles) if n_particles else tuple(cv[0]) if kind == KIND_CV else VARIABLES[kind],
                                   () if kind == KIND_NONBONDED else per_term, own,
                                   where=where, tabulated=tabulated, periodic_distance=(kind == KIND_EXTERNAL and periodic),
                                   n_particles=n_particles, particle_prefix='g' if kind == KIND_CENTROID else 'p',
@@ -820,6 +956,13 @@ def custom_terms_desc(forces, masses=None, box_vectors=None):
                                       % (where, ', '.join(repr(n) for n, _ in tabulated)))
         if kind == KIND_NONBONDED:
             out['%03d' % len(out)] = _nonbonded_entry(f, cls, prog, names, defaults, per_term, masses, box_vectors)
+            continue
+        if kind == KIND_CV:
+            # one term without atoms or parameters of its own: the variables are the RMSDs (VAR 0 ... 2, CustomExternalForce's operands)
+            out['%03d' % len(out)] = dict(kind=kind, atoms=np.zeros((1, 0), dtype=np.int32), params=np.zeros((1, 0)), global_names=list(names),
+                                          global_defaults=np.array(defaults, dtype=np.float64), program=prog['program'], consts=prog['consts'],
+                                          stack_depth=prog['stack_depth'], periodic=0, force_group=int(f.getForceGroup()),
+                                          energy=f.getEnergyFunction(), cv_names=list(cv[0]), cv_offsets=cv[1], cv_atoms=cv[2], cv_reference=cv[3])
             continue
         atoms, params = f._term_arrays()
         if len(atoms) == 0:
@@ -881,6 +1024,7 @@ def custom_globals(system, names, states):
     defaults = {}
     for f in system.getForces():
         if is_custom_term_force(f):
+            f = as_cv_force(f)
             for i in range(f.getNumGlobalParameters()):
                 defaults.setdefault(f.getGlobalParameterName(i), float(f.getGlobalParameterDefaultValue(i)))
     out = np.empty((len(states), len(names)))

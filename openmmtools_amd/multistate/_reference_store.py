@@ -435,7 +435,7 @@ class ReferenceStoreWriter:
         """None when this layout can hold the objects, else what it cannot (other state classes, other moves, alchemical Systems
         outside the factory's defaults)."""
         from .. import system_xml
-        from ..custom_expr import is_custom_term_force
+        from ..custom_expr import is_custom_term_force, energy_text
         seen = set()
         for s in list(thermodynamic_states) + list(unsampled_states):
             if type(s).__name__ not in ('ThermodynamicState', 'CompoundThermodynamicState'):
@@ -444,7 +444,7 @@ class ReferenceStoreWriter:
                 if type(f).__name__ in ('MonteCarloAnisotropicBarostat', 'MonteCarloMembraneBarostat'):
                     return 'a System with a %s' % type(f).__name__
                 if is_custom_term_force(f):                 # (nor that of a custom force with an expression of its own)
-                    return 'a System with a %s (energy %r)' % (type(f).__name__, f.getEnergyFunction())
+                    return 'a System with a %s (energy %r)' % (type(f).__name__, energy_text(f))
             if (getattr(s.system, 'alchemical_region', None) is not None or getattr(s.system, 'alchemical_regions', None) is not None) and id(s.system) not in seen:
                 seen.add(id(s.system))
                 try:                                        # the factory's force set for this System (_alchemical_xml.py) or why not

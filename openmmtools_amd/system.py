@@ -581,6 +581,74 @@ class CustomCentroidBondForce(_CustomForce):
         return _term_arrays(self._bonds, self._n_groups_per_bond, len(self._per_bond), 'CustomCentroidBondForce')
 
 
+class RMSDForce(Force):
+    """openmm.RMSDForce: the root-mean-square deviation (nm, numerically kJ/mol) of ``particles`` from ``referencePositions`` after
+    the optimal superposition.  ``referencePositions`` is [N][3] for ALL particles of the System (nm, or a unit Quantity); only the
+    rows of ``particles`` are used, and an empty list means every particle.  No periodic boundary conditions (OpenMM's rule).  Meant
+    as a collective variable of a CustomCVForce; added to a System on its own it acts as CustomCVForce('v') with itself as v
+    (csrc/custom_cv.hip)."""
+
+    def __init__(self, referencePositions, particles=()):
+        super().__init__()
+        self.setReferencePositions(referencePositions)
+        self.setParticles(particles)
+
+    def getReferencePositions(self):
+        return self._reference.copy()
+
+    def setReferencePositions(self, positions):
+        from .unit import to_md
+        ref = np.array(to_md(positions), dtype=np.float64)
+        if ref.ndim != 2 or ref.shape[1] != 3:
+            raise ValueError('RMSDForce: reference positions of shape %s (one row of x, y, z per particle of the System)' % (ref.shape,))
+        self._reference = ref
+
+    def getParticles(self):
+        return list(self._particles)
+
+    def setParticles(self, particles):
+        self._particles = [int(p) for p in particles]
+
+    def usesPeriodicBoundaryConditions(self):
+        return False
+
+    def updateParametersInContext(self, context=None):
+        raise NotImplementedError('RMSDForce: changing the reference positions or the particles after set_system (updateParametersInContext) '
+                                  'is not supported: the engine keeps the reference it was given, build the states again')
+
+
+class CustomCVForce(_CustomForce):
+    """openmm.CustomCVForce: the energy an expression of collective variables, each the energy of a Force of its own, of global
+    parameters and of tabulated functions.  The engine takes one to three collective variables, each an RMSDForce
+    (csrc/custom_cv.hip); the variables keep the objects they were given, as in OpenMM."""
+
+    def __init__(self, energy):
+        super().__init__(energy)
+        self._variables = []                  # (name, force)
+
+    def addCollectiveVariable(self, name, force):
+        self._variables.append((str(name), force))
+        return len(self._variables) - 1
+
+    def getNumCollectiveVariables(self):
+        return len(self._variables)
+
+    def getCollectiveVariableName(self, index):
+        return self._variables[index][0]
+
+    def getCollectiveVariable(self, index):
+        return self._variables[index][1]
+
+    def usesPeriodicBoundaryConditions(self):
+        return False
+
+    def addEnergyParameterDerivative(self, name):
+        raise NotImplementedError('CustomCVForce: energy parameter derivatives (addEnergyParameterDerivative %r) are not supported' % (name,))
+
+    def getNumEnergyParameterDerivatives(self):
+        return 0
+
+
 class CustomExternalForce(_CustomForce):
     """openmm.CustomExternalForce: the energy a function of a particle's x, y, z, of per-particle and of global parameters.  The
     harmonic-well expression of testsystems.HarmonicOscillator (testsystems.py:779-786) keeps the engine's own kernel (ext_K / ext_x0 /
@@ -1261,6 +1329,8 @@ def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
         from .custom_expr import custom_terms_desc
         terms = custom_terms_desc(custom, system.masses, box_vectors=system.getDefaultPeriodicBoxVectors())
         if terms:
+            from .custom_expr import check_cv_molecules
+            check_cv_molecules(d, terms)
             d['custom_terms'] = terms
             # the handle's global-parameter columns, once (every entry above repeats them for remd_custom_force_desc)
             first = terms['000']

@@ -77,7 +77,7 @@ def _emit_force(forces, f, force_group=None, particles=None, exceptions=None, gl
             ET.SubElement(b, 'Exception', dict(eps=_f(eps), p1=str(i), p2=str(j), q=_f(qq), sig=_f(sig)))
     elif _is_custom_term(f):
         raise NotImplementedError('%s with the energy %r in a System document (only the HarmonicOscillator string and the restraint forms are written)'
-                                  % (name, f.getEnergyFunction()))
+                                  % (name, _energy_text(f)))
     elif isinstance(f, CustomExternalForce):
         e = ET.SubElement(forces, 'Force', dict(common, energy=f.energy_expression, version='1'))
         ET.SubElement(e, 'PerParticleParameters')
@@ -158,6 +158,11 @@ def parse_custom_gb_force(e):
     if _nonempty(e, 'Functions'):
         raise NotImplementedError('CustomGBForce: tabulated functions')
     return f
+
+
+def _energy_text(f):
+    from .custom_expr import energy_text
+    return energy_text(f)
 
 
 def _is_custom_term(f):

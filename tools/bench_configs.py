@@ -209,6 +209,43 @@ def main():
             out[name] = dict(launches_timed=n, us_per_launch=1e3 * ms / max(n, 1))
         engine.profile_enable(0)
         print(json.dumps(dict(config=tag, profile=out)), flush=True)
+    if '4rm' in which:
+        # config 4's share with one RMSD restraint (custom_expr.py kind 7, csrc/custom_cv.hip): a harmonic CustomCVForce on the RMSD of
+        # the 126 atoms of CB7 from the starting geometry, its spring constant k_rmsd rising 0 -> 2000 kJ/mol/nm^2 along the coupled half.
+        # 126 atoms because RMSDForce takes no minimum images: CB7 is the largest molecule of the System, and a variable that spans
+        # molecules is refused.  After the timed iterations one more runs with the engine's profile on for the three launches.
+        from openmmtools_amd.system import CustomCVForce, RMSDForce
+
+        class RmsdState(states.GlobalParameterState):
+            k_rmsd = states.GlobalParameterState.GlobalParameter('k_rmsd', standard_value=1.0)
+        hg = testsystems.HostGuestExplicit()
+        lam_e = np.concatenate([np.linspace(1.0, 0.0, 32), np.zeros(32)])
+        lam_s = np.concatenate([np.ones(32), np.linspace(1.0, 0.0, 32)])
+        k_r = np.concatenate([np.linspace(0.0, 2000.0, 32), np.full(32, 2000.0)])
+        asys = alchemy.AbsoluteAlchemicalFactory().create_alchemical_system(hg.system, alchemy.AlchemicalRegion(alchemical_atoms=range(126, 156)))
+        f = CustomCVForce('0.5*k_rmsd*v^2')
+        f.addGlobalParameter('k_rmsd', 2000.0)
+        f.addCollectiveVariable('v', RMSDForce(hg.positions, list(range(0, 126))))
+        asys.addForce(f)
+        ths = [states.CompoundThermodynamicState(states.ThermodynamicState(asys, 300.0),
+                                                 [states.AlchemicalState(lambda_sterics=ls, lambda_electrostatics=le), RmsdState(k_rmsd=k)])
+               for le, ls, k in zip(lam_e, lam_s, k_r)]
+        engine = HipEngine()
+        s = SAMSSampler(mcmc_moves=move(2.0, 'V R R O R R V'), number_of_iterations=10 ** 9, engine=engine, seed=1)
+        ss = states.SamplerState(hg.positions, box_vectors=hg.system.getDefaultPeriodicBoxVectors())
+        s.create(ths, [ss] * 8)
+        run('4rm (1-GPU share, RMSD restraint on the 126 atoms of CB7): HostGuestExplicit + one CustomCVForce, 8 replicas x 64 states, '
+            'g-BAOAB 2 fs x 500', s, 3)
+        engine.profile_enable(1, 'custom_cv')
+        engine.profile_reset()
+        s.run(1)
+        torch.cuda.synchronize()
+        out = {}
+        for name in ('custom_cv_superpose', 'custom_cv_expression', 'custom_cv_spread'):
+            n, ms = engine.profile_get(name)
+            out[name] = dict(launches_timed=n, us_per_launch=1e3 * ms / max(n, 1))
+        engine.profile_enable(0)
+        print(json.dumps(dict(config='4rm', profile=out)), flush=True)
     if '4cr' in which:
         # config 4's share with EVERY harmonic bond, harmonic angle and periodic torsion of the System moved to custom forces with the
         # same formulas (custom_expr.py): what the expression machine costs at a force field's size, against the built-in listed terms of '4'
