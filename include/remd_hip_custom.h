@@ -1,6 +1,6 @@
 /*
  * remd_hip_custom.h — GPU-only extension of the C ABI in remd_hip.h: custom bond, angle, torsion, external, compound-bond,
- * centroid-bond, nonbonded and collective-variable forces.
+ * centroid-bond, nonbonded and collective-variable forces, and CMAP torsion maps.
  *
  * OpenMM's CustomBondForce, CustomAngleForce, CustomTorsionForce and CustomExternalForce: an energy expression of r (bond), theta
  * (angle, torsion) or x, y, z (external), of per-term parameters and of global parameters, evaluated per term.  The host compiles
@@ -57,6 +57,24 @@
  * gives particle i of variable k -(dE/dV_k) (x_i - c - U ref_i) / (n V_k); a mean square deviation below 1e-20 nm^2 gives V = 0 and no
  * force from that variable (csrc/custom_cv.hip).  remd_get_custom_cv_values reads the RMSDs back.
  *
+ * CMAP torsion forces (REMD_CUSTOM_CMAP, OpenMM's CMAPTorsionForce): a term is two dihedrals, phi of the particles atoms[k][0 ... 3] and
+ * psi of atoms[k][4 ... 7] (n_particles = 8; the two quadruples usually share particles), each in (-pi, pi] with the sign convention
+ * of REMD_CUSTOM_TORSION and of REMD_CX_DIHEDRAL, and its energy is map map_index[k] of the force at (phi, psi).  A map is OpenMM's:
+ * size x size energies in kJ/mol, energy[i + size j] at phi = 2 pi i / size and psi = 2 pi j / size, periodic in both angles, and
+ * between the nodes the bicubic patch whose node derivatives come from periodic cubic splines (fx along phi, fy along psi, fxy from
+ * the spline of fx along psi: OpenMM's CMAPTorsionForceImpl::calcMapDerivatives).  That is exactly a periodic REMD_CX_TABLE2D block (below) over
+ * [0, 2 pi] x [0, 2 pi] with nx = ny = size + 1, the first row and column repeated at the end, and such blocks are what the force
+ * carries: consts holds the n_maps blocks back to back and map_offsets[m] is the offset of map m's.  The angles are wrapped by the
+ * block's periodic rule.  The force has no program, no per-term parameters and no globals of its own (n_program = 0, n_params = 0,
+ * stack_depth ignored; n_globals and global_defaults are the handle's, like every descriptor's).  periodic != 0: every difference inside
+ * a dihedral is a minimum image.  Degenerate geometry follows REMD_CX_DIHEDRAL: |b1 x b2|^2 and |b2 x b3|^2 are taken as at least
+ * 1e-24 nm^4, so three collinear particles give a finite angle (atan2 of zeros) and finite gradients: the one on the end particle of
+ * the collinear triple falls to zero with the cross product, the others keep their formulas.
+ * One lane per term, the geometry once, the map picked by index (csrc/cmap.hip); its energy is a column of remd_get_custom_energies
+ * and joins the replica's potential; having no globals it adds nothing of its own to the u_kl rows.  remd_set_custom_terms checks the
+ * atoms, every map_index and every block's header (nx = ny an integer 3 ... 256, periodic, the range [0, 2 pi], its end inside
+ * consts, finite nodes).
+ *
  * Tabulated functions (OpenMM's Continuous1DFunction and Discrete1DFunction) of every kind above: REMD_CX_TABLE1D and
  * REMD_CX_LOOKUP1D take one argument x from the stack and push one result; the operand is the offset of the function's block in the
  * force's constants.  The blocks follow the scalar constants, one per function:
@@ -107,7 +125,8 @@
  * and NaN where any index falls outside its range.  No arguments make the device load outside the block.
  *
  * Not provided: Continuous3DFunction, changing a table or a reference after remd_set_custom_terms, pointangle, pointdihedral, interaction
- * groups, collective variables other than the RMSD, a weighted RMSD, energy parameter derivatives.
+ * groups, collective variables other than the RMSD, a weighted RMSD, energy parameter derivatives, changing a map or a torsion pair
+ * after remd_set_custom_terms.
  *
  * Global parameters belong to the handle: every force's program addresses the same n_globals columns, and every state carries one
  * value per column (remd_set_custom_globals).  A term acts in every force evaluation (MD steps, energies, the barostat,
@@ -118,7 +137,8 @@
  * REMD_CUSTOM_MAX_PARAMS parameters per term, REMD_CUSTOM_MAX_GLOBALS global columns per handle, REMD_CUSTOM_MAX_FORCES forces
  * per handle (of all kinds together), REMD_CUSTOM_MAX_PARTICLES particles per compound bond or groups per centroid bond,
  * REMD_CUSTOM_MAX_TABLE_POINTS points per tabulated function of one argument, REMD_CUSTOM_MAX_TABLE_CELLS values per tabulated
- * function of two or three, REMD_CUSTOM_MAX_CVS collective variables per collective-variable force.
+ * function of two or three, REMD_CUSTOM_MAX_CVS collective variables per collective-variable force,
+ * REMD_CUSTOM_MAX_MAPS maps per CMAP force (each of at most 255 x 255 energies: (size + 1)^2 <= REMD_CUSTOM_MAX_TABLE_CELLS).
  *
  * These entry points are declared here and not in remd_hip.h because the CPU port of the ABI does not provide them: a host binds
  * them only where the loaded library exports them.  Conventions as in remd_hip.h.
@@ -142,6 +162,8 @@ extern "C" {
 
 #define REMD_CUSTOM_CV       7     /* atoms NULL, n_terms = 1; variables the RMSDs of the force's collective variables            */
 
+#define REMD_CUSTOM_CMAP     8     /* atoms [n][8] (n_particles = 8): two dihedrals; the energy is map map_index[k] at them; no program */
+
 #define REMD_CUSTOM_MAX_PROGRAM 256
 #define REMD_CUSTOM_MAX_STACK   16
 #define REMD_CUSTOM_MAX_PARAMS  16
@@ -149,6 +171,7 @@ extern "C" {
 #define REMD_CUSTOM_MAX_FORCES  8
 #define REMD_CUSTOM_MAX_PARTICLES 8
 #define REMD_CUSTOM_MAX_CVS   3
+#define REMD_CUSTOM_MAX_MAPS  64
 #define REMD_CUSTOM_MAX_TABLE_POINTS 8192   /* points of one tabulated function of one argument                               */
 #define REMD_CUSTOM_MAX_TABLE_CELLS 65536   /* nx ny (nz) of one tabulated function of two or three arguments                  */
 
@@ -231,6 +254,10 @@ typedef struct remd_custom_force_desc {
     const int32_t* cv_offsets;     /* [n_cvs + 1]: variable k holds cv_atoms[cv_offsets[k] ... cv_offsets[k + 1]), at least 3 */
     const int32_t* cv_atoms;       /* particle indices, 0 ... N - 1, none twice within a variable                          */
     const double* cv_reference;    /* beside cv_atoms, [.][3] nm: each variable's rows centred on their own centroid       */
+    /* REMD_CUSTOM_CMAP only (every other kind ignores them)                                                              */
+    const int32_t* map_index;      /* [n_terms]: the map of every term, 0 ... n_maps - 1                                   */
+    int32_t n_maps;                /* the force's maps, 1 ... REMD_CUSTOM_MAX_MAPS                                         */
+    const int32_t* map_offsets;    /* [n_maps]: the offset in consts of each map's block ([nx, ny, 0, 2 pi, 0, 2 pi, 1, 0], node[ny][nx][4]) */
 } remd_custom_force_desc;
 
 /* the custom forces of the system; call after remd_set_system (which forgets them).  n = 0: none.  Every custom force of a handle

@@ -82,6 +82,12 @@ class RemdCustomForceDesc(C.Structure):
                 ('n_cvs', C.c_int32), ('cv_offsets', c_int32_p), ('cv_atoms', c_int32_p), ('cv_reference', c_double_p)]
 
 
+class RemdCustomForceDescCMAP(RemdCustomForceDesc):
+    """remd_custom_force_desc as remd_set_custom_terms takes it: the fields above, then those REMD_CUSTOM_CMAP appended at the end of
+    the struct (a ctypes subclass lays its own fields out behind the base's, as C does behind a pointer member)"""
+    _fields_ = [('map_index', c_int32_p), ('n_maps', C.c_int32), ('map_offsets', c_int32_p)]
+
+
 class RemdGbModelDesc(C.Structure):
     """remd_gb_model_desc of include/remd_hip_gb.h (the constants and the cutoff of an OBC-family implicit-solvent model)."""
     _fields_ = [('offset', C.c_double), ('alpha', C.c_double), ('beta', C.c_double), ('gamma', C.c_double), ('ke', C.c_double),
@@ -217,7 +223,7 @@ def load_library(path=None):
         for name in RESTRAINT_FRAMES_EXPORTS:
             getattr(lib, name).restype = C.c_int
     if hasattr(lib, 'remd_set_custom_terms'):             # include/remd_hip_custom.h (GPU-only, like the restraints)
-        lib.remd_set_custom_terms.argtypes = [vp, C.POINTER(RemdCustomForceDesc), C.c_int]
+        lib.remd_set_custom_terms.argtypes = [vp, C.POINTER(RemdCustomForceDescCMAP), C.c_int]
         lib.remd_set_custom_globals.argtypes = [vp, c_double_p]
         lib.remd_set_custom_lrc.argtypes = [vp, c_double_p]
         lib.remd_get_custom_energies.argtypes = [vp, c_double_p]
@@ -598,7 +604,7 @@ class HipEngine:
     def _custom_entry(self, name):
         if not hasattr(self.lib, name):
             raise NotImplementedError('%s: this build of the engine library has no custom bond / angle / torsion / external forces and no compound-bond forces, '
-                                      'centroid-bond forces or nonbonded custom forces (include/remd_hip_custom.h is GPU-only)' % name)
+                                      'centroid-bond forces or nonbonded custom forces, nor CMAP torsion forces (include/remd_hip_custom.h is GPU-only)' % name)
         return getattr(self.lib, name)
 
     def set_custom_terms(self, terms):
@@ -607,7 +613,7 @@ class HipEngine:
         n_cv = sum(len(t['cv_offsets']) - 1 for t in terms if 'cv_offsets' in t)
         if n_cv:
             self._custom_cv_entry('remd_get_custom_cv_values')
-        arr = (RemdCustomForceDesc * max(1, len(terms)))()
+        arr = (RemdCustomForceDescCMAP * max(1, len(terms)))()
         keep = []
         for k, t in enumerate(terms):
             atoms = np.ascontiguousarray(t['atoms'], dtype=np.int32)
@@ -644,10 +650,18 @@ class HipEngine:
                 keep += [c_off, c_atoms, c_ref]
                 cvs = (len(c_off) - 1, _ip(c_off), _ip(c_atoms), _dp(c_ref))
                 n_terms = 1
+            maps = (None, 0, None)
+            if 'map_index' in t:                                     # a CMAP force: atoms [n][8], the maps' blocks in consts
+                m_index = np.ascontiguousarray(t['map_index'], dtype=np.int32)
+                m_off = np.ascontiguousarray(t['map_offsets'], dtype=np.int32)
+                if len(m_index) != n_terms:
+                    raise ValueError('set_custom_terms: map_index must hold one map per term (%d, not %d)' % (n_terms, len(m_index)))
+                keep += [m_index, m_off]
+                maps = (_ip(m_index), len(m_off), _ip(m_off))
             no_atoms = nonbonded or 'cv_offsets' in t
-            arr[k] = RemdCustomForceDesc(int(t['kind']), n_terms, None if no_atoms else _ip(atoms), params.shape[1], _dp(params), len(program), _ip(program),
+            arr[k] = RemdCustomForceDescCMAP(int(t['kind']), n_terms, None if no_atoms else _ip(atoms), params.shape[1], _dp(params), len(program), _ip(program),
                                          len(consts), _dp(consts), int(t['stack_depth']), len(defaults), _dp(defaults),
-                                         int(t['periodic']), int(t['force_group']), n_particles, *groups, *pairs, *cvs)
+                                         int(t['periodic']), int(t['force_group']), n_particles, *groups, *pairs, *cvs, *maps)
         self._check(fn(self.h, arr, len(terms)), 'remd_set_custom_terms')
         self.n_custom = len(terms)
         self.n_custom_cvs = n_cv

@@ -1,6 +1,8 @@
 // The stack machine of the custom forces (include/remd_hip_custom.h), shared by custom_terms.hip (bond, angle, torsion, external),
-// custom_compound.hip (compound bonds) and custom_centroid.hip (centroid bonds, whose particles are centroids) and custom_cv.hip (collective variables, whose variables are RMSDs): the per-force record, the handle's tables, and cst_eval, which runs a postfix program
-// one term per lane with every stack slot a value and three partials, the stack in LDS as [slot][component][lane].
+// custom_compound.hip (compound bonds), custom_centroid.hip (centroid bonds, whose particles are centroids) and custom_cv.hip
+// (collective variables, whose variables are RMSDs): the per-force record, the handle's tables, and cst_eval, which runs a postfix
+// program one term per lane with every stack slot a value and three partials, the stack in LDS as [slot][component][lane].
+// cmap.hip (CMAP torsion maps) runs no program: it shares the record, the tables and the patch of two arguments (table2d_patch.h).
 //
 // cst_eval<GEOM>: the instantiation of the four one-variable kinds (GEOM = false) has the variables in three registers and no case
 // for the opcodes of particles; the one of a compound-bond force (GEOM = true) reads the variables x1 y1 z1 ... from the lane's
@@ -13,6 +15,7 @@
 #pragma once
 #include "remd_internal.h"
 #include "../../include/remd_hip_custom.h"
+#include "table2d_patch.h"
 
 struct cst_force {
     int kind, periodic, n_terms, n_params;
@@ -27,13 +30,16 @@ struct cst_force {
     double cutoff, switch_dist;  // switch_dist < 0: no switching function
     // REMD_CUSTOM_CV only (custom_cv.hip): n_terms = 1, npad = 64, no atoms of its own
     int cv0, n_cvs;              // its first collective variable among the handle's, and how many it has (1 ... 3)
+    // REMD_CUSTOM_CMAP only (cmap.hip): n_particles = 8, no program and no parameters; its constants are its maps' blocks
+    int map0, n_maps;            // its first map among the handle's map_off, and how many it has (1 ... REMD_CUSTOM_MAX_MAPS)
 };
 
 struct cst_tables {
     int nf = 0, ng = 0, K = 0, total_pad = 0, waves_simple = 0; long long glob_version = -1;   // (waves_simple: the wavefronts of the four one-variable kinds, in front; glob belongs to the states of that remd_set_states)
     int waves_compound = 0;                                                    // where the compound-bond forces' wavefronts end and the nonbonded forces' tiles begin
     int waves_particles = 0;                                                   // where the nonbonded forces' tiles end and the centroid forces' wavefronts begin
-    int waves_centroid = 0;                                                    // where the centroid forces' wavefronts end and the collective-variable forces' begin (the last part)
+    int waves_centroid = 0;                                                    // where the centroid forces' wavefronts end and the collective-variable forces' begin
+    int waves_cv = 0;                                                          // where the collective-variable forces' wavefronts end and the CMAP forces' begin (the last part)
     int n_cv = 0;                                                              // the collective variables of all such forces (0: no such force, none of the cv members below holds anything)
     int n_groups = 0;                                                          // the groups of all centroid forces (0: no centroid force, none of the members below holds anything)
     bool uniform = true;                                                       // every state carries the same globals: no u_kl share
@@ -58,6 +64,10 @@ struct cst_tables {
     dev_array<int> d_cv_atoms;         // the variables' particles
     dev_array<double> d_cv_ref;        // beside cv_atoms, [.][3]: the reference, centred on each variable's own centroid
     dev_array<double> d_W;             // [R][n_cv][16]: RMSD, "no force" flag, centroid, rotation, dE/dRMSD (custom_cv.hip)
+    // CMAP forces (cmap.hip): the maps of all of them and the map of every slot of their part of the padded term space
+    std::vector<int> map_off, map_index;
+    dev_array<int> d_map_off;          // per map the offset of its block in consts (cst_force::map0 names a force's first)
+    dev_array<int> d_map_index;        // [total_pad - 64 waves_cv]: the slot's map among its force's, 0 ... n_maps - 1 (a padding slot repeats the last term's)
     // nonbonded forces (custom_nonbonded.hip): the exclusion rows of all of them, and the long-range coefficients of the states
     std::vector<int> excl_off, excl_atoms; std::vector<double> lrc;
     dev_array<int> d_excl_off;         // per nonbonded force N + 1 offsets into excl_atoms (cst_force::excl0 names the first)
@@ -185,58 +195,7 @@ __device__ __forceinline__ double cst_lookup1d(const double* __restrict__ B, dou
     return v;
 }
 
-// One argument of REMD_CX_TABLE2D on its axis of n nodes over [lo, hi] with spacing h, by the rules of cst_table1d: the wrap of a
-// periodic function, the range test in f64, then the patch index (clamped again) and the offset u = (t - min) / h - i in the patch.
-// Returns whether the argument lies inside; `nan` whether it is a NaN (an infinite argument of a periodic function wraps to one).
-__device__ __forceinline__ bool cst_table_axis(int n, double lo, double hi, double h, bool periodic, double x, int& i, double& u, bool& nan)
-{
-    const double L = hi - lo;
-    const double w = x - L * floor((x - lo) / L);
-    const double t = periodic ? (w < lo ? lo : w > hi ? hi : w) : x;
-    const bool inside = t >= lo && t <= hi;
-    const double s = inside ? (t - lo) / h : 0.0;
-    i = min(max((int)s, 0), n - 2);
-    u = s - (double)i;
-    nan = t != t;
-    return inside;
-}
-
-// REMD_CX_TABLE2D (include/remd_hip_custom.h): the bicubic Hermite patch of the block [nx, ny, xmin, xmax, ymin, ymax, periodic, 0],
-// node[ny][nx][4] = (f, fx, fy, fxy), with its two partials kx = dF/dx, ky = dF/dy.  The sixteen terms are summed row by row: the two
-// corners (j + b, i) and (j + b, i + 1) of a row are 64 contiguous bytes, one access of the memory system's granularity, and only
-// their eight numbers are live beside the row's four sums -- sixteen loads in flight at once would not fit beside the stack machine's
-// state in the nonbonded tile kernel.  Along x a row gives P = sum_a h0a(u) f_a + hx h1a(u) fx_a and Q, the same of (fy, fxy), with
-// their u-derivatives; along y, F = sum_b h0b(w) P_b + hy h1b(w) Q_b.  A lane whose arguments are not both inside loads nothing and
-// pushes 0, or NaN where either argument is a NaN (the discipline of cst_table1d, per argument).
-__device__ __forceinline__ void cst_table2d(const double* __restrict__ B, double x, double y, double& v, double& kx, double& ky)
-{
-    const int nx = (int)B[0], ny = (int)B[1];                 // 2 ..., nx ny <= REMD_CUSTOM_MAX_TABLE_CELLS
-    const double hx = (B[3] - B[2]) / (double)(nx - 1), hy = (B[5] - B[4]) / (double)(ny - 1);
-    const bool periodic = B[6] != 0.0;
-    int i, j; double u, w; bool nanx, nany;
-    const bool inx = cst_table_axis(nx, B[2], B[3], hx, periodic, x, i, u, nanx);
-    const bool iny = cst_table_axis(ny, B[4], B[5], hy, periodic, y, j, w, nany);
-    v = nanx || nany ? __builtin_nan("") : 0.0; kx = 0.0; ky = 0.0;
-    if (inx && iny) {
-        const double u2 = u * u, u3 = u2 * u, w2 = w * w, w3 = w2 * w;
-        // h00, h01, hx h10, hx h11 at u and their u-derivatives (the latter still to be divided by hx)
-        const double a0 = 2.0 * u3 - 3.0 * u2 + 1.0, a1 = 3.0 * u2 - 2.0 * u3, a2 = hx * (u3 - 2.0 * u2 + u), a3 = hx * (u3 - u2);
-        const double d0 = 6.0 * (u2 - u), d2 = hx * (3.0 * u2 - 4.0 * u + 1.0), d3 = hx * (3.0 * u2 - 2.0 * u);      // d1 = -d0
-        double F = 0.0, Fu = 0.0, Fw = 0.0;
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const double* __restrict__ c = B + 8 + 4 * ((j + b) * nx + i);        // (f, fx, fy, fxy) of corner i, then of corner i + 1
-            const double P = a0 * c[0] + a1 * c[4] + a2 * c[1] + a3 * c[5], Q = a0 * c[2] + a1 * c[6] + a2 * c[3] + a3 * c[7];
-            const double dP = d0 * (c[0] - c[4]) + d2 * c[1] + d3 * c[5], dQ = d0 * (c[2] - c[6]) + d2 * c[3] + d3 * c[7];
-            const double e0 = b ? 3.0 * w2 - 2.0 * w3 : 2.0 * w3 - 3.0 * w2 + 1.0, e1 = hy * (b ? w3 - w2 : w3 - 2.0 * w2 + w);
-            const double g0 = b ? -6.0 * (w2 - w) : 6.0 * (w2 - w), g1 = hy * (b ? 3.0 * w2 - 2.0 * w : 3.0 * w2 - 4.0 * w + 1.0);
-            F += e0 * P + e1 * Q;
-            Fu += e0 * dP + e1 * dQ;
-            Fw += g0 * P + g1 * Q;
-        }
-        v = F; kx = Fu / hx; ky = Fw / hy;
-    }
-}
+// cst_table_axis and cst_table2d, the bicubic Hermite patch of REMD_CX_TABLE2D, live in table2d_patch.h: cmap.hip evaluates the same patch.
 
 // values[round(x) + nx round(y)] of the block [nx, ny], values[ny][nx]; NaN, and no load, where an index falls outside its range
 __device__ __forceinline__ double cst_lookup2d(const double* __restrict__ B, double x, double y)
@@ -397,6 +356,8 @@ void remd_custom_centroid_ukl(remd_ctx* h, cst_tables& t);
 void remd_custom_cv_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
 void remd_custom_cv_ukl(remd_ctx* h, cst_tables& t);
 size_t remd_custom_cv_w();             // doubles per (replica, variable) of cst_tables::d_W; the RMSD is the first
+// cmap.hip: the force launch of the CMAP forces' wavefronts (those behind waves_cv); they have no globals, so no u_kl launch
+void remd_cmap_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
 // custom_nonbonded.hip: the same for the nonbonded forces' tiles (those between waves_compound and waves_particles), and the long-range
 // correction's share of the energies (behind custom_reduce_kernel) and of the u_kl rows (behind custom_ukl_reduce_kernel)
 void remd_custom_nonbonded_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);

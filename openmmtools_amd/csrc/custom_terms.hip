@@ -27,7 +27,8 @@
 // wavefronts follow the ones of this file's four kinds in the padded term space and share the energy and u_kl reductions below, and
 // custom_centroid.hip runs it for CustomCentroidBondForce, whose wavefronts come last; custom_nonbonded.hip runs it for
 // CustomNonbondedForce, one wavefront per tile of 64 x 64 atoms, between those two; custom_cv.hip runs it for CustomCVForce, one
-// wavefront per force behind the centroid forces', its variables the RMSDs a launch of its own computed.
+// wavefront per force behind the centroid forces', its variables the RMSDs a launch of its own computed.  cmap.hip (CMAPTorsionForce)
+// comes last and runs no program: it shares the term space, the tables and the energy reduction only.
 #include "remd_internal.h"
 #include "listed_terms.h"
 #include "custom_machine.h"
@@ -214,7 +215,8 @@ int set_tables(remd_ctx* h, cst_tables& t)
         (rc = t.d_grp_w.upload(h, t.grp_w)) || (rc = t.d_grp_periodic.upload(h, t.grp_periodic)) || (rc = t.d_ref_off.upload(h, t.ref_off)) ||
         (rc = t.d_refs.upload(h, t.refs)) || (rc = t.d_excl_off.upload(h, t.excl_off)) || (rc = t.d_excl_atoms.upload(h, t.excl_atoms)) ||
         (rc = t.d_lrc.upload(h, t.lrc)) || (rc = t.d_mol_first.upload(h, t.mol_first)) || (rc = t.d_mol_size.upload(h, t.mol_size)) ||
-        (rc = t.d_cv_off.upload(h, t.cv_off)) || (rc = t.d_cv_atoms.upload(h, t.cv_atoms)) || (rc = t.d_cv_ref.upload(h, t.cv_ref))) return rc;
+        (rc = t.d_cv_off.upload(h, t.cv_off)) || (rc = t.d_cv_atoms.upload(h, t.cv_atoms)) || (rc = t.d_cv_ref.upload(h, t.cv_ref)) ||
+        (rc = t.d_map_off.upload(h, t.map_off)) || (rc = t.d_map_index.upload(h, t.map_index))) return rc;
     t.d_E.reset(); t.d_Ewave.reset(); t.d_D.reset(); t.d_C.reset(); t.d_G.reset(); t.d_W.reset();
     return 0;
 }
@@ -333,6 +335,7 @@ int remd_custom_clone(remd_ctx* parent, remd_ctx* child)
     c.excl_off = t->excl_off; c.excl_atoms = t->excl_atoms; c.lrc = t->lrc; c.has_lrc = t->has_lrc; c.lrc_valid = t->lrc_valid; c.periodic_cutoff = t->periodic_cutoff;
     c.mol_first = t->mol_first; c.mol_size = t->mol_size;
     c.waves_centroid = t->waves_centroid; c.n_cv = t->n_cv; c.cv_off = t->cv_off; c.cv_atoms = t->cv_atoms; c.cv_ref = t->cv_ref;
+    c.waves_cv = t->waves_cv; c.map_off = t->map_off; c.map_index = t->map_index;
     c.grp_off = t->grp_off; c.grp_atoms = t->grp_atoms; c.grp_w = t->grp_w; c.grp_periodic = t->grp_periodic; c.ref_off = t->ref_off; c.refs = t->refs;
     c.glob_version = t->glob_version == parent->states_version ? child->states_version : -1;
     c.F = t->F; c.wave_force = t->wave_force; c.atoms = t->atoms; c.par = t->par; c.consts = t->consts; c.glob = t->glob;
@@ -371,7 +374,8 @@ int remd_custom_forces(remd_ctx* h, bool with_energy, int ep_slot, hipStream_t s
     if (t.waves_compound > t.waves_simple) remd_custom_compound_forces(h, t, with_energy, st);    // (custom_compound.hip: the wavefronts behind)
     if (t.waves_particles > t.waves_compound) remd_custom_nonbonded_forces(h, t, with_energy, st); // (custom_nonbonded.hip: the tiles behind those)
     if (t.waves_centroid > t.waves_particles) remd_custom_centroid_forces(h, t, with_energy, st);  // (custom_centroid.hip: behind those)
-    if (waves > t.waves_centroid) remd_custom_cv_forces(h, t, with_energy, st);                    // (custom_cv.hip: the last ones)
+    if (t.waves_cv > t.waves_centroid) remd_custom_cv_forces(h, t, with_energy, st);               // (custom_cv.hip: behind those)
+    if (waves > t.waves_cv) remd_cmap_forces(h, t, with_energy, st);                               // (cmap.hip: the last ones)
     if (with_energy)
         hipLaunchKernelGGL(custom_reduce_kernel, dim3(h->R), dim3(64), 0, st, t.nf, t.d_F, waves, t.d_Ewave, t.d_E, h->d_epart, h->n_epart, ep_slot);
     if (with_energy && t.has_lrc) remd_custom_nonbonded_lrc(h, t, ep_slot, st);
@@ -392,7 +396,11 @@ int remd_custom_ukl(remd_ctx* h, double* d_rows)
     if (t.uniform) return 0;                          // every state carries the same globals: the share is exactly zero
     const int waves = t.total_pad / 64;
     const size_t nD = (size_t)h->R * h->K * waves;
-    if (t.d_D.size() != nD) REMD_TRY(t.d_D.alloc(h, nD));
+    if (t.d_D.size() != nD) {
+        // (the CMAP forces' wavefronts have no globals and no u_kl launch: their columns are zeroed here, once, and nothing writes them)
+        REMD_TRY(t.d_D.alloc(h, nD));
+        if (waves > t.waves_cv) REMD_CHECK(h, hipMemsetAsync(t.d_D, 0, sizeof(double) * nD, h->stream));
+    }
     remd_prof_scope ps(h, "custom_ukl");
     if (t.waves_simple > 0)
         hipLaunchKernelGGL(custom_ukl_kernel, dim3(t.waves_simple, h->R), dim3(64), 0, h->stream, t.total_pad, waves, t.d_F, t.d_wave_force,
@@ -400,7 +408,7 @@ int remd_custom_ukl(remd_ctx* h, double* d_rows)
     if (t.waves_compound > t.waves_simple) remd_custom_compound_ukl(h, t);
     if (t.waves_particles > t.waves_compound) remd_custom_nonbonded_ukl(h, t);
     if (t.waves_centroid > t.waves_particles) remd_custom_centroid_ukl(h, t);
-    if (waves > t.waves_centroid) remd_custom_cv_ukl(h, t);
+    if (t.waves_cv > t.waves_centroid) remd_custom_cv_ukl(h, t);
     hipLaunchKernelGGL(custom_ukl_reduce_kernel, dim3(h->K, h->R), dim3(64), 0, h->stream, h->K, waves, t.d_D, h->d_beta, d_rows);
     if (t.has_lrc) remd_custom_nonbonded_lrc_ukl(h, t, d_rows);
     REMD_CHECK(h, hipGetLastError());
@@ -426,12 +434,13 @@ int remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, int
     for (int i = 0; i < n; ++i) {
         const remd_custom_force_desc& d = desc[i];
         const std::string who = "remd_set_custom_terms: force " + std::to_string(i) + ": ";
-        if (d.kind < 0 || d.kind > REMD_CUSTOM_CV) return remd_fail(h, -1, who + "unknown kind");
-        const bool nonbonded = d.kind == REMD_CUSTOM_NONBONDED, cv = d.kind == REMD_CUSTOM_CV;
+        if (d.kind < 0 || d.kind > REMD_CUSTOM_CMAP) return remd_fail(h, -1, who + "unknown kind");
+        const bool nonbonded = d.kind == REMD_CUSTOM_NONBONDED, cv = d.kind == REMD_CUSTOM_CV, cmap = d.kind == REMD_CUSTOM_CMAP;
         const bool centroid = d.kind == REMD_CUSTOM_CENTROID, compound = d.kind == REMD_CUSTOM_COMPOUND || centroid;
-        if (compound ? (d.n_particles < 1 || d.n_particles > REMD_CUSTOM_MAX_PARTICLES) : d.n_particles != 0)
+        if (cmap && d.n_particles != 8) return remd_fail(h, -1, who + "n_particles is 8 for a CMAP force (two dihedrals of four particles)");
+        if (!cmap && (compound ? (d.n_particles < 1 || d.n_particles > REMD_CUSTOM_MAX_PARTICLES) : d.n_particles != 0))
             return remd_fail(h, -1, who + "n_particles is 1 ... REMD_CUSTOM_MAX_PARTICLES for a compound-bond or centroid-bond force and 0 for every other kind");
-        const int wd = compound ? d.n_particles : (nonbonded || cv) ? 0 : width4[d.kind];
+        const int wd = compound ? d.n_particles : cmap ? 8 : (nonbonded || cv) ? 0 : width4[d.kind];
         if (d.n_terms <= 0 || (!d.atoms && !nonbonded && !cv)) return remd_fail(h, -1, who + "no terms");
         if (d.n_params < 0 || d.n_params > REMD_CUSTOM_MAX_PARAMS || (d.n_params > 0 && !d.params))
             return remd_fail(h, -1, who + "0 ... REMD_CUSTOM_MAX_PARAMS parameters per term are supported");
@@ -484,11 +493,32 @@ int remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, int
                     if (!(fabs(m[x]) <= 1e-9 * (e - b))) return remd_fail(h, -1, who + "collective variable " + std::to_string(c) + ": the reference must be centred on its own centroid (within 1e-9 nm)");
             }
         }
+        if (cmap) {
+            // what cmap.hip indexes unchecked: every term's map, every map's block (the header cst_table2d trusts, and its extent)
+            if (d.n_params != 0 || d.n_program != 0) return remd_fail(h, -1, who + "a CMAP force has no per-term parameters and no program");
+            if (d.n_maps < 1 || d.n_maps > REMD_CUSTOM_MAX_MAPS) return remd_fail(h, -1, who + "a CMAP force has 1 ... REMD_CUSTOM_MAX_MAPS maps");
+            if (!d.map_index || !d.map_offsets || !d.consts || d.n_consts <= 0) return remd_fail(h, -1, who + "a CMAP force needs map_index, map_offsets and the maps' blocks in consts");
+            for (int k = 0; k < d.n_terms; ++k)
+                if (d.map_index[k] < 0 || d.map_index[k] >= d.n_maps) return remd_fail(h, -1, who + "term " + std::to_string(k) + ": map index out of range");
+            for (int m = 0; m < d.n_maps; ++m) {
+                const std::string map = who + "map " + std::to_string(m) + ": ";
+                const long long off = d.map_offsets[m];
+                if (off < 0 || off + 8 > (long long)d.n_consts) return remd_fail(h, -1, map + "a block that runs past n_consts");
+                const double* B = d.consts + off;
+                if (!(B[0] >= 3.0 && B[0] <= 256.0) || B[0] != floor(B[0]) || B[1] != B[0]) return remd_fail(h, -1, map + "a block whose sizes are not nx = ny, an integer 3 ... 256");
+                if (B[6] != 1.0) return remd_fail(h, -1, map + "a block that is not periodic");
+                if (B[2] != 0.0 || B[4] != 0.0 || !(fabs(B[3] - 2.0 * M_PI) <= 1e-12) || B[5] != B[3]) return remd_fail(h, -1, map + "a block whose range is not [0, 2 pi] in both angles");
+                const long long nn = (long long)B[0];
+                if (off + 8 + 4 * nn * nn > (long long)d.n_consts) return remd_fail(h, -1, map + "a block that runs past n_consts");
+                for (long long k = 0; k < 4 * nn * nn; ++k) if (!std::isfinite(B[8 + k])) return remd_fail(h, -1, map + "a node value that is not finite");
+            }
+        }
         if (d.n_globals != t.ng) return remd_fail(h, -1, who + "every descriptor must carry the handle's n_globals");
         for (int k = 0; k < t.ng; ++k) if (d.global_defaults && d.global_defaults[k] != t.defaults[k]) return remd_fail(h, -1, who + "global_defaults differ between the descriptors");
         if (d.force_group != desc[0].force_group || d.force_group < 0 || d.force_group > 31)
             return remd_fail(h, -1, who + "every custom force of a handle must sit in one force group (0 ... 31)");
-        if (const char* bad = check_program(d, compound ? 3 * d.n_particles : nonbonded ? 1 : cv ? d.n_cvs : n_vars4[d.kind])) return remd_fail(h, -1, who + bad);
+        if (!cmap)       // (a CMAP force has no program)
+            if (const char* bad = check_program(d, compound ? 3 * d.n_particles : nonbonded ? 1 : cv ? d.n_cvs : n_vars4[d.kind])) return remd_fail(h, -1, who + bad);
         if (centroid) {
             // the groups: CSR offsets that start at 0 and increase (no empty group), atoms of the system, weights that sum to 1
             if (d.n_groups <= 0 || !d.group_offsets || !d.group_atoms || !d.group_weights) return remd_fail(h, -1, who + "a centroid-bond force needs n_groups > 0, group_offsets, group_atoms and group_weights");
@@ -541,15 +571,20 @@ int remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, int
             t.cv_ref.insert(t.cv_ref.end(), d.cv_reference, d.cv_reference + 3 * (size_t)total);
             t.n_cv += d.n_cvs;
         }
+        if (cmap) {
+            // its maps join the handle's: each block's offset in the handle's constants
+            f.map0 = (int)t.map_off.size(); f.n_maps = d.n_maps;
+            for (int m = 0; m < d.n_maps; ++m) t.map_off.push_back(f.const0 + d.map_offsets[m]);
+        }
         t.F.push_back(f);
     }
     // the padded term space: the four one-variable kinds first, the compound-bond forces behind them, then the nonbonded forces' tiles,
-    // the centroid-bond forces, the collective-variable forces last (each part has its own kernel); the energy columns keep the forces'
-    // order whatever their slots
-    for (int pass = 0; pass < 5; ++pass) {
+    // the centroid-bond forces, the collective-variable forces, the CMAP forces last (each part has its own kernel); the energy columns
+    // keep the forces' order whatever their slots
+    for (int pass = 0; pass < 6; ++pass) {
         for (int i = 0; i < n; ++i) {
             cst_force& f = t.F[i];
-            if ((f.kind == REMD_CUSTOM_CV ? 4 : f.kind == REMD_CUSTOM_CENTROID ? 3 : f.kind == REMD_CUSTOM_NONBONDED ? 2 : f.kind == REMD_CUSTOM_COMPOUND ? 1 : 0) != pass) continue;
+            if ((f.kind == REMD_CUSTOM_CMAP ? 5 : f.kind == REMD_CUSTOM_CV ? 4 : f.kind == REMD_CUSTOM_CENTROID ? 3 : f.kind == REMD_CUSTOM_NONBONDED ? 2 : f.kind == REMD_CUSTOM_COMPOUND ? 1 : 0) != pass) continue;
             f.slot0 = t.total_pad; t.total_pad += f.npad;
             for (int w = 0; w < f.npad / 64; ++w) t.wave_force.push_back(i);
         }
@@ -557,6 +592,7 @@ int remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, int
         if (pass == 1) t.waves_compound = t.total_pad / 64;
         if (pass == 2) t.waves_particles = t.total_pad / 64;
         if (pass == 3) t.waves_centroid = t.total_pad / 64;
+        if (pass == 4) t.waves_cv = t.total_pad / 64;
     }
     int rows = 4;
     for (int i = 0; i < n; ++i) rows = std::max(rows, t.F[i].n_particles);
@@ -580,6 +616,13 @@ int remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, int
         const cst_force& f = t.F[i]; const int wd = f.n_particles;
         for (int s = 0; s < f.npad; ++s) for (int a = 0; a < wd; ++a)
             t.atoms[(size_t)a * t.total_pad + f.slot0 + s] = group0[i] + desc[i].atoms[(size_t)std::min(s, f.n_terms - 1) * wd + a];
+    }
+    // the map of every slot of the CMAP forces' part (a padding slot repeats the last term's, like its atoms)
+    t.map_index.assign((size_t)t.total_pad - (size_t)t.waves_cv * 64, 0);
+    for (int i = 0; i < n; ++i) {
+        const cst_force& f = t.F[i];
+        if (f.kind != REMD_CUSTOM_CMAP) continue;
+        for (int s = 0; s < f.npad; ++s) t.map_index[f.slot0 + s - t.waves_cv * 64] = desc[i].map_index[std::min(s, f.n_terms - 1)];
     }
     if (t.n_groups > 0) {
         // per group, every (bond, position) that names it, in table order: the spread kernel adds their gradients in this order

@@ -46,9 +46,11 @@ MAX_TABLE_CELLS = 65536                         # values (the product of the siz
 KIND_BOND, KIND_ANGLE, KIND_TORSION, KIND_EXTERNAL, KIND_COMPOUND, KIND_CENTROID, KIND_NONBONDED = 0, 1, 2, 3, 4, 5, 6
 KIND_CV = 7                                     # system.CustomCVForce over RMSDForce variables (csrc/custom_cv.hip)
 MAX_CVS = 3                                     # collective variables per CustomCVForce: the machine carries three partials
+KIND_CMAP = 8                                   # system.CMAPTorsionForce: no expression, the energy a map of two dihedrals (csrc/cmap.hip)
+MAX_MAPS = 64                                   # maps per CMAPTorsionForce
 KIND_OF_CLASS = {'CustomNonbondedForce': KIND_NONBONDED, 'CustomBondForce': KIND_BOND, 'CustomAngleForce': KIND_ANGLE, 'CustomTorsionForce': KIND_TORSION,
                  'CustomExternalForce': KIND_EXTERNAL, 'CustomCompoundBondForce': KIND_COMPOUND, 'CustomCentroidBondForce': KIND_CENTROID,
-                 'CustomCVForce': KIND_CV}
+                 'CustomCVForce': KIND_CV, 'CMAPTorsionForce': KIND_CMAP}
 VARIABLES = {KIND_BOND: ('r',), KIND_ANGLE: ('theta',), KIND_TORSION: ('theta',), KIND_EXTERNAL: ('x', 'y', 'z'), KIND_NONBONDED: ('r',)}
 
 
@@ -273,6 +275,53 @@ def table2d_nodes(nx, ny, values, xmin, xmax, ymin, ymax, periodic=False):
     return np.stack([f, fx, fy, fxy], axis=-1)
 
 
+def cmap_block(size, energy):
+    """The block of one map of a system.CMAPTorsionForce: the periodic Continuous2DFunction layout [nx, ny, 0, 2 pi, 0, 2 pi, 1, 0],
+    node [ny][nx][4] with nx = ny = size + 1 -- energy[i + size*j] at (2 pi i / size, 2 pi j / size), the first row and column repeated
+    at the end, and the node derivatives of periodic cubic splines (table2d_nodes: OpenMM's calcMapDerivatives)."""
+    size = int(size)
+    grid = np.asarray(energy, dtype=np.float64).reshape(size, size)
+    grid = np.concatenate([grid, grid[:1]], axis=0)
+    grid = np.concatenate([grid, grid[:, :1]], axis=1)
+    two_pi = 2.0 * np.pi
+    nodes = table2d_nodes(size + 1, size + 1, grid.reshape(-1), 0.0, two_pi, 0.0, two_pi, periodic=True)
+    return np.concatenate([[size + 1.0, size + 1.0, 0.0, two_pi, 0.0, two_pi, 1.0, 0.0], nodes.reshape(-1)])
+
+
+def _cmap_entry(f, names, defaults, n_atoms):
+    """the entry of a CMAPTorsionForce: atoms [n][8] and n_particles = 8, map_index int32 [n], map_offsets int32 [n_maps] into consts,
+    which holds the maps' blocks (cmap_block) back to back; no program, no parameters; None for a force without torsions"""
+    n_maps, n = f.getNumMaps(), f.getNumTorsions()
+    if n and not n_maps:
+        raise ValueError('CMAPTorsionForce: %d torsions but no map' % n)
+    if n_maps > MAX_MAPS:
+        raise NotImplementedError('CMAPTorsionForce: %d maps in one force (the engine takes %d)' % (n_maps, MAX_MAPS))
+    if not n:
+        return None
+    terms = np.array([f.getTorsionParameters(k) for k in range(n)], dtype=np.int64).reshape(n, 9)
+    for k, row in enumerate(terms):
+        if not 0 <= row[0] < n_maps:
+            raise ValueError('CMAPTorsionForce: torsion %d names map %d (the force has %d)' % (k, row[0], n_maps))
+        for quad in (row[1:5], row[5:9]):
+            if len(set(quad.tolist())) != 4:
+                raise ValueError('CMAPTorsionForce: torsion %d names particle %d twice in one dihedral'
+                                 % (k, [p for p in quad.tolist() if quad.tolist().count(p) > 1][0]))
+        bad = [int(p) for p in row[1:] if p < 0 or (n_atoms is not None and p >= n_atoms)]
+        if bad:
+            raise ValueError('CMAPTorsionForce: torsion %d names particle %d (the System has %s)' % (k, bad[0], n_atoms))
+    blocks, offsets = [], []
+    for m in range(n_maps):
+        size, energy = f.getMapParameters(m)
+        if (size + 1) ** 2 > MAX_TABLE_CELLS:
+            raise NotImplementedError('CMAPTorsionForce: map %d of size %d (the engine takes 2 ... 255)' % (m, size))
+        offsets.append(sum(len(b) for b in blocks))
+        blocks.append(cmap_block(size, energy))
+    return dict(kind=KIND_CMAP, atoms=terms[:, 1:].astype(np.int32), params=np.zeros((n, 0)), global_names=list(names),
+                global_defaults=np.array(defaults, dtype=np.float64), program=np.zeros((0, 2), dtype=np.int32), consts=np.concatenate(blocks),
+                stack_depth=0, periodic=int(bool(f.usesPeriodicBoundaryConditions())), force_group=int(f.getForceGroup()),
+                energy=CMAP_ENERGY_TEXT, n_particles=8, map_index=terms[:, 0].astype(np.int32), map_offsets=np.array(offsets, dtype=np.int32))
+
+
 def _table_block(name, function, where):
     """(opcode, the function's block of the constant table): [n, min, max, periodic], y [n], y'' [n] of a Continuous1DFunction,
     [n], values [n] of a Discrete1DFunction, [nx, ny, xmin, xmax, ymin, ymax, periodic, 0], node [ny][nx][4] of a Continuous2DFunction,
@@ -474,7 +523,7 @@ def is_custom_term_force(force):
     from . import system as _system
     from . import forces as _forces
     if isinstance(force, (_system.CustomCompoundBondForce, _system.CustomCentroidBondForce, _system.CustomNonbondedForce,
-                          _system.CustomCVForce, _system.RMSDForce)):
+                          _system.CustomCVForce, _system.RMSDForce, _system.CMAPTorsionForce)):
         return True
     if isinstance(force, _system.CustomExternalForce):
         return not force.is_harmonic_oscillator()
@@ -487,8 +536,15 @@ def is_custom_term_force(force):
 
 def energy_text(force):
     """The energy string by which a message names a custom force; a bare RMSDForce has none of its own (OpenMM gives it no
-    getEnergyFunction): it is named by the expression it acts as, 'v'."""
+    getEnergyFunction): it is named by the expression it acts as, 'v'; a CMAPTorsionForce has no expression at all and is named
+    by CMAP_ENERGY_TEXT."""
+    from . import system as _system
+    if isinstance(force, _system.CMAPTorsionForce):
+        return CMAP_ENERGY_TEXT
     return as_cv_force(force).getEnergyFunction()
+
+
+CMAP_ENERGY_TEXT = 'map(dihedral(a1,a2,a3,a4), dihedral(b1,b2,b3,b4))'
 
 
 def as_cv_force(force):
@@ -900,8 +956,11 @@ def custom_terms_desc(forces, masses=None, box_vectors=None):
     forces = [as_cv_force(f) for f in forces]
     if len(forces) > MAX_FORCES:
         raise NotImplementedError('%d custom forces in one System (the engine takes %d)' % (len(forces), MAX_FORCES))
+    from . import system as _system
     names, defaults = [], []
     for f in forces:
+        if isinstance(f, _system.CMAPTorsionForce):                         # (no globals of its own)
+            continue
         for i in range(f.getNumGlobalParameters()):
             name, value = f.getGlobalParameterName(i), float(f.getGlobalParameterDefaultValue(i))
             if name in names:
@@ -923,6 +982,11 @@ def custom_terms_desc(forces, masses=None, box_vectors=None):
     for k, f in enumerate(forces):
         cls = [c for c in KIND_OF_CLASS if c in [b.__name__ for b in type(f).__mro__]][0]
         kind = KIND_OF_CLASS[cls]
+        if kind == KIND_CMAP:
+            entry = _cmap_entry(f, names, defaults, None if masses is None else len(masses))
+            if entry is not None:
+                out['%03d' % len(out)] = entry
+            continue
         where = '%s (energy %r)' % (cls, f.getEnergyFunction())
         per_term = _per_term_names(f)
         if kind == KIND_NONBONDED and len(per_term) > MAX_PAIR_PARAMS:
@@ -1023,7 +1087,7 @@ def custom_globals(system, names, states):
     default value the forces carry."""
     defaults = {}
     for f in system.getForces():
-        if is_custom_term_force(f):
+        if is_custom_term_force(f) and hasattr(as_cv_force(f), 'getNumGlobalParameters'):
             f = as_cv_force(f)
             for i in range(f.getNumGlobalParameters()):
                 defaults.setdefault(f.getGlobalParameterName(i), float(f.getGlobalParameterDefaultValue(i)))

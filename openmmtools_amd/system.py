@@ -649,6 +649,88 @@ class CustomCVForce(_CustomForce):
         return 0
 
 
+class CMAPTorsionForce(Force):
+    """openmm.CMAPTorsionForce: the energy of a pair of dihedrals read from a map -- the backbone phi / psi correction of CHARMM22/36
+    and Amber ff19SB.  A map is ``size * size`` energies in kJ/mol, ``energy[i + size*j]`` at the first angle 2 pi i / size and the
+    second 2 pi j / size, periodic in both; between the nodes it is the bicubic patch whose node derivatives come from periodic cubic
+    splines (OpenMM's CMAPTorsionForceImpl::calcMapDerivatives; custom_expr.cmap_block builds it).  A torsion pair names a map and two
+    quadruples of particles, which usually share three; each dihedral has the sign and range of PeriodicTorsionForce.  Off by
+    default, setUsesPeriodicBoundaryConditions makes every difference inside a dihedral a minimum image.  The force counts among the
+    custom forces of a System (one force group, custom_expr.MAX_FORCES) and runs in csrc/cmap.hip; size 2 ... MAX_SIZE and at most
+    MAX_MAPS maps are the engine's limits."""
+    MAX_MAPS = 64                             # REMD_CUSTOM_MAX_MAPS
+    MAX_SIZE = 255                            # (size + 1)^2 node values must stay within custom_expr.MAX_TABLE_CELLS
+
+    def __init__(self):
+        super().__init__()
+        self._maps = []                       # (size, energies float64 [size * size])
+        self._torsions = []                   # (map, a1, a2, a3, a4, b1, b2, b3, b4)
+        self._periodic = False
+
+    @staticmethod
+    def _map(size, energy):
+        from .unit import to_md
+        if int(size) != size or int(size) < 2:
+            raise ValueError('CMAPTorsionForce: a map of size %r (at least 2)' % (size,))
+        size = int(size)
+        energy = np.array(to_md(energy), dtype=np.float64).reshape(-1)
+        if len(energy) != size * size:
+            raise ValueError('CMAPTorsionForce: a map of size %d needs %d energies, not %d' % (size, size * size, len(energy)))
+        if not np.isfinite(energy).all():
+            raise ValueError('CMAPTorsionForce: a map energy that is not finite')
+        if size > CMAPTorsionForce.MAX_SIZE:
+            raise NotImplementedError('CMAPTorsionForce: a map of size %d (the engine takes 2 ... %d)' % (size, CMAPTorsionForce.MAX_SIZE))
+        return size, energy
+
+    def addMap(self, size, energy):
+        entry = self._map(size, energy)
+        if len(self._maps) >= self.MAX_MAPS:
+            raise NotImplementedError('CMAPTorsionForce: more than %d maps in one force' % self.MAX_MAPS)
+        self._maps.append(entry)
+        return len(self._maps) - 1
+
+    def getNumMaps(self):
+        return len(self._maps)
+
+    def getMapParameters(self, index):
+        size, energy = self._maps[index]
+        return size, energy.tolist()
+
+    def setMapParameters(self, index, size, energy):
+        self._maps[index] = self._map(size, energy)
+
+    @staticmethod
+    def _torsion(map, a, b):
+        for name, quad in (('first', a), ('second', b)):
+            if len(set(quad)) != 4:
+                raise ValueError('CMAPTorsionForce: the %s dihedral (%s) names particle %d twice'
+                                 % (name, ', '.join(str(p) for p in quad), [p for p in quad if quad.count(p) > 1][0]))
+        return (int(map),) + tuple(a) + tuple(b)
+
+    def addTorsion(self, map, a1, a2, a3, a4, b1, b2, b3, b4):
+        self._torsions.append(self._torsion(map, [int(p) for p in (a1, a2, a3, a4)], [int(p) for p in (b1, b2, b3, b4)]))
+        return len(self._torsions) - 1
+
+    def getNumTorsions(self):
+        return len(self._torsions)
+
+    def getTorsionParameters(self, index):
+        return self._torsions[index]
+
+    def setTorsionParameters(self, index, map, a1, a2, a3, a4, b1, b2, b3, b4):
+        self._torsions[index] = self._torsion(map, [int(p) for p in (a1, a2, a3, a4)], [int(p) for p in (b1, b2, b3, b4)])
+
+    def setUsesPeriodicBoundaryConditions(self, periodic):
+        self._periodic = bool(periodic)
+
+    def usesPeriodicBoundaryConditions(self):
+        return self._periodic
+
+    def updateParametersInContext(self, context=None):
+        raise NotImplementedError('CMAPTorsionForce: changing a map or a torsion after set_system (updateParametersInContext) is not '
+                                  'supported: the engine keeps the maps it was given, build the states again')
+
+
 class CustomExternalForce(_CustomForce):
     """openmm.CustomExternalForce: the energy a function of a particle's x, y, z, of per-particle and of global parameters.  The
     harmonic-well expression of testsystems.HarmonicOscillator (testsystems.py:779-786) keeps the engine's own kernel (ext_K / ext_x0 /
@@ -1389,6 +1471,15 @@ def from_openmm(omm_system):
             g.setEwaldErrorTolerance(f.getEwaldErrorTolerance())
         elif isinstance(f, openmm.CMMotionRemover):
             g = CMMotionRemover(f.getFrequency())
+        elif isinstance(f, openmm.CMAPTorsionForce):
+            g = CMAPTorsionForce()
+            for k in range(f.getNumMaps()):
+                size, energy = f.getMapParameters(k)
+                g.addMap(size, energy.value_in_unit(u.kilojoule_per_mole))
+            for k in range(f.getNumTorsions()):
+                g.addTorsion(*f.getTorsionParameters(k))
+            g.setUsesPeriodicBoundaryConditions(f.usesPeriodicBoundaryConditions())
+            g.setForceGroup(f.getForceGroup())
         else:
             raise NotImplementedError('unsupported OpenMM force %s' % type(f).__name__)
         s.addForce(g)

@@ -246,6 +246,54 @@ def main():
             out[name] = dict(launches_timed=n, us_per_launch=1e3 * ms / max(n, 1))
         engine.profile_enable(0)
         print(json.dumps(dict(config='4rm', profile=out)), flush=True)
+    if '4cm' in which:
+        # config 4's share with a CMAPTorsionForce (custom_expr.py kind 8, csrc/cmap.hip): CB7 is no peptide, so the torsion pairs are
+        # synthetic phi / psi-like quadruples of the host -- every run of five atoms along a bonded path, (a, b, c, d) and (b, c, d, e), on
+        # two 24 x 24 maps.  After the timed iterations one more runs with the engine's profile on for the custom-force launches.
+        from openmmtools_amd.system import CMAPTorsionForce, HarmonicBondForce
+        hg = testsystems.HostGuestExplicit()
+        lam_e = np.concatenate([np.linspace(1.0, 0.0, 32), np.zeros(32)])
+        lam_s = np.concatenate([np.ones(32), np.linspace(1.0, 0.0, 32)])
+        asys = alchemy.AbsoluteAlchemicalFactory().create_alchemical_system(hg.system, alchemy.AlchemicalRegion(alchemical_atoms=range(126, 156)))
+        bonded = {}
+        for f in hg.system.getForces():
+            if isinstance(f, HarmonicBondForce):
+                for k in range(f.getNumBonds()):
+                    i, j = f.getBondParameters(k)[:2]
+                    if i < 126 and j < 126:
+                        bonded.setdefault(i, []).append(j); bonded.setdefault(j, []).append(i)
+        paths = set()
+        for a in sorted(bonded):
+            for b in bonded[a]:
+                for c in bonded[b]:
+                    for d in bonded[c]:
+                        for e in bonded[d]:
+                            if len({a, b, c, d, e}) == 5 and a < e:
+                                paths.add((a, b, c, d, e))
+        paths = sorted(paths)[::4]
+        angle = 2.0 * np.pi * np.arange(24) / 24
+        cmap = CMAPTorsionForce()
+        for k in range(2):
+            cmap.addMap(24, (2.0 * np.cos(angle[None, :] + k) + 1.5 * np.sin(2.0 * angle[:, None]) + np.cos(angle[None, :] - angle[:, None])).reshape(-1))
+        for t, (a, b, c, d, e) in enumerate(paths):
+            cmap.addTorsion(t % 2, a, b, c, d, b, c, d, e)
+        cmap.setUsesPeriodicBoundaryConditions(True)
+        asys.addForce(cmap)
+        ths = [states.CompoundThermodynamicState(states.ThermodynamicState(asys, 300.0),
+                                                 [states.AlchemicalState(lambda_sterics=ls, lambda_electrostatics=le)])
+               for le, ls in zip(lam_e, lam_s)]
+        engine = HipEngine()
+        s = SAMSSampler(mcmc_moves=move(2.0, 'V R R O R R V'), number_of_iterations=10 ** 9, engine=engine, seed=1)
+        ss = states.SamplerState(hg.positions, box_vectors=hg.system.getDefaultPeriodicBoxVectors())
+        s.create(ths, [ss] * 8)
+        run('4cm (1-GPU share, %d CMAP torsion pairs on CB7): HostGuestExplicit + one CMAPTorsionForce, 8 replicas x 64 states, '
+            'g-BAOAB 2 fs x 500' % len(paths), s, 3)
+        engine.profile_enable(1, 'custom_terms')
+        engine.profile_reset()
+        s.run(1)
+        n, ms = engine.profile_get('custom_terms')
+        engine.profile_enable(0)
+        print(json.dumps(dict(config='4cm', profile=dict(custom_terms=dict(launches_timed=n, us_per_launch=1e3 * ms / max(n, 1))))), flush=True)
     if '4cr' in which:
         # config 4's share with EVERY harmonic bond, harmonic angle and periodic torsion of the System moved to custom forces with the
         # same formulas (custom_expr.py): what the expression machine costs at a force field's size, against the built-in listed terms of '4'
