@@ -109,6 +109,13 @@ BAROSTAT_ANISOTROPIC, BAROSTAT_MEMBRANE = 1, 2
 MBAR_EXPORTS = ['remd_mbar_create', 'remd_mbar_destroy', 'remd_mbar_log_denominator', 'remd_mbar_self_consistent', 'remd_mbar_newton_parts',
                 'remd_mbar_gram', 'remd_mbar_log_weights', 'remd_mbar_chunks', 'remd_mbar_last_ms']
 MBAR_MAX_STATES = 512
+# the GPU-only extension of include/remd_hip_vsites.h (virtual sites), bound the same way
+VSITE_EXPORTS = ['remd_set_virtual_sites']
+
+
+class RemdVsiteDesc(C.Structure):
+    """remd_vsite_desc (include/remd_hip_vsites.h)."""
+    _fields_ = [('kind', C.c_int32), ('site', C.c_int32), ('parent', C.c_int32 * 3), ('weight', C.c_double * 3)]
 
 EXPORTS = [
     'remd_create', 'remd_destroy', 'remd_last_error', 'remd_version', 'remd_set_system', 'remd_set_coulomb_cutoff', 'remd_set_reaction_field', 'remd_set_alchemical_options', 'remd_set_alchemical_regions',
@@ -241,6 +248,9 @@ def load_library(path=None):
     if hasattr(lib, 'remd_set_gb_model'):                 # include/remd_hip_gb.h (GPU-only, like the restraints)
         lib.remd_set_gb_model.argtypes = [vp, C.POINTER(RemdGbModelDesc)]
         lib.remd_set_gb_model.restype = C.c_int
+    if hasattr(lib, 'remd_set_virtual_sites'):            # include/remd_hip_vsites.h (GPU-only, like the restraints)
+        lib.remd_set_virtual_sites.argtypes = [vp, C.POINTER(RemdVsiteDesc), C.c_int32]
+        lib.remd_set_virtual_sites.restype = C.c_int
     if hasattr(lib, 'remd_mbar_create'):                  # include/remd_hip_mbar.h (GPU-only, like the restraints)
         lib.remd_mbar_create.argtypes = [C.c_int, C.c_int, C.c_int64, c_double_p, c_int64_p, C.POINTER(vp)]
         lib.remd_mbar_destroy.argtypes = [vp]
@@ -501,6 +511,10 @@ class HipEngine:
 
     # ---- set-up ---------------------------------------------------------------------
     def set_system(self, desc_dict):
+        sites = desc_dict.get('virtual_sites')
+        if sites is not None and not hasattr(self.lib, 'remd_set_virtual_sites'):       # (before the handle changes)
+            raise NotImplementedError('remd_set_virtual_sites: this build of the engine library has no virtual sites '
+                                      '(include/remd_hip_vsites.h is GPU-only)')
         s, keep = build_desc(desc_dict)
         # Ewald split (system.system_to_desc(ewald_split=...)): range of the direct-space Coulomb sum, 0 = the cutoff
         self._check(self.lib.remd_set_coulomb_cutoff(self.h, float(desc_dict.get('coulomb_cutoff', 0.0))), 'remd_set_coulomb_cutoff')
@@ -510,6 +524,9 @@ class HipEngine:
         self._check(self.lib.remd_set_alchemical_options(self.h, int(bool(desc_dict.get('annihilate_sterics', False)))), 'remd_set_alchemical_options')
         self._check(self.lib.remd_set_system(self.h, C.byref(s)), 'remd_set_system')
         self.N = int(desc_dict['n_atoms'])
+        self.n_virtual_sites = 0
+        if sites is not None:                            # virtual sites (system.setVirtualSite; csrc/virtual_sites.hip)
+            self.set_virtual_sites(sites)
         self.n_regions = 0
         regions = desc_dict.get('alch_regions')
         if regions is not None:                          # general alchemical regions: the factory's custom forces (alchemy.py:1539-2038)
@@ -568,6 +585,23 @@ class HipEngine:
         custom = desc_dict.get('custom_terms')
         if custom:                                       # custom bond / angle / torsion / external forces (custom_expr.py; csrc/custom_terms.hip)
             self.set_custom_terms([custom[k] for k in sorted(custom)])
+
+    def set_virtual_sites(self, sites):
+        """The site table of the system (system.system_to_desc's 'virtual_sites': site, kind, parent, weight); after set_system,
+        which forgets it."""
+        if not hasattr(self.lib, 'remd_set_virtual_sites'):
+            raise NotImplementedError('remd_set_virtual_sites: this build of the engine library has no virtual sites '
+                                      '(include/remd_hip_vsites.h is GPU-only)')
+        site, kind = np.asarray(sites['site']).reshape(-1), np.asarray(sites['kind']).reshape(-1)
+        parent = np.asarray(sites['parent']).reshape(len(site), 3)
+        weight = np.asarray(sites['weight'], dtype=np.float64).reshape(len(site), 3)
+        arr = (RemdVsiteDesc * max(1, len(site)))()
+        for k in range(len(site)):
+            arr[k].kind, arr[k].site = int(kind[k]), int(site[k])
+            for q in range(3):
+                arr[k].parent[q] = int(parent[k, q]); arr[k].weight[q] = float(weight[k, q])
+        self._check(self.lib.remd_set_virtual_sites(self.h, arr, len(site)), 'remd_set_virtual_sites')
+        self.n_virtual_sites = len(site)
 
     def _restraint_entry(self, name):
         if not hasattr(self.lib, name):

@@ -108,6 +108,8 @@ class AbsoluteAlchemicalFactory:
             if seen & set(r.alchemical_atoms):
                 raise ValueError('alchemical regions overlap')
             seen |= set(r.alchemical_atoms)
+            if any(system.isVirtualSite(int(i)) for i in r.alchemical_atoms):                          # alchemy.py:705-710
+                raise ValueError('Virtual atoms in region %s. Alchemically modified virtual sites are not supported' % r.name)
         system.alchemical_lrc = not self.disable_alchemical_dispersion_correction
         nbs = [f for f in system.getForces() if isinstance(f, NonbondedForce)]
         nb = nbs[0] if nbs else None

@@ -167,11 +167,15 @@ int remd_set_system(remd_handle h, const remd_system_desc* d)
     remd_regions_release(h);                    // remd_set_alchemical_regions follows the system it belongs to
     remd_restraints_release(h);                 // ... and so do remd_set_restraints (restraints.hip)
     remd_custom_release(h);                     // ... and remd_set_custom_terms (custom_terms.hip)
+    remd_vsites_release(h);                     // ... and remd_set_virtual_sites (virtual_sites.hip)
     h->N = d->n_atoms;
     h->Npad = (d->n_atoms + 63) / 64 * 64;
     std::vector<float> im(h->Npad, 0.f), m(h->Npad, 0.f);
-    h->total_mass = 0;
+    h->total_mass = 0; h->n_massless = 0;
     for (int i = 0; i < h->N; ++i) {
+        // (mass exactly 0: a virtual site to be, mass and inverse mass 0 -- remd_set_replicas refuses the handle until
+        // remd_set_virtual_sites has declared every one of them)
+        if (d->mass[i] == 0.0) { h->n_massless++; continue; }
         if (!(d->mass[i] > 0)) return remd_fail(h, -3, "massless particles are not supported");
         m[i] = (float)d->mass[i]; im[i] = (float)(1.0 / d->mass[i]); h->total_mass += d->mass[i];
     }
@@ -276,6 +280,8 @@ int remd_set_replicas(remd_handle h, int R_global, int r_begin, int R_local, con
     if (!h || !h->has_system) return remd_fail(h, -1, "remd_set_replicas: call remd_set_system first");
     if (R_global <= 0 || R_local <= 0 || r_begin < 0 || r_begin + R_local > R_global || !labels)
         return remd_fail(h, -1, "remd_set_replicas: bad arguments");
+    if (h->n_massless != h->n_vsites)
+        return remd_fail(h, -3, "massless particles are not supported (unless every one of them is declared a virtual site: remd_set_virtual_sites)");
     // (validated before anything of the handle changes: a refused call leaves it as it was)
     if (h->nb_method != REMD_NB_NONE && box)
         for (int r = 0; r < R_local; ++r) for (int k = 0; k < 3; ++k)
@@ -346,6 +352,7 @@ int remd_set_replicas(remd_handle h, int R_global, int r_begin, int R_local, con
     // (the mesh buffers follow the replica count; a call that only replaces coordinates keeps them -- one handle per compatibility
     // group re-enters here every iteration, multistate/_engine_pool.py)
     if (h->nb_method == REMD_NB_PME && (realloc || !h->pme)) { int rc = remd_pme_setup(h); if (rc) return rc; }
+    REMD_TRY(remd_vsites_place(h, h->stream, true));      // (whatever the caller gave for a site: its place, velocity 0)
     return remd_set_labels(h, labels);
 }
 
@@ -390,6 +397,7 @@ int remd_copy_replicas(remd_handle dst, const int32_t* dst_slot, remd_handle src
                        pos ? dst->d_pos : (float4*)nullptr, src->d_pos, vel ? dst->d_vel : (float4*)nullptr, src->d_vel,
                        box ? dst->d_box : (float*)nullptr, src->d_box);
     REMD_CHECK(dst, hipGetLastError());
+    REMD_TRY(remd_vsites_place(dst, dst->stream, true));      // (the source need not hold the same sites)
     if (box) {
         std::vector<float> hb(4 * (size_t)dst->R);
         REMD_CHECK(dst, hipMemcpyAsync(hb.data(), dst->d_box, sizeof(float) * hb.size(), hipMemcpyDeviceToHost, dst->stream));
@@ -650,6 +658,7 @@ static int phase_children(remd_ctx* h, int P)
         if (h->n_regions > 0 && (rc = remd_regions_clone(h, c))) return rc;       // general alchemical regions (alch_regions.hip)
         if (h->n_restraints > 0 && (rc = remd_restraints_clone(h, c))) return rc;  // receptor-ligand restraints (restraints.hip)
         if (h->n_custom > 0 && (rc = remd_custom_clone(h, c))) return rc;          // custom bond / angle / torsion / external forces (custom_terms.hip)
+        if (h->n_vsites > 0 && (rc = remd_vsites_clone(h, c))) return rc;          // virtual sites (virtual_sites.hip)
         if (h->baro_frequency > 0) {
             if ((rc = remd_set_barostat(c, h->K, h->pressure_host.data(), h->baro_frequency))) return remd_fail(h, rc, std::string("phases: ") + c->err);
             c->econst_vref = h->econst_vref;

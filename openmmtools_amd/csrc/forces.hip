@@ -2096,12 +2096,15 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask, bool
     // on the main stream -- or, where the caller's next main-stream launch is an integrator chain, that chain's prologue.  With the
     // listed terms off the direct-space stream the scatter is its last launch, and the chain can poll the scatter's done counter
     // (remd_fold_args) with no signal launch either, if launch_nb takes the request (REMD_NB_FOLD=0: signal launch).
-    const bool join_in_chain = forked && !h->sync_events && chain_follows && !with_energy;
+    // (a handle with virtual sites joins by a launch: the spread at the end of this function reads d_force behind both branches, so
+    // neither the chain's prologue nor the scatter's done counter can carry the join)
+    const bool join_in_chain = forked && !h->sync_events && chain_follows && !with_energy && h->n_vsites == 0;
     const bool want_fold = join_in_chain && listed_off_direct && h->sw.nb_fold && (class_mask & 63u) == 63u && h->profiling != 2;
     h->next.forked = forked;
     if (nbt) nbt->p.prio = prio_pair;
 
     // ---- in front of the fork: both branches are ordered behind these --------------------------------------------------------
+    REMD_TRY(remd_vsites_place(h, main_st));            // (virtual_sites.hip: nothing for a handle without sites)
     if (!h->force_zeroed)
         REMD_CHECK(h, hipMemsetAsync(h->d_force, 0, sizeof(long long) * 3 * (size_t)h->Npad * h->R, main_st));
     h->force_zeroed = false;
@@ -2206,6 +2209,8 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask, bool
         mesh.part = 2;                 // (what is left: the energy reduction of the mesh part)
     }
     if (forked || (nbt && nbt->method == NB_EWALD && do_recip)) REMD_TRY(remd_pme_forces(h, with_energy, main_st, mesh));
+    // behind the join and the mesh branch's force pass, in front of every reader of d_force: the sites' forces go to their parents
+    REMD_TRY(remd_vsites_spread(h, main_st));
     if (with_energy && nbt) {
         const nb_tables& t = *nbt;
         hipLaunchKernelGGL(const_energy_kernel, dim3((R + 63) / 64), dim3(64), 0, main_st, R, t.disp_coeff, t.self_nn, t.self_aa,

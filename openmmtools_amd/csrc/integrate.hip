@@ -525,7 +525,11 @@ int remd_build_constraints(remd_ctx* h, const remd_system_desc* d)
     // kernel's registers) 16 x 33 = 528 workgroups are THREE rounds of the chip; four to a unit: 7988 units = 32 workgroups, 512 = two rounds)
     {
         std::vector<int> fr;
-        for (int i = 0; i < N; ++i) if (!used[i]) fr.push_back(i);
+        // (a massless particle -- a virtual site, virtual_sites.hip -- is in no unit: nothing that works on units moves or kicks it)
+        for (int i = 0; i < N; ++i) {
+            if (d->mass[i] == 0.0) { if (used[i]) return remd_fail(h, -3, "a massless particle (virtual site) takes part in a constraint"); continue; }
+            if (!used[i]) fr.push_back(i);
+        }
         size_t q = 0;
         for (; q + 4 <= fr.size(); q += 4) {
             atoms.push_back(make_int4(fr[q], fr[q + 1], fr[q + 2], fr[q + 3])); type.push_back(UNIT_FREE);
@@ -543,7 +547,7 @@ int remd_build_constraints(remd_ctx* h, const remd_system_desc* d)
     h->n_settle = d->n_settle; h->n_shake = d->n_shake;
     int n_con = 3 * d->n_settle;
     for (int s = 0; s < d->n_shake; ++s) for (int k = 1; k < 4; ++k) if (d->shake_atoms[4 * s + k] >= 0) n_con++;
-    h->n_dof = 3 * N - n_con - (d->cmm_frequency > 0 ? 3 : 0);
+    h->n_dof = 3 * (N - h->n_massless) - n_con - (d->cmm_frequency > 0 ? 3 : 0);
     if (d->n_settle > 0) {
         const int* a = d->settle_atoms;
         const double mO = d->mass[a[0]], mH = d->mass[a[1]];
@@ -902,6 +906,7 @@ struct step_runner {
         if (done_by_resident) return 0;
         flush(false);
         remd_launch_join_wait(h);
+        { const int rc = remd_vsites_place(h, h->stream); if (rc) return rc; }     // (the positions this call leaves carry placed sites)
         h->force_zeroed = zeroed_by_chain;
         REMD_CHECK(h, hipGetLastError());
         return 0;

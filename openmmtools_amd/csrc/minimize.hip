@@ -199,7 +199,7 @@ int remd_minimize_impl(remd_ctx* h, double tolerance, int max_iterations, int32_
     const float timestep = 0.001f;                               // 1 fs (integrators.py:2318)
     fire_consts c{};
     c.dt_max = 0.010f; c.f_inc = 1.1f; c.f_dec = 0.5f; c.alpha0 = 0.1f; c.f_alpha = 0.99f; c.n_min = 5;
-    c.dt_min = 1.0e-5f * timestep; c.ftol = (float)tolerance; c.ndof = 3.0f * (float)h->N;
+    c.dt_min = 1.0e-5f * timestep; c.ftol = (float)tolerance; c.ndof = 3.0f * (float)(h->N - h->n_massless);
     std::vector<fire_rep> init(2 * (size_t)R);
     for (auto& s : init) { s.dt = timestep; s.alpha = c.alpha0; s.n_neg = 0; s.converged = 0; s.E = 0.0; s.f2 = 0.0; }
     REMD_CHECK(h, hipMemcpyAsync(st, init.data(), sizeof(fire_rep) * init.size(), hipMemcpyHostToDevice, h->stream));
@@ -238,6 +238,8 @@ int remd_minimize_impl(remd_ctx* h, double tolerance, int max_iterations, int32_
         for (int r = 0; r < R; ++r) all_done = all_done && host[r].converged;
         if (max_iterations > 0) all_done = false;               // a fixed number of steps was asked for
     }
+    // (virtual sites: a restarted step put the parents back, the sites follow here)
+    if ((rc = remd_vsites_place(h, h->stream))) return rc;
     hipMemcpyAsync(host.data(), st + (size_t)cur * R, sizeof(fire_rep) * R, hipMemcpyDeviceToHost, h->stream);
     hipStreamSynchronize(h->stream);
     if (converged_out) for (int r = 0; r < R; ++r) converged_out[r] = host[r].converged;

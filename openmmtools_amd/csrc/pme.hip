@@ -1497,7 +1497,8 @@ remd_chain_bins remd_pme_chain_bins(remd_ctx* h)
 {
     remd_chain_bins b;
     const pme_state* s = h->pme.get();
-    if (!s || !s->d_cbin_count || s->R != h->R || !h->next.forked || h->no_chain_bins) return b;
+    // (virtual sites: the chain does not move them, and the evaluation places them only behind it -- the binning launch sees them)
+    if (!s || !s->d_cbin_count || s->R != h->R || !h->next.forked || h->no_chain_bins || h->n_vsites > 0) return b;
     b.nx = s->n[0]; b.cap = s->cbin_cap; b.count = s->d_cbin_count + (size_t)s->cbin_parity * s->R * s->n[0]; b.atoms = s->d_cbin_atoms;
     b.box = h->d_box; b.err = h->d_sync + 2;
     // charges ride in the bins only when they do not depend on the replica's state: the chain runs before the evaluation

@@ -62,12 +62,13 @@ private:
 #define REMD_TRY(expr) do { const int _rc = (expr); if (_rc) return _rc; } while (0)
 
 // The feature tables a handle owns, each defined in the .hip file that builds it; the deleter of each is defined there too.
-struct nb_tables; struct pme_state; struct unit_tables; struct gbsa_tables; struct nocutoff_tables; struct region_tables; struct rst_tables; struct cst_tables;
+struct nb_tables; struct pme_state; struct unit_tables; struct gbsa_tables; struct nocutoff_tables; struct region_tables; struct rst_tables; struct cst_tables; struct vs_tables;
 struct mix_pre_buffers;
 struct remd_table_deleter {
     void operator()(nb_tables*) const; void operator()(pme_state*) const; void operator()(unit_tables*) const;
     void operator()(gbsa_tables*) const; void operator()(nocutoff_tables*) const; void operator()(region_tables*) const;
     void operator()(rst_tables*) const; void operator()(cst_tables*) const; void operator()(mix_pre_buffers*) const;
+    void operator()(vs_tables*) const;
 };
 template <typename T> using remd_table = std::unique_ptr<T, remd_table_deleter>;
 // a handle's table, made on first use
@@ -265,6 +266,7 @@ struct remd_ctx {
     int n_restraints = 0, rst_group = 0;   // remd_set_restraints: receptor-ligand restraints and their force group (restraints.hip holds the tables)
     double cst_cutoff = 0;                 // the longest cutoff of a CutoffPeriodic CustomNonbondedForce (custom_nonbonded.hip): the box checks honour it
     int n_custom = 0, cst_group = 0;       // remd_set_custom_terms: custom bond / angle / torsion / external forces and their force group (custom_terms.hip)
+    int n_massless = 0, n_vsites = 0;      // particles of mass 0 in the descriptor / sites declared by remd_set_virtual_sites (virtual_sites.hip): equal before anything runs
 
     // ---- states ---------------------------------------------------------------------
     int K = 0;
@@ -341,6 +343,7 @@ struct remd_ctx {
     remd_table<region_tables> reg;     // alch_regions.hip
     remd_table<rst_tables> rst;        // restraints.hip
     remd_table<cst_tables> cst;        // custom_terms.hip
+    remd_table<vs_tables> vs;          // virtual_sites.hip
     remd_table<mix_pre_buffers> mix_pre;   // mix.hip: the hoisted swap-all path
 
     // ---- mixing scratch ----------------------------------------------------------------
@@ -524,6 +527,12 @@ int remd_custom_clone(remd_ctx* parent, remd_ctx* child);
 int remd_custom_molecules(remd_ctx* h, const int** first, const int** size);   // molecule table of a handle whose only pair force is a periodic CustomNonbondedForce (device); 0: none
 int remd_custom_forces(remd_ctx* h, bool with_energy, int ep_slot, hipStream_t st);
 int remd_custom_ukl(remd_ctx* h, double* d_rows /*[R][K], added to*/);
+
+// virtual_sites.hip: virtual sites (include/remd_hip_vsites.h); both launches are skipped by a handle without sites
+void remd_vsites_release(remd_ctx* h);
+int remd_vsites_clone(remd_ctx* parent, remd_ctx* child);
+int remd_vsites_place(remd_ctx* h, hipStream_t st, bool zero_velocities = false);   // every site from its parents' current positions
+int remd_vsites_spread(remd_ctx* h, hipStream_t st);      // the sites' words of d_force to their parents, zero left behind
 
 // ---- pme.hip ----------------------------------------------------------------------------
 int remd_pme_setup(remd_ctx* h);

@@ -234,7 +234,7 @@ void resident_md_kernel(resident_prog prog, resident_sys S, float4* __restrict__
 // tokens that fits the kernel argument, no heat / shadow work
 static bool resident_takes_request(const remd_ctx* h, const std::vector<char>& tokens, int n_steps)
 {
-    if (!h->sw.resident || h->no_resident) return false;
+    if (!h->sw.resident || h->no_resident || h->n_vsites > 0) return false;      // (the resident kernels know nothing of virtual sites)
     if (h->baro_frequency > 0 || h->profiling == 2 || (int)tokens.size() > MAX_TOK || n_steps < 1) return false;
     if (h->measure_heat || h->measure_shadow) return false;
     for (char c : tokens) if (c != 'V' && c != 'R' && c != 'O') return false;

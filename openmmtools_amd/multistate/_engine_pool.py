@@ -64,6 +64,8 @@ class EnginePool:
             raise NotImplementedError('restraints (forces.py) in more than one compatibility group')
         if any(d.get('custom_terms') for d in descs):
             raise NotImplementedError('custom bond / angle / torsion / external forces and compound-bond forces, centroid-bond forces or nonbonded custom forces, or CMAP torsion forces (custom_expr.py) in more than one compatibility group')
+        if any(d.get('virtual_sites') for d in descs):
+            raise NotImplementedError('virtual sites (system.setVirtualSite) in more than one compatibility group')
         n = {int(d['n_atoms']) for d in descs}
         if len(n) != 1:
             raise ValueError('the Systems of all thermodynamic states must hold the same particles (%s)' % sorted(n))

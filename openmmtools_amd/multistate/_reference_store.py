@@ -440,6 +440,8 @@ class ReferenceStoreWriter:
         for s in list(thermodynamic_states) + list(unsampled_states):
             if type(s).__name__ not in ('ThermodynamicState', 'CompoundThermodynamicState'):
                 return type(s).__name__
+            if getattr(s.system, 'virtual_sites', None):    # (nor that of virtual sites)
+                return 'a System with virtual sites'
             for f in s.system.getForces():                  # (the System XML of the per-axis barostats is not written: system_xml.to_xml)
                 if type(f).__name__ in ('MonteCarloAnisotropicBarostat', 'MonteCarloMembraneBarostat'):
                     return 'a System with a %s' % type(f).__name__

@@ -11,6 +11,7 @@ System into the arrays behind ``remd_system_desc`` (include/remd_hip.h).  A real
 """
 import hashlib
 import math
+import types
 import numpy as np
 
 
@@ -1061,7 +1062,73 @@ class MonteCarloMembraneBarostat(Force):
     def usesPeriodicBoundaryConditions(self): return False      # (as OpenMM's barostats answer: the other forces decide)
 
 
+class VirtualSite:
+    """A massless particle whose position is a fixed function of its parents' (OpenMM's VirtualSite; csrc/virtual_sites.hip)."""
+    kind = -1
+
+    def __init__(self, particles, weights):
+        self._particles = tuple(int(p) for p in particles)
+        self._weights = tuple(float(w) for w in weights)
+        if any(not math.isfinite(w) for w in self._weights):
+            raise ValueError('%s: a weight is not finite' % type(self).__name__)
+
+    def getNumParticles(self):
+        return len(self._particles)
+
+    def getParticle(self, particle):
+        return self._particles[particle]
+
+    def __eq__(self, other):
+        return type(self) is type(other) and self._particles == other._particles and self._weights == other._weights
+
+    def __hash__(self):
+        return hash((type(self).__name__, self._particles, self._weights))
+
+
+class TwoParticleAverageSite(VirtualSite):
+    """x = w1 x1 + w2 x2."""
+    kind = 0
+
+    def __init__(self, particle1, particle2, weight1, weight2):
+        super().__init__((particle1, particle2), (weight1, weight2))
+
+    def getWeight(self, particle):
+        return self._weights[particle]
+
+
+class ThreeParticleAverageSite(VirtualSite):
+    """x = w1 x1 + w2 x2 + w3 x3."""
+    kind = 1
+
+    def __init__(self, particle1, particle2, particle3, weight1, weight2, weight3):
+        super().__init__((particle1, particle2, particle3), (weight1, weight2, weight3))
+
+    def getWeight(self, particle):
+        return self._weights[particle]
+
+
+class OutOfPlaneSite(VirtualSite):
+    """x = x1 + w12 r12 + w13 r13 + wcross (r12 x r13), r12 = x2 - x1, r13 = x3 - x1."""
+    kind = 2
+
+    def __init__(self, particle1, particle2, particle3, weight12, weight13, weightCross):
+        super().__init__((particle1, particle2, particle3), (weight12, weight13, weightCross))
+
+    def getWeight12(self):
+        return self._weights[0]
+
+    def getWeight13(self):
+        return self._weights[1]
+
+    def getWeightCross(self):
+        return self._weights[2]
+
+
 class System:
+    # particle index -> VirtualSite.  An instance gets a dict of its own with its first setVirtualSite: a System without sites
+    # pickles as it always did (the stores' bytes are pinned).
+    virtual_sites = types.MappingProxyType({})
+
     def __init__(self):
         self.masses = []
         self.forces = []
@@ -1102,6 +1169,26 @@ class System:
 
     def getConstraintParameters(self, idx):
         return self.constraints[idx]
+
+    def setVirtualSite(self, index, virtualSite):
+        """Make particle ``index`` (mass 0) a virtual site; what the System cannot run is refused by system_to_desc."""
+        index = int(index)
+        if not 0 <= index < len(self.masses):
+            raise ValueError('setVirtualSite: particle index %d out of range' % index)
+        if not isinstance(virtualSite, VirtualSite):
+            raise NotImplementedError('setVirtualSite: %s is not supported (TwoParticleAverageSite, ThreeParticleAverageSite and '
+                                      'OutOfPlaneSite are)' % type(virtualSite).__name__)
+        if 'virtual_sites' not in self.__dict__:
+            self.virtual_sites = {}
+        self.virtual_sites[index] = virtualSite
+
+    def isVirtualSite(self, index):
+        return int(index) in self.virtual_sites
+
+    def getVirtualSite(self, index):
+        if int(index) not in self.virtual_sites:
+            raise ValueError('getVirtualSite: particle %d is not a virtual site' % int(index))
+        return self.virtual_sites[int(index)]
 
     def setDefaultPeriodicBoxVectors(self, a, b, c):
         self._box = (tuple(float(v) for v in a), tuple(float(v) for v in b), tuple(float(v) for v in c))
@@ -1232,6 +1319,88 @@ def _classify_constraints(system):
     return settle, shake, shake_d
 
 
+def _virtual_site_table(system, d):
+    """The site table of remd_set_virtual_sites (include/remd_hip_vsites.h) or None, and every refusal that needs the whole System.
+
+    ``molecule``: per site, the smallest particle index of the molecule it is counted into -- its parents'.  Molecules are the
+    connected components of bonds, constraints and exceptions (the engine's molecule table takes exceptions and constraints), a
+    site joined to its parents."""
+    sites = getattr(system, 'virtual_sites', None) or {}
+    n = system.getNumParticles()
+    for i, m in enumerate(system.masses):
+        if m == 0.0 and i not in sites:
+            raise ValueError('massless particles are not supported: particle %d has mass 0 and is not a virtual site' % i)
+    if not sites:
+        return None
+    constrained = {p for (i, j, _) in system.constraints for p in (i, j)}
+    for s, site in sorted(sites.items()):
+        if not isinstance(site, VirtualSite) or site.kind not in (0, 1, 2):
+            raise NotImplementedError('virtual site %d: %s is not supported (TwoParticleAverageSite, ThreeParticleAverageSite and '
+                                      'OutOfPlaneSite are)' % (s, type(site).__name__))
+        if system.masses[s] != 0.0:
+            raise ValueError('virtual site %d has mass %g: a virtual site must have mass 0' % (s, system.masses[s]))
+        if s in constrained:
+            raise ValueError('virtual site %d takes part in a constraint' % s)
+        parents = [site.getParticle(k) for k in range(site.getNumParticles())]
+        for p in parents:
+            if not 0 <= p < n:
+                raise ValueError('virtual site %d: parent index %d out of range' % (s, p))
+            if p in sites:
+                raise NotImplementedError('virtual site %d: parent %d is itself a virtual site (sites on top of sites are not supported)' % (s, p))
+        if len(set(parents)) != len(parents):
+            raise ValueError('virtual site %d: a parent is named twice %r' % (s, tuple(parents)))
+    # molecules without the sites' own links: the parents of a site must already lie in one
+    root = list(range(n))
+
+    def find(a):
+        while root[a] != a:
+            root[a] = root[root[a]]
+            a = root[a]
+        return a
+
+    def unite(a, b):
+        a, b = find(a), find(b)
+        if a != b:
+            root[max(a, b)] = min(a, b)
+    for (i, j, _) in system.constraints:
+        unite(i, j)
+    for k in range(len(d['bond_atoms'])):
+        unite(int(d['bond_atoms'][k][0]), int(d['bond_atoms'][k][1]))
+    exc = [(int(e[0]), int(e[1])) for e in d['exception_atoms']]
+    for (i, j) in exc:
+        if i not in sites and j not in sites:
+            unite(i, j)
+    periodic = d['nb_method'] in (1, 2) or system.usesPeriodicBoundaryConditions()
+    linked = {s: set() for s in sites}
+    for (i, j) in exc:
+        if i in sites:
+            linked[i].add(j)
+        if j in sites:
+            linked[j].add(i)
+    order = sorted(sites)
+    molecule = []
+    for s in order:
+        site = sites[s]
+        parents = [site.getParticle(k) for k in range(site.getNumParticles())]
+        mols = {find(p) for p in parents}
+        if periodic and len(mols) != 1:
+            raise ValueError('virtual site %d: its parents %r lie in different molecules of a periodic System (positions are taken '
+                             'without minimum images; a molecule is kept whole)' % (s, tuple(parents)))
+        if periodic and d['nb_method'] in (1, 2) and not (linked[s] & set(parents)):
+            raise ValueError('virtual site %d has no exception with any of its parents: the engine counts it into their molecule '
+                             'through the exceptions of the NonbondedForce' % s)
+        molecule.append(min(mols))
+    width = np.full((len(order), 3), -1, dtype=np.int32)
+    weight = np.zeros((len(order), 3), dtype=np.float64)
+    for row, s in enumerate(order):
+        site = sites[s]
+        for k in range(site.getNumParticles()):
+            width[row, k] = site.getParticle(k)
+        weight[row, :len(site._weights)] = site._weights
+    return dict(site=np.array(order, dtype=np.int32), kind=np.array([sites[s].kind for s in order], dtype=np.int32),
+                parent=width, weight=weight, molecule=np.array(molecule, dtype=np.int32))
+
+
 def _is_restraint(force):
     from .forces import is_restraint_force
     return is_restraint_force(force)
@@ -1358,6 +1527,9 @@ def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
                 d['pme_grid'] = np.array(grid, dtype=np.int32)
                 if rcc > d['cutoff']:
                     d['coulomb_cutoff'] = rcc
+    sites = _virtual_site_table(system, d)          # (in front of the constraint classification: a site takes no part in it)
+    if sites is not None:
+        d['virtual_sites'] = sites
     settle, shake, shake_d = _classify_constraints(system)
     d['settle_atoms'] = np.array([s[:3] for s in settle], dtype=np.int32).reshape(-1, 3)
     d['settle_dOH'] = settle[0][3] if settle else 0.0
@@ -1424,6 +1596,20 @@ def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
     return d
 
 
+def virtual_site_from_openmm(site):
+    """An OpenMM virtual site as the class of the same name here; by the object's class name and getters, so that no OpenMM is needed."""
+    name = type(site).__name__
+    p = [int(site.getParticle(k)) for k in range(site.getNumParticles())] if hasattr(site, 'getNumParticles') else []
+    if name == 'TwoParticleAverageSite':
+        return TwoParticleAverageSite(p[0], p[1], site.getWeight(0), site.getWeight(1))
+    if name == 'ThreeParticleAverageSite':
+        return ThreeParticleAverageSite(p[0], p[1], p[2], site.getWeight(0), site.getWeight(1), site.getWeight(2))
+    if name == 'OutOfPlaneSite':
+        return OutOfPlaneSite(p[0], p[1], p[2], site.getWeight12(), site.getWeight13(), site.getWeightCross())
+    raise NotImplementedError('virtual site class %s is not supported (TwoParticleAverageSite, ThreeParticleAverageSite and '
+                              'OutOfPlaneSite are)' % name)
+
+
 def from_openmm(omm_system):
     """Convert a real ``openmm.System`` (only where OpenMM is importable; not exercised in CI here)."""
     import openmm
@@ -1436,6 +1622,9 @@ def from_openmm(omm_system):
     for i in range(omm_system.getNumConstraints()):
         p, q, dist = omm_system.getConstraintParameters(i)
         s.addConstraint(p, q, dist.value_in_unit(u.nanometer))
+    for i in range(omm_system.getNumParticles()):
+        if getattr(omm_system, 'isVirtualSite', lambda index: False)(i):
+            s.setVirtualSite(i, virtual_site_from_openmm(omm_system.getVirtualSite(i)))
     for f in omm_system.getForces():
         if isinstance(f, openmm.HarmonicBondForce):
             g = HarmonicBondForce()

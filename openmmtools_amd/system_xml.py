@@ -245,6 +245,9 @@ def _parse_restraint(e):
 def to_xml(system, pressure=None, temperature=None, barostat_frequency=25):
     """Serialise ``system`` (and, when ``pressure`` is given, a MonteCarloBarostat force in bar / kelvin, which is how
     the reference carries the pressure of an NPT ThermodynamicState, states.py:1020-1068)."""
+    if getattr(system, 'virtual_sites', None):
+        raise NotImplementedError('virtual sites in a System document (the <VirtualSite> elements of particles %s are not written)'
+                                  % sorted(system.virtual_sites)[:4])
     root = ET.Element('System', dict(openmmVersion='8.0', type='System', version='1'))
     box = ET.SubElement(root, 'PeriodicBoxVectors')
     for tag, v in zip('ABC', system.getDefaultPeriodicBoxVectors()):

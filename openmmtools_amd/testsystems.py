@@ -472,3 +472,148 @@ class CustomGBForceSystem(TestSystem):
         system.addForce(nonbonded)
         system.addForce(custom)
         self.system, self.positions = system, subrandom_particle_positions(n_particles, system.getDefaultPeriodicBoxVectors())
+
+
+# ---- water boxes (testsystems.py:2828-3170) --------------------------------------------------------------------------------------
+# The published rigid geometries and parameters of the water models, as data (nm, degrees, e, kJ/mol, amu).  No openmm.app here: the
+# box is built on a lattice at liquid density.  r_OM: distance of the TIP4P-Ew charge site from the oxygen along the HOH bisector;
+# r_OL / LOL: distance of a TIP5P lone pair from the oxygen and the angle between the two (Horn et al. 2004; Mahoney & Jorgensen 2000).
+WATER_MODELS = {
+    'tip3p':   dict(r_OH=0.09572, HOH=104.52, q_H=0.417, sigma_O=0.31507524065751241, eps_O=0.635968),
+    'spce':    dict(r_OH=0.1, HOH=109.47, q_H=0.4238, sigma_O=0.31657195050398818, eps_O=0.6497752),
+    'tip4pew': dict(r_OH=0.09572, HOH=104.52, q_H=0.52422, sigma_O=0.316435, eps_O=0.680946, r_OM=0.0125),
+    'tip5p':   dict(r_OH=0.09572, HOH=104.52, q_H=0.241, sigma_O=0.312, eps_O=0.66944, r_OL=0.07, LOL=109.47),
+}
+WATER_MASS_O, WATER_MASS_H = 15.99943, 1.007947
+WATER_NUMBER_DENSITY = 33.4        # molecules per nm^3 (0.997 g/cm^3)
+
+
+def water_site_weights(model):
+    """The virtual sites of one water of ``model`` as (class name, weights) from the published geometry: () for the three-site
+    models; TIP4P-Ew: a three-particle average over (O, H1, H2) with w_H = r_OM / (2 r_OH cos(HOH/2)), w_O = 1 - 2 w_H; TIP5P: two
+    out-of-plane sites with w12 = w13 = -r_OL cos(LOL/2) / (2 r_OH cos(HOH/2)) and wcross = +- r_OL sin(LOL/2) / (r_OH^2 sin HOH)."""
+    m = WATER_MODELS[model]
+    half = 0.5 * m['HOH'] * unit.degrees
+    if 'r_OM' in m:
+        w_h = m['r_OM'] / (2.0 * m['r_OH'] * np.cos(half))
+        return (('ThreeParticleAverageSite', (1.0 - 2.0 * w_h, w_h, w_h)),)
+    if 'r_OL' in m:
+        lone = 0.5 * m['LOL'] * unit.degrees
+        w = -m['r_OL'] * np.cos(lone) / (2.0 * m['r_OH'] * np.cos(half))
+        wc = m['r_OL'] * np.sin(lone) / (m['r_OH'] ** 2 * np.sin(2.0 * half))
+        return (('OutOfPlaneSite', (w, w, wc)), ('OutOfPlaneSite', (w, w, -wc)))
+    return ()
+
+
+class WaterBox(TestSystem):
+    """testsystems.py:2828-2976: a periodic box of rigid water, ``model`` one of 'tip3p', 'spce', 'tip4pew' (four sites) and 'tip5p'
+    (five sites); the reference's constructor arguments and defaults.  The charge site of TIP4P-Ew and the lone pairs of TIP5P are
+    virtual sites (System.setVirtualSite).  The reference fills the box with openmm.app's Modeller; here round(33.4 V) molecules
+    sit on a cubic lattice, each turned so that its hydrogens keep away from the molecules placed before -- minimise before running.
+    Not built here: flexible water (constrained=False) and ions (ionic_strength != 0).  ``ndof`` counts 6 per rigid water: the
+    sites are no degrees of freedom."""
+
+    def __init__(self, box_edge=25.0 * unit.angstroms, cutoff=DEFAULT_CUTOFF_DISTANCE, model='tip3p', switch_width=DEFAULT_SWITCH_WIDTH,
+                 constrained=True, dispersion_correction=True, nonbondedMethod=NonbondedForce.PME,
+                 ewaldErrorTolerance=DEFAULT_EWALD_ERROR_TOLERANCE, positive_ion='Na+', negative_ion='Cl-', ionic_strength=0.0, **kwargs):
+        super().__init__(**kwargs)
+        from .system import ThreeParticleAverageSite, OutOfPlaneSite
+        if model not in WATER_MODELS:
+            raise Exception("Specified water model '{}' is not in list of supported models: {}".format(model, str(sorted(WATER_MODELS))))
+        if not constrained:
+            raise NotImplementedError('WaterBox(constrained=False): flexible water is not built here')
+        if ionic_strength != 0.0:
+            raise NotImplementedError('WaterBox(ionic_strength=%r): ions are not built here' % (ionic_strength,))
+        m = WATER_MODELS[model]
+        box_edge, cutoff = float(unit.to_md(box_edge)), float(unit.to_md(cutoff))
+        sites = water_site_weights(model)
+        per = 3 + len(sites)
+        n_waters = max(1, int(round(WATER_NUMBER_DENSITY * box_edge ** 3)))
+        half = 0.5 * m['HOH'] * unit.degrees
+        d_hh = 2.0 * m['r_OH'] * np.sin(half)
+        q_site = -2.0 * m['q_H'] / len(sites) if sites else 0.0
+        system = System()
+        system.setDefaultPeriodicBoxVectors([box_edge, 0, 0], [0, box_edge, 0], [0, 0, box_edge])
+        nb = NonbondedForce()
+        nb.setNonbondedMethod(nonbondedMethod)
+        nb.setCutoffDistance(cutoff)
+        nb.setUseSwitchingFunction(False)
+        if switch_width is not None:
+            nb.setUseSwitchingFunction(True)
+            nb.setSwitchingDistance(cutoff - float(unit.to_md(switch_width)))
+        nb.setUseDispersionCorrection(bool(dispersion_correction))
+        nb.setEwaldErrorTolerance(ewaldErrorTolerance)
+        for w in range(n_waters):
+            o = system.addParticle(WATER_MASS_O)
+            h1, h2 = system.addParticle(WATER_MASS_H), system.addParticle(WATER_MASS_H)
+            nb.addParticle(0.0 if sites else -2.0 * m['q_H'], m['sigma_O'], m['eps_O'])
+            nb.addParticle(m['q_H'], 1.0, 0.0)
+            nb.addParticle(m['q_H'], 1.0, 0.0)
+            system.addConstraint(o, h1, m['r_OH'])
+            system.addConstraint(o, h2, m['r_OH'])
+            system.addConstraint(h1, h2, d_hh)
+            for (cls, weights) in sites:
+                s = system.addParticle(0.0)
+                nb.addParticle(q_site, 1.0, 0.0)
+                system.setVirtualSite(s, ThreeParticleAverageSite(o, h1, h2, *weights) if cls == 'ThreeParticleAverageSite'
+                                      else OutOfPlaneSite(o, h1, h2, *weights))
+            for a in range(o, o + per):
+                for b in range(a + 1, o + per):
+                    nb.addException(a, b, 0.0, 1.0, 0.0)
+        system.addForce(nb)
+        self.system = system
+        self.model, self.n_waters, self.sites_per_water = model, n_waters, len(sites)
+        self.positions = self._lattice_positions(m, sites, n_waters, box_edge)
+        self.ndof = 6 * n_waters
+
+    @staticmethod
+    def _lattice_positions(m, sites, n_waters, box_edge):
+        from . import virtual_sites
+        half = 0.5 * m['HOH'] * unit.degrees
+        # one water: O at the origin, the hydrogens in the xy plane about the x axis
+        local = np.array([[0.0, 0.0, 0.0], [m['r_OH'] * np.cos(half), m['r_OH'] * np.sin(half), 0.0],
+                          [m['r_OH'] * np.cos(half), -m['r_OH'] * np.sin(half), 0.0]])
+        side = int(np.ceil(n_waters ** (1.0 / 3.0) - 1e-9))
+        cell = box_edge / side
+        rng = np.random.RandomState(20041001)
+        per = 3 + len(sites)
+        pos = np.zeros((n_waters * per, 3))
+        placed = np.zeros((0, 3))
+        for w in range(n_waters):
+            centre = (np.array([w % side, (w // side) % side, w // (side * side)]) + 0.5) * cell
+            best, best_d = None, -1.0
+            for _ in range(24):
+                q = rng.normal(size=4)
+                q /= np.linalg.norm(q)
+                a, b, c, d = q
+                rot = np.array([[a * a + b * b - c * c - d * d, 2 * (b * c - a * d), 2 * (b * d + a * c)],
+                                [2 * (b * c + a * d), a * a - b * b + c * c - d * d, 2 * (c * d - a * b)],
+                                [2 * (b * d - a * c), 2 * (c * d + a * b), a * a - b * b - c * c + d * d]])
+                trial = centre + local @ rot.T
+                if len(placed) == 0:
+                    best = trial
+                    break
+                delta = trial[1:, None, :] - placed[None, :, :]
+                delta -= box_edge * np.round(delta / box_edge)
+                dmin = np.sqrt((delta ** 2).sum(axis=2)).min()
+                if dmin > best_d:
+                    best, best_d = trial, dmin
+            pos[w * per:w * per + 3] = best
+            placed = np.vstack([placed, best])
+            for k, (cls, weights) in enumerate(sites):
+                pos[w * per + 3 + k] = virtual_sites.place(cls, best, weights)
+        return pos
+
+
+class FourSiteWaterBox(WaterBox):
+    """testsystems.py:3099-3125: a TIP4P-Ew water box."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(model='tip4pew', *args, **kwargs)
+
+
+class FiveSiteWaterBox(WaterBox):
+    """testsystems.py:3128-3154: a TIP5P water box."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(model='tip5p', *args, **kwargs)

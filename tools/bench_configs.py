@@ -353,6 +353,20 @@ def main():
         s = ReplicaExchangeSampler(mcmc_moves=move(2.0, 'V R R O R R V'), number_of_iterations=10 ** 9, engine=HipEngine(), seed=1)
         s.create(ths, [states.SamplerState(t.positions)])
         run('%s: %s (%d atoms, NoCutoff), %d temperatures, swap-all, g-BAOAB 2 fs x 500' % (tag, cls, t.system.getNumParticles(), nt), s, 5)
+    for tag, model in (('w3', 'tip3p'), ('w4', 'tip4pew')):
+        if tag not in which:
+            continue
+        # a water box of 522 molecules (testsystems.WaterBox at its default 2.5 nm edge) as three-site TIP3P and as four-site TIP4P-Ew,
+        # whose charge site is a virtual site (csrc/virtual_sites.hip): the same molecule count, 24 temperatures, the headline's protocol;
+        # the difference per iteration is what the sites cost (one more particle per water, the two launches per force evaluation, the
+        # join by a launch instead of in the chain).  The lattice start is relaxed by FIRE first.
+        wb = testsystems.WaterBox(model=model)
+        ths = [states.ThermodynamicState(wb.system, T) for T in np.geomspace(300.0, 400.0, 24)]
+        s = ReplicaExchangeSampler(mcmc_moves=move(2.0, 'V R R O R R V'), number_of_iterations=10 ** 9, engine=HipEngine(), seed=1)
+        s.create(ths, [states.SamplerState(wb.positions, box_vectors=wb.system.getDefaultPeriodicBoxVectors())])
+        s.minimize(max_iterations=200)
+        run('%s: WaterBox(%s), %d waters = %d particles, 24 temperatures, swap-all, g-BAOAB 2 fs x 500'
+            % (tag, model, wb.n_waters, wb.system.getNumParticles()), s, 3)
     if 'n' in which:
         # the headline ensemble at constant pressure (NPT states: Monte Carlo barostat every 25 steps inside the propagation)
         al = testsystems.AlanineDipeptideExplicit()
