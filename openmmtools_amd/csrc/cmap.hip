@@ -60,7 +60,7 @@ void cmap_kernel(int total_pad, int w0, int waves, const cst_force* __restrict__
 
 void remd_cmap_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st)
 {
-    const int waves = t.total_pad / 64, w0 = t.waves_cv;
+    const int waves = t.total_pad / 64, w0 = t.begin(CST_CMAP);
     if (with_energy)
         hipLaunchKernelGGL(cmap_kernel<true>, dim3(waves - w0, h->R), dim3(64), 0, st, t.total_pad, w0, waves, t.d_F, t.d_wave_force, t.d_atoms,
                            t.d_map_index, t.d_map_off, t.d_consts, h->Npad, h->d_pos, h->d_box, h->d_force, t.d_Ewave);

@@ -157,16 +157,16 @@ void launch_centroids(remd_ctx* h, cst_tables& t, hipStream_t st)
 // (the caller, remd_custom_forces, has sized d_C and d_G: ensure_buffers of custom_terms.hip)
 void remd_custom_centroid_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st)
 {
-    const int waves = t.total_pad / 64, w0 = t.waves_particles;
+    const int waves = t.total_pad / 64, w0 = t.begin(CST_CENTROID);
     launch_centroids(h, t, st);
     {
         remd_prof_scope ps(h, "custom_centroid_bonds", st);
         if (with_energy)
-            hipLaunchKernelGGL(custom_centroid_bonds_kernel<true>, dim3(t.waves_centroid - w0, h->R), dim3(64), 0, st, t.total_pad, w0, waves, t.d_F,
+            hipLaunchKernelGGL(custom_centroid_bonds_kernel<true>, dim3(t.end(CST_CENTROID) - w0, h->R), dim3(64), 0, st, t.total_pad, w0, waves, t.d_F,
                                t.d_wave_force, t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, h->d_labels, h->r_begin, t.n_groups,
                                t.d_C, h->d_box, t.d_G, t.d_Ewave);
         else
-            hipLaunchKernelGGL(custom_centroid_bonds_kernel<false>, dim3(t.waves_centroid - w0, h->R), dim3(64), 0, st, t.total_pad, w0, waves, t.d_F,
+            hipLaunchKernelGGL(custom_centroid_bonds_kernel<false>, dim3(t.end(CST_CENTROID) - w0, h->R), dim3(64), 0, st, t.total_pad, w0, waves, t.d_F,
                                t.d_wave_force, t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, h->d_labels, h->r_begin, t.n_groups,
                                t.d_C, h->d_box, t.d_G, t.d_Ewave);
     }
@@ -177,9 +177,9 @@ void remd_custom_centroid_forces(remd_ctx* h, cst_tables& t, bool with_energy, h
 
 void remd_custom_centroid_ukl(remd_ctx* h, cst_tables& t)
 {
-    const int waves = t.total_pad / 64, w0 = t.waves_particles;
+    const int waves = t.total_pad / 64, w0 = t.begin(CST_CENTROID);
     launch_centroids(h, t, h->stream);
-    hipLaunchKernelGGL(custom_centroid_ukl_kernel, dim3(t.waves_centroid - w0, h->R), dim3(64), 0, h->stream, t.total_pad, w0, waves, t.d_F, t.d_wave_force,
+    hipLaunchKernelGGL(custom_centroid_ukl_kernel, dim3(t.end(CST_CENTROID) - w0, h->R), dim3(64), 0, h->stream, t.total_pad, w0, waves, t.d_F, t.d_wave_force,
                        t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, h->K, h->d_labels, h->r_begin, t.n_groups, t.d_C, h->d_box,
                        t.d_D);
 }

@@ -107,21 +107,21 @@ void custom_compound_ukl_kernel(int total_pad, int w0, int waves, const cst_forc
 
 void remd_custom_compound_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st)
 {
-    const int waves = t.total_pad / 64, w0 = t.waves_simple;
+    const int waves = t.total_pad / 64, w0 = t.begin(CST_COMPOUND);
     if (with_energy)
-        hipLaunchKernelGGL(custom_compound_kernel<true>, dim3(t.waves_compound - w0, h->R), dim3(64), 0, st, t.total_pad, w0, waves, t.d_F, t.d_wave_force,
+        hipLaunchKernelGGL(custom_compound_kernel<true>, dim3(t.end(CST_COMPOUND) - w0, h->R), dim3(64), 0, st, t.total_pad, w0, waves, t.d_F, t.d_wave_force,
                            t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, h->d_labels, h->r_begin, h->Npad, h->d_pos, h->d_box,
                            h->d_force, t.d_Ewave);
     else
-        hipLaunchKernelGGL(custom_compound_kernel<false>, dim3(t.waves_compound - w0, h->R), dim3(64), 0, st, t.total_pad, w0, waves, t.d_F, t.d_wave_force,
+        hipLaunchKernelGGL(custom_compound_kernel<false>, dim3(t.end(CST_COMPOUND) - w0, h->R), dim3(64), 0, st, t.total_pad, w0, waves, t.d_F, t.d_wave_force,
                            t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, h->d_labels, h->r_begin, h->Npad, h->d_pos, h->d_box,
                            h->d_force, t.d_Ewave);
 }
 
 void remd_custom_compound_ukl(remd_ctx* h, cst_tables& t)
 {
-    const int waves = t.total_pad / 64, w0 = t.waves_simple;
-    hipLaunchKernelGGL(custom_compound_ukl_kernel, dim3(t.waves_compound - w0, h->R), dim3(64), 0, h->stream, t.total_pad, w0, waves, t.d_F, t.d_wave_force,
+    const int waves = t.total_pad / 64, w0 = t.begin(CST_COMPOUND);
+    hipLaunchKernelGGL(custom_compound_ukl_kernel, dim3(t.end(CST_COMPOUND) - w0, h->R), dim3(64), 0, h->stream, t.total_pad, w0, waves, t.d_F, t.d_wave_force,
                        t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, h->K, h->d_labels, h->r_begin, h->Npad, h->d_pos, h->d_box,
                        t.d_D);
 }

@@ -216,15 +216,15 @@ size_t remd_custom_cv_w() { return CV_W; }
 // (the caller, remd_custom_forces, has sized d_W: ensure_buffers of custom_terms.hip)
 void remd_custom_cv_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st)
 {
-    const int waves = t.total_pad / 64, w0 = t.waves_centroid;
+    const int waves = t.total_pad / 64, w0 = t.begin(CST_CV);
     launch_superpose(h, t, st);
     {
         remd_prof_scope ps(h, "custom_cv_expression", st);
         if (with_energy)
-            hipLaunchKernelGGL(custom_cv_expression_kernel<true>, dim3(t.waves_cv - w0, h->R), dim3(64), 0, st, w0, waves, t.d_F, t.d_wave_force,
+            hipLaunchKernelGGL(custom_cv_expression_kernel<true>, dim3(t.end(CST_CV) - w0, h->R), dim3(64), 0, st, w0, waves, t.d_F, t.d_wave_force,
                                t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, h->d_labels, h->r_begin, t.n_cv, t.d_W, t.d_Ewave);
         else
-            hipLaunchKernelGGL(custom_cv_expression_kernel<false>, dim3(t.waves_cv - w0, h->R), dim3(64), 0, st, w0, waves, t.d_F, t.d_wave_force,
+            hipLaunchKernelGGL(custom_cv_expression_kernel<false>, dim3(t.end(CST_CV) - w0, h->R), dim3(64), 0, st, w0, waves, t.d_F, t.d_wave_force,
                                t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, h->d_labels, h->r_begin, t.n_cv, t.d_W, t.d_Ewave);
     }
     remd_prof_scope ps(h, "custom_cv_spread", st);
@@ -234,8 +234,8 @@ void remd_custom_cv_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStre
 
 void remd_custom_cv_ukl(remd_ctx* h, cst_tables& t)
 {
-    const int waves = t.total_pad / 64, w0 = t.waves_centroid;
+    const int waves = t.total_pad / 64, w0 = t.begin(CST_CV);
     launch_superpose(h, t, h->stream);
-    hipLaunchKernelGGL(custom_cv_ukl_kernel, dim3(t.waves_cv - w0, h->R), dim3(64), 0, h->stream, w0, waves, t.d_F, t.d_wave_force, t.d_par, t.d_prog,
+    hipLaunchKernelGGL(custom_cv_ukl_kernel, dim3(t.end(CST_CV) - w0, h->R), dim3(64), 0, h->stream, w0, waves, t.d_F, t.d_wave_force, t.d_par, t.d_prog,
                        t.d_consts, t.d_glob, t.ng, h->K, h->d_labels, h->r_begin, t.n_cv, t.d_W, t.d_D);
 }

@@ -1,7 +1,7 @@
 // The stack machine of the custom forces (include/remd_hip_custom.h), shared by custom_terms.hip (bond, angle, torsion, external),
 // custom_compound.hip (compound bonds), custom_centroid.hip (centroid bonds, whose particles are centroids) and custom_cv.hip
-// (collective variables, whose variables are RMSDs): the per-force record, the handle's tables, and cst_eval, which runs a postfix
-// program one term per lane with every stack slot a value and three partials, the stack in LDS as [slot][component][lane].
+// (collective variables, whose variables are RMSDs): the handle's tables (the per-force record and the host plan behind them live in
+// custom_plan.h, which needs no HIP) and cst_eval, which runs a postfix program one term per lane with every stack slot a value and three partials, the stack in LDS as [slot][component][lane].
 // cmap.hip (CMAP torsion maps) runs no program: it shares the record, the tables and the patch of two arguments (table2d_patch.h).
 //
 // cst_eval<GEOM>: the instantiation of the four one-variable kinds (GEOM = false) has the variables in three registers and no case
@@ -14,70 +14,24 @@
 // REMD_CX_TABLE2D / REMD_CX_LOOKUP2D / REMD_CX_LOOKUP3D (cst_table2d, cst_lookup2d, cst_lookup3d).
 #pragma once
 #include "remd_internal.h"
-#include "../../include/remd_hip_custom.h"
+#include "custom_plan.h"
 #include "table2d_patch.h"
 
-struct cst_force {
-    int kind, periodic, n_terms, n_params;
-    int n_particles;             // atoms per term (the particles per bond of a compound-bond force, the groups per bond of a centroid force)
-    int slot0, npad;             // first slot in the padded term space of the launch / slots of this force (a multiple of 64)
-    int par0;                    // offset of its parameters [n_params][npad]
-    int prog0, n_prog, const0;   // its program and constants in the handle's tables
-    // REMD_CUSTOM_NONBONDED only (custom_nonbonded.hip): n_terms = N particles, npad = 64 x its upper-triangular tiles, parameters [n_params][Npad]
-    int nb_method;               // 0 NoCutoff, 1 CutoffNonPeriodic, 2 CutoffPeriodic
-    int excl0;                   // its row offsets [N + 1] in the handle's excl_off (which point into the handle's excl_atoms)
-    int lrc;                     // 1: it has a long-range correction (the handle's lrc table carries its column)
-    double cutoff, switch_dist;  // switch_dist < 0: no switching function
-    // REMD_CUSTOM_CV only (custom_cv.hip): n_terms = 1, npad = 64, no atoms of its own
-    int cv0, n_cvs;              // its first collective variable among the handle's, and how many it has (1 ... 3)
-    // REMD_CUSTOM_CMAP only (cmap.hip): n_particles = 8, no program and no parameters; its constants are its maps' blocks
-    int map0, n_maps;            // its first map among the handle's map_off, and how many it has (1 ... REMD_CUSTOM_MAX_MAPS)
-};
-
-struct cst_tables {
-    int nf = 0, ng = 0, K = 0, total_pad = 0, waves_simple = 0; long long glob_version = -1;   // (waves_simple: the wavefronts of the four one-variable kinds, in front; glob belongs to the states of that remd_set_states)
-    int waves_compound = 0;                                                    // where the compound-bond forces' wavefronts end and the nonbonded forces' tiles begin
-    int waves_particles = 0;                                                   // where the nonbonded forces' tiles end and the centroid forces' wavefronts begin
-    int waves_centroid = 0;                                                    // where the centroid forces' wavefronts end and the collective-variable forces' begin
-    int waves_cv = 0;                                                          // where the collective-variable forces' wavefronts end and the CMAP forces' begin (the last part)
-    int n_cv = 0;                                                              // the collective variables of all such forces (0: no such force, none of the cv members below holds anything)
-    int n_groups = 0;                                                          // the groups of all centroid forces (0: no centroid force, none of the members below holds anything)
-    bool uniform = true;                                                       // every state carries the same globals: no u_kl share
-    std::vector<cst_force> F; std::vector<int> wave_force, atoms; std::vector<double> par, consts, glob, defaults; std::vector<int2> prog;
-    dev_array<cst_force> d_F; dev_array<int> d_wave_force; dev_array<int> d_atoms;      // atoms [max(4, most particles per bond)][total_pad]
-    dev_array<double> d_par; dev_array<double> d_consts; dev_array<double> d_glob; dev_array<int2> d_prog;
+// what a handle with custom forces owns: the plan of the set-up (custom_plan.h: every host table, the scalars and the parts of the
+// padded term space), its tables on the device under the same names with d_ in front, and the work buffers of the launches
+struct cst_tables : cst_plan {
+    dev_array<cst_force> d_F; dev_array<int> d_wave_force, d_atoms; dev_array<double> d_par, d_consts, d_glob; dev_array<int2> d_prog;
+    dev_array<int> d_grp_off, d_grp_atoms, d_grp_periodic, d_ref_off, d_refs; dev_array<double> d_grp_w;
+    dev_array<int> d_cv_off, d_cv_atoms; dev_array<double> d_cv_ref;
+    dev_array<int> d_map_off, d_map_index;
+    dev_array<int> d_excl_off, d_excl_atoms; dev_array<double> d_lrc;
+    dev_array<int> d_mol_first, d_mol_size;
     dev_array<double> d_E;             // [R][nf]
     dev_array<double> d_Ewave;         // [R][total_pad / 64]
     dev_array<double> d_D;             // [R][K][total_pad / 64] u_kl partials
-    // centroid forces (custom_centroid.hip): a centroid force's row of `atoms` holds handle-wide group numbers
-    std::vector<int> grp_off, grp_atoms, grp_periodic, ref_off, refs; std::vector<double> grp_w;
-    dev_array<int> d_grp_off;          // [n_groups + 1] into grp_atoms / grp_w
-    dev_array<int> d_grp_atoms; dev_array<double> d_grp_w;      // the groups' atoms and their weights (sum 1 per group)
-    dev_array<int> d_grp_periodic;     // [n_groups]: the flag of the force the group belongs to
-    dev_array<int> d_ref_off;          // [n_groups + 1] into refs
-    dev_array<int> d_refs;             // (centroid slot * REMD_CUSTOM_MAX_PARTICLES + position in the bond) of every bond that names the group, in table order
     dev_array<double> d_C;             // [R][n_groups][3] centroids
     dev_array<double> d_G;             // [R][centroid slots][REMD_CUSTOM_MAX_PARTICLES][3] dE / d centroid
-    // collective-variable forces (custom_cv.hip): the RMSD variables of all of them in CSR form (cst_force::cv0 names a force's first)
-    std::vector<int> cv_off, cv_atoms; std::vector<double> cv_ref;
-    dev_array<int> d_cv_off;           // [n_cv + 1] into cv_atoms / cv_ref
-    dev_array<int> d_cv_atoms;         // the variables' particles
-    dev_array<double> d_cv_ref;        // beside cv_atoms, [.][3]: the reference, centred on each variable's own centroid
     dev_array<double> d_W;             // [R][n_cv][16]: RMSD, "no force" flag, centroid, rotation, dE/dRMSD (custom_cv.hip)
-    // CMAP forces (cmap.hip): the maps of all of them and the map of every slot of their part of the padded term space
-    std::vector<int> map_off, map_index;
-    dev_array<int> d_map_off;          // per map the offset of its block in consts (cst_force::map0 names a force's first)
-    dev_array<int> d_map_index;        // [total_pad - 64 waves_cv]: the slot's map among its force's, 0 ... n_maps - 1 (a padding slot repeats the last term's)
-    // nonbonded forces (custom_nonbonded.hip): the exclusion rows of all of them, and the long-range coefficients of the states
-    std::vector<int> excl_off, excl_atoms; std::vector<double> lrc;
-    dev_array<int> d_excl_off;         // per nonbonded force N + 1 offsets into excl_atoms (cst_force::excl0 names the first)
-    dev_array<int> d_excl_atoms;       // symmetric, sorted within a row
-    dev_array<double> d_lrc;           // [K][nf] kJ/mol nm^3: the energy is lrc[state][force] / V (zero for a force without the correction)
-    bool has_lrc = false, lrc_valid = false;   // (lrc_valid: remd_set_custom_lrc ran since the globals were last set)
-    double periodic_cutoff = 0.0;      // the longest cutoff of a CutoffPeriodic nonbonded force (remd_ctx::cst_cutoff)
-    // the molecules a barostat moves as wholes where the handle has no NonbondedForce to take them from (remd_custom_molecules): atoms
-    // the custom bonds, angles, torsions and compound bonds join, each a contiguous range [first, first + size); empty: no table
-    std::vector<int> mol_first, mol_size; dev_array<int> d_mol_first; dev_array<int> d_mol_size;
 };
 
 namespace {
@@ -345,20 +299,20 @@ __device__ __forceinline__ double cst_wave_sum(double v)
 
 }  // namespace
 
-// custom_compound.hip: the launches of the compound-bond forces' wavefronts (those behind waves_simple), on the stream and between the
+// custom_compound.hip: the launches of the compound-bond forces' wavefronts (the part CST_COMPOUND), on the stream and between the
 // launches of remd_custom_forces / remd_custom_ukl
 void remd_custom_compound_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
 void remd_custom_compound_ukl(remd_ctx* h, cst_tables& t);
-// custom_centroid.hip: the same for the centroid forces' wavefronts (those behind waves_particles): centroids, bonds, spread
+// custom_centroid.hip: the same for the centroid forces' wavefronts (the part CST_CENTROID): centroids, bonds, spread
 void remd_custom_centroid_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
 void remd_custom_centroid_ukl(remd_ctx* h, cst_tables& t);
-// custom_cv.hip: the same for the collective-variable forces' wavefronts (those behind waves_centroid): superposition, expression, spread
+// custom_cv.hip: the same for the collective-variable forces' wavefronts (the part CST_CV): superposition, expression, spread
 void remd_custom_cv_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
 void remd_custom_cv_ukl(remd_ctx* h, cst_tables& t);
 size_t remd_custom_cv_w();             // doubles per (replica, variable) of cst_tables::d_W; the RMSD is the first
-// cmap.hip: the force launch of the CMAP forces' wavefronts (those behind waves_cv); they have no globals, so no u_kl launch
+// cmap.hip: the force launch of the CMAP forces' wavefronts (the part CST_CMAP); they have no globals, so no u_kl launch
 void remd_cmap_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
-// custom_nonbonded.hip: the same for the nonbonded forces' tiles (those between waves_compound and waves_particles), and the long-range
+// custom_nonbonded.hip: the same for the nonbonded forces' tiles (the part CST_NONBONDED), and the long-range
 // correction's share of the energies (behind custom_reduce_kernel) and of the u_kl rows (behind custom_ukl_reduce_kernel)
 void remd_custom_nonbonded_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
 void remd_custom_nonbonded_lrc(remd_ctx* h, cst_tables& t, int ep_slot, hipStream_t st);

@@ -225,13 +225,13 @@ void custom_nonbonded_lrc_ukl_kernel(int nf, int K, const cst_force* __restrict_
 
 void remd_custom_nonbonded_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st)
 {
-    const int waves = t.total_pad / 64, w0 = t.waves_compound;
+    const int waves = t.total_pad / 64, w0 = t.begin(CST_NONBONDED);
     if (with_energy)
-        hipLaunchKernelGGL(custom_nonbonded_kernel<true>, dim3(t.waves_particles - w0, h->R), dim3(64), 0, st, w0, waves, t.d_F, t.d_wave_force,
+        hipLaunchKernelGGL(custom_nonbonded_kernel<true>, dim3(t.end(CST_NONBONDED) - w0, h->R), dim3(64), 0, st, w0, waves, t.d_F, t.d_wave_force,
                            t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, t.d_excl_off, t.d_excl_atoms, h->d_labels, h->r_begin, h->Npad,
                            h->d_pos, h->d_box, h->d_force, t.d_Ewave);
     else
-        hipLaunchKernelGGL(custom_nonbonded_kernel<false>, dim3(t.waves_particles - w0, h->R), dim3(64), 0, st, w0, waves, t.d_F, t.d_wave_force,
+        hipLaunchKernelGGL(custom_nonbonded_kernel<false>, dim3(t.end(CST_NONBONDED) - w0, h->R), dim3(64), 0, st, w0, waves, t.d_F, t.d_wave_force,
                            t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, t.d_excl_off, t.d_excl_atoms, h->d_labels, h->r_begin, h->Npad,
                            h->d_pos, h->d_box, h->d_force, t.d_Ewave);
 }
@@ -244,8 +244,8 @@ void remd_custom_nonbonded_lrc(remd_ctx* h, cst_tables& t, int ep_slot, hipStrea
 
 void remd_custom_nonbonded_ukl(remd_ctx* h, cst_tables& t)
 {
-    const int waves = t.total_pad / 64, w0 = t.waves_compound;
-    hipLaunchKernelGGL(custom_nonbonded_ukl_kernel, dim3(t.waves_particles - w0, h->R), dim3(64), 0, h->stream, w0, waves, t.d_F, t.d_wave_force,
+    const int waves = t.total_pad / 64, w0 = t.begin(CST_NONBONDED);
+    hipLaunchKernelGGL(custom_nonbonded_ukl_kernel, dim3(t.end(CST_NONBONDED) - w0, h->R), dim3(64), 0, h->stream, w0, waves, t.d_F, t.d_wave_force,
                        t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, h->K, t.d_excl_off, t.d_excl_atoms, h->d_labels, h->r_begin, h->Npad,
                        h->d_pos, h->d_box, t.d_D);
 }

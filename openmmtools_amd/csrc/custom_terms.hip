@@ -197,7 +197,7 @@ int ensure_buffers(remd_ctx* h, cst_tables& t)
     }
     if (t.d_Ewave.size() != (size_t)h->R * waves) REMD_TRY(t.d_Ewave.alloc(h, (size_t)h->R * waves));
     // centroid forces: the centroids and the gradients on them (a handle without such a force: n_groups = 0, nothing is allocated)
-    const size_t nC = (size_t)h->R * t.n_groups * 3, nG = (size_t)h->R * (waves - t.waves_particles) * 64 * REMD_CUSTOM_MAX_PARTICLES * 3;
+    const size_t nC = (size_t)h->R * t.n_groups * 3, nG = (size_t)h->R * (waves - t.begin(CST_CENTROID)) * 64 * REMD_CUSTOM_MAX_PARTICLES * 3;
     if (t.d_C.size() != nC) REMD_TRY(t.d_C.alloc(h, nC));
     if (t.d_G.size() != nG) REMD_TRY(t.d_G.alloc(h, nG));
     // collective-variable forces: what the superposition hands on (n_cv = 0: nothing is allocated)
@@ -206,12 +206,16 @@ int ensure_buffers(remd_ctx* h, cst_tables& t)
     return 0;
 }
 
-int set_tables(remd_ctx* h, cst_tables& t)
+// the one list of the plan's tables: each to the device array of its name; the work buffers are forgotten (ensure_buffers)
+int upload_tables(remd_ctx* h, cst_tables& t)
 {
     int rc;
+    // (the programs are int32 pairs on the host and int2 to the kernels)
+    if ((rc = t.d_prog.alloc(h, t.prog.size() / 2))) return rc;
+    if (!t.prog.empty()) REMD_CHECK(h, hipMemcpy(t.d_prog, t.prog.data(), sizeof(int) * t.prog.size(), hipMemcpyHostToDevice));
     if ((rc = t.d_F.upload(h, t.F)) || (rc = t.d_wave_force.upload(h, t.wave_force)) || (rc = t.d_atoms.upload(h, t.atoms)) ||
         (rc = t.d_par.upload(h, t.par)) || (rc = t.d_consts.upload(h, t.consts)) || (rc = t.d_glob.upload(h, t.glob)) ||
-        (rc = t.d_prog.upload(h, t.prog)) || (rc = t.d_grp_off.upload(h, t.grp_off)) || (rc = t.d_grp_atoms.upload(h, t.grp_atoms)) ||
+        (rc = t.d_grp_off.upload(h, t.grp_off)) || (rc = t.d_grp_atoms.upload(h, t.grp_atoms)) ||
         (rc = t.d_grp_w.upload(h, t.grp_w)) || (rc = t.d_grp_periodic.upload(h, t.grp_periodic)) || (rc = t.d_ref_off.upload(h, t.ref_off)) ||
         (rc = t.d_refs.upload(h, t.refs)) || (rc = t.d_excl_off.upload(h, t.excl_off)) || (rc = t.d_excl_atoms.upload(h, t.excl_atoms)) ||
         (rc = t.d_lrc.upload(h, t.lrc)) || (rc = t.d_mol_first.upload(h, t.mol_first)) || (rc = t.d_mol_size.upload(h, t.mol_size)) ||
@@ -227,85 +231,14 @@ bool globals_uniform(const cst_tables& t)
     return true;
 }
 
-// what a program may do is settled here, once: the kernels index the stack, the constants, the parameters and the globals unchecked
-const char* check_program(const remd_custom_force_desc& d, int n_vars)
+// what a launch refuses to act on: globals of an older set of states, coefficients older than the globals
+int check_current(remd_ctx* h, const cst_tables& t)
 {
-    const bool compound = d.kind == REMD_CUSTOM_COMPOUND || d.kind == REMD_CUSTOM_CENTROID;
-    const int n_par = d.kind == REMD_CUSTOM_NONBONDED ? 2 * d.n_params : d.n_params;     // (a pair: particle 1's parameters, then particle 2's)
-    if (d.n_program <= 0 || !d.program) return "an empty program";
-    if (d.n_program > REMD_CUSTOM_MAX_PROGRAM) return "a program over REMD_CUSTOM_MAX_PROGRAM instructions";
-    int sp = 0, top = 0;
-    for (int pc = 0; pc < d.n_program; ++pc) {
-        const int op = d.program[2 * pc], arg = d.program[2 * pc + 1];
-        int pops = 1;
-        switch (op) {
-        case REMD_CX_CONST:  if (arg < 0 || arg >= d.n_consts || !d.consts) return "a constant index out of range"; pops = 0; break;
-        case REMD_CX_VAR:    if (arg < 0 || arg >= n_vars) return "a variable index out of range"; pops = 0; break;
-        case REMD_CX_PARAM:  if (arg < 0 || arg >= n_par) return "a parameter index out of range"; pops = 0; break;
-        case REMD_CX_GLOBAL: if (arg < 0 || arg >= d.n_globals) return "a global-parameter index out of range"; pops = 0; break;
-        case REMD_CX_ADD: case REMD_CX_SUB: case REMD_CX_MUL: case REMD_CX_DIV: case REMD_CX_POW: case REMD_CX_ATAN2:
-        case REMD_CX_MIN: case REMD_CX_MAX: pops = 2; break;
-        case REMD_CX_SELECT: pops = 3; break;
-        case REMD_CX_PERIODICDISTANCE: pops = 6; break;
-        case REMD_CX_DISTANCE: case REMD_CX_ANGLE: case REMD_CX_DIHEDRAL: {
-            // the zero-based particle slots in 4-bit fields, first argument lowest; nothing above them
-            if (!compound) return "a function of particles outside a compound-bond or centroid-bond force";
-            const int n_args = op - REMD_CX_DISTANCE + 2;
-            if (arg < 0 || (arg >> (4 * n_args)) != 0) return "a particle slot out of range";
-            for (int k = 0; k < n_args; ++k) if (((arg >> (4 * k)) & 15) >= d.n_particles) return "a particle slot out of range";
-            pops = 0;
-        } break;
-        case REMD_CX_POWI: if (arg < -64 || arg > 64) return "an integer power beyond +-64"; break;
-        case REMD_CX_TABLE1D: case REMD_CX_LOOKUP1D: {
-            // the block of the function at consts[arg] (include/remd_hip_custom.h): the kernels trust n, min, max and the block's extent
-            const bool spline = op == REMD_CX_TABLE1D;
-            if (arg < 0 || arg >= d.n_consts || !d.consts) return "a table offset out of range";
-            const double n = d.consts[arg];
-            if (!(n >= (spline ? 2.0 : 1.0) && n <= (double)REMD_CUSTOM_MAX_TABLE_POINTS) || n != floor(n))
-                return spline ? "a table whose point count is not an integer 2 ... REMD_CUSTOM_MAX_TABLE_POINTS"
-                              : "a lookup table whose value count is not an integer 1 ... REMD_CUSTOM_MAX_TABLE_POINTS";
-            if ((long long)arg + (spline ? 4 + 2 * (long long)n : 1 + (long long)n) > (long long)d.n_consts) return "a table that runs past n_consts";
-            if (spline) {
-                const double lo = d.consts[arg + 1], hi = d.consts[arg + 2], periodic = d.consts[arg + 3];
-                if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi)) return "a table whose bounds are not finite with min < max";
-                if (periodic != 0.0 && periodic != 1.0) return "a table whose periodic flag is neither 0 nor 1";
-            }
-        } break;
-        case REMD_CX_TABLE2D: case REMD_CX_LOOKUP2D: case REMD_CX_LOOKUP3D: {
-            // the same for the blocks of two and three arguments: the sizes, their product, the bounds and the extent
-            const bool patch = op == REMD_CX_TABLE2D;
-            const int dims = op == REMD_CX_LOOKUP3D ? 3 : 2, header = patch ? 8 : dims == 3 ? 4 : 2;
-            if (arg < 0 || arg >= d.n_consts || !d.consts) return "a table offset out of range";
-            if ((long long)arg + header > (long long)d.n_consts) return "a table that runs past n_consts";
-            double cells = 1.0;
-            for (int k = 0; k < dims; ++k) {
-                const double n = d.consts[arg + k];
-                if (!(n >= (patch ? 2.0 : 1.0) && n <= (double)REMD_CUSTOM_MAX_TABLE_CELLS) || n != floor(n))
-                    return patch ? "a 2D table whose size is not an integer 2 ... REMD_CUSTOM_MAX_TABLE_CELLS"
-                                 : "a lookup table whose size is not an integer 1 ... REMD_CUSTOM_MAX_TABLE_CELLS";
-                cells *= n;
-            }
-            if (cells > (double)REMD_CUSTOM_MAX_TABLE_CELLS) return "a table of more than REMD_CUSTOM_MAX_TABLE_CELLS cells";
-            if ((long long)arg + header + (patch ? 4 : 1) * (long long)cells > (long long)d.n_consts) return "a table that runs past n_consts";
-            if (patch) {
-                for (int k = 0; k < 2; ++k) {
-                    const double lo = d.consts[arg + 2 + 2 * k], hi = d.consts[arg + 3 + 2 * k];
-                    if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi)) return "a table whose bounds are not finite with min < max";
-                }
-                if (d.consts[arg + 6] != 0.0 && d.consts[arg + 6] != 1.0) return "a table whose periodic flag is neither 0 nor 1";
-            }
-            pops = dims;
-        } break;
-        default: if (op < 0 || op >= REMD_CX_N_OPCODES) return "an unknown opcode"; break;
-        }
-        if (sp < pops) return "a program that pops an empty stack";
-        sp += 1 - pops;
-        top = std::max(top, sp);
-        if (sp > REMD_CUSTOM_MAX_STACK) return "a program over REMD_CUSTOM_MAX_STACK stack slots";
-    }
-    if (sp != 1) return "a program that does not leave exactly one value";
-    if (top != d.stack_depth) return "a stack depth that is not the program's";
-    return nullptr;
+    if (t.K != h->K || t.glob_version != h->states_version)
+        return remd_fail(h, -1, "custom terms: the states changed since remd_set_custom_globals (call it after remd_set_states)");
+    if (t.has_lrc && !t.lrc_valid)
+        return remd_fail(h, -1, "custom terms: a nonbonded force has a long-range correction and the globals changed since remd_set_custom_lrc (call it after remd_set_custom_globals)");
+    return 0;
 }
 
 }  // namespace
@@ -330,18 +263,10 @@ int remd_custom_clone(remd_ctx* parent, remd_ctx* child)
     if (!t || parent->n_custom == 0) return 0;
     child->cst.reset(new cst_tables());
     cst_tables& c = *child->cst;
-    c.nf = t->nf; c.ng = t->ng; c.K = t->K; c.total_pad = t->total_pad; c.waves_simple = t->waves_simple; c.uniform = t->uniform;
-    c.waves_particles = t->waves_particles; c.n_groups = t->n_groups; c.waves_compound = t->waves_compound;
-    c.excl_off = t->excl_off; c.excl_atoms = t->excl_atoms; c.lrc = t->lrc; c.has_lrc = t->has_lrc; c.lrc_valid = t->lrc_valid; c.periodic_cutoff = t->periodic_cutoff;
-    c.mol_first = t->mol_first; c.mol_size = t->mol_size;
-    c.waves_centroid = t->waves_centroid; c.n_cv = t->n_cv; c.cv_off = t->cv_off; c.cv_atoms = t->cv_atoms; c.cv_ref = t->cv_ref;
-    c.waves_cv = t->waves_cv; c.map_off = t->map_off; c.map_index = t->map_index;
-    c.grp_off = t->grp_off; c.grp_atoms = t->grp_atoms; c.grp_w = t->grp_w; c.grp_periodic = t->grp_periodic; c.ref_off = t->ref_off; c.refs = t->refs;
+    static_cast<cst_plan&>(c) = *t;                     // the plan as a whole: whatever tables it has
     c.glob_version = t->glob_version == parent->states_version ? child->states_version : -1;
-    c.F = t->F; c.wave_force = t->wave_force; c.atoms = t->atoms; c.par = t->par; c.consts = t->consts; c.glob = t->glob;
-    c.defaults = t->defaults; c.prog = t->prog;
     hipSetDevice(child->device);
-    const int rc = set_tables(child, c);
+    const int rc = upload_tables(child, c);
     if (rc) return remd_fail(parent, rc, std::string("phases: ") + child->err);
     child->n_custom = parent->n_custom; child->cst_group = parent->cst_group; child->cst_cutoff = parent->cst_cutoff;
     child->config_version++;
@@ -354,28 +279,25 @@ int remd_custom_forces(remd_ctx* h, bool with_energy, int ep_slot, hipStream_t s
     cst_tables* tp = h->cst.get();
     if (!tp || h->n_custom == 0) return 0;
     cst_tables& t = *tp;
-    if (t.K != h->K || t.glob_version != h->states_version)
-        return remd_fail(h, -1, "custom terms: the states changed since remd_set_custom_globals (call it after remd_set_states)");
-    if (t.has_lrc && !t.lrc_valid)
-        return remd_fail(h, -1, "custom terms: a nonbonded force has a long-range correction and the globals changed since remd_set_custom_lrc (call it after remd_set_custom_globals)");
+    REMD_TRY(check_current(h, t));
     int rc = ensure_buffers(h, t); if (rc) return rc;
     const int waves = t.total_pad / 64;
     remd_prof_scope ps(h, "custom_terms", st);
-    if (t.waves_simple > 0) {
+    if (t.has(CST_SIMPLE)) {                             // (the first part: its wavefronts start at 0)
         if (with_energy)
-            hipLaunchKernelGGL(custom_terms_kernel<true>, dim3(t.waves_simple, h->R), dim3(64), 0, st, t.total_pad, waves, t.d_F,
+            hipLaunchKernelGGL(custom_terms_kernel<true>, dim3(t.end(CST_SIMPLE), h->R), dim3(64), 0, st, t.total_pad, waves, t.d_F,
                                t.d_wave_force, t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, h->d_labels, h->r_begin, h->Npad, h->d_pos,
                                h->d_box, h->d_force, t.d_Ewave);
         else
-            hipLaunchKernelGGL(custom_terms_kernel<false>, dim3(t.waves_simple, h->R), dim3(64), 0, st, t.total_pad, waves, t.d_F,
+            hipLaunchKernelGGL(custom_terms_kernel<false>, dim3(t.end(CST_SIMPLE), h->R), dim3(64), 0, st, t.total_pad, waves, t.d_F,
                                t.d_wave_force, t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, h->d_labels, h->r_begin, h->Npad, h->d_pos,
                                h->d_box, h->d_force, t.d_Ewave);
     }
-    if (t.waves_compound > t.waves_simple) remd_custom_compound_forces(h, t, with_energy, st);    // (custom_compound.hip: the wavefronts behind)
-    if (t.waves_particles > t.waves_compound) remd_custom_nonbonded_forces(h, t, with_energy, st); // (custom_nonbonded.hip: the tiles behind those)
-    if (t.waves_centroid > t.waves_particles) remd_custom_centroid_forces(h, t, with_energy, st);  // (custom_centroid.hip: behind those)
-    if (t.waves_cv > t.waves_centroid) remd_custom_cv_forces(h, t, with_energy, st);               // (custom_cv.hip: behind those)
-    if (waves > t.waves_cv) remd_cmap_forces(h, t, with_energy, st);                               // (cmap.hip: the last ones)
+    if (t.has(CST_COMPOUND)) remd_custom_compound_forces(h, t, with_energy, st);      // (each in the file of its kind, on its own part)
+    if (t.has(CST_NONBONDED)) remd_custom_nonbonded_forces(h, t, with_energy, st);
+    if (t.has(CST_CENTROID)) remd_custom_centroid_forces(h, t, with_energy, st);
+    if (t.has(CST_CV)) remd_custom_cv_forces(h, t, with_energy, st);
+    if (t.has(CST_CMAP)) remd_cmap_forces(h, t, with_energy, st);
     if (with_energy)
         hipLaunchKernelGGL(custom_reduce_kernel, dim3(h->R), dim3(64), 0, st, t.nf, t.d_F, waves, t.d_Ewave, t.d_E, h->d_epart, h->n_epart, ep_slot);
     if (with_energy && t.has_lrc) remd_custom_nonbonded_lrc(h, t, ep_slot, st);
@@ -389,26 +311,23 @@ int remd_custom_ukl(remd_ctx* h, double* d_rows)
     cst_tables* tp = h->cst.get();
     if (!tp || h->n_custom == 0) return 0;
     cst_tables& t = *tp;
-    if (t.K != h->K || t.glob_version != h->states_version)
-        return remd_fail(h, -1, "custom terms: the states changed since remd_set_custom_globals (call it after remd_set_states)");
-    if (t.has_lrc && !t.lrc_valid)
-        return remd_fail(h, -1, "custom terms: a nonbonded force has a long-range correction and the globals changed since remd_set_custom_lrc (call it after remd_set_custom_globals)");
+    REMD_TRY(check_current(h, t));
     if (t.uniform) return 0;                          // every state carries the same globals: the share is exactly zero
     const int waves = t.total_pad / 64;
     const size_t nD = (size_t)h->R * h->K * waves;
     if (t.d_D.size() != nD) {
         // (the CMAP forces' wavefronts have no globals and no u_kl launch: their columns are zeroed here, once, and nothing writes them)
         REMD_TRY(t.d_D.alloc(h, nD));
-        if (waves > t.waves_cv) REMD_CHECK(h, hipMemsetAsync(t.d_D, 0, sizeof(double) * nD, h->stream));
+        if (t.has(CST_CMAP)) REMD_CHECK(h, hipMemsetAsync(t.d_D, 0, sizeof(double) * nD, h->stream));
     }
     remd_prof_scope ps(h, "custom_ukl");
-    if (t.waves_simple > 0)
-        hipLaunchKernelGGL(custom_ukl_kernel, dim3(t.waves_simple, h->R), dim3(64), 0, h->stream, t.total_pad, waves, t.d_F, t.d_wave_force,
+    if (t.has(CST_SIMPLE))
+        hipLaunchKernelGGL(custom_ukl_kernel, dim3(t.end(CST_SIMPLE), h->R), dim3(64), 0, h->stream, t.total_pad, waves, t.d_F, t.d_wave_force,
                            t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, h->K, h->d_labels, h->r_begin, h->Npad, h->d_pos, h->d_box, t.d_D);
-    if (t.waves_compound > t.waves_simple) remd_custom_compound_ukl(h, t);
-    if (t.waves_particles > t.waves_compound) remd_custom_nonbonded_ukl(h, t);
-    if (t.waves_centroid > t.waves_particles) remd_custom_centroid_ukl(h, t);
-    if (t.waves_cv > t.waves_centroid) remd_custom_cv_ukl(h, t);
+    if (t.has(CST_COMPOUND)) remd_custom_compound_ukl(h, t);
+    if (t.has(CST_NONBONDED)) remd_custom_nonbonded_ukl(h, t);
+    if (t.has(CST_CENTROID)) remd_custom_centroid_ukl(h, t);
+    if (t.has(CST_CV)) remd_custom_cv_ukl(h, t);
     hipLaunchKernelGGL(custom_ukl_reduce_kernel, dim3(h->K, h->R), dim3(64), 0, h->stream, h->K, waves, t.d_D, h->d_beta, d_rows);
     if (t.has_lrc) remd_custom_nonbonded_lrc_ukl(h, t, d_rows);
     REMD_CHECK(h, hipGetLastError());
@@ -423,251 +342,15 @@ int remd_set_custom_terms(remd_handle h, const remd_custom_force_desc* desc, int
     if (!h->has_system) return remd_fail(h, -1, "remd_set_custom_terms: call remd_set_system first");
     hipSetDevice(h->device);
     if (n == 0) { remd_custom_release(h); h->config_version++; return 0; }
-    // (everything below up to set_tables only fills `t`: a refused call leaves the handle as it was)
-    if (n > REMD_CUSTOM_MAX_FORCES) return remd_fail(h, -1, "remd_set_custom_terms: more than REMD_CUSTOM_MAX_FORCES custom forces");
+    // (the planner only fills `t` and touches nothing of the handle or the device: a refused call leaves the handle as it was)
+    const bool bare = h->nb_method == REMD_NB_NONE && !h->nocutoff && h->n_bonds + h->n_angles + h->n_torsions + h->n_settle + h->n_shake == 0;
+    const cst_facts facts{h->N, h->Npad, h->K, h->states_version, h->box_host.data(), h->box_host.size(), bare};
     cst_tables t;
-    t.nf = n; t.ng = desc[0].n_globals;
-    if (t.ng < 0 || t.ng > REMD_CUSTOM_MAX_GLOBALS) return remd_fail(h, -1, "remd_set_custom_terms: more than REMD_CUSTOM_MAX_GLOBALS global parameters");
-    if (t.ng > 0 && !desc[0].global_defaults) return remd_fail(h, -1, "remd_set_custom_terms: global_defaults missing");
-    t.defaults.assign(desc[0].global_defaults, desc[0].global_defaults + t.ng);
-    static const int width4[4] = {2, 3, 4, 1}, n_vars4[4] = {1, 1, 1, 3};
-    for (int i = 0; i < n; ++i) {
-        const remd_custom_force_desc& d = desc[i];
-        const std::string who = "remd_set_custom_terms: force " + std::to_string(i) + ": ";
-        if (d.kind < 0 || d.kind > REMD_CUSTOM_CMAP) return remd_fail(h, -1, who + "unknown kind");
-        const bool nonbonded = d.kind == REMD_CUSTOM_NONBONDED, cv = d.kind == REMD_CUSTOM_CV, cmap = d.kind == REMD_CUSTOM_CMAP;
-        const bool centroid = d.kind == REMD_CUSTOM_CENTROID, compound = d.kind == REMD_CUSTOM_COMPOUND || centroid;
-        if (cmap && d.n_particles != 8) return remd_fail(h, -1, who + "n_particles is 8 for a CMAP force (two dihedrals of four particles)");
-        if (!cmap && (compound ? (d.n_particles < 1 || d.n_particles > REMD_CUSTOM_MAX_PARTICLES) : d.n_particles != 0))
-            return remd_fail(h, -1, who + "n_particles is 1 ... REMD_CUSTOM_MAX_PARTICLES for a compound-bond or centroid-bond force and 0 for every other kind");
-        const int wd = compound ? d.n_particles : cmap ? 8 : (nonbonded || cv) ? 0 : width4[d.kind];
-        if (d.n_terms <= 0 || (!d.atoms && !nonbonded && !cv)) return remd_fail(h, -1, who + "no terms");
-        if (d.n_params < 0 || d.n_params > REMD_CUSTOM_MAX_PARAMS || (d.n_params > 0 && !d.params))
-            return remd_fail(h, -1, who + "0 ... REMD_CUSTOM_MAX_PARAMS parameters per term are supported");
-        if (nonbonded) {
-            // what custom_nonbonded.hip indexes unchecked: one parameter row per atom of the system, 2 n_params operands, the exclusion rows
-            if (d.n_terms != h->N) return remd_fail(h, -1, who + "a nonbonded force has " + std::to_string(d.n_terms) + " particles, the system has " + std::to_string(h->N));
-            if (2 * d.n_params > REMD_CUSTOM_MAX_PARAMS) return remd_fail(h, -1, who + "a nonbonded force takes at most REMD_CUSTOM_MAX_PARAMS / 2 per-particle parameters");
-            if (d.nb_method < 0 || d.nb_method > 2) return remd_fail(h, -1, who + "unknown nonbonded method (0 NoCutoff, 1 CutoffNonPeriodic, 2 CutoffPeriodic)");
-            if ((d.periodic != 0) != (d.nb_method == 2)) return remd_fail(h, -1, who + "a nonbonded force is periodic exactly where its method is CutoffPeriodic");
-            if (d.nb_method != 0 && !(d.cutoff > 0.0)) return remd_fail(h, -1, who + "a cutoff that is not positive");
-            if (d.switch_distance >= 0.0 && (d.nb_method == 0 || !(d.switch_distance > 0.0 && d.switch_distance < d.cutoff)))
-                return remd_fail(h, -1, who + "the switching distance must lie in (0, cutoff) and needs a cutoff");
-            if (d.long_range_correction && d.nb_method != 2) return remd_fail(h, -1, who + "a long-range correction needs CutoffPeriodic");
-            if (!d.excl_offsets || d.excl_offsets[0] != 0) return remd_fail(h, -1, who + "excl_offsets [N + 1] must start at 0");
-            for (int a = 0; a < d.n_terms; ++a) {
-                const int b = d.excl_offsets[a], e = d.excl_offsets[a + 1];
-                if (e < b || (e > b && !d.excl_atoms)) return remd_fail(h, -1, who + "excl_offsets must not decrease");
-                for (int k = b; k < e; ++k) {
-                    if (d.excl_atoms[k] < 0 || d.excl_atoms[k] >= d.n_terms) return remd_fail(h, -1, who + "exclusion index out of range");
-                    if (d.excl_atoms[k] == a) return remd_fail(h, -1, who + "a particle excluded from itself");
-                }
-            }
-            if (d.nb_method == 2 && !h->box_host.empty())
-                for (size_t k = 0; k < h->box_host.size(); ++k)
-                    if (!(h->box_host[k] >= 2.0 * d.cutoff)) return remd_fail(h, -1, who + "box smaller than twice the cutoff");
-        }
-        if (cv) {
-            // what custom_cv.hip indexes unchecked: the variables in CSR form, their particles, the reference beside them
-            if (d.n_terms != 1 || d.n_params != 0 || d.periodic != 0) return remd_fail(h, -1, who + "a collective-variable force has n_terms = 1, no per-term parameters and is not periodic");
-            if (d.n_cvs < 1 || d.n_cvs > REMD_CUSTOM_MAX_CVS) return remd_fail(h, -1, who + "a collective-variable force has 1 ... REMD_CUSTOM_MAX_CVS collective variables");
-            if (!d.cv_offsets || !d.cv_atoms || !d.cv_reference) return remd_fail(h, -1, who + "a collective-variable force needs cv_offsets, cv_atoms and cv_reference");
-            if (d.cv_offsets[0] != 0) return remd_fail(h, -1, who + "cv_offsets must start at 0");
-            std::vector<char> seen(h->N);
-            for (int c = 0; c < d.n_cvs; ++c) {
-                const int b = d.cv_offsets[c], e = d.cv_offsets[c + 1];
-                if (e < b || e - b < 3) return remd_fail(h, -1, who + "collective variable " + std::to_string(c) + ": an RMSD needs at least 3 particles");
-                std::fill(seen.begin(), seen.end(), 0);
-                double m[3] = {0.0, 0.0, 0.0};
-                for (int k = b; k < e; ++k) {
-                    const int a = d.cv_atoms[k];
-                    if (a < 0 || a >= h->N) return remd_fail(h, -1, who + "collective variable " + std::to_string(c) + ": particle index out of range");
-                    if (seen[a]) return remd_fail(h, -1, who + "collective variable " + std::to_string(c) + ": particle " + std::to_string(a) + " named twice");
-                    seen[a] = 1;
-                    for (int x = 0; x < 3; ++x) {
-                        if (!std::isfinite(d.cv_reference[3 * (size_t)k + x])) return remd_fail(h, -1, who + "collective variable " + std::to_string(c) + ": a reference position that is not finite");
-                        m[x] += d.cv_reference[3 * (size_t)k + x];
-                    }
-                }
-                for (int x = 0; x < 3; ++x)
-                    if (!(fabs(m[x]) <= 1e-9 * (e - b))) return remd_fail(h, -1, who + "collective variable " + std::to_string(c) + ": the reference must be centred on its own centroid (within 1e-9 nm)");
-            }
-        }
-        if (cmap) {
-            // what cmap.hip indexes unchecked: every term's map, every map's block (the header cst_table2d trusts, and its extent)
-            if (d.n_params != 0 || d.n_program != 0) return remd_fail(h, -1, who + "a CMAP force has no per-term parameters and no program");
-            if (d.n_maps < 1 || d.n_maps > REMD_CUSTOM_MAX_MAPS) return remd_fail(h, -1, who + "a CMAP force has 1 ... REMD_CUSTOM_MAX_MAPS maps");
-            if (!d.map_index || !d.map_offsets || !d.consts || d.n_consts <= 0) return remd_fail(h, -1, who + "a CMAP force needs map_index, map_offsets and the maps' blocks in consts");
-            for (int k = 0; k < d.n_terms; ++k)
-                if (d.map_index[k] < 0 || d.map_index[k] >= d.n_maps) return remd_fail(h, -1, who + "term " + std::to_string(k) + ": map index out of range");
-            for (int m = 0; m < d.n_maps; ++m) {
-                const std::string map = who + "map " + std::to_string(m) + ": ";
-                const long long off = d.map_offsets[m];
-                if (off < 0 || off + 8 > (long long)d.n_consts) return remd_fail(h, -1, map + "a block that runs past n_consts");
-                const double* B = d.consts + off;
-                if (!(B[0] >= 3.0 && B[0] <= 256.0) || B[0] != floor(B[0]) || B[1] != B[0]) return remd_fail(h, -1, map + "a block whose sizes are not nx = ny, an integer 3 ... 256");
-                if (B[6] != 1.0) return remd_fail(h, -1, map + "a block that is not periodic");
-                if (B[2] != 0.0 || B[4] != 0.0 || !(fabs(B[3] - 2.0 * M_PI) <= 1e-12) || B[5] != B[3]) return remd_fail(h, -1, map + "a block whose range is not [0, 2 pi] in both angles");
-                const long long nn = (long long)B[0];
-                if (off + 8 + 4 * nn * nn > (long long)d.n_consts) return remd_fail(h, -1, map + "a block that runs past n_consts");
-                for (long long k = 0; k < 4 * nn * nn; ++k) if (!std::isfinite(B[8 + k])) return remd_fail(h, -1, map + "a node value that is not finite");
-            }
-        }
-        if (d.n_globals != t.ng) return remd_fail(h, -1, who + "every descriptor must carry the handle's n_globals");
-        for (int k = 0; k < t.ng; ++k) if (d.global_defaults && d.global_defaults[k] != t.defaults[k]) return remd_fail(h, -1, who + "global_defaults differ between the descriptors");
-        if (d.force_group != desc[0].force_group || d.force_group < 0 || d.force_group > 31)
-            return remd_fail(h, -1, who + "every custom force of a handle must sit in one force group (0 ... 31)");
-        if (!cmap)       // (a CMAP force has no program)
-            if (const char* bad = check_program(d, compound ? 3 * d.n_particles : nonbonded ? 1 : cv ? d.n_cvs : n_vars4[d.kind])) return remd_fail(h, -1, who + bad);
-        if (centroid) {
-            // the groups: CSR offsets that start at 0 and increase (no empty group), atoms of the system, weights that sum to 1
-            if (d.n_groups <= 0 || !d.group_offsets || !d.group_atoms || !d.group_weights) return remd_fail(h, -1, who + "a centroid-bond force needs n_groups > 0, group_offsets, group_atoms and group_weights");
-            if (d.group_offsets[0] != 0) return remd_fail(h, -1, who + "group_offsets must start at 0");
-            for (int g = 0; g < d.n_groups; ++g) {
-                const int b = d.group_offsets[g], e = d.group_offsets[g + 1];
-                if (e <= b) return remd_fail(h, -1, who + "group_offsets must increase (an empty group has no centroid)");
-                double W = 0.0;
-                for (int k = b; k < e; ++k) {
-                    if (d.group_atoms[k] < 0 || d.group_atoms[k] >= h->N) return remd_fail(h, -1, who + "group atom index out of range");
-                    if (!(d.group_weights[k] >= 0.0)) return remd_fail(h, -1, who + "negative group weight");
-                    W += d.group_weights[k];
-                }
-                if (!(fabs(W - 1.0) <= 1e-12)) return remd_fail(h, -1, who + "the weights of a group must sum to 1 (within 1e-12)");
-            }
-            for (int k = 0; k < d.n_terms * wd; ++k) if (d.atoms[k] < 0 || d.atoms[k] >= d.n_groups) return remd_fail(h, -1, who + "group index out of range");
-        } else
-            for (int k = 0; k < d.n_terms * wd; ++k) if (d.atoms[k] < 0 || d.atoms[k] >= h->N) return remd_fail(h, -1, who + "atom index out of range");
-        cst_force f{};
-        f.kind = d.kind; f.periodic = d.periodic ? 1 : 0; f.n_terms = d.n_terms; f.n_params = d.n_params; f.n_particles = wd;
-        f.npad = (d.n_terms + 63) / 64 * 64;
-        f.par0 = (int)t.par.size(); f.prog0 = (int)t.prog.size(); f.n_prog = d.n_program; f.const0 = (int)t.consts.size();
-        f.switch_dist = -1.0;
-        int par_stride = f.npad;
-        if (nonbonded) {
-            // its wavefronts are the upper-triangular tiles of 64 x 64 atoms; its parameters one row per atom, [n_params][Npad]
-            const int nb = (d.n_terms + 63) / 64;
-            f.npad = 64 * (nb * (nb + 1) / 2);
-            par_stride = h->Npad;
-            f.nb_method = d.nb_method; f.cutoff = d.nb_method ? d.cutoff : 0.0; f.switch_dist = d.switch_distance >= 0.0 ? d.switch_distance : -1.0;
-            f.lrc = d.long_range_correction ? 1 : 0;
-            if (f.lrc) t.has_lrc = true;
-            if (d.nb_method == 2) t.periodic_cutoff = std::max(t.periodic_cutoff, d.cutoff);
-            f.excl0 = (int)t.excl_off.size();
-            const int base = (int)t.excl_atoms.size();
-            for (int a = 0; a <= d.n_terms; ++a) t.excl_off.push_back(base + d.excl_offsets[a]);
-            if (d.excl_offsets[d.n_terms] > 0) t.excl_atoms.insert(t.excl_atoms.end(), d.excl_atoms, d.excl_atoms + d.excl_offsets[d.n_terms]);
-        }
-        // parameters [n_params][npad]; a padding slot repeats the last term (finite arithmetic in lanes that add nothing)
-        for (int p = 0; p < d.n_params; ++p) for (int s = 0; s < par_stride; ++s) t.par.push_back(d.params[(size_t)std::min(s, d.n_terms - 1) * d.n_params + p]);
-        for (int pc = 0; pc < d.n_program; ++pc) t.prog.push_back(make_int2(d.program[2 * pc], d.program[2 * pc + 1]));
-        if (d.n_consts > 0) t.consts.insert(t.consts.end(), d.consts, d.consts + d.n_consts);
-        if (cv) {
-            // its variables join the handle's tables
-            f.cv0 = t.n_cv; f.n_cvs = d.n_cvs;
-            if (t.cv_off.empty()) t.cv_off.push_back(0);
-            const int base = (int)t.cv_atoms.size(), total = d.cv_offsets[d.n_cvs];
-            for (int c = 1; c <= d.n_cvs; ++c) t.cv_off.push_back(base + d.cv_offsets[c]);
-            t.cv_atoms.insert(t.cv_atoms.end(), d.cv_atoms, d.cv_atoms + total);
-            t.cv_ref.insert(t.cv_ref.end(), d.cv_reference, d.cv_reference + 3 * (size_t)total);
-            t.n_cv += d.n_cvs;
-        }
-        if (cmap) {
-            // its maps join the handle's: each block's offset in the handle's constants
-            f.map0 = (int)t.map_off.size(); f.n_maps = d.n_maps;
-            for (int m = 0; m < d.n_maps; ++m) t.map_off.push_back(f.const0 + d.map_offsets[m]);
-        }
-        t.F.push_back(f);
-    }
-    // the padded term space: the four one-variable kinds first, the compound-bond forces behind them, then the nonbonded forces' tiles,
-    // the centroid-bond forces, the collective-variable forces, the CMAP forces last (each part has its own kernel); the energy columns
-    // keep the forces' order whatever their slots
-    for (int pass = 0; pass < 6; ++pass) {
-        for (int i = 0; i < n; ++i) {
-            cst_force& f = t.F[i];
-            if ((f.kind == REMD_CUSTOM_CMAP ? 5 : f.kind == REMD_CUSTOM_CV ? 4 : f.kind == REMD_CUSTOM_CENTROID ? 3 : f.kind == REMD_CUSTOM_NONBONDED ? 2 : f.kind == REMD_CUSTOM_COMPOUND ? 1 : 0) != pass) continue;
-            f.slot0 = t.total_pad; t.total_pad += f.npad;
-            for (int w = 0; w < f.npad / 64; ++w) t.wave_force.push_back(i);
-        }
-        if (pass == 0) t.waves_simple = t.total_pad / 64;
-        if (pass == 1) t.waves_compound = t.total_pad / 64;
-        if (pass == 2) t.waves_particles = t.total_pad / 64;
-        if (pass == 3) t.waves_centroid = t.total_pad / 64;
-        if (pass == 4) t.waves_cv = t.total_pad / 64;
-    }
-    int rows = 4;
-    for (int i = 0; i < n; ++i) rows = std::max(rows, t.F[i].n_particles);
-    t.atoms.assign((size_t)rows * t.total_pad, 0);
-    // a centroid force's groups join the handle's group tables; its row of `atoms` holds the handle-wide group numbers
-    std::vector<int> group0(n, 0);
-    for (int i = 0; i < n; ++i) {
-        if (t.F[i].kind != REMD_CUSTOM_CENTROID) continue;
-        const remd_custom_force_desc& d = desc[i];
-        group0[i] = t.n_groups;
-        if (t.grp_off.empty()) t.grp_off.push_back(0);
-        for (int g = 0; g < d.n_groups; ++g) {
-            t.grp_atoms.insert(t.grp_atoms.end(), d.group_atoms + d.group_offsets[g], d.group_atoms + d.group_offsets[g + 1]);
-            t.grp_w.insert(t.grp_w.end(), d.group_weights + d.group_offsets[g], d.group_weights + d.group_offsets[g + 1]);
-            t.grp_off.push_back((int)t.grp_atoms.size());
-            t.grp_periodic.push_back(t.F[i].periodic);
-        }
-        t.n_groups += d.n_groups;
-    }
-    for (int i = 0; i < n; ++i) {
-        const cst_force& f = t.F[i]; const int wd = f.n_particles;
-        for (int s = 0; s < f.npad; ++s) for (int a = 0; a < wd; ++a)
-            t.atoms[(size_t)a * t.total_pad + f.slot0 + s] = group0[i] + desc[i].atoms[(size_t)std::min(s, f.n_terms - 1) * wd + a];
-    }
-    // the map of every slot of the CMAP forces' part (a padding slot repeats the last term's, like its atoms)
-    t.map_index.assign((size_t)t.total_pad - (size_t)t.waves_cv * 64, 0);
-    for (int i = 0; i < n; ++i) {
-        const cst_force& f = t.F[i];
-        if (f.kind != REMD_CUSTOM_CMAP) continue;
-        for (int s = 0; s < f.npad; ++s) t.map_index[f.slot0 + s - t.waves_cv * 64] = desc[i].map_index[std::min(s, f.n_terms - 1)];
-    }
-    if (t.n_groups > 0) {
-        // per group, every (bond, position) that names it, in table order: the spread kernel adds their gradients in this order
-        std::vector<std::vector<int>> named(t.n_groups);
-        const int slot_c = t.waves_particles * 64;
-        for (int i = 0; i < n; ++i) {
-            const cst_force& f = t.F[i];
-            if (f.kind != REMD_CUSTOM_CENTROID) continue;
-            for (int b = 0; b < f.n_terms; ++b) for (int a = 0; a < f.n_particles; ++a)
-                named[t.atoms[(size_t)a * t.total_pad + f.slot0 + b]].push_back((f.slot0 + b - slot_c) * REMD_CUSTOM_MAX_PARTICLES + a);
-        }
-        t.ref_off.push_back(0);
-        for (const std::vector<int>& v : named) { t.refs.insert(t.refs.end(), v.begin(), v.end()); t.ref_off.push_back((int)t.refs.size()); }
-    }
-    t.K = h->K; t.glob_version = h->states_version; t.uniform = true;
-    for (int k = 0; k < std::max(h->K, 0); ++k) t.glob.insert(t.glob.end(), t.defaults.begin(), t.defaults.end());
-    if (t.glob.empty()) t.glob.assign(1, 0.0);          // (a force without globals: the kernels still take a pointer)
-    t.lrc.assign((size_t)std::max(h->K, 1) * n, 0.0);
-    if (t.periodic_cutoff > 0.0 && h->nb_method == REMD_NB_NONE && !h->nocutoff && h->n_bonds + h->n_angles + h->n_torsions + h->n_settle + h->n_shake == 0) {
-        // no NonbondedForce and no built-in bonded term or constraint: the molecules a barostat scales are what the custom bonds,
-        // angles, torsions and compound bonds join (OpenMM takes molecules from the bonds its forces report); the scaling kernels take
-        // contiguous ranges, so a molecule whose atoms are not one gives no table (the barostat then refuses)
-        std::vector<int> root(h->N);
-        for (int a = 0; a < h->N; ++a) root[a] = a;
-        auto find = [&](int a) { while (root[a] != a) a = root[a] = root[root[a]]; return a; };
-        for (int i = 0; i < n; ++i) {
-            const cst_force& f = t.F[i];
-            if (f.kind == REMD_CUSTOM_EXTERNAL || f.kind == REMD_CUSTOM_CENTROID || f.kind == REMD_CUSTOM_NONBONDED || f.kind == REMD_CUSTOM_CV) continue;
-            for (int b = 0; b < f.n_terms; ++b) for (int a = 1; a < f.n_particles; ++a) {
-                const int p = find(desc[i].atoms[(size_t)b * f.n_particles]), q = find(desc[i].atoms[(size_t)b * f.n_particles + a]);
-                if (p != q) root[std::max(p, q)] = std::min(p, q);
-            }
-        }
-        bool contiguous = true;                         // (roots are the lowest atom of a molecule: a range starts at its root)
-        for (int a = 0; a < h->N && contiguous; ++a) {
-            const int r = find(a);
-            if (r == a) { t.mol_first.push_back(a); t.mol_size.push_back(1); }
-            else if (r == t.mol_first.back()) t.mol_size.back()++;
-            else contiguous = false;
-        }
-        if (!contiguous) { t.mol_first.clear(); t.mol_size.clear(); }
-    }
+    const std::string refusal = cst_build_plan(desc, n, facts, t);
+    if (!refusal.empty()) return remd_fail(h, -1, "remd_set_custom_terms: " + refusal);
     remd_custom_release(h);
     h->config_version++;
-    int rc = set_tables(h, t);
+    int rc = upload_tables(h, t);
     if (rc) return rc;
     const double periodic_cutoff = t.periodic_cutoff;
     h->cst.reset(new cst_tables(std::move(t)));

@@ -434,3 +434,114 @@ def test_resident_lennard_jones_path_steps_aside(hip_engine_factory):
     d = y[:, 0] - target
     d -= box * np.rint(d / box)
     assert np.all(np.linalg.norm(d, axis=1) < 0.15), np.linalg.norm(d, axis=1)
+
+
+# ---- every kind in one handle, against the order of the parts ----------------------------------------------------------------------------
+def _every_kind(x):
+    """one force of each kind over a chain of 65 atoms, in the reverse of the order their parts have in the padded term space: a CMAP
+    force, a collective-variable force, a centroid force, a nonbonded force (65 particles: 3 tiles), a compound-bond force, a torsion,
+    an angle and a bond force of 65 terms (two wavefronts).  With the external force that is nine, one more than REMD_CUSTOM_MAX_FORCES:
+    the engine refuses nine in a handle, so the external force comes back alone, for a second handle"""
+    from openmmtools_amd.system import (CMAPTorsionForce, CustomCVForce, RMSDForce, CustomCentroidBondForce, CustomNonbondedForce,
+                                        CustomCompoundBondForce)
+    n = len(x)
+    a = 2.0 * np.pi * np.arange(6) / 6
+    cmap = CMAPTorsionForce()
+    cmap.addMap(6, (3.0 * np.cos(a[None, :]) + 2.0 * np.sin(a[:, None]) + np.cos(a[None, :] - a[:, None])).reshape(-1))
+    cmap.addMap(6, (2.0 * np.sin(2.0 * a[None, :]) - np.cos(a[:, None])).reshape(-1))
+    for t in range(0, 30, 3):
+        cmap.addTorsion(t % 2, t, t + 1, t + 2, t + 3, t + 1, t + 2, t + 3, t + 4)
+    cv = CustomCVForce('40*v^2')
+    cv.addCollectiveVariable('v', RMSDForce(x + 0.01 * np.cos(7.0 * x), list(range(40, 52))))
+    cen = CustomCentroidBondForce(2, '0.5*k*(distance(g1,g2)-d0)^2')
+    cen.addPerBondParameter('k'); cen.addPerBondParameter('d0')
+    for atoms in ([52, 53, 54], [55, 56], [57, 58, 59, 60]):
+        cen.addGroup(atoms)
+    cen.addBond([0, 1], [300.0, 0.3]); cen.addBond([1, 2], [200.0, 0.4])
+    nb = CustomNonbondedForce('a1*a2*exp(-r/0.08)')
+    nb.addPerParticleParameter('a')
+    for i in range(n):
+        nb.addParticle([1.0 + 0.01 * i])
+    for i in range(n - 1):
+        nb.addExclusion(i, i + 1)
+    comp = CustomCompoundBondForce(3, '0.5*k*(distance(p1,p3)-0.25)^2+angle(p1,p2,p3)')
+    comp.addPerBondParameter('k')
+    for t in range(0, 60, 4):
+        comp.addBond([t, t + 1, t + 2], [50.0 + t])
+    tor = CustomTorsionForce('k*(1+cos(2*theta-0.3))'); tor.addPerTorsionParameter('k')
+    for t in range(0, 61, 5):
+        tor.addTorsion(t, t + 1, t + 2, t + 3, [2.0 + 0.1 * t])
+    ang = CustomAngleForce('0.5*k*(theta-1.9)^2'); ang.addPerAngleParameter('k')
+    for t in range(0, 63, 2):
+        ang.addAngle(t, t + 1, t + 2, [80.0])
+    bond = CustomBondForce('0.5*k*(r-r0)^2'); bond.addPerBondParameter('k'); bond.addPerBondParameter('r0')
+    for t in range(n - 1):
+        bond.addBond(t, t + 1, [20000.0, 0.15])
+    bond.addBond(0, 2, [500.0, 0.25])
+    ext = CustomExternalForce('2*(x^2+y^2+z^2)')
+    for i in range(n):
+        ext.addParticle(i, [])
+    return [cmap, cv, cen, nb, comp, tor, ang, bond], ext
+
+
+def _chain_handle(factory, x, customs, phases=0, R=6):
+    """a NoCutoff system of 65 atoms (a NonbondedForce beside the custom forces: the general NoCutoff step) at 6 replicas"""
+    from openmmtools_amd.system import NonbondedForce
+    s = System()
+    for _ in range(len(x)):
+        s.addParticle(12.0)
+    nbf = NonbondedForce(); nbf.setNonbondedMethod(NonbondedForce.NoCutoff)
+    for i in range(len(x)):
+        nbf.addParticle(0.05 * (-1) ** i, 0.1, 0.2)
+    for i in range(len(x) - 1):
+        nbf.addException(i, i + 1, 0.0, 0.1, 0.0)
+    s.addForce(nbf)
+    for f in customs:
+        s.addForce(copy.deepcopy(f))
+    desc = system_to_desc(s)
+    eng = factory()
+    if phases:
+        eng.set_phases(phases)
+    eng.set_system(desc)
+    eng.set_states(1.0 / (KB * np.linspace(300.0, 330.0, R)))
+    eng.set_custom_globals(np.zeros((R, 0)))
+    eng.set_integrator('V R R O R R V', 0.001, 1.0, 20, True, 1e-8)
+    eng.seed(11)
+    xs = _f32(np.stack([x + 0.002 * r * np.sin(5.0 * x + r) for r in range(R)]))
+    eng.set_replicas(R, 0, xs, None, np.zeros((R, 3)), np.arange(R))
+    return eng, desc
+
+
+def test_every_kind_in_one_handle_against_the_part_order(hip_engine_factory):
+    """Eight kinds in one handle, the descriptors in the reverse of the order of their parts in the padded term space, the bond force
+    crossing a wavefront boundary (65 terms); the external force sits in a second handle (a handle takes REMD_CUSTOM_MAX_FORCES = 8).
+    Each column of custom_energies() equals, bit for bit, the energy of the same force alone in a handle of its own: the reduction adds
+    a force's wavefront partials in an order that does not depend on where its slots lie.  And with remd_set_phases(1) and (2) the
+    columns and the positions after a short propagation are bit-identical (the check of tests/test_phases_gpu.py): the second block's
+    tables are a clone of the first's"""
+    import cmap_oracle
+    x = cmap_oracle.chain_positions(65, replicas=1, seed=3, special=False)[0].astype(np.float64)
+    customs, ext = _every_kind(x)
+    eng, desc = _chain_handle(hip_engine_factory, x, customs)
+    kinds = [t['kind'] for _, t in sorted(desc['custom_terms'].items())]
+    assert kinds == [cx.KIND_CMAP, cx.KIND_CV, cx.KIND_CENTROID, cx.KIND_NONBONDED, cx.KIND_COMPOUND, cx.KIND_TORSION, cx.KIND_ANGLE, cx.KIND_BOND]
+    assert len(desc['custom_terms']['007']['atoms']) == 65
+    E = eng.custom_energies()
+    assert E.shape == (6, 8) and np.all(np.isfinite(E)) and np.all(np.abs(E).min(axis=0) > 0.0)
+    for k, f in enumerate(customs):
+        alone = _chain_handle(hip_engine_factory, x, [f])[0].custom_energies()
+        assert alone.shape == (6, 1) and np.array_equal(alone[:, 0], E[:, k]), (k, alone[:, 0], E[:, k])
+    both = _chain_handle(hip_engine_factory, x, [ext, customs[7]])[0].custom_energies()       # the second handle: the external force, beside the bonds
+    assert np.array_equal(both[:, 1], E[:, 7]) and np.array_equal(both[:, 0], _chain_handle(hip_engine_factory, x, [ext])[0].custom_energies()[:, 0])
+    out = []
+    for phases in (1, 2):
+        e = _chain_handle(hip_engine_factory, x, customs, phases)[0]
+        for it in range(2):
+            assert not e.propagate(it).any()
+            u = e.compute_energies()
+        xs, vs = e.get_replicas()[:2]
+        out.append((xs.copy(), vs.copy(), u.copy(), e.custom_energies(), e.phases_active()))
+    assert out[0][4] == 1 and out[1][4] == 2
+    for p, q in zip(out[0][:4], out[1][:4]):
+        assert np.array_equal(p, q)
+    assert np.all(np.isfinite(out[0][0])) and not np.array_equal(out[0][3], E)
