@@ -73,8 +73,9 @@ def _check_plain(eng, rtol, ftol):
 
 
 def _droplet_in_implicit_solvent(n=150):
-    """a droplet of charged Lennard-Jones particles with GBSA parameters: more than two 64-atom tiles, an alchemical half (the tiled GB
-    kernels and the multi-wavefront NoCutoff sum beyond one tile; the dipeptide has 22 atoms)"""
+    """a droplet of charged Lennard-Jones particles with GBSA parameters: more than two 64-atom tiles, no alchemical particle (the tiled GB
+    kernels and the multi-wavefront NoCutoff sum beyond one tile; the dipeptide has 22 atoms).  Every pair of it is in the "far" regime
+    of the Born-radius sum; overlapping and alchemical atoms beyond one tile are in tests/test_gbsa_zoo_gpu.py"""
     from openmmtools_amd.system import System, NonbondedForce
     g = np.stack(np.meshgrid(*[np.arange(6)] * 3, indexing='ij'), axis=-1).reshape(-1, 3) * 0.38
     x = g[np.argsort(np.linalg.norm(g - g.mean(0), axis=1), kind='stable')[:n]].astype(np.float64)
