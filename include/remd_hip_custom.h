@@ -1,6 +1,6 @@
 /*
  * remd_hip_custom.h — GPU-only extension of the C ABI in remd_hip.h: custom bond, angle, torsion, external, compound-bond,
- * centroid-bond, nonbonded and collective-variable forces, and CMAP torsion maps.
+ * centroid-bond, nonbonded, collective-variable and donor-acceptor (hydrogen-bond) forces, and CMAP torsion maps.
  *
  * OpenMM's CustomBondForce, CustomAngleForce, CustomTorsionForce and CustomExternalForce: an energy expression of r (bond), theta
  * (angle, torsion) or x, y, z (external), of per-term parameters and of global parameters, evaluated per term.  The host compiles
@@ -74,6 +74,26 @@
  * and joins the replica's potential; having no globals it adds nothing of its own to the u_kl rows.  remd_set_custom_terms checks the
  * atoms, every map_index and every block's header (nx = ny an integer 3 ... 256, periodic, the range [0, 2 pi], its end inside
  * consts, finite nodes).
+ *
+ * Donor-acceptor forces (REMD_CUSTOM_HBOND, OpenMM's CustomHbondForce): a donor is up to three particles d1 d2 d3, an acceptor up to
+ * three particles a1 a2 a3, and the energy is an expression of the distances, angles and dihedrals among the six (REMD_CX_DISTANCE /
+ * REMD_CX_ANGLE / REMD_CX_DIHEDRAL with d1 d2 d3 the particle slots 0 1 2 and a1 a2 a3 the slots 3 4 5; no REMD_CX_VAR: raw coordinates
+ * are not variables of this kind), of per-donor and per-acceptor parameters and of global parameters, summed over every (donor,
+ * acceptor) pair that no exclusion names and, with a cutoff, whose distance(d1, a1) is below it.  n_terms = hb_n_donors > 0,
+ * hb_n_acceptors > 0, atoms NULL, n_params = 0, params NULL, n_particles = 0.  hb_donor_atoms is [hb_n_donors][3] and hb_acceptor_atoms
+ * [hb_n_acceptors][3], -1 for a particle the donor or acceptor does not have (the first, d1 / a1, always exists; no particle twice
+ * within a row).  hb_particle_mask has bit s set for every particle slot s = 0 ... 5 the program names, and only those: every donor
+ * (acceptor) has the particle of every named slot, and the device runs one seeded pass per set bit.  REMD_CX_PARAM operand k is
+ * parameter k of the pair's donor for k < hb_n_donor_params (hb_donor_params [hb_n_donors][hb_n_donor_params]), parameter
+ * k - hb_n_donor_params of its acceptor behind that (hb_acceptor_params); together at most REMD_CUSTOM_MAX_PARAMS.  Exclusions:
+ * hb_excl_offsets [hb_n_donors + 1] and hb_excl_acceptors, donor i is excluded from the acceptors hb_excl_acceptors[hb_excl_offsets[i]
+ * ... hb_excl_offsets[i + 1]), each row sorted, no acceptor twice in a row.  A pair that shares a particle must be excluded (refused
+ * otherwise).  nb_method and cutoff as for REMD_CUSTOM_NONBONDED: 0 every pair, 1 a cutoff without and 2 with minimum images under the
+ * replica's own box (periodic = 1 exactly then: every difference inside a distance, angle or dihedral is then a minimum image, and so
+ * is the one of the cutoff test; every box edge must stay >= 2 cutoff, also under a barostat); switch_distance and
+ * long_range_correction are ignored.  One wavefront per tile of 64 donors x 64 acceptors, every one of the ceil(nD / 64) ceil(nA / 64)
+ * tiles visited (csrc/custom_hbond.hip): the cost is proportional to nD nA, there is no list.  Degenerate geometry follows
+ * REMD_CX_DISTANCE / ANGLE / DIHEDRAL.
  *
  * Tabulated functions (OpenMM's Continuous1DFunction and Discrete1DFunction) of every kind above: REMD_CX_TABLE1D and
  * REMD_CX_LOOKUP1D take one argument x from the stack and push one result; the operand is the offset of the function's block in the
@@ -163,6 +183,9 @@ extern "C" {
 #define REMD_CUSTOM_CV       7     /* atoms NULL, n_terms = 1; variables the RMSDs of the force's collective variables            */
 
 #define REMD_CUSTOM_CMAP     8     /* atoms [n][8] (n_particles = 8): two dihedrals; the energy is map map_index[k] at them; no program */
+
+/* kind 9 is not assigned: a descriptor that carries it is refused as an unknown kind                                              */
+#define REMD_CUSTOM_HBOND    10    /* atoms NULL, n_terms = hb_n_donors; functions of the particles d1 d2 d3 a1 a2 a3 of every donor-acceptor pair */
 
 #define REMD_CUSTOM_MAX_PROGRAM 256
 #define REMD_CUSTOM_MAX_STACK   16
@@ -258,6 +281,18 @@ typedef struct remd_custom_force_desc {
     const int32_t* map_index;      /* [n_terms]: the map of every term, 0 ... n_maps - 1                                   */
     int32_t n_maps;                /* the force's maps, 1 ... REMD_CUSTOM_MAX_MAPS                                         */
     const int32_t* map_offsets;    /* [n_maps]: the offset in consts of each map's block ([nx, ny, 0, 2 pi, 0, 2 pi, 1, 0], node[ny][nx][4]) */
+    /* REMD_CUSTOM_HBOND only (every other kind ignores them); it also reads nb_method and cutoff above                   */
+    int32_t hb_n_donors;           /* = n_terms, > 0                                                                       */
+    int32_t hb_n_acceptors;        /* > 0                                                                                  */
+    const int32_t* hb_donor_atoms; /* [hb_n_donors][3]: d1 d2 d3, -1 for an unused second or third particle                */
+    const int32_t* hb_acceptor_atoms; /* [hb_n_acceptors][3]: a1 a2 a3, likewise                                           */
+    int32_t hb_n_donor_params;     /* per-donor parameters: REMD_CX_PARAM operands 0 ... hb_n_donor_params - 1             */
+    const double* hb_donor_params; /* [hb_n_donors][hb_n_donor_params]                                                     */
+    int32_t hb_n_acceptor_params;  /* per-acceptor parameters: the operands behind the donor's                             */
+    const double* hb_acceptor_params; /* [hb_n_acceptors][hb_n_acceptor_params]                                            */
+    const int32_t* hb_excl_offsets; /* [hb_n_donors + 1]: donor i is excluded from hb_excl_acceptors[hb_excl_offsets[i] ... hb_excl_offsets[i + 1]) */
+    const int32_t* hb_excl_acceptors; /* acceptor indices, sorted within a row, none twice                                 */
+    int32_t hb_particle_mask;      /* bit s: the program names particle slot s (d1 d2 d3 = 0 1 2, a1 a2 a3 = 3 4 5)        */
 } remd_custom_force_desc;
 
 /* the custom forces of the system; call after remd_set_system (which forgets them).  n = 0: none.  Every custom force of a handle

@@ -88,6 +88,14 @@ class RemdCustomForceDescCMAP(RemdCustomForceDesc):
     _fields_ = [('map_index', c_int32_p), ('n_maps', C.c_int32), ('map_offsets', c_int32_p)]
 
 
+class RemdCustomForceDescHbond(RemdCustomForceDescCMAP):
+    """the same, then the fields of REMD_CUSTOM_HBOND behind those of REMD_CUSTOM_CMAP: the whole remd_custom_force_desc"""
+    _fields_ = [('hb_n_donors', C.c_int32), ('hb_n_acceptors', C.c_int32), ('hb_donor_atoms', c_int32_p), ('hb_acceptor_atoms', c_int32_p),
+                ('hb_n_donor_params', C.c_int32), ('hb_donor_params', c_double_p), ('hb_n_acceptor_params', C.c_int32),
+                ('hb_acceptor_params', c_double_p), ('hb_excl_offsets', c_int32_p), ('hb_excl_acceptors', c_int32_p),
+                ('hb_particle_mask', C.c_int32)]
+
+
 class RemdGbModelDesc(C.Structure):
     """remd_gb_model_desc of include/remd_hip_gb.h (the constants and the cutoff of an OBC-family implicit-solvent model)."""
     _fields_ = [('offset', C.c_double), ('alpha', C.c_double), ('beta', C.c_double), ('gamma', C.c_double), ('ke', C.c_double),
@@ -230,7 +238,7 @@ def load_library(path=None):
         for name in RESTRAINT_FRAMES_EXPORTS:
             getattr(lib, name).restype = C.c_int
     if hasattr(lib, 'remd_set_custom_terms'):             # include/remd_hip_custom.h (GPU-only, like the restraints)
-        lib.remd_set_custom_terms.argtypes = [vp, C.POINTER(RemdCustomForceDescCMAP), C.c_int]
+        lib.remd_set_custom_terms.argtypes = [vp, C.POINTER(RemdCustomForceDescHbond), C.c_int]
         lib.remd_set_custom_globals.argtypes = [vp, c_double_p]
         lib.remd_set_custom_lrc.argtypes = [vp, c_double_p]
         lib.remd_get_custom_energies.argtypes = [vp, c_double_p]
@@ -647,14 +655,14 @@ class HipEngine:
         n_cv = sum(len(t['cv_offsets']) - 1 for t in terms if 'cv_offsets' in t)
         if n_cv:
             self._custom_cv_entry('remd_get_custom_cv_values')
-        arr = (RemdCustomForceDescCMAP * max(1, len(terms)))()
+        arr = (RemdCustomForceDescHbond * max(1, len(terms)))()
         keep = []
         for k, t in enumerate(terms):
             atoms = np.ascontiguousarray(t['atoms'], dtype=np.int32)
             nonbonded = 'excl_offsets' in t                          # a nonbonded force: no atoms, one parameter row per particle
             params = np.ascontiguousarray(t['params'], dtype=np.float64)
-            n_terms = len(params) if nonbonded else len(atoms)
-            params = params.reshape(n_terms, -1)
+            n_terms = len(params) if nonbonded else len(t['donor_atoms']) if 'donor_atoms' in t else len(atoms)
+            params = params.reshape(n_terms, -1) if params.size or n_terms else np.zeros((n_terms, 0))
             n_particles = int(t.get('n_particles', 0))               # a compound-bond force: atoms [n][n_particles]
             program = np.ascontiguousarray(t['program'], dtype=np.int32).reshape(-1, 2)
             consts = np.ascontiguousarray(t['consts'], dtype=np.float64)
@@ -692,10 +700,25 @@ class HipEngine:
                     raise ValueError('set_custom_terms: map_index must hold one map per term (%d, not %d)' % (n_terms, len(m_index)))
                 keep += [m_index, m_off]
                 maps = (_ip(m_index), len(m_off), _ip(m_off))
-            no_atoms = nonbonded or 'cv_offsets' in t
-            arr[k] = RemdCustomForceDescCMAP(int(t['kind']), n_terms, None if no_atoms else _ip(atoms), params.shape[1], _dp(params), len(program), _ip(program),
+            hbond = (0, 0, None, None, 0, None, 0, None, None, None, 0)
+            if 'donor_atoms' in t:                                   # a donor-acceptor force: no atoms or parameters of the common kind
+                d_atoms = np.ascontiguousarray(t['donor_atoms'], dtype=np.int32).reshape(-1, 3)
+                a_atoms = np.ascontiguousarray(t['acceptor_atoms'], dtype=np.int32).reshape(-1, 3)
+                d_par = np.ascontiguousarray(t['donor_params'], dtype=np.float64).reshape(len(d_atoms), -1)
+                a_par = np.ascontiguousarray(t['acceptor_params'], dtype=np.float64).reshape(len(a_atoms), -1)
+                h_off = np.ascontiguousarray(t['hb_excl_offsets'], dtype=np.int32)
+                h_acc = np.ascontiguousarray(t['hb_excl_acceptors'], dtype=np.int32)
+                if len(h_off) != len(d_atoms) + 1 or len(h_acc) != h_off[-1]:
+                    raise ValueError('set_custom_terms: hb_excl_offsets must hold one row per donor and hb_excl_acceptors hb_excl_offsets[-1] = %d entries' % h_off[-1])
+                keep += [d_atoms, a_atoms, d_par, a_par, h_off, h_acc]
+                hbond = (len(d_atoms), len(a_atoms), _ip(d_atoms), _ip(a_atoms), d_par.shape[1], _dp(d_par) if d_par.size else None,
+                         a_par.shape[1], _dp(a_par) if a_par.size else None, _ip(h_off), _ip(h_acc) if len(h_acc) else None, int(t['particle_mask']))
+                pairs = (int(t['nb_method']), float(t['cutoff']), -1.0, None, None, 0)
+                params = None
+            no_atoms = nonbonded or 'cv_offsets' in t or 'donor_atoms' in t
+            arr[k] = RemdCustomForceDescHbond(int(t['kind']), n_terms, None if no_atoms else _ip(atoms), 0 if params is None else params.shape[1], _dp(params), len(program), _ip(program),
                                          len(consts), _dp(consts), int(t['stack_depth']), len(defaults), _dp(defaults),
-                                         int(t['periodic']), int(t['force_group']), n_particles, *groups, *pairs, *cvs, *maps)
+                                         int(t['periodic']), int(t['force_group']), n_particles, *groups, *pairs, *cvs, *maps, *hbond)
         self._check(fn(self.h, arr, len(terms)), 'remd_set_custom_terms')
         self.n_custom = len(terms)
         self.n_custom_cvs = n_cv

@@ -99,6 +99,18 @@ class AbsoluteAlchemicalFactory:
             # _alchemically_modify_CustomNonbondedForce (alchemy.py:2347-2396) is not built
             raise NotImplementedError('AbsoluteAlchemicalFactory: a System with a CustomNonbondedForce (the alchemical modification of a '
                                       'CustomNonbondedForce is not supported)')
+        from .system import CustomHbondForce
+        for f in reference_system.getForces():
+            # a CustomHbondForce passes through untouched where no donor or acceptor particle is alchemical; scaling its terms is not built
+            if isinstance(f, CustomHbondForce):
+                alchemical = set(int(i) for r in regions for i in r.alchemical_atoms)
+                for side, count, get in (('donor', f.getNumDonors(), f.getDonorParameters), ('acceptor', f.getNumAcceptors(), f.getAcceptorParameters)):
+                    for k in range(count):
+                        hit = sorted(alchemical & set(get(k)[:3]))
+                        if hit:
+                            raise NotImplementedError('AbsoluteAlchemicalFactory: CustomHbondForce (energy %r): %s %d holds the alchemical particle %d '
+                                                      '(the alchemical modification of a CustomHbondForce is not supported)'
+                                                      % (f.getEnergyFunction(), side, k, hit[0]))
         system = copy.deepcopy(reference_system)
         n = system.getNumParticles()
         seen = set()

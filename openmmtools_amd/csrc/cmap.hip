@@ -24,7 +24,7 @@ namespace {
 template <bool ENERGY>
 __global__ __launch_bounds__(64)
 void cmap_kernel(int total_pad, int w0, int waves, const cst_force* __restrict__ F, const int* __restrict__ wave_force,
-                 const int* __restrict__ atoms, const int* __restrict__ map_index /*[(waves - w0) * 64]*/, const int* __restrict__ map_off,
+                 const int* __restrict__ atoms, const int* __restrict__ map_index /*[the CMAP forces' slots]*/, const int* __restrict__ map_off,
                  const double* __restrict__ consts, int Npad, const float4* __restrict__ pos, const float* __restrict__ box,
                  long long* __restrict__ force, double* __restrict__ Ewave /*[R][waves]*/)
 {
@@ -62,9 +62,9 @@ void remd_cmap_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t 
 {
     const int waves = t.total_pad / 64, w0 = t.begin(CST_CMAP);
     if (with_energy)
-        hipLaunchKernelGGL(cmap_kernel<true>, dim3(waves - w0, h->R), dim3(64), 0, st, t.total_pad, w0, waves, t.d_F, t.d_wave_force, t.d_atoms,
+        hipLaunchKernelGGL(cmap_kernel<true>, dim3(t.end(CST_CMAP) - w0, h->R), dim3(64), 0, st, t.total_pad, w0, waves, t.d_F, t.d_wave_force, t.d_atoms,
                            t.d_map_index, t.d_map_off, t.d_consts, h->Npad, h->d_pos, h->d_box, h->d_force, t.d_Ewave);
     else
-        hipLaunchKernelGGL(cmap_kernel<false>, dim3(waves - w0, h->R), dim3(64), 0, st, t.total_pad, w0, waves, t.d_F, t.d_wave_force, t.d_atoms,
+        hipLaunchKernelGGL(cmap_kernel<false>, dim3(t.end(CST_CMAP) - w0, h->R), dim3(64), 0, st, t.total_pad, w0, waves, t.d_F, t.d_wave_force, t.d_atoms,
                            t.d_map_index, t.d_map_off, t.d_consts, h->Npad, h->d_pos, h->d_box, h->d_force, t.d_Ewave);
 }

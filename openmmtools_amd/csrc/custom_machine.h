@@ -1,6 +1,6 @@
 // The stack machine of the custom forces (include/remd_hip_custom.h), shared by custom_terms.hip (bond, angle, torsion, external),
-// custom_compound.hip (compound bonds), custom_centroid.hip (centroid bonds, whose particles are centroids) and custom_cv.hip
-// (collective variables, whose variables are RMSDs): the handle's tables (the per-force record and the host plan behind them live in
+// custom_compound.hip (compound bonds), custom_centroid.hip (centroid bonds, whose particles are centroids), custom_cv.hip
+// (collective variables, whose variables are RMSDs) and custom_hbond.hip (donor-acceptor pairs, whose particles are d1 d2 d3 a1 a2 a3): the handle's tables (the per-force record and the host plan behind them live in
 // custom_plan.h, which needs no HIP) and cst_eval, which runs a postfix program one term per lane with every stack slot a value and three partials, the stack in LDS as [slot][component][lane].
 // cmap.hip (CMAP torsion maps) runs no program: it shares the record, the tables and the patch of two arguments (table2d_patch.h).
 //
@@ -24,6 +24,7 @@ struct cst_tables : cst_plan {
     dev_array<int> d_grp_off, d_grp_atoms, d_grp_periodic, d_ref_off, d_refs; dev_array<double> d_grp_w;
     dev_array<int> d_cv_off, d_cv_atoms; dev_array<double> d_cv_ref;
     dev_array<int> d_map_off, d_map_index;
+    dev_array<int> d_hb_atoms;
     dev_array<int> d_excl_off, d_excl_atoms; dev_array<double> d_lrc;
     dev_array<int> d_mol_first, d_mol_size;
     dev_array<double> d_E;             // [R][nf]
@@ -318,3 +319,6 @@ void remd_custom_nonbonded_forces(remd_ctx* h, cst_tables& t, bool with_energy, 
 void remd_custom_nonbonded_lrc(remd_ctx* h, cst_tables& t, int ep_slot, hipStream_t st);
 void remd_custom_nonbonded_ukl(remd_ctx* h, cst_tables& t);
 void remd_custom_nonbonded_lrc_ukl(remd_ctx* h, cst_tables& t, double* d_rows);
+// custom_hbond.hip: the same for the donor-acceptor forces' tiles (the part CST_HBOND, the last one)
+void remd_custom_hbond_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
+void remd_custom_hbond_ukl(remd_ctx* h, cst_tables& t);

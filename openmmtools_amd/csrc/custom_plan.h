@@ -7,7 +7,8 @@
 //
 // A new kind: its REMD_CUSTOM_* value gets an entry in cst_part_of_kind, cst_width and cst_n_vars (and a cst_part of its own where it
 // has a kernel of its own), a validator beside cst_check_cmap called from cst_check_force, its share of cst_pack_force, and its
-// tables as members of cst_plan with one line in upload_tables (custom_terms.hip).  Nothing else lists the tables.
+// tables as members of cst_plan with one line in upload_tables (custom_terms.hip).  Nothing else lists the tables.  The donor-acceptor kind
+// (REMD_CUSTOM_HBOND) keeps its validator, its share of the packing and its molecules in custom_hbond_plan.h, included below.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -30,12 +31,19 @@ struct cst_force {
     int cv0, n_cvs;              // its first collective variable among the handle's, and how many it has (1 ... 3)
     // REMD_CUSTOM_CMAP only (cmap.hip): n_particles = 8, no program and no parameters; its constants are its maps' blocks
     int map0, n_maps;            // its first map among the handle's map_off, and how many it has (1 ... REMD_CUSTOM_MAX_MAPS)
+    // REMD_CUSTOM_HBOND only (custom_hbond.hip): n_terms = donors, npad = 64 x its tiles (donor blocks x acceptor blocks, row by row);
+    // it shares nb_method, cutoff and excl0 (its rows [donors + 1] in excl_off, acceptor indices in excl_atoms) with the nonbonded kind
+    int hb_na;                   // acceptors
+    int hb_atoms0;               // in the handle's hb_atoms: donors [3][ndpad], then acceptors [3][napad] (ndpad = 64 ceil(donors / 64), ...)
+    int hb_npd, hb_npa;          // per-donor and per-acceptor parameters: [hb_npd][ndpad] at par0, then [hb_npa][napad]
+    int hb_mask;                 // bit s: the program names particle slot s (d1 d2 d3 a1 a2 a3 = 0 ... 5); one seeded pass per bit
 };
 
 // The parts of the padded term space, in its order; each has its own kernels, which run the wavefronts [begin(part), end(part)).
-enum cst_part { CST_SIMPLE, CST_COMPOUND, CST_NONBONDED, CST_CENTROID, CST_CV, CST_CMAP, CST_N_PARTS };
+enum cst_part { CST_SIMPLE, CST_COMPOUND, CST_NONBONDED, CST_CENTROID, CST_CV, CST_CMAP, CST_HBOND, CST_N_PARTS };
 // indexed by REMD_CUSTOM_*: the part of a kind (the four one-variable kinds share the first)
-static const int cst_part_of_kind[REMD_CUSTOM_CMAP + 1] = {CST_SIMPLE, CST_SIMPLE, CST_SIMPLE, CST_SIMPLE, CST_COMPOUND, CST_CENTROID, CST_NONBONDED, CST_CV, CST_CMAP};
+// (kind 9 is not assigned and never gets this far: cst_check_shape refuses it; its entries below only keep the tables indexed by kind)
+static const int cst_part_of_kind[REMD_CUSTOM_HBOND + 1] = {CST_SIMPLE, CST_SIMPLE, CST_SIMPLE, CST_SIMPLE, CST_COMPOUND, CST_CENTROID, CST_NONBONDED, CST_CV, CST_CMAP, CST_HBOND, CST_HBOND};
 
 // everything the set-up computes on the host; the energy columns keep the forces' order whatever their slots
 struct cst_plan {
@@ -63,13 +71,16 @@ struct cst_plan {
     std::vector<double> cv_ref;        // beside cv_atoms, [.][3]: the reference, centred on each variable's own centroid
     // CMAP forces (cmap.hip): the maps of all of them and the map of every slot of their part of the padded term space
     std::vector<int> map_off;          // per map the offset of its block in consts (cst_force::map0 names a force's first)
-    std::vector<int> map_index;        // [total_pad - 64 begin(CST_CMAP)]: the slot's map among its force's, 0 ... n_maps - 1 (a padding slot repeats the last term's)
+    std::vector<int> map_index;        // [64 (end(CST_CMAP) - begin(CST_CMAP))]: the slot's map among its force's, 0 ... n_maps - 1 (a padding slot repeats the last term's)
     // nonbonded forces (custom_nonbonded.hip): the exclusion rows of all of them, and the long-range coefficients of the states
     std::vector<int> excl_off;         // per nonbonded force N + 1 offsets into excl_atoms (cst_force::excl0 names the first)
     std::vector<int> excl_atoms;       // symmetric, sorted within a row
     std::vector<double> lrc;           // [K][nf] kJ/mol nm^3: the energy is lrc[state][force] / V (zero for a force without the correction)
+    // donor-acceptor forces (custom_hbond.hip): per force the donors' particles [3][ndpad], then the acceptors' [3][napad]; -1: the donor
+    // (acceptor) has no such particle; a padding column repeats the last donor (acceptor).  Their exclusion rows join excl_off / excl_atoms.
+    std::vector<int> hb_atoms;
     bool has_lrc = false, lrc_valid = false;   // (lrc_valid: remd_set_custom_lrc ran since the globals were last set)
-    double periodic_cutoff = 0.0;      // the longest cutoff of a CutoffPeriodic nonbonded force (remd_ctx::cst_cutoff)
+    double periodic_cutoff = 0.0;      // the longest cutoff of a CutoffPeriodic nonbonded or donor-acceptor force (remd_ctx::cst_cutoff)
     // the molecules a barostat moves as wholes where the handle has no NonbondedForce to take them from (remd_custom_molecules): atoms
     // the custom bonds, angles, torsions and compound bonds join, each a contiguous range [first, first + size); empty: no table
     std::vector<int> mol_first, mol_size;
@@ -86,15 +97,17 @@ inline bool cst_is_compound(int kind) { return kind == REMD_CUSTOM_COMPOUND || k
 // atoms (group numbers) per term in the descriptor's `atoms`
 inline int cst_width(const remd_custom_force_desc& d)
 {
-    static const int width[REMD_CUSTOM_CMAP + 1] = {2, 3, 4, 1, -1, -1, 0, 0, 8};
+    static const int width[REMD_CUSTOM_HBOND + 1] = {2, 3, 4, 1, -1, -1, 0, 0, 8, 0, 0};
     return cst_is_compound(d.kind) ? d.n_particles : width[d.kind];
 }
 // the variables a program may name
 inline int cst_n_vars(const remd_custom_force_desc& d)
 {
-    static const int n_vars[REMD_CUSTOM_CMAP + 1] = {1, 1, 1, 3, -1, -1, 1, -1, 0};
+    static const int n_vars[REMD_CUSTOM_HBOND + 1] = {1, 1, 1, 3, -1, -1, 1, -1, 0, 0, 0};
     return cst_is_compound(d.kind) ? 3 * d.n_particles : d.kind == REMD_CUSTOM_CV ? d.n_cvs : n_vars[d.kind];
 }
+
+#include "custom_hbond_plan.h"     // the donor-acceptor kind's validator, packer and molecules (cst_check_hbond, cst_pack_hbond, cst_hbond_molecules)
 
 // the block of the function at consts[arg] (include/remd_hip_custom.h): the kernels trust n, min, max and the block's extent
 inline const char* cst_check_table1d(const remd_custom_force_desc& d, int op, int arg)
@@ -144,7 +157,8 @@ inline const char* cst_check_table2d3d(const remd_custom_force_desc& d, int op, 
 // what a program may do is settled here, once: the kernels index the stack, the constants, the parameters and the globals unchecked
 inline const char* check_program(const remd_custom_force_desc& d, int n_vars)
 {
-    const int n_par = d.kind == REMD_CUSTOM_NONBONDED ? 2 * d.n_params : d.n_params;     // (a pair: particle 1's parameters, then particle 2's)
+    const int n_par = d.kind == REMD_CUSTOM_NONBONDED ? 2 * d.n_params                   // (a pair: particle 1's parameters, then particle 2's)
+                    : d.kind == REMD_CUSTOM_HBOND ? d.hb_n_donor_params + d.hb_n_acceptor_params : d.n_params;   // (the donor's, then the acceptor's)
     if (d.n_program <= 0 || !d.program) return "an empty program";
     if (d.n_program > REMD_CUSTOM_MAX_PROGRAM) return "a program over REMD_CUSTOM_MAX_PROGRAM instructions";
     int sp = 0, top = 0;
@@ -163,10 +177,14 @@ inline const char* check_program(const remd_custom_force_desc& d, int n_vars)
         case REMD_CX_PERIODICDISTANCE: pops = 6; break;
         case REMD_CX_DISTANCE: case REMD_CX_ANGLE: case REMD_CX_DIHEDRAL: {
             // the zero-based particle slots in 4-bit fields, first argument lowest; nothing above them
-            if (!cst_is_compound(d.kind)) return "a function of particles outside a compound-bond or centroid-bond force";
+            const bool hbond = d.kind == REMD_CUSTOM_HBOND;
+            if (!cst_is_compound(d.kind) && !hbond) return "a function of particles outside a compound-bond or centroid-bond force";
             const int n_args = op - REMD_CX_DISTANCE + 2;
             if (arg < 0 || (arg >> (4 * n_args)) != 0) return "a particle slot out of range";
-            for (int k = 0; k < n_args; ++k) if (((arg >> (4 * k)) & 15) >= d.n_particles) return "a particle slot out of range";
+            for (int k = 0; k < n_args; ++k) {
+                const int slot = (arg >> (4 * k)) & 15;
+                if (slot >= (hbond ? 6 : d.n_particles)) return "a particle slot out of range";
+            }
             pops = 0;
         } break;
         case REMD_CX_POWI: if (arg < -64 || arg > 64) return "an integer power beyond +-64"; break;
@@ -190,8 +208,8 @@ inline const char* check_program(const remd_custom_force_desc& d, int n_vars)
 // every kind: the kind itself, the particles per term, the terms, the per-term parameters
 inline std::string cst_check_shape(const remd_custom_force_desc& d)
 {
-    if (d.kind < 0 || d.kind > REMD_CUSTOM_CMAP) return "unknown kind";
-    const bool cmap = d.kind == REMD_CUSTOM_CMAP, atomless = d.kind == REMD_CUSTOM_NONBONDED || d.kind == REMD_CUSTOM_CV;
+    if (d.kind < 0 || d.kind > REMD_CUSTOM_HBOND || d.kind == REMD_CUSTOM_CMAP + 1) return "unknown kind";      // (9 is not assigned)
+    const bool cmap = d.kind == REMD_CUSTOM_CMAP, atomless = d.kind == REMD_CUSTOM_NONBONDED || d.kind == REMD_CUSTOM_CV || d.kind == REMD_CUSTOM_HBOND;
     if (cmap && d.n_particles != 8) return "n_particles is 8 for a CMAP force (two dihedrals of four particles)";
     if (!cmap && (cst_is_compound(d.kind) ? (d.n_particles < 1 || d.n_particles > REMD_CUSTOM_MAX_PARTICLES) : d.n_particles != 0))
         return "n_particles is 1 ... REMD_CUSTOM_MAX_PARTICLES for a compound-bond or centroid-bond force and 0 for every other kind";
@@ -317,6 +335,7 @@ inline std::string cst_check_force(const remd_custom_force_desc& d, const remd_c
     if (bad.empty() && d.kind == REMD_CUSTOM_NONBONDED) bad = cst_check_nonbonded(d, s);
     if (bad.empty() && d.kind == REMD_CUSTOM_CV) bad = cst_check_cv(d, s.N);
     if (bad.empty() && d.kind == REMD_CUSTOM_CMAP) bad = cst_check_cmap(d);
+    if (bad.empty() && d.kind == REMD_CUSTOM_HBOND) bad = cst_check_hbond(d, s);
     if (bad.empty()) bad = cst_check_shared(d, d0);
     if (bad.empty() && d.kind != REMD_CUSTOM_CMAP)       // (a CMAP force has no program)
         if (const char* p = check_program(d, cst_n_vars(d))) bad = p;
@@ -349,6 +368,7 @@ inline void cst_pack_force(const remd_custom_force_desc& d, const cst_facts& s, 
         for (int a = 0; a <= d.n_terms; ++a) p.excl_off.push_back(base + d.excl_offsets[a]);
         if (d.excl_offsets[d.n_terms] > 0) p.excl_atoms.insert(p.excl_atoms.end(), d.excl_atoms, d.excl_atoms + d.excl_offsets[d.n_terms]);
     }
+    if (d.kind == REMD_CUSTOM_HBOND) cst_pack_hbond(d, f, p);
     // parameters [n_params][npad]; a padding slot repeats the last term (finite arithmetic in lanes that add nothing)
     for (int q = 0; q < d.n_params; ++q) for (int k = 0; k < par_stride; ++k) p.par.push_back(d.params[(size_t)std::min(k, d.n_terms - 1) * d.n_params + q]);
     if (d.n_program > 0) p.prog.insert(p.prog.end(), d.program, d.program + 2 * (size_t)d.n_program);
@@ -428,7 +448,7 @@ inline void cst_fill_refs(cst_plan& p)
 inline void cst_fill_map_index(const remd_custom_force_desc* desc, cst_plan& p)
 {
     const int slot_m = p.begin(CST_CMAP) * 64;
-    p.map_index.assign((size_t)p.total_pad - slot_m, 0);
+    p.map_index.assign((size_t)p.end(CST_CMAP) * 64 - slot_m, 0);
     for (int i = 0; i < p.nf; ++i) {
         const cst_force& f = p.F[i];
         if (f.kind != REMD_CUSTOM_CMAP) continue;
@@ -446,6 +466,7 @@ inline void cst_fill_molecules(const remd_custom_force_desc* desc, int N, cst_pl
     auto find = [&](int a) { while (root[a] != a) a = root[a] = root[root[a]]; return a; };
     for (int i = 0; i < p.nf; ++i) {
         const cst_force& f = p.F[i];
+        if (f.kind == REMD_CUSTOM_HBOND) { cst_hbond_molecules(desc[i], f, find, root); continue; }
         if (f.kind == REMD_CUSTOM_EXTERNAL || f.kind == REMD_CUSTOM_CENTROID || f.kind == REMD_CUSTOM_NONBONDED || f.kind == REMD_CUSTOM_CV) continue;
         for (int b = 0; b < f.n_terms; ++b) for (int a = 1; a < f.n_particles; ++a) {
             const int u = find(desc[i].atoms[(size_t)b * f.n_particles]), v = find(desc[i].atoms[(size_t)b * f.n_particles + a]);

@@ -28,7 +28,8 @@
 // custom_centroid.hip runs it for CustomCentroidBondForce, whose wavefronts come last; custom_nonbonded.hip runs it for
 // CustomNonbondedForce, one wavefront per tile of 64 x 64 atoms, between those two; custom_cv.hip runs it for CustomCVForce, one
 // wavefront per force behind the centroid forces', its variables the RMSDs a launch of its own computed.  cmap.hip (CMAPTorsionForce)
-// comes last and runs no program: it shares the term space, the tables and the energy reduction only.
+// runs no program: it shares the term space, the tables and the energy reduction only.  custom_hbond.hip runs the machine for
+// CustomHbondForce, one wavefront per tile of 64 donors x 64 acceptors; its tiles come last, so that no other kind's slot depends on them.
 #include "remd_internal.h"
 #include "listed_terms.h"
 #include "custom_machine.h"
@@ -197,7 +198,7 @@ int ensure_buffers(remd_ctx* h, cst_tables& t)
     }
     if (t.d_Ewave.size() != (size_t)h->R * waves) REMD_TRY(t.d_Ewave.alloc(h, (size_t)h->R * waves));
     // centroid forces: the centroids and the gradients on them (a handle without such a force: n_groups = 0, nothing is allocated)
-    const size_t nC = (size_t)h->R * t.n_groups * 3, nG = (size_t)h->R * (waves - t.begin(CST_CENTROID)) * 64 * REMD_CUSTOM_MAX_PARTICLES * 3;
+    const size_t nC = (size_t)h->R * t.n_groups * 3, nG = t.n_groups ? (size_t)h->R * (waves - t.begin(CST_CENTROID)) * 64 * REMD_CUSTOM_MAX_PARTICLES * 3 : 0;
     if (t.d_C.size() != nC) REMD_TRY(t.d_C.alloc(h, nC));
     if (t.d_G.size() != nG) REMD_TRY(t.d_G.alloc(h, nG));
     // collective-variable forces: what the superposition hands on (n_cv = 0: nothing is allocated)
@@ -220,7 +221,8 @@ int upload_tables(remd_ctx* h, cst_tables& t)
         (rc = t.d_refs.upload(h, t.refs)) || (rc = t.d_excl_off.upload(h, t.excl_off)) || (rc = t.d_excl_atoms.upload(h, t.excl_atoms)) ||
         (rc = t.d_lrc.upload(h, t.lrc)) || (rc = t.d_mol_first.upload(h, t.mol_first)) || (rc = t.d_mol_size.upload(h, t.mol_size)) ||
         (rc = t.d_cv_off.upload(h, t.cv_off)) || (rc = t.d_cv_atoms.upload(h, t.cv_atoms)) || (rc = t.d_cv_ref.upload(h, t.cv_ref)) ||
-        (rc = t.d_map_off.upload(h, t.map_off)) || (rc = t.d_map_index.upload(h, t.map_index))) return rc;
+        (rc = t.d_map_off.upload(h, t.map_off)) || (rc = t.d_map_index.upload(h, t.map_index)) ||
+        (rc = t.d_hb_atoms.upload(h, t.hb_atoms))) return rc;
     t.d_E.reset(); t.d_Ewave.reset(); t.d_D.reset(); t.d_C.reset(); t.d_G.reset(); t.d_W.reset();
     return 0;
 }
@@ -298,6 +300,7 @@ int remd_custom_forces(remd_ctx* h, bool with_energy, int ep_slot, hipStream_t s
     if (t.has(CST_CENTROID)) remd_custom_centroid_forces(h, t, with_energy, st);
     if (t.has(CST_CV)) remd_custom_cv_forces(h, t, with_energy, st);
     if (t.has(CST_CMAP)) remd_cmap_forces(h, t, with_energy, st);
+    if (t.has(CST_HBOND)) remd_custom_hbond_forces(h, t, with_energy, st);
     if (with_energy)
         hipLaunchKernelGGL(custom_reduce_kernel, dim3(h->R), dim3(64), 0, st, t.nf, t.d_F, waves, t.d_Ewave, t.d_E, h->d_epart, h->n_epart, ep_slot);
     if (with_energy && t.has_lrc) remd_custom_nonbonded_lrc(h, t, ep_slot, st);
@@ -328,6 +331,7 @@ int remd_custom_ukl(remd_ctx* h, double* d_rows)
     if (t.has(CST_NONBONDED)) remd_custom_nonbonded_ukl(h, t);
     if (t.has(CST_CENTROID)) remd_custom_centroid_ukl(h, t);
     if (t.has(CST_CV)) remd_custom_cv_ukl(h, t);
+    if (t.has(CST_HBOND)) remd_custom_hbond_ukl(h, t);
     hipLaunchKernelGGL(custom_ukl_reduce_kernel, dim3(h->K, h->R), dim3(64), 0, h->stream, h->K, waves, t.d_D, h->d_beta, d_rows);
     if (t.has_lrc) remd_custom_nonbonded_lrc_ukl(h, t, d_rows);
     REMD_CHECK(h, hipGetLastError());

@@ -1,6 +1,6 @@
-"""Compiler of OpenMM energy expressions for the custom bond, angle, torsion, external, compound-bond, centroid-bond and nonbonded forces
-(system.CustomBondForce, CustomAngleForce, CustomTorsionForce, CustomExternalForce, CustomCompoundBondForce, CustomCentroidBondForce,
-CustomNonbondedForce): an energy string becomes the postfix program of include/remd_hip_custom.h, which csrc/custom_terms.hip,
+"""Compiler of OpenMM energy expressions for the custom bond, angle, torsion, external, compound-bond, centroid-bond, nonbonded and
+donor-acceptor forces (system.CustomBondForce, CustomAngleForce, CustomTorsionForce, CustomExternalForce, CustomCompoundBondForce,
+CustomCentroidBondForce, CustomNonbondedForce, CustomHbondForce): an energy string becomes the postfix program of include/remd_hip_custom.h, which csrc/custom_terms.hip,
 csrc/custom_compound.hip, csrc/custom_centroid.hip, csrc/custom_cv.hip and csrc/custom_nonbonded.hip run on a forward-mode stack machine (every stack slot a value and its partial derivatives with respect to
 the force's variables).
 
@@ -16,6 +16,11 @@ A nonbonded force has the one variable r; a per-particle parameter p appears as 
 n_params + k for particle 2; at most MAX_PAIR_PARAMS per-particle parameters, so that MAX_PARAMS bounds the operand).  A bare
 per-particle name, a suffix 3 and x / y / z are refused by name.  Its long-range correction is computed here, on the host in f64
 (long_range_coefficients).
+
+A donor-acceptor force (system.CustomHbondForce) compiles through the compound-bond path: distance, angle and dihedral over the names
+d1 d2 d3 (particle slots 0 1 2) and a1 a2 a3 (slots 3 4 5), no coordinates, no pointdistance; the per-donor parameters are the first
+PARAM operands, the per-acceptor ones follow; the set of particle slots the expression names is recorded as a 6-bit mask
+(particle_mask): the engine runs one seeded pass per named slot (csrc/custom_hbond.hip).
 
 Grammar: numbers (exponent notation included), ``+ - * / ^``, unary minus, parentheses, function calls, and ``;``-separated
 definitions ``name = expr`` in any order, substituted where they are used.  ``^`` binds tighter than unary minus and groups to the
@@ -48,9 +53,11 @@ KIND_CV = 7                                     # system.CustomCVForce over RMSD
 MAX_CVS = 3                                     # collective variables per CustomCVForce: the machine carries three partials
 KIND_CMAP = 8                                   # system.CMAPTorsionForce: no expression, the energy a map of two dihedrals (csrc/cmap.hip)
 MAX_MAPS = 64                                   # maps per CMAPTorsionForce
+KIND_HBOND = 10                                 # system.CustomHbondForce: donor-acceptor pairs (csrc/custom_hbond.hip)
+HBOND_SLOTS = dict(d1=0, d2=1, d3=2, a1=3, a2=4, a3=5)   # the particle names of a donor-acceptor expression -> particle slot
 KIND_OF_CLASS = {'CustomNonbondedForce': KIND_NONBONDED, 'CustomBondForce': KIND_BOND, 'CustomAngleForce': KIND_ANGLE, 'CustomTorsionForce': KIND_TORSION,
                  'CustomExternalForce': KIND_EXTERNAL, 'CustomCompoundBondForce': KIND_COMPOUND, 'CustomCentroidBondForce': KIND_CENTROID,
-                 'CustomCVForce': KIND_CV, 'CMAPTorsionForce': KIND_CMAP}
+                 'CustomCVForce': KIND_CV, 'CMAPTorsionForce': KIND_CMAP, 'CustomHbondForce': KIND_HBOND}
 VARIABLES = {KIND_BOND: ('r',), KIND_ANGLE: ('theta',), KIND_TORSION: ('theta',), KIND_EXTERNAL: ('x', 'y', 'z'), KIND_NONBONDED: ('r',)}
 
 
@@ -357,7 +364,7 @@ def _table_block(name, function, where):
 
 
 def compile_expression(energy, variables, parameters, global_columns, where='expression', tabulated=(), periodic_distance=False,
-                       n_particles=0, particle_prefix='p', pair_parameters=()):
+                       n_particles=0, particle_prefix='p', pair_parameters=(), particle_slots=None):
     """The postfix program of ``energy``.
 
     variables: the force's own variable names in operand order; parameters: the per-term parameter names in order; global_columns:
@@ -369,9 +376,10 @@ def compile_expression(energy, variables, parameters, global_columns, where='exp
     per bond of a compound-bond force (0: another force), which opens distance / angle / dihedral over p1 ... pP and pointdistance;
     particle_prefix: 'p', or 'g' for the groups g1 ... gP of a centroid-bond force (the messages then speak of groups);
     pair_parameters: the per-particle parameter names of a nonbonded force, in order: name p is legal as p1 (PARAM operand k) and p2
-    (operand len(pair_parameters) + k) only.
+    (operand len(pair_parameters) + k) only; particle_slots: {particle name: slot} of a donor-acceptor force (HBOND_SLOTS), which opens
+    distance / angle / dihedral over exactly those names and nothing else of the compound-bond forces.
 
-    Returns dict(program int32 [n][2], consts float64 [m], stack_depth).
+    Returns dict(program int32 [n][2], consts float64 [m], stack_depth), and particle_mask (bit s: slot s is named) with particle_slots.
     """
     body, definitions = split_definitions(energy, where)
     _PARTICLE_NAME, noun = _PARTICLE_NAMES[particle_prefix]
@@ -381,6 +389,7 @@ def compile_expression(energy, variables, parameters, global_columns, where='exp
     functions = dict(tabulated)                 # name -> function
     blocks, table_calls = {}, []                # name -> (opcode, block), in the order first called; (instruction, name) of every call
     depth = [0, 0]                              # current, maximum
+    named_slots = set()                         # (particle_slots) the slots the expression names
 
     def tree_of(name):
         if name not in trees:
@@ -427,6 +436,8 @@ def compile_expression(energy, variables, parameters, global_columns, where='exp
                                               % (where, name, name.rstrip('0123456789'), name.rstrip('0123456789')))
                 if name in ('x', 'y', 'z'):
                     raise NotImplementedError('%s: variable %r (the only variable of a nonbonded force is r)' % (where, name))
+            if particle_slots is not None and name in particle_slots:
+                raise NotImplementedError('%s: particle name %r outside distance(), angle() and dihedral()' % (where, name))
             if n_particles and _PARTICLE_NAME.fullmatch(name):
                 raise NotImplementedError('%s: %s name %r outside distance(), angle() and dihedral()' % (where, noun, name))
             if n_particles and _PARTICLE_NAMES[other][0].fullmatch(name):
@@ -460,6 +471,20 @@ def compile_expression(energy, variables, parameters, global_columns, where='exp
                     walk(a, active)
                 table_calls.append((len(program), name))
                 return emit(blocks[name][0])
+            if particle_slots is not None and name in PARTICLE_FUNCTIONS:
+                op, n_args = PARTICLE_FUNCTIONS[name]
+                if len(args) != n_args:
+                    raise NotImplementedError('%s: function %r takes %d particles, not %d' % (where, name, n_args, len(args)))
+                packed = 0
+                for k, a in enumerate(args):
+                    if a[0] != 'name' or a[1] not in particle_slots:
+                        raise NotImplementedError('%s: the arguments of %r are particle names among %s%s' % (
+                            where, name, ' '.join(particle_slots), ', not %r' % (a[1],) if a[0] == 'name' else ''))
+                    named_slots.add(particle_slots[a[1]])
+                    packed |= particle_slots[a[1]] << (4 * k)
+                return emit(op, packed)
+            if particle_slots is not None and name in ('pointdistance', 'pointangle', 'pointdihedral'):
+                raise NotImplementedError('%s: function %r (pointdistance, pointangle and pointdihedral are not functions of this force)' % (where, name))
             if n_particles and name in PARTICLE_FUNCTIONS:
                 op, n_args = PARTICLE_FUNCTIONS[name]
                 if len(args) != n_args:
@@ -507,8 +532,11 @@ def compile_expression(energy, variables, parameters, global_columns, where='exp
         raise NotImplementedError('%s: a program of %d instructions (the engine takes %d)' % (where, len(program), MAX_PROGRAM))
     if depth[1] > MAX_STACK:
         raise NotImplementedError('%s: an expression that needs %d stack slots (the engine has %d)' % (where, depth[1], MAX_STACK))
-    return dict(program=np.array(program, dtype=np.int32).reshape(-1, 2), consts=np.array(consts, dtype=np.float64),
-                stack_depth=int(depth[1]))
+    out = dict(program=np.array(program, dtype=np.int32).reshape(-1, 2), consts=np.array(consts, dtype=np.float64),
+               stack_depth=int(depth[1]))
+    if particle_slots is not None:
+        out['particle_mask'] = sum(1 << s for s in named_slots)
+    return out
 
 
 # ---- the forces of a System -------------------------------------------------------------------------------------------------------
@@ -523,7 +551,7 @@ def is_custom_term_force(force):
     from . import system as _system
     from . import forces as _forces
     if isinstance(force, (_system.CustomCompoundBondForce, _system.CustomCentroidBondForce, _system.CustomNonbondedForce,
-                          _system.CustomCVForce, _system.RMSDForce, _system.CMAPTorsionForce)):
+                          _system.CustomCVForce, _system.RMSDForce, _system.CMAPTorsionForce, _system.CustomHbondForce)):
         return True
     if isinstance(force, _system.CustomExternalForce):
         return not force.is_harmonic_oscillator()
@@ -988,6 +1016,11 @@ def custom_terms_desc(forces, masses=None, box_vectors=None):
                 out['%03d' % len(out)] = entry
             continue
         where = '%s (energy %r)' % (cls, f.getEnergyFunction())
+        if kind == KIND_HBOND:
+            entry = _hbond_entry(f, cls, where, names, defaults, columns, masses, box_vectors)
+            if entry is not None:
+                out['%03d' % len(out)] = entry
+            continue
         per_term = _per_term_names(f)
         if kind == KIND_NONBONDED and len(per_term) > MAX_PAIR_PARAMS:
             raise NotImplementedError('%s: %d per-particle parameters (the engine takes %d): %s' % (cls, len(per_term), MAX_PAIR_PARAMS, ', '.join(per_term)))
@@ -1080,6 +1113,121 @@ def _nonbonded_entry(f, cls, prog, names, defaults, per_term, masses, box_vector
                 stack_depth=prog['stack_depth'], periodic=int(method == 2), force_group=int(f.getForceGroup()),
                 energy=f.getEnergyFunction(), nb_method=method, cutoff=cutoff, switch_distance=switch, excl_offsets=offsets,
                 excl_atoms=atoms, long_range_correction=int(bool(f.getUseLongRangeCorrection()) and method == 2))
+
+
+def hbond_exclusions(force, n_donors, n_acceptors):
+    """The exclusions of a donor-acceptor force in CSR form: (offsets int32 [n_donors + 1], acceptors int32), each row sorted."""
+    rows = [set() for _ in range(n_donors)]
+    for k in range(force.getNumExclusions()):
+        i, j = force.getExclusionParticles(k)
+        if not 0 <= i < n_donors:
+            raise ValueError('CustomHbondForce: exclusion %d names donor %d (the force has %d)' % (k, i, n_donors))
+        if not 0 <= j < n_acceptors:
+            raise ValueError('CustomHbondForce: exclusion %d names acceptor %d (the force has %d)' % (k, j, n_acceptors))
+        if j in rows[i]:
+            raise ValueError('CustomHbondForce: donor %d and acceptor %d are excluded twice' % (i, j))
+        rows[i].add(j)
+    offsets = np.zeros(n_donors + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum([len(r) for r in rows])
+    return offsets, np.array([j for r in rows for j in sorted(r)], dtype=np.int32), rows
+
+
+def _hbond_entry(f, cls, where, names, defaults, columns, masses, box_vectors):
+    """the entry of a donor-acceptor force, or None for an empty one: atoms is empty, params [0][0]; donor_atoms [nD][3] and
+    acceptor_atoms [nA][3] (-1: unused), donor_params, acceptor_params, hb_excl_offsets / hb_excl_acceptors, nb_method, cutoff and
+    particle_mask beside the common keys"""
+    per_donor = [f.getPerDonorParameterName(i) for i in range(f.getNumPerDonorParameters())]
+    per_acceptor = [f.getPerAcceptorParameterName(i) for i in range(f.getNumPerAcceptorParameters())]
+    if len(per_donor) + len(per_acceptor) > MAX_PARAMS:
+        raise NotImplementedError('%s: %d per-donor and %d per-acceptor parameters (the engine takes %d together): %s'
+                                  % (cls, len(per_donor), len(per_acceptor), MAX_PARAMS, ', '.join(per_donor + per_acceptor)))
+    twice = [n for n in per_acceptor if n in per_donor]
+    if twice:
+        raise ValueError('%s: %r is both a per-donor and a per-acceptor parameter' % (cls, twice[0]))
+    tabulated = [(f.getTabulatedFunctionName(i), f.getTabulatedFunction(i)) for i in range(f.getNumTabulatedFunctions())]
+    own = {n: columns[n] for n in (f.getGlobalParameterName(i) for i in range(f.getNumGlobalParameters()))}
+    prog = compile_expression(f.getEnergyFunction(), (), per_donor + per_acceptor, own, where=where, tabulated=tabulated, particle_slots=HBOND_SLOTS)
+    mask = prog['particle_mask']
+    n_atoms = None if masses is None else len(masses)
+    nD, nA = f.getNumDonors(), f.getNumAcceptors()
+    if nD == 0 and nA == 0:
+        return None
+    if nD == 0 or nA == 0:
+        trivial = len(prog['program']) == 1 and prog['program'][0, 0] == CONST and prog['consts'][prog['program'][0, 1]] == 0.0
+        if trivial:
+            return None
+        raise ValueError('%s has %d donors and %d acceptors: a force with %s has no pair to act on'
+                         % (where, nD, nA, 'donors but no acceptors' if nA == 0 else 'acceptors but no donors'))
+    sides = []
+    for side, count, get, n_par, first_slot in (('donor', nD, f.getDonorParameters, len(per_donor), 0), ('acceptor', nA, f.getAcceptorParameters, len(per_acceptor), 3)):
+        atoms, params = np.empty((count, 3), dtype=np.int32), np.empty((count, n_par), dtype=np.float64)
+        for k in range(count):
+            row = get(k)
+            p, values = [int(a) for a in row[:3]], list(row[3])
+            if len(values) != n_par:
+                raise ValueError('%s: %s %d carries %d parameters, the force declares %d' % (cls, side, k, len(values), n_par))
+            if p[0] == -1:
+                raise ValueError('%s: %s %d has no first particle (%s1 = -1)' % (cls, side, k, side[0]))
+            for q, a in enumerate(p):
+                if a < -1 or (n_atoms is not None and a >= n_atoms):
+                    raise ValueError('%s: %s %d names particle %d (the System has %s)' % (cls, side, k, a, n_atoms))
+                if a >= 0 and a in p[:q]:
+                    raise ValueError('%s: %s %d names particle %d twice' % (cls, side, k, a))
+                if a == -1 and (mask >> (first_slot + q)) & 1:
+                    raise ValueError('%s: the expression names %s%d, which %s %d does not have (-1)' % (where, side[0], q + 1, side, k))
+            atoms[k], params[k] = p, values
+        sides.append((atoms, params))
+    (d_atoms, d_params), (a_atoms, a_params) = sides
+    offsets, excluded, rows = hbond_exclusions(f, nD, nA)
+    # a pair that shares a particle has no geometry of its own: OpenMM leaves it to the user to exclude it
+    of_atom = {}
+    for j in range(nA):
+        for a in a_atoms[j]:
+            if a >= 0:
+                of_atom.setdefault(int(a), []).append(j)
+    for i in range(nD):
+        for a in d_atoms[i]:
+            for j in of_atom.get(int(a), ()) if a >= 0 else ():
+                if j not in rows[i]:
+                    raise ValueError('%s: donor %d and acceptor %d share particle %d and are not excluded: add the exclusion (addExclusion(%d, %d))'
+                                     % (cls, i, j, a, i, j))
+    method = int(f.getNonbondedMethod())
+    cutoff = float(f.getCutoffDistance()) if method else 0.0
+    if method and not cutoff > 0.0:
+        raise ValueError('%s: cutoff distance %r' % (cls, cutoff))
+    if method == 2:
+        if box_vectors is None:
+            raise ValueError('%s: CutoffPeriodic needs the periodic box vectors of the System' % cls)
+        box = np.asarray(box_vectors, dtype=np.float64).reshape(3, 3)
+        if np.any(box != np.diag(np.diag(box))):
+            raise NotImplementedError('%s: triclinic boxes are not supported (CutoffPeriodic takes a rectangular box)' % cls)
+        if cutoff > 0.5 * np.diag(box).min():
+            raise ValueError('%s: the cutoff %r nm exceeds half the smallest box edge (%r nm)' % (cls, cutoff, float(np.diag(box).min())))
+    return dict(kind=KIND_HBOND, atoms=np.zeros((0, 0), dtype=np.int32), params=np.zeros((0, 0)), global_names=list(names),
+                global_defaults=np.array(defaults, dtype=np.float64), program=prog['program'], consts=prog['consts'],
+                stack_depth=prog['stack_depth'], periodic=int(method == 2), force_group=int(f.getForceGroup()),
+                energy=f.getEnergyFunction(), nb_method=method, cutoff=cutoff, donor_atoms=d_atoms, acceptor_atoms=a_atoms,
+                donor_params=d_params, acceptor_params=a_params, hb_excl_offsets=offsets, hb_excl_acceptors=excluded,
+                particle_mask=int(mask))
+
+
+def check_hbond_molecules(desc, terms):
+    """The engine's barostats move and wrap molecule by molecule: under CutoffPeriodic the particles of one donor, and of one
+    acceptor, must lie in one molecule (their differences are minimum images, so a wrapped molecule is fine, a split donor is not)."""
+    molecule = None
+    for t in terms.values():
+        if t['kind'] != KIND_HBOND or int(t['nb_method']) != 2:
+            continue
+        if molecule is None:
+            molecule = barostat_molecules(desc)
+            if molecule is None:            # (no NonbondedForce: the library joins every donor's and acceptor's particles itself)
+                return
+        for side, key in (('donor', 'donor_atoms'), ('acceptor', 'acceptor_atoms')):
+            for k, row in enumerate(np.asarray(t[key])):
+                mols = {int(molecule[a]) for a in row if a >= 0}
+                if len(mols) > 1:
+                    raise NotImplementedError('CustomHbondForce (energy %r): %s %d (particles %s) spans %d molecules under CutoffPeriodic '
+                                              '(the barostat moves molecules as wholes)' % (t['energy'], side, k, [int(a) for a in row if a >= 0], len(mols)))
 
 
 def custom_globals(system, names, states):

@@ -894,6 +894,108 @@ class CustomNonbondedForce(_CustomForce):
         return 0
 
 
+class CustomHbondForce(_CustomForce):
+    """openmm.CustomHbondForce: donors (up to three particles d1 d2 d3) and acceptors (a1 a2 a3), the energy an expression of
+    distance(), angle() and dihedral() among the six, of per-donor, per-acceptor and global parameters and of tabulated functions,
+    summed over every (donor, acceptor) pair that no exclusion names and, with a cutoff, whose distance(d1, a1) is below it.  -1 marks
+    an unused second or third particle; the expression may name only particles every donor and acceptor has.  Every expression goes
+    to csrc/custom_hbond.hip (one wavefront per tile of 64 donors x 64 acceptors: the cost is proportional to donors x acceptors).
+    A non-excluded pair that shares a particle is refused, as are raw coordinates and pointdistance / pointangle / pointdihedral."""
+    NoCutoff, CutoffNonPeriodic, CutoffPeriodic = 0, 1, 2
+
+    def __init__(self, energy):
+        super().__init__(energy)
+        self._per_acceptor = []               # per-acceptor parameter names (_per_bond holds the per-donor ones)
+        self._donors = []                     # (d1, d2, d3, parameters)
+        self._acceptors = []                  # (a1, a2, a3, parameters)
+        self._exclusions = []                 # (donor, acceptor)
+        self._method = CustomHbondForce.NoCutoff
+        self._cutoff = 1.0
+
+    addPerDonorParameter = _CustomForce.addPerBondParameter
+    getNumPerDonorParameters = _CustomForce.getNumPerBondParameters
+    getPerDonorParameterName = _CustomForce.getPerBondParameterName
+
+    def addPerAcceptorParameter(self, name):
+        self._per_acceptor.append(str(name))
+        return len(self._per_acceptor) - 1
+
+    def getNumPerAcceptorParameters(self):
+        return len(self._per_acceptor)
+
+    def getPerAcceptorParameterName(self, index):
+        return self._per_acceptor[index]
+
+    @staticmethod
+    def _row(p1, p2, p3, parameters):
+        return (int(p1), int(p2), int(p3), [float(p) for p in parameters])
+
+    def addDonor(self, d1, d2, d3, parameters=()):
+        self._donors.append(self._row(d1, d2, d3, parameters))
+        return len(self._donors) - 1
+
+    def getNumDonors(self):
+        return len(self._donors)
+
+    def getDonorParameters(self, index):
+        d1, d2, d3, parameters = self._donors[index]
+        return d1, d2, d3, list(parameters)
+
+    def setDonorParameters(self, index, d1, d2, d3, parameters=()):
+        self._donors[index] = self._row(d1, d2, d3, parameters)
+
+    def addAcceptor(self, a1, a2, a3, parameters=()):
+        self._acceptors.append(self._row(a1, a2, a3, parameters))
+        return len(self._acceptors) - 1
+
+    def getNumAcceptors(self):
+        return len(self._acceptors)
+
+    def getAcceptorParameters(self, index):
+        a1, a2, a3, parameters = self._acceptors[index]
+        return a1, a2, a3, list(parameters)
+
+    def setAcceptorParameters(self, index, a1, a2, a3, parameters=()):
+        self._acceptors[index] = self._row(a1, a2, a3, parameters)
+
+    def addExclusion(self, donor, acceptor):
+        self._exclusions.append((int(donor), int(acceptor)))
+        return len(self._exclusions) - 1
+
+    def getNumExclusions(self):
+        return len(self._exclusions)
+
+    def getExclusionParticles(self, index):
+        return self._exclusions[index]
+
+    def setExclusionParticles(self, index, donor, acceptor):
+        self._exclusions[index] = (int(donor), int(acceptor))
+
+    def setNonbondedMethod(self, method):
+        if int(method) not in (0, 1, 2):
+            raise ValueError('CustomHbondForce: nonbonded method %r (NoCutoff, CutoffNonPeriodic or CutoffPeriodic)' % (method,))
+        self._method = int(method)
+
+    def getNonbondedMethod(self):
+        return self._method
+
+    def setCutoffDistance(self, distance):
+        self._cutoff = float(distance)
+
+    def getCutoffDistance(self):
+        return self._cutoff
+
+    def usesPeriodicBoundaryConditions(self):
+        return self._method == CustomHbondForce.CutoffPeriodic
+
+    def setUsesPeriodicBoundaryConditions(self, periodic):
+        raise ValueError('CustomHbondForce: periodic boundary conditions follow the nonbonded method (setNonbondedMethod(CutoffPeriodic))')
+
+    def updateParametersInContext(self, context=None):
+        raise NotImplementedError('CustomHbondForce: changing donors, acceptors or exclusions after set_system (updateParametersInContext) is not '
+                                  'supported: build the System again')
+
+
 class GBSAOBCForce(Force):
     """openmm.GBSAOBCForce: OBC2 Born radii + ACE surface term (the form the reference's alchemical factory spells out, alchemy.py:2144-2225).
     NoCutoff only."""
@@ -1583,8 +1685,9 @@ def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
         from .custom_expr import custom_terms_desc
         terms = custom_terms_desc(custom, system.masses, box_vectors=system.getDefaultPeriodicBoxVectors())
         if terms:
-            from .custom_expr import check_cv_molecules
+            from .custom_expr import check_cv_molecules, check_hbond_molecules
             check_cv_molecules(d, terms)
+            check_hbond_molecules(d, terms)
             d['custom_terms'] = terms
             # the handle's global-parameter columns, once (every entry above repeats them for remd_custom_force_desc)
             first = terms['000']
@@ -1608,6 +1711,47 @@ def virtual_site_from_openmm(site):
         return OutOfPlaneSite(p[0], p[1], p[2], site.getWeight12(), site.getWeight13(), site.getWeightCross())
     raise NotImplementedError('virtual site class %s is not supported (TwoParticleAverageSite, ThreeParticleAverageSite and '
                               'OutOfPlaneSite are)' % name)
+
+
+def hbond_force_from_openmm(f):
+    """An openmm.CustomHbondForce as the class of the same name here; by the object's getters, so that no OpenMM is needed.  The cutoff
+    may carry a unit (anything with value_in_unit) or be a number in nm; functions are taken over as they are when they are this
+    module's classes and rebuilt from getFunctionParameters() by class name otherwise."""
+    g = CustomHbondForce(f.getEnergyFunction())
+    for i in range(f.getNumPerDonorParameters()):
+        g.addPerDonorParameter(f.getPerDonorParameterName(i))
+    for i in range(f.getNumPerAcceptorParameters()):
+        g.addPerAcceptorParameter(f.getPerAcceptorParameterName(i))
+    for i in range(f.getNumGlobalParameters()):
+        g.addGlobalParameter(f.getGlobalParameterName(i), f.getGlobalParameterDefaultValue(i))
+    functions = dict(Continuous1DFunction=Continuous1DFunction, Discrete1DFunction=Discrete1DFunction, Continuous2DFunction=Continuous2DFunction,
+                     Discrete2DFunction=Discrete2DFunction, Discrete3DFunction=Discrete3DFunction)
+    for i in range(f.getNumTabulatedFunctions()):
+        fn, name = f.getTabulatedFunction(i), f.getTabulatedFunctionName(i)
+        cls = type(fn).__name__
+        if cls not in functions:
+            raise NotImplementedError('CustomHbondForce: tabulated function %r is a %s (Continuous1DFunction, Discrete1DFunction, '
+                                      'Continuous2DFunction, Discrete2DFunction and Discrete3DFunction are supported)' % (name, cls))
+        if not isinstance(fn, tuple(functions.values())):
+            args = list(fn.getFunctionParameters())
+            fn = functions[cls](*args, **(dict(periodic=bool(fn.getPeriodic())) if hasattr(fn, 'getPeriodic') else {}))
+        g.addTabulatedFunction(name, fn)
+    for i in range(f.getNumDonors()):
+        d1, d2, d3, parameters = f.getDonorParameters(i)
+        g.addDonor(d1, d2, d3, parameters)
+    for i in range(f.getNumAcceptors()):
+        a1, a2, a3, parameters = f.getAcceptorParameters(i)
+        g.addAcceptor(a1, a2, a3, parameters)
+    for i in range(f.getNumExclusions()):
+        g.addExclusion(*f.getExclusionParticles(i))
+    g.setNonbondedMethod(int(f.getNonbondedMethod()))
+    cutoff = f.getCutoffDistance()
+    if hasattr(cutoff, 'value_in_unit_system'):
+        from .unit import to_md
+        cutoff = to_md(cutoff)
+    g.setCutoffDistance(cutoff)
+    g.setForceGroup(int(f.getForceGroup()))
+    return g
 
 
 def from_openmm(omm_system):
@@ -1669,6 +1813,8 @@ def from_openmm(omm_system):
                 g.addTorsion(*f.getTorsionParameters(k))
             g.setUsesPeriodicBoundaryConditions(f.usesPeriodicBoundaryConditions())
             g.setForceGroup(f.getForceGroup())
+        elif type(f).__name__ == 'CustomHbondForce':
+            g = hbond_force_from_openmm(f)
         else:
             raise NotImplementedError('unsupported OpenMM force %s' % type(f).__name__)
         s.addForce(g)

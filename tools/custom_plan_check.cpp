@@ -64,8 +64,9 @@ int main(int argc, char** argv)
         printf("scalars 10 %d %d %d %d %d %d %d %d %d %lld\n", p.nf, p.ng, p.K, p.total_pad, p.n_groups, p.n_cv, (int)p.uniform, (int)p.has_lrc,
                (int)p.lrc_valid, p.glob_version);
         printf("periodic_cutoff 1 %a\n", p.periodic_cutoff);
-        printf("part_end %d", (int)CST_N_PARTS); for (int k = 0; k < CST_N_PARTS; ++k) printf(" %d", p.end(k)); printf("\n");
-        printf("part_begin %d", (int)CST_N_PARTS); for (int k = 0; k < CST_N_PARTS; ++k) printf(" %d", p.begin(k)); printf("\n");
+        // (the parts of the kinds this program can describe; the donor-acceptor part, the last one, has tools/custom_hbond_plan_check.cpp)
+        printf("part_end %d", (int)CST_HBOND); for (int k = 0; k < CST_HBOND; ++k) printf(" %d", p.end(k)); printf("\n");
+        printf("part_begin %d", (int)CST_HBOND); for (int k = 0; k < CST_HBOND; ++k) printf(" %d", p.begin(k)); printf("\n");
         for (const cst_force& f : p.F)
             printf("force 20 %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %a %a\n", f.kind, f.periodic, f.n_terms, f.n_params, f.n_particles,
                    f.slot0, f.npad, f.par0, f.prog0, f.n_prog, f.const0, f.nb_method, f.excl0, f.lrc, f.cv0, f.n_cvs, f.map0, f.n_maps, f.cutoff, f.switch_dist);
