@@ -1,6 +1,7 @@
 /*
  * remd_hip_custom.h — GPU-only extension of the C ABI in remd_hip.h: custom bond, angle, torsion, external, compound-bond,
- * centroid-bond, nonbonded, collective-variable and donor-acceptor (hydrogen-bond) forces, and CMAP torsion maps.
+ * centroid-bond, nonbonded, collective-variable, donor-acceptor (hydrogen-bond) and many-particle (three-body) forces, and CMAP
+ * torsion maps.
  *
  * OpenMM's CustomBondForce, CustomAngleForce, CustomTorsionForce and CustomExternalForce: an energy expression of r (bond), theta
  * (angle, torsion) or x, y, z (external), of per-term parameters and of global parameters, evaluated per term.  The host compiles
@@ -95,6 +96,27 @@
  * tiles visited (csrc/custom_hbond.hip): the cost is proportional to nD nA, there is no list.  Degenerate geometry follows
  * REMD_CX_DISTANCE / ANGLE / DIHEDRAL.
  *
+ * Many-particle forces (REMD_CUSTOM_MANYPARTICLE, OpenMM's CustomManyParticleForce with three particles per set): the energy is an
+ * expression of the distances, angles and dihedrals among the particles p1 p2 p3 of a set (REMD_CX_DISTANCE / REMD_CX_ANGLE /
+ * REMD_CX_DIHEDRAL with p1 p2 p3 the particle slots 0 1 2; no REMD_CX_VAR), of per-particle parameters and of global parameters,
+ * summed over sets of three distinct particles.  n_terms = N, atoms NULL, n_particles = 0, params [N][n_params] with n_params <=
+ * REMD_CUSTOM_MAX_PARAMS / 3: REMD_CX_PARAM operand 3 q + s is parameter q of the particle in slot s.  mp_permutation_mode 0
+ * (SinglePermutation): every unordered set {i, j, k} once; with a cutoff all three distances must lie below it.  1
+ * (UniqueCentralParticle): every set once per choice of its central particle p1, the other two unordered; with a cutoff only the two
+ * distances to p1 must lie below it.  A set in which any pair is excluded is skipped (excl_offsets / excl_atoms as for
+ * REMD_CUSTOM_NONBONDED, symmetric, and here each row must be sorted and name no particle twice).  mp_types [N] holds every particle's
+ * type 0 ... 31; mp_filter[s] has bit t set where type t may fill slot s (all ones: no filter).  Of the assignments of a set to the
+ * slots (six in mode 0, the two with p1 the central particle in mode 1) the first in lexicographic order of the atom indices
+ * (p1, p2, p3) that passes all three filters is evaluated; a set without one is skipped.  mp_particle_mask has bit s set for every
+ * slot the program names, and only those: the device runs one seeded pass per set bit.  nb_method, cutoff and periodic as for
+ * REMD_CUSTOM_NONBONDED (switch_distance and long_range_correction are ignored); with nb_method 0 N is at most
+ * REMD_CUSTOM_MP_MAX_NEIGHBORS + 1.  Two launches (csrc/custom_manyparticle.hip): a neighbour row of at most
+ * REMD_CUSTOM_MP_MAX_NEIGHBORS entries per particle and replica, then one wavefront per central particle over the pairs of its row.
+ * A central particle whose row would overflow makes that replica's energy NaN (and adds no force): the device cannot raise, the
+ * caller's NaN check sees it, as for the lookup opcodes.  A force evaluation without energies (an MD or minimiser step) drops that
+ * particle's sets silently: the NaN appears at the next evaluation with energies.  A particle that cannot be central (mode 1, its type
+ * outside mp_filter[0]) is never flagged.
+ *
  * Tabulated functions (OpenMM's Continuous1DFunction and Discrete1DFunction) of every kind above: REMD_CX_TABLE1D and
  * REMD_CX_LOOKUP1D take one argument x from the stack and push one result; the operand is the offset of the function's block in the
  * force's constants.  The blocks follow the scalar constants, one per function:
@@ -187,6 +209,8 @@ extern "C" {
 /* kind 9 is not assigned: a descriptor that carries it is refused as an unknown kind                                              */
 #define REMD_CUSTOM_HBOND    10    /* atoms NULL, n_terms = hb_n_donors; functions of the particles d1 d2 d3 a1 a2 a3 of every donor-acceptor pair */
 
+#define REMD_CUSTOM_MANYPARTICLE 11 /* atoms NULL, n_terms = N, params [N][n_params]; functions of the particles p1 p2 p3 of every set of three */
+
 #define REMD_CUSTOM_MAX_PROGRAM 256
 #define REMD_CUSTOM_MAX_STACK   16
 #define REMD_CUSTOM_MAX_PARAMS  16
@@ -195,6 +219,7 @@ extern "C" {
 #define REMD_CUSTOM_MAX_PARTICLES 8
 #define REMD_CUSTOM_MAX_CVS   3
 #define REMD_CUSTOM_MAX_MAPS  64
+#define REMD_CUSTOM_MP_MAX_NEIGHBORS 128     /* the capacity of one particle's neighbour row of a many-particle force          */
 #define REMD_CUSTOM_MAX_TABLE_POINTS 8192   /* points of one tabulated function of one argument                               */
 #define REMD_CUSTOM_MAX_TABLE_CELLS 65536   /* nx ny (nz) of one tabulated function of two or three arguments                  */
 
@@ -293,6 +318,11 @@ typedef struct remd_custom_force_desc {
     const int32_t* hb_excl_offsets; /* [hb_n_donors + 1]: donor i is excluded from hb_excl_acceptors[hb_excl_offsets[i] ... hb_excl_offsets[i + 1]) */
     const int32_t* hb_excl_acceptors; /* acceptor indices, sorted within a row, none twice                                 */
     int32_t hb_particle_mask;      /* bit s: the program names particle slot s (d1 d2 d3 = 0 1 2, a1 a2 a3 = 3 4 5)        */
+    /* REMD_CUSTOM_MANYPARTICLE only (every other kind ignores them); it also reads nb_method, cutoff, excl_offsets and excl_atoms above */
+    const int32_t* mp_types;       /* [N]: every particle's type, 0 ... 31                                                 */
+    int32_t mp_permutation_mode;   /* 0 SinglePermutation, 1 UniqueCentralParticle                                         */
+    uint32_t mp_filter[3];         /* per slot p1 p2 p3: bit t set where a particle of type t may fill it (all ones: no filter) */
+    int32_t mp_particle_mask;      /* bit s: the program names particle slot s (p1 p2 p3 = 0 1 2)                          */
 } remd_custom_force_desc;
 
 /* the custom forces of the system; call after remd_set_system (which forgets them).  n = 0: none.  Every custom force of a handle

@@ -96,6 +96,11 @@ class RemdCustomForceDescHbond(RemdCustomForceDescCMAP):
                 ('hb_particle_mask', C.c_int32)]
 
 
+class RemdCustomForceDescManyParticle(RemdCustomForceDescHbond):
+    """the same, then the fields of REMD_CUSTOM_MANYPARTICLE behind those of REMD_CUSTOM_HBOND: the whole remd_custom_force_desc"""
+    _fields_ = [('mp_types', c_int32_p), ('mp_permutation_mode', C.c_int32), ('mp_filter', C.c_uint32 * 3), ('mp_particle_mask', C.c_int32)]
+
+
 class RemdGbModelDesc(C.Structure):
     """remd_gb_model_desc of include/remd_hip_gb.h (the constants and the cutoff of an OBC-family implicit-solvent model)."""
     _fields_ = [('offset', C.c_double), ('alpha', C.c_double), ('beta', C.c_double), ('gamma', C.c_double), ('ke', C.c_double),
@@ -238,7 +243,7 @@ def load_library(path=None):
         for name in RESTRAINT_FRAMES_EXPORTS:
             getattr(lib, name).restype = C.c_int
     if hasattr(lib, 'remd_set_custom_terms'):             # include/remd_hip_custom.h (GPU-only, like the restraints)
-        lib.remd_set_custom_terms.argtypes = [vp, C.POINTER(RemdCustomForceDescHbond), C.c_int]
+        lib.remd_set_custom_terms.argtypes = [vp, C.POINTER(RemdCustomForceDescManyParticle), C.c_int]
         lib.remd_set_custom_globals.argtypes = [vp, c_double_p]
         lib.remd_set_custom_lrc.argtypes = [vp, c_double_p]
         lib.remd_get_custom_energies.argtypes = [vp, c_double_p]
@@ -646,7 +651,8 @@ class HipEngine:
     def _custom_entry(self, name):
         if not hasattr(self.lib, name):
             raise NotImplementedError('%s: this build of the engine library has no custom bond / angle / torsion / external forces and no compound-bond forces, '
-                                      'centroid-bond forces or nonbonded custom forces, nor CMAP torsion forces (include/remd_hip_custom.h is GPU-only)' % name)
+                                      'centroid-bond forces or nonbonded custom forces, nor CMAP torsion forces, donor-acceptor forces or many-particle forces '
+                                      '(include/remd_hip_custom.h is GPU-only)' % name)
         return getattr(self.lib, name)
 
     def set_custom_terms(self, terms):
@@ -655,7 +661,7 @@ class HipEngine:
         n_cv = sum(len(t['cv_offsets']) - 1 for t in terms if 'cv_offsets' in t)
         if n_cv:
             self._custom_cv_entry('remd_get_custom_cv_values')
-        arr = (RemdCustomForceDescHbond * max(1, len(terms)))()
+        arr = (RemdCustomForceDescManyParticle * max(1, len(terms)))()
         keep = []
         for k, t in enumerate(terms):
             atoms = np.ascontiguousarray(t['atoms'], dtype=np.int32)
@@ -715,10 +721,17 @@ class HipEngine:
                          a_par.shape[1], _dp(a_par) if a_par.size else None, _ip(h_off), _ip(h_acc) if len(h_acc) else None, int(t['particle_mask']))
                 pairs = (int(t['nb_method']), float(t['cutoff']), -1.0, None, None, 0)
                 params = None
+            many = (None, 0, (C.c_uint32 * 3)(), 0)
+            if 'permutation_mode' in t:                              # a many-particle force: the nonbonded kind's shape, then its own fields
+                m_types = np.ascontiguousarray(t['types'], dtype=np.int32)
+                if len(m_types) != n_terms:
+                    raise ValueError('set_custom_terms: types must hold one type per particle (%d, not %d)' % (n_terms, len(m_types)))
+                keep.append(m_types)
+                many = (_ip(m_types), int(t['permutation_mode']), (C.c_uint32 * 3)(*[int(v) for v in t['filters']]), int(t['particle_mask']))
             no_atoms = nonbonded or 'cv_offsets' in t or 'donor_atoms' in t
-            arr[k] = RemdCustomForceDescHbond(int(t['kind']), n_terms, None if no_atoms else _ip(atoms), 0 if params is None else params.shape[1], _dp(params), len(program), _ip(program),
+            arr[k] = RemdCustomForceDescManyParticle(int(t['kind']), n_terms, None if no_atoms else _ip(atoms), 0 if params is None else params.shape[1], _dp(params), len(program), _ip(program),
                                          len(consts), _dp(consts), int(t['stack_depth']), len(defaults), _dp(defaults),
-                                         int(t['periodic']), int(t['force_group']), n_particles, *groups, *pairs, *cvs, *maps, *hbond)
+                                         int(t['periodic']), int(t['force_group']), n_particles, *groups, *pairs, *cvs, *maps, *hbond, *many)
         self._check(fn(self.h, arr, len(terms)), 'remd_set_custom_terms')
         self.n_custom = len(terms)
         self.n_custom_cvs = n_cv

@@ -99,8 +99,11 @@ class AbsoluteAlchemicalFactory:
             # _alchemically_modify_CustomNonbondedForce (alchemy.py:2347-2396) is not built
             raise NotImplementedError('AbsoluteAlchemicalFactory: a System with a CustomNonbondedForce (the alchemical modification of a '
                                       'CustomNonbondedForce is not supported)')
-        from .system import CustomHbondForce
+        from .system import CustomHbondForce, CustomManyParticleForce
         for f in reference_system.getForces():
+            if isinstance(f, CustomManyParticleForce):
+                raise NotImplementedError('AbsoluteAlchemicalFactory: a System with a CustomManyParticleForce (energy %r): the alchemical '
+                                          'modification of a CustomManyParticleForce is not supported' % f.getEnergyFunction())
             # a CustomHbondForce passes through untouched where no donor or acceptor particle is alchemical; scaling its terms is not built
             if isinstance(f, CustomHbondForce):
                 alchemical = set(int(i) for r in regions for i in r.alchemical_atoms)

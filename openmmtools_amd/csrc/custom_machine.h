@@ -1,6 +1,7 @@
 // The stack machine of the custom forces (include/remd_hip_custom.h), shared by custom_terms.hip (bond, angle, torsion, external),
 // custom_compound.hip (compound bonds), custom_centroid.hip (centroid bonds, whose particles are centroids), custom_cv.hip
-// (collective variables, whose variables are RMSDs) and custom_hbond.hip (donor-acceptor pairs, whose particles are d1 d2 d3 a1 a2 a3): the handle's tables (the per-force record and the host plan behind them live in
+// (collective variables, whose variables are RMSDs), custom_hbond.hip (donor-acceptor pairs, whose particles are d1 d2 d3 a1 a2 a3) and
+// custom_manyparticle.hip (sets of three particles p1 p2 p3): the handle's tables (the per-force record and the host plan behind them live in
 // custom_plan.h, which needs no HIP) and cst_eval, which runs a postfix program one term per lane with every stack slot a value and three partials, the stack in LDS as [slot][component][lane].
 // cmap.hip (CMAP torsion maps) runs no program: it shares the record, the tables and the patch of two arguments (table2d_patch.h).
 //
@@ -25,6 +26,7 @@ struct cst_tables : cst_plan {
     dev_array<int> d_cv_off, d_cv_atoms; dev_array<double> d_cv_ref;
     dev_array<int> d_map_off, d_map_index;
     dev_array<int> d_hb_atoms;
+    dev_array<int> d_mp_types;
     dev_array<int> d_excl_off, d_excl_atoms; dev_array<double> d_lrc;
     dev_array<int> d_mol_first, d_mol_size;
     dev_array<double> d_E;             // [R][nf]
@@ -33,6 +35,8 @@ struct cst_tables : cst_plan {
     dev_array<double> d_C;             // [R][n_groups][3] centroids
     dev_array<double> d_G;             // [R][centroid slots][REMD_CUSTOM_MAX_PARTICLES][3] dE / d centroid
     dev_array<double> d_W;             // [R][n_cv][16]: RMSD, "no force" flag, centroid, rotation, dE/dRMSD (custom_cv.hip)
+    dev_array<int> d_mp_nbr;           // [R][mp_rows][REMD_CUSTOM_MP_MAX_NEIGHBORS]: the neighbour rows of the many-particle forces (custom_manyparticle.hip)
+    dev_array<int> d_mp_cnt;           // [R][mp_rows]: their counts (which may exceed a row: the row then holds its first entries)
 };
 
 namespace {
@@ -319,6 +323,10 @@ void remd_custom_nonbonded_forces(remd_ctx* h, cst_tables& t, bool with_energy, 
 void remd_custom_nonbonded_lrc(remd_ctx* h, cst_tables& t, int ep_slot, hipStream_t st);
 void remd_custom_nonbonded_ukl(remd_ctx* h, cst_tables& t);
 void remd_custom_nonbonded_lrc_ukl(remd_ctx* h, cst_tables& t, double* d_rows);
-// custom_hbond.hip: the same for the donor-acceptor forces' tiles (the part CST_HBOND, the last one)
+// custom_hbond.hip: the same for the donor-acceptor forces' tiles (the part CST_HBOND)
 void remd_custom_hbond_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
 void remd_custom_hbond_ukl(remd_ctx* h, cst_tables& t);
+// custom_manyparticle.hip: the same for the many-particle forces' central particles (the part CST_MANYPARTICLE, the last one): the
+// neighbour rows, then the sets
+void remd_custom_manyparticle_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
+void remd_custom_manyparticle_ukl(remd_ctx* h, cst_tables& t);

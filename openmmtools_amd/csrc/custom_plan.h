@@ -8,7 +8,8 @@
 // A new kind: its REMD_CUSTOM_* value gets an entry in cst_part_of_kind, cst_width and cst_n_vars (and a cst_part of its own where it
 // has a kernel of its own), a validator beside cst_check_cmap called from cst_check_force, its share of cst_pack_force, and its
 // tables as members of cst_plan with one line in upload_tables (custom_terms.hip).  Nothing else lists the tables.  The donor-acceptor kind
-// (REMD_CUSTOM_HBOND) keeps its validator, its share of the packing and its molecules in custom_hbond_plan.h, included below.
+// (REMD_CUSTOM_HBOND) keeps its validator, its share of the packing and its molecules in custom_hbond_plan.h, included below, and the
+// many-particle kind (REMD_CUSTOM_MANYPARTICLE) its validator and packer in custom_manyparticle_plan.h.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -37,13 +38,20 @@ struct cst_force {
     int hb_atoms0;               // in the handle's hb_atoms: donors [3][ndpad], then acceptors [3][napad] (ndpad = 64 ceil(donors / 64), ...)
     int hb_npd, hb_npa;          // per-donor and per-acceptor parameters: [hb_npd][ndpad] at par0, then [hb_npa][napad]
     int hb_mask;                 // bit s: the program names particle slot s (d1 d2 d3 a1 a2 a3 = 0 ... 5); one seeded pass per bit
+    // REMD_CUSTOM_MANYPARTICLE only (custom_manyparticle.hip): n_terms = N particles, npad = 64 N (one wavefront per central particle),
+    // parameters [n_params][Npad]; it shares nb_method, cutoff and excl0 (rows [N + 1], symmetric, sorted) with the nonbonded kind
+    int mp_mode;                 // 0 SinglePermutation, 1 UniqueCentralParticle
+    int mp_types0;               // its types [Npad] in the handle's mp_types
+    int mp_row0;                 // its first neighbour row among the handle's (Npad rows per such force)
+    int mp_mask;                 // bit s: the program names particle slot s (p1 p2 p3 = 0 1 2); one seeded pass per bit
+    unsigned mp_filter[3];       // per slot: bit t set where type t may fill it
 };
 
 // The parts of the padded term space, in its order; each has its own kernels, which run the wavefronts [begin(part), end(part)).
-enum cst_part { CST_SIMPLE, CST_COMPOUND, CST_NONBONDED, CST_CENTROID, CST_CV, CST_CMAP, CST_HBOND, CST_N_PARTS };
+enum cst_part { CST_SIMPLE, CST_COMPOUND, CST_NONBONDED, CST_CENTROID, CST_CV, CST_CMAP, CST_HBOND, CST_MANYPARTICLE, CST_N_PARTS };
 // indexed by REMD_CUSTOM_*: the part of a kind (the four one-variable kinds share the first)
 // (kind 9 is not assigned and never gets this far: cst_check_shape refuses it; its entries below only keep the tables indexed by kind)
-static const int cst_part_of_kind[REMD_CUSTOM_HBOND + 1] = {CST_SIMPLE, CST_SIMPLE, CST_SIMPLE, CST_SIMPLE, CST_COMPOUND, CST_CENTROID, CST_NONBONDED, CST_CV, CST_CMAP, CST_HBOND, CST_HBOND};
+static const int cst_part_of_kind[REMD_CUSTOM_MANYPARTICLE + 1] = {CST_SIMPLE, CST_SIMPLE, CST_SIMPLE, CST_SIMPLE, CST_COMPOUND, CST_CENTROID, CST_NONBONDED, CST_CV, CST_CMAP, CST_HBOND, CST_HBOND, CST_MANYPARTICLE};
 
 // everything the set-up computes on the host; the energy columns keep the forces' order whatever their slots
 struct cst_plan {
@@ -79,8 +87,13 @@ struct cst_plan {
     // donor-acceptor forces (custom_hbond.hip): per force the donors' particles [3][ndpad], then the acceptors' [3][napad]; -1: the donor
     // (acceptor) has no such particle; a padding column repeats the last donor (acceptor).  Their exclusion rows join excl_off / excl_atoms.
     std::vector<int> hb_atoms;
+    // many-particle forces (custom_manyparticle.hip): per force the particles' types [Npad] (a padding column repeats the last atom's),
+    // and the neighbour rows of all of them (Npad per force; the rows themselves are work buffers on the device).  Their exclusion
+    // rows join excl_off / excl_atoms.
+    std::vector<int> mp_types;
+    int mp_rows = 0;
     bool has_lrc = false, lrc_valid = false;   // (lrc_valid: remd_set_custom_lrc ran since the globals were last set)
-    double periodic_cutoff = 0.0;      // the longest cutoff of a CutoffPeriodic nonbonded or donor-acceptor force (remd_ctx::cst_cutoff)
+    double periodic_cutoff = 0.0;      // the longest cutoff of a CutoffPeriodic nonbonded, donor-acceptor or many-particle force (remd_ctx::cst_cutoff)
     // the molecules a barostat moves as wholes where the handle has no NonbondedForce to take them from (remd_custom_molecules): atoms
     // the custom bonds, angles, torsions and compound bonds join, each a contiguous range [first, first + size); empty: no table
     std::vector<int> mol_first, mol_size;
@@ -97,17 +110,18 @@ inline bool cst_is_compound(int kind) { return kind == REMD_CUSTOM_COMPOUND || k
 // atoms (group numbers) per term in the descriptor's `atoms`
 inline int cst_width(const remd_custom_force_desc& d)
 {
-    static const int width[REMD_CUSTOM_HBOND + 1] = {2, 3, 4, 1, -1, -1, 0, 0, 8, 0, 0};
+    static const int width[REMD_CUSTOM_MANYPARTICLE + 1] = {2, 3, 4, 1, -1, -1, 0, 0, 8, 0, 0, 0};
     return cst_is_compound(d.kind) ? d.n_particles : width[d.kind];
 }
 // the variables a program may name
 inline int cst_n_vars(const remd_custom_force_desc& d)
 {
-    static const int n_vars[REMD_CUSTOM_HBOND + 1] = {1, 1, 1, 3, -1, -1, 1, -1, 0, 0, 0};
+    static const int n_vars[REMD_CUSTOM_MANYPARTICLE + 1] = {1, 1, 1, 3, -1, -1, 1, -1, 0, 0, 0, 0};
     return cst_is_compound(d.kind) ? 3 * d.n_particles : d.kind == REMD_CUSTOM_CV ? d.n_cvs : n_vars[d.kind];
 }
 
 #include "custom_hbond_plan.h"     // the donor-acceptor kind's validator, packer and molecules (cst_check_hbond, cst_pack_hbond, cst_hbond_molecules)
+#include "custom_manyparticle_plan.h"   // the many-particle kind's validator and packer (cst_check_manyparticle, cst_pack_manyparticle)
 
 // the block of the function at consts[arg] (include/remd_hip_custom.h): the kernels trust n, min, max and the block's extent
 inline const char* cst_check_table1d(const remd_custom_force_desc& d, int op, int arg)
@@ -158,7 +172,8 @@ inline const char* cst_check_table2d3d(const remd_custom_force_desc& d, int op, 
 inline const char* check_program(const remd_custom_force_desc& d, int n_vars)
 {
     const int n_par = d.kind == REMD_CUSTOM_NONBONDED ? 2 * d.n_params                   // (a pair: particle 1's parameters, then particle 2's)
-                    : d.kind == REMD_CUSTOM_HBOND ? d.hb_n_donor_params + d.hb_n_acceptor_params : d.n_params;   // (the donor's, then the acceptor's)
+                    : d.kind == REMD_CUSTOM_HBOND ? d.hb_n_donor_params + d.hb_n_acceptor_params                 // (the donor's, then the acceptor's)
+                    : d.kind == REMD_CUSTOM_MANYPARTICLE ? 3 * d.n_params : d.n_params;                           // (operand 3 q + s: parameter q of slot s)
     if (d.n_program <= 0 || !d.program) return "an empty program";
     if (d.n_program > REMD_CUSTOM_MAX_PROGRAM) return "a program over REMD_CUSTOM_MAX_PROGRAM instructions";
     int sp = 0, top = 0;
@@ -177,13 +192,13 @@ inline const char* check_program(const remd_custom_force_desc& d, int n_vars)
         case REMD_CX_PERIODICDISTANCE: pops = 6; break;
         case REMD_CX_DISTANCE: case REMD_CX_ANGLE: case REMD_CX_DIHEDRAL: {
             // the zero-based particle slots in 4-bit fields, first argument lowest; nothing above them
-            const bool hbond = d.kind == REMD_CUSTOM_HBOND;
-            if (!cst_is_compound(d.kind) && !hbond) return "a function of particles outside a compound-bond or centroid-bond force";
+            const bool hbond = d.kind == REMD_CUSTOM_HBOND, many = d.kind == REMD_CUSTOM_MANYPARTICLE;
+            if (!cst_is_compound(d.kind) && !hbond && !many) return "a function of particles outside a compound-bond or centroid-bond force";
             const int n_args = op - REMD_CX_DISTANCE + 2;
             if (arg < 0 || (arg >> (4 * n_args)) != 0) return "a particle slot out of range";
             for (int k = 0; k < n_args; ++k) {
                 const int slot = (arg >> (4 * k)) & 15;
-                if (slot >= (hbond ? 6 : d.n_particles)) return "a particle slot out of range";
+                if (slot >= (hbond ? 6 : many ? 3 : d.n_particles)) return "a particle slot out of range";
             }
             pops = 0;
         } break;
@@ -208,8 +223,8 @@ inline const char* check_program(const remd_custom_force_desc& d, int n_vars)
 // every kind: the kind itself, the particles per term, the terms, the per-term parameters
 inline std::string cst_check_shape(const remd_custom_force_desc& d)
 {
-    if (d.kind < 0 || d.kind > REMD_CUSTOM_HBOND || d.kind == REMD_CUSTOM_CMAP + 1) return "unknown kind";      // (9 is not assigned)
-    const bool cmap = d.kind == REMD_CUSTOM_CMAP, atomless = d.kind == REMD_CUSTOM_NONBONDED || d.kind == REMD_CUSTOM_CV || d.kind == REMD_CUSTOM_HBOND;
+    if (d.kind < 0 || d.kind > REMD_CUSTOM_MANYPARTICLE || d.kind == REMD_CUSTOM_CMAP + 1) return "unknown kind";      // (9 is not assigned)
+    const bool cmap = d.kind == REMD_CUSTOM_CMAP, atomless = d.kind == REMD_CUSTOM_NONBONDED || d.kind == REMD_CUSTOM_CV || d.kind == REMD_CUSTOM_HBOND || d.kind == REMD_CUSTOM_MANYPARTICLE;
     if (cmap && d.n_particles != 8) return "n_particles is 8 for a CMAP force (two dihedrals of four particles)";
     if (!cmap && (cst_is_compound(d.kind) ? (d.n_particles < 1 || d.n_particles > REMD_CUSTOM_MAX_PARTICLES) : d.n_particles != 0))
         return "n_particles is 1 ... REMD_CUSTOM_MAX_PARTICLES for a compound-bond or centroid-bond force and 0 for every other kind";
@@ -336,6 +351,7 @@ inline std::string cst_check_force(const remd_custom_force_desc& d, const remd_c
     if (bad.empty() && d.kind == REMD_CUSTOM_CV) bad = cst_check_cv(d, s.N);
     if (bad.empty() && d.kind == REMD_CUSTOM_CMAP) bad = cst_check_cmap(d);
     if (bad.empty() && d.kind == REMD_CUSTOM_HBOND) bad = cst_check_hbond(d, s);
+    if (bad.empty() && d.kind == REMD_CUSTOM_MANYPARTICLE) bad = cst_check_manyparticle(d, s);
     if (bad.empty()) bad = cst_check_shared(d, d0);
     if (bad.empty() && d.kind != REMD_CUSTOM_CMAP)       // (a CMAP force has no program)
         if (const char* p = check_program(d, cst_n_vars(d))) bad = p;
@@ -369,6 +385,7 @@ inline void cst_pack_force(const remd_custom_force_desc& d, const cst_facts& s, 
         if (d.excl_offsets[d.n_terms] > 0) p.excl_atoms.insert(p.excl_atoms.end(), d.excl_atoms, d.excl_atoms + d.excl_offsets[d.n_terms]);
     }
     if (d.kind == REMD_CUSTOM_HBOND) cst_pack_hbond(d, f, p);
+    if (d.kind == REMD_CUSTOM_MANYPARTICLE) { cst_pack_manyparticle(d, s, f, p); par_stride = s.Npad; }
     // parameters [n_params][npad]; a padding slot repeats the last term (finite arithmetic in lanes that add nothing)
     for (int q = 0; q < d.n_params; ++q) for (int k = 0; k < par_stride; ++k) p.par.push_back(d.params[(size_t)std::min(k, d.n_terms - 1) * d.n_params + q]);
     if (d.n_program > 0) p.prog.insert(p.prog.end(), d.program, d.program + 2 * (size_t)d.n_program);
@@ -467,7 +484,7 @@ inline void cst_fill_molecules(const remd_custom_force_desc* desc, int N, cst_pl
     for (int i = 0; i < p.nf; ++i) {
         const cst_force& f = p.F[i];
         if (f.kind == REMD_CUSTOM_HBOND) { cst_hbond_molecules(desc[i], f, find, root); continue; }
-        if (f.kind == REMD_CUSTOM_EXTERNAL || f.kind == REMD_CUSTOM_CENTROID || f.kind == REMD_CUSTOM_NONBONDED || f.kind == REMD_CUSTOM_CV) continue;
+        if (f.kind == REMD_CUSTOM_EXTERNAL || f.kind == REMD_CUSTOM_CENTROID || f.kind == REMD_CUSTOM_NONBONDED || f.kind == REMD_CUSTOM_CV || f.kind == REMD_CUSTOM_MANYPARTICLE) continue;
         for (int b = 0; b < f.n_terms; ++b) for (int a = 1; a < f.n_particles; ++a) {
             const int u = find(desc[i].atoms[(size_t)b * f.n_particles]), v = find(desc[i].atoms[(size_t)b * f.n_particles + a]);
             if (u != v) root[std::max(u, v)] = std::min(u, v);

@@ -29,7 +29,8 @@
 // CustomNonbondedForce, one wavefront per tile of 64 x 64 atoms, between those two; custom_cv.hip runs it for CustomCVForce, one
 // wavefront per force behind the centroid forces', its variables the RMSDs a launch of its own computed.  cmap.hip (CMAPTorsionForce)
 // runs no program: it shares the term space, the tables and the energy reduction only.  custom_hbond.hip runs the machine for
-// CustomHbondForce, one wavefront per tile of 64 donors x 64 acceptors; its tiles come last, so that no other kind's slot depends on them.
+// CustomHbondForce, one wavefront per tile of 64 donors x 64 acceptors, and custom_manyparticle.hip for CustomManyParticleForce, one
+// wavefront per central particle behind a neighbour search of its own; each new part comes last, so that no other kind's slot depends on it.
 #include "remd_internal.h"
 #include "listed_terms.h"
 #include "custom_machine.h"
@@ -204,6 +205,10 @@ int ensure_buffers(remd_ctx* h, cst_tables& t)
     // collective-variable forces: what the superposition hands on (n_cv = 0: nothing is allocated)
     const size_t nW = (size_t)h->R * t.n_cv * remd_custom_cv_w();
     if (t.d_W.size() != nW) REMD_TRY(t.d_W.alloc(h, nW));
+    // many-particle forces: the neighbour rows and their counts (mp_rows = 0: nothing is allocated)
+    const size_t nR = (size_t)h->R * t.mp_rows;
+    if (t.d_mp_cnt.size() != nR) REMD_TRY(t.d_mp_cnt.alloc(h, nR));
+    if (t.d_mp_nbr.size() != nR * REMD_CUSTOM_MP_MAX_NEIGHBORS) REMD_TRY(t.d_mp_nbr.alloc(h, nR * REMD_CUSTOM_MP_MAX_NEIGHBORS));
     return 0;
 }
 
@@ -222,8 +227,8 @@ int upload_tables(remd_ctx* h, cst_tables& t)
         (rc = t.d_lrc.upload(h, t.lrc)) || (rc = t.d_mol_first.upload(h, t.mol_first)) || (rc = t.d_mol_size.upload(h, t.mol_size)) ||
         (rc = t.d_cv_off.upload(h, t.cv_off)) || (rc = t.d_cv_atoms.upload(h, t.cv_atoms)) || (rc = t.d_cv_ref.upload(h, t.cv_ref)) ||
         (rc = t.d_map_off.upload(h, t.map_off)) || (rc = t.d_map_index.upload(h, t.map_index)) ||
-        (rc = t.d_hb_atoms.upload(h, t.hb_atoms))) return rc;
-    t.d_E.reset(); t.d_Ewave.reset(); t.d_D.reset(); t.d_C.reset(); t.d_G.reset(); t.d_W.reset();
+        (rc = t.d_hb_atoms.upload(h, t.hb_atoms)) || (rc = t.d_mp_types.upload(h, t.mp_types))) return rc;
+    t.d_E.reset(); t.d_Ewave.reset(); t.d_D.reset(); t.d_C.reset(); t.d_G.reset(); t.d_W.reset(); t.d_mp_nbr.reset(); t.d_mp_cnt.reset();
     return 0;
 }
 
@@ -301,6 +306,7 @@ int remd_custom_forces(remd_ctx* h, bool with_energy, int ep_slot, hipStream_t s
     if (t.has(CST_CV)) remd_custom_cv_forces(h, t, with_energy, st);
     if (t.has(CST_CMAP)) remd_cmap_forces(h, t, with_energy, st);
     if (t.has(CST_HBOND)) remd_custom_hbond_forces(h, t, with_energy, st);
+    if (t.has(CST_MANYPARTICLE)) remd_custom_manyparticle_forces(h, t, with_energy, st);
     if (with_energy)
         hipLaunchKernelGGL(custom_reduce_kernel, dim3(h->R), dim3(64), 0, st, t.nf, t.d_F, waves, t.d_Ewave, t.d_E, h->d_epart, h->n_epart, ep_slot);
     if (with_energy && t.has_lrc) remd_custom_nonbonded_lrc(h, t, ep_slot, st);
@@ -332,6 +338,7 @@ int remd_custom_ukl(remd_ctx* h, double* d_rows)
     if (t.has(CST_CENTROID)) remd_custom_centroid_ukl(h, t);
     if (t.has(CST_CV)) remd_custom_cv_ukl(h, t);
     if (t.has(CST_HBOND)) remd_custom_hbond_ukl(h, t);
+    if (t.has(CST_MANYPARTICLE)) { REMD_TRY(ensure_buffers(h, t)); remd_custom_manyparticle_ukl(h, t); }
     hipLaunchKernelGGL(custom_ukl_reduce_kernel, dim3(h->K, h->R), dim3(64), 0, h->stream, h->K, waves, t.d_D, h->d_beta, d_rows);
     if (t.has_lrc) remd_custom_nonbonded_lrc_ukl(h, t, d_rows);
     REMD_CHECK(h, hipGetLastError());

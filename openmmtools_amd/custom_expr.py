@@ -22,6 +22,10 @@ d1 d2 d3 (particle slots 0 1 2) and a1 a2 a3 (slots 3 4 5), no coordinates, no p
 PARAM operands, the per-acceptor ones follow; the set of particle slots the expression names is recorded as a 6-bit mask
 (particle_mask): the engine runs one seeded pass per named slot (csrc/custom_hbond.hip).
 
+A many-particle force (system.CustomManyParticleForce, three particles per set) compiles the same way over the names p1 p2 p3
+(particle slots 0 1 2); per-particle parameter q is legal with the slot appended only (sigma1, sigma2, sigma3) and is PARAM operand
+3 q + s for slot s; the 3-bit particle_mask is recorded likewise (csrc/custom_manyparticle.hip).
+
 Grammar: numbers (exponent notation included), ``+ - * / ^``, unary minus, parentheses, function calls, and ``;``-separated
 definitions ``name = expr`` in any order, substituted where they are used.  ``^`` binds tighter than unary minus and groups to the
 right, as in OpenMM's Lepton.  A constant integer exponent up to +-64 becomes REMD_CX_POWI (multiplications: defined for a negative
@@ -55,9 +59,14 @@ KIND_CMAP = 8                                   # system.CMAPTorsionForce: no ex
 MAX_MAPS = 64                                   # maps per CMAPTorsionForce
 KIND_HBOND = 10                                 # system.CustomHbondForce: donor-acceptor pairs (csrc/custom_hbond.hip)
 HBOND_SLOTS = dict(d1=0, d2=1, d3=2, a1=3, a2=4, a3=5)   # the particle names of a donor-acceptor expression -> particle slot
+KIND_MANYPARTICLE = 11                          # system.CustomManyParticleForce: sets of three particles (csrc/custom_manyparticle.hip)
+MANYPARTICLE_SLOTS = dict(p1=0, p2=1, p3=2)     # the particle names of a many-particle expression -> particle slot
+MAX_SET_PARAMS = 5                              # per-particle parameters of a many-particle force: 3 x 5 of the machine's 16 columns
+MP_MAX_NEIGHBORS = 128                          # REMD_CUSTOM_MP_MAX_NEIGHBORS: the capacity of one particle's neighbour row
 KIND_OF_CLASS = {'CustomNonbondedForce': KIND_NONBONDED, 'CustomBondForce': KIND_BOND, 'CustomAngleForce': KIND_ANGLE, 'CustomTorsionForce': KIND_TORSION,
                  'CustomExternalForce': KIND_EXTERNAL, 'CustomCompoundBondForce': KIND_COMPOUND, 'CustomCentroidBondForce': KIND_CENTROID,
-                 'CustomCVForce': KIND_CV, 'CMAPTorsionForce': KIND_CMAP, 'CustomHbondForce': KIND_HBOND}
+                 'CustomCVForce': KIND_CV, 'CMAPTorsionForce': KIND_CMAP, 'CustomHbondForce': KIND_HBOND,
+                 'CustomManyParticleForce': KIND_MANYPARTICLE}
 VARIABLES = {KIND_BOND: ('r',), KIND_ANGLE: ('theta',), KIND_TORSION: ('theta',), KIND_EXTERNAL: ('x', 'y', 'z'), KIND_NONBONDED: ('r',)}
 
 
@@ -364,7 +373,7 @@ def _table_block(name, function, where):
 
 
 def compile_expression(energy, variables, parameters, global_columns, where='expression', tabulated=(), periodic_distance=False,
-                       n_particles=0, particle_prefix='p', pair_parameters=(), particle_slots=None):
+                       n_particles=0, particle_prefix='p', pair_parameters=(), particle_slots=None, set_parameters=None):
     """The postfix program of ``energy``.
 
     variables: the force's own variable names in operand order; parameters: the per-term parameter names in order; global_columns:
@@ -377,7 +386,9 @@ def compile_expression(energy, variables, parameters, global_columns, where='exp
     particle_prefix: 'p', or 'g' for the groups g1 ... gP of a centroid-bond force (the messages then speak of groups);
     pair_parameters: the per-particle parameter names of a nonbonded force, in order: name p is legal as p1 (PARAM operand k) and p2
     (operand len(pair_parameters) + k) only; particle_slots: {particle name: slot} of a donor-acceptor force (HBOND_SLOTS), which opens
-    distance / angle / dihedral over exactly those names and nothing else of the compound-bond forces.
+    distance / angle / dihedral over exactly those names and nothing else of the compound-bond forces; set_parameters: the bare
+    per-particle parameter names of a many-particle force (None: another force; whose suffixed forms are in ``parameters``): named bare,
+    they are refused by name, and so are the raw coordinates x1 y1 z1 ...
 
     Returns dict(program int32 [n][2], consts float64 [m], stack_depth), and particle_mask (bit s: slot s is named) with particle_slots.
     """
@@ -438,6 +449,10 @@ def compile_expression(energy, variables, parameters, global_columns, where='exp
                     raise NotImplementedError('%s: variable %r (the only variable of a nonbonded force is r)' % (where, name))
             if particle_slots is not None and name in particle_slots:
                 raise NotImplementedError('%s: particle name %r outside distance(), angle() and dihedral()' % (where, name))
+            if set_parameters is not None and re.fullmatch(r'[xyz][0-9]+', name):
+                raise NotImplementedError('%s: variable %r (raw coordinates are not variables of this force: use distance(), angle() and dihedral())' % (where, name))
+            if set_parameters is not None and name in set_parameters:
+                raise NotImplementedError('%s: per-particle parameter %r without a particle suffix (%s1, %s2 or %s3)' % (where, name, name, name, name))
             if n_particles and _PARTICLE_NAME.fullmatch(name):
                 raise NotImplementedError('%s: %s name %r outside distance(), angle() and dihedral()' % (where, noun, name))
             if n_particles and _PARTICLE_NAMES[other][0].fullmatch(name):
@@ -551,7 +566,8 @@ def is_custom_term_force(force):
     from . import system as _system
     from . import forces as _forces
     if isinstance(force, (_system.CustomCompoundBondForce, _system.CustomCentroidBondForce, _system.CustomNonbondedForce,
-                          _system.CustomCVForce, _system.RMSDForce, _system.CMAPTorsionForce, _system.CustomHbondForce)):
+                          _system.CustomCVForce, _system.RMSDForce, _system.CMAPTorsionForce, _system.CustomHbondForce,
+                          _system.CustomManyParticleForce)):
         return True
     if isinstance(force, _system.CustomExternalForce):
         return not force.is_harmonic_oscillator()
@@ -1021,6 +1037,9 @@ def custom_terms_desc(forces, masses=None, box_vectors=None):
             if entry is not None:
                 out['%03d' % len(out)] = entry
             continue
+        if kind == KIND_MANYPARTICLE:
+            out['%03d' % len(out)] = _manyparticle_entry(f, cls, where, names, defaults, columns, masses, box_vectors)
+            continue
         per_term = _per_term_names(f)
         if kind == KIND_NONBONDED and len(per_term) > MAX_PAIR_PARAMS:
             raise NotImplementedError('%s: %d per-particle parameters (the engine takes %d): %s' % (cls, len(per_term), MAX_PAIR_PARAMS, ', '.join(per_term)))
@@ -1209,6 +1228,83 @@ def _hbond_entry(f, cls, where, names, defaults, columns, masses, box_vectors):
                 energy=f.getEnergyFunction(), nb_method=method, cutoff=cutoff, donor_atoms=d_atoms, acceptor_atoms=a_atoms,
                 donor_params=d_params, acceptor_params=a_params, hb_excl_offsets=offsets, hb_excl_acceptors=excluded,
                 particle_mask=int(mask))
+
+
+def manyparticle_exclusions(force, n):
+    """The exclusions of a many-particle force in CSR form: (excl_offsets int32 [n + 1], excl_atoms int32), symmetric, each row sorted."""
+    rows = [set() for _ in range(n)]
+    for k in range(force.getNumExclusions()):
+        i, j = force.getExclusionParticles(k)
+        if not (0 <= i < n and 0 <= j < n):
+            raise ValueError('CustomManyParticleForce: exclusion %d names particle %d (the force has %d)' % (k, i if not 0 <= i < n else j, n))
+        if i == j:
+            raise ValueError('CustomManyParticleForce: exclusion %d excludes particle %d from itself' % (k, i))
+        if j in rows[i]:
+            raise ValueError('CustomManyParticleForce: particles %d and %d are excluded twice' % (i, j))
+        rows[i].add(j); rows[j].add(i)
+    offsets = np.zeros(n + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum([len(r) for r in rows])
+    return offsets, np.array([j for r in rows for j in sorted(r)], dtype=np.int32)
+
+
+def _manyparticle_entry(f, cls, where, names, defaults, columns, masses, box_vectors):
+    """the entry of a many-particle force: atoms is empty ([0][0]; the terms are the particles, n_terms = N), params [N][n_params],
+    nb_method, cutoff, excl_offsets / excl_atoms, permutation_mode, types [N], filters [3] (bit t: type t may fill the slot; all
+    ones: no filter) and particle_mask beside the common keys"""
+    if int(f.getNumParticlesPerSet()) != 3:
+        raise NotImplementedError('%s: sets of %d particles (sets of 3 particles are supported)' % (cls, int(f.getNumParticlesPerSet())))
+    per_particle = [f.getPerParticleParameterName(i) for i in range(f.getNumPerParticleParameters())]
+    if len(per_particle) > MAX_SET_PARAMS:
+        raise NotImplementedError('%s: %d per-particle parameters (the engine takes %d: three columns each of its %d): %s'
+                                  % (cls, len(per_particle), MAX_SET_PARAMS, MAX_PARAMS, ', '.join(per_particle)))
+    n = f.getNumParticles()
+    if masses is not None and n != len(masses):
+        raise ValueError('%s has %d particles, the System has %d' % (cls, n, len(masses)))
+    if n == 0:
+        raise ValueError('%s has no particles' % cls)
+    tabulated = [(f.getTabulatedFunctionName(i), f.getTabulatedFunction(i)) for i in range(f.getNumTabulatedFunctions())]
+    own = {g: columns[g] for g in (f.getGlobalParameterName(i) for i in range(f.getNumGlobalParameters()))}
+    operands = ['%s%d' % (q, s + 1) for q in per_particle for s in range(3)]          # operand 3 q + s: parameter q of slot s
+    prog = compile_expression(f.getEnergyFunction(), (), operands, own, where=where, tabulated=tabulated, particle_slots=MANYPARTICLE_SLOTS,
+                              set_parameters=tuple(per_particle))
+    params, types = np.empty((n, len(per_particle)), dtype=np.float64), np.empty(n, dtype=np.int32)
+    for k in range(n):
+        values, t = f.getParticleParameters(k)
+        if len(values) != len(per_particle):
+            raise ValueError('%s: particle %d carries %d parameters, the force declares %d' % (cls, k, len(values), len(per_particle)))
+        if not 0 <= int(t) <= 31:
+            raise ValueError('%s: particle %d has type %d (the types are 0 ... 31)' % (cls, k, int(t)))
+        params[k], types[k] = values, int(t)
+    filters = np.full(3, 0xFFFFFFFF, dtype=np.uint32)
+    for s in range(3):
+        allowed = list(f.getTypeFilter(s))
+        for t in allowed:
+            if not 0 <= int(t) <= 31:
+                raise ValueError('%s: type filter %d names type %d (the types are 0 ... 31)' % (cls, s, int(t)))
+        if allowed:
+            filters[s] = sum(1 << int(t) for t in set(allowed))
+    method = int(f.getNonbondedMethod())
+    cutoff = float(f.getCutoffDistance()) if method else 0.0
+    if method and not cutoff > 0.0:
+        raise ValueError('%s: cutoff distance %r' % (cls, cutoff))
+    if method == 0 and n > MP_MAX_NEIGHBORS + 1:
+        raise NotImplementedError('%s: NoCutoff with %d particles (a neighbour row holds %d particles, so NoCutoff takes at most %d: use a cutoff)'
+                                  % (cls, n, MP_MAX_NEIGHBORS, MP_MAX_NEIGHBORS + 1))
+    if method == 2:
+        if box_vectors is None:
+            raise ValueError('%s: CutoffPeriodic needs the periodic box vectors of the System' % cls)
+        box = np.asarray(box_vectors, dtype=np.float64).reshape(3, 3)
+        if np.any(box != np.diag(np.diag(box))):
+            raise NotImplementedError('%s: triclinic boxes are not supported (CutoffPeriodic takes a rectangular box)' % cls)
+        if cutoff > 0.5 * np.diag(box).min():
+            raise ValueError('%s: the cutoff %r nm exceeds half the smallest box edge (%r nm)' % (cls, cutoff, float(np.diag(box).min())))
+    offsets, atoms = manyparticle_exclusions(f, n)
+    return dict(kind=KIND_MANYPARTICLE, atoms=np.zeros((0, 0), dtype=np.int32), params=params, global_names=list(names),
+                global_defaults=np.array(defaults, dtype=np.float64), program=prog['program'], consts=prog['consts'],
+                stack_depth=prog['stack_depth'], periodic=int(method == 2), force_group=int(f.getForceGroup()),
+                energy=f.getEnergyFunction(), nb_method=method, cutoff=cutoff, switch_distance=-1.0, excl_offsets=offsets, excl_atoms=atoms,
+                long_range_correction=0, permutation_mode=int(f.getPermutationMode()), types=types, filters=filters,
+                particle_mask=int(prog['particle_mask']))
 
 
 def check_hbond_molecules(desc, terms):

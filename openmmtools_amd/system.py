@@ -996,6 +996,122 @@ class CustomHbondForce(_CustomForce):
                                   'supported: build the System again')
 
 
+class CustomManyParticleForce(_CustomForce):
+    """openmm.CustomManyParticleForce with three particles per set: the energy an expression of distance(), angle() and dihedral()
+    among p1 p2 p3, of per-particle parameters (a parameter sigma appears as sigma1, sigma2 and sigma3, the slot appended), of global
+    parameters and of tabulated functions, summed over sets of three distinct particles none of whose pairs is excluded.
+    SinglePermutation: every unordered set once, with a cutoff all three distances below it.  UniqueCentralParticle: every set once per
+    choice of its central particle p1, the other two unordered, with a cutoff only the two distances to p1 below it.  A type filter on
+    slot s admits a set only under an assignment that puts a particle of an allowed type into slot s; where several assignments pass,
+    OpenMM leaves the choice open: here it is the first in lexicographic order of the atom indices (p1, p2, p3) -- over six
+    assignments in SinglePermutation, over the two with p1 fixed in UniqueCentralParticle.  Every expression goes to
+    csrc/custom_manyparticle.hip (a neighbour row of at most 128 entries per particle, then one wavefront per central particle).
+    Sets of another size, raw coordinates and pointdistance / pointangle / pointdihedral are refused."""
+    NoCutoff, CutoffNonPeriodic, CutoffPeriodic = 0, 1, 2
+    SinglePermutation, UniqueCentralParticle = 0, 1
+
+    def __init__(self, particlesPerSet, energy):
+        super().__init__(energy)
+        if int(particlesPerSet) != 3:
+            raise NotImplementedError('CustomManyParticleForce: sets of %d particles (sets of 3 particles are supported)' % int(particlesPerSet))
+        self._per_set = 3
+        self._particles = []                  # (parameters, type)
+        self._exclusions = []                 # (i, j)
+        self._method = CustomManyParticleForce.NoCutoff
+        self._cutoff = 1.0
+        self._mode = CustomManyParticleForce.SinglePermutation
+        self._filters = {}                    # slot -> sorted types
+
+    addPerParticleParameter = _CustomForce.addPerBondParameter
+    getNumPerParticleParameters = _CustomForce.getNumPerBondParameters
+    getPerParticleParameterName = _CustomForce.getPerBondParameterName
+
+    def getNumParticlesPerSet(self):
+        return self._per_set
+
+    @staticmethod
+    def _particle(parameters, type):
+        if not 0 <= int(type) <= 31:
+            raise ValueError('CustomManyParticleForce: particle type %d (the types are 0 ... 31)' % int(type))
+        return ([float(p) for p in parameters], int(type))
+
+    def addParticle(self, parameters=(), type=0):
+        self._particles.append(self._particle(parameters, type))
+        return len(self._particles) - 1
+
+    def getNumParticles(self):
+        return len(self._particles)
+
+    def getParticleParameters(self, index):
+        parameters, type = self._particles[index]
+        return list(parameters), type
+
+    def setParticleParameters(self, index, parameters=(), type=0):
+        self._particles[index] = self._particle(parameters, type)
+
+    def addExclusion(self, particle1, particle2):
+        self._exclusions.append((int(particle1), int(particle2)))
+        return len(self._exclusions) - 1
+
+    def getNumExclusions(self):
+        return len(self._exclusions)
+
+    def getExclusionParticles(self, index):
+        return self._exclusions[index]
+
+    def setExclusionParticles(self, index, particle1, particle2):
+        self._exclusions[index] = (int(particle1), int(particle2))
+
+    createExclusionsFromBonds = CustomNonbondedForce.createExclusionsFromBonds
+
+    def setNonbondedMethod(self, method):
+        if int(method) not in (0, 1, 2):
+            raise ValueError('CustomManyParticleForce: nonbonded method %r (NoCutoff, CutoffNonPeriodic or CutoffPeriodic)' % (method,))
+        self._method = int(method)
+
+    def getNonbondedMethod(self):
+        return self._method
+
+    def setCutoffDistance(self, distance):
+        self._cutoff = float(distance)
+
+    def getCutoffDistance(self):
+        return self._cutoff
+
+    def setPermutationMode(self, mode):
+        if int(mode) not in (0, 1):
+            raise ValueError('CustomManyParticleForce: permutation mode %r (SinglePermutation or UniqueCentralParticle)' % (mode,))
+        self._mode = int(mode)
+
+    def getPermutationMode(self):
+        return self._mode
+
+    def setTypeFilter(self, index, types):
+        if not 0 <= int(index) <= 2:
+            raise ValueError('CustomManyParticleForce: type filter index %d (the particles of a set are 0 ... 2)' % int(index))
+        types = sorted({int(t) for t in types})
+        for t in types:
+            if not 0 <= t <= 31:
+                raise ValueError('CustomManyParticleForce: type filter %d names type %d (the types are 0 ... 31)' % (int(index), t))
+        self._filters[int(index)] = types
+
+    def getTypeFilter(self, index):
+        """the allowed types of slot ``index``; an empty list: no filter (OpenMM's convention)"""
+        if not 0 <= int(index) <= 2:
+            raise ValueError('CustomManyParticleForce: type filter index %d (the particles of a set are 0 ... 2)' % int(index))
+        return list(self._filters.get(int(index), ()))
+
+    def usesPeriodicBoundaryConditions(self):
+        return self._method == CustomManyParticleForce.CutoffPeriodic
+
+    def setUsesPeriodicBoundaryConditions(self, periodic):
+        raise ValueError('CustomManyParticleForce: periodic boundary conditions follow the nonbonded method (setNonbondedMethod(CutoffPeriodic))')
+
+    def updateParametersInContext(self, context=None):
+        raise NotImplementedError('CustomManyParticleForce: changing particles, exclusions or filters after set_system (updateParametersInContext) is '
+                                  'not supported: build the System again')
+
+
 class GBSAOBCForce(Force):
     """openmm.GBSAOBCForce: OBC2 Born radii + ACE surface term (the form the reference's alchemical factory spells out, alchemy.py:2144-2225).
     NoCutoff only."""
@@ -1713,6 +1829,52 @@ def virtual_site_from_openmm(site):
                               'OutOfPlaneSite are)' % name)
 
 
+def _functions_from_openmm(f, g, cls_name):
+    """the tabulated functions of ``f`` added to ``g``: taken over as they are when they are this module's classes, rebuilt from
+    getFunctionParameters() by class name otherwise"""
+    functions = dict(Continuous1DFunction=Continuous1DFunction, Discrete1DFunction=Discrete1DFunction, Continuous2DFunction=Continuous2DFunction,
+                     Discrete2DFunction=Discrete2DFunction, Discrete3DFunction=Discrete3DFunction)
+    for i in range(f.getNumTabulatedFunctions()):
+        fn, name = f.getTabulatedFunction(i), f.getTabulatedFunctionName(i)
+        cls = type(fn).__name__
+        if cls not in functions:
+            raise NotImplementedError('%s: tabulated function %r is a %s (Continuous1DFunction, Discrete1DFunction, '
+                                      'Continuous2DFunction, Discrete2DFunction and Discrete3DFunction are supported)' % (cls_name, name, cls))
+        if not isinstance(fn, tuple(functions.values())):
+            args = list(fn.getFunctionParameters())
+            fn = functions[cls](*args, **(dict(periodic=bool(fn.getPeriodic())) if hasattr(fn, 'getPeriodic') else {}))
+        g.addTabulatedFunction(name, fn)
+
+
+def manyparticle_force_from_openmm(f):
+    """An openmm.CustomManyParticleForce as the class of the same name here; by the object's getters, so that no OpenMM is needed.
+    The cutoff may carry a unit (anything with value_in_unit_system) or be a number in nm; an empty type filter means none."""
+    g = CustomManyParticleForce(f.getNumParticlesPerSet(), f.getEnergyFunction())
+    for i in range(f.getNumPerParticleParameters()):
+        g.addPerParticleParameter(f.getPerParticleParameterName(i))
+    for i in range(f.getNumGlobalParameters()):
+        g.addGlobalParameter(f.getGlobalParameterName(i), f.getGlobalParameterDefaultValue(i))
+    _functions_from_openmm(f, g, 'CustomManyParticleForce')
+    for i in range(f.getNumParticles()):
+        parameters, type = f.getParticleParameters(i)
+        g.addParticle(parameters, type)
+    for i in range(f.getNumExclusions()):
+        g.addExclusion(*f.getExclusionParticles(i))
+    g.setNonbondedMethod(int(f.getNonbondedMethod()))
+    cutoff = f.getCutoffDistance()
+    if hasattr(cutoff, 'value_in_unit_system'):
+        from .unit import to_md
+        cutoff = to_md(cutoff)
+    g.setCutoffDistance(cutoff)
+    g.setPermutationMode(int(f.getPermutationMode()))
+    for s in range(3):
+        types = list(f.getTypeFilter(s))
+        if types:
+            g.setTypeFilter(s, types)
+    g.setForceGroup(int(f.getForceGroup()))
+    return g
+
+
 def hbond_force_from_openmm(f):
     """An openmm.CustomHbondForce as the class of the same name here; by the object's getters, so that no OpenMM is needed.  The cutoff
     may carry a unit (anything with value_in_unit) or be a number in nm; functions are taken over as they are when they are this
@@ -1724,18 +1886,7 @@ def hbond_force_from_openmm(f):
         g.addPerAcceptorParameter(f.getPerAcceptorParameterName(i))
     for i in range(f.getNumGlobalParameters()):
         g.addGlobalParameter(f.getGlobalParameterName(i), f.getGlobalParameterDefaultValue(i))
-    functions = dict(Continuous1DFunction=Continuous1DFunction, Discrete1DFunction=Discrete1DFunction, Continuous2DFunction=Continuous2DFunction,
-                     Discrete2DFunction=Discrete2DFunction, Discrete3DFunction=Discrete3DFunction)
-    for i in range(f.getNumTabulatedFunctions()):
-        fn, name = f.getTabulatedFunction(i), f.getTabulatedFunctionName(i)
-        cls = type(fn).__name__
-        if cls not in functions:
-            raise NotImplementedError('CustomHbondForce: tabulated function %r is a %s (Continuous1DFunction, Discrete1DFunction, '
-                                      'Continuous2DFunction, Discrete2DFunction and Discrete3DFunction are supported)' % (name, cls))
-        if not isinstance(fn, tuple(functions.values())):
-            args = list(fn.getFunctionParameters())
-            fn = functions[cls](*args, **(dict(periodic=bool(fn.getPeriodic())) if hasattr(fn, 'getPeriodic') else {}))
-        g.addTabulatedFunction(name, fn)
+    _functions_from_openmm(f, g, 'CustomHbondForce')
     for i in range(f.getNumDonors()):
         d1, d2, d3, parameters = f.getDonorParameters(i)
         g.addDonor(d1, d2, d3, parameters)
@@ -1815,6 +1966,8 @@ def from_openmm(omm_system):
             g.setForceGroup(f.getForceGroup())
         elif type(f).__name__ == 'CustomHbondForce':
             g = hbond_force_from_openmm(f)
+        elif type(f).__name__ == 'CustomManyParticleForce':
+            g = manyparticle_force_from_openmm(f)
         else:
             raise NotImplementedError('unsupported OpenMM force %s' % type(f).__name__)
         s.addForce(g)

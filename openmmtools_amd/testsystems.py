@@ -218,6 +218,52 @@ class WCAFluid(TestSystem):
         self.ndof = 3 * nparticles
 
 
+class StillingerWeberFluid(TestSystem):
+    """A Stillinger-Weber fluid on a simple cubic lattice at liquid density.  NOT one of the reference's test systems: it exists to
+    exercise CustomManyParticleForce.  model='mW' is monatomic water (Molinero and Moore, J. Phys. Chem. B 113, 4008 (2009)): epsilon
+    = 6.189 kcal/mol, sigma = 0.23925 nm, A = 7.049556277, B = 0.6022245584, p = 4, q = 0, gamma = 1.2, a = 1.8, lambda = 23.15,
+    cos(theta0) = -1/3, one particle of 18.015 amu per molecule at 33.4 molecules per nm^3.  The two-body term
+    A eps (B (sigma/r)^p - (sigma/r)^q) exp(sigma / (r - a sigma)) is a CustomNonbondedForce and the three-body term
+    lambda eps (cos theta_jik - cos theta0)^2 exp(gamma sigma / (r_ij - a sigma)) exp(gamma sigma / (r_ik - a sigma)) a
+    CustomManyParticleForce in UniqueCentralParticle mode, both CutoffPeriodic with the cutoff a sigma (where every term vanishes with
+    all its derivatives).  nparticles must be a cube (64, 512, 4096, ...)."""
+    MODELS = dict(mW=dict(epsilon=6.189 * 4.184, sigma=0.23925, A=7.049556277, B=0.6022245584, p=4, q=0, gamma=1.2, a=1.8, lam=23.15,
+                          cos0=-1.0 / 3.0, mass=18.015, density=33.4))
+
+    def __init__(self, nparticles=512, model='mW', **kwargs):
+        super().__init__(**kwargs)
+        from .system import CustomManyParticleForce
+        if model not in self.MODELS:
+            raise ValueError('StillingerWeberFluid: model %r (the models are %s)' % (model, ', '.join(self.MODELS)))
+        m = self.MODELS[model]
+        n = int(round(nparticles ** (1.0 / 3.0)))
+        if n ** 3 != nparticles:
+            raise ValueError('StillingerWeberFluid: nparticles must be a cube, not %d' % nparticles)
+        length = float(np.float32((nparticles / m['density']) ** (1.0 / 3.0)))
+        cutoff = m['a'] * m['sigma']
+        system = System()
+        system.setDefaultPeriodicBoxVectors([length, 0, 0], [0, length, 0], [0, 0, length])
+        for _ in range(nparticles):
+            system.addParticle(m['mass'])
+        constants = 'A=%r; B=%r; eps=%r; sigma=%r; a=%r; gamma=%r; lam=%r; cos0=%r' % (m['A'], m['B'], m['epsilon'], m['sigma'], m['a'], m['gamma'],
+                                                                                       m['lam'], m['cos0'])
+        two = CustomNonbondedForce('A*eps*(B*(sigma/r)^%d-(sigma/r)^%d)*exp(sigma/(r-a*sigma)); %s' % (m['p'], m['q'], constants))
+        three = CustomManyParticleForce(3, 'lam*eps*(cos(angle(p2,p1,p3))-cos0)^2*exp(gamma*sigma/(distance(p1,p2)-a*sigma))'
+                                           '*exp(gamma*sigma/(distance(p1,p3)-a*sigma)); %s' % constants)
+        three.setPermutationMode(CustomManyParticleForce.UniqueCentralParticle)
+        for _ in range(nparticles):
+            two.addParticle([])
+            three.addParticle([], 0)
+        for f in (two, three):
+            f.setNonbondedMethod(f.CutoffPeriodic)
+            f.setCutoffDistance(cutoff)
+            system.addForce(f)
+        self.system = system
+        grid = (np.arange(n) + 0.5) * (length / n)
+        self.positions = np.array([[x, y, z] for x in grid for y in grid for z in grid], dtype=np.float64)
+        self.ndof = 3 * nparticles
+
+
 class DoubleWellDimer_WCAFluid(WCAFluid):
     """testsystems.py:2393-2533: ``ndimers`` pairs (2k, 2k + 1) of the WCA fluid joined by the double-well CustomBondForce
     h (1 - ((r - r0 - w) / w)^2)^2.  The reference puts that force in force group 1; here it stays in group 0 beside the WCA force,

@@ -66,6 +66,15 @@ def main():
         s.create(states.ThermodynamicState(wca.system, 120.0 * unit.kelvin), [ss], storage=None, min_temperature=120.0 * unit.kelvin,
                  max_temperature=240.0 * unit.kelvin, n_temperatures=24)
         run('wca: WCAFluid(216), 24 temperatures 120 - 240 K, BAOAB 2 fs x 500', s, 5)
+    if 'mw' in which:
+        # monatomic water: a CustomNonbondedForce and a CustomManyParticleForce (custom_expr.py kind 11, csrc/custom_manyparticle.hip) are
+        # the only forces: 24-replica parallel tempering of testsystems.StillingerWeberFluid (512 particles)
+        mw = testsystems.StillingerWeberFluid(nparticles=512)
+        s = ParallelTemperingSampler(mcmc_moves=move(5.0, 'V R O R V'), number_of_iterations=10 ** 9, engine=HipEngine(), seed=1)
+        ss = states.SamplerState(mw.positions, box_vectors=mw.system.getDefaultPeriodicBoxVectors())
+        s.create(states.ThermodynamicState(mw.system, 250.0 * unit.kelvin), [ss], storage=None, min_temperature=250.0 * unit.kelvin,
+                 max_temperature=320.0 * unit.kelvin, n_temperatures=24)
+        run('mw: StillingerWeberFluid(512, mW), 24 temperatures 250 - 320 K, BAOAB 5 fs x 500', s, 5)
     if '4rs' in which:
         # config 4's share with a receptor-ligand restraint (forces.py, csrc/restraints.hip): a HarmonicRestraintForce between the CB7
         # heavy atoms and the B2 guest, K = 0.2 kcal/mol/A^2, lambda_restraints rising 0 -> 1 along the coupled half and 1 where the

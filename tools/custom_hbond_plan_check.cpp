@@ -63,7 +63,8 @@ int main(int argc, char** argv)
         printf("PLAN\n");
         printf("scalars 4 %d %d %d %d\n", p.nf, p.ng, p.K, p.total_pad);
         printf("periodic_cutoff 1 %a\n", p.periodic_cutoff);
-        printf("part_end %d", (int)CST_N_PARTS); for (int k = 0; k < CST_N_PARTS; ++k) printf(" %d", p.end(k)); printf("\n");
+        // (the parts up to the donor-acceptor one; the many-particle part behind it has tools/custom_manyparticle_plan_check.cpp)
+        printf("part_end %d", (int)CST_HBOND + 1); for (int k = 0; k <= CST_HBOND; ++k) printf(" %d", p.end(k)); printf("\n");
         for (const cst_force& f : p.F)
             printf("force 15 %d %d %d %d %d %d %d %d %d %d %d %d %d %d %a\n", f.kind, f.periodic, f.n_terms, f.n_params, f.n_particles, f.slot0, f.npad,
                    f.par0, f.nb_method, f.excl0, f.hb_na, f.hb_atoms0, f.hb_npd * 100 + f.hb_npa, f.hb_mask, f.cutoff);
