@@ -1,6 +1,6 @@
 /*
  * remd_hip_custom.h — GPU-only extension of the C ABI in remd_hip.h: custom bond, angle, torsion, external, compound-bond,
- * centroid-bond, nonbonded, collective-variable, donor-acceptor (hydrogen-bond) and many-particle (three-body) forces, and CMAP
+ * centroid-bond, nonbonded, collective-variable, donor-acceptor (hydrogen-bond), many-particle (three-body) and Generalized-Born forces, and CMAP
  * torsion maps.
  *
  * OpenMM's CustomBondForce, CustomAngleForce, CustomTorsionForce and CustomExternalForce: an energy expression of r (bond), theta
@@ -117,6 +117,31 @@
  * particle's sets silently: the NaN appears at the next evaluation with energies.  A particle that cannot be central (mode 1, its type
  * outside mp_filter[0]) is never flagged.
  *
+ * Generalized-Born forces (REMD_CUSTOM_GB, OpenMM's CustomGBForce by its definition): up to REMD_CUSTOM_GB_MAX_VALUES computed values
+ * per particle and up to REMD_CUSTOM_GB_MAX_TERMS energy terms.  Value 0 is a pair sum, V_0,i = sum over j != i of f(r_ij; i, j) (with
+ * a cutoff only r < cutoff counts; excluded j are left out where the stage says so); every later value is an expression of the
+ * particle's earlier values and parameters.  An energy term is a sum over particles of an expression of the particle's values and
+ * parameters, or a sum over unordered pairs (particle 1 the lower index) of an expression of r and of both particles' values and
+ * parameters.  n_terms = N, atoms NULL, n_particles = 0, params [N][n_params], nb_method / cutoff / periodic / excl_offsets / excl_atoms
+ * as for REMD_CUSTOM_NONBONDED (symmetric rows).  The force carries no globals of its own: the host folds them into the constants.
+ * program holds the programs of all stages back to back and consts their constants; gb_stages is the stage table, gb_n_stages rows of
+ * REMD_CUSTOM_GB_STAGE_INTS int32:
+ *     [0] type: 0 pair value, 1 single-particle value, 2 single-particle energy term, 3 pair energy term
+ *     [1] 1: excluded pairs are left out (pair types)            [2] the value (types 0, 1) or energy term (2, 3) the stage belongs to
+ *     [3] pass: an energy term whose expression names more than three differentiated quantities has one stage per pass; its energy
+ *         counts in pass 0 only                                  [4] [5] its program: first instruction, instruction count
+ *     [6] the stack depth of that program                        [7 ... 9] the quantity that REMD_CX_VAR 0, 1, 2 is; -1: not used
+ *     [10] staged columns, 0 ... REMD_CUSTOM_MAX_PARAMS          [11 ... 26] the quantity that REMD_CX_PARAM c is     [27] 0
+ * A quantity: 0 = r (pair types); 1 + 2 k + s = value k of particle s; 16 + 2 q + s = parameter q of particle s; s = 0 particle 1 (the
+ * particle itself in a single-particle stage, where s = 0 always), 1 particle 2.  The machine differentiates with respect to its three
+ * variables, so the quantities to be differentiated (r and the values) are the variables of some pass and staged columns of the
+ * others.  Stage 0 is the pair value (variable 0 = r, no value named); the single-particle values follow in order, each naming earlier
+ * values only as its variables; the energy stages come last.  Five launches (csrc/custom_gb.hip): the pair value in partial sums per
+ * column slice; the values and the single-particle terms with dE/dV; the pair terms (lane i evaluates every pair of its row and keeps
+ * half the energy, the dE/dr force on i and dE/dV_k,i); the chain rule back to dE/dV_0; and the chain force sum_j [dE/dV_0,i
+ * df(i,j)/dr + dE/dV_0,j df(j,i)/dr].  No lane writes another lane's particle, sums run in a fixed order: results are bit-identical
+ * from run to run.  r = 0 between distinct particles gives an energy and no pair force.  The cost is quadratic in N.
+ *
  * Tabulated functions (OpenMM's Continuous1DFunction and Discrete1DFunction) of every kind above: REMD_CX_TABLE1D and
  * REMD_CX_LOOKUP1D take one argument x from the stack and push one result; the operand is the offset of the function's block in the
  * force's constants.  The blocks follow the scalar constants, one per function:
@@ -211,6 +236,8 @@ extern "C" {
 
 #define REMD_CUSTOM_MANYPARTICLE 11 /* atoms NULL, n_terms = N, params [N][n_params]; functions of the particles p1 p2 p3 of every set of three */
 
+#define REMD_CUSTOM_GB       12    /* atoms NULL, n_terms = N, params [N][n_params]; computed values and energy terms of a CustomGBForce (gb_stages) */
+
 #define REMD_CUSTOM_MAX_PROGRAM 256
 #define REMD_CUSTOM_MAX_STACK   16
 #define REMD_CUSTOM_MAX_PARAMS  16
@@ -220,6 +247,10 @@ extern "C" {
 #define REMD_CUSTOM_MAX_CVS   3
 #define REMD_CUSTOM_MAX_MAPS  64
 #define REMD_CUSTOM_MP_MAX_NEIGHBORS 128     /* the capacity of one particle's neighbour row of a many-particle force          */
+#define REMD_CUSTOM_GB_MAX_VALUES 4           /* computed values of a Generalized-Born force                                    */
+#define REMD_CUSTOM_GB_MAX_TERMS  8           /* its energy terms                                                               */
+#define REMD_CUSTOM_GB_MAX_STAGES 32          /* rows of its stage table: values, and one per energy term and pass              */
+#define REMD_CUSTOM_GB_STAGE_INTS 28          /* int32 per row                                                                  */
 #define REMD_CUSTOM_MAX_TABLE_POINTS 8192   /* points of one tabulated function of one argument                               */
 #define REMD_CUSTOM_MAX_TABLE_CELLS 65536   /* nx ny (nz) of one tabulated function of two or three arguments                  */
 
@@ -323,6 +354,10 @@ typedef struct remd_custom_force_desc {
     int32_t mp_permutation_mode;   /* 0 SinglePermutation, 1 UniqueCentralParticle                                         */
     uint32_t mp_filter[3];         /* per slot p1 p2 p3: bit t set where a particle of type t may fill it (all ones: no filter) */
     int32_t mp_particle_mask;      /* bit s: the program names particle slot s (p1 p2 p3 = 0 1 2)                          */
+    /* REMD_CUSTOM_GB only (every other kind ignores them); it also reads nb_method, cutoff, excl_offsets and excl_atoms above */
+    const int32_t* gb_stages;      /* [gb_n_stages][REMD_CUSTOM_GB_STAGE_INTS] (the pointer first: it starts at a multiple of 8, where a host that lays the fields out kind by kind puts it) */
+    int32_t gb_n_values;           /* computed values, 1 ... REMD_CUSTOM_GB_MAX_VALUES                                     */
+    int32_t gb_n_stages;           /* rows of the stage table, 1 ... REMD_CUSTOM_GB_MAX_STAGES                             */
 } remd_custom_force_desc;
 
 /* the custom forces of the system; call after remd_set_system (which forgets them).  n = 0: none.  Every custom force of a handle

@@ -101,6 +101,11 @@ class RemdCustomForceDescManyParticle(RemdCustomForceDescHbond):
     _fields_ = [('mp_types', c_int32_p), ('mp_permutation_mode', C.c_int32), ('mp_filter', C.c_uint32 * 3), ('mp_particle_mask', C.c_int32)]
 
 
+class RemdCustomForceDescGB(RemdCustomForceDescManyParticle):
+    """the same, then the fields of REMD_CUSTOM_GB behind those of REMD_CUSTOM_MANYPARTICLE: the whole remd_custom_force_desc"""
+    _fields_ = [('gb_stages', c_int32_p), ('gb_n_values', C.c_int32), ('gb_n_stages', C.c_int32)]    # (the pointer first, as in C)
+
+
 class RemdGbModelDesc(C.Structure):
     """remd_gb_model_desc of include/remd_hip_gb.h (the constants and the cutoff of an OBC-family implicit-solvent model)."""
     _fields_ = [('offset', C.c_double), ('alpha', C.c_double), ('beta', C.c_double), ('gamma', C.c_double), ('ke', C.c_double),
@@ -243,7 +248,7 @@ def load_library(path=None):
         for name in RESTRAINT_FRAMES_EXPORTS:
             getattr(lib, name).restype = C.c_int
     if hasattr(lib, 'remd_set_custom_terms'):             # include/remd_hip_custom.h (GPU-only, like the restraints)
-        lib.remd_set_custom_terms.argtypes = [vp, C.POINTER(RemdCustomForceDescManyParticle), C.c_int]
+        lib.remd_set_custom_terms.argtypes = [vp, C.POINTER(RemdCustomForceDescGB), C.c_int]
         lib.remd_set_custom_globals.argtypes = [vp, c_double_p]
         lib.remd_set_custom_lrc.argtypes = [vp, c_double_p]
         lib.remd_get_custom_energies.argtypes = [vp, c_double_p]
@@ -651,7 +656,7 @@ class HipEngine:
     def _custom_entry(self, name):
         if not hasattr(self.lib, name):
             raise NotImplementedError('%s: this build of the engine library has no custom bond / angle / torsion / external forces and no compound-bond forces, '
-                                      'centroid-bond forces or nonbonded custom forces, nor CMAP torsion forces, donor-acceptor forces or many-particle forces '
+                                      'centroid-bond forces or nonbonded custom forces, nor CMAP torsion forces, donor-acceptor forces, many-particle forces or Generalized-Born expressions '
                                       '(include/remd_hip_custom.h is GPU-only)' % name)
         return getattr(self.lib, name)
 
@@ -661,7 +666,7 @@ class HipEngine:
         n_cv = sum(len(t['cv_offsets']) - 1 for t in terms if 'cv_offsets' in t)
         if n_cv:
             self._custom_cv_entry('remd_get_custom_cv_values')
-        arr = (RemdCustomForceDescManyParticle * max(1, len(terms)))()
+        arr = (RemdCustomForceDescGB * max(1, len(terms)))()
         keep = []
         for k, t in enumerate(terms):
             atoms = np.ascontiguousarray(t['atoms'], dtype=np.int32)
@@ -728,10 +733,15 @@ class HipEngine:
                     raise ValueError('set_custom_terms: types must hold one type per particle (%d, not %d)' % (n_terms, len(m_types)))
                 keep.append(m_types)
                 many = (_ip(m_types), int(t['permutation_mode']), (C.c_uint32 * 3)(*[int(v) for v in t['filters']]), int(t['particle_mask']))
+            gb = (None, 0, 0)
+            if 'stages' in t:                                        # a Generalized-Born force: the nonbonded kind's shape, then its stage table
+                g_stages = np.ascontiguousarray(t['stages'], dtype=np.int32).reshape(-1, 28)
+                keep.append(g_stages)
+                gb = (_ip(g_stages), int(t['n_values']), len(g_stages))
             no_atoms = nonbonded or 'cv_offsets' in t or 'donor_atoms' in t
-            arr[k] = RemdCustomForceDescManyParticle(int(t['kind']), n_terms, None if no_atoms else _ip(atoms), 0 if params is None else params.shape[1], _dp(params), len(program), _ip(program),
+            arr[k] = RemdCustomForceDescGB(int(t['kind']), n_terms, None if no_atoms else _ip(atoms), 0 if params is None else params.shape[1], _dp(params), len(program), _ip(program),
                                          len(consts), _dp(consts), int(t['stack_depth']), len(defaults), _dp(defaults),
-                                         int(t['periodic']), int(t['force_group']), n_particles, *groups, *pairs, *cvs, *maps, *hbond, *many)
+                                         int(t['periodic']), int(t['force_group']), n_particles, *groups, *pairs, *cvs, *maps, *hbond, *many, *gb)
         self._check(fn(self.h, arr, len(terms)), 'remd_set_custom_terms')
         self.n_custom = len(terms)
         self.n_custom_cvs = n_cv

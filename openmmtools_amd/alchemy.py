@@ -153,6 +153,10 @@ class AbsoluteAlchemicalFactory:
         if custom_gb and len(regions) > 1:
             raise NotImplementedError("Multiple regions does not work with CustomGBForce")              # alchemy.py:2274-2275
         for k in custom_gb:
+            from .custom_gb import takes_general_path
+            if takes_general_path(system.forces[k]):
+                raise NotImplementedError('AbsoluteAlchemicalFactory: a CustomGBForce that takes the general expression path (not one of the '
+                                          'OBC-family templates of openmmtools_amd/custom_gb.py): its alchemical rewrite is not supported')
             # _alchemically_modify_CustomGBForce (alchemy.py:2223-2345): the reference's rewritten strings; the force joins the
             # lambda_electrostatics forces when the System is written (_alchemical_xml.emit_region_forces)
             from .custom_gb import alchemically_modify_custom_gb

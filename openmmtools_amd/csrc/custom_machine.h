@@ -37,6 +37,8 @@ struct cst_tables : cst_plan {
     dev_array<double> d_W;             // [R][n_cv][16]: RMSD, "no force" flag, centroid, rotation, dE/dRMSD (custom_cv.hip)
     dev_array<int> d_mp_nbr;           // [R][mp_rows][REMD_CUSTOM_MP_MAX_NEIGHBORS]: the neighbour rows of the many-particle forces (custom_manyparticle.hip)
     dev_array<int> d_mp_cnt;           // [R][mp_rows]: their counts (which may exceed a row: the row then holds its first entries)
+    dev_array<int> d_gb_stages;        // the stage rows of the Generalized-Born forces (custom_gb.hip)
+    dev_array<double> d_gb_work;       // [R][gb_work]: their partial sums, values and dE/dV (custom_gb_plan.h)
 };
 
 namespace {
@@ -330,3 +332,6 @@ void remd_custom_hbond_ukl(remd_ctx* h, cst_tables& t);
 // neighbour rows, then the sets
 void remd_custom_manyparticle_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
 void remd_custom_manyparticle_ukl(remd_ctx* h, cst_tables& t);
+// custom_gb.hip: the same for the Generalized-Born forces (the part CST_GB, the last one): five launches per force.  They carry no
+// globals, so they have no u_kl launch
+void remd_custom_gb_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);

@@ -9,7 +9,8 @@
 // has a kernel of its own), a validator beside cst_check_cmap called from cst_check_force, its share of cst_pack_force, and its
 // tables as members of cst_plan with one line in upload_tables (custom_terms.hip).  Nothing else lists the tables.  The donor-acceptor kind
 // (REMD_CUSTOM_HBOND) keeps its validator, its share of the packing and its molecules in custom_hbond_plan.h, included below, and the
-// many-particle kind (REMD_CUSTOM_MANYPARTICLE) its validator and packer in custom_manyparticle_plan.h.
+// many-particle kind (REMD_CUSTOM_MANYPARTICLE) its validator and packer in custom_manyparticle_plan.h, the Generalized-Born kind
+// (REMD_CUSTOM_GB) its own in custom_gb_plan.h.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -45,13 +46,19 @@ struct cst_force {
     int mp_row0;                 // its first neighbour row among the handle's (Npad rows per such force)
     int mp_mask;                 // bit s: the program names particle slot s (p1 p2 p3 = 0 1 2); one seeded pass per bit
     unsigned mp_filter[3];       // per slot: bit t set where type t may fill it
+    // REMD_CUSTOM_GB only (custom_gb.hip): n_terms = N particles, npad = 64 nb (gb_slices + 1), parameters [n_params][Npad]; it shares
+    // nb_method, cutoff and excl0 (rows [N + 1], symmetric, sorted) with the nonbonded kind
+    int gb_n_values, gb_n_stages;  // its computed values and the rows of its stage table
+    int gb_stage0;               // its first row in the handle's gb_stages
+    int gb_slices;               // column slices of its pair launches (cst_gb_slices)
+    long long gb_work0;          // its first double in a replica's share of the handle's gb work buffer
 };
 
 // The parts of the padded term space, in its order; each has its own kernels, which run the wavefronts [begin(part), end(part)).
-enum cst_part { CST_SIMPLE, CST_COMPOUND, CST_NONBONDED, CST_CENTROID, CST_CV, CST_CMAP, CST_HBOND, CST_MANYPARTICLE, CST_N_PARTS };
+enum cst_part { CST_SIMPLE, CST_COMPOUND, CST_NONBONDED, CST_CENTROID, CST_CV, CST_CMAP, CST_HBOND, CST_MANYPARTICLE, CST_GB, CST_N_PARTS };
 // indexed by REMD_CUSTOM_*: the part of a kind (the four one-variable kinds share the first)
 // (kind 9 is not assigned and never gets this far: cst_check_shape refuses it; its entries below only keep the tables indexed by kind)
-static const int cst_part_of_kind[REMD_CUSTOM_MANYPARTICLE + 1] = {CST_SIMPLE, CST_SIMPLE, CST_SIMPLE, CST_SIMPLE, CST_COMPOUND, CST_CENTROID, CST_NONBONDED, CST_CV, CST_CMAP, CST_HBOND, CST_HBOND, CST_MANYPARTICLE};
+static const int cst_part_of_kind[REMD_CUSTOM_GB + 1] = {CST_SIMPLE, CST_SIMPLE, CST_SIMPLE, CST_SIMPLE, CST_COMPOUND, CST_CENTROID, CST_NONBONDED, CST_CV, CST_CMAP, CST_HBOND, CST_HBOND, CST_MANYPARTICLE, CST_GB};
 
 // everything the set-up computes on the host; the energy columns keep the forces' order whatever their slots
 struct cst_plan {
@@ -92,6 +99,10 @@ struct cst_plan {
     // rows join excl_off / excl_atoms.
     std::vector<int> mp_types;
     int mp_rows = 0;
+    // Generalized-Born forces (custom_gb.hip): the stage rows of all of them, and the doubles of work buffer one replica needs for
+    // all of them (custom_gb_plan.h).  Their exclusion rows join excl_off / excl_atoms.
+    std::vector<int> gb_stages;
+    size_t gb_work = 0;
     bool has_lrc = false, lrc_valid = false;   // (lrc_valid: remd_set_custom_lrc ran since the globals were last set)
     double periodic_cutoff = 0.0;      // the longest cutoff of a CutoffPeriodic nonbonded, donor-acceptor or many-particle force (remd_ctx::cst_cutoff)
     // the molecules a barostat moves as wholes where the handle has no NonbondedForce to take them from (remd_custom_molecules): atoms
@@ -110,13 +121,13 @@ inline bool cst_is_compound(int kind) { return kind == REMD_CUSTOM_COMPOUND || k
 // atoms (group numbers) per term in the descriptor's `atoms`
 inline int cst_width(const remd_custom_force_desc& d)
 {
-    static const int width[REMD_CUSTOM_MANYPARTICLE + 1] = {2, 3, 4, 1, -1, -1, 0, 0, 8, 0, 0, 0};
+    static const int width[REMD_CUSTOM_GB + 1] = {2, 3, 4, 1, -1, -1, 0, 0, 8, 0, 0, 0, 0};
     return cst_is_compound(d.kind) ? d.n_particles : width[d.kind];
 }
 // the variables a program may name
 inline int cst_n_vars(const remd_custom_force_desc& d)
 {
-    static const int n_vars[REMD_CUSTOM_MANYPARTICLE + 1] = {1, 1, 1, 3, -1, -1, 1, -1, 0, 0, 0, 0};
+    static const int n_vars[REMD_CUSTOM_GB + 1] = {1, 1, 1, 3, -1, -1, 1, -1, 0, 0, 0, 0, 3};
     return cst_is_compound(d.kind) ? 3 * d.n_particles : d.kind == REMD_CUSTOM_CV ? d.n_cvs : n_vars[d.kind];
 }
 
@@ -218,13 +229,15 @@ inline const char* check_program(const remd_custom_force_desc& d, int n_vars)
     return nullptr;
 }
 
+#include "custom_gb_plan.h"            // the Generalized-Born kind's validator and packer (cst_check_gb, cst_pack_gb); it runs check_program per stage
+
 // The validators: each returns the sentence of the first fault, or nothing.  cst_check_force fixes their order.
 
 // every kind: the kind itself, the particles per term, the terms, the per-term parameters
 inline std::string cst_check_shape(const remd_custom_force_desc& d)
 {
-    if (d.kind < 0 || d.kind > REMD_CUSTOM_MANYPARTICLE || d.kind == REMD_CUSTOM_CMAP + 1) return "unknown kind";      // (9 is not assigned)
-    const bool cmap = d.kind == REMD_CUSTOM_CMAP, atomless = d.kind == REMD_CUSTOM_NONBONDED || d.kind == REMD_CUSTOM_CV || d.kind == REMD_CUSTOM_HBOND || d.kind == REMD_CUSTOM_MANYPARTICLE;
+    if (d.kind < 0 || d.kind > REMD_CUSTOM_GB || d.kind == REMD_CUSTOM_CMAP + 1) return "unknown kind";      // (9 is not assigned)
+    const bool cmap = d.kind == REMD_CUSTOM_CMAP, atomless = d.kind == REMD_CUSTOM_NONBONDED || d.kind == REMD_CUSTOM_CV || d.kind == REMD_CUSTOM_HBOND || d.kind == REMD_CUSTOM_MANYPARTICLE || d.kind == REMD_CUSTOM_GB;
     if (cmap && d.n_particles != 8) return "n_particles is 8 for a CMAP force (two dihedrals of four particles)";
     if (!cmap && (cst_is_compound(d.kind) ? (d.n_particles < 1 || d.n_particles > REMD_CUSTOM_MAX_PARTICLES) : d.n_particles != 0))
         return "n_particles is 1 ... REMD_CUSTOM_MAX_PARTICLES for a compound-bond or centroid-bond force and 0 for every other kind";
@@ -353,7 +366,8 @@ inline std::string cst_check_force(const remd_custom_force_desc& d, const remd_c
     if (bad.empty() && d.kind == REMD_CUSTOM_HBOND) bad = cst_check_hbond(d, s);
     if (bad.empty() && d.kind == REMD_CUSTOM_MANYPARTICLE) bad = cst_check_manyparticle(d, s);
     if (bad.empty()) bad = cst_check_shared(d, d0);
-    if (bad.empty() && d.kind != REMD_CUSTOM_CMAP)       // (a CMAP force has no program)
+    if (bad.empty() && d.kind == REMD_CUSTOM_GB) bad = cst_check_gb(d, s);      // (with the programs of its stages, one by one)
+    if (bad.empty() && d.kind != REMD_CUSTOM_CMAP && d.kind != REMD_CUSTOM_GB)   // (a CMAP force has no program)
         if (const char* p = check_program(d, cst_n_vars(d))) bad = p;
     if (bad.empty() && d.kind == REMD_CUSTOM_CENTROID) bad = cst_check_groups(d, s.N);
     if (bad.empty() && d.kind != REMD_CUSTOM_CENTROID)
@@ -386,6 +400,7 @@ inline void cst_pack_force(const remd_custom_force_desc& d, const cst_facts& s, 
     }
     if (d.kind == REMD_CUSTOM_HBOND) cst_pack_hbond(d, f, p);
     if (d.kind == REMD_CUSTOM_MANYPARTICLE) { cst_pack_manyparticle(d, s, f, p); par_stride = s.Npad; }
+    if (d.kind == REMD_CUSTOM_GB) { cst_pack_gb(d, s, f, p); par_stride = s.Npad; }
     // parameters [n_params][npad]; a padding slot repeats the last term (finite arithmetic in lanes that add nothing)
     for (int q = 0; q < d.n_params; ++q) for (int k = 0; k < par_stride; ++k) p.par.push_back(d.params[(size_t)std::min(k, d.n_terms - 1) * d.n_params + q]);
     if (d.n_program > 0) p.prog.insert(p.prog.end(), d.program, d.program + 2 * (size_t)d.n_program);
@@ -484,7 +499,7 @@ inline void cst_fill_molecules(const remd_custom_force_desc* desc, int N, cst_pl
     for (int i = 0; i < p.nf; ++i) {
         const cst_force& f = p.F[i];
         if (f.kind == REMD_CUSTOM_HBOND) { cst_hbond_molecules(desc[i], f, find, root); continue; }
-        if (f.kind == REMD_CUSTOM_EXTERNAL || f.kind == REMD_CUSTOM_CENTROID || f.kind == REMD_CUSTOM_NONBONDED || f.kind == REMD_CUSTOM_CV || f.kind == REMD_CUSTOM_MANYPARTICLE) continue;
+        if (f.kind == REMD_CUSTOM_EXTERNAL || f.kind == REMD_CUSTOM_CENTROID || f.kind == REMD_CUSTOM_NONBONDED || f.kind == REMD_CUSTOM_CV || f.kind == REMD_CUSTOM_MANYPARTICLE || f.kind == REMD_CUSTOM_GB) continue;
         for (int b = 0; b < f.n_terms; ++b) for (int a = 1; a < f.n_particles; ++a) {
             const int u = find(desc[i].atoms[(size_t)b * f.n_particles]), v = find(desc[i].atoms[(size_t)b * f.n_particles + a]);
             if (u != v) root[std::max(u, v)] = std::min(u, v);

@@ -209,6 +209,8 @@ int ensure_buffers(remd_ctx* h, cst_tables& t)
     const size_t nR = (size_t)h->R * t.mp_rows;
     if (t.d_mp_cnt.size() != nR) REMD_TRY(t.d_mp_cnt.alloc(h, nR));
     if (t.d_mp_nbr.size() != nR * REMD_CUSTOM_MP_MAX_NEIGHBORS) REMD_TRY(t.d_mp_nbr.alloc(h, nR * REMD_CUSTOM_MP_MAX_NEIGHBORS));
+    // Generalized-Born forces: partial sums, values and dE/dV (gb_work = 0: nothing is allocated)
+    if (t.d_gb_work.size() != (size_t)h->R * t.gb_work) REMD_TRY(t.d_gb_work.alloc(h, (size_t)h->R * t.gb_work));
     return 0;
 }
 
@@ -227,8 +229,9 @@ int upload_tables(remd_ctx* h, cst_tables& t)
         (rc = t.d_lrc.upload(h, t.lrc)) || (rc = t.d_mol_first.upload(h, t.mol_first)) || (rc = t.d_mol_size.upload(h, t.mol_size)) ||
         (rc = t.d_cv_off.upload(h, t.cv_off)) || (rc = t.d_cv_atoms.upload(h, t.cv_atoms)) || (rc = t.d_cv_ref.upload(h, t.cv_ref)) ||
         (rc = t.d_map_off.upload(h, t.map_off)) || (rc = t.d_map_index.upload(h, t.map_index)) ||
-        (rc = t.d_hb_atoms.upload(h, t.hb_atoms)) || (rc = t.d_mp_types.upload(h, t.mp_types))) return rc;
-    t.d_E.reset(); t.d_Ewave.reset(); t.d_D.reset(); t.d_C.reset(); t.d_G.reset(); t.d_W.reset(); t.d_mp_nbr.reset(); t.d_mp_cnt.reset();
+        (rc = t.d_hb_atoms.upload(h, t.hb_atoms)) || (rc = t.d_mp_types.upload(h, t.mp_types)) ||
+        (rc = t.d_gb_stages.upload(h, t.gb_stages))) return rc;
+    t.d_E.reset(); t.d_Ewave.reset(); t.d_D.reset(); t.d_C.reset(); t.d_G.reset(); t.d_W.reset(); t.d_mp_nbr.reset(); t.d_mp_cnt.reset(); t.d_gb_work.reset();
     return 0;
 }
 
@@ -307,6 +310,7 @@ int remd_custom_forces(remd_ctx* h, bool with_energy, int ep_slot, hipStream_t s
     if (t.has(CST_CMAP)) remd_cmap_forces(h, t, with_energy, st);
     if (t.has(CST_HBOND)) remd_custom_hbond_forces(h, t, with_energy, st);
     if (t.has(CST_MANYPARTICLE)) remd_custom_manyparticle_forces(h, t, with_energy, st);
+    if (t.has(CST_GB)) remd_custom_gb_forces(h, t, with_energy, st);
     if (with_energy)
         hipLaunchKernelGGL(custom_reduce_kernel, dim3(h->R), dim3(64), 0, st, t.nf, t.d_F, waves, t.d_Ewave, t.d_E, h->d_epart, h->n_epart, ep_slot);
     if (with_energy && t.has_lrc) remd_custom_nonbonded_lrc(h, t, ep_slot, st);
@@ -325,9 +329,9 @@ int remd_custom_ukl(remd_ctx* h, double* d_rows)
     const int waves = t.total_pad / 64;
     const size_t nD = (size_t)h->R * h->K * waves;
     if (t.d_D.size() != nD) {
-        // (the CMAP forces' wavefronts have no globals and no u_kl launch: their columns are zeroed here, once, and nothing writes them)
+        // (the CMAP and Generalized-Born forces' wavefronts have no globals and no u_kl launch: their columns are zeroed here, once, and nothing writes them)
         REMD_TRY(t.d_D.alloc(h, nD));
-        if (t.has(CST_CMAP)) REMD_CHECK(h, hipMemsetAsync(t.d_D, 0, sizeof(double) * nD, h->stream));
+        if (t.has(CST_CMAP) || t.has(CST_GB)) REMD_CHECK(h, hipMemsetAsync(t.d_D, 0, sizeof(double) * nD, h->stream));
     }
     remd_prof_scope ps(h, "custom_ukl");
     if (t.has(CST_SIMPLE))

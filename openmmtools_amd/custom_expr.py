@@ -1003,7 +1003,7 @@ def custom_terms_desc(forces, masses=None, box_vectors=None):
     from . import system as _system
     names, defaults = [], []
     for f in forces:
-        if isinstance(f, _system.CMAPTorsionForce):                         # (no globals of its own)
+        if isinstance(f, (_system.CMAPTorsionForce, _system.CustomGBForce)):    # (no globals of its own; a CustomGBForce's are folded into its constants)
             continue
         for i in range(f.getNumGlobalParameters()):
             name, value = f.getGlobalParameterName(i), float(f.getGlobalParameterDefaultValue(i))
@@ -1024,6 +1024,10 @@ def custom_terms_desc(forces, masses=None, box_vectors=None):
     columns = {n: i for i, n in enumerate(names)}
     out = {}
     for k, f in enumerate(forces):
+        if isinstance(f, _system.CustomGBForce):                            # the general path of a CustomGBForce (custom_gb.py; csrc/custom_gb.hip)
+            from .custom_gb import compile_custom_gb
+            out['%03d' % len(out)] = compile_custom_gb(f, None if masses is None else len(masses), box_vectors, names, defaults)
+            continue
         cls = [c for c in KIND_OF_CLASS if c in [b.__name__ for b in type(f).__mro__]][0]
         kind = KIND_OF_CLASS[cls]
         if kind == KIND_CMAP:
@@ -1331,7 +1335,7 @@ def custom_globals(system, names, states):
     default value the forces carry."""
     defaults = {}
     for f in system.getForces():
-        if is_custom_term_force(f) and hasattr(as_cv_force(f), 'getNumGlobalParameters'):
+        if is_custom_term_force(f) and hasattr(as_cv_force(f), 'getNumGlobalParameters'):   # (a CustomGBForce is none: its globals are constants)
             f = as_cv_force(f)
             for i in range(f.getNumGlobalParameters()):
                 defaults.setdefault(f.getGlobalParameterName(i), float(f.getGlobalParameterDefaultValue(i)))

@@ -1,8 +1,10 @@
 """CustomGBForce of the OBC family: the one recognizer that system_to_desc, system_xml and _alchemical_xml share, and the reference's
 alchemical rewrite of a CustomGBForce.
 
-The engine evaluates no expression language.  A CustomGBForce is accepted when its strings are one of two template shapes with numbers
-in named slots, every other literal fixed:
+Two paths.  The template path (csrc/gbsa.hip) evaluates no expression language: it takes a CustomGBForce whose strings are one of two
+template shapes with numbers in named slots, every other literal fixed (below).  Every other CustomGBForce goes the general path at the
+end of this module: compile_custom_gb turns every computed value and energy term into programs of the custom forces' stack machine
+(REMD_CUSTOM_GB of include/remd_hip_custom.h, csrc/custom_gb.hip).  The templates:
 
   A  the strings of testsystems.CustomGBForceSystem (the reference's testsystems.py:4332-4351): computed values I (ParticlePairNoExclusions)
      and B (SingleParticle), one SingleParticle energy term (surface term + self term) and one ParticlePairNoExclusions pair term, the
@@ -321,8 +323,14 @@ def recognize_custom_gb(force):
 
 
 def custom_gb_to_desc(force, n, nb_method, box):
-    """d['gbsa'] of system_to_desc for a CustomGBForce: the particle tables and the model (remd_set_gbsa + remd_set_gb_model)"""
-    m = recognize_custom_gb(force)
+    """d['gbsa'] of system_to_desc for a CustomGBForce: the particle tables and the model (remd_set_gbsa + remd_set_gb_model); None for
+    a force the recognizer refuses: system_to_desc then compiles it for the general path (compile_custom_gb)"""
+    try:
+        m = recognize_custom_gb(force)
+    except NotImplementedError:
+        if not force.computed and not force.energy_terms:      # nothing to compile: the recognizer's sentence stands
+            raise
+        return None
     if force.getNumParticles() != n:
         raise ValueError('CustomGBForce has %d particles, system has %d' % (force.getNumParticles(), n))
     if m['method'] == 2:
@@ -350,3 +358,205 @@ def is_default_model(gb):
         if float(gb.get(k, OBC2_MODEL[k])) != float(OBC2_MODEL[k]):
             return False
     return True
+
+
+# ---- the general path: every other CustomGBForce, compiled for the stack machine (csrc/custom_gb.hip) ---------------------------------
+KIND_GB = 12                                    # REMD_CUSTOM_GB of include/remd_hip_custom.h
+MAX_VALUES, MAX_TERMS, MAX_STAGES, STAGE_INTS = 4, 8, 32, 28
+STAGE_PAIR_VALUE, STAGE_SINGLE_VALUE, STAGE_SINGLE_ENERGY, STAGE_PAIR_ENERGY = 0, 1, 2, 3
+_TYPE_NAMES = {SINGLE: 'SingleParticle', PAIR: 'ParticlePair', PAIR_NO_EXCLUSIONS: 'ParticlePairNoExclusions'}
+
+
+def quantity_code(kind, index=0, particle=0):
+    """the stage table's code of a quantity: 'r'; ('value', k, s) = value k of particle s; ('param', q, s) = parameter q of particle s
+    (s = 0: particle 1, or the particle itself in a single-particle expression; 1: particle 2)"""
+    return 0 if kind == 'r' else (1 if kind == 'value' else 16) + 2 * index + particle
+
+
+def _names_of(expression, where):
+    """every name an expression and its definitions use (function names included)"""
+    from .custom_expr import split_definitions, _TOKEN
+    body, definitions = split_definitions(expression, where)
+    names = set()
+    for text in [body] + list(definitions.values()):
+        for m in _TOKEN.finditer(text):
+            if m.group(2) is not None:
+                names.add(m.group(2))
+    return names, definitions
+
+
+def compile_gb_expression(expression, pair, values_known, per_particle, global_values, tabulated, where):
+    """The programs of one expression of a CustomGBForce, one per pass: [dict(program, consts, stack_depth, variables, columns)],
+    variables and columns being quantity codes.  The quantities to be differentiated -- r and name1 / name2 of every value the
+    expression names (pair), the values it names (single particle) -- are the machine's three variables, pass by pass; everything
+    else the expression names is a staged column.  Globals are folded into the constants: each becomes a definition
+    ``name = value`` unless the expression defines the name itself."""
+    from .custom_expr import compile_expression, MAX_PARAMS
+    used, definitions = _names_of(expression, where)
+    if not pair:
+        for bad in ('x', 'y', 'z'):
+            if bad in used and bad not in definitions and bad not in per_particle and bad not in values_known:
+                raise NotImplementedError('%s: variable %r (a single-particle expression of a CustomGBForce that depends on the position is not supported)' % (where, bad))
+    text = str(expression).rstrip().rstrip(';')
+    for name, value in global_values:
+        if name in used and name not in definitions:
+            text += '; %s = %r' % (name, float(value))
+    # what a name means here: name -> quantity code
+    meaning = {}
+    for s in ((0, 1) if pair else (0,)):
+        suffix = str(s + 1) if pair else ''
+        for k, v in enumerate(values_known):
+            meaning[v + suffix] = quantity_code('value', k, s)
+        for q, p in enumerate(per_particle):
+            meaning[p + suffix] = quantity_code('param', q, s)
+    if pair:
+        meaning['r'] = 0
+        for name in sorted(used):
+            if name not in definitions and name not in meaning and (name in per_particle or name in values_known):
+                raise NotImplementedError('%s: per-particle name %r without a particle suffix (%s1 or %s2)' % (where, name, name, name))
+    named = [n for n in sorted(used, key=lambda n: meaning.get(n, -1)) if n in meaning and n not in definitions]
+    if pair:
+        values_named = sorted({(meaning[n] - 1) // 2 for n in named if 1 <= meaning[n] < 16})
+        differentiated = ['r'] + [values_known[k] + s for k in values_named for s in ('1', '2')]
+    else:
+        differentiated = [n for n in named if 1 <= meaning[n] < 16]
+    passes = [differentiated[k:k + 3] for k in range(0, len(differentiated), 3)] or [[]]
+    out = []
+    for variables in passes:
+        columns = [n for n in named if n not in variables]
+        if len(columns) > MAX_PARAMS:
+            raise NotImplementedError('%s: a program that names %d staged columns (the engine takes %d): %s' % (where, len(columns), MAX_PARAMS, ', '.join(columns)))
+        prog = compile_expression(text, tuple(variables), columns, {}, where=where, tabulated=tabulated)
+        out.append(dict(program=prog['program'], consts=prog['consts'], stack_depth=prog['stack_depth'],
+                        variables=[meaning[n] for n in variables], columns=[meaning[n] for n in columns]))
+    return out
+
+
+def gb_exclusions(force, n):
+    """The exclusions of a CustomGBForce in CSR form: (excl_offsets int32 [n + 1], excl_atoms int32), symmetric, each row sorted."""
+    rows = [set() for _ in range(n)]
+    for k in range(force.getNumExclusions()):
+        i, j = force.getExclusionParticles(k)
+        if not (0 <= i < n and 0 <= j < n):
+            raise ValueError('CustomGBForce: exclusion %d names particle %d (the force has %d)' % (k, i if not 0 <= i < n else j, n))
+        if i == j:
+            raise ValueError('CustomGBForce: exclusion %d excludes particle %d from itself' % (k, i))
+        if j in rows[i]:
+            raise ValueError('CustomGBForce: particles %d and %d are excluded twice' % (i, j))
+        rows[i].add(j); rows[j].add(i)
+    offsets = np.zeros(n + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum([len(r) for r in rows])
+    return offsets, np.array([j for r in rows for j in sorted(r)], dtype=np.int32)
+
+
+_TABLE_OPS = (38, 39, 40, 41, 42)               # TABLE1D ... LOOKUP3D: their operand is an offset into the constants, like CONST's (0)
+
+
+def compile_custom_gb(force, n_atoms=None, box_vectors=None, global_names=(), global_defaults=()):
+    """The custom_terms entry of a CustomGBForce on the general path (REMD_CUSTOM_GB): the common keys, with program and consts the
+    stages' back to back, params [N][n_params], nb_method, cutoff, excl_offsets / excl_atoms, n_values and stages int32
+    [n][STAGE_INTS] (include/remd_hip_custom.h).  global_names / global_defaults are the handle's columns (the other custom forces');
+    the force's own globals are folded into its constants at their default values.  ValueError for bad input, NotImplementedError for
+    what the engine does not evaluate."""
+    cls = 'CustomGBForce'
+    n = force.getNumParticles()
+    if n_atoms is not None and n != n_atoms:
+        raise ValueError('%s has %d particles, system has %d' % (cls, n, n_atoms))
+    if n == 0:
+        raise ValueError('%s has no particles' % cls)
+    per_particle = list(force.per_particle)
+    for k in range(n):
+        if len(force.particles[k]) != len(per_particle):
+            raise ValueError('%s: particle %d carries %d parameters, the force declares %d' % (cls, k, len(force.particles[k]), len(per_particle)))
+    from .custom_expr import MAX_PARAMS, CONST
+    if len(per_particle) > MAX_PARAMS:
+        raise NotImplementedError('%s: %d per-particle parameters (the engine takes %d): %s' % (cls, len(per_particle), MAX_PARAMS, ', '.join(per_particle)))
+    if not force.computed and not force.energy_terms:
+        raise ValueError('%s has neither computed values nor energy terms' % cls)
+    if len(force.computed) > MAX_VALUES:
+        raise NotImplementedError('%s: %d computed values (the engine takes %d): %s' % (cls, len(force.computed), MAX_VALUES, ', '.join(v[0] for v in force.computed)))
+    if len(force.energy_terms) > MAX_TERMS:
+        raise NotImplementedError('%s: %d energy terms (the engine takes %d)' % (cls, len(force.energy_terms), MAX_TERMS))
+    computed = list(force.computed)
+    if not computed:                            # (energy terms alone: a pair value that is zero keeps the stage table's shape)
+        computed = [('__none', '0', PAIR_NO_EXCLUSIONS)]
+    for k, (name, expr, kind) in enumerate(computed):
+        if kind not in _TYPE_NAMES:
+            raise ValueError('%s: computed value %r has the unknown type %r' % (cls, name, kind))
+        if k == 0 and kind == SINGLE:
+            raise NotImplementedError('%s: the first computed value %r is of type SingleParticle (it must be ParticlePair or ParticlePairNoExclusions)' % (cls, name))
+        if k > 0 and kind != SINGLE:
+            raise NotImplementedError('%s: computed value %r of type %s behind the first (every value after the first must be SingleParticle)'
+                                      % (cls, name, _TYPE_NAMES[kind]))
+        if name in [v[0] for v in computed[:k]] or name in per_particle:
+            raise ValueError('%s: computed value %r is named twice' % (cls, name))
+    for expr, kind in force.energy_terms:
+        if kind not in _TYPE_NAMES:
+            raise ValueError('%s: energy term %r has the unknown type %r' % (cls, expr[:60], kind))
+    method = int(force.getNonbondedMethod())
+    if method not in (0, 1, 2):
+        raise NotImplementedError('%s: nonbonded method %d (NoCutoff, CutoffNonPeriodic and CutoffPeriodic are supported)' % (cls, method))
+    cutoff = float(force.getCutoffDistance()) if method else 0.0
+    if method and not cutoff > 0.0:
+        raise ValueError('%s: cutoff distance %r' % (cls, cutoff))
+    if method == 2:
+        if box_vectors is None:
+            raise ValueError('%s: CutoffPeriodic needs the periodic box vectors of the System' % cls)
+        box = np.asarray(box_vectors, dtype=np.float64).reshape(3, 3)
+        if np.any(box != np.diag(np.diag(box))):
+            raise NotImplementedError('%s: triclinic boxes are not supported (CutoffPeriodic takes a rectangular box)' % cls)
+        if cutoff > 0.5 * np.diag(box).min():
+            raise ValueError('%s: the cutoff %r nm exceeds half the smallest box edge (%r nm)' % (cls, cutoff, float(np.diag(box).min())))
+    offsets, excluded = gb_exclusions(force, n)
+    tabulated = list(force.functions)
+    global_values = [(g[0], g[1]) for g in force.globals]
+    value_names = [v[0] for v in computed]
+    program, consts, stages = [], [], []
+
+    def add_stages(kind_code, excl, target, passes):
+        for p, s in enumerate(passes):
+            base = len(consts)
+            prog = np.array(s['program'], dtype=np.int64).reshape(-1, 2)
+            shift = np.isin(prog[:, 0], (CONST,) + _TABLE_OPS)
+            prog[shift, 1] += base
+            row = np.zeros(STAGE_INTS, dtype=np.int32)
+            row[:7] = (kind_code, excl, target, p, len(program), len(prog), s['stack_depth'])
+            row[7:10] = (list(s['variables']) + [-1, -1, -1])[:3]
+            row[10] = len(s['columns'])
+            row[11:11 + len(s['columns'])] = s['columns']
+            stages.append(row)
+            program.extend(prog.tolist())
+            consts.extend(np.asarray(s['consts'], dtype=np.float64).tolist())
+
+    for k, (name, expr, kind) in enumerate(computed):
+        where = '%s (computed value %r = %r)' % (cls, name, expr)
+        passes = compile_gb_expression(expr, k == 0, value_names[:k], per_particle, global_values, tabulated, where)
+        if k == 0:
+            passes[0]['variables'] = [0]        # (one pass with r: an expression without r still has the variable)
+            if len(passes) > 1:
+                raise AssertionError('the first value names no value')
+            if 0 in passes[0]['columns']:
+                raise AssertionError('r is a variable')
+        add_stages(STAGE_PAIR_VALUE if k == 0 else STAGE_SINGLE_VALUE, int(kind == PAIR), k, passes)
+    for t, (expr, kind) in enumerate(force.energy_terms):
+        where = '%s (energy term %d = %r)' % (cls, t, expr)
+        passes = compile_gb_expression(expr, kind != SINGLE, value_names, per_particle, global_values, tabulated, where)
+        add_stages(STAGE_SINGLE_ENERGY if kind == SINGLE else STAGE_PAIR_ENERGY, int(kind == PAIR), t, passes)
+    if len(stages) > MAX_STAGES:
+        raise NotImplementedError('%s: %d stages (values, and one per energy term and pass; the engine takes %d)' % (cls, len(stages), MAX_STAGES))
+    params = np.array(force.particles, dtype=np.float64).reshape(n, len(per_particle))
+    return dict(kind=KIND_GB, atoms=np.zeros((0, 0), dtype=np.int32), params=params, global_names=list(global_names),
+                global_defaults=np.array(global_defaults, dtype=np.float64), program=np.array(program, dtype=np.int32).reshape(-1, 2),
+                consts=np.array(consts, dtype=np.float64), stack_depth=int(max(s[6] for s in stages)), periodic=int(method == 2),
+                force_group=int(force.getForceGroup()), energy='CustomGBForce(%s)' % '; '.join(v[0] for v in force.computed),
+                nb_method=method, cutoff=cutoff, switch_distance=-1.0, excl_offsets=offsets, excl_atoms=excluded, long_range_correction=0,
+                n_values=len(computed), stages=np.array(stages, dtype=np.int32).reshape(-1, STAGE_INTS), value_names=value_names)
+
+
+def takes_general_path(force):
+    """True for a CustomGBForce that recognize_custom_gb refuses: system_to_desc then compiles it (compile_custom_gb)"""
+    try:
+        recognize_custom_gb(force)
+    except NotImplementedError:
+        return True
+    return False

@@ -63,7 +63,7 @@ class EnginePool:
         if any(d.get('restraints') for d in descs):
             raise NotImplementedError('restraints (forces.py) in more than one compatibility group')
         if any(d.get('custom_terms') for d in descs):
-            raise NotImplementedError('custom bond / angle / torsion / external forces and compound-bond forces, centroid-bond forces or nonbonded custom forces, or CMAP torsion forces, donor-acceptor forces or many-particle forces (custom_expr.py) in more than one compatibility group')
+            raise NotImplementedError('custom bond / angle / torsion / external forces and compound-bond forces, centroid-bond forces or nonbonded custom forces, or CMAP torsion forces, donor-acceptor forces, many-particle forces or Generalized-Born expressions (custom_expr.py, custom_gb.py) in more than one compatibility group')
         if any(d.get('virtual_sites') for d in descs):
             raise NotImplementedError('virtual sites (system.setVirtualSite) in more than one compatibility group')
         n = {int(d['n_atoms']) for d in descs}

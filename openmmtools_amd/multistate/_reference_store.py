@@ -447,6 +447,10 @@ class ReferenceStoreWriter:
                     return 'a System with a %s' % type(f).__name__
                 if is_custom_term_force(f):                 # (nor that of a custom force with an expression of its own)
                     return 'a System with a %s (energy %r)' % (type(f).__name__, energy_text(f))
+                if type(f).__name__ == 'CustomGBForce':     # (nor a CustomGBForce on the general path: the XML reader refuses it)
+                    from ..custom_gb import takes_general_path
+                    if takes_general_path(f):
+                        return 'a System with a CustomGBForce that takes the general expression path (computed values %s)' % ', '.join(repr(v[0]) for v in f.computed)
             if (getattr(s.system, 'alchemical_region', None) is not None or getattr(s.system, 'alchemical_regions', None) is not None) and id(s.system) not in seen:
                 seen.add(id(s.system))
                 try:                                        # the factory's force set for this System (_alchemical_xml.py) or why not

@@ -1141,9 +1141,11 @@ class GBSAOBCForce(Force):
 
 class CustomGBForce(Force):
     """openmm.CustomGBForce: per-particle parameters, global parameters, computed values and energy terms given as expression strings.
-    The engine evaluates only the OBC family (openmmtools_amd/custom_gb.py recognises it: the CustomGBForceSystem strings of
-    testsystems.py:4332-4351, the alchemical factory's GBSA strings, and both after _alchemically_modify_CustomGBForce), with
-    NoCutoff or CutoffPeriodic; system_to_desc refuses everything else with NotImplementedError."""
+    The OBC family (openmmtools_amd/custom_gb.py recognises it: the CustomGBForceSystem strings of testsystems.py:4332-4351, the
+    alchemical factory's GBSA strings, and both after _alchemically_modify_CustomGBForce), with NoCutoff or CutoffPeriodic, goes to
+    csrc/gbsa.hip; every other force is compiled for the custom forces' stack machine (custom_gb.compile_custom_gb, csrc/custom_gb.hip):
+    at most 4 computed values, the first a pair sum and the others SingleParticle, at most 8 energy terms, tabulated functions,
+    exclusions, the three nonbonded methods; global parameters take their default values."""
     NoCutoff, CutoffNonPeriodic, CutoffPeriodic = 0, 1, 2
     SingleParticle, ParticlePair, ParticlePairNoExclusions = 0, 1, 2
 
@@ -1155,7 +1157,7 @@ class CustomGBForce(Force):
         self.energy_terms = []              # (expression, type)
         self.particles = []                 # tuples of floats
         self.exclusions = []                # (i, j)
-        self.functions = []                 # (name, function): tabulated functions (refused by the engine)
+        self.functions = []                 # (name, function): tabulated functions (the general path evaluates them)
         self._method, self._cutoff = 0, 1.0
 
     def addPerParticleParameter(self, name):
@@ -1195,6 +1197,10 @@ class CustomGBForce(Force):
     def getCutoffDistance(self): return self._cutoff
     def setCutoffDistance(self, d): self._cutoff = float(d)
     def usesPeriodicBoundaryConditions(self): return self._method == CustomGBForce.CutoffPeriodic
+
+    def updateParametersInContext(self, context=None):
+        raise NotImplementedError('CustomGBForce: changing particles, exclusions or functions after set_system (updateParametersInContext) is '
+                                  'not supported: the engine keeps the tables it was given, build the states again')
 
 
 class CMMotionRemover(Force):
@@ -1772,7 +1778,11 @@ def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
         from .custom_gb import custom_gb_to_desc
         if box is None:
             box = np.diag(system.getDefaultPeriodicBoxVectors())
-        d['gbsa'] = custom_gb_to_desc(gb, n, d['nb_method'], box)
+        gbsa = custom_gb_to_desc(gb, n, d['nb_method'], box)
+        if gbsa is None:                    # not of the OBC templates: the general path, one of the custom forces (csrc/custom_gb.hip)
+            custom.append(gb)
+        else:
+            d['gbsa'] = gbsa
     elif gb is not None:
         # implicit solvent: remd_set_gbsa (csrc/gbsa.hip).  The surface term is the ACE one with OpenMM's default energy (28.3919551 = 4 pi x
         # 2.25936 kJ/mol/nm^2 in the factory's expression, alchemy.py:2207); 0 switches it off
@@ -1875,6 +1885,36 @@ def manyparticle_force_from_openmm(f):
     return g
 
 
+def gb_force_from_openmm(f):
+    """An openmm.CustomGBForce as the class of the same name here; by the object's getters, so that no OpenMM is needed.  The cutoff may
+    carry a unit (anything with value_in_unit_system) or be a number in nm; functions are taken over as they are when they are this
+    module's classes and rebuilt from getFunctionParameters() by class name otherwise (a GBn / GBn2 System brings its neck tables)."""
+    g = CustomGBForce()
+    for i in range(f.getNumPerParticleParameters()):
+        g.addPerParticleParameter(f.getPerParticleParameterName(i))
+    for i in range(f.getNumGlobalParameters()):
+        g.addGlobalParameter(f.getGlobalParameterName(i), f.getGlobalParameterDefaultValue(i))
+    _functions_from_openmm(f, g, 'CustomGBForce')
+    for i in range(f.getNumComputedValues()):
+        name, expression, kind = f.getComputedValueParameters(i)
+        g.addComputedValue(name, expression, int(kind))
+    for i in range(f.getNumEnergyTerms()):
+        expression, kind = f.getEnergyTermParameters(i)
+        g.addEnergyTerm(expression, int(kind))
+    for i in range(f.getNumParticles()):
+        g.addParticle(list(f.getParticleParameters(i)))
+    for i in range(f.getNumExclusions()):
+        g.addExclusion(*f.getExclusionParticles(i))
+    g.setNonbondedMethod(int(f.getNonbondedMethod()))
+    cutoff = f.getCutoffDistance()
+    if hasattr(cutoff, 'value_in_unit_system'):
+        from .unit import to_md
+        cutoff = to_md(cutoff)
+    g.setCutoffDistance(cutoff)
+    g.setForceGroup(int(f.getForceGroup()))
+    return g
+
+
 def hbond_force_from_openmm(f):
     """An openmm.CustomHbondForce as the class of the same name here; by the object's getters, so that no OpenMM is needed.  The cutoff
     may carry a unit (anything with value_in_unit) or be a number in nm; functions are taken over as they are when they are this
@@ -1968,6 +2008,8 @@ def from_openmm(omm_system):
             g = hbond_force_from_openmm(f)
         elif type(f).__name__ == 'CustomManyParticleForce':
             g = manyparticle_force_from_openmm(f)
+        elif type(f).__name__ == 'CustomGBForce':
+            g = gb_force_from_openmm(f)
         else:
             raise NotImplementedError('unsupported OpenMM force %s' % type(f).__name__)
         s.addForce(g)

@@ -438,14 +438,37 @@ class AlanineDipeptideImplicit(AlanineDipeptideVacuum):
     current OpenMM builds as a CustomGBForce from its own expression library (not in the reference's tree); what is built here is
     ``implicitSolvent='OBC2'`` = openmm.GBSAOBCForce -- the force the reference's alchemical factory spells out term by term
     (alchemy.py:2144-2225) -- with the topology's own GB radii and screening factors (prmtop RADII / SCREEN, mbondi2), solvent
-    dielectric 78.5, solute dielectric 1, ACE surface term."""
+    dielectric 78.5, solute dielectric 1, ACE surface term.
+
+    ``implicitSolvent='HCT'`` is the Hawkins-Cramer-Truhlar model as a CustomGBForce whose strings are written here: the same
+    integral I, B = 1 / (1 / or - I), the self and pair terms of the OBC strings and the ACE surface term.  It uses the same radii and
+    screening factors, the file's mbondi2 ones -- not the radii set openmm.app pairs with HCT.  The engine compiles it for the custom
+    forces' stack machine (custom_gb.compile_custom_gb)."""
 
     def __init__(self, implicitSolvent='OBC2', constraints='HBonds', hydrogenMass=None, **kwargs):
-        if implicitSolvent != 'OBC2':
-            raise NotImplementedError("implicitSolvent=%r: only 'OBC2' (openmm.GBSAOBCForce) is built" % (implicitSolvent,))
+        if implicitSolvent not in ('OBC2', 'HCT'):
+            raise NotImplementedError("implicitSolvent=%r: only 'OBC2' (openmm.GBSAOBCForce) and 'HCT' (a CustomGBForce) are built" % (implicitSolvent,))
         super().__init__(constraints=constraints, hydrogenMass=hydrogenMass, **kwargs)
-        from .system import GBSAOBCForce
+        from .system import GBSAOBCForce, CustomGBForce
         z = np.load(os.path.join(_DATA, 'alanine-dipeptide-vacuum.npz'))
+        if implicitSolvent == 'HCT':
+            gb = CustomGBForce()
+            for name in ('charge', 'radius', 'scale'):
+                gb.addPerParticleParameter(name)
+            gb.addGlobalParameter('solventDielectric', 78.5)
+            gb.addGlobalParameter('soluteDielectric', 1.0)
+            gb.addComputedValue('I', 'step(r+sr2-or1)*0.5*(1/L-1/U+0.25*(r-sr2^2/r)*(1/(U^2)-1/(L^2))+0.5*log(L/U)/r+C);'
+                                'U=r+sr2; C=2*(1/or1-1/L)*step(sr2-r-or1); L=max(or1,D); D=abs(r-sr2); sr2=scale2*or2;'
+                                'or1=radius1-0.009; or2=radius2-0.009', CustomGBForce.ParticlePairNoExclusions)
+            gb.addComputedValue('B', '1/(1/or-I); or=radius-0.009', CustomGBForce.SingleParticle)
+            gb.addEnergyTerm('28.3919551*(radius+0.14)^2*(radius/B)^6-0.5*138.935485*(1/soluteDielectric-1/solventDielectric)*charge^2/B',
+                             CustomGBForce.SingleParticle)
+            gb.addEnergyTerm('-138.935485*(1/soluteDielectric-1/solventDielectric)*charge1*charge2/f; f=sqrt(r^2+B1*B2*exp(-r^2/(4*B1*B2)))',
+                             CustomGBForce.ParticlePairNoExclusions)
+            for q, r, sc in zip(z['charge'], z['gb_radii'], z['gb_screen']):
+                gb.addParticle([q, r, sc])
+            self.system.addForce(gb)
+            return
         gb = GBSAOBCForce()
         for q, r, sc in zip(z['charge'], z['gb_radii'], z['gb_screen']):
             gb.addParticle(q, r, sc)

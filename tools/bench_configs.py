@@ -75,6 +75,20 @@ def main():
         s.create(states.ThermodynamicState(mw.system, 250.0 * unit.kelvin), [ss], storage=None, min_temperature=250.0 * unit.kelvin,
                  max_temperature=320.0 * unit.kelvin, n_temperatures=24)
         run('mw: StillingerWeberFluid(512, mW), 24 temperatures 250 - 320 K, BAOAB 5 fs x 500', s, 5)
+    if 'hct' in which:
+        # implicit-solvent parallel tempering with a CustomGBForce on the general path (custom_gb.compile_custom_gb, csrc/custom_gb.hip):
+        # 24 temperatures of testsystems.AlanineDipeptideImplicit(implicitSolvent='HCT'); 'obc2' runs the same on csrc/gbsa.hip
+        al = testsystems.AlanineDipeptideImplicit(implicitSolvent='HCT')
+        s = ParallelTemperingSampler(mcmc_moves=move(2.0, 'V R O R V'), number_of_iterations=10 ** 9, engine=HipEngine(), seed=1)
+        s.create(states.ThermodynamicState(al.system, 300.0 * unit.kelvin), [states.SamplerState(al.positions)], storage=None,
+                 min_temperature=300.0 * unit.kelvin, max_temperature=600.0 * unit.kelvin, n_temperatures=24)
+        run('hct: AlanineDipeptideImplicit(HCT, CustomGBForce expressions), 24 temperatures 300 - 600 K, BAOAB 2 fs x 500', s, 5)
+    if 'obc2' in which:
+        al = testsystems.AlanineDipeptideImplicit()
+        s = ParallelTemperingSampler(mcmc_moves=move(2.0, 'V R O R V'), number_of_iterations=10 ** 9, engine=HipEngine(), seed=1)
+        s.create(states.ThermodynamicState(al.system, 300.0 * unit.kelvin), [states.SamplerState(al.positions)], storage=None,
+                 min_temperature=300.0 * unit.kelvin, max_temperature=600.0 * unit.kelvin, n_temperatures=24)
+        run('obc2: AlanineDipeptideImplicit(OBC2, GBSAOBCForce), 24 temperatures 300 - 600 K, BAOAB 2 fs x 500', s, 5)
     if '4rs' in which:
         # config 4's share with a receptor-ligand restraint (forces.py, csrc/restraints.hip): a HarmonicRestraintForce between the CB7
         # heavy atoms and the B2 guest, K = 0.2 kcal/mol/A^2, lambda_restraints rising 0 -> 1 along the coupled half and 1 where the

@@ -61,7 +61,7 @@ int main(int argc, char** argv)
         printf("PLAN\n");
         printf("scalars 5 %d %d %d %d %d\n", p.nf, p.ng, p.K, p.total_pad, p.mp_rows);
         printf("periodic_cutoff 1 %a\n", p.periodic_cutoff);
-        printf("part_end %d", (int)CST_N_PARTS); for (int k = 0; k < CST_N_PARTS; ++k) printf(" %d", p.end(k)); printf("\n");
+        printf("part_end %d", (int)CST_MANYPARTICLE + 1); for (int k = 0; k <= CST_MANYPARTICLE; ++k) printf(" %d", p.end(k)); printf("\n");   // (the parts up to this kind's: later kinds add theirs behind it)
         for (const cst_force& f : p.F)
             printf("force 17 %d %d %d %d %d %d %d %d %d %d %d %d %d %u %u %u %a\n", f.kind, f.periodic, f.n_terms, f.n_params, f.slot0, f.npad,
                    f.par0, f.nb_method, f.excl0, f.mp_mode, f.mp_types0, f.mp_row0, f.mp_mask, f.mp_filter[0], f.mp_filter[1], f.mp_filter[2], f.cutoff);
