@@ -135,6 +135,17 @@ class RemdVsiteDesc(C.Structure):
     """remd_vsite_desc (include/remd_hip_vsites.h)."""
     _fields_ = [('kind', C.c_int32), ('site', C.c_int32), ('parent', C.c_int32 * 3), ('weight', C.c_double * 3)]
 
+
+# the GPU-only extension of include/remd_hip_mcmoves.h (Metropolized rigid-body moves on the device), bound the same way
+MC_MOVE_EXPORTS = ['remd_mc_rigid_moves']
+MC_DISPLACEMENT, MC_ROTATION, MC_MAX_MOVES = 0, 1, 16
+
+
+class RemdMcMoveDesc(C.Structure):
+    """remd_mc_move_desc (include/remd_hip_mcmoves.h)."""
+    _fields_ = [('kind', C.c_int32), ('n_atoms', C.c_int32), ('atoms', C.POINTER(C.c_int32)), ('sigma_nm', C.c_double),
+                ('position', C.c_int32)]
+
 EXPORTS = [
     'remd_create', 'remd_destroy', 'remd_last_error', 'remd_version', 'remd_set_system', 'remd_set_coulomb_cutoff', 'remd_set_reaction_field', 'remd_set_alchemical_options', 'remd_set_alchemical_regions',
     'remd_set_region_lambdas', 'remd_set_region_bonded_lambdas', 'remd_set_gbsa', 'remd_set_states',
@@ -269,6 +280,9 @@ def load_library(path=None):
     if hasattr(lib, 'remd_set_virtual_sites'):            # include/remd_hip_vsites.h (GPU-only, like the restraints)
         lib.remd_set_virtual_sites.argtypes = [vp, C.POINTER(RemdVsiteDesc), C.c_int32]
         lib.remd_set_virtual_sites.restype = C.c_int
+    if hasattr(lib, 'remd_mc_rigid_moves'):               # include/remd_hip_mcmoves.h (GPU-only, like the restraints)
+        lib.remd_mc_rigid_moves.argtypes = [vp, C.POINTER(RemdMcMoveDesc), C.c_int32, C.c_int64, c_int32_p]
+        lib.remd_mc_rigid_moves.restype = C.c_int
     if hasattr(lib, 'remd_mbar_create'):                  # include/remd_hip_mbar.h (GPU-only, like the restraints)
         lib.remd_mbar_create.argtypes = [C.c_int, C.c_int, C.c_int64, c_double_p, c_int64_p, C.POINTER(vp)]
         lib.remd_mbar_destroy.argtypes = [vp]
@@ -895,6 +909,25 @@ class HipEngine:
     def barostat_attempts(self, n_attempts):
         """mcmc.py:1597-1700 MonteCarloBarostatMove: n volume moves of every local replica outside the integrator."""
         self._check(self.lib.remd_barostat_attempts(self.h, int(n_attempts)), 'remd_barostat_attempts')
+
+    def mc_rigid_moves(self, moves, iteration):
+        """mcmc.py:1704-1910 MCDisplacementMove / MCRotationMove with proposal='device': the moves in order for every local
+        replica, entirely on the device (include/remd_hip_mcmoves.h).  ``moves``: (kind, atom indices, sigma in nm, place in the
+        flattened sequence) each; returns the accepted flags, [n_moves][R_local] of 0 / 1."""
+        if not hasattr(self.lib, 'remd_mc_rigid_moves'):
+            raise NotImplementedError('remd_mc_rigid_moves: this build of the engine library has no Monte Carlo moves on the device '
+                                      '(include/remd_hip_mcmoves.h is GPU-only)')
+        arr = (RemdMcMoveDesc * max(1, len(moves)))()
+        keep = []
+        for k, (kind, atoms, sigma, position) in enumerate(moves):
+            a = np.ascontiguousarray(atoms, dtype=np.int32).reshape(-1)
+            keep.append(a)
+            arr[k].kind, arr[k].n_atoms, arr[k].atoms = int(kind), len(a), a.ctypes.data_as(c_int32_p)
+            arr[k].sigma_nm, arr[k].position = float(sigma), int(position)
+        accepted = np.zeros((max(1, len(moves)), max(1, self.R)), dtype=np.int32)     # (never empty: the library names what it refuses)
+        self._check(self.lib.remd_mc_rigid_moves(self.h, arr, len(moves), int(iteration), accepted.ctypes.data_as(c_int32_p)),
+                    'remd_mc_rigid_moves')
+        return accepted[:len(moves), :self.R]
 
     def barostat_stats(self):
         vs = np.zeros(self.R); na = np.zeros(self.R, np.int64); nc = np.zeros(self.R, np.int64)

@@ -1,6 +1,7 @@
 // C ABI of libremd_hip.so (see include/remd_hip.h for the contract and reference citations).
 #include <chrono>
 #include "remd_internal.h"
+#include "../../include/remd_hip_mcmoves.h"
 #include "coulomb_table.h"
 #include <cstring>
 #include <cmath>
@@ -980,6 +981,21 @@ int remd_barostat_attempts(remd_handle h, int n_attempts)
     }
     REMD_CHECK(h, hipStreamSynchronize(h->stream));
     return remd_check_device_flags(h, "remd_barostat_attempts");
+}
+
+// include/remd_hip_mcmoves.h
+int remd_mc_rigid_moves(remd_handle h, const remd_mc_move_desc* moves, int32_t n_moves, int64_t iteration, int32_t* accepted)
+{
+    if (!h) return -1;
+    if (!h->has_system || h->K <= 0 || h->R <= 0 || !h->d_pos) return remd_fail(h, -1, "remd_mc_rigid_moves: replicas not set");
+    if (!moves || !accepted) return remd_fail(h, -1, "remd_mc_rigid_moves: bad arguments");
+    hipSetDevice(h->device);
+    int rc = remd_mc_moves_enqueue(h, moves, n_moves, iteration);
+    if (rc) return rc;
+    static_assert(sizeof(int) == sizeof(int32_t), "accepted flags are copied as they are");
+    REMD_CHECK(h, hipMemcpyAsync(accepted, h->d_mc_acc, sizeof(int32_t) * (size_t)n_moves * h->R, hipMemcpyDeviceToHost, h->stream));
+    REMD_CHECK(h, hipStreamSynchronize(h->stream));
+    return remd_check_device_flags(h, "remd_mc_rigid_moves");
 }
 
 int remd_get_barostat_stats(remd_handle h, double* volume_scale, int64_t* n_attempted, int64_t* n_accepted)

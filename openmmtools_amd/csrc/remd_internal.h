@@ -310,6 +310,9 @@ struct remd_ctx {
     dev_array<double> d_tension;       // [K] kJ/mol/nm^2 (membrane kind)
     dev_array<double> d_baro_axis;     // [R][REMD_BARO_AXIS_STRIDE]: see barostat.hip
     dev_array<float> d_box_old; dev_array<float4> d_baro_x0; dev_array<long long> d_baro_f0; dev_array<double> d_baro_U0; dev_array<int> d_baro_acc;
+    // rigid-body Monte Carlo moves (include/remd_hip_mcmoves.h; mc_moves.hip): the subsets of the last call, one after the other, and
+    // the accepted flags [REMD_MC_MAX_MOVES][R]; the copies a rejection restores from are the barostat's (d_baro_x0, d_baro_f0, d_baro_U0)
+    std::vector<int> mc_atoms_host; dev_array<int> d_mc_atoms; dev_array<int> d_mc_acc;
     bool box_uniform = false;          // every local replica has the same box (set_replicas; a barostat move clears it)
     int box_version = 0;               // bumped whenever the box edges on the device change (PME influence table)
     int n_restart_attempts = 0;        // mcmc.py:706-759
@@ -471,6 +474,8 @@ int remd_minimize_impl(remd_ctx* h, double tolerance, int max_iterations, int32_
 int remd_barostat_attempt(remd_ctx* h);                      // barostat.hip
 int remd_barostat_buffers(remd_ctx* h);                      // (its per-replica state and scratch, allocated on first use)
 #define REMD_BARO_AXIS_STRIDE 24
+struct remd_mc_move_desc;
+int remd_mc_moves_enqueue(remd_ctx* h, const remd_mc_move_desc* moves, int n_moves, int64_t iteration);   // mc_moves.hip: checked, then enqueued; flags in d_mc_acc
 int remd_tension_ukl(remd_ctx* h, double* d_rows);           // membrane barostat: - beta_l gamma_l A_xy(r) into the u_kl rows
 int remd_nb_molecules(remd_ctx* h, const int** first, const int** size);   // molecule table of the nonbonded setup (device); 0: none
 void remd_nb_invalidate_sort(remd_ctx* h);            // the next force evaluation re-sorts the molecules

@@ -381,12 +381,33 @@ class MetropolizedMove(MCMCMove):
     """mcmc.py:810-975: propose new positions for a subset of atoms, accept with min(1, exp(-delta u)) on the reduced potential
     of the replica's own state, restore otherwise.  The reference pushes one replica through a Context twice; the sampler
     here does it for all local replicas at once (positions of every replica proposed on the host, two batched energy
-    evaluations on the device; multistatesampler._apply_metropolized_move).  Subclasses implement ``_propose_positions``."""
+    evaluations on the device; multistatesampler._apply_metropolized_move).  Subclasses implement ``_propose_positions``.
 
-    def __init__(self, atom_subset=None, **kwargs):
+    ``proposal='device'`` keeps the whole move on the engine (HipEngine.mc_rigid_moves, include/remd_hip_mcmoves.h): draws,
+    proposal, both evaluations, the decision and the restoring of rejected replicas, with one Philox stream per replica in place
+    of the numpy streams of the host path.  The device knows the displacement and the rotation of this module only.  The
+    attribute is an instance attribute only where it is not the default, so default moves pickle and store as they always did."""
+
+    proposal = 'host'
+
+    def __init__(self, atom_subset=None, proposal='host', **kwargs):
+        if proposal not in ('host', 'device'):
+            raise ValueError("proposal must be 'host' or 'device', got %r" % (proposal,))
         self.n_accepted = 0
         self.n_proposed = 0
         self.atom_subset = atom_subset
+        if proposal != 'host':
+            self.proposal = proposal
+
+    def device_description(self, n_particles):
+        """(kind, atom indices, sigma in nm) of this move for the engine: kind 0 displacement, 1 rotation.  A move whose proposal is
+        not one of the two built-in ones is refused by name."""
+        for kind, klass in enumerate((MCDisplacementMove, MCRotationMove)):
+            if isinstance(self, klass) and type(self)._propose_positions is klass._propose_positions:
+                atoms = np.arange(int(n_particles))[self._subset()]
+                return kind, np.ascontiguousarray(atoms, dtype=np.int32), float(getattr(self, 'displacement_sigma', 0.0))
+        raise NotImplementedError("%s: proposal='device' runs the proposals of MCDisplacementMove and MCRotationMove only; a move "
+                                  "with a _propose_positions of its own takes proposal='host'" % type(self).__name__)
 
     @property
     def statistics(self):

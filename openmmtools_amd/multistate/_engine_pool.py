@@ -193,6 +193,10 @@ class EnginePool:
     def barostat_attempts(self, n_attempts):
         self._on_groups(lambda eng: eng.barostat_attempts(n_attempts), True)
 
+    def mc_rigid_moves(self, moves, iteration):
+        raise NotImplementedError('EnginePool.mc_rigid_moves: Monte Carlo moves on the device (include/remd_hip_mcmoves.h) are '
+                                  "not available with more than one compatibility group; use proposal='host'")
+
     def minimize(self, tolerance=1.0, max_iterations=0):
         conv = np.zeros(self.R, dtype=np.int32)
         steps = 0

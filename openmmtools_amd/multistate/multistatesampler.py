@@ -575,7 +575,7 @@ class MultiStateSampler:
         if isinstance(m, mcmc.MetropolizedMove):
             sub = m.atom_subset
             sub = None if sub is None else ((sub.start, sub.stop, sub.step) if isinstance(sub, slice) else tuple(int(i) for i in sub))
-            return ('metropolized', type(m).__name__, sub, getattr(m, 'displacement_sigma', None))
+            return ('metropolized', type(m).__name__, sub, getattr(m, 'displacement_sigma', None), getattr(m, 'proposal', 'host'))
         if isinstance(m, mcmc.LangevinSplittingDynamicsMove):
             return ('langevin', m.timestep, m.collision_rate, m.n_steps, m.reassign_velocities, m.splitting,
                     getattr(m, 'measure_heat', False), getattr(m, 'measure_shadow_work', False))
@@ -997,7 +997,10 @@ class MultiStateSampler:
         self._engine.set_labels(self._replica_thermodynamic_states)
         program = self._engine_program()                           # SequenceMove: in order, once per iteration (mcmc.py:406-424)
         integrations = [m for m in program if isinstance(m, mcmc.LangevinSplittingDynamicsMove)]
+        device_run_end = -1
         for position, move in enumerate(program):
+            if position < device_run_end:                           # went to the engine with the moves in front of it
+                continue
             if isinstance(move, mcmc.MonteCarloBarostatMove):
                 if not getattr(self, '_npt', False):
                     raise RuntimeError('Requested a MonteCarloBarostat move' ' on a system at constant pressure')   # mcmc.py:1673-1676 (the reference's wording: it means a state without a barostat)
@@ -1005,7 +1008,15 @@ class MultiStateSampler:
                 self._sampler_states_stale = True
                 continue
             if isinstance(move, mcmc.MetropolizedMove):
-                self._apply_metropolized_move(position, move, it)
+                if getattr(move, 'proposal', 'host') == 'device':
+                    # the run of consecutive device moves that starts here: one engine call, one synchronisation
+                    device_run_end = position + 1
+                    while (device_run_end < len(program) and isinstance(program[device_run_end], mcmc.MetropolizedMove)
+                           and getattr(program[device_run_end], 'proposal', 'host') == 'device'):
+                        device_run_end += 1
+                    self._apply_device_metropolized_moves(position, program[position:device_run_end], it)
+                else:
+                    self._apply_metropolized_move(position, move, it)
                 self._sampler_states_stale = True
                 continue
             key = it
@@ -1068,6 +1079,28 @@ class MultiStateSampler:
         if not np.all(accept):
             proposed[~accept] = x[~accept]                                    # :897-898: restore the rejected replicas
             eng.set_replicas(self.n_replicas, self._r_begin, proposed, v, box, labels)
+
+    def _apply_device_metropolized_moves(self, first_position, moves, it):
+        """The moves at ``first_position ...`` of the flattened sequence, all with proposal='device', in one engine call
+        (HipEngine.mc_rigid_moves, include/remd_hip_mcmoves.h): nothing crosses to the host but the accepted flags, which are
+        credited to the move of the state each local replica was in, as the host path credits them."""
+        eng = self._engine
+        if not hasattr(eng, 'mc_rigid_moves'):
+            raise NotImplementedError("proposal='device' needs an engine with remd_mc_rigid_moves (include/remd_hip_mcmoves.h is "
+                                      "GPU-only); %s has none: use proposal='host'" % type(eng).__name__)
+        n_particles = self._thermodynamic_states[0].n_particles
+        described = [m.device_description(n_particles) + (first_position + k,) for k, m in enumerate(moves)]
+        local_states = None
+        max_moves = 16                                              # REMD_MC_MAX_MOVES per call
+        for lo in range(0, len(described), max_moves):
+            accepted = np.asarray(eng.mc_rigid_moves(described[lo:lo + max_moves], it))
+            if local_states is None:
+                local_states = np.asarray(self._replica_thermodynamic_states)[self._r_begin:self._r_begin + accepted.shape[1]]
+            for k in range(accepted.shape[0]):
+                for r, state in enumerate(local_states):
+                    mv = self._flatten(self._mcmc_moves[int(state)])[first_position + lo + k]
+                    mv.n_accepted += int(accepted[k, r])
+                    mv.n_proposed += 1
 
     def _credit_metropolized_steps(self, position, before, after):
         """mcmc.py:1478-1489: a GHMCMove accumulates the accepted / attempted steps of the integrations it drove.  The engine

@@ -57,6 +57,22 @@ def main():
         ss = states.SamplerState(hg.positions, box_vectors=hg.system.getDefaultPeriodicBoxVectors())
         s.create(ths, [ss] * 8)
         run('4 (1-GPU share): HostGuestExplicit, 8 replicas x 64 alchemical states, g-BAOAB 2 fs x 500', s, 3)
+    if '4mc' in which:
+        # config 4's share with YANK's move set for binding free energies: displacement and rotation of the guest (atoms 126 .. 155), then
+        # the dynamics; once with the proposals on the host, once on the device (mcmc.MetropolizedMove proposal=, csrc/mc_moves.hip)
+        hg = testsystems.HostGuestExplicit()
+        lam_e = np.concatenate([np.linspace(1.0, 0.0, 32), np.zeros(32)])
+        lam_s = np.concatenate([np.ones(32), np.linspace(1.0, 0.0, 32)])
+        ths = alchemical_states(hg.system, range(126, 156), lam_e, lam_s)
+        guest = list(range(126, 156))
+        for proposal in ('host', 'device'):
+            seq = mcmc.SequenceMove([mcmc.MCDisplacementMove(displacement_sigma=0.1 * unit.nanometer, atom_subset=guest, proposal=proposal),
+                                     mcmc.MCRotationMove(atom_subset=guest, proposal=proposal), move(2.0, 'V R R O R R V')])
+            s = SAMSSampler(mcmc_moves=seq, number_of_iterations=10 ** 9, engine=HipEngine(), seed=1)
+            ss = states.SamplerState(hg.positions, box_vectors=hg.system.getDefaultPeriodicBoxVectors())
+            s.create(ths, [ss] * 8)
+            run("4mc (1-GPU share, proposal='%s'): HostGuestExplicit, 8 replicas x 64 alchemical states, guest displacement + rotation, "
+                'g-BAOAB 2 fs x 500' % proposal, s, 3)
     if 'wca' in which:
         # a System whose only pair force is a CustomNonbondedForce (custom_expr.py kind 6, csrc/custom_nonbonded.hip): 24-replica parallel
         # tempering of testsystems.WCAFluid (216 particles, no NonbondedForce)
