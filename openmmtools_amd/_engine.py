@@ -127,6 +127,10 @@ BAROSTAT_ANISOTROPIC, BAROSTAT_MEMBRANE = 1, 2
 MBAR_EXPORTS = ['remd_mbar_create', 'remd_mbar_destroy', 'remd_mbar_log_denominator', 'remd_mbar_self_consistent', 'remd_mbar_newton_parts',
                 'remd_mbar_gram', 'remd_mbar_log_weights', 'remd_mbar_chunks', 'remd_mbar_last_ms']
 MBAR_MAX_STATES = 512
+# the GPU-only extension of include/remd_hip_timeseries.h (statistical inefficiencies of the suffixes of a timeseries), bound the same way
+TIMESERIES_EXPORTS = ['remd_timeseries_create', 'remd_timeseries_destroy', 'remd_timeseries_inefficiency', 'remd_timeseries_chunks',
+                      'remd_timeseries_last_ms']
+TIMESERIES_MAX_BATCH = 64
 # the GPU-only extension of include/remd_hip_vsites.h (virtual sites), bound the same way
 VSITE_EXPORTS = ['remd_set_virtual_sites']
 
@@ -295,6 +299,14 @@ def load_library(path=None):
         lib.remd_mbar_last_ms.argtypes = [vp, c_double_p]
         for name in MBAR_EXPORTS:
             getattr(lib, name).restype = None if name == 'remd_mbar_destroy' else C.c_int
+    if hasattr(lib, 'remd_timeseries_create'):            # include/remd_hip_timeseries.h (GPU-only, like the restraints)
+        lib.remd_timeseries_create.argtypes = [C.c_int, C.c_int64, c_double_p, C.POINTER(vp)]
+        lib.remd_timeseries_destroy.argtypes = [vp]
+        lib.remd_timeseries_inefficiency.argtypes = [vp, C.c_int32, c_int64_p, C.c_int, C.c_int, c_double_p, c_int32_p, c_int64_p]
+        lib.remd_timeseries_chunks.argtypes = [vp, c_int64_p]
+        lib.remd_timeseries_last_ms.argtypes = [vp, c_double_p]
+        for name in TIMESERIES_EXPORTS:
+            getattr(lib, name).restype = None if name == 'remd_timeseries_destroy' else C.c_int
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -493,6 +505,65 @@ class DeviceMBAR:
         """Device milliseconds of the kernels of the last pass."""
         ms = C.c_double()
         self._check(self.lib.remd_mbar_last_ms(self.h, C.byref(ms)), 'remd_mbar_last_ms')
+        return ms.value
+
+
+class DeviceTimeseries:
+    """One timeseries on the device (include/remd_hip_timeseries.h): A [N] is uploaded once; ``inefficiency`` is one call for any
+    number of time origins.  What the host keeps: the choice of the origins, n_effective and its maximum (multistate/analysis.py)."""
+
+    def __init__(self, A_n, device=0, lib_path=None):
+        self.lib = load_library(lib_path)
+        self.h = None
+        for name in TIMESERIES_EXPORTS:
+            if not hasattr(self.lib, name):
+                raise NotImplementedError('%s: this build of the engine library has no timeseries passes (include/remd_hip_timeseries.h is '
+                                          'GPU-only)' % name)
+        A = np.ascontiguousarray(A_n, dtype=np.float64)
+        if A.ndim != 1:
+            raise ValueError('A_n must be one timeseries [N]')
+        self.N = int(A.size)
+        h = C.c_void_p()
+        rc = self.lib.remd_timeseries_create(int(device), self.N, _dp(A), C.byref(h))
+        if rc != 0:
+            raise RuntimeError('remd_timeseries_create failed (%d): %s' % (rc, self.lib.remd_last_error(None).decode()))
+        self.h = h
+
+    def close(self):
+        if self.h is not None:
+            self.lib.remd_timeseries_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, name):
+        if rc != 0:
+            raise RuntimeError('%s failed (%d): %s' % (name, rc, self.lib.remd_last_error(None).decode()))
+
+    def inefficiency(self, origins, fast=False, mintime=3):
+        """(g [S], status [S], last_lag [S]) of the suffixes A[t:] for t in ``origins``: the statistical inefficiency as
+        analysis.statistical_inefficiency defines it; status 1 (and g NaN) where the suffix has no variance; the last lag summed."""
+        t = np.ascontiguousarray(origins, dtype=np.int64).reshape(-1)
+        S = int(t.size)
+        g, status, last = np.empty(S), np.empty(S, dtype=np.int32), np.empty(S, dtype=np.int64)
+        self._check(self.lib.remd_timeseries_inefficiency(self.h, S, _lp(t), int(bool(fast)), int(mintime), _dp(g), _ip(status), _lp(last)),
+                    'remd_timeseries_inefficiency')
+        return g, status, last
+
+    def chunk(self):
+        """Samples per workgroup: chunk c of every pass covers the samples [c * chunk, (c + 1) * chunk)."""
+        c = C.c_int64()
+        self._check(self.lib.remd_timeseries_chunks(self.h, C.byref(c)), 'remd_timeseries_chunks')
+        return c.value
+
+    def last_ms(self):
+        """Device milliseconds of the kernels of the last ``inefficiency``."""
+        ms = C.c_double()
+        self._check(self.lib.remd_timeseries_last_ms(self.h, C.byref(ms)), 'remd_timeseries_last_ms')
         return ms.value
 
 

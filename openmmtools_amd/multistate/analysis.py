@@ -7,7 +7,8 @@ published algorithms the analyzer relies on, in plain numpy:
 
 * ``statistical_inefficiency`` / ``subsample_correlated_data`` — pymbar.timeseries (Chodera et al., JCTC 3, 26 (2007);
   integrated autocorrelation time summed until the normalised fluctuation autocorrelation function first crosses zero,
-  ``mintime = 3``, optional ``fast`` increments);
+  ``mintime = 3``, optional ``fast`` increments); ``solver='device'`` runs the same lags and sums on the GPU for any number of time
+  origins at once (include/remd_hip_timeseries.h, csrc/timeseries.hip; ``analysis_kwargs={'timeseries_solver': 'device'}``);
 * ``get_equilibration_data_per_sample`` — openmmtools/multistate/utils.py:107-190 (automated equilibration detection of
   Chodera, JCTC 12, 1799 (2016) on at most ``max_subset`` time origins);
 * ``MBAR`` — Shirts & Chodera, J. Chem. Phys. 129, 124105 (2008): self-consistent / Newton solution of eq. 11 for the
@@ -29,14 +30,42 @@ import numpy as np
 
 
 # ---- timeseries ------------------------------------------------------------------------------------------------
-def statistical_inefficiency(A_n, fast=False, mintime=3):
-    """g = 1 + 2 tau of the stationary timeseries ``A_n`` (>= 1).  pymbar.timeseries.statistical_inefficiency."""
+_NO_VARIANCE = 'sample covariance is zero: cannot compute the statistical inefficiency'
+
+
+def _check_timeseries_solver(solver):
+    if solver not in ('numpy', 'device'):
+        raise ValueError("solver must be 'numpy' or 'device', not %r" % (solver,))
+
+
+def _device_inefficiencies(A_n, origins, fast, mintime, device, lib_path):
+    """g of the suffixes ``A_n[t:]`` for t in ``origins``, in ONE call of the device (include/remd_hip_timeseries.h); the ValueError
+    of the host loop where a suffix has no variance."""
+    from .._engine import DeviceTimeseries
+    ts = DeviceTimeseries(A_n, device=device, lib_path=lib_path)
+    try:
+        g, status, _ = ts.inefficiency(origins, fast=fast, mintime=mintime)
+    finally:
+        ts.close()
+    if status.any():
+        raise ValueError(_NO_VARIANCE)
+    return g
+
+
+def statistical_inefficiency(A_n, fast=False, mintime=3, solver='numpy', device=0, lib_path=None):
+    """g = 1 + 2 tau of the stationary timeseries ``A_n`` (>= 1).  pymbar.timeseries.statistical_inefficiency.
+
+    ``solver='numpy'`` (the default) runs the loop over the lags below; ``solver='device'`` runs the same lags, sums and stopping rule
+    on the GPU (csrc/timeseries.hip).  ``device`` and ``lib_path`` choose the GPU and the engine library of the device solver."""
+    _check_timeseries_solver(solver)
+    if solver == 'device':
+        return float(_device_inefficiencies(A_n, [0], fast, mintime, device, lib_path)[0])
     A = np.asarray(A_n, dtype=np.float64)
     N = A.size
     dA = A - A.mean()
     sigma2 = np.mean(dA * dA)
     if sigma2 == 0.0:
-        raise ValueError('sample covariance is zero: cannot compute the statistical inefficiency')
+        raise ValueError(_NO_VARIANCE)
     g = 1.0
     t, increment = 1, 1
     while t < N - 1:
@@ -80,11 +109,13 @@ def statistical_inefficiency_multiple(A_kn, fast=False, mintime=3):
     return max(g, 1.0)
 
 
-def subsample_correlated_data(A_t, g=None, fast=False, conservative=False):
-    """Indices of an (approximately) uncorrelated subset: every ``g``-th sample, rounded (pymbar.timeseries)."""
+def subsample_correlated_data(A_t, g=None, fast=False, conservative=False, solver='numpy', device=0, lib_path=None):
+    """Indices of an (approximately) uncorrelated subset: every ``g``-th sample, rounded (pymbar.timeseries).  ``solver``, ``device``
+    and ``lib_path`` are statistical_inefficiency's, used when ``g`` is None."""
+    _check_timeseries_solver(solver)
     T = len(A_t)
     if g is None:
-        g = statistical_inefficiency(A_t, fast=fast)
+        g = statistical_inefficiency(A_t, fast=fast, solver=solver, device=device, lib_path=lib_path)
     if conservative:
         stride = int(np.ceil(g))
         return list(range(0, T, stride))
@@ -97,8 +128,10 @@ def subsample_correlated_data(A_t, g=None, fast=False, conservative=False):
     return indices
 
 
-def get_equilibration_data_per_sample(timeseries_to_analyze, fast=True, max_subset=100):
-    """(i_t, g_i, n_effective_i) on at most ``max_subset`` evenly spaced time origins (multistate/utils.py:107-190)."""
+def get_equilibration_data_per_sample(timeseries_to_analyze, fast=True, max_subset=100, solver='numpy', device=0, lib_path=None):
+    """(i_t, g_i, n_effective_i) on at most ``max_subset`` evenly spaced time origins (multistate/utils.py:107-190).
+    ``solver='device'``: the statistical inefficiencies of all origins in one call of the GPU (csrc/timeseries.hip)."""
+    _check_timeseries_solver(solver)
     series = np.array(timeseries_to_analyze)
     time_size = series.size
     set_size = time_size - 1
@@ -113,20 +146,25 @@ def get_equilibration_data_per_sample(timeseries_to_analyze, fast=True, max_subs
     n_effective_i = np.ones([max_subset], np.float32)
     counter = np.arange(max_subset)
     i_t = np.floor(counter * time_size / max_subset).astype(int)
+    g_all = _device_inefficiencies(series, i_t, fast, 3, device, lib_path) if solver == 'device' else None
     for i, t in enumerate(i_t):
-        g_i[i] = statistical_inefficiency(series[t:], fast=fast)       # (:176-181: an error here is raised, not papered over)
+        if g_all is not None:
+            g_i[i] = g_all[i]
+        else:
+            g_i[i] = statistical_inefficiency(series[t:], fast=fast)   # (:176-181: an error here is raised, not papered over)
         n_effective_i[i] = (time_size - t + 1) / g_i[i]
     return i_t[1:], g_i[1:], n_effective_i[1:]                          # :190: the origin t = 0 is not a candidate
 
 
-def get_decorrelation_time(timeseries_to_analyze):
+def get_decorrelation_time(timeseries_to_analyze, solver='numpy', device=0, lib_path=None):
     """multistate/utils.py:98-104."""
-    return statistical_inefficiency(timeseries_to_analyze)
+    return statistical_inefficiency(timeseries_to_analyze, solver=solver, device=device, lib_path=lib_path)
 
 
-def get_equilibration_data(timeseries_to_analyze, fast=True, max_subset=1000):
+def get_equilibration_data(timeseries_to_analyze, fast=True, max_subset=1000, solver='numpy', device=0, lib_path=None):
     """multistate/utils.py:195-235 (kept by the reference for old callers): (n_equilibration, g_t, n_effective_max)."""
-    i_t, g_i, n_effective_i = get_equilibration_data_per_sample(timeseries_to_analyze, fast=fast, max_subset=max_subset)
+    i_t, g_i, n_effective_i = get_equilibration_data_per_sample(timeseries_to_analyze, fast=fast, max_subset=max_subset, solver=solver,
+                                                                device=device, lib_path=lib_path)
     i_max = n_effective_i.argmax()
     return i_t[i_max], g_i[i_max], n_effective_i.max()
 
@@ -510,6 +548,9 @@ class MultiStateSamplerAnalyzer:
         # who evaluates the restraint at the stored frames: 'numpy' (restraint_frames_numpy, no GPU) or 'device' (csrc/restraint_frames.hip)
         if self._kwargs.get('restraint_solver', 'numpy') not in ('numpy', 'device'):
             raise ValueError("analysis_kwargs['restraint_solver'] must be 'numpy' or 'device', not %r" % (self._kwargs['restraint_solver'],))
+        # who scans the effective-energy timeseries for the equilibration time: 'numpy' (the loop over the lags) or 'device' (csrc/timeseries.hip)
+        if self._kwargs.get('timeseries_solver', 'numpy') not in ('numpy', 'device'):
+            raise ValueError("analysis_kwargs['timeseries_solver'] must be 'numpy' or 'device', not %r" % (self._kwargs['timeseries_solver'],))
         self._equilibration_data = None
         self._mbar = None
         self._unbiased = None                   # (u_ln, N_l, initial_f_k) handed to MBAR
@@ -685,7 +726,9 @@ class MultiStateSamplerAnalyzer:
             t0_sams = self._sams_t0()                                     # :2068-2076: only the asymptotically optimal SAMS stage
             if t0_sams is not None:
                 t0 = max(t0, t0_sams)
-            i_t, g_i, n_effective_i = get_equilibration_data_per_sample(u_n[t0:], max_subset=self._max_subset)
+            i_t, g_i, n_effective_i = get_equilibration_data_per_sample(
+                u_n[t0:], max_subset=self._max_subset, solver=self._kwargs.get('timeseries_solver', 'numpy'),
+                device=self._kwargs.get('device', 0), lib_path=self._kwargs.get('lib_path'))
             n_eff = n_effective_i.max()
             i_max = n_effective_i.argmax()
             n_eq = int(i_t[i_max] + t0)
