@@ -45,6 +45,21 @@ int  remd_mbar_newton_parts(remd_mbar m, const double* f_k, double* W_sum, doubl
 /* gram[C][C] = W^T W over all K states (C = K), or with_observable != 0: C = 2K, column K + k = exp(ln W_nk + ln A_kn - log_cA_k)
    with the observable A = u - (min u - 1) and log_cA_k = ln sum_n W_nk A_kn, returned in log_cA[K] (or NULL).                     */
 int  remd_mbar_gram(remd_mbar m, const double* f_k, int with_observable, double* gram, double* log_cA);
+/* The Gram matrix over the K stored states, L perturbed states and I observables of this call: what perturbed free energies and
+   expectations with their uncertainties need (C = K + L + I columns, each a normalised weight of the N stored samples):
+     columns 0 .. K-1        W_nk = exp(f_k - u_kn - log_den_n), as in remd_mbar_gram
+     columns K .. K+L-1      exp(f_l - u_ln - log_den_n)  with  f_l = -ln sum_n exp(-u_ln - log_den_n)  (eq. 11), returned in f_l[L];
+                             a +inf in u_ln gives that sample the weight 0 in that state
+     columns K+L .. C-1      exp(ln W_n,s + ln A_in - log_cA_i)  with s = obs_state[i] a column below K + L and
+                             log_cA_i = ln sum_n W_ns A_in, returned in log_cA[I]; A_in is the observable already shifted above 0
+   u_ln[L][N] and A_in[I][N] (sample index fastest) are uploaded for the call and freed after it.  L or I may be 0 (its arrays NULL),
+   not both.  Refused: a negative count, C > 2 x REMD_MBAR_MAX_STATES, a NaN or -inf in u_ln, a perturbed state whose weights all
+   vanish, an obs_state outside 0 .. K+L-1, a non-positive or non-finite A_in.  The samples per workgroup are those
+   remd_mbar_chunks reports: the row chunk for f_l and log_cA, the Gram chunk of C columns for the matrix.                        */
+int  remd_mbar_augmented_gram(remd_mbar m, const double* f_k,
+                              int L, const double* u_ln,
+                              int I, const double* A_in, const int32_t* obs_state,
+                              double* f_l, double* log_cA, double* gram);
 /* log_W_nk[N][K] = f_k - u_kn - log_den_n, state index fastest                                                                   */
 int  remd_mbar_log_weights(remd_mbar m, const double* f_k, double* log_W_nk);
 /* the samples per workgroup of the column pass, the row pass and the Gram pass (C columns) of this problem, for tests and tools  */

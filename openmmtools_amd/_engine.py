@@ -127,6 +127,8 @@ BAROSTAT_ANISOTROPIC, BAROSTAT_MEMBRANE = 1, 2
 MBAR_EXPORTS = ['remd_mbar_create', 'remd_mbar_destroy', 'remd_mbar_log_denominator', 'remd_mbar_self_consistent', 'remd_mbar_newton_parts',
                 'remd_mbar_gram', 'remd_mbar_log_weights', 'remd_mbar_chunks', 'remd_mbar_last_ms']
 MBAR_MAX_STATES = 512
+# the augmented Gram matrix of the same header (perturbed states and observables): a library built before it lacks the entry point
+MBAR_AUGMENTED_EXPORTS = ['remd_mbar_augmented_gram']
 # the GPU-only extension of include/remd_hip_timeseries.h (statistical inefficiencies of the suffixes of a timeseries), bound the same way
 TIMESERIES_EXPORTS = ['remd_timeseries_create', 'remd_timeseries_destroy', 'remd_timeseries_inefficiency', 'remd_timeseries_chunks',
                       'remd_timeseries_last_ms']
@@ -299,6 +301,10 @@ def load_library(path=None):
         lib.remd_mbar_last_ms.argtypes = [vp, c_double_p]
         for name in MBAR_EXPORTS:
             getattr(lib, name).restype = None if name == 'remd_mbar_destroy' else C.c_int
+    if hasattr(lib, 'remd_mbar_augmented_gram'):
+        lib.remd_mbar_augmented_gram.argtypes = [vp, c_double_p, C.c_int, c_double_p, C.c_int, c_double_p, c_int32_p, c_double_p, c_double_p,
+                                                 c_double_p]
+        lib.remd_mbar_augmented_gram.restype = C.c_int
     if hasattr(lib, 'remd_timeseries_create'):            # include/remd_hip_timeseries.h (GPU-only, like the restraints)
         lib.remd_timeseries_create.argtypes = [C.c_int, C.c_int64, c_double_p, C.POINTER(vp)]
         lib.remd_timeseries_destroy.argtypes = [vp]
@@ -487,6 +493,33 @@ class DeviceMBAR:
         log_cA = np.empty(self.K) if with_observable else None
         self._check(self.lib.remd_mbar_gram(self.h, _dp(f), int(bool(with_observable)), _dp(g), _dp(log_cA)), 'remd_mbar_gram')
         return (g, log_cA) if with_observable else g
+
+    def augmented_gram(self, f_k, u_ln=None, A_in=None, obs_state=None):
+        """(f_l [L], log_cA [I], gram [C][C]) over the K stored states, the L perturbed states ``u_ln`` [L][N] and the I observables
+        ``A_in`` [I][N] (positive), observable i on the weights of column ``obs_state[i]`` < K + L; C = K + L + I.  Either of ``u_ln``
+        and ``A_in`` may be None.  NotImplementedError where the library lacks remd_mbar_augmented_gram."""
+        for name in MBAR_AUGMENTED_EXPORTS:
+            if not hasattr(self.lib, name):
+                raise NotImplementedError('%s: this build of the engine library has no augmented Gram pass (include/remd_hip_mbar.h '
+                                          'declares it)' % name)
+        f = self._f(f_k)
+        u = None if u_ln is None else np.ascontiguousarray(u_ln, dtype=np.float64)
+        A = None if A_in is None else np.ascontiguousarray(A_in, dtype=np.float64)
+        for a, what in ((u, 'u_ln'), (A, 'A_in')):
+            if a is not None and (a.ndim != 2 or a.shape[1] != self.N):
+                raise ValueError('%s must be [.][N] with N = %d' % (what, self.N))
+        L = 0 if u is None else int(u.shape[0])
+        I = 0 if A is None else int(A.shape[0])
+        obs = None
+        if I:
+            obs = np.ascontiguousarray(obs_state, dtype=np.int32).reshape(-1)
+            if obs.shape != (I,):
+                raise ValueError('obs_state must name one column per observable')
+        c = self.K + L + I
+        f_l, log_cA, g = np.empty(L), np.empty(I), np.empty((c, c))
+        self._check(self.lib.remd_mbar_augmented_gram(self.h, _dp(f), L, _dp(u) if L else None, I, _dp(A) if I else None, _ip(obs),
+                                                      _dp(f_l) if L else None, _dp(log_cA) if I else None, _dp(g)), 'remd_mbar_augmented_gram')
+        return f_l, log_cA, g
 
     def log_weights(self, f_k):
         """log_W_nk [N][K] at f_k."""

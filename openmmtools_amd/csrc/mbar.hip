@@ -5,6 +5,8 @@
 //   Gram pass    workgroups per (64 x 64 tile of the lower triangle, chunk of samples): the weights are recomputed from u, f and
 //                log_den into LDS, 16 samples at a time, and accumulated in a 4 x 4 register tile per thread with plain f64 FMAs;
 //                the per-chunk partials are summed in chunk order by a second stage
+//   augmented    remd_mbar_augmented_gram: the same three passes over K stored states + L perturbed states + I observables of one
+//                call (the row pass of eq. 11 on u_ln, a row pass for ln <A>, the Gram tiles over the K + L + I columns)
 //
 // No floating-point atomics: every sum has one fixed order, set by (K, N) alone.
 #include "remd_internal.h"
@@ -207,6 +209,104 @@ __global__ __launch_bounds__(MBAR_BLOCK) void mbar_gram_sum_kernel(const double*
     for (int c = 0; c < chunks; c++) s += partial[(int64_t)c * C * C + idx];
     gram[(int64_t)i * C + j] = s;
     gram[(int64_t)j * C + i] = s;
+}
+
+// ---- augmented columns (remd_mbar_augmented_gram) -------------------------------------------------------------------------------
+// Column c of the augmented set: c < K a stored state, K <= c < K + L a perturbed state of the call, beyond that observable
+// c - (K + L) on the weights of column obs_state[.].  States 0 .. K + L - 1 share f[K + L] (f_k, then f_l) and mbar_aug_row.
+struct mbar_aug_args {
+    const double* u; const double* u_ln; const double* A; const double* log_den; const double* f; const double* log_cA;
+    const int* obs_state;        // [I]
+    const int2* tiles;           // (ti, tj), ti >= tj
+    int K, L, C;
+    int64_t N, chunk;
+    double* partial;             // [chunks][C][C], the lower triangle's tiles
+};
+
+__device__ __forceinline__ const double* mbar_aug_row(const double* __restrict__ u, const double* __restrict__ u_ln, int K, int64_t N, int s)
+{
+    return s < K ? u + (int64_t)s * N : u_ln + (int64_t)(s - K) * N;
+}
+
+// grid (chunks, I): pairs[i * chunks + c] = (max, sum exp(term - guarded max)) of  term = ln W_n,obs_state[i] + ln A_in
+__global__ __launch_bounds__(MBAR_BLOCK) void mbar_aug_logca_kernel(const double* __restrict__ u, const double* __restrict__ u_ln,
+                                                                    const double* __restrict__ A, const double* __restrict__ log_den,
+                                                                    const double* __restrict__ f, const int* __restrict__ obs_state,
+                                                                    int K, int64_t N, double2* __restrict__ pairs)
+{
+    __shared__ double sh[4];
+    const int i = blockIdx.y, s = obs_state[i];
+    const int64_t n0 = (int64_t)blockIdx.x * MBAR_ROW_CHUNK;
+    const int64_t n1 = n0 + MBAR_ROW_CHUNK < N ? n0 + MBAR_ROW_CHUNK : N;
+    const double* __restrict__ us = mbar_aug_row(u, u_ln, K, N, s);
+    const double* __restrict__ Ai = A + (int64_t)i * N;
+    const double fs = f[s];
+    double mt = -INFINITY;
+    for (int64_t n = n0 + threadIdx.x; n < n1; n += MBAR_BLOCK) mt = mbar_nanmax(mt, ((fs - us[n]) - log_den[n]) + log(Ai[n]));
+    const double mraw = mbar_block_nanmax(mt, sh);
+    const double m = mbar_guard(mraw);
+    double sum = 0.0;
+    for (int64_t n = n0 + threadIdx.x; n < n1; n += MBAR_BLOCK) sum += exp((((fs - us[n]) - log_den[n]) + log(Ai[n])) - m);
+    const double t = mbar_block_sum(sum, sh);
+    if (threadIdx.x == 0) pairs[(int64_t)i * gridDim.x + blockIdx.x] = make_double2(mraw, t);
+}
+
+__device__ __forceinline__ double mbar_aug_column_value(const mbar_aug_args& a, int c, int64_t n, int64_t n1, double ld)
+{
+    if (c >= a.C || n >= n1) return 0.0;
+    const int i = c - (a.K + a.L);
+    const int s = i < 0 ? c : a.obs_state[i];
+    double lw = (a.f[s] - mbar_aug_row(a.u, a.u_ln, a.K, a.N, s)[n]) - ld;
+    if (i >= 0) lw = (lw + log(a.A[(int64_t)i * a.N + n])) - a.log_cA[i];
+    return exp(lw);
+}
+
+// mbar_gram_kernel's tiles, staging and 4 x 4 register tile over the augmented columns
+__global__ __launch_bounds__(MBAR_BLOCK) void mbar_aug_gram_kernel(mbar_aug_args a)
+{
+    __shared__ double As[MBAR_TSTEP][MBAR_LDS_STRIDE];
+    __shared__ double Bs[MBAR_TSTEP][MBAR_LDS_STRIDE];
+    const int2 tile = a.tiles[blockIdx.x];
+    const int i0 = tile.x * MBAR_TILE, j0 = tile.y * MBAR_TILE;
+    const int64_t n0 = (int64_t)blockIdx.y * a.chunk;
+    const int64_t n1 = n0 + a.chunk < a.N ? n0 + a.chunk : a.N;
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const int fs = t & (MBAR_TSTEP - 1), fc = t >> 4;
+    const bool diagonal = i0 == j0;
+    const double (*Bp)[MBAR_LDS_STRIDE] = diagonal ? As : Bs;
+    double acc[4][4];
+    for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) acc[i][j] = 0.0;
+    for (int64_t nb = n0; nb < n1; nb += MBAR_TSTEP) {
+        const int64_t n = nb + fs;
+        const double ld = n < n1 ? a.log_den[n] : 0.0;
+        #pragma unroll
+        for (int p = 0; p < 4; p++) {
+            const int cl = fc + 16 * p;
+            As[fs][cl] = mbar_aug_column_value(a, i0 + cl, n, n1, ld);
+            if (!diagonal) Bs[fs][cl] = mbar_aug_column_value(a, j0 + cl, n, n1, ld);
+        }
+        __syncthreads();
+        #pragma unroll
+        for (int s = 0; s < MBAR_TSTEP; s++) {
+            double av[4], bv[4];
+            #pragma unroll
+            for (int i = 0; i < 4; i++) { av[i] = As[s][ty * 4 + i]; bv[i] = Bp[s][tx * 4 + i]; }
+            #pragma unroll
+            for (int i = 0; i < 4; i++)
+                #pragma unroll
+                for (int j = 0; j < 4; j++) acc[i][j] = fma(av[i], bv[j], acc[i][j]);
+        }
+        __syncthreads();
+    }
+    double* out = a.partial + (int64_t)blockIdx.y * a.C * a.C;
+    for (int i = 0; i < 4; i++) {
+        const int gi = i0 + ty * 4 + i;
+        if (gi >= a.C) continue;
+        for (int j = 0; j < 4; j++) {
+            const int gj = j0 + tx * 4 + j;
+            if (gj < a.C) out[(int64_t)gi * a.C + gj] = acc[i][j];
+        }
+    }
 }
 
 // ---- weights --------------------------------------------------------------------------------------------------------------------
@@ -469,6 +569,103 @@ int remd_mbar_gram(remd_mbar m, const double* f_k, int with_observable, double* 
     REMD_TRY(mbar_end(m));
     MBAR_CHECK(hipMemcpy(gram, m->gram, sizeof(double) * (size_t)C * C, hipMemcpyDeviceToHost));
     if (with_observable && log_cA) MBAR_CHECK(hipMemcpy(log_cA, m->log_cA, sizeof(double) * K, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int remd_mbar_augmented_gram(remd_mbar m, const double* f_k, int L, const double* u_ln, int I, const double* A_in, const int32_t* obs_state,
+                             double* f_l, double* log_cA, double* gram)
+{
+    const std::string who = "remd_mbar_augmented_gram";
+    if (!m) return remd_fail(nullptr, -1, who + ": the problem is NULL");
+    if (L < 0 || I < 0) return remd_fail(nullptr, -1, who + ": L = " + std::to_string(L) + " or I = " + std::to_string(I) + " is negative");
+    if (L == 0 && I == 0) return remd_fail(nullptr, -1, who + ": L and I are both 0 (remd_mbar_gram gives the plain Gram matrix)");
+    const int K = m->K;
+    const int64_t N = m->N, C64 = (int64_t)K + L + I;
+    if (C64 > 2 * REMD_MBAR_MAX_STATES)
+        return remd_fail(nullptr, -1, who + ": C = K + L + I = " + std::to_string(C64) + " exceeds 2 x REMD_MBAR_MAX_STATES = " + std::to_string(2 * REMD_MBAR_MAX_STATES));
+    const int C = (int)C64;
+    if ((L > 0 && (!u_ln || !f_l)) || (I > 0 && (!A_in || !obs_state || !log_cA)))
+        return remd_fail(nullptr, -1, who + ": an array of a non-zero count is NULL");
+    for (int l = 0; l < L; l++)
+        for (int64_t n = 0; n < N; n++) {
+            const double v = u_ln[(int64_t)l * N + n];
+            if (v != v || v == -std::numeric_limits<double>::infinity())
+                return remd_fail(nullptr, -1, who + ": u_ln of perturbed state " + std::to_string(l) + " holds a NaN or -inf");
+        }
+    for (int i = 0; i < I; i++) {
+        if (obs_state[i] < 0 || obs_state[i] >= K + L)
+            return remd_fail(nullptr, -1, who + ": obs_state[" + std::to_string(i) + "] = " + std::to_string(obs_state[i]) + " is outside 0 ... " + std::to_string(K + L - 1));
+        for (int64_t n = 0; n < N; n++) {
+            const double v = A_in[(int64_t)i * N + n];
+            if (!(v > 0.0) || !std::isfinite(v))
+                return remd_fail(nullptr, -1, who + ": A_in of observable " + std::to_string(i) + " holds a non-positive or non-finite value");
+        }
+    }
+    if (!f_k) return remd_fail(nullptr, -1, who + ": f_k is NULL");
+    if (!gram) return remd_fail(nullptr, -1, who + ": an output array is NULL");
+    MBAR_CHECK(hipSetDevice(m->device));
+    // the arrays of this call: freed when it returns
+    const int row_chunks = (int)((N + MBAR_ROW_CHUNK - 1) / MBAR_ROW_CHUNK);
+    dev_array<double> d_u_ln, d_A, d_f, d_log_cA;
+    dev_array<int> d_obs;
+    dev_array<double2> d_pairs;
+    REMD_TRY(d_u_ln.alloc(nullptr, (size_t)L * N));
+    REMD_TRY(d_A.alloc(nullptr, (size_t)I * N));
+    REMD_TRY(d_f.alloc(nullptr, (size_t)K + L));
+    REMD_TRY(d_log_cA.alloc(nullptr, (size_t)I));
+    REMD_TRY(d_obs.alloc(nullptr, (size_t)I));
+    REMD_TRY(d_pairs.alloc(nullptr, (size_t)std::max(L, I) * row_chunks));
+    if (L) MBAR_CHECK(hipMemcpy(d_u_ln, u_ln, sizeof(double) * (size_t)L * N, hipMemcpyHostToDevice));
+    if (I) MBAR_CHECK(hipMemcpy(d_A, A_in, sizeof(double) * (size_t)I * N, hipMemcpyHostToDevice));
+    if (I) MBAR_CHECK(hipMemcpy(d_obs, obs_state, sizeof(int) * (size_t)I, hipMemcpyHostToDevice));
+    MBAR_CHECK(hipMemset(d_f, 0, sizeof(double) * ((size_t)K + L)));
+    MBAR_CHECK(hipMemcpy(d_f, f_k, sizeof(double) * K, hipMemcpyHostToDevice));
+    REMD_TRY(mbar_begin(m, who.c_str(), f_k));
+    REMD_TRY(mbar_column_pass(m));
+    std::vector<double> fl(L);
+    if (L) {                                                 // eq. 11 on the rows of u_ln, into f[K ...]
+        hipLaunchKernelGGL(mbar_row_kernel<MBAR_ROW_SC>, dim3((unsigned)row_chunks, (unsigned)L), dim3(MBAR_BLOCK), 0, m->stream, d_u_ln.get(),
+                           m->log_den.get(), d_f.get(), N, 0.0, d_pairs.get());
+        hipLaunchKernelGGL(mbar_row_merge_kernel, dim3((unsigned)((L + 63) / 64)), dim3(64), 0, m->stream, d_pairs.get(), L, row_chunks, 1, -1.0,
+                           d_f.get() + K);
+        MBAR_CHECK(hipGetLastError());
+        MBAR_CHECK(hipMemcpyAsync(fl.data(), d_f.get() + K, sizeof(double) * L, hipMemcpyDeviceToHost, m->stream));
+        MBAR_CHECK(hipStreamSynchronize(m->stream));
+        for (int l = 0; l < L; l++)
+            if (!std::isfinite(fl[l])) {
+                REMD_TRY(mbar_end(m));                       // (remd_mbar_last_ms then reports the passes this call did run)
+                return remd_fail(nullptr, -1, who + ": perturbed state " + std::to_string(l) + " has no sample with a non-zero weight");
+            }
+    }
+    if (I) {
+        hipLaunchKernelGGL(mbar_aug_logca_kernel, dim3((unsigned)row_chunks, (unsigned)I), dim3(MBAR_BLOCK), 0, m->stream, m->u.get(), d_u_ln.get(),
+                           d_A.get(), m->log_den.get(), d_f.get(), d_obs.get(), K, N, d_pairs.get());
+        hipLaunchKernelGGL(mbar_row_merge_kernel, dim3((unsigned)((I + 63) / 64)), dim3(64), 0, m->stream, d_pairs.get(), I, row_chunks, 1, 1.0,
+                           d_log_cA.get());
+        MBAR_CHECK(hipGetLastError());
+    }
+    const int T = (C + MBAR_TILE - 1) / MBAR_TILE;
+    std::vector<int2> tiles;
+    for (int ti = 0; ti < T; ti++) for (int tj = 0; tj <= ti; tj++) tiles.push_back(make_int2(ti, tj));
+    const int64_t chunk = mbar_gram_chunk(N, C);
+    const int chunks = (int)((N + chunk - 1) / chunk);
+    REMD_TRY(m->tiles.grow(nullptr, tiles.size()));
+    REMD_TRY(m->gram.grow(nullptr, (size_t)C * C));
+    REMD_TRY(m->gram_partial.grow(nullptr, (size_t)chunks * C * C));
+    MBAR_CHECK(hipMemcpyAsync(m->tiles, tiles.data(), sizeof(int2) * tiles.size(), hipMemcpyHostToDevice, m->stream));
+    MBAR_CHECK(hipStreamSynchronize(m->stream));            // (the source is a local)
+    mbar_aug_args a;
+    a.u = m->u; a.u_ln = d_u_ln; a.A = d_A; a.log_den = m->log_den; a.f = d_f; a.log_cA = d_log_cA; a.obs_state = d_obs; a.tiles = m->tiles;
+    a.K = K; a.L = L; a.C = C; a.N = N; a.chunk = chunk; a.partial = m->gram_partial;
+    hipLaunchKernelGGL(mbar_aug_gram_kernel, dim3((unsigned)tiles.size(), (unsigned)chunks), dim3(MBAR_BLOCK), 0, m->stream, a);
+    const int64_t entries = (int64_t)C * C;
+    hipLaunchKernelGGL(mbar_gram_sum_kernel, dim3((unsigned)((entries + MBAR_BLOCK - 1) / MBAR_BLOCK)), dim3(MBAR_BLOCK), 0, m->stream,
+                       m->gram_partial.get(), C, chunks, m->gram.get());
+    MBAR_CHECK(hipGetLastError());
+    REMD_TRY(mbar_end(m));
+    MBAR_CHECK(hipMemcpy(gram, m->gram, sizeof(double) * (size_t)C * C, hipMemcpyDeviceToHost));
+    for (int l = 0; l < L; l++) f_l[l] = fl[l];
+    if (I) MBAR_CHECK(hipMemcpy(log_cA, d_log_cA, sizeof(double) * I, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -301,6 +301,13 @@ class MBAR:
     ``solver='numpy'`` (the default) does every pass over ``u_kn`` on the host; ``solver='device'`` does them on the GPU
     (include/remd_hip_mbar.h: the same sweeps, Newton iteration, backtracking rule and convergence test, with the K x K algebra
     still on the host).  ``device`` and ``lib_path`` choose the GPU and the engine library of the device solver.
+
+    ``compute_perturbed_free_energies``, ``compute_expectations``, ``compute_multiple_expectations``, ``compute_overlap`` and
+    ``compute_effective_sample_number`` take pymbar 4's argument order and defaults and return dicts with pymbar 4's keys.  Their
+    uncertainties use the same eq. 8 SVD form (``_theta_of_gram``) as ``compute_free_energy_differences`` and
+    ``compute_entropy_and_enthalpy``, on the Gram matrix of the weights augmented by one column per perturbed state and per
+    observable (N_k = 0 for those).  With ``solver='device'`` that matrix comes from one call of remd_mbar_augmented_gram and the
+    ``[N][K]`` weights never leave the GPU.
     """
 
     def __init__(self, u_kn, N_k, initial_f_k=None, relative_tolerance=1.0e-12, maximum_iterations=10000, solver='numpy',
@@ -525,6 +532,153 @@ class MBAR:
             dDelta = np.sqrt(d2)                     # NaN where the estimate of the variance is negative (under-sampling)
         np.fill_diagonal(dDelta, 0.0)
         return Delta, dDelta
+
+    # ---- perturbed states, observables, overlap: one augmented Gram matrix each ------------------------------------
+    @staticmethod
+    def _sqrt_of_variance(v):
+        """sqrt with the rule of compute_free_energy_differences: |v| < 1e-14 is 0, a negative variance gives NaN"""
+        v = np.where(np.abs(v) < 1e-14, 0.0, v)
+        with np.errstate(invalid='ignore'):
+            return np.sqrt(v)
+
+    @classmethod
+    def _error_of_differences(cls, cov):
+        err = cls._sqrt_of_variance(np.diag(cov)[:, None] + np.diag(cov)[None, :] - 2.0 * cov)
+        np.fill_diagonal(err, 0.0)
+        return err
+
+    def _check_u_ln(self, u_ln, what='u_ln'):
+        """[L][N] reduced potentials of perturbed states: +inf is a sample of weight 0, -inf and NaN are refused, and so is a state
+        whose weights all vanish."""
+        u = np.array(u_ln, dtype=np.float64)
+        if u.ndim != 2 or u.shape[0] < 1 or u.shape[1] != self.N:
+            raise ParameterError('%s must be [L][N] with L >= 1 and N = %d samples' % (what, self.N))
+        if np.any(np.isnan(u)) or np.any(np.isneginf(u)):
+            raise ParameterError('%s holds a NaN or -inf: only +inf (a sample of weight 0) is allowed' % what)
+        empty = np.flatnonzero(np.all(np.isposinf(u), axis=1))
+        if empty.size:
+            raise ParameterError('state %d of %s has no sample with a non-zero weight' % (empty[0], what))
+        return u
+
+    def _check_observables(self, A, rows, what):
+        A = np.array(A, dtype=np.float64)
+        if A.shape != (rows, self.N):
+            raise ParameterError('%s must be [%d][N] with N = %d samples' % (what, rows, self.N))
+        if not np.all(np.isfinite(A)):
+            raise ParameterError('%s holds a non-finite value' % what)
+        return A
+
+    def _augmented_gram(self, u_ln=None, A_in=None, obs_state=None):
+        """(f_l [L], log_cA [I], G [C][C]): the Gram matrix of the weights of the K states, then of the L perturbed states ``u_ln``,
+        then of the I observables ``A_in`` (> 0), observable i weighted into column ``obs_state[i]`` < K + L:
+        exp(ln W_n,s + ln A_in - log_cA_i) with log_cA_i = ln sum_n W_ns A_in.  On the device: remd_mbar_augmented_gram."""
+        if self._dev is not None:
+            return self._dev.augmented_gram(self.f_k, u_ln, A_in, obs_state)
+        log_den = self._log_denominator(self.f_k)
+        log_W = self.log_W_nk.T                                               # [K][N]
+        f_l = np.zeros(0)
+        if u_ln is not None:
+            f_l = -_logsumexp(-u_ln - log_den[None, :], axis=1)
+            log_W = np.concatenate([log_W, (f_l[:, None] - u_ln) - log_den[None, :]], axis=0)
+        W, log_cA = np.exp(log_W), np.zeros(0)
+        if A_in is not None:
+            raw = log_W[np.asarray(obs_state, dtype=np.int64)] + np.log(A_in)
+            log_cA = _logsumexp(raw, axis=1)
+            W = np.concatenate([W, np.exp(raw - log_cA[:, None])], axis=0)
+        return f_l, log_cA, W @ W.T
+
+    def _observable_covariance(self, G, obs_state, cA, constant):
+        """Covariance of <A_i> = cA_i (+ shift): ln cA_i = f_s(i) - f_(column of observable i), so d cA_i = cA_i (df_s(i) - df_col(i));
+        an observable that is constant over the samples has no variance and no covariance, exactly."""
+        C, n_obs = G.shape[0], len(cA)
+        Theta = self._theta_of_gram(G, np.concatenate([self.N_k, np.zeros(C - self.K, dtype=np.int64)]))
+        J = np.zeros((n_obs, C))
+        rows = np.arange(n_obs)
+        J[rows, obs_state] = cA
+        J[rows, C - n_obs + rows] = -cA
+        J[constant] = 0.0
+        return J @ Theta @ J.T
+
+    def compute_perturbed_free_energies(self, u_ln):
+        """Free energy differences between L states that were not simulated, from the stored samples: ``u_ln[l, n]`` is the reduced
+        potential of sample n in new state l (+inf: the sample has weight 0 there).  f_l = -ln sum_n exp(-u_ln - log_den_n); the
+        uncertainties come from Theta over the K + L columns, the new ones with N_k = 0.  Returns a dict with Delta_f [L][L] and
+        dDelta_f [L][L]; Delta_f[i, j] = f_j - f_i.  ParameterError for a -inf or NaN entry and for a state whose weights all vanish."""
+        u_ln = self._check_u_ln(u_ln)
+        f_l, _, G = self._augmented_gram(u_ln=u_ln)
+        K = self.K
+        Theta = self._theta_of_gram(G, np.concatenate([self.N_k, np.zeros(len(f_l), dtype=np.int64)]))
+        return dict(Delta_f=f_l[None, :] - f_l[:, None], dDelta_f=self._error_of_differences(Theta[K:, K:]))
+
+    def compute_expectations(self, A_n, u_kn=None, output='averages', state_dependent=False):
+        """<A> at every state with its uncertainty.  ``A_n`` is [N], or [S][N] with ``state_dependent=True`` (row s is the observable
+        of state s).  ``u_kn=None``: the S = K states of the estimator; otherwise the S = L perturbed states ``u_kn`` [L][N].
+        ``output='averages'`` returns a dict with mu [S] and sigma [S]; ``'differences'`` one with mu [S][S] (mu_j - mu_i) and the
+        sigma [S][S] of those differences.  The observable is shifted by min(A) - 1 to be positive for the logarithm, as in
+        compute_entropy_and_enthalpy; a constant observable has sigma = 0."""
+        if output not in ('averages', 'differences'):
+            raise ParameterError("output must be 'averages' or 'differences', not %r" % (output,))
+        u_ln = None if u_kn is None else self._check_u_ln(u_kn, 'u_kn')
+        K = self.K
+        S = K if u_ln is None else u_ln.shape[0]
+        if state_dependent:
+            A = self._check_observables(A_n, S, 'A_n (state_dependent)')
+        else:
+            A = np.broadcast_to(self._check_observables(np.reshape(np.asarray(A_n, dtype=np.float64), (1, -1)), 1, 'A_n'), (S, self.N))
+        shift = A.min() - 1.0
+        obs_state = np.arange(S) + (0 if u_ln is None else K)
+        _, log_cA, G = self._augmented_gram(u_ln, np.ascontiguousarray(A - shift), obs_state)
+        cA = np.exp(log_cA)
+        constant = A.max(axis=1) == A.min(axis=1)
+        mu = np.where(constant, A[:, 0], cA + shift)                          # <c> = c, not c (1 + the rounding of sum_n W)
+        cov = self._observable_covariance(G, obs_state, cA, constant)
+        if output == 'averages':
+            return dict(mu=mu, sigma=self._sqrt_of_variance(np.diag(cov)))
+        return dict(mu=mu[None, :] - mu[:, None], sigma=self._error_of_differences(cov))
+
+    def compute_multiple_expectations(self, A_in, u_n, compute_covariance=False):
+        """<A_i> of I observables ``A_in`` [I][N] at the one state whose reduced potentials of the stored samples are ``u_n`` [N].
+        Returns a dict with mu [I] and sigma [I], and with ``compute_covariance`` also covariances [I][I].  Each observable is
+        shifted by its own minimum - 1."""
+        u_ln = self._check_u_ln(np.reshape(np.asarray(u_n, dtype=np.float64), (1, -1)), 'u_n')
+        A = np.asarray(A_in, dtype=np.float64)
+        if A.ndim != 2 or A.shape[0] < 1:
+            raise ParameterError('A_in must be [I][N] with I >= 1')
+        A = self._check_observables(A, A.shape[0], 'A_in')
+        shift = A.min(axis=1) - 1.0
+        obs_state = np.full(A.shape[0], self.K)
+        _, log_cA, G = self._augmented_gram(u_ln, A - shift[:, None], obs_state)
+        cA = np.exp(log_cA)
+        constant = A.max(axis=1) == A.min(axis=1)
+        cov = self._observable_covariance(G, obs_state, cA, constant)
+        out = dict(mu=np.where(constant, A[:, 0], cA + shift), sigma=self._sqrt_of_variance(np.diag(cov)))
+        if compute_covariance:
+            out['covariances'] = cov
+        return out
+
+    def _gram(self):
+        """W^T W [K][K] of the weights of the K states"""
+        if self._dev is not None:
+            return self._dev.gram(self.f_k)
+        W = np.exp(self.log_W_nk)
+        return W.T @ W
+
+    def compute_overlap(self):
+        """The overlap of the states: matrix = W^T W diag(N_k) [K][K] (row i: the probability that a sample weighted into state i
+        was drawn from state j; rows sum to 1), its eigenvalues sorted from greatest to least (the first is 1) and
+        scalar = 1 - the second eigenvalue (1 with a single state, where there is no second).  Returns a dict with scalar,
+        eigenvalues, matrix.  The eigenvalues are those of the symmetric sqrt(N) W^T W sqrt(N), which has the same spectrum."""
+        G = self._gram()
+        root = np.sqrt(self.N_k.astype(np.float64))
+        eigenvalues = np.linalg.eigvalsh(root[:, None] * G * root[None, :])[::-1]
+        second = eigenvalues[1] if eigenvalues.size > 1 else 0.0
+        return dict(scalar=1.0 - second, eigenvalues=eigenvalues, matrix=G * self.N_k[None, :].astype(np.float64))
+
+    def compute_effective_sample_number(self):
+        """Kish's effective number of samples of every state, 1 / sum_n W_nk^2 (pymbar returns the array itself; here, like the
+        other methods, a dict: n_eff [K])."""
+        with np.errstate(divide='ignore'):
+            return dict(n_eff=1.0 / np.diag(self._gram()))
 
 
 # ---- the analyzer pipeline (global neighbourhoods) --------------------------------------------------------------
