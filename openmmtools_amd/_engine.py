@@ -133,6 +133,11 @@ MBAR_AUGMENTED_EXPORTS = ['remd_mbar_augmented_gram']
 TIMESERIES_EXPORTS = ['remd_timeseries_create', 'remd_timeseries_destroy', 'remd_timeseries_inefficiency', 'remd_timeseries_chunks',
                       'remd_timeseries_last_ms']
 TIMESERIES_MAX_BATCH = 64
+# the GPU-only extension of include/remd_hip_energy_store.h (the stored energies and state indices of a run on the device), bound the same way
+ENERGY_STORE_EXPORTS = ['remd_energy_store_create', 'remd_energy_store_destroy', 'remd_energy_store_effective_energy',
+                        'remd_energy_store_gather_u_ln', 'remd_energy_store_transition_counts', 'remd_energy_store_chunks',
+                        'remd_energy_store_last_ms', 'remd_series_inefficiency_multiple', 'remd_series_inefficiency_multiple_batched']
+SERIES_MAX_BATCH = 64
 # the GPU-only extension of include/remd_hip_vsites.h (virtual sites), bound the same way
 VSITE_EXPORTS = ['remd_set_virtual_sites']
 
@@ -313,6 +318,21 @@ def load_library(path=None):
         lib.remd_timeseries_last_ms.argtypes = [vp, c_double_p]
         for name in TIMESERIES_EXPORTS:
             getattr(lib, name).restype = None if name == 'remd_timeseries_destroy' else C.c_int
+    if hasattr(lib, 'remd_energy_store_create'):          # include/remd_hip_energy_store.h (GPU-only, like the restraints)
+        lib.remd_energy_store_create.argtypes = [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, c_int32_p,
+                                                 C.POINTER(vp)]
+        lib.remd_energy_store_destroy.argtypes = [vp]
+        lib.remd_energy_store_effective_energy.argtypes = [vp, c_double_p, c_double_p, c_double_p]
+        lib.remd_energy_store_gather_u_ln.argtypes = [vp, C.c_int64, c_int64_p, c_double_p, c_int64_p]
+        lib.remd_energy_store_transition_counts.argtypes = [vp, C.c_int64, C.c_int64, c_int64_p]
+        lib.remd_energy_store_chunks.argtypes = [vp, c_int64_p, c_int64_p, c_int64_p, c_int32_p]
+        lib.remd_energy_store_last_ms.argtypes = [vp, c_double_p]
+        lib.remd_series_inefficiency_multiple.argtypes = [C.c_int, C.c_int32, C.c_int64, c_double_p, C.c_int, C.c_int, c_double_p, c_int32_p,
+                                                          c_int64_p]
+        lib.remd_series_inefficiency_multiple_batched.argtypes = [C.c_int, C.c_int32, C.c_int64, c_double_p, C.c_int, C.c_int, C.c_int32,
+                                                                  c_double_p, c_int32_p, c_int64_p, c_double_p, c_int64_p]
+        for name in ENERGY_STORE_EXPORTS:
+            getattr(lib, name).restype = None if name == 'remd_energy_store_destroy' else C.c_int
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -598,6 +618,120 @@ class DeviceTimeseries:
         ms = C.c_double()
         self._check(self.lib.remd_timeseries_last_ms(self.h, C.byref(ms)), 'remd_timeseries_last_ms')
         return ms.value
+
+
+def _require_energy_store(lib):
+    for name in ENERGY_STORE_EXPORTS:
+        if not hasattr(lib, name):
+            raise NotImplementedError('%s: this build of the engine library has no energy-store passes (include/remd_hip_energy_store.h '
+                                      'is GPU-only)' % name)
+
+
+class DeviceEnergyStore:
+    """The stored energies of a multistate run on the device (include/remd_hip_energy_store.h), in the reporter's own layouts:
+    energies [T][R][S], unsampled [T][R][U] (U 0 or 2; None for 0) and states [T][R] are uploaded once; the effective energies, the
+    u_ln / N_l of a selection and the transition counts are one call each."""
+
+    def __init__(self, energies, unsampled, states, device=0, lib_path=None):
+        self.lib = load_library(lib_path)
+        self.h = None
+        _require_energy_store(self.lib)
+        e = np.ascontiguousarray(energies, dtype=np.float64)
+        st = np.ascontiguousarray(states, dtype=np.int32)
+        if e.ndim != 3 or st.shape != e.shape[:2]:
+            raise ValueError('energies must be [T][R][S] and states [T][R]')
+        if not np.array_equal(st, np.asarray(states)):
+            raise ValueError('states must be integers that fit 32 bits')
+        self.T, self.R, self.S = (int(n) for n in e.shape)
+        u = None
+        if unsampled is not None and np.shape(unsampled)[-1] != 0:
+            u = np.ascontiguousarray(unsampled, dtype=np.float64)
+            if u.ndim != 3 or u.shape[:2] != e.shape[:2]:
+                raise ValueError('unsampled must be [T][R][U]')
+        self.U = 0 if u is None else int(u.shape[2])
+        h = C.c_void_p()
+        rc = self.lib.remd_energy_store_create(int(device), self.T, self.R, self.S, self.U, _dp(e), _dp(u), _ip(st), C.byref(h))
+        if rc != 0:
+            raise RuntimeError('remd_energy_store_create failed (%d): %s' % (rc, self.lib.remd_last_error(None).decode()))
+        self.h = h
+
+    def close(self):
+        if self.h is not None:
+            self.lib.remd_energy_store_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, name):
+        if rc != 0:
+            raise RuntimeError('%s failed (%d): %s' % (name, rc, self.lib.remd_last_error(None).decode()))
+
+    def effective_energy(self, log_weights=None, f_l=None):
+        """u_n [T]: the sum over the replicas of the energy in the state each occupies; with log_weights [T][S] and f_l [S] the
+        expanded-ensemble correction of SAMS on top (both or neither)."""
+        lw = None if log_weights is None else np.ascontiguousarray(log_weights, dtype=np.float64)
+        f = None if f_l is None else np.ascontiguousarray(f_l, dtype=np.float64)
+        if lw is not None and lw.shape != (self.T, self.S):
+            raise ValueError('log_weights must be [T][S]')
+        if f is not None and f.shape != (self.S,):
+            raise ValueError('f_l must be [S]')
+        u_n = np.empty(self.T)
+        self._check(self.lib.remd_energy_store_effective_energy(self.h, _dp(lw), _dp(f), _dp(u_n)), 'remd_energy_store_effective_energy')
+        return u_n
+
+    def gather_u_ln(self, iterations):
+        """(u_ln [U + S][R * n_sel], N_l [U + S]) of the selected iterations: column r * n_sel + j is (iterations[j], replica r)."""
+        it = np.ascontiguousarray(iterations, dtype=np.int64).reshape(-1)
+        n_sel = int(it.size)
+        u_ln = np.zeros([self.U + self.S, self.R * n_sel])
+        N_l = np.zeros([self.U + self.S], dtype=np.int64)
+        self._check(self.lib.remd_energy_store_gather_u_ln(self.h, n_sel, _lp(it), _dp(u_ln), _lp(N_l)), 'remd_energy_store_gather_u_ln')
+        return u_ln, N_l
+
+    def transition_counts(self, t_begin, t_end):
+        """n_ij [S][S]: the (iteration, replica) pairs with t_begin <= t < t_end - 1 that go from state i to state j."""
+        n_ij = np.zeros([self.S, self.S], dtype=np.int64)
+        self._check(self.lib.remd_energy_store_transition_counts(self.h, int(t_begin), int(t_end), _lp(n_ij)),
+                    'remd_energy_store_transition_counts')
+        return n_ij
+
+    def chunks(self):
+        """(iterations per workgroup of the effective-energy pass, tile edge of the gather, pairs per workgroup of the counting passes,
+        the most states the counting passes keep an LDS histogram for)."""
+        a, b, c, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int32()
+        self._check(self.lib.remd_energy_store_chunks(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)), 'remd_energy_store_chunks')
+        return a.value, b.value, c.value, d.value
+
+    def last_ms(self):
+        """Device milliseconds of the kernels of the last pass."""
+        ms = C.c_double()
+        self._check(self.lib.remd_energy_store_last_ms(self.h, C.byref(ms)), 'remd_energy_store_last_ms')
+        return ms.value
+
+
+def series_inefficiency_multiple(A_kn, fast=False, mintime=3, device=0, lib_path=None, first_batch=None):
+    """(g, status, last_lag, device ms, samples per workgroup) of K series of one length, A_kn [K][N], in one call of the device
+    (remd_series_inefficiency_multiple of include/remd_hip_energy_store.h); ``first_batch``: the lags of the first batch, for tests."""
+    lib = load_library(lib_path)
+    _require_energy_store(lib)
+    A = np.ascontiguousarray(A_kn, dtype=np.float64)
+    if A.ndim != 2:
+        raise ValueError('A_kn must be [K][N]')
+    K, N = (int(n) for n in A.shape)
+    g, status, last, ms, chunk = C.c_double(), C.c_int32(), C.c_int64(), C.c_double(), C.c_int64()
+    if first_batch is None:
+        rc = lib.remd_series_inefficiency_multiple(int(device), K, N, _dp(A), int(bool(fast)), int(mintime), C.byref(g), C.byref(status),
+                                                   C.byref(last))
+    else:
+        rc = lib.remd_series_inefficiency_multiple_batched(int(device), K, N, _dp(A), int(bool(fast)), int(mintime), int(first_batch),
+                                                           C.byref(g), C.byref(status), C.byref(last), C.byref(ms), C.byref(chunk))
+    if rc != 0:
+        raise RuntimeError('remd_series_inefficiency_multiple failed (%d): %s' % (rc, lib.remd_last_error(None).decode()))
+    return g.value, status.value, last.value, ms.value, chunk.value
 
 
 class HipEngine:

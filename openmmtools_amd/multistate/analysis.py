@@ -19,7 +19,9 @@ published algorithms the analyzer relies on, in plain numpy:
   receptor-ligand restraint (:1355-1408, :1556-1913): the restraint is re-evaluated at every stored, decorrelated frame, frames
   outside a cutoff are dropped and two end states without the restraint join the MBAR problem.  The frames are evaluated in one
   call, by ``restraint_frames_numpy`` or on the device (``analysis_kwargs={'restraint_solver': 'device'}``, csrc/restraint_frames.hip),
-  with the centroid convention the run was sampled with -- not the reference's, see DESIGN.md.
+  with the centroid convention the run was sampled with -- not the reference's, see DESIGN.md.  The walks over the stored energies
+  (effective energies, u_ln / N_l assembly, transition counts and the state walk's statistical inefficiency) run as numpy loops or on
+  the device (``analysis_kwargs={'assembly_solver': 'device'}``, include/remd_hip_energy_store.h, csrc/energy_store.hip).
 
 Parity: unpinned against pymbar itself (absent); pinned against the analytical free energies of harmonic oscillators,
 the reference's own acceptance test (tests/test_sampling.py:100-300), in tests/test_analysis_cpu.py.
@@ -79,10 +81,22 @@ def statistical_inefficiency(A_n, fast=False, mintime=3, solver='numpy', device=
     return max(g, 1.0)
 
 
-def statistical_inefficiency_multiple(A_kn, fast=False, mintime=3):
+def statistical_inefficiency_multiple(A_kn, fast=False, mintime=3, solver='numpy', device=0, lib_path=None):
     """One statistical inefficiency from several timeseries of the same observable (pymbar.timeseries): the fluctuation
-    autocorrelation function is averaged over the series before it is integrated."""
+    autocorrelation function is averaged over the series before it is integrated.
+
+    ``solver='device'`` runs the same lags, pooled sums and stopping rule on the GPU in one call (csrc/energy_store.hip); the series
+    must then have one common length."""
+    _check_timeseries_solver(solver)
     series = [np.asarray(a, dtype=np.float64) for a in A_kn]
+    if solver == 'device':
+        if len({a.size for a in series}) != 1 or any(a.ndim != 1 for a in series):
+            raise ValueError("solver='device' needs series of one common length (ragged series run with solver='numpy')")
+        from .._engine import series_inefficiency_multiple
+        g, status = series_inefficiency_multiple(np.stack(series), fast=fast, mintime=mintime, device=device, lib_path=lib_path)[:2]
+        if status:
+            raise ValueError(_NO_VARIANCE)
+        return g
     N_k = np.array([a.size for a in series])
     Nmax, N = int(N_k.max()), int(N_k.sum())
     mu = sum(a.sum() for a in series) / float(N)
@@ -705,6 +719,11 @@ class MultiStateSamplerAnalyzer:
         # who scans the effective-energy timeseries for the equilibration time: 'numpy' (the loop over the lags) or 'device' (csrc/timeseries.hip)
         if self._kwargs.get('timeseries_solver', 'numpy') not in ('numpy', 'device'):
             raise ValueError("analysis_kwargs['timeseries_solver'] must be 'numpy' or 'device', not %r" % (self._kwargs['timeseries_solver'],))
+        # who walks the stored energies (effective energies, u_ln / N_l assembly, transition counts and the state walk's statistical
+        # inefficiency): 'numpy' (the loops below) or 'device' (csrc/energy_store.hip)
+        if self._kwargs.get('assembly_solver', 'numpy') not in ('numpy', 'device'):
+            raise ValueError("analysis_kwargs['assembly_solver'] must be 'numpy' or 'device', not %r" % (self._kwargs['assembly_solver'],))
+        self._energy_store = None               # the DeviceEnergyStore of assembly_solver = 'device', made on first use
         self._equilibration_data = None
         self._mbar = None
         self._unbiased = None                   # (u_ln, N_l, initial_f_k) handed to MBAR
@@ -783,6 +802,31 @@ class MultiStateSamplerAnalyzer:
         self._unbiased = None
         self._radially_symmetric_restraint_data = None
         self._restraint_energies, self._restraint_distances = {}, {}
+        self._release_energy_store()
+
+    def _release_energy_store(self):
+        store, self._energy_store = getattr(self, '_energy_store', None), None
+        if store is not None:
+            store.close()
+
+    def __del__(self):
+        try:
+            self._release_energy_store()
+        except Exception:
+            pass
+
+    @property
+    def _assembles_on_device(self):
+        return self._kwargs.get('assembly_solver', 'numpy') == 'device'
+
+    def _device_energy_store(self):
+        """The stored energies and state indices on the device (include/remd_hip_energy_store.h): uploaded on first use from the
+        records ``_read_energies`` serves, in the reporter's own [iteration][replica][state] layout, and kept until ``clear()``."""
+        if self._energy_store is None:
+            from .._engine import DeviceEnergyStore
+            e, eu, _, states = self._read_records()
+            self._energy_store = DeviceEnergyStore(e, eu, states, device=self._kwargs.get('device', 0), lib_path=self._kwargs.get('lib_path'))
+        return self._energy_store
 
     @property
     def effective_length(self):
@@ -825,8 +869,9 @@ class MultiStateSamplerAnalyzer:
         self._sign = '-' if self._sign == '+' else '+'           # :1128-1134
         return self
 
-    def _read_energies(self):
-        """[replica, state, iteration] arrays like the reference's ``_read_energies`` (:1353-1412)."""
+    def _read_records(self):
+        """(sampled [iteration, replica, state], unsampled, neighborhoods, replica state indices [iteration, replica]): the
+        reporter's records up to the last good iteration and ``max_n_iterations``."""
         e, nb, eu = self._reporter.read_energies()
         states = self._reporter.read_replica_thermodynamic_states()
         # records beyond the last completely written iteration are stale (a resume from an earlier checkpoint leaves the
@@ -835,8 +880,11 @@ class MultiStateSamplerAnalyzer:
         n = e.shape[0] if last is None else min(e.shape[0], int(last) + 1)
         if self._max_n_iterations is not None:
             n = min(n, self._max_n_iterations + 1)
-        return (np.moveaxis(e[:n], 0, -1), np.moveaxis(eu[:n], 0, -1), np.moveaxis(nb[:n], 0, -1),
-                np.moveaxis(states[:n], 0, -1))
+        return e[:n], eu[:n], nb[:n], states[:n]
+
+    def _read_energies(self):
+        """[replica, state, iteration] arrays like the reference's ``_read_energies`` (:1353-1412)."""
+        return tuple(np.moveaxis(a, 0, -1) for a in self._read_records())
 
     @property
     def has_log_weights(self):
@@ -860,6 +908,11 @@ class MultiStateSamplerAnalyzer:
             if lw.shape[0] >= n_iterations:
                 log_weights = lw[:n_iterations].T
                 f_l = -self._reporter.read_online_analysis_data(None, 'logZ')['logZ']
+        if self._assembles_on_device:
+            store = self._device_energy_store()
+            if energies.shape != (store.R, store.S, store.T) or replica_state_indices.shape != (store.R, store.T):
+                raise ValueError("assembly_solver='device' answers from the stored energies: pass what _read_energies() returns")
+            return store.effective_energy(None if log_weights is None else log_weights.T, f_l)
         for it in range(n_iterations):
             states = replica_state_indices[:, it]
             u_n[it] = np.sum(energies[rep, states, it])
@@ -920,7 +973,9 @@ class MultiStateSamplerAnalyzer:
 
     def _compute_mbar_decorrelated_energies(self, selection=None):
         """(u_ln, N_l) with the unsampled states at the two end points (:1479-1545)."""
-        e, eu, states, _ = selection or self._decorrelated_selection()
+        e, eu, states, iterations = selection or self._decorrelated_selection()
+        if self._assembles_on_device:
+            return self._device_energy_store().gather_u_ln(iterations)
         n_replicas, n_sampled, n_it = e.shape
         n_uns = eu.shape[1]
         n_total = n_sampled + n_uns
@@ -1112,9 +1167,16 @@ class MultiStateSamplerAnalyzer:
             states = states[:self._max_n_iterations + 1]
         n_iter, n_replicas = states.shape
         n_states = int(self._reporter._meta['n_states'])
-        n_ij = np.zeros([n_states, n_states], np.int64)
-        for it in range(number_equilibrated, n_iter - 1):
-            np.add.at(n_ij, (states[it], states[it + 1]), 1)
+        if self._assembles_on_device:
+            store = self._device_energy_store()
+            if (n_iter, n_replicas, n_states) != (store.T, store.R, store.S):
+                raise ValueError("assembly_solver='device': the stored state indices are [%d][%d] over %d states, the energies on the "
+                                 'device [%d][%d] over %d' % (n_iter, n_replicas, n_states, store.T, store.R, store.S))
+            n_ij = store.transition_counts(min(max(int(number_equilibrated), 0), n_iter), n_iter)
+        else:
+            n_ij = np.zeros([n_states, n_states], np.int64)
+            for it in range(number_equilibrated, n_iter - 1):
+                np.add.at(n_ij, (states[it], states[it + 1]), 1)
         t_ij = np.zeros([n_states, n_states], np.float64)
         for i in range(n_states):
             den = float(n_ij[i, :].sum() + n_ij[:, i].sum())
@@ -1123,7 +1185,11 @@ class MultiStateSamplerAnalyzer:
             else:
                 t_ij[i, i] = 1.0
         mu = -np.sort(-np.linalg.eigvals(t_ij))
-        g = statistical_inefficiency_multiple(np.transpose(states[number_equilibrated:]))
+        if self._assembles_on_device:
+            g = statistical_inefficiency_multiple(np.transpose(states[number_equilibrated:]), solver='device',
+                                                  device=self._kwargs.get('device', 0), lib_path=self._kwargs.get('lib_path'))
+        else:
+            g = statistical_inefficiency_multiple(np.transpose(states[number_equilibrated:]))
         return self.MixingStatistics(transition_matrix=t_ij, eigenvalues=mu, statistical_inefficiency=g)
 
     def get_enthalpy(self):
