@@ -441,30 +441,30 @@ def restraint_frames_last_ms(lib_path=None):
     return ms.value
 
 
-class DeviceMBAR:
-    """One MBAR problem on the device (include/remd_hip_mbar.h): u_kn [K][N] and N_k are uploaded once; every method is one pass at
-    the f_k it is given.  The K x K algebra of the estimator stays with the caller (multistate/analysis.py::MBAR, solver='device')."""
+def _require_exports(lib, names, what):
+    for name in names:
+        if not hasattr(lib, name):
+            raise NotImplementedError('%s: this build of the engine library has no %s' % (name, what))
 
-    def __init__(self, u_kn, N_k, device=0, lib_path=None):
+
+class _DeviceObject:
+    """What the device objects without a HipEngine share: the library and the probe for their entry points, the handle ``h`` made by
+    remd_<PREFIX>_create and freed by remd_<PREFIX>_destroy, the check of a return code and the device time of the last call."""
+    PREFIX = EXPORTS_NEEDED = MISSING = None
+
+    def __init__(self, lib_path):
         self.lib = load_library(lib_path)
         self.h = None
-        for name in MBAR_EXPORTS:
-            if not hasattr(self.lib, name):
-                raise NotImplementedError('%s: this build of the engine library has no MBAR passes (include/remd_hip_mbar.h is GPU-only)' % name)
-        u = np.ascontiguousarray(u_kn, dtype=np.float64)
-        nk = np.ascontiguousarray(N_k, dtype=np.int64)
-        if u.ndim != 2 or nk.shape != (u.shape[0],):
-            raise ValueError('u_kn must be [K][N] and N_k [K]')
-        self.K, self.N = int(u.shape[0]), int(u.shape[1])
+        _require_exports(self.lib, self.EXPORTS_NEEDED, self.MISSING)
+
+    def _create(self, *args):
         h = C.c_void_p()
-        rc = self.lib.remd_mbar_create(int(device), self.K, self.N, _dp(u), _lp(nk), C.byref(h))
-        if rc != 0:
-            raise RuntimeError('remd_mbar_create failed (%d): %s' % (rc, self.lib.remd_last_error(None).decode()))
+        self._check(getattr(self.lib, 'remd_%s_create' % self.PREFIX)(*args, C.byref(h)), 'remd_%s_create' % self.PREFIX)
         self.h = h
 
     def close(self):
         if self.h is not None:
-            self.lib.remd_mbar_destroy(self.h)
+            getattr(self.lib, 'remd_%s_destroy' % self.PREFIX)(self.h)
             self.h = None
 
     def __del__(self):
@@ -476,6 +476,28 @@ class DeviceMBAR:
     def _check(self, rc, name):
         if rc != 0:
             raise RuntimeError('%s failed (%d): %s' % (name, rc, self.lib.remd_last_error(None).decode()))
+
+    def last_ms(self):
+        """Device milliseconds of the kernels of the last pass."""
+        ms = C.c_double()
+        self._check(getattr(self.lib, 'remd_%s_last_ms' % self.PREFIX)(self.h, C.byref(ms)), 'remd_%s_last_ms' % self.PREFIX)
+        return ms.value
+
+
+class DeviceMBAR(_DeviceObject):
+    """One MBAR problem on the device (include/remd_hip_mbar.h): u_kn [K][N] and N_k are uploaded once; every method is one pass at
+    the f_k it is given.  The K x K algebra of the estimator stays with the caller (multistate/analysis.py::MBAR, solver='device')."""
+
+    PREFIX, EXPORTS_NEEDED, MISSING = 'mbar', MBAR_EXPORTS, 'MBAR passes (include/remd_hip_mbar.h is GPU-only)'
+
+    def __init__(self, u_kn, N_k, device=0, lib_path=None):
+        super().__init__(lib_path)
+        u = np.ascontiguousarray(u_kn, dtype=np.float64)
+        nk = np.ascontiguousarray(N_k, dtype=np.int64)
+        if u.ndim != 2 or nk.shape != (u.shape[0],):
+            raise ValueError('u_kn must be [K][N] and N_k [K]')
+        self.K, self.N = int(u.shape[0]), int(u.shape[1])
+        self._create(int(device), self.K, self.N, _dp(u), _lp(nk))
 
     def _f(self, f_k):
         f = np.ascontiguousarray(f_k, dtype=np.float64)
@@ -518,10 +540,7 @@ class DeviceMBAR:
         """(f_l [L], log_cA [I], gram [C][C]) over the K stored states, the L perturbed states ``u_ln`` [L][N] and the I observables
         ``A_in`` [I][N] (positive), observable i on the weights of column ``obs_state[i]`` < K + L; C = K + L + I.  Either of ``u_ln``
         and ``A_in`` may be None.  NotImplementedError where the library lacks remd_mbar_augmented_gram."""
-        for name in MBAR_AUGMENTED_EXPORTS:
-            if not hasattr(self.lib, name):
-                raise NotImplementedError('%s: this build of the engine library has no augmented Gram pass (include/remd_hip_mbar.h '
-                                          'declares it)' % name)
+        _require_exports(self.lib, MBAR_AUGMENTED_EXPORTS, 'augmented Gram pass (include/remd_hip_mbar.h declares it)')
         f = self._f(f_k)
         u = None if u_ln is None else np.ascontiguousarray(u_ln, dtype=np.float64)
         A = None if A_in is None else np.ascontiguousarray(A_in, dtype=np.float64)
@@ -554,48 +573,20 @@ class DeviceMBAR:
         self._check(self.lib.remd_mbar_chunks(self.h, int(C_columns), C.byref(a), C.byref(b), C.byref(c)), 'remd_mbar_chunks')
         return a.value, b.value, c.value
 
-    def last_ms(self):
-        """Device milliseconds of the kernels of the last pass."""
-        ms = C.c_double()
-        self._check(self.lib.remd_mbar_last_ms(self.h, C.byref(ms)), 'remd_mbar_last_ms')
-        return ms.value
 
-
-class DeviceTimeseries:
+class DeviceTimeseries(_DeviceObject):
     """One timeseries on the device (include/remd_hip_timeseries.h): A [N] is uploaded once; ``inefficiency`` is one call for any
     number of time origins.  What the host keeps: the choice of the origins, n_effective and its maximum (multistate/analysis.py)."""
 
+    PREFIX, EXPORTS_NEEDED, MISSING = 'timeseries', TIMESERIES_EXPORTS, 'timeseries passes (include/remd_hip_timeseries.h is GPU-only)'
+
     def __init__(self, A_n, device=0, lib_path=None):
-        self.lib = load_library(lib_path)
-        self.h = None
-        for name in TIMESERIES_EXPORTS:
-            if not hasattr(self.lib, name):
-                raise NotImplementedError('%s: this build of the engine library has no timeseries passes (include/remd_hip_timeseries.h is '
-                                          'GPU-only)' % name)
+        super().__init__(lib_path)
         A = np.ascontiguousarray(A_n, dtype=np.float64)
         if A.ndim != 1:
             raise ValueError('A_n must be one timeseries [N]')
         self.N = int(A.size)
-        h = C.c_void_p()
-        rc = self.lib.remd_timeseries_create(int(device), self.N, _dp(A), C.byref(h))
-        if rc != 0:
-            raise RuntimeError('remd_timeseries_create failed (%d): %s' % (rc, self.lib.remd_last_error(None).decode()))
-        self.h = h
-
-    def close(self):
-        if self.h is not None:
-            self.lib.remd_timeseries_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, name):
-        if rc != 0:
-            raise RuntimeError('%s failed (%d): %s' % (name, rc, self.lib.remd_last_error(None).decode()))
+        self._create(int(device), self.N, _dp(A))
 
     def inefficiency(self, origins, fast=False, mintime=3):
         """(g [S], status [S], last_lag [S]) of the suffixes A[t:] for t in ``origins``: the statistical inefficiency as
@@ -613,29 +604,19 @@ class DeviceTimeseries:
         self._check(self.lib.remd_timeseries_chunks(self.h, C.byref(c)), 'remd_timeseries_chunks')
         return c.value
 
-    def last_ms(self):
-        """Device milliseconds of the kernels of the last ``inefficiency``."""
-        ms = C.c_double()
-        self._check(self.lib.remd_timeseries_last_ms(self.h, C.byref(ms)), 'remd_timeseries_last_ms')
-        return ms.value
+
+ENERGY_STORE_MISSING = 'energy-store passes (include/remd_hip_energy_store.h is GPU-only)'
 
 
-def _require_energy_store(lib):
-    for name in ENERGY_STORE_EXPORTS:
-        if not hasattr(lib, name):
-            raise NotImplementedError('%s: this build of the engine library has no energy-store passes (include/remd_hip_energy_store.h '
-                                      'is GPU-only)' % name)
-
-
-class DeviceEnergyStore:
+class DeviceEnergyStore(_DeviceObject):
     """The stored energies of a multistate run on the device (include/remd_hip_energy_store.h), in the reporter's own layouts:
     energies [T][R][S], unsampled [T][R][U] (U 0 or 2; None for 0) and states [T][R] are uploaded once; the effective energies, the
     u_ln / N_l of a selection and the transition counts are one call each."""
 
+    PREFIX, EXPORTS_NEEDED, MISSING = 'energy_store', ENERGY_STORE_EXPORTS, ENERGY_STORE_MISSING
+
     def __init__(self, energies, unsampled, states, device=0, lib_path=None):
-        self.lib = load_library(lib_path)
-        self.h = None
-        _require_energy_store(self.lib)
+        super().__init__(lib_path)
         e = np.ascontiguousarray(energies, dtype=np.float64)
         st = np.ascontiguousarray(states, dtype=np.int32)
         if e.ndim != 3 or st.shape != e.shape[:2]:
@@ -649,26 +630,7 @@ class DeviceEnergyStore:
             if u.ndim != 3 or u.shape[:2] != e.shape[:2]:
                 raise ValueError('unsampled must be [T][R][U]')
         self.U = 0 if u is None else int(u.shape[2])
-        h = C.c_void_p()
-        rc = self.lib.remd_energy_store_create(int(device), self.T, self.R, self.S, self.U, _dp(e), _dp(u), _ip(st), C.byref(h))
-        if rc != 0:
-            raise RuntimeError('remd_energy_store_create failed (%d): %s' % (rc, self.lib.remd_last_error(None).decode()))
-        self.h = h
-
-    def close(self):
-        if self.h is not None:
-            self.lib.remd_energy_store_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, name):
-        if rc != 0:
-            raise RuntimeError('%s failed (%d): %s' % (name, rc, self.lib.remd_last_error(None).decode()))
+        self._create(int(device), self.T, self.R, self.S, self.U, _dp(e), _dp(u), _ip(st))
 
     def effective_energy(self, log_weights=None, f_l=None):
         """u_n [T]: the sum over the replicas of the energy in the state each occupies; with log_weights [T][S] and f_l [S] the
@@ -706,18 +668,12 @@ class DeviceEnergyStore:
         self._check(self.lib.remd_energy_store_chunks(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)), 'remd_energy_store_chunks')
         return a.value, b.value, c.value, d.value
 
-    def last_ms(self):
-        """Device milliseconds of the kernels of the last pass."""
-        ms = C.c_double()
-        self._check(self.lib.remd_energy_store_last_ms(self.h, C.byref(ms)), 'remd_energy_store_last_ms')
-        return ms.value
-
 
 def series_inefficiency_multiple(A_kn, fast=False, mintime=3, device=0, lib_path=None, first_batch=None):
     """(g, status, last_lag, device ms, samples per workgroup) of K series of one length, A_kn [K][N], in one call of the device
     (remd_series_inefficiency_multiple of include/remd_hip_energy_store.h); ``first_batch``: the lags of the first batch, for tests."""
     lib = load_library(lib_path)
-    _require_energy_store(lib)
+    _require_exports(lib, ENERGY_STORE_EXPORTS, ENERGY_STORE_MISSING)
     A = np.ascontiguousarray(A_kn, dtype=np.float64)
     if A.ndim != 2:
         raise ValueError('A_kn must be [K][N]')

@@ -10,11 +10,11 @@
 //                      pairs; for S <= ES_HIST_MAX_S it counts them in a 32-bit LDS histogram (a cell holds at most ES_COUNT_CHUNK,
 //                      see the static_assert) and adds the cells that are not zero to the 64-bit result, above that it adds every
 //                      pair straight to the 64-bit result.
-//   several series     the passes of timeseries.hip for K series and one origin: sums per (series, chunk of ES_SERIES_CHUNK
-//                      samples), merged by one thread in the order (series, chunk); one thread walks the lags of a batch.
+//   several series     remd_series_inefficiency_multiple checks its arguments here; the passes are those of timeseries.hip, for K
+//                      series and the one origin 0 (series_inefficiency, defined there).
 //
 // No floating-point atomics anywhere.  Every index that can pass 2^31 is 64 bits wide.
-#include "remd_internal.h"
+#include "device_object.h"
 #include "../../include/remd_hip_energy_store.h"
 #include <cmath>
 #include <limits>
@@ -24,9 +24,7 @@
 #define ES_TILE_ROWS      8                       // blockDim.y of the gather: a thread moves ES_TILE / ES_TILE_ROWS words each way
 #define ES_COUNT_CHUNK    8192                    // (iteration, replica) pairs per workgroup of the counting passes
 #define ES_HIST_MAX_S     64                      // the LDS histogram of the transition counts has S x S cells: 16 KiB at 64
-#define ES_SERIES_CHUNK   2048                    // samples per workgroup of the series passes: 8 per thread
-#define ES_FIRST_BATCH    8
-#define ES_PARTIAL_CAP    (int64_t(1) << 22)      // doubles of per-chunk partials at most (32 MiB)
+#define ES_FIRST_BATCH    8                       // lags of the first batch of remd_series_inefficiency_multiple
 
 static_assert((uint64_t)ES_COUNT_CHUNK < (uint64_t(1) << 32), "a 32-bit LDS counter must hold every pair of a workgroup's chunk");
 static_assert(ES_HIST_MAX_S * ES_HIST_MAX_S * sizeof(uint32_t) <= 64 * 1024, "the LDS histogram must fit a workgroup's LDS");
@@ -145,176 +143,21 @@ __global__ __launch_bounds__(ES_BLOCK) void es_transition_kernel(const int32_t* 
     if (HIST) es_flush(hist, S * S, n_ij);
 }
 
-// ---- several series --------------------------------------------------------------------------------------------------------------
-// lanes by __shfl_down, then the four waves in wave order: one fixed order (as ts_block_sum of timeseries.hip)
-__device__ __forceinline__ double es_block_sum(double v, double* sh)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
-__device__ __forceinline__ int64_t es_lag(int64_t t0, int64_t inc0, int fast, int b)
-{
-    return fast ? t0 + (int64_t)b * inc0 + (int64_t)b * (b - 1) / 2 : t0 + b;
-}
-__device__ __forceinline__ int64_t es_increment(int64_t inc0, int fast, int b) { return fast ? inc0 + b : 1; }
-
-struct es_walk { double mu, sigma2, g; int64_t last; int done, status; };
-
-// grid (chunks, K): partial[k * chunks + c] = sum over chunk c of series k of A (SQUARED = 0) or (A - mu)^2 (SQUARED = 1)
-template <int SQUARED>
-__global__ __launch_bounds__(ES_BLOCK) void es_series_moment_kernel(const double* __restrict__ A, int64_t N, const es_walk* __restrict__ w,
-                                                                    double* __restrict__ partial)
-{
-    __shared__ double sh[4];
-    const int64_t n0 = (int64_t)blockIdx.x * ES_SERIES_CHUNK;
-    const int64_t hi = n0 + ES_SERIES_CHUNK < N ? n0 + ES_SERIES_CHUNK : N;
-    const double* a = A + (int64_t)blockIdx.y * N;
-    const double m = SQUARED ? w->mu : 0.0;
-    double acc = 0.0;
-    for (int64_t n = n0 + threadIdx.x; n < hi; n += ES_BLOCK) {
-        const double d = a[n] - m;
-        acc += SQUARED ? d * d : d;
-    }
-    const double t = es_block_sum(acc, sh);
-    if (threadIdx.x == 0) partial[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = t;
-}
-
-// one thread: the K * chunks partials in the order (series, chunk)
-template <int SQUARED>
-__global__ void es_series_moment_merge_kernel(const double* __restrict__ partial, int64_t n_partial, double count, es_walk* __restrict__ w)
-{
-    double sum = 0.0;
-    for (int64_t i = 0; i < n_partial; i++) sum += partial[i];
-    const double v = sum / count;
-    if (!SQUARED) {
-        w->mu = v; w->g = 1.0; w->last = 0; w->done = 0; w->status = 0;
-    } else {
-        w->sigma2 = v;
-        if (v == 0.0) { w->g = std::numeric_limits<double>::quiet_NaN(); w->done = 1; w->status = 1; }
-    }
-}
-
-struct es_batch {
-    const double* A; int64_t N; int K; int64_t chunks;                   // chunks of a whole series
-    int64_t t0, inc0; int fast, B, mintime;
-    double* partial;                                                     // [B][K][chunks]
-    double* lagsum;                                                      // [B]
-    es_walk* w;
-};
-
-// grid (chunks, B, K)
-__global__ __launch_bounds__(ES_BLOCK) void es_series_lag_kernel(es_batch a)
-{
-    __shared__ double sh[4];
-    const int64_t t = es_lag(a.t0, a.inc0, a.fast, blockIdx.y);
-    if (t >= a.N - 1) return;                                            // the walk stops before this lag
-    const int64_t end = a.N - t;                                         // n + t < N for every n below it
-    const int64_t n0 = (int64_t)blockIdx.x * ES_SERIES_CHUNK;
-    if (n0 >= end) return;
-    const int64_t hi = n0 + ES_SERIES_CHUNK < end ? n0 + ES_SERIES_CHUNK : end;
-    const double* s = a.A + (int64_t)blockIdx.z * a.N;
-    const double m = a.w->mu;
-    double acc = 0.0;
-    for (int64_t n = n0 + threadIdx.x; n < hi; n += ES_BLOCK) acc += (s[n] - m) * (s[n + t] - m);
-    const double v = es_block_sum(acc, sh);
-    if (threadIdx.x == 0) a.partial[((int64_t)blockIdx.y * a.K + blockIdx.z) * a.chunks + blockIdx.x] = v;
-}
-
-// one thread per lag of the batch: the series in order, of each the chunks [0, (N - t - 1) / chunk] in order
-__global__ __launch_bounds__(64) void es_series_lag_merge_kernel(es_batch a)
-{
-    const int b = threadIdx.x;
-    if (b >= a.B) return;
-    const int64_t t = es_lag(a.t0, a.inc0, a.fast, b);
-    double sum = 0.0;
-    if (t < a.N - 1) {
-        const int64_t chunks = (a.N - t - 1) / ES_SERIES_CHUNK + 1;
-        for (int k = 0; k < a.K; k++)
-            for (int64_t c = 0; c < chunks; c++) sum += a.partial[((int64_t)b * a.K + k) * a.chunks + c];
-    }
-    a.lagsum[b] = sum;
-}
-
-// one thread: the loop of analysis.statistical_inefficiency_multiple over the lags of this batch
-__global__ void es_series_walk_kernel(es_batch a)
-{
-    es_walk w = *a.w;
-    int done = 0;
-    for (int b = 0; b < a.B; b++) {
-        const int64_t t = es_lag(a.t0, a.inc0, a.fast, b);
-        if (t >= a.N - 1) { done = 1; break; }
-        const double C = a.lagsum[b] / ((double)a.K * (double)(a.N - t) * w.sigma2);
-        if (C <= 0.0 && t > a.mintime) { done = 1; break; }
-        w.g += 2.0 * C * (1.0 - (double)t / (double)a.N) * (double)es_increment(a.inc0, a.fast, b);
-        w.last = t;
-    }
-    w.done = done;
-    *a.w = w;
-}
-
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-#define ES_CHECK(expr) do { const hipError_t _e = (expr); if (_e != hipSuccess) return remd_hip_fail(nullptr, #expr, _e); } while (0)
-
-// a stream and the two events that time the launches on it
-struct es_timer {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    double ms = 0.0;
-    int open(int dev)
-    {
-        device = dev;
-        ES_CHECK(hipStreamCreate(&stream));
-        ES_CHECK(hipEventCreate(&ev0));
-        ES_CHECK(hipEventCreate(&ev1));
-        return 0;
-    }
-    int begin() { ES_CHECK(hipEventRecord(ev0, stream)); return 0; }
-    // waits for the launches since begin() and adds their time to ms
-    int end()
-    {
-        ES_CHECK(hipGetLastError());
-        ES_CHECK(hipEventRecord(ev1, stream));
-        ES_CHECK(hipStreamSynchronize(stream));
-        float t = 0.0f;
-        ES_CHECK(hipEventElapsedTime(&t, ev0, ev1));
-        ms += t;
-        return 0;
-    }
-    ~es_timer()
-    {
-        hipSetDevice(device);
-        if (stream) { hipStreamSynchronize(stream); hipStreamDestroy(stream); }
-        if (ev0) hipEventDestroy(ev0);
-        if (ev1) hipEventDestroy(ev1);
-    }
-};
-
 struct remd_energy_store_ctx {
     int64_t T = 0;
     int R = 0, S = 0, U = 0;
     bool timed = false;
-    es_timer tm;
     dev_array<double> energies, unsampled, log_weights, f_l, u_n, u_ln;
     dev_array<int32_t> states;
     dev_array<int64_t> iterations;
     dev_array<es_u64> counts;
+    device_timer tm;
 };
 
-static int es_device(const char* who, int device)
-{
-    int n = 0;
-    const hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n == 0)
-        return remd_fail(nullptr, -2, std::string(who) + ": no HIP device available (" + hipGetErrorString(e) + ")");
-    if (device < 0 || device >= n) return remd_fail(nullptr, -1, std::string(who) + ": bad device index");
-    ES_CHECK(hipSetDevice(device));
-    return 0;
-}
+// the passes of timeseries.hip at K series and the one origin 0 (defined there)
+int series_inefficiency(const char* who, int device, int K, int64_t N, const double* A_kn, int fast, int mintime, int first_batch, double* g,
+                        int32_t* status, int64_t* last_lag, double* ms, int64_t* chunk);
 
 static int es_series(int device, int32_t K, int64_t N, const double* A_kn, int fast, int mintime, int32_t first_batch, double* g,
                      int32_t* status, int64_t* last_lag, double* ms, int64_t* chunk)
@@ -331,52 +174,7 @@ static int es_series(int device, int32_t K, int64_t N, const double* A_kn, int f
     for (int64_t i = 0; i < total; i++)
         if (!std::isfinite(A_kn[i]))
             return remd_fail(nullptr, -1, std::string(who) + ": non-finite sample " + std::to_string(i % N) + " of series " + std::to_string(i / N));
-    REMD_TRY(es_device(who, device));
-    es_timer tm;
-    REMD_TRY(tm.open(device));
-    const int64_t chunks = (N - 1) / ES_SERIES_CHUNK + 1;
-    const int64_t per_lag = (int64_t)K * chunks;
-    dev_array<double> A, partial, lagsum;
-    dev_array<es_walk> walk;
-    REMD_TRY(A.alloc(nullptr, (size_t)total));
-    REMD_TRY(partial.alloc(nullptr, (size_t)std::max<int64_t>(ES_PARTIAL_CAP, per_lag)));
-    REMD_TRY(lagsum.alloc(nullptr, REMD_SERIES_MAX_BATCH));
-    REMD_TRY(walk.alloc(nullptr, 1));
-    ES_CHECK(hipMemcpy(A, A_kn, sizeof(double) * (size_t)total, hipMemcpyHostToDevice));
-
-    const dim3 mgrid((unsigned)chunks, (unsigned)K);
-    REMD_TRY(tm.begin());
-    hipLaunchKernelGGL(es_series_moment_kernel<0>, mgrid, dim3(ES_BLOCK), 0, tm.stream, A.get(), N, walk.get(), partial.get());
-    hipLaunchKernelGGL(es_series_moment_merge_kernel<0>, dim3(1), dim3(1), 0, tm.stream, partial.get(), per_lag, (double)total, walk.get());
-    hipLaunchKernelGGL(es_series_moment_kernel<1>, mgrid, dim3(ES_BLOCK), 0, tm.stream, A.get(), N, walk.get(), partial.get());
-    hipLaunchKernelGGL(es_series_moment_merge_kernel<1>, dim3(1), dim3(1), 0, tm.stream, partial.get(), per_lag, (double)total, walk.get());
-    REMD_TRY(tm.end());
-
-    es_walk w;
-    ES_CHECK(hipMemcpy(&w, walk, sizeof(es_walk), hipMemcpyDeviceToHost));
-    int64_t t0 = 1, inc0 = 1;
-    int ramp = first_batch;
-    while (!w.done && t0 < N - 1) {
-        const int B = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(ramp, REMD_SERIES_MAX_BATCH), ES_PARTIAL_CAP / per_lag));
-        es_batch a;
-        a.A = A; a.N = N; a.K = K; a.chunks = chunks; a.t0 = t0; a.inc0 = inc0; a.fast = fast; a.B = B; a.mintime = mintime;
-        a.partial = partial; a.lagsum = lagsum; a.w = walk;
-        const int64_t lag_chunks = (N - t0 - 1) / ES_SERIES_CHUNK + 1;                 // of the batch's first lag, the most
-        REMD_TRY(tm.begin());
-        hipLaunchKernelGGL(es_series_lag_kernel, dim3((unsigned)lag_chunks, (unsigned)B, (unsigned)K), dim3(ES_BLOCK), 0, tm.stream, a);
-        hipLaunchKernelGGL(es_series_lag_merge_kernel, dim3(1), dim3(64), 0, tm.stream, a);
-        hipLaunchKernelGGL(es_series_walk_kernel, dim3(1), dim3(1), 0, tm.stream, a);
-        REMD_TRY(tm.end());
-        ES_CHECK(hipMemcpy(&w, walk, sizeof(es_walk), hipMemcpyDeviceToHost));          // the one read-back of a batch
-        for (int b = 0; b < B; b++) { t0 += inc0; if (fast) inc0++; }
-        ramp = std::min(2 * ramp, REMD_SERIES_MAX_BATCH);
-    }
-    *status = w.status;
-    *g = w.status ? w.g : std::max(w.g, 1.0);
-    if (last_lag) *last_lag = w.last;
-    if (ms) *ms = tm.ms;
-    if (chunk) *chunk = ES_SERIES_CHUNK;
-    return 0;
+    return series_inefficiency(who, device, K, N, A_kn, fast, mintime, first_batch, g, status, last_lag, ms, chunk);
 }
 
 extern "C" {
@@ -397,17 +195,17 @@ int remd_energy_store_create(int device, int64_t T, int32_t R, int32_t S, int32_
         if (states[p] < 0 || states[p] >= S)
             return remd_fail(nullptr, -1, std::string(who) + ": states[" + std::to_string(p / R) + "][" + std::to_string(p % R) + "] = " +
                                           std::to_string(states[p]) + " is outside 0 ... S - 1 = " + std::to_string(S - 1));
-    REMD_TRY(es_device(who, device));
+    REMD_TRY(select_device(who, device));
     std::unique_ptr<remd_energy_store_ctx> st(new remd_energy_store_ctx());
     st->T = T; st->R = R; st->S = S; st->U = U;
     REMD_TRY(st->tm.open(device));
     REMD_TRY(st->energies.alloc(nullptr, (size_t)pairs * S));
     REMD_TRY(st->states.alloc(nullptr, (size_t)pairs));
-    ES_CHECK(hipMemcpy(st->energies, energies, sizeof(double) * (size_t)pairs * S, hipMemcpyHostToDevice));
-    ES_CHECK(hipMemcpy(st->states, states, sizeof(int32_t) * (size_t)pairs, hipMemcpyHostToDevice));
+    DEVICE_CHECK(hipMemcpy(st->energies, energies, sizeof(double) * (size_t)pairs * S, hipMemcpyHostToDevice));
+    DEVICE_CHECK(hipMemcpy(st->states, states, sizeof(int32_t) * (size_t)pairs, hipMemcpyHostToDevice));
     if (U) {
         REMD_TRY(st->unsampled.alloc(nullptr, (size_t)pairs * U));
-        ES_CHECK(hipMemcpy(st->unsampled, unsampled, sizeof(double) * (size_t)pairs * U, hipMemcpyHostToDevice));
+        DEVICE_CHECK(hipMemcpy(st->unsampled, unsampled, sizeof(double) * (size_t)pairs * U, hipMemcpyHostToDevice));
     }
     *out = st.release();
     return 0;
@@ -422,14 +220,14 @@ int remd_energy_store_effective_energy(remd_energy_store st, const double* log_w
     if (!u_n) return remd_fail(nullptr, -1, std::string(who) + ": u_n is NULL");
     if ((log_weights == nullptr) != (f_l == nullptr))
         return remd_fail(nullptr, -1, std::string(who) + ": log_weights and f_l go together: pass both or neither");
-    ES_CHECK(hipSetDevice(st->tm.device));
+    DEVICE_CHECK(hipSetDevice(st->tm.device));
     const int64_t T = st->T;
     REMD_TRY(st->u_n.grow(nullptr, (size_t)T));
     if (log_weights) {
         REMD_TRY(st->log_weights.grow(nullptr, (size_t)T * st->S));
         REMD_TRY(st->f_l.grow(nullptr, (size_t)st->S));
-        ES_CHECK(hipMemcpy(st->log_weights, log_weights, sizeof(double) * (size_t)T * st->S, hipMemcpyHostToDevice));
-        ES_CHECK(hipMemcpy(st->f_l, f_l, sizeof(double) * (size_t)st->S, hipMemcpyHostToDevice));
+        DEVICE_CHECK(hipMemcpy(st->log_weights, log_weights, sizeof(double) * (size_t)T * st->S, hipMemcpyHostToDevice));
+        DEVICE_CHECK(hipMemcpy(st->f_l, f_l, sizeof(double) * (size_t)st->S, hipMemcpyHostToDevice));
     }
     st->tm.ms = 0.0; st->timed = false;
     REMD_TRY(st->tm.begin());
@@ -438,7 +236,7 @@ int remd_energy_store_effective_energy(remd_energy_store st, const double* log_w
                        st->u_n.get());
     REMD_TRY(st->tm.end());
     st->timed = true;
-    ES_CHECK(hipMemcpy(u_n, st->u_n, sizeof(double) * (size_t)T, hipMemcpyDeviceToHost));
+    DEVICE_CHECK(hipMemcpy(u_n, st->u_n, sizeof(double) * (size_t)T, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -460,12 +258,12 @@ int remd_energy_store_gather_u_ln(remd_energy_store st, int64_t n_sel, const int
     const int64_t count_groups = (cols + ES_COUNT_CHUNK - 1) / ES_COUNT_CHUNK;
     if (tiles > 0x7fffffff || (cols + ES_BLOCK - 1) / ES_BLOCK > 0x7fffffff)
         return remd_fail(nullptr, -1, std::string(who) + ": the selection is too large for one launch");
-    ES_CHECK(hipSetDevice(st->tm.device));
+    DEVICE_CHECK(hipSetDevice(st->tm.device));
     REMD_TRY(st->iterations.grow(nullptr, (size_t)n_sel));
     REMD_TRY(st->u_ln.grow(nullptr, (size_t)rows * cols));
     REMD_TRY(st->counts.grow(nullptr, (size_t)S * S));
-    ES_CHECK(hipMemcpy(st->iterations, iterations, sizeof(int64_t) * (size_t)n_sel, hipMemcpyHostToDevice));
-    ES_CHECK(hipMemsetAsync(st->counts, 0, sizeof(es_u64) * (size_t)S, st->tm.stream));
+    DEVICE_CHECK(hipMemcpy(st->iterations, iterations, sizeof(int64_t) * (size_t)n_sel, hipMemcpyHostToDevice));
+    DEVICE_CHECK(hipMemsetAsync(st->counts, 0, sizeof(es_u64) * (size_t)S, st->tm.stream));
     st->tm.ms = 0.0; st->timed = false;
     REMD_TRY(st->tm.begin());
     hipLaunchKernelGGL(es_gather_kernel, dim3((unsigned)tiles), dim3(ES_TILE, ES_TILE_ROWS), 0, st->tm.stream, (const es_u64*)st->energies.get(),
@@ -481,9 +279,9 @@ int remd_energy_store_gather_u_ln(remd_energy_store st, int64_t n_sel, const int
                            st->iterations.get(), cols, R, S, st->counts.get());
     REMD_TRY(st->tm.end());
     st->timed = true;
-    ES_CHECK(hipMemcpy(u_ln, st->u_ln, sizeof(double) * (size_t)rows * cols, hipMemcpyDeviceToHost));
+    DEVICE_CHECK(hipMemcpy(u_ln, st->u_ln, sizeof(double) * (size_t)rows * cols, hipMemcpyDeviceToHost));
     static_assert(sizeof(es_u64) == sizeof(int64_t), "the counters are read back as int64_t");
-    ES_CHECK(hipMemcpy(N_l + first, st->counts, sizeof(int64_t) * (size_t)S, hipMemcpyDeviceToHost));
+    DEVICE_CHECK(hipMemcpy(N_l + first, st->counts, sizeof(int64_t) * (size_t)S, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -504,9 +302,9 @@ int remd_energy_store_transition_counts(remd_energy_store st, int64_t t_begin, i
     const int64_t n_pairs = (t_end - 1 - t_begin) * R;
     const int64_t groups = (n_pairs + ES_COUNT_CHUNK - 1) / ES_COUNT_CHUNK;
     if (groups > 0x7fffffff) return remd_fail(nullptr, -1, std::string(who) + ": the range is too large for one launch");
-    ES_CHECK(hipSetDevice(st->tm.device));
+    DEVICE_CHECK(hipSetDevice(st->tm.device));
     REMD_TRY(st->counts.grow(nullptr, cells));
-    ES_CHECK(hipMemsetAsync(st->counts, 0, sizeof(es_u64) * cells, st->tm.stream));
+    DEVICE_CHECK(hipMemsetAsync(st->counts, 0, sizeof(es_u64) * cells, st->tm.stream));
     st->tm.ms = 0.0; st->timed = false;
     REMD_TRY(st->tm.begin());
     const int32_t* from = st->states.get() + t_begin * R;
@@ -516,7 +314,7 @@ int remd_energy_store_transition_counts(remd_energy_store st, int64_t t_begin, i
         hipLaunchKernelGGL(es_transition_kernel<0>, dim3((unsigned)groups), dim3(ES_BLOCK), 0, st->tm.stream, from, n_pairs, R, S, st->counts.get());
     REMD_TRY(st->tm.end());
     st->timed = true;
-    ES_CHECK(hipMemcpy(n_ij, st->counts, sizeof(int64_t) * cells, hipMemcpyDeviceToHost));
+    DEVICE_CHECK(hipMemcpy(n_ij, st->counts, sizeof(int64_t) * cells, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -9,7 +9,7 @@
 //                call (the row pass of eq. 11 on u_ln, a row pass for ln <A>, the Gram tiles over the K + L + I columns)
 //
 // No floating-point atomics: every sum has one fixed order, set by (K, N) alone.
-#include "remd_internal.h"
+#include "device_object.h"
 #include "../../include/remd_hip_mbar.h"
 #include <cmath>
 #include <limits>
@@ -25,28 +25,8 @@
 
 enum { MBAR_ROW_SC = 0, MBAR_ROW_LOGCA = 1, MBAR_ROW_WSUM = 2 };
 
-// np.max's NaN: it stays
-__device__ __forceinline__ double mbar_nanmax(double m, double a) { return (a > m || a != a) ? a : m; }
 // _logsumexp's guard: a non-finite maximum counts as 0
 __device__ __forceinline__ double mbar_guard(double m) { return isfinite(m) ? m : 0.0; }
-
-// both in one fixed order: lanes by __shfl_down, then the four waves in wave order; every thread gets the result
-__device__ __forceinline__ double mbar_block_sum(double v, double* sh)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-__device__ __forceinline__ double mbar_block_nanmax(double v, double* sh)
-{
-    for (int o = 32; o > 0; o >>= 1) v = mbar_nanmax(v, __shfl_down(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return mbar_nanmax(mbar_nanmax(mbar_nanmax(sh[0], sh[1]), sh[2]), sh[3]);
-}
 
 // ---- column pass ----------------------------------------------------------------------------------------------------------------
 // fs[Ks], nk[Ks], srow[Ks]: f_k, N_k and the row of u of the sampled states
@@ -59,14 +39,14 @@ __global__ __launch_bounds__(MBAR_BLOCK) void mbar_logden_kernel(const double* _
     double ld = 0.0;
     if (n < N) {
         double m = -INFINITY;
-        for (int j = 0; j < Ks; j++) m = mbar_nanmax(m, fs[j] - u[(int64_t)srow[j] * N + n]);
+        for (int j = 0; j < Ks; j++) m = nanmax(m, fs[j] - u[(int64_t)srow[j] * N + n]);
         m = mbar_guard(m);
         double s = 0.0;
         for (int j = 0; j < Ks; j++) s += nk[j] * exp((fs[j] - u[(int64_t)srow[j] * N + n]) - m);
         ld = log(s) + m;
         log_den[n] = ld;
     }
-    const double t = mbar_block_sum(ld, sh);
+    const double t = block_sum(ld, sh);
     if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
@@ -76,7 +56,7 @@ __global__ __launch_bounds__(MBAR_BLOCK) void mbar_sum_kernel(const double* __re
     __shared__ double sh[4];
     double s = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += MBAR_BLOCK) s += partial[i];
-    const double t = mbar_block_sum(s, sh);
+    const double t = block_sum(s, sh);
     if (threadIdx.x == 0) out[0] = t;
 }
 
@@ -105,13 +85,13 @@ __global__ __launch_bounds__(MBAR_BLOCK) void mbar_row_kernel(const double* __re
     double mraw = 0.0, m = 0.0;
     if (MODE != MBAR_ROW_WSUM) {
         double mt = -INFINITY;
-        for (int64_t n = n0 + threadIdx.x; n < n1; n += MBAR_BLOCK) mt = mbar_nanmax(mt, mbar_row_term<MODE>(uk[n], log_den[n], fk, shift));
-        mraw = mbar_block_nanmax(mt, sh);
+        for (int64_t n = n0 + threadIdx.x; n < n1; n += MBAR_BLOCK) mt = nanmax(mt, mbar_row_term<MODE>(uk[n], log_den[n], fk, shift));
+        mraw = block_nanmax(mt, sh);
         m = mbar_guard(mraw);
     }
     double s = 0.0;
     for (int64_t n = n0 + threadIdx.x; n < n1; n += MBAR_BLOCK) s += exp(mbar_row_term<MODE>(uk[n], log_den[n], fk, shift) - m);
-    const double t = mbar_block_sum(s, sh);
+    const double t = block_sum(s, sh);
     if (threadIdx.x == 0) pairs[(int64_t)k * gridDim.x + blockIdx.x] = make_double2(mraw, t);
 }
 
@@ -122,7 +102,7 @@ __global__ void mbar_row_merge_kernel(const double2* __restrict__ pairs, int K, 
     if (k >= K) return;
     const double2* p = pairs + (int64_t)k * chunks;
     double M = -INFINITY;
-    for (int c = 0; c < chunks; c++) M = mbar_nanmax(M, p[c].x);
+    for (int c = 0; c < chunks; c++) M = nanmax(M, p[c].x);
     M = mbar_guard(M);
     double S = 0.0;
     for (int c = 0; c < chunks; c++)
@@ -242,12 +222,12 @@ __global__ __launch_bounds__(MBAR_BLOCK) void mbar_aug_logca_kernel(const double
     const double* __restrict__ Ai = A + (int64_t)i * N;
     const double fs = f[s];
     double mt = -INFINITY;
-    for (int64_t n = n0 + threadIdx.x; n < n1; n += MBAR_BLOCK) mt = mbar_nanmax(mt, ((fs - us[n]) - log_den[n]) + log(Ai[n]));
-    const double mraw = mbar_block_nanmax(mt, sh);
+    for (int64_t n = n0 + threadIdx.x; n < n1; n += MBAR_BLOCK) mt = nanmax(mt, ((fs - us[n]) - log_den[n]) + log(Ai[n]));
+    const double mraw = block_nanmax(mt, sh);
     const double m = mbar_guard(mraw);
     double sum = 0.0;
     for (int64_t n = n0 + threadIdx.x; n < n1; n += MBAR_BLOCK) sum += exp((((fs - us[n]) - log_den[n]) + log(Ai[n])) - m);
-    const double t = mbar_block_sum(sum, sh);
+    const double t = block_sum(sum, sh);
     if (threadIdx.x == 0) pairs[(int64_t)i * gridDim.x + blockIdx.x] = make_double2(mraw, t);
 }
 
@@ -331,28 +311,18 @@ __global__ __launch_bounds__(MBAR_BLOCK) void mbar_log_weights_kernel(const doub
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
 struct remd_mbar_ctx {
-    int device = 0, K = 0, Ks = 0;
+    int K = 0, Ks = 0;
     int64_t N = 0;
     double shift = 0.0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;                     // a pass has run: ev0 and ev1 hold its kernels
+    bool timed = false;                     // a pass has run: tm.ms holds its kernels
     std::vector<double> nk_all;             // [K]
     std::vector<int> srow;                  // [Ks]
     dev_array<double> u, nk, fs, f, log_den, col_partial, scalar, row_out, log_cA, gram, gram_partial, weights;
     dev_array<int> d_srow, col_state;
     dev_array<int2> tiles;
     dev_array<double2> pairs;
-    ~remd_mbar_ctx()
-    {
-        hipSetDevice(device);
-        if (stream) { hipStreamSynchronize(stream); hipStreamDestroy(stream); }
-        if (ev0) hipEventDestroy(ev0);
-        if (ev1) hipEventDestroy(ev1);
-    }
+    device_timer tm;
 };
-
-#define MBAR_CHECK(expr) do { const hipError_t _e = (expr); if (_e != hipSuccess) return remd_hip_fail(nullptr, #expr, _e); } while (0)
 
 static int64_t mbar_gram_chunk(int64_t N, int C)
 {
@@ -369,20 +339,19 @@ static int mbar_begin(remd_mbar m, const char* who, const double* f_k, const voi
     if (!m) return remd_fail(nullptr, -1, std::string(who) + ": the problem is NULL");
     if (!f_k) return remd_fail(nullptr, -1, std::string(who) + ": f_k is NULL");
     if (!out || !out2) return remd_fail(nullptr, -1, std::string(who) + ": an output array is NULL");
-    MBAR_CHECK(hipSetDevice(m->device));
+    DEVICE_CHECK(hipSetDevice(m->tm.device));
     std::vector<double> fs(m->Ks);
     for (int j = 0; j < m->Ks; j++) fs[j] = f_k[m->srow[j]];
-    MBAR_CHECK(hipMemcpyAsync(m->f, f_k, sizeof(double) * m->K, hipMemcpyHostToDevice, m->stream));
-    MBAR_CHECK(hipMemcpyAsync(m->fs, fs.data(), sizeof(double) * m->Ks, hipMemcpyHostToDevice, m->stream));
-    MBAR_CHECK(hipStreamSynchronize(m->stream));            // (fs is a local)
-    MBAR_CHECK(hipEventRecord(m->ev0, m->stream));
-    return 0;
+    DEVICE_CHECK(hipMemcpyAsync(m->f, f_k, sizeof(double) * m->K, hipMemcpyHostToDevice, m->tm.stream));
+    DEVICE_CHECK(hipMemcpyAsync(m->fs, fs.data(), sizeof(double) * m->Ks, hipMemcpyHostToDevice, m->tm.stream));
+    DEVICE_CHECK(hipStreamSynchronize(m->tm.stream));            // (fs is a local)
+    m->tm.ms = 0.0;
+    return m->tm.begin();
 }
 
 static int mbar_end(remd_mbar m)
 {
-    MBAR_CHECK(hipEventRecord(m->ev1, m->stream));
-    MBAR_CHECK(hipStreamSynchronize(m->stream));
+    REMD_TRY(m->tm.end());
     m->timed = true;
     return 0;
 }
@@ -391,17 +360,17 @@ static int mbar_end(remd_mbar m)
 static int mbar_column_pass(remd_mbar m)
 {
     const int64_t blocks = (m->N + MBAR_BLOCK - 1) / MBAR_BLOCK;
-    hipLaunchKernelGGL(mbar_logden_kernel, dim3((unsigned)blocks), dim3(MBAR_BLOCK), 0, m->stream, m->u.get(), m->fs.get(), m->nk.get(),
+    hipLaunchKernelGGL(mbar_logden_kernel, dim3((unsigned)blocks), dim3(MBAR_BLOCK), 0, m->tm.stream, m->u.get(), m->fs.get(), m->nk.get(),
                        m->d_srow.get(), m->Ks, m->N, m->log_den.get(), m->col_partial.get());
-    hipLaunchKernelGGL(mbar_sum_kernel, dim3(1), dim3(MBAR_BLOCK), 0, m->stream, m->col_partial.get(), blocks, m->scalar.get());
-    MBAR_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(mbar_sum_kernel, dim3(1), dim3(MBAR_BLOCK), 0, m->tm.stream, m->col_partial.get(), blocks, m->scalar.get());
+    DEVICE_CHECK(hipGetLastError());
     return 0;
 }
 
 static int mbar_phi(remd_mbar m, const double* f_k, double* phi)
 {
     double sum = 0.0;
-    MBAR_CHECK(hipMemcpy(&sum, m->scalar, sizeof(double), hipMemcpyDeviceToHost));
+    DEVICE_CHECK(hipMemcpy(&sum, m->scalar, sizeof(double), hipMemcpyDeviceToHost));
     double dot = 0.0;
     for (int j = 0; j < m->Ks; j++) dot += m->nk_all[m->srow[j]] * f_k[m->srow[j]];
     *phi = sum - dot;
@@ -414,14 +383,14 @@ static int mbar_row_pass(remd_mbar m, int mode, double* dst)
     const int chunks = (int)((m->N + MBAR_ROW_CHUNK - 1) / MBAR_ROW_CHUNK);
     const dim3 grid((unsigned)chunks, (unsigned)m->K);
     if (mode == MBAR_ROW_SC)
-        hipLaunchKernelGGL(mbar_row_kernel<MBAR_ROW_SC>, grid, dim3(MBAR_BLOCK), 0, m->stream, m->u.get(), m->log_den.get(), m->f.get(), m->N, m->shift, m->pairs.get());
+        hipLaunchKernelGGL(mbar_row_kernel<MBAR_ROW_SC>, grid, dim3(MBAR_BLOCK), 0, m->tm.stream, m->u.get(), m->log_den.get(), m->f.get(), m->N, m->shift, m->pairs.get());
     else if (mode == MBAR_ROW_LOGCA)
-        hipLaunchKernelGGL(mbar_row_kernel<MBAR_ROW_LOGCA>, grid, dim3(MBAR_BLOCK), 0, m->stream, m->u.get(), m->log_den.get(), m->f.get(), m->N, m->shift, m->pairs.get());
+        hipLaunchKernelGGL(mbar_row_kernel<MBAR_ROW_LOGCA>, grid, dim3(MBAR_BLOCK), 0, m->tm.stream, m->u.get(), m->log_den.get(), m->f.get(), m->N, m->shift, m->pairs.get());
     else
-        hipLaunchKernelGGL(mbar_row_kernel<MBAR_ROW_WSUM>, grid, dim3(MBAR_BLOCK), 0, m->stream, m->u.get(), m->log_den.get(), m->f.get(), m->N, m->shift, m->pairs.get());
-    hipLaunchKernelGGL(mbar_row_merge_kernel, dim3((unsigned)((m->K + 63) / 64)), dim3(64), 0, m->stream, m->pairs.get(), m->K, chunks,
+        hipLaunchKernelGGL(mbar_row_kernel<MBAR_ROW_WSUM>, grid, dim3(MBAR_BLOCK), 0, m->tm.stream, m->u.get(), m->log_den.get(), m->f.get(), m->N, m->shift, m->pairs.get());
+    hipLaunchKernelGGL(mbar_row_merge_kernel, dim3((unsigned)((m->K + 63) / 64)), dim3(64), 0, m->tm.stream, m->pairs.get(), m->K, chunks,
                        mode == MBAR_ROW_WSUM ? 0 : 1, mode == MBAR_ROW_SC ? -1.0 : 1.0, dst);
-    MBAR_CHECK(hipGetLastError());
+    DEVICE_CHECK(hipGetLastError());
     return 0;
 }
 
@@ -438,17 +407,17 @@ static int mbar_gram_pass(remd_mbar m, const std::vector<int>& states, int n_pla
     REMD_TRY(m->tiles.grow(nullptr, tiles.size()));
     REMD_TRY(m->gram.grow(nullptr, (size_t)C * C));
     REMD_TRY(m->gram_partial.grow(nullptr, (size_t)chunks * C * C));
-    MBAR_CHECK(hipMemcpyAsync(m->col_state, states.data(), sizeof(int) * C, hipMemcpyHostToDevice, m->stream));
-    MBAR_CHECK(hipMemcpyAsync(m->tiles, tiles.data(), sizeof(int2) * tiles.size(), hipMemcpyHostToDevice, m->stream));
-    MBAR_CHECK(hipStreamSynchronize(m->stream));            // (both sources are locals)
+    DEVICE_CHECK(hipMemcpyAsync(m->col_state, states.data(), sizeof(int) * C, hipMemcpyHostToDevice, m->tm.stream));
+    DEVICE_CHECK(hipMemcpyAsync(m->tiles, tiles.data(), sizeof(int2) * tiles.size(), hipMemcpyHostToDevice, m->tm.stream));
+    DEVICE_CHECK(hipStreamSynchronize(m->tm.stream));            // (both sources are locals)
     mbar_gram_args a;
     a.u = m->u; a.log_den = m->log_den; a.f = m->f; a.log_cA = m->log_cA; a.col_state = m->col_state; a.tiles = m->tiles;
     a.C = C; a.n_plain = n_plain; a.N = m->N; a.chunk = chunk; a.shift = m->shift; a.partial = m->gram_partial;
-    hipLaunchKernelGGL(mbar_gram_kernel, dim3((unsigned)tiles.size(), (unsigned)chunks), dim3(MBAR_BLOCK), 0, m->stream, a);
+    hipLaunchKernelGGL(mbar_gram_kernel, dim3((unsigned)tiles.size(), (unsigned)chunks), dim3(MBAR_BLOCK), 0, m->tm.stream, a);
     const int64_t entries = (int64_t)C * C;
-    hipLaunchKernelGGL(mbar_gram_sum_kernel, dim3((unsigned)((entries + MBAR_BLOCK - 1) / MBAR_BLOCK)), dim3(MBAR_BLOCK), 0, m->stream,
+    hipLaunchKernelGGL(mbar_gram_sum_kernel, dim3((unsigned)((entries + MBAR_BLOCK - 1) / MBAR_BLOCK)), dim3(MBAR_BLOCK), 0, m->tm.stream,
                        m->gram_partial.get(), C, chunks, m->gram.get());
-    MBAR_CHECK(hipGetLastError());
+    DEVICE_CHECK(hipGetLastError());
     return 0;
 }
 
@@ -479,14 +448,9 @@ int remd_mbar_create(int device, int K, int64_t N, const double* u_kn, const int
             if (row[n] < umin) umin = row[n];
         }
     }
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n == 0)
-        return remd_fail(nullptr, -2, std::string("remd_mbar_create: no HIP device available (") + hipGetErrorString(e) + ")");
-    if (device < 0 || device >= n) return remd_fail(nullptr, -1, "remd_mbar_create: bad device index");
-    MBAR_CHECK(hipSetDevice(device));
+    REMD_TRY(select_device("remd_mbar_create", device));
     std::unique_ptr<remd_mbar_ctx> m(new remd_mbar_ctx());
-    m->device = device; m->K = K; m->N = N;
+    m->K = K; m->N = N;
     m->shift = (has_nan ? std::numeric_limits<double>::quiet_NaN() : umin) - 1.0;      // np.min keeps a NaN
     std::vector<double> nk;
     m->nk_all.resize(K);
@@ -495,11 +459,9 @@ int remd_mbar_create(int device, int K, int64_t N, const double* u_kn, const int
         if (N_k[k] > 0) { m->srow.push_back(k); nk.push_back((double)N_k[k]); }
     }
     m->Ks = (int)m->srow.size();
-    MBAR_CHECK(hipStreamCreate(&m->stream));
-    MBAR_CHECK(hipEventCreate(&m->ev0));
-    MBAR_CHECK(hipEventCreate(&m->ev1));
+    REMD_TRY(m->tm.open(device));
     REMD_TRY(m->u.alloc(nullptr, (size_t)K * N));
-    MBAR_CHECK(hipMemcpy(m->u, u_kn, sizeof(double) * (size_t)K * N, hipMemcpyHostToDevice));
+    DEVICE_CHECK(hipMemcpy(m->u, u_kn, sizeof(double) * (size_t)K * N, hipMemcpyHostToDevice));
     REMD_TRY(m->nk.upload(nullptr, nk));
     REMD_TRY(m->d_srow.upload(nullptr, m->srow));
     REMD_TRY(m->fs.alloc(nullptr, m->Ks));
@@ -521,7 +483,7 @@ int remd_mbar_log_denominator(remd_mbar m, const double* f_k, double* log_den, d
     REMD_TRY(mbar_begin(m, "remd_mbar_log_denominator", f_k));
     REMD_TRY(mbar_column_pass(m));
     REMD_TRY(mbar_end(m));
-    if (log_den) MBAR_CHECK(hipMemcpy(log_den, m->log_den, sizeof(double) * m->N, hipMemcpyDeviceToHost));
+    if (log_den) DEVICE_CHECK(hipMemcpy(log_den, m->log_den, sizeof(double) * m->N, hipMemcpyDeviceToHost));
     if (phi) REMD_TRY(mbar_phi(m, f_k, phi));
     return 0;
 }
@@ -532,7 +494,7 @@ int remd_mbar_self_consistent(remd_mbar m, const double* f_k, double* f_new)
     REMD_TRY(mbar_column_pass(m));
     REMD_TRY(mbar_row_pass(m, MBAR_ROW_SC, m->row_out));
     REMD_TRY(mbar_end(m));
-    MBAR_CHECK(hipMemcpy(f_new, m->row_out, sizeof(double) * m->K, hipMemcpyDeviceToHost));
+    DEVICE_CHECK(hipMemcpy(f_new, m->row_out, sizeof(double) * m->K, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -545,8 +507,8 @@ int remd_mbar_newton_parts(remd_mbar m, const double* f_k, double* W_sum, double
     REMD_TRY(mbar_end(m));
     const int K = m->K, Ks = m->Ks;
     std::vector<double> ws(K), g((size_t)Ks * Ks);
-    MBAR_CHECK(hipMemcpy(ws.data(), m->row_out, sizeof(double) * K, hipMemcpyDeviceToHost));
-    MBAR_CHECK(hipMemcpy(g.data(), m->gram, sizeof(double) * g.size(), hipMemcpyDeviceToHost));
+    DEVICE_CHECK(hipMemcpy(ws.data(), m->row_out, sizeof(double) * K, hipMemcpyDeviceToHost));
+    DEVICE_CHECK(hipMemcpy(g.data(), m->gram, sizeof(double) * g.size(), hipMemcpyDeviceToHost));
     for (int k = 0; k < K; k++) W_sum[k] = 0.0;
     for (int64_t i = 0; i < (int64_t)K * K; i++) gram[i] = 0.0;
     for (int a = 0; a < Ks; a++) {
@@ -567,8 +529,8 @@ int remd_mbar_gram(remd_mbar m, const double* f_k, int with_observable, double* 
     if (with_observable) REMD_TRY(mbar_row_pass(m, MBAR_ROW_LOGCA, m->log_cA));
     REMD_TRY(mbar_gram_pass(m, states, K));
     REMD_TRY(mbar_end(m));
-    MBAR_CHECK(hipMemcpy(gram, m->gram, sizeof(double) * (size_t)C * C, hipMemcpyDeviceToHost));
-    if (with_observable && log_cA) MBAR_CHECK(hipMemcpy(log_cA, m->log_cA, sizeof(double) * K, hipMemcpyDeviceToHost));
+    DEVICE_CHECK(hipMemcpy(gram, m->gram, sizeof(double) * (size_t)C * C, hipMemcpyDeviceToHost));
+    if (with_observable && log_cA) DEVICE_CHECK(hipMemcpy(log_cA, m->log_cA, sizeof(double) * K, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -603,7 +565,7 @@ int remd_mbar_augmented_gram(remd_mbar m, const double* f_k, int L, const double
     }
     if (!f_k) return remd_fail(nullptr, -1, who + ": f_k is NULL");
     if (!gram) return remd_fail(nullptr, -1, who + ": an output array is NULL");
-    MBAR_CHECK(hipSetDevice(m->device));
+    DEVICE_CHECK(hipSetDevice(m->tm.device));
     // the arrays of this call: freed when it returns
     const int row_chunks = (int)((N + MBAR_ROW_CHUNK - 1) / MBAR_ROW_CHUNK);
     dev_array<double> d_u_ln, d_A, d_f, d_log_cA;
@@ -615,22 +577,22 @@ int remd_mbar_augmented_gram(remd_mbar m, const double* f_k, int L, const double
     REMD_TRY(d_log_cA.alloc(nullptr, (size_t)I));
     REMD_TRY(d_obs.alloc(nullptr, (size_t)I));
     REMD_TRY(d_pairs.alloc(nullptr, (size_t)std::max(L, I) * row_chunks));
-    if (L) MBAR_CHECK(hipMemcpy(d_u_ln, u_ln, sizeof(double) * (size_t)L * N, hipMemcpyHostToDevice));
-    if (I) MBAR_CHECK(hipMemcpy(d_A, A_in, sizeof(double) * (size_t)I * N, hipMemcpyHostToDevice));
-    if (I) MBAR_CHECK(hipMemcpy(d_obs, obs_state, sizeof(int) * (size_t)I, hipMemcpyHostToDevice));
-    MBAR_CHECK(hipMemset(d_f, 0, sizeof(double) * ((size_t)K + L)));
-    MBAR_CHECK(hipMemcpy(d_f, f_k, sizeof(double) * K, hipMemcpyHostToDevice));
+    if (L) DEVICE_CHECK(hipMemcpy(d_u_ln, u_ln, sizeof(double) * (size_t)L * N, hipMemcpyHostToDevice));
+    if (I) DEVICE_CHECK(hipMemcpy(d_A, A_in, sizeof(double) * (size_t)I * N, hipMemcpyHostToDevice));
+    if (I) DEVICE_CHECK(hipMemcpy(d_obs, obs_state, sizeof(int) * (size_t)I, hipMemcpyHostToDevice));
+    DEVICE_CHECK(hipMemset(d_f, 0, sizeof(double) * ((size_t)K + L)));
+    DEVICE_CHECK(hipMemcpy(d_f, f_k, sizeof(double) * K, hipMemcpyHostToDevice));
     REMD_TRY(mbar_begin(m, who.c_str(), f_k));
     REMD_TRY(mbar_column_pass(m));
     std::vector<double> fl(L);
     if (L) {                                                 // eq. 11 on the rows of u_ln, into f[K ...]
-        hipLaunchKernelGGL(mbar_row_kernel<MBAR_ROW_SC>, dim3((unsigned)row_chunks, (unsigned)L), dim3(MBAR_BLOCK), 0, m->stream, d_u_ln.get(),
+        hipLaunchKernelGGL(mbar_row_kernel<MBAR_ROW_SC>, dim3((unsigned)row_chunks, (unsigned)L), dim3(MBAR_BLOCK), 0, m->tm.stream, d_u_ln.get(),
                            m->log_den.get(), d_f.get(), N, 0.0, d_pairs.get());
-        hipLaunchKernelGGL(mbar_row_merge_kernel, dim3((unsigned)((L + 63) / 64)), dim3(64), 0, m->stream, d_pairs.get(), L, row_chunks, 1, -1.0,
+        hipLaunchKernelGGL(mbar_row_merge_kernel, dim3((unsigned)((L + 63) / 64)), dim3(64), 0, m->tm.stream, d_pairs.get(), L, row_chunks, 1, -1.0,
                            d_f.get() + K);
-        MBAR_CHECK(hipGetLastError());
-        MBAR_CHECK(hipMemcpyAsync(fl.data(), d_f.get() + K, sizeof(double) * L, hipMemcpyDeviceToHost, m->stream));
-        MBAR_CHECK(hipStreamSynchronize(m->stream));
+        DEVICE_CHECK(hipGetLastError());
+        DEVICE_CHECK(hipMemcpyAsync(fl.data(), d_f.get() + K, sizeof(double) * L, hipMemcpyDeviceToHost, m->tm.stream));
+        DEVICE_CHECK(hipStreamSynchronize(m->tm.stream));
         for (int l = 0; l < L; l++)
             if (!std::isfinite(fl[l])) {
                 REMD_TRY(mbar_end(m));                       // (remd_mbar_last_ms then reports the passes this call did run)
@@ -638,11 +600,11 @@ int remd_mbar_augmented_gram(remd_mbar m, const double* f_k, int L, const double
             }
     }
     if (I) {
-        hipLaunchKernelGGL(mbar_aug_logca_kernel, dim3((unsigned)row_chunks, (unsigned)I), dim3(MBAR_BLOCK), 0, m->stream, m->u.get(), d_u_ln.get(),
+        hipLaunchKernelGGL(mbar_aug_logca_kernel, dim3((unsigned)row_chunks, (unsigned)I), dim3(MBAR_BLOCK), 0, m->tm.stream, m->u.get(), d_u_ln.get(),
                            d_A.get(), m->log_den.get(), d_f.get(), d_obs.get(), K, N, d_pairs.get());
-        hipLaunchKernelGGL(mbar_row_merge_kernel, dim3((unsigned)((I + 63) / 64)), dim3(64), 0, m->stream, d_pairs.get(), I, row_chunks, 1, 1.0,
+        hipLaunchKernelGGL(mbar_row_merge_kernel, dim3((unsigned)((I + 63) / 64)), dim3(64), 0, m->tm.stream, d_pairs.get(), I, row_chunks, 1, 1.0,
                            d_log_cA.get());
-        MBAR_CHECK(hipGetLastError());
+        DEVICE_CHECK(hipGetLastError());
     }
     const int T = (C + MBAR_TILE - 1) / MBAR_TILE;
     std::vector<int2> tiles;
@@ -652,20 +614,20 @@ int remd_mbar_augmented_gram(remd_mbar m, const double* f_k, int L, const double
     REMD_TRY(m->tiles.grow(nullptr, tiles.size()));
     REMD_TRY(m->gram.grow(nullptr, (size_t)C * C));
     REMD_TRY(m->gram_partial.grow(nullptr, (size_t)chunks * C * C));
-    MBAR_CHECK(hipMemcpyAsync(m->tiles, tiles.data(), sizeof(int2) * tiles.size(), hipMemcpyHostToDevice, m->stream));
-    MBAR_CHECK(hipStreamSynchronize(m->stream));            // (the source is a local)
+    DEVICE_CHECK(hipMemcpyAsync(m->tiles, tiles.data(), sizeof(int2) * tiles.size(), hipMemcpyHostToDevice, m->tm.stream));
+    DEVICE_CHECK(hipStreamSynchronize(m->tm.stream));            // (the source is a local)
     mbar_aug_args a;
     a.u = m->u; a.u_ln = d_u_ln; a.A = d_A; a.log_den = m->log_den; a.f = d_f; a.log_cA = d_log_cA; a.obs_state = d_obs; a.tiles = m->tiles;
     a.K = K; a.L = L; a.C = C; a.N = N; a.chunk = chunk; a.partial = m->gram_partial;
-    hipLaunchKernelGGL(mbar_aug_gram_kernel, dim3((unsigned)tiles.size(), (unsigned)chunks), dim3(MBAR_BLOCK), 0, m->stream, a);
+    hipLaunchKernelGGL(mbar_aug_gram_kernel, dim3((unsigned)tiles.size(), (unsigned)chunks), dim3(MBAR_BLOCK), 0, m->tm.stream, a);
     const int64_t entries = (int64_t)C * C;
-    hipLaunchKernelGGL(mbar_gram_sum_kernel, dim3((unsigned)((entries + MBAR_BLOCK - 1) / MBAR_BLOCK)), dim3(MBAR_BLOCK), 0, m->stream,
+    hipLaunchKernelGGL(mbar_gram_sum_kernel, dim3((unsigned)((entries + MBAR_BLOCK - 1) / MBAR_BLOCK)), dim3(MBAR_BLOCK), 0, m->tm.stream,
                        m->gram_partial.get(), C, chunks, m->gram.get());
-    MBAR_CHECK(hipGetLastError());
+    DEVICE_CHECK(hipGetLastError());
     REMD_TRY(mbar_end(m));
-    MBAR_CHECK(hipMemcpy(gram, m->gram, sizeof(double) * (size_t)C * C, hipMemcpyDeviceToHost));
+    DEVICE_CHECK(hipMemcpy(gram, m->gram, sizeof(double) * (size_t)C * C, hipMemcpyDeviceToHost));
     for (int l = 0; l < L; l++) f_l[l] = fl[l];
-    if (I) MBAR_CHECK(hipMemcpy(log_cA, d_log_cA, sizeof(double) * I, hipMemcpyDeviceToHost));
+    if (I) DEVICE_CHECK(hipMemcpy(log_cA, d_log_cA, sizeof(double) * I, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -674,11 +636,11 @@ int remd_mbar_log_weights(remd_mbar m, const double* f_k, double* log_W_nk)
     REMD_TRY(mbar_begin(m, "remd_mbar_log_weights", f_k, log_W_nk));
     REMD_TRY(m->weights.grow(nullptr, (size_t)m->N * m->K));
     REMD_TRY(mbar_column_pass(m));
-    hipLaunchKernelGGL(mbar_log_weights_kernel, dim3((unsigned)((m->N + 15) / 16), (unsigned)((m->K + 15) / 16)), dim3(MBAR_BLOCK), 0, m->stream,
+    hipLaunchKernelGGL(mbar_log_weights_kernel, dim3((unsigned)((m->N + 15) / 16), (unsigned)((m->K + 15) / 16)), dim3(MBAR_BLOCK), 0, m->tm.stream,
                        m->u.get(), m->log_den.get(), m->f.get(), m->K, m->N, m->weights.get());
-    MBAR_CHECK(hipGetLastError());
+    DEVICE_CHECK(hipGetLastError());
     REMD_TRY(mbar_end(m));
-    MBAR_CHECK(hipMemcpy(log_W_nk, m->weights, sizeof(double) * (size_t)m->N * m->K, hipMemcpyDeviceToHost));
+    DEVICE_CHECK(hipMemcpy(log_W_nk, m->weights, sizeof(double) * (size_t)m->N * m->K, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -695,10 +657,7 @@ int remd_mbar_last_ms(remd_mbar m, double* ms)
 {
     if (!m || !ms) return remd_fail(nullptr, -1, "remd_mbar_last_ms: the problem or ms is NULL");
     if (!m->timed) return remd_fail(nullptr, -1, "remd_mbar_last_ms: no pass has run on this problem yet");
-    MBAR_CHECK(hipSetDevice(m->device));
-    float t = 0.0f;
-    MBAR_CHECK(hipEventElapsedTime(&t, m->ev0, m->ev1));
-    *ms = t;
+    *ms = m->tm.ms;
     return 0;
 }
 

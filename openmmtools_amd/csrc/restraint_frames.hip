@@ -6,7 +6,7 @@
 // a group's atoms, the centroid is the engine's own (centroid_sum.h: first atom + sum_i w_i img(x_i - x_first), f64, xor-shuffle tree in
 // a fixed order, no atomics), the distance is imaged as restraint_kernel images it and the energy forms are restraint_kernel's.  A
 // frame's result depends on that frame alone, so it does not depend on how the host cuts F into launches.  No LDS, no barrier.
-#include "remd_internal.h"
+#include "device_object.h"
 #include "centroid_sum.h"
 #include "../../include/remd_hip_restraints.h"
 #include <cmath>
@@ -50,13 +50,6 @@ void restraint_frames_kernel(rstf_param p, const int* __restrict__ atoms, const 
 }
 
 double g_last_kernel_ms = -1.0;                         // the kernels of the last successful call (remd_restraint_frames_last_ms)
-
-struct rstf_events {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~rstf_events() { if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); }
-};
-
-#define RSTF_CHECK(expr) do { const hipError_t _e = (expr); if (_e != hipSuccess) return remd_hip_fail(nullptr, #expr, _e); } while (0)
 
 int refuse(const std::string& msg) { return remd_fail(nullptr, -1, "remd_restraint_frames: " + msg); }
 
@@ -108,12 +101,7 @@ int remd_restraint_frames(int device, const remd_restraint_desc* desc, int64_t F
     chunk = std::min<int64_t>(chunk, (int64_t)RSTF_FRAMES_PER_BLOCK * 0x7fffffff);          // (the grid of one launch)
 
     // ---- the device ----
-    int n_dev = 0;
-    const hipError_t e = hipGetDeviceCount(&n_dev);
-    if (e != hipSuccess || n_dev == 0)
-        return remd_fail(nullptr, -2, std::string("remd_restraint_frames: no HIP device available (") + hipGetErrorString(e) + ")");
-    if (device < 0 || device >= n_dev) return refuse("bad device index");
-    RSTF_CHECK(hipSetDevice(device));
+    REMD_TRY(select_device("remd_restraint_frames", device));
     dev_array<int> d_atoms; dev_array<double> d_w, d_E, d_r; dev_array<float> d_pos, d_box;
     REMD_TRY(d_atoms.upload(nullptr, atoms));
     REMD_TRY(d_w.upload(nullptr, w));
@@ -121,30 +109,23 @@ int remd_restraint_frames(int device, const remd_restraint_desc* desc, int64_t F
     if (pbc) REMD_TRY(d_box.alloc(nullptr, (size_t)(3 * chunk)));
     REMD_TRY(d_E.alloc(nullptr, (size_t)chunk));
     REMD_TRY(d_r.alloc(nullptr, (size_t)chunk));
-    rstf_events ev;
-    RSTF_CHECK(hipEventCreate(&ev.e0));
-    RSTF_CHECK(hipEventCreate(&ev.e1));
+    device_timer tm;                                     // (after the arrays: it waits for its stream before they are freed)
+    REMD_TRY(tm.open(device, false));
     rstf_param p{};
     p.kind = d.kind; p.periodic = pbc ? 1 : 0; p.n1 = d.n1; p.n2 = d.n2; p.K = d.K; p.r0 = d.r0;
-    double kernel_ms = 0.0;
     for (int64_t f0 = 0; f0 < F; f0 += chunk) {
         const int64_t n = std::min(chunk, F - f0);
-        RSTF_CHECK(hipMemcpy(d_pos, pos + f0 * frame_floats, sizeof(float) * (size_t)(n * frame_floats), hipMemcpyHostToDevice));
-        if (pbc) RSTF_CHECK(hipMemcpy(d_box, box + 3 * f0, sizeof(float) * (size_t)(3 * n), hipMemcpyHostToDevice));
+        DEVICE_CHECK(hipMemcpy(d_pos, pos + f0 * frame_floats, sizeof(float) * (size_t)(n * frame_floats), hipMemcpyHostToDevice));
+        if (pbc) DEVICE_CHECK(hipMemcpy(d_box, box + 3 * f0, sizeof(float) * (size_t)(3 * n), hipMemcpyHostToDevice));
         const unsigned blocks = (unsigned)((n + RSTF_FRAMES_PER_BLOCK - 1) / RSTF_FRAMES_PER_BLOCK);
-        RSTF_CHECK(hipEventRecord(ev.e0, nullptr));
-        hipLaunchKernelGGL(restraint_frames_kernel, dim3(blocks), dim3(RSTF_BLOCK), 0, nullptr, p, d_atoms.get(), d_w.get(), n, n_atoms,
+        REMD_TRY(tm.begin());
+        hipLaunchKernelGGL(restraint_frames_kernel, dim3(blocks), dim3(RSTF_BLOCK), 0, tm.stream, p, d_atoms.get(), d_w.get(), n, n_atoms,
                            d_pos.get(), pbc ? d_box.get() : nullptr, d_E.get(), d_r.get());
-        RSTF_CHECK(hipGetLastError());
-        RSTF_CHECK(hipEventRecord(ev.e1, nullptr));
-        RSTF_CHECK(hipEventSynchronize(ev.e1));
-        float ms = 0.0f;
-        RSTF_CHECK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
-        kernel_ms += (double)ms;
-        if (energy) RSTF_CHECK(hipMemcpy(energy + f0, d_E, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-        if (distance) RSTF_CHECK(hipMemcpy(distance + f0, d_r, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+        REMD_TRY(tm.end());
+        if (energy) DEVICE_CHECK(hipMemcpy(energy + f0, d_E, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+        if (distance) DEVICE_CHECK(hipMemcpy(distance + f0, d_r, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
     }
-    g_last_kernel_ms = kernel_ms;
+    g_last_kernel_ms = tm.ms;
     return 0;
 }
 

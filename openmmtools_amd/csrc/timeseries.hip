@@ -1,10 +1,12 @@
-// The statistical inefficiency of the suffixes of a timeseries on the device (include/remd_hip_timeseries.h).  All f64.
+// The statistical inefficiency on the device: of the suffixes of one timeseries (include/remd_hip_timeseries.h) and of several series
+// of one length taken together (remd_series_inefficiency_multiple of include/remd_hip_energy_store.h).  All f64.  One set of passes for
+// K series of one length N and S origins, of which the entries reach K = 1 (any S) and S = 1 with origin 0 (any K):
 //
-//   moments      workgroups per (origin, chunk of samples): sum A over the suffix, merged per origin in chunk order -> mean; then the
-//                same for sum (A - mean)^2 -> sigma2.  Two passes, as the host takes them.
-//   lag batch    workgroups per (origin, lag of the batch, chunk of n): sum (A[n] - mean)(A[n + t] - mean) over the chunk; one thread
-//                per (origin, lag) merges the chunks in chunk order; one thread per origin walks the lags of the batch in order,
-//                applies the stopping rule and carries (g, done, last lag) to the next batch
+//   moments      workgroups per (series, origin, chunk of samples): sum A over the suffix, merged per origin in the order (series,
+//                chunk) -> mean; then the same for sum (A - mean)^2 -> sigma2.  Two passes, as the host takes them.
+//   lag batch    workgroups per (series, origin, lag of the batch, chunk of n): sum (A[n] - mean)(A[n + t] - mean) over the chunk; one
+//                thread per (origin, lag) merges in the order (series, chunk); one thread per origin walks the lags of the batch in
+//                order, applies the stopping rule and carries (g, done, last lag) to the next batch
 //
 // Chunk c is the samples [c * TS_CHUNK, (c + 1) * TS_CHUNK) whatever the origin and the lag, clipped to the range a sum runs over,
 // and thread i of a workgroup always takes the samples c * TS_CHUNK + i, + 256, ...: a sum has one fixed order, set by (A, origin,
@@ -12,8 +14,9 @@
 //
 // Until it stops, every origin visits the same lags (1, 2, 3, ... or 1, 2, 4, 7, ...), so the lag and the increment a batch starts
 // at are the host's, one pair for all origins, and a batch is (first lag, first increment, number of lags).
-#include "remd_internal.h"
+#include "device_object.h"
 #include "../../include/remd_hip_timeseries.h"
+#include "../../include/remd_hip_energy_store.h"
 #include <cmath>
 #include <limits>
 
@@ -23,15 +26,7 @@
 #define TS_PARTIAL_CAP  (int64_t(1) << 22)      // doubles of per-chunk partials at most (32 MiB)
 #define TS_GROUP_MAX    32768                   // origins of one pass over the series at most (a grid dimension)
 
-// lanes by __shfl_down, then the four waves in wave order: one fixed order; every thread gets the result
-__device__ __forceinline__ double ts_block_sum(double v, double* sh)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
+static_assert(REMD_SERIES_MAX_BATCH == REMD_TIMESERIES_MAX_BATCH, "both entries walk batches of one size");
 
 // lag b of a batch that starts at lag t0 with increment inc0, and the increment that goes with it
 __device__ __forceinline__ int64_t ts_lag(int64_t t0, int64_t inc0, int fast, int b)
@@ -40,44 +35,51 @@ __device__ __forceinline__ int64_t ts_lag(int64_t t0, int64_t inc0, int fast, in
 }
 __device__ __forceinline__ int64_t ts_increment(int64_t inc0, int fast, int b) { return fast ? inc0 + b : 1; }
 
+// Every kernel and the host loop are written once, for K series and S origins, and compiled twice.  SEVERAL = 0: one series (k = 0,
+// K = 1 to the compiler), any origins.  SEVERAL = 1: K series and the one origin 0 (s = 0, t_s = 0 to the compiler; no origin or active
+// list is read).  What folds away leaves the arithmetic of each case as it was when the two were separate files.
+
 // ---- moments --------------------------------------------------------------------------------------------------------------------
-// grid (chunks from the origin's own first chunk on, origins): partial[x * S + s] = sum over chunk ∩ [t_s, N) of A (SQUARED = 0) or
-// of (A - mean_s)^2 (SQUARED = 1)
-template <int SQUARED>
+// grid (chunks from the origin's own first chunk on, origins or series): partial[(k * chunks + c) * S + s] = sum over chunk ∩ [t_s, N)
+// of series k of A (SQUARED = 0) or of (A - mean_s)^2 (SQUARED = 1)
+template <int SQUARED, int SEVERAL>
 __global__ __launch_bounds__(TS_BLOCK) void ts_moment_kernel(const double* __restrict__ A, int64_t N, const int64_t* __restrict__ origin,
                                                              const double* __restrict__ mean, double* __restrict__ partial)
 {
     __shared__ double sh[4];
-    const int s = blockIdx.y;
-    const int64_t ts = origin[s];
+    const int s = SEVERAL ? 0 : blockIdx.y, k = SEVERAL ? blockIdx.y : 0;
+    const int64_t ts = SEVERAL ? 0 : origin[s];
     const int64_t n0 = (ts / TS_CHUNK + blockIdx.x) * TS_CHUNK;
     if (n0 >= N) return;                                                 // (the whole workgroup: this origin has fewer chunks)
     const int64_t hi = n0 + TS_CHUNK < N ? n0 + TS_CHUNK : N;
+    const double* a = A + (int64_t)k * N;
     const double m = SQUARED ? mean[s] : 0.0;
     double acc = 0.0;
     for (int64_t n = n0 + threadIdx.x; n < hi; n += TS_BLOCK)
         if (n >= ts) {
-            const double d = A[n] - m;
+            const double d = a[n] - m;
             acc += SQUARED ? d * d : d;
         }
-    const double t = ts_block_sum(acc, sh);
-    if (threadIdx.x == 0) partial[(int64_t)blockIdx.x * gridDim.y + s] = t;
+    const double t = block_sum(acc, sh);
+    if (threadIdx.x == 0) partial[((int64_t)k * gridDim.x + blockIdx.x) * (SEVERAL ? 1 : gridDim.y) + s] = t;
 }
 
-// one thread per origin adds its chunks in chunk order.  SQUARED = 0: the mean, and the walk's state at its start; SQUARED = 1: sigma2,
-// and a suffix without variance is marked and done
-template <int SQUARED>
-__global__ void ts_moment_merge_kernel(const double* __restrict__ partial, int64_t N, const int64_t* __restrict__ origin, int S,
-                                       double* __restrict__ mean, double* __restrict__ sigma2, double* __restrict__ g,
-                                       int* __restrict__ done, int* __restrict__ status, int64_t* __restrict__ last_lag)
+// one thread per origin adds the series in order, of each its chunks in chunk order (`stride` chunks per series).  SQUARED = 0: the
+// mean, and the walk's state at its start; SQUARED = 1: sigma2, and a suffix without variance is marked and done
+template <int SQUARED, int SEVERAL>
+__global__ void ts_moment_merge_kernel(const double* __restrict__ partial, int series, int64_t N, int64_t stride,
+                                       const int64_t* __restrict__ origin, int S, double* __restrict__ mean, double* __restrict__ sigma2,
+                                       double* __restrict__ g, int* __restrict__ done, int* __restrict__ status, int64_t* __restrict__ last_lag)
 {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= S) return;
-    const int64_t ts = origin[s];
+    const int K = SEVERAL ? series : 1;
+    const int64_t ts = SEVERAL ? 0 : origin[s];
     const int64_t chunks = (N - 1) / TS_CHUNK - ts / TS_CHUNK + 1;
     double sum = 0.0;
-    for (int64_t k = 0; k < chunks; k++) sum += partial[k * S + s];
-    const double v = sum / (double)(N - ts);
+    for (int k = 0; k < K; k++)
+        for (int64_t c = 0; c < chunks; c++) sum += partial[(k * stride + c) * S + s];
+    const double v = sum / (double)((int64_t)K * (N - ts));
     if (!SQUARED) {
         mean[s] = v; g[s] = 1.0; done[s] = 0; status[s] = 0; last_lag[s] = 0;
     } else {
@@ -88,58 +90,78 @@ __global__ void ts_moment_merge_kernel(const double* __restrict__ partial, int64
 
 // ---- lag batches ----------------------------------------------------------------------------------------------------------------
 struct ts_batch {
-    const double* A; int64_t N;
+    const double* A; int K; int64_t N;
     const int64_t* origin; const double* mean; const double* sigma2;      // per origin of the group
     const int* active; int n_active;                                     // the origins that have not stopped
     int64_t t0, inc0; int fast, B, mintime;
-    double* partial;                                                     // [chunk from the origin's first][active][B]
+    int64_t chunks;                                                      // of the batch's first lag and the longest suffix: the most
+    double* partial;                                                     // ts_partial
     double* lagsum;                                                      // [active][B]
     double* g; int* done; int64_t* last_lag;
 };
 
-// grid (chunks, B, active)
+// where the sum of (series k, chunk c from the origin's first) goes for slot = active origin * B + lag of the batch.  Many origins:
+// the chunk is the slowest index, so the merge threads read side by side.  Several series have one origin and at most 64 merge
+// threads: each keeps a run of its own, [slot][series][chunk], and meets every cache line once (with the chunk slowest the merge of
+// K = 24, N = 94 500 took 1.6 times as long)
+template <int SEVERAL>
+__device__ __forceinline__ int64_t ts_partial(const ts_batch& a, int k, int64_t c, int64_t slot)
+{
+    return SEVERAL ? (slot * a.K + k) * a.chunks + c : c * a.n_active * a.B + slot;
+}
+
+// grid (chunks, B, active origins or series)
+template <int SEVERAL>
 __global__ __launch_bounds__(TS_BLOCK) void ts_lag_kernel(ts_batch a)
 {
     __shared__ double sh[4];
-    const int s = a.active[blockIdx.z];
-    const int64_t ts = a.origin[s];
+    const int i = SEVERAL ? 0 : blockIdx.z, k = SEVERAL ? blockIdx.z : 0;
+    const int s = SEVERAL ? 0 : a.active[i];
+    const int64_t ts = SEVERAL ? 0 : a.origin[s];
     const int64_t t = ts_lag(a.t0, a.inc0, a.fast, blockIdx.y);
     if (t >= a.N - ts - 1) return;                                       // the walk stops before this lag
     const int64_t end = a.N - t;                                         // n + t < N for every n below it
     const int64_t n0 = (ts / TS_CHUNK + blockIdx.x) * TS_CHUNK;
     if (n0 >= end) return;
     const int64_t hi = n0 + TS_CHUNK < end ? n0 + TS_CHUNK : end;
+    const double* A = a.A + (int64_t)k * a.N;
     const double m = a.mean[s];
     double acc = 0.0;
     for (int64_t n = n0 + threadIdx.x; n < hi; n += TS_BLOCK)
-        if (n >= ts) acc += (a.A[n] - m) * (a.A[n + t] - m);
-    const double v = ts_block_sum(acc, sh);
-    if (threadIdx.x == 0) a.partial[((int64_t)blockIdx.x * a.n_active + blockIdx.z) * a.B + blockIdx.y] = v;
+        if (n >= ts) acc += (A[n] - m) * (A[n + t] - m);
+    const double v = block_sum(acc, sh);
+    if (threadIdx.x == 0) a.partial[ts_partial<SEVERAL>(a, k, blockIdx.x, (int64_t)i * a.B + blockIdx.y)] = v;
 }
 
-// one thread per (active origin, lag): the chunks [t_s / chunk, (N - t - 1) / chunk] in order, each of which the lag kernel wrote
+// one thread per (active origin, lag): the series in order, of each the chunks [t_s / chunk, (N - t - 1) / chunk] in order, each of
+// which the lag kernel wrote
+template <int SEVERAL>
 __global__ __launch_bounds__(TS_BLOCK) void ts_lag_merge_kernel(ts_batch a)
 {
     const int64_t idx = (int64_t)blockIdx.x * TS_BLOCK + threadIdx.x;
     if (idx >= (int64_t)a.n_active * a.B) return;
-    const int s = a.active[idx / a.B];
-    const int64_t ts = a.origin[s];
+    const int K = SEVERAL ? a.K : 1;
+    const int s = SEVERAL ? 0 : a.active[idx / a.B];
+    const int64_t ts = SEVERAL ? 0 : a.origin[s];
     const int64_t t = ts_lag(a.t0, a.inc0, a.fast, (int)(idx % a.B));
     double sum = 0.0;
     if (t < a.N - ts - 1) {
         const int64_t chunks = (a.N - t - 1) / TS_CHUNK - ts / TS_CHUNK + 1;
-        for (int64_t k = 0; k < chunks; k++) sum += a.partial[k * a.n_active * a.B + idx];
+        for (int k = 0; k < K; k++)
+            for (int64_t c = 0; c < chunks; c++) sum += a.partial[ts_partial<SEVERAL>(a, k, c, idx)];
     }
     a.lagsum[idx] = sum;
 }
 
-// one thread per active origin: the loop of analysis.statistical_inefficiency over the lags of this batch
+// one thread per active origin: the loop of analysis.statistical_inefficiency (_multiple) over the lags of this batch
+template <int SEVERAL>
 __global__ void ts_walk_kernel(ts_batch a)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n_active) return;
-    const int s = a.active[i];
-    const int64_t Ns = a.N - a.origin[s];
+    const int K = SEVERAL ? a.K : 1;
+    const int s = SEVERAL ? 0 : a.active[i];
+    const int64_t Ns = a.N - (SEVERAL ? 0 : a.origin[s]);
     const double sigma2 = a.sigma2[s];
     double g = a.g[s];
     int64_t last = a.last_lag[s];
@@ -147,7 +169,7 @@ __global__ void ts_walk_kernel(ts_batch a)
     for (int b = 0; b < a.B; b++) {
         const int64_t t = ts_lag(a.t0, a.inc0, a.fast, b);
         if (t >= Ns - 1) { done = 1; break; }
-        const double C = a.lagsum[(int64_t)i * a.B + b] / ((double)(Ns - t) * sigma2);
+        const double C = a.lagsum[(int64_t)i * a.B + b] / ((double)K * (double)(Ns - t) * sigma2);
         if (C <= 0.0 && t > a.mintime) { done = 1; break; }
         g += 2.0 * C * (1.0 - (double)t / (double)Ns) * (double)ts_increment(a.inc0, a.fast, b);
         last = t;
@@ -157,76 +179,72 @@ __global__ void ts_walk_kernel(ts_batch a)
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
 struct remd_timeseries_ctx {
-    int device = 0;
+    int K = 1;
     int64_t N = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
-    double ms = 0.0;                        // kernels of the last call
-    dev_array<double> A, mean, sigma2, g, partial, lagsum;
-    dev_array<int64_t> origin, last_lag;
-    dev_array<int> done, status, active;
-    ~remd_timeseries_ctx()
-    {
-        hipSetDevice(device);
-        if (stream) { hipStreamSynchronize(stream); hipStreamDestroy(stream); }
-        if (ev0) hipEventDestroy(ev0);
-        if (ev1) hipEventDestroy(ev1);
-    }
+    dev_array<double> A, partial, lagsum;
+    dev_array<int64_t> state;               // per origin of a group: mean, sigma2, g, origin, last lag, then done, status, active
+    device_timer tm;                        // ms: the kernels of the last call
 };
 
-#define TS_CHECK(expr) do { const hipError_t _e = (expr); if (_e != hipSuccess) return remd_hip_fail(nullptr, #expr, _e); } while (0)
-
-// the launches between ts_begin and ts_end are timed; ts_end waits for them
-static int ts_begin(remd_timeseries ts) { TS_CHECK(hipEventRecord(ts->ev0, ts->stream)); return 0; }
-static int ts_end(remd_timeseries ts)
+// K series of length N on `device`, A [K][N]
+static int ts_open(const char* who, int device, int K, int64_t N, const double* A, std::unique_ptr<remd_timeseries_ctx>& ts)
 {
-    TS_CHECK(hipGetLastError());
-    TS_CHECK(hipEventRecord(ts->ev1, ts->stream));
-    TS_CHECK(hipStreamSynchronize(ts->stream));
-    float t = 0.0f;
-    TS_CHECK(hipEventElapsedTime(&t, ts->ev0, ts->ev1));
-    ts->ms += t;
+    REMD_TRY(select_device(who, device));
+    ts.reset(new remd_timeseries_ctx());
+    ts->K = K; ts->N = N;
+    REMD_TRY(ts->tm.open(device));
+    REMD_TRY(ts->A.alloc(nullptr, (size_t)K * (size_t)N));
+    DEVICE_CHECK(hipMemcpy(ts->A, A, sizeof(double) * (size_t)K * (size_t)N, hipMemcpyHostToDevice));
     return 0;
 }
 
-// g, status and last lag of the S origins of one group (S <= TS_GROUP_MAX, S * chunks of the series <= TS_PARTIAL_CAP where that can be)
-static int ts_group(remd_timeseries ts, int S, const int64_t* origin, int fast, int mintime, double* g, int32_t* status, int64_t* last_lag)
+// g, status and last lag of the S origins of one group (S <= TS_GROUP_MAX, S * chunks of the series <= TS_PARTIAL_CAP where that can
+// be).  SEVERAL: the K series of ts taken together, S = 1 and the origin 0.  The result does not depend on first_batch
+template <int SEVERAL>
+static int ts_group(remd_timeseries ts, int S, const int64_t* origin, int fast, int mintime, int first_batch, double* g, int32_t* status,
+                    int64_t* last_lag)
 {
     const int64_t N = ts->N;
+    const int K = SEVERAL ? ts->K : 1;
     const int64_t all_chunks = (N - 1) / TS_CHUNK + 1;
-    const size_t cap = (size_t)std::max<int64_t>(TS_PARTIAL_CAP, (int64_t)S * all_chunks);
-    REMD_TRY(ts->partial.grow(nullptr, cap));
+    REMD_TRY(ts->partial.grow(nullptr, (size_t)std::max<int64_t>(TS_PARTIAL_CAP, (int64_t)K * S * all_chunks)));
     REMD_TRY(ts->lagsum.grow(nullptr, (size_t)S * REMD_TIMESERIES_MAX_BATCH));
-    REMD_TRY(ts->origin.grow(nullptr, S));
-    REMD_TRY(ts->last_lag.grow(nullptr, S));
-    REMD_TRY(ts->mean.grow(nullptr, S));
-    REMD_TRY(ts->sigma2.grow(nullptr, S));
-    REMD_TRY(ts->g.grow(nullptr, S));
-    REMD_TRY(ts->done.grow(nullptr, S));
-    REMD_TRY(ts->status.grow(nullptr, S));
-    REMD_TRY(ts->active.grow(nullptr, S));
-    TS_CHECK(hipMemcpyAsync(ts->origin, origin, sizeof(int64_t) * S, hipMemcpyHostToDevice, ts->stream));
-    TS_CHECK(hipStreamSynchronize(ts->stream));
+    static_assert(sizeof(double) == sizeof(int64_t) && 2 * sizeof(int) == sizeof(int64_t), "the per-origin state is cut from 64-bit words");
+    REMD_TRY(ts->state.grow(nullptr, 5 * (size_t)S + (3 * (size_t)S + 1) / 2));
+    double* d_mean = (double*)ts->state.get();
+    double* d_sigma2 = d_mean + S;
+    double* d_g = d_sigma2 + S;
+    int64_t* d_origin = ts->state.get() + 3 * (size_t)S;
+    int64_t* d_last = d_origin + S;
+    int* d_done = (int*)(d_last + S);
+    int* d_status = d_done + S;
+    int* d_active = d_status + S;
+    const hipStream_t stream = ts->tm.stream;
+    if (!SEVERAL) {
+        DEVICE_CHECK(hipMemcpyAsync(d_origin, origin, sizeof(int64_t) * S, hipMemcpyHostToDevice, stream));
+        DEVICE_CHECK(hipStreamSynchronize(stream));
+    }
 
     // moments: mean, then sigma2 around it
     int64_t first = origin[0];
     for (int s = 1; s < S; s++) first = std::min(first, origin[s]);
-    const dim3 mgrid((unsigned)(all_chunks - first / TS_CHUNK), (unsigned)S);
+    const int64_t mchunks = all_chunks - first / TS_CHUNK;
+    const dim3 mgrid((unsigned)mchunks, (unsigned)(SEVERAL ? K : S));
     const dim3 sgrid((unsigned)((S + 63) / 64));
-    REMD_TRY(ts_begin(ts));
-    hipLaunchKernelGGL(ts_moment_kernel<0>, mgrid, dim3(TS_BLOCK), 0, ts->stream, ts->A.get(), N, ts->origin.get(), ts->mean.get(), ts->partial.get());
-    hipLaunchKernelGGL(ts_moment_merge_kernel<0>, sgrid, dim3(64), 0, ts->stream, ts->partial.get(), N, ts->origin.get(), S, ts->mean.get(),
-                       ts->sigma2.get(), ts->g.get(), ts->done.get(), ts->status.get(), ts->last_lag.get());
-    hipLaunchKernelGGL(ts_moment_kernel<1>, mgrid, dim3(TS_BLOCK), 0, ts->stream, ts->A.get(), N, ts->origin.get(), ts->mean.get(), ts->partial.get());
-    hipLaunchKernelGGL(ts_moment_merge_kernel<1>, sgrid, dim3(64), 0, ts->stream, ts->partial.get(), N, ts->origin.get(), S, ts->mean.get(),
-                       ts->sigma2.get(), ts->g.get(), ts->done.get(), ts->status.get(), ts->last_lag.get());
-    REMD_TRY(ts_end(ts));
+    REMD_TRY(ts->tm.begin());
+    hipLaunchKernelGGL((ts_moment_kernel<0, SEVERAL>), mgrid, dim3(TS_BLOCK), 0, stream, ts->A.get(), N, d_origin, d_mean, ts->partial.get());
+    hipLaunchKernelGGL((ts_moment_merge_kernel<0, SEVERAL>), sgrid, dim3(64), 0, stream, ts->partial.get(), K, N, mchunks, d_origin, S, d_mean,
+                       d_sigma2, d_g, d_done, d_status, d_last);
+    hipLaunchKernelGGL((ts_moment_kernel<1, SEVERAL>), mgrid, dim3(TS_BLOCK), 0, stream, ts->A.get(), N, d_origin, d_mean, ts->partial.get());
+    hipLaunchKernelGGL((ts_moment_merge_kernel<1, SEVERAL>), sgrid, dim3(64), 0, stream, ts->partial.get(), K, N, mchunks, d_origin, S, d_mean,
+                       d_sigma2, d_g, d_done, d_status, d_last);
+    REMD_TRY(ts->tm.end());
 
-    std::vector<int> done(S), active;
-    TS_CHECK(hipMemcpy(done.data(), ts->done, sizeof(int) * S, hipMemcpyDeviceToHost));
+    std::vector<int> done(S), active, sent;
+    DEVICE_CHECK(hipMemcpy(done.data(), d_done, sizeof(int) * S, hipMemcpyDeviceToHost));
     int64_t t0 = 1, inc0 = 1;
-    int ramp = TS_FIRST_BATCH;
+    int ramp = first_batch;
     for (;;) {
         // the origins that go on, and the longest suffix among them
         active.clear();
@@ -236,29 +254,46 @@ static int ts_group(remd_timeseries ts, int S, const int64_t* origin, int fast, 
         if (active.empty()) break;
         const int n_active = (int)active.size();
         const int64_t chunks = (N - t0 - 1) / TS_CHUNK - lo / TS_CHUNK + 1;          // of the batch's first lag, the most
-        const int64_t fit = TS_PARTIAL_CAP / ((int64_t)n_active * chunks);
+        const int64_t fit = TS_PARTIAL_CAP / ((int64_t)K * n_active * chunks);
         const int B = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(ramp, REMD_TIMESERIES_MAX_BATCH), fit));
-        TS_CHECK(hipMemcpyAsync(ts->active, active.data(), sizeof(int) * n_active, hipMemcpyHostToDevice, ts->stream));
-        TS_CHECK(hipStreamSynchronize(ts->stream));
+        if (!SEVERAL && active != sent) {
+            DEVICE_CHECK(hipMemcpyAsync(d_active, active.data(), sizeof(int) * n_active, hipMemcpyHostToDevice, stream));
+            DEVICE_CHECK(hipStreamSynchronize(stream));
+            sent = active;
+        }
         ts_batch a;
-        a.A = ts->A; a.N = N; a.origin = ts->origin; a.mean = ts->mean; a.sigma2 = ts->sigma2; a.active = ts->active; a.n_active = n_active;
-        a.t0 = t0; a.inc0 = inc0; a.fast = fast; a.B = B; a.mintime = mintime;
-        a.partial = ts->partial; a.lagsum = ts->lagsum; a.g = ts->g; a.done = ts->done; a.last_lag = ts->last_lag;
+        a.A = ts->A; a.K = K; a.N = N; a.origin = d_origin; a.mean = d_mean; a.sigma2 = d_sigma2; a.active = d_active; a.n_active = n_active;
+        a.t0 = t0; a.inc0 = inc0; a.fast = fast; a.B = B; a.mintime = mintime; a.chunks = chunks;
+        a.partial = ts->partial; a.lagsum = ts->lagsum; a.g = d_g; a.done = d_done; a.last_lag = d_last;
         const int64_t pairs = (int64_t)n_active * B;
-        REMD_TRY(ts_begin(ts));
-        hipLaunchKernelGGL(ts_lag_kernel, dim3((unsigned)chunks, (unsigned)B, (unsigned)n_active), dim3(TS_BLOCK), 0, ts->stream, a);
-        hipLaunchKernelGGL(ts_lag_merge_kernel, dim3((unsigned)((pairs + TS_BLOCK - 1) / TS_BLOCK)), dim3(TS_BLOCK), 0, ts->stream, a);
-        hipLaunchKernelGGL(ts_walk_kernel, dim3((unsigned)((n_active + 63) / 64)), dim3(64), 0, ts->stream, a);
-        REMD_TRY(ts_end(ts));
-        TS_CHECK(hipMemcpy(done.data(), ts->done, sizeof(int) * S, hipMemcpyDeviceToHost));      // the one read-back of a batch
+        REMD_TRY(ts->tm.begin());
+        hipLaunchKernelGGL(ts_lag_kernel<SEVERAL>, dim3((unsigned)chunks, (unsigned)B, (unsigned)(SEVERAL ? K : n_active)), dim3(TS_BLOCK), 0, stream, a);
+        hipLaunchKernelGGL(ts_lag_merge_kernel<SEVERAL>, dim3((unsigned)((pairs + TS_BLOCK - 1) / TS_BLOCK)), dim3(TS_BLOCK), 0, stream, a);
+        hipLaunchKernelGGL(ts_walk_kernel<SEVERAL>, dim3((unsigned)((n_active + 63) / 64)), dim3(64), 0, stream, a);
+        REMD_TRY(ts->tm.end());
+        DEVICE_CHECK(hipMemcpy(done.data(), d_done, sizeof(int) * S, hipMemcpyDeviceToHost));    // the one read-back of a batch
         for (int b = 0; b < B; b++) { t0 += inc0; if (fast) inc0++; }
         ramp = std::min(2 * ramp, REMD_TIMESERIES_MAX_BATCH);
     }
-    TS_CHECK(hipMemcpy(g, ts->g, sizeof(double) * S, hipMemcpyDeviceToHost));
-    TS_CHECK(hipMemcpy(status, ts->status, sizeof(int32_t) * S, hipMemcpyDeviceToHost));
-    if (last_lag) TS_CHECK(hipMemcpy(last_lag, ts->last_lag, sizeof(int64_t) * S, hipMemcpyDeviceToHost));
+    DEVICE_CHECK(hipMemcpy(g, d_g, sizeof(double) * S, hipMemcpyDeviceToHost));
+    DEVICE_CHECK(hipMemcpy(status, d_status, sizeof(int32_t) * S, hipMemcpyDeviceToHost));
+    if (last_lag) DEVICE_CHECK(hipMemcpy(last_lag, d_last, sizeof(int64_t) * S, hipMemcpyDeviceToHost));
     for (int s = 0; s < S; s++)
         if (!status[s]) g[s] = std::max(g[s], 1.0);
+    return 0;
+}
+
+// g, status and last lag of the K series A_kn [K][N] taken together (remd_series_inefficiency_multiple of energy_store.hip, which has
+// checked the arguments); the first batch has first_batch lags.  ms (the kernels) and chunk (samples per workgroup) may be NULL
+int series_inefficiency(const char* who, int device, int K, int64_t N, const double* A_kn, int fast, int mintime, int first_batch, double* g,
+                        int32_t* status, int64_t* last_lag, double* ms, int64_t* chunk)
+{
+    std::unique_ptr<remd_timeseries_ctx> ts;
+    REMD_TRY(ts_open(who, device, K, N, A_kn, ts));
+    const int64_t origin = 0;
+    REMD_TRY((K > 1 ? ts_group<1> : ts_group<0>)(ts.get(), 1, &origin, fast, mintime, first_batch, g, status, last_lag));
+    if (ms) *ms = ts->tm.ms;
+    if (chunk) *chunk = TS_CHUNK;
     return 0;
 }
 
@@ -272,19 +307,8 @@ int remd_timeseries_create(int device, int64_t N, const double* A, remd_timeseri
     if (!A) return remd_fail(nullptr, -1, "remd_timeseries_create: A is NULL");
     for (int64_t n = 0; n < N; n++)
         if (!std::isfinite(A[n])) return remd_fail(nullptr, -1, "remd_timeseries_create: non-finite sample " + std::to_string(n));
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n == 0)
-        return remd_fail(nullptr, -2, std::string("remd_timeseries_create: no HIP device available (") + hipGetErrorString(e) + ")");
-    if (device < 0 || device >= n) return remd_fail(nullptr, -1, "remd_timeseries_create: bad device index");
-    TS_CHECK(hipSetDevice(device));
-    std::unique_ptr<remd_timeseries_ctx> ts(new remd_timeseries_ctx());
-    ts->device = device; ts->N = N;
-    TS_CHECK(hipStreamCreate(&ts->stream));
-    TS_CHECK(hipEventCreate(&ts->ev0));
-    TS_CHECK(hipEventCreate(&ts->ev1));
-    REMD_TRY(ts->A.alloc(nullptr, (size_t)N));
-    TS_CHECK(hipMemcpy(ts->A, A, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
+    std::unique_ptr<remd_timeseries_ctx> ts;
+    REMD_TRY(ts_open("remd_timeseries_create", device, 1, N, A, ts));
     *out = ts.release();
     return 0;
 }
@@ -302,15 +326,15 @@ int remd_timeseries_inefficiency(remd_timeseries ts, int32_t S, const int64_t* o
         if (origin[s] < 0 || origin[s] > ts->N - 2)
             return remd_fail(nullptr, -1, "remd_timeseries_inefficiency: origin[" + std::to_string(s) + "] = " + std::to_string(origin[s]) +
                                           " is outside 0 ... N - 2 = " + std::to_string(ts->N - 2));
-    TS_CHECK(hipSetDevice(ts->device));
-    ts->ms = 0.0;
+    DEVICE_CHECK(hipSetDevice(ts->tm.device));
+    ts->tm.ms = 0.0;
     ts->timed = false;
     // groups of origins whose per-chunk partials of one lag fit the cap
     const int64_t all_chunks = (ts->N - 1) / TS_CHUNK + 1;
     const int group = (int)std::max<int64_t>(1, std::min<int64_t>(TS_GROUP_MAX, TS_PARTIAL_CAP / all_chunks));
     for (int s0 = 0; s0 < S; s0 += group) {
         const int n = std::min(group, S - s0);
-        REMD_TRY(ts_group(ts, n, origin + s0, fast ? 1 : 0, mintime, g + s0, status + s0, last_lag ? last_lag + s0 : nullptr));
+        REMD_TRY(ts_group<0>(ts, n, origin + s0, fast ? 1 : 0, mintime, TS_FIRST_BATCH, g + s0, status + s0, last_lag ? last_lag + s0 : nullptr));
     }
     ts->timed = true;
     return 0;
@@ -327,7 +351,7 @@ int remd_timeseries_last_ms(remd_timeseries ts, double* ms)
 {
     if (!ts || !ms) return remd_fail(nullptr, -1, "remd_timeseries_last_ms: the timeseries or ms is NULL");
     if (!ts->timed) return remd_fail(nullptr, -1, "remd_timeseries_last_ms: no pass has run on this timeseries yet");
-    *ms = ts->ms;
+    *ms = ts->tm.ms;
     return 0;
 }
 

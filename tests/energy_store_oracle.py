@@ -9,7 +9,7 @@ the order of a sum could decide where the walk stops and no bound on g could hol
 import numpy as np
 from openmmtools_amd.multistate import analysis as an
 
-SERIES_CHUNK = 2048     # ES_SERIES_CHUNK of csrc/energy_store.hip, for the tests without a device
+SERIES_CHUNK = 2048     # TS_CHUNK of csrc/timeseries.hip, for the tests without a device
 EFFECTIVE_CHUNK, GATHER_TILE, COUNT_CHUNK, HIST_MAX_STATES = 256, 32, 8192, 64      # what remd_energy_store_chunks reports
 C_FLOOR = 1e-9
 G_RTOL = 1e-10          # |g_dev - g_np| <= G_RTOL * max(1, g_np): the figure of the timeseries extension

@@ -15,6 +15,7 @@ import pytest
 from openmmtools_amd._engine import DeviceEnergyStore, series_inefficiency_multiple
 from openmmtools_amd.multistate import analysis as an
 import energy_store_oracle as eo
+import analysis_device_bits as adb
 
 pytestmark = pytest.mark.gpu
 EPS = 2.0 ** -52
@@ -208,6 +209,15 @@ def test_constant_series_are_status_1_and_the_hosts_value_error():
     for solver in ('numpy', 'device'):
         with pytest.raises(ValueError, match='sample covariance is zero'):
             an.statistical_inefficiency_multiple(A, solver=solver)
+
+
+def test_every_result_has_the_bits_recorded_before_the_passes_were_shared():
+    """tests/golden/analysis_device_bits.npz (tests/analysis_device_bits.py): g as uint64, status and last lag of every several-series
+    case; one case per kernel family of the MBAR passes and the effective energy with SAMS weights, whose scaffolding is shared"""
+    adb.assert_same_bits(adb.several_series(eo.SERIES_CHUNK), 'several')
+    now = adb.mbar_and_energy_store()
+    adb.assert_same_bits({k: v for k, v in now.items() if k.startswith('mbar/')}, 'mbar')
+    adb.assert_same_bits({k: v for k, v in now.items() if k.startswith('energy_store/')}, 'energy_store')
 
 
 # ---- refusals -----------------------------------------------------------------------------------------------------------------------

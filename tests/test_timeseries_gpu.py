@@ -8,10 +8,11 @@ import functools
 import numpy as np
 import pytest
 from openmmtools_amd import testsystems, states, mcmc, unit
-from openmmtools_amd._engine import DeviceTimeseries, TIMESERIES_MAX_BATCH
+from openmmtools_amd._engine import DeviceTimeseries, TIMESERIES_MAX_BATCH, series_inefficiency_multiple
 from openmmtools_amd.multistate import ReplicaExchangeSampler, MultiStateReporter
 from openmmtools_amd.multistate import analysis as an
 import timeseries_cases as tc
+import analysis_device_bits as adb
 
 pytestmark = pytest.mark.gpu
 
@@ -152,6 +153,24 @@ def test_results_are_bit_identical_from_run_to_run_and_whatever_shares_the_call(
             alone, _, last_alone = other.inefficiency([hundred[i]], fast=fast)
             assert alone[0] == g[i] and last_alone[0] == last[i]
     assert first.last_ms() > 0.0
+
+
+def test_every_result_has_the_bits_recorded_before_the_passes_were_shared():
+    """tests/golden/analysis_device_bits.npz (tests/analysis_device_bits.py): g as uint64, status and last lag of every single-series case"""
+    adb.assert_same_bits(adb.single_series(_chunk()), 'single')
+
+
+@pytest.mark.parametrize('N', [2, 100, tc.CHUNK + 1, 3 * tc.CHUNK + 7])
+def test_one_series_through_the_several_series_entry_is_the_single_series_at_origin_0_to_the_bit(N):
+    """K = 1: the normalisations differ by an exact factor 1.0 and the merge order (series, chunk) is the chunk order"""
+    A = tc.series('ar05', N)
+    ts = DeviceTimeseries(A)
+    for fast, mintime in adb.SETTINGS:
+        g, status, last = ts.inefficiency([0], fast=fast, mintime=mintime)
+        g_k, status_k, last_k = series_inefficiency_multiple(A[None, :], fast=fast, mintime=mintime)[:3]
+        assert np.float64(g_k).view(np.uint64) == g.view(np.uint64)[0], (fast, mintime, g_k, g[0])
+        assert (status_k, last_k) == (status[0], last[0]), (fast, mintime)
+    ts.close()
 
 
 def test_refusals_by_message():
