@@ -12,7 +12,7 @@
 //   alchemical soft-core sterics        alchemy/alchemy.py:1383-1388 (softcore_c = 6 closed form)
 // The f64 restatement used for parity is oracle/md_oracle.py.
 //
-// Nonbonded design: atoms are kept in a spatial (Morton) order of whole molecules; 8-atom clusters of that order are
+// Nonbonded design: atoms are kept in a spatial (Hilbert-curve) order of whole molecules; 8-atom clusters of that order are
 // paired through per-tile union lists with every cluster pair listed once (nonbonded_sci_kernel, Newton's third law);
 // a list that outgrows its capacity, or a system without sortable molecules, runs on the 64-atom tile kernel
 // (nonbonded_kernel: lane = atom i, wave-uniform j stream, each pair from both sides, exclusions as a bit window).
@@ -40,6 +40,63 @@
 
 #define MAX_EXCL_WORDS 8
 
+struct gather_args; struct sci_list_args; struct sci_args;       // kernel arguments, defined beside their kernels
+
+// One sorted system of the direct-space pair path -- every atom, or the LJ-only sub-system of an Ewald / reaction-field run -- for the
+// replicas of one handle: the order, what the gather and list launches write in it, and the accumulator the pair kernel adds to.
+// N, Npad and words describe the system (remd_build_nonbonded); everything else is made by alloc for R replicas.
+struct nb_sorted {
+    int N = 0, Npad = 0, words = 1;       // atoms, padded to whole 64-atom tiles; 64-bit exclusion words per atom
+    int cap = 0;                          // entries per tile list
+    int excl_W = 0;                       // near-diagonal exclusion words per cluster
+    dev_array<int> d_order;               // [R][Npad] sorted slot -> atom (-1: padding)
+    dev_array<float4> d_spos;             // [R][Npad] positions in sorted order (refreshed every evaluation)
+    dev_array<float4> d_sposi;            // [R][Npad] the same as 32-bit box fractions (bit patterns in x, y, z) + charge in w
+    dev_array<float4> d_sparam;           // [R][Npad]
+    dev_array<unsigned long long> d_smask;// [R][Npad][words]
+    dev_array<float4> d_tile_c, d_tile_h; // [R][ntile] bounding-box centre / half extent
+    // 8-atom cluster pair lists (sorted slot space): lane = (i atom, j atom) of an 8 x 8 cluster pair
+    dev_array<float4> d_cl_c, d_cl_h;     // [R][ncl] cluster bounding boxes
+    // Newton's-third-law path: per-tile union lists (jc | imask << 16) and near-diagonal exclusion words
+    dev_array<unsigned int> d_sci_list;   // [R][ntile][cap]
+    dev_array<int> d_sci_count;           // [R][ntile]
+    dev_array<unsigned long long> d_excl; // [R][ncl][excl_W]
+    dev_array<long long> d_sforce;        // [R][3][Npad] forces in sorted slot space
+
+    int ntile() const { return Npad / 64; }
+    int ncl() const { return Npad / 8; }
+    void release();
+    int alloc(remd_ctx* h, int R);
+    int alloc_clusters(remd_ctx* h, int R, hipStream_t st);
+    hipError_t clear_forces(int R, hipStream_t st) const;
+    gather_args gather(bool charges) const;
+    sci_list_args list() const;
+    sci_args pair(int ep_off, int nsplit, const int* tile_of_rank) const;
+};
+
+// How many workgroups of the pair kernel stay resident next to the mesh kernels (0 = one per item) is a balance between
+// the two streams that depends on the system (24 x alanine dipeptide: 2 per CU is 4 % faster than one per item, 8 x
+// host-guest: 7 % slower), so it is measured: during the first long remd_run_steps the candidates take turns over
+// segments of TUNE_SEG real MD steps timed with events; results are bit-identical under every choice (fixed-point sums).
+struct nb_tuner {
+    struct seg { int cand; hipEvent_t a, b; };            // cand: index into g_tune_cands; each segment owns its pair of events
+    std::vector<seg> segs;
+    int state = 0 /* 0 measuring, 1 awaiting resolve, 2 done */, left = 0, next = 0;
+    int grid = 0;                         // current choice (workgroups; 0 = one per item)
+    int prio = 0;                         // current choice: 1 = the pair kernel runs at raised wave priority and the mesh kernels do not
+    void drop_segs()
+    {
+        for (auto& sg : segs) { if (sg.a) hipEventDestroy(sg.a); if (sg.b) hipEventDestroy(sg.b); }
+        segs.clear();
+    }
+    nb_tuner() = default;
+    nb_tuner(const nb_tuner&) = delete;
+    nb_tuner& operator=(const nb_tuner&) = delete;
+    ~nb_tuner() { drop_segs(); }
+};
+
+// What a handle's NonbondedForce needs on the device: the force-field parameters and exclusions in atom order, the alchemical state
+// behind u_kl, the molecule order with the two sorted systems of the pair path, the residency tuner, and the Coulomb table.
 struct nb_tables {
     nb_params p{};
     int method = NB_LJ_ONLY;
@@ -54,6 +111,7 @@ struct nb_tables {
     int n_excl = 0; dev_array<int> d_excl_atoms; dev_array<float> d_excl_qq;      // all excluded pairs (Ewald correction)
     dev_array<float> d_rep_lam;           // [R][4] per replica: lambda_s^a, alpha (1-lambda_s)^b, lambda_e, pad
     int rep_lam_R = 0;
+    std::vector<float> rep_lam_host;      // what d_rep_lam holds
     std::vector<double> state_lam_a, state_sc;   // per state, for the alchemical u_kl kernel
     dev_array<double> d_state_lam;        // [K][2]
     dev_array<double> d_alch_ukl;         // [R][K]
@@ -65,49 +123,26 @@ struct nb_tables {
     std::vector<double> charge;           // original charges
     std::vector<char> is_alch;
     // spatial ordering: exclusion/constraint-connected groups (molecules) stay contiguous, groups are ordered
-    // along a Morton curve of their cells every resort_interval force evaluations
+    // along a Hilbert curve of their cells every resort_interval force evaluations
     int n_groups = 0; dev_array<int> d_grp_first; dev_array<int> d_grp_size;
-    dev_array<int> d_order;               // [R][Npad] sorted slot -> atom (-1: padding)
-    dev_array<float4> d_spos;             // [R][Npad] positions in sorted order (refreshed every evaluation)
-    dev_array<float4> d_sposi;            // [R][Npad] the same as 32-bit box fractions (bit patterns in x, y, z) + charge in w
-    dev_array<float4> d_lj_sposi;         // [R][NLpad] the LJ sub-system's
-    dev_array<float4> d_sparam;           // [R][Npad]
-    dev_array<unsigned long long> d_smask;// [R][Npad][excl_words]
-    dev_array<float4> d_tile_c; dev_array<float4> d_tile_h;   // [R][ntile] bounding-box centre / half extent
-    dev_array<float4> d_partial;          // [R][n_jsplit][Npad] nonbonded force partials (grown on demand)
-    // 8-atom cluster pair lists (sorted slot space): lane = (i atom, j atom) of an 8 x 8 cluster pair
-    dev_array<float4> d_cl_c; dev_array<float4> d_cl_h;     // [R][ncl] cluster bounding boxes
-    int cl_cap = 0; bool clusters = true;
-    // LJ-active sub-system (atoms with eps != 0; 1/3 of a TIP3P box): own sorted order, clusters and pair list, so
-    // that the main cluster kernel is Coulomb-only
-    bool lj_split = false; int NL = 0, NLpad = 0, lj_words = 1, lj_cap = 0;
-    dev_array<int> d_lj_ord;              // [Npad] atom -> LJ ordinal (-1: no LJ)
-    dev_array<unsigned long long> d_lj_mask;   // [NLpad][lj_words] exclusion window in LJ-ordinal space
-    dev_array<int> d_lj_order; dev_array<float4> d_lj_spos; dev_array<float4> d_lj_sparam; dev_array<unsigned long long> d_lj_smask;
-    dev_array<float4> d_lj_tile_c; dev_array<float4> d_lj_tile_h; dev_array<float4> d_lj_cl_c; dev_array<float4> d_lj_cl_h;
-    // Newton's-third-law path: per-tile union lists (jc | imask << 16) and near-diagonal exclusion words
-    int sci_split = 12;     // list slices per tile (workgroups of 4 wavefronts); set per system in remd_build_nonbonded
-    dev_array<unsigned int> d_sci_list; dev_array<int> d_sci_count; dev_array<unsigned long long> d_excl; int excl_W = 0;
-    dev_array<long long> d_sforce; dev_array<long long> d_lj_sforce;   // [R][3][Npad] / [R][3][NLpad] forces in sorted slot space
-    dev_array<unsigned int> d_lj_sci_list; dev_array<int> d_lj_sci_count; dev_array<unsigned long long> d_lj_excl; int lj_excl_W = 0;
-    int sort_R = 0; int evals_since_sort = 1 << 30; int resort_interval = 40; bool sorting = true;
-    std::vector<float> rep_lam_host;      // what d_rep_lam holds
-    dev_array<unsigned int> d_queue;      // item queues of the resident-workgroup pair kernel: [0] Coulomb, [1] LJ, [2] workgroups done
-    // How many workgroups of the pair kernel stay resident next to the mesh kernels (0 = one per item) is a balance between
-    // the two streams that depends on the system (24 x alanine dipeptide: 2 per CU is 4 % faster than one per item, 8 x
-    // host-guest: 7 % slower), so it is measured: during the first long remd_run_steps the candidates take turns over
-    // segments of TUNE_SEG real MD steps timed with events; results are bit-identical under every choice (fixed-point sums).
-    struct tune_seg { int cand; hipEvent_t a, b; };       // cand: index into g_tune_cands
-    int nb_prio = 0;                      // current choice: 1 = the pair kernel runs at raised wave priority and the mesh kernels do not
-    std::vector<tune_seg> tune_segs; int tune_state = 0 /* 0 measuring, 1 awaiting resolve, 2 done */, tune_left = 0, tune_next = 0;
-    int nb_grid = 0;                      // current choice (workgroups; 0 = one per item)
     int sort_hbits = 0;                   // 2^sort_hbits cells per box edge along the Hilbert curve (0: not chosen yet)
+    dev_array<int> d_sort_scratch;        // sort_groups_large_kernel (more than 8191 molecules), grown on demand
+    int sort_R = 0; int evals_since_sort = 1 << 30; int resort_interval = 40; bool sorting = true;
+    bool clusters = true;                 // the cluster-pair path (false: REMD_NB_TILES, or a list outgrew its capacity)
+    int sci_split = 12;                   // list slices per tile (workgroups of 4 wavefronts); set per system in remd_build_nonbonded
+    // LJ-active sub-system (atoms with eps != 0; 1/3 of a TIP3P box): own sorted order, clusters and pair list, so
+    // that the main cluster kernel is Coulomb-only.  The maps describe the system; lj.N, lj.Npad and lj.words are set with them
+    bool lj_split = false;
+    dev_array<int> d_lj_ord;              // [Npad] atom -> LJ ordinal (-1: no LJ)
+    dev_array<unsigned long long> d_lj_mask;   // [lj.Npad][lj.words] exclusion window in LJ-ordinal space
+    nb_sorted main, lj;                   // the replicas' sorted state: every atom / the LJ sub-system
+    dev_array<int> d_tile_of_rank;        // [R][ntile] the main system's tiles by descending list length, refreshed with the molecule order
+    dev_array<unsigned int> d_queue;      // item queues of the resident-workgroup pair kernel: [0] Coulomb, [1] LJ, [2] workgroups done
+    dev_array<unsigned int> d_pair_done; unsigned int pair_done_target = 0;      // remd_fold_args: the scatter launch's done counter
+    dev_array<float4> d_partial;          // [R][n_jsplit][Npad] force partials of the tile kernel (grown on demand)
+    nb_tuner tune;
     // Ewald direct-space force table of the force-only pair kernels (coulomb_table.h); energy evaluations: Abramowitz & Stegun erfc
     dev_array<float4> d_ctab; bool use_table = false;
-    dev_array<unsigned int> d_pair_done; unsigned int pair_done_target = 0;      // remd_fold_args: the scatter launch's done counter
-    dev_array<int> d_tile_of_rank;        // [R][ntile] the main system's tiles by descending list length, refreshed with the molecule order
-    dev_array<int> d_sort_scratch;    // sort_groups_large_kernel (more than 8191 molecules), grown on demand
-    ~nb_tables() { for (auto& sg : tune_segs) { if (sg.a) hipEventDestroy(sg.a); if (sg.b) hipEventDestroy(sg.b); } }
 };
 void remd_table_deleter::operator()(nb_tables* t) const { delete t; }
 
@@ -1510,6 +1545,7 @@ int remd_build_nonbonded(remd_ctx* h, const remd_system_desc* d)
     }
     p.alpha = (float)d->ewald_alpha; p.two_alpha_sqrtpi = (float)(2.0 * d->ewald_alpha / sqrt(M_PI));
     p.excl_words = words;
+    t.main.N = N; t.main.Npad = h->Npad; t.main.words = words;
     // Ewald split (remd_set_coulomb_cutoff): the erfc tail may be summed beyond the NonbondedForce cutoff, with the alpha and
     // the mesh of the descriptor chosen for that range by the host; Lennard-Jones terms keep d->cutoff and its switch
     p.rcc2 = p.rc2;
@@ -1581,19 +1617,20 @@ int remd_build_nonbonded(remd_ctx* h, const remd_system_desc* d)
         for (int i = 0; i < N; ++i) if (d->epsilon[i] != 0.0) ord[i] = NL++;
         t.lj_split = any_charge && NL > 0 && NL * 10 <= N * 6;
         if (t.lj_split) {
-            t.NL = NL; t.NLpad = (NL + 63) / 64 * 64;
+            t.lj.N = NL; t.lj.Npad = (NL + 63) / 64 * 64;
             int maxd_lj = 0;
             for (int e = 0; e < d->n_exceptions; ++e) {
                 const int a = ord[d->exception_atoms[2 * e]], b2 = ord[d->exception_atoms[2 * e + 1]];
                 if (a >= 0 && b2 >= 0) maxd_lj = std::max(maxd_lj, std::abs(a - b2));
             }
-            t.lj_words = std::max(1, (maxd_lj + 32) / 32);
-            if (t.lj_words > MAX_EXCL_WORDS) t.lj_split = false;
+            t.lj.words = std::max(1, (maxd_lj + 32) / 32);
+            if (t.lj.words > MAX_EXCL_WORDS) t.lj_split = false;
         }
         if (t.lj_split) {
-            std::vector<unsigned long long> lm((size_t)t.NLpad * t.lj_words, 0ull);
-            auto setb = [&](int a, int b2) { const int dd = b2 - a + 32 * t.lj_words; lm[(size_t)a * t.lj_words + (dd >> 6)] |= 1ull << (dd & 63); };
-            for (int a = 0; a < t.NL; ++a) setb(a, a);
+            const int lw = t.lj.words;
+            std::vector<unsigned long long> lm((size_t)t.lj.Npad * lw, 0ull);
+            auto setb = [&](int a, int b2) { const int dd = b2 - a + 32 * lw; lm[(size_t)a * lw + (dd >> 6)] |= 1ull << (dd & 63); };
+            for (int a = 0; a < NL; ++a) setb(a, a);
             for (int e = 0; e < d->n_exceptions; ++e) {
                 const int a = ord[d->exception_atoms[2 * e]], b2 = ord[d->exception_atoms[2 * e + 1]];
                 if (a >= 0 && b2 >= 0) { setb(a, b2); setb(b2, a); }
@@ -1647,155 +1684,200 @@ static int update_replica_lambdas(remd_ctx* h, nb_tables& t)
     return 0;
 }
 
-// sorted order (refreshed every resort_interval evaluations), sorted positions + bounding boxes and the super-cluster
-// lists (every evaluation) of the cluster-pair path, on stream st
-static int ensure_sorted(remd_ctx* h, nb_tables& t, hipStream_t st)
+// ---- the sorted systems of the pair path: allocation and kernel arguments ---------------------------------------------------------
+void nb_sorted::release()
 {
-    if (!t.sorting || t.n_groups <= 0) return 0;
-    const int ntile = (h->N + 63) / 64;
-    const bool cl = t.clusters && ntile * 8 < 65536;
-    if (t.sort_R != h->R) {
-        t.d_order.reset(); t.d_spos.reset(); t.d_sparam.reset(); t.d_smask.reset(); t.d_tile_c.reset(); t.d_tile_h.reset();
-        const size_t n = (size_t)h->R * h->Npad;
-        REMD_TRY(t.d_order.alloc(h, n));
-        REMD_TRY(t.d_spos.alloc(h, n));
-        t.d_sposi.reset();
-        REMD_TRY(t.d_sposi.alloc(h, n));
-        REMD_TRY(t.d_sparam.alloc(h, n));
-        REMD_TRY(t.d_smask.alloc(h, n * t.p.excl_words));
-        REMD_TRY(t.d_tile_c.alloc(h, (size_t)h->R * ntile));
-        REMD_TRY(t.d_tile_h.alloc(h, (size_t)h->R * ntile));
-        t.d_pair_done.reset();
-        REMD_TRY(t.d_pair_done.alloc(h, 16 * h->R));       // one arrival counter per replica, 64 bytes apart
-        REMD_CHECK(h, hipMemsetAsync(t.d_pair_done, 0, sizeof(unsigned int) * 16 * h->R, st));
-        t.pair_done_target = 0;
-        t.d_cl_c.reset(); t.d_cl_h.reset();
-        t.d_sci_list.reset(); t.d_sci_count.reset(); t.d_excl.reset(); t.d_sforce.reset(); t.d_lj_sforce.reset();
-        t.d_lj_sci_list.reset(); t.d_lj_sci_count.reset(); t.d_lj_excl.reset();
-        const int ncl = ntile * 8;
-        t.cl_cap = std::min(ncl, 4096);     // whole row for systems up to 32k atoms: a cluster that straddles a large molecule can neighbour half the box
-        if (cl) {
-            REMD_TRY(t.d_cl_c.alloc(h, (size_t)h->R * ncl));
-            REMD_TRY(t.d_cl_h.alloc(h, (size_t)h->R * ncl));
-            t.excl_W = 4 * t.p.excl_words + 1;
-            REMD_TRY(t.d_sci_list.alloc(h, (size_t)h->R * ntile * t.cl_cap));
-            REMD_TRY(t.d_sci_count.alloc(h, (size_t)h->R * ntile));
-            t.d_tile_of_rank.reset();
-            REMD_TRY(t.d_tile_of_rank.alloc(h, (size_t)h->R * ntile));
-            REMD_TRY(t.d_excl.alloc(h, (size_t)h->R * ncl * t.excl_W));
-            REMD_TRY(t.d_sforce.alloc(h, n * 3));
-            REMD_CHECK(h, hipMemsetAsync(t.d_sforce, 0, sizeof(long long) * n * 3, st));
-            if (!t.d_queue) {
-                REMD_TRY(t.d_queue.alloc(h, 4));
-                REMD_CHECK(h, hipMemsetAsync(t.d_queue, 0, 4 * sizeof(unsigned int), st));
-            }
+    d_order.reset(); d_spos.reset(); d_sposi.reset(); d_sparam.reset(); d_smask.reset(); d_tile_c.reset(); d_tile_h.reset();
+    d_cl_c.reset(); d_cl_h.reset(); d_sci_list.reset(); d_sci_count.reset(); d_excl.reset(); d_sforce.reset();
+}
+
+// the sorted accumulator is zero between evaluations (the scatter clears what it takes): at allocation, and after a discarded evaluation
+hipError_t nb_sorted::clear_forces(int R, hipStream_t st) const
+{
+    return d_sforce ? hipMemsetAsync(d_sforce, 0, sizeof(long long) * 3 * (size_t)R * Npad, st) : hipSuccess;
+}
+
+// for R replicas, in two parts (the handle's own R-sized arrays keep their places of old between and behind them: the pair path's
+// launch times follow the addresses, profiles/pair_path_owner_cost.txt).  First what the 64-atom tile kernel reads too: order, sorted
+// positions, parameters, masks, tile boxes
+int nb_sorted::alloc(remd_ctx* h, int R)
+{
+    release();
+    const size_t n = (size_t)R * Npad;
+    cap = std::min(ncl(), 4096);      // whole row for systems up to 32k atoms: a cluster that straddles a large molecule can neighbour half the box
+    excl_W = 4 * words + 1;
+    REMD_TRY(d_order.alloc(h, n));
+    REMD_TRY(d_spos.alloc(h, n));
+    REMD_TRY(d_sposi.alloc(h, n));
+    REMD_TRY(d_sparam.alloc(h, n));
+    REMD_TRY(d_smask.alloc(h, n * words));
+    REMD_TRY(d_tile_c.alloc(h, (size_t)R * ntile()));
+    REMD_TRY(d_tile_h.alloc(h, (size_t)R * ntile()));
+    return 0;
+}
+// ... then what only the cluster-pair path needs
+int nb_sorted::alloc_clusters(remd_ctx* h, int R, hipStream_t st)
+{
+    const size_t n = (size_t)R * Npad;
+    REMD_TRY(d_cl_c.alloc(h, (size_t)R * ncl()));
+    REMD_TRY(d_cl_h.alloc(h, (size_t)R * ncl()));
+    REMD_TRY(d_sci_list.alloc(h, (size_t)R * ntile() * cap));
+    REMD_TRY(d_sci_count.alloc(h, (size_t)R * ntile()));
+    REMD_TRY(d_excl.alloc(h, (size_t)R * ncl() * excl_W));
+    REMD_TRY(d_sforce.alloc(h, n * 3));
+    REMD_CHECK(h, clear_forces(R, st));       // on the evaluation's stream: ordered in front of the pair kernel that adds to it
+    return 0;
+}
+
+// charges: the gather also puts the charge of d_sparam into the w of the sorted positions (the main system's Coulomb-only kernel)
+gather_args nb_sorted::gather(bool charges) const
+{
+    return gather_args{Npad, d_order, d_spos, d_tile_c, d_tile_h, d_cl_c, d_cl_h, charges ? d_sparam.get() : nullptr, d_sposi};
+}
+sci_list_args nb_sorted::list() const
+{
+    return sci_list_args{ncl(), cap, d_cl_c, d_cl_h, d_tile_c, d_tile_h, d_sci_list, d_sci_count};
+}
+// ep_off: the system's first energy slot behind EP_NB0; a system's Npad_force is its own padded count (it adds to its own d_sforce)
+sci_args nb_sorted::pair(int ep_off, int nsplit, const int* tile_of_rank) const
+{
+    return sci_args{N, Npad, ncl(), cap, excl_W, Npad, ep_off, nsplit, d_spos, d_sparam, d_excl, d_sci_list, d_sci_count, d_sforce, d_sposi, tile_of_rank};
+}
+
+// ---- sorted order (refreshed every resort_interval evaluations), sorted positions + bounding boxes and the super-cluster lists
+// (every evaluation) of the cluster-pair path, on stream st: the four steps of ensure_sorted ------------------------------------------
+
+// the cluster-pair path is on: not switched off, and cluster indices fit the 16 bits of a list entry
+static bool nb_cluster_path(const nb_tables& t) { return t.clusters && t.main.ncl() < 65536; }
+
+// 1. the replica count changed (or this is the first evaluation): everything sized by R is made again
+static int sorted_realloc(remd_ctx* h, nb_tables& t, hipStream_t st)
+{
+    const bool cl = nb_cluster_path(t);
+    // the main system keeps order, sorted positions, parameters, masks and tile boxes with the cluster path off too: the tile kernel
+    // reads them; the LJ sub-system exists for the cluster path only
+    REMD_TRY(t.main.alloc(h, h->R));
+    t.d_pair_done.reset();                  // re-made with its target: the counters start at zero
+    REMD_TRY(t.d_pair_done.alloc(h, 16 * h->R));       // one arrival counter per replica, 64 bytes apart
+    REMD_CHECK(h, hipMemsetAsync(t.d_pair_done, 0, sizeof(unsigned int) * 16 * h->R, st));
+    t.pair_done_target = 0;
+    t.lj.release();
+    if (cl) {
+        REMD_TRY(t.main.alloc_clusters(h, h->R, st));
+        // the ranking of the tiles belongs to the main system alone (launch_nb decides whether it is used)
+        REMD_TRY(t.d_tile_of_rank.alloc(h, (size_t)h->R * t.main.ntile()));
+        if (!t.d_queue) {                   // not sized by R: made once and kept
+            REMD_TRY(t.d_queue.alloc(h, 4));
+            REMD_CHECK(h, hipMemsetAsync(t.d_queue, 0, 4 * sizeof(unsigned int), st));
         }
-        if (cl && t.lj_split) {
-            t.d_lj_order.reset(); t.d_lj_spos.reset(); t.d_lj_sparam.reset(); t.d_lj_smask.reset(); t.d_lj_tile_c.reset(); t.d_lj_tile_h.reset();
-            t.d_lj_cl_c.reset(); t.d_lj_cl_h.reset();
-            const size_t nl = (size_t)h->R * t.NLpad;
-            const int ncl_lj = t.NLpad / 8;
-            t.lj_cap = std::min(ncl_lj, 4096);
-            REMD_TRY(t.d_lj_order.alloc(h, nl));
-            REMD_TRY(t.d_lj_spos.alloc(h, nl));
-            t.d_lj_sposi.reset();
-            REMD_TRY(t.d_lj_sposi.alloc(h, nl));
-            REMD_TRY(t.d_lj_sparam.alloc(h, nl));
-            REMD_TRY(t.d_lj_smask.alloc(h, nl * t.lj_words));
-            REMD_TRY(t.d_lj_tile_c.alloc(h, (size_t)h->R * (t.NLpad / 64)));
-            REMD_TRY(t.d_lj_tile_h.alloc(h, (size_t)h->R * (t.NLpad / 64)));
-            REMD_TRY(t.d_lj_cl_c.alloc(h, (size_t)h->R * ncl_lj));
-            REMD_TRY(t.d_lj_cl_h.alloc(h, (size_t)h->R * ncl_lj));
-            t.lj_excl_W = 4 * t.lj_words + 1;
-            REMD_TRY(t.d_lj_sci_list.alloc(h, (size_t)h->R * (ncl_lj / 8) * t.lj_cap));
-            REMD_TRY(t.d_lj_sci_count.alloc(h, (size_t)h->R * (ncl_lj / 8)));
-            REMD_TRY(t.d_lj_excl.alloc(h, (size_t)h->R * ncl_lj * t.lj_excl_W));
-            REMD_TRY(t.d_lj_sforce.alloc(h, nl * 3));
-            REMD_CHECK(h, hipMemsetAsync(t.d_lj_sforce, 0, sizeof(long long) * nl * 3, st));
-        }
-        t.sort_R = h->R; t.evals_since_sort = 1 << 30;
+        if (t.lj_split) { REMD_TRY(t.lj.alloc(h, h->R)); REMD_TRY(t.lj.alloc_clusters(h, h->R, st)); }
     }
-    const bool split = cl && t.lj_split;
-    if (t.evals_since_sort >= t.resort_interval) {
-        remd_prof_scope ps(h, "nb_sort", st);
-        // cells of the molecule order: 2^b per box edge with an edge of ~0.11 nm (b from the longest edge of the first replica's box, as
-        // the host mirrors it; 32 per edge on the headline system, 64 on DHFR: profiles/r06_35_hilbert_cells.txt), along the Hilbert curve
-        // (the Z-order curve on cells of 0.45 nm, used until round 6, was removed after that measurement).  A property of the handle:
-        // fixed at the first sort.
-        if (t.sort_hbits == 0) {
-            double lmax = 0.0;
-            for (int k = 0; k < 3 && (size_t)k < h->box_host.size(); ++k) lmax = std::max(lmax, h->box_host[k]);
-            t.sort_hbits = lmax > 0.0 ? std::max(1, std::min(6, (int)lround(log2(lmax / 0.11)))) : 4;
-        }
-        if (t.n_groups < 8192) {
-            const size_t lds = sizeof(int) * 4 * (size_t)t.n_groups;
-            hipLaunchKernelGGL(sort_groups_kernel, dim3(h->R), dim3(1024), lds, st, t.n_groups, h->N, h->Npad, t.d_grp_first,
-                               t.d_grp_size, h->d_pos, h->d_box, t.d_order, t.sort_hbits);
-        } else {
-            const size_t need = (size_t)h->R * 5 * t.n_groups;
-            REMD_TRY(t.d_sort_scratch.grow(h, need));
-            hipLaunchKernelGGL(sort_groups_large_kernel, dim3(h->R), dim3(1024), 0, st, t.n_groups, h->N, h->Npad, t.d_grp_first,
-                               t.d_grp_size, h->d_pos, h->d_box, t.d_order, t.d_sort_scratch, t.sort_hbits);
-        }
-        hipLaunchKernelGGL(gather_params_kernel, dim3((h->Npad + 255) / 256, h->R), dim3(256), 0, st, h->Npad, t.p.excl_words,
-                           t.d_order, t.d_param, t.d_mask, t.d_sparam, t.d_smask);
-        if (split)
-            hipLaunchKernelGGL(compact_lj_kernel, dim3(h->R), dim3(1024), 0, st, h->N, h->Npad, t.NL, t.NLpad, t.lj_words, t.d_order,
-                               t.d_lj_ord, t.d_param, t.d_lj_mask, t.d_lj_order, t.d_lj_sparam, t.d_lj_smask);
-        if (cl) {
-            hipLaunchKernelGGL(build_excl_kernel, dim3(ntile * 8, h->R), dim3(64), 0, st, h->Npad, ntile * 8, t.excl_W, t.p.excl_words,
-                               t.d_smask, t.d_excl);
-            if (split)
-                hipLaunchKernelGGL(build_excl_kernel, dim3(t.NLpad / 8, h->R), dim3(64), 0, st, t.NLpad, t.NLpad / 8, t.lj_excl_W,
-                                   t.lj_words, t.d_lj_smask, t.d_lj_excl);
-        }
-        t.evals_since_sort = 0;
+    t.sort_R = h->R; t.evals_since_sort = 1 << 30;      // the new order arrays hold nothing: sort now
+    return 0;
+}
+
+// 2. the molecule order is due: sort, bring parameters and masks into the order, compact the LJ sub-system, exclusion words
+static int sorted_resort(remd_ctx* h, nb_tables& t, hipStream_t st)
+{
+    remd_prof_scope ps(h, "nb_sort", st);
+    const bool cl = nb_cluster_path(t), split = cl && t.lj_split;
+    nb_sorted& m = t.main; nb_sorted& l = t.lj;
+    // cells of the molecule order: 2^b per box edge with an edge of ~0.11 nm (b from the longest edge of the first replica's box, as
+    // the host mirrors it; 32 per edge on the headline system, 64 on DHFR: profiles/r06_35_hilbert_cells.txt), along the Hilbert curve
+    // (the Z-order curve on cells of 0.45 nm, used until round 6, was removed after that measurement).  A property of the handle:
+    // fixed at the first sort.
+    if (t.sort_hbits == 0) {
+        double lmax = 0.0;
+        for (int k = 0; k < 3 && (size_t)k < h->box_host.size(); ++k) lmax = std::max(lmax, h->box_host[k]);
+        t.sort_hbits = lmax > 0.0 ? std::max(1, std::min(6, (int)lround(log2(lmax / 0.11)))) : 4;
     }
-    t.evals_since_sort++;
-    remd_prof_scope ps(h, "nb_gather", st);
-    if (split) {
-        // main system + LJ sub-system in one gather launch and one list launch
-        const int ntile_lj = t.NLpad / 64;
-        gather_args ga{h->Npad, t.d_order, t.d_spos, t.d_tile_c, t.d_tile_h, t.d_cl_c, t.d_cl_h, t.d_sparam, t.d_sposi};
-        gather_args gb{t.NLpad, t.d_lj_order, t.d_lj_spos, t.d_lj_tile_c, t.d_lj_tile_h, t.d_lj_cl_c, t.d_lj_cl_h, nullptr, t.d_lj_sposi};
-        sci_list_args la{ntile * 8, t.cl_cap, t.d_cl_c, t.d_cl_h, t.d_tile_c, t.d_tile_h, t.d_sci_list, t.d_sci_count};
-        sci_list_args lb{t.NLpad / 8, t.lj_cap, t.d_lj_cl_c, t.d_lj_cl_h, t.d_lj_tile_c, t.d_lj_tile_h, t.d_lj_sci_list, t.d_lj_sci_count};
-        const float rc2_main = t.method == NB_EWALD ? t.p.rcc2 : t.p.rc2;
+    if (t.n_groups < 8192) {
+        const size_t lds = sizeof(int) * 4 * (size_t)t.n_groups;
+        hipLaunchKernelGGL(sort_groups_kernel, dim3(h->R), dim3(1024), lds, st, t.n_groups, h->N, h->Npad, t.d_grp_first,
+                           t.d_grp_size, h->d_pos, h->d_box, m.d_order, t.sort_hbits);
+    } else {
+        const size_t need = (size_t)h->R * 5 * t.n_groups;
+        REMD_TRY(t.d_sort_scratch.grow(h, need));
+        hipLaunchKernelGGL(sort_groups_large_kernel, dim3(h->R), dim3(1024), 0, st, t.n_groups, h->N, h->Npad, t.d_grp_first,
+                           t.d_grp_size, h->d_pos, h->d_box, m.d_order, t.d_sort_scratch, t.sort_hbits);
+    }
+    hipLaunchKernelGGL(gather_params_kernel, dim3((m.Npad + 255) / 256, h->R), dim3(256), 0, st, m.Npad, m.words,
+                       m.d_order, t.d_param, t.d_mask, m.d_sparam, m.d_smask);
+    if (split)
+        hipLaunchKernelGGL(compact_lj_kernel, dim3(h->R), dim3(1024), 0, st, m.N, m.Npad, l.N, l.Npad, l.words, m.d_order,
+                           t.d_lj_ord, t.d_param, t.d_lj_mask, l.d_order, l.d_sparam, l.d_smask);
+    auto excl_words = [&](const nb_sorted& s) {
+        hipLaunchKernelGGL(build_excl_kernel, dim3(s.ncl(), h->R), dim3(64), 0, st, s.Npad, s.ncl(), s.excl_W, s.words, s.d_smask, s.d_excl);
+    };
+    if (cl) excl_words(m);
+    if (split) excl_words(l);
+    t.evals_since_sort = 0;
+    return 0;
+}
+
+// 3. every evaluation: sorted positions and boxes, then the lists; after a re-sort the main system's tiles are ranked
+static void sorted_gather_and_list(remd_ctx* h, nb_tables& t, hipStream_t st)
+{
+    const bool cl = nb_cluster_path(t);
+    const nb_sorted& m = t.main; const nb_sorted& l = t.lj;
+    const int ntile = m.ntile();
+    // the Coulomb sum's range under Ewald (remd_set_coulomb_cutoff); the LJ sub-system's lists keep the NonbondedForce cutoff
+    const float rc2_main = t.method == NB_EWALD ? t.p.rcc2 : t.p.rc2;
+    if (cl && t.lj_split) {
+        // main system + LJ sub-system in one gather launch and one list launch; only this gather writes the integer positions, and the
+        // charge into their w for the main system (gather_positions_kernel below writes neither)
         // (one launch for both with an arrival-counter barrier between the phases was measured twice in round 4: with a release fence
         // before the arrival -- a device-scope release writes back the XCD's whole L2 -- 90 us instead of 11.6 + 12.7; with the boxes
         // as write-through device-scope stores and no fence 23.3 us, what the two launches take: profiles/r04_h_rejected.txt,
         // profiles/r04_r_fused_list_v2.txt)
-        hipLaunchKernelGGL(gather_positions2_kernel, dim3(ntile + ntile_lj, h->R), dim3(64), 0, st, ntile, ga, gb, h->Npad, h->d_pos, h->d_box);
-        hipLaunchKernelGGL(build_sci_list2_kernel, dim3(ntile + ntile_lj, h->R), dim3(64), 0, st, ntile, la, lb, rc2_main, t.p.rc2, h->d_box);
+        const dim3 grid(ntile + l.ntile(), h->R);
+        hipLaunchKernelGGL(gather_positions2_kernel, grid, dim3(64), 0, st, ntile, m.gather(true), l.gather(false), m.Npad, h->d_pos, h->d_box);
+        hipLaunchKernelGGL(build_sci_list2_kernel, grid, dim3(64), 0, st, ntile, m.list(), l.list(), rc2_main, t.p.rc2, h->d_box);
         // (the list lengths of the evaluation that re-sorted the molecules order the work items until the next re-sort: the geometry
         // of a tile changes slowly)
         if (t.evals_since_sort == 1 && t.d_tile_of_rank && ntile <= 2048)
-            hipLaunchKernelGGL(rank_tiles_kernel, dim3((ntile + 255) / 256, h->R), dim3(256), 0, st, ntile, t.d_sci_count, t.d_tile_of_rank);
+            hipLaunchKernelGGL(rank_tiles_kernel, dim3((ntile + 255) / 256, h->R), dim3(256), 0, st, ntile, m.d_sci_count, t.d_tile_of_rank);
     } else {
-        hipLaunchKernelGGL(gather_positions_kernel, dim3(ntile, h->R), dim3(64), 0, st, h->Npad, h->Npad, t.d_order, h->d_pos, h->d_box,
-                           t.d_spos, t.d_tile_c, t.d_tile_h, cl ? t.d_cl_c : (float4*)nullptr, cl ? t.d_cl_h : (float4*)nullptr);
+        hipLaunchKernelGGL(gather_positions_kernel, dim3(ntile, h->R), dim3(64), 0, st, m.Npad, m.Npad, m.d_order, h->d_pos, h->d_box,
+                           m.d_spos, m.d_tile_c, m.d_tile_h, cl ? m.d_cl_c : (float4*)nullptr, cl ? m.d_cl_h : (float4*)nullptr);
         if (cl)         // per-tile union lists
-            hipLaunchKernelGGL(build_sci_list_kernel, dim3(ntile, h->R), dim3(64), 0, st, ntile * 8, t.cl_cap, t.method == NB_EWALD ? t.p.rcc2 : t.p.rc2,
-                               t.d_cl_c, t.d_cl_h, t.d_tile_c, t.d_tile_h, h->d_box, t.d_sci_list, t.d_sci_count);
+            hipLaunchKernelGGL(build_sci_list_kernel, dim3(ntile, h->R), dim3(64), 0, st, m.ncl(), m.cap, rc2_main,
+                               m.d_cl_c, m.d_cl_h, m.d_tile_c, m.d_tile_h, h->d_box, m.d_sci_list, m.d_sci_count);
     }
+}
+
+// 4. once per re-sort, and only where a list can outgrow its row (or for the debug printer): the one host synchronisation of this path
+static int sorted_check_capacity(remd_ctx* h, nb_tables& t, hipStream_t st)
+{
+    const nb_sorted& m = t.main;
+    const int ntile = m.ntile();
     const bool debug = h->sw.debug;
-    if (cl && t.evals_since_sort == 1 && (t.cl_cap < ntile * 8 || debug)) {
-        // capacity check once per re-sort (the only host synchronisation of this path)
-        std::vector<int> cnt((size_t)h->R * ntile);
-        REMD_CHECK(h, hipMemcpyAsync(cnt.data(), t.d_sci_count, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost, st));
-        REMD_CHECK(h, hipStreamSynchronize(st));
-        int mx = 0; for (int c : cnt) mx = std::max(mx, c);
-        if (debug) {
-            std::vector<unsigned int> ll((size_t)ntile * t.cl_cap);
-            hipMemcpy(ll.data(), t.d_sci_list, sizeof(unsigned int) * ll.size(), hipMemcpyDeviceToHost);
-            double ne = 0, nb = 0;
-            for (int T = 0; T < ntile; ++T) for (int k = 0; k < std::min(cnt[T], t.cl_cap); ++k) { ne += 1; nb += __builtin_popcount(ll[(size_t)T * t.cl_cap + k] >> 16); }
-            fprintf(stderr, "[remd] sci list (replica 0): %d tiles, %.1f entries per tile (max %d, cap %d), %.2f i clusters per entry\n",
-                    ntile, ne / ntile, mx, t.cl_cap, nb / std::max(1.0, ne));
-        }
-        if (mx > t.cl_cap) t.clusters = false;        // fall back to the tile kernel
+    if (!(nb_cluster_path(t) && t.evals_since_sort == 1 && (m.cap < m.ncl() || debug))) return 0;
+    std::vector<int> cnt((size_t)h->R * ntile);
+    REMD_CHECK(h, hipMemcpyAsync(cnt.data(), m.d_sci_count, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost, st));
+    REMD_CHECK(h, hipStreamSynchronize(st));
+    int mx = 0; for (int c : cnt) mx = std::max(mx, c);
+    if (debug) {
+        std::vector<unsigned int> ll((size_t)ntile * m.cap);
+        hipMemcpy(ll.data(), m.d_sci_list, sizeof(unsigned int) * ll.size(), hipMemcpyDeviceToHost);
+        double ne = 0, nb = 0;
+        for (int T = 0; T < ntile; ++T) for (int k = 0; k < std::min(cnt[T], m.cap); ++k) { ne += 1; nb += __builtin_popcount(ll[(size_t)T * m.cap + k] >> 16); }
+        fprintf(stderr, "[remd] sci list (replica 0): %d tiles, %.1f entries per tile (max %d, cap %d), %.2f i clusters per entry\n",
+                ntile, ne / ntile, mx, m.cap, nb / std::max(1.0, ne));
     }
+    if (mx > m.cap) t.clusters = false;        // fall back to the tile kernel
     return 0;
+}
+
+static int ensure_sorted(remd_ctx* h, nb_tables& t, hipStream_t st)
+{
+    if (!t.sorting || t.n_groups <= 0) return 0;
+    if (t.sort_R != h->R) REMD_TRY(sorted_realloc(h, t, st));
+    if (t.evals_since_sort >= t.resort_interval) REMD_TRY(sorted_resort(h, t, st));
+    t.evals_since_sort++;
+    remd_prof_scope ps(h, "nb_gather", st);
+    sorted_gather_and_list(h, t, st);
+    return sorted_check_capacity(h, t, st);
 }
 
 // direct-space launch: the Newton's-third-law cluster-pair kernel over the super-cluster lists (main system and, for the
@@ -1808,10 +1890,10 @@ static int launch_nb(remd_ctx* h, nb_tables& t, hipStream_t st, bool count_done,
 {
     armed = remd_fold_args();
     const int ntile = (h->N + 63) / 64;
-    if (t.sorting && t.clusters && t.d_order && t.d_sci_list && t.n_groups > 0 && ntile * 8 < 65536) {
-        const int ncl = ntile * 8;
+    const nb_sorted& m = t.main; const nb_sorted& l = t.lj;
+    if (t.sorting && t.clusters && m.d_order && m.d_sci_list && t.n_groups > 0 && ntile * 8 < 65536) {
         const float* rl = t.has_alch ? t.d_rep_lam : (const float*)nullptr;
-        const bool split = t.lj_split && t.d_lj_sci_list && (METHOD == NB_EWALD || METHOD == NB_RF);
+        const bool split = t.lj_split && l.d_sci_list && (METHOD == NB_EWALD || METHOD == NB_RF);
         constexpr int MAIN = (METHOD == NB_EWALD) ? NB_EWALD_NOLJ : (METHOD == NB_RF) ? NB_RF_NOLJ : METHOD;
         const int ssplit = std::max(SCI_NW, std::min(16, t.sci_split / SCI_NW * SCI_NW));
         // (measured, profiles/r05_7_*: -1.2 % of a step on 8 x host-guest (71 tiles) and 16 x DHFR (369 tiles), +1 % on 24 x alanine dipeptide
@@ -1820,17 +1902,15 @@ static int launch_nb(remd_ctx* h, nb_tables& t, hipStream_t st, bool count_done,
         // more than the tail it removes)
         // (round 6, the blocks of a phased propagation: a block's launch is one round of the chip beside the other block's kernels, and the
         // longest lists first help there at 36 tiles too: 24 x alanine dipeptide +2.5 %, profiles/r06_45)
-        const bool ranked = (ntile >= 64 || h->parent != nullptr) && ntile <= 2048 && t.lj_split && t.d_lj_sci_list && t.d_tile_of_rank && (METHOD == NB_EWALD || METHOD == NB_RF);
-        sci_args sa{h->N, h->Npad, ncl, t.cl_cap, t.excl_W, h->Npad, 0, ssplit, t.d_spos, t.d_sparam, t.d_excl, t.d_sci_list, t.d_sci_count, t.d_sforce,
-                    t.d_sposi, ranked ? t.d_tile_of_rank : (const int*)nullptr};
+        const bool ranked = (ntile >= 64 || h->parent != nullptr) && ntile <= 2048 && t.lj_split && l.d_sci_list && t.d_tile_of_rank && (METHOD == NB_EWALD || METHOD == NB_RF);
+        const sci_args sa = m.pair(0, ssplit, ranked ? t.d_tile_of_rank : (const int*)nullptr);
         const int items_a = ntile * h->R * (ssplit / SCI_NW);
         if (split) {
             // one launch for both systems, one scatter for both sorted accumulators; the launch is either one workgroup per
-            // work item or a resident set pulling items from a queue (t.nb_grid, chosen by timing: remd_nb_tune_step)
-            sci_args sb{t.NL, t.NLpad, t.NLpad / 8, t.lj_cap, t.lj_excl_W, t.NLpad, ncl * 4, ssplit, t.d_lj_spos, t.d_lj_sparam, t.d_lj_excl,
-                        t.d_lj_sci_list, t.d_lj_sci_count, t.d_lj_sforce, t.d_lj_sposi, nullptr};
-            const int items = items_a + (t.NLpad / 64) * h->R * (ssplit / SCI_NW);
-            const int persist_grid = h->sw.nb_persist_grid >= 0 ? h->sw.nb_persist_grid : t.nb_grid;
+            // work item or a resident set pulling items from a queue (t.tune.grid, chosen by timing: remd_nb_tune_step)
+            const sci_args sb = l.pair(m.ncl() * 4, ssplit, nullptr);     // its energy slots follow the main system's 4 per cluster
+            const int items = items_a + l.ntile() * h->R * (ssplit / SCI_NW);
+            const int persist_grid = h->sw.nb_persist_grid >= 0 ? h->sw.nb_persist_grid : t.tune.grid;
             const int grid = (h->next.forked && persist_grid > 0) ? std::min(items, persist_grid) : items;
             const bool fold = count_done && !ENERGY && t.d_pair_done;
             const bool tab = t.use_table && !ENERGY && SCI_EWALD(MAIN);
@@ -1841,13 +1921,13 @@ static int launch_nb(remd_ctx* h, nb_tables& t, hipStream_t st, bool count_done,
             if (t.has_alch) { if (tab) LAUNCH_SCI2(true, true); else LAUNCH_SCI2(true, false); }
             else { if (tab) LAUNCH_SCI2(false, true); else LAUNCH_SCI2(false, false); }
 #undef LAUNCH_SCI2
-            const dim3 sgrid((h->Npad + t.NLpad + 255) / 256, h->R);
+            const dim3 sgrid((m.Npad + l.Npad + 255) / 256, h->R);
             if (fold) {
                 t.pair_done_target += sgrid.x;           // per replica
                 armed.done = t.d_pair_done; armed.target = t.pair_done_target;
             }
-            hipLaunchKernelGGL(scatter_sorted_forces_kernel, sgrid, dim3(256), 0, st, h->Npad,
-                               t.d_order, t.d_sforce, t.NLpad, t.d_lj_order, t.d_lj_sforce, h->d_force, h->Npad, fold ? t.d_pair_done : (unsigned int*)nullptr);
+            hipLaunchKernelGGL(scatter_sorted_forces_kernel, sgrid, dim3(256), 0, st, m.Npad,
+                               m.d_order, m.d_sforce, l.Npad, l.d_order, l.d_sforce, h->d_force, h->Npad, fold ? t.d_pair_done : (unsigned int*)nullptr);
             return 0;
         }
         const bool tab1 = t.use_table && !ENERGY && SCI_EWALD(METHOD);
@@ -1857,24 +1937,24 @@ static int launch_nb(remd_ctx* h, nb_tables& t, hipStream_t st, bool count_done,
         if (t.has_alch) { if (tab1) LAUNCH_SCI(true, true); else LAUNCH_SCI(true, false); }
         else { if (tab1) LAUNCH_SCI(false, true); else LAUNCH_SCI(false, false); }
 #undef LAUNCH_SCI
-        hipLaunchKernelGGL(scatter_sorted_forces_kernel, dim3((h->Npad + 255) / 256, h->R), dim3(256), 0, st, h->Npad, t.d_order,
-                           t.d_sforce, 0, (const int*)nullptr, (long long*)nullptr, h->d_force, h->Npad);
+        hipLaunchKernelGGL(scatter_sorted_forces_kernel, dim3((m.Npad + 255) / 256, h->R), dim3(256), 0, st, m.Npad, m.d_order,
+                           m.d_sforce, 0, (const int*)nullptr, (long long*)nullptr, h->d_force, h->Npad);
         return 0;
     }
     dim3 grid((ntile + NB_WAVES - 1) / NB_WAVES, t.p.n_jsplit, h->R);
     const size_t need = (size_t)h->R * t.p.n_jsplit * h->Npad;
     REMD_TRY(t.d_partial.grow(h, need));
-    const bool sorted = t.sorting && t.d_order && t.n_groups > 0;
-    const float4* P = sorted ? t.d_spos : h->d_pos;
-    const float4* prm = sorted ? t.d_sparam : t.d_param;
-    const unsigned long long* mk = sorted ? t.d_smask : t.d_mask;
-    const int* ord = sorted ? t.d_order : nullptr;
+    const bool sorted = t.sorting && m.d_order && t.n_groups > 0;
+    const float4* P = sorted ? m.d_spos : h->d_pos;
+    const float4* prm = sorted ? m.d_sparam : t.d_param;
+    const unsigned long long* mk = sorted ? m.d_smask : t.d_mask;
+    const int* ord = sorted ? m.d_order : nullptr;
     if (t.has_alch)
         hipLaunchKernelGGL((nonbonded_kernel<METHOD, ENERGY, true>), grid, dim3(64 * NB_WAVES), 0, st, t.p, h->N, h->Npad, P,
-                           prm, mk, ord, t.d_tile_c, t.d_tile_h, h->d_box, t.d_rep_lam, t.d_partial, h->d_epart, h->n_epart, ntile);
+                           prm, mk, ord, m.d_tile_c, m.d_tile_h, h->d_box, t.d_rep_lam, t.d_partial, h->d_epart, h->n_epart, ntile);
     else
         hipLaunchKernelGGL((nonbonded_kernel<METHOD, ENERGY, false>), grid, dim3(64 * NB_WAVES), 0, st, t.p, h->N, h->Npad, P,
-                           prm, mk, ord, t.d_tile_c, t.d_tile_h, h->d_box, (const float*)nullptr, t.d_partial, h->d_epart, h->n_epart, ntile);
+                           prm, mk, ord, m.d_tile_c, m.d_tile_h, h->d_box, (const float*)nullptr, t.d_partial, h->d_epart, h->n_epart, ntile);
     hipLaunchKernelGGL(nb_reduce_kernel, dim3((h->N + 255) / 256, h->R), dim3(256), 0, st, h->N, h->Npad, t.p.n_jsplit,
                        t.d_partial, h->d_force);
     return 0;
@@ -1893,8 +1973,8 @@ void remd_nb_reset_accumulators(remd_ctx* h)
 {
     nb_tables* t = h->nb.get();
     if (!t || h->R <= 0) return;
-    if (t->d_sforce) hipMemsetAsync(t->d_sforce, 0, sizeof(long long) * 3 * (size_t)h->R * h->Npad, h->stream);
-    if (t->d_lj_sforce) hipMemsetAsync(t->d_lj_sforce, 0, sizeof(long long) * 3 * (size_t)h->R * t->NLpad, h->stream);
+    t->main.clear_forces(h->R, h->stream);
+    t->lj.clear_forces(h->R, h->stream);
 }
 
 int remd_nb_molecules(remd_ctx* h, const int** first, const int** size)
@@ -1943,50 +2023,48 @@ void remd_nb_tune_step(remd_ctx* h, int steps_left_in_call)
 {
     nb_tables* tp = h->nb.get();
     if (!tp || h->nb_method == REMD_NB_NONE) return;
-    nb_tables& t = *tp;
-    if (h->sw.nb_persist_grid >= 0 || t.tune_state != 0 || !h->next.forked || h->profiling == 2) return;
-    if (t.tune_left == 0) {
+    nb_tuner& t = tp->tune;
+    if (h->sw.nb_persist_grid >= 0 || t.state != 0 || !h->next.forked || h->profiling == 2) return;
+    if (t.left == 0) {
         hipEvent_t boundary = nullptr;
-        if (!t.tune_segs.empty() && !t.tune_segs.back().b) {            // close the open segment
+        if (!t.segs.empty() && !t.segs.back().b) {            // close the open segment
             hipEventCreate(&boundary); hipEventRecord(boundary, h->stream);
-            t.tune_segs.back().b = boundary;
+            t.segs.back().b = boundary;
         }
-        if (t.tune_next == 2 * TUNE_NC) { t.tune_state = 1; t.nb_grid = 0; return; }      // two rounds of the candidates measured
-        if (steps_left_in_call < TUNE_SEG) { t.nb_grid = 0; return; }           // resume in a later call
-        nb_tables::tune_seg sg{t.tune_next % TUNE_NC, nullptr, nullptr};
-        hipEventCreate(&sg.a); hipEventRecord(sg.a, h->stream);                // (each segment owns its pair of events)
-        t.tune_segs.push_back(sg);
-        t.nb_grid = g_tune_cands[sg.cand].grid; t.nb_prio = g_tune_cands[sg.cand].prio_pair;
-        t.tune_next++;
-        t.tune_left = TUNE_SEG;
+        if (t.next == 2 * TUNE_NC) { t.state = 1; t.grid = 0; return; }      // two rounds of the candidates measured
+        if (steps_left_in_call < TUNE_SEG) { t.grid = 0; return; }           // resume in a later call
+        nb_tuner::seg sg{t.next % TUNE_NC, nullptr, nullptr};
+        hipEventCreate(&sg.a); hipEventRecord(sg.a, h->stream);
+        t.segs.push_back(sg);
+        t.grid = g_tune_cands[sg.cand].grid; t.prio = g_tune_cands[sg.cand].prio_pair;
+        t.next++;
+        t.left = TUNE_SEG;
     }
-    t.tune_left--;
+    t.left--;
 }
 // after the stream has been synchronised: pick the fastest candidate
 void remd_nb_tune_resolve(remd_ctx* h)
 {
     nb_tables* tp = h->nb.get();
-    if (!tp || tp->tune_state != 1) return;
-    nb_tables& t = *tp;
+    if (!tp || tp->tune.state != 1) return;
+    nb_tuner& t = tp->tune;
     double ms[TUNE_NC] = {0};
     bool ok = true;
-    for (auto& sg : t.tune_segs) {
+    for (auto& sg : t.segs) {
         float e = 0.f;
         if (!sg.a || !sg.b || hipEventElapsedTime(&e, sg.a, sg.b) != hipSuccess) { ok = false; (void)hipGetLastError(); }
         ms[sg.cand] += e;
-        if (sg.a) hipEventDestroy(sg.a);
-        if (sg.b) hipEventDestroy(sg.b);
     }
-    t.tune_segs.clear();
+    t.drop_segs();
     int best = 0;
     for (int c = 1; c < TUNE_NC; ++c) if (ok && ms[c] < ms[best] * 0.995) best = c;     // ties go to the earlier candidate
-    t.nb_grid = ok ? g_tune_cands[best].grid : 0; t.nb_prio = ok ? g_tune_cands[best].prio_pair : 0;
-    t.tune_state = 2;
+    t.grid = ok ? g_tune_cands[best].grid : 0; t.prio = ok ? g_tune_cands[best].prio_pair : 0;
+    t.state = 2;
     if (h->sw.nb_tune_verbose)
     {
         fprintf(stderr, "[remd] pair-kernel residency, ms per %d steps:", 2 * TUNE_SEG);
         for (int c = 0; c < TUNE_NC; ++c) fprintf(stderr, " %d%s: %.2f", g_tune_cands[c].grid, g_tune_cands[c].prio_pair ? "p" : "", ms[c]);
-        fprintf(stderr, " -> %d workgroups\n", t.nb_grid);
+        fprintf(stderr, " -> %d workgroups\n", t.grid);
     }
 }
 // the next force evaluation re-sorts the molecules (a propagation that is run again after a device-side failure starts in the
@@ -2075,7 +2153,7 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask, bool
     const hipStream_t main_st = h->stream, direct_st = forked ? h->stream2 : h->stream;
     // which stream's kernels run at raised wave priority (the pair kernel's: the direct-space stream is the critical path of a step):
     // chosen together with the pair kernel's residency (remd_nb_tune_step)
-    const int prio_pair = forked ? (h->sw.nb_prio >= 0 ? h->sw.nb_prio : nbt->nb_prio) : 0;
+    const int prio_pair = forked ? (h->sw.nb_prio >= 0 ? h->sw.nb_prio : nbt->tune.prio) : 0;
     // Where the listed terms, and the restraints with them, go.  Energy evaluation: a kernel per kind on the direct-space stream.
     // Force-only evaluation: ONE launch, behind the pair kernel (it then starts 20 us earlier, next to the
     // spreading pass: 118.9 -> 116.8 ms per 500 steps).
