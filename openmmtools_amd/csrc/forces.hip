@@ -213,8 +213,8 @@ void ext_force_kernel(int n_ext, const int* __restrict__ ext_atoms, float K, flo
     }
 }
 
-// ---- bonded terms (float3 helpers: listed_terms.h) ------------------------------------------------
-template <bool ENERGY>
+// ---- listed terms of an evaluation with energies: the arithmetic of listed_terms.h, the energy summed here in f64 -----------------
+// (one workgroup per replica; remd_compute_forces launches these only with energies -- force-only evaluations take listed_forces_kernel)
 __global__ __launch_bounds__(256)
 void bond_kernel(int n, const int* __restrict__ atoms, const float* __restrict__ params, int Npad,
                  const float4* __restrict__ pos, long long* __restrict__ force, double* __restrict__ epart, int n_epart)
@@ -225,20 +225,16 @@ void bond_kernel(int n, const int* __restrict__ atoms, const float* __restrict__
     long long* F = force + (size_t)r * 3 * Npad;
     double e = 0.0;
     for (int t = threadIdx.x; t < n; t += 256) {
-        const int i = atoms[2 * t], j = atoms[2 * t + 1];
-        const float r0 = params[2 * t], k = params[2 * t + 1];
-        const float3 d = sub3(ld3(P, j), ld3(P, i));
-        const float len = sqrtf(dotf(d, d));
-        const float dl = len - r0;
-        const float fs = k * dl / len;               // F_i = +fs * d, F_j = -fs * d
-        add_force(F, Npad, i, fs * d.x, fs * d.y, fs * d.z);
-        add_force(F, Npad, j, -fs * d.x, -fs * d.y, -fs * d.z);
-        if (ENERGY) e += 0.5 * (double)k * (double)dl * (double)dl;
+        const float k = params[2 * t + 1];
+        listed_out o;
+        const float dl = bond_term(atoms[2 * t], atoms[2 * t + 1], params[2 * t], k, P, o);
+        listed_add(F, Npad, o, 2);
+        e += 0.5 * (double)k * (double)dl * (double)dl;
     }
-    if (ENERGY) { e = block_sum_256(e, s_part); if (threadIdx.x == 0) epart[(size_t)r * n_epart + EP_BOND] = e; }
+    e = block_sum_256(e, s_part);
+    if (threadIdx.x == 0) epart[(size_t)r * n_epart + EP_BOND] = e;
 }
 
-template <bool ENERGY>
 __global__ __launch_bounds__(256)
 void angle_kernel(int n, const int* __restrict__ atoms, const float* __restrict__ params, int Npad,
                   const float4* __restrict__ pos, long long* __restrict__ force, double* __restrict__ epart, int n_epart)
@@ -249,30 +245,18 @@ void angle_kernel(int n, const int* __restrict__ atoms, const float* __restrict_
     long long* F = force + (size_t)r * 3 * Npad;
     double e = 0.0;
     for (int t = threadIdx.x; t < n; t += 256) {
-        const int a = atoms[3 * t], b = atoms[3 * t + 1], c = atoms[3 * t + 2];
-        const float th0 = params[2 * t], k = params[2 * t + 1];
-        const float3 v0 = sub3(ld3(P, a), ld3(P, b));     // b -> a
-        const float3 v1 = sub3(ld3(P, c), ld3(P, b));     // b -> c
-        const float3 cp = crs3(v0, v1);
-        const float rp = fmaxf(sqrtf(dotf(cp, cp)), 1e-6f);
-        const float r20 = dotf(v0, v0), r21 = dotf(v1, v1);
-        const float dt = dotf(v0, v1);
-        const float cosine = fminf(fmaxf(dt * rsqrtf(r20 * r21), -1.f), 1.f);
-        const float theta = acosf(cosine);
-        const float dth = theta - th0;
-        const float dEdth = k * dth;
-        // dtheta/dx_a = (v0 x cp) / (|v0|^2 |cp|),  dtheta/dx_c = (cp x v1) / (|v1|^2 |cp|)
-        const float3 fa = scl3(crs3(v0, cp), -dEdth / (r20 * rp));
-        const float3 fc = scl3(crs3(cp, v1), -dEdth / (r21 * rp));
-        add_force(F, Npad, a, fa.x, fa.y, fa.z);
-        add_force(F, Npad, c, fc.x, fc.y, fc.z);
-        add_force(F, Npad, b, -(fa.x + fc.x), -(fa.y + fc.y), -(fa.z + fc.z));
-        if (ENERGY) e += 0.5 * (double)k * (double)dth * (double)dth;
+        const float k = params[2 * t + 1];
+        listed_out o;
+        const float dth = angle_term(atoms[3 * t], atoms[3 * t + 1], atoms[3 * t + 2], params[2 * t], k, P, o);
+        listed_add_angle(F, Npad, o);
+        e += 0.5 * (double)k * (double)dth * (double)dth;
     }
-    if (ENERGY) { e = block_sum_256(e, s_part); if (threadIdx.x == 0) epart[(size_t)r * n_epart + EP_ANGLE] = e; }
+    e = block_sum_256(e, s_part);
+    if (threadIdx.x == 0) epart[(size_t)r * n_epart + EP_ANGLE] = e;
 }
 
-template <bool ENERGY>
+// (its own statement of torsion_term's arithmetic, product for product: built on torsion_term the compiler pairs other products of this
+//  kernel into packed multiplies and contracts four FMAs fewer, which moves the last bits of the forces and of EP_TORSION)
 __global__ __launch_bounds__(256)
 void torsion_kernel(int n, const int* __restrict__ atoms, const float* __restrict__ params, int Npad,
                     const float4* __restrict__ pos, long long* __restrict__ force, double* __restrict__ epart, int n_epart)
@@ -304,9 +288,10 @@ void torsion_kernel(int n, const int* __restrict__ atoms, const float* __restric
         add_force(F, Npad, a2, -dEdphi * g2.x, -dEdphi * g2.y, -dEdphi * g2.z);
         add_force(F, Npad, a3, -dEdphi * g3.x, -dEdphi * g3.y, -dEdphi * g3.z);
         add_force(F, Npad, a4, -dEdphi * g4.x, -dEdphi * g4.y, -dEdphi * g4.z);
-        if (ENERGY) e += (double)k * (1.0 + (double)cosf(arg));
+        e += (double)k * (1.0 + (double)cosf(arg));
     }
-    if (ENERGY) { e = block_sum_256(e, s_part); if (threadIdx.x == 0) epart[(size_t)r * n_epart + EP_TORSION] = e; }
+    e = block_sum_256(e, s_part);
+    if (threadIdx.x == 0) epart[(size_t)r * n_epart + EP_TORSION] = e;
 }
 
 __global__ __launch_bounds__(256)
@@ -1172,8 +1157,7 @@ void nb_reduce_kernel(int N, int Npad, int nsplit, const float4* __restrict__ pa
     add_force(force + (size_t)r * 3 * Npad, Npad, i, fx, fy, fz);
 }
 
-// 1-4 style exceptions with non-zero parameters: plain Coulomb + LJ, no cutoff, no switch
-template <bool ENERGY>
+// 1-4 style exceptions with non-zero parameters and the Ewald correction for excluded pairs, likewise (exception_term, exclusion_term)
 __global__ __launch_bounds__(256)
 void exception_kernel(int n, const int* __restrict__ atoms, const float* __restrict__ params,
                       const int* __restrict__ alch, const float* __restrict__ rep_lam, int Npad,
@@ -1184,37 +1168,18 @@ void exception_kernel(int n, const int* __restrict__ atoms, const float* __restr
     const int r = blockIdx.x;
     const float4* P = pos + (size_t)r * Npad;
     long long* F = force + (size_t)r * 3 * Npad;
-    const float Lx = box[4 * r], Ly = box[4 * r + 1], Lz = box[4 * r + 2];
+    const float3 L = box_edges(box, r);
+    const float* lam = rep_lam ? rep_lam + 4 * r : nullptr;
     double e = 0.0;
     for (int t = threadIdx.x; t < n; t += 256) {
-        const int i = atoms[2 * t], j = atoms[2 * t + 1];
-        float qq = params[3 * t];
-        const float sig = params[3 * t + 1], eps = params[3 * t + 2];
-        if (rep_lam && alch[t] > 0) qq *= rep_lam[4 * r + 2];
-        float3 d = sub3(ld3(P, j), ld3(P, i));
-        if (Lx > 0.f) { d.x -= Lx * rintf(d.x / Lx); d.y -= Ly * rintf(d.y / Ly); d.z -= Lz * rintf(d.z / Lz); }
-        const float r2 = dotf(d, d);
-        const float inv_r = rsqrtf(r2);
-        float Ulj, dUlj;
-        if (rep_lam && alch[t] == 1 && eps != 0.f) {             // soft-core: listed_terms.h
-            const float2 sc = softcore_exception(rep_lam[4 * r], rep_lam[4 * r + 1], sig, eps, r2, inv_r);
-            Ulj = sc.x; dUlj = sc.y;
-        } else {
-            const float s2 = sig * sig * inv_r * inv_r, s6 = s2 * s2 * s2;
-            Ulj = 4.f * eps * s6 * (s6 - 1.f); dUlj = 4.f * eps * s6 * (6.f - 12.f * s6) * inv_r;
-        }
-        const float U = Ulj + qq * inv_r;
-        const float dUdr = dUlj - qq * inv_r * inv_r;
-        const float fr = dUdr * inv_r;
-        add_force(F, Npad, i, fr * d.x, fr * d.y, fr * d.z);
-        add_force(F, Npad, j, -fr * d.x, -fr * d.y, -fr * d.z);
-        if (ENERGY) e += (double)U;
+        listed_out o;
+        e += (double)exception_term(atoms[2 * t], atoms[2 * t + 1], params[3 * t], params[3 * t + 1], params[3 * t + 2], lam ? alch[t] : 0, lam, L, P, o);
+        listed_add(F, Npad, o, 2);
     }
-    if (ENERGY) { e = block_sum_256(e, s_part); if (threadIdx.x == 0) epart[(size_t)r * n_epart + EP_EXCEPT] = e; }
+    e = block_sum_256(e, s_part);
+    if (threadIdx.x == 0) epart[(size_t)r * n_epart + EP_EXCEPT] = e;
 }
 
-// Ewald correction for excluded pairs: the reciprocal sum contains them, so subtract qq erf(alpha r)/r
-template <bool ENERGY>
 __global__ __launch_bounds__(256)
 void ewald_exclusion_kernel(int n, const int* __restrict__ atoms, const float* __restrict__ qq_arr,
                             const int* __restrict__ alch, const float* __restrict__ rep_lam, float alpha,
@@ -1225,27 +1190,16 @@ void ewald_exclusion_kernel(int n, const int* __restrict__ atoms, const float* _
     const int r = blockIdx.x;
     const float4* P = pos + (size_t)r * Npad;
     long long* F = force + (size_t)r * 3 * Npad;
-    const float Lx = box[4 * r], Ly = box[4 * r + 1], Lz = box[4 * r + 2];
+    const float3 L = box_edges(box, r);
+    const float* lam = rep_lam ? rep_lam + 4 * r : nullptr;
     double e = 0.0;
     for (int t = threadIdx.x; t < n; t += 256) {
-        const int i = atoms[2 * t], j = atoms[2 * t + 1];
-        float qq = qq_arr[t];
-        if (rep_lam) { const float le = rep_lam[4 * r + 2]; const int na = alch[t]; qq *= (na == 2) ? le * le : (na == 1) ? le : 1.f; }
-        float3 d = sub3(ld3(P, j), ld3(P, i));
-        d.x -= Lx * rintf(d.x / Lx); d.y -= Ly * rintf(d.y / Ly); d.z -= Lz * rintf(d.z / Lz);
-        const float r2 = dotf(d, d);
-        const float inv_r = rsqrtf(r2);
-        const float rr = r2 * inv_r;
-        const float ar = alpha * rr;
-        const float erf_ar = erff(ar);
-        const float U = -qq * erf_ar * inv_r;
-        const float dUdr = -qq * (two_alpha_sqrtpi * __expf(-ar * ar) * inv_r - erf_ar * inv_r * inv_r);
-        const float fr = dUdr * inv_r;
-        add_force(F, Npad, i, fr * d.x, fr * d.y, fr * d.z);
-        add_force(F, Npad, j, -fr * d.x, -fr * d.y, -fr * d.z);
-        if (ENERGY) e += (double)U;
+        listed_out o;
+        e += (double)exclusion_term<true>(atoms[2 * t], atoms[2 * t + 1], qq_arr[t], lam ? alch[t] : 0, lam, L, alpha, two_alpha_sqrtpi, P, o);
+        listed_add(F, Npad, o, 2);
     }
-    if (ENERGY) { e = block_sum_256(e, s_part); if (threadIdx.x == 0) epart[(size_t)r * n_epart + EP_EXCLCORR] = e; }
+    e = block_sum_256(e, s_part);
+    if (threadIdx.x == 0) epart[(size_t)r * n_epart + EP_EXCLCORR] = e;
 }
 
 // per-replica constants: dispersion correction, Ewald self energy, neutralising background.  Alchemical charges
@@ -2198,6 +2152,7 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask, bool
         LAUNCH_E(ext_force_kernel, dim3(R), dim3(64), 0, main_st, h->n_ext, h->d_ext_atoms, (float)h->ext_K, (float)h->ext_x0,
                  h->ext_U0, h->Npad, h->d_pos, h->d_force, h->d_epart, h->n_epart);
     }
+#undef LAUNCH_E
     if (nbt) REMD_TRY(update_replica_lambdas(h, *nbt));      // per-replica lambdas must be current before ANY kernel reads them
     int listed_total = 0;
     const listed_tables listed_tab = with_energy ? listed_tables{} : listed_terms(h, class_mask, listed_total);
@@ -2224,18 +2179,18 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask, bool
     if (listed == LISTED_KERNELS) {
         if (h->n_bonds > 0) {
             remd_prof_scope ps(h, "bonded", direct_st);
-            LAUNCH_E(bond_kernel, dim3(R), dim3(256), 0, direct_st, h->n_bonds, h->d_bond_atoms, h->d_bond_params, h->Npad,
-                     h->d_pos, h->d_force, h->d_epart, h->n_epart);
+            hipLaunchKernelGGL(bond_kernel, dim3(R), dim3(256), 0, direct_st, h->n_bonds, h->d_bond_atoms, h->d_bond_params, h->Npad,
+                               h->d_pos, h->d_force, h->d_epart, h->n_epart);
         }
         if (h->n_angles > 0) {
             remd_prof_scope ps(h, "bonded", direct_st);
-            LAUNCH_E(angle_kernel, dim3(R), dim3(256), 0, direct_st, h->n_angles, h->d_angle_atoms, h->d_angle_params, h->Npad,
-                     h->d_pos, h->d_force, h->d_epart, h->n_epart);
+            hipLaunchKernelGGL(angle_kernel, dim3(R), dim3(256), 0, direct_st, h->n_angles, h->d_angle_atoms, h->d_angle_params, h->Npad,
+                               h->d_pos, h->d_force, h->d_epart, h->n_epart);
         }
         if (h->n_torsions > 0) {
             remd_prof_scope ps(h, "bonded", direct_st);
-            LAUNCH_E(torsion_kernel, dim3(R), dim3(256), 0, direct_st, h->n_torsions, h->d_torsion_atoms, h->d_torsion_params, h->Npad,
-                     h->d_pos, h->d_force, h->d_epart, h->n_epart);
+            hipLaunchKernelGGL(torsion_kernel, dim3(R), dim3(256), 0, direct_st, h->n_torsions, h->d_torsion_atoms, h->d_torsion_params, h->Npad,
+                               h->d_pos, h->d_force, h->d_epart, h->n_epart);
         }
         if (do_rst) REMD_TRY(remd_restraints_forces(h, with_energy, h->n_epart - 1, direct_st));
         if (do_cst) REMD_TRY(remd_custom_forces(h, with_energy, h->n_epart - 1, direct_st));
@@ -2254,18 +2209,17 @@ int remd_compute_forces(remd_ctx* h, bool with_energy, unsigned class_mask, bool
         nb_tables& t = *nbt;
         if (t.n_exc > 0) {
             remd_prof_scope ps(h, "exceptions", direct_st);
-            LAUNCH_E(exception_kernel, dim3(R), dim3(256), 0, direct_st, t.n_exc, t.d_exc_atoms, t.d_exc_params, t.d_exc_alch,
-                     t.has_alch ? t.d_rep_lam : (const float*)nullptr, h->Npad,
-                     h->d_pos, h->d_box, h->d_force, h->d_epart, h->n_epart);
+            hipLaunchKernelGGL(exception_kernel, dim3(R), dim3(256), 0, direct_st, t.n_exc, t.d_exc_atoms, t.d_exc_params, t.d_exc_alch,
+                               t.has_alch ? t.d_rep_lam : (const float*)nullptr, h->Npad,
+                               h->d_pos, h->d_box, h->d_force, h->d_epart, h->n_epart);
         }
         if (t.n_excl > 0) {
             remd_prof_scope ps(h, "exceptions", direct_st);
-            LAUNCH_E(ewald_exclusion_kernel, dim3(R), dim3(256), 0, direct_st, t.n_excl, t.d_excl_atoms, t.d_excl_qq, t.d_excl_alch,
-                     t.has_alch ? t.d_rep_lam : (const float*)nullptr, t.p.alpha,
-                     t.p.two_alpha_sqrtpi, h->Npad, h->d_pos, h->d_box, h->d_force, h->d_epart, h->n_epart);
+            hipLaunchKernelGGL(ewald_exclusion_kernel, dim3(R), dim3(256), 0, direct_st, t.n_excl, t.d_excl_atoms, t.d_excl_qq, t.d_excl_alch,
+                               t.has_alch ? t.d_rep_lam : (const float*)nullptr, t.p.alpha,
+                               t.p.two_alpha_sqrtpi, h->Npad, h->d_pos, h->d_box, h->d_force, h->d_epart, h->n_epart);
         }
     }
-#undef LAUNCH_E
 
     // ---- join, and what is left of the mesh branch behind it ---------------------------------------------------------------------
     if (forked) {

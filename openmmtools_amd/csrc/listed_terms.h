@@ -1,7 +1,8 @@
-// Listed terms of a force-only evaluation (harmonic bonds, angles, periodic torsions, non-zero 1-4 exceptions, Ewald exclusion
-// correction), one term per thread.  Shared by forces.hip (listed_forces_kernel) and pme.hip (round 4: in the mode in which the
-// direct-space stream is the critical one the terms ride as extra workgroups of the spreading launch on the mesh stream --
-// one dependent 13 us launch less).  Functional forms: OpenMM HarmonicBondForce / HarmonicAngleForce / PeriodicTorsionForce /
+// Listed terms (harmonic bonds, angles, periodic torsions, non-zero 1-4 exceptions, Ewald exclusion correction), one term per thread.
+// Force-only evaluations: listed_forces_body, shared by forces.hip (listed_forces_kernel), resident.hip and pme.hip (round 4: in the
+// mode in which the direct-space stream is the critical one the terms ride as extra workgroups of the spreading launch on the mesh
+// stream -- one dependent 13 us launch less).  Evaluations with energies: bond_kernel, angle_kernel, exception_kernel and
+// ewald_exclusion_kernel of forces.hip call the same <class>_term and sum the energy themselves.  Functional forms: OpenMM HarmonicBondForce / HarmonicAngleForce / PeriodicTorsionForce /
 // NonbondedForce exceptions as the reference's test systems build them (testsystems.py:3504-3517); f64 restatement:
 // oracle/forcefield.py.
 #pragma once
@@ -41,101 +42,167 @@ __device__ __forceinline__ float2 softcore_exception(float lam_a, float sc, floa
 }
 
 
-// ---- the terms, one function per class: the forces on every atom of term t (slot order = the order of its atom indices).
-// Shared by the two ways the launch is organised below, so that both add exactly the same fixed-point numbers.
+// ---- the terms, one statement per class.  <class>_term is the arithmetic: it takes the term's atom indices and parameters as values,
+// leaves the forces on every atom of the term in `o` (slot order = the order of its atom indices) and returns what a caller needs to
+// form the energy in its own precision (forces.hip: f64 sums).  listed_<class> reads the values of
+// term t from listed_tables.  Every caller adds exactly the same fixed-point forces; one that does not use the forces, or the
+// returned value, leaves that part to dead-code elimination.
 // (named members, no arrays: a slot picked at run time from an array would put the array into scratch memory)
 struct listed_out { int a0, a1, a2, a3; float f0x, f0y, f0z, f1x, f1y, f1z, f2x, f2y, f2z, f3x, f3y, f3z; };
 #define LISTED_SET(o, k, X, Y, Z) do { (o).f##k##x = (X); (o).f##k##y = (Y); (o).f##k##z = (Z); } while (0)
-__device__ __forceinline__ void listed_bond(const listed_tables& T, int t, const float4* __restrict__ P, listed_out& o)
+// the forces of a term's first n atoms into the fixed-point accumulator of one replica
+__device__ __forceinline__ void listed_add(long long* __restrict__ F, int Npad, const listed_out& o, int n)
 {
-    const int i = T.bond_atoms[2 * t], j = T.bond_atoms[2 * t + 1];
-    const float r0 = T.bond_params[2 * t], k = T.bond_params[2 * t + 1];
+    add_force(F, Npad, o.a0, o.f0x, o.f0y, o.f0z);
+    add_force(F, Npad, o.a1, o.f1x, o.f1y, o.f1z);
+    if (n > 2) add_force(F, Npad, o.a2, o.f2x, o.f2y, o.f2z);
+    if (n > 3) add_force(F, Npad, o.a3, o.f3x, o.f3y, o.f3z);
+}
+// an angle's forces, ends first, for the caller that has always added them so (angle_kernel of forces.hip).  The
+// integer sums do not care, the compiler does: it pairs the products behind the atomics into packed multiplies and FMAs in the order
+// it meets them, and another order contracts other products -- other last bits of that caller's forces.
+__device__ __forceinline__ void listed_add_angle(long long* __restrict__ F, int Npad, const listed_out& o)
+{
+    add_force(F, Npad, o.a0, o.f0x, o.f0y, o.f0z);
+    add_force(F, Npad, o.a2, o.f2x, o.f2y, o.f2z);
+    add_force(F, Npad, o.a1, o.f1x, o.f1y, o.f1z);
+}
+
+// harmonic bond 0.5 k (len - r0)^2; returns len - r0
+__device__ __forceinline__ float bond_term(int i, int j, float r0, float k, const float4* __restrict__ P, listed_out& o)
+{
     const float3 d = sub3(ld3(P, j), ld3(P, i));
     const float len = sqrtf(dotf(d, d));
-    const float fs = k * (len - r0) / len;
+    const float dl = len - r0;
+    const float fs = k * dl / len;                   // F_i = +fs * d, F_j = -fs * d
     o.a0 = i; o.a1 = j;
     LISTED_SET(o, 0, fs * d.x, fs * d.y, fs * d.z);
     LISTED_SET(o, 1, -fs * d.x, -fs * d.y, -fs * d.z);
+    return dl;
 }
-__device__ __forceinline__ void listed_angle(const listed_tables& T, int t, const float4* __restrict__ P, listed_out& o)
+// harmonic angle 0.5 k (theta - th0)^2 at b; returns theta - th0
+__device__ __forceinline__ float angle_term(int a, int b, int c, float th0, float k, const float4* __restrict__ P, listed_out& o)
 {
-    const int a = T.angle_atoms[3 * t], b = T.angle_atoms[3 * t + 1], c = T.angle_atoms[3 * t + 2];
-    const float th0 = T.angle_params[2 * t], k = T.angle_params[2 * t + 1];
-    const float3 v0 = sub3(ld3(P, a), ld3(P, b)), v1 = sub3(ld3(P, c), ld3(P, b));
+    const float3 v0 = sub3(ld3(P, a), ld3(P, b)), v1 = sub3(ld3(P, c), ld3(P, b));      // b -> a, b -> c
     const float3 cp = crs3(v0, v1);
     const float rp = fmaxf(sqrtf(dotf(cp, cp)), 1e-6f);
     const float r20 = dotf(v0, v0), r21 = dotf(v1, v1);
     const float cosine = fminf(fmaxf(dotf(v0, v1) * rsqrtf(r20 * r21), -1.f), 1.f);
-    const float dEdth = k * (acosf(cosine) - th0);
+    const float dth = acosf(cosine) - th0;
+    const float dEdth = k * dth;
+    // dtheta/dx_a = (v0 x cp) / (|v0|^2 |cp|),  dtheta/dx_c = (cp x v1) / (|v1|^2 |cp|)
     const float3 fa = scl3(crs3(v0, cp), -dEdth / (r20 * rp));
     const float3 fc = scl3(crs3(cp, v1), -dEdth / (r21 * rp));
     o.a0 = a; o.a1 = b; o.a2 = c;
     LISTED_SET(o, 0, fa.x, fa.y, fa.z); LISTED_SET(o, 2, fc.x, fc.y, fc.z);
     LISTED_SET(o, 1, -(fa.x + fc.x), -(fa.y + fc.y), -(fa.z + fc.z));
+    return dth;
 }
-__device__ __forceinline__ void listed_torsion(const listed_tables& T, int t, const float4* __restrict__ P, listed_out& o)
+// periodic torsion k (1 + cos(per phi - phase)); returns per phi - phase
+__device__ __forceinline__ float torsion_term(int a1, int a2, int a3, int a4, float per, float phase, float k, const float4* __restrict__ P,
+                                              listed_out& o)
 {
-    const int a1 = T.torsion_atoms[4 * t], a2 = T.torsion_atoms[4 * t + 1], a3 = T.torsion_atoms[4 * t + 2], a4 = T.torsion_atoms[4 * t + 3];
-    const float per = T.torsion_params[3 * t], phase = T.torsion_params[3 * t + 1], k = T.torsion_params[3 * t + 2];
     const float3 p1 = ld3(P, a1), p2 = ld3(P, a2), p3 = ld3(P, a3), p4 = ld3(P, a4);
     const float3 b1 = sub3(p2, p1), b2 = sub3(p3, p2), b3 = sub3(p4, p3);
     const float3 m = crs3(b1, b2), nn = crs3(b2, b3);
     const float m2 = fmaxf(dotf(m, m), 1e-12f), n2 = fmaxf(dotf(nn, nn), 1e-12f);
     const float lb2 = sqrtf(dotf(b2, b2));
+    // IUPAC dihedral: phi = atan2(|b2| b1.(b2 x b3), (b1 x b2).(b2 x b3))
     const float phi = atan2f(lb2 * dotf(b1, nn), dotf(m, nn));
-    const float dEdphi = -k * per * sinf(per * phi - phase);
+    const float arg = per * phi - phase;
+    const float dEdphi = -k * per * sinf(arg);
+    // gradient of phi (Blondel & Karplus 1996)
     const float3 g1 = scl3(m, -lb2 / m2);
     const float3 g4 = scl3(nn, lb2 / n2);
     const float s12 = dotf(b1, b2) / (lb2 * lb2), s32 = dotf(b3, b2) / (lb2 * lb2);
-    const float3 g2 = add3(scl3(g1, -(1.f + s12)), scl3(g4, s32));
+    const float3 g2 = add3(scl3(g1, -(1.f + s12)), scl3(g4, s32));     // = -g1 - s12 g1 + s32 g4
     const float3 g3 = add3(scl3(g4, -(1.f + s32)), scl3(g1, s12));
     o.a0 = a1; o.a1 = a2; o.a2 = a3; o.a3 = a4;
     LISTED_SET(o, 0, -dEdphi * g1.x, -dEdphi * g1.y, -dEdphi * g1.z);
     LISTED_SET(o, 1, -dEdphi * g2.x, -dEdphi * g2.y, -dEdphi * g2.z);
     LISTED_SET(o, 2, -dEdphi * g3.x, -dEdphi * g3.y, -dEdphi * g3.z);
     LISTED_SET(o, 3, -dEdphi * g4.x, -dEdphi * g4.y, -dEdphi * g4.z);
+    return arg;
 }
-__device__ __forceinline__ void listed_exception(const listed_tables& T, int t, const float4* __restrict__ P, const float* __restrict__ box, int r,
-                                                 listed_out& o)
+// 1-4 style exception with non-zero parameters: plain Coulomb + LJ, no cutoff, no switch; returns U.  L: the box edges (L.x <= 0: no
+// box).  lam: the replica's row of rep_lam (NULL: no alchemy), alch: the pair's alchemical atoms -- > 0 scales the charge product
+// (alchemy.py:1964-1966 exception offset), 1 with eps != 0 takes the soft-core.
+__device__ __forceinline__ float exception_term(int i, int j, float qq, float sig, float eps, int alch, const float* __restrict__ lam, float3 L,
+                                                const float4* __restrict__ P, listed_out& o)
 {
-    const float Lx = box[4 * r], Ly = box[4 * r + 1], Lz = box[4 * r + 2];
-    const int i = T.exc_atoms[2 * t], j = T.exc_atoms[2 * t + 1];
-    float qq = T.exc_params[3 * t];
-    const float sig = T.exc_params[3 * t + 1], eps = T.exc_params[3 * t + 2];
-    if (T.rep_lam && T.exc_alch[t] > 0) qq *= T.rep_lam[4 * r + 2];      // alchemy.py:1964-1966 exception offset
+    if (lam && alch > 0) qq *= lam[2];
     float3 d = sub3(ld3(P, j), ld3(P, i));
-    if (Lx > 0.f) { d.x -= Lx * rintf(d.x / Lx); d.y -= Ly * rintf(d.y / Ly); d.z -= Lz * rintf(d.z / Lz); }
+    if (L.x > 0.f) { d.x -= L.x * rintf(d.x / L.x); d.y -= L.y * rintf(d.y / L.y); d.z -= L.z * rintf(d.z / L.z); }
     const float r2 = dotf(d, d);
     const float inv_r = rsqrtf(r2);
-    float dUlj;
-    if (T.rep_lam && T.exc_alch[t] == 1 && eps != 0.f) {
-        dUlj = softcore_exception(T.rep_lam[4 * r], T.rep_lam[4 * r + 1], sig, eps, r2, inv_r).y;
+    float Ulj, dUlj;
+    if (lam && alch == 1 && eps != 0.f) {
+        const float2 sc = softcore_exception(lam[0], lam[1], sig, eps, r2, inv_r);
+        Ulj = sc.x; dUlj = sc.y;
     } else {
         const float s2 = sig * sig * inv_r * inv_r, s6 = s2 * s2 * s2;
-        dUlj = 4.f * eps * s6 * (6.f - 12.f * s6) * inv_r;
+        Ulj = 4.f * eps * s6 * (s6 - 1.f); dUlj = 4.f * eps * s6 * (6.f - 12.f * s6) * inv_r;
     }
-    const float fr = (dUlj - qq * inv_r * inv_r) * inv_r;
+    const float U = Ulj + qq * inv_r;
+    const float dUdr = dUlj - qq * inv_r * inv_r;
+    const float fr = dUdr * inv_r;
     o.a0 = i; o.a1 = j;
     LISTED_SET(o, 0, fr * d.x, fr * d.y, fr * d.z);
     LISTED_SET(o, 1, -fr * d.x, -fr * d.y, -fr * d.z);
+    return U;
+}
+// Ewald correction for an excluded pair: the reciprocal sum contains it, so subtract qq erf(alpha r)/r; returns U.  alch alchemical
+// atoms scale the charge product by lambda_electrostatics^alch.
+// R_FIRST: alpha r is formed as alpha (r2 / r) instead of (alpha r2) / r.  The evaluations with energies have always rounded it the
+// first way and the force-only ones the second; the two differ in the last bit, and each caller keeps its own.
+template <bool R_FIRST>
+__device__ __forceinline__ float exclusion_term(int i, int j, float qq, int alch, const float* __restrict__ lam, float3 L, float alpha,
+                                                float two_alpha_sqrtpi, const float4* __restrict__ P, listed_out& o)
+{
+    if (lam) { const float le = lam[2]; qq *= (alch == 2) ? le * le : (alch == 1) ? le : 1.f; }
+    float3 d = sub3(ld3(P, j), ld3(P, i));
+    d.x -= L.x * rintf(d.x / L.x); d.y -= L.y * rintf(d.y / L.y); d.z -= L.z * rintf(d.z / L.z);
+    const float r2 = dotf(d, d);
+    const float inv_r = rsqrtf(r2);
+    const float ar = R_FIRST ? alpha * (r2 * inv_r) : alpha * r2 * inv_r;
+    const float erf_ar = erff(ar);
+    const float U = -qq * erf_ar * inv_r;
+    const float dUdr = -qq * (two_alpha_sqrtpi * __expf(-ar * ar) * inv_r - erf_ar * inv_r * inv_r);
+    const float fr = dUdr * inv_r;
+    o.a0 = i; o.a1 = j;
+    LISTED_SET(o, 0, fr * d.x, fr * d.y, fr * d.z);
+    LISTED_SET(o, 1, -fr * d.x, -fr * d.y, -fr * d.z);
+    return U;
+}
+
+// the loaders: term t of listed_tables, replica r
+__device__ __forceinline__ void listed_bond(const listed_tables& T, int t, const float4* __restrict__ P, listed_out& o)
+{
+    bond_term(T.bond_atoms[2 * t], T.bond_atoms[2 * t + 1], T.bond_params[2 * t], T.bond_params[2 * t + 1], P, o);
+}
+__device__ __forceinline__ void listed_angle(const listed_tables& T, int t, const float4* __restrict__ P, listed_out& o)
+{
+    angle_term(T.angle_atoms[3 * t], T.angle_atoms[3 * t + 1], T.angle_atoms[3 * t + 2], T.angle_params[2 * t], T.angle_params[2 * t + 1], P, o);
+}
+__device__ __forceinline__ void listed_torsion(const listed_tables& T, int t, const float4* __restrict__ P, listed_out& o)
+{
+    torsion_term(T.torsion_atoms[4 * t], T.torsion_atoms[4 * t + 1], T.torsion_atoms[4 * t + 2], T.torsion_atoms[4 * t + 3],
+                 T.torsion_params[3 * t], T.torsion_params[3 * t + 1], T.torsion_params[3 * t + 2], P, o);
+}
+__device__ __forceinline__ float3 box_edges(const float* __restrict__ box, int r) { return make_float3(box[4 * r], box[4 * r + 1], box[4 * r + 2]); }
+__device__ __forceinline__ void listed_exception(const listed_tables& T, int t, const float4* __restrict__ P, const float* __restrict__ box, int r,
+                                                 listed_out& o)
+{
+    const float* lam = T.rep_lam ? T.rep_lam + 4 * r : nullptr;
+    exception_term(T.exc_atoms[2 * t], T.exc_atoms[2 * t + 1], T.exc_params[3 * t], T.exc_params[3 * t + 1], T.exc_params[3 * t + 2],
+                   lam ? T.exc_alch[t] : 0, lam, box_edges(box, r), P, o);
 }
 __device__ __forceinline__ void listed_exclusion(const listed_tables& T, int t, const float4* __restrict__ P, const float* __restrict__ box, int r,
                                                  listed_out& o)
 {
-    const float Lx = box[4 * r], Ly = box[4 * r + 1], Lz = box[4 * r + 2];
-    const int i = T.excl_atoms[2 * t], j = T.excl_atoms[2 * t + 1];
-    float qq = T.excl_qq[t];
-    if (T.rep_lam) { const float le = T.rep_lam[4 * r + 2]; const int na = T.excl_alch[t]; qq *= (na == 2) ? le * le : (na == 1) ? le : 1.f; }
-    float3 d = sub3(ld3(P, j), ld3(P, i));
-    d.x -= Lx * rintf(d.x / Lx); d.y -= Ly * rintf(d.y / Ly); d.z -= Lz * rintf(d.z / Lz);
-    const float r2 = dotf(d, d);
-    const float inv_r = rsqrtf(r2);
-    const float ar = T.alpha * r2 * inv_r;
-    const float erf_ar = erff(ar);
-    const float fr = -qq * (T.two_alpha_sqrtpi * __expf(-ar * ar) * inv_r - erf_ar * inv_r * inv_r) * inv_r;
-    o.a0 = i; o.a1 = j;
-    LISTED_SET(o, 0, fr * d.x, fr * d.y, fr * d.z);
-    LISTED_SET(o, 1, -fr * d.x, -fr * d.y, -fr * d.z);
+    const float* lam = T.rep_lam ? T.rep_lam + 4 * r : nullptr;
+    exclusion_term<false>(T.excl_atoms[2 * t], T.excl_atoms[2 * t + 1], T.excl_qq[t], lam ? T.excl_alch[t] : 0, lam, box_edges(box, r),
+                          T.alpha, T.two_alpha_sqrtpi, P, o);
 }
 
 // All short "listed" terms of one force evaluation in a single launch (force-only path): harmonic bonds, angles,
@@ -220,8 +287,5 @@ void listed_forces_body(const listed_tables& T, int Npad, const float4* __restri
         }
         return;
     }
-    add_force(F, Npad, o.a0, o.f0x, o.f0y, o.f0z);
-    add_force(F, Npad, o.a1, o.f1x, o.f1y, o.f1z);
-    if (n > 2) add_force(F, Npad, o.a2, o.f2x, o.f2y, o.f2z);
-    if (n > 3) add_force(F, Npad, o.a3, o.f3x, o.f3y, o.f3z);
+    listed_add(F, Npad, o, n);
 }
