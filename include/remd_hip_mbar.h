@@ -67,6 +67,55 @@ int  remd_mbar_chunks(remd_mbar m, int C, int64_t* column_chunk, int64_t* row_ch
 /* device milliseconds of the kernels of the last call on this object (events around its launches), for tools                     */
 int  remd_mbar_last_ms(remd_mbar m, double* ms);
 
+/* ---- bootstrap replicates -------------------------------------------------------------------------------------------------------
+ * A bootstrap replicate of the problem resamples every sampled state's samples with replacement, N_k draws from the N_k samples of
+ * state k.  It is kept as a vector of multiplicities c_n >= 0 over the N stored samples (sum of c_n over the samples of state k =
+ * N_k), never as a gathered matrix, and enters every equation as the weight of sample n:
+ *
+ *   log_den_n  unchanged                                        f_i = -ln sum_n c_n exp(-u_in - log_den_n)
+ *   W_sum_k = sum_n c_n W_kn                                    gram = W diag(c) W^T
+ *   phi = sum_n c_n log_den_n - sum_k N_k f_k
+ *
+ * Draw j = 0 .. N_k - 1 of state k (its row of u_kn) in replicate t takes the Philox4x32-10 block of csrc/rng.h with the key `seed`
+ * and the counter (a, b, t) = (j >> 1, k, t) on stream REMD_STREAM_BOOTSTRAP = 9: the 64-bit word x = (w0 << 32) | w1 for even j,
+ * (w2 << 32) | w3 for odd j, selects the floor(x N_k / 2^64)-th sample of state k in ascending sample order (an exact integer high
+ * multiply).  The counts are accumulated with integer atomics: exact, and free of any order.
+ *
+ * The drawn replicates stay on the device until the next draw.  At most REMD_MBAR_BOOTSTRAP_BATCH_ELEMENTS / N of them (and at most
+ * REMD_MBAR_BOOTSTRAP_MAX_BATCH, at least 1) may be resident: 4 bytes of multiplicities and 8 of log denominator per replicate and
+ * sample, 192 MiB at the bound; the partial Gram matrices of a launch are bounded by 256 MiB on top.  A host that wants more
+ * replicates draws and solves them batch by batch.
+ *
+ * Every batched pass takes nr replicates reps[nr] of the drawn range, in any order, each at its own f_b[nr][K]; the replicate is a
+ * grid dimension of its kernels.  What a pass returns for a replicate depends on (u_kn, N_k, sample_states, seed, the replicate's
+ * number, its f_b) alone: not on the other replicates of the call or of the draw, and not on the run.
+ * Refused, with a message: nr (or nb) < 1, a replicate outside the drawn range, a non-finite f_b, a sample_states entry that is
+ * not a sampled state, a histogram of sample_states that is not N_k.                                                              */
+#define REMD_MBAR_BOOTSTRAP_BATCH_ELEMENTS (1 << 24)
+#define REMD_MBAR_BOOTSTRAP_MAX_BATCH 1024
+
+/* the most replicates one draw may make resident for this problem                                                                */
+int  remd_mbar_bootstrap_max_batch(remd_mbar m, int* nb);
+/* draws the multiplicities of replicates b0 .. b0 + nb - 1.  sample_states[N]: the row of u_kn each sample was drawn from, or
+   NULL: the samples lie in blocks, the first N_0 from state 0 and so on.                                                         */
+int  remd_mbar_bootstrap_draw(remd_mbar m, uint64_t seed, const int32_t* sample_states, int b0, int nb);
+/* counts[nb][N] of drawn replicates b0 .. b0 + nb - 1, for tests                                                                 */
+int  remd_mbar_bootstrap_counts(remd_mbar m, int b0, int nb, uint32_t* counts);
+/* log_den[nr][N] (or NULL; unchanged by the multiplicities) and phi[nr] (or NULL)                                                */
+int  remd_mbar_bootstrap_log_denominator(remd_mbar m, int nr, const int32_t* reps, const double* f_b, double* log_den, double* phi);
+/* one weighted application of eq. 11 to every state, sampled or not: f_new[nr][K], not shifted                                   */
+int  remd_mbar_bootstrap_self_consistent(remd_mbar m, int nr, const int32_t* reps, const double* f_b, double* f_new);
+/* W_sum[nr][K], gram[nr][K][K] (rows and columns of unsampled states 0; the lower triangle is computed, with c_n multiplied into
+   one operand, and mirrored) and phi[nr] (or NULL)                                                                               */
+int  remd_mbar_bootstrap_newton_parts(remd_mbar m, int nr, const int32_t* reps, const double* f_b, double* W_sum, double* gram, double* phi);
+/* The weighted row passes of perturbed free energies and expectations.  u_ln[L][N] and A_in[I][N] are uploaded once for the call.
+     f_l[nr][L]      -ln sum_n c_n exp(-u_ln - log_den_n)
+     log_cA[nr][I]   ln sum_n c_n W_n,s A_in  with s = obs_state[i] < K + L a stored state (at f_b) or a perturbed one (at f_l)
+   L or I may be 0 (its arrays NULL), not both.  Refused as in remd_mbar_augmented_gram, and where a perturbed state keeps no
+   sample with a non-zero weight in a replicate.                                                                                  */
+int  remd_mbar_bootstrap_rows(remd_mbar m, int nr, const int32_t* reps, const double* f_b, int L, const double* u_ln, int I, const double* A_in,
+                              const int32_t* obs_state, double* f_l, double* log_cA);
+
 #ifdef __cplusplus
 }
 #endif

@@ -129,6 +129,10 @@ MBAR_EXPORTS = ['remd_mbar_create', 'remd_mbar_destroy', 'remd_mbar_log_denomina
 MBAR_MAX_STATES = 512
 # the augmented Gram matrix of the same header (perturbed states and observables): a library built before it lacks the entry point
 MBAR_AUGMENTED_EXPORTS = ['remd_mbar_augmented_gram']
+# the bootstrap replicates of the same header (multiplicities drawn on the device, the batched weighted passes), bound the same way
+MBAR_BOOTSTRAP_EXPORTS = ['remd_mbar_bootstrap_max_batch', 'remd_mbar_bootstrap_draw', 'remd_mbar_bootstrap_counts',
+                          'remd_mbar_bootstrap_log_denominator', 'remd_mbar_bootstrap_self_consistent', 'remd_mbar_bootstrap_newton_parts',
+                          'remd_mbar_bootstrap_rows']
 # the GPU-only extension of include/remd_hip_timeseries.h (statistical inefficiencies of the suffixes of a timeseries), bound the same way
 TIMESERIES_EXPORTS = ['remd_timeseries_create', 'remd_timeseries_destroy', 'remd_timeseries_inefficiency', 'remd_timeseries_chunks',
                       'remd_timeseries_last_ms']
@@ -310,6 +314,17 @@ def load_library(path=None):
         lib.remd_mbar_augmented_gram.argtypes = [vp, c_double_p, C.c_int, c_double_p, C.c_int, c_double_p, c_int32_p, c_double_p, c_double_p,
                                                  c_double_p]
         lib.remd_mbar_augmented_gram.restype = C.c_int
+    if hasattr(lib, 'remd_mbar_bootstrap_draw'):
+        lib.remd_mbar_bootstrap_max_batch.argtypes = [vp, C.POINTER(C.c_int)]
+        lib.remd_mbar_bootstrap_draw.argtypes = [vp, C.c_uint64, c_int32_p, C.c_int, C.c_int]
+        lib.remd_mbar_bootstrap_counts.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_uint32)]
+        lib.remd_mbar_bootstrap_log_denominator.argtypes = [vp, C.c_int, c_int32_p, c_double_p, c_double_p, c_double_p]
+        lib.remd_mbar_bootstrap_self_consistent.argtypes = [vp, C.c_int, c_int32_p, c_double_p, c_double_p]
+        lib.remd_mbar_bootstrap_newton_parts.argtypes = [vp, C.c_int, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p]
+        lib.remd_mbar_bootstrap_rows.argtypes = [vp, C.c_int, c_int32_p, c_double_p, C.c_int, c_double_p, C.c_int, c_double_p, c_int32_p,
+                                                 c_double_p, c_double_p]
+        for name in MBAR_BOOTSTRAP_EXPORTS:
+            getattr(lib, name).restype = C.c_int
     if hasattr(lib, 'remd_timeseries_create'):            # include/remd_hip_timeseries.h (GPU-only, like the restraints)
         lib.remd_timeseries_create.argtypes = [C.c_int, C.c_int64, c_double_p, C.POINTER(vp)]
         lib.remd_timeseries_destroy.argtypes = [vp]
@@ -559,6 +574,90 @@ class DeviceMBAR(_DeviceObject):
         self._check(self.lib.remd_mbar_augmented_gram(self.h, _dp(f), L, _dp(u) if L else None, I, _dp(A) if I else None, _ip(obs),
                                                       _dp(f_l) if L else None, _dp(log_cA) if I else None, _dp(g)), 'remd_mbar_augmented_gram')
         return f_l, log_cA, g
+
+    # ---- bootstrap replicates (remd_mbar_bootstrap_*): NotImplementedError where the library lacks them -----------------------------
+    def _require_bootstrap(self):
+        _require_exports(self.lib, MBAR_BOOTSTRAP_EXPORTS, 'bootstrap passes (include/remd_hip_mbar.h declares them)')
+
+    def _batch(self, reps, f_b):
+        reps = np.ascontiguousarray(reps, dtype=np.int32).reshape(-1)
+        f = np.ascontiguousarray(f_b, dtype=np.float64)
+        if f.shape != (reps.size, self.K):
+            raise ValueError('f_b must be [nb][K], one row per replicate')
+        return reps, f
+
+    def bootstrap_max_batch(self):
+        """The most replicates one draw may make resident for this problem."""
+        self._require_bootstrap()
+        nb = C.c_int()
+        self._check(self.lib.remd_mbar_bootstrap_max_batch(self.h, C.byref(nb)), 'remd_mbar_bootstrap_max_batch')
+        return nb.value
+
+    def bootstrap_draw(self, seed, b0, nb, sample_states=None):
+        """Draws the multiplicities of replicates b0 .. b0 + nb - 1 on the device; they stay resident until the next draw."""
+        self._require_bootstrap()
+        labels = None if sample_states is None else np.ascontiguousarray(sample_states, dtype=np.int32).reshape(-1)
+        if labels is not None and labels.shape != (self.N,):
+            raise ValueError('sample_states must have one entry per sample')
+        self._check(self.lib.remd_mbar_bootstrap_draw(self.h, int(seed) & 0xFFFFFFFFFFFFFFFF, _ip(labels), int(b0), int(nb)),
+                    'remd_mbar_bootstrap_draw')
+
+    def bootstrap_counts(self, b0, nb):
+        """The multiplicities [nb][N] (uint32) of drawn replicates b0 .. b0 + nb - 1."""
+        self._require_bootstrap()
+        out = np.empty((max(int(nb), 0), self.N), dtype=np.uint32)
+        self._check(self.lib.remd_mbar_bootstrap_counts(self.h, int(b0), int(nb), out.ctypes.data_as(C.POINTER(C.c_uint32))),
+                    'remd_mbar_bootstrap_counts')
+        return out
+
+    def bootstrap_log_denominator(self, reps, f_b, want_log_den=True):
+        """(log_den [nb][N] or None, phi [nb]) of the replicates ``reps``, each at its row of ``f_b`` [nb][K]."""
+        self._require_bootstrap()
+        reps, f = self._batch(reps, f_b)
+        log_den = np.empty((reps.size, self.N)) if want_log_den else None
+        phi = np.empty(reps.size)
+        self._check(self.lib.remd_mbar_bootstrap_log_denominator(self.h, reps.size, _ip(reps), _dp(f), _dp(log_den), _dp(phi)),
+                    'remd_mbar_bootstrap_log_denominator')
+        return log_den, phi
+
+    def bootstrap_self_consistent(self, reps, f_b):
+        """One weighted application of eq. 11 per replicate: f_new [nb][K], not shifted."""
+        self._require_bootstrap()
+        reps, f = self._batch(reps, f_b)
+        out = np.empty((reps.size, self.K))
+        self._check(self.lib.remd_mbar_bootstrap_self_consistent(self.h, reps.size, _ip(reps), _dp(f), _dp(out)), 'remd_mbar_bootstrap_self_consistent')
+        return out
+
+    def bootstrap_newton_parts(self, reps, f_b):
+        """(W_sum [nb][K], W diag(c) W^T [nb][K][K], phi [nb]) per replicate; rows and columns of unsampled states are 0."""
+        self._require_bootstrap()
+        reps, f = self._batch(reps, f_b)
+        w, g, phi = np.empty((reps.size, self.K)), np.empty((reps.size, self.K, self.K)), np.empty(reps.size)
+        self._check(self.lib.remd_mbar_bootstrap_newton_parts(self.h, reps.size, _ip(reps), _dp(f), _dp(w), _dp(g), _dp(phi)),
+                    'remd_mbar_bootstrap_newton_parts')
+        return w, g, phi
+
+    def bootstrap_rows(self, reps, f_b, u_ln=None, A_in=None, obs_state=None):
+        """(f_l [nb][L], log_cA [nb][I]) per replicate: the weighted eq. 11 on the perturbed states ``u_ln`` [L][N] and ln sum_n c_n W A
+        of the observables ``A_in`` [I][N] (positive) on the weights of column ``obs_state[i]`` < K + L."""
+        self._require_bootstrap()
+        reps, f = self._batch(reps, f_b)
+        u = None if u_ln is None else np.ascontiguousarray(u_ln, dtype=np.float64)
+        A = None if A_in is None else np.ascontiguousarray(A_in, dtype=np.float64)
+        for a, what in ((u, 'u_ln'), (A, 'A_in')):
+            if a is not None and (a.ndim != 2 or a.shape[1] != self.N):
+                raise ValueError('%s must be [.][N] with N = %d' % (what, self.N))
+        L = 0 if u is None else int(u.shape[0])
+        I = 0 if A is None else int(A.shape[0])
+        obs = None
+        if I:
+            obs = np.ascontiguousarray(obs_state, dtype=np.int32).reshape(-1)
+            if obs.shape != (I,):
+                raise ValueError('obs_state must name one column per observable')
+        f_l, log_cA = np.empty((reps.size, L)), np.empty((reps.size, I))
+        self._check(self.lib.remd_mbar_bootstrap_rows(self.h, reps.size, _ip(reps), _dp(f), L, _dp(u) if L else None, I, _dp(A) if I else None,
+                                                      _ip(obs), _dp(f_l) if L else None, _dp(log_cA) if I else None), 'remd_mbar_bootstrap_rows')
+        return f_l, log_cA
 
     def log_weights(self, f_k):
         """log_W_nk [N][K] at f_k."""

@@ -9,24 +9,15 @@
 //                call (the row pass of eq. 11 on u_ln, a row pass for ln <A>, the Gram tiles over the K + L + I columns)
 //
 // No floating-point atomics: every sum has one fixed order, set by (K, N) alone.
-#include "device_object.h"
-#include "../../include/remd_hip_mbar.h"
+#include "mbar_ctx.h"
 #include <cmath>
 #include <limits>
 
-#define MBAR_BLOCK       256
-#define MBAR_ROW_CHUNK   4096          // samples per workgroup of the row pass: 16 per thread
-#define MBAR_TILE        64            // columns of the Gram matrix per tile edge
-#define MBAR_TSTEP       16            // samples staged in LDS per step of the Gram pass
-#define MBAR_LDS_STRIDE  (MBAR_TILE + 2)
 #define MBAR_GRAM_MIN_CHUNK   256
 #define MBAR_GRAM_MAX_CHUNKS  256
 #define MBAR_GRAM_PARTIAL_CAP (int64_t(1) << 25)   // doubles of per-chunk partials at most (256 MiB)
 
 enum { MBAR_ROW_SC = 0, MBAR_ROW_LOGCA = 1, MBAR_ROW_WSUM = 2 };
-
-// _logsumexp's guard: a non-finite maximum counts as 0
-__device__ __forceinline__ double mbar_guard(double m) { return isfinite(m) ? m : 0.0; }
 
 // ---- column pass ----------------------------------------------------------------------------------------------------------------
 // fs[Ks], nk[Ks], srow[Ks]: f_k, N_k and the row of u of the sampled states
@@ -95,20 +86,7 @@ __global__ __launch_bounds__(MBAR_BLOCK) void mbar_row_kernel(const double* __re
     if (threadIdx.x == 0) pairs[(int64_t)k * gridDim.x + blockIdx.x] = make_double2(mraw, t);
 }
 
-// one thread per state merges its pairs in chunk order.  as_log: out = sign * (ln S + M), else out = S
-__global__ void mbar_row_merge_kernel(const double2* __restrict__ pairs, int K, int chunks, int as_log, double sign, double* __restrict__ out)
-{
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= K) return;
-    const double2* p = pairs + (int64_t)k * chunks;
-    double M = -INFINITY;
-    for (int c = 0; c < chunks; c++) M = nanmax(M, p[c].x);
-    M = mbar_guard(M);
-    double S = 0.0;
-    for (int c = 0; c < chunks; c++)
-        if (p[c].y != 0.0) S += p[c].y * exp(mbar_guard(p[c].x) - M);      // (an empty chunk's scale may overflow: it adds nothing)
-    out[k] = as_log ? sign * (log(S) + M) : S;
-}
+// (mbar_row_merge_kernel: mbar_ctx.h)
 
 // ---- Gram pass ------------------------------------------------------------------------------------------------------------------
 struct mbar_gram_args {
@@ -310,19 +288,7 @@ __global__ __launch_bounds__(MBAR_BLOCK) void mbar_log_weights_kernel(const doub
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-struct remd_mbar_ctx {
-    int K = 0, Ks = 0;
-    int64_t N = 0;
-    double shift = 0.0;
-    bool timed = false;                     // a pass has run: tm.ms holds its kernels
-    std::vector<double> nk_all;             // [K]
-    std::vector<int> srow;                  // [Ks]
-    dev_array<double> u, nk, fs, f, log_den, col_partial, scalar, row_out, log_cA, gram, gram_partial, weights;
-    dev_array<int> d_srow, col_state;
-    dev_array<int2> tiles;
-    dev_array<double2> pairs;
-    device_timer tm;
-};
+// (remd_mbar_ctx: mbar_ctx.h)
 
 static int64_t mbar_gram_chunk(int64_t N, int C)
 {

@@ -21,6 +21,7 @@
 #define REMD_STREAM_METROPOLIS 7u // a = index of the '}' inside the step program, b = global replica ; t = global step
 #define REMD_STREAM_BAROSTAT  6u  // a = 0: volume draw, 1: acceptance uniform ; b = global replica ; t = attempt counter
 #define REMD_STREAM_MC_MOVE   8u  // a = 4 * place in the move sequence + block (0, 1: proposal uniforms, 2: acceptance uniform), b = global replica ; t = iteration
+#define REMD_STREAM_BOOTSTRAP 9u  // a = draw >> 1 (words 0, 1: the even draw; 2, 3: the odd one), b = state ; t = bootstrap replicate
 
 struct philox4 { uint32_t w[4]; };
 

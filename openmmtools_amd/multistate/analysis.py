@@ -322,12 +322,31 @@ class MBAR:
     ``compute_entropy_and_enthalpy``, on the Gram matrix of the weights augmented by one column per perturbed state and per
     observable (N_k = 0 for those).  With ``solver='device'`` that matrix comes from one call of remd_mbar_augmented_gram and the
     ``[N][K]`` weights never leave the GPU.
+
+    ``n_bootstraps=B`` > 0 also solves B bootstrap replicates (pymbar 4's ``n_bootstraps``), each from the full-sample ``f_k``, and
+    keeps their free energies in ``f_k_boots`` [B][K] (each row shifted to f_0 = 0).  A replicate resamples every sampled state's
+    samples with replacement, N_k draws from its own N_k samples, and is a vector of multiplicities c_n over the stored samples
+    that weights every sum of the estimator (include/remd_hip_mbar.h states the equations and the Philox draws, which
+    ``bootstrap_seed`` keys; both solvers draw the same replicates).  ``sample_states`` [N] names the row of ``u_kn`` each sample was
+    drawn from; without it the samples lie in pymbar's blocks, the first N_0 from state 0 and so on.
+    ``compute_free_energy_differences``, ``compute_perturbed_free_energies`` and ``compute_expectations`` then take
+    ``uncertainty_method='bootstrap'``: the population standard deviation (ddof = 0) over the replicates in place of eq. 8.
+    With ``solver='device'`` the multiplicities are drawn on the GPU and the replicates are solved there in batches, every pass
+    one call for the whole batch; the K x K algebra stays on the host, batched.
     """
 
+    UNCERTAINTY_METHODS = (None, 'svd', 'bootstrap')
+
     def __init__(self, u_kn, N_k, initial_f_k=None, relative_tolerance=1.0e-12, maximum_iterations=10000, solver='numpy',
-                 device=0, lib_path=None):
+                 device=0, lib_path=None, n_bootstraps=0, bootstrap_seed=0, sample_states=None):
         if solver not in ('numpy', 'device'):
             raise ValueError("solver must be 'numpy' or 'device', not %r" % (solver,))
+        if isinstance(n_bootstraps, bool) or int(n_bootstraps) != n_bootstraps or n_bootstraps < 0:
+            raise ValueError('n_bootstraps must be a non-negative integer, not %r' % (n_bootstraps,))
+        if isinstance(bootstrap_seed, bool) or int(bootstrap_seed) != bootstrap_seed or not 0 <= bootstrap_seed < 2 ** 64:
+            raise ValueError('bootstrap_seed must be an integer in 0 ... 2^64 - 1, not %r' % (bootstrap_seed,))
+        self.n_bootstraps, self.bootstrap_seed = int(n_bootstraps), int(bootstrap_seed)
+        self.f_k_boots = None
         self.solver = solver
         self._dev = None
         self.u_kn = np.array(u_kn, dtype=np.float64)
@@ -338,14 +357,30 @@ class MBAR:
         if not np.all(np.isfinite(self.u_kn[self.N_k > 0])):
             raise ParameterError('non-finite reduced potentials in a sampled state')
         self.K, self.N = K, N
+        self.sample_states = None
+        if sample_states is not None:
+            labels = np.array(sample_states)
+            if labels.shape != (N,) or labels.dtype.kind not in 'iu' or np.any(labels < 0) or np.any(labels >= K) \
+                    or not np.array_equal(np.bincount(labels, minlength=K), self.N_k):
+                raise ParameterError('sample_states must name the state each of the %d samples was drawn from: its histogram must be N_k' % N)
+            self.sample_states = labels.astype(np.int64)
         f = np.zeros(K) if initial_f_k is None else np.array(initial_f_k, dtype=np.float64) - float(np.asarray(initial_f_k)[0])
         if solver == 'device':
             from .._engine import DeviceMBAR
             self._dev = DeviceMBAR(self.u_kn, self.N_k, device=device, lib_path=lib_path)
+            if self.n_bootstraps:
+                self._dev._require_bootstrap()
             self.f_k = self._solve_device(f, relative_tolerance, maximum_iterations)
         else:
             self.f_k = self._solve(f, relative_tolerance, maximum_iterations)
         self._log_W = None
+        if self.n_bootstraps:
+            self._rtol, self._maxiter = relative_tolerance, maximum_iterations
+            replicates = np.arange(self.n_bootstraps)
+            if self._dev is not None:
+                self.f_k_boots = np.concatenate([self._solve_bootstrap_device(r) for r in self._device_batches(replicates)], axis=0)
+            else:
+                self.f_k_boots = np.stack([self._solve_weighted(self._bootstrap_counts(b), b) for b in replicates])
 
     # log of the mixture denominator per sample: ln sum_k N_k exp(f_k - u_kn)
     def _log_denominator(self, f_k):
@@ -461,6 +496,178 @@ class MBAR:
             out[uns] = dev.self_consistent(out)[uns]
         return out - out[0]
 
+    # ---- bootstrap replicates: the same equations with the multiplicity c_n as the weight of sample n -------------------------------
+    def _bootstrap_counts(self, replicate):
+        """c_n [N] of one replicate, as the device draws it"""
+        from ._philox import bootstrap_counts
+        return bootstrap_counts(self.bootstrap_seed, int(replicate), self.N_k, self.sample_states)
+
+    def _solve_weighted(self, c_n, replicate):
+        """_solve on the weighted equations, line by line, from the full-sample f_k.  Samples with c_n = 0 do not enter."""
+        rtol, maxiter = self._rtol, self._maxiter
+        s = np.flatnonzero(self.N_k > 0)
+        n = np.flatnonzero(c_n)
+        c = np.asarray(c_n, dtype=np.float64)[n]
+        u = self.u_kn[np.ix_(s, n)]
+        Nk = self.N_k[s].astype(np.float64)
+        f = self.f_k[s] - self.f_k[s][0]
+
+        def objective_parts(f):
+            log_den = _logsumexp(f[:, None] - u, axis=0, b=Nk[:, None])
+            log_W = f[:, None] - u - log_den[None, :]                     # [Ks, Nc]
+            return log_den, log_W
+
+        for _ in range(5):
+            log_den, _ = objective_parts(f)
+            f_new = -_logsumexp(-u - log_den[None, :], axis=1, b=c[None, :])
+            f = f_new - f_new[0]
+        for _ in range(maxiter):
+            log_den, log_W = objective_parts(f)
+            W = np.exp(log_W)
+            cW = W * c[None, :]
+            g = Nk * (cW.sum(axis=1) - 1.0)
+            H = np.diag(Nk * cW.sum(axis=1)) - (Nk[:, None] * Nk[None, :]) * (cW @ W.T)
+            if s.size > 1:
+                try:
+                    step = np.zeros_like(f)
+                    step[1:] = np.linalg.solve(H[1:, 1:], g[1:])
+                except np.linalg.LinAlgError:
+                    step = np.zeros_like(f)
+                    step[1:] = np.linalg.lstsq(H[1:, 1:], g[1:], rcond=None)[0]
+            else:
+                step = np.zeros_like(f)
+            phi0 = np.dot(c, log_den) - np.dot(Nk, f)
+            scale = 1.0
+            while True:                                                   # backtrack: the objective must not increase
+                f_try = f - scale * step
+                phi = np.dot(c, objective_parts(f_try)[0]) - np.dot(Nk, f_try)
+                if phi <= phi0 + 1e-12 * abs(phi0) or scale < 1e-6:
+                    break
+                scale *= 0.5
+            delta = np.max(np.abs(f_try - f))
+            f = f_try
+            if delta <= rtol * max(1.0, np.max(np.abs(f))):
+                break
+        else:
+            raise ParameterError('MBAR did not converge for bootstrap replicate %d' % replicate)
+        if not np.all(np.isfinite(f)):
+            raise ParameterError('MBAR produced non-finite free energies for bootstrap replicate %d' % replicate)
+        out = np.zeros(self.K)
+        out[s] = f
+        log_den = _logsumexp(f[:, None] - u, axis=0, b=Nk[:, None])
+        uns = np.flatnonzero(self.N_k == 0)
+        if uns.size:
+            out[uns] = -_logsumexp(-self.u_kn[np.ix_(uns, n)] - log_den[None, :], axis=1, b=c[None, :])
+        return out - out[0]
+
+    def _device_batches(self, replicates):
+        """``replicates`` in runs of at most the device's resident batch; each run is drawn on the device before it is handed out"""
+        most = self._dev.bootstrap_max_batch()
+        for i in range(0, len(replicates), most):
+            r = np.asarray(replicates[i:i + most], dtype=np.int64)
+            self._dev.bootstrap_draw(self.bootstrap_seed, int(r.min()), int(r.max() - r.min()) + 1, self.sample_states)
+            yield r
+
+    def _solve_bootstrap_device(self, reps):
+        """_solve_weighted for the drawn replicates ``reps`` at once: every pass is one call of the device for the replicates still
+        iterating, the K x K algebra is batched on the host.  Returns f [len(reps)][K], each row shifted to f_0 = 0."""
+        dev, rtol, maxiter = self._dev, self._rtol, self._maxiter
+        reps = np.asarray(reps, dtype=np.int64)
+        s = np.flatnonzero(self.N_k > 0)
+        Ks, nb = s.size, reps.size
+        Nk = self.N_k[s].astype(np.float64)
+        F = np.tile(self.f_k[s] - self.f_k[s][0], (nb, 1))               # [nb][Ks]
+
+        def full(F):
+            out = np.zeros((F.shape[0], self.K))
+            out[:, s] = F
+            return out
+
+        for _ in range(5):
+            f_new = dev.bootstrap_self_consistent(reps, full(F))[:, s]
+            F = f_new - f_new[:, :1]
+        active = np.arange(nb)
+        for _ in range(maxiter):
+            f = F[active]
+            W_sum, gram, phi0 = dev.bootstrap_newton_parts(reps[active], full(f))
+            W_sum, WWt = W_sum[:, s], gram[:, s][:, :, s]
+            g = Nk[None, :] * (W_sum - 1.0)
+            H = -(Nk[:, None] * Nk[None, :])[None, :, :] * WWt
+            H[:, np.arange(Ks), np.arange(Ks)] += Nk[None, :] * W_sum
+            step = np.zeros_like(f)
+            if Ks > 1:
+                try:
+                    step[:, 1:] = np.linalg.solve(H[:, 1:, 1:], g[:, 1:, None])[:, :, 0]
+                except np.linalg.LinAlgError:                             # a singular replicate: each on its own, as _solve does
+                    for i in range(len(active)):
+                        try:
+                            step[i, 1:] = np.linalg.solve(H[i, 1:, 1:], g[i, 1:])
+                        except np.linalg.LinAlgError:
+                            step[i, 1:] = np.linalg.lstsq(H[i, 1:, 1:], g[i, 1:], rcond=None)[0]
+            scale = np.ones(len(active))
+            f_try = f - scale[:, None] * step
+            pending = np.arange(len(active))
+            while pending.size:                                           # backtrack: the objective must not increase
+                f_try[pending] = f[pending] - scale[pending, None] * step[pending]
+                phi = dev.bootstrap_log_denominator(reps[active[pending]], full(f_try[pending]), want_log_den=False)[1]
+                done = (phi <= phi0[pending] + 1e-12 * np.abs(phi0[pending])) | (scale[pending] < 1e-6)
+                pending = pending[~done]
+                scale[pending] *= 0.5
+            delta = np.max(np.abs(f_try - f), axis=1)
+            F[active] = f_try
+            active = active[~(delta <= rtol * np.maximum(1.0, np.max(np.abs(f_try), axis=1)))]
+            if not active.size:
+                break
+        else:
+            raise ParameterError('MBAR did not converge for bootstrap replicate %d' % reps[active[0]])
+        bad = np.flatnonzero(~np.all(np.isfinite(F), axis=1))
+        if bad.size:
+            raise ParameterError('MBAR produced non-finite free energies for bootstrap replicate %d' % reps[bad[0]])
+        out = full(F)
+        uns = np.flatnonzero(self.N_k == 0)
+        if uns.size:
+            out[:, uns] = dev.bootstrap_self_consistent(reps, out)[:, uns]
+        return out - out[:, :1]
+
+    def _check_uncertainty_method(self, uncertainty_method):
+        """True for 'bootstrap'.  ValueError for a method that is not one of UNCERTAINTY_METHODS, ParameterError (pymbar's sentence) for
+        'bootstrap' on an estimator built without replicates."""
+        if uncertainty_method not in self.UNCERTAINTY_METHODS:
+            raise ValueError("uncertainty_method must be None, 'svd' or 'bootstrap', not %r" % (uncertainty_method,))
+        if uncertainty_method == 'bootstrap' and self.n_bootstraps == 0:
+            raise ParameterError('Cannot request bootstrap sampling of free energy differences without any bootstraps.')
+        return uncertainty_method == 'bootstrap'
+
+    def _bootstrap_rows(self, u_ln=None, A_in=None, obs_state=None):
+        """(f_l [B][L], log_cA [B][I]) replicate by replicate: one weighted row pass at each replicate's f_k, as _augmented_gram takes
+        them for the full sample.  On the device: remd_mbar_bootstrap_rows, batch by batch."""
+        if self._dev is not None:
+            parts = [self._dev.bootstrap_rows(r, self.f_k_boots[r], u_ln, A_in, obs_state) for r in self._device_batches(np.arange(self.n_bootstraps))]
+            return np.concatenate([p[0] for p in parts], axis=0), np.concatenate([p[1] for p in parts], axis=0)
+        L = 0 if u_ln is None else len(u_ln)
+        I = 0 if A_in is None else len(A_in)
+        f_l, log_cA = np.zeros((self.n_bootstraps, L)), np.zeros((self.n_bootstraps, I))
+        sampled = self.N_k > 0
+        Nk = self.N_k[sampled, None].astype(np.float64)
+        for b in range(self.n_bootstraps):
+            c_n = self._bootstrap_counts(b)
+            n = np.flatnonzero(c_n)
+            c = c_n[n].astype(np.float64)
+            f = self.f_k_boots[b]
+            log_den = _logsumexp(f[sampled, None] - self.u_kn[np.ix_(sampled, n)], axis=0, b=Nk)
+            log_W = f[:, None] - self.u_kn[:, n] - log_den[None, :]      # [K][Nc]
+            if L:
+                f_l[b] = -_logsumexp(-u_ln[:, n] - log_den[None, :], axis=1, b=c[None, :])
+                log_W = np.concatenate([log_W, (f_l[b][:, None] - u_ln[:, n]) - log_den[None, :]], axis=0)
+            if I:
+                log_cA[b] = _logsumexp(log_W[np.asarray(obs_state, dtype=np.int64)] + np.log(A_in[:, n]), axis=1, b=c[None, :])
+        return f_l, log_cA
+
+    @staticmethod
+    def _bootstrap_error_of_differences(x_b):
+        """the population standard deviation over the replicates of x_j - x_i, [S][S], for x_b [B][S]"""
+        return np.std(x_b[:, None, :] - x_b[:, :, None], axis=0)
+
     @property
     def log_W_nk(self):
         if self._log_W is None and self._dev is not None:
@@ -491,12 +698,19 @@ class MBAR:
             return self._theta_of_gram(self._dev.gram(self.f_k), self.N_k)
         return self._theta_of(np.exp(self.log_W_nk), self.N_k)
 
-    def compute_entropy_and_enthalpy(self):
+    def _refuse_bootstrap(self, method, uncertainty_method):
+        if uncertainty_method not in self.UNCERTAINTY_METHODS:
+            raise ValueError("uncertainty_method must be None, 'svd' or 'bootstrap', not %r" % (uncertainty_method,))
+        if uncertainty_method == 'bootstrap':
+            raise ValueError("%s does not support uncertainty_method='bootstrap'" % method)
+
+    def compute_entropy_and_enthalpy(self, uncertainty_method=None):
         """Reduced enthalpy <u_i>_i and entropy s_i = <u_i>_i - f_i differences with their uncertainties
         (pymbar's compute_entropy_and_enthalpy; section IV of the MBAR paper: each <u_i>_i is the ratio of the
         normalisation constants of an extra, u-weighted state and of state i, so its error follows from the covariance
         of the augmented set of free energies).  Returns a dict with Delta_f, dDelta_f, Delta_u, dDelta_u, Delta_s,
-        dDelta_s; Delta_x[i, j] = x_j - x_i."""
+        dDelta_s; Delta_x[i, j] = x_j - x_i.  Asymptotic uncertainties only: 'bootstrap' is a ValueError."""
+        self._refuse_bootstrap('compute_entropy_and_enthalpy', uncertainty_method)
         K = self.K
         if self._dev is not None:
             shift = self.u_kn.min() - 1.0
@@ -535,10 +749,14 @@ class MBAR:
         Ds, dDs = diff_and_err(u_i - self.f_k, Lu - Lf)
         return dict(Delta_f=Df, dDelta_f=dDf, Delta_u=Du, dDelta_u=dDu, Delta_s=Ds, dDelta_s=dDs)
 
-    def compute_free_energy_differences(self):
-        """(Delta_f_ij, dDelta_f_ij) with Delta_f_ij[i, j] = f_j - f_i (pymbar's convention)."""
+    def compute_free_energy_differences(self, uncertainty_method=None):
+        """(Delta_f_ij, dDelta_f_ij) with Delta_f_ij[i, j] = f_j - f_i (pymbar's convention).  ``uncertainty_method``: None or 'svd',
+        the asymptotic covariance; 'bootstrap', the standard deviation of f_j - f_i over the replicates."""
+        bootstrap = self._check_uncertainty_method(uncertainty_method)
         f = self.f_k
         Delta = f[None, :] - f[:, None]
+        if bootstrap:
+            return Delta, self._bootstrap_error_of_differences(self.f_k_boots)
         Theta = self._theta()
         d2 = np.diag(Theta)[:, None] + np.diag(Theta)[None, :] - 2.0 * Theta
         d2 = np.where(np.abs(d2) < 1e-14, 0.0, d2)
@@ -613,25 +831,31 @@ class MBAR:
         J[constant] = 0.0
         return J @ Theta @ J.T
 
-    def compute_perturbed_free_energies(self, u_ln):
+    def compute_perturbed_free_energies(self, u_ln, uncertainty_method=None):
         """Free energy differences between L states that were not simulated, from the stored samples: ``u_ln[l, n]`` is the reduced
         potential of sample n in new state l (+inf: the sample has weight 0 there).  f_l = -ln sum_n exp(-u_ln - log_den_n); the
-        uncertainties come from Theta over the K + L columns, the new ones with N_k = 0.  Returns a dict with Delta_f [L][L] and
+        uncertainties come from Theta over the K + L columns, the new ones with N_k = 0, or with ``uncertainty_method='bootstrap'``
+        from the f_l of every replicate (one weighted row pass at the replicate's f_k).  Returns a dict with Delta_f [L][L] and
         dDelta_f [L][L]; Delta_f[i, j] = f_j - f_i.  ParameterError for a -inf or NaN entry and for a state whose weights all vanish."""
+        bootstrap = self._check_uncertainty_method(uncertainty_method)
         u_ln = self._check_u_ln(u_ln)
         f_l, _, G = self._augmented_gram(u_ln=u_ln)
+        if bootstrap:
+            return dict(Delta_f=f_l[None, :] - f_l[:, None], dDelta_f=self._bootstrap_error_of_differences(self._bootstrap_rows(u_ln=u_ln)[0]))
         K = self.K
         Theta = self._theta_of_gram(G, np.concatenate([self.N_k, np.zeros(len(f_l), dtype=np.int64)]))
         return dict(Delta_f=f_l[None, :] - f_l[:, None], dDelta_f=self._error_of_differences(Theta[K:, K:]))
 
-    def compute_expectations(self, A_n, u_kn=None, output='averages', state_dependent=False):
+    def compute_expectations(self, A_n, u_kn=None, output='averages', state_dependent=False, uncertainty_method=None):
         """<A> at every state with its uncertainty.  ``A_n`` is [N], or [S][N] with ``state_dependent=True`` (row s is the observable
         of state s).  ``u_kn=None``: the S = K states of the estimator; otherwise the S = L perturbed states ``u_kn`` [L][N].
         ``output='averages'`` returns a dict with mu [S] and sigma [S]; ``'differences'`` one with mu [S][S] (mu_j - mu_i) and the
         sigma [S][S] of those differences.  The observable is shifted by min(A) - 1 to be positive for the logarithm, as in
-        compute_entropy_and_enthalpy; a constant observable has sigma = 0."""
+        compute_entropy_and_enthalpy; a constant observable has sigma = 0.  ``uncertainty_method='bootstrap'``: sigma is the standard
+        deviation over the replicates of mu (or of mu_j - mu_i), each replicate's mu from one weighted row pass at its own f_k."""
         if output not in ('averages', 'differences'):
             raise ParameterError("output must be 'averages' or 'differences', not %r" % (output,))
+        bootstrap = self._check_uncertainty_method(uncertainty_method)
         u_ln = None if u_kn is None else self._check_u_ln(u_kn, 'u_kn')
         K = self.K
         S = K if u_ln is None else u_ln.shape[0]
@@ -645,15 +869,22 @@ class MBAR:
         cA = np.exp(log_cA)
         constant = A.max(axis=1) == A.min(axis=1)
         mu = np.where(constant, A[:, 0], cA + shift)                          # <c> = c, not c (1 + the rounding of sum_n W)
+        if bootstrap:
+            log_cA_b = self._bootstrap_rows(u_ln, np.ascontiguousarray(A - shift), obs_state)[1]
+            mu_b = np.where(constant[None, :], A[None, :, 0], np.exp(log_cA_b) + shift)             # [B][S]
+            if output == 'averages':
+                return dict(mu=mu, sigma=np.std(mu_b, axis=0))
+            return dict(mu=mu[None, :] - mu[:, None], sigma=self._bootstrap_error_of_differences(mu_b))
         cov = self._observable_covariance(G, obs_state, cA, constant)
         if output == 'averages':
             return dict(mu=mu, sigma=self._sqrt_of_variance(np.diag(cov)))
         return dict(mu=mu[None, :] - mu[:, None], sigma=self._error_of_differences(cov))
 
-    def compute_multiple_expectations(self, A_in, u_n, compute_covariance=False):
+    def compute_multiple_expectations(self, A_in, u_n, compute_covariance=False, uncertainty_method=None):
         """<A_i> of I observables ``A_in`` [I][N] at the one state whose reduced potentials of the stored samples are ``u_n`` [N].
         Returns a dict with mu [I] and sigma [I], and with ``compute_covariance`` also covariances [I][I].  Each observable is
-        shifted by its own minimum - 1."""
+        shifted by its own minimum - 1.  Asymptotic uncertainties only: 'bootstrap' is a ValueError."""
+        self._refuse_bootstrap('compute_multiple_expectations', uncertainty_method)
         u_ln = self._check_u_ln(np.reshape(np.asarray(u_n, dtype=np.float64), (1, -1)), 'u_n')
         A = np.asarray(A_in, dtype=np.float64)
         if A.ndim != 2 or A.shape[0] < 1:
@@ -723,6 +954,12 @@ class MultiStateSamplerAnalyzer:
         # inefficiency): 'numpy' (the loops below) or 'device' (csrc/energy_store.hip)
         if self._kwargs.get('assembly_solver', 'numpy') not in ('numpy', 'device'):
             raise ValueError("analysis_kwargs['assembly_solver'] must be 'numpy' or 'device', not %r" % (self._kwargs['assembly_solver'],))
+        # bootstrap uncertainties of MBAR: the number of replicates (0: none), the key of their draws, and the uncertainty the free
+        # energies are reported with (None or 'svd': asymptotic; 'bootstrap')
+        self._check_bootstrap_option('n_bootstraps', self._kwargs.get('n_bootstraps', 0))
+        self._check_bootstrap_option('bootstrap_seed', self._kwargs.get('bootstrap_seed', 0))
+        self._check_bootstrap_option('uncertainty_method', self._kwargs.get('uncertainty_method'))
+        self._sample_states = None              # [N]: the row of the matrix handed to MBAR each of its columns was drawn from
         self._energy_store = None               # the DeviceEnergyStore of assembly_solver = 'device', made on first use
         self._equilibration_data = None
         self._mbar = None
@@ -755,6 +992,33 @@ class MultiStateSamplerAnalyzer:
                 self._mbar = None
                 self._unbiased = None
         return property(fget, fset)
+
+    @staticmethod
+    def _check_bootstrap_option(key, value):
+        if key == 'uncertainty_method':
+            ok = value in MBAR.UNCERTAINTY_METHODS
+        else:
+            ok = isinstance(value, (int, np.integer)) and not isinstance(value, bool) and 0 <= value < (2 ** 31 if key == 'n_bootstraps' else 2 ** 64)
+        if not ok:
+            raise ValueError("analysis_kwargs[%r] must be %s, not %r" % (key, {
+                'n_bootstraps': 'a non-negative integer', 'bootstrap_seed': 'an integer in 0 ... 2^64 - 1',
+                'uncertainty_method': "None, 'svd' or 'bootstrap'"}[key], value))
+
+    def _bootstrap_option(key, default, forgets_mbar):      # a change of the replicates forgets MBAR alone; of the method, nothing
+        def fget(self):
+            return self._kwargs.get(key, default)
+
+        def fset(self, value):
+            self._check_bootstrap_option(key, value)
+            if forgets_mbar and value != self._kwargs.get(key, default):
+                self._mbar = None
+            self._kwargs[key] = value
+        return property(fget, fset)
+
+    n_bootstraps = _bootstrap_option('n_bootstraps', 0, True)
+    bootstrap_seed = _bootstrap_option('bootstrap_seed', 0, True)
+    uncertainty_method = _bootstrap_option('uncertainty_method', None, False)
+    del _bootstrap_option
 
     unbias_restraint = _restraint_option('unbias_restraint')
     restraint_energy_cutoff = _restraint_option('restraint_energy_cutoff')            # kT, 'auto' or None
@@ -1105,6 +1369,8 @@ class MultiStateSamplerAnalyzer:
         self._unbiased = None
         selection = self._decorrelated_selection()
         u_ln, N_l = self._compute_mbar_decorrelated_energies(selection)
+        # the column of frame [replica][iteration] was drawn from the sampled state the replica was in, past the unsampled rows in front
+        self._sample_states = selection[2].reshape(-1) + int((len(N_l) - selection[0].shape[1]) / 2)
         initial_f_k = self._kwargs.get('initial_f_k')
         restraint_data = None
         if self.unbias_restraint:
@@ -1132,6 +1398,7 @@ class MultiStateSamplerAnalyzer:
         np.subtract.at(N_l, state_indices_ln[drop] + first_sampled_state_idx, 1)
         keep = np.flatnonzero(~drop)
         u_ln, energies_kJ = u_ln[:, keep], energies_kJ[keep]
+        self._sample_states = self._sample_states[keep] + 1                  # (the kept columns, past the end row added in front)
         u_ln_new = np.zeros((u_ln.shape[0] + 2, u_ln.shape[1]), u_ln.dtype)
         N_l_new = np.zeros(len(N_l) + 2, N_l.dtype)
         # each end row loses the restraint in the kT of ITS OWN end state.  The reference divides both by the first state's kT
@@ -1152,6 +1419,8 @@ class MultiStateSamplerAnalyzer:
         if self._mbar is None:
             u_ln, N_l = self._compute_mbar_unbiased_energies()
             extra = {k: self._kwargs[k] for k in ('solver', 'device', 'lib_path') if k in self._kwargs}
+            if self.n_bootstraps:
+                extra.update(n_bootstraps=int(self.n_bootstraps), bootstrap_seed=int(self.bootstrap_seed), sample_states=self._sample_states)
             self._mbar = MBAR(u_ln, N_l, initial_f_k=self._unbiased[2], **extra)
         return self._mbar
 
@@ -1204,7 +1473,9 @@ class MultiStateSamplerAnalyzer:
 
     def get_free_energy(self):
         """(Delta_f_ij, dDelta_f_ij) in kT between all (unsampled + sampled) states (:1958-2003)."""
-        return self.mbar.compute_free_energy_differences()
+        if self.uncertainty_method is None:
+            return self.mbar.compute_free_energy_differences()
+        return self.mbar.compute_free_energy_differences(uncertainty_method=self.uncertainty_method)
 
 
 
