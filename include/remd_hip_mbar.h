@@ -116,6 +116,41 @@ int  remd_mbar_bootstrap_newton_parts(remd_mbar m, int nr, const int32_t* reps, 
 int  remd_mbar_bootstrap_rows(remd_mbar m, int nr, const int32_t* reps, const double* f_b, int L, const double* u_ln, int I, const double* A_in,
                               const int32_t* obs_state, double* f_l, double* log_cA);
 
+/* ---- free energy surfaces over binned samples -----------------------------------------------------------------------------------
+ * The histogram estimator of a potential of mean force (pymbar's computePMF / FES): u_n[N] is the reduced potential of every stored
+ * sample at the state the surface is wanted at (+inf: the sample has weight 0), bin_n[N] its bin, -1 ... nbins - 1 (-1: in no bin).
+ * With  log w_n = -u_n - log_den_n  the free energy of bin i is
+ *
+ *   f_i = -ln sum_{n: bin_n = i} exp(log w_n)                   (+inf for a bin without a sample of non-zero weight: it is empty)
+ *
+ * and its column of the weight matrix  W_n,i = exp(f_i + log w_n)  on the samples of the bin, 0 elsewhere (all 0 for an empty bin).
+ * The bins are disjoint: the bin-bin block of the Gram matrix is diagonal, and neither it nor the state-bin block is formed over N.
+ *
+ * The host groups the samples by bin in ascending sample order (a stable counting sort) and cuts every bin's list into chunks of
+ * REMD_MBAR_PMF_CHUNK samples; a workgroup reduces one chunk, reading its samples of u_kn through the list, and the chunks of a bin
+ * are merged in chunk order.  No floating-point atomic: a result depends on the inputs alone, and a replicate's on no other replicate.
+ * Refused, with a message: nbins outside 1 ... REMD_MBAR_PMF_MAX_BINS, a bin_n outside -1 ... nbins - 1, a NaN or -inf in u_n, a
+ * non-finite f_k or f_b, N above 2^31 - 1, and for the replicates what remd_mbar_bootstrap_rows refuses.                            */
+#define REMD_MBAR_PMF_MAX_BINS 65536
+#define REMD_MBAR_PMF_CHUNK 256
+
+/* the samples of one bin that one workgroup of the passes below reduces (REMD_MBAR_PMF_CHUNK), for tests and tools               */
+int  remd_mbar_pmf_chunk(remd_mbar m, int64_t* chunk);
+/* f_i[nbins] at f_k, and the sums the covariance needs:
+     cross[K][nbins]   sum_{n in i} W_nk W_n,i                  diag[nbins]   sum_{n in i} W_n,i^2           (0 for an empty bin)
+   all_parts (or NULL) [2 + K + nbins]: the column z of the normalised weight over all binned samples, W_n,z = exp(f_z + log w_n)
+   with f_z = -ln sum_i exp(-f_i), from the same per-bin sums in bin order:
+     [0] f_z (+inf if every bin is empty; the rest is then 0)    [1] sum_n W_n,z^2
+     [2 + k] sum_n W_nk W_n,z                                    [2 + K + i] sum_n W_n,i W_n,z
+   The K x K block of the Gram matrix is remd_mbar_gram's.                                                                        */
+int  remd_mbar_pmf(remd_mbar m, const double* f_k, const double* u_n, const int32_t* bin_n, int nbins,
+                   double* f_i, double* cross, double* diag, double* all_parts);
+/* f_i[nr][nbins] = -ln sum_{n in i} c_n exp(-u_n - log_den_n) of nr drawn replicates, each with its multiplicities and its log_den at
+   its f_b[nr][K] (+inf where the replicate keeps no sample of non-zero weight in the bin).  The replicate is a grid dimension; u_n and
+   bin_n are uploaded once for the call.  Batching as in remd_mbar_bootstrap_rows.                                                  */
+int  remd_mbar_bootstrap_pmf(remd_mbar m, int nr, const int32_t* reps, const double* f_b, const double* u_n, const int32_t* bin_n, int nbins,
+                             double* f_i);
+
 #ifdef __cplusplus
 }
 #endif

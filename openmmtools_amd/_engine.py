@@ -133,6 +133,9 @@ MBAR_AUGMENTED_EXPORTS = ['remd_mbar_augmented_gram']
 MBAR_BOOTSTRAP_EXPORTS = ['remd_mbar_bootstrap_max_batch', 'remd_mbar_bootstrap_draw', 'remd_mbar_bootstrap_counts',
                           'remd_mbar_bootstrap_log_denominator', 'remd_mbar_bootstrap_self_consistent', 'remd_mbar_bootstrap_newton_parts',
                           'remd_mbar_bootstrap_rows']
+# the free energy surfaces over binned samples of the same header (a bin index per sample), bound the same way
+MBAR_PMF_EXPORTS = ['remd_mbar_pmf_chunk', 'remd_mbar_pmf', 'remd_mbar_bootstrap_pmf']
+MBAR_PMF_MAX_BINS = 65536
 # the GPU-only extension of include/remd_hip_timeseries.h (statistical inefficiencies of the suffixes of a timeseries), bound the same way
 TIMESERIES_EXPORTS = ['remd_timeseries_create', 'remd_timeseries_destroy', 'remd_timeseries_inefficiency', 'remd_timeseries_chunks',
                       'remd_timeseries_last_ms']
@@ -324,6 +327,12 @@ def load_library(path=None):
         lib.remd_mbar_bootstrap_rows.argtypes = [vp, C.c_int, c_int32_p, c_double_p, C.c_int, c_double_p, C.c_int, c_double_p, c_int32_p,
                                                  c_double_p, c_double_p]
         for name in MBAR_BOOTSTRAP_EXPORTS:
+            getattr(lib, name).restype = C.c_int
+    if hasattr(lib, 'remd_mbar_pmf'):
+        lib.remd_mbar_pmf_chunk.argtypes = [vp, c_int64_p]
+        lib.remd_mbar_pmf.argtypes = [vp, c_double_p, c_double_p, c_int32_p, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p]
+        lib.remd_mbar_bootstrap_pmf.argtypes = [vp, C.c_int, c_int32_p, c_double_p, c_double_p, c_int32_p, C.c_int, c_double_p]
+        for name in MBAR_PMF_EXPORTS:
             getattr(lib, name).restype = C.c_int
     if hasattr(lib, 'remd_timeseries_create'):            # include/remd_hip_timeseries.h (GPU-only, like the restraints)
         lib.remd_timeseries_create.argtypes = [C.c_int, C.c_int64, c_double_p, C.POINTER(vp)]
@@ -658,6 +667,48 @@ class DeviceMBAR(_DeviceObject):
         self._check(self.lib.remd_mbar_bootstrap_rows(self.h, reps.size, _ip(reps), _dp(f), L, _dp(u) if L else None, I, _dp(A) if I else None,
                                                       _ip(obs), _dp(f_l) if L else None, _dp(log_cA) if I else None), 'remd_mbar_bootstrap_rows')
         return f_l, log_cA
+
+    # ---- free energy surfaces over binned samples (remd_mbar_pmf*): NotImplementedError where the library lacks them ------------------
+    def _require_pmf(self):
+        _require_exports(self.lib, MBAR_PMF_EXPORTS, 'passes over binned samples (include/remd_hip_mbar.h declares them)')
+
+    def _binned(self, u_n, bin_n):
+        u = np.ascontiguousarray(u_n, dtype=np.float64)
+        bins = np.ascontiguousarray(bin_n, dtype=np.int32)
+        if u.shape != (self.N,) or bins.shape != (self.N,):
+            raise ValueError('u_n and bin_n must be [N] with N = %d' % self.N)
+        return u, bins
+
+    def pmf_chunk(self):
+        """The samples of one bin that one workgroup of the passes over binned samples reduces."""
+        self._require_pmf()
+        c = C.c_int64()
+        self._check(self.lib.remd_mbar_pmf_chunk(self.h, C.byref(c)), 'remd_mbar_pmf_chunk')
+        return c.value
+
+    def pmf(self, f_k, u_n, bin_n, nbins, want_all=False):
+        """(f_i [nbins], cross [K][nbins], diag [nbins], all_parts [2 + K + nbins] or None) at f_k: the free energies of the bins
+        ``bin_n`` [N] (-1: in no bin) of the state ``u_n`` [N] (+inf for an empty bin), sum_{n in i} W_nk W_n,i, sum_{n in i} W_n,i^2 and
+        the parts of the column over all binned samples (its f, its self-product, its K and its nbins cross terms)."""
+        self._require_pmf()
+        f = self._f(f_k)
+        u, bins = self._binned(u_n, bin_n)
+        nb = max(int(nbins), 0)
+        f_i, cross, diag = np.empty(nb), np.empty((self.K, nb)), np.empty(nb)
+        parts = np.empty(2 + self.K + nb) if want_all else None
+        self._check(self.lib.remd_mbar_pmf(self.h, _dp(f), _dp(u), _ip(bins), int(nbins), _dp(f_i), _dp(cross), _dp(diag), _dp(parts)), 'remd_mbar_pmf')
+        return f_i, cross, diag, parts
+
+    def bootstrap_pmf(self, reps, f_b, u_n, bin_n, nbins):
+        """f_i [nb][nbins] of the drawn replicates ``reps``, each with its multiplicities at its row of ``f_b`` [nb][K]."""
+        self._require_bootstrap()
+        self._require_pmf()
+        reps, f = self._batch(reps, f_b)
+        u, bins = self._binned(u_n, bin_n)
+        out = np.empty((reps.size, max(int(nbins), 0)))
+        self._check(self.lib.remd_mbar_bootstrap_pmf(self.h, reps.size, _ip(reps), _dp(f), _dp(u), _ip(bins), int(nbins), _dp(out)),
+                    'remd_mbar_bootstrap_pmf')
+        return out
 
     def log_weights(self, f_k):
         """log_W_nk [N][K] at f_k."""

@@ -300,7 +300,7 @@ static int64_t mbar_gram_chunk(int64_t N, int C)
 }
 
 // every pointer of a call is checked before anything is copied; `out` and `out2` are the outputs that may not be NULL
-static int mbar_begin(remd_mbar m, const char* who, const double* f_k, const void* out = (const void*)1, const void* out2 = (const void*)1)
+int mbar_begin(remd_mbar m, const char* who, const double* f_k, const void* out, const void* out2)
 {
     if (!m) return remd_fail(nullptr, -1, std::string(who) + ": the problem is NULL");
     if (!f_k) return remd_fail(nullptr, -1, std::string(who) + ": f_k is NULL");
@@ -315,7 +315,7 @@ static int mbar_begin(remd_mbar m, const char* who, const double* f_k, const voi
     return m->tm.begin();
 }
 
-static int mbar_end(remd_mbar m)
+int mbar_end(remd_mbar m)
 {
     REMD_TRY(m->tm.end());
     m->timed = true;
@@ -323,7 +323,7 @@ static int mbar_end(remd_mbar m)
 }
 
 // log_den on the device, its sum in scalar[0]
-static int mbar_column_pass(remd_mbar m)
+int mbar_column_pass(remd_mbar m)
 {
     const int64_t blocks = (m->N + MBAR_BLOCK - 1) / MBAR_BLOCK;
     hipLaunchKernelGGL(mbar_logden_kernel, dim3((unsigned)blocks), dim3(MBAR_BLOCK), 0, m->tm.stream, m->u.get(), m->fs.get(), m->nk.get(),

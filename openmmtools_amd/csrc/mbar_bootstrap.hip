@@ -307,7 +307,7 @@ static int64_t boot_gram_chunk(int64_t N)
 }
 
 // checks a batched call, uploads reps[nr] and f_b[nr][K], sizes log_den[nr][N] and starts the clock
-static int boot_begin(remd_mbar m, const std::string& who, int nr, const int32_t* reps, const double* f_b)
+int boot_begin(remd_mbar m, const std::string& who, int nr, const int32_t* reps, const double* f_b)
 {
     if (!m) return remd_fail(nullptr, -1, who + ": the problem is NULL");
     if (nr < 1) return remd_fail(nullptr, -1, who + ": nb = " + std::to_string(nr) + " replicates; at least 1 is needed");
@@ -335,7 +335,7 @@ static int boot_begin(remd_mbar m, const std::string& who, int nr, const int32_t
     return m->tm.begin();
 }
 
-static int boot_end(remd_mbar m)
+int boot_end(remd_mbar m)
 {
     REMD_TRY(m->tm.end());
     m->timed = true;
@@ -343,7 +343,7 @@ static int boot_end(remd_mbar m)
 }
 
 // log_den[nr][N] on the device, sum_n c_n log_den_n per replicate in phi_sum[nr]
-static int boot_column_pass(remd_mbar m, int nr)
+int boot_column_pass(remd_mbar m, int nr)
 {
     mbar_bootstrap_state& b = m->boot;
     const int64_t blocks = (m->N + MBAR_BLOCK - 1) / MBAR_BLOCK;

@@ -54,3 +54,14 @@ struct remd_mbar_ctx {
     mbar_bootstrap_state boot;
     device_timer tm;
 };
+
+// How a call of either file starts and ends, and its column pass; mbar_pmf.hip's calls go through the same ones.
+// mbar.hip: every pointer is checked, f_k uploaded and the clock started; log_den on the device with its sum in scalar[0]; the clock
+// stopped.  mbar_bootstrap.hip: a batched call is checked, reps[nr] and f_b[nr][K] uploaded, log_den[nr][N] sized and the clock
+// started; log_den[nr][N] with sum_n c_n log_den_n per replicate in phi_sum[nr]; the clock stopped.
+int mbar_begin(remd_mbar m, const char* who, const double* f_k, const void* out = (const void*)1, const void* out2 = (const void*)1);
+int mbar_column_pass(remd_mbar m);
+int mbar_end(remd_mbar m);
+int boot_begin(remd_mbar m, const std::string& who, int nr, const int32_t* reps, const double* f_b);
+int boot_column_pass(remd_mbar m, int nr);
+int boot_end(remd_mbar m);

@@ -304,6 +304,36 @@ def _logsumexp(a, axis=None, b=None):
 class ParameterError(Exception):
     """Raised when the estimator cannot be computed from the data it was given (pymbar.utils.ParameterError)."""
 
+def bin_samples(values, edges):
+    """(bin_n [N], nbins): the flat bin index of every sample for ``MBAR.compute_pmf``.  ``values`` is [N], or [N][D] with D <= 3
+    coordinates per sample; ``edges`` one ascending array of bin edges per dimension (for [N] values, the array itself will do).
+    Intervals are half-open, [e_j, e_j+1), and the last is closed at its right edge, as numpy.histogram has them.  The first
+    dimension varies fastest in the flat index; nbins is the product of the intervals per dimension.  A value outside the range of
+    any dimension, or a NaN, gives -1: the sample lies in no bin."""
+    v = np.asarray(values, dtype=np.float64)
+    if v.ndim == 1:
+        if len(edges) > 0 and np.ndim(edges[0]) == 0:
+            edges = [edges]
+        v = v[:, None]
+    if v.ndim != 2 or not 1 <= v.shape[1] <= 3:
+        raise ValueError('values must be [N] or [N][D] with D <= 3, not an array of shape %r' % (np.shape(values),))
+    if len(edges) != v.shape[1]:
+        raise ValueError('edges must hold one array per dimension: %d, not %d' % (v.shape[1], len(edges)))
+    flat = np.zeros(v.shape[0], dtype=np.int64)
+    inside = np.ones(v.shape[0], dtype=bool)
+    stride = 1
+    for d, e in enumerate(edges):
+        e = np.asarray(e, dtype=np.float64)
+        if e.ndim != 1 or e.size < 2 or not np.all(np.diff(e) > 0.0):
+            raise ValueError('edges[%d] must be an ascending array of at least two bin edges' % d)
+        x = v[:, d]
+        ok = (x >= e[0]) & (x <= e[-1])                                   # (a NaN is outside)
+        j = np.minimum(np.searchsorted(e, np.where(ok, x, e[0]), side='right') - 1, e.size - 2)
+        flat += stride * j
+        inside &= ok
+        stride *= e.size - 1
+    return np.where(inside, flat, -1), int(stride)
+
 
 class MBAR:
     """Multistate Bennett acceptance ratio estimator.
@@ -333,9 +363,16 @@ class MBAR:
     ``uncertainty_method='bootstrap'``: the population standard deviation (ddof = 0) over the replicates in place of eq. 8.
     With ``solver='device'`` the multiplicities are drawn on the GPU and the replicates are solved there in batches, every pass
     one call for the whole batch; the K x K algebra stays on the host, batched.
+
+    ``compute_pmf`` is the histogram estimator of a free energy surface (pymbar 3's computePMF): a bin index per sample, never a
+    row per bin.  Its bin-bin block of the Gram matrix is diagonal and its state-bin block one pass of cost N x K; with
+    ``solver='device'`` both come from remd_mbar_pmf, the bootstrap's weighted bin sums from remd_mbar_bootstrap_pmf.
     """
 
     UNCERTAINTY_METHODS = (None, 'svd', 'bootstrap')
+    PMF_UNCERTAINTIES = ('from-lowest', 'from-specified', 'from-normalization', 'all-differences')
+    PMF_MAX_BINS = 65536                         # REMD_MBAR_PMF_MAX_BINS of include/remd_hip_mbar.h, for both solvers
+    PMF_MAX_COLUMNS = 4096                       # K + non-empty bins + 1 at most where Theta is wanted: it is a host SVD
 
     def __init__(self, u_kn, N_k, initial_f_k=None, relative_tolerance=1.0e-12, maximum_iterations=10000, solver='numpy',
                  device=0, lib_path=None, n_bootstraps=0, bootstrap_seed=0, sample_states=None):
@@ -846,6 +883,168 @@ class MBAR:
         Theta = self._theta_of_gram(G, np.concatenate([self.N_k, np.zeros(len(f_l), dtype=np.int64)]))
         return dict(Delta_f=f_l[None, :] - f_l[:, None], dDelta_f=self._error_of_differences(Theta[K:, K:]))
 
+    # ---- free energy surfaces over binned samples ---------------------------------------------------------------------------------
+    @staticmethod
+    def _bin_lists(bin_n, nbins):
+        """(order, present, first): the binned samples by bin, ascending in each bin; the bins that hold a sample; where the list of
+        each of those starts in ``order``"""
+        order = np.flatnonzero(bin_n >= 0)
+        order = order[np.argsort(bin_n[order], kind='stable')]
+        present, first = np.unique(bin_n[order], return_index=True)
+        return order, present, first
+
+    @staticmethod
+    def _bin_free_energies(term, weight, lists, nbins):
+        """f_i [nbins] = -ln sum_{n in i} weight_n exp(term_n), every bin shifted by its own maximum over weight_n > 0; +inf for a bin
+        without a sample of non-zero weight.  ``term`` and ``weight`` are [N]."""
+        order, present, first = lists
+        f_i = np.full(nbins, np.inf)
+        if order.size == 0:
+            return f_i
+        w = weight[order]
+        t = np.where(w > 0.0, term[order], -np.inf)
+        m = np.maximum.reduceat(t, first)
+        m = np.where(np.isfinite(m), m, 0.0)
+        size = np.diff(np.append(first, order.size))
+        with np.errstate(divide='ignore'):
+            f_i[present] = -(np.log(np.add.reduceat(w * np.exp(t - np.repeat(m, size)), first)) + m)
+        return f_i
+
+    def _pmf_parts(self, u_n, bin_n, nbins, want_all):
+        """(f_i [nbins], cross [K][nbins], diag [nbins], parts of the column z or None) at the solved f_k: what remd_mbar_pmf returns,
+        and on the device its call."""
+        if self._dev is not None:
+            return self._dev.pmf(self.f_k, u_n, bin_n, nbins, want_all=want_all)
+        K = self.K
+        lists = order, present, first = self._bin_lists(bin_n, nbins)
+        log_w = -u_n - self._log_denominator(self.f_k)
+        f_i = self._bin_free_energies(log_w, np.ones(self.N), lists, nbins)
+        cross, diag = np.zeros((K, nbins)), np.zeros(nbins)
+        if order.size:
+            f_of = f_i[bin_n[order]]
+            finite = np.isfinite(f_of)
+            W_i = np.zeros(order.size)
+            W_i[finite] = np.exp(f_of[finite] + log_w[order][finite])     # W_n,i on the samples of the bins, 0 for an empty bin
+            diag[present] = np.add.reduceat(W_i * W_i, first)
+            cross[:, present] = np.add.reduceat(np.exp(self.log_W_nk[order]) * W_i[:, None], first, axis=0).T
+        parts = None
+        if want_all:                             # W_n,z = exp(f_z - f_i) W_n,i on the samples of bin i: the same per-bin sums
+            parts = np.zeros(2 + K + nbins)
+            full = np.isfinite(f_i)
+            parts[0] = np.inf
+            if full.any():
+                f_z = parts[0] = -_logsumexp(-f_i[full])
+                e = np.exp(f_z - f_i[full])
+                parts[1] = np.sum(e * e * diag[full])
+                parts[2:2 + K] = cross[:, full] @ e
+                parts[2 + K:][full] = e * diag[full]
+        return f_i, cross, diag, parts
+
+    def _bootstrap_pmf(self, u_n, bin_n, nbins):
+        """f_i [B][nbins] replicate by replicate: the weighted bin sums with the replicate's multiplicities and its log_den at
+        f_k_boots[b].  On the device: remd_mbar_bootstrap_pmf, batch by batch."""
+        if self._dev is not None:
+            return np.concatenate([self._dev.bootstrap_pmf(r, self.f_k_boots[r], u_n, bin_n, nbins)
+                                   for r in self._device_batches(np.arange(self.n_bootstraps))], axis=0)
+        lists = self._bin_lists(bin_n, nbins)
+        out = np.empty((self.n_bootstraps, nbins))
+        for b in range(self.n_bootstraps):
+            c_n = self._bootstrap_counts(b).astype(np.float64)
+            out[b] = self._bin_free_energies(-u_n - self._log_denominator(self.f_k_boots[b]), c_n, lists, nbins)
+        return out
+
+    def compute_pmf(self, u_n, bin_n, nbins, uncertainties='from-lowest', pmf_reference=None, uncertainty_method=None):
+        """The free energy surface over binned samples (pymbar 3's computePMF, histogram form): ``u_n[n]`` is the reduced potential
+        of sample n at the state the surface is wanted at (+inf: the sample has weight 0), ``bin_n[n]`` its bin in 0 ... nbins - 1,
+        or -1 for a sample in no bin (``bin_samples`` makes them from coordinates and edges).  f_i = -ln sum_{n in i}
+        exp(-u_n - log_den_n); a bin without a sample of non-zero weight is empty: f_i = +inf, df_i = NaN, no part in the covariance.
+
+        ``uncertainties``: 'from-lowest' shifts f_i by its lowest entry f_j and gives the error of f_i - f_j; 'from-specified' the same
+        with j = ``pmf_reference`` in the errors; 'from-normalization' shifts to sum_i exp(-f_i) = 1 and gives the error against the
+        normalised weight over all binned samples; 'all-differences' shifts as 'from-lowest' and gives the [nbins][nbins] matrix of the
+        errors of f_i - f_j (NaN in the rows and columns of empty bins).  The errors come from Theta (eq. 8) over the K states and one
+        column per non-empty bin (N = 0 for those), or with ``uncertainty_method='bootstrap'`` as the population standard deviation
+        over the replicates in which both bins are non-empty (NaN with fewer than two such replicates).
+
+        Returns a dict with f_i [nbins], df_i [nbins] (or [nbins][nbins]) and n_i [nbins], the samples per bin.  ParameterError: a NaN
+        or -inf in u_n, every bin empty.  ValueError: bin_n, nbins, uncertainties, pmf_reference; K + non-empty bins + 1 above
+        PMF_MAX_COLUMNS for the asymptotic errors."""
+        bootstrap = self._check_uncertainty_method(uncertainty_method)
+        if uncertainties not in self.PMF_UNCERTAINTIES:
+            raise ValueError('uncertainties must be one of %s, not %r' % (', '.join(repr(x) for x in self.PMF_UNCERTAINTIES), uncertainties))
+        if isinstance(nbins, bool) or not isinstance(nbins, (int, np.integer)) or not 1 <= nbins <= self.PMF_MAX_BINS:
+            raise ValueError('nbins must be an integer in 1 ... %d, not %r' % (self.PMF_MAX_BINS, nbins))
+        nbins = int(nbins)
+        bins = np.asarray(bin_n)
+        if bins.shape != (self.N,) or bins.dtype.kind not in 'iu' or np.any(bins < -1) or np.any(bins >= nbins):
+            raise ValueError('bin_n must hold one integer in -1 ... nbins - 1 = %d for each of the %d samples' % (nbins - 1, self.N))
+        bins = bins.astype(np.int64)
+        u = np.array(u_n, dtype=np.float64)
+        if u.shape != (self.N,):
+            raise ParameterError('u_n must be [N] with N = %d samples' % self.N)
+        if np.any(np.isnan(u)) or np.any(np.isneginf(u)):
+            raise ParameterError('u_n holds a NaN or -inf: only +inf (a sample of weight 0) is allowed')
+        f_i, cross, diag, parts = self._pmf_parts(u, bins, nbins, uncertainties == 'from-normalization')
+        full = np.flatnonzero(np.isfinite(f_i))
+        if full.size == 0:
+            raise ParameterError('every bin is empty: no binned sample has a non-zero weight')
+        lowest = int(np.argmin(f_i))
+        reference = lowest
+        if uncertainties == 'from-specified':
+            if isinstance(pmf_reference, bool) or not isinstance(pmf_reference, (int, np.integer)) or not 0 <= pmf_reference < nbins \
+                    or not np.isfinite(f_i[pmf_reference]):
+                raise ValueError('pmf_reference must be a non-empty bin in 0 ... %d, not %r' % (nbins - 1, pmf_reference))
+            reference = int(pmf_reference)
+        n_i = np.bincount(bins[bins >= 0], minlength=nbins)
+        normalised = uncertainties == 'from-normalization'
+        f_z = -_logsumexp(-f_i[full])
+        out_f = f_i - (f_z if normalised else f_i[lowest])
+        if bootstrap:
+            f_b = self._bootstrap_pmf(u, bins, nbins)                         # [B][nbins], +inf where a replicate leaves a bin empty
+            with np.errstate(invalid='ignore'):
+                if normalised:
+                    ref_b = np.array([-_logsumexp(-row[np.isfinite(row)]) if np.isfinite(row).any() else np.inf for row in f_b])
+                    d = f_b - ref_b[:, None]
+                elif uncertainties == 'all-differences':
+                    d = f_b[:, :, None] - f_b[:, None, :]
+                else:
+                    d = f_b - f_b[:, reference:reference + 1]
+            return dict(f_i=out_f, df_i=self._std_of_finite(d), n_i=n_i)
+        K, ne = self.K, full.size
+        C = K + ne + (1 if normalised else 0)
+        if K + ne + 1 > self.PMF_MAX_COLUMNS:
+            raise ValueError("compute_pmf: K + non-empty bins + 1 = %d exceeds %d columns of the asymptotic covariance (a host SVD); "
+                             "use uncertainty_method='bootstrap'" % (K + ne + 1, self.PMF_MAX_COLUMNS))
+        G = np.zeros((C, C))
+        G[:K, :K] = self._gram()
+        G[:K, K:K + ne] = cross[:, full]
+        G[K:K + ne, :K] = cross[:, full].T
+        G[np.arange(K, K + ne), np.arange(K, K + ne)] = diag[full]
+        if normalised:
+            G[-1, -1] = parts[1]
+            G[-1, :K] = G[:K, -1] = parts[2:2 + K]
+            G[-1, K:K + ne] = G[K:K + ne, -1] = parts[2 + K:][full]
+        Theta = self._theta_of_gram(G, np.concatenate([self.N_k, np.zeros(C - K, dtype=np.int64)]))
+        err = self._error_of_differences(Theta[K:, K:])                       # [ne (+ 1)][ne (+ 1)]
+        if uncertainties == 'all-differences':
+            df = np.full((nbins, nbins), np.nan)
+            df[np.ix_(full, full)] = err
+        else:
+            df = np.full(nbins, np.nan)
+            df[full] = err[:ne, -1] if normalised else err[:ne, int(np.searchsorted(full, reference))]
+        return dict(f_i=out_f, df_i=df, n_i=n_i)
+
+    @staticmethod
+    def _std_of_finite(d):
+        """the population standard deviation over axis 0 of the finite entries of d; NaN where fewer than two are finite"""
+        ok = np.isfinite(d)
+        n = ok.sum(axis=0)
+        x = np.where(ok, d, 0.0)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            mean = x.sum(axis=0) / n
+            var = np.where(ok, (d - mean) ** 2, 0.0).sum(axis=0) / n
+        return np.where(n >= 2, np.sqrt(var), np.nan)
+
     def compute_expectations(self, A_n, u_kn=None, output='averages', state_dependent=False, uncertainty_method=None):
         """<A> at every state with its uncertainty.  ``A_n`` is [N], or [S][N] with ``state_dependent=True`` (row s is the observable
         of state s).  ``u_kn=None``: the S = K states of the estimator; otherwise the S = L perturbed states ``u_kn`` [L][N].
@@ -960,6 +1159,7 @@ class MultiStateSamplerAnalyzer:
         self._check_bootstrap_option('bootstrap_seed', self._kwargs.get('bootstrap_seed', 0))
         self._check_bootstrap_option('uncertainty_method', self._kwargs.get('uncertainty_method'))
         self._sample_states = None              # [N]: the row of the matrix handed to MBAR each of its columns was drawn from
+        self._sample_columns = None             # (iterations, kept columns or None): the frames behind the columns of that matrix
         self._energy_store = None               # the DeviceEnergyStore of assembly_solver = 'device', made on first use
         self._equilibration_data = None
         self._mbar = None
@@ -1371,6 +1571,7 @@ class MultiStateSamplerAnalyzer:
         u_ln, N_l = self._compute_mbar_decorrelated_energies(selection)
         # the column of frame [replica][iteration] was drawn from the sampled state the replica was in, past the unsampled rows in front
         self._sample_states = selection[2].reshape(-1) + int((len(N_l) - selection[0].shape[1]) / 2)
+        self._sample_columns = (selection[3], None)         # the iterations of the columns, and which columns were kept (None: all)
         initial_f_k = self._kwargs.get('initial_f_k')
         restraint_data = None
         if self.unbias_restraint:
@@ -1399,6 +1600,7 @@ class MultiStateSamplerAnalyzer:
         keep = np.flatnonzero(~drop)
         u_ln, energies_kJ = u_ln[:, keep], energies_kJ[keep]
         self._sample_states = self._sample_states[keep] + 1                  # (the kept columns, past the end row added in front)
+        self._sample_columns = (iterations, keep)
         u_ln_new = np.zeros((u_ln.shape[0] + 2, u_ln.shape[1]), u_ln.dtype)
         N_l_new = np.zeros(len(N_l) + 2, N_l.dtype)
         # each end row loses the restraint in the kT of ITS OWN end state.  The reference divides both by the first state's kT
@@ -1477,6 +1679,29 @@ class MultiStateSamplerAnalyzer:
             return self.mbar.compute_free_energy_differences()
         return self.mbar.compute_free_energy_differences(uncertainty_method=self.uncertainty_method)
 
+    def get_pmf(self, values, edges, state=0, uncertainties='from-lowest', pmf_reference=None):
+        """(f_i, df_i, n_i) in kT: the free energy surface at sampled state ``state`` along the coordinate ``values``
+        [n_iterations + 1][n_replicas] (or [...][D], D <= 3), the coordinate of every replica at every stored iteration, binned by
+        ``edges`` (``bin_samples``).  The columns are those MBAR was given: the same equilibration cut and decorrelated selection, in
+        the same order, less the frames a restraint cutoff dropped.  Errors by the analyzer's ``uncertainty_method``."""
+        n_it, n_replicas, n_states = self.n_iterations + 1, self.n_replicas, self.n_states
+        v = np.asarray(values, dtype=np.float64)
+        if v.ndim not in (2, 3) or v.shape[:2] != (n_it, n_replicas):
+            raise ValueError('values must be [n_iterations + 1][n_replicas] = [%d][%d], or that with a last axis of D <= 3 coordinates, '
+                             'not an array of shape %r' % (n_it, n_replicas, v.shape))
+        if isinstance(state, bool) or not isinstance(state, (int, np.integer)) or not 0 <= state < n_states:
+            raise ValueError('state must be the index of a sampled state in 0 ... %d, not %r' % (n_states - 1, state))
+        mbar = self.mbar
+        iterations, keep = self._sample_columns
+        v = np.swapaxes(v[iterations], 0, 1)                                  # [replica][iteration]: the order of the columns of u_ln
+        v = v.reshape((-1,) + v.shape[2:])
+        if keep is not None:
+            v = v[keep]
+        bin_n, nbins = bin_samples(v, edges)
+        u_n = mbar.u_kn[int((mbar.K - n_states) / 2) + int(state)]
+        r = mbar.compute_pmf(u_n, bin_n, nbins, uncertainties=uncertainties, pmf_reference=pmf_reference,
+                             uncertainty_method=self.uncertainty_method)
+        return r['f_i'], r['df_i'], r['n_i']
 
 
 class ReplicaExchangeAnalyzer(MultiStateSamplerAnalyzer):
