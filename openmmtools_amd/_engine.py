@@ -106,6 +106,12 @@ class RemdCustomForceDescGB(RemdCustomForceDescManyParticle):
     _fields_ = [('gb_stages', c_int32_p), ('gb_n_values', C.c_int32), ('gb_n_stages', C.c_int32)]    # (the pointer first, as in C)
 
 
+class RemdFrameCvTables(C.Structure):
+    """remd_frame_cv_tables of include/remd_hip_frame_cvs.h (the collective variables of a call as CSR tables)."""
+    _fields_ = [('n_cv', C.c_int32), ('kind', c_int32_p), ('periodic', c_int32_p), ('cv_groups', c_int32_p), ('group_off', c_int32_p),
+                ('atoms', c_int32_p), ('weights', c_double_p), ('reference', c_double_p)]
+
+
 class RemdGbModelDesc(C.Structure):
     """remd_gb_model_desc of include/remd_hip_gb.h (the constants and the cutoff of an OBC-family implicit-solvent model)."""
     _fields_ = [('offset', C.c_double), ('alpha', C.c_double), ('beta', C.c_double), ('gamma', C.c_double), ('ke', C.c_double),
@@ -116,6 +122,8 @@ class RemdGbModelDesc(C.Structure):
 RESTRAINT_EXPORTS = ['remd_set_restraints', 'remd_set_restraint_lambdas', 'remd_get_restraint_energies']
 # the analysis pass over stored frames of the same header (no handle: a device), bound the same way
 RESTRAINT_FRAMES_EXPORTS = ['remd_restraint_frames', 'remd_restraint_frames_last_ms']
+# the GPU-only extension of include/remd_hip_frame_cvs.h (collective variables of stored frames; no handle: a device), bound the same way
+FRAME_CVS_EXPORTS = ['remd_frame_cvs']
 # the GPU-only extension of include/remd_hip_custom.h (custom bond / angle / torsion / external forces), bound the same way
 CUSTOM_EXPORTS = ['remd_set_custom_terms', 'remd_set_custom_globals', 'remd_set_custom_lrc', 'remd_get_custom_energies']
 # the collective-variable forces of the same header (REMD_CUSTOM_CV): a library built before them lacks the entry point
@@ -276,6 +284,10 @@ def load_library(path=None):
         lib.remd_restraint_frames_last_ms.argtypes = [c_double_p]
         for name in RESTRAINT_FRAMES_EXPORTS:
             getattr(lib, name).restype = C.c_int
+    if hasattr(lib, 'remd_frame_cvs'):                    # include/remd_hip_frame_cvs.h (GPU-only, like the restraints)
+        lib.remd_frame_cvs.argtypes = [C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(RemdFrameCvTables),
+                                       C.c_int64, c_double_p, c_double_p]
+        lib.remd_frame_cvs.restype = C.c_int
     if hasattr(lib, 'remd_set_custom_terms'):             # include/remd_hip_custom.h (GPU-only, like the restraints)
         lib.remd_set_custom_terms.argtypes = [vp, C.POINTER(RemdCustomForceDescGB), C.c_int]
         lib.remd_set_custom_globals.argtypes = [vp, c_double_p]
@@ -463,6 +475,36 @@ def restraint_frames_last_ms(lib_path=None):
     if fn(C.byref(ms)) != 0:
         raise RuntimeError('remd_restraint_frames_last_ms failed: %s' % lib.remd_last_error(None).decode())
     return ms.value
+
+
+def frame_cvs(cvs, pos, box=None, masses=None, device=0, frames_per_pass=0, lib_path=None, timing=None):
+    """values [F][n_cv] f64 (nm, rad) of the collective variables ``cvs`` (multistate.analysis: DistanceCV, AngleCV, DihedralCV, RMSDCV,
+    their atom indices addressing the atoms of ``pos``) at F stored frames (include/remd_hip_frame_cvs.h, csrc/frame_cvs.hip): the
+    device counterpart of analysis.frame_cvs_numpy, with its arguments and refusals.  ``pos`` [F][n_atoms][3] f32, ``box`` [F][3] f32 or
+    None.  The frames are uploaded ``frames_per_pass`` at a time (0: the library's choice); a frame's value does not depend on that.
+    ``timing``: a dict that receives 'kernel_ms', the device milliseconds of the kernels of this call."""
+    from .multistate import analysis
+    lib = load_library(lib_path)
+    if not hasattr(lib, 'remd_frame_cvs'):
+        raise NotImplementedError('remd_frame_cvs: this build of the engine library has no collective variables of stored frames '
+                                  '(include/remd_hip_frame_cvs.h is GPU-only)')
+    cvs, pos, box = analysis._check_frames(cvs, pos, box)
+    pos = np.ascontiguousarray(pos, dtype=np.float32)
+    F, n_atoms = int(pos.shape[0]), int(pos.shape[1])
+    box = None if box is None else np.ascontiguousarray(box, dtype=np.float32)
+    if int(frames_per_pass) < 0:
+        raise ValueError('frames_per_pass must not be negative (0: the library chooses)')
+    t = analysis.frame_cv_tables(cvs, n_atoms, masses)
+    tables = RemdFrameCvTables(len(cvs), _ip(t['kind']), _ip(t['periodic']), _ip(t['cv_groups']), _ip(t['group_off']), _ip(t['atoms']),
+                               _dp(t['weights']), _dp(t['reference']))
+    out = np.empty((F, len(cvs)))
+    ms = C.c_double(0.0)
+    rc = lib.remd_frame_cvs(int(device), F, n_atoms, _fp(pos), _fp(box), C.byref(tables), int(frames_per_pass), _dp(out), C.byref(ms))
+    if rc != 0:
+        raise RuntimeError('remd_frame_cvs failed (%d): %s' % (rc, lib.remd_last_error(None).decode()))
+    if timing is not None:
+        timing['kernel_ms'] = ms.value
+    return out
 
 
 def _require_exports(lib, names, what):

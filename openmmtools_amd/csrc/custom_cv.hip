@@ -27,33 +27,19 @@
 #include "remd_internal.h"
 #include "listed_terms.h"
 #include "custom_machine.h"
-#include "centroid_sum.h"
-#include "custom_cv_math.h"
+#include "custom_cv_superpose.h"
 
 namespace {
 
-constexpr int CV_BLOCK = 256;
 constexpr int CV_W = 16;            // doubles per (replica, variable) of W: V, flag, c[3], U[9], dE/dV, one spare
-constexpr double CV_MSD_FLOOR = 1e-20;
 
-// N sums over the workgroup of four wavefronts in a fixed order; every thread gets the results (s: [N][4] doubles of LDS)
-template <int N>
-__device__ __forceinline__ void cv_block_sum(double (&v)[N], double (*s)[4])
-{
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = wave_sum_d(v[k]);
-    const int wv = threadIdx.x >> 6;
-    __syncthreads();                                  // (the previous call's readers are done with s)
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) s[k][wv] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = ((s[k][0] + s[k][1]) + s[k][2]) + s[k][3];
-}
+// a replica's positions as the superposition reads them (custom_cv_superpose.h)
+struct cv_pos4 {
+    const float4* __restrict__ P;
+    __device__ __forceinline__ void operator()(int a, float& x, float& y, float& z) const { const float4 q = P[a]; x = q.x; y = q.y; z = q.z; }
+};
 
-// grid (n_cv, R), CV_BLOCK threads
+// grid (n_cv, R), CV_BLOCK threads: the two passes of custom_cv_superpose.h
 __global__ __launch_bounds__(CV_BLOCK)
 void custom_cv_superpose_kernel(int n_cv, const int* __restrict__ cv_off, const int* __restrict__ cv_atoms, const double* __restrict__ cv_ref,
                                 int Npad, const float4* __restrict__ pos, double* __restrict__ W /*[R][n_cv][CV_W]*/)
@@ -61,47 +47,18 @@ void custom_cv_superpose_kernel(int n_cv, const int* __restrict__ cv_off, const 
     __shared__ double s[12][4];
     const int cv = blockIdx.x, r = blockIdx.y;
     const int b = cv_off[cv], n = cv_off[cv + 1] - b;
-    const float4* P = pos + (size_t)r * Npad;
-    const float4 a0 = P[cv_atoms[b]];
-    double acc[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) acc[k] = 0.0;
-    for (int k = threadIdx.x; k < n; k += CV_BLOCK) {
-        const float4 q = P[cv_atoms[b + k]];
-        const double* y = cv_ref + 3 * (size_t)(b + k);
-        const double dx = (double)q.x - (double)a0.x, dy = (double)q.y - (double)a0.y, dz = (double)q.z - (double)a0.z;
-        const double y0 = y[0], y1 = y[1], y2 = y[2];
-        acc[0] += dx; acc[1] += dy; acc[2] += dz;
-        acc[3] += dx * y0; acc[4] += dx * y1; acc[5] += dx * y2;
-        acc[6] += dy * y0; acc[7] += dy * y1; acc[8] += dy * y2;
-        acc[9] += dz * y0; acc[10] += dz * y1; acc[11] += dz * y2;
-    }
-    cv_block_sum<12>(acc, s);
-    const double inv_n = 1.0 / (double)n;
-    const double cx_ = acc[0] * inv_n, cy_ = acc[1] * inv_n, cz_ = acc[2] * inv_n;     // the centroid relative to the first particle
-    const double S[3][3] = {{acc[3], acc[4], acc[5]}, {acc[6], acc[7], acc[8]}, {acc[9], acc[10], acc[11]}};
-    double U[3][3];
-    cv_superpose(S, U);
-    double m[1] = {0.0};
-    for (int k = threadIdx.x; k < n; k += CV_BLOCK) {
-        const float4 q = P[cv_atoms[b + k]];
-        const double* y = cv_ref + 3 * (size_t)(b + k);
-        const double y0 = y[0], y1 = y[1], y2 = y[2];
-        const double ex = ((double)q.x - (double)a0.x) - cx_ - (U[0][0] * y0 + U[0][1] * y1 + U[0][2] * y2);
-        const double ey = ((double)q.y - (double)a0.y) - cy_ - (U[1][0] * y0 + U[1][1] * y1 + U[1][2] * y2);
-        const double ez = ((double)q.z - (double)a0.z) - cz_ - (U[2][0] * y0 + U[2][1] * y1 + U[2][2] * y2);
-        m[0] += ex * ex + ey * ey + ez * ez;
-    }
-    cv_block_sum<1>(m, s);
+    const cv_pos4 X{pos + (size_t)r * Npad};
+    cv_fit fit;
+    cv_superpose_block(X, cv_atoms, cv_ref, b, n, s, fit);
     if (threadIdx.x == 0) {
-        const double msd = m[0] * inv_n;
+        const double msd = fit.msd;
         const bool flat = !(msd >= CV_MSD_FLOOR);                 // (a NaN sets the flag too: no force from it)
         double* o = W + ((size_t)r * n_cv + cv) * CV_W;
         o[0] = flat ? (msd != msd ? msd : 0.0) : sqrt(msd);
         o[1] = flat ? 1.0 : 0.0;
-        o[2] = (double)a0.x + cx_; o[3] = (double)a0.y + cy_; o[4] = (double)a0.z + cz_;
+        o[2] = (double)fit.ax + fit.cx; o[3] = (double)fit.ay + fit.cy; o[4] = (double)fit.az + fit.cz;
 #pragma unroll
-        for (int a = 0; a < 3; ++a) { o[5 + 3 * a] = U[a][0]; o[6 + 3 * a] = U[a][1]; o[7 + 3 * a] = U[a][2]; }
+        for (int a = 0; a < 3; ++a) { o[5 + 3 * a] = fit.U[a][0]; o[6 + 3 * a] = fit.U[a][1]; o[7 + 3 * a] = fit.U[a][2]; }
     }
 }
 

@@ -22,6 +22,9 @@ published algorithms the analyzer relies on, in plain numpy:
   with the centroid convention the run was sampled with -- not the reference's, see DESIGN.md.  The walks over the stored energies
   (effective energies, u_ln / N_l assembly, transition counts and the state walk's statistical inefficiency) run as numpy loops or on
   the device (``analysis_kwargs={'assembly_solver': 'device'}``, include/remd_hip_energy_store.h, csrc/energy_store.hip).
+* ``DistanceCV`` / ``AngleCV`` / ``DihedralCV`` / ``RMSDCV``, ``frame_cvs_numpy`` and ``get_collective_variables`` -- not in the
+  reference: the coordinates ``get_pmf`` takes, computed from the stored frames of the analysis particles with the conventions of the
+  force kernels, in numpy or on the device (``analysis_kwargs={'cv_solver': 'device'}``, include/remd_hip_frame_cvs.h, csrc/frame_cvs.hip).
 
 Parity: unpinned against pymbar itself (absent); pinned against the analytical free energies of harmonic oscillators,
 the reference's own acceptance test (tests/test_sampling.py:100-300), in tests/test_analysis_cpu.py.
@@ -333,6 +336,342 @@ def bin_samples(values, edges):
         inside &= ok
         stride *= e.size - 1
     return np.where(inside, flat, -1), int(stride)
+
+
+# ---- collective variables of stored frames ------------------------------------------------------------------------
+# The coordinates a surface is taken over, with the conventions of the force kernels (include/remd_hip_frame_cvs.h): the centroid of
+# a group is c = x_first + sum_i w_i img(x_i - x_first) / sum w, img the minimum image under the frame's own box when the variable is
+# periodic (restraint_frames_numpy, csrc/custom_centroid.hip); differences between centroids are imaged the same way.
+FRAME_CV_DISTANCE, FRAME_CV_ANGLE, FRAME_CV_DIHEDRAL, FRAME_CV_RMSD = 0, 1, 2, 3
+_RMSD_MSD_FLOOR = 1e-20                 # nm^2 (csrc/custom_cv_superpose.h)
+
+
+class _CentroidCV:
+    """What DistanceCV, AngleCV and DihedralCV share: ``groups`` (tuples of atom indices in System numbering), ``weights`` (one tuple
+    per group or None: the particles' masses; a group of one atom has weight 1) and ``periodic``."""
+    kind = None
+
+    def __init__(self, groups, weights, periodic):
+        name = type(self).__name__
+        self.groups = tuple(self._group(name, g + 1, group) for g, group in enumerate(groups))
+        if weights is None:
+            weights = [None] * len(self.groups)
+        weights = list(weights)
+        if len(weights) != len(self.groups):
+            raise ValueError('%s: weights must hold one list (or None) per group: %d, not %d' % (name, len(self.groups), len(weights)))
+        self.weights = tuple(self._weights(name, g + 1, w, self.groups[g]) for g, w in enumerate(weights))
+        self.periodic = bool(periodic)
+
+    @staticmethod
+    def _group(name, g, group, what='group %d'):
+        what = what % g if '%' in what else what
+        atoms = [group] if np.ndim(group) == 0 else list(group)
+        if not atoms:
+            raise ValueError('%s: %s is empty' % (name, what))
+        out = []
+        for a in atoms:
+            if isinstance(a, bool) or not isinstance(a, (int, np.integer)):
+                raise ValueError('%s: %s holds %r, which is not an atom index' % (name, what, a))
+            if a < 0:
+                raise ValueError('%s: %s holds the negative index %d' % (name, what, a))
+            if int(a) in out:
+                raise ValueError('%s: %s names atom %d twice' % (name, what, a))
+            out.append(int(a))
+        return tuple(out)
+
+    @staticmethod
+    def _weights(name, g, w, atoms):
+        if w is None:
+            return None
+        w = np.asarray(w, dtype=np.float64).reshape(-1)
+        if w.size != len(atoms):
+            raise ValueError('%s: group %d has %d atoms but %d weights' % (name, g, len(atoms), w.size))
+        if not np.all(np.isfinite(w)) or np.any(w < 0.0):
+            raise ValueError('%s: the weights of group %d must be finite and not negative' % (name, g))
+        if not w.sum() > 0.0:
+            raise ValueError('%s: the weights of group %d sum to zero' % (name, g))
+        return tuple(float(x) for x in w)
+
+    def _key(self):
+        return (self.kind, self.groups, self.weights, self.periodic)
+
+    def _atoms(self):
+        return [a for group in self.groups for a in group]
+
+    def _remapped(self, where, n_system):
+        """the same variable over the columns ``where[atom]`` of the stored frames"""
+        new = object.__new__(type(self))
+        new.groups = tuple(tuple(where[a] for a in group) for group in self.groups)
+        new.weights, new.periodic = self.weights, self.periodic
+        return new
+
+    def _not_periodic(self):
+        new = object.__new__(type(self))
+        new.groups, new.weights, new.periodic = self.groups, self.weights, False
+        return new
+
+
+class DistanceCV(_CentroidCV):
+    """The distance |d| (nm) between the centroids of two groups, d the minimum image of c2 - c1 when periodic."""
+    kind = FRAME_CV_DISTANCE
+
+    def __init__(self, group1, group2, weights1=None, weights2=None, periodic=True):
+        super().__init__((group1, group2), (weights1, weights2), periodic)
+
+
+class AngleCV(_CentroidCV):
+    """The angle (rad, [0, pi]) at the centroid of group2 between those of group1 and group3: acos of the cosine clamped to [-1, 1]."""
+    kind = FRAME_CV_ANGLE
+
+    def __init__(self, group1, group2, group3, weights=None, periodic=True):
+        super().__init__((group1, group2, group3), weights, periodic)
+
+
+class DihedralCV(_CentroidCV):
+    """The dihedral (rad, (-pi, pi]) of the centroids of four groups, atan2(|b2| b1.(b2 x b3), (b1 x b2).(b2 x b3)) with b_k = c_k+1 -
+    c_k: the sign and range of PeriodicTorsionForce and of dihedral(p1,p2,p3,p4) in a custom-force expression."""
+    kind = FRAME_CV_DIHEDRAL
+
+    def __init__(self, group1, group2, group3, group4, weights=None, periodic=True):
+        super().__init__((group1, group2, group3, group4), weights, periodic)
+
+
+class RMSDCV:
+    """The RMSD (nm) of ``particles`` from ``reference_positions`` [N][3] (all particles of the System, as system.RMSDForce takes them)
+    after the optimal superposition: system.RMSDForce's value.  A mean square deviation below 1e-20 nm^2 gives 0.  No minimum images
+    are taken: the particles must belong to one molecule that the run kept whole."""
+    kind = FRAME_CV_RMSD
+    periodic = False
+
+    def __init__(self, reference_positions, particles):
+        ref = np.array(reference_positions, dtype=np.float64)
+        if ref.ndim != 2 or ref.shape[1] != 3:
+            raise ValueError('RMSDCV: reference_positions must be [N][3], not an array of shape %r' % (ref.shape,))
+        if not np.all(np.isfinite(ref)):
+            raise ValueError('RMSDCV: reference_positions are not finite (particle %d)' % int(np.flatnonzero(~np.isfinite(ref).all(axis=1))[0]))
+        self.particles = _CentroidCV._group('RMSDCV', 0, particles, what='particles')
+        if len(self.particles) < 3:
+            raise ValueError('RMSDCV: particles holds %d atoms; an RMSD needs at least 3' % len(self.particles))
+        self.reference_positions = ref
+
+    def _key(self):
+        return (self.kind, self.particles, self.reference_positions.tobytes())
+
+    def _atoms(self):
+        return list(self.particles)
+
+    def _remapped(self, where, n_system):
+        if len(self.reference_positions) != n_system:
+            raise ValueError('RMSDCV: reference_positions holds %d particles but the System has %d' % (len(self.reference_positions), n_system))
+        new = object.__new__(RMSDCV)
+        columns = sorted(where.items(), key=lambda item: item[1])                   # (atom, column) in the order of the columns
+        new.particles = tuple(where[a] for a in self.particles)
+        new.reference_positions = self.reference_positions[[a for a, _ in columns]]
+        return new
+
+    def _not_periodic(self):
+        return self
+
+
+def _compile_frame_cvs(cvs, n_atoms, masses):
+    """[(kind, periodic, [(atoms int64, normalised weights f64)], centred reference [n][3] or None)] of descriptors whose indices
+    address the ``n_atoms`` atoms of a frame: what both evaluators work from."""
+    if masses is not None:
+        masses = np.asarray(masses, dtype=np.float64).reshape(-1)
+        if masses.size != n_atoms:
+            raise ValueError('masses must have one entry per atom of pos: %d, not %d' % (n_atoms, masses.size))
+    out = []
+    for v, cv in enumerate(cvs):
+        who = 'variable %d (%s)' % (v, type(cv).__name__)
+        if not isinstance(cv, (_CentroidCV, RMSDCV)):
+            raise ValueError('variable %d is %r, not a DistanceCV, AngleCV, DihedralCV or RMSDCV' % (v, cv))
+        for a in cv._atoms():
+            if a >= n_atoms:
+                raise ValueError('%s: atom %d is outside the %d atoms of the frames' % (who, a, n_atoms))
+        if cv.kind == FRAME_CV_RMSD:
+            if len(cv.reference_positions) != n_atoms:
+                raise ValueError('%s: reference_positions holds %d particles but the frames have %d' % (who, len(cv.reference_positions), n_atoms))
+            atoms = np.array(cv.particles, dtype=np.int64)
+            ref = cv.reference_positions[atoms]
+            out.append((cv.kind, False, [(atoms, np.full(atoms.size, 1.0 / atoms.size))], ref - ref.mean(axis=0)))
+            continue
+        groups = []
+        for g, (group, w) in enumerate(zip(cv.groups, cv.weights)):
+            atoms = np.array(group, dtype=np.int64)
+            if atoms.size == 1:
+                w = np.ones(1)
+            elif w is None:
+                if masses is None:
+                    raise ValueError('%s: group %d has no weights and no masses were given' % (who, g + 1))
+                w = masses[atoms]
+                if not np.all(np.isfinite(w)) or np.any(w < 0.0) or not w.sum() > 0.0:
+                    raise ValueError('%s: the masses of group %d sum to zero (or are negative): give weights' % (who, g + 1))
+            else:
+                w = np.array(w, dtype=np.float64)
+            groups.append((atoms, w / w.sum()))
+        out.append((cv.kind, bool(cv.periodic), groups, None))
+    return out
+
+
+def frame_cv_tables(cvs, n_atoms, masses=None):
+    """The CSR tables of remd_frame_cv_tables (include/remd_hip_frame_cvs.h) for descriptors whose indices address the atoms of a frame:
+    a dict of kind, periodic [n_cv] i4, cv_groups [n_cv + 1] i4, group_off i4, atoms i4, weights f8 (normalised) and reference
+    [entries][3] f8 (the centred reference in the rows of an RMSD's particles, zeros elsewhere)."""
+    compiled = _compile_frame_cvs(cvs, n_atoms, masses)
+    kind, periodic, cv_groups, group_off, atoms, weights, reference = [], [], [0], [0], [], [], []
+    for k, pbc, groups, ref in compiled:
+        kind.append(k); periodic.append(int(pbc))
+        for a, w in groups:
+            atoms.append(a); weights.append(w)
+            reference.append(np.zeros((a.size, 3)) if ref is None else ref)
+            group_off.append(group_off[-1] + a.size)
+        cv_groups.append(cv_groups[-1] + len(groups))
+    i4 = lambda x: np.ascontiguousarray(x, dtype=np.int32)
+    cat = lambda parts, shape: np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(shape)
+    return dict(kind=i4(kind), periodic=i4(periodic), cv_groups=i4(cv_groups), group_off=i4(group_off),
+                atoms=i4(cat(atoms, (0,))), weights=cat(weights, (0,)), reference=cat(reference, (0, 3)))
+
+
+def _check_frames(cvs, pos, box):
+    """(cvs as a list, pos, box as f64 or None) of an evaluator call; the refusals both evaluators share"""
+    cvs = list(cvs)
+    if not cvs:
+        raise ValueError('no collective variable was given')
+    pos = np.asarray(pos)
+    if pos.ndim != 3 or pos.shape[2] != 3 or pos.shape[0] < 1 or pos.shape[1] < 1:
+        raise ValueError('pos must be [F][n_atoms][3] with F >= 1')
+    F = pos.shape[0]
+    if box is None:
+        for v, cv in enumerate(cvs):
+            if getattr(cv, 'periodic', False):
+                raise ValueError('variable %d (%s) is periodic but the frames have no box: give box [F][3], or periodic=False'
+                                 % (v, type(cv).__name__))
+    else:
+        box = np.asarray(box)
+        if box.shape != (F, 3):
+            raise ValueError('box must be [F][3] (the edges of a rectangular box; triclinic boxes are not supported)')
+        if not (np.all(np.isfinite(box)) and np.all(box > 0.0)):
+            raise ValueError('a non-finite or non-positive box edge')
+    return cvs, pos, box
+
+
+def _jacobi_superpose(S):
+    """U [F][3][3] with x_i ~ U ref_i from S [F][3][3], S_ab = sum_i x_ia ref_ib (both centred): csrc/custom_cv_math.h over many frames
+    at once -- Horn's 4 x 4 matrix, cyclic Jacobi rotations until the off-diagonal share falls below 1e-32 (a frame that has
+    converged is rotated no further), the eigenvector of the largest eigenvalue (the first of equal ones) as a unit quaternion."""
+    Sxx, Sxy, Sxz = S[:, 0, 0], S[:, 1, 0], S[:, 2, 0]
+    Syx, Syy, Syz = S[:, 0, 1], S[:, 1, 1], S[:, 2, 1]
+    Szx, Szy, Szz = S[:, 0, 2], S[:, 1, 2], S[:, 2, 2]
+    A = np.empty((S.shape[0], 4, 4))
+    A[:, 0, 0] = Sxx + Syy + Szz; A[:, 1, 1] = Sxx - Syy - Szz; A[:, 2, 2] = -Sxx + Syy - Szz; A[:, 3, 3] = -Sxx - Syy + Szz
+    A[:, 0, 1] = A[:, 1, 0] = Syz - Szy; A[:, 0, 2] = A[:, 2, 0] = Szx - Sxz; A[:, 0, 3] = A[:, 3, 0] = Sxy - Syx
+    A[:, 1, 2] = A[:, 2, 1] = Sxy + Syx; A[:, 1, 3] = A[:, 3, 1] = Szx + Sxz; A[:, 2, 3] = A[:, 3, 2] = Syz + Szy
+    V = np.zeros_like(A)
+    V[:, [0, 1, 2, 3], [0, 1, 2, 3]] = 1.0
+    pairs = [(0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3)]
+    with np.errstate(all='ignore'):
+        for _ in range(30):
+            off = sum(A[:, p, q] * A[:, p, q] for p, q in pairs)
+            diag = sum(A[:, k, k] * A[:, k, k] for k in range(4))
+            live = off > 1e-32 * (diag + 2.0 * off)
+            if not live.any():
+                break
+            for p, q in pairs:
+                apq = A[:, p, q].copy()
+                turn = live & (apq != 0.0)
+                theta = (A[:, q, q] - A[:, p, p]) / (2.0 * np.where(turn, apq, 1.0))
+                t = np.where(np.abs(theta) > 1e150, 0.5 / theta, np.where(theta >= 0.0, 1.0, -1.0) / (np.abs(theta) + np.sqrt(theta * theta + 1.0)))
+                t = np.where(turn, t, 0.0)                                     # (t = 0: c = 1, s = 0, the identity)
+                c = 1.0 / np.sqrt(t * t + 1.0)
+                s = t * c
+                tau = s / (1.0 + c)
+                A[:, p, p] -= t * apq; A[:, q, q] += t * apq
+                A[:, p, q] = np.where(turn, 0.0, apq); A[:, q, p] = A[:, p, q]
+                for k in range(4):
+                    if k != p and k != q:
+                        akp, akq = A[:, k, p].copy(), A[:, k, q].copy()
+                        A[:, k, p] = A[:, p, k] = akp - s * (akq + tau * akp)
+                        A[:, k, q] = A[:, q, k] = akq + s * (akp - tau * akq)
+                for k in range(4):
+                    vkp, vkq = V[:, k, p].copy(), V[:, k, q].copy()
+                    V[:, k, p] = vkp - s * (vkq + tau * vkp)
+                    V[:, k, q] = vkq + s * (vkp - tau * vkq)
+        lam, quat = A[:, 0, 0].copy(), V[:, :, 0].copy()
+        for j in range(1, 4):
+            up = A[:, j, j] > lam
+            lam = np.where(up, A[:, j, j], lam)
+            quat = np.where(up[:, None], V[:, :, j], quat)
+        nq = (quat * quat).sum(axis=1)
+        quat = quat * np.where(nq > 0.0, 1.0 / np.sqrt(nq), 0.0)[:, None]
+    q0, q1, q2, q3 = quat[:, 0], quat[:, 1], quat[:, 2], quat[:, 3]
+    U = np.empty((S.shape[0], 3, 3))
+    U[:, 0, 0] = q0 * q0 + q1 * q1 - q2 * q2 - q3 * q3; U[:, 0, 1] = 2.0 * (q1 * q2 - q0 * q3); U[:, 0, 2] = 2.0 * (q1 * q3 + q0 * q2)
+    U[:, 1, 0] = 2.0 * (q1 * q2 + q0 * q3); U[:, 1, 1] = q0 * q0 - q1 * q1 + q2 * q2 - q3 * q3; U[:, 1, 2] = 2.0 * (q2 * q3 - q0 * q1)
+    U[:, 2, 0] = 2.0 * (q1 * q3 - q0 * q2); U[:, 2, 1] = 2.0 * (q2 * q3 + q0 * q1); U[:, 2, 2] = q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3
+    return U
+
+
+def _frames_rmsd(x, ref):
+    """RMSD [F] of x [F][n][3] (f64) against the centred reference [n][3]: the two passes of csrc/custom_cv_superpose.h"""
+    d = x - x[:, :1, :]
+    n = d.shape[1]
+    c, S = np.zeros((d.shape[0], 3)), np.zeros((d.shape[0], 3, 3))
+    for k in range(n):                                                         # (ascending order within the group)
+        c += d[:, k, :]
+        S += d[:, k, :, None] * ref[k][None, None, :]
+    c /= n
+    U = _jacobi_superpose(S)
+    m = np.zeros(d.shape[0])
+    for k in range(n):
+        e = d[:, k, :] - c - U @ ref[k]
+        m += (e * e).sum(axis=1)
+    msd = m / n
+    with np.errstate(invalid='ignore'):
+        return np.where(msd >= _RMSD_MSD_FLOOR, np.sqrt(np.where(msd >= _RMSD_MSD_FLOOR, msd, 1.0)), np.where(np.isnan(msd), msd, 0.0))
+
+
+def frame_cvs_numpy(cvs, pos, box=None, masses=None, frames_per_pass=4096):
+    """values [F][n_cv] f64 (nm, rad) of the collective variables ``cvs`` (DistanceCV, AngleCV, DihedralCV, RMSDCV) at F frames, in
+    f64 and vectorised over the frames: the host counterpart of remd_frame_cvs (include/remd_hip_frame_cvs.h) with the engine's
+    conventions.  ``pos`` [F][n_atoms][3]; the descriptors' indices address its atoms.  ``box`` [F][3] or None (then no variable
+    may be periodic); ``masses`` [n_atoms] weigh the groups that carry no weights of their own.  Within a group the sum runs over the
+    atoms in ascending order of their place in the group, so a value depends neither on ``frames_per_pass`` nor on the other variables."""
+    cvs, pos, box = _check_frames(cvs, pos, box)
+    if int(frames_per_pass) < 1:
+        raise ValueError('frames_per_pass must be at least 1')
+    F, n_atoms = pos.shape[0], pos.shape[1]
+    compiled = _compile_frame_cvs(cvs, n_atoms, masses)
+    out = np.empty((F, len(compiled)))
+    for f0 in range(0, F, int(frames_per_pass)):                 # (bounds the f64 copies of the positions)
+        sl = slice(f0, min(F, f0 + int(frames_per_pass)))
+        for v, (kind, periodic, groups, ref) in enumerate(compiled):
+            if kind == FRAME_CV_RMSD:
+                out[sl, v] = _frames_rmsd(pos[sl][:, groups[0][0], :].astype(np.float64), ref)
+                continue
+            L = box[sl].astype(np.float64) if periodic else None
+
+            def img(d):
+                return d - L * np.rint(d / L) if periodic else d
+            c = []
+            for atoms, w in groups:
+                x = pos[sl][:, atoms, :].astype(np.float64)
+                acc = np.zeros((x.shape[0], 3))
+                for k in range(atoms.size):
+                    acc += w[k] * img(x[:, k, :] - x[:, 0, :])
+                c.append(x[:, 0, :] + acc)
+            with np.errstate(invalid='ignore', divide='ignore'):
+                if kind == FRAME_CV_DISTANCE:
+                    d = img(c[1] - c[0])
+                    out[sl, v] = np.sqrt((d * d).sum(axis=1))
+                elif kind == FRAME_CV_ANGLE:
+                    v0, v1 = img(c[0] - c[1]), img(c[2] - c[1])
+                    cosine = (v0 * v1).sum(axis=1) / np.sqrt((v0 * v0).sum(axis=1) * (v1 * v1).sum(axis=1))
+                    out[sl, v] = np.arccos(np.fmin(np.fmax(cosine, -1.0), 1.0))
+                else:
+                    b1, b2, b3 = img(c[1] - c[0]), img(c[2] - c[1]), img(c[3] - c[2])
+                    m, nn = np.cross(b1, b2), np.cross(b2, b3)
+                    out[sl, v] = np.arctan2(np.sqrt((b2 * b2).sum(axis=1)) * (b1 * nn).sum(axis=1), (m * nn).sum(axis=1))
+    return out
 
 
 class MBAR:
@@ -1153,6 +1492,9 @@ class MultiStateSamplerAnalyzer:
         # inefficiency): 'numpy' (the loops below) or 'device' (csrc/energy_store.hip)
         if self._kwargs.get('assembly_solver', 'numpy') not in ('numpy', 'device'):
             raise ValueError("analysis_kwargs['assembly_solver'] must be 'numpy' or 'device', not %r" % (self._kwargs['assembly_solver'],))
+        # who evaluates collective variables at the stored frames: 'numpy' (frame_cvs_numpy, no GPU) or 'device' (csrc/frame_cvs.hip)
+        self._check_cv_solver(self._kwargs.get('cv_solver', 'numpy'))
+        self._collective_variables = {}         # {descriptor keys: [n_iterations + 1][n_replicas][n_cv]}, kept until clear()
         # bootstrap uncertainties of MBAR: the number of replicates (0: none), the key of their draws, and the uncertainty the free
         # energies are reported with (None or 'svd': asymptotic; 'bootstrap')
         self._check_bootstrap_option('n_bootstraps', self._kwargs.get('n_bootstraps', 0))
@@ -1220,6 +1562,23 @@ class MultiStateSamplerAnalyzer:
     uncertainty_method = _bootstrap_option('uncertainty_method', None, False)
     del _bootstrap_option
 
+    @staticmethod
+    def _check_cv_solver(value, what="analysis_kwargs['cv_solver']"):
+        if value not in ('numpy', 'device'):
+            raise ValueError("%s must be 'numpy' or 'device', not %r" % (what, value))
+
+    @property
+    def cv_solver(self):
+        """Who evaluates ``get_collective_variables``: 'numpy' or 'device'.  A change forgets the values computed so far."""
+        return self._kwargs.get('cv_solver', 'numpy')
+
+    @cv_solver.setter
+    def cv_solver(self, value):
+        self._check_cv_solver(value)
+        if value != self.cv_solver:
+            self._collective_variables = {}
+        self._kwargs['cv_solver'] = value
+
     unbias_restraint = _restraint_option('unbias_restraint')
     restraint_energy_cutoff = _restraint_option('restraint_energy_cutoff')            # kT, 'auto' or None
     restraint_distance_cutoff = _restraint_option('restraint_distance_cutoff')        # nm, 'auto' or None
@@ -1266,6 +1625,7 @@ class MultiStateSamplerAnalyzer:
         self._unbiased = None
         self._radially_symmetric_restraint_data = None
         self._restraint_energies, self._restraint_distances = {}, {}
+        self._collective_variables = {}
         self._release_energy_store()
 
     def _release_energy_store(self):
@@ -1678,6 +2038,65 @@ class MultiStateSamplerAnalyzer:
         if self.uncertainty_method is None:
             return self.mbar.compute_free_energy_differences()
         return self.mbar.compute_free_energy_differences(uncertainty_method=self.uncertainty_method)
+
+    def get_collective_variables(self, cvs, solver=None):
+        """values [n_iterations + 1][n_replicas][n_cv] f64 (nm, rad) of the collective variables ``cvs`` (DistanceCV, AngleCV,
+        DihedralCV, RMSDCV; atom indices in System numbering) of every replica at every stored iteration: the ``values`` of ``get_pmf``.
+        A single descriptor given bare returns [n_iterations + 1][n_replicas].  The frames are the analysis particles of the store,
+        read in bulk and evaluated in ONE call by ``frame_cvs_numpy`` or on the device (``analysis_kwargs={'cv_solver': 'device'}``, or
+        ``solver`` for this call: csrc/frame_cvs.hip); the masses are those of the first thermodynamic state's System.  A periodic
+        variable takes minimum images under each frame's own stored box; in a store that is not periodic it takes none.  Values are
+        kept per tuple of descriptors until ``clear()``."""
+        bare = isinstance(cvs, (_CentroidCV, RMSDCV))
+        cvs = [cvs] if bare else list(cvs)
+        if solver is None:
+            solver = self.cv_solver
+        else:
+            self._check_cv_solver(solver, what='solver')
+        for v, cv in enumerate(cvs):
+            if not isinstance(cv, (_CentroidCV, RMSDCV)):
+                raise ValueError('variable %d is %r, not a DistanceCV, AngleCV, DihedralCV or RMSDCV' % (v, cv))
+        if not cvs:
+            raise ValueError('no collective variable was given')
+        key = (solver,) + tuple(cv._key() for cv in cvs)
+        if key not in self._collective_variables:
+            n_it, n_replicas = self.n_iterations + 1, self.n_replicas      # (what get_pmf asks of its values)
+            system = self._reporter.read_thermodynamic_states()[0][0].system
+            masses = np.asarray(system.masses, dtype=np.float64)
+            analysis_indices = [int(i) for i in self._reporter.analysis_particle_indices]
+            where = {a: k for k, a in enumerate(analysis_indices)}
+            for v, cv in enumerate(cvs):
+                for a in cv._atoms():
+                    if a >= len(masses):
+                        raise ValueError('variable %d (%s): atom %d is outside the %d particles of the System' % (v, type(cv).__name__, a, len(masses)))
+                    if a not in where:
+                        raise ValueError('variable %d (%s): atom %d is not one of the analysis particles of the store: create the reporter '
+                                         'with analysis_particle_indices that include every atom of the variable' % (v, type(cv).__name__, a))
+            mapped = [cv._remapped(where, len(masses)) for cv in cvs]
+            x, box = self._reporter.read_analysis_positions(range(n_it))     # [n_it][R][n_analysis][3], [n_it][R][3] or None
+            if x.shape[1] != n_replicas:
+                raise ValueError('the store holds the analysis particles of %d replicas but the energies of %d' % (x.shape[1], n_replicas))
+            if box is None and any(cv.periodic for cv in mapped):
+                try:
+                    store_is_periodic = bool(self._reporter.is_periodic)
+                except (TypeError, IndexError, KeyError):                     # (no checkpoint to ask: the analysis store holds no box)
+                    store_is_periodic = False
+                for v, cv in enumerate(mapped):
+                    if cv.periodic and store_is_periodic:
+                        raise ValueError('variable %d (%s) is periodic but the store holds no box vectors of the analysis particles: '
+                                         'give periodic=False' % (v, type(cv).__name__))
+                mapped = [cv._not_periodic() for cv in mapped]
+            pos = x.reshape(n_it * n_replicas, x.shape[2], 3)
+            box = None if box is None else box.reshape(n_it * n_replicas, 3)
+            m = masses[analysis_indices]
+            if solver == 'device':
+                from .._engine import frame_cvs
+                values = frame_cvs(mapped, pos, box, m, device=self._kwargs.get('device', 0), lib_path=self._kwargs.get('lib_path'))
+            else:
+                values = frame_cvs_numpy(mapped, pos, box, m)
+            self._collective_variables[key] = np.asarray(values).reshape(n_it, n_replicas, len(cvs))
+        values = self._collective_variables[key]
+        return values[:, :, 0].copy() if bare else values.copy()
 
     def get_pmf(self, values, edges, state=0, uncertainties='from-lowest', pmf_reference=None):
         """(f_i, df_i, n_i) in kT: the free energy surface at sampled state ``state`` along the coordinate ``values``
