@@ -192,8 +192,23 @@
  * and NaN where any index falls outside its range.  No arguments make the device load outside the block.
  *
  * Not provided: Continuous3DFunction, changing a table or a reference after remd_set_custom_terms, pointangle, pointdihedral, interaction
- * groups, collective variables other than the RMSD, a weighted RMSD, energy parameter derivatives, changing a map or a torsion pair
- * after remd_set_custom_terms.
+ * groups, collective variables other than the RMSD, a weighted RMSD, energy parameter derivatives of nonbonded, collective-variable and
+ * Generalized-Born forces, changing a map or a torsion pair after remd_set_custom_terms.
+ *
+ * Energy parameter derivatives (OpenMM's addEnergyParameterDerivative / getEnergyParameterDerivatives) of the bond, angle, torsion,
+ * external, compound-bond, centroid-bond, donor-acceptor and many-particle kinds: dE/dg of a global column g at the replica's current
+ * positions and its own state's globals, in kJ/mol per unit of the parameter.  The machine is a forward-mode differentiator, so the
+ * same program gives it exactly: in the derivative mode the REMD_CX_GLOBAL push of column g carries the unit partial, every variable
+ * (REMD_CX_VAR, REMD_CX_DISTANCE / ANGLE / DIHEDRAL) is pushed with zero partials, and the result's first partial is dE/dg; piecewise
+ * functions differentiate as the branch taken, a lookup's index contributes 0, REMD_CX_POW takes the logarithm term where the exponent
+ * varies.  remd_set_custom_parameter_derivatives names the n distinct columns and, per force in the descriptors' order, the mask of
+ * those the force declared (bit d: columns[d]); a force contributes to a column only where its bit is set, even if another force's
+ * program names the same global (OpenMM's rule).  remd_get_custom_parameter_derivatives evaluates them: one launch per part of the
+ * term space that holds a served kind, siblings of the u_kl launches with the same staging (centroids, candidate pairs, neighbour
+ * rows), the column loop over the listed derivatives, per-wavefront partials D[r][d][wave] and a fixed-order f64 sum over the
+ * wavefronts.  No floating-point atomics: results are bit-identical from run to run and a column's bits do not depend on which other
+ * columns are listed.  It runs whatever the states' globals are (also where every state carries the same ones).  A many-particle row
+ * over capacity gives NaN in the columns that force declared.  A handle without declared derivatives launches and allocates nothing.
  *
  * Global parameters belong to the handle: every force's program addresses the same n_globals columns, and every state carries one
  * value per column (remd_set_custom_globals).  A term acts in every force evaluation (MD steps, energies, the barostat,
@@ -374,6 +389,14 @@ int  remd_get_custom_energies(remd_handle h, double* out);
 /* out[R_local][total]: the RMSD (nm) of every collective variable of the REMD_CUSTOM_CV forces at the local replicas' current
    positions, in the order of the descriptors and of the variables within one (OpenMM's getCollectiveVariableValues)              */
 int  remd_get_custom_cv_values(remd_handle h, double* out);
+/* the energy parameter derivatives to compute: columns[n] distinct global columns (0 <= n <= REMD_CUSTOM_MAX_GLOBALS; n = 0: none),
+   force_masks[number of descriptors]: bit d set where that force declared columns[d].  Call after remd_set_custom_terms (which
+   forgets them).  Refused: a column out of range or named twice, a mask bit >= n, a mask bit on a REMD_CUSTOM_NONBONDED, _CV, _CMAP or
+   _GB force.                                                                                                                     */
+int  remd_set_custom_parameter_derivatives(remd_handle h, const int32_t* columns, int n, const uint32_t* force_masks);
+/* out[R_local][n]: dE/d(columns[d]) (kJ/mol per unit of the parameter) summed over the forces that declared it, at the local
+   replicas' current positions and own states' globals                                                                           */
+int  remd_get_custom_parameter_derivatives(remd_handle h, double* out);
 
 #ifdef __cplusplus
 }

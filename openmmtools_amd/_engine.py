@@ -128,6 +128,8 @@ FRAME_CVS_EXPORTS = ['remd_frame_cvs']
 CUSTOM_EXPORTS = ['remd_set_custom_terms', 'remd_set_custom_globals', 'remd_set_custom_lrc', 'remd_get_custom_energies']
 # the collective-variable forces of the same header (REMD_CUSTOM_CV): a library built before them lacks the entry point
 CUSTOM_CV_EXPORTS = ['remd_get_custom_cv_values']
+# the energy parameter derivatives of the same header: a library built before them lacks the entry points
+CUSTOM_DERIVATIVE_EXPORTS = ['remd_set_custom_parameter_derivatives', 'remd_get_custom_parameter_derivatives']
 # the GPU-only extension of include/remd_hip_barostat.h (per-axis Monte Carlo barostats), bound the same way
 BAROSTAT_AXIS_EXPORTS = ['remd_set_barostat_axes', 'remd_get_barostat_axis_stats']
 BAROSTAT_ANISOTROPIC, BAROSTAT_MEMBRANE = 1, 2
@@ -297,6 +299,11 @@ def load_library(path=None):
             getattr(lib, name).restype = C.c_int
     if hasattr(lib, 'remd_get_custom_cv_values'):
         lib.remd_get_custom_cv_values.argtypes = [vp, c_double_p]
+    if hasattr(lib, 'remd_set_custom_parameter_derivatives'):
+        lib.remd_set_custom_parameter_derivatives.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_uint32)]
+        lib.remd_get_custom_parameter_derivatives.argtypes = [vp, c_double_p]
+        for name in CUSTOM_DERIVATIVE_EXPORTS:
+            getattr(lib, name).restype = C.c_int
         for name in CUSTOM_CV_EXPORTS:
             getattr(lib, name).restype = C.c_int
     if hasattr(lib, 'remd_set_barostat_axes'):            # include/remd_hip_barostat.h (GPU-only, like the restraints)
@@ -1000,9 +1007,14 @@ class HipEngine:
             self.set_restraints([restraints[k] for k in sorted(restraints)])
         self.n_custom = self.n_custom_globals = self.n_custom_cvs = 0
         self._custom_lrc = None
+        self.custom_derivative_names = []
         custom = desc_dict.get('custom_terms')
         if custom:                                       # custom bond / angle / torsion / external forces (custom_expr.py; csrc/custom_terms.hip)
-            self.set_custom_terms([custom[k] for k in sorted(custom)])
+            terms = [custom[k] for k in sorted(custom)]
+            self.set_custom_terms(terms)
+            if terms[0].get('derivative_columns') is not None and len(terms[0]['derivative_columns']):
+                self.set_custom_parameter_derivatives(terms[0]['derivative_columns'], [t.get('derivative_mask', 0) for t in terms],
+                                                      terms[0]['derivative_names'])
 
     def set_virtual_sites(self, sites):
         """The site table of the system (system.system_to_desc's 'virtual_sites': site, kind, parent, weight); after set_system,
@@ -1166,6 +1178,37 @@ class HipEngine:
         fn = self._custom_entry('remd_get_custom_energies')
         out = np.zeros((self.R, self.n_custom))
         self._check(fn(self.h, _dp(out)), 'remd_get_custom_energies')
+        return out
+
+    def _custom_derivative_entry(self, name):
+        if not hasattr(self.lib, name):
+            raise NotImplementedError('%s: this build of the engine library has no energy parameter derivatives of custom forces '
+                                      '(addEnergyParameterDerivative: the entry points of include/remd_hip_custom.h are GPU-only)' % name)
+        return getattr(self.lib, name)
+
+    def set_custom_parameter_derivatives(self, columns, force_masks, names=None):
+        """The energy parameter derivatives the custom forces declared (custom_expr.custom_terms_desc): the distinct global columns and,
+        per custom force, the mask of those it declared; after set_custom_terms, which forgets them."""
+        fn = self._custom_derivative_entry('remd_set_custom_parameter_derivatives')
+        columns = np.ascontiguousarray(columns, dtype=np.int32).reshape(-1)
+        masks = np.ascontiguousarray(force_masks, dtype=np.uint32).reshape(-1)
+        if len(masks) != self.n_custom:
+            raise ValueError('set_custom_parameter_derivatives: one mask per custom force (%d, not %d)' % (self.n_custom, len(masks)))
+        self._check(fn(self.h, columns.ctypes.data_as(C.POINTER(C.c_int32)), len(columns), masks.ctypes.data_as(C.POINTER(C.c_uint32))),
+                    'remd_set_custom_parameter_derivatives')
+        self.custom_derivative_names = [str(n) for n in names] if names is not None else ['column %d' % c for c in columns]
+
+    def custom_energy_parameter_derivatives(self):
+        """[R_local][n_derivatives]: dE/dparameter (kJ/mol per unit of the parameter) of the global parameters the custom forces declared
+        with addEnergyParameterDerivative, summed over the forces that declared each, at the current positions and each replica's own
+        state's globals (OpenMM's State.getEnergyParameterDerivatives); the columns are ``custom_derivative_names``."""
+        fn = self._custom_derivative_entry('remd_get_custom_parameter_derivatives')
+        names = getattr(self, 'custom_derivative_names', [])
+        if not names:
+            raise ValueError('custom_energy_parameter_derivatives: no custom force of the system declares an energy parameter derivative '
+                             '(addEnergyParameterDerivative)')
+        out = np.zeros((self.R, len(names)))
+        self._check(fn(self.h, _dp(out)), 'remd_get_custom_parameter_derivatives')
         return out
 
     def _custom_cv_entry(self, name):

@@ -32,6 +32,9 @@ struct cst_tables : cst_plan {
     dev_array<double> d_E;             // [R][nf]
     dev_array<double> d_Ewave;         // [R][total_pad / 64]
     dev_array<double> d_D;             // [R][K][total_pad / 64] u_kl partials
+    dev_array<int> d_dcols; dev_array<unsigned> d_dmask;   // the declared energy parameter derivatives (cst_plan::dcols, dmask); empty: none
+    dev_array<double> d_dD;            // [R][n_derivatives][total_pad / 64] their partials; allocated by the first remd_get_custom_parameter_derivatives
+    dev_array<double> d_dOut;          // [R][n_derivatives] dE/dglobal
     dev_array<double> d_C;             // [R][n_groups][3] centroids
     dev_array<double> d_G;             // [R][centroid slots][REMD_CUSTOM_MAX_PARTICLES][3] dE / d centroid
     dev_array<double> d_W;             // [R][n_cv][16]: RMSD, "no force" flag, centroid, rotation, dE/dRMSD (custom_cv.hip)
@@ -185,11 +188,15 @@ __device__ __forceinline__ double cst_lookup3d(const double* __restrict__ B, dou
 
 // the program of force f at term t (lane's own) under the globals g (wave-uniform); the result's partials are dE/dvariable
 // (GEOM: dE/d(x, y, z) of particle `seed`; x0, x1, x2 are not read)
-template <bool GEOM>
+// DPAR (energy parameter derivatives, remd_get_custom_parameter_derivatives): the differentiated quantity is global column `dcol`
+// instead of the variables -- that REMD_CX_GLOBAL push carries the unit partial in component a, every variable is pushed with zero
+// partials (GEOM: the caller passes seed = -1, so coordinates and functions of particles are), and the result's a is dE/dglobal.
+// A compile-time switch: the instantiations without it are the code they were.
+template <bool GEOM, bool DPAR = false>
 __device__ __forceinline__ cx cst_eval(const cst_force& f, const int2* __restrict__ prog, const double* __restrict__ consts,
                                        const double* __restrict__ par, int t, const double* __restrict__ g, double x0, double x1,
                                        double x2, double Lx, double Ly, double Lz, cst_slot* S, int lane,
-                                       const cst_pos* X = nullptr, int seed = -1)
+                                       const cst_pos* X = nullptr, int seed = -1, int dcol = -1)
 {
     int sp = 0;
     for (int pc = 0; pc < f.n_prog; ++pc) {
@@ -203,11 +210,13 @@ __device__ __forceinline__ cx cst_eval(const cst_force& f, const int2* __restric
                 const int q = arg / 3, c = arg - 3 * q;
                 const bool on = q == seed;
                 cx_st(S, sp++, lane, cx{X[q][c][lane], on && c == 0 ? 1.0 : 0.0, on && c == 1 ? 1.0 : 0.0, on && c == 2 ? 1.0 : 0.0});
-            } else
+            } else if (DPAR)
+                cx_st(S, sp++, lane, cx{arg == 0 ? x0 : arg == 1 ? x1 : x2, 0.0, 0.0, 0.0});
+            else
                 cx_st(S, sp++, lane, cx{arg == 0 ? x0 : arg == 1 ? x1 : x2, arg == 0 ? 1.0 : 0.0, arg == 1 ? 1.0 : 0.0, arg == 2 ? 1.0 : 0.0});
             break;
         case REMD_CX_PARAM:  cx_st(S, sp++, lane, cx{par[f.par0 + (size_t)arg * f.npad + t], 0.0, 0.0, 0.0}); break;
-        case REMD_CX_GLOBAL: cx_st(S, sp++, lane, cx{g[arg], 0.0, 0.0, 0.0}); break;
+        case REMD_CX_GLOBAL: cx_st(S, sp++, lane, cx{g[arg], DPAR && arg == dcol ? 1.0 : 0.0, 0.0, 0.0}); break;
         case REMD_CX_ADD: case REMD_CX_SUB: case REMD_CX_MUL: case REMD_CX_DIV: case REMD_CX_POW: case REMD_CX_ATAN2:
         case REMD_CX_MIN: case REMD_CX_MAX: case REMD_CX_TABLE2D: case REMD_CX_LOOKUP2D: {
             const cx x = cx_ld(S, sp - 2, lane), y = cx_ld(S, sp - 1, lane);
@@ -310,9 +319,11 @@ __device__ __forceinline__ double cst_wave_sum(double v)
 // launches of remd_custom_forces / remd_custom_ukl
 void remd_custom_compound_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
 void remd_custom_compound_ukl(remd_ctx* h, cst_tables& t);
+void remd_custom_compound_dpar(remd_ctx* h, cst_tables& t);     // (the *_dpar launches: D[r][d][w] of the declared energy parameter derivatives, on the main stream)
 // custom_centroid.hip: the same for the centroid forces' wavefronts (the part CST_CENTROID): centroids, bonds, spread
 void remd_custom_centroid_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
 void remd_custom_centroid_ukl(remd_ctx* h, cst_tables& t);
+void remd_custom_centroid_dpar(remd_ctx* h, cst_tables& t);
 // custom_cv.hip: the same for the collective-variable forces' wavefronts (the part CST_CV): superposition, expression, spread
 void remd_custom_cv_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
 void remd_custom_cv_ukl(remd_ctx* h, cst_tables& t);
@@ -328,10 +339,12 @@ void remd_custom_nonbonded_lrc_ukl(remd_ctx* h, cst_tables& t, double* d_rows);
 // custom_hbond.hip: the same for the donor-acceptor forces' tiles (the part CST_HBOND)
 void remd_custom_hbond_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
 void remd_custom_hbond_ukl(remd_ctx* h, cst_tables& t);
+void remd_custom_hbond_dpar(remd_ctx* h, cst_tables& t);
 // custom_manyparticle.hip: the same for the many-particle forces' central particles (the part CST_MANYPARTICLE, the last one): the
 // neighbour rows, then the sets
 void remd_custom_manyparticle_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
 void remd_custom_manyparticle_ukl(remd_ctx* h, cst_tables& t);
+void remd_custom_manyparticle_dpar(remd_ctx* h, cst_tables& t);
 // custom_gb.hip: the same for the Generalized-Born forces (the part CST_GB, the last one): five launches per force.  They carry no
 // globals, so they have no u_kl launch
 void remd_custom_gb_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);

@@ -70,6 +70,9 @@ struct cst_plan {
     int n_cv = 0;                      // the collective variables of all such forces (0: no such force, none of the cv members below holds anything)
     int n_groups = 0;                  // the groups of all centroid forces (0: no centroid force, none of the grp / ref members below holds anything)
     bool uniform = true;               // every state carries the same globals: no u_kl share
+    // energy parameter derivatives (remd_set_custom_parameter_derivatives): the distinct global columns asked for, and per force the
+    // mask of those it declared (bit d: column dcols[d]); a force contributes to a derivative only where its bit is set.  Empty: none.
+    std::vector<int> dcols; std::vector<unsigned> dmask;
     std::vector<cst_force> F; std::vector<int> wave_force;
     std::vector<int> atoms;            // [max(4, most particles per bond)][total_pad]; a padding slot repeats the force's last term
     std::vector<double> par, consts, glob, defaults;

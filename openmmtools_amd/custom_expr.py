@@ -1022,27 +1022,42 @@ def custom_terms_desc(forces, masses=None, box_vectors=None):
         raise NotImplementedError('custom forces in several force groups (%s): every custom force of a System must sit in one (%s)'
                                   % (', '.join(str(g) for g in groups), ', '.join('%s in %d' % (type(f).__name__, f.getForceGroup()) for f in forces)))
     columns = {n: i for i, n in enumerate(names)}
+    # energy parameter derivatives (addEnergyParameterDerivative): the distinct global columns in the order of their first declaration
+    # over the forces, and per force the mask of those it declared (bit d: derivative_columns[d]) -- a force contributes to a
+    # parameter's derivative only where it declared it, even when another force's expression names the same global (OpenMM's rule)
+    derivative_names = []
+    for f in forces:
+        for name in getattr(f, '_derivatives', ()):
+            if name not in derivative_names:
+                derivative_names.append(name)
+    derivative_columns = np.array([columns[n] for n in derivative_names], dtype=np.int32)
+
+    def finish(entry, f):
+        """the derivative keys of an emitted entry: the System's list (the same in every entry) and this force's mask"""
+        entry.update(derivative_names=list(derivative_names), derivative_columns=derivative_columns.copy(),
+                     derivative_mask=sum(1 << derivative_names.index(n) for n in getattr(f, '_derivatives', ())))
+        return entry
     out = {}
     for k, f in enumerate(forces):
         if isinstance(f, _system.CustomGBForce):                            # the general path of a CustomGBForce (custom_gb.py; csrc/custom_gb.hip)
             from .custom_gb import compile_custom_gb
-            out['%03d' % len(out)] = compile_custom_gb(f, None if masses is None else len(masses), box_vectors, names, defaults)
+            out['%03d' % len(out)] = finish(compile_custom_gb(f, None if masses is None else len(masses), box_vectors, names, defaults), f)
             continue
         cls = [c for c in KIND_OF_CLASS if c in [b.__name__ for b in type(f).__mro__]][0]
         kind = KIND_OF_CLASS[cls]
         if kind == KIND_CMAP:
             entry = _cmap_entry(f, names, defaults, None if masses is None else len(masses))
             if entry is not None:
-                out['%03d' % len(out)] = entry
+                out['%03d' % len(out)] = finish(entry, f)
             continue
         where = '%s (energy %r)' % (cls, f.getEnergyFunction())
         if kind == KIND_HBOND:
             entry = _hbond_entry(f, cls, where, names, defaults, columns, masses, box_vectors)
             if entry is not None:
-                out['%03d' % len(out)] = entry
+                out['%03d' % len(out)] = finish(entry, f)
             continue
         if kind == KIND_MANYPARTICLE:
-            out['%03d' % len(out)] = _manyparticle_entry(f, cls, where, names, defaults, columns, masses, box_vectors)
+            out['%03d' % len(out)] = finish(_manyparticle_entry(f, cls, where, names, defaults, columns, masses, box_vectors), f)
             continue
         per_term = _per_term_names(f)
         if kind == KIND_NONBONDED and len(per_term) > MAX_PAIR_PARAMS:
@@ -1075,14 +1090,14 @@ def custom_terms_desc(forces, masses=None, box_vectors=None):
             raise NotImplementedError('%s: the long-range correction of an expression that calls a tabulated function (%s)'
                                       % (where, ', '.join(repr(n) for n, _ in tabulated)))
         if kind == KIND_NONBONDED:
-            out['%03d' % len(out)] = _nonbonded_entry(f, cls, prog, names, defaults, per_term, masses, box_vectors)
+            out['%03d' % len(out)] = finish(_nonbonded_entry(f, cls, prog, names, defaults, per_term, masses, box_vectors), f)
             continue
         if kind == KIND_CV:
             # one term without atoms or parameters of its own: the variables are the RMSDs (VAR 0 ... 2, CustomExternalForce's operands)
-            out['%03d' % len(out)] = dict(kind=kind, atoms=np.zeros((1, 0), dtype=np.int32), params=np.zeros((1, 0)), global_names=list(names),
-                                          global_defaults=np.array(defaults, dtype=np.float64), program=prog['program'], consts=prog['consts'],
-                                          stack_depth=prog['stack_depth'], periodic=0, force_group=int(f.getForceGroup()),
-                                          energy=f.getEnergyFunction(), cv_names=list(cv[0]), cv_offsets=cv[1], cv_atoms=cv[2], cv_reference=cv[3])
+            out['%03d' % len(out)] = finish(dict(kind=kind, atoms=np.zeros((1, 0), dtype=np.int32), params=np.zeros((1, 0)), global_names=list(names),
+                                                 global_defaults=np.array(defaults, dtype=np.float64), program=prog['program'], consts=prog['consts'],
+                                                 stack_depth=prog['stack_depth'], periodic=0, force_group=int(f.getForceGroup()),
+                                                 energy=f.getEnergyFunction(), cv_names=list(cv[0]), cv_offsets=cv[1], cv_atoms=cv[2], cv_reference=cv[3]), f)
             continue
         atoms, params = f._term_arrays()
         if len(atoms) == 0:
@@ -1100,6 +1115,7 @@ def custom_terms_desc(forces, masses=None, box_vectors=None):
             out['%03d' % (len(out) - 1)]['n_particles'] = n_particles
         if kind == KIND_CENTROID:
             out['%03d' % (len(out) - 1)].update(group_offsets=groups[0], group_atoms=groups[1], group_weights=groups[2])
+        finish(out['%03d' % (len(out) - 1)], f)
     return out
 
 

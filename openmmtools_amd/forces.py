@@ -180,6 +180,13 @@ class RadiallySymmetricRestraintForce(Force):
     def _create_bond(self, bond_parameter_values, restrained_atom_indices1, restrained_atom_indices2):
         raise NotImplementedError()
 
+    def addEnergyParameterDerivative(self, name):
+        raise NotImplementedError('%s: energy parameter derivatives (addEnergyParameterDerivative %r) of a restraint force are not '
+                                  'supported (csrc/restraints.hip has no such path)' % (type(self).__name__, name))
+
+    def getNumEnergyParameterDerivatives(self):
+        return 0
+
     @property
     def restraint_parameters(self):
         """OrderedDict: The restraint parameters in dictionary form."""

@@ -333,6 +333,8 @@ class _CustomForce(Force):
         self._per_bond = []                   # per-term parameter names (per bond / angle / torsion / particle)
         self._periodic = False
         self._functions = []                  # (name, function)
+        self._derivatives = []                # global parameter names (addEnergyParameterDerivative)
+        self._in_engine = None                # id(self) once system_to_desc has read the force (a copy is another object and starts afresh)
 
     def getEnergyFunction(self):
         return self._energy
@@ -355,6 +357,27 @@ class _CustomForce(Force):
 
     def setGlobalParameterDefaultValue(self, index, defaultValue):
         self._globals[index][1] = float(defaultValue)
+
+    def addEnergyParameterDerivative(self, name):
+        """openmm's addEnergyParameterDerivative: ask for dE/d(global parameter ``name``) of this force
+        (HipEngine.custom_energy_parameter_derivatives).  Only a force that declared a parameter contributes to its derivative."""
+        cls, name = type(self).__name__, str(name)
+        if getattr(self, '_in_engine', None) == id(self):
+            raise NotImplementedError('%s: adding an energy parameter derivative (%r) after set_system is not supported: the engine keeps '
+                                      'the declarations it was given, build the states again' % (cls, name))
+        if name not in [g[0] for g in self._globals]:
+            raise ValueError('%s: addEnergyParameterDerivative(%r): the force has no global parameter of that name (%s)'
+                             % (cls, name, ', '.join(g[0] for g in self._globals) or 'it has none'))
+        if name in self._derivatives:
+            raise ValueError('%s: addEnergyParameterDerivative(%r): the derivative with respect to that parameter was already added' % (cls, name))
+        self._derivatives.append(name)
+        return len(self._derivatives) - 1
+
+    def getNumEnergyParameterDerivatives(self):
+        return len(getattr(self, '_derivatives', ()))
+
+    def getEnergyParameterDerivativeName(self, index):
+        return self._derivatives[index]
 
     def addPerBondParameter(self, name):
         self._per_bond.append(str(name))
@@ -1198,6 +1221,13 @@ class CustomGBForce(Force):
     def setCutoffDistance(self, d): self._cutoff = float(d)
     def usesPeriodicBoundaryConditions(self): return self._method == CustomGBForce.CutoffPeriodic
 
+    def addEnergyParameterDerivative(self, name):
+        raise NotImplementedError('CustomGBForce: energy parameter derivatives (addEnergyParameterDerivative %r) are not supported: the '
+                                  'global parameters of a CustomGBForce are folded into its constants' % (name,))
+
+    def getNumEnergyParameterDerivatives(self):
+        return 0
+
     def updateParametersInContext(self, context=None):
         raise NotImplementedError('CustomGBForce: changing particles, exclusions or functions after set_system (updateParametersInContext) is '
                                   'not supported: the engine keeps the tables it was given, build the states again')
@@ -1672,6 +1702,9 @@ def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
         if _is_custom_term(f):
             custom.append(f)
         elif isinstance(f, CustomExternalForce):
+            if getattr(f, '_derivatives', None):
+                raise NotImplementedError('CustomExternalForce: energy parameter derivatives (addEnergyParameterDerivative %r) of the built-in '
+                                          'harmonic oscillator form are not supported' % (f._derivatives[0],))
             d['n_ext'] = len(f.particles)
             d['ext_atoms'] = np.array(f.particles, dtype=np.int32)
             d['ext_K'] = f.globals['testsystems_HarmonicOscillator_K']
@@ -1696,6 +1729,9 @@ def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
         elif isinstance(f, (MonteCarloAnisotropicBarostat, MonteCarloMembraneBarostat)):
             pass        # no energy: the ThermodynamicState reads it (states.py) and the sampler hands it to the engine's barostat
         elif _is_restraint(f):
+            if getattr(f, '_derivatives', None):
+                raise NotImplementedError('%s: energy parameter derivatives (addEnergyParameterDerivative %r) of a restraint force are not '
+                                          'supported' % (type(f).__name__, f._derivatives[0]))
             from .forces import restraint_terms
             restraints.append(restraint_terms(f, system.masses))
         else:
@@ -1810,6 +1846,9 @@ def system_to_desc(system, box=None, ewald_split=None, min_edge=None):
     if custom:
         from .custom_expr import custom_terms_desc
         terms = custom_terms_desc(custom, system.masses, box_vectors=system.getDefaultPeriodicBoxVectors())
+        for f in custom:                     # (what an engine is given does not follow a later addEnergyParameterDerivative)
+            if hasattr(f, '_derivatives'):
+                f._in_engine = id(f)
         if terms:
             from .custom_expr import check_cv_molecules, check_hbond_molecules
             check_cv_molecules(d, terms)
@@ -1856,6 +1895,12 @@ def _functions_from_openmm(f, g, cls_name):
         g.addTabulatedFunction(name, fn)
 
 
+def _derivatives_from_openmm(f, g):
+    """the energy parameter derivatives ``f`` declares, declared on ``g`` (an object without the getters declares none)"""
+    for i in range(f.getNumEnergyParameterDerivatives() if hasattr(f, 'getNumEnergyParameterDerivatives') else 0):
+        g.addEnergyParameterDerivative(f.getEnergyParameterDerivativeName(i))
+
+
 def manyparticle_force_from_openmm(f):
     """An openmm.CustomManyParticleForce as the class of the same name here; by the object's getters, so that no OpenMM is needed.
     The cutoff may carry a unit (anything with value_in_unit_system) or be a number in nm; an empty type filter means none."""
@@ -1881,6 +1926,7 @@ def manyparticle_force_from_openmm(f):
         types = list(f.getTypeFilter(s))
         if types:
             g.setTypeFilter(s, types)
+    _derivatives_from_openmm(f, g)
     g.setForceGroup(int(f.getForceGroup()))
     return g
 
@@ -1911,6 +1957,7 @@ def gb_force_from_openmm(f):
         from .unit import to_md
         cutoff = to_md(cutoff)
     g.setCutoffDistance(cutoff)
+    _derivatives_from_openmm(f, g)          # (a CustomGBForce refuses them by name)
     g.setForceGroup(int(f.getForceGroup()))
     return g
 
@@ -1941,6 +1988,7 @@ def hbond_force_from_openmm(f):
         from .unit import to_md
         cutoff = to_md(cutoff)
     g.setCutoffDistance(cutoff)
+    _derivatives_from_openmm(f, g)
     g.setForceGroup(int(f.getForceGroup()))
     return g
 
