@@ -210,6 +210,15 @@
  * columns are listed.  It runs whatever the states' globals are (also where every state carries the same ones).  A many-particle row
  * over capacity gives NaN in the columns that force declared.  A handle without declared derivatives launches and allocates nothing.
  *
+ * remd_get_custom_parameter_derivatives_at_states evaluates the same derivatives under the globals of every state l of
+ * remd_set_states (unsampled ones included) at each local replica's current positions: out[r][l][d], what thermodynamic integration
+ * and the MBAR expectation of du/dlambda at every state need.  The same launches with a compile-time switch: the staging (centroids,
+ * candidate queues, neighbour rows, the particles of a term) runs once per call and the loop over the states sits inside it, the
+ * partials are D[r][l][d][wave] in a buffer of R K n (wavefronts) doubles that the first such call allocates, and the same
+ * fixed-order sum.  out[r][label_r][d] is bit-identical to remd_get_custom_parameter_derivatives' out[r][d], two states with
+ * bit-identical globals give bit-identical results, and a many-particle row over capacity gives NaN at every l.  A handle that never
+ * makes the call allocates and launches nothing for it.
+ *
  * Global parameters belong to the handle: every force's program addresses the same n_globals columns, and every state carries one
  * value per column (remd_set_custom_globals).  A term acts in every force evaluation (MD steps, energies, the barostat,
  * minimisation); the u_kl rows get beta_l (E_r(g_l) - E_r(g_own(r))) for every state l, E_r(g) the sum of all custom terms at
@@ -397,6 +406,9 @@ int  remd_set_custom_parameter_derivatives(remd_handle h, const int32_t* columns
 /* out[R_local][n]: dE/d(columns[d]) (kJ/mol per unit of the parameter) summed over the forces that declared it, at the local
    replicas' current positions and own states' globals                                                                           */
 int  remd_get_custom_parameter_derivatives(remd_handle h, double* out);
+/* out[R_local][K][n]: dE/d(columns[d]) (kJ/mol per unit of the parameter), summed over the forces that declared it, at the local
+   replicas' current positions under the globals of state l, for every state l of remd_set_states (unsampled ones included) */
+int  remd_get_custom_parameter_derivatives_at_states(remd_handle h, double* out);
 
 #ifdef __cplusplus
 }

@@ -130,6 +130,8 @@ CUSTOM_EXPORTS = ['remd_set_custom_terms', 'remd_set_custom_globals', 'remd_set_
 CUSTOM_CV_EXPORTS = ['remd_get_custom_cv_values']
 # the energy parameter derivatives of the same header: a library built before them lacks the entry points
 CUSTOM_DERIVATIVE_EXPORTS = ['remd_set_custom_parameter_derivatives', 'remd_get_custom_parameter_derivatives']
+# the same at every state's globals (thermodynamic integration): a library built before it lacks the entry point
+CUSTOM_DERIVATIVE_STATES_EXPORTS = ['remd_get_custom_parameter_derivatives_at_states']
 # the GPU-only extension of include/remd_hip_barostat.h (per-axis Monte Carlo barostats), bound the same way
 BAROSTAT_AXIS_EXPORTS = ['remd_set_barostat_axes', 'remd_get_barostat_axis_stats']
 BAROSTAT_ANISOTROPIC, BAROSTAT_MEMBRANE = 1, 2
@@ -304,6 +306,9 @@ def load_library(path=None):
         lib.remd_get_custom_parameter_derivatives.argtypes = [vp, c_double_p]
         for name in CUSTOM_DERIVATIVE_EXPORTS:
             getattr(lib, name).restype = C.c_int
+    if hasattr(lib, 'remd_get_custom_parameter_derivatives_at_states'):
+        lib.remd_get_custom_parameter_derivatives_at_states.argtypes = [vp, c_double_p]
+        lib.remd_get_custom_parameter_derivatives_at_states.restype = C.c_int
         for name in CUSTOM_CV_EXPORTS:
             getattr(lib, name).restype = C.c_int
     if hasattr(lib, 'remd_set_barostat_axes'):            # include/remd_hip_barostat.h (GPU-only, like the restraints)
@@ -1209,6 +1214,20 @@ class HipEngine:
                              '(addEnergyParameterDerivative)')
         out = np.zeros((self.R, len(names)))
         self._check(fn(self.h, _dp(out)), 'remd_get_custom_parameter_derivatives')
+        return out
+
+    def custom_energy_parameter_derivatives_at_states(self):
+        """[R_local][K][n_derivatives]: the same derivatives (kJ/mol per unit of the parameter) at the current positions under the globals
+        of every thermodynamic state, unsampled ones included -- ``[r][label_r]`` is bit-identical to
+        ``custom_energy_parameter_derivatives()[r]``; the columns are ``custom_derivative_names``.  One call: whatever depends on the
+        positions alone (centroids, candidate pairs, neighbour rows) is computed once for all K states."""
+        fn = self._custom_derivative_entry('remd_get_custom_parameter_derivatives_at_states')
+        names = getattr(self, 'custom_derivative_names', [])
+        if not names:
+            raise ValueError('custom_energy_parameter_derivatives_at_states: no custom force of the system declares an energy parameter '
+                             'derivative (addEnergyParameterDerivative)')
+        out = np.zeros((self.R, self.K, len(names)))
+        self._check(fn(self.h, _dp(out)), 'remd_get_custom_parameter_derivatives_at_states')
         return out
 
     def _custom_cv_entry(self, name):

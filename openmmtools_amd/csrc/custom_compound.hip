@@ -105,12 +105,14 @@ void custom_compound_ukl_kernel(int total_pad, int w0, int waves, const cst_forc
 
 // energy parameter derivatives, same grid: D[r][d][w] = sum over the wavefront's bonds of dE/dglobal(dcols[d]) under the replica's own
 // globals (custom_dpar_kernel of custom_terms.hip: the machine seeded at the column, no particle seeded)
+// STATES: under the globals of every state l in turn, D[r][l][d][w], behind the one load of the particles
+template <bool STATES>
 __global__ __launch_bounds__(64)
 void custom_compound_dpar_kernel(int total_pad, int w0, int waves, const cst_force* __restrict__ F, const int* __restrict__ wave_force,
                                  const int* __restrict__ atoms, const double* __restrict__ par, const int2* __restrict__ prog,
                                  const double* __restrict__ consts, const double* __restrict__ glob, int ng, int nd,
                                  const int* __restrict__ dcols, const unsigned* __restrict__ dmask, const int64_t* __restrict__ labels,
-                                 int r_begin, int Npad, const float4* __restrict__ pos, const float* __restrict__ box, double* __restrict__ D)
+                                 int r_begin, int Npad, const float4* __restrict__ pos, const float* __restrict__ box, double* __restrict__ D, int K)
 {
     __shared__ cst_slot S[REMD_CUSTOM_MAX_STACK];
     __shared__ cst_pos X[REMD_CUSTOM_MAX_PARTICLES];
@@ -121,16 +123,19 @@ void custom_compound_dpar_kernel(int total_pad, int w0, int waves, const cst_for
     const float4* P = pos + (size_t)r * Npad;
     const bool pbc = f.periodic != 0;
     const double Lx = pbc ? box[4 * r] : 0.0, Ly = pbc ? box[4 * r + 1] : 0.0, Lz = pbc ? box[4 * r + 2] : 0.0;
-    const double* g = glob + (size_t)labels[r_begin + r] * ng;
     cmp_load(f, atoms, total_pad, s, P, X, lane);
     const bool active = t < f.n_terms;
-    for (int d = 0; d < nd; ++d) {
-        double v = 0.0;
-        if ((mask >> d) & 1u) {
-            const cx e = cst_eval<true, true>(f, prog, consts, par, t, g, 0.0, 0.0, 0.0, Lx, Ly, Lz, S, lane, X, -1, dcols[d]);
-            v = cst_wave_sum(active ? e.a : 0.0);
+    const int nl = STATES ? K : 1;
+    for (int l = 0; l < nl; ++l) {
+        const double* g = glob + (size_t)(STATES ? l : labels[r_begin + r]) * ng;
+        for (int d = 0; d < nd; ++d) {
+            double v = 0.0;
+            if ((mask >> d) & 1u) {
+                const cx e = cst_eval<true, true>(f, prog, consts, par, t, g, 0.0, 0.0, 0.0, Lx, Ly, Lz, S, lane, X, -1, dcols[d]);
+                v = cst_wave_sum(active ? e.a : 0.0);
+            }
+            if (lane == 0) D[(((size_t)r * nl + l) * nd + d) * waves + w] = v;
         }
-        if (lane == 0) D[((size_t)r * nd + d) * waves + w] = v;
     }
 }
 
@@ -157,10 +162,16 @@ void remd_custom_compound_ukl(remd_ctx* h, cst_tables& t)
                        t.d_D);
 }
 
-void remd_custom_compound_dpar(remd_ctx* h, cst_tables& t)
+void remd_custom_compound_dpar(remd_ctx* h, cst_tables& t, bool states)
 {
     const int waves = t.total_pad / 64, w0 = t.begin(CST_COMPOUND);
-    hipLaunchKernelGGL(custom_compound_dpar_kernel, dim3(t.end(CST_COMPOUND) - w0, h->R), dim3(64), 0, h->stream, t.total_pad, w0, waves, t.d_F, t.d_wave_force,
-                       t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, (int)t.dcols.size(), t.d_dcols, t.d_dmask, h->d_labels, h->r_begin,
-                       h->Npad, h->d_pos, h->d_box, t.d_dD);
+    const dim3 grid(t.end(CST_COMPOUND) - w0, h->R);
+    if (states)
+        hipLaunchKernelGGL(custom_compound_dpar_kernel<true>, grid, dim3(64), 0, h->stream, t.total_pad, w0, waves, t.d_F, t.d_wave_force,
+                           t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, (int)t.dcols.size(), t.d_dcols, t.d_dmask, h->d_labels, h->r_begin,
+                           h->Npad, h->d_pos, h->d_box, t.d_dDK, h->K);
+    else
+        hipLaunchKernelGGL(custom_compound_dpar_kernel<false>, grid, dim3(64), 0, h->stream, t.total_pad, w0, waves, t.d_F, t.d_wave_force,
+                           t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, (int)t.dcols.size(), t.d_dcols, t.d_dmask, h->d_labels, h->r_begin,
+                           h->Npad, h->d_pos, h->d_box, t.d_dD, 1);
 }

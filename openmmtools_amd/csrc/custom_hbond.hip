@@ -200,13 +200,16 @@ void custom_hbond_ukl_kernel(int w0, int waves, const cst_force* __restrict__ F,
 }
 
 // energy parameter derivatives, same grid and candidate stage: D[r][d][w] = sum over the tile's pairs of dE/dglobal(dcols[d]) under the
-// replica's own globals, the machine seeded at the column and at no particle; the batches added in their order by lane 0 alone
+// replica's own globals, the machine seeded at the column and at no particle; the batches added in their order by lane 0 alone.
+// STATES: under the globals of every state l in turn, D[r][l][d][w]; the candidate queue and each batch's staging run once, the
+// states loop inside a batch, so a (state, column)'s batches are added in the order of the own-state kernel
+template <bool STATES>
 __global__ __launch_bounds__(64)
 void custom_hbond_dpar_kernel(int w0, int waves, const cst_force* __restrict__ F, const int* __restrict__ wave_force, const int* __restrict__ hb_atoms,
                               const double* __restrict__ par, const int2* __restrict__ prog, const double* __restrict__ consts,
                               const double* __restrict__ glob, int ng, int nd, const int* __restrict__ dcols, const unsigned* __restrict__ dmask,
                               const int* __restrict__ excl_off, const int* __restrict__ excl_atoms, const int64_t* __restrict__ labels,
-                              int r_begin, int Npad, const float4* __restrict__ pos, const float* __restrict__ box, double* __restrict__ D)
+                              int r_begin, int Npad, const float4* __restrict__ pos, const float* __restrict__ box, double* __restrict__ D, int K)
 {
     __shared__ cst_slot S[REMD_CUSTOM_MAX_STACK];
     __shared__ cst_pos X[6];
@@ -216,20 +219,23 @@ void custom_hbond_dpar_kernel(int w0, int waves, const cst_force* __restrict__ F
     const int w = w0 + blockIdx.x, r = blockIdx.y, lane = threadIdx.x;
     const cst_force f = F[wave_force[w]];
     const unsigned mask = dmask[wave_force[w]];
-    if (lane == 0) for (int d = 0; d < nd; ++d) D[((size_t)r * nd + d) * waves + w] = 0.0;
+    const int nl = STATES ? K : 1;
+    if (lane == 0) for (int ld = 0; ld < nl * nd; ++ld) D[((size_t)r * nl * nd + ld) * waves + w] = 0.0;
     if (mask == 0u) return;                                  // (wave-uniform: the force declared no derivative)
     cst_force fl = f; fl.par0 = 0; fl.npad = 64;
     const chb_tile_ctx c = chb_tile(f, w, lane, box, r);
     const double Lx = c.pbc ? c.Lx : 0.0, Ly = c.pbc ? c.Ly : 0.0, Lz = c.pbc ? c.Lz : 0.0;
-    const double* g = glob + (size_t)labels[r_begin + r] * ng;
     const float4* P = pos + (size_t)r * Npad;
     chb_pairs(f, c, P, hb_atoms, excl_off, excl_atoms, xi, xj, queue, [&](int entry, bool on) {
         chb_stage(f, c, entry, P, hb_atoms, par, X, PAR);
-        for (int d = 0; d < nd; ++d) {
-            if (!((mask >> d) & 1u)) continue;
-            const cx e = cst_eval<true, true>(fl, prog, consts, &PAR[0][0], lane, g, 0.0, 0.0, 0.0, Lx, Ly, Lz, S, lane, X, -1, dcols[d]);
-            const double v = cst_wave_sum(on ? e.a : 0.0);
-            if (lane == 0) D[((size_t)r * nd + d) * waves + w] += v;
+        for (int l = 0; l < nl; ++l) {
+            const double* g = glob + (size_t)(STATES ? l : labels[r_begin + r]) * ng;
+            for (int d = 0; d < nd; ++d) {
+                if (!((mask >> d) & 1u)) continue;
+                const cx e = cst_eval<true, true>(fl, prog, consts, &PAR[0][0], lane, g, 0.0, 0.0, 0.0, Lx, Ly, Lz, S, lane, X, -1, dcols[d]);
+                const double v = cst_wave_sum(on ? e.a : 0.0);
+                if (lane == 0) D[(((size_t)r * nl + l) * nd + d) * waves + w] += v;
+            }
         }
     });
 }
@@ -257,10 +263,16 @@ void remd_custom_hbond_ukl(remd_ctx* h, cst_tables& t)
                        h->d_pos, h->d_box, t.d_D);
 }
 
-void remd_custom_hbond_dpar(remd_ctx* h, cst_tables& t)
+void remd_custom_hbond_dpar(remd_ctx* h, cst_tables& t, bool states)
 {
     const int waves = t.total_pad / 64, w0 = t.begin(CST_HBOND);
-    hipLaunchKernelGGL(custom_hbond_dpar_kernel, dim3(t.end(CST_HBOND) - w0, h->R), dim3(64), 0, h->stream, w0, waves, t.d_F, t.d_wave_force, t.d_hb_atoms,
-                       t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, (int)t.dcols.size(), t.d_dcols, t.d_dmask, t.d_excl_off, t.d_excl_atoms, h->d_labels,
-                       h->r_begin, h->Npad, h->d_pos, h->d_box, t.d_dD);
+    const dim3 grid(t.end(CST_HBOND) - w0, h->R);
+    if (states)
+        hipLaunchKernelGGL(custom_hbond_dpar_kernel<true>, grid, dim3(64), 0, h->stream, w0, waves, t.d_F, t.d_wave_force, t.d_hb_atoms,
+                           t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, (int)t.dcols.size(), t.d_dcols, t.d_dmask, t.d_excl_off, t.d_excl_atoms, h->d_labels,
+                           h->r_begin, h->Npad, h->d_pos, h->d_box, t.d_dDK, h->K);
+    else
+        hipLaunchKernelGGL(custom_hbond_dpar_kernel<false>, grid, dim3(64), 0, h->stream, w0, waves, t.d_F, t.d_wave_force, t.d_hb_atoms,
+                           t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, (int)t.dcols.size(), t.d_dcols, t.d_dmask, t.d_excl_off, t.d_excl_atoms, h->d_labels,
+                           h->r_begin, h->Npad, h->d_pos, h->d_box, t.d_dD, 1);
 }

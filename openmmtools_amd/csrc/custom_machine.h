@@ -35,6 +35,8 @@ struct cst_tables : cst_plan {
     dev_array<int> d_dcols; dev_array<unsigned> d_dmask;   // the declared energy parameter derivatives (cst_plan::dcols, dmask); empty: none
     dev_array<double> d_dD;            // [R][n_derivatives][total_pad / 64] their partials; allocated by the first remd_get_custom_parameter_derivatives
     dev_array<double> d_dOut;          // [R][n_derivatives] dE/dglobal
+    dev_array<double> d_dDK;           // [R][K][n_derivatives][total_pad / 64] the same under every state's globals; allocated by the first
+    dev_array<double> d_dOutK;         // [R][K][n_derivatives]                 remd_get_custom_parameter_derivatives_at_states
     dev_array<double> d_C;             // [R][n_groups][3] centroids
     dev_array<double> d_G;             // [R][centroid slots][REMD_CUSTOM_MAX_PARTICLES][3] dE / d centroid
     dev_array<double> d_W;             // [R][n_cv][16]: RMSD, "no force" flag, centroid, rotation, dE/dRMSD (custom_cv.hip)
@@ -319,11 +321,13 @@ __device__ __forceinline__ double cst_wave_sum(double v)
 // launches of remd_custom_forces / remd_custom_ukl
 void remd_custom_compound_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
 void remd_custom_compound_ukl(remd_ctx* h, cst_tables& t);
-void remd_custom_compound_dpar(remd_ctx* h, cst_tables& t);     // (the *_dpar launches: D[r][d][w] of the declared energy parameter derivatives, on the main stream)
+// (the *_dpar launches: D[r][d][w] of the declared energy parameter derivatives -> d_dD, on the main stream; states: D[r][l][d][w]
+// under every state's globals -> d_dDK)
+void remd_custom_compound_dpar(remd_ctx* h, cst_tables& t, bool states);
 // custom_centroid.hip: the same for the centroid forces' wavefronts (the part CST_CENTROID): centroids, bonds, spread
 void remd_custom_centroid_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
 void remd_custom_centroid_ukl(remd_ctx* h, cst_tables& t);
-void remd_custom_centroid_dpar(remd_ctx* h, cst_tables& t);
+void remd_custom_centroid_dpar(remd_ctx* h, cst_tables& t, bool states);
 // custom_cv.hip: the same for the collective-variable forces' wavefronts (the part CST_CV): superposition, expression, spread
 void remd_custom_cv_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
 void remd_custom_cv_ukl(remd_ctx* h, cst_tables& t);
@@ -339,12 +343,12 @@ void remd_custom_nonbonded_lrc_ukl(remd_ctx* h, cst_tables& t, double* d_rows);
 // custom_hbond.hip: the same for the donor-acceptor forces' tiles (the part CST_HBOND)
 void remd_custom_hbond_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
 void remd_custom_hbond_ukl(remd_ctx* h, cst_tables& t);
-void remd_custom_hbond_dpar(remd_ctx* h, cst_tables& t);
+void remd_custom_hbond_dpar(remd_ctx* h, cst_tables& t, bool states);
 // custom_manyparticle.hip: the same for the many-particle forces' central particles (the part CST_MANYPARTICLE, the last one): the
 // neighbour rows, then the sets
 void remd_custom_manyparticle_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);
 void remd_custom_manyparticle_ukl(remd_ctx* h, cst_tables& t);
-void remd_custom_manyparticle_dpar(remd_ctx* h, cst_tables& t);
+void remd_custom_manyparticle_dpar(remd_ctx* h, cst_tables& t, bool states);
 // custom_gb.hip: the same for the Generalized-Born forces (the part CST_GB, the last one): five launches per force.  They carry no
 // globals, so they have no u_kl launch
 void remd_custom_gb_forces(remd_ctx* h, cst_tables& t, bool with_energy, hipStream_t st);

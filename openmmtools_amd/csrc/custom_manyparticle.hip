@@ -272,7 +272,10 @@ void custom_manyparticle_ukl_kernel(int w0, int waves, const cst_force* __restri
 }
 
 // energy parameter derivatives, same grid behind the same neighbour rows: D[r][d][w] = sum over the central particle's sets of
-// dE/dglobal(dcols[d]) under the replica's own globals; a row over capacity gives NaN in every column the force declared
+// dE/dglobal(dcols[d]) under the replica's own globals; a row over capacity gives NaN in every column the force declared.
+// STATES: under the globals of every state l in turn, D[r][l][d][w] (the NaN at every l); the row, the sets and each batch's staging
+// run once, the states loop inside a batch, so a (state, column)'s batches are added in the order of the own-state kernel
+template <bool STATES>
 __global__ __launch_bounds__(64)
 void custom_manyparticle_dpar_kernel(int w0, int waves, const cst_force* __restrict__ F, const int* __restrict__ wave_force, const int* __restrict__ types,
                                      const double* __restrict__ par, const int2* __restrict__ prog, const double* __restrict__ consts,
@@ -280,7 +283,7 @@ void custom_manyparticle_dpar_kernel(int w0, int waves, const cst_force* __restr
                                      const unsigned* __restrict__ dmask, const int* __restrict__ excl_off, const int* __restrict__ excl_atoms,
                                      const int64_t* __restrict__ labels, int r_begin, int Npad, const float4* __restrict__ pos,
                                      const float* __restrict__ box, int mp_rows, const int* __restrict__ nbr, const int* __restrict__ cnt,
-                                     double* __restrict__ D)
+                                     double* __restrict__ D, int K)
 {
     __shared__ cst_slot S[REMD_CUSTOM_MAX_STACK];
     __shared__ cst_pos X[3];
@@ -293,23 +296,27 @@ void custom_manyparticle_dpar_kernel(int w0, int waves, const cst_force* __restr
     const int i = w - f.slot0 / 64;
     const int n = mp_load_row(f, i, r, lane, mp_rows, nbr, cnt, row);
     const bool central = f.mp_mode == 0 || ((f.mp_filter[0] >> types[f.mp_types0 + i]) & 1u);
+    const int nl = STATES ? K : 1;
     if (lane == 0)
-        for (int d = 0; d < nd; ++d)
-            D[((size_t)r * nd + d) * waves + w] = central && n > MP_ROW && ((mask >> d) & 1u) ? __longlong_as_double(0x7ff8000000000000ll) : 0.0;
+        for (int l = 0; l < nl; ++l)
+            for (int d = 0; d < nd; ++d)
+                D[(((size_t)r * nl + l) * nd + d) * waves + w] = central && n > MP_ROW && ((mask >> d) & 1u) ? __longlong_as_double(0x7ff8000000000000ll) : 0.0;
     if (n < 2 || n > MP_ROW || !central || mask == 0u) return;     // (wave-uniform)
     cst_force fl = f; fl.par0 = 0; fl.npad = 64;
     const bool pbc = f.periodic != 0;
     const double bx = box[4 * r], by = box[4 * r + 1], bz = box[4 * r + 2];
     const double Lx = pbc ? bx : 0.0, Ly = pbc ? by : 0.0, Lz = pbc ? bz : 0.0;
-    const double* g = glob + (size_t)labels[r_begin + r] * ng;
     const float4* P = pos + (size_t)r * Npad;
     mp_sets(f, i, n, lane, pbc, bx, by, bz, P, types, excl_off, excl_atoms, row, queue, [&](int entry, bool on) {
         mp_stage(f, i, entry, row, lane, P, par, Npad, X, PAR);
-        for (int d = 0; d < nd; ++d) {
-            if (!((mask >> d) & 1u)) continue;
-            const cx e = cst_eval<true, true>(fl, prog, consts, &PAR[0][0], lane, g, 0.0, 0.0, 0.0, Lx, Ly, Lz, S, lane, X, -1, dcols[d]);
-            const double v = cst_wave_sum(on ? e.a : 0.0);
-            if (lane == 0) D[((size_t)r * nd + d) * waves + w] += v;
+        for (int l = 0; l < nl; ++l) {
+            const double* g = glob + (size_t)(STATES ? l : labels[r_begin + r]) * ng;
+            for (int d = 0; d < nd; ++d) {
+                if (!((mask >> d) & 1u)) continue;
+                const cx e = cst_eval<true, true>(fl, prog, consts, &PAR[0][0], lane, g, 0.0, 0.0, 0.0, Lx, Ly, Lz, S, lane, X, -1, dcols[d]);
+                const double v = cst_wave_sum(on ? e.a : 0.0);
+                if (lane == 0) D[(((size_t)r * nl + l) * nd + d) * waves + w] += v;
+            }
         }
     });
 }
@@ -349,11 +356,17 @@ void remd_custom_manyparticle_ukl(remd_ctx* h, cst_tables& t)
 }
 
 // (the caller has sized the rows: ensure_buffers of custom_terms.hip)
-void remd_custom_manyparticle_dpar(remd_ctx* h, cst_tables& t)
+void remd_custom_manyparticle_dpar(remd_ctx* h, cst_tables& t, bool states)
 {
     const int waves = t.total_pad / 64, w0 = t.begin(CST_MANYPARTICLE);
     mp_neighbours(h, t, h->stream);
-    hipLaunchKernelGGL(custom_manyparticle_dpar_kernel, dim3(t.end(CST_MANYPARTICLE) - w0, h->R), dim3(64), 0, h->stream, w0, waves, t.d_F, t.d_wave_force,
-                       t.d_mp_types, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, (int)t.dcols.size(), t.d_dcols, t.d_dmask, t.d_excl_off, t.d_excl_atoms,
-                       h->d_labels, h->r_begin, h->Npad, h->d_pos, h->d_box, t.mp_rows, t.d_mp_nbr, t.d_mp_cnt, t.d_dD);
+    const dim3 grid(t.end(CST_MANYPARTICLE) - w0, h->R);
+    if (states)
+        hipLaunchKernelGGL(custom_manyparticle_dpar_kernel<true>, grid, dim3(64), 0, h->stream, w0, waves, t.d_F, t.d_wave_force,
+                           t.d_mp_types, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, (int)t.dcols.size(), t.d_dcols, t.d_dmask, t.d_excl_off, t.d_excl_atoms,
+                           h->d_labels, h->r_begin, h->Npad, h->d_pos, h->d_box, t.mp_rows, t.d_mp_nbr, t.d_mp_cnt, t.d_dDK, h->K);
+    else
+        hipLaunchKernelGGL(custom_manyparticle_dpar_kernel<false>, grid, dim3(64), 0, h->stream, w0, waves, t.d_F, t.d_wave_force,
+                           t.d_mp_types, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, (int)t.dcols.size(), t.d_dcols, t.d_dmask, t.d_excl_off, t.d_excl_atoms,
+                           h->d_labels, h->r_begin, h->Npad, h->d_pos, h->d_box, t.mp_rows, t.d_mp_nbr, t.d_mp_cnt, t.d_dD, 1);
 }

@@ -192,13 +192,16 @@ void custom_ukl_reduce_kernel(int K, int waves, const double* __restrict__ D, co
 
 // energy parameter derivatives, grid (wavefronts of the four kinds' part, R): D[r][d][w] = sum over the wavefront's terms of
 // dE/dglobal(dcols[d]) under the replica's own globals, the machine seeded at that column (cst_eval<., true>); a force whose mask lacks
-// the column is skipped wave-uniformly and contributes exactly 0, and so do padding lanes
+// the column is skipped wave-uniformly and contributes exactly 0, and so do padding lanes.
+// STATES (remd_get_custom_parameter_derivatives_at_states): the same under the globals of every state l in turn, D[r][l][d][w]; the
+// geometry is computed once.  A compile-time switch: without it K is not read and the kernel is the code it was.
+template <bool STATES>
 __global__ __launch_bounds__(64)
 void custom_dpar_kernel(int total_pad, int waves, const cst_force* __restrict__ F, const int* __restrict__ wave_force, const int* __restrict__ atoms,
                         const double* __restrict__ par, const int2* __restrict__ prog, const double* __restrict__ consts,
                         const double* __restrict__ glob, int ng, int nd, const int* __restrict__ dcols, const unsigned* __restrict__ dmask,
                         const int64_t* __restrict__ labels, int r_begin, int Npad, const float4* __restrict__ pos,
-                        const float* __restrict__ box, double* __restrict__ D /*[R][nd][waves]*/)
+                        const float* __restrict__ box, double* __restrict__ D /*[R][nd][waves]; STATES: [R][K][nd][waves]*/, int K)
 {
     __shared__ cst_slot S[REMD_CUSTOM_MAX_STACK];
     const int w = blockIdx.x, r = blockIdx.y, lane = threadIdx.x;
@@ -207,21 +210,24 @@ void custom_dpar_kernel(int total_pad, int waves, const cst_force* __restrict__ 
     const int s = w * 64 + lane, t = s - f.slot0;
     const float4* P = pos + (size_t)r * Npad;
     const double Lx = box[4 * r], Ly = box[4 * r + 1], Lz = box[4 * r + 2];
-    const double* g = glob + (size_t)labels[r_begin + r] * ng;
     cst_geom o;
     cst_geometry(f, atoms, total_pad, s, P, Lx, Ly, Lz, o);
     const bool active = t < f.n_terms;
-    for (int d = 0; d < nd; ++d) {
-        double v = 0.0;
-        if ((mask >> d) & 1u) {
-            const cx e = cst_eval<false, true>(f, prog, consts, par, t, g, o.x0, o.x1, o.x2, Lx, Ly, Lz, S, lane, nullptr, -1, dcols[d]);
-            v = cst_wave_sum(active ? e.a : 0.0);
+    const int nl = STATES ? K : 1;
+    for (int l = 0; l < nl; ++l) {
+        const double* g = glob + (size_t)(STATES ? l : labels[r_begin + r]) * ng;
+        for (int d = 0; d < nd; ++d) {
+            double v = 0.0;
+            if ((mask >> d) & 1u) {
+                const cx e = cst_eval<false, true>(f, prog, consts, par, t, g, o.x0, o.x1, o.x2, Lx, Ly, Lz, S, lane, nullptr, -1, dcols[d]);
+                v = cst_wave_sum(active ? e.a : 0.0);
+            }
+            if (lane == 0) D[(((size_t)r * nl + l) * nd + d) * waves + w] = v;
         }
-        if (lane == 0) D[((size_t)r * nd + d) * waves + w] = v;
     }
 }
 
-// grid (nd, R), 64 threads: out[r][d] = sum_w D[r][d][w], in a fixed order
+// grid (nd, R), 64 threads: out[r][d] = sum_w D[r][d][w], in a fixed order (at every state: the rows are the R K pairs (r, l))
 __global__ __launch_bounds__(64)
 void custom_dpar_reduce_kernel(int nd, int waves, const double* __restrict__ D, double* __restrict__ out)
 {
@@ -273,7 +279,7 @@ int upload_tables(remd_ctx* h, cst_tables& t)
         (rc = t.d_map_off.upload(h, t.map_off)) || (rc = t.d_map_index.upload(h, t.map_index)) ||
         (rc = t.d_hb_atoms.upload(h, t.hb_atoms)) || (rc = t.d_mp_types.upload(h, t.mp_types)) ||
         (rc = t.d_gb_stages.upload(h, t.gb_stages)) || (rc = t.d_dcols.upload(h, t.dcols)) || (rc = t.d_dmask.upload(h, t.dmask))) return rc;
-    t.d_dD.reset(); t.d_dOut.reset();
+    t.d_dD.reset(); t.d_dOut.reset(); t.d_dDK.reset(); t.d_dOutK.reset();
     t.d_E.reset(); t.d_Ewave.reset(); t.d_D.reset(); t.d_C.reset(); t.d_G.reset(); t.d_W.reset(); t.d_mp_nbr.reset(); t.d_mp_cnt.reset(); t.d_gb_work.reset();
     return 0;
 }
@@ -401,29 +407,40 @@ static bool dpar_served(int kind)
 
 // dE/dglobal of the declared columns at the current positions and the replicas' own globals -> d_dOut [R][nd], on the main stream.
 // It runs whatever the states' globals are: a derivative does not vanish where every state carries the same ones.
-static int remd_custom_dpar(remd_ctx* h, cst_tables& t)
+// states: under every state's globals instead -> d_dOutK [R][K][nd], through partials of their own (d_dDK), so that the own-state
+// call's buffers are what they were.  The staging launches (centroids, neighbour rows) run once either way.
+static int remd_custom_dpar(remd_ctx* h, cst_tables& t, bool states)
 {
     REMD_TRY(check_current(h, t));
     REMD_TRY(ensure_buffers(h, t));                     // (the centroids and the neighbour rows of the staging launches)
     REMD_TRY(remd_vsites_place(h, h->stream));
     const int waves = t.total_pad / 64, nd = (int)t.dcols.size();
-    const size_t nD = (size_t)h->R * nd * waves;
-    if (t.d_dD.size() != nD) {
+    const size_t rows = (size_t)h->R * (states ? h->K : 1), nD = rows * nd * waves;
+    if (rows > 65535) return remd_fail(h, -1, "custom terms: more than 65535 (replica, state) pairs in one energy parameter derivative call");
+    dev_array<double>& dD = states ? t.d_dDK : t.d_dD;
+    dev_array<double>& dOut = states ? t.d_dOutK : t.d_dOut;
+    if (dD.size() != nD) {
         // (the wavefronts of the kinds that are not served are never written: zeroed here, once)
-        REMD_TRY(t.d_dD.alloc(h, nD));
-        REMD_CHECK(h, hipMemsetAsync(t.d_dD, 0, sizeof(double) * nD, h->stream));
+        REMD_TRY(dD.alloc(h, nD));
+        REMD_CHECK(h, hipMemsetAsync(dD, 0, sizeof(double) * nD, h->stream));
     }
-    if (t.d_dOut.size() != (size_t)h->R * nd) REMD_TRY(t.d_dOut.alloc(h, (size_t)h->R * nd));
-    remd_prof_scope ps(h, "custom_dpar");
-    if (t.has(CST_SIMPLE))
-        hipLaunchKernelGGL(custom_dpar_kernel, dim3(t.end(CST_SIMPLE), h->R), dim3(64), 0, h->stream, t.total_pad, waves, t.d_F, t.d_wave_force,
-                           t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, nd, t.d_dcols, t.d_dmask, h->d_labels, h->r_begin, h->Npad,
-                           h->d_pos, h->d_box, t.d_dD);
-    if (t.has(CST_COMPOUND)) remd_custom_compound_dpar(h, t);
-    if (t.has(CST_CENTROID)) remd_custom_centroid_dpar(h, t);
-    if (t.has(CST_HBOND)) remd_custom_hbond_dpar(h, t);
-    if (t.has(CST_MANYPARTICLE)) remd_custom_manyparticle_dpar(h, t);
-    hipLaunchKernelGGL(custom_dpar_reduce_kernel, dim3(nd, h->R), dim3(64), 0, h->stream, nd, waves, t.d_dD, t.d_dOut);
+    if (dOut.size() != rows * nd) REMD_TRY(dOut.alloc(h, rows * nd));
+    remd_prof_scope ps(h, states ? "custom_dpar_states" : "custom_dpar");
+    if (t.has(CST_SIMPLE)) {
+        if (states)
+            hipLaunchKernelGGL(custom_dpar_kernel<true>, dim3(t.end(CST_SIMPLE), h->R), dim3(64), 0, h->stream, t.total_pad, waves, t.d_F, t.d_wave_force,
+                               t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, nd, t.d_dcols, t.d_dmask, h->d_labels, h->r_begin, h->Npad,
+                               h->d_pos, h->d_box, dD, h->K);
+        else
+            hipLaunchKernelGGL(custom_dpar_kernel<false>, dim3(t.end(CST_SIMPLE), h->R), dim3(64), 0, h->stream, t.total_pad, waves, t.d_F, t.d_wave_force,
+                               t.d_atoms, t.d_par, t.d_prog, t.d_consts, t.d_glob, t.ng, nd, t.d_dcols, t.d_dmask, h->d_labels, h->r_begin, h->Npad,
+                               h->d_pos, h->d_box, dD, 1);
+    }
+    if (t.has(CST_COMPOUND)) remd_custom_compound_dpar(h, t, states);
+    if (t.has(CST_CENTROID)) remd_custom_centroid_dpar(h, t, states);
+    if (t.has(CST_HBOND)) remd_custom_hbond_dpar(h, t, states);
+    if (t.has(CST_MANYPARTICLE)) remd_custom_manyparticle_dpar(h, t, states);
+    hipLaunchKernelGGL(custom_dpar_reduce_kernel, dim3(nd, (unsigned)rows), dim3(64), 0, h->stream, nd, waves, dD, dOut);
     REMD_CHECK(h, hipGetLastError());
     return 0;
 }
@@ -452,7 +469,7 @@ int remd_set_custom_parameter_derivatives(remd_handle h, const int32_t* columns,
     if (h->stream2) hipStreamSynchronize(h->stream2);
     t->dcols.assign(columns, columns + n);
     if (n > 0) t->dmask.assign(force_masks, force_masks + t->nf); else t->dmask.clear();
-    t->d_dD.reset(); t->d_dOut.reset();
+    t->d_dD.reset(); t->d_dOut.reset(); t->d_dDK.reset(); t->d_dOutK.reset();
     int rc;
     if ((rc = t->d_dcols.upload(h, t->dcols)) || (rc = t->d_dmask.upload(h, t->dmask))) return rc;
     h->config_version++;
@@ -466,8 +483,23 @@ int remd_get_custom_parameter_derivatives(remd_handle h, double* out)
     if (!t || h->n_custom == 0 || t->dcols.empty())
         return remd_fail(h, -1, "remd_get_custom_parameter_derivatives: no energy parameter derivative declared (remd_set_custom_parameter_derivatives)");
     hipSetDevice(h->device);
-    int rc = remd_custom_dpar(h, *t); if (rc) return rc;
+    int rc = remd_custom_dpar(h, *t, false); if (rc) return rc;
     REMD_CHECK(h, hipMemcpyAsync(out, t->d_dOut, sizeof(double) * (size_t)h->R * t->dcols.size(), hipMemcpyDeviceToHost, h->stream));
+    REMD_CHECK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int remd_get_custom_parameter_derivatives_at_states(remd_handle h, double* out)
+{
+    if (!h || !out) return remd_fail(h, -1, "remd_get_custom_parameter_derivatives_at_states: bad arguments");
+    if (h->R <= 0) return remd_fail(h, -1, "remd_get_custom_parameter_derivatives_at_states: no replicas (remd_set_replicas)");
+    cst_tables* t = h->cst.get();
+    if (!t || h->n_custom == 0 || t->dcols.empty())
+        return remd_fail(h, -1, "remd_get_custom_parameter_derivatives_at_states: no energy parameter derivative declared (remd_set_custom_parameter_derivatives)");
+    if (h->K <= 0) return remd_fail(h, -1, "remd_get_custom_parameter_derivatives_at_states: no states (remd_set_states, then remd_set_custom_globals)");
+    hipSetDevice(h->device);
+    int rc = remd_custom_dpar(h, *t, true); if (rc) return rc;
+    REMD_CHECK(h, hipMemcpyAsync(out, t->d_dOutK, sizeof(double) * (size_t)h->R * h->K * t->dcols.size(), hipMemcpyDeviceToHost, h->stream));
     REMD_CHECK(h, hipStreamSynchronize(h->stream));
     return 0;
 }

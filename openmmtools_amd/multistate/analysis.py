@@ -1495,6 +1495,7 @@ class MultiStateSamplerAnalyzer:
         # who evaluates collective variables at the stored frames: 'numpy' (frame_cvs_numpy, no GPU) or 'device' (csrc/frame_cvs.hip)
         self._check_cv_solver(self._kwargs.get('cv_solver', 'numpy'))
         self._collective_variables = {}         # {descriptor keys: [n_iterations + 1][n_replicas][n_cv]}, kept until clear()
+        self._parameter_derivatives = None      # (names, reduced [n_iterations + 1][n_replicas][n_states][n]), kept until clear()
         # bootstrap uncertainties of MBAR: the number of replicates (0: none), the key of their draws, and the uncertainty the free
         # energies are reported with (None or 'svd': asymptotic; 'bootstrap')
         self._check_bootstrap_option('n_bootstraps', self._kwargs.get('n_bootstraps', 0))
@@ -1626,6 +1627,7 @@ class MultiStateSamplerAnalyzer:
         self._radially_symmetric_restraint_data = None
         self._restraint_energies, self._restraint_distances = {}, {}
         self._collective_variables = {}
+        self._parameter_derivatives = None
         self._release_energy_store()
 
     def _release_energy_store(self):
@@ -2121,6 +2123,120 @@ class MultiStateSamplerAnalyzer:
         r = mbar.compute_pmf(u_n, bin_n, nbins, uncertainties=uncertainties, pmf_reference=pmf_reference,
                              uncertainty_method=self.uncertainty_method)
         return r['f_i'], r['df_i'], r['n_i']
+
+    # ---- thermodynamic integration over the stored energy parameter derivatives ----------------------------------------------
+    def get_parameter_derivatives(self):
+        """(names, dudl): the global parameters whose derivatives the store holds (a run with ``store_parameter_derivatives=True``)
+        and dudl [n_iterations + 1][n_replicas][n_states][n], the REDUCED derivative beta_l dE/dparameter_d (no units, per unit of
+        the parameter) of every replica's configuration under the globals of every sampled state l.  Kept until ``clear()``."""
+        if self._parameter_derivatives is None:
+            from .. import constants
+            names = list(self._reporter.read_parameter_derivative_names())
+            d = np.asarray(self._reporter.read_parameter_derivatives(), dtype=np.float64)[:self.n_iterations + 1]
+            beta = np.array([1.0 / (constants.kB * float(s.temperature)) for s in self._reporter.read_thermodynamic_states()[0]])
+            self._parameter_derivatives = (names, d * beta[None, None, :, None])
+        names, dudl = self._parameter_derivatives
+        return list(names), dudl.copy()
+
+    @staticmethod
+    def _state_parameters(state):
+        """{name: value} of everything the composable states of ``state`` control (global parameters, alchemical lambdas)"""
+        from ..states import AlchemicalState
+        out = {}
+        for g in getattr(state, '_globals', ()):
+            for name in g._parameters:
+                out[name] = g._get_global_parameter_value(name)
+        for c in getattr(state, '_alchs', ()):
+            sfx = c.parameters_name_suffix
+            for p in AlchemicalState._PARAMETERS:
+                out[p if sfx is None else p + '_' + sfx] = getattr(c, p)
+        return out
+
+    def get_thermodynamic_integration(self, estimator='mbar'):
+        """Thermodynamic integration along the sampled states in index order: a dict with ``names`` [n] (the declared parameters),
+        ``lambdas`` [K][n] (their values at every state), ``mean`` and ``sigma`` [K][n] (<du/dlambda_d> at state k, reduced, and its
+        uncertainty), ``Delta_f`` and ``dDelta_f`` [K][K] in kT, the trapezoid rule over the path
+
+            Delta_f[i][j] = sum_{k=i}^{j-1} 1/2 sum_d (mean[k][d] + mean[k+1][d]) (lambda[k+1][d] - lambda[k][d])       (antisymmetric)
+
+        an estimate of ``get_free_energy()`` that does not share MBAR's route to it.  Both estimators work on the columns handed to
+        MBAR (the same equilibration cut and decorrelated iterations): ``'samples'`` averages du/dlambda at state k over the samples
+        drawn AT state k; ``'mbar'`` takes <du/dlambda>_k from all samples, reweighted (``mbar.compute_expectations(...,
+        state_dependent=True)``, so with the analyzer's MBAR solver).
+
+        Uncertainty: for a pair (i, j) every state k on the path carries ONE observable B_k = sum_d w_kd du/dlambda_d with its
+        trapezoid weight w_kd (half the adjacent step at the ends, half the sum of both inside), and dDelta_f[i][j]^2 = sum_k
+        sigma^2(B_k), sigma the standard error of the mean ('samples'; NaN for a state with fewer than two samples) or
+        compute_expectations' sigma ('mbar').  The states are treated as independent (alchemlyb's convention for TI): for 'mbar'
+        this NEGLECTS the correlation between the states' estimates, which all come from the same samples.
+
+        ValueError: fewer than two states; states that differ in temperature, pressure or in any parameter that is not one of the
+        stored derivative columns (a built-in alchemical lambda, a global no force declared) -- the integrand along that
+        parameter is not in the store."""
+        if estimator not in ('mbar', 'samples'):
+            raise ValueError("estimator must be 'mbar' or 'samples', not %r" % (estimator,))
+        names, dudl = self.get_parameter_derivatives()
+        states = self._reporter.read_thermodynamic_states()[0]
+        K, n = len(states), len(names)
+        if K < 2:
+            raise ValueError('thermodynamic integration needs at least 2 states, the store holds %d' % K)
+        for what in ('temperature', 'pressure'):
+            values = [getattr(s, what) for s in states]
+            if any(v != values[0] for v in values):
+                raise ValueError('thermodynamic integration over states that differ in %s (%s): the stored derivatives cover the '
+                                 'declared parameters %s only' % (what, values, names))
+        parameters = [self._state_parameters(s) for s in states]
+        for p in sorted(set().union(*parameters)):
+            values = [q.get(p) for q in parameters]
+            if p not in names and any(v != values[0] for v in values):
+                raise ValueError('thermodynamic integration: the states differ in %s (%s), which is not one of the stored energy parameter '
+                                 'derivatives %s (addEnergyParameterDerivative on a custom force that carries it)' % (p, values, names))
+        from ..custom_expr import custom_globals
+        lambdas = custom_globals(states[0].system, names, states)                 # [K][n]
+        step = np.diff(lambdas, axis=0)                                            # [K - 1][n]
+        # the trapezoid weights of state k: what it takes from the step on its left, on its right, and from both
+        left, right = np.zeros((K, n)), np.zeros((K, n))
+        left[1:], right[:-1] = 0.5 * step, 0.5 * step
+        mbar = self.mbar
+        iterations, keep = self._sample_columns
+        first = int((mbar.K - K) / 2)
+        A = np.swapaxes(dudl[iterations], 0, 1).reshape(-1, K, n)                 # [replica][iteration] -> column, as in get_pmf
+        if keep is not None:
+            A = A[keep]
+        A = np.ascontiguousarray(np.moveaxis(A, 0, -1))                           # [K][n][N]
+        B = [np.einsum('kd,kdn->kn', w, A) for w in (left, right, left + right)]   # [3][K][N]
+        mean, sigma, sB = np.zeros((K, n)), np.zeros((K, n)), np.zeros((3, K))
+        if estimator == 'mbar':
+            def expectation(a_kn):
+                rows = np.zeros((mbar.K, a_kn.shape[1]))
+                rows[first:first + K] = a_kn
+                r = mbar.compute_expectations(rows, state_dependent=True)
+                return r['mu'][first:first + K], r['sigma'][first:first + K]
+            for d in range(n):
+                mean[:, d], sigma[:, d] = expectation(A[:, d, :])
+            for c in range(3):
+                sB[c] = expectation(B[c])[1]
+        else:
+            def sem(x):              # standard error of the mean over the last axis; a constant observable has exactly 0, as in MBAR
+                m = x.shape[-1]
+                if m < 2:
+                    return np.full(x.shape[:-1], np.nan)
+                return np.where(x.max(axis=-1) == x.min(axis=-1), 0.0, np.std(x, axis=-1, ddof=1) / np.sqrt(m))
+            drawn = np.asarray(self._sample_states) - first
+            for k in range(K):
+                at = np.flatnonzero(drawn == k)
+                if at.size == 0:
+                    raise ValueError("estimator='samples': no sample was drawn at state %d" % k)
+                mean[k], sigma[k] = A[k][:, at].mean(axis=1), sem(A[k][:, at])
+                sB[:, k] = [sem(B[c][k, at]) for c in range(3)]
+        seg = 0.5 * np.sum((mean[:-1] + mean[1:]) * step, axis=1)                  # [K - 1]
+        Delta_f, dDelta_f = np.zeros((K, K)), np.zeros((K, K))
+        for i in range(K):
+            for j in range(i + 1, K):
+                Delta_f[i, j] = seg[i:j].sum()
+                Delta_f[j, i] = -Delta_f[i, j]
+                dDelta_f[i, j] = dDelta_f[j, i] = np.sqrt(sB[1, i] ** 2 + np.sum(sB[2, i + 1:j] ** 2) + sB[0, j] ** 2)
+        return dict(names=names, lambdas=lambdas, mean=mean, sigma=sigma, Delta_f=Delta_f, dDelta_f=dDelta_f)
 
 
 class ReplicaExchangeAnalyzer(MultiStateSamplerAnalyzer):

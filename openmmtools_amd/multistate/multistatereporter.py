@@ -243,7 +243,8 @@ class MultiStateReporter:
 
     _OWNED_NAMES = re.compile(
         r'^(meta\.json|last_iteration\.json(\.tmp)?|(thermodynamic_states|mcmc_moves|options|metadata)\.pkl|online_\w+_\d{9}\.pkl|'
-        r'(energies|unsampled_energies|timestamp|logZ|log_weights|f_k|f_k_offline|free_energy)\.f8|neighborhoods\.i1|'
+        r'(energies|unsampled_energies|timestamp|logZ|log_weights|f_k|f_k_offline|free_energy|parameter_derivatives)\.f8|neighborhoods\.i1|'
+        r'parameter_derivative_names\.json|'
         r'(states|accepted|proposed)\.i4|analysis_(positions|box_vectors)\.f4|iteration_\d{9}(\.tmp)?\.npz)$')
 
     @classmethod
@@ -296,6 +297,12 @@ class MultiStateReporter:
             # the box file exists only for a periodic store
             self._files['analysis_positions'] = _RecordFile(os.path.join(d, 'analysis_positions.f4'), 'f4', (R, n_analysis, 3))
             self._files['analysis_box_vectors'] = _RecordFile(os.path.join(d, 'analysis_box_vectors.f4'), 'f4', (R, 3, 3))
+        names = os.path.join(d, 'parameter_derivative_names.json')
+        if os.path.exists(names):
+            # energy parameter derivatives at every sampled state (a run with store_parameter_derivatives=True): the record kind exists
+            # only in a store that was given the column names
+            with open(names) as fh:
+                self._files['parameter_derivatives'] = _RecordFile(os.path.join(d, 'parameter_derivatives.f8'), 'f8', (R, K, len(json.load(fh))))
 
     def initialize(self, n_replicas, n_states, n_unsampled, n_atoms):
         """Dimensions of the record variables (the reference creates them lazily on first write)."""
@@ -371,6 +378,51 @@ class MultiStateReporter:
         self._files['energies'].write(iteration, energy_thermodynamic_states)
         self._files['neighborhoods'].write(iteration, energy_neighborhoods)
         self._files['unsampled_energies'].write(iteration, energy_unsampled_states)
+
+    # ---- energy parameter derivatives at every sampled state (thermodynamic integration; the record container only) ------------
+    _NO_DERIVATIVES = ('the store holds no energy parameter derivatives: run the simulation with store_parameter_derivatives=True '
+                       '(MultiStateSampler) on a System whose custom forces declare them (addEnergyParameterDerivative)')
+
+    def write_parameter_derivative_names(self, names):
+        """The columns of the derivative records (the declared global parameters), stored once, before the first record."""
+        self._require_write()
+        if self._ncw is not None:
+            raise ValueError('the netCDF4 layout holds no energy parameter derivatives (and no System with a custom force): use the record container')
+        names = [str(n) for n in names]
+        if 'parameter_derivatives' in self._files:
+            if names != self.read_parameter_derivative_names():
+                raise ValueError('the store holds the energy parameter derivatives %s, not %s' % (self.read_parameter_derivative_names(), names))
+            return
+        if self._meta is None:
+            raise IOError('initialize() the store before the names of its energy parameter derivatives')
+        with open(os.path.join(self._storage_analysis, 'parameter_derivative_names.json'), 'w') as fh:
+            json.dump(names, fh)
+        self._declare()
+
+    def read_parameter_derivative_names(self):
+        if self._ref is not None or 'parameter_derivatives' not in self._files:
+            raise ValueError(self._NO_DERIVATIVES)
+        with open(os.path.join(self._storage_analysis, 'parameter_derivative_names.json')) as fh:
+            return [str(n) for n in json.load(fh)]
+
+    def write_parameter_derivatives(self, derivatives, iteration):
+        """[R][K][n]: dE/dparameter (kJ/mol per unit of the parameter) of replica r's configuration under sampled state k's globals,
+        the columns of write_parameter_derivative_names; one record per iteration, like the energies."""
+        self._require_write()
+        if 'parameter_derivatives' not in self._files:
+            raise ValueError('write_parameter_derivative_names first: the store does not know the columns of the energy parameter derivatives')
+        f = self._files['parameter_derivatives']
+        if np.shape(derivatives) != f.shape:
+            raise ValueError('energy parameter derivatives of shape %s, the store holds [replicas][states][parameters] = %s'
+                             % (np.shape(derivatives), f.shape))
+        f.write(iteration, derivatives)
+
+    def read_parameter_derivatives(self, iteration=slice(None)):
+        """[iterations][R][K][n] f64 (one iteration: [R][K][n]); the iteration semantics of read_energies.  ValueError where the
+        store holds none."""
+        if self._ref is not None or 'parameter_derivatives' not in self._files:
+            raise ValueError(self._NO_DERIVATIVES)
+        return self._files['parameter_derivatives'].read(self._map_iteration_to_good(iteration)).astype(np.float64)
 
     def _calculate_checkpoint_iteration(self, iteration):
         """:1504-1515: the frame of ``iteration`` in the checkpoint store, None off the checkpoint interval."""
@@ -670,6 +722,10 @@ class MultiStateReporter:
         self.write_energies(sampler._energy_thermodynamic_states, sampler._neighborhoods,
                             sampler._energy_unsampled_states, it)                                   # :1220
         self.write_mixing_statistics(sampler._n_accepted_matrix, sampler._n_proposed_matrix, it)    # :1221
+        if getattr(sampler, 'store_parameter_derivatives', False):
+            if 'parameter_derivatives' not in self._files:
+                self.write_parameter_derivative_names(sampler._parameter_derivative_names)
+            self.write_parameter_derivatives(sampler._parameter_derivatives, it)
         online = sampler._online_data() if hasattr(sampler, '_online_data') else None
         if online:
             self.write_online_data_dynamic_and_static(it, **online)

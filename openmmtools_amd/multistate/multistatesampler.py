@@ -45,7 +45,8 @@ def restraint_lambdas(system, parameters, states):
 class MultiStateSampler:
     def __init__(self, mcmc_moves=None, number_of_iterations=1, locality=None,
                  online_analysis_interval=200, online_analysis_target_error=0.0,
-                 online_analysis_minimum_iterations=200, engine=None, seed=0xC0FFEE, comm=None, online_analysis_solver='numpy'):
+                 online_analysis_minimum_iterations=200, engine=None, seed=0xC0FFEE, comm=None, online_analysis_solver='numpy',
+                 store_parameter_derivatives=False):
         if locality is not None and ((type(locality) != int) or (locality <= 0)):      # :504-508
             raise ValueError('locality must be an int > 0')
         # multistatesampler.py:478-501
@@ -74,6 +75,11 @@ class MultiStateSampler:
         self.online_analysis_target_error = online_analysis_target_error
         self.online_analysis_minimum_iterations = online_analysis_minimum_iterations
         self.online_analysis_solver = online_analysis_solver      # analysis.MBAR's solver for the offline estimate inside the run loop
+        # thermodynamic integration: dE/dparameter of the declared energy parameter derivatives at every sampled state's globals,
+        # computed behind every energy evaluation and stored per iteration (MultiStateReporter.write_parameter_derivatives)
+        self.store_parameter_derivatives = bool(store_parameter_derivatives)
+        self._parameter_derivatives = None        # [R][K][n] kJ/mol per unit of the parameter
+        self._parameter_derivative_names = None
         self._last_mbar_f_k = None                # :246-247
         self._last_err_free_energy = None
         self._engine = engine
@@ -354,6 +360,8 @@ class MultiStateSampler:
                       online_analysis_minimum_iterations=self.online_analysis_minimum_iterations)
         if self.online_analysis_solver != 'numpy':                # stored only off its default: stores written before the option read and write unchanged
             kwargs['online_analysis_solver'] = self.online_analysis_solver
+        if self.store_parameter_derivatives:                      # (the same rule)
+            kwargs['store_parameter_derivatives'] = True
         kwargs.update(self._ctor_kwargs())
         return dict(cls=type(self).__name__, module=type(self).__module__, number_of_iterations=self.number_of_iterations,
                     seed=self._seed, kwargs=kwargs)
@@ -411,6 +419,8 @@ class MultiStateSampler:
         s._n_accepted_matrix[:, :] = acc
         s._n_proposed_matrix[:, :] = prop
         s._restore_online(rep.read_online_data_if_present(it))
+        if s.store_parameter_derivatives:
+            s._parameter_derivatives = np.array(rep.read_parameter_derivatives(it), dtype=np.float64)
         if s.online_analysis_interval is not None:                              # :991-995
             last_f_k, last_free_energy = cls._read_last_free_energy(rep, it)
             if last_f_k is not None:
@@ -664,6 +674,16 @@ class MultiStateSampler:
         if len(barostats) > 1:
             raise ValueError('the thermodynamic states carry different barostats: %s' % sorted(barostats, key=repr))
         groups, group_indices = group_by_compatibility(all_states)
+        if self.store_parameter_derivatives:
+            from ._engine_pool import EnginePool
+            if len(groups) > 1 or isinstance(self._engine, EnginePool):
+                raise NotImplementedError('store_parameter_derivatives: several compatibility groups (an EnginePool) are not served: the '
+                                          'derivatives at every state need one engine that holds every state\'s globals')
+            if self._comm.world_size > 1:
+                raise NotImplementedError('store_parameter_derivatives: more than one rank is not served (the derivatives are not gathered)')
+            if not hasattr(self._engine, 'custom_energy_parameter_derivatives_at_states'):
+                raise NotImplementedError('store_parameter_derivatives: %s has no custom_energy_parameter_derivatives_at_states (the energy '
+                                          'parameter derivatives of custom forces are computed by the GPU engine only)' % type(self._engine).__name__)
         if len(groups) > 1:
             if any(getattr(g[0].system, 'alchemical_region', None) is not None or getattr(g[0].system, 'alchemical_regions', None) is not None for g in groups):
                 raise NotImplementedError('alchemical states in more than one compatibility group')
@@ -741,6 +761,14 @@ class MultiStateSampler:
             box = np.zeros((self._r_count, 3))
         eng.set_replicas(R, self._r_begin, x, v, box, self._replica_thermodynamic_states)
         self._K_total = len(all_states)
+        if self.store_parameter_derivatives:
+            names = list(getattr(eng, 'custom_derivative_names', None) or [])
+            if not names:
+                raise ValueError('store_parameter_derivatives: no custom force of the System declares an energy parameter derivative '
+                                 '(addEnergyParameterDerivative)')
+            self._parameter_derivative_names = names
+            if self._parameter_derivatives is None:
+                self._parameter_derivatives = np.zeros([R, self.n_states, len(names)], np.float64)
 
     # ---- run / equilibrate ------------------------------------------------------------------
     @with_timer('Minimizing all replicas')
@@ -1151,6 +1179,9 @@ class MultiStateSampler:
         else:
             full = self._gather_rows()
         full = np.asarray(full)
+        if self.store_parameter_derivatives:
+            # at the positions the energies belong to; the engine answers for the unsampled states too, the store keeps the sampled ones
+            self._parameter_derivatives[:, :, :] = self._engine.custom_energy_parameter_derivatives_at_states()[:, :K, :]
         if U:
             self._energy_unsampled_states[:, :] = full[:, K:]
         if self.locality is None:
